@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: ACT policy steps/sec on synthetic 4-camera 480x640 batches (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--mode infer|train|eval-shard]
+  python bench.py --gpus N --steps K --warmup W [--mode infer|train|eval-shard] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints the result line (metric, value, unit, ms_per_step, dtype, ...);
+everything else listed below is measured only with --full.  --dump-outputs DIR writes what the last timed step returned to
+its caller as DIR/<name>.npy (float32 / float64; inputs and weights are seeded, so two builds can be compared output for output).
 
 N > 1: either launched by  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...  (WORLD_SIZE set:
 this process is one rank), or started plainly as  python bench.py --gpus N  -- then this process is only a LAUNCHER: it
@@ -14,7 +18,7 @@ random-init of the reference architecture (no network for checkpoints), inputs s
 independent of the values.  N > 1 runs N independent replicas on disjoint batches (episodes shard embarrassingly;
 the path has no data-path collective) and reports the whole-job aggregate with max-over-ranks timing.
 
-Rank 0 prints ONE JSON line with the driver's contract plus:
+Rank 0 prints ONE JSON line with the driver's contract plus, with --full:
   roofline     dominant kernel (the instantiation with the largest total time): achieved = algorithmic FLOPs of its
                launches / their summed duration, measured with HIP events on the launch stream; peak = the dense MFMA
                peak of the arithmetic the kernel uses (see kernel_peak); traffic = fabric bytes per launch from the PMC
@@ -75,6 +79,25 @@ def kernel_peak(name):
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as <dirname>/<name>.npy, float64 where the path returns float64, else float32.  An array
+    larger than its even share of DUMP_LIMIT_BYTES is stored as a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {dirname}: {', '.join(sorted(arrays))}")
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -154,17 +177,24 @@ def main():
                     help="(default) replay the step as ONE captured hipGraph; per-kernel events then come from extra eager "
                          "steps after the timed region, since events cannot bracket kernels inside a graph")
     ap.add_argument("--no-graph", dest="graph", action="store_false", help="launch the step's kernels eagerly")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel table and roofline, sustained leg, step latency, with_h2d, ranks_seen, "
+                         "sub-records of the other configurations and the CPU baseline (the options below refine it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--no-extras", action="store_true", help="skip the b1 / b50 / native_fp32 / train_b64 sub-records")
     ap.add_argument("--sustained-s", type=float, default=10.0, help="length of the sustained leg in seconds (0 = skip)")
     ap.add_argument("--shapes", action="store_true",
-                    help="per-shape GEMM table (M,N,K,groups,split,workgroups,us,TFLOP/s per distinct launch) in 'shapes'")
+                    help="--full: per-shape GEMM table (M,N,K,groups,split,workgroups,us,TFLOP/s per distinct launch) in 'shapes'")
     ap.add_argument("--train-prec", choices=["f16x3", "bf16"], default=None,
                     help="--mode train: arithmetic of the step's GEMMs (default f16x3 = fp32-grade; bf16 = BASELINE config 3 as written)")
     ap.add_argument("--episodes-per-gpu", type=int, default=50, help="eval-shard: episodes per rank (config 5: 50)")
     ap.add_argument("--episode-len", type=int, default=None, help="eval-shard: timesteps per episode (task default 400)")
     args = ap.parse_args()
+    if args.shapes and not args.full:
+        ap.error("--shapes is part of the --full run")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -385,17 +415,21 @@ def bench_infer(args, cfg, B, ctx):
         rig.step()
     barrier()
     log("warm-up done")
-    L.profile_enable(not rig.graphed)
+    L.profile_enable(args.full and not rig.graphed)      # --full eager: the timed steps carry the per-kernel events themselves
     t0 = time.perf_counter()
     for _ in range(args.steps):
         rig.step()
     barrier()
     elapsed = time.perf_counter() - t0
-    if rig.graphed:                    # per-kernel timing leg: the same number of steps, eager, outside the timed region
-        prof = profile_eager(rig, args.steps)
-    else:
-        L.profile_enable(False)
-        prof = L.profile_report()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"a_hat": rig.output(), "raw_action": rig.ens.out})
+    prof = None
+    if args.full:
+        if rig.graphed:                # per-kernel timing leg: the same number of steps, eager, outside the timed region
+            prof = profile_eager(rig, args.steps)
+        else:
+            L.profile_enable(False)
+            prof = L.profile_report()
     log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms/step")
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -403,6 +437,27 @@ def bench_infer(args, cfg, B, ctx):
         elapsed = float(tt.item())
     assert torch.isfinite(rig.output()).all()
     rig.eng.check_flags()              # default-on range guard of the f16x3 arithmetic (reads the device flag word)
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * B * args.steps / elapsed
+    prec = os.environ.get("ACTMI_GEMM_PREC", "f16x3")
+    from actmi.buildinfo import kernel_source_sha16
+    live_sha = kernel_source_sha16()
+    out = {
+        "metric": "policy steps/sec (4x480x640 cams, chunk=100, bs=8)",
+        "value": value, "unit": "policy steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": DTYPE["f32" if prec.startswith("f3") else "f16x3"], "data": "synthetic",
+        "arithmetic": ARITH["f32" if prec.startswith("f3") else "f16x3"],
+        "kernel_source_sha16": live_sha,
+        "config": {"workload": "ACT eval policy query: 4 cams 480x640 u8, chunk 100, hidden 512, ff 3200, "
+                               "4 enc + 7 dec layers (layer 0 live), per-GPU batch %d, + temporal ensemble" % B,
+                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"replicas x{world}",
+                   "launch": ("hipGraph replay" if rig.graphed else "eager") + LAUNCH_NOTE},
+    }
+    if not args.full:
+        rig.close()
+        return out if rank == 0 else None
+
     # which ranks took part: every rank's id through the eval path's own collective (all_gather_rows: RCCL when world > 1)
     from actmi import dist_utils
     ids = dist_utils.all_gather_rows(torch.full((1, 2), float(rank)), [1] * world)
@@ -425,15 +480,11 @@ def bench_infer(args, cfg, B, ctx):
 
     lat = latency(rig, max(10, min(200, args.steps)))
     h2d_dt = rig.timed(args.steps, 2, with_h2d=True)
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * B * args.steps / elapsed
     prof, kernels, gpu_ms = kernel_table(prof, args.steps)
     dom, ach = dominant(prof)
     peak, peak_is = kernel_peak(dom["name"])
     # fabric traffic per launch of the dominant kernel: measured in separate rocprofv3 --pmc passes (FETCH_SIZE x2 for the
     # gfx950 under-count, + WRITE_SIZE) of this same command and COMMITTED under profiles/ -- read from there, not produced here
-    from actmi.buildinfo import kernel_source_sha16
-    live_sha = kernel_source_sha16()
     traffic, traffic_source, traffic_commit, traffic_sha = None, None, None, None
     for f in TRAFFIC_FILES:
         try:
@@ -459,18 +510,7 @@ def bench_infer(args, cfg, B, ctx):
         runner_up = {"kernel": r2["name"], "achieved": a2, "frac": a2 / kernel_peak(r2["name"])[0], "share_of_dominant_time": r2["ms"] / dom["ms"],
                      "avg_launch_us": r2["ms"] * 1e3 / r2["count"], "launches_per_step": r2["count"] / args.steps,
                      "algorithmic_bytes_per_launch": r2["bytes"] / r2["count"], "traffic": t2}
-    prec = os.environ.get("ACTMI_GEMM_PREC", "f16x3")
-    out = {
-        "metric": "policy steps/sec (4x480x640 cams, chunk=100, bs=8)",
-        "value": value, "unit": "policy steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": DTYPE["f32" if prec.startswith("f3") else "f16x3"], "data": "synthetic",
-        "arithmetic": ARITH["f32" if prec.startswith("f3") else "f16x3"],
-        "kernel_source_sha16": live_sha,
-        "config": {"workload": "ACT eval policy query: 4 cams 480x640 u8, chunk 100, hidden 512, ff 3200, "
-                               "4 enc + 7 dec layers (layer 0 live), per-GPU batch %d, + temporal ensemble" % B,
-                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"replicas x{world}",
-                   "launch": ("hipGraph replay" if rig.graphed else "eager") + LAUNCH_NOTE},
+    out.update({
         "roofline": {"bound": "mfma", "kernel": dom["name"], "achieved": ach, "peak": peak, "unit": "TFLOP/s",
                      "measured": "per-launch HIP events on the launch stream, launches back to back on ONE stream (the profiled "
                                  "steps run the trunk as a single branch: events cannot bracket a launch that overlaps "
@@ -497,7 +537,7 @@ def bench_infer(args, cfg, B, ctx):
         "kernels": kernels,
         "step_latency_ms": lat,
         "ranks_seen": ranks_seen,
-    }
+    })
     if args.shapes:
         out["shapes"] = shape_table(prof, args.steps)
     rig.close()
@@ -693,13 +733,16 @@ def bench_train(args, cfg, B, ctx):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    # the kernel table comes from an untimed pass of its own: the in-library profiler brackets every launch with events (~4 % of the step)
-    L.profile_enable(True)
-    for i in range(args.steps):
-        step(args.warmup + args.steps + i)
-    torch.cuda.synchronize(dev)
-    L.profile_enable(False)
-    prof = L.profile_report()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if v is not None})
+    if args.full:
+        # the kernel table comes from an untimed pass of its own: the in-library profiler brackets every launch with events (~4 % of the step)
+        L.profile_enable(True)
+        for i in range(args.steps):
+            step(args.warmup + args.steps + i)
+        torch.cuda.synchronize(dev)
+        L.profile_enable(False)
+        prof = L.profile_report()
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -707,10 +750,8 @@ def bench_train(args, cfg, B, ctx):
     assert torch.isfinite(out["loss"]).all()
     if rank != 0:
         return None
-    prof, rows, gpu_ms = kernel_table(prof, args.steps)
-    dom, ach = dominant(prof)
     value = world * B * args.steps / elapsed
-    return {
+    res = {
         "metric": "ACT training samples/sec (fwd+bwd+AdamW, 4x480x640 cams, chunk=100)", "value": value,
         "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -719,6 +760,12 @@ def bench_train(args, cfg, B, ctx):
         "train_prec": args.train_prec or "f16x3",
         "config": {"workload": f"ACT training step, per-GPU batch {B}, 4 cams 480x640, hidden 512, ff 3200, dropout 0",
                    "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}" if world > 1 else "single"},
+    }
+    if not args.full:
+        return res
+    prof, rows, gpu_ms = kernel_table(prof, args.steps)
+    dom, ach = dominant(prof)
+    res.update({
         "roofline": {"bound": "mfma", "kernel": dom["name"], "achieved": ach, "peak": kernel_peak(dom["name"])[0],
                      "unit": "TFLOP/s", "frac": ach / kernel_peak(dom["name"])[0], "traffic": None,
                      "peak_is": kernel_peak(dom["name"])[1], "avg_launch_us": dom["ms"] * 1e3 / dom["count"]},
@@ -727,7 +774,8 @@ def bench_train(args, cfg, B, ctx):
                        "gpu_kernel_ms_per_step": gpu_ms / args.steps},
         "kernels": [{k: r[k] for k in ("name", "launches_per_step", "avg_us", "share", "tflops")}
                     for r in (rows if os.environ.get("ACTMI_PROF_SHAPES") == "1" else rows[:16])],
-    }
+    })
+    return res
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -738,6 +786,7 @@ def bench_eval_shard(args, ctx):
     (episode_return, highest_reward); value = policy steps/s over the whole job, rollout loop included (env stepping on
     host threads, u8 frames over PCIe every step, one D2H of the ensembled action per step)."""
     import tempfile
+    import numpy as np
     import torch
     import imitate_episodes as IE
     from actmi.constants import SIM_TASK_CONFIGS
@@ -769,9 +818,13 @@ def bench_eval_shard(args, ctx):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    # which ranks contributed: gather each rank's id through the same collective path the metrics used
-    ids = dist_utils.all_gather_rows(torch.full((1, 2), float(rank)), [1] * world)
-    ranks_seen = sorted(int(x) for x in ids[:, 0].tolist())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"success_rate": np.float64(sr), "avg_return": np.float64(avg_ret)})
+    ranks_seen = None
+    if args.full:
+        # which ranks contributed: gather each rank's id through the same collective path the metrics used
+        ids = dist_utils.all_gather_rows(torch.full((1, 2), float(rank)), [1] * world)
+        ranks_seen = sorted(int(x) for x in ids[:, 0].tolist())
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -788,8 +841,8 @@ def bench_eval_shard(args, ctx):
                                    "(episode_return, highest_reward)",
                        "episodes": n_total, "per_gpu_batch": n_local, "parallelism": f"episode shards x{world}",
                        "collective": "all_gather over RCCL" if world > 1 else "none (1 rank)"},
-            "ranks_seen": ranks_seen, "success_rate_synthetic_env": sr, "avg_return_synthetic_env": avg_ret,
-            "seconds": elapsed}
+            "success_rate_synthetic_env": sr, "avg_return_synthetic_env": avg_ret, "seconds": elapsed,
+            **({"ranks_seen": ranks_seen} if args.full else {})}
 
 
 def cpu_baseline(cfg, B, iters):

@@ -19,3 +19,11 @@ def pytest_configure(config):
 @pytest.fixture(scope="session")
 def golden_dir():
     return GOLDEN
+
+
+@pytest.fixture
+def host_only(monkeypatch):
+    """Hide the GPU from torch.cuda.is_available() for one test: eval_bc and dist_utils move to the GPU (and RCCL) whenever
+    one is visible, while the host-logic tests drive them with CPU test doubles."""
+    import torch
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)

@@ -26,3 +26,26 @@ def test_shape_table_and_peaks():
     assert abs(rows[0]["avg_us"] - 200.0) < 1e-9
     assert abs(bench.kernel_peak("gemm_f16x3_kernel<..>")[0] - 16 * 157.3 / 3) < 1e-9
     assert bench.kernel_peak("gemm_f32_kernel<..>")[0] == 157.3
+
+
+def test_shapes_is_part_of_the_full_run():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--shapes"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr and not r.stdout.strip()
+
+
+def test_dump_outputs_dtypes_and_seeded_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)           # three arrays: 1365 bytes each
+    arrays = {"a_hat": torch.arange(3000, dtype=torch.float32), "raw_action": torch.ones(4, dtype=torch.float64),
+              "loss": torch.tensor(0.5, dtype=torch.float16)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a = np.load(tmp_path / "a" / "a_hat.npy")
+    assert a.dtype == np.float32 and 0 < a.nbytes <= 4096 // 3 and np.all(np.diff(a) > 0)   # distinct elements, in order
+    assert np.array_equal(np.load(tmp_path / "b" / "a_hat.npy"), a)                          # the same sample every run
+    r = np.load(tmp_path / "a" / "raw_action.npy")
+    assert r.dtype == np.float64 and r.tolist() == [1.0] * 4
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and float(loss) == 0.5

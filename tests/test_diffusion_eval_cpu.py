@@ -88,6 +88,7 @@ def _diff_config(tmp, temporal_agg):
             "task_name": "sim_transfer_cube_scripted", "temporal_agg": temporal_agg}
 
 
+@pytest.mark.usefixtures("host_only")
 @pytest.mark.parametrize("temporal_agg", [False, True])
 def test_eval_bc_diffusion_branch(tmp_path, temporal_agg):
     stats = {"qpos_mean": np.zeros(S), "qpos_std": np.ones(S), "action_mean": np.zeros(A), "action_std": np.ones(A),

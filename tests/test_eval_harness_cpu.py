@@ -13,6 +13,8 @@ from actmi.envs import SyntheticEnv
 from actmi.sim_utils import draw_episode_poses, sample_box_pose, sample_insertion_pose, set_seed, shard_range
 from oracle.act_ref import TemporalEnsembleRef
 
+pytestmark = pytest.mark.usefixtures("host_only")
+
 Q, A, T, S = 4, 16, 12, 14
 CAMS = ["top", "left_wrist"]
 
@@ -101,6 +103,7 @@ def test_no_temporal_agg_queries_every_chunk(tmp_path):
 
 
 def _worker(rank, world, port, tmp, n):
+    torch.cuda.is_available = lambda: False        # the parent's host_only, in this spawned rank: gloo, CPU test doubles
     os.environ.update({"RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank),
                        "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port)})
     for p in (os.path.dirname(os.path.abspath(__file__)), ):

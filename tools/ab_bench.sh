@@ -11,7 +11,7 @@ while read -r line; do
   rest=$(echo "$line" | cut -d' ' -f2- -s)
   envs=$(echo "$rest" | sed 's/ -- .*//; s/^-- .*//')
   args=$(echo "$rest" | grep -o -- '-- .*' | sed 's/^-- //')
-  env $envs timeout -k 10 150 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras --sustained-s 0 $args > $O/${name}_$rep.json 2> $O/${name}_$rep.err || { echo "$name FAILED"; tail -3 $O/${name}_$rep.err; exit 1; }
+  env $envs timeout -k 10 150 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras --sustained-s 0 $args > $O/${name}_$rep.json 2> $O/${name}_$rep.err || { echo "$name FAILED"; tail -3 $O/${name}_$rep.err; exit 1; }
   python - "$O/${name}_$rep.json" "$name" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

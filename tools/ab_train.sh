@@ -8,7 +8,7 @@ while read -r line; do
   rest=$(echo "$line" | cut -d' ' -f2- -s)
   envs=$(echo "$rest" | sed 's/ -- .*//; s/^-- .*//')
   args=$(echo "$rest" | grep -o -- '-- .*' | sed 's/^-- //')
-  env $envs timeout -k 10 200 python bench.py --mode train --steps 5 --warmup 2 $args > $O/$name.json 2> $O/$name.err || { echo "$name FAILED"; tail -3 $O/$name.err; exit 1; }
+  env $envs timeout -k 10 200 python bench.py --full --mode train --steps 5 --warmup 2 $args > $O/$name.json 2> $O/$name.err || { echo "$name FAILED"; tail -3 $O/$name.err; exit 1; }
   python - "$O/$name.json" "$name" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

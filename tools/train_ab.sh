@@ -5,9 +5,9 @@ mkdir -p $O
 for cfg in "base" "ACTMI_ATTN_BWD_TILE=1" "ACTMI_ATTN_BWD_TILE=2" "$@"; do
   name=$(echo $cfg | tr '= ' '__')
   if [ "$cfg" = "base" ]; then
-    python3 $R/bench.py --mode train --batch 64 --steps 4 --warmup 1 --no-cpu-baseline --no-extras > $O/$name.json 2>/dev/null
+    python3 $R/bench.py --full --mode train --batch 64 --steps 4 --warmup 1 --no-cpu-baseline --no-extras > $O/$name.json 2>/dev/null
   else
-    env $cfg python3 $R/bench.py --mode train --batch 64 --steps 4 --warmup 1 --no-cpu-baseline --no-extras > $O/$name.json 2>/dev/null
+    env $cfg python3 $R/bench.py --full --mode train --batch 64 --steps 4 --warmup 1 --no-cpu-baseline --no-extras > $O/$name.json 2>/dev/null
   fi
   python3 -c "
 import json,sys
