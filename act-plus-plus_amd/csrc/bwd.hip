@@ -288,44 +288,6 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
     }
 }
 
-// P[g][q][k] = exp(S - lse[g][q]) (0 for masked / padded keys), in place; S was produced as scale * q.k
-__global__ void attn_probs_kernel(float* __restrict__ S, const float* __restrict__ lse, const uint8_t* __restrict__ kpm,
-                                  int64_t kpm_bs, int H, int Nq, int Nk, int ldp, int64_t total) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int k = (int)(idx % ldp);
-    const int64_t gq = idx / ldp;
-    const int64_t g = gq / Nq;
-    float v = 0.f;
-    if (k < Nk) {
-        const bool dead = kpm && kpm[(g / H) * kpm_bs + k] != 0;
-        if (!dead) v = expf(S[idx] - lse[gq]);
-    }
-    S[idx] = v;
-}
-
-// the same over 16-byte pieces of the rows (ldp % 4 == 0), 32-bit index arithmetic, bounded grid
-__global__ __launch_bounds__(256) void attn_probs_vec_kernel(f32x4* __restrict__ S, const float* __restrict__ lse,
-                                                             const uint8_t* __restrict__ kpm, int64_t kpm_bs, unsigned H, unsigned Nq,
-                                                             int Nk, unsigned ldp4, unsigned total4) {
-    const unsigned step = gridDim.x * 256u;
-    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total4; i += step) {
-        const unsigned gq = i / ldp4;
-        const int k0 = (int)(i - gq * ldp4) * 4;
-        const float l = lse[gq];
-        const f32x4 s = S[i];
-        const uint8_t* km = kpm ? kpm + (int64_t)(gq / Nq / H) * kpm_bs + k0 : nullptr;
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool live = k0 + e < Nk && !(km && km[e] != 0);
-            v[e] = live ? expf(s[e] - l) : 0.f;
-        }
-        S[i] = v;
-        if (i + step < i) break;
-    }
-}
-
 // x[r][c0 .. ld) = 0 for every row (the pad columns of the probability buffers)
 __global__ void zero_cols_kernel(float* __restrict__ x, int64_t rows, int ld, int c0) {
     const int w = ld - c0;
@@ -333,42 +295,6 @@ __global__ void zero_cols_kernel(float* __restrict__ x, int64_t rows, int ld, in
     if (i >= rows * w) return;
     const int64_t r = i / w;
     x[r * ld + c0 + (int)(i - r * w)] = 0.f;
-}
-
-// dS = P * (dP - delta[g][q]) * scale, in place of dP
-__global__ void attn_ds_kernel(const float* __restrict__ P, float* __restrict__ dP, const float* __restrict__ delta,
-                               float scale, int Nk, int ldp, int64_t total) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int k = (int)(idx % ldp);
-    const int64_t gq = idx / ldp;
-    dP[idx] = (k < Nk) ? P[idx] * (dP[idx] - delta[gq]) * scale : 0.f;
-}
-
-// the same over 16-byte pieces; amax_bits (optional) collects the bits of max |dS| (operand scale of the dQ / dK products)
-__global__ __launch_bounds__(256) void attn_ds_vec_kernel(const f32x4* __restrict__ P, f32x4* __restrict__ dP,
-                                                          const float* __restrict__ delta, float scale, int Nk, unsigned ldp4,
-                                                          unsigned total4, unsigned* __restrict__ amax_bits) {
-    const unsigned step = gridDim.x * 256u;
-    unsigned am = 0;
-    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total4; i += step) {
-        const unsigned gq = i / ldp4;
-        const int k0 = (int)(i - gq * ldp4) * 4;
-        const float dl = delta[gq];
-        const f32x4 pr = P[i], d = dP[i];
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[e] = (k0 + e < Nk) ? pr[e] * (d[e] - dl) * scale : 0.f;
-            am = max(am, __float_as_uint(v[e]) & 0x7fffffffu);
-        }
-        dP[i] = v;
-        if (i + step < i) break;
-    }
-    if (amax_bits) {
-        for (int o = 32; o > 0; o >>= 1) am = max(am, (unsigned)__shfl_xor((int)am, o, 64));
-        if ((threadIdx.x & 63) == 0 && am) amax_commit(amax_bits, am);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------- losses
@@ -749,48 +675,10 @@ int launch_attn_delta(const float* dO, const float* O, float* delta, int B, int 
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int launch_attn_probs(float* S, const float* lse, const uint8_t* kpm, int64_t kpm_bs, int G, int H, int Nq, int Nk, int ldp,
-                      hipStream_t st) {
-    const int64_t total = (int64_t)G * Nq * ldp;
-    if (total <= 0) return 0;
-    prof_begin("attn_probs_kernel", 0.0, 8.0 * total, st);
-    if ((ldp & 3) == 0 && ((uintptr_t)S & 15) == 0 && total / 4 < ((int64_t)1 << 32)) {
-        const unsigned t4 = (unsigned)(total / 4);
-        unsigned blocks = (t4 + 256u * 4u - 1) / (256u * 4u);
-        if (blocks > 16384) blocks = 16384;
-        hipLaunchKernelGGL(attn_probs_vec_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<f32x4*>(S), lse, kpm, kpm_bs,
-                           (unsigned)H, (unsigned)Nq, Nk, (unsigned)(ldp / 4), t4);
-    } else
-        hipLaunchKernelGGL(attn_probs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, lse, kpm, kpm_bs, H, Nq,
-                           Nk, ldp, total);
-    prof_end(st);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
 int launch_zero_cols(float* x, int64_t rows, int ld, int c0, hipStream_t st) {
     if (c0 >= ld || rows <= 0) return 0;
     const int64_t total = rows * (ld - c0);
     hipLaunchKernelGGL(zero_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, rows, ld, c0);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-int launch_attn_ds(const float* P, float* dP, const float* delta, float scale, int G, int Nq, int Nk, int ldp,
-                   hipStream_t st, unsigned* amax_bits) {
-    const int64_t total = (int64_t)G * Nq * ldp;
-    if (total <= 0) return 0;
-    const bool vec = (ldp & 3) == 0 && ((uintptr_t)P & 15) == 0 && ((uintptr_t)dP & 15) == 0 && total / 4 < ((int64_t)1 << 32);
-    if (amax_bits && !vec) return -2;                       // the caller registered a producer-side amax: only this form has it
-    prof_begin("attn_ds_kernel", 0.0, 12.0 * total, st);
-    if (vec) {
-        const unsigned t4 = (unsigned)(total / 4);
-        unsigned blocks = (t4 + 256u * 4u - 1) / (256u * 4u);
-        if (blocks > 16384) blocks = 16384;
-        hipLaunchKernelGGL(attn_ds_vec_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const f32x4*>(P),
-                           reinterpret_cast<f32x4*>(dP), delta, scale, Nk, (unsigned)(ldp / 4), t4, amax_bits);
-    } else
-        hipLaunchKernelGGL(attn_ds_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, dP, delta, scale, Nk, ldp,
-                           total);
-    prof_end(st);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -583,7 +583,7 @@ int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err) {
     if (prec == ACTMI_PREC_F16X3) {
         const int tiles_per_row = (a.Wo + F_TP - 1) / F_TP;
         const int tiles_per_cam = a.B * ((a.Ho + F_ROWS - 1) / F_ROWS) * tiles_per_row;
-        static const int blocks_target = getenv("ACTMI_CONV1_BLOCKS") ? atoi(getenv("ACTMI_CONV1_BLOCKS")) : 512;   // tuning aid; 512 measured best at B = 1, 2, 8 (tools/conv1_blocks_sweep.sh)
+        constexpr int blocks_target = 512;   // measured best at B = 1, 2, 8 against 256, 1024 and 2048 (commit 3680fa5)
         int cap = blocks_target / (a.C > 0 ? a.C : 1);
         if (cap < 1) cap = 1;
         int gx = tiles_per_cam < cap ? tiles_per_cam : cap;

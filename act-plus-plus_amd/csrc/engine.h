@@ -98,6 +98,7 @@ struct TrainState {
     // backward scratch
     float *gA = nullptr, *gB = nullptr, *gC = nullptr, *gH = nullptr, *gQKV = nullptr, *Pbuf = nullptr, *dPbuf = nullptr,
           *delta = nullptr, *dXg = nullptr, *tmp2BD = nullptr, *tmpD = nullptr, *dqb = nullptr;
+    int64_t P_floats = 0;              // size of Pbuf and of dPbuf (train_fit_prec)
     int* pos_rows = nullptr;
 };
 
@@ -129,11 +130,8 @@ struct actmi_ctx {
     int64_t splitk_ws_floats = 0;
     int conv1_vpool = 1;               // inference: conv1 emits the vertical half of the max pool (ACTMI_CONV1_VPOOL=0: off)
     int fwd_splitk = 1;                // 0: never split a forward contraction (ACTMI_FWD_SPLITK=0)
-    int sk_target = 1536, sk_minnk = 12, sk_maxtiles = 768;     // split heuristic (tuning aids ACTMI_FWD_SPLITK_*)
-    int sk_target_long = 4864, sk_maxtiles_long = 1300, sk_long_nk = 128;   // B = 8: very long contractions (layer4, K = 4608)
     hipStream_t side_stream = nullptr; // downsample branch of the ResNet blocks (engine_backbone)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool ds_fork = true;
     // two camera halves of the ResNet trunk as two parallel branches (second stream): the tail of one half's launch is
     // filled by the other half's next launch (default on, ACTMI_CAM_PIPE=0 disables; engine_backbone)
     hipStream_t pipe_stream = nullptr;             // branch 1 (non-null = branches available)
@@ -142,7 +140,6 @@ struct actmi_ctx {
     hipEvent_t ev_pjoins[3] = {nullptr, nullptr, nullptr};
     int nbranch = 2;                   // ACTMI_BRANCHES (2 .. 4)
     bool cam_pipe = false;
-    int ln_split_short = 1;            // the same for 16 <= K/32 < 64 (out-proj: K = 512) (ACTMI_LN_SPLIT_SHORT)
     int ln_split = 3;                  // split factor of a long-K product followed by a slice-summing LayerNorm (ACTMI_LN_SPLIT)
     int last_B = 0;                    // batch of the forward in flight (debug views)
     int policy_mult = 1;               // split-K policy counts the tiles of the WHOLE camera set while a half is being launched
@@ -150,7 +147,6 @@ struct actmi_ctx {
     bool calibrating = false;          // engine_backbone is running the calibration forward
     float ip_a_scale = 1.f;            // the same for input_proj's operand (the layer4 maps)
     float* act_scale_dev = nullptr;    // device copies [convs.size() + 1] for the kernels that take a device scale (conv3.hip)
-    bool fuse_ds = true;               // downsample branch inside conv2's contraction (ACTMI_FUSE_DS=0: three launches as before)
     int64_t ptotal = 0;
     bool finalized = false;
     // geometry
@@ -167,8 +163,7 @@ struct actmi_ctx {
     // activations
     float *act1 = nullptr, *buf[3] = {nullptr, nullptr, nullptr};
     float *X = nullptr, *X1 = nullptr, *Y = nullptr, *ATT = nullptr, *QKV = nullptr, *Hb = nullptr;
-    float* XP = nullptr;               // x + pos of the encoder stream, written by the LayerNorm that produces x (ACTMI_LN_XP=0: off)
-    bool ln_xp = true, ln_head = true; // LayerNorm extras: x + pos second output, action head in the decoder's last LayerNorm
+    float* XP = nullptr;               // x + pos of the encoder stream, written by the LayerNorm that produces x
     float *dO = nullptr, *dY = nullptr, *dT2 = nullptr, *dH = nullptr, *hs = nullptr;
     float* attn_ws = nullptr;          // split-KV partials (attn.hip)
     int64_t attn_ws_floats = 0;
@@ -207,6 +202,7 @@ int engine_measure_act_scale(actmi_ctx* ctx, const float* x, int64_t rows, int c
 int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream_t st);
 float engine_weight_scale(const actmi_ctx* ctx, const float* w);
 int train_create(actmi_ctx* ctx);
+int train_fit_prec(actmi_ctx* ctx);
 int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt, const float* actions, const uint8_t* is_pad,
                   const float* eps, uint64_t dropout_seed, float dropout_p, int B, float* losses, float* a_hat_out,
                   float* mu_out, float* logvar_out, hipStream_t st);

@@ -180,24 +180,26 @@ int ctx_gemm(actmi_ctx* ctx, GemmArgs a, hipStream_t st, int ws_half, LnFuse* ln
     // Small grids (B = 1-4 rollouts: layer3/4 convolutions, the K = 3200 FFN products): a launch of a few hundred tiles
     // leaves CUs idle and its lone workgroups latency-bound on a long K loop.  Split the contraction over blockIdx.z into
     // plain slices and let a combine pass sum them in a fixed order and apply the epilogue.  Thresholds from a sweep at
-    // B = 1, 2, 4, 8 (tools/splitk_sweep.sh): aim at 1536 64x64-tile equivalents, keep >= 12 K tiles per split, leave
-    // launches of >= 768 such tiles alone (B = 8 and the training batch never qualify).
+    // B = 1, 2, 4, 8 (profiles/r01_i_splitk_sweep.json): aim at 1536 64x64-tile equivalents, keep >= 12 K tiles per split,
+    // leave launches of >= 768 such tiles alone (B = 8 and the training batch never qualify).
+    constexpr int sk_target = 1536, sk_minnk = 12, sk_maxtiles = 768;
+    // B = 8: very long contractions (layer4, K = 4608)
+    constexpr int sk_target_long = 4864, sk_maxtiles_long = 1300, sk_long_nk = 128;
     if (ctx->fwd_splitk && ctx->splitk_ws && a.splitk <= 1 && a.tb == 0 && a.ta == 0 && (a.mode == 0 || a.mode == 1) &&
         !a.rowmap && !a.C2 && !a.mask && a.drop_p == 0.f && a.res_mod == 0 && a.groups_inner == 0 && !a.stamps) {
         const int groups = a.groups > 0 ? a.groups : 1;
         const int64_t tiles = (int64_t)((a.M + 63) / 64) * ((a.N + 63) / 64) * groups * (ws_half >= 0 ? ctx->policy_mult : 1);
         const int nk = (a.K + 31) / 32;
-        int S = tiles < ctx->sk_maxtiles ? (int)((ctx->sk_target + tiles - 1) / tiles) : 1;
+        int S = tiles < sk_maxtiles ? (int)((sk_target + tiles - 1) / tiles) : 1;
         // B = 8: the 304-workgroup launches with a very long contraction (layer4's K = 4608 convolutions: 217 us unsplit,
         // 167 us + a 26 us combine pass split four ways; the K <= 3200 shapes do not pay for their combine pass --
         // profiles/r02_splitk_b8_sweep.json)
-        if (S == 1 && tiles < ctx->sk_maxtiles_long && nk >= ctx->sk_long_nk) S = (int)((ctx->sk_target_long + tiles - 1) / tiles);
+        if (S == 1 && tiles < sk_maxtiles_long && nk >= sk_long_nk) S = (int)((sk_target_long + tiles - 1) / tiles);
         // a product whose LayerNorm sums the slices itself pays no combine pass: a long contraction on a grid that leaves CUs
         // idle (FFN2: K = 3200 on 304 workgroups at B = 8) is split even where the general rule would not (ACTMI_LN_SPLIT)
-        if (ln && S == 1 && ctx->ln_split > 1 && nk >= 64 && tiles < 2 * ctx->sk_maxtiles) S = ctx->ln_split;
-        if (ln && S == 1 && ctx->ln_split_short > 1 && nk >= 16 && nk < 64 && tiles < 2 * ctx->sk_maxtiles) S = ctx->ln_split_short;
+        if (ln && S == 1 && ctx->ln_split > 1 && nk >= 64 && tiles < 2 * sk_maxtiles) S = ctx->ln_split;
         if (S > 8) S = 8;
-        if (S > nk / ctx->sk_minnk) S = nk / ctx->sk_minnk;
+        if (S > nk / sk_minnk) S = nk / sk_minnk;
         while (S >= 2 && (S - 1) * ((nk + S - 1) / S) >= nk) --S;              // every split must own a K tile
         const int64_t slice = (int64_t)a.M * a.N;
         if (S >= 2 && slice * groups * S <= ws_floats && (a.N & 3) == 0) {
@@ -409,12 +411,8 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
         { const char* vp = getenv("ACTMI_CONV1_VPOOL"); ctx->conv1_vpool = !(vp && vp[0] == '0'); }
         const char* sk = getenv("ACTMI_FWD_SPLITK");
         ctx->fwd_splitk = !(sk && sk[0] == '0');
-        if (const char* e2 = getenv("ACTMI_FWD_SPLITK_TARGET")) ctx->sk_target = atoi(e2);
-        if (const char* e2 = getenv("ACTMI_FWD_SPLITK_MINNK")) ctx->sk_minnk = atoi(e2) > 0 ? atoi(e2) : 1;
-        if (const char* e2 = getenv("ACTMI_FWD_SPLITK_MAXTILES")) ctx->sk_maxtiles = atoi(e2);
-        if (const char* e2 = getenv("ACTMI_FWD_SPLITK_LONG_NK")) ctx->sk_long_nk = atoi(e2) > 0 ? atoi(e2) : 1 << 30;
         // slices of split contractions (ctx_gemm checks the fit); 256 MB covers 4-way splits of the B = 8 launches
-        ctx->splitk_ws_floats = (int64_t)(getenv("ACTMI_FWD_SPLITK_WS_MB") ? atoi(getenv("ACTMI_FWD_SPLITK_WS_MB")) : 256) << 18;
+        ctx->splitk_ws_floats = (int64_t)256 << 18;
         if ((rc = dev_alloc(ctx, &ctx->splitk_ws, ctx->splitk_ws_floats))) return fail(rc);
     }
     {
@@ -495,7 +493,8 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
     }
     const int D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N, B = g.max_batch;
     if ((rc = dev_alloc(ctx, &ctx->conv1_w, (int64_t)C * w0 * 148))) return fail(rc);
-    if (ctx->gemm_prec == ACTMI_PREC_F16X3 && (rc = dev_alloc(ctx, &ctx->conv1_wimg, (int64_t)C * conv1_wimg_bytes() / 4))) return fail(rc);
+    // (whatever the precision at create: actmi_set_gemm_prec may select f16x3 later)
+    if ((rc = dev_alloc(ctx, &ctx->conv1_wimg, (int64_t)C * conv1_wimg_bytes() / 4))) return fail(rc);
     if ((rc = dev_alloc(ctx, &ctx->conv1_scale, (int64_t)C * w0))) return fail(rc);
     if ((rc = dev_alloc(ctx, &ctx->conv1_bias, (int64_t)C * w0))) return fail(rc);
     if ((rc = dev_alloc(ctx, &ctx->lut, 768))) return fail(rc);
@@ -521,8 +520,6 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
     if ((rc = dev_alloc(ctx, &ctx->XP, BN_ * D))) return fail(rc);
     if ((rc = dev_alloc(ctx, &ctx->act_scale_dev, (int64_t)ctx->convs.size() + 4))) return fail(rc);
     { const char* e1 = getenv("ACTMI_ACT_CALIB"); ctx->act_calib = !(e1 && e1[0] == '0'); }
-    { const char* e1 = getenv("ACTMI_LN_XP"); ctx->ln_xp = !(e1 && e1[0] == '0'); }
-    { const char* e1 = getenv("ACTMI_LN_HEAD"); ctx->ln_head = !(e1 && e1[0] == '0'); }
     if ((rc = dev_alloc(ctx, &ctx->Y, BN_ * D))) return fail(rc);
     if ((rc = dev_alloc(ctx, &ctx->ATT, BN_ * D))) return fail(rc);
     if ((rc = dev_alloc(ctx, &ctx->QKV, BN_ * 3 * D))) return fail(rc);
@@ -539,12 +536,9 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
         if ((rc = dev_alloc(ctx, &ctx->attn_ws, ctx->attn_ws_floats))) return fail(rc);
     }
     {
-        // second stream for the downsample branch of the ResNet blocks (ACTMI_DS_FORK=0 keeps everything on one stream).
-        // Not used while the per-launch profiler is on (its events bracket launches on one stream) or when forward
-        // contractions are being split (the side branch would share the slice workspace)
-        const char* e = getenv("ACTMI_DS_FORK");
-        ctx->ds_fork = !(e && e[0] == '0');
-        { const char* ef = getenv("ACTMI_FUSE_DS"); ctx->fuse_ds = !(ef && ef[0] == '0'); }
+        // second stream for the downsample branch of the ResNet blocks.  Not used while the per-launch profiler is on (its
+        // events bracket launches on one stream) or when forward contractions are being split (the side branch would share
+        // the slice workspace)
         if (hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess) {
@@ -552,7 +546,6 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
             return fail(ACTMI_E_LAUNCH);
         }
         if (const char* e8 = getenv("ACTMI_LN_SPLIT")) ctx->ln_split = atoi(e8);
-        if (const char* e9 = getenv("ACTMI_LN_SPLIT_SHORT")) ctx->ln_split_short = atoi(e9);
         const char* e5 = getenv("ACTMI_CAM_PIPE");
         ctx->cam_pipe = !(e5 && e5[0] == '0');             // default on; ACTMI_CAM_PIPE=0: one branch (every launch spans all cameras)
         if (const char* e6 = getenv("ACTMI_BRANCHES")) ctx->nbranch = atoi(e6);
@@ -626,12 +619,11 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
         // finalize raises ACTMI_FLAG_WEIGHT instead of silently becoming inf
         CHK(launch_split16_map(ctx->pbase, ctx->p16base, ctx->ptotal, ctx->pseg64, ctx->pscale_dev, ctx->flags, st));
         CHK(launch_conv1_wimg(ctx->conv1_w, ctx->conv1_wimg, C, w0, st, ctx->conv1_wscale));
-        static const bool tap_inner_on = !(getenv("ACTMI_K_TAP_INNER") && getenv("ACTMI_K_TAP_INNER")[0] == '0');
         for (ConvLayer& cl : ctx->convs) {
             // K order of the image: channel blocks outer, taps inner, for the convolutions of the implicit-GEMM kernel (L2 reuse of
             // the input patch); the direct kernel of layer1 reads (r, s, c)
             const bool direct = cl.k == 3 && cl.stride == 1 && cl.pad == 1 && cl.cin == 64 && cl.cout == 64;
-            cl.k_tap_inner = tap_inner_on && cl.k == 3 && (cl.cin % 32) == 0 && !direct &&
+            cl.k_tap_inner = cl.k == 3 && (cl.cin % 32) == 0 && !direct &&
                              (int64_t)C * cl.cout * (cl.K + cl.Kx) <= ctx->splitk_ws_floats;
             if (cl.k_tap_inner) {
                 CHK(launch_permute_conv_k(cl.w, ctx->splitk_ws, (int64_t)C * cl.cout, cl.k * cl.k, cl.cin, cl.K, st));
@@ -677,6 +669,8 @@ int engine_finalize(actmi_ctx* ctx, hipStream_t st) {
     ctx->err.clear();
     const actmi_config& g = ctx->cfg;
     const int C = g.num_cams, D = g.hidden_dim;
+    // 1. training scratch for the current precision (actmi_set_gemm_prec may have changed it since create)
+    if (ctx->train) CHK(train_fit_prec(ctx));
     // 2. u8 -> normalised float LUT with the reference's arithmetic:
     //    x = float(v / 255.0 in f64)  (imitate_episodes.py:212), (x - mean) / std in f32 (policy.py:268-272)
     {
@@ -854,28 +848,11 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
     // row-wise pass finishes it.  Same maxima, so the result is bit-identical to conv1 -> 3x3 pool.
     const bool vpool = ctx->conv1_vpool && ctx->stop_stage != "conv1" && ctx->gemm_prec == ACTMI_PREC_F16X3 && (ctx->H1 & 1) == 0 &&
                        (w0 & 3) == 0 && ctx->H2 == ctx->H1 / 2;
-    // stem (conv1 + pool) of the cameras [c0, c0 + nc) on stream ss
-    auto run_stem = [&](int c0, int nc, hipStream_t ss) -> int {
-        Conv1Args cc = c1;
-        cc.cam0 = c0; cc.ncam = nc;
-        if (vpool) {
-            cc.vpool = 1;
-            CHK(launch_conv1(cc, ss, &ctx->err));
-            const int64_t a_cam = (int64_t)B * ctx->H2 * ctx->W1 * w0, p_cam = (int64_t)B * ctx->H2 * ctx->W2 * w0;
-            CHK(launch_hpool(ctx->act1 + c0 * a_cam, ctx->buf[0] + c0 * p_cam, nc * B * ctx->H2, ctx->W1, w0, ctx->W2, ss));
-        } else {
-            CHK(launch_conv1(cc, ss, &ctx->err));
-            const int64_t a_cam = (int64_t)B * ctx->H1 * ctx->W1 * w0, p_cam = (int64_t)B * ctx->H2 * ctx->W2 * w0;
-            CHK(launch_maxpool(ctx->act1 + c0 * a_cam, ctx->buf[0] + c0 * p_cam, nc * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, ss));
-        }
-        return 0;
-    };
-    // the stem inside the branches (ACTMI_STEM_BRANCH=1): one branch's conv1 (bound by its own instruction stream) beside the
-    // other's pool / layer1 launches
-    static const bool stem_in_branch = getenv("ACTMI_STEM_BRANCH") && getenv("ACTMI_STEM_BRANCH")[0] == '1';
-    const bool pipe_early = stem_in_branch && ctx->cam_pipe && ctx->pipe_stream && C >= 2 && !prof_enabled() && ctx->stop_stage.empty() &&
-                            !ctx->calibrating;
-    if (!pipe_early) CHK(run_stem(0, C, st));
+    // stem (conv1 + pool) of all cameras, ahead of the branches
+    c1.vpool = vpool ? 1 : 0;
+    CHK(launch_conv1(c1, st, &ctx->err));
+    if (vpool) CHK(launch_hpool(ctx->act1, ctx->buf[0], C * B * ctx->H2, ctx->W1, w0, ctx->W2, st));
+    else CHK(launch_maxpool(ctx->act1, ctx->buf[0], C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st));
     ctx->dbg.clear();
     ctx->dbg["conv1"] = {ctx->act1, (int64_t)C * B * ctx->H1 * ctx->W1 * w0};
     ctx->dbg["maxpool"] = {ctx->buf[0], (int64_t)C * B * ctx->H2 * ctx->W2 * w0};
@@ -924,7 +901,7 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
     // the side branch needs the split-K workspace for itself: only taken when the main stream's launches do not split
     // (not while the per-launch profiler brackets launches with events, nor for the debug early-outs)
     const bool pipe = ctx->cam_pipe && ctx->pipe_stream && C >= 2 && !prof_enabled() && ctx->stop_stage.empty() && !ctx->calibrating;
-    const bool fork_ds = ctx->side_stream != nullptr && ctx->ds_fork && !pipe && !ctx->calibrating;
+    const bool fork_ds = ctx->side_stream != nullptr && !pipe && !ctx->calibrating;
     float* final_cur = nullptr;
     // layer1 .. layer4 for the cameras [c0, c0 + nc) on stream ls
     auto run_layers = [&](int c0, int nc, hipStream_t ls, int half) -> int {
@@ -960,7 +937,7 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
                 const ConvLayer& k1 = ctx->convs[ci++];
                 const ConvLayer& k2 = ctx->convs[ci++];
                 const bool has_ds = (bi == 0 && li > 1);
-                if (has_ds && ctx->fuse_ds && k2.wf && ctx->gemm_prec == ACTMI_PREC_F16X3 && !ctx->calibrating && k2.a_scale == 1.f &&
+                if (has_ds && k2.wf && ctx->gemm_prec == ACTMI_PREC_F16X3 && !ctx->calibrating && k2.a_scale == 1.f &&
                     ctx->convs[k2.ds_index].a_scale == 1.f) {
                     // the downsample branch rides in conv2's contraction (second source = the block input at stride 2):
                     // two launches instead of three, and the branch's map is neither written nor read back
@@ -1025,9 +1002,7 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
         const int nb = C < ctx->nbranch ? C : ctx->nbranch;
         const int rc = run_branches(ctx, nb, st, [&](int i, hipStream_t bs) -> int {
             const int c0 = i * C / nb, c1 = (i + 1) * C / nb;
-            int r = pipe_early ? run_stem(c0, c1 - c0, bs) : 0;
-            if (r == 0) r = run_layers(c0, c1 - c0, bs, i);
-            return r;
+            return run_layers(c0, c1 - c0, bs, i);
         });
         if (rc != 0) return rc;
     } else {
@@ -1136,7 +1111,7 @@ int engine_decoder_infer(actmi_ctx* ctx, const TView& V, int B, float* a_hat, hi
     // default-on output guard: an operand that left the fp16 range of the f16x3 products surfaces as inf / NaN in a_hat and
     // raises the flag (read at the caller's next natural synchronisation: actmi_get_flags)
     LnExtra hx;
-    const bool head_in_ln = ctx->ln_head && g.action_dim <= 64;
+    const bool head_in_ln = g.action_dim <= 64;
     if (head_in_ln) {
         hx.head_out = a_hat; hx.head_w = ctx->P("action_head.weight"); hx.head_b = ctx->P("action_head.bias"); hx.head_n = g.action_dim;
         hx.flag = ctx->flags; hx.flag_bit = ACTMI_FLAG_OUTPUT;
@@ -1200,7 +1175,7 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
         const TView V = make_view(ctx, b0, nb, half);
         // x + pos as a matrix of its own (written by each layer's last LayerNorm) wherever the consumer's column split falls on
         // a tile boundary: the packed QKV products of layers 1.. and the decoder's KV product are then plain GEMMs
-        const bool xp_qkv = ctx->ln_xp && ((2 * D) % 128) == 0, xp_kv = ctx->ln_xp && (D % 128) == 0;
+        const bool xp_qkv = ((2 * D) % 128) == 0, xp_kv = (D % 128) == 0;
         for (int l = 0; l < g.enc_layers; ++l)
             CHK(engine_encoder_layer(ctx, ctx->enc[l], V, ctx->pos_tokens, nb, N, nullptr, ts, l > 0 && xp_qkv,
                                      l + 1 < g.enc_layers ? xp_qkv : xp_kv));

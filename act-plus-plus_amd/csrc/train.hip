@@ -11,6 +11,7 @@
 #include "engine.h"
 #include "dropout.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -154,8 +155,7 @@ int pick_splitk(int M, int N, int groups, int K) {
     // outputs of at least one 128x128 tile per side: the launch runs 128x128 tiles, two per CU = 512 at a time.  Choose the split
     // that fills whole rounds of 512 (layer4's weight gradient: 576 workgroups unsplit = one full round + a round of 64 that lasts
     // as long -- 132 TF; layer3's: 432): the smallest S within 3 % of the best fill, at least 16 K tiles per split.
-    static const bool fill_rule = !(getenv("ACTMI_WGRAD_SPLIT_FILL") && getenv("ACTMI_WGRAD_SPLIT_FILL")[0] == '0');
-    if (fill_rule && M >= 128 && N >= 128) {
+    if (M >= 128 && N >= 128) {
         const long w = (long)((M + 127) / 128) * ((N + 127) / 128) * groups;
         const long nk = (K + 31) / 32;
         long smax = nk / 16;
@@ -241,35 +241,37 @@ struct AttnBwd {
 
 // long sequences (the encoder's 1202 x 1202 self-attention) take the fused kernels of attn_bwd.hip: no P / dS buffers
 static bool attn_bwd_fused(const actmi_ctx* ctx, int Nq, int Nk, int HD, bool shared_q) {
-    static const bool flash = !(getenv("ACTMI_ATTN_BWD_FLASH") && getenv("ACTMI_ATTN_BWD_FLASH")[0] == '0');
-    return flash && ctx->gemm_prec == ACTMI_PREC_F16X3 && !shared_q && Nq >= 256 && Nk >= 256 && (HD == 64 || HD == 32 || HD == 16);
+    return ctx->gemm_prec == ACTMI_PREC_F16X3 && !shared_q && Nq >= 256 && Nk >= 256 && (HD == 64 || HD == 32 || HD == 16);
 }
 
 int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
     TrainState& T = *ctx->train;
     const int G = t.B * t.H, D = t.H * t.HD;
-    {
-        if (attn_bwd_fused(ctx, t.Nq, t.Nk, t.HD, t.q_bs == 0)) {
-            CHK(launch_attn_delta(t.dO, t.O, T.delta, t.B, t.H, t.Nq, t.HD, st));
-            AttnBwdArgs a{};
-            a.Q = t.Q; a.K = t.K; a.V = t.V; a.dO = t.dO; a.lse = t.lse; a.delta = T.delta;
-            a.dO_scale = dyn_scale(ctx, t.dO, D, t.B * t.Nq, D, st);
-            a.dQ = t.dQ; a.dK = t.dK; a.dV = t.dV;
-            a.q_bs = t.q_bs; a.q_rs = t.q_rs; a.k_bs = t.k_bs; a.k_rs = t.k_rs; a.v_bs = t.v_bs; a.v_rs = t.v_rs;
-            a.do_bs = (int64_t)t.Nq * D; a.do_rs = D;
-            a.dq_bs = t.dq_bs; a.dq_rs = t.dq_rs; a.dk_bs = t.dk_bs; a.dk_rs = t.dk_rs; a.dv_bs = t.dv_bs; a.dv_rs = t.dv_rs;
-            a.kpm = t.kpm; a.kpm_bs = t.kpm_bs;
-            a.B = t.B; a.H = t.H; a.Nq = t.Nq; a.Nk = t.Nk; a.HD = t.HD;
-            a.scale = 1.0f / sqrtf((float)t.HD); a.drop_p = t.drop_p; a.drop_seed = t.drop_seed;
-            a.amax_out = t.out_amax;
-            return launch_attention_bwd(a, st, &ctx->err);
-        }
+    if (attn_bwd_fused(ctx, t.Nq, t.Nk, t.HD, t.q_bs == 0)) {
+        CHK(launch_attn_delta(t.dO, t.O, T.delta, t.B, t.H, t.Nq, t.HD, st));
+        AttnBwdArgs a{};
+        a.Q = t.Q; a.K = t.K; a.V = t.V; a.dO = t.dO; a.lse = t.lse; a.delta = T.delta;
+        a.dO_scale = dyn_scale(ctx, t.dO, D, t.B * t.Nq, D, st);
+        a.dQ = t.dQ; a.dK = t.dK; a.dV = t.dV;
+        a.q_bs = t.q_bs; a.q_rs = t.q_rs; a.k_bs = t.k_bs; a.k_rs = t.k_rs; a.v_bs = t.v_bs; a.v_rs = t.v_rs;
+        a.do_bs = (int64_t)t.Nq * D; a.do_rs = D;
+        a.dq_bs = t.dq_bs; a.dq_rs = t.dq_rs; a.dk_bs = t.dk_bs; a.dk_rs = t.dk_rs; a.dv_bs = t.dv_bs; a.dv_rs = t.dv_rs;
+        a.kpm = t.kpm; a.kpm_bs = t.kpm_bs;
+        a.B = t.B; a.H = t.H; a.Nq = t.Nq; a.Nk = t.Nk; a.HD = t.HD;
+        a.scale = 1.0f / sqrtf((float)t.HD); a.drop_p = t.drop_p; a.drop_seed = t.drop_seed;
+        a.amax_out = t.out_amax;
+        return launch_attention_bwd(a, st, &ctx->err);
     }
     const int ldp = (t.Nk + 3) & ~3;
     const float scale = 1.0f / sqrtf((float)t.HD);
     float* P = T.Pbuf;
     float* dP = T.dPbuf;
     const int64_t pg = (int64_t)t.Nq * ldp;
+    if ((int64_t)G * pg > T.P_floats) {
+        ctx->err = "attention backward: P / dS need " + std::to_string((int64_t)G * pg) + " floats, the handle holds " +
+                   std::to_string(T.P_floats) + " (precision changed without finalize?)";
+        return ACTMI_E_STATE;
+    }
     // S = scale * Q K^T
     GemmArgs s = G0();
     s.A = t.Q; s.lda = t.q_rs; s.M = t.Nq; s.K = t.HD; s.Bw = t.K; s.ldb = t.k_rs; s.N = t.Nk; s.C = P; s.ldc = ldp;
@@ -277,18 +279,10 @@ int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
     s.gA = t.q_bs; s.gA2 = t.HD; s.gB = t.k_bs; s.gB2 = t.HD; s.gC = pg * t.H; s.gC2 = pg;
     // P = exp(S - lse) (key-padded columns zero) straight from the epilogue of the score product; the columns Nk .. ldp-1 of
     // the buffer are cleared by a small kernel (the buffer is shared by attention calls of different widths)
-    static const bool fuse = !(getenv("ACTMI_ATTN_BWD_FUSE") && getenv("ACTMI_ATTN_BWD_FUSE")[0] == '0');
-    static const int sd_tile = getenv("ACTMI_ATTN_BWD_TILE") ? atoi(getenv("ACTMI_ATTN_BWD_TILE")) : 0;
-    s.tile_hint = sd_tile;
-    if (fuse) {
-        s.epi = 1; s.epi_row = t.lse; s.gRow = (int64_t)t.H * t.Nq; s.gRow2 = t.Nq;
-        s.epi_colkill = t.kpm; s.gColkill = t.kpm_bs;
-        CHK(tgemm(ctx, s, st));
-        if (ldp != t.Nk) CHK(launch_zero_cols(P, (int64_t)G * t.Nq, ldp, t.Nk, st));
-    } else {
-        CHK(tgemm(ctx, s, st));
-        CHK(launch_attn_probs(P, t.lse, t.kpm, t.kpm_bs, G, t.H, t.Nq, t.Nk, ldp, st));
-    }
+    s.epi = 1; s.epi_row = t.lse; s.gRow = (int64_t)t.H * t.Nq; s.gRow2 = t.Nq;
+    s.epi_colkill = t.kpm; s.gColkill = t.kpm_bs;
+    CHK(tgemm(ctx, s, st));
+    if (ldp != t.Nk) CHK(launch_zero_cols(P, (int64_t)G * t.Nq, ldp, t.Nk, st));
     CHK(launch_attn_delta(t.dO, t.O, T.delta, t.B, t.H, t.Nq, t.HD, st));
     // dV[key][d] = sum_q Pd[q][key] dO[q][d]   (Pd = dropped weights; staged in the dP buffer before dP overwrites it)
     const float* Pv = P;
@@ -311,9 +305,11 @@ int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
     d.groups = G; d.groups_inner = t.H;
     d.gA = (int64_t)t.Nq * D; d.gA2 = t.HD; d.gB = t.v_bs; d.gB2 = t.HD; d.gC = pg * t.H; d.gC2 = pg;
     d.a_scale_dev = dO_sc;
-    d.tile_hint = sd_tile;
-    const bool fuse_ds = fuse && !(t.drop_p > 0.f);
-    if (fuse_ds) {
+    if (t.drop_p > 0.f) {
+        CHK(tgemm(ctx, d, st));
+        // dS = P * (dP - delta) * scale in place of dP, with dP = dPd * mask / (1-p)
+        CHK(launch_attn_ds_drop(P, dP, T.delta, scale, t.drop_seed, t.drop_p, G, t.Nq, t.Nk, ldp, st));
+    } else {
         // dS = P * (dP - delta) * scale in the epilogue of the dP product (dP itself is never stored), with the operand-scale
         // maximum of dS collected on the way out
         d.epi = 2; d.epi_scale = scale; d.epi_row = T.delta; d.gRow = (int64_t)t.H * t.Nq; d.gRow2 = t.Nq;
@@ -321,11 +317,6 @@ int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
         d.amax_out = amax_pre(ctx, dP, st);
         CHK(tgemm(ctx, d, st));
         if (ldp != t.Nk) CHK(launch_zero_cols(dP, (int64_t)G * t.Nq, ldp, t.Nk, st));
-    } else {
-        CHK(tgemm(ctx, d, st));
-        // dS = P * (dP - delta) * scale   (in place of dP; with dropout dP = dPd * mask / (1-p))
-        if (t.drop_p > 0.f) CHK(launch_attn_ds_drop(P, dP, T.delta, scale, t.drop_seed, t.drop_p, G, t.Nq, t.Nk, ldp, st));
-        else CHK(launch_attn_ds(P, dP, T.delta, scale, G, t.Nq, t.Nk, ldp, st, amax_pre(ctx, dP, st)));
     }
     // dQ[q][d] = sum_key dS[q][key] K[key][d]
     GemmArgs q = G0();
@@ -443,8 +434,7 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
 int conv_wgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, const float* x, int B, hipStream_t st) {
     TrainState& T = *ctx->train;
     const int C = ctx->cfg.num_cams;
-    static const bool direct_on = !(getenv("ACTMI_WGRAD_DIRECT") && getenv("ACTMI_WGRAD_DIRECT")[0] == '0');
-    if (direct_on && ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.cin == 64 && cl.cout == 64 && cl.k == 3 && cl.stride == 1 && cl.pad == 1 &&
+    if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.cin == 64 && cl.cout == 64 && cl.k == 3 && cl.stride == 1 && cl.pad == 1 &&
         T.det_ws && T.det_ws_floats >= (int64_t)C * 64 * 576) {
         // layer1: the direct kernel (wgrad3.hip) + fixed-order sum of its per-workgroup partials into the packed gradient
         const float* sc = dyn_scale(ctx, dys, cl.cout, C * B * cl.Ho * cl.Wo, cl.cout, st);
@@ -477,8 +467,7 @@ int conv_wgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, co
 // layer1's data gradients (64 -> 64 channels, 3x3 / s1 / p1) run as a forward convolution of dY with the flipped, transposed
 // weights on the direct kernel of the inference path (conv3.hip: LDS-resident patch, 1.3 ms against the gather GEMM's 2.5 ms)
 bool dgrad_direct(const actmi_ctx* ctx, const ConvLayer& cl) {
-    static const bool on = !(getenv("ACTMI_DGRAD_DIRECT") && getenv("ACTMI_DGRAD_DIRECT")[0] == '0');
-    return on && ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.cin == 64 && cl.cout == 64 && cl.k == 3 && cl.stride == 1 && cl.pad == 1;
+    return ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.cin == 64 && cl.cout == 64 && cl.k == 3 && cl.stride == 1 && cl.pad == 1;
 }
 
 // dx[C][B][H][W][cin] = dgrad(dys) (+res) , then masked by (mask > 0) and multiplied by scale[cin] (previous BN)
@@ -563,10 +552,8 @@ int train_create(actmi_ctx* ctx) {
         float *gw, *wd;
         TA(gw, (int64_t)C * cl.cout * cl.K); TA(wd, (int64_t)C * cl.cin * cl.k * cl.k * cl.cout);
         T.conv_gw.push_back(gw); T.conv_wd.push_back(wd);
-        float* wd16 = nullptr;
-        if (dgrad_direct(ctx, cl)) TA(wd16, (int64_t)C * cl.cin * cl.k * cl.k * cl.cout);
-        T.conv_wd16.push_back(wd16);
     }
+    T.conv_wd16.assign(ctx->convs.size(), nullptr);
     TA(T.conv1_gw, (int64_t)C * w0 * 196);
     {
         float* pa = nullptr;           // argmax codes of the stem max-pool, one byte per pooled element
@@ -619,16 +606,8 @@ int train_create(actmi_ctx* ctx) {
     // backward scratch
     const int64_t MN = (int64_t)B * N;
     TA(T.gA, MN * D); TA(T.gB, MN * D); TA(T.gC, MN * D); TA(T.gH, MN * F); TA(T.gQKV, MN * 3 * D);
-    const int ldp = (N + 3) & ~3;
-    {
-        // materialised P / dS of the attention calls that do not take the fused backward: decoder cross-attention (Q x N), the
-        // CVAE encoder ((Q+2)^2), and -- only without the fused kernels -- the encoder's N x N (2 x 3 GB at B = 64)
-        const int ldq = (Q + 2 + 3) & ~3;
-        int64_t prow = (int64_t)Q * ldp;
-        if ((int64_t)(Q + 2) * ldq > prow) prow = (int64_t)(Q + 2) * ldq;
-        if (!attn_bwd_fused(ctx, N, N, D / H, false) && (int64_t)N * ldp > prow) prow = (int64_t)N * ldp;
-        TA(T.Pbuf, (int64_t)B * H * prow); TA(T.dPbuf, (int64_t)B * H * prow); TA(T.delta, (int64_t)B * H * (N > Q + 2 ? N : Q + 2));
-    }
+    TA(T.delta, (int64_t)B * H * (N > Q + 2 ? N : Q + 2));
+    if ((rc = train_fit_prec(ctx))) return rc;
     TA(T.dXg, (int64_t)B * (C * ctx->P_ > Q ? C * ctx->P_ : Q) * D);
     TA(T.tmp2BD, (int64_t)2 * B * D); TA(T.tmpD, 4 * D); TA(T.dqb, BQ * D);
     {
@@ -639,6 +618,39 @@ int train_create(actmi_ctx* ctx) {
         // note: rows are for the max batch layout; entries b < B_call are valid for any smaller batch too
     }
 #undef TA
+    return 0;
+}
+
+// Training scratch whose size depends on the handle's precision: P / dS of the attention calls that take the materialised
+// backward, and the split images of the direct data-gradient weights.  Sized at create and again at every finalize, so a
+// precision set after create (actmi_set_gemm_prec clears `finalized`) gets the scratch of a handle created with it.
+int train_fit_prec(actmi_ctx* ctx) {
+    const actmi_config& g = ctx->cfg;
+    TrainState& T = *ctx->train;
+    const int B = g.max_batch, C = g.num_cams, D = g.hidden_dim, H = g.nheads, Q = g.num_queries, N = ctx->N;
+    auto release = [&](float*& p) {           // (hipFree waits for the device: no launch in flight still uses p)
+        ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), (void*)p), ctx->allocs.end());
+        (void)hipFree(p);
+        p = nullptr;
+    };
+    int rc;
+    // materialised P / dS: decoder cross-attention (Q x N), the CVAE encoder ((Q+2)^2), and -- only without the fused kernels --
+    // the encoder's N x N (2 x 3 GB at B = 64)
+    const int ldp = (N + 3) & ~3, ldq = (Q + 2 + 3) & ~3;
+    int64_t prow = std::max((int64_t)Q * ldp, (int64_t)(Q + 2) * ldq);
+    if (!attn_bwd_fused(ctx, N, N, D / H, false)) prow = std::max(prow, (int64_t)N * ldp);
+    if ((int64_t)B * H * prow != T.P_floats) {
+        release(T.Pbuf); release(T.dPbuf);
+        T.P_floats = 0;
+        if ((rc = talloc(ctx, &T.Pbuf, (int64_t)B * H * prow)) || (rc = talloc(ctx, &T.dPbuf, (int64_t)B * H * prow))) return rc;
+        T.P_floats = (int64_t)B * H * prow;
+    }
+    for (size_t i = 0; i < ctx->convs.size(); ++i) {
+        const ConvLayer& cl = ctx->convs[i];
+        if (!dgrad_direct(ctx, cl) && T.conv_wd16[i]) release(T.conv_wd16[i]);
+        if (dgrad_direct(ctx, cl) && !T.conv_wd16[i] && (rc = talloc(ctx, &T.conv_wd16[i], (int64_t)C * cl.cin * cl.k * cl.k * cl.cout)))
+            return rc;
+    }
     return 0;
 }
 
@@ -1053,8 +1065,7 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     // (ReLU + FrozenBN backward of the stem and the operand-scale maximum ride on the pool's backward: one pass over the map)
     CHK(launch_maxpool_bwd_idx(T.pool_arg, gcur, T.g_act1, C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st, ctx->act1,
                                ctx->conv1_scale, B, amax_pre(ctx, T.g_act1, st)));
-    static const bool stem_direct = !(getenv("ACTMI_WGRAD_DIRECT") && getenv("ACTMI_WGRAD_DIRECT")[0] == '0');
-    if (stem_direct && ctx->gemm_prec == ACTMI_PREC_F16X3 && w0 == 64 && T.det_ws && ctx->H1 == (g.image_h - 1) / 2 + 1 &&
+    if (ctx->gemm_prec == ACTMI_PREC_F16X3 && w0 == 64 && T.det_ws && ctx->H1 == (g.image_h - 1) / 2 + 1 &&
         ctx->W1 == (g.image_w - 1) / 2 + 1 && T.det_ws_floats >= (int64_t)C * 64 * 196) {
         // the direct kernel (wgrad7.hip) + fixed-order sum of its per-workgroup partials into the packed gradient
         const float* sc = dyn_scale(ctx, T.g_act1, w0, C * B * ctx->H1 * ctx->W1, w0, st);
@@ -1069,8 +1080,7 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         c.res = T.conv1_gw; c.ldres = 196; c.gRes = slice;
         c.C = T.conv1_gw; c.ldc = 196; c.gC = slice; c.M = 64; c.N = 196; c.groups = C;
         if (launch_splitk_combine(c, st) != 0) { ctx->err = "splitk combine launch failed"; return ACTMI_E_LAUNCH; }
-    } else
-    {
+    } else {
         GemmArgs a = G0();
         a.A = T.g_act1; a.lda = w0; a.ta = 1; a.M = w0; a.K = B * ctx->H1 * ctx->W1;
         a.Bw = T.xn4; a.tb = 2; a.N = 196; a.H = g.image_h; a.W = g.image_w; a.Cin = 4; a.KH = a.KW = 7; a.stride = 2; a.pad = 3;

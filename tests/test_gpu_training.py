@@ -389,3 +389,37 @@ def test_bf16_training_mode_is_opt_in_and_close_to_the_reference(name):
     # the inference path of the same handle is untouched by the training mode: still fp32-grade
     a = eng.forward_infer(args[0], args[1]).cpu().numpy()
     assert np.abs(a - z["infer.a_hat"]).max() <= 1e-4
+
+
+@pytest.mark.parametrize("prec,dropout_p", [("f32", 0.0), ("f32", 0.1), ("f16x3", 0.0)])
+def test_precision_set_after_create_trains_like_precision_at_create(monkeypatch, prec, dropout_p):
+    """A precision set on a training handle after create (ACTEngine(gemm_prec=...) -> actmi_set_gemm_prec) takes the same step,
+    bit for bit, as a handle created under ACTMI_GEMM_PREC.  f32: the full-size encoder (N = 1202, head dim 64) takes the
+    materialised attention backward, whose P / dS scratch a handle created for f16x3 does not hold.  f16x3: conv1's weight image
+    and layer1's direct data gradient need buffers of their own.  finalize sizes them for the current precision."""
+    from actmi.config import ACTConfig
+    cfg = ACTConfig()
+    sd_np = W.generate_state_dict(cfg, seed=0)
+    inp = W.generate_inputs(cfg, 1, seed=3, with_actions=True)
+    t = {k: torch.from_numpy(v).cuda() for k, v in inp.items()}
+
+    def step(env_prec, gemm_prec=None):
+        if env_prec == "f32":
+            monkeypatch.setenv("ACTMI_GEMM_PREC", "f32")
+        else:
+            monkeypatch.delenv("ACTMI_GEMM_PREC", raising=False)
+        eng = ACTEngine(cfg, max_batch=1, training=True, gemm_prec=gemm_prec)
+        eng.load_state_dict(sd_np)
+        eng.finalize()
+        eng.zero_grad()
+        out = eng.forward_train(t["qpos"], t["image_u8"], t["actions"], t["is_pad"], eps=t["eps"], dropout_p=dropout_p,
+                                dropout_seed=11)
+        eng.backward(1.0)
+        torch.cuda.synchronize()
+        return {k: float(out[k]) for k in ("l1", "kl", "loss")}, eng.grad_arena().clone()
+
+    l_set, g_set = step("f16x3" if prec == "f32" else "f32", gemm_prec=prec)
+    l_env, g_env = step(prec)
+    assert all(np.isfinite(v) for v in l_set.values()) and l_set == l_env, (l_set, l_env)
+    assert torch.isfinite(g_set).all() and float(g_set.abs().max()) > 0
+    assert torch.equal(g_set, g_env), f"{int((g_set != g_env).sum())} gradient elements differ"

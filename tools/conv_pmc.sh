@@ -1,5 +1,5 @@
 # SQ / cache counters of the B=8 step's kernels, eager single-branch launches (one gpurun call); outputs under gpurun_out/pmc_r03
-# usage: bash tools/conv_pmc.sh [extra env assignments for the bench, e.g. ACTMI_FUSE_DS=0]
+# usage: bash tools/conv_pmc.sh [extra env assignments for the bench, e.g. ACTMI_CONV1_VPOOL=0]
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/pmc_r03
 mkdir -p $O
