@@ -530,11 +530,7 @@ int launch_attention(const AttnArgs& a, hipStream_t st, std::string* err) {
     if (((uintptr_t)a.Q & 15) || ((uintptr_t)a.K & 15) || ((uintptr_t)a.V & 15) || ((uintptr_t)a.O & 15))
         return fail("pointers must be 16-byte aligned");
     // precision: explicit in the descriptor, else ACTMI_GEMM_PREC (f32 | f16x3), else native fp32
-    static const int env_prec = [] {
-        const char* e = getenv("ACTMI_GEMM_PREC");
-        if (!e) return ACTMI_PREC_F32;
-        return (e[0] == 'f' && e[1] == '3') ? ACTMI_PREC_F32 : ACTMI_PREC_F16X3;
-    }();
+    static const int env_prec = env_gemm_prec(ACTMI_PREC_F32);
     const int prec = a.prec ? a.prec : env_prec;
     if (prec != ACTMI_PREC_F32 && prec != ACTMI_PREC_F16X3) return fail("bad prec");
     const bool f16 = prec == ACTMI_PREC_F16X3;

@@ -465,3 +465,15 @@ int launch_attention_bwd(const AttnBwdArgs& a, hipStream_t st, std::string* err)
     if (e != hipSuccess) { if (err) *err = std::string("attention backward launch: ") + hipGetErrorString(e); return -3; }
     return 0;
 }
+
+int launch_attention_bwd_dense(AttnBwdArgs a, const float* O, float* delta, hipStream_t st, std::string* err) {
+    const int64_t D = (int64_t)a.H * a.HD;
+    a.do_bs = (int64_t)a.Nq * D; a.do_rs = D;
+    a.scale = 1.0f / sqrtf((float)a.HD);
+    a.delta = delta;
+    if (launch_attn_delta(a.dO, O, delta, a.B, a.H, a.Nq, a.HD, st) != 0) {
+        if (err) *err = "attention backward: delta launch failed";
+        return -3;
+    }
+    return launch_attention_bwd(a, st, err);
+}

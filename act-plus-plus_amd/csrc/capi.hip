@@ -279,18 +279,15 @@ int actmi_op_attention(const actmi_attn_desc* d, void* stream) {
 int actmi_op_attention_bwd(const actmi_attn_bwd_desc* d, void* stream) {
     g_op_error.clear();
     if (!d || !d->o || !d->delta_ws) { g_op_error = "attention_bwd: null descriptor / output / scratch"; return ACTMI_E_INVALID; }
-    const int64_t D = (int64_t)d->H * d->HD;
-    if (launch_attn_delta(d->d_o, d->o, d->delta_ws, d->B, d->H, d->Nq, d->HD, S(stream)) != 0) { g_op_error = "attention_bwd: delta launch failed"; return ACTMI_E_LAUNCH; }
     AttnBwdArgs a{};
-    a.Q = d->q; a.K = d->k; a.V = d->v; a.dO = d->d_o; a.lse = d->lse; a.delta = d->delta_ws; a.dO_scale = d->do_scale;
+    a.Q = d->q; a.K = d->k; a.V = d->v; a.dO = d->d_o; a.lse = d->lse; a.dO_scale = d->do_scale;
     a.dQ = d->dq; a.dK = d->dk; a.dV = d->dv;
     a.q_bs = d->q_bs; a.q_rs = d->q_rs; a.k_bs = d->k_bs; a.k_rs = d->k_rs; a.v_bs = d->v_bs; a.v_rs = d->v_rs;
-    a.do_bs = (int64_t)d->Nq * D; a.do_rs = D;
     a.dq_bs = d->dq_bs; a.dq_rs = d->dq_rs; a.dk_bs = d->dk_bs; a.dk_rs = d->dk_rs; a.dv_bs = d->dv_bs; a.dv_rs = d->dv_rs;
     a.kpm = d->kpm; a.kpm_bs = d->kpm_bs;
     a.B = d->B; a.H = d->H; a.Nq = d->Nq; a.Nk = d->Nk; a.HD = d->HD;
-    a.scale = 1.0f / sqrtf((float)d->HD); a.drop_p = d->drop_p; a.drop_seed = d->drop_seed; a.amax_out = d->amax_out;
-    const int rc = launch_attention_bwd(a, S(stream), &g_op_error);
+    a.drop_p = d->drop_p; a.drop_seed = d->drop_seed; a.amax_out = d->amax_out;
+    const int rc = launch_attention_bwd_dense(a, d->o, d->delta_ws, S(stream), &g_op_error);
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_SHAPE : ACTMI_E_LAUNCH);
 }
 
@@ -312,9 +309,7 @@ int actmi_op_conv1(const void* image, int image_fmt, const float* w_oihw, const 
     int rc = launch_repack_conv_w(w_oihw, wp, C, Cout, 3, 7, 7, (int64_t)Cout * 147, (int64_t)Cout * 148, 148, S(stream));
     if (rc) return rc;
     float hl[768];
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    for (int c = 0; c < 3; ++c)
-        for (int v = 0; v < 256; ++v) hl[c * 256 + v] = ((float)((double)v / 255.0) - mean[c]) / stdv[c];
+    u8_lut(hl, true);
     if (hipMemcpyAsync(lut, hl, sizeof(hl), hipMemcpyHostToDevice, S(stream)) != hipSuccess) return ACTMI_E_LAUNCH;
     if (hipStreamSynchronize(S(stream)) != hipSuccess) return ACTMI_E_LAUNCH;
     Conv1Args a;
@@ -340,12 +335,7 @@ int actmi_op_conv1_prepare(const float* w_oihw, float* workspace, int C, int Cou
     int rc = launch_repack_conv_w(w_oihw, workspace, C, Cout, 3, 7, 7, (int64_t)Cout * 147, (int64_t)Cout * 148, 148, S(stream));
     if (rc) return ACTMI_E_LAUNCH;
     std::vector<float> host(768 + 2 * (size_t)C * Cout);
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    for (int c = 0; c < 3; ++c)
-        for (int v = 0; v < 256; ++v) {
-            const float x = (float)((double)v / 255.0);
-            host[c * 256 + v] = lut_mode == 0 ? (x - mean[c]) / stdv[c] : x;
-        }
+    u8_lut(host.data(), lut_mode == 0);
     for (int i = 0; i < C * Cout; ++i) { host[768 + i] = 1.f; host[768 + C * Cout + i] = 0.f; }
     if (hipMemcpyAsync(lut, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, S(stream)) != hipSuccess) return ACTMI_E_LAUNCH;
     rc = launch_conv1_wimg(workspace, wimg, C, Cout, S(stream), 256.f);
@@ -383,31 +373,17 @@ int actmi_op_conv3x3_c64(const float* x, const float* w16, float w_scale, const 
 int actmi_op_wgrad3x3_c64(const float* dy, const float* x, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev, int G,
                           int B, int H, int W, void* stream) {
     g_op_error.clear();
-    int nwg = 0;
-    int rc = launch_wgrad3x3_c64(dy, x, ws, ws_floats, dy_scale_dev, G, B, H, W, &nwg, S(stream));
+    const int rc = launch_wgrad3x3_c64(dy, x, dw, 0, ws, ws_floats, dy_scale_dev, G, B, H, W, S(stream));
     if (rc != 0) { g_op_error = "wgrad3x3_c64: bad arguments or launch failure"; return rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH; }
-    SplitCombineArgs c{};
-    const int64_t slice = (int64_t)64 * 576;
-    c.part = ws; c.nsplit = nwg; c.split_stride = slice; c.gP = slice * nwg; c.ldp = 576;
-    c.C = dw; c.ldc = 576; c.gC = slice; c.M = 64; c.N = 576; c.groups = G;
-    rc = launch_splitk_combine(c, S(stream));
-    if (rc != 0) { g_op_error = "wgrad3x3_c64: combine launch failed"; return ACTMI_E_LAUNCH; }
     return 0;
 }
 
 int actmi_op_wgrad7x7s2(const float* dy, const float* x4, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev, int G,
                         int B, int H, int W, void* stream) {
     g_op_error.clear();
-    int nwg = 0;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    int rc = launch_wgrad7x7s2(dy, x4, ws, ws_floats, dy_scale_dev, G, B, H, W, Ho, Wo, &nwg, S(stream));
+    const int rc = launch_wgrad7x7s2(dy, x4, dw, 0, ws, ws_floats, dy_scale_dev, G, B, H, W, Ho, Wo, S(stream));
     if (rc != 0) { g_op_error = "wgrad7x7s2: bad arguments or launch failure"; return rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH; }
-    SplitCombineArgs c{};
-    const int64_t slice = (int64_t)64 * 196;
-    c.part = ws; c.nsplit = nwg; c.split_stride = slice; c.gP = slice * nwg; c.ldp = 196;
-    c.C = dw; c.ldc = 196; c.gC = slice; c.M = 64; c.N = 196; c.groups = G;
-    rc = launch_splitk_combine(c, S(stream));
-    if (rc != 0) { g_op_error = "wgrad7x7s2: combine launch failed"; return ACTMI_E_LAUNCH; }
     return 0;
 }
 

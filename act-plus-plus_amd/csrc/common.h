@@ -30,6 +30,8 @@ struct ActmiError {
 typedef actmi_gemm_desc GemmArgs;
 
 int launch_gemm(const GemmArgs& a, hipStream_t st, std::string* err);
+// the precision ACTMI_GEMM_PREC asks for (f3... = ACTMI_PREC_F32, any other value = ACTMI_PREC_F16X3), `unset` without it
+int env_gemm_prec(int unset);
 
 // sums the slices of a sliced split-K product (GemmArgs::split_stride) in split order and applies the forward epilogue
 // v = sum * scale[n] + bias[n] (+ res[m][n]) -> ReLU / GELU (misc.hip)
@@ -134,6 +136,9 @@ struct AttnBwdArgs {
     unsigned* amax_out;            // optional: bits of the largest |value| written (integer atomicMax)
 };
 int launch_attention_bwd(const AttnBwdArgs& a, hipStream_t st, std::string* err);
+// the same for a dense dO [B][Nq][H*HD] (a.do_bs / do_rs / scale are filled in), with the delta pass in front: delta [B][H][Nq]
+// from dO and the forward output O (same layout as dO)
+int launch_attention_bwd_dense(AttnBwdArgs a, const float* O, float* delta, hipStream_t st, std::string* err);
 
 // ---- small kernels (misc.hip) --------------------------------------------------------------------
 int launch_small_linear(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy,
@@ -198,14 +203,14 @@ int launch_small_linear_wgrad(const float* dy, int64_t lddy, const float* x, int
 int launch_cvae_maps(int* map, uint8_t* kpm, const uint8_t* is_pad, int B, int Q, hipStream_t st);
 int launch_axpy(float* dst, const float* src, int64_t n, hipStream_t st);
 int launch_scale(float* x, int64_t n, float s, hipStream_t st);
-// direct weight gradient of the 64 -> 64 channel 3x3 / s1 / p1 convolutions (wgrad3.hip): per-workgroup partials
-// [groups][*nwg_out][64][576] into ws, to be summed by launch_splitk_combine
-int launch_wgrad3x3_c64(const float* dy, const float* x, float* ws, int64_t ws_floats, const float* dy_scale_dev, int groups, int B,
-                        int H, int W, int* nwg_out, hipStream_t st);
-// direct weight gradient of the stem (7x7 / s2 / p3, 4-channel-padded image -> 64 channels; wgrad7.hip): per-workgroup partials
-// [groups][*nwg_out][64][196]
-int launch_wgrad7x7s2(const float* dy, const float* x4, float* ws, int64_t ws_floats, const float* dy_scale_dev, int groups, int B,
-                      int H, int W, int Ho, int Wo, int* nwg_out, hipStream_t st);
+// direct weight gradient of the 64 -> 64 channel 3x3 / s1 / p1 convolutions (wgrad3.hip): dw [groups][64][576] (K index
+// (r, s, c)), accumulated into when `accumulate`; ws holds the per-workgroup partials (at least groups * 64 * 576 floats)
+int launch_wgrad3x3_c64(const float* dy, const float* x, float* dw, int accumulate, float* ws, int64_t ws_floats,
+                        const float* dy_scale_dev, int groups, int B, int H, int W, hipStream_t st);
+// direct weight gradient of the stem (7x7 / s2 / p3, 4-channel-padded image -> 64 channels; wgrad7.hip): dw [groups][64][196],
+// accumulated into when `accumulate`; ws holds the per-workgroup partials (at least groups * 64 * 196 floats)
+int launch_wgrad7x7s2(const float* dy, const float* x4, float* dw, int accumulate, float* ws, int64_t ws_floats,
+                      const float* dy_scale_dev, int groups, int B, int H, int W, int Ho, int Wo, hipStream_t st);
 int launch_pow2_scale(const float* x, int64_t ld, int M, int N, float* out, hipStream_t st);
 int launch_pow2_from_bits(float* out, hipStream_t st);      // the scale from bits a producing kernel left in out[1]
 int launch_split16(const float* src, float* dst, int64_t nfloats, float scale, hipStream_t st, uint32_t* flag = nullptr);

@@ -574,11 +574,7 @@ int launch_conv1_wimg(const float* w, void* img, int C, int Cout, hipStream_t st
 int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err) {
     if (a.Cout > 64 || a.Cout < 1) { if (err) *err = "conv1: Cout must be in 1..64"; return -2; }
     if (a.Ho != (a.H + 6 - 7) / 2 + 1 || a.Wo != (a.W + 6 - 7) / 2 + 1) { if (err) *err = "conv1: bad output size"; return -2; }
-    static const int env_prec = [] {
-        const char* e = getenv("ACTMI_GEMM_PREC");
-        if (!e) return ACTMI_PREC_F32;
-        return (e[0] == 'f' && e[1] == '3') ? ACTMI_PREC_F32 : ACTMI_PREC_F16X3;
-    }();
+    static const int env_prec = env_gemm_prec(ACTMI_PREC_F32);
     const int prec = a.prec ? a.prec : env_prec;
     if (prec == ACTMI_PREC_F16X3) {
         const int tiles_per_row = (a.Wo + F_TP - 1) / F_TP;

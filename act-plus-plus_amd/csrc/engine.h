@@ -44,6 +44,9 @@ struct ConvLayer {
     // the split images (w16, wf16) store their K index channel-block-major, taps inner (actmi_gemm_desc.k_tap_inner): every 3x3
     // convolution that runs on the implicit-GEMM kernel with Cin % 32 == 0; the direct kernels (layer1) keep (r, s, c)
     bool k_tap_inner = false;
+    // 64 -> 64 channels, 3x3 / s1 / p1 (layer1): under f16x3 its forward, data gradient and weight gradient take the direct
+    // kernels (conv3.hip, wgrad3.hip) instead of the implicit GEMM; set at create
+    bool direct = false;
 };
 
 struct MhaW { float *in_w, *in_b, *out_w, *out_b; };
@@ -174,6 +177,28 @@ struct actmi_ctx {
     float* P(const std::string& key);
 };
 
+// error returns of the host code that works on a handle (`ctx` in scope): the first message wins
+#define HIPCHK(expr)                                                                            \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess) {                                                                 \
+            ctx->err = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
+            return ACTMI_E_LAUNCH;                                                              \
+        }                                                                                       \
+    } while (0)
+
+#define CHK(expr)                                                                               \
+    do {                                                                                        \
+        int _rc = (expr);                                                                       \
+        if (_rc != 0) {                                                                         \
+            if (ctx->err.empty()) ctx->err = std::string("failed: ") + #expr;                   \
+            return _rc < -5 ? ACTMI_E_LAUNCH : _rc;                                             \
+        }                                                                                       \
+    } while (0)
+
+// device memory owned by the handle (freed by engine_destroy)
+int dev_alloc(actmi_ctx* ctx, float** p, int64_t nfloats);
+
 int engine_create(const actmi_config* cfg, actmi_ctx** out);
 // forward GEMMs of a handle go through here: applies the handle's precision and swaps in pre-split weights
 // LayerNorm that follows a product (y = LN(C), optionally a second LN on top): when the product's contraction is split, the
@@ -186,6 +211,30 @@ struct LnFuse {
     const LnExtra* extra = nullptr;    // extra outputs of that LayerNorm (x + pos for the next attention block, the action head)
 };
 int ctx_gemm(actmi_ctx* ctx, GemmArgs a, hipStream_t st, int ws_half = -1, LnFuse* ln = nullptr);
+// a's contraction split S ways: every split stores a plain M x N slice into ws (groups * S slices), and ONE pass sums them in
+// slice order and applies a's epilogue (scale, bias, residual, activation) -- no float atomics, bitwise repeatable.  res = C
+// accumulates into C.  ln: that LayerNorm sums the slices itself where it can (ln->done), instead of the combine pass.
+int gemm_slices(actmi_ctx* ctx, const GemmArgs& a, int S, float* ws, hipStream_t st, LnFuse* ln = nullptr);
+
+// ---- launch descriptors shared by the inference forward, the training step and the op entry points (engine.hip)
+// y[M][N] = A[M][K] W[N][K]^T + bias
+GemmArgs linear_args(const float* A, int64_t lda, int M, int K, const float* W, int N, const float* bias, float* C, int64_t ldc);
+// one trunk convolution over the cameras [c0, c0 + nc) (in / out / res point at camera c0's camera-major NHWC map): the
+// implicit GEMM, and the direct kernel for a layer with cl.direct (its x_scale_dev is left to the caller)
+GemmArgs conv_gemm_args(const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out, const float* res, int relu);
+Conv3Args conv3_args(const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out, const float* res, int relu);
+// the stem (conv1 + FrozenBN + ReLU) of all cameras into ctx->act1
+Conv1Args stem_args(const actmi_ctx* ctx, const void* image, int fmt, int B);
+// self-attention of n tokens per sample over a packed [q | k | v] buffer [B][n][3D] -> out [B][n][D] (kpm, if any: [B][n])
+AttnArgs packed_self_attn_args(const actmi_ctx* ctx, const float* qkv, float* out, int B, int n);
+// cross-attention of the num_queries queries (q: [Q][D] shared by the batch, or [B][Q][D] per sample) against a [k | v] buffer
+// [B][N][2D] of the token sequence -> out [B][Q][D]
+AttnArgs cross_attn_args(const actmi_ctx* ctx, const float* q, bool per_sample_q, const float* kv, float* out, int B);
+// u8 -> float table [3][256] of the stem: x = float(v / 255.0 in f64) (imitate_episodes.py:212), then (x - mean) / std in f32
+// (policy.py:268-272) when normalize, else x alone
+void u8_lut(float* lut, bool normalize);
+// arena distance between same-named parameters of consecutive backbones (one launch per layer covers all cameras)
+int64_t backbone_cam_stride(actmi_ctx* ctx);
 // precision of the GEMMs issued while a training call is running (restored on every exit path)
 struct PrecScope {
     actmi_ctx* c;

@@ -14,24 +14,6 @@ namespace {
 
 thread_local std::string g_create_error;
 
-#define HIPCHK(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) {                                                                 \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
-            return ACTMI_E_LAUNCH;                                                              \
-        }                                                                                       \
-    } while (0)
-
-#define CHK(expr)                                                                               \
-    do {                                                                                        \
-        int _rc = (expr);                                                                       \
-        if (_rc != 0) {                                                                         \
-            if (ctx->err.empty()) ctx->err = std::string("failed: ") + #expr;                   \
-            return _rc < -5 ? ACTMI_E_LAUNCH : _rc;                                             \
-        }                                                                                       \
-    } while (0)
-
 int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
 
 void add_param(actmi_ctx* c, const std::string& key, std::vector<int64_t> shape, bool is_buffer) {
@@ -139,6 +121,8 @@ void build_spec(actmi_ctx* c) {
     add_param(c, "additional_pos_embed.weight", {2, D}, false);
 }
 
+}  // namespace
+
 int dev_alloc(actmi_ctx* ctx, float** p, int64_t nfloats) {
     void* q = nullptr;
     hipError_t e = hipMalloc(&q, (size_t)(nfloats > 0 ? nfloats : 1) * sizeof(float));
@@ -150,8 +134,6 @@ int dev_alloc(actmi_ctx* ctx, float** p, int64_t nfloats) {
     *p = reinterpret_cast<float*>(q);
     return 0;
 }
-
-}  // namespace
 
 int ctx_gemm(actmi_ctx* ctx, GemmArgs a, hipStream_t st, int ws_half, LnFuse* ln) {
     if (ln) ln->done = false;
@@ -201,38 +183,41 @@ int ctx_gemm(actmi_ctx* ctx, GemmArgs a, hipStream_t st, int ws_half, LnFuse* ln
         if (S > 8) S = 8;
         if (S > nk / sk_minnk) S = nk / sk_minnk;
         while (S >= 2 && (S - 1) * ((nk + S - 1) / S) >= nk) --S;              // every split must own a K tile
-        const int64_t slice = (int64_t)a.M * a.N;
-        if (S >= 2 && slice * groups * S <= ws_floats && (a.N & 3) == 0) {
-            GemmArgs p = a;
-            p.scale = p.bias = p.res = nullptr;
-            p.relu = 0;
-            p.C = ws;
-            p.ldc = a.N;
-            p.gC = slice * S;
-            p.splitk = S;
-            p.split_stride = slice;
-            int rc = launch_gemm(p, st, &ctx->err);
-            if (rc) return rc;
-            if (ln && groups == 1 && !a.scale && !a.relu && (!a.res || a.ldres == a.N)) {
-                // the LayerNorm that follows reads the slices itself: sum in slice order + bias + residual, as the combine does
-                rc = launch_layernorm(ws, a.res, 0, ln->w, ln->b, ln->w2, ln->b2, ln->out, a.M, a.N, ln->eps, st, &ctx->err, S, slice,
-                                      a.bias, ln->extra);
-                ln->done = rc == 0;
-                return rc;
-            }
-            SplitCombineArgs c{};
-            c.part = ws; c.nsplit = S; c.split_stride = slice; c.gP = slice * S; c.ldp = a.N;
-            c.scale = a.scale; c.bias = a.bias; c.gSB = a.gSB;
-            c.res = a.res; c.ldres = a.ldres; c.gRes = a.gRes;
-            c.relu = a.relu;
-            c.C = a.C; c.ldc = a.ldc; c.gC = a.gC;
-            c.M = a.M; c.N = a.N; c.groups = groups;
-            rc = launch_splitk_combine(c, st);
-            if (rc) ctx->err = "splitk combine launch failed";
-            return rc;
-        }
+        if (S >= 2 && (int64_t)a.M * a.N * groups * S <= ws_floats && (a.N & 3) == 0) return gemm_slices(ctx, a, S, ws, st, ln);
     }
     return launch_gemm(a, st, &ctx->err);
+}
+
+int gemm_slices(actmi_ctx* ctx, const GemmArgs& a, int S, float* ws, hipStream_t st, LnFuse* ln) {
+    const int groups = a.groups > 0 ? a.groups : 1;
+    const int64_t slice = (int64_t)a.M * a.N;
+    GemmArgs p = a;
+    p.scale = p.bias = p.res = nullptr;
+    p.relu = 0;
+    p.C = ws;
+    p.ldc = a.N;
+    p.gC = slice * S;
+    p.splitk = S;
+    p.split_stride = slice;
+    int rc = launch_gemm(p, st, &ctx->err);
+    if (rc) return rc;
+    if (ln && groups == 1 && !a.scale && !a.relu && (!a.res || a.ldres == a.N)) {
+        // the LayerNorm that follows reads the slices itself: sum in slice order + bias + residual, as the combine does
+        rc = launch_layernorm(ws, a.res, 0, ln->w, ln->b, ln->w2, ln->b2, ln->out, a.M, a.N, ln->eps, st, &ctx->err, S, slice,
+                              a.bias, ln->extra);
+        ln->done = rc == 0;
+        return rc;
+    }
+    SplitCombineArgs c{};
+    c.part = ws; c.nsplit = S; c.split_stride = slice; c.gP = slice * S; c.ldp = a.N;
+    c.scale = a.scale; c.bias = a.bias; c.gSB = a.gSB;
+    c.res = a.res; c.ldres = a.ldres; c.gRes = a.gRes;
+    c.relu = a.relu;
+    c.C = a.C; c.ldc = a.ldc; c.gC = a.gC;
+    c.M = a.M; c.N = a.N; c.groups = groups;
+    rc = launch_splitk_combine(c, st);
+    if (rc) ctx->err = "splitk combine launch failed";
+    return rc;
 }
 
 // scale of the split image of the parameter that contains address w (parameters are laid out in increasing offset order)
@@ -341,6 +326,8 @@ void resolve_layers(actmi_ctx* c) {
     }
 }
 
+}  // namespace
+
 GemmArgs linear_args(const float* A, int64_t lda, int M, int K, const float* W, int N, const float* bias, float* C,
                      int64_t ldc) {
     GemmArgs a;
@@ -350,7 +337,81 @@ GemmArgs linear_args(const float* A, int64_t lda, int M, int K, const float* W, 
     return a;
 }
 
-}  // namespace
+// feature maps and weights are camera-major: a camera range is a pointer offset plus a group count
+GemmArgs conv_gemm_args(const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out, const float* res, int relu) {
+    GemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.mode = 1;
+    a.A = in; a.H = cl.H; a.W = cl.W; a.Cin = cl.cin; a.KH = a.KW = cl.k; a.stride = cl.stride; a.pad = cl.pad;
+    a.Ho = cl.Ho; a.Wo = cl.Wo; a.img_stride = (int64_t)cl.H * cl.W * cl.cin;
+    a.M = B * cl.Ho * cl.Wo; a.N = cl.cout; a.K = cl.K;
+    a.Bw = cl.w + (int64_t)c0 * cl.cout * cl.K; a.ldb = cl.K;
+    a.scale = cl.scale + (int64_t)c0 * cl.cout; a.bias = cl.bias + (int64_t)c0 * cl.cout; a.res = res; a.ldres = cl.cout; a.relu = relu;
+    a.C = out; a.ldc = cl.cout;
+    a.groups = nc;
+    a.gA = (int64_t)B * cl.H * cl.W * cl.cin; a.gB = (int64_t)cl.cout * cl.K; a.gSB = cl.cout;
+    a.gC = (int64_t)a.M * cl.cout; a.gRes = a.gC;
+    return a;
+}
+
+Conv3Args conv3_args(const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out, const float* res, int relu) {
+    Conv3Args c;
+    c.x = in; c.w16 = cl.w16 + (int64_t)c0 * cl.cout * cl.K; c.scale = cl.scale + (int64_t)c0 * cl.cout;
+    c.bias = cl.bias + (int64_t)c0 * cl.cout; c.res = res; c.out = out;
+    c.G = nc; c.B = B; c.H = cl.H; c.W = cl.W; c.relu = relu; c.w_scale = cl.w16_scale;
+    return c;
+}
+
+Conv1Args stem_args(const actmi_ctx* ctx, const void* image, int fmt, int B) {
+    const actmi_config& g = ctx->cfg;
+    Conv1Args c1;
+    c1.image = image; c1.fmt = fmt; c1.lut = ctx->lut; c1.w = ctx->conv1_w; c1.scale = ctx->conv1_scale;
+    c1.bias = ctx->conv1_bias; c1.out = ctx->act1; c1.B = B; c1.C = g.num_cams; c1.H = g.image_h; c1.W = g.image_w;
+    c1.Ho = ctx->H1; c1.Wo = ctx->W1; c1.Cout = g.base_width;
+    c1.prec = ctx->gemm_prec;
+    c1.wimg = reinterpret_cast<const unsigned char*>(ctx->conv1_wimg);
+    c1.wscale = ctx->conv1_wscale;
+    return c1;
+}
+
+AttnArgs packed_self_attn_args(const actmi_ctx* ctx, const float* qkv, float* out, int B, int n) {
+    const int H = ctx->cfg.nheads, D = ctx->cfg.hidden_dim, hd = D / H;
+    AttnArgs at;
+    memset(&at, 0, sizeof(at));
+    at.Q = qkv; at.q_bs = (int64_t)n * 3 * D; at.q_rs = 3 * D;
+    at.K = qkv + D; at.k_bs = at.q_bs; at.k_rs = 3 * D;
+    at.V = qkv + 2 * D; at.v_bs = at.q_bs; at.v_rs = 3 * D;
+    at.O = out; at.o_bs = (int64_t)n * D; at.o_rs = D;
+    at.kpm_bs = n;
+    at.B = B; at.H = H; at.Nq = n; at.Nk = n; at.HD = hd; at.scale = 1.0f / sqrtf((float)hd);
+    return at;
+}
+
+AttnArgs cross_attn_args(const actmi_ctx* ctx, const float* q, bool per_sample_q, const float* kv, float* out, int B) {
+    const int H = ctx->cfg.nheads, D = ctx->cfg.hidden_dim, hd = D / H, Q = ctx->cfg.num_queries, N = ctx->N;
+    AttnArgs at;
+    memset(&at, 0, sizeof(at));
+    at.Q = q; at.q_bs = per_sample_q ? (int64_t)Q * D : 0; at.q_rs = D;
+    at.K = kv; at.k_bs = (int64_t)N * 2 * D; at.k_rs = 2 * D;
+    at.V = kv + D; at.v_bs = at.k_bs; at.v_rs = 2 * D;
+    at.O = out; at.o_bs = (int64_t)Q * D; at.o_rs = D;
+    at.B = B; at.H = H; at.Nq = Q; at.Nk = N; at.HD = hd; at.scale = 1.0f / sqrtf((float)hd);
+    return at;
+}
+
+void u8_lut(float* lut, bool normalize) {
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    for (int c = 0; c < 3; ++c)
+        for (int v = 0; v < 256; ++v) {
+            const float x = (float)((double)v / 255.0);
+            lut[c * 256 + v] = normalize ? (x - mean[c]) / stdv[c] : x;
+        }
+}
+
+int64_t backbone_cam_stride(actmi_ctx* ctx) {
+    const std::string p1 = "backbones." + std::to_string(ctx->cfg.num_cams > 1 ? 1 : 0) + ".0.body.";
+    return ctx->P(p1 + "conv1.weight") - ctx->P("backbones.0.0.body.conv1.weight");
+}
 
 float* actmi_ctx::P(const std::string& key) {
     auto it = index.find(key);
@@ -403,8 +464,7 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
     if (hipMemset(ctx->pbase, 0, ctx->ptotal * sizeof(float)) != hipSuccess) { ctx->err = "hipMemset failed"; return fail(ACTMI_E_LAUNCH); }
     {
         // forward precision of this handle: fp16-split products unless ACTMI_GEMM_PREC=f32 asks for the native fp32 MFMA
-        const char* e = getenv("ACTMI_GEMM_PREC");
-        ctx->gemm_prec = (e && e[0] == 'f' && e[1] == '3') ? ACTMI_PREC_F32 : ACTMI_PREC_F16X3;
+        ctx->gemm_prec = env_gemm_prec(ACTMI_PREC_F16X3);
         { const char* tp = getenv("ACTMI_TRAIN_PREC"); if (tp && tp[0] == 'b') ctx->train_prec = ACTMI_PREC_BF16; }
         if (ctx->ptotal & 3) { ctx->err = "parameter arena not a multiple of 4 floats"; return fail(ACTMI_E_LAUNCH); }
         if ((rc = dev_alloc(ctx, &ctx->p16base, ctx->ptotal))) return fail(rc);
@@ -470,7 +530,10 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
                 cin = cout; H = c1.Ho; W = c1.Wo;
             }
         }
-        for (auto& cl : ctx->convs) cl.K = cl.k * cl.k * cl.cin;
+        for (auto& cl : ctx->convs) {
+            cl.K = cl.k * cl.k * cl.cin;
+            cl.direct = cl.k == 3 && cl.stride == 1 && cl.pad == 1 && cl.cin == 64 && cl.cout == 64;
+        }
         // conv2 of every block with a downsample branch carries the branch in its own contraction (inference, f16x3)
         for (size_t i = 0; i + 2 < ctx->convs.size(); ++i) {
             ConvLayer& k2 = ctx->convs[i + 1];
@@ -596,8 +659,8 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
     // conv weights OIHW -> [cam][O][(r,s,c)]: one launch per layer over the cameras (same-named parameters of consecutive
     // backbones are a constant stride apart in the arena)
     {
-        const std::string p0 = "backbones.0.0.body.", p1 = "backbones." + std::to_string(C > 1 ? 1 : 0) + ".0.body.";
-        const int64_t cam_stride = ctx->P(p1 + "conv1.weight") - ctx->P(p0 + "conv1.weight");
+        const std::string p0 = "backbones.0.0.body.";
+        const int64_t cam_stride = backbone_cam_stride(ctx);
         CHK(launch_repack_conv_w(ctx->P(p0 + "conv1.weight"), ctx->conv1_w, C, w0, 3, 7, 7, cam_stride, (int64_t)w0 * 148, 148, st));
         for (auto& cl : ctx->convs)
             CHK(launch_repack_conv_w(ctx->P(p0 + cl.name + ".weight"), cl.w, C, cl.cout, cl.cin, cl.k, cl.k, cam_stride,
@@ -622,8 +685,7 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
         for (ConvLayer& cl : ctx->convs) {
             // K order of the image: channel blocks outer, taps inner, for the convolutions of the implicit-GEMM kernel (L2 reuse of
             // the input patch); the direct kernel of layer1 reads (r, s, c)
-            const bool direct = cl.k == 3 && cl.stride == 1 && cl.pad == 1 && cl.cin == 64 && cl.cout == 64;
-            cl.k_tap_inner = cl.k == 3 && (cl.cin % 32) == 0 && !direct &&
+            cl.k_tap_inner = cl.k == 3 && (cl.cin % 32) == 0 && !cl.direct &&
                              (int64_t)C * cl.cout * (cl.K + cl.Kx) <= ctx->splitk_ws_floats;
             if (cl.k_tap_inner) {
                 CHK(launch_permute_conv_k(cl.w, ctx->splitk_ws, (int64_t)C * cl.cout, cl.k * cl.k, cl.cin, cl.K, st));
@@ -671,16 +733,10 @@ int engine_finalize(actmi_ctx* ctx, hipStream_t st) {
     const int C = g.num_cams, D = g.hidden_dim;
     // 1. training scratch for the current precision (actmi_set_gemm_prec may have changed it since create)
     if (ctx->train) CHK(train_fit_prec(ctx));
-    // 2. u8 -> normalised float LUT with the reference's arithmetic:
-    //    x = float(v / 255.0 in f64)  (imitate_episodes.py:212), (x - mean) / std in f32 (policy.py:268-272)
+    // 2. u8 -> normalised float LUT with the reference's arithmetic
     {
-        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
         std::vector<float> lut(768);
-        for (int c = 0; c < 3; ++c)
-            for (int v = 0; v < 256; ++v) {
-                const float x = (float)((double)v / 255.0);
-                lut[c * 256 + v] = (x - mean[c]) / stdv[c];
-            }
+        u8_lut(lut.data(), true);
         HIPCHK(hipMemcpyAsync(ctx->lut, lut.data(), 768 * sizeof(float), hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
     }
@@ -837,13 +893,7 @@ static int run_branches(actmi_ctx* ctx, int nb, hipStream_t st, Body body) {
 int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream_t st) {
     const actmi_config& g = ctx->cfg;
     const int C = g.num_cams, w0 = g.base_width, D = g.hidden_dim;
-    Conv1Args c1;
-    c1.image = image; c1.fmt = fmt; c1.lut = ctx->lut; c1.w = ctx->conv1_w; c1.scale = ctx->conv1_scale;
-    c1.bias = ctx->conv1_bias; c1.out = ctx->act1; c1.B = B; c1.C = C; c1.H = g.image_h; c1.W = g.image_w;
-    c1.Ho = ctx->H1; c1.Wo = ctx->W1; c1.Cout = w0;
-    c1.prec = ctx->gemm_prec;
-    c1.wimg = reinterpret_cast<const unsigned char*>(ctx->conv1_wimg);
-    c1.wscale = ctx->conv1_wscale;
+    Conv1Args c1 = stem_args(ctx, image, fmt, B);
     // inference never needs conv1's own map: the stem emits the vertical half of the max pool (half the bytes) and a
     // row-wise pass finishes it.  Same maxima, so the result is bit-identical to conv1 -> 3x3 pool.
     const bool vpool = ctx->conv1_vpool && ctx->stop_stage != "conv1" && ctx->gemm_prec == ACTMI_PREC_F16X3 && (ctx->H1 & 1) == 0 &&
@@ -862,10 +912,6 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
     auto run_conv_on = [&](const ConvLayer& cl, const float* in, float* out, const float* res, int relu, hipStream_t cs, int c0,
                            int nc, int half) -> int {
         // (in / out / res already point at the range's first camera: run_layers)
-        const int64_t in_cam = (int64_t)B * cl.H * cl.W * cl.cin;
-        const int64_t w_cam = (int64_t)cl.cout * cl.K;
-        const float* scale = cl.scale + (int64_t)c0 * cl.cout;
-        const float* bias = cl.bias + (int64_t)c0 * cl.cout;
         const int cl_index = (int)(&cl - ctx->convs.data());
         if (ctx->calibrating) {
             // calibration forward (actmi_finalize): measure this layer's input, fix its pre-scale, THEN run the layer with it
@@ -876,25 +922,13 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
             HIPCHK(hipMemcpyAsync(ctx->act_scale_dev + cl_index, &cl.a_scale, sizeof(float), hipMemcpyHostToDevice, cs));
             HIPCHK(hipStreamSynchronize(cs));
         }
-        if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.k == 3 && cl.stride == 1 && cl.pad == 1 && cl.cin == 64 && cl.cout == 64) {
+        if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.direct) {
             // layer1: direct convolution over an LDS-resident patch (the im2col GEMM is L2-traffic bound at 64 channels)
-            Conv3Args c3;
-            c3.x = in; c3.w16 = cl.w16 + c0 * w_cam; c3.scale = scale; c3.bias = bias; c3.res = res; c3.out = out;
-            c3.G = nc; c3.B = B; c3.H = cl.H; c3.W = cl.W; c3.relu = relu; c3.w_scale = cl.w16_scale;
+            Conv3Args c3 = conv3_args(cl, B, c0, nc, in, out, res, relu);
             if (cl.a_scale != 1.f) c3.x_scale_dev = ctx->act_scale_dev + cl_index;
             return launch_conv3x3_c64(c3, cs, &ctx->err);
         }
-        GemmArgs a;
-        memset(&a, 0, sizeof(a));
-        a.mode = 1;
-        a.A = in; a.H = cl.H; a.W = cl.W; a.Cin = cl.cin; a.KH = a.KW = cl.k; a.stride = cl.stride; a.pad = cl.pad;
-        a.Ho = cl.Ho; a.Wo = cl.Wo; a.img_stride = (int64_t)cl.H * cl.W * cl.cin;
-        a.M = B * cl.Ho * cl.Wo; a.N = cl.cout; a.K = cl.K;
-        a.Bw = cl.w + c0 * w_cam; a.ldb = cl.K; a.scale = scale; a.bias = bias; a.res = res; a.ldres = cl.cout; a.relu = relu;
-        a.C = out; a.ldc = cl.cout;
-        a.groups = nc;
-        a.gA = in_cam; a.gB = w_cam; a.gSB = cl.cout;
-        a.gC = (int64_t)a.M * cl.cout; a.gRes = a.gC;
+        GemmArgs a = conv_gemm_args(cl, B, c0, nc, in, out, res, relu);
         if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.a_scale != 1.f) a.a_scale = cl.a_scale;
         return ctx_gemm(ctx, a, cs, half);
     };
@@ -1041,19 +1075,13 @@ int engine_encoder_layer(actmi_ctx* ctx, const EncW& w, const TView& V, const fl
                          hipStream_t st, bool xp_in, bool xp_out) {
     float* x = V.X;
     const actmi_config& g = ctx->cfg;
-    const int D = g.hidden_dim, F = g.dim_feedforward, M = B * n, hd = D / g.nheads;
+    const int D = g.hidden_dim, F = g.dim_feedforward, M = B * n;
     GemmArgs qkv = linear_args(x, D, M, D, w.attn.in_w, 3 * D, w.attn.in_b, V.QKV, 3 * D);
     if (xp_in) { qkv.A_alt = V.XP; qkv.alt_ncols = 2 * D; }                      // q = k = x + pos (a matrix already), v = x
     else { qkv.A_add = pos; qkv.ld_add = D; qkv.add_mod = n; qkv.add_ncols = 2 * D; }     // q = k = x + pos, v = x
     CHK(ctx_gemm(ctx, qkv, st, V.half));
-    AttnArgs at;
-    memset(&at, 0, sizeof(at));
-    at.Q = V.QKV; at.q_bs = (int64_t)n * 3 * D; at.q_rs = 3 * D;
-    at.K = V.QKV + D; at.k_bs = at.q_bs; at.k_rs = 3 * D;
-    at.V = V.QKV + 2 * D; at.v_bs = at.q_bs; at.v_rs = 3 * D;
-    at.O = V.ATT; at.o_bs = (int64_t)n * D; at.o_rs = D;
-    at.kpm = kpm; at.kpm_bs = n;
-    at.B = B; at.H = g.nheads; at.Nq = n; at.Nk = n; at.HD = hd; at.scale = 1.0f / sqrtf((float)hd);
+    AttnArgs at = packed_self_attn_args(ctx, V.QKV, V.ATT, B, n);
+    at.kpm = kpm;
     at.ws = V.attn_ws; at.ws_floats = V.attn_ws_floats;
     at.prec = ctx->gemm_prec;
     CHK(launch_attention(at, st, &ctx->err));
@@ -1080,20 +1108,14 @@ int engine_encoder_layer(actmi_ctx* ctx, const EncW& w, const TView& V, const fl
 // decoder layer 0 with the constant query path + heads (transformer.py:274-295,175; detr_vae.py:245,252)
 int engine_decoder_infer(actmi_ctx* ctx, const TView& V, int B, float* a_hat, hipStream_t st, bool xp_in) {
     const actmi_config& g = ctx->cfg;
-    const int D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N, hd = D / g.nheads;
+    const int D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N;
     const DecW& d = ctx->dec[0];
     float* KV = V.QKV;   // [B*N][2D]
     GemmArgs kv = linear_args(V.X, D, B * N, D, d.cross.in_w + (int64_t)D * D, 2 * D, d.cross.in_b + D, KV, 2 * D);
     if (xp_in) { kv.A_alt = V.XP; kv.alt_ncols = D; }                                   // k = memory + pos (a matrix already), v = memory
     else { kv.A_add = ctx->pos_tokens; kv.ld_add = D; kv.add_mod = N; kv.add_ncols = D; }      // k = memory + pos, v = memory
     CHK(ctx_gemm(ctx, kv, st, V.half));
-    AttnArgs at;
-    memset(&at, 0, sizeof(at));
-    at.Q = ctx->dec_q; at.q_bs = 0; at.q_rs = D;
-    at.K = KV; at.k_bs = (int64_t)N * 2 * D; at.k_rs = 2 * D;
-    at.V = KV + D; at.v_bs = at.k_bs; at.v_rs = 2 * D;
-    at.O = V.dO; at.o_bs = (int64_t)Q * D; at.o_rs = D;
-    at.B = B; at.H = g.nheads; at.Nq = Q; at.Nk = N; at.HD = hd; at.scale = 1.0f / sqrtf((float)hd);
+    AttnArgs at = cross_attn_args(ctx, ctx->dec_q, false, KV, V.dO, B);
     at.ws = V.attn_ws; at.ws_floats = V.attn_ws_floats;
     at.prec = ctx->gemm_prec;
     CHK(launch_attention(at, st, &ctx->err));

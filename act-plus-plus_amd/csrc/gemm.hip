@@ -1149,6 +1149,12 @@ int launch_gemm_bf16(int amode, int bmode, bool has_add, const GemmArgs& a, hipS
 #else
 int launch_gemm_bf16(int amode, int bmode, bool has_add, const GemmArgs& a, hipStream_t st);
 
+int env_gemm_prec(int unset) {
+    const char* e = getenv("ACTMI_GEMM_PREC");
+    if (!e) return unset;
+    return (e[0] == 'f' && e[1] == '3') ? ACTMI_PREC_F32 : ACTMI_PREC_F16X3;
+}
+
 int launch_gemm(const GemmArgs& a_in, hipStream_t st, std::string* err) {
     GemmArgs a = a_in;
     if (a.groups <= 0) a.groups = 1;
@@ -1214,11 +1220,7 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t st, std::string* err) {
     } else return fail("bad tb");
     int rc;
     // precision: explicit in the descriptor, else ACTMI_GEMM_PREC (f32 | f16x3), else the library default
-    static const int env_prec = [] {
-        const char* e = getenv("ACTMI_GEMM_PREC");
-        if (!e) return ACTMI_PREC_DEFAULT_IS;
-        return (e[0] == 'f' && e[1] == '3') ? ACTMI_PREC_F32 : ACTMI_PREC_F16X3;
-    }();
+    static const int env_prec = env_gemm_prec(ACTMI_PREC_DEFAULT_IS);
     const int prec = a.prec ? a.prec : env_prec;
     if (prec != ACTMI_PREC_F32 && prec != ACTMI_PREC_F16X3 && prec != ACTMI_PREC_BF16) return fail("bad prec");
     if (a.b_split && (prec != ACTMI_PREC_F16X3 || bmode != B_N || !(amode == A_N || amode == A_CONV)))

@@ -17,35 +17,6 @@
 
 namespace {
 
-#define CHK(expr)                                                                               \
-    do {                                                                                        \
-        int _rc = (expr);                                                                       \
-        if (_rc != 0) {                                                                         \
-            if (ctx->err.empty()) ctx->err = std::string("failed: ") + #expr;                   \
-            return _rc < -5 ? ACTMI_E_LAUNCH : _rc;                                             \
-        }                                                                                       \
-    } while (0)
-
-#define HIPCHK(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) {                                                                 \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
-            return ACTMI_E_LAUNCH;                                                              \
-        }                                                                                       \
-    } while (0)
-
-int talloc(actmi_ctx* ctx, float** p, int64_t n) {
-    void* q = nullptr;
-    if (hipMalloc(&q, (size_t)(n > 0 ? n : 1) * sizeof(float)) != hipSuccess) {
-        ctx->err = "hipMalloc failed (training buffers)";
-        return ACTMI_E_NOMEM;
-    }
-    ctx->allocs.push_back(q);
-    *p = reinterpret_cast<float*>(q);
-    return 0;
-}
-
 GemmArgs G0() {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
@@ -68,24 +39,9 @@ int tgemm(actmi_ctx* ctx, GemmArgs a, hipStream_t st) {
         while (S >= 2 && (S - 1) * ((nk + S - 1) / S) >= nk) --S;              // every split must own a K tile
         const int64_t slice = (int64_t)a.M * a.N;
         while (S >= 2 && slice * groups * S > T->det_ws_floats) --S;
-        if (S >= 2 && (a.N & 3) == 0) {
-            GemmArgs p = a;
-            p.C = T->det_ws; p.ldc = a.N; p.gC = slice * S;
-            p.splitk = S; p.split_stride = slice;
-            p.res = nullptr;
-            int rc = launch_gemm(p, st, &ctx->err);
-            if (rc) return rc;
-            SplitCombineArgs c{};
-            c.part = T->det_ws; c.nsplit = S; c.split_stride = slice; c.gP = slice * S; c.ldp = a.N;
-            c.res = a.C; c.ldres = a.ldc; c.gRes = a.gC;                        // accumulate: C = C + sum of slices
-            c.C = a.C; c.ldc = a.ldc; c.gC = a.gC;
-            c.M = a.M; c.N = a.N; c.groups = groups;
-            rc = launch_splitk_combine(c, st);
-            if (rc) ctx->err = "splitk combine launch failed";
-            return rc;
-        }
+        a.res = a.C; a.ldres = a.ldc; a.gRes = a.gC;    // accumulate: C = C + A B
+        if (S >= 2 && (a.N & 3) == 0) return gemm_slices(ctx, a, S, T->det_ws, st);
         a.splitk = 0;                                   // cannot slice: one pass over the whole contraction, C += through res
-        a.res = a.C; a.ldres = a.ldc; a.gRes = a.gC;
     }
     return launch_gemm(a, st, &ctx->err);
 }
@@ -183,8 +139,7 @@ int pick_splitk(int M, int N, int groups, int K) {
 // y[M][N] = x[M][K] W[N][K]^T + b (+res) (relu)
 int lin_fwd(actmi_ctx* ctx, const float* x, int64_t ldx, int M, int K, const float* W, int N, const float* b, float* y,
             int64_t ldy, const float* res, int relu, hipStream_t st, float drop_p = 0.f, uint64_t drop_seed = 0) {
-    GemmArgs a = G0();
-    a.A = x; a.lda = ldx; a.M = M; a.K = K; a.N = N; a.Bw = W; a.ldb = K; a.bias = b; a.C = y; a.ldc = ldy;
+    GemmArgs a = linear_args(x, ldx, M, K, W, N, b, y, ldy);
     a.res = res; a.ldres = ldy; a.relu = relu; a.drop_p = drop_p; a.drop_seed = drop_seed;
     return tgemm(ctx, a, st);
 }
@@ -228,39 +183,19 @@ int lin_wgrad(actmi_ctx* ctx, const float* dy, int64_t lddy, int M, int N, const
 }
 
 // ---- attention backward through materialised probabilities (batched MFMA products) -------------------------------
-struct AttnBwd {
-    const float *Q, *K, *V, *O, *dO, *lse;
-    int64_t q_bs, q_rs, k_bs, k_rs, v_bs, v_rs;     // forward operand strides (q_bs = 0: shared queries)
-    float *dQ, *dK, *dV;
-    int64_t dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs;
-    const uint8_t* kpm; int64_t kpm_bs;
-    int B, H, Nq, Nk, HD;
-    float drop_p; uint64_t drop_seed;
-    unsigned* out_amax;        // optional: one bits word that the dQ, dK and dV products all raise (shared operand scale of gQKV)
-};
-
 // long sequences (the encoder's 1202 x 1202 self-attention) take the fused kernels of attn_bwd.hip: no P / dS buffers
 static bool attn_bwd_fused(const actmi_ctx* ctx, int Nq, int Nk, int HD, bool shared_q) {
     return ctx->gemm_prec == ACTMI_PREC_F16X3 && !shared_q && Nq >= 256 && Nk >= 256 && (HD == 64 || HD == 32 || HD == 16);
 }
 
-int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
+// t: everything but delta, dO_scale and the dO strides (dO and O are dense [B][Nq][D]); t.amax_out (optional): one bits word that
+// the dQ, dK and dV products all raise
+int attn_bwd(actmi_ctx* ctx, AttnBwdArgs t, const float* O, hipStream_t st) {
     TrainState& T = *ctx->train;
     const int G = t.B * t.H, D = t.H * t.HD;
     if (attn_bwd_fused(ctx, t.Nq, t.Nk, t.HD, t.q_bs == 0)) {
-        CHK(launch_attn_delta(t.dO, t.O, T.delta, t.B, t.H, t.Nq, t.HD, st));
-        AttnBwdArgs a{};
-        a.Q = t.Q; a.K = t.K; a.V = t.V; a.dO = t.dO; a.lse = t.lse; a.delta = T.delta;
-        a.dO_scale = dyn_scale(ctx, t.dO, D, t.B * t.Nq, D, st);
-        a.dQ = t.dQ; a.dK = t.dK; a.dV = t.dV;
-        a.q_bs = t.q_bs; a.q_rs = t.q_rs; a.k_bs = t.k_bs; a.k_rs = t.k_rs; a.v_bs = t.v_bs; a.v_rs = t.v_rs;
-        a.do_bs = (int64_t)t.Nq * D; a.do_rs = D;
-        a.dq_bs = t.dq_bs; a.dq_rs = t.dq_rs; a.dk_bs = t.dk_bs; a.dk_rs = t.dk_rs; a.dv_bs = t.dv_bs; a.dv_rs = t.dv_rs;
-        a.kpm = t.kpm; a.kpm_bs = t.kpm_bs;
-        a.B = t.B; a.H = t.H; a.Nq = t.Nq; a.Nk = t.Nk; a.HD = t.HD;
-        a.scale = 1.0f / sqrtf((float)t.HD); a.drop_p = t.drop_p; a.drop_seed = t.drop_seed;
-        a.amax_out = t.out_amax;
-        return launch_attention_bwd(a, st, &ctx->err);
+        t.dO_scale = dyn_scale(ctx, t.dO, D, t.B * t.Nq, D, st);
+        return launch_attention_bwd_dense(t, O, T.delta, st, &ctx->err);
     }
     const int ldp = (t.Nk + 3) & ~3;
     const float scale = 1.0f / sqrtf((float)t.HD);
@@ -283,7 +218,7 @@ int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
     s.epi_colkill = t.kpm; s.gColkill = t.kpm_bs;
     CHK(tgemm(ctx, s, st));
     if (ldp != t.Nk) CHK(launch_zero_cols(P, (int64_t)G * t.Nq, ldp, t.Nk, st));
-    CHK(launch_attn_delta(t.dO, t.O, T.delta, t.B, t.H, t.Nq, t.HD, st));
+    CHK(launch_attn_delta(t.dO, O, T.delta, t.B, t.H, t.Nq, t.HD, st));
     // dV[key][d] = sum_q Pd[q][key] dO[q][d]   (Pd = dropped weights; staged in the dP buffer before dP overwrites it)
     const float* Pv = P;
     if (t.drop_p > 0.f) {
@@ -297,7 +232,7 @@ int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
     v.a_scale = 256.f;          // probabilities (<= 1/(1-p)) are mostly ~1/Nk
     const float* dO_sc = dyn_scale(ctx, t.dO, D, t.B * t.Nq, D, st);
     v.b_scale_dev = dO_sc;
-    v.amax_out = t.out_amax;
+    v.amax_out = t.amax_out;
     CHK(tgemm(ctx, v, st));
     // dP = dO V^T
     GemmArgs d = G0();
@@ -325,7 +260,7 @@ int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
     q.gA = pg * t.H; q.gA2 = pg; q.gB = t.k_bs; q.gB2 = t.HD; q.gC = t.dq_bs; q.gC2 = t.HD;
     const float* dS_sc = dyn_scale(ctx, dP, ldp, G * t.Nq, t.Nk, st);
     q.a_scale_dev = dS_sc;
-    q.amax_out = t.out_amax;
+    q.amax_out = t.amax_out;
     CHK(tgemm(ctx, q, st));
     // dK[key][d] = sum_q dS[q][key] Q[q][d]
     GemmArgs k = G0();
@@ -333,7 +268,7 @@ int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
     k.C = t.dK; k.ldc = t.dk_rs; k.groups = G; k.groups_inner = t.H;
     k.gA = pg * t.H; k.gA2 = pg; k.gB = t.q_bs; k.gB2 = t.HD; k.gC = t.dk_bs; k.gC2 = t.HD;
     k.a_scale_dev = dS_sc;
-    k.amax_out = t.out_amax;
+    k.amax_out = t.amax_out;
     CHK(tgemm(ctx, k, st));
     return 0;
 }
@@ -342,20 +277,12 @@ int attn_bwd(actmi_ctx* ctx, const AttnBwd& t, hipStream_t st) {
 int enc_fwd(actmi_ctx* ctx, const EncW& w, EncSave& s, float* out, const float* pos, int B, int n, const uint8_t* kpm,
             const Drop& dr, hipStream_t st) {
     const actmi_config& g = ctx->cfg;
-    const int D = g.hidden_dim, F = g.dim_feedforward, M = B * n, hd = D / g.nheads;
-    GemmArgs qkv = G0();
-    qkv.A = s.x_in; qkv.lda = D; qkv.M = M; qkv.K = D; qkv.Bw = w.attn.in_w; qkv.ldb = D; qkv.N = 3 * D;
-    qkv.bias = w.attn.in_b; qkv.C = s.QKV; qkv.ldc = 3 * D;
+    const int D = g.hidden_dim, F = g.dim_feedforward, M = B * n;
+    GemmArgs qkv = linear_args(s.x_in, D, M, D, w.attn.in_w, 3 * D, w.attn.in_b, s.QKV, 3 * D);
     qkv.A_add = pos; qkv.ld_add = D; qkv.add_mod = n; qkv.add_ncols = 2 * D;
     CHK(tgemm(ctx, qkv, st));
-    AttnArgs at;
-    memset(&at, 0, sizeof(at));
-    at.Q = s.QKV; at.q_bs = (int64_t)n * 3 * D; at.q_rs = 3 * D;
-    at.K = s.QKV + D; at.k_bs = at.q_bs; at.k_rs = 3 * D;
-    at.V = s.QKV + 2 * D; at.v_bs = at.q_bs; at.v_rs = 3 * D;
-    at.O = s.ATT; at.o_bs = (int64_t)n * D; at.o_rs = D;
-    at.kpm = kpm; at.kpm_bs = n; at.lse = s.lse;
-    at.B = B; at.H = g.nheads; at.Nq = n; at.Nk = n; at.HD = hd; at.scale = 1.0f / sqrtf((float)hd);
+    AttnArgs at = packed_self_attn_args(ctx, s.QKV, s.ATT, B, n);
+    at.kpm = kpm; at.lse = s.lse;
     at.ws = ctx->attn_ws; at.ws_floats = ctx->attn_ws_floats;
     at.prec = ctx->gemm_prec;
     at.drop_p = dr.p; at.drop_seed = dr.s(0);
@@ -397,10 +324,9 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
     CHK(lin_dgrad(ctx, dz1, D, M, D, w.attn.out_w, D, dATT, D, nullptr, nullptr, st, 1.f, true));            // dATT = dO of the attention
     CHK(lin_wgrad(ctx, dz1, D, M, D, s.ATT, D, D, nullptr, 0, Gp(w.attn.out_w), Gp(w.attn.out_b), st));
     // attention
-    AttnBwd t;
-    memset(&t, 0, sizeof(t));
+    AttnBwdArgs t{};
     const int64_t bs = (int64_t)n * 3 * D;
-    t.Q = s.QKV; t.K = s.QKV + D; t.V = s.QKV + 2 * D; t.O = s.ATT; t.dO = dATT; t.lse = s.lse;
+    t.Q = s.QKV; t.K = s.QKV + D; t.V = s.QKV + 2 * D; t.dO = dATT; t.lse = s.lse;
     t.q_bs = t.k_bs = t.v_bs = bs; t.q_rs = t.k_rs = t.v_rs = 3 * D;
     t.dQ = gQKV; t.dK = gQKV + D; t.dV = gQKV + 2 * D;
     t.dq_bs = t.dk_bs = t.dv_bs = bs; t.dq_rs = t.dk_rs = t.dv_rs = 3 * D;
@@ -409,8 +335,8 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
     // ONE operand scale for gQKV = [dQ | dK | dV]: the three products that write it raise the same bits word, and the data
     // gradient and the two weight gradients below all use it (three strided amax passes over gQKV otherwise)
     float* qkv_slot = scale_slot(ctx);
-    t.out_amax = qkv_slot ? reinterpret_cast<unsigned*>(qkv_slot + 1) : nullptr;
-    CHK(attn_bwd(ctx, t, st));
+    t.amax_out = qkv_slot ? reinterpret_cast<unsigned*>(qkv_slot + 1) : nullptr;
+    CHK(attn_bwd(ctx, t, s.ATT, st));
     if (qkv_slot && launch_pow2_from_bits(qkv_slot, st) != 0) return ACTMI_E_LAUNCH;
     // in_proj: dIn = dQKV W_in + dY1 ; dW rows [0,2D) see x+pos, rows [2D,3D) see x
     CHK(lin_dgrad(ctx, gQKV, 3 * D, M, 3 * D, w.attn.in_w, D, dIn, D, gA, nullptr, st, 1.f, false, qkv_slot));
@@ -434,22 +360,13 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
 int conv_wgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, const float* x, int B, hipStream_t st) {
     TrainState& T = *ctx->train;
     const int C = ctx->cfg.num_cams;
-    if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.cin == 64 && cl.cout == 64 && cl.k == 3 && cl.stride == 1 && cl.pad == 1 &&
-        T.det_ws && T.det_ws_floats >= (int64_t)C * 64 * 576) {
-        // layer1: the direct kernel (wgrad3.hip) + fixed-order sum of its per-workgroup partials into the packed gradient
+    if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.direct && T.det_ws && T.det_ws_floats >= (int64_t)C * 64 * 576) {
+        // layer1: the direct kernel (wgrad3.hip), accumulating into the packed gradient like autograd
         const float* sc = dyn_scale(ctx, dys, cl.cout, C * B * cl.Ho * cl.Wo, cl.cout, st);
-        int nwg = 0;
-        if (launch_wgrad3x3_c64(dys, x, T.det_ws, T.det_ws_floats, sc, C, B, cl.H, cl.W, &nwg, st) != 0) {
+        if (launch_wgrad3x3_c64(dys, x, T.conv_gw[li], 1, T.det_ws, T.det_ws_floats, sc, C, B, cl.H, cl.W, st) != 0) {
             ctx->err = "wgrad3x3_c64 launch failed";
             return ACTMI_E_LAUNCH;
         }
-        SplitCombineArgs c{};
-        const int64_t slice = (int64_t)64 * 576;
-        c.part = T.det_ws; c.nsplit = nwg; c.split_stride = slice; c.gP = slice * nwg; c.ldp = 576;
-        c.res = T.conv_gw[li]; c.ldres = cl.K; c.gRes = (int64_t)cl.cout * cl.K;         // accumulate like autograd
-        c.C = T.conv_gw[li]; c.ldc = cl.K; c.gC = (int64_t)cl.cout * cl.K;
-        c.M = 64; c.N = 576; c.groups = C;
-        if (launch_splitk_combine(c, st) != 0) { ctx->err = "splitk combine launch failed"; return ACTMI_E_LAUNCH; }
         return 0;
     }
     GemmArgs a = G0();
@@ -467,7 +384,7 @@ int conv_wgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, co
 // layer1's data gradients (64 -> 64 channels, 3x3 / s1 / p1) run as a forward convolution of dY with the flipped, transposed
 // weights on the direct kernel of the inference path (conv3.hip: LDS-resident patch, 1.3 ms against the gather GEMM's 2.5 ms)
 bool dgrad_direct(const actmi_ctx* ctx, const ConvLayer& cl) {
-    return ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.cin == 64 && cl.cout == 64 && cl.k == 3 && cl.stride == 1 && cl.pad == 1;
+    return ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.direct;
 }
 
 // dx[C][B][H][W][cin] = dgrad(dys) (+res) , then masked by (mask > 0) and multiplied by scale[cin] (previous BN)
@@ -511,7 +428,7 @@ int train_create(actmi_ctx* ctx) {
     const int B = g.max_batch, C = g.num_cams, D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N,
               w0 = g.base_width, H = g.nheads, L = g.latent_dim, A = g.action_dim;
     int rc;
-#define TA(ptr, n) if ((rc = talloc(ctx, &(ptr), (n)))) return rc
+#define TA(ptr, n) if ((rc = dev_alloc(ctx, &(ptr), (n)))) return rc
     TA(T.gbase, ctx->ptotal); TA(T.mbase, ctx->ptotal); TA(T.vbase, ctx->ptotal);
     if (hipMemset(T.gbase, 0, ctx->ptotal * 4) != hipSuccess || hipMemset(T.mbase, 0, ctx->ptotal * 4) != hipSuccess ||
         hipMemset(T.vbase, 0, ctx->ptotal * 4) != hipSuccess) { ctx->err = "hipMemset failed"; return ACTMI_E_LAUNCH; }
@@ -642,13 +559,13 @@ int train_fit_prec(actmi_ctx* ctx) {
     if ((int64_t)B * H * prow != T.P_floats) {
         release(T.Pbuf); release(T.dPbuf);
         T.P_floats = 0;
-        if ((rc = talloc(ctx, &T.Pbuf, (int64_t)B * H * prow)) || (rc = talloc(ctx, &T.dPbuf, (int64_t)B * H * prow))) return rc;
+        if ((rc = dev_alloc(ctx, &T.Pbuf, (int64_t)B * H * prow)) || (rc = dev_alloc(ctx, &T.dPbuf, (int64_t)B * H * prow))) return rc;
         T.P_floats = (int64_t)B * H * prow;
     }
     for (size_t i = 0; i < ctx->convs.size(); ++i) {
         const ConvLayer& cl = ctx->convs[i];
         if (!dgrad_direct(ctx, cl) && T.conv_wd16[i]) release(T.conv_wd16[i]);
-        if (dgrad_direct(ctx, cl) && !T.conv_wd16[i] && (rc = talloc(ctx, &T.conv_wd16[i], (int64_t)C * cl.cin * cl.k * cl.k * cl.cout)))
+        if (dgrad_direct(ctx, cl) && !T.conv_wd16[i] && (rc = dev_alloc(ctx, &T.conv_wd16[i], (int64_t)C * cl.cin * cl.k * cl.k * cl.cout)))
             return rc;
     }
     return 0;
@@ -688,9 +605,9 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
         CHK(launch_fill_rows(T.Xc, D, (int64_t)n * D, ctx->P("cls_embed.weight"), 0, B, D, st));
         CHK(launch_small_linear(qpos, S, ctx->P("encoder_joint_proj.weight"), ctx->P("encoder_joint_proj.bias"), T.Xc + D,
                                 (int64_t)n * D, B, D, S, st));
-        GemmArgs ap = G0();
-        ap.A = T.actions; ap.lda = A; ap.M = B * Q; ap.K = A; ap.Bw = ctx->P("encoder_action_proj.weight"); ap.ldb = A; ap.N = D;
-        ap.bias = ctx->P("encoder_action_proj.bias"); ap.C = T.Xc; ap.ldc = D; ap.rowmap = T.cmap;
+        GemmArgs ap = linear_args(T.actions, A, B * Q, A, ctx->P("encoder_action_proj.weight"), D, ctx->P("encoder_action_proj.bias"),
+                                  T.Xc, D);
+        ap.rowmap = T.cmap;
         CHK(tgemm(ctx, ap, st));
         for (int l = 0; l < g.enc_layers; ++l) {
             float* out = (l + 1 < g.enc_layers) ? T.cv[l + 1].x_in : T.cv_out;
@@ -716,34 +633,13 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
 
     // ---- backbone with saved maps
     CHK(launch_normalize_pad(image, fmt, ctx->lut, T.xn4, B, C, g.image_h, g.image_w, st));
-    {
-        Conv1Args c1;
-        c1.image = image; c1.fmt = fmt; c1.lut = ctx->lut; c1.w = ctx->conv1_w; c1.scale = ctx->conv1_scale;
-        c1.bias = ctx->conv1_bias; c1.out = ctx->act1; c1.B = B; c1.C = C; c1.H = g.image_h; c1.W = g.image_w;
-        c1.Ho = ctx->H1; c1.Wo = ctx->W1; c1.Cout = w0;
-        c1.prec = ctx->gemm_prec;
-        c1.wimg = reinterpret_cast<const unsigned char*>(ctx->conv1_wimg);
-        c1.wscale = ctx->conv1_wscale;
-        CHK(launch_conv1(c1, st, &ctx->err));
-        CHK(launch_maxpool_idx(ctx->act1, T.pool, T.pool_arg, C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st));
-    }
+    CHK(launch_conv1(stem_args(ctx, image, fmt, B), st, &ctx->err));
+    CHK(launch_maxpool_idx(ctx->act1, T.pool, T.pool_arg, C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st));
+    // (no activation pre-scales: those are calibrated for the inference forward)
     auto run_conv = [&](const ConvLayer& cl, const float* in, float* out, const float* res, int relu) -> int {
-        if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.k == 3 && cl.stride == 1 && cl.pad == 1 && cl.cin == 64 && cl.cout == 64) {
-            Conv3Args c3;           // layer1: direct convolution (conv3.hip), as in the inference engine
-            c3.x = in; c3.w16 = cl.w16; c3.scale = cl.scale; c3.bias = cl.bias; c3.res = res; c3.out = out;
-            c3.G = C; c3.B = B; c3.H = cl.H; c3.W = cl.W; c3.relu = relu; c3.w_scale = cl.w16_scale;
-            return launch_conv3x3_c64(c3, st, &ctx->err);
-        }
-        GemmArgs a = G0();
-        a.mode = 1;
-        a.A = in; a.H = cl.H; a.W = cl.W; a.Cin = cl.cin; a.KH = a.KW = cl.k; a.stride = cl.stride; a.pad = cl.pad;
-        a.Ho = cl.Ho; a.Wo = cl.Wo; a.img_stride = (int64_t)cl.H * cl.W * cl.cin;
-        a.M = B * cl.Ho * cl.Wo; a.N = cl.cout; a.K = cl.K;
-        a.Bw = cl.w; a.ldb = cl.K; a.scale = cl.scale; a.bias = cl.bias; a.res = res; a.ldres = cl.cout; a.relu = relu;
-        a.C = out; a.ldc = cl.cout; a.groups = C;
-        a.gA = (int64_t)B * cl.H * cl.W * cl.cin; a.gB = (int64_t)cl.cout * cl.K; a.gSB = cl.cout;
-        a.gC = (int64_t)a.M * cl.cout; a.gRes = a.gC;
-        return tgemm(ctx, a, st);
+        if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.direct)      // layer1: direct convolution (conv3.hip), as in the inference engine
+            return launch_conv3x3_c64(conv3_args(cl, B, 0, C, in, out, res, relu), st, &ctx->err);
+        return tgemm(ctx, conv_gemm_args(cl, B, 0, C, in, out, res, relu), st);
     };
     const float* x = T.pool;
     for (auto& bs : T.blocks) {
@@ -761,9 +657,8 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
         ctx->rowmap_B = B;
     }
     {
-        GemmArgs ip = G0();
-        ip.A = x; ip.lda = 8 * w0; ip.M = C * B * ctx->P_; ip.K = 8 * w0; ip.Bw = ctx->P("input_proj.weight"); ip.ldb = 8 * w0;
-        ip.N = D; ip.bias = ctx->P("input_proj.bias"); ip.C = ctx->X; ip.ldc = D; ip.rowmap = ctx->rowmap;
+        GemmArgs ip = linear_args(x, 8 * w0, C * B * ctx->P_, 8 * w0, ctx->P("input_proj.weight"), D, ctx->P("input_proj.bias"), ctx->X, D);
+        ip.rowmap = ctx->rowmap;
         CHK(tgemm(ctx, ip, st));
     }
     CHK(launch_small_linear(qpos, S, ctx->P("input_proj_robot_state.weight"), ctx->P("input_proj_robot_state.bias"),
@@ -802,34 +697,24 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
         CHK(launch_attention(sa, st, &ctx->err));
         CHK(lin_fwd(ctx, T.sO, D, M, D, d.self_attn.out_w, D, d.self_attn.out_b, T.saB, D, nullptr, 0, st, dropout_p, dr_dec.s(1)));
         CHK(launch_layernorm(T.saB, nullptr, 0, d.n1w, d.n1b, nullptr, nullptr, T.T1B, M, D, 1e-5f, st, &ctx->err));
-        GemmArgs qg = G0();
-        qg.A = T.T1B; qg.lda = D; qg.M = M; qg.K = D; qg.Bw = d.cross.in_w; qg.ldb = D; qg.N = D; qg.bias = d.cross.in_b;
-        qg.C = T.dqB; qg.ldc = D; qg.A_add = ctx->P("query_embed.weight"); qg.ld_add = D; qg.add_mod = Q; qg.add_ncols = D;
+        GemmArgs qg = linear_args(T.T1B, D, M, D, d.cross.in_w, D, d.cross.in_b, T.dqB, D);
+        qg.A_add = ctx->P("query_embed.weight"); qg.ld_add = D; qg.add_mod = Q; qg.add_ncols = D;
         CHK(tgemm(ctx, qg, st));
     }
     {
-        GemmArgs kv = G0();
-        kv.A = T.mem; kv.lda = D; kv.M = B * N; kv.K = D; kv.Bw = d.cross.in_w + (int64_t)D * D; kv.ldb = D; kv.N = 2 * D;
-        kv.bias = d.cross.in_b + D; kv.C = T.KV; kv.ldc = 2 * D;
+        GemmArgs kv = linear_args(T.mem, D, B * N, D, d.cross.in_w + (int64_t)D * D, 2 * D, d.cross.in_b + D, T.KV, 2 * D);
         kv.A_add = ctx->pos_tokens; kv.ld_add = D; kv.add_mod = N; kv.add_ncols = D;
         CHK(tgemm(ctx, kv, st));
-        AttnArgs at;
-        memset(&at, 0, sizeof(at));
-        at.Q = gen ? T.dqB : T.dq; at.q_bs = gen ? (int64_t)Q * D : 0; at.q_rs = D;
-        at.K = T.KV; at.k_bs = (int64_t)N * 2 * D; at.k_rs = 2 * D;
-        at.V = T.KV + D; at.v_bs = at.k_bs; at.v_rs = 2 * D;
-        at.O = T.Oc; at.o_bs = (int64_t)Q * D; at.o_rs = D; at.lse = T.lse_c;
-        at.B = B; at.H = g.nheads; at.Nq = Q; at.Nk = N; at.HD = hd; at.scale = 1.0f / sqrtf((float)hd);
+        AttnArgs at = cross_attn_args(ctx, gen ? T.dqB : T.dq, gen, T.KV, T.Oc, B);
+        at.lse = T.lse_c;
         at.ws = ctx->attn_ws; at.ws_floats = ctx->attn_ws_floats;
         at.prec = ctx->gemm_prec;
-    at.prec = ctx->gemm_prec;
         at.drop_p = dropout_p; at.drop_seed = dr_dec.s(4);
         CHK(launch_attention(at, st, &ctx->err));
     }
     {
-        GemmArgs op = G0();
-        op.A = T.Oc; op.lda = D; op.M = M; op.K = D; op.Bw = d.cross.out_w; op.ldb = D; op.N = D; op.bias = d.cross.out_b;
-        op.C = T.Y2pre; op.ldc = D; op.res = gen ? T.T1B : T.t1; op.ldres = D; op.res_mod = gen ? 0 : 1;
+        GemmArgs op = linear_args(T.Oc, D, M, D, d.cross.out_w, D, d.cross.out_b, T.Y2pre, D);
+        op.res = gen ? T.T1B : T.t1; op.ldres = D; op.res_mod = gen ? 0 : 1;
         op.drop_p = dropout_p; op.drop_seed = dr_dec.s(5);
         CHK(tgemm(ctx, op, st));
     }
@@ -920,18 +805,17 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     // cross attention
     float* dKV = T.gQKV;                    // [B*N][2D]
     {
-        AttnBwd t;
-        memset(&t, 0, sizeof(t));
+        AttnBwdArgs t{};
         t.Q = gen ? T.dqB : T.dq; t.q_bs = gen ? (int64_t)Q * D : 0; t.q_rs = D;
         t.K = T.KV; t.k_bs = (int64_t)N * 2 * D; t.k_rs = 2 * D;
         t.V = T.KV + D; t.v_bs = t.k_bs; t.v_rs = 2 * D;
-        t.O = T.Oc; t.dO = dOc; t.lse = T.lse_c;
+        t.dO = dOc; t.lse = T.lse_c;
         t.dQ = T.dqb; t.dq_bs = (int64_t)Q * D; t.dq_rs = D;
         t.dK = dKV; t.dk_bs = (int64_t)N * 2 * D; t.dk_rs = 2 * D;
         t.dV = dKV + D; t.dv_bs = t.dk_bs; t.dv_rs = 2 * D;
         t.B = B; t.H = H; t.Nq = Q; t.Nk = N; t.HD = hd;
         t.drop_p = dp; t.drop_seed = dr_dec.s(4);
-        CHK(attn_bwd(ctx, t, st));
+        CHK(attn_bwd(ctx, t, T.Oc, st));
     }
     if (!gen) {
         // q = (query_embed + t1) Wq^T + bq  (shared over the batch)
@@ -963,18 +847,17 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         CHK(lin_dgrad(ctx, T.gT1, D, M, D, d.self_attn.out_w, D, dsO, D, nullptr, nullptr, st));
         CHK(lin_wgrad(ctx, T.gT1, D, M, D, T.sO, D, D, nullptr, 0, Gp(d.self_attn.out_w), Gp(d.self_attn.out_b), st));
         // self-attention: q = k = query_pos (shared over the batch), every value row = b_v
-        AttnBwd t;
-        memset(&t, 0, sizeof(t));
+        AttnBwdArgs t{};
         t.Q = T.qkd; t.q_bs = 0; t.q_rs = 2 * D;
         t.K = T.qkd + D; t.k_bs = 0; t.k_rs = 2 * D;
         t.V = d.self_attn.in_b + 2 * D; t.v_bs = 0; t.v_rs = 0;
-        t.O = T.sO; t.dO = dsO; t.lse = T.lse_s;
+        t.dO = dsO; t.lse = T.lse_s;
         t.dQ = T.dqkB; t.dq_bs = (int64_t)Q * 2 * D; t.dq_rs = 2 * D;
         t.dK = T.dqkB + D; t.dk_bs = t.dq_bs; t.dk_rs = 2 * D;
         t.dV = T.dvB; t.dv_bs = (int64_t)Q * D; t.dv_rs = D;
         t.B = B; t.H = H; t.Nq = Q; t.Nk = Q; t.HD = hd;
         t.drop_p = dp; t.drop_seed = dr_dec.s(0);
-        CHK(attn_bwd(ctx, t, st));
+        CHK(attn_bwd(ctx, t, T.sO, st));
         CHK(colsum_d(ctx, T.dvB, D, Gp(d.self_attn.in_b) + 2 * D, M, D, st));                     // d b_v (sum over keys and batch)
         CHK(launch_sum_batch(T.dqkB, (int64_t)Q * 2 * D, 2 * D, T.dqk_d, B, Q, 2 * D, 0, st));    // q/k are shared over the batch
         CHK(lin_dgrad(ctx, T.dqk_d, 2 * D, Q, 2 * D, d.self_attn.in_w, D, T.tmpQD, D, nullptr, nullptr, st));
@@ -1067,19 +950,13 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
                                ctx->conv1_scale, B, amax_pre(ctx, T.g_act1, st)));
     if (ctx->gemm_prec == ACTMI_PREC_F16X3 && w0 == 64 && T.det_ws && ctx->H1 == (g.image_h - 1) / 2 + 1 &&
         ctx->W1 == (g.image_w - 1) / 2 + 1 && T.det_ws_floats >= (int64_t)C * 64 * 196) {
-        // the direct kernel (wgrad7.hip) + fixed-order sum of its per-workgroup partials into the packed gradient
+        // the direct kernel (wgrad7.hip), accumulating into the packed gradient
         const float* sc = dyn_scale(ctx, T.g_act1, w0, C * B * ctx->H1 * ctx->W1, w0, st);
-        int nwg = 0;
-        if (launch_wgrad7x7s2(T.g_act1, T.xn4, T.det_ws, T.det_ws_floats, sc, C, B, g.image_h, g.image_w, ctx->H1, ctx->W1, &nwg, st) != 0) {
+        if (launch_wgrad7x7s2(T.g_act1, T.xn4, T.conv1_gw, 1, T.det_ws, T.det_ws_floats, sc, C, B, g.image_h, g.image_w, ctx->H1,
+                              ctx->W1, st) != 0) {
             ctx->err = "wgrad7x7s2 launch failed";
             return ACTMI_E_LAUNCH;
         }
-        SplitCombineArgs c{};
-        const int64_t slice = (int64_t)64 * 196;
-        c.part = T.det_ws; c.nsplit = nwg; c.split_stride = slice; c.gP = slice * nwg; c.ldp = 196;
-        c.res = T.conv1_gw; c.ldres = 196; c.gRes = slice;
-        c.C = T.conv1_gw; c.ldc = 196; c.gC = slice; c.M = 64; c.N = 196; c.groups = C;
-        if (launch_splitk_combine(c, st) != 0) { ctx->err = "splitk combine launch failed"; return ACTMI_E_LAUNCH; }
     } else {
         GemmArgs a = G0();
         a.A = T.g_act1; a.lda = w0; a.ta = 1; a.M = w0; a.K = B * ctx->H1 * ctx->W1;
@@ -1092,11 +969,10 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         a.a_scale_dev = dyn_scale(ctx, T.g_act1, w0, C * B * ctx->H1 * ctx->W1, w0, st);
         CHK(tgemm(ctx, a, st));
     }
-    // packed conv gradients -> OIHW state_dict gradients (one launch per layer over the cameras: same-named parameters of
-    // consecutive backbones are a constant stride apart in the arena)
+    // packed conv gradients -> OIHW state_dict gradients (one launch per layer over the cameras)
     {
-        const std::string p0 = "backbones.0.0.body.", p1 = "backbones." + std::to_string(C > 1 ? 1 : 0) + ".0.body.";
-        const int64_t cam_stride = ctx->P(p1 + "conv1.weight") - ctx->P(p0 + "conv1.weight");
+        const std::string p0 = "backbones.0.0.body.";
+        const int64_t cam_stride = backbone_cam_stride(ctx);
         CHK(launch_unpack_wgrad(T.conv1_gw, GP((p0 + "conv1.weight").c_str()), w0, 3, 7, 7, 196, 4, st, C, (int64_t)w0 * 196, cam_stride));
         for (size_t li = 0; li < ctx->convs.size(); ++li) {
             const ConvLayer& cl = ctx->convs[li];

@@ -176,10 +176,10 @@ __global__ __launch_bounds__(256) void wgrad3x3_c64_kernel(Wgrad3Args p) {
 
 }  // namespace
 
-// dW[g][64][576] += sum over the images of group g; ws: >= groups * nwg * 64 * 576 floats.  Returns the number of workgroups
-// per group it used through *nwg_out (the caller combines that many partials).
-int launch_wgrad3x3_c64(const float* dy, const float* x, float* ws, int64_t ws_floats, const float* dy_scale_dev, int groups, int B,
-                        int H, int W, int* nwg_out, hipStream_t st) {
+// dW[g][64][576] (+)= sum over the images of group g: nwg partials per group into ws (>= groups * nwg * 64 * 576 floats), then
+// summed in workgroup order by launch_splitk_combine
+int launch_wgrad3x3_c64(const float* dy, const float* x, float* dw, int accumulate, float* ws, int64_t ws_floats,
+                        const float* dy_scale_dev, int groups, int B, int H, int W, hipStream_t st) {
     if (groups <= 0 || B <= 0 || H <= 0 || W <= 0) return -2;
     if (((uintptr_t)dy & 15) || ((uintptr_t)x & 15) || ((uintptr_t)ws & 15)) return -2;
     const int strips = (W + SW - 1) / SW, units = B * strips;
@@ -202,6 +202,11 @@ int launch_wgrad3x3_c64(const float* dy, const float* x, float* ws, int64_t ws_f
     prof_begin("wgrad3x3_c64_kernel", 2.0 * CH * 576 * (double)groups * B * H * W, 8.0 * CH * (double)groups * B * H * W, st);
     hipLaunchKernelGGL(wgrad3x3_c64_kernel, dim3(nwg, groups), dim3(256), SMEM_B, st, a);
     prof_end(st);
-    if (nwg_out) *nwg_out = nwg;
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    if (hipGetLastError() != hipSuccess) return -3;
+    SplitCombineArgs c{};
+    const int64_t slice = (int64_t)CH * 576;
+    c.part = ws; c.nsplit = nwg; c.split_stride = slice; c.gP = slice * nwg; c.ldp = 576;
+    if (accumulate) { c.res = dw; c.ldres = 576; c.gRes = slice; }
+    c.C = dw; c.ldc = 576; c.gC = slice; c.M = CH; c.N = 576; c.groups = groups;
+    return launch_splitk_combine(c, st) == 0 ? 0 : -3;
 }

@@ -190,9 +190,10 @@ __global__ __launch_bounds__(256, 2) void wgrad7x7s2_kernel(Wgrad7Args p) {
 
 }  // namespace
 
-// dW[g][64][196] partials over the images of group g: ws >= groups * nwg * 64 * 196 floats; *nwg_out = partials per group
-int launch_wgrad7x7s2(const float* dy, const float* x4, float* ws, int64_t ws_floats, const float* dy_scale_dev, int groups, int B,
-                      int H, int W, int Ho, int Wo, int* nwg_out, hipStream_t st) {
+// dW[g][64][196] (+)= sum over the images of group g: nwg partials per group into ws (>= groups * nwg * 64 * 196 floats), then
+// summed in workgroup order by launch_splitk_combine
+int launch_wgrad7x7s2(const float* dy, const float* x4, float* dw, int accumulate, float* ws, int64_t ws_floats,
+                      const float* dy_scale_dev, int groups, int B, int H, int W, int Ho, int Wo, hipStream_t st) {
     if (groups <= 0 || B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return -2;
     if (Ho != (H + 6 - 7) / 2 + 1 || Wo != (W + 6 - 7) / 2 + 1) return -2;
     if (((uintptr_t)dy & 15) || ((uintptr_t)x4 & 15) || ((uintptr_t)ws & 15)) return -2;
@@ -216,6 +217,11 @@ int launch_wgrad7x7s2(const float* dy, const float* x4, float* ws, int64_t ws_fl
                4.0 * (double)groups * B * ((double)Ho * Wo * CO + (double)H * W * 4), st);
     hipLaunchKernelGGL(wgrad7x7s2_kernel, dim3(nwg, groups), dim3(256), SMEM_B, st, a);
     prof_end(st);
-    if (nwg_out) *nwg_out = nwg;
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    if (hipGetLastError() != hipSuccess) return -3;
+    SplitCombineArgs c{};
+    const int64_t slice = (int64_t)CO * 196;
+    c.part = ws; c.nsplit = nwg; c.split_stride = slice; c.gP = slice * nwg; c.ldp = 196;
+    if (accumulate) { c.res = dw; c.ldres = 196; c.gRes = slice; }
+    c.C = dw; c.ldc = 196; c.gC = slice; c.M = CO; c.N = 196; c.groups = groups;
+    return launch_splitk_combine(c, st) == 0 ? 0 : -3;
 }
