@@ -162,58 +162,6 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restric
     if (ok && rl == 0) out[n] += t;
 }
 
-// ---------------------------------------------------------------------------------------------- max-pool bwd
-// dx[pixel] = sum over the (<= 4) windows containing it of dy[window] where the window's FIRST maximum (scan order
-// r then s, strict '>', as ATen's max_pool2d) is this pixel.  Gather form: no atomics, bit-reproducible.
-__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                          float* __restrict__ dx, int H, int W, int C4, int Ho, int Wo,
-                                                          int64_t total) {
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        // 32-bit index arithmetic (the host checks total < 2^31): 64-bit divisions were most of this kernel's time
-        const unsigned uidx = (unsigned)idx;
-        const unsigned upix = uidx / (unsigned)C4;
-        const int c4 = (int)(uidx - upix * (unsigned)C4);
-        const unsigned urow = upix / (unsigned)W;
-        const int wi = (int)(upix - urow * (unsigned)W);
-        const unsigned uimg = urow / (unsigned)H;
-        const int hi = (int)(urow - uimg * (unsigned)H);
-        const int64_t img = uimg;
-        const f32x4* xs = reinterpret_cast<const f32x4*>(x) + img * H * W * C4 + c4;
-        const f32x4* gs = reinterpret_cast<const f32x4*>(dy) + img * Ho * Wo * C4 + c4;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        const int ho_lo = hi >> 1, ho_hi = (hi + 1) >> 1;      // windows with 2ho-1 <= hi <= 2ho+1
-        const int wo_lo = wi >> 1, wo_hi = (wi + 1) >> 1;
-        for (int ho = ho_lo; ho <= ho_hi; ++ho) {
-            if (ho >= Ho) continue;
-            for (int wo = wo_lo; wo <= wo_hi; ++wo) {
-                if (wo >= Wo) continue;
-                f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                int bpos[4] = {-1, -1, -1, -1};
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const int h2 = 2 * ho - 1 + r;
-                    if ((unsigned)h2 >= (unsigned)H) continue;
-#pragma unroll
-                    for (int s = 0; s < 3; ++s) {
-                        const int w2 = 2 * wo - 1 + s;
-                        if ((unsigned)w2 >= (unsigned)W) continue;
-                        const f32x4 v = xs[((int64_t)h2 * W + w2) * C4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (v[e] > best[e] || bpos[e] < 0) { best[e] = v[e]; bpos[e] = h2 * W + w2; }
-                    }
-                }
-                const f32x4 g = gs[((int64_t)ho * Wo + wo) * C4];
-                const int me = hi * W + wi;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (bpos[e] == me) acc[e] += g[e];
-            }
-        }
-        reinterpret_cast<f32x4*>(dx)[idx] = acc;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- column sums
 // out[n] += sum_m src[m][n]   (bias gradients; rows split over blockIdx.y, one atomic per column per block)
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ src, int64_t ld, float* __restrict__ out,
@@ -615,19 +563,6 @@ int launch_maxpool_bwd_idx(const uint8_t* arg, const float* dy, float* dx, int n
     prof_begin("maxpool_bwd_idx_kernel", 0.0, 4.0 * nimg * C * ((double)H * W + 1.25 * Ho * Wo), st);
     hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3((unsigned)blocks), dim3(256), 0, st, arg, dy, dx, H, W, C / 4, Ho, Wo, (unsigned)total,
                        relu_x, bn_scale, imgs_per_group > 0 ? imgs_per_group : 1, amax_bits);
-    prof_end(st);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-int launch_maxpool_bwd(const float* x, const float* dy, float* dx, int nimg, int H, int W, int C, int Ho, int Wo,
-                       hipStream_t st) {
-    if (C & 3) return -2;
-    const int64_t total = (int64_t)nimg * H * W * (C / 4);
-    if (total >= ((int64_t)1 << 31)) return -2;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    prof_begin("maxpool_bwd_kernel", 0.0, 4.0 * nimg * C * (2.0 * H * W + (double)Ho * Wo), st);
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, dy, dx, H, W, C / 4, Ho, Wo, total);
     prof_end(st);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

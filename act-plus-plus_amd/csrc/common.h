@@ -167,8 +167,6 @@ void prof_end(hipStream_t st);
 // ws (optional): scratch for the deterministic form -- per-block dw / db partials summed in block order instead of float atomics
 int launch_ln_bwd(const float* x, const float* w, const float* dy, const float* dx_add, float* dx, float* dw, float* db,
                   int M, int D, float eps, hipStream_t st, float* ws = nullptr, int64_t ws_floats = 0, unsigned* dx_amax = nullptr);
-int launch_maxpool_bwd(const float* x, const float* dy, float* dx, int nimg, int H, int W, int C, int Ho, int Wo,
-                       hipStream_t st);
 int launch_colsum(const float* src, int64_t ld, float* out, int M, int N, hipStream_t st, float* ws = nullptr, int64_t ws_floats = 0);
 int launch_sum_batch(const float* src, int64_t bs, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                      hipStream_t st);
@@ -202,7 +200,6 @@ int launch_small_linear_wgrad(const float* dy, int64_t lddy, const float* x, int
                               hipStream_t st);
 int launch_cvae_maps(int* map, uint8_t* kpm, const uint8_t* is_pad, int B, int Q, hipStream_t st);
 int launch_axpy(float* dst, const float* src, int64_t n, hipStream_t st);
-int launch_scale(float* x, int64_t n, float s, hipStream_t st);
 // direct weight gradient of the 64 -> 64 channel 3x3 / s1 / p1 convolutions (wgrad3.hip): dw [groups][64][576] (K index
 // (r, s, c)), accumulated into when `accumulate`; ws holds the per-workgroup partials (at least groups * 64 * 576 floats)
 int launch_wgrad3x3_c64(const float* dy, const float* x, float* dw, int accumulate, float* ws, int64_t ws_floats,

@@ -87,15 +87,11 @@ struct TrainState {
     float* vq_probs = nullptr;         // VQ-ACT: softmax of the latent logits [B][vq_class*vq_dim]
     bool have_eps = true;              // false: no eps / code was supplied (VQ: draw the code on the device)
     uint8_t* pool_arg = nullptr;       // stem max-pool argmax codes (maxpool_idx_kernel)
-    bool grads_dirty = false;
     hipEvent_t ev_phase1 = nullptr;    // recorded inside train_backward once the transformer.* gradients are final
     float* det_ws = nullptr;           // slices / partials of the fixed-order reductions of the backward pass
     int64_t det_ws_floats = 0;
-    float* scale_slots = nullptr;      // [SCALE_SLOTS][2]: device-computed operand scales of the f16x3 backward GEMMs
-    int scale_next = 0;
-    const float* amax_key_ptr = nullptr; int64_t amax_key_ld = 0; int amax_key_m = 0, amax_key_n = 0;   // one-shot reuse
-    const float* amax_key_slot = nullptr;
-    const float* amax_pre_ptr = nullptr; float* amax_pre_slot = nullptr;   // a producer kernel left this tensor's amax bits          // the gradient arena holds gradients of an earlier backward (no zero_grad since)
+    float* scale_slots = nullptr;      // ring of [SCALE_SLOTS][2]: device-computed operand scales of the f16x3 backward GEMMs
+    int scale_next = 0;                // ([scale, bits of the largest magnitude]; train.hip hands every slot to one caller)
     float *qkd = nullptr, *sO = nullptr, *lse_s = nullptr, *saB = nullptr, *T1B = nullptr, *dqB = nullptr, *gT1 = nullptr,
           *dsaB = nullptr, *dqkB = nullptr, *dvB = nullptr, *dqk_d = nullptr, *tmpQD = nullptr;
     // backward scratch

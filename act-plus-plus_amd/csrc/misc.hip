@@ -339,16 +339,6 @@ int launch_check_finite(const float* x, int64_t n, uint32_t* flag, uint32_t bit,
 }
 
 
-__global__ void scale_kernel(float* __restrict__ x, int64_t n4, int64_t n, float s) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n4) {
-        actmi_f32x4* p = reinterpret_cast<actmi_f32x4*>(x) + i;
-        *p = *p * s;
-    } else if (i == n4) {
-        for (int64_t j = n4 * 4; j < n; ++j) x[j] *= s;
-    }
-}
-
 // max |x| over an M x N matrix (row stride ld) as the bits of a non-negative float (monotone as unsigned), then the
 // power-of-two scale derived from it
 __global__ void amax_kernel(const float* __restrict__ x, int64_t ld, int M, int N, unsigned* __restrict__ bits) {
@@ -496,13 +486,6 @@ int launch_splitk_combine(const SplitCombineArgs& a, hipStream_t st) {
     else hipLaunchKernelGGL(splitk_combine_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
     prof_end(st);
     return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-int launch_scale(float* x, int64_t n, float s, hipStream_t st) {
-    if (n <= 0) return 0;
-    const int64_t n4 = n / 4;
-    hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((n4 + 1 + 255) / 256)), dim3(256), 0, st, x, n4, n, s);
-    return (int)hipGetLastError();
 }
 
 int launch_axpy(float* dst, const float* src, int64_t n, hipStream_t st) {

@@ -30,7 +30,7 @@ int tgemm(actmi_ctx* ctx, GemmArgs a, hipStream_t st) {
     if (a.ta == 0 && a.tb == 0 && a.mode != 2) return ctx_gemm(ctx, a, st);
     a.prec = ctx->prec_override ? ctx->prec_override : ctx->gemm_prec;
     TrainState* T = ctx->train;
-    if (a.splitk > 1 && a.split_stride == 0 && T && T->det_ws && !a.rowmap && !a.C2 && !a.mask && a.groups_inner == 0) {
+    if (a.splitk > 1 && a.split_stride == 0 && !a.rowmap && !a.C2 && !a.mask && a.groups_inner == 0) {
         // C += A B with the contraction split over the grid.  The atomic form (every split adds into C) is not run-to-run
         // repeatable; here every split stores a plain slice and a second kernel adds the slices to C in split order.
         const int groups = a.groups > 0 ? a.groups : 1;
@@ -57,51 +57,38 @@ int colsum_d(actmi_ctx* ctx, const float* src, int64_t ld, float* out, int M, in
 
 // Gradient operands of the f16x3 backward GEMMs get a power-of-two scale computed on the device from their largest
 // magnitude (gradients range from ~1e-7 at the stem to ~1e2 in the CVAE encoder: no single loss scale fits the fp16
-// range).  A dgrad / wgrad pair on the same dY computes it once (one-shot reuse, cleared by any other request).
+// range).  A scale is a value: the code that has the tensor obtains it once, in one of the two ways below, and passes it to
+// every product that reads the tensor.  Both give a null pointer (operands used as they are) unless the handle runs f16x3.
+// A slot of the ring is [scale, bits]; the bits word is zero between uses (pow2_scale_kernel re-arms it).
 constexpr int SCALE_SLOTS = 1024;
-const float* dyn_scale(actmi_ctx* ctx, const float* x, int64_t ld, int M, int N, hipStream_t st, bool keep = false) {
-    if (ctx->gemm_prec != ACTMI_PREC_F16X3) return nullptr;
-    TrainState& T = *ctx->train;
-    if (T.amax_key_ptr == x && T.amax_key_ld == ld && T.amax_key_m == M && T.amax_key_n == N) {
-        const float* slot = T.amax_key_slot;
-        T.amax_key_ptr = nullptr;
-        return slot;
-    }
-    if (T.amax_pre_ptr == x) {
-        // the kernel that wrote x accumulated the bits of its largest magnitude (amax_pre): no pass over x
-        float* slot = T.amax_pre_slot;
-        T.amax_pre_ptr = nullptr;
-        if (launch_pow2_from_bits(slot, st) != 0) return nullptr;
-        // always kept for one more request: these tensors feed a weight-gradient / data-gradient pair
-        T.amax_key_ptr = x; T.amax_key_ld = ld; T.amax_key_m = M; T.amax_key_n = N; T.amax_key_slot = slot;
-        return slot;
-    }
-    float* slot = T.scale_slots + 2 * (T.scale_next++ % SCALE_SLOTS);
-    if (launch_pow2_scale(x, ld, M, N, slot, st) != 0) return nullptr;
-    T.amax_key_ptr = keep ? x : nullptr; T.amax_key_ld = ld; T.amax_key_m = M; T.amax_key_n = N; T.amax_key_slot = slot;
-    return slot;
-}
-
-// a fresh scale slot for a caller that manages it by hand: slot[0] = the scale (after launch_pow2_from_bits), slot[1] = the bits
-// word the producers raise (zero between uses)
-float* scale_slot(actmi_ctx* ctx) {
+float* next_scale_slot(actmi_ctx* ctx) {
     if (ctx->gemm_prec != ACTMI_PREC_F16X3) return nullptr;
     TrainState& T = *ctx->train;
     return T.scale_slots + 2 * (T.scale_next++ % SCALE_SLOTS);
 }
 
-// The kernel that WRITES a gradient tensor can collect the amax bits itself (relu_bn_bwd, the GEMM epilogue: an integer
-// atomicMax, independent of arrival order): amax_pre() hands it the bits word of a fresh slot, and the dyn_scale() request
-// for that tensor then only derives the scale from it.  Returns nullptr when no scale will be asked for.
-unsigned* amax_pre(actmi_ctx* ctx, const float* out, hipStream_t st) {
-    if (ctx->gemm_prec != ACTMI_PREC_F16X3) return nullptr;
-    TrainState& T = *ctx->train;
-    if (T.amax_pre_ptr)          // an unclaimed registration: re-arm its word (does not happen on the paths below)
-        if (hipMemsetAsync(T.amax_pre_slot + 1, 0, sizeof(unsigned), st) != hipSuccess) return nullptr;
-    if (T.amax_key_ptr == out) T.amax_key_ptr = nullptr;         // the tensor is being rewritten
-    float* slot = T.scale_slots + 2 * (T.scale_next++ % SCALE_SLOTS);
-    T.amax_pre_ptr = out; T.amax_pre_slot = slot;
-    return reinterpret_cast<unsigned*>(slot + 1);
+// a gradient operand dY[M][N] (row stride ld) with its scale; column blocks of one tensor may share the scale of the whole
+struct Grad {
+    const float* p; int64_t ld; int M, N; const float* scale;
+};
+
+// way 1: a measuring pass over the finished tensor
+Grad measured(actmi_ctx* ctx, const float* p, int64_t ld, int M, int N, hipStream_t st) {
+    float* slot = next_scale_slot(ctx);
+    return Grad{p, ld, M, N, slot && launch_pow2_scale(p, ld, M, N, slot, st) == 0 ? slot : nullptr};
+}
+
+// way 2: the kernels that WRITE the tensor collect the bits of its largest magnitude themselves (relu_bn_bwd, ln_bwd, the pool
+// backward, the GEMM / conv3 / attention-backward epilogues: an integer atomicMax, independent of arrival order) -- no pass
+// over the tensor.  produce(bits) launches them with the bits word of a fresh slot (null: nothing to collect), and the slot is
+// finished right behind them, so every word handed out is turned into a scale, and re-armed, exactly once.
+template <class Produce>
+int produced_scale(actmi_ctx* ctx, hipStream_t st, const float** scale, Produce&& produce) {
+    float* slot = next_scale_slot(ctx);
+    CHK(produce(slot ? reinterpret_cast<unsigned*>(slot + 1) : nullptr));
+    if (slot) CHK(launch_pow2_from_bits(slot, st));
+    *scale = slot;
+    return 0;
 }
 
 // weight operands of the backward GEMMs (f16x3) are split on the fly with the handle's static power-of-two scale
@@ -144,18 +131,16 @@ int lin_fwd(actmi_ctx* ctx, const float* x, int64_t ldx, int M, int K, const flo
     return tgemm(ctx, a, st);
 }
 
-// dx[M][K] = dy[M][N] W[N][K] (+res) (masked by mask>0)
-int lin_dgrad(actmi_ctx* ctx, const float* dy, int64_t lddy, int M, int N, const float* W, int K, float* dx, int64_t lddx,
-              const float* res, const float* mask, hipStream_t st, float alpha = 1.f, bool dx_feeds_gemm = false,
-              const float* dy_scale = nullptr) {
+// dx[M][K] = alpha * dy[M][N] W[N][K] (+res) (masked by mask>0); dx_amax (optional): the bits word that collects the largest
+// magnitude of dx, for the products that take dx as their dY (produced_scale)
+int lin_dgrad(actmi_ctx* ctx, const Grad& dy, const float* W, int K, float* dx, int64_t lddx, const float* res, const float* mask,
+              hipStream_t st, float alpha = 1.f, unsigned* dx_amax = nullptr) {
     GemmArgs a = G0();
-    a.A = dy; a.lda = lddy; a.M = M; a.K = N; a.N = K; a.Bw = W; a.ldb = K; a.tb = 1; a.C = dx; a.ldc = lddx;
+    a.A = dy.p; a.lda = dy.ld; a.M = dy.M; a.K = dy.N; a.N = K; a.Bw = W; a.ldb = K; a.tb = 1; a.C = dx; a.ldc = lddx;
     a.res = res; a.ldres = lddx; a.mask = mask; a.ldmask = lddx; a.alpha = alpha;
     a.b_scale = ctx->bwd_wscale;
-    a.a_scale_dev = dy_scale ? dy_scale : dyn_scale(ctx, dy, lddy, M, N, st, true);
-    // dx is the dY operand of the next data / weight gradient pair (same pointer, ld, M and K columns): its maximum is taken
-    // in this product's epilogue
-    if (dx_feeds_gemm && lddx == K) a.amax_out = amax_pre(ctx, dx, st);
+    a.a_scale_dev = dy.scale;
+    a.amax_out = dx_amax;
     return tgemm(ctx, a, st);
 }
 
@@ -166,20 +151,31 @@ struct Drop {
 };
 
 // dW[N][K] += dy[M][N]^T x'[M][K],  x' = x + x_add[m % add_mod];  db[N] += colsum(dy)
-int lin_wgrad(actmi_ctx* ctx, const float* dy, int64_t lddy, int M, int N, const float* x, int64_t ldx, int K,
-              const float* x_add, int add_mod, float* dW, float* db, hipStream_t st, const float* dy_scale = nullptr) {
+int lin_wgrad(actmi_ctx* ctx, const Grad& dy, const float* x, int64_t ldx, int K, const float* x_add, int add_mod, float* dW,
+              float* db, hipStream_t st) {
     if (dW) {
         GemmArgs a = G0();
-        a.A = dy; a.lda = lddy; a.ta = 1; a.M = N; a.K = M; a.Bw = x; a.ldb = ldx; a.tb = 1; a.N = K;
+        a.A = dy.p; a.lda = dy.ld; a.ta = 1; a.M = dy.N; a.K = dy.M; a.Bw = x; a.ldb = ldx; a.tb = 1; a.N = K;
         a.B_add = x_add; a.ld_badd = K; a.badd_mod = add_mod > 0 ? add_mod : 1;
         a.C = dW; a.ldc = K;
-        a.splitk = pick_splitk(N, K, 1, M);
+        a.splitk = pick_splitk(dy.N, K, 1, dy.M);
         if (a.splitk <= 1) { a.splitk = 0; a.res = dW; a.ldres = K; }
-        a.a_scale_dev = dy_scale ? dy_scale : dyn_scale(ctx, dy, lddy, M, N, st);
+        a.a_scale_dev = dy.scale;
         CHK(tgemm(ctx, a, st));
     }
-    if (db) CHK(colsum_d(ctx, dy, lddy, db, M, N, st));
+    if (db) CHK(colsum_d(ctx, dy.p, dy.ld, db, dy.M, dy.N, st));
     return 0;
+}
+
+// backward of one linear layer y[M][N] = x'[M][K] W[N][K]^T + b for its dY: the data gradient into dx (lin_dgrad), then the
+// weight gradient and the bias column sum (lin_wgrad), all on the one scale of dY.  dx_scale (optional) receives the scale of dx,
+// collected by the data gradient, for the layer below
+int lin_bwd(actmi_ctx* ctx, const Grad& dy, const float* W, int K, const float* x, int64_t ldx, float* dx, int64_t lddx, float* dW,
+            float* db, hipStream_t st, const float* res = nullptr, const float* mask = nullptr, float alpha = 1.f,
+            const float** dx_scale = nullptr, const float* x_add = nullptr, int add_mod = 0) {
+    auto dgrad = [&](unsigned* amax) { return lin_dgrad(ctx, dy, W, K, dx, lddx, res, mask, st, alpha, amax); };
+    CHK(dx_scale ? produced_scale(ctx, st, dx_scale, dgrad) : dgrad(nullptr));
+    return lin_wgrad(ctx, dy, x, ldx, K, x_add, add_mod, dW, db, st);
 }
 
 // ---- attention backward through materialised probabilities (batched MFMA products) -------------------------------
@@ -188,13 +184,14 @@ static bool attn_bwd_fused(const actmi_ctx* ctx, int Nq, int Nk, int HD, bool sh
     return ctx->gemm_prec == ACTMI_PREC_F16X3 && !shared_q && Nq >= 256 && Nk >= 256 && (HD == 64 || HD == 32 || HD == 16);
 }
 
-// t: everything but delta, dO_scale and the dO strides (dO and O are dense [B][Nq][D]); t.amax_out (optional): one bits word that
-// the dQ, dK and dV products all raise
+// t: everything but delta and the dO strides (dO and O are dense [B][Nq][D]); t.dO_scale: the scale of dO where the kernel that
+// wrote dO collected it, null where it is measured here; t.amax_out (optional): one bits word that the dQ, dK and dV products
+// all raise
 int attn_bwd(actmi_ctx* ctx, AttnBwdArgs t, const float* O, hipStream_t st) {
     TrainState& T = *ctx->train;
     const int G = t.B * t.H, D = t.H * t.HD;
     if (attn_bwd_fused(ctx, t.Nq, t.Nk, t.HD, t.q_bs == 0)) {
-        t.dO_scale = dyn_scale(ctx, t.dO, D, t.B * t.Nq, D, st);
+        if (!t.dO_scale) t.dO_scale = measured(ctx, t.dO, D, t.B * t.Nq, D, st).scale;
         return launch_attention_bwd_dense(t, O, T.delta, st, &ctx->err);
     }
     const int ldp = (t.Nk + 3) & ~3;
@@ -230,7 +227,7 @@ int attn_bwd(actmi_ctx* ctx, AttnBwdArgs t, const float* O, hipStream_t st) {
     v.C = t.dV; v.ldc = t.dv_rs; v.groups = G; v.groups_inner = t.H;
     v.gA = pg * t.H; v.gA2 = pg; v.gB = (int64_t)t.Nq * D; v.gB2 = t.HD; v.gC = t.dv_bs; v.gC2 = t.HD;
     v.a_scale = 256.f;          // probabilities (<= 1/(1-p)) are mostly ~1/Nk
-    const float* dO_sc = dyn_scale(ctx, t.dO, D, t.B * t.Nq, D, st);
+    const float* dO_sc = t.dO_scale ? t.dO_scale : measured(ctx, t.dO, D, t.B * t.Nq, D, st).scale;
     v.b_scale_dev = dO_sc;
     v.amax_out = t.amax_out;
     CHK(tgemm(ctx, v, st));
@@ -240,25 +237,28 @@ int attn_bwd(actmi_ctx* ctx, AttnBwdArgs t, const float* O, hipStream_t st) {
     d.groups = G; d.groups_inner = t.H;
     d.gA = (int64_t)t.Nq * D; d.gA2 = t.HD; d.gB = t.v_bs; d.gB2 = t.HD; d.gC = pg * t.H; d.gC2 = pg;
     d.a_scale_dev = dO_sc;
+    const float* dS_sc = nullptr;
     if (t.drop_p > 0.f) {
         CHK(tgemm(ctx, d, st));
         // dS = P * (dP - delta) * scale in place of dP, with dP = dPd * mask / (1-p)
         CHK(launch_attn_ds_drop(P, dP, T.delta, scale, t.drop_seed, t.drop_p, G, t.Nq, t.Nk, ldp, st));
+        dS_sc = measured(ctx, dP, ldp, G * t.Nq, t.Nk, st).scale;
     } else {
         // dS = P * (dP - delta) * scale in the epilogue of the dP product (dP itself is never stored), with the operand-scale
         // maximum of dS collected on the way out
         d.epi = 2; d.epi_scale = scale; d.epi_row = T.delta; d.gRow = (int64_t)t.H * t.Nq; d.gRow2 = t.Nq;
         d.res = P; d.ldres = ldp; d.gRes = pg * t.H; d.gRes2 = pg;
-        d.amax_out = amax_pre(ctx, dP, st);
-        CHK(tgemm(ctx, d, st));
-        if (ldp != t.Nk) CHK(launch_zero_cols(dP, (int64_t)G * t.Nq, ldp, t.Nk, st));
+        CHK(produced_scale(ctx, st, &dS_sc, [&](unsigned* amax) -> int {
+            d.amax_out = amax;
+            CHK(tgemm(ctx, d, st));
+            return ldp != t.Nk ? launch_zero_cols(dP, (int64_t)G * t.Nq, ldp, t.Nk, st) : 0;
+        }));
     }
     // dQ[q][d] = sum_key dS[q][key] K[key][d]
     GemmArgs q = G0();
     q.A = dP; q.lda = ldp; q.M = t.Nq; q.K = t.Nk; q.Bw = t.K; q.ldb = t.k_rs; q.tb = 1; q.N = t.HD;
     q.C = t.dQ; q.ldc = t.dq_rs; q.groups = G; q.groups_inner = t.H;
     q.gA = pg * t.H; q.gA2 = pg; q.gB = t.k_bs; q.gB2 = t.HD; q.gC = t.dq_bs; q.gC2 = t.HD;
-    const float* dS_sc = dyn_scale(ctx, dP, ldp, G * t.Nq, t.Nk, st);
     q.a_scale_dev = dS_sc;
     q.amax_out = t.amax_out;
     CHK(tgemm(ctx, q, st));
@@ -305,26 +305,30 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
     float* gA = T.gA; float* gC = T.gC; float* gH = T.gH; float* gQKV = T.gQKV;
     const bool drop = dr.p > 0.f;
     const float inv_keep = drop ? 1.f / (1.f - dr.p) : 1.f;
+    // dY of a sublayer from the LayerNorm behind it: gA with the scale its LayerNorm backward collected; with dropout the masked
+    // copy in gC, which is measured
+    auto norm_bwd = [&](const float* y, const float* nw, const float* nb, const float* dy, uint32_t site, Grad* dz) -> int {
+        auto ln = [&](unsigned* amax) { return ln_bwd_d(ctx, y, nw, dy, nullptr, gA, Gp(nw), Gp(nb), M, D, 1e-5f, st, amax); };
+        *dz = Grad{gA, D, M, D, nullptr};
+        if (!drop) return produced_scale(ctx, st, &dz->scale, ln);
+        CHK(ln(nullptr));
+        CHK(launch_dropout_bwd(gA, gC, dr.s(site), dr.p, (int64_t)M * D, st));
+        *dz = measured(ctx, gC, D, M, D, st);
+        return 0;
+    };
+    Grad dz2, dz1;
     // norm2:  Y2 = X1 + drop3(linear2(Hb))
-    CHK(ln_bwd_d(ctx, s.Y2, w.n2w, dOut, nullptr, gA, Gp(w.n2w), Gp(w.n2b), M, D, 1e-5f, st,
-                 drop ? nullptr : amax_pre(ctx, gA, st)));                                                   // gA = dY2
-    const float* dz2 = gA;
-    if (drop) { CHK(launch_dropout_bwd(gA, gC, dr.s(3), dr.p, (int64_t)M * D, st)); dz2 = gC; }
+    CHK(norm_bwd(s.Y2, w.n2w, w.n2b, dOut, 3, &dz2));                                                        // gA = dY2
     // linear2 / dropout / relu / linear1:  Hb = drop2(relu(linear1(X1))); dropped or negative entries are 0 in Hb
-    CHK(lin_dgrad(ctx, dz2, D, M, D, w.l2w, F, gH, F, nullptr, s.Hb, st, inv_keep, true));                   // gH = dHpre
-    CHK(lin_wgrad(ctx, dz2, D, M, D, s.Hb, F, F, nullptr, 0, Gp(w.l2w), Gp(w.l2b), st));
-    CHK(lin_dgrad(ctx, gH, F, M, F, w.l1w, D, gC, D, gA, nullptr, st));                                      // gC = dX1
-    CHK(lin_wgrad(ctx, gH, F, M, F, s.X1, D, D, nullptr, 0, Gp(w.l1w), Gp(w.l1b), st));
+    Grad dH{gH, F, M, F, nullptr};                                                                           // gH = dHpre
+    CHK(lin_bwd(ctx, dz2, w.l2w, F, s.Hb, F, gH, F, Gp(w.l2w), Gp(w.l2b), st, nullptr, s.Hb, inv_keep, &dH.scale));
+    CHK(lin_bwd(ctx, dH, w.l1w, D, s.X1, D, gC, D, Gp(w.l1w), Gp(w.l1b), st, gA));                           // gC = dX1
     // norm1:  Y1 = x_in + drop1(out_proj(ATT))
-    CHK(ln_bwd_d(ctx, s.Y1, w.n1w, gC, nullptr, gA, Gp(w.n1w), Gp(w.n1b), M, D, 1e-5f, st,
-                 drop ? nullptr : amax_pre(ctx, gA, st)));                                                   // gA = dY1
-    const float* dz1 = gA;
-    if (drop) { CHK(launch_dropout_bwd(gA, gC, dr.s(1), dr.p, (int64_t)M * D, st)); dz1 = gC; }
+    CHK(norm_bwd(s.Y1, w.n1w, w.n1b, gC, 1, &dz1));                                                          // gA = dY1
+    // attention: its dO is dATT, with the scale the out-projection's data gradient collects
     float* dATT = gH;                                                                                        // [M][D] view
-    CHK(lin_dgrad(ctx, dz1, D, M, D, w.attn.out_w, D, dATT, D, nullptr, nullptr, st, 1.f, true));            // dATT = dO of the attention
-    CHK(lin_wgrad(ctx, dz1, D, M, D, s.ATT, D, D, nullptr, 0, Gp(w.attn.out_w), Gp(w.attn.out_b), st));
-    // attention
     AttnBwdArgs t{};
+    CHK(lin_bwd(ctx, dz1, w.attn.out_w, D, s.ATT, D, dATT, D, Gp(w.attn.out_w), Gp(w.attn.out_b), st, nullptr, nullptr, 1.f, &t.dO_scale));
     const int64_t bs = (int64_t)n * 3 * D;
     t.Q = s.QKV; t.K = s.QKV + D; t.V = s.QKV + 2 * D; t.dO = dATT; t.lse = s.lse;
     t.q_bs = t.k_bs = t.v_bs = bs; t.q_rs = t.k_rs = t.v_rs = 3 * D;
@@ -334,14 +338,15 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
     t.drop_p = dr.p; t.drop_seed = dr.s(0);
     // ONE operand scale for gQKV = [dQ | dK | dV]: the three products that write it raise the same bits word, and the data
     // gradient and the two weight gradients below all use it (three strided amax passes over gQKV otherwise)
-    float* qkv_slot = scale_slot(ctx);
-    t.amax_out = qkv_slot ? reinterpret_cast<unsigned*>(qkv_slot + 1) : nullptr;
-    CHK(attn_bwd(ctx, t, s.ATT, st));
-    if (qkv_slot && launch_pow2_from_bits(qkv_slot, st) != 0) return ACTMI_E_LAUNCH;
+    const float* qkv_sc = nullptr;
+    CHK(produced_scale(ctx, st, &qkv_sc, [&](unsigned* amax) {
+        t.amax_out = amax;
+        return attn_bwd(ctx, t, s.ATT, st);
+    }));
     // in_proj: dIn = dQKV W_in + dY1 ; dW rows [0,2D) see x+pos, rows [2D,3D) see x
-    CHK(lin_dgrad(ctx, gQKV, 3 * D, M, 3 * D, w.attn.in_w, D, dIn, D, gA, nullptr, st, 1.f, false, qkv_slot));
-    CHK(lin_wgrad(ctx, gQKV, 3 * D, M, 2 * D, s.x_in, D, D, pos, n, Gp(w.attn.in_w), nullptr, st, qkv_slot));
-    CHK(lin_wgrad(ctx, gQKV + 2 * D, 3 * D, M, D, s.x_in, D, D, nullptr, 0, Gp(w.attn.in_w) + (int64_t)2 * D * D, nullptr, st, qkv_slot));
+    CHK(lin_dgrad(ctx, Grad{gQKV, 3 * D, M, 3 * D, qkv_sc}, w.attn.in_w, D, dIn, D, gA, nullptr, st));
+    CHK(lin_wgrad(ctx, Grad{gQKV, 3 * D, M, 2 * D, qkv_sc}, s.x_in, D, D, pos, n, Gp(w.attn.in_w), nullptr, st));
+    CHK(lin_wgrad(ctx, Grad{gQKV + 2 * D, 3 * D, M, D, qkv_sc}, s.x_in, D, D, nullptr, 0, Gp(w.attn.in_w) + (int64_t)2 * D * D, nullptr, st));
     CHK(colsum_d(ctx, gQKV, 3 * D, Gp(w.attn.in_b), M, 3 * D, st));
     if (dpos2) {
         // additional_pos_embed rows: d(x+pos)[b][j] = dQK[b][j] W_in[0:2D], summed over the batch, j in {0,1}
@@ -349,7 +354,7 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
         a.A = gQKV; a.lda = 3 * D; a.a_rowmap = T.pos_rows; a.M = 2 * B; a.K = 2 * D; a.Bw = w.attn.in_w; a.ldb = D; a.tb = 1;
         a.N = D; a.C = T.tmp2BD; a.ldc = D;
         a.b_scale = ctx->bwd_wscale;
-        a.a_scale_dev = dyn_scale(ctx, gQKV, 3 * D, M, 2 * D, st);
+        a.a_scale_dev = measured(ctx, gQKV, 3 * D, M, 2 * D, st).scale;
         CHK(tgemm(ctx, a, st));
         CHK(launch_sum_batch(T.tmp2BD, 2 * D, D, dpos2, B, 2, D, 1, st));
     }
@@ -357,13 +362,14 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
 }
 
 // ---- convolution backward pieces --------------------------------------------------------------------------------------
-int conv_wgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, const float* x, int B, hipStream_t st) {
+// dys_scale: the operand scale of dys, one value for the weight and the data gradient of a convolution
+int conv_wgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, const float* dys_scale, const float* x, int B,
+               hipStream_t st) {
     TrainState& T = *ctx->train;
     const int C = ctx->cfg.num_cams;
-    if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.direct && T.det_ws && T.det_ws_floats >= (int64_t)C * 64 * 576) {
+    if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.direct && T.det_ws_floats >= (int64_t)C * 64 * 576) {
         // layer1: the direct kernel (wgrad3.hip), accumulating into the packed gradient like autograd
-        const float* sc = dyn_scale(ctx, dys, cl.cout, C * B * cl.Ho * cl.Wo, cl.cout, st);
-        if (launch_wgrad3x3_c64(dys, x, T.conv_gw[li], 1, T.det_ws, T.det_ws_floats, sc, C, B, cl.H, cl.W, st) != 0) {
+        if (launch_wgrad3x3_c64(dys, x, T.conv_gw[li], 1, T.det_ws, T.det_ws_floats, dys_scale, C, B, cl.H, cl.W, st) != 0) {
             ctx->err = "wgrad3x3_c64 launch failed";
             return ACTMI_E_LAUNCH;
         }
@@ -377,7 +383,7 @@ int conv_wgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, co
     a.gA = (int64_t)B * cl.Ho * cl.Wo * cl.cout; a.gB = (int64_t)B * cl.H * cl.W * cl.cin; a.gC = (int64_t)cl.cout * cl.K;
     a.splitk = pick_splitk(cl.cout, cl.K, C, a.K);
     if (a.splitk <= 1) { a.splitk = 0; a.res = a.C; a.ldres = cl.K; a.gRes = a.gC; }
-    a.a_scale_dev = dyn_scale(ctx, dys, cl.cout, C * B * cl.Ho * cl.Wo, cl.cout, st);
+    a.a_scale_dev = dys_scale;
     return tgemm(ctx, a, st);
 }
 
@@ -387,18 +393,19 @@ bool dgrad_direct(const actmi_ctx* ctx, const ConvLayer& cl) {
     return ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.direct;
 }
 
-// dx[C][B][H][W][cin] = dgrad(dys) (+res) , then masked by (mask > 0) and multiplied by scale[cin] (previous BN)
-int conv_dgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, float* dx, const float* res, const float* mask,
-               const float* scale, int B, hipStream_t st, bool dx_feeds_gemm = false) {
+// dx[C][B][H][W][cin] = dgrad(dys) (+res) , then masked by (mask > 0) and multiplied by scale[cin] (previous BN); dx_amax
+// (optional): the bits word that collects the largest magnitude of dx (produced_scale)
+int conv_dgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, const float* dys_scale, float* dx, const float* res,
+               const float* mask, const float* scale, int B, hipStream_t st, unsigned* dx_amax = nullptr) {
     TrainState& T = *ctx->train;
     const int C = ctx->cfg.num_cams;
     if (dgrad_direct(ctx, cl) && T.conv_wd16[li]) {
         Conv3Args c{};
         c.x = dys; c.w16 = T.conv_wd16[li]; c.res = res; c.out = dx; c.G = C; c.B = B; c.H = cl.H; c.W = cl.W; c.relu = 0;
         c.w_scale = ctx->bwd_wscale;
-        c.x_scale_dev = dyn_scale(ctx, dys, cl.cout, C * B * cl.Ho * cl.Wo, cl.cout, st, true);
+        c.x_scale_dev = dys_scale;
         c.mask = mask; c.post_scale = scale;
-        if (dx_feeds_gemm) c.amax_out = amax_pre(ctx, dx, st);
+        c.amax_out = dx_amax;
         return launch_conv3x3_c64(c, st, &ctx->err) == 0 ? 0 : ACTMI_E_LAUNCH;
     }
     GemmArgs a = G0();
@@ -410,9 +417,19 @@ int conv_dgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, fl
     a.res = res; a.ldres = cl.cin; a.gRes = a.gC; a.mask = mask; a.ldmask = cl.cin; a.gMask = a.gC;
     a.scale = scale; a.gSB = cl.cin;
     a.b_scale = ctx->bwd_wscale;
-    a.a_scale_dev = dyn_scale(ctx, dys, cl.cout, C * B * cl.Ho * cl.Wo, cl.cout, st, true);
-    if (dx_feeds_gemm) a.amax_out = amax_pre(ctx, dx, st);       // dx is the dY operand of the next wgrad / dgrad pair
+    a.a_scale_dev = dys_scale;
+    a.amax_out = dx_amax;
     return tgemm(ctx, a, st);
+}
+
+// backward of one convolution for its dY (dys, already multiplied by the BN scale): the weight gradient from the input x, then
+// the data gradient into dx, both on the one scale of dys.  dx_scale (optional) receives the scale of dx, collected by the data
+// gradient, for the convolution below
+int conv_bwd(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, const float* dys_scale, const float* x, float* dx,
+             const float* res, const float* mask, const float* scale, int B, hipStream_t st, const float** dx_scale = nullptr) {
+    CHK(conv_wgrad(ctx, cl, li, dys, dys_scale, x, B, st));
+    auto dgrad = [&](unsigned* amax) { return conv_dgrad(ctx, cl, li, dys, dys_scale, dx, res, mask, scale, B, st, amax); };
+    return dx_scale ? produced_scale(ctx, st, dx_scale, dgrad) : dgrad(nullptr);
 }
 
 }  // namespace
@@ -751,27 +768,12 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     const int M = B * Q;
     const DecW& d = ctx->dec[0];
 
-    // ---- optional global loss scale (f16x3, ACTMI_LOSS_SCALE_LOG2; tuning aid): the seed is multiplied by a power of two
-    // and the finished gradient arena multiplied back (both exact); gradients already in the arena (accumulation
-    // without zero_grad) are carried through the same scale.  Off by default -- see dyn_scale.
-    T.amax_key_ptr = nullptr;
-    T.amax_pre_ptr = nullptr;
-    float LS = 1.f;
-    if (ctx->gemm_prec == ACTMI_PREC_F16X3) {
-        static const char* ls_env = getenv("ACTMI_LOSS_SCALE_LOG2");
-        int e = ls_env ? atoi(ls_env) : 0;         // off by default: operands are scaled individually (dyn_scale)
-        if (e < 0) e = 0;
-        if (e > 24) e = 24;
-        LS = ldexpf(1.f, e);
-    }
-    if (LS != 1.f && T.grads_dirty) CHK(launch_scale(T.gbase, ctx->ptotal, LS, st));
-    loss_scale *= LS;
     // ---- loss -> a_hat -> heads
     float* d_ahat = T.gQKV;                 // scratch [M][A]
     CHK(launch_l1_bwd(T.a_hat, T.actions, T.is_pad, d_ahat, B, Q, A, loss_scale, st));
     float* dhs = T.gA;
-    CHK(lin_dgrad(ctx, d_ahat, A, M, A, ctx->P("action_head.weight"), D, dhs, D, nullptr, nullptr, st));
-    CHK(lin_wgrad(ctx, d_ahat, A, M, A, T.hs, D, D, nullptr, 0, GP("action_head.weight"), GP("action_head.bias"), st));
+    CHK(lin_bwd(ctx, measured(ctx, d_ahat, A, M, A, st), ctx->P("action_head.weight"), D, T.hs, D, dhs, D, GP("action_head.weight"),
+                GP("action_head.bias"), st));
     // decoder.norm, norm3
     float* dT3 = T.gC;
     CHK(ln_bwd_d(ctx, T.T3, ctx->P("transformer.decoder.norm.weight"), dhs, nullptr, dT3, GP("transformer.decoder.norm.weight"),
@@ -785,19 +787,16 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     // FFN:  Y3pre = T2 + drop3(linear2(Hd)),  Hd = drop(relu(linear1(T2)))
     const float* dz3 = dY3;
     if (gen) { CHK(launch_dropout_bwd(dY3, T.gC, dr_dec.s(3), dp, (int64_t)M * D, st)); dz3 = T.gC; }
-    CHK(lin_dgrad(ctx, dz3, D, M, D, d.l2w, F, T.gH, F, nullptr, T.Hd, st, inv_keep));
-    CHK(lin_wgrad(ctx, dz3, D, M, D, T.Hd, F, F, nullptr, 0, Gp(d.l2w), Gp(d.l2b), st));
+    CHK(lin_bwd(ctx, measured(ctx, dz3, D, M, D, st), d.l2w, F, T.Hd, F, T.gH, F, Gp(d.l2w), Gp(d.l2b), st, nullptr, T.Hd, inv_keep));
     float* dT2 = T.gC;
-    CHK(lin_dgrad(ctx, T.gH, F, M, F, d.l1w, D, dT2, D, dY3, nullptr, st));
-    CHK(lin_wgrad(ctx, T.gH, F, M, F, T.T2, D, D, nullptr, 0, Gp(d.l1w), Gp(d.l1b), st));
+    CHK(lin_bwd(ctx, measured(ctx, T.gH, F, M, F, st), d.l1w, D, T.T2, D, dT2, D, Gp(d.l1w), Gp(d.l1b), st, dY3));
     // norm2:  Y2pre = t1 + drop2(out_proj(Oc))
     float* dY2 = T.gA;
     CHK(ln_bwd_d(ctx, T.Y2pre, d.n2w, dT2, nullptr, dY2, Gp(d.n2w), Gp(d.n2b), M, D, 1e-5f, st));
     const float* dz2 = dY2;
     if (gen) { CHK(launch_dropout_bwd(dY2, T.gC, dr_dec.s(5), dp, (int64_t)M * D, st)); dz2 = T.gC; }
     float* dOc = T.gH;                      // [M][D] view of the big scratch
-    CHK(lin_dgrad(ctx, dz2, D, M, D, d.cross.out_w, D, dOc, D, nullptr, nullptr, st));
-    CHK(lin_wgrad(ctx, dz2, D, M, D, T.Oc, D, D, nullptr, 0, Gp(d.cross.out_w), Gp(d.cross.out_b), st));
+    CHK(lin_bwd(ctx, measured(ctx, dz2, D, M, D, st), d.cross.out_w, D, T.Oc, D, dOc, D, Gp(d.cross.out_w), Gp(d.cross.out_b), st));
     float* dt1 = T.tmpD;                    // [D]  (constant path: t1 is one broadcast row)
     HIPCHK(hipMemsetAsync(T.tmpD, 0, 4 * D * sizeof(float), st));
     if (!gen) CHK(colsum_d(ctx, dY2, D, dt1, M, D, st));
@@ -822,30 +821,29 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         float* ddq = T.gA;                      // [Q][D]
         CHK(launch_sum_batch(T.dqb, (int64_t)Q * D, D, ddq, B, Q, D, 0, st));
         float* dqin = T.gC;                     // [Q][D]
-        CHK(lin_dgrad(ctx, ddq, D, Q, D, d.cross.in_w, D, dqin, D, nullptr, nullptr, st));
-        CHK(lin_wgrad(ctx, ddq, D, Q, D, T.qin, D, D, nullptr, 0, Gp(d.cross.in_w), Gp(d.cross.in_b), st));
+        CHK(lin_bwd(ctx, measured(ctx, ddq, D, Q, D, st), d.cross.in_w, D, T.qin, D, dqin, D, Gp(d.cross.in_w), Gp(d.cross.in_b), st));
         CHK(launch_axpy(GP("query_embed.weight"), dqin, (int64_t)Q * D, st));
         CHK(colsum_d(ctx, dqin, D, dt1, Q, D, st));
         // t1 = norm1(out_proj(b_v) + b_o)
         float* dsa = T.tmpD + D;
         CHK(ln_bwd_d(ctx, T.sa_tmp, d.n1w, dt1, nullptr, dsa, Gp(d.n1w), Gp(d.n1b), 1, D, 1e-5f, st));
         float* dbv = T.tmpD + 2 * D;
-        CHK(lin_dgrad(ctx, dsa, D, 1, D, d.self_attn.out_w, D, dbv, D, nullptr, nullptr, st));
-        CHK(lin_wgrad(ctx, dsa, D, 1, D, d.self_attn.in_b + 2 * D, D, D, nullptr, 0, Gp(d.self_attn.out_w), Gp(d.self_attn.out_b), st));
+        CHK(lin_bwd(ctx, measured(ctx, dsa, D, 1, D, st), d.self_attn.out_w, D, d.self_attn.in_b + 2 * D, D, dbv, D, Gp(d.self_attn.out_w),
+                    Gp(d.self_attn.out_b), st));
         CHK(launch_axpy(Gp(d.self_attn.in_b) + 2 * D, dbv, D, st));
     } else {
         // q[b] = (T1[b] + query_embed) Wq^T + bq
         float* dqin = T.gA;                     // [M][D]
-        CHK(lin_dgrad(ctx, T.dqb, D, M, D, d.cross.in_w, D, dqin, D, nullptr, nullptr, st));
-        CHK(lin_wgrad(ctx, T.dqb, D, M, D, T.T1B, D, D, ctx->P("query_embed.weight"), Q, Gp(d.cross.in_w), Gp(d.cross.in_b), st));
+        CHK(lin_bwd(ctx, measured(ctx, T.dqb, D, M, D, st), d.cross.in_w, D, T.T1B, D, dqin, D, Gp(d.cross.in_w), Gp(d.cross.in_b), st,
+                    nullptr, nullptr, 1.f, nullptr, ctx->P("query_embed.weight"), Q));
         CHK(launch_sum_batch(dqin, (int64_t)Q * D, D, GP("query_embed.weight"), B, Q, D, 1, st));
         CHK(launch_axpy(T.gT1, dqin, (int64_t)M * D, st));
         // T1 = norm1(drop1(out_proj(sO)))
         CHK(ln_bwd_d(ctx, T.saB, d.n1w, T.gT1, nullptr, T.dsaB, Gp(d.n1w), Gp(d.n1b), M, D, 1e-5f, st));
         CHK(launch_dropout_bwd(T.dsaB, T.gT1, dr_dec.s(1), dp, (int64_t)M * D, st));            // gT1 := d(out_proj output)
         float* dsO = T.gA;
-        CHK(lin_dgrad(ctx, T.gT1, D, M, D, d.self_attn.out_w, D, dsO, D, nullptr, nullptr, st));
-        CHK(lin_wgrad(ctx, T.gT1, D, M, D, T.sO, D, D, nullptr, 0, Gp(d.self_attn.out_w), Gp(d.self_attn.out_b), st));
+        CHK(lin_bwd(ctx, measured(ctx, T.gT1, D, M, D, st), d.self_attn.out_w, D, T.sO, D, dsO, D, Gp(d.self_attn.out_w),
+                    Gp(d.self_attn.out_b), st));
         // self-attention: q = k = query_pos (shared over the batch), every value row = b_v
         AttnBwdArgs t{};
         t.Q = T.qkd; t.q_bs = 0; t.q_rs = 2 * D;
@@ -860,16 +858,19 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         CHK(attn_bwd(ctx, t, T.sO, st));
         CHK(colsum_d(ctx, T.dvB, D, Gp(d.self_attn.in_b) + 2 * D, M, D, st));                     // d b_v (sum over keys and batch)
         CHK(launch_sum_batch(T.dqkB, (int64_t)Q * 2 * D, 2 * D, T.dqk_d, B, Q, 2 * D, 0, st));    // q/k are shared over the batch
-        CHK(lin_dgrad(ctx, T.dqk_d, 2 * D, Q, 2 * D, d.self_attn.in_w, D, T.tmpQD, D, nullptr, nullptr, st));
+        const Grad dqk = measured(ctx, T.dqk_d, 2 * D, Q, 2 * D, st);
+        CHK(lin_dgrad(ctx, dqk, d.self_attn.in_w, D, T.tmpQD, D, nullptr, nullptr, st));
         CHK(launch_axpy(GP("query_embed.weight"), T.tmpQD, (int64_t)Q * D, st));
-        CHK(lin_wgrad(ctx, T.dqk_d, 2 * D, Q, 2 * D, ctx->P("query_embed.weight"), D, D, nullptr, 0, Gp(d.self_attn.in_w),
-                      Gp(d.self_attn.in_b), st));
+        CHK(lin_wgrad(ctx, dqk, ctx->P("query_embed.weight"), D, D, nullptr, 0, Gp(d.self_attn.in_w), Gp(d.self_attn.in_b), st));
     }
     // k = (memory + pos) Wk^T, v = memory Wv^T
     float* dmem = T.gB;
-    CHK(lin_dgrad(ctx, dKV, 2 * D, B * N, 2 * D, d.cross.in_w + (int64_t)D * D, D, dmem, D, nullptr, nullptr, st));
-    CHK(lin_wgrad(ctx, dKV, 2 * D, B * N, D, T.mem, D, D, ctx->pos_tokens, N, Gp(d.cross.in_w) + (int64_t)D * D, nullptr, st));
-    CHK(lin_wgrad(ctx, dKV + D, 2 * D, B * N, D, T.mem, D, D, nullptr, 0, Gp(d.cross.in_w) + (int64_t)2 * D * D, nullptr, st));
+    // (dKV, its dK block twice and its dV block are each measured on their own)
+    CHK(lin_dgrad(ctx, measured(ctx, dKV, 2 * D, B * N, 2 * D, st), d.cross.in_w + (int64_t)D * D, D, dmem, D, nullptr, nullptr, st));
+    CHK(lin_wgrad(ctx, measured(ctx, dKV, 2 * D, B * N, D, st), T.mem, D, D, ctx->pos_tokens, N, Gp(d.cross.in_w) + (int64_t)D * D,
+                  nullptr, st));
+    CHK(lin_wgrad(ctx, measured(ctx, dKV + D, 2 * D, B * N, D, st), T.mem, D, D, nullptr, 0, Gp(d.cross.in_w) + (int64_t)2 * D * D,
+                  nullptr, st));
     CHK(colsum_d(ctx, dKV, 2 * D, Gp(d.cross.in_b) + D, B * N, 2 * D, st));
     float* dpos2 = GP("additional_pos_embed.weight");
     {
@@ -877,7 +878,7 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         a.A = dKV; a.lda = 2 * D; a.a_rowmap = T.pos_rows; a.M = 2 * B; a.K = D; a.Bw = d.cross.in_w + (int64_t)D * D; a.ldb = D;
         a.tb = 1; a.N = D; a.C = T.tmp2BD; a.ldc = D;
         a.b_scale = ctx->bwd_wscale;
-        a.a_scale_dev = dyn_scale(ctx, dKV, 2 * D, B * N, D, st);
+        a.a_scale_dev = measured(ctx, dKV, 2 * D, B * N, D, st).scale;
         CHK(tgemm(ctx, a, st));
         CHK(launch_sum_batch(T.tmp2BD, 2 * D, D, dpos2, B, 2, D, 1, st));
     }
@@ -897,7 +898,7 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     if (g.has_cvae_encoder) {
         const int Lz = g.vq ? g.vq_class * g.vq_dim : L;
         CHK(launch_small_linear_wgrad(dX, (int64_t)N * D, T.z, Lz, GP("latent_out_proj.weight"), B, D, Lz, st));
-        CHK(lin_dgrad(ctx, dX, (int64_t)N * D, B, D, ctx->P("latent_out_proj.weight"), Lz, T.dz, Lz, nullptr, nullptr, st));
+        CHK(lin_dgrad(ctx, measured(ctx, dX, (int64_t)N * D, B, D, st), ctx->P("latent_out_proj.weight"), Lz, T.dz, Lz, nullptr, nullptr, st));
     }
     CHK(colsum_d(ctx, dX, (int64_t)N * D, GP("latent_out_proj.bias"), B, D, st));
     // tokens 2..: input_proj (1x1 conv) of the layer4 maps
@@ -905,8 +906,8 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     CHK(launch_gather_rows(dX, ctx->rowmap, T.dXg, MP, D, st));
     const BlockSave& last = T.blocks.back();
     float* gcur = T.gbuf[0];                // grad wrt the current block output
-    CHK(lin_dgrad(ctx, T.dXg, D, MP, D, ctx->P("input_proj.weight"), 8 * w0, gcur, 8 * w0, nullptr, nullptr, st));
-    CHK(lin_wgrad(ctx, T.dXg, D, MP, D, last.out, 8 * w0, 8 * w0, nullptr, 0, GP("input_proj.weight"), GP("input_proj.bias"), st));
+    CHK(lin_bwd(ctx, measured(ctx, T.dXg, D, MP, D, st), ctx->P("input_proj.weight"), 8 * w0, last.out, 8 * w0, gcur, 8 * w0,
+                GP("input_proj.weight"), GP("input_proj.bias"), st));
 
     // ---- backbone: BasicBlocks in reverse.  Frozen BN: y = conv * scale + bias  =>  dconv = dy * scale.
     for (size_t li = 0; li < ctx->convs.size(); ++li) {
@@ -927,32 +928,34 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         const float* x = bi > 0 ? T.blocks[bi - 1].out : T.pool;
         const int64_t per = (int64_t)B * k2.Ho * k2.Wo * k2.cout;
         // dz = dout * (out > 0) ; dzs = dz * scale_bn2 ; (downsample) dsc = dz * scale_ds
-        CHK(launch_relu_bn_bwd(gcur, nullptr, bs.out, k2.scale, dz, dzs, C, per, k2.cout, st, amax_pre(ctx, dzs, st)));
-        CHK(conv_wgrad(ctx, k2, bs.c2, dzs, bs.y1, B, st));
+        const float *dzs_sc = nullptr, *dsc_sc = nullptr;
+        CHK(produced_scale(ctx, st, &dzs_sc, [&](unsigned* amax) {
+            return launch_relu_bn_bwd(gcur, nullptr, bs.out, k2.scale, dz, dzs, C, per, k2.cout, st, amax);
+        }));
         // d(pre-bn1) = dgrad_conv2(dzs) * (y1 > 0) * scale_bn1
-        CHK(conv_dgrad(ctx, k2, bs.c2, dzs, dsc, nullptr, bs.y1, k1.scale, B, st, true));
-        CHK(conv_wgrad(ctx, k1, bs.c1, dsc, x, B, st));
-        // dx = dgrad_conv1(dsc) + identity path
+        CHK(conv_bwd(ctx, k2, bs.c2, dzs, dzs_sc, bs.y1, dsc, nullptr, bs.y1, k1.scale, B, st, &dsc_sc));
+        // dx = dgrad_conv1(dsc) + identity path (dz itself, or its downsample branch)
         float* dx = gcur;                     // gcur (dout) is dead after relu_bn_bwd
-        if (bs.ds < 0) {
-            CHK(conv_dgrad(ctx, k1, bs.c1, dsc, dx, dz, nullptr, nullptr, B, st));
-        } else {
+        CHK(conv_bwd(ctx, k1, bs.c1, dsc, dsc_sc, x, dx, bs.ds < 0 ? dz : nullptr, nullptr, nullptr, B, st));
+        if (bs.ds >= 0) {
             const ConvLayer& ds = ctx->convs[bs.ds];
-            CHK(conv_dgrad(ctx, k1, bs.c1, dsc, dx, nullptr, nullptr, nullptr, B, st));
-            CHK(launch_relu_bn_bwd(dz, nullptr, nullptr, ds.scale, nullptr, dzs, C, per, ds.cout, st, amax_pre(ctx, dzs, st)));   // dzs = dz * scale_ds
-            CHK(conv_wgrad(ctx, ds, bs.ds, dzs, x, B, st));
-            CHK(conv_dgrad(ctx, ds, bs.ds, dzs, dx, dx, nullptr, nullptr, B, st));
+            CHK(produced_scale(ctx, st, &dzs_sc, [&](unsigned* amax) {                                               // dzs = dz * scale_ds
+                return launch_relu_bn_bwd(dz, nullptr, nullptr, ds.scale, nullptr, dzs, C, per, ds.cout, st, amax);
+            }));
+            CHK(conv_bwd(ctx, ds, bs.ds, dzs, dzs_sc, x, dx, dx, nullptr, nullptr, B, st));
         }
     }
     // stem: maxpool, relu, bn1, conv1 weight gradient through the NHWC4 normalised image
     // (ReLU + FrozenBN backward of the stem and the operand-scale maximum ride on the pool's backward: one pass over the map)
-    CHK(launch_maxpool_bwd_idx(T.pool_arg, gcur, T.g_act1, C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st, ctx->act1,
-                               ctx->conv1_scale, B, amax_pre(ctx, T.g_act1, st)));
-    if (ctx->gemm_prec == ACTMI_PREC_F16X3 && w0 == 64 && T.det_ws && ctx->H1 == (g.image_h - 1) / 2 + 1 &&
-        ctx->W1 == (g.image_w - 1) / 2 + 1 && T.det_ws_floats >= (int64_t)C * 64 * 196) {
+    const float* g_act1_sc = nullptr;
+    CHK(produced_scale(ctx, st, &g_act1_sc, [&](unsigned* amax) {
+        return launch_maxpool_bwd_idx(T.pool_arg, gcur, T.g_act1, C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st, ctx->act1,
+                                      ctx->conv1_scale, B, amax);
+    }));
+    if (ctx->gemm_prec == ACTMI_PREC_F16X3 && w0 == 64 && ctx->H1 == (g.image_h - 1) / 2 + 1 && ctx->W1 == (g.image_w - 1) / 2 + 1 &&
+        T.det_ws_floats >= (int64_t)C * 64 * 196) {
         // the direct kernel (wgrad7.hip), accumulating into the packed gradient
-        const float* sc = dyn_scale(ctx, T.g_act1, w0, C * B * ctx->H1 * ctx->W1, w0, st);
-        if (launch_wgrad7x7s2(T.g_act1, T.xn4, T.conv1_gw, 1, T.det_ws, T.det_ws_floats, sc, C, B, g.image_h, g.image_w, ctx->H1,
+        if (launch_wgrad7x7s2(T.g_act1, T.xn4, T.conv1_gw, 1, T.det_ws, T.det_ws_floats, g_act1_sc, C, B, g.image_h, g.image_w, ctx->H1,
                               ctx->W1, st) != 0) {
             ctx->err = "wgrad7x7s2 launch failed";
             return ACTMI_E_LAUNCH;
@@ -966,7 +969,7 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         a.gA = (int64_t)B * ctx->H1 * ctx->W1 * w0; a.gB = (int64_t)B * g.image_h * g.image_w * 4; a.gC = (int64_t)w0 * 196;
         a.splitk = pick_splitk(w0, 196, C, a.K);
         if (a.splitk <= 1) { a.splitk = 0; a.res = a.C; a.ldres = 196; a.gRes = a.gC; }
-        a.a_scale_dev = dyn_scale(ctx, T.g_act1, w0, C * B * ctx->H1 * ctx->W1, w0, st);
+        a.a_scale_dev = g_act1_sc;
         CHK(tgemm(ctx, a, st));
     }
     // packed conv gradients -> OIHW state_dict gradients (one launch per layer over the cameras)
@@ -990,9 +993,8 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         else CHK(launch_reparam_kl_bwd(T.latent_info, T.eps, T.dz, T.d_latent_info, B, L, g.kl_weight * loss_scale, st));
         float* dcv = T.gB;                   // grad wrt the CVAE encoder output [B][n][D]: only the CLS rows are non-zero
         HIPCHK(hipMemsetAsync(dcv, 0, (size_t)B * n * D * 4, st));
-        CHK(lin_dgrad(ctx, T.d_latent_info, Lp, B, Lp, ctx->P("latent_proj.weight"), D, dcv, (int64_t)n * D, nullptr, nullptr, st));
-        CHK(lin_wgrad(ctx, T.d_latent_info, Lp, B, Lp, T.cv_out, (int64_t)n * D, D, nullptr, 0, GP("latent_proj.weight"),
-                      GP("latent_proj.bias"), st));
+        CHK(lin_bwd(ctx, measured(ctx, T.d_latent_info, Lp, B, Lp, st), ctx->P("latent_proj.weight"), D, T.cv_out, (int64_t)n * D, dcv,
+                    (int64_t)n * D, GP("latent_proj.weight"), GP("latent_proj.bias"), st));
         for (int l = g.enc_layers - 1; l >= 0; --l)
             CHK(enc_bwd(ctx, ctx->cvae[l], T.cv[l], T.gB, T.gB, ctx->P("pos_table"), B, n, T.ckpm, nullptr,
                         Drop{dp, T.drop_seed, (uint32_t)(8 * l)}, st));
@@ -1001,11 +1003,9 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         CHK(launch_small_linear_wgrad(dXc + D, (int64_t)n * D, T.qpos, S, GP("encoder_joint_proj.weight"), B, D, S, st));
         CHK(colsum_d(ctx, dXc + D, (int64_t)n * D, GP("encoder_joint_proj.bias"), B, D, st));
         CHK(launch_gather_rows(dXc, T.cmap, T.dXg, B * Q, D, st));
-        CHK(lin_wgrad(ctx, T.dXg, D, B * Q, D, T.actions, A, A, nullptr, 0, GP("encoder_action_proj.weight"),
+        CHK(lin_wgrad(ctx, measured(ctx, T.dXg, D, B * Q, D, st), T.actions, A, A, nullptr, 0, GP("encoder_action_proj.weight"),
                       GP("encoder_action_proj.bias"), st));
     }
-    if (LS != 1.f) CHK(launch_scale(T.gbase, ctx->ptotal, 1.f / LS, st));
-    T.grads_dirty = true;
     T.have_forward = false;
     return 0;
 }
@@ -1013,7 +1013,6 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
 int train_zero_grad(actmi_ctx* ctx, hipStream_t st) {
     if (!ctx->train) { ctx->err = "handle was created without enable_training"; return ACTMI_E_STATE; }
     HIPCHK(hipMemsetAsync(ctx->train->gbase, 0, (size_t)ctx->ptotal * 4, st));
-    ctx->train->grads_dirty = false;
     return 0;
 }
 
