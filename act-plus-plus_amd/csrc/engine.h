@@ -133,12 +133,11 @@ struct actmi_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // two camera halves of the ResNet trunk as two parallel branches (second stream): the tail of one half's launch is
     // filled by the other half's next launch (default on, ACTMI_CAM_PIPE=0 disables; engine_backbone)
-    hipStream_t pipe_stream = nullptr;             // branch 1 (non-null = branches available)
-    hipStream_t pipe_streams[3] = {nullptr, nullptr, nullptr};     // branches 1 .. nbranch-1 (pipe_streams[0] == pipe_stream)
-    hipEvent_t ev_pfork = nullptr, ev_pjoin = nullptr;
+    hipStream_t pipe_streams[3] = {nullptr, nullptr, nullptr};     // branches 1 .. nbranch-1, created when cam_pipe
+    hipEvent_t ev_pfork = nullptr;
     hipEvent_t ev_pjoins[3] = {nullptr, nullptr, nullptr};
     int nbranch = 2;                   // ACTMI_BRANCHES (2 .. 4)
-    bool cam_pipe = false;
+    bool cam_pipe = false;             // branches available
     int ln_split = 3;                  // split factor of a long-K product followed by a slice-summing LayerNorm (ACTMI_LN_SPLIT)
     int last_B = 0;                    // batch of the forward in flight (debug views)
     int policy_mult = 1;               // split-K policy counts the tiles of the WHOLE camera set while a half is being launched
@@ -153,8 +152,12 @@ struct actmi_ctx {
     // prepared weights
     std::vector<ConvLayer> convs;
     float *conv1_w = nullptr, *conv1_scale = nullptr, *conv1_bias = nullptr, *lut = nullptr;
-    float* conv1_wimg = nullptr;       // f16x3: conv1's LDS weight image per camera (launch_conv1_wimg), rebuilt with the weights
-    float *pos_tokens = nullptr, *dec_t1 = nullptr, *dec_q = nullptr, *tmp_vec = nullptr;
+    unsigned char* conv1_wimg = nullptr;   // f16x3: conv1's LDS weight image per camera (launch_conv1_wimg), rebuilt with the weights
+    float *pos_tokens = nullptr, *dec_t1 = nullptr, *dec_q = nullptr;
+    float* dec_sa = nullptr;           // [D] decoder layer 0: the constant self-attention row out_proj(b_v) + b_o
+    // [scale, bits] slots of launch_pow2_scale (the bits word is zero before a use): one for engine_measure_act_scale, one per
+    // convolution layer for the fused conv2 + downsample images measured at finalize
+    float *act_scale_slot = nullptr, *wf_scale_slots = nullptr;
     int* rowmap = nullptr;
     int rowmap_B = -1;
     std::vector<EncW> enc, cvae;
@@ -192,11 +195,23 @@ struct actmi_ctx {
         }                                                                                       \
     } while (0)
 
-// device memory owned by the handle (freed by engine_destroy)
-int dev_alloc(actmi_ctx* ctx, float** p, int64_t nfloats);
+// device memory owned by the handle (registered in ctx->allocs, freed by engine_destroy): count elements of T
+int dev_alloc_bytes(actmi_ctx* ctx, void** p, size_t bytes);
+template <class T>
+int dev_alloc(actmi_ctx* ctx, T** p, int64_t count) {
+    void* q = nullptr;
+    const int rc = dev_alloc_bytes(ctx, &q, (size_t)(count > 0 ? count : 1) * sizeof(T));
+    *p = static_cast<T*>(q);
+    return rc;
+}
+// a buffer of the handle, with the early return of CHK
+#define ALLOC(ptr, count) CHK(dev_alloc(ctx, &(ptr), (count)))
+// precision of the GEMMs issued right now: the training override (PrecScope) while a training call runs, else the handle's
+inline int engine_prec(const actmi_ctx* ctx) { return ctx->prec_override ? ctx->prec_override : ctx->gemm_prec; }
 
 int engine_create(const actmi_config* cfg, actmi_ctx** out);
-// forward GEMMs of a handle go through here: applies the handle's precision and swaps in pre-split weights
+// forward GEMMs of a handle go through here: applies the precision in force and, for a B operand inside the parameter arena
+// that does not already name a split image (b_split), swaps in the arena's image (same offset into p16base)
 // LayerNorm that follows a product (y = LN(C), optionally a second LN on top): when the product's contraction is split, the
 // LayerNorm kernel sums the slices itself (no combine pass); done tells the caller whether that happened
 struct LnFuse {
@@ -216,8 +231,13 @@ int gemm_slices(actmi_ctx* ctx, const GemmArgs& a, int S, float* ws, hipStream_t
 // y[M][N] = A[M][K] W[N][K]^T + bias
 GemmArgs linear_args(const float* A, int64_t lda, int M, int K, const float* W, int N, const float* bias, float* C, int64_t ldc);
 // one trunk convolution over the cameras [c0, c0 + nc) (in / out / res point at camera c0's camera-major NHWC map): the
-// implicit GEMM, and the direct kernel for a layer with cl.direct (its x_scale_dev is left to the caller)
-GemmArgs conv_gemm_args(const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out, const float* res, int relu);
+// implicit GEMM, and the direct kernel for a layer with cl.direct (its x_scale_dev is left to the caller).  The GEMM builders
+// name the weight operand themselves: under f16x3 the layer's split image with its scale and K order, else the plain weights
+GemmArgs conv_gemm_args(const actmi_ctx* ctx, const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out,
+                        const float* res, int relu);
+// conv2 of a downsample block with the branch in its contraction (f16x3): y = relu([W2' | Wd'] [y1 taps ; x at stride 2] + b)
+GemmArgs conv_fused_args(const actmi_ctx* ctx, const ConvLayer& cl, int B, int c0, int nc, const float* y1, const float* x,
+                         float* out);
 Conv3Args conv3_args(const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out, const float* res, int relu);
 // the stem (conv1 + FrozenBN + ReLU) of all cameras into ctx->act1
 Conv1Args stem_args(const actmi_ctx* ctx, const void* image, int fmt, int B);

@@ -123,41 +123,29 @@ void build_spec(actmi_ctx* c) {
 
 }  // namespace
 
-int dev_alloc(actmi_ctx* ctx, float** p, int64_t nfloats) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, (size_t)(nfloats > 0 ? nfloats : 1) * sizeof(float));
+int dev_alloc_bytes(actmi_ctx* ctx, void** p, size_t bytes) {
+    hipError_t e = hipMalloc(p, (bytes + 15) & ~(size_t)15);       // whole 16-byte vectors, whatever the element type
     if (e != hipSuccess) {
         ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
         return ACTMI_E_NOMEM;
     }
-    ctx->allocs.push_back(q);
-    *p = reinterpret_cast<float*>(q);
+    ctx->allocs.push_back(*p);
     return 0;
 }
 
 int ctx_gemm(actmi_ctx* ctx, GemmArgs a, hipStream_t st, int ws_half, LnFuse* ln) {
     if (ln) ln->done = false;
-    a.prec = ctx->prec_override ? ctx->prec_override : ctx->gemm_prec;
+    a.prec = engine_prec(ctx);
     // ws_half 0 / 1: this launch belongs to one of two concurrent branches, each with its own half of the slice workspace
     const int64_t ws_part = (ctx->splitk_ws_floats / ctx->nbranch) & ~(int64_t)3;
     float* const ws = ctx->splitk_ws ? ctx->splitk_ws + (ws_half > 0 ? ws_half * ws_part : 0) : nullptr;
     const int64_t ws_floats = ws_half >= 0 ? ws_part : ctx->splitk_ws_floats;
-    if (a.prec == ACTMI_PREC_F16X3 && a.tb == 0) {
-        // B is a weight matrix: use its pre-split image (same offsets) where one exists
-        if (a.Bw >= ctx->pbase && a.Bw < ctx->pbase + ctx->ptotal) {
-            a.b_scale = engine_weight_scale(ctx, a.Bw);
-            a.Bw = ctx->p16base + (a.Bw - ctx->pbase);
-            a.b_split = 1;
-        } else {
-            for (const ConvLayer& cl : ctx->convs) {
-                if (a.Bw >= cl.w && a.Bw < cl.w + (int64_t)ctx->cfg.num_cams * cl.cout * cl.K) {     // (a camera's slice of it)
-                    a.Bw = cl.w16 + (a.Bw - cl.w); a.b_split = 1; a.b_scale = cl.w16_scale; a.k_tap_inner = cl.k_tap_inner ? 1 : 0; break;
-                }
-                if (cl.wf && a.Bw >= cl.wf && a.Bw < cl.wf + (int64_t)ctx->cfg.num_cams * cl.cout * (cl.K + cl.Kx)) {
-                    a.Bw = cl.wf16 + (a.Bw - cl.wf); a.b_split = 1; a.b_scale = cl.wf16_scale; a.k_tap_inner = cl.k_tap_inner ? 1 : 0; break;
-                }
-            }
-        }
+    if (a.prec == ACTMI_PREC_F16X3 && a.tb == 0 && !a.b_split && a.Bw >= ctx->pbase && a.Bw < ctx->pbase + ctx->ptotal) {
+        // B is a parameter: its pre-split image sits at the same offset of the arena's image (the convolution builders name
+        // the images of the repacked weights themselves)
+        a.b_scale = engine_weight_scale(ctx, a.Bw);
+        a.Bw = ctx->p16base + (a.Bw - ctx->pbase);
+        a.b_split = 1;
     }
     // Small grids (B = 1-4 rollouts: layer3/4 convolutions, the K = 3200 FFN products): a launch of a few hundred tiles
     // leaves CUs idle and its lone workgroups latency-bound on a long K loop.  Split the contraction over blockIdx.z into
@@ -337,20 +325,42 @@ GemmArgs linear_args(const float* A, int64_t lda, int M, int K, const float* W, 
     return a;
 }
 
-// feature maps and weights are camera-major: a camera range is a pointer offset plus a group count
-GemmArgs conv_gemm_args(const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out, const float* res, int relu) {
+// feature maps and weights are camera-major: a camera range is a pointer offset plus a group count.  The part the plain and
+// the fused convolution share: the implicit GEMM over `in` with a contraction of K, and the weight operand [cam][cout][K] --
+// under f16x3 the split image w16 with its scale and K order, else the plain matrix w
+static GemmArgs conv_args(const actmi_ctx* ctx, const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out, int K,
+                          const float* w, const float* w16, float w16_scale) {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.mode = 1;
     a.A = in; a.H = cl.H; a.W = cl.W; a.Cin = cl.cin; a.KH = a.KW = cl.k; a.stride = cl.stride; a.pad = cl.pad;
     a.Ho = cl.Ho; a.Wo = cl.Wo; a.img_stride = (int64_t)cl.H * cl.W * cl.cin;
-    a.M = B * cl.Ho * cl.Wo; a.N = cl.cout; a.K = cl.K;
-    a.Bw = cl.w + (int64_t)c0 * cl.cout * cl.K; a.ldb = cl.K;
-    a.scale = cl.scale + (int64_t)c0 * cl.cout; a.bias = cl.bias + (int64_t)c0 * cl.cout; a.res = res; a.ldres = cl.cout; a.relu = relu;
+    a.M = B * cl.Ho * cl.Wo; a.N = cl.cout; a.K = K;
+    const bool split = engine_prec(ctx) == ACTMI_PREC_F16X3;
+    a.Bw = (split ? w16 : w) + (int64_t)c0 * cl.cout * K; a.ldb = K;
+    if (split) { a.b_split = 1; a.b_scale = w16_scale; a.k_tap_inner = cl.k_tap_inner ? 1 : 0; }
     a.C = out; a.ldc = cl.cout;
     a.groups = nc;
-    a.gA = (int64_t)B * cl.H * cl.W * cl.cin; a.gB = (int64_t)cl.cout * cl.K; a.gSB = cl.cout;
-    a.gC = (int64_t)a.M * cl.cout; a.gRes = a.gC;
+    a.gA = (int64_t)B * cl.H * cl.W * cl.cin; a.gB = (int64_t)cl.cout * K; a.gSB = cl.cout;
+    a.gC = (int64_t)a.M * cl.cout;
+    return a;
+}
+
+GemmArgs conv_gemm_args(const actmi_ctx* ctx, const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out,
+                        const float* res, int relu) {
+    GemmArgs a = conv_args(ctx, cl, B, c0, nc, in, out, cl.K, cl.w, cl.w16, cl.w16_scale);
+    a.scale = cl.scale + (int64_t)c0 * cl.cout; a.bias = cl.bias + (int64_t)c0 * cl.cout; a.res = res; a.ldres = cl.cout; a.relu = relu;
+    a.gRes = a.gC;
+    return a;
+}
+
+GemmArgs conv_fused_args(const actmi_ctx* ctx, const ConvLayer& cl, int B, int c0, int nc, const float* y1, const float* x,
+                         float* out) {
+    const ConvLayer& ds = ctx->convs[cl.ds_index];
+    GemmArgs a = conv_args(ctx, cl, B, c0, nc, y1, out, cl.K + cl.Kx, cl.wf, cl.wf16, cl.wf16_scale);
+    a.Ax = x; a.kx_begin = cl.K; a.Hx = ds.H; a.Wx = ds.W; a.Cx = ds.cin; a.stride_x = ds.stride;
+    a.gAx = (int64_t)B * ds.H * ds.W * ds.cin;
+    a.bias = cl.bias_f + (int64_t)c0 * cl.cout; a.relu = 1;
     return a;
 }
 
@@ -369,7 +379,7 @@ Conv1Args stem_args(const actmi_ctx* ctx, const void* image, int fmt, int B) {
     c1.bias = ctx->conv1_bias; c1.out = ctx->act1; c1.B = B; c1.C = g.num_cams; c1.H = g.image_h; c1.W = g.image_w;
     c1.Ho = ctx->H1; c1.Wo = ctx->W1; c1.Cout = g.base_width;
     c1.prec = ctx->gemm_prec;
-    c1.wimg = reinterpret_cast<const unsigned char*>(ctx->conv1_wimg);
+    c1.wimg = ctx->conv1_wimg;
     c1.wscale = ctx->conv1_wscale;
     return c1;
 }
@@ -423,58 +433,41 @@ float* actmi_ctx::P(const std::string& key) {
 // create / destroy
 // ------------------------------------------------------------------------------------------------
 
-int engine_create(const actmi_config* cfg, actmi_ctx** out) {
-    if (!cfg || !out) { g_create_error = "null argument"; return ACTMI_E_INVALID; }
-    const actmi_config& g = *cfg;
-    if (g.struct_size != (uint32_t)sizeof(actmi_config)) {
-        // the first field is readable whatever the caller's struct looks like; nothing else is trusted before this check
-        g_create_error = "actmi_config.struct_size is " + std::to_string(g.struct_size) + ", this library expects " +
-                         std::to_string(sizeof(actmi_config)) + " (binding built against a different include/actmi.h)";
-        return ACTMI_E_INVALID;
-    }
-    if (g.num_cams < 1 || g.max_batch < 1 || g.hidden_dim % g.nheads || (g.hidden_dim & 3) || (g.dim_feedforward & 3) ||
-        (g.base_width & 3) || g.base_width > 64 || g.enc_layers < 1 || g.dec_layers < 1) {
-        g_create_error = "unsupported configuration";
-        return ACTMI_E_INVALID;
-    }
-    const int hd = g.hidden_dim / g.nheads;
-    if (hd != 16 && hd != 32 && hd != 64) { g_create_error = "head_dim must be 16, 32 or 64"; return ACTMI_E_INVALID; }
-    if (g.vq && (g.vq_class < 1 || g.vq_dim < 1 || ((g.vq_class * g.vq_dim) & 3))) {
-        g_create_error = "vq needs positive vq_class, vq_dim with vq_class*vq_dim a multiple of 4";
-        return ACTMI_E_INVALID;
-    }
-    actmi_ctx* ctx = new actmi_ctx();
-    ctx->cfg = g;
-    if (hipGetDevice(&ctx->device) != hipSuccess) { g_create_error = "hipGetDevice failed"; delete ctx; return ACTMI_E_LAUNCH; }
-    ctx->ptotal = 0;
-    build_spec(ctx);
-    // geometry
-    ctx->H1 = conv_out(g.image_h, 7, 2, 3); ctx->W1 = conv_out(g.image_w, 7, 2, 3);
-    ctx->H2 = conv_out(ctx->H1, 3, 2, 1); ctx->W2 = conv_out(ctx->W1, 3, 2, 1);
-    int h = ctx->H2, w = ctx->W2;
-    for (int i = 0; i < 3; ++i) { h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1); }
-    ctx->fh = h; ctx->fw = w;
-    ctx->P_ = h * w;
-    ctx->N = 2 + g.num_cams * h * w;
-    if (h < 1 || w < 1) { g_create_error = "image too small"; delete ctx; return ACTMI_E_INVALID; }
+namespace {
 
-    auto fail = [&](int rc) { g_create_error = ctx->err; engine_destroy(ctx); return rc; };
-    int rc;
-    if ((rc = dev_alloc(ctx, &ctx->pbase, ctx->ptotal))) return fail(rc);
-    if (hipMemset(ctx->pbase, 0, ctx->ptotal * sizeof(float)) != hipSuccess) { ctx->err = "hipMemset failed"; return fail(ACTMI_E_LAUNCH); }
-    {
-        // forward precision of this handle: fp16-split products unless ACTMI_GEMM_PREC=f32 asks for the native fp32 MFMA
-        ctx->gemm_prec = env_gemm_prec(ACTMI_PREC_F16X3);
-        { const char* tp = getenv("ACTMI_TRAIN_PREC"); if (tp && tp[0] == 'b') ctx->train_prec = ACTMI_PREC_BF16; }
-        if (ctx->ptotal & 3) { ctx->err = "parameter arena not a multiple of 4 floats"; return fail(ACTMI_E_LAUNCH); }
-        if ((rc = dev_alloc(ctx, &ctx->p16base, ctx->ptotal))) return fail(rc);
-        { const char* vp = getenv("ACTMI_CONV1_VPOOL"); ctx->conv1_vpool = !(vp && vp[0] == '0'); }
-        const char* sk = getenv("ACTMI_FWD_SPLITK");
-        ctx->fwd_splitk = !(sk && sk[0] == '0');
-        // slices of split contractions (ctx_gemm checks the fit); 256 MB covers 4-way splits of the B = 8 launches
-        ctx->splitk_ws_floats = (int64_t)256 << 18;
-        if ((rc = dev_alloc(ctx, &ctx->splitk_ws, ctx->splitk_ws_floats))) return fail(rc);
-    }
+bool env_on(const char* name) {        // a switch that is on unless the variable starts with 0
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+}
+int env_int(const char* name, int unset) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
+}
+
+// the handle's switches, all read here (the launchers keep their own tuning aids)
+void read_switches(actmi_ctx* ctx) {
+    // forward precision of this handle: fp16-split products unless ACTMI_GEMM_PREC=f32 asks for the native fp32 MFMA
+    ctx->gemm_prec = env_gemm_prec(ACTMI_PREC_F16X3);
+    const char* tp = getenv("ACTMI_TRAIN_PREC");
+    if (tp && tp[0] == 'b') ctx->train_prec = ACTMI_PREC_BF16;
+    ctx->conv1_vpool = env_on("ACTMI_CONV1_VPOOL");
+    ctx->fwd_splitk = env_on("ACTMI_FWD_SPLITK");
+    ctx->act_calib = env_on("ACTMI_ACT_CALIB");
+    ctx->cam_pipe = env_on("ACTMI_CAM_PIPE");              // off: one branch (every launch spans all cameras)
+    ctx->ln_split = env_int("ACTMI_LN_SPLIT", ctx->ln_split);
+    ctx->nbranch = std::min(std::max(env_int("ACTMI_BRANCHES", ctx->nbranch), 2), 4);
+}
+
+// everything the handle owns on the device; on an error the caller destroys the handle with whatever was created
+int create_device_state(actmi_ctx* ctx) {
+    const actmi_config& g = ctx->cfg;
+    if (ctx->ptotal & 3) { ctx->err = "parameter arena not a multiple of 4 floats"; return ACTMI_E_LAUNCH; }
+    ALLOC(ctx->pbase, ctx->ptotal);
+    HIPCHK(hipMemset(ctx->pbase, 0, ctx->ptotal * sizeof(float)));
+    ALLOC(ctx->p16base, ctx->ptotal);
+    // slices of split contractions (ctx_gemm checks the fit); 256 MB covers 4-way splits of the B = 8 launches
+    ctx->splitk_ws_floats = (int64_t)256 << 18;
+    ALLOC(ctx->splitk_ws, ctx->splitk_ws_floats);
     {
         // tables of the weight range guard: parameter index of every 64-float slot, offsets / sizes for the amax kernel
         const int np = (int)ctx->params.size();
@@ -485,28 +478,14 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
             const int64_t g0 = ctx->params[i].off / 64, g1 = (i + 1 < np ? ctx->params[i + 1].off : ctx->ptotal) / 64;
             for (int64_t g = g0; g < g1; ++g) seg[(size_t)g] = i;
         }
-        float *f0 = nullptr, *f1 = nullptr, *f2 = nullptr, *f3 = nullptr, *f4 = nullptr, *f5 = nullptr;
-        if ((rc = dev_alloc(ctx, &f0, (int64_t)seg.size()))) return fail(rc);
-        if ((rc = dev_alloc(ctx, &f1, 2 * np))) return fail(rc);
-        if ((rc = dev_alloc(ctx, &f2, 2 * np))) return fail(rc);
-        if ((rc = dev_alloc(ctx, &f3, np))) return fail(rc);
-        if ((rc = dev_alloc(ctx, &f4, np))) return fail(rc);
-        if ((rc = dev_alloc(ctx, &f5, 4))) return fail(rc);
-        ctx->pseg64 = reinterpret_cast<int*>(f0);
-        ctx->poff_dev = reinterpret_cast<int64_t*>(f1);
-        ctx->pnumel_dev = reinterpret_cast<int64_t*>(f2);
-        ctx->pamax_dev = reinterpret_cast<unsigned*>(f3);
-        ctx->pscale_dev = f4;
-        ctx->flags = reinterpret_cast<uint32_t*>(f5);
+        ALLOC(ctx->pseg64, (int64_t)seg.size()); ALLOC(ctx->poff_dev, np); ALLOC(ctx->pnumel_dev, np);
+        ALLOC(ctx->pamax_dev, np); ALLOC(ctx->pscale_dev, np); ALLOC(ctx->flags, 4);
         ctx->pscale.assign(np, W16_SCALE);
-        if (hipMemcpy(ctx->pseg64, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(ctx->poff_dev, off.data(), np * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(ctx->pnumel_dev, numel.data(), np * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(ctx->pscale_dev, ctx->pscale.data(), np * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(ctx->flags, 0, 16) != hipSuccess) {
-            ctx->err = "hipMemcpy failed (weight scale tables)";
-            return fail(ACTMI_E_LAUNCH);
-        }
+        HIPCHK(hipMemcpy(ctx->pseg64, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ctx->poff_dev, off.data(), np * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ctx->pnumel_dev, numel.data(), np * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ctx->pscale_dev, ctx->pscale.data(), np * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(ctx->flags, 0, 16));
     }
     resolve_layers(ctx);
 
@@ -542,89 +521,90 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
                 ds.name.find("downsample") != std::string::npos && (k2.cin % 32) == 0 && (ds.cin % 32) == 0) {
                 k2.ds_index = (int)i + 2;
                 k2.Kx = ds.cin;
-                if ((rc = dev_alloc(ctx, &k2.wf, (int64_t)C * k2.cout * (k2.K + k2.Kx)))) return fail(rc);
-                if ((rc = dev_alloc(ctx, &k2.wf16, (int64_t)C * k2.cout * (k2.K + k2.Kx)))) return fail(rc);
-                if ((rc = dev_alloc(ctx, &k2.bias_f, (int64_t)C * k2.cout))) return fail(rc);
+                ALLOC(k2.wf, (int64_t)C * k2.cout * (k2.K + k2.Kx)); ALLOC(k2.wf16, (int64_t)C * k2.cout * (k2.K + k2.Kx));
+                ALLOC(k2.bias_f, (int64_t)C * k2.cout);
             }
         }
         for (auto& cl : ctx->convs) {
-            if ((rc = dev_alloc(ctx, &cl.w, (int64_t)C * cl.cout * cl.K))) return fail(rc);
-            if ((rc = dev_alloc(ctx, &cl.w16, (int64_t)C * cl.cout * cl.K))) return fail(rc);
-            if ((rc = dev_alloc(ctx, &cl.scale, (int64_t)C * cl.cout))) return fail(rc);
-            if ((rc = dev_alloc(ctx, &cl.bias, (int64_t)C * cl.cout))) return fail(rc);
+            ALLOC(cl.w, (int64_t)C * cl.cout * cl.K); ALLOC(cl.w16, (int64_t)C * cl.cout * cl.K);
+            ALLOC(cl.scale, (int64_t)C * cl.cout); ALLOC(cl.bias, (int64_t)C * cl.cout);
         }
     }
     const int D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N, B = g.max_batch;
-    if ((rc = dev_alloc(ctx, &ctx->conv1_w, (int64_t)C * w0 * 148))) return fail(rc);
+    ALLOC(ctx->conv1_w, (int64_t)C * w0 * 148);
     // (whatever the precision at create: actmi_set_gemm_prec may select f16x3 later)
-    if ((rc = dev_alloc(ctx, &ctx->conv1_wimg, (int64_t)C * conv1_wimg_bytes() / 4))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->conv1_scale, (int64_t)C * w0))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->conv1_bias, (int64_t)C * w0))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->lut, 768))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->pos_tokens, (int64_t)N * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->dec_t1, D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->dec_q, (int64_t)Q * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->tmp_vec, 4 * D))) return fail(rc);
-    {
-        float* rm = nullptr;
-        if ((rc = dev_alloc(ctx, &rm, (int64_t)B * C * ctx->P_))) return fail(rc);
-        ctx->rowmap = reinterpret_cast<int*>(rm);
-        ctx->rowmap_B = -1;
-    }
+    ALLOC(ctx->conv1_wimg, (int64_t)C * conv1_wimg_bytes());
+    ALLOC(ctx->conv1_scale, (int64_t)C * w0); ALLOC(ctx->conv1_bias, (int64_t)C * w0); ALLOC(ctx->lut, 768);
+    ALLOC(ctx->pos_tokens, (int64_t)N * D); ALLOC(ctx->dec_t1, D); ALLOC(ctx->dec_q, (int64_t)Q * D); ALLOC(ctx->dec_sa, D);
+    ALLOC(ctx->act_scale_slot, 2); ALLOC(ctx->wf_scale_slots, 2 * (int64_t)ctx->convs.size());
+    ALLOC(ctx->act_scale_dev, (int64_t)ctx->convs.size() + 4);
+    ALLOC(ctx->rowmap, (int64_t)B * C * ctx->P_);
+    ctx->rowmap_B = -1;
     // ---- activations (camera-major NHWC maps, token-major [B][N][D])
-    const int64_t n1 = (int64_t)C * B * ctx->H1 * ctx->W1 * w0;
-    const int64_t n2 = (int64_t)C * B * ctx->H2 * ctx->W2 * w0;
-    if ((rc = dev_alloc(ctx, &ctx->act1, n1))) return fail(rc);
-    for (int i = 0; i < 3; ++i)
-        if ((rc = dev_alloc(ctx, &ctx->buf[i], n2))) return fail(rc);
-    const int64_t BN_ = (int64_t)B * N;
-    if ((rc = dev_alloc(ctx, &ctx->X, BN_ * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->X1, BN_ * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->XP, BN_ * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->act_scale_dev, (int64_t)ctx->convs.size() + 4))) return fail(rc);
-    { const char* e1 = getenv("ACTMI_ACT_CALIB"); ctx->act_calib = !(e1 && e1[0] == '0'); }
-    if ((rc = dev_alloc(ctx, &ctx->Y, BN_ * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->ATT, BN_ * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->QKV, BN_ * 3 * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->Hb, BN_ * F))) return fail(rc);
-    const int64_t BQ = (int64_t)B * Q;
-    if ((rc = dev_alloc(ctx, &ctx->dO, BQ * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->dY, BQ * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->dT2, BQ * D))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->dH, BQ * F))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->hs, BQ * D))) return fail(rc);
-    {
-        const int64_t rows = std::max<int64_t>((int64_t)8 * B * Q, (int64_t)2 * B * N);
-        ctx->attn_ws_floats = rows * (D + 2 * g.nheads);
-        if ((rc = dev_alloc(ctx, &ctx->attn_ws, ctx->attn_ws_floats))) return fail(rc);
-    }
-    {
-        // second stream for the downsample branch of the ResNet blocks.  Not used while the per-launch profiler is on (its
-        // events bracket launches on one stream) or when forward contractions are being split (the side branch would share
-        // the slice workspace)
-        if (hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess) {
-            ctx->err = "cannot create the side stream";
-            return fail(ACTMI_E_LAUNCH);
-        }
-        if (const char* e8 = getenv("ACTMI_LN_SPLIT")) ctx->ln_split = atoi(e8);
-        const char* e5 = getenv("ACTMI_CAM_PIPE");
-        ctx->cam_pipe = !(e5 && e5[0] == '0');             // default on; ACTMI_CAM_PIPE=0: one branch (every launch spans all cameras)
-        if (const char* e6 = getenv("ACTMI_BRANCHES")) ctx->nbranch = atoi(e6);
-        if (ctx->nbranch < 2) ctx->nbranch = 2;
-        if (ctx->nbranch > 4) ctx->nbranch = 4;
-        if (ctx->cam_pipe) {
-            bool ok = hipEventCreateWithFlags(&ctx->ev_pfork, hipEventDisableTiming) == hipSuccess;
-            for (int i = 0; ok && i < ctx->nbranch - 1; ++i)
-                ok = hipStreamCreateWithFlags(&ctx->pipe_streams[i], hipStreamNonBlocking) == hipSuccess &&
-                     hipEventCreateWithFlags(&ctx->ev_pjoins[i], hipEventDisableTiming) == hipSuccess;
-            if (!ok) { ctx->err = "cannot create the branch streams"; return fail(ACTMI_E_LAUNCH); }
-            ctx->pipe_stream = ctx->pipe_streams[0];
+    ALLOC(ctx->act1, (int64_t)C * B * ctx->H1 * ctx->W1 * w0);
+    for (int i = 0; i < 3; ++i) ALLOC(ctx->buf[i], (int64_t)C * B * ctx->H2 * ctx->W2 * w0);
+    const int64_t BN_ = (int64_t)B * N, BQ = (int64_t)B * Q;
+    ALLOC(ctx->X, BN_ * D); ALLOC(ctx->X1, BN_ * D); ALLOC(ctx->XP, BN_ * D); ALLOC(ctx->Y, BN_ * D);
+    ALLOC(ctx->ATT, BN_ * D); ALLOC(ctx->QKV, BN_ * 3 * D); ALLOC(ctx->Hb, BN_ * F);
+    ALLOC(ctx->dO, BQ * D); ALLOC(ctx->dY, BQ * D); ALLOC(ctx->dT2, BQ * D); ALLOC(ctx->dH, BQ * F); ALLOC(ctx->hs, BQ * D);
+    ctx->attn_ws_floats = std::max<int64_t>((int64_t)8 * B * Q, (int64_t)2 * B * N) * (D + 2 * g.nheads);
+    ALLOC(ctx->attn_ws, ctx->attn_ws_floats);
+    // second stream for the downsample branch of the ResNet blocks.  Not used while the per-launch profiler is on (its
+    // events bracket launches on one stream) or when forward contractions are being split (the side branch would share
+    // the slice workspace)
+    HIPCHK(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    if (ctx->cam_pipe) {
+        HIPCHK(hipEventCreateWithFlags(&ctx->ev_pfork, hipEventDisableTiming));
+        for (int i = 0; i < ctx->nbranch - 1; ++i) {
+            HIPCHK(hipStreamCreateWithFlags(&ctx->pipe_streams[i], hipStreamNonBlocking));
+            HIPCHK(hipEventCreateWithFlags(&ctx->ev_pjoins[i], hipEventDisableTiming));
         }
     }
-    ctx->finalized = false;
-    if (g.enable_training && (rc = train_create(ctx))) return fail(rc);
+    return g.enable_training ? train_create(ctx) : 0;
+}
+
+}  // namespace
+
+int engine_create(const actmi_config* cfg, actmi_ctx** out) {
+    if (!cfg || !out) { g_create_error = "null argument"; return ACTMI_E_INVALID; }
+    const actmi_config& g = *cfg;
+    if (g.struct_size != (uint32_t)sizeof(actmi_config)) {
+        // the first field is readable whatever the caller's struct looks like; nothing else is trusted before this check
+        g_create_error = "actmi_config.struct_size is " + std::to_string(g.struct_size) + ", this library expects " +
+                         std::to_string(sizeof(actmi_config)) + " (binding built against a different include/actmi.h)";
+        return ACTMI_E_INVALID;
+    }
+    if (g.num_cams < 1 || g.max_batch < 1 || g.hidden_dim % g.nheads || (g.hidden_dim & 3) || (g.dim_feedforward & 3) ||
+        (g.base_width & 3) || g.base_width > 64 || g.enc_layers < 1 || g.dec_layers < 1) {
+        g_create_error = "unsupported configuration";
+        return ACTMI_E_INVALID;
+    }
+    const int hd = g.hidden_dim / g.nheads;
+    if (hd != 16 && hd != 32 && hd != 64) { g_create_error = "head_dim must be 16, 32 or 64"; return ACTMI_E_INVALID; }
+    if (g.vq && (g.vq_class < 1 || g.vq_dim < 1 || ((g.vq_class * g.vq_dim) & 3))) {
+        g_create_error = "vq needs positive vq_class, vq_dim with vq_class*vq_dim a multiple of 4";
+        return ACTMI_E_INVALID;
+    }
+    actmi_ctx* ctx = new actmi_ctx();
+    ctx->cfg = g;
+    if (hipGetDevice(&ctx->device) != hipSuccess) { g_create_error = "hipGetDevice failed"; delete ctx; return ACTMI_E_LAUNCH; }
+    ctx->ptotal = 0;
+    build_spec(ctx);
+    // geometry
+    ctx->H1 = conv_out(g.image_h, 7, 2, 3); ctx->W1 = conv_out(g.image_w, 7, 2, 3);
+    ctx->H2 = conv_out(ctx->H1, 3, 2, 1); ctx->W2 = conv_out(ctx->W1, 3, 2, 1);
+    int h = ctx->H2, w = ctx->W2;
+    for (int i = 0; i < 3; ++i) { h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1); }
+    ctx->fh = h; ctx->fw = w;
+    ctx->P_ = h * w;
+    ctx->N = 2 + g.num_cams * h * w;
+    if (h < 1 || w < 1) { g_create_error = "image too small"; delete ctx; return ACTMI_E_INVALID; }
+
+    read_switches(ctx);
+    const int rc = create_device_state(ctx);
+    if (rc) { g_create_error = ctx->err; engine_destroy(ctx); return rc; }
     *out = ctx;
     return 0;
 }
@@ -651,6 +631,44 @@ const char* engine_create_error() { return g_create_error.c_str(); }
 // ------------------------------------------------------------------------------------------------
 // finalize: weight preparation
 // ------------------------------------------------------------------------------------------------
+
+// fp16-split image w16 of a convolution's weight matrix w [cam][cout][K] (the plain or the fused one), its K index permuted
+// first where the layer's images are stored taps-inner; flag (optional): raised when a weight leaves the fp16 range of the image
+static int split_conv_image(actmi_ctx* ctx, const ConvLayer& cl, const float* w, float* w16, int K, float scale, uint32_t* flag,
+                            hipStream_t st) {
+    const int64_t rows = (int64_t)ctx->cfg.num_cams * cl.cout;
+    if (cl.k_tap_inner) {
+        CHK(launch_permute_conv_k(w, ctx->splitk_ws, rows, cl.k * cl.k, cl.cin, K, st));
+        w = ctx->splitk_ws;
+    }
+    CHK(launch_split16(w, w16, rows * K, scale, st, flag));
+    return 0;
+}
+
+// position table per token: rows 0,1 = additional_pos_embed (transformer.py:91-92); rows 2.. =
+// PositionEmbeddingSine(normalize=True) (position_encoding.py:30-52), identical for every camera
+static int build_pos_tokens(actmi_ctx* ctx) {
+    const int C = ctx->cfg.num_cams, D = ctx->cfg.hidden_dim, fh = ctx->fh, fw = ctx->fw, N = ctx->N, npf = D / 2;
+    std::vector<float> pos((size_t)N * D, 0.f);
+    HIPCHK(hipMemcpy(pos.data(), ctx->P("additional_pos_embed.weight"), 2 * D * sizeof(float), hipMemcpyDeviceToHost));
+    const float eps = 1e-6f, scale = (float)(2.0 * M_PI);
+    std::vector<float> dim_t(npf);
+    for (int k = 0; k < npf; ++k) dim_t[k] = powf(10000.f, (2.f * (float)(k / 2)) / (float)npf);
+    for (int hh = 0; hh < fh; ++hh)
+        for (int cam = 0; cam < C; ++cam)
+            for (int ww = 0; ww < fw; ++ww) {
+                float* row = &pos[(size_t)(2 + hh * (fw * C) + cam * fw + ww) * D];
+                const float y = (float)(hh + 1) / ((float)fh + eps) * scale;
+                const float x = (float)(ww + 1) / ((float)fw + eps) * scale;
+                for (int k = 0; k < npf; ++k) {
+                    const float py = y / dim_t[k], px = x / dim_t[k];
+                    row[k] = (k & 1) ? cosf(py) : sinf(py);
+                    row[npf + k] = (k & 1) ? cosf(px) : sinf(px);
+                }
+            }
+    HIPCHK(hipMemcpy(ctx->pos_tokens, pos.data(), pos.size() * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
 
 // device-side weight preparation; runs at finalize and after every optimizer step (all asynchronous on `st`)
 int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
@@ -687,12 +705,7 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
             // the input patch); the direct kernel of layer1 reads (r, s, c)
             cl.k_tap_inner = cl.k == 3 && (cl.cin % 32) == 0 && !cl.direct &&
                              (int64_t)C * cl.cout * (cl.K + cl.Kx) <= ctx->splitk_ws_floats;
-            if (cl.k_tap_inner) {
-                CHK(launch_permute_conv_k(cl.w, ctx->splitk_ws, (int64_t)C * cl.cout, cl.k * cl.k, cl.cin, cl.K, st));
-                CHK(launch_split16(ctx->splitk_ws, cl.w16, (int64_t)C * cl.cout * cl.K, cl.w16_scale, st, ctx->flags));
-            } else {
-                CHK(launch_split16(cl.w, cl.w16, (int64_t)C * cl.cout * cl.K, cl.w16_scale, st, ctx->flags));
-            }
+            CHK(split_conv_image(ctx, cl, cl.w, cl.w16, cl.K, cl.w16_scale, ctx->flags, st));
         }
         // blocks with a downsample branch: [bn2.scale * conv2.w | bn_ds.scale * ds.w] and the summed bias (FrozenBN statistics
         // are buffers: only the weights change under training, so the fold is redone with them)
@@ -702,12 +715,7 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
                 CHK(launch_fold_cat_w(cl.w, cl.scale, cl.bias, ds.w, ds.scale, ds.bias, cl.wf, cl.bias_f, C, cl.cout, cl.K, cl.Kx, st));
                 // (at finalize the scale is measured right after this and the image split again: no overflow report from the
                 // provisional one)
-                const float* src = cl.wf;
-                if (cl.k_tap_inner) {
-                    CHK(launch_permute_conv_k(cl.wf, ctx->splitk_ws, (int64_t)C * cl.cout, cl.k * cl.k, cl.cin, cl.K + cl.Kx, st));
-                    src = ctx->splitk_ws;
-                }
-                CHK(launch_split16(src, cl.wf16, (int64_t)C * cl.cout * (cl.K + cl.Kx), cl.wf16_scale, st, after_step ? ctx->flags : nullptr));
+                CHK(split_conv_image(ctx, cl, cl.wf, cl.wf16, cl.K + cl.Kx, cl.wf16_scale, after_step ? ctx->flags : nullptr, st));
             }
     }
     // learned rows of the token position table (transformer.py:91-92)
@@ -717,9 +725,9 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
     // out_proj(b_v) + b_o for every query; t1 = norm1 of it; q = (t1 + query_embed) Wq^T + bq.
     {
         const DecW& d = ctx->dec[0];
-        GemmArgs a = linear_args(d.self_attn.in_b + 2 * D, D, 1, D, d.self_attn.out_w, D, d.self_attn.out_b, ctx->tmp_vec, D);
+        GemmArgs a = linear_args(d.self_attn.in_b + 2 * D, D, 1, D, d.self_attn.out_w, D, d.self_attn.out_b, ctx->dec_sa, D);
         CHK(ctx_gemm(ctx, a, st));
-        CHK(launch_layernorm(ctx->tmp_vec, nullptr, 0, d.n1w, d.n1b, nullptr, nullptr, ctx->dec_t1, 1, D, 1e-5f, st, &ctx->err));
+        CHK(launch_layernorm(ctx->dec_sa, nullptr, 0, d.n1w, d.n1b, nullptr, nullptr, ctx->dec_t1, 1, D, 1e-5f, st, &ctx->err));
         GemmArgs q = linear_args(ctx->P("query_embed.weight"), D, Q, D, d.cross.in_w, D, d.cross.in_b, ctx->dec_q, D);
         q.A_add = ctx->dec_t1; q.ld_add = D; q.add_mod = 1; q.add_ncols = D;
         CHK(ctx_gemm(ctx, q, st));
@@ -729,8 +737,7 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
 
 int engine_finalize(actmi_ctx* ctx, hipStream_t st) {
     ctx->err.clear();
-    const actmi_config& g = ctx->cfg;
-    const int C = g.num_cams, D = g.hidden_dim;
+    const int C = ctx->cfg.num_cams;
     // 1. training scratch for the current precision (actmi_set_gemm_prec may have changed it since create)
     if (ctx->train) CHK(train_fit_prec(ctx));
     // 2. u8 -> normalised float LUT with the reference's arithmetic
@@ -740,29 +747,8 @@ int engine_finalize(actmi_ctx* ctx, hipStream_t st) {
         HIPCHK(hipMemcpyAsync(ctx->lut, lut.data(), 768 * sizeof(float), hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
     }
-    // 3. position table per token: rows 0,1 = additional_pos_embed (transformer.py:91-92); rows 2.. =
-    //    PositionEmbeddingSine(normalize=True) (position_encoding.py:30-52), identical for every camera
-    {
-        const int fh = ctx->fh, fw = ctx->fw, N = ctx->N, npf = D / 2;
-        std::vector<float> pos((size_t)N * D, 0.f);
-        HIPCHK(hipMemcpy(pos.data(), ctx->P("additional_pos_embed.weight"), 2 * D * sizeof(float), hipMemcpyDeviceToHost));
-        const float eps = 1e-6f, scale = (float)(2.0 * M_PI);
-        std::vector<float> dim_t(npf);
-        for (int k = 0; k < npf; ++k) dim_t[k] = powf(10000.f, (2.f * (float)(k / 2)) / (float)npf);
-        for (int hh = 0; hh < fh; ++hh)
-            for (int cam = 0; cam < C; ++cam)
-                for (int ww = 0; ww < fw; ++ww) {
-                    float* row = &pos[(size_t)(2 + hh * (fw * C) + cam * fw + ww) * D];
-                    const float y = (float)(hh + 1) / ((float)fh + eps) * scale;
-                    const float x = (float)(ww + 1) / ((float)fw + eps) * scale;
-                    for (int k = 0; k < npf; ++k) {
-                        const float py = y / dim_t[k], px = x / dim_t[k];
-                        row[k] = (k & 1) ? cosf(py) : sinf(py);
-                        row[npf + k] = (k & 1) ? cosf(px) : sinf(px);
-                    }
-                }
-        HIPCHK(hipMemcpy(ctx->pos_tokens, pos.data(), pos.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+    // 3. position table per token
+    CHK(build_pos_tokens(ctx));
     CHK(engine_calibrate_weight_scales(ctx, st));
     CHK(engine_prepare_weights(ctx, st));
     if (ctx->gemm_prec == ACTMI_PREC_F16X3) {
@@ -771,27 +757,21 @@ int engine_finalize(actmi_ctx* ctx, hipStream_t st) {
         // other image) and split again with that scale; training keeps it and raises ACTMI_FLAG_WEIGHT on overflow
         std::vector<ConvLayer*> fl;
         for (auto& cl : ctx->convs) if (cl.wf) fl.push_back(&cl);
-        if (!fl.empty() && 2 * fl.size() <= (size_t)(4 * ctx->cfg.hidden_dim)) {
-            HIPCHK(hipMemsetAsync(ctx->tmp_vec, 0, 2 * fl.size() * sizeof(float), st));
+        if (!fl.empty()) {
+            HIPCHK(hipMemsetAsync(ctx->wf_scale_slots, 0, 2 * fl.size() * sizeof(float), st));
             for (size_t i = 0; i < fl.size(); ++i) {
-                const int64_t Kf = fl[i]->K + fl[i]->Kx;
-                CHK(launch_pow2_scale(fl[i]->wf, Kf, ctx->cfg.num_cams * fl[i]->cout, (int)Kf, ctx->tmp_vec + 2 * i, st));
+                const int Kf = fl[i]->K + fl[i]->Kx;
+                CHK(launch_pow2_scale(fl[i]->wf, Kf, C * fl[i]->cout, Kf, ctx->wf_scale_slots + 2 * i, st));
             }
             std::vector<float> sc(2 * fl.size());
-            HIPCHK(hipMemcpyAsync(sc.data(), ctx->tmp_vec, sc.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(sc.data(), ctx->wf_scale_slots, sc.size() * sizeof(float), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             for (size_t i = 0; i < fl.size(); ++i) {
-                float v = sc[2 * i];
-                if (!(v > 0.f) || !(v <= 3.0e38f)) { ctx->err = "fused weights of " + fl[i]->name + " are not finite"; return ACTMI_E_INVALID; }
-                fl[i]->wf16_scale = v < 4096.f ? v : 4096.f;
-                const float* src = fl[i]->wf;
-                if (fl[i]->k_tap_inner) {
-                    CHK(launch_permute_conv_k(fl[i]->wf, ctx->splitk_ws, (int64_t)ctx->cfg.num_cams * fl[i]->cout, fl[i]->k * fl[i]->k, fl[i]->cin,
-                                              fl[i]->K + fl[i]->Kx, st));
-                    src = ctx->splitk_ws;
-                }
-                CHK(launch_split16(src, fl[i]->wf16, (int64_t)ctx->cfg.num_cams * fl[i]->cout * (fl[i]->K + fl[i]->Kx),
-                                   fl[i]->wf16_scale, st, ctx->flags));
+                ConvLayer& cl = *fl[i];
+                const float v = sc[2 * i];
+                if (!(v > 0.f) || !(v <= 3.0e38f)) { ctx->err = "fused weights of " + cl.name + " are not finite"; return ACTMI_E_INVALID; }
+                cl.wf16_scale = v < 4096.f ? v : 4096.f;
+                CHK(split_conv_image(ctx, cl, cl.wf, cl.wf16, cl.K + cl.Kx, cl.wf16_scale, ctx->flags, st));
             }
         }
     }
@@ -815,7 +795,7 @@ int engine_finalize(actmi_ctx* ctx, hipStream_t st) {
 int engine_measure_act_scale(actmi_ctx* ctx, const float* x, int64_t rows, int cols, hipStream_t st, float* out) {
     *out = 1.f;
     if (rows <= 0 || rows > 0x7fffffff) return 0;
-    float* slot = ctx->tmp_vec + 2;             // [scale, bits word]: the word must be zero before the first use
+    float* slot = ctx->act_scale_slot;          // [scale, bits word]: the word must be zero before the first use
     HIPCHK(hipMemsetAsync(slot, 0, 2 * sizeof(float), st));
     CHK(launch_pow2_scale(x, cols, (int)rows, cols, slot, st));
     float s = 1.f;
@@ -909,16 +889,14 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
     if (ctx->stop_stage == "conv1" || ctx->stop_stage == "maxpool") return 1;
     // one convolution of the trunk for the cameras [c0, c0 + nc) (feature maps and weights are camera-major, so a camera range
     // is a pointer offset + a group count); half >= 0: one of two concurrent branches (own half of the slice workspace)
-    auto run_conv_on = [&](const ConvLayer& cl, const float* in, float* out, const float* res, int relu, hipStream_t cs, int c0,
+    auto run_conv_on = [&](ConvLayer& cl, const float* in, float* out, const float* res, int relu, hipStream_t cs, int c0,
                            int nc, int half) -> int {
         // (in / out / res already point at the range's first camera: run_layers)
         const int cl_index = (int)(&cl - ctx->convs.data());
         if (ctx->calibrating) {
             // calibration forward (actmi_finalize): measure this layer's input, fix its pre-scale, THEN run the layer with it
             // (so that a map far outside the fp16 range does not poison the measurements downstream); one host sync per layer
-            float sc = 1.f;
-            CHK(engine_measure_act_scale(ctx, in, (int64_t)nc * B * cl.H * cl.W, cl.cin, cs, &sc));
-            const_cast<ConvLayer&>(cl).a_scale = sc;
+            CHK(engine_measure_act_scale(ctx, in, (int64_t)nc * B * cl.H * cl.W, cl.cin, cs, &cl.a_scale));
             HIPCHK(hipMemcpyAsync(ctx->act_scale_dev + cl_index, &cl.a_scale, sizeof(float), hipMemcpyHostToDevice, cs));
             HIPCHK(hipStreamSynchronize(cs));
         }
@@ -928,48 +906,28 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
             if (cl.a_scale != 1.f) c3.x_scale_dev = ctx->act_scale_dev + cl_index;
             return launch_conv3x3_c64(c3, cs, &ctx->err);
         }
-        GemmArgs a = conv_gemm_args(cl, B, c0, nc, in, out, res, relu);
+        GemmArgs a = conv_gemm_args(ctx, cl, B, c0, nc, in, out, res, relu);
         if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.a_scale != 1.f) a.a_scale = cl.a_scale;
         return ctx_gemm(ctx, a, cs, half);
     };
     // the side branch needs the split-K workspace for itself: only taken when the main stream's launches do not split
     // (not while the per-launch profiler brackets launches with events, nor for the debug early-outs)
-    const bool pipe = ctx->cam_pipe && ctx->pipe_stream && C >= 2 && !prof_enabled() && ctx->stop_stage.empty() && !ctx->calibrating;
+    const bool pipe = ctx->cam_pipe && C >= 2 && !prof_enabled() && ctx->stop_stage.empty() && !ctx->calibrating;
     const bool fork_ds = ctx->side_stream != nullptr && !pipe && !ctx->calibrating;
-    float* final_cur = nullptr;
     // layer1 .. layer4 for the cameras [c0, c0 + nc) on stream ls
     auto run_layers = [&](int c0, int nc, hipStream_t ls, int half) -> int {
         // the range's maps live at the offset of its first camera in the POOLED map (the largest per-camera block): every
         // later map of the range fits behind it without reaching the next range's block, whatever layer the other branch is in
         const int64_t hb = (int64_t)c0 * B * ctx->H2 * ctx->W2 * w0;
         float *cur = ctx->buf[0] + hb, *s1 = ctx->buf[1] + hb, *s2 = ctx->buf[2] + hb;
-        auto run_conv = [&](const ConvLayer& cl, const float* in, float* out, const float* res, int relu) -> int {
+        auto run_conv = [&](ConvLayer& cl, const float* in, float* out, const float* res, int relu) -> int {
             return run_conv_on(cl, in, out, res, relu, ls, c0, nc, half);
-        };
-        // conv2 of a downsample block with the branch in its contraction: y = relu([W2' | Wd'] [y1 taps ; x at stride 2] + b)
-        auto run_conv_fused = [&](const ConvLayer& cl, const float* y1, const float* x, float* out) -> int {
-            const ConvLayer& ds = ctx->convs[cl.ds_index];
-            const int Kf = cl.K + cl.Kx;
-            GemmArgs a;
-            memset(&a, 0, sizeof(a));
-            a.mode = 1;
-            a.A = y1; a.H = cl.H; a.W = cl.W; a.Cin = cl.cin; a.KH = a.KW = cl.k; a.stride = cl.stride; a.pad = cl.pad;
-            a.Ho = cl.Ho; a.Wo = cl.Wo; a.img_stride = (int64_t)cl.H * cl.W * cl.cin;
-            a.M = B * cl.Ho * cl.Wo; a.N = cl.cout; a.K = Kf;
-            a.Ax = x; a.kx_begin = cl.K; a.Hx = ds.H; a.Wx = ds.W; a.Cx = ds.cin; a.stride_x = ds.stride;
-            a.gAx = (int64_t)B * ds.H * ds.W * ds.cin;
-            a.Bw = cl.wf + (int64_t)c0 * cl.cout * Kf; a.ldb = Kf; a.bias = cl.bias_f + (int64_t)c0 * cl.cout; a.relu = 1;
-            a.C = out; a.ldc = cl.cout;
-            a.groups = nc;
-            a.gA = (int64_t)B * cl.H * cl.W * cl.cin; a.gB = (int64_t)cl.cout * Kf; a.gSB = cl.cout;
-            a.gC = (int64_t)a.M * cl.cout;
-            return ctx_gemm(ctx, a, ls, half);
         };
         size_t ci = 0;
         for (int li = 1; li <= 4; ++li) {
             for (int bi = 0; bi < 2; ++bi) {
-                const ConvLayer& k1 = ctx->convs[ci++];
-                const ConvLayer& k2 = ctx->convs[ci++];
+                ConvLayer& k1 = ctx->convs[ci++];
+                ConvLayer& k2 = ctx->convs[ci++];
                 const bool has_ds = (bi == 0 && li > 1);
                 if (has_ds && k2.wf && ctx->gemm_prec == ACTMI_PREC_F16X3 && !ctx->calibrating && k2.a_scale == 1.f &&
                     ctx->convs[k2.ds_index].a_scale == 1.f) {
@@ -977,10 +935,10 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
                     // two launches instead of three, and the branch's map is neither written nor read back
                     ++ci;                                        // (the downsample layer's own entry)
                     CHK(run_conv(k1, cur, s1, nullptr, 1));
-                    CHK(run_conv_fused(k2, s1, cur, s2));
+                    CHK(ctx_gemm(ctx, conv_fused_args(ctx, k2, B, c0, nc, s1, cur, s2), ls, half));
                     std::swap(cur, s2);                          // x stays live until conv2 has read it: the output goes to s2
                 } else if (has_ds) {
-                    const ConvLayer& ds = ctx->convs[ci++];
+                    ConvLayer& ds = ctx->convs[ci++];
                     if (fork_ds) {
                         // the 1x1 / stride-2 downsample (23-50 us, HBM bound, few workgroups) only needs the block input: it
                         // runs on a second stream beside the block's first 3x3 convolution (fork / join through events: in a
@@ -1009,11 +967,10 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
                 if (bi == 1 && c0 == 0) {
                     const std::string nm = "layer" + std::to_string(li);
                     ctx->dbg[nm] = {cur, (int64_t)C * B * k2.Ho * k2.Wo * k2.cout};
-                    if (ctx->stop_stage == nm) { final_cur = cur; return 1; }    // debug early-out: buffers rotate, views alias
+                    if (ctx->stop_stage == nm) return 1;    // debug early-out: buffers rotate, views alias
                 }
             }
         }
-        final_cur = cur;
         // input_proj (1x1 convolution, detr_vae.py:184) of the range's layer4 maps, rows scattered to their tokens
         GemmArgs ip = linear_args(cur, 8 * w0, nc * B * ctx->P_, 8 * w0, ctx->P("input_proj.weight"), D, ctx->P("input_proj.bias"),
                                   ctx->X, D);
@@ -1043,7 +1000,6 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
         const int rc = run_layers(0, C, st, -1);
         if (rc != 0) return rc;
     }
-    (void)final_cur;
     return 0;
 }
 
@@ -1205,7 +1161,7 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
     };
     // encoder + decoder as two concurrent branches over the two halves of the batch (samples are independent): the 304-workgroup
     // launches (out-proj, FFN2: 59 % of the 512 residency slots) of one half run beside the other half's launches
-    const bool tpipe = ctx->cam_pipe && ctx->pipe_stream && B >= 2 && !prof_enabled() && ctx->stop_stage.empty();
+    const bool tpipe = ctx->cam_pipe && B >= 2 && !prof_enabled() && ctx->stop_stage.empty();
     ctx->dbg["memory"] = {ctx->X, (int64_t)B * N * D};
     if (tpipe) {
         const int nb = B < ctx->nbranch ? B : ctx->nbranch;

@@ -28,7 +28,7 @@ GemmArgs G0() {
 // B is a parameter), the backward forms take the handle precision directly
 int tgemm(actmi_ctx* ctx, GemmArgs a, hipStream_t st) {
     if (a.ta == 0 && a.tb == 0 && a.mode != 2) return ctx_gemm(ctx, a, st);
-    a.prec = ctx->prec_override ? ctx->prec_override : ctx->gemm_prec;
+    a.prec = engine_prec(ctx);
     TrainState* T = ctx->train;
     if (a.splitk > 1 && a.split_stride == 0 && !a.rowmap && !a.C2 && !a.mask && a.groups_inner == 0) {
         // C += A B with the contraction split over the grid.  The atomic form (every split adds into C) is not run-to-run
@@ -444,9 +444,7 @@ int train_create(actmi_ctx* ctx) {
     TrainState& T = *ctx->train;
     const int B = g.max_batch, C = g.num_cams, D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N,
               w0 = g.base_width, H = g.nheads, L = g.latent_dim, A = g.action_dim;
-    int rc;
-#define TA(ptr, n) if ((rc = dev_alloc(ctx, &(ptr), (n)))) return rc
-    TA(T.gbase, ctx->ptotal); TA(T.mbase, ctx->ptotal); TA(T.vbase, ctx->ptotal);
+    ALLOC(T.gbase, ctx->ptotal); ALLOC(T.mbase, ctx->ptotal); ALLOC(T.vbase, ctx->ptotal);
     if (hipMemset(T.gbase, 0, ctx->ptotal * 4) != hipSuccess || hipMemset(T.mbase, 0, ctx->ptotal * 4) != hipSuccess ||
         hipMemset(T.vbase, 0, ctx->ptotal * 4) != hipSuccess) { ctx->err = "hipMemset failed"; return ACTMI_E_LAUNCH; }
     {
@@ -457,18 +455,16 @@ int train_create(actmi_ctx* ctx) {
             if (!p.is_buffer && p.key.rfind("is_pad_head", 0) != 0) gcode = p.key.find("backbone") != std::string::npos ? 2 : 1;
             for (int64_t c = p.off / 64; c < (p.off + ((p.numel + 63) & ~int64_t(63))) / 64; ++c) grp[(size_t)c] = gcode;
         }
-        float* gp = nullptr;
-        TA(gp, (int64_t)(grp.size() + 3) / 4);
-        T.group = reinterpret_cast<uint8_t*>(gp);
+        ALLOC(T.group, (int64_t)grp.size());
         if (hipMemcpy(T.group, grp.data(), grp.size(), hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "hipMemcpy failed"; return ACTMI_E_LAUNCH; }
     }
     // backbone saves
     const int64_t n2 = (int64_t)C * B * ctx->H2 * ctx->W2 * w0;
     const int64_t n1 = (int64_t)C * B * ctx->H1 * ctx->W1 * w0;
-    TA(T.xn4, (int64_t)C * B * g.image_h * g.image_w * 4);
-    TA(T.pool, n2);
-    TA(T.g_act1, n1);
-    for (int i = 0; i < 4; ++i) TA(T.gbuf[i], n2);
+    ALLOC(T.xn4, (int64_t)C * B * g.image_h * g.image_w * 4);
+    ALLOC(T.pool, n2);
+    ALLOC(T.g_act1, n1);
+    for (int i = 0; i < 4; ++i) ALLOC(T.gbuf[i], n2);
     {
         size_t ci = 0;
         for (int li = 1; li <= 4; ++li)
@@ -478,80 +474,75 @@ int train_create(actmi_ctx* ctx) {
                 bs.c1 = (int)ci; bs.c2 = (int)ci + 1; bs.ds = (bi == 0 && li > 1) ? (int)ci + 2 : -1;
                 ci += (bs.ds >= 0) ? 3 : 2;
                 const int64_t nout = (int64_t)C * B * k1.Ho * k1.Wo * k1.cout;
-                TA(bs.y1, nout); TA(bs.out, nout);
+                ALLOC(bs.y1, nout); ALLOC(bs.out, nout);
                 T.blocks.push_back(bs);
             }
     }
     for (auto& cl : ctx->convs) {
         float *gw, *wd;
-        TA(gw, (int64_t)C * cl.cout * cl.K); TA(wd, (int64_t)C * cl.cin * cl.k * cl.k * cl.cout);
+        ALLOC(gw, (int64_t)C * cl.cout * cl.K); ALLOC(wd, (int64_t)C * cl.cin * cl.k * cl.k * cl.cout);
         T.conv_gw.push_back(gw); T.conv_wd.push_back(wd);
     }
     T.conv_wd16.assign(ctx->convs.size(), nullptr);
-    TA(T.conv1_gw, (int64_t)C * w0 * 196);
-    {
-        float* pa = nullptr;           // argmax codes of the stem max-pool, one byte per pooled element
-        TA(pa, ((int64_t)C * B * ctx->H2 * ctx->W2 * w0 + 3) / 4);
-        T.pool_arg = reinterpret_cast<uint8_t*>(pa);
-    }
-    TA(T.scale_slots, 2 * SCALE_SLOTS);
+    ALLOC(T.conv1_gw, (int64_t)C * w0 * 196);
+    ALLOC(T.pool_arg, n2);             // argmax codes of the stem max-pool, one byte per pooled element
+    ALLOC(T.scale_slots, 2 * SCALE_SLOTS);
     // deterministic reductions: slices of split weight-gradient contractions and per-block partials of the LayerNorm /
     // bias-gradient sums, all combined in a fixed order (no float atomics: gradients are bitwise repeatable)
     if (hipEventCreateWithFlags(&T.ev_phase1, hipEventDisableTiming) != hipSuccess) { ctx->err = "hipEventCreate failed"; return ACTMI_E_LAUNCH; }
     T.det_ws_floats = (int64_t)48 << 20;
-    TA(T.det_ws, T.det_ws_floats);
+    ALLOC(T.det_ws, T.det_ws_floats);
     if (hipMemset(T.scale_slots, 0, 2 * SCALE_SLOTS * 4) != hipSuccess) { ctx->err = "hipMemset failed"; return ACTMI_E_LAUNCH; }
     // transformer saves
     auto alloc_enc = [&](std::vector<EncSave>& v, int n, float* first_in) -> int {
         const int64_t M = (int64_t)B * n;
         for (int l = 0; l < g.enc_layers; ++l) {
             EncSave s;
-            if (l == 0 && first_in) s.x_in = first_in; else TA(s.x_in, M * D);
-            TA(s.QKV, M * 3 * D); TA(s.ATT, M * D); TA(s.Y1, M * D); TA(s.X1, M * D); TA(s.Hb, M * F); TA(s.Y2, M * D);
-            TA(s.lse, (int64_t)B * H * n);
+            if (l == 0 && first_in) s.x_in = first_in; else ALLOC(s.x_in, M * D);
+            ALLOC(s.QKV, M * 3 * D); ALLOC(s.ATT, M * D); ALLOC(s.Y1, M * D); ALLOC(s.X1, M * D); ALLOC(s.Hb, M * F); ALLOC(s.Y2, M * D);
+            ALLOC(s.lse, (int64_t)B * H * n);
             v.push_back(s);
         }
         return 0;
     };
-    if ((rc = alloc_enc(T.en, N, ctx->X))) return rc;
-    TA(T.mem, (int64_t)B * N * D);
+    CHK(alloc_enc(T.en, N, ctx->X));
+    ALLOC(T.mem, (int64_t)B * N * D);
     if (g.has_cvae_encoder) {
-        TA(T.Xc, (int64_t)B * (Q + 2) * D);
-        if ((rc = alloc_enc(T.cv, Q + 2, T.Xc))) return rc;
-        TA(T.cv_out, (int64_t)B * (Q + 2) * D);
-        float* t1; TA(t1, (int64_t)B * Q); T.cmap = reinterpret_cast<int*>(t1);
-        float* t2; TA(t2, ((int64_t)B * (Q + 2) + 3) / 4 + 1); T.ckpm = reinterpret_cast<uint8_t*>(t2);
+        ALLOC(T.Xc, (int64_t)B * (Q + 2) * D);
+        CHK(alloc_enc(T.cv, Q + 2, T.Xc));
+        ALLOC(T.cv_out, (int64_t)B * (Q + 2) * D);
+        ALLOC(T.cmap, (int64_t)B * Q);
+        ALLOC(T.ckpm, (int64_t)B * (Q + 2) + 4);         // (+4 here and for is_pad: the slack they had when counted in floats)
         const int Lp = g.vq ? g.vq_class * g.vq_dim : 2 * L, Lz = g.vq ? g.vq_class * g.vq_dim : L;
-        TA(T.latent_info, (int64_t)B * Lp); TA(T.z, (int64_t)B * Lz); TA(T.eps, (int64_t)B * Lz);
-        TA(T.d_latent_info, (int64_t)B * Lp); TA(T.dz, (int64_t)B * Lz);
-        if (g.vq) TA(T.vq_probs, (int64_t)B * Lp);
+        ALLOC(T.latent_info, (int64_t)B * Lp); ALLOC(T.z, (int64_t)B * Lz); ALLOC(T.eps, (int64_t)B * Lz);
+        ALLOC(T.d_latent_info, (int64_t)B * Lp); ALLOC(T.dz, (int64_t)B * Lz);
+        if (g.vq) ALLOC(T.vq_probs, (int64_t)B * Lp);
     }
     // decoder layer 0 saves
     const int64_t BQ = (int64_t)B * Q;
-    TA(T.sa_tmp, D); TA(T.t1, D); TA(T.qin, (int64_t)Q * D); TA(T.dq, (int64_t)Q * D);
-    TA(T.KV, (int64_t)B * N * 2 * D); TA(T.lse_c, (int64_t)B * H * Q); TA(T.Oc, BQ * D); TA(T.Y2pre, BQ * D);
-    TA(T.T2, BQ * D); TA(T.Hd, BQ * F); TA(T.Y3pre, BQ * D); TA(T.T3, BQ * D); TA(T.hs, BQ * D);
-    TA(T.a_hat, BQ * A); TA(T.actions, BQ * A);
-    TA(T.qkd, (int64_t)Q * 2 * D); TA(T.sO, BQ * D); TA(T.lse_s, (int64_t)B * H * Q); TA(T.saB, BQ * D); TA(T.T1B, BQ * D);
-    TA(T.dqB, BQ * D); TA(T.gT1, BQ * D); TA(T.dsaB, BQ * D); TA(T.dqkB, BQ * 2 * D); TA(T.dvB, BQ * D); TA(T.dqk_d, (int64_t)Q * 2 * D);
-    TA(T.tmpQD, (int64_t)Q * D);
-    { float* t; TA(t, (BQ + 3) / 4 + 1); T.is_pad = reinterpret_cast<uint8_t*>(t); }
-    TA(T.losses, 4 + 520);               // [l1, kl, loss, -] + block partials of the l1 sum (launch_losses)
+    ALLOC(T.sa_tmp, D); ALLOC(T.t1, D); ALLOC(T.qin, (int64_t)Q * D); ALLOC(T.dq, (int64_t)Q * D);
+    ALLOC(T.KV, (int64_t)B * N * 2 * D); ALLOC(T.lse_c, (int64_t)B * H * Q); ALLOC(T.Oc, BQ * D); ALLOC(T.Y2pre, BQ * D);
+    ALLOC(T.T2, BQ * D); ALLOC(T.Hd, BQ * F); ALLOC(T.Y3pre, BQ * D); ALLOC(T.T3, BQ * D); ALLOC(T.hs, BQ * D);
+    ALLOC(T.a_hat, BQ * A); ALLOC(T.actions, BQ * A);
+    ALLOC(T.qkd, (int64_t)Q * 2 * D); ALLOC(T.sO, BQ * D); ALLOC(T.lse_s, (int64_t)B * H * Q); ALLOC(T.saB, BQ * D); ALLOC(T.T1B, BQ * D);
+    ALLOC(T.dqB, BQ * D); ALLOC(T.gT1, BQ * D); ALLOC(T.dsaB, BQ * D); ALLOC(T.dqkB, BQ * 2 * D); ALLOC(T.dvB, BQ * D); ALLOC(T.dqk_d, (int64_t)Q * 2 * D);
+    ALLOC(T.tmpQD, (int64_t)Q * D);
+    ALLOC(T.is_pad, BQ + 4);
+    ALLOC(T.losses, 4 + 520);               // [l1, kl, loss, -] + block partials of the l1 sum (launch_losses)
     // backward scratch
     const int64_t MN = (int64_t)B * N;
-    TA(T.gA, MN * D); TA(T.gB, MN * D); TA(T.gC, MN * D); TA(T.gH, MN * F); TA(T.gQKV, MN * 3 * D);
-    TA(T.delta, (int64_t)B * H * (N > Q + 2 ? N : Q + 2));
-    if ((rc = train_fit_prec(ctx))) return rc;
-    TA(T.dXg, (int64_t)B * (C * ctx->P_ > Q ? C * ctx->P_ : Q) * D);
-    TA(T.tmp2BD, (int64_t)2 * B * D); TA(T.tmpD, 4 * D); TA(T.dqb, BQ * D);
+    ALLOC(T.gA, MN * D); ALLOC(T.gB, MN * D); ALLOC(T.gC, MN * D); ALLOC(T.gH, MN * F); ALLOC(T.gQKV, MN * 3 * D);
+    ALLOC(T.delta, (int64_t)B * H * (N > Q + 2 ? N : Q + 2));
+    CHK(train_fit_prec(ctx));
+    ALLOC(T.dXg, (int64_t)B * (C * ctx->P_ > Q ? C * ctx->P_ : Q) * D);
+    ALLOC(T.tmp2BD, (int64_t)2 * B * D); ALLOC(T.tmpD, 4 * D); ALLOC(T.dqb, BQ * D);
     {
         std::vector<int> rows(2 * B);
         for (int b = 0; b < B; ++b) { rows[2 * b] = b * N; rows[2 * b + 1] = b * N + 1; }
-        float* t; TA(t, 2 * B); T.pos_rows = reinterpret_cast<int*>(t);
+        ALLOC(T.pos_rows, 2 * B);
         if (hipMemcpy(T.pos_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "hipMemcpy failed"; return ACTMI_E_LAUNCH; }
         // note: rows are for the max batch layout; entries b < B_call are valid for any smaller batch too
     }
-#undef TA
     return 0;
 }
 
@@ -567,7 +558,6 @@ int train_fit_prec(actmi_ctx* ctx) {
         (void)hipFree(p);
         p = nullptr;
     };
-    int rc;
     // materialised P / dS: decoder cross-attention (Q x N), the CVAE encoder ((Q+2)^2), and -- only without the fused kernels --
     // the encoder's N x N (2 x 3 GB at B = 64)
     const int ldp = (N + 3) & ~3, ldq = (Q + 2 + 3) & ~3;
@@ -576,14 +566,14 @@ int train_fit_prec(actmi_ctx* ctx) {
     if ((int64_t)B * H * prow != T.P_floats) {
         release(T.Pbuf); release(T.dPbuf);
         T.P_floats = 0;
-        if ((rc = dev_alloc(ctx, &T.Pbuf, (int64_t)B * H * prow)) || (rc = dev_alloc(ctx, &T.dPbuf, (int64_t)B * H * prow))) return rc;
+        ALLOC(T.Pbuf, (int64_t)B * H * prow);
+        ALLOC(T.dPbuf, (int64_t)B * H * prow);
         T.P_floats = (int64_t)B * H * prow;
     }
     for (size_t i = 0; i < ctx->convs.size(); ++i) {
         const ConvLayer& cl = ctx->convs[i];
         if (!dgrad_direct(ctx, cl) && T.conv_wd16[i]) release(T.conv_wd16[i]);
-        if (dgrad_direct(ctx, cl) && !T.conv_wd16[i] && (rc = dev_alloc(ctx, &T.conv_wd16[i], (int64_t)C * cl.cin * cl.k * cl.k * cl.cout)))
-            return rc;
+        if (dgrad_direct(ctx, cl) && !T.conv_wd16[i]) ALLOC(T.conv_wd16[i], (int64_t)C * cl.cin * cl.k * cl.k * cl.cout);
     }
     return 0;
 }
@@ -656,7 +646,7 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
     auto run_conv = [&](const ConvLayer& cl, const float* in, float* out, const float* res, int relu) -> int {
         if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.direct)      // layer1: direct convolution (conv3.hip), as in the inference engine
             return launch_conv3x3_c64(conv3_args(cl, B, 0, C, in, out, res, relu), st, &ctx->err);
-        return tgemm(ctx, conv_gemm_args(cl, B, 0, C, in, out, res, relu), st);
+        return tgemm(ctx, conv_gemm_args(ctx, cl, B, 0, C, in, out, res, relu), st);
     };
     const float* x = T.pool;
     for (auto& bs : T.blocks) {
