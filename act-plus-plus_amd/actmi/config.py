@@ -46,6 +46,16 @@ class ACTConfig:
     image_w: int = 640
     # resnet stem width; 64 for resnet18. Reduced only by tiny test configs.
     base_width: int = 64
+    # point-cloud input (reference detr_vae.py:375-381: PointNet(n_coordinates=3, n_color=3, output_dim=512, hidden_dim=512,
+    # hidden_depth=3)): one extra transformer token [latent, proprio, pcl] in front of the image tokens
+    use_pcd: bool = False
+    pcd_hidden_dim: int = 512
+    pcd_output_dim: int = 512
+
+    @property
+    def num_extra_tokens(self) -> int:
+        """tokens in front of the image tokens: latent, proprio and, with use_pcd, the point-cloud token (transformer.py:94-99)"""
+        return 3 if self.use_pcd else 2
 
     @property
     def latent_in_dim(self) -> int:
@@ -80,7 +90,7 @@ class ACTConfig:
     @property
     def num_tokens(self) -> int:
         fh, fw = self.feat_hw
-        return 2 + self.num_cams * fh * fw
+        return self.num_extra_tokens + self.num_cams * fh * fw
 
     def validate(self):
         if self.backbone != "resnet18":
@@ -92,6 +102,9 @@ class ACTConfig:
                 raise ValueError("vq needs positive vq_class and vq_dim")
             if (self.vq_class * self.vq_dim) % 4:
                 raise ValueError("vq_class * vq_dim must be a multiple of 4")
+        if self.use_pcd and (self.pcd_hidden_dim % 32 or self.pcd_output_dim % 32 or self.hidden_dim % 32
+                             or self.pcd_hidden_dim <= 0 or self.pcd_output_dim <= 0):
+            raise ValueError("use_pcd needs pcd_hidden_dim, pcd_output_dim and hidden_dim to be multiples of 32")
         if self.pre_norm:
             raise NotImplementedError("pre_norm is never enabled by the reference CLI")
         if self.hidden_dim % self.nheads:

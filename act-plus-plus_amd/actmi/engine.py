@@ -24,14 +24,16 @@ _CHECK_FINITE = os.environ.get("ACTMI_CHECK_FINITE") == "1"
 
 class ACTEngine:
     def __init__(self, cfg: ACTConfig, max_batch: int = 8, device: str = "cuda:0", training: bool = False,
-                 gemm_prec: str = None, train_prec: str = None):
-        """gemm_prec: "f16x3" (default; fp32 products formed from three fp16 MFMA products of exactly split operands,
+                 gemm_prec: str = None, train_prec: str = None, max_points: int = 4096):
+        """max_points (cfg.use_pcd): the point-cloud workspace is sized for this many points per sample.
+        gemm_prec: "f16x3" (default; fp32 products formed from three fp16 MFMA products of exactly split operands,
         fp32-grade results) or "f32" (native fp32 MFMA); None = environment ACTMI_GEMM_PREC or the default."""
         if not torch.cuda.is_available():
             raise RuntimeError("ACTEngine needs an MI355X (torch.cuda.is_available() is False); no CPU fallback exists")
         self.cfg = cfg.validate()
         self.device = torch.device(device)
         self.max_batch = int(max_batch)
+        self.max_points = int(max_points)
         if self.device.type != "cuda":
             raise ValueError(f"ACTEngine device must be a cuda device, got {device!r}")
         if self.device.index is None:
@@ -48,7 +50,12 @@ class ACTEngine:
         # the handle binds to the device that is current at create time; the process-wide current device is left alone
         # (one process may hold engines on several GPUs; every later call switches to the handle's device by itself)
         with torch.cuda.device(self.device):
-            rc = self.lib.actmi_create(C.byref(c), C.byref(h))
+            if cfg.use_pcd:
+                pc = L.ActmiPcdConfig(struct_size=C.sizeof(L.ActmiPcdConfig), max_points=self.max_points,
+                                      hidden_dim=cfg.pcd_hidden_dim, output_dim=cfg.pcd_output_dim)
+                rc = self.lib.actmi_create_ex(C.byref(c), C.byref(pc), C.byref(h))
+            else:
+                rc = self.lib.actmi_create(C.byref(c), C.byref(h))
         if rc != 0:
             raise RuntimeError(f"actmi_create failed ({rc}): {self.lib.actmi_last_error(None).decode()}")
         self.h = h
@@ -153,8 +160,36 @@ class ACTEngine:
             raise ValueError(f"image shape {tuple(image.shape)} != {want}")
         return fmt
 
+    def _bind_pointcloud(self, pointcloud, B: int):
+        """Check the clouds of a use_pcd engine ({"xyz": [B, P, 3], "rgb": [B, P, 3]} float32 device tensors) and bind them for
+        the next forward (actmi_set_pointcloud).  Returns the tensors the library will read."""
+        if not self.cfg.use_pcd:
+            if pointcloud is not None:
+                raise ValueError("pointcloud given to an engine whose config has use_pcd=False")
+            return None
+        if pointcloud is None:
+            raise ValueError("a use_pcd engine needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]}")
+        xyz, rgb = pointcloud["xyz"], pointcloud["rgb"]
+        for name, t in (("pointcloud['xyz']", xyz), ("pointcloud['rgb']", rgb)):
+            if not t.is_cuda:
+                raise ValueError(f"{name} must be a CUDA tensor on the engine's device")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{name} dtype {t.dtype} not supported (float32)")
+        self._check_dev(**{"pointcloud['xyz']": xyz, "pointcloud['rgb']": rgb})
+        if xyz.dim() != 3 or xyz.shape[0] != B or xyz.shape[2] != 3:
+            raise ValueError(f"pointcloud['xyz'] shape {tuple(xyz.shape)} != {(B, 'P', 3)}")
+        P = xyz.shape[1]
+        if tuple(rgb.shape) != (B, P, 3):
+            raise ValueError(f"pointcloud['rgb'] shape {tuple(rgb.shape)} != {(B, P, 3)}")
+        if P < 1 or P > self.max_points:
+            raise ValueError(f"{P} points per sample: needs 1 <= P <= max_points {self.max_points}")
+        xyz, rgb = xyz.contiguous(), rgb.contiguous()
+        L.check(self.lib.actmi_set_pointcloud(self.h, C.c_void_p(xyz.data_ptr()), C.c_void_p(rgb.data_ptr()), B, P), self.h,
+                "set_pointcloud")
+        return xyz, rgb
+
     def forward_infer(self, qpos: torch.Tensor, image: torch.Tensor, out: torch.Tensor = None,
-                      vq_sample: torch.Tensor = None) -> torch.Tensor:
+                      vq_sample: torch.Tensor = None, pointcloud=None) -> torch.Tensor:
         if not self._finalized:
             self.finalize()
         cfg = self.cfg
@@ -164,6 +199,7 @@ class ACTEngine:
         if not (qpos.is_cuda and image.is_cuda):
             raise ValueError("qpos and image must be CUDA tensors on the engine's device")
         self._check_dev(qpos=qpos, image=image, out=out)
+        cloud = self._bind_pointcloud(pointcloud, B)          # (kept alive until the forward below has been enqueued)
         qpos = qpos.to(torch.float32).contiguous()
         image = image.contiguous()
         fmt = self._image_fmt(image, B)
@@ -193,9 +229,11 @@ class ACTEngine:
         """0: forward_infer runs the whole step; 1: trunk + token assembly only; 2: transformer only (actmi_set_forward_phase)"""
         L.check(self.lib.actmi_set_forward_phase(self.h, int(phase)), self.h, "set_forward_phase")
 
-    def capture_infer(self, batch: int, image_dtype=torch.uint8, with_ensemble=None, statics=None, phase: int = 0):
+    def capture_infer(self, batch: int, image_dtype=torch.uint8, with_ensemble=None, statics=None, phase: int = 0,
+                      num_points: int = None):
         """Capture one forward (optionally + the temporal-ensemble kernel) into a hipGraph and return
-        ``replay(qpos, image) -> a_hat`` that copies into static inputs and replays.  The forward path allocates
+        ``replay(qpos, image) -> a_hat`` that copies into static inputs and replays.  A use_pcd engine captures static
+        xyz / rgb buffers of ``num_points`` points (default max_points) and replays ``replay(qpos, image, pointcloud)``.  The forward path allocates
         nothing and never synchronises, so the whole step is one graph launch (removes ~60 kernel-launch gaps; matters
         at small batch where the step is launch-bound)."""
         if not self._finalized:
@@ -209,12 +247,16 @@ class ACTEngine:
             s_qpos = torch.zeros((batch, cfg.state_dim), dtype=torch.float32, device=dev)
             s_img = torch.zeros(shape, dtype=image_dtype, device=dev)
             s_out = torch.empty((batch, cfg.num_queries, cfg.action_dim), dtype=torch.float32, device=dev)
+        s_cloud = None
+        if cfg.use_pcd:
+            npts = self.max_points if num_points is None else int(num_points)
+            s_cloud = {k: torch.zeros((batch, npts, 3), dtype=torch.float32, device=dev) for k in ("xyz", "rgb")}
         # warm-up on a side stream (first launches set function attributes; not allowed during capture)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(2):
-                self.forward_infer(s_qpos, s_img, out=s_out)
+                self.forward_infer(s_qpos, s_img, out=s_out, pointcloud=s_cloud)
                 if with_ensemble is not None:
                     with_ensemble.step(s_out)
         torch.cuda.current_stream(dev).wait_stream(side)
@@ -227,7 +269,7 @@ class ACTEngine:
         try:
             # thread_local: calls made by other threads (e.g. the RCCL watchdog of a multi-rank bench) must not void the capture
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                self.forward_infer(s_qpos, s_img, out=s_out)
+                self.forward_infer(s_qpos, s_img, out=s_out, pointcloud=s_cloud)
                 if with_ensemble is not None and phase != 1:
                     ens_out = with_ensemble.step(s_out)
         finally:
@@ -235,22 +277,32 @@ class ACTEngine:
         if with_ensemble is not None:
             with_ensemble.reset()               # the capture itself does not execute, but keep the state explicit
 
-        def replay(qpos, image):
+        def replay(qpos, image, pointcloud=None):
             # a caller that owns the step's inputs writes them straight into replay.static (H2D copies land there): no copy
             if qpos.data_ptr() != s_qpos.data_ptr():
                 s_qpos.copy_(qpos, non_blocking=True)
             if image.data_ptr() != s_img.data_ptr():
                 s_img.copy_(image, non_blocking=True)
+            if s_cloud is not None:
+                if pointcloud is None:
+                    raise ValueError("a use_pcd engine needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]}")
+                for k in ("xyz", "rgb"):
+                    if tuple(pointcloud[k].shape) != tuple(s_cloud[k].shape):
+                        raise ValueError(f"pointcloud[{k!r}] shape {tuple(pointcloud[k].shape)} != the captured "
+                                         f"{tuple(s_cloud[k].shape)}")
+                    if pointcloud[k].data_ptr() != s_cloud[k].data_ptr():
+                        s_cloud[k].copy_(pointcloud[k], non_blocking=True)
             graph.replay()
             return (s_out, ens_out) if with_ensemble is not None else s_out
 
         replay.graph = graph
         replay.static = (s_qpos, s_img, s_out)
+        replay.static_cloud = s_cloud
         return replay
 
     # ---- training -----------------------------------------------------------------------------
     def forward_train(self, qpos, image, actions, is_pad, eps=None, dropout_p: float = 0.0, dropout_seed: int = 0,
-                      vq_code=None):
+                      vq_code=None, pointcloud=None):
         """ACTPolicy.__call__ training branch (policy.py:288-320). Returns dict(l1, kl, loss, a_hat, mu, logvar) of
         device tensors.  ``eps`` replaces the normal_() draw of reparametrize (detr_vae.py:19-22).
         VQ-ACT (cfg.vq): ``vq_code`` [B, vq_class, vq_dim] replaces the multinomial draw of detr_vae.py:140 (None: drawn
@@ -288,7 +340,8 @@ class ACTEngine:
         a_hat = torch.empty((B, Q, A), dtype=torch.float32, device=dev)
         mu = torch.empty((B, Lz), dtype=torch.float32, device=dev)
         logvar = torch.empty((B, Lz), dtype=torch.float32, device=dev)
-        self._keep = (qpos, image, actions, is_pad_u8, eps)               # the library reads qpos again in backward
+        cloud = self._bind_pointcloud(pointcloud, B)
+        self._keep = (qpos, image, actions, is_pad_u8, eps, cloud)        # the library reads qpos and the clouds again in backward
         L.check(self.lib.actmi_forward_train(
             self.h, C.c_void_p(qpos.data_ptr()), C.c_void_p(image.data_ptr()), fmt, C.c_void_p(actions.data_ptr()),
             C.c_void_p(is_pad_u8.data_ptr()), C.c_void_p(eps.data_ptr() if eps is not None else 0), C.c_uint64(dropout_seed),
@@ -556,6 +609,8 @@ class InferPipeline:
     step t stay valid until step t + 2 is issued."""
 
     def __init__(self, engine: "ACTEngine", batch: int, with_ensemble=None, image_dtype=torch.uint8, copy_stream_candidates: int = 8):
+        if engine.cfg.use_pcd:
+            raise NotImplementedError("InferPipeline has no host feed for point clouds yet (use capture_infer)")
         self.engine, self.dev = engine, engine.device
         cfg, dev = engine.cfg, engine.device
         shape = (batch, cfg.num_cams, cfg.image_h, cfg.image_w, 3) if image_dtype == torch.uint8 else \

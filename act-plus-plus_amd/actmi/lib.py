@@ -25,6 +25,11 @@ class ActmiConfig(C.Structure):
         "enable_training")] + [("kl_weight", C.c_float)] + [(n, C.c_int32) for n in ("vq", "vq_class", "vq_dim")]
 
 
+class ActmiPcdConfig(C.Structure):
+    # the point-cloud branch of a handle (actmi_create_ex); struct_size guards it like ActmiConfig's
+    _fields_ = [("struct_size", C.c_uint32), ("max_points", C.c_int32), ("hidden_dim", C.c_int32), ("output_dim", C.c_int32)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("lda", C.c_int64), ("mode", C.c_int32),
@@ -93,6 +98,8 @@ def load():
     sigs = {
         "actmi_version": ([], i32),
         "actmi_create": ([C.POINTER(ActmiConfig), C.POINTER(vp)], i32),
+        "actmi_create_ex": ([C.POINTER(ActmiConfig), C.POINTER(ActmiPcdConfig), C.POINTER(vp)], i32),
+        "actmi_set_pointcloud": ([vp, vp, vp, i32, i32], i32),
         "actmi_destroy": ([vp], i32),
         "actmi_last_error": ([vp], C.c_char_p),
         "actmi_num_params": ([vp], i32),
@@ -147,6 +154,8 @@ def load():
         "actmi_op_argmax_l1": ([vp, vp, i32, i32, vp, vp, vp], i32),
         "actmi_op_layernorm_bwd": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, C.c_int64, vp], i32),
         "actmi_op_colsum": ([vp, C.c_int64, vp, i32, i32, vp, C.c_int64, vp], i32),
+        "actmi_op_pcd_embed": ([vp, vp, vp, vp, vp, C.c_int64, i32, vp], i32),
+        "actmi_op_colmax": ([vp, i32, i32, i32, C.c_int64, vp, vp, vp, C.c_int64, vp], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

@@ -551,6 +551,29 @@ def colsum(src, out, ws):
     L.check(L.load().actmi_op_colsum(_p(src), src.stride(0), _p(out), M, N, _p(ws), ws.numel(), L.current_stream_ptr()), None, "op_colsum")
 
 
+def pcd_embed(xyz, rgb, w0, b0):
+    """PointNet layer 0: gelu(cat(xyz, rgb) @ w0.T + b0) in fp32 FMAs; xyz, rgb [..., 3] -> [rows, H]"""
+    xyz, rgb = xyz.contiguous().view(-1, 3), rgb.contiguous().view(-1, 3)
+    rows, H = xyz.shape[0], w0.shape[0]
+    out = torch.empty((rows, H), dtype=torch.float32, device=xyz.device)
+    L.check(L.load().actmi_op_pcd_embed(_p(xyz), _p(rgb), _p(w0.contiguous()), _p(b0.contiguous()), _p(out), rows, H,
+                                        L.current_stream_ptr()), None, "op_pcd_embed")
+    return out
+
+
+def colmax(x, O=None, split=True):
+    """x [B, P, ld] -> (max over the points [B, O], int32 index of the winner [B, O]) for the columns < O (default ld); the
+    lowest index wins a tie, a NaN propagates.  split=False: one block column per sample (no workspace)."""
+    B, P, ld = x.shape
+    O = ld if O is None else O
+    out = torch.empty((B, O), dtype=torch.float32, device=x.device)
+    arg = torch.empty((B, O), dtype=torch.int32, device=x.device)
+    ws = torch.empty(2 * B * 64 * O, dtype=torch.float32, device=x.device) if split else None
+    L.check(L.load().actmi_op_colmax(_p(x), B, P, O, ld, _p(out), _p(arg), _p(ws), ws.numel() if split else 0,
+                                     L.current_stream_ptr()), None, "op_colmax")
+    return out, arg
+
+
 def sum_batch(src, dst, accumulate=False):
     """src [B,R,D] -> dst[R,D] (+)= sum_b src[b]"""
     B, Rr, D = src.shape

@@ -144,12 +144,21 @@ def act_state_dict_spec(cfg: ACTConfig, prefix: str = "") -> "OrderedDict[str, t
     for c in range(cfg.num_cams):
         _backbone(f"backbones.{c}.0.body.", cfg.base_width, o)
     o["input_proj_robot_state.weight"] = (D, S); o["input_proj_robot_state.bias"] = (D,)
+    if cfg.use_pcd:                                                 # detr_vae.py:64-65
+        o["input_proj_pointnet.weight"] = (D, cfg.pcd_output_dim); o["input_proj_pointnet.bias"] = (D,)
     o["cls_embed.weight"] = (1, D)
     o["encoder_action_proj.weight"] = (D, A); o["encoder_action_proj.bias"] = (D,)
     o["encoder_joint_proj.weight"] = (D, S); o["encoder_joint_proj.bias"] = (D,)
     o["latent_proj.weight"] = (cfg.latent_proj_dim, D); o["latent_proj.bias"] = (cfg.latent_proj_dim,)
     o["latent_out_proj.weight"] = (D, cfg.latent_in_dim); o["latent_out_proj.bias"] = (D,)
-    o["additional_pos_embed.weight"] = (2, D)
+    if cfg.use_pcd:
+        # PointNet(hidden_depth=3) -> build_mlp: Linear, Identity, GELU three times, then Linear (pointnet.py:20-26; the norm
+        # slots hold nn.Identity, so the Linear layers sit at 0, 3, 6, 9); registered at detr_vae.py:98-99
+        Hp, Op = cfg.pcd_hidden_dim, cfg.pcd_output_dim
+        for i, (n_out, n_in) in zip((0, 3, 6, 9), ((Hp, 6), (Hp, Hp), (Hp, Hp), (Op, Hp))):
+            o[f"pcl_backbone.pointnet._mlp.{i}.weight"] = (n_out, n_in)
+            o[f"pcl_backbone.pointnet._mlp.{i}.bias"] = (n_out,)
+    o["additional_pos_embed.weight"] = (cfg.num_extra_tokens, D)     # detr_vae.py:100-102
     if prefix:
         o = OrderedDict((prefix + k, v) for k, v in o.items())
     return o
@@ -220,8 +229,10 @@ def generate_state_dict(cfg: ACTConfig, seed: int = 0, prefix: str = "") -> "Ord
     return sd
 
 
-def generate_inputs(cfg: ACTConfig, batch: int, seed: int = 1234, with_actions: bool = False):
-    """Synthetic inputs of SURVEY §8(d): u8 NHWC images, N(0,1) qpos, optional actions / is_pad / eps."""
+def generate_inputs(cfg: ACTConfig, batch: int, seed: int = 1234, with_actions: bool = False, num_points: int = 37):
+    """Synthetic inputs of SURVEY §8(d): u8 NHWC images, N(0,1) qpos, optional actions / is_pad / eps; with cfg.use_pcd a
+    cloud of `num_points` points per sample: pcd_xyz ~ N(0,1), pcd_rgb ~ U(0,1) (streams of their own: the other tensors of a
+    seed do not change)."""
     C = cfg.num_cams
     img = rand_u8(seed, "image", (batch, C, cfg.image_h, cfg.image_w, 3))
     qpos = normal(seed, "qpos", batch * cfg.state_dim).astype(np.float32).reshape(batch, cfg.state_dim)
@@ -233,6 +244,10 @@ def generate_inputs(cfg: ACTConfig, batch: int, seed: int = 1234, with_actions: 
         for b in range(batch):
             code[b, np.arange(cfg.vq_class), np.minimum(pick[b], cfg.vq_dim - 1)] = 1.0
         out["vq_sample"] = code
+    if cfg.use_pcd:
+        n = batch * num_points * 3
+        out["pcd_xyz"] = normal(seed, "pcd_xyz", n).astype(np.float32).reshape(batch, num_points, 3)
+        out["pcd_rgb"] = uniform01(seed, "pcd_rgb", n).astype(np.float32).reshape(batch, num_points, 3)
     if with_actions:
         Q, A = cfg.num_queries, cfg.action_dim
         out["actions"] = normal(seed, "actions", batch * Q * A).astype(np.float32).reshape(batch, Q, A)

@@ -27,11 +27,27 @@ extern "C" {
 int actmi_version(void) { return ACTMI_VERSION; }
 
 int actmi_create(const actmi_config* cfg, actmi_handle* out) {
+    return actmi_create_ex(cfg, nullptr, out);
+}
+
+int actmi_create_ex(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_handle* out) {
     try {
-        return engine_create(cfg, out);
+        return engine_create(cfg, pcd, out);
     } catch (const std::exception& e) {
         return ACTMI_E_NOMEM;
     }
+}
+
+int actmi_set_pointcloud(actmi_handle h, const float* xyz, const float* rgb, int B, int P) {
+    if (!h) return ACTMI_E_INVALID;
+    ENTER(h);
+    if (!h->has_pcd) return bad(h, "handle was created without a point-cloud config (actmi_create_ex)", ACTMI_E_STATE);
+    if (!xyz || !rgb) return bad(h, "null pointer");
+    if (B < 1 || B > h->cfg.max_batch) return bad(h, "batch exceeds max_batch");
+    if (P < 1 || P > h->pcd.max_points)
+        return bad(h, "point clouds of " + std::to_string(P) + " points: needs 1 <= P <= max_points " + std::to_string(h->pcd.max_points));
+    h->pcd_xyz = xyz; h->pcd_rgb = rgb; h->pcd_B = B; h->pcd_P = P;
+    return ACTMI_OK;
 }
 
 int actmi_destroy(actmi_handle h) {
@@ -485,6 +501,18 @@ int actmi_op_layernorm_bwd(const float* x, const float* w, const float* dy, cons
 int actmi_op_colsum(const float* src, int64_t ld, float* out, int M, int N, float* ws, int64_t ws_floats, void* stream) {
     OPCHK(src && out && M >= 0 && N >= 0, "colsum: bad argument");
     OPRC(launch_colsum(src, ld, out, M, N, S(stream), ws, ws_floats), "colsum launch failed");
+}
+int actmi_op_pcd_embed(const float* xyz, const float* rgb, const float* w0, const float* b0, float* out, int64_t rows, int H,
+                       void* stream) {
+    OPCHK(xyz && rgb && w0 && b0 && out && rows >= 0, "pcd_embed: bad argument");
+    OPRC(launch_pcd_embed(xyz, rgb, nullptr, w0, b0, out, nullptr, rows, H, S(stream)),
+         "pcd_embed: H must be a multiple of 4 and <= 2048, out 16-byte aligned");
+}
+int actmi_op_colmax(const float* x, int B, int P, int O, int64_t ld, float* out, int32_t* argmax, float* ws, int64_t ws_floats,
+                    void* stream) {
+    OPCHK(x && out && argmax && B >= 0 && P >= 1 && O >= 0 && ws_floats >= 0, "colmax: bad argument");
+    OPRC(launch_colmax(x, B, P, O, ld, out, argmax, ws, ws_floats, S(stream)),
+         "colmax: O and ld must be multiples of 4, ld >= O, x 16-byte aligned");
 }
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream) {

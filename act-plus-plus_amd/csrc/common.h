@@ -152,11 +152,27 @@ int launch_ensemble(float* ring, int* tcount, const float* chunk, double k, doub
                     int Q, int A, hipStream_t st);
 int launch_bn_fold(const float* w, const float* b, const float* rm, const float* rv, float* scale, float* bias, int n,
                    hipStream_t st);
-int launch_build_rowmap(int* map, int B, int C, int fh, int fw, int N, hipStream_t st);
+int launch_build_rowmap(int* map, int B, int C, int fh, int fw, int N, int n_extra, hipStream_t st);
 int launch_permute_conv_k(const float* src, float* dst, int64_t rows, int taps, int cin, int ld, hipStream_t st);
 // [s2 * w2 | sd * wd] per output row + summed bias: the fused weights of a block's conv2 + downsample (misc.hip)
 int launch_fold_cat_w(const float* w2, const float* s2, const float* b2, const float* wd, const float* sd, const float* bd,
                       float* out, float* bias, int G, int N, int K2, int Kd, hipStream_t st);
+
+// ---- point-cloud branch (pointnet.hip) ---------------------------------------------------------------
+// PointNet layer 0: out[r][h] = gelu(pre), pre = cat(xyz, rgb)[src(r)] . w0[h] + b0[h], src(r) = rowmap[r] or r; pre (optional)
+// receives the pre-activation
+int launch_pcd_embed(const float* xyz, const float* rgb, const int* rowmap, const float* w0, const float* b0, float* out, float* pre,
+                     int64_t rows, int H, hipStream_t st);
+// out[b][c] = max_p x[b][p][c], argmax = the lowest index that attains it (NaN propagates); ws: (value, index) of the splits
+int launch_colmax(const float* x, int B, int P, int O, int64_t ld, float* out, int* argmax, float* ws, int64_t ws_floats,
+                  hipStream_t st);
+// rows[b * O + c] = b * P + argmax[b][c]
+int launch_pcd_winner_rows(const int* argmax, int* rows, int B, int P, int O, hipStream_t st);
+// last PointNet layer, backward over the winner rows: dA[(b,c)][:] = g[b][c] * w[c][:], dW[c][:] += sum_b g[b][c] * a[(b,c)][:]
+int launch_pcd_head_bwd(const float* g, const float* w, const float* a, float* dA, float* dW, int B, int O, int H, hipStream_t st);
+// layer 0's weight gradient dW[h][k] += sum_r dz[r][h] * cat(xyz, rgb)[rows[r]][k]; ws: >= 6 * H floats per split
+int launch_pcd_wgrad0(const float* dz, const float* xyz, const float* rgb, const int* rows, float* dW, int R, int H, float* ws,
+                      int64_t ws_floats, hipStream_t st);
 
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------
 bool prof_enabled();

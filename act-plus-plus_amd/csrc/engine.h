@@ -99,10 +99,34 @@ struct TrainState {
           *delta = nullptr, *dXg = nullptr, *tmp2BD = nullptr, *tmpD = nullptr, *dqb = nullptr;
     int64_t P_floats = 0;              // size of Pbuf and of dPbuf (train_fit_prec)
     int* pos_rows = nullptr;
+    // point-cloud branch: the B * O winner rows of the last forward (row (b, c) = the point that won column c of sample b),
+    // their recomputed activations a0 / a3 / a6 with the pre-activations z0 / z3 / z6, and two gradient buffers, all
+    // [max_batch * O][H]; the clouds the forward read (layer 0's weight gradient reads the winners again)
+    int* pcd_win = nullptr;
+    float *pcd_z0 = nullptr, *pcd_a0 = nullptr, *pcd_z3 = nullptr, *pcd_a3 = nullptr, *pcd_z6 = nullptr, *pcd_a6 = nullptr,
+          *pcd_g0 = nullptr, *pcd_g1 = nullptr, *pcd_dfeat = nullptr, *pcd_dtok = nullptr;
+    const float *pcd_xyz = nullptr, *pcd_rgb = nullptr;
+    int pcd_P = 0;
 };
+
+// weights of the point-cloud branch (pointnet.py:20-26 with hidden_depth = 3; detr_vae.py:64-65)
+struct PcdW { float *w0, *b0, *w3, *b3, *w6, *b6, *w9, *b9, *pw, *pb; };
 
 struct actmi_ctx {
     actmi_config cfg;
+    // point-cloud branch (actmi_create_ex): off unless has_pcd.  n_extra = tokens in front of the image tokens, [latent, proprio]
+    // or [latent, proprio, pcl] (transformer.py:94-99)
+    bool has_pcd = false;
+    actmi_pcd_config pcd{};
+    int n_extra = 2;
+    PcdW pcdw{};
+    const float *pcd_xyz = nullptr, *pcd_rgb = nullptr;    // clouds bound for the next forward (actmi_set_pointcloud), then cleared
+    int pcd_B = 0, pcd_P = 0;
+    float *pcd_act[2] = {nullptr, nullptr};                // ping-pong activations [max_batch * max_points][max(H, O)]
+    float* pcd_feat = nullptr;                             // [max_batch][O] pooled features
+    int* pcd_arg = nullptr;                                // [max_batch][O] winning point of every column
+    float* pcd_ws = nullptr;                               // candidates of the split column maximum
+    int64_t pcd_ws_floats = 0;
     int device = 0;                    // HIP device the handle was created on (all its memory lives there)
     std::string err;
     std::vector<Param> params;
@@ -209,7 +233,11 @@ int dev_alloc(actmi_ctx* ctx, T** p, int64_t count) {
 // precision of the GEMMs issued right now: the training override (PrecScope) while a training call runs, else the handle's
 inline int engine_prec(const actmi_ctx* ctx) { return ctx->prec_override ? ctx->prec_override : ctx->gemm_prec; }
 
-int engine_create(const actmi_config* cfg, actmi_ctx** out);
+int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_ctx** out);
+// the clouds of this forward: checks the binding of a point-cloud handle against B (ACTMI_E_STATE with a message) and consumes it
+int engine_take_pointcloud(actmi_ctx* ctx, int B, const float** xyz, const float** rgb, int* P);
+// PointNet + input_proj_pointnet of B clouds of P points -> token row 2 of ctx->X, features / winners in ctx->pcd_feat / pcd_arg
+int engine_pointnet(actmi_ctx* ctx, const float* xyz, const float* rgb, int B, int P, hipStream_t st);
 // forward GEMMs of a handle go through here: applies the precision in force and, for a B operand inside the parameter arena
 // that does not already name a split image (b_split), swaps in the arena's image (same offset into p16base)
 // LayerNorm that follows a product (y = LN(C), optionally a second LN on top): when the product's contraction is split, the

@@ -107,6 +107,10 @@ void build_spec(actmi_ctx* c) {
     }
     add_param(c, "input_proj_robot_state.weight", {D, S}, false);
     add_param(c, "input_proj_robot_state.bias", {D}, false);
+    if (c->has_pcd) {                                   // detr_vae.py:64-65
+        add_param(c, "input_proj_pointnet.weight", {D, c->pcd.output_dim}, false);
+        add_param(c, "input_proj_pointnet.bias", {D}, false);
+    }
     add_param(c, "cls_embed.weight", {1, D}, false);
     add_param(c, "encoder_action_proj.weight", {D, A}, false);
     add_param(c, "encoder_action_proj.bias", {D}, false);
@@ -118,7 +122,17 @@ void build_spec(actmi_ctx* c) {
     add_param(c, "latent_proj.bias", {Lp}, false);
     add_param(c, "latent_out_proj.weight", {D, Li}, false);
     add_param(c, "latent_out_proj.bias", {D}, false);
-    add_param(c, "additional_pos_embed.weight", {2, D}, false);
+    if (c->has_pcd) {
+        // PointNet(hidden_depth = 3): the Linear layers of build_mlp sit at 0, 3, 6, 9 (pointnet.py:20-26; detr_vae.py:98-99)
+        const int Hp = c->pcd.hidden_dim, Op = c->pcd.output_dim;
+        const int idx[4] = {0, 3, 6, 9}, nout[4] = {Hp, Hp, Hp, Op}, nin[4] = {6, Hp, Hp, Hp};
+        for (int i = 0; i < 4; ++i) {
+            const std::string p = "pcl_backbone.pointnet._mlp." + std::to_string(idx[i]) + ".";
+            add_param(c, p + "weight", {nout[i], nin[i]}, false);
+            add_param(c, p + "bias", {nout[i]}, false);
+        }
+    }
+    add_param(c, "additional_pos_embed.weight", {c->n_extra, D}, false);
 }
 
 }  // namespace
@@ -311,6 +325,12 @@ void resolve_layers(actmi_ctx* c) {
         d.n2w = c->P(p + "norm2.weight"); d.n2b = c->P(p + "norm2.bias");
         d.n3w = c->P(p + "norm3.weight"); d.n3b = c->P(p + "norm3.bias");
         c->dec.push_back(d);
+    }
+    if (c->has_pcd) {
+        const std::string p = "pcl_backbone.pointnet._mlp.";
+        c->pcdw = PcdW{c->P(p + "0.weight"), c->P(p + "0.bias"), c->P(p + "3.weight"), c->P(p + "3.bias"),
+                       c->P(p + "6.weight"), c->P(p + "6.bias"), c->P(p + "9.weight"), c->P(p + "9.bias"),
+                       c->P("input_proj_pointnet.weight"), c->P("input_proj_pointnet.bias")};
     }
 }
 
@@ -540,6 +560,13 @@ int create_device_state(actmi_ctx* ctx) {
     ALLOC(ctx->act_scale_dev, (int64_t)ctx->convs.size() + 4);
     ALLOC(ctx->rowmap, (int64_t)B * C * ctx->P_);
     ctx->rowmap_B = -1;
+    if (ctx->has_pcd) {
+        const int64_t Hp = ctx->pcd.hidden_dim, Op = ctx->pcd.output_dim, rows = (int64_t)B * ctx->pcd.max_points;
+        for (int i = 0; i < 2; ++i) ALLOC(ctx->pcd_act[i], rows * std::max(Hp, Op));
+        ALLOC(ctx->pcd_feat, B * Op); ALLOC(ctx->pcd_arg, B * Op);
+        ctx->pcd_ws_floats = 2 * (int64_t)B * 64 * Op;           // up to 64 splits of the points (launch_colmax fits the rest)
+        ALLOC(ctx->pcd_ws, ctx->pcd_ws_floats);
+    }
     // ---- activations (camera-major NHWC maps, token-major [B][N][D])
     ALLOC(ctx->act1, (int64_t)C * B * ctx->H1 * ctx->W1 * w0);
     for (int i = 0; i < 3; ++i) ALLOC(ctx->buf[i], (int64_t)C * B * ctx->H2 * ctx->W2 * w0);
@@ -567,9 +594,14 @@ int create_device_state(actmi_ctx* ctx) {
 
 }  // namespace
 
-int engine_create(const actmi_config* cfg, actmi_ctx** out) {
+int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_ctx** out) {
     if (!cfg || !out) { g_create_error = "null argument"; return ACTMI_E_INVALID; }
     const actmi_config& g = *cfg;
+    if (pcd && pcd->struct_size != (uint32_t)sizeof(actmi_pcd_config)) {
+        g_create_error = "actmi_pcd_config.struct_size is " + std::to_string(pcd->struct_size) + ", this library expects " +
+                         std::to_string(sizeof(actmi_pcd_config)) + " (binding built against a different include/actmi.h)";
+        return ACTMI_E_INVALID;
+    }
     if (g.struct_size != (uint32_t)sizeof(actmi_config)) {
         // the first field is readable whatever the caller's struct looks like; nothing else is trusted before this check
         g_create_error = "actmi_config.struct_size is " + std::to_string(g.struct_size) + ", this library expects " +
@@ -587,8 +619,18 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
         g_create_error = "vq needs positive vq_class, vq_dim with vq_class*vq_dim a multiple of 4";
         return ACTMI_E_INVALID;
     }
+    if (pcd) {
+        // the dense layers go through the GEMM launcher: contractions in multiples of 32; the rows of a cloud batch are an int
+        if (pcd->max_points < 1 || pcd->hidden_dim < 32 || pcd->output_dim < 32 || (pcd->hidden_dim % 32) || (pcd->output_dim % 32) ||
+            (g.hidden_dim % 32) || pcd->hidden_dim > 2048 || (int64_t)g.max_batch * pcd->max_points > (int64_t)1 << 30) {
+            g_create_error = "point-cloud config: max_points >= 1, hidden_dim / output_dim / the model's hidden_dim multiples of 32, "
+                             "hidden_dim <= 2048, max_batch * max_points <= 2^30";
+            return ACTMI_E_INVALID;
+        }
+    }
     actmi_ctx* ctx = new actmi_ctx();
     ctx->cfg = g;
+    if (pcd) { ctx->has_pcd = true; ctx->pcd = *pcd; ctx->n_extra = 3; }
     if (hipGetDevice(&ctx->device) != hipSuccess) { g_create_error = "hipGetDevice failed"; delete ctx; return ACTMI_E_LAUNCH; }
     ctx->ptotal = 0;
     build_spec(ctx);
@@ -599,7 +641,7 @@ int engine_create(const actmi_config* cfg, actmi_ctx** out) {
     for (int i = 0; i < 3; ++i) { h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1); }
     ctx->fh = h; ctx->fw = w;
     ctx->P_ = h * w;
-    ctx->N = 2 + g.num_cams * h * w;
+    ctx->N = ctx->n_extra + g.num_cams * h * w;
     if (h < 1 || w < 1) { g_create_error = "image too small"; delete ctx; return ACTMI_E_INVALID; }
 
     read_switches(ctx);
@@ -645,19 +687,19 @@ static int split_conv_image(actmi_ctx* ctx, const ConvLayer& cl, const float* w,
     return 0;
 }
 
-// position table per token: rows 0,1 = additional_pos_embed (transformer.py:91-92); rows 2.. =
+// position table per token: rows 0 .. n_extra-1 = additional_pos_embed (transformer.py:91-92); rows n_extra.. =
 // PositionEmbeddingSine(normalize=True) (position_encoding.py:30-52), identical for every camera
 static int build_pos_tokens(actmi_ctx* ctx) {
     const int C = ctx->cfg.num_cams, D = ctx->cfg.hidden_dim, fh = ctx->fh, fw = ctx->fw, N = ctx->N, npf = D / 2;
     std::vector<float> pos((size_t)N * D, 0.f);
-    HIPCHK(hipMemcpy(pos.data(), ctx->P("additional_pos_embed.weight"), 2 * D * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pos.data(), ctx->P("additional_pos_embed.weight"), (size_t)ctx->n_extra * D * sizeof(float), hipMemcpyDeviceToHost));
     const float eps = 1e-6f, scale = (float)(2.0 * M_PI);
     std::vector<float> dim_t(npf);
     for (int k = 0; k < npf; ++k) dim_t[k] = powf(10000.f, (2.f * (float)(k / 2)) / (float)npf);
     for (int hh = 0; hh < fh; ++hh)
         for (int cam = 0; cam < C; ++cam)
             for (int ww = 0; ww < fw; ++ww) {
-                float* row = &pos[(size_t)(2 + hh * (fw * C) + cam * fw + ww) * D];
+                float* row = &pos[(size_t)(ctx->n_extra + hh * (fw * C) + cam * fw + ww) * D];
                 const float y = (float)(hh + 1) / ((float)fh + eps) * scale;
                 const float x = (float)(ww + 1) / ((float)fw + eps) * scale;
                 for (int k = 0; k < npf; ++k) {
@@ -719,7 +761,7 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
             }
     }
     // learned rows of the token position table (transformer.py:91-92)
-    HIPCHK(hipMemcpyAsync(ctx->pos_tokens, ctx->P("additional_pos_embed.weight"), 2 * D * sizeof(float),
+    HIPCHK(hipMemcpyAsync(ctx->pos_tokens, ctx->P("additional_pos_embed.weight"), (size_t)ctx->n_extra * D * sizeof(float),
                           hipMemcpyDeviceToDevice, st));
     // decoder layer 0, constant part: tgt = 0 => self-attention output is
     // out_proj(b_v) + b_o for every query; t1 = norm1 of it; q = (t1 + query_embed) Wq^T + bq.
@@ -869,7 +911,7 @@ static int run_branches(actmi_ctx* ctx, int nb, hipStream_t st, Body body) {
     return 0;
 }
 
-// multi-camera ResNet18 trunk + input_proj -> token rows 2.. of X   (backbone.py:66-71, detr_vae.py:180-185)
+// multi-camera ResNet18 trunk + input_proj -> token rows n_extra.. of X   (backbone.py:66-71, detr_vae.py:180-185)
 int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream_t st) {
     const actmi_config& g = ctx->cfg;
     const int C = g.num_cams, w0 = g.base_width, D = g.hidden_dim;
@@ -983,7 +1025,7 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
         return ctx_gemm(ctx, ip, ls, half);
     };
     if (ctx->rowmap_B != B) {
-        CHK(launch_build_rowmap(ctx->rowmap, B, C, ctx->fh, ctx->fw, ctx->N, st));
+        CHK(launch_build_rowmap(ctx->rowmap, B, C, ctx->fh, ctx->fw, ctx->N, ctx->n_extra, st));
         ctx->rowmap_B = B;
     }
     if (pipe) {
@@ -1000,6 +1042,48 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
         const int rc = run_layers(0, C, st, -1);
         if (rc != 0) return rc;
     }
+    return 0;
+}
+
+int engine_take_pointcloud(actmi_ctx* ctx, int B, const float** xyz, const float** rgb, int* P) {
+    *xyz = *rgb = nullptr;
+    *P = 0;
+    if (!ctx->has_pcd) return 0;
+    if (!ctx->pcd_xyz || !ctx->pcd_rgb) {
+        ctx->err = "this handle has a point-cloud branch: bind the clouds of every forward with actmi_set_pointcloud";
+        return ACTMI_E_STATE;
+    }
+    if (ctx->pcd_B != B) {
+        ctx->err = "forward of batch " + std::to_string(B) + " but the bound point clouds hold " + std::to_string(ctx->pcd_B) + " samples";
+        return ACTMI_E_STATE;
+    }
+    *xyz = ctx->pcd_xyz; *rgb = ctx->pcd_rgb; *P = ctx->pcd_P;
+    ctx->pcd_xyz = ctx->pcd_rgb = nullptr;              // one binding, one forward
+    return 0;
+}
+
+// Point-cloud token (detr_vae.py:205-207): PointNet over the B * P points, maximum over the points of a sample, input_proj_pointnet
+// into token row 2.  Layer 0 runs in fp32 FMAs; the H x H / O x H / D x O layers are GEMMs of the handle's precision with the
+// bias + GELU epilogue, their weights arena parameters like the transformer's FFN (split images and scales come with them).
+int engine_pointnet(actmi_ctx* ctx, const float* xyz, const float* rgb, int B, int P, hipStream_t st) {
+    const int Hp = ctx->pcd.hidden_dim, Op = ctx->pcd.output_dim, D = ctx->cfg.hidden_dim, R = B * P;
+    const PcdW& w = ctx->pcdw;
+    float *a = ctx->pcd_act[0], *b = ctx->pcd_act[1];
+    if (launch_pcd_embed(xyz, rgb, nullptr, w.w0, w.b0, a, nullptr, R, Hp, st) != 0) { ctx->err = "pcd_embed launch failed"; return ACTMI_E_LAUNCH; }
+    GemmArgs l3 = linear_args(a, Hp, R, Hp, w.w3, Hp, w.b3, b, Hp);
+    l3.relu = 2;
+    CHK(ctx_gemm(ctx, l3, st));
+    GemmArgs l6 = linear_args(b, Hp, R, Hp, w.w6, Hp, w.b6, a, Hp);
+    l6.relu = 2;
+    CHK(ctx_gemm(ctx, l6, st));
+    CHK(ctx_gemm(ctx, linear_args(a, Hp, R, Hp, w.w9, Op, w.b9, b, Op), st));
+    if (launch_colmax(b, B, P, Op, Op, ctx->pcd_feat, ctx->pcd_arg, ctx->pcd_ws, ctx->pcd_ws_floats, st) != 0) {
+        ctx->err = "colmax launch failed";
+        return ACTMI_E_LAUNCH;
+    }
+    CHK(ctx_gemm(ctx, linear_args(ctx->pcd_feat, Op, B, Op, w.pw, D, w.pb, ctx->X + 2 * D, (int64_t)ctx->N * D), st));
+    ctx->dbg["pcd_feat"] = {ctx->pcd_feat, (int64_t)B * Op};
+    ctx->dbg["pcd_argmax"] = {reinterpret_cast<const float*>(ctx->pcd_arg), (int64_t)B * Op};
     return 0;
 }
 
@@ -1119,6 +1203,9 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
     if (fmt != ACTMI_IMG_U8_NHWC && fmt != ACTMI_IMG_F32_NCHW) { ctx->err = "bad image format"; return ACTMI_E_INVALID; }
     const actmi_config& g = ctx->cfg;
     const int D = g.hidden_dim, N = ctx->N;
+    const float *pc_xyz = nullptr, *pc_rgb = nullptr;
+    int pc_P = 0;
+    if (ctx->fwd_phase != 2) CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_P));     // (before anything is launched)
     // actmi_set_forward_phase: the step as two halves a caller can capture into two graphs -- the trunk with the token assembly
     // (the only reader of `image` and `qpos`, and the HBM-heavy part) and the transformer -- so that the host-to-device copy of the
     // NEXT frame hangs on an ordinary stream event between them and runs beside the transformer.  Phase 2 continues from the tokens
@@ -1141,6 +1228,8 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
         CHK(launch_small_linear(qpos, g.state_dim, ctx->P("input_proj_robot_state.weight"),
                                 ctx->P("input_proj_robot_state.bias"), ctx->X + D, (int64_t)N * D, B, D, g.state_dim, st, fill_dst,
                                 ctx->P("latent_out_proj.bias"), 0));
+        // token 2: the point cloud (detr_vae.py:205-207), part of phase 1 like the trunk
+        if (ctx->has_pcd) CHK(engine_pointnet(ctx, pc_xyz, pc_rgb, B, pc_P, st));
         if (ctx->fwd_phase == 1) { ctx->last_B = B; return 0; }
     } else if (B != ctx->last_B) {
         ctx->err = "forward phase 2 without a phase 1 of the same batch before it";

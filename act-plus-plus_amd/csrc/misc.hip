@@ -137,9 +137,9 @@ __global__ void bn_fold_kernel(const float* __restrict__ w, const float* __restr
     bias[i] = b[i] - rm[i] * s;
 }
 
-// feature row m = ((cam*B + b)*fh + h)*fw + w  ->  token row b*N + 2 + h*(fw*C) + cam*fw + w
-// (concat along width at detr_vae.py:216, flatten(2).permute at transformer.py:60, 2 extra tokens in front :102)
-__global__ void build_rowmap_kernel(int* __restrict__ map, int B, int C, int fh, int fw, int N) {
+// feature row m = ((cam*B + b)*fh + h)*fw + w  ->  token row b*N + n_extra + h*(fw*C) + cam*fw + w
+// (concat along width at detr_vae.py:216, flatten(2).permute at transformer.py:60, n_extra = 2 or 3 extra tokens in front :94-102)
+__global__ void build_rowmap_kernel(int* __restrict__ map, int B, int C, int fh, int fw, int N, int n_extra) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= C * B * fh * fw) return;
     const int w = m % fw;
@@ -147,7 +147,7 @@ __global__ void build_rowmap_kernel(int* __restrict__ map, int B, int C, int fh,
     const int h = r % fh; r /= fh;
     const int b = r % B;
     const int cam = r / B;
-    map[m] = b * N + 2 + h * (fw * C) + cam * fw + w;
+    map[m] = b * N + n_extra + h * (fw * C) + cam * fw + w;
 }
 
 // image (u8 NHWC [B][C][H][W][3] or f32 NCHW [B][C][3][H][W]) -> normalised f32 camera-major NHWC4 [C][B][H][W][4]
@@ -547,9 +547,9 @@ int launch_permute_conv_k(const float* src, float* dst, int64_t rows, int taps, 
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int launch_build_rowmap(int* map, int B, int C, int fh, int fw, int N, hipStream_t st) {
+int launch_build_rowmap(int* map, int B, int C, int fh, int fw, int N, int n_extra, hipStream_t st) {
     const int total = C * B * fh * fw;
-    hipLaunchKernelGGL(build_rowmap_kernel, dim3((total + 255) / 256), dim3(256), 0, st, map, B, C, fh, fw, N);
+    hipLaunchKernelGGL(build_rowmap_kernel, dim3((total + 255) / 256), dim3(256), 0, st, map, B, C, fh, fw, N, n_extra);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

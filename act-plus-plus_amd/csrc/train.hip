@@ -297,7 +297,7 @@ int enc_fwd(actmi_ctx* ctx, const EncW& w, EncSave& s, float* out, const float* 
 
 // backward of the same layer: dOut -> dIn (dIn may alias T.gB); grads accumulate into the gradient arena
 int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, float* dIn, const float* pos, int B, int n,
-            const uint8_t* kpm, float* dpos2 /* [2][D] additional_pos_embed grad or null */, const Drop& dr, hipStream_t st) {
+            const uint8_t* kpm, float* dpos2 /* [n_extra][D] additional_pos_embed grad or null */, const Drop& dr, hipStream_t st) {
     TrainState& T = *ctx->train;
     const actmi_config& g = ctx->cfg;
     const int D = g.hidden_dim, F = g.dim_feedforward, M = B * n, hd = D / g.nheads;
@@ -349,14 +349,15 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
     CHK(lin_wgrad(ctx, Grad{gQKV + 2 * D, 3 * D, M, D, qkv_sc}, s.x_in, D, D, nullptr, 0, Gp(w.attn.in_w) + (int64_t)2 * D * D, nullptr, st));
     CHK(colsum_d(ctx, gQKV, 3 * D, Gp(w.attn.in_b), M, 3 * D, st));
     if (dpos2) {
-        // additional_pos_embed rows: d(x+pos)[b][j] = dQK[b][j] W_in[0:2D], summed over the batch, j in {0,1}
+        // additional_pos_embed rows: d(x+pos)[b][j] = dQK[b][j] W_in[0:2D], summed over the batch, j < n_extra
+        const int ne = ctx->n_extra;
         GemmArgs a = G0();
-        a.A = gQKV; a.lda = 3 * D; a.a_rowmap = T.pos_rows; a.M = 2 * B; a.K = 2 * D; a.Bw = w.attn.in_w; a.ldb = D; a.tb = 1;
+        a.A = gQKV; a.lda = 3 * D; a.a_rowmap = T.pos_rows; a.M = ne * B; a.K = 2 * D; a.Bw = w.attn.in_w; a.ldb = D; a.tb = 1;
         a.N = D; a.C = T.tmp2BD; a.ldc = D;
         a.b_scale = ctx->bwd_wscale;
         a.a_scale_dev = measured(ctx, gQKV, 3 * D, M, 2 * D, st).scale;
         CHK(tgemm(ctx, a, st));
-        CHK(launch_sum_batch(T.tmp2BD, 2 * D, D, dpos2, B, 2, D, 1, st));
+        CHK(launch_sum_batch(T.tmp2BD, (int64_t)ne * D, D, dpos2, B, ne, D, 1, st));
     }
     return 0;
 }
@@ -535,11 +536,20 @@ int train_create(actmi_ctx* ctx) {
     ALLOC(T.delta, (int64_t)B * H * (N > Q + 2 ? N : Q + 2));
     CHK(train_fit_prec(ctx));
     ALLOC(T.dXg, (int64_t)B * (C * ctx->P_ > Q ? C * ctx->P_ : Q) * D);
-    ALLOC(T.tmp2BD, (int64_t)2 * B * D); ALLOC(T.tmpD, 4 * D); ALLOC(T.dqb, BQ * D);
+    const int ne = ctx->n_extra;
+    ALLOC(T.tmp2BD, (int64_t)ne * B * D); ALLOC(T.tmpD, 4 * D); ALLOC(T.dqb, BQ * D);
+    if (ctx->has_pcd) {
+        // saved for the backward of the point-cloud branch: O(B * O * H), the winners of the maximum only
+        const int64_t Hp = ctx->pcd.hidden_dim, Op = ctx->pcd.output_dim, RH = (int64_t)B * Op * Hp;
+        ALLOC(T.pcd_win, B * Op); ALLOC(T.pcd_dfeat, B * Op); ALLOC(T.pcd_dtok, (int64_t)B * D);
+        ALLOC(T.pcd_z0, RH); ALLOC(T.pcd_a0, RH); ALLOC(T.pcd_z3, RH); ALLOC(T.pcd_a3, RH); ALLOC(T.pcd_z6, RH); ALLOC(T.pcd_a6, RH);
+        ALLOC(T.pcd_g0, RH); ALLOC(T.pcd_g1, RH);
+    }
     {
-        std::vector<int> rows(2 * B);
-        for (int b = 0; b < B; ++b) { rows[2 * b] = b * N; rows[2 * b + 1] = b * N + 1; }
-        ALLOC(T.pos_rows, 2 * B);
+        std::vector<int> rows((size_t)ne * B);
+        for (int b = 0; b < B; ++b)
+            for (int j = 0; j < ne; ++j) rows[(size_t)ne * b + j] = b * N + j;
+        ALLOC(T.pos_rows, ne * B);
         if (hipMemcpy(T.pos_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "hipMemcpy failed"; return ACTMI_E_LAUNCH; }
         // note: rows are for the max batch layout; entries b < B_call are valid for any smaller batch too
     }
@@ -590,6 +600,9 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
     if (!ctx->finalized) { ctx->err = "forward before finalize"; return ACTMI_E_STATE; }
     if (B < 1 || B > ctx->cfg.max_batch) { ctx->err = "batch exceeds max_batch"; return ACTMI_E_INVALID; }
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) { ctx->err = "dropout_p must be in [0, 1)"; return ACTMI_E_INVALID; }
+    const float *pc_xyz = nullptr, *pc_rgb = nullptr;
+    int pc_P = 0;
+    CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_P));            // (before anything is launched)
     PrecScope prec_scope(ctx);               // the opt-in bf16 product mode covers the GEMMs of this call only
     TrainState& T = *ctx->train;
     const actmi_config& g = ctx->cfg;
@@ -660,7 +673,7 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
         x = bs.out;
     }
     if (ctx->rowmap_B != B) {
-        CHK(launch_build_rowmap(ctx->rowmap, B, C, ctx->fh, ctx->fw, N, st));
+        CHK(launch_build_rowmap(ctx->rowmap, B, C, ctx->fh, ctx->fw, N, ctx->n_extra, st));
         ctx->rowmap_B = B;
     }
     {
@@ -670,6 +683,21 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
     }
     CHK(launch_small_linear(qpos, S, ctx->P("input_proj_robot_state.weight"), ctx->P("input_proj_robot_state.bias"),
                             ctx->X + D, (int64_t)N * D, B, D, S, st));
+    if (ctx->has_pcd) {
+        // token 2: the point cloud.  The dense forward keeps nothing: only the point that won a column carries gradient through
+        // the maximum, so the B * O winners are gathered and layers 0-6 run again for those rows alone, saving their
+        // pre-activations (the backward treats every (sample, column) pair as a row of its own)
+        CHK(engine_pointnet(ctx, pc_xyz, pc_rgb, B, pc_P, st));
+        const PcdW& w = ctx->pcdw;
+        const int Hp = ctx->pcd.hidden_dim, Op = ctx->pcd.output_dim, R2 = B * Op;
+        T.pcd_xyz = pc_xyz; T.pcd_rgb = pc_rgb; T.pcd_P = pc_P;
+        CHK(launch_pcd_winner_rows(ctx->pcd_arg, T.pcd_win, B, pc_P, Op, st));
+        CHK(launch_pcd_embed(pc_xyz, pc_rgb, T.pcd_win, w.w0, w.b0, T.pcd_a0, T.pcd_z0, R2, Hp, st));
+        CHK(lin_fwd(ctx, T.pcd_a0, Hp, R2, Hp, w.w3, Hp, w.b3, T.pcd_z3, Hp, nullptr, 0, st));
+        CHK(launch_gelu(T.pcd_z3, T.pcd_a3, (int64_t)R2 * Hp, st));
+        CHK(lin_fwd(ctx, T.pcd_a3, Hp, R2, Hp, w.w6, Hp, w.b6, T.pcd_z6, Hp, nullptr, 0, st));
+        CHK(launch_gelu(T.pcd_z6, T.pcd_a6, (int64_t)R2 * Hp, st));
+    }
 
     // ---- encoder
     for (int l = 0; l < g.enc_layers; ++l) {
@@ -865,12 +893,12 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     float* dpos2 = GP("additional_pos_embed.weight");
     {
         GemmArgs a = G0();
-        a.A = dKV; a.lda = 2 * D; a.a_rowmap = T.pos_rows; a.M = 2 * B; a.K = D; a.Bw = d.cross.in_w + (int64_t)D * D; a.ldb = D;
+        a.A = dKV; a.lda = 2 * D; a.a_rowmap = T.pos_rows; a.M = ctx->n_extra * B; a.K = D; a.Bw = d.cross.in_w + (int64_t)D * D; a.ldb = D;
         a.tb = 1; a.N = D; a.C = T.tmp2BD; a.ldc = D;
         a.b_scale = ctx->bwd_wscale;
         a.a_scale_dev = measured(ctx, dKV, 2 * D, B * N, D, st).scale;
         CHK(tgemm(ctx, a, st));
-        CHK(launch_sum_batch(T.tmp2BD, 2 * D, D, dpos2, B, 2, D, 1, st));
+        CHK(launch_sum_batch(T.tmp2BD, (int64_t)ctx->n_extra * D, D, dpos2, B, ctx->n_extra, D, 1, st));
     }
     // ---- encoder layers, last to first.  dOut lives in gB; each layer returns its dIn in gB again.
     for (int l = g.enc_layers - 1; l >= 0; --l)
@@ -891,7 +919,29 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
         CHK(lin_dgrad(ctx, measured(ctx, dX, (int64_t)N * D, B, D, st), ctx->P("latent_out_proj.weight"), Lz, T.dz, Lz, nullptr, nullptr, st));
     }
     CHK(colsum_d(ctx, dX, (int64_t)N * D, GP("latent_out_proj.bias"), B, D, st));
-    // tokens 2..: input_proj (1x1 conv) of the layer4 maps
+    // token 2: the point cloud = input_proj_pointnet(max over the points of the PointNet).  Dense MLP backward over the B * O
+    // winner rows saved by the forward; row (b, c) carries the gradient of column c of sample b alone
+    if (ctx->has_pcd) {
+        const PcdW& w = ctx->pcdw;
+        const int Hp = ctx->pcd.hidden_dim, Op = ctx->pcd.output_dim, R2 = B * Op;
+        const int64_t RH = (int64_t)R2 * Hp;
+        float *g0 = T.pcd_g0, *g1 = T.pcd_g1;
+        // (debug view: the gradient that reaches the token, [B][D]; dX is scratch of the CVAE encoder's backward further down)
+        HIPCHK(hipMemcpy2DAsync(T.pcd_dtok, (size_t)D * 4, dX + 2 * D, (size_t)N * D * 4, (size_t)D * 4, B, hipMemcpyDeviceToDevice, st));
+        ctx->dbg["pcd_dtoken"] = {T.pcd_dtok, (int64_t)B * D};
+        CHK(lin_bwd(ctx, measured(ctx, dX + 2 * D, (int64_t)N * D, B, D, st), w.pw, Op, ctx->pcd_feat, Op, T.pcd_dfeat, Op, Gp(w.pw),
+                    Gp(w.pb), st));
+        CHK(colsum_d(ctx, T.pcd_dfeat, Op, Gp(w.b9), B, Op, st));
+        CHK(launch_pcd_head_bwd(T.pcd_dfeat, w.w9, T.pcd_a6, g0, Gp(w.w9), B, Op, Hp, st));                     // g0 = dA6
+        CHK(launch_gelu_bwd(T.pcd_z6, g0, g1, RH, st));                                                           // g1 = dZ6
+        CHK(lin_bwd(ctx, measured(ctx, g1, Hp, R2, Hp, st), w.w6, Hp, T.pcd_a3, Hp, g0, Hp, Gp(w.w6), Gp(w.b6), st)); // g0 = dA3
+        CHK(launch_gelu_bwd(T.pcd_z3, g0, g1, RH, st));                                                           // g1 = dZ3
+        CHK(lin_bwd(ctx, measured(ctx, g1, Hp, R2, Hp, st), w.w3, Hp, T.pcd_a0, Hp, g0, Hp, Gp(w.w3), Gp(w.b3), st)); // g0 = dA0
+        CHK(launch_gelu_bwd(T.pcd_z0, g0, g1, RH, st));                                                           // g1 = dZ0
+        CHK(launch_pcd_wgrad0(g1, T.pcd_xyz, T.pcd_rgb, T.pcd_win, Gp(w.w0), R2, Hp, T.det_ws, T.det_ws_floats, st));
+        CHK(colsum_d(ctx, g1, Hp, Gp(w.b0), R2, Hp, st));
+    }
+    // tokens n_extra..: input_proj (1x1 conv) of the layer4 maps
     const int MP = C * B * ctx->P_;
     CHK(launch_gather_rows(dX, ctx->rowmap, T.dXg, MP, D, st));
     const BlockSave& last = T.blocks.back();

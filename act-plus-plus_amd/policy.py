@@ -72,8 +72,8 @@ class ACTPolicy:
         self.use_depth = args_override.get("use_depth", False)
         self.use_pcd = args_override.get("use_pcd", False)
         self.depth_camera_names = args_override.get("depth_camera_names", None)
-        if self.use_depth or self.use_pcd:
-            raise NotImplementedError("depth / point-cloud inputs are outside the accelerated ACT path")
+        if self.use_depth:
+            raise NotImplementedError("depth inputs are outside the accelerated ACT path")
         self.cfg = ACTConfig.from_policy_config(args_override)
         self.kl_weight = args_override["kl_weight"]
         self.vq = args_override.get("vq", False)
@@ -82,7 +82,8 @@ class ACTPolicy:
         # GPU: dist_utils.init_from_env has made cuda:LOCAL_RANK current) -- never a hard-coded cuda:0
         if device is None:
             device = args_override.get("device") or (f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cuda:0")
-        self.model = ACTEngine(self.cfg, max_batch=mb, device=device, training=bool(args_override.get("training", True)))
+        self.model = ACTEngine(self.cfg, max_batch=mb, device=device, training=bool(args_override.get("training", True)),
+                               max_points=int(args_override.get("max_points", 4096)))
         # random init of the reference architecture (the ImageNet fetch of backbone.py:121-124 cannot run offline)
         from actmi.weights import generate_state_dict
         self.model.load_state_dict(generate_state_dict(self.cfg, seed=init_seed))
@@ -94,6 +95,9 @@ class ACTPolicy:
         print(f"Use Depth: {self.use_depth}")
 
     def __call__(self, qpos, image, actions=None, is_pad=None, vq_sample=None, depth_img=None, pointcloud=None):
+        if self.use_pcd and pointcloud is None:
+            raise ValueError("a use_pcd policy needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]}")
+        pointcloud = pointcloud if self.use_pcd else None       # reference policy.py:301, 329
         if actions is not None:                                # training / validation (policy.py:288-320)
             eps = getattr(self, "next_eps", None)
             self.next_eps = None
@@ -103,13 +107,14 @@ class ACTPolicy:
             code = getattr(self, "next_vq_code", None)          # tests: replay the reference's multinomial draw
             self.next_vq_code = None
             out = self.model.forward_train(qpos, image, actions, is_pad, eps=eps, dropout_p=p,
-                                           dropout_seed=(self.dropout_seed << 20) + self._drop_step, vq_code=code)
+                                           dropout_seed=(self.dropout_seed << 20) + self._drop_step, vq_code=code,
+                                           pointcloud=pointcloud)
             loss_dict = {"l1": out["l1"], "kl": out["kl"], "loss": _Loss.wrap(out["loss"], self)}
             if self.vq:                                         # policy.py:311-312 (logged, not part of the loss)
                 loss_dict["vq_discrepancy"] = out["vq_discrepancy"]
             return loss_dict
         # inference: ImageNet normalisation (policy.py:268-272) is fused into the conv1 loader
-        return self.model.forward_infer(qpos, image, vq_sample=vq_sample)
+        return self.model.forward_infer(qpos, image, vq_sample=vq_sample, pointcloud=pointcloud)
 
     # ---- nn.Module-like surface used by imitate_episodes.py ---------------------------------------
     def cuda(self):

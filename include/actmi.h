@@ -212,6 +212,26 @@ int actmi_version(void);
 /* ---- lifecycle ------------------------------------------------------------------------------------ */
 /* replaces build_ACT_model_and_optimizer (detr/main.py:92-112) without touching sys.argv */
 int actmi_create(const actmi_config* cfg, actmi_handle* out);
+
+/* Point-cloud input (reference --use_pcd: detr/models/pointnet.py, detr_vae.py:64-65, 98-100, 205-210): a PointNet over the
+ * fused RGB-D cloud -- Linear(6, H) GELU Linear(H, H) GELU Linear(H, H) GELU Linear(H, O), maximum over the points,
+ * input_proj_pointnet: Linear(O, hidden_dim) -- becomes a third token [latent, proprio, pcl] in front of the image tokens;
+ * additional_pos_embed.weight is [3][hidden_dim] and the state_dict gains input_proj_pointnet.* and
+ * pcl_backbone.pointnet._mlp.{0,3,6,9}.*.  hidden_depth is 3 and subtract_mean is off, as the reference's build() leaves them.
+ * hidden_dim, output_dim and actmi_config.hidden_dim must be multiples of 32. */
+typedef struct actmi_pcd_config {
+    uint32_t struct_size;      /* sizeof(actmi_pcd_config), same guard as actmi_config */
+    int32_t max_points;        /* workspace is sized for this many points per sample */
+    int32_t hidden_dim;        /* H, 512 in the reference */
+    int32_t output_dim;        /* O, 512 in the reference */
+} actmi_pcd_config;
+/* actmi_create plus the point-cloud branch; pcd == NULL is exactly actmi_create */
+int actmi_create_ex(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_handle* out);
+/* binds the clouds that the NEXT actmi_forward_infer / _infer_vq / _forward_train reads (forward phase 2 reads none):
+ * xyz, rgb: [B][P][3] f32 device, 1 <= P <= max_points; the pointers must stay valid until that forward (and, for training,
+ * until actmi_backward) has been enqueued.  A forward of a point-cloud handle without bound clouds, or with another B, returns
+ * ACTMI_E_STATE; so does this call on a handle created without a point-cloud config. */
+int actmi_set_pointcloud(actmi_handle h, const float* xyz, const float* rgb, int B, int P);
 int actmi_destroy(actmi_handle h);
 const char* actmi_last_error(actmi_handle h);   /* h may be NULL: last error of a failed create */
 
@@ -414,6 +434,16 @@ int actmi_op_layernorm_bwd(const float* x, const float* w, const float* dy, cons
                            int M, int D, float eps, float* ws, int64_t ws_floats, void* stream);
 /* out[n] += sum_m src[m][n] (bias gradients); with ws (>= ceil(M/256)*N floats) in a fixed order */
 int actmi_op_colsum(const float* src, int64_t ld, float* out, int M, int N, float* ws, int64_t ws_floats, void* stream);
+/* PointNet layer 0 with the concatenation and the exact GELU fused (fp32 FMAs in every precision mode):
+ * out[r][h] = gelu(sum_k cat(xyz[r], rgb[r])[k] * w0[h][k] + b0[h]); xyz, rgb [rows][3], w0 [H][6], out [rows][H], H % 4 == 0,
+ * H <= 2048 */
+int actmi_op_pcd_embed(const float* xyz, const float* rgb, const float* w0, const float* b0, float* out, int64_t rows, int H,
+                       void* stream);
+/* torch.max(x, dim=-2) of x [B][P][ld] over its first O columns: out [B][O] and the int32 index of the winning point
+ * argmax [B][O]; the lowest index wins a tie, a NaN in a column propagates.  With ws (2 * B * S * O floats hold S splits) the
+ * points are split over blocks and the candidates merged in split order: bitwise repeatable.  O % 4 == 0, ld % 4 == 0 */
+int actmi_op_colmax(const float* x, int B, int P, int O, int64_t ld, float* out, int32_t* argmax, float* ws, int64_t ws_floats,
+                    void* stream);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
@@ -423,7 +453,9 @@ int actmi_op_adamw(float* p, const float* g, float* m, float* v, int64_t n, floa
 const char* actmi_op_last_error(void);
 
 /* intermediate activations of the last forward (parity tests): name in {"conv1","maxpool","layer1".."layer4",
- * "src","memory","hs"}; camera-major NHWC for the maps, [B][N][D] for tokens. */
+ * "src","memory","hs"}; camera-major NHWC for the maps, [B][N][D] for tokens.  A point-cloud handle adds "pcd_feat" [B][O]
+ * (the pooled PointNet features) and "pcd_argmax" [B][O] (int32 bits: the winning point of every column), and after actmi_backward
+ * "pcd_dtoken" [B][D], the gradient that reached the point-cloud token. */
 int actmi_debug_tensor(actmi_handle h, const char* name, const float** dev_ptr, int64_t* numel);
 /* debug: make the next forwards return right after the named stage ("" = run everything); the maps of the
  * trunk live in rotating buffers, so a stage is only readable when the forward stopped there. */
