@@ -240,6 +240,25 @@ def conv3x3_c64(x, w_ohwi, scale=None, bias=None, res=None, relu=False, w_scale=
     return out
 
 
+def conv3x3_c64_dgrad(dy, wd_ohwi, dy_scale=None, res=None, mask=None, post_scale=None, amax_out=None, w_scale=256.0):
+    """the direct 3x3 kernel as layer1's data gradient: dy [G,B,H,W,64]; wd_ohwi [G,64 cin,3,3,64 cout] = the flipped, transposed
+    forward weights; dx = where(mask > 0, conv(dy) (+ res), 0) * post_scale[G,64].  dy_scale: pow2_scale tensor of dy;
+    amax_out: one int32 word raised to the bits of max |dx|."""
+    lib = L.load()
+    G, B, H, W, Cc = dy.shape
+    assert Cc == 64 and tuple(wd_ohwi.shape[1:]) == (64, 3, 3, 64)
+    dy = dy.contiguous()
+    dx = torch.empty_like(dy)
+    for t in (res, mask):
+        assert t is None or (t.shape == dy.shape and t.is_contiguous())
+    assert post_scale is None or (tuple(post_scale.shape) == (G, 64) and post_scale.is_contiguous())
+    w16 = split16(wd_ohwi, w_scale)
+    L.check(lib.actmi_op_conv3x3_c64_dgrad(_p(dy), _p(w16), float(w_scale), _p(dy_scale), _p(res),
+                                           _p(mask), _p(post_scale), _p(amax_out), _p(dx), G, B, H, W, L.current_stream_ptr()),
+            None, "op_conv3x3_c64_dgrad")
+    return dx
+
+
 def wgrad3x3_c64(dy, x, dy_scale=None):
     """dW [G][64][3][3][64] (O, kh, kw, I) of the 64 -> 64 channel 3x3 / s1 / p1 convolution from dy, x [G][B][H][W][64]."""
     G, B, H, W, Cc = x.shape

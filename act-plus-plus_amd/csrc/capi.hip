@@ -385,6 +385,20 @@ int actmi_op_conv3x3_c64(const float* x, const float* w16, float w_scale, const 
     return launch_conv3x3_c64(a, S(stream), &g_op_error);
 }
 
+int actmi_op_conv3x3_c64_dgrad(const float* dy, const float* w16, float w_scale, const float* dy_scale_dev, const float* res,
+                               const float* mask, const float* post_scale, uint32_t* amax_out, float* dx, int G, int B, int H,
+                               int W, void* stream) {
+    g_op_error.clear();
+    if (!dy || !w16 || !dx || (((uintptr_t)res | (uintptr_t)mask | (uintptr_t)post_scale | (uintptr_t)dx) & 15)) {
+        g_op_error = "conv3x3_c64_dgrad: dy, w16 and dx are required; res, mask, post_scale and dx must be 16-byte aligned";
+        return ACTMI_E_INVALID;
+    }
+    Conv3Args a;
+    a.x = dy; a.w16 = w16; a.scale = nullptr; a.bias = nullptr; a.res = res; a.out = dx;
+    a.G = G; a.B = B; a.H = H; a.W = W; a.relu = 0; a.w_scale = w_scale;
+    a.x_scale_dev = dy_scale_dev; a.mask = mask; a.post_scale = post_scale; a.amax_out = amax_out;
+    return launch_conv3x3_c64(a, S(stream), &g_op_error);
+}
 
 int actmi_op_wgrad3x3_c64(const float* dy, const float* x, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev, int G,
                           int B, int H, int W, void* stream) {

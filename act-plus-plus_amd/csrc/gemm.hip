@@ -1162,6 +1162,21 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t st, std::string* err) {
     auto fail = [&](const char* m) { if (err) *err = std::string("gemm: ") + m; return -2; };
     if (a.K <= 0) return fail("K must be positive");
     if (((uintptr_t)a.A & 15) || ((uintptr_t)a.Bw & 15)) return fail("A/B must be 16-byte aligned");
+    if (a.epi != 0) {
+        // the fused attention-backward epilogues exist in the kernel's fast epilogue only: whatever sends a launch to the
+        // feature-complete one (the `simple` test of the kernel) would store plain products without a word
+        if (a.epi != 1 && a.epi != 2) return fail("bad epi");
+        if (!a.epi_row) return fail("epi needs epi_row");
+        if (a.epi == 2 && !a.res) return fail("epi 2 needs res (the factor P)");
+        if (a.rowmap) return fail("epi is not available with a row map");
+        if (a.C2) return fail("epi is not available with a second output (C2)");
+        if (a.drop_p > 0.f) return fail("epi is not available with dropout");
+        if (a.res_mod != 0) return fail("epi is not available with res_mod");
+        if (a.splitk > 1 && a.split_stride == 0) return fail("epi is not available with an atomic split-K");
+        const int64_t lim = (int64_t)1 << 31, ldmask = a.ldmask ? a.ldmask : a.ldc;
+        if ((int64_t)a.M * a.ldc >= lim || (a.res && (int64_t)a.M * a.ldres >= lim) || (a.mask && (int64_t)a.M * ldmask >= lim))
+            return fail("epi needs M*ldc, M*ldres and M*ldmask below 2^31");
+    }
     if (a.splitk > 1 && (a.bias || a.res || a.mask || a.relu || a.C2 || a.scale)) return fail("split-K supports a plain accumulate only");
     if (a.split_stride != 0) {
         if (a.splitk <= 1) return fail("split_stride needs splitk > 1");

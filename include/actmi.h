@@ -142,7 +142,8 @@ typedef struct actmi_gemm_desc {
      * actmi_op_pow2_scale computes with a pass of its own, for the GEMM that reads this output next.  Meaningless with an
      * atomic split-K (partial sums are stored). */
     uint32_t* amax_out;
-    /* fused attention-backward epilogues (training path; fast epilogue forms only, no row map / C2 / dropout):
+    /* fused attention-backward epilogues (training path; fast epilogue forms only: with a row map, C2, dropout, res_mod, an
+     * atomic split-K, or M*ldc / M*ldres / M*ldmask >= 2^31 the launch is rejected with ACTMI_E_SHAPE):
      *   epi = 1: C = exp(v - epi_row[m]), zero where epi_colkill[n] != 0   (v = alpha * acc: softmax probabilities from the
      *            scores and the saved log-sum-exp; epi_colkill = key padding mask, optional)
      *   epi = 2: C = res[m][n] * (v - epi_row[m]) * epi_scale              (dS = P * (dP - delta) * scale; res is a factor here,
@@ -371,6 +372,14 @@ int actmi_op_conv1_prepared(const void* image_u8, const float* workspace, const 
  * out = act(conv * scale + bias (+ res)) */
 int actmi_op_conv3x3_c64(const float* x, const float* w16, float w_scale, const float* scale, const float* bias,
                          const float* res, float* out, int G, int B, int H, int W, int relu, void* stream);
+/* the same kernel in its data-gradient role (training path, layer1 in f16x3): dy [G][B][H][W][64] is a gradient map, w16 the
+ * split image (built with w_scale) of the flipped, transposed forward weights [G][64 cin][(2-r, 2-s, cout) = 576];
+ * dx = where(mask > 0, conv(dy) (+ res), 0) * post_scale[G][64].  dy_scale_dev: optional device power-of-two scale applied to dy
+ * before the fp16 split and undone in the result (actmi_op_pow2_scale); mask (same shape as dx), post_scale and res are optional;
+ * amax_out (optional): raised to the bits of the largest |dx| stored (zero, or an earlier maximum, on entry) */
+int actmi_op_conv3x3_c64_dgrad(const float* dy, const float* w16, float w_scale, const float* dy_scale_dev, const float* res,
+                               const float* mask, const float* post_scale, uint32_t* amax_out, float* dx, int G, int B, int H,
+                               int W, void* stream);
 /* weight gradient of the same 64 -> 64 channel 3x3 / s1 / p1 convolution (training path; torch.autograd of F.conv2d in
  * torchvision's BasicBlock, reference backbone.py:95-134), f16x3 arithmetic: dw[G][64][(r,s,ci)] = sum over images and pixels of
  * dy[G][B][H][W][64] x x[G][B][H][W][64] shifted by the tap.  ws: workspace of >= G * 64 * 576 * min(256 / G, B * ceil(W/32))

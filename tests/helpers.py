@@ -38,3 +38,26 @@ def sample_like(a, z):
 
 def torch_sd(sd_np, prefix="model."):
     return {prefix + k: torch.from_numpy(v) for k, v in sd_np.items()}
+
+
+def rel_err(got, exp):
+    """max |got - exp| over max |exp|, in float64 on the CPU"""
+    got, exp = got.detach().cpu().double(), exp.detach().cpu().double()
+    return float((got - exp).abs().max() / (exp.abs().max() + 1e-30))
+
+
+def gemm_desc(**kw):
+    """an actmi_gemm_desc from keyword fields; tensors become their device addresses (the caller keeps them alive)"""
+    from actmi import lib as L
+    d = L.GemmDesc()
+    for k, v in kw.items():
+        setattr(d, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    return d
+
+
+def run_gemm(what, **kw):
+    """actmi_op_gemm on the current stream; RuntimeError with the library's message when the launch is rejected"""
+    import ctypes as C
+    from actmi import lib as L
+    desc = gemm_desc(**kw)
+    L.check(L.load().actmi_op_gemm(C.byref(desc), L.current_stream_ptr()), None, what)

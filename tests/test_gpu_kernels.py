@@ -11,6 +11,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from actmi import ops  # noqa: E402
+from helpers import run_gemm  # noqa: E402
 
 
 def dev():
@@ -199,6 +200,54 @@ def test_conv3x3_c64_direct(G, B, H, W, with_res):
                           scale.to(d), bias.to(d), res.permute(0, 1, 3, 4, 2).contiguous().to(d) if with_res else None,
                           relu=True, stride=1, pad=1, prec="f16x3")
     assert rel_err(got, ref) < 2e-6
+
+
+@pytest.mark.parametrize("with_res", [False, True])
+@pytest.mark.parametrize("G,B,H,W", [(2, 2, 16, 32), (1, 3, 15, 20), (1, 1, 9, 70)])
+def test_conv3x3_c64_as_data_gradient(G, B, H, W, with_res):
+    """the same kernel in the role conv_dgrad gives it for layer1 (actmi_op_conv3x3_c64_dgrad): a gradient map at 1e-6 under
+    its device-side power-of-two scale, the flipped and transposed weights of a forward convolution, the ReLU mask of the
+    layer below, its per-group per-channel FrozenBN scale AFTER the mask, and the amax word:
+    dx = where(mask > 0, dgrad (+ res), 0) * post_scale against float64 autograd; and against the gather GEMM (mode 2) on the
+    same operands -- that kernel applies a per-channel scale before the residual, so its scale is applied to its output here."""
+    g = torch.Generator().manual_seed(H * 7 + W + 1)
+    x = torch.zeros(G, B, 64, H, W, dtype=torch.float64, requires_grad=True)
+    w = (torch.randn(G, 64, 64, 3, 3, generator=g) / 24.0)                        # forward weights [G][cout][cin][r][s]
+    dy = torch.randn(G, B, 64, H, W, generator=g) * 1e-6
+    for i in range(G):
+        F.conv2d(x[i], w[i].double(), None, 1, 1).backward(dy[i].double())
+    mask = torch.randn(G, B, 64, H, W, generator=g)
+    mask[mask.abs() < 0.3] = 0.0                                                  # zeros, negatives and positives
+    post = torch.rand(G, 64, generator=g) + 0.5
+    res = torch.randn(G, B, 64, H, W, generator=g) * (0.5 * float(x.grad.abs().max())) if with_res else None
+    raw = x.grad + (res.double() if with_res else 0.0)
+    exp = torch.where(mask > 0, raw, torch.zeros_like(raw)) * post.double().view(G, 1, 64, 1, 1)
+    d = dev()
+
+    def nhwc(t):
+        return t.permute(0, 1, 3, 4, 2).contiguous().to(d)
+    dyd, maskd, postd = nhwc(dy), nhwc(mask), post.to(d)
+    resd = nhwc(res) if with_res else None
+    sc = ops.pow2_scale(dyd.view(-1, 64))
+    amax = torch.zeros(1, dtype=torch.int32, device=d)
+    wd = w.flip(3, 4).permute(0, 2, 3, 4, 1).contiguous().to(d)                   # [G][cin][2-r][2-s][cout]
+    got = ops.conv3x3_c64_dgrad(dyd, wd, dy_scale=sc, res=resd, mask=maskd, post_scale=postd, amax_out=amax)
+    e = rel_err(got.permute(0, 1, 4, 2, 3), exp)
+    # the gather GEMM: weights [G][cin][(r,s,cout)] unflipped, the same scales, residual and mask
+    wg = w.permute(0, 2, 3, 4, 1).contiguous().to(d)
+    ref = torch.zeros_like(got)
+    n = B * H * W * 64
+    run_gemm("dgrad", mode=2, A=dyd, H=H, W=W, Cin=64, KH=3, KW=3, stride=1, pad=1, Ho=H, Wo=W, img_stride=H * W * 64, M=B * H * W,
+             N=64, K=576, Bw=wg, ldb=576, C=ref, ldc=64, groups=G, gA=n, gB=64 * 576, gC=n, res=resd, ldres=64, gRes=n,
+             mask=maskd, ldmask=64, gMask=n, b_scale=256.0, a_scale_dev=sc, prec=ops.PREC["f16x3"])
+    ref = ref * postd.view(G, 1, 1, 1, 64)
+    e2 = rel_err(got, ref)
+    print(f"conv3x3_c64 as dgrad {(G, B, H, W)} res={with_res}: {e:.2e} against float64 (bound 2.0e-06), {e2:.2e} against the "
+          f"gather GEMM (bound 3.0e-06)")
+    assert e < 2e-6
+    assert e2 < 3e-6
+    assert int(amax) == int(got.abs().max().cpu().view(torch.int32)), "amax_out: the bits of the largest stored magnitude"
+    assert bool((got.permute(0, 1, 4, 2, 3).cpu()[mask <= 0] == 0).all())
 
 
 @pytest.mark.parametrize("B,H,Nq,Nk,hd,masked,shared", [(2, 8, 1202, 1202, 64, False, False), (3, 8, 100, 1202, 64, False, True),

@@ -11,23 +11,11 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from helpers import load_fixture, regenerate, sample_like  # noqa: E402
+from helpers import gemm_desc as _gemm_desc, load_fixture, regenerate, rel_err, sample_like  # noqa: E402
 from actmi import weights as W  # noqa: E402
 from actmi import lib as L  # noqa: E402
 from actmi import ops  # noqa: E402
 from actmi.engine import ACTEngine  # noqa: E402
-
-
-def rel_err(got, exp):
-    got, exp = got.detach().cpu().double(), exp.detach().cpu().double()
-    return float((got - exp).abs().max() / (exp.abs().max() + 1e-30))
-
-
-def _gemm_desc(**kw):
-    d = L.GemmDesc()
-    for k, v in kw.items():
-        setattr(d, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-    return d
 
 
 @pytest.mark.parametrize("M,N,K", [(77, 130, 96), (1202, 64, 1202), (16, 512, 800), (300, 36, 17)])
@@ -94,11 +82,11 @@ def test_conv_dgrad_wgrad(G, B, H, W, Cin, Cout, k, stride, pad):
     assert rel_err(gw.permute(0, 1, 4, 2, 3), w.grad) < 3e-6
 
 
-def _run_training_fixture(name, check_all):
+def _run_training_fixture(name, check_all, gemm_prec=None):
     z, cfg = load_fixture(name)
     sd_np, inp = regenerate(z, cfg)
     B = int(z["batch"])
-    eng = ACTEngine(cfg, max_batch=B, training=True)
+    eng = ACTEngine(cfg, max_batch=B, training=True, gemm_prec=gemm_prec)
     eng.load_state_dict(sd_np)
     eng.finalize()
     d = eng.device
@@ -154,9 +142,12 @@ def _run_training_fixture(name, check_all):
     return eng, z, cfg, sd_np, inp
 
 
-@pytest.mark.parametrize("name", ["tiny", "tiny_c3", "tiny_vq"])
-def test_training_step_matches_reference_gradients(name):
-    _run_training_fixture(name, True)
+@pytest.mark.parametrize("name,gemm_prec", [pytest.param(n, p, id=n if p is None else f"{n}-{p}")
+                                            for p in (None, "f32") for n in ("tiny", "tiny_c3", "tiny_vq")])
+def test_training_step_matches_reference_gradients(name, gemm_prec):
+    """gemm_prec None: the default step (f16x3).  "f32": the native-fp32 step, which takes other code -- the materialised
+    attention backward everywhere, the gather GEMM for layer1's data gradients, no operand scales -- held to the same bounds."""
+    _run_training_fixture(name, True, gemm_prec)
 
 
 def test_training_full_size_gradients_and_adamw():
@@ -188,6 +179,12 @@ def test_training_full_size_gradients_and_adamw():
     d = eng.device
     a1 = eng.forward_infer(torch.from_numpy(inp["qpos"]).to(d), torch.from_numpy(inp["image_u8"]).to(d))
     assert torch.isfinite(a1).all()
+
+
+def test_training_full_size_gradients_native_fp32():
+    """the gradient part of full4 on the native-fp32 step (ACTEngine(gemm_prec="f32")): losses, gradient norms of every
+    parameter and the sampled elements, at the bounds of the default precision"""
+    _run_training_fixture("full4", False, gemm_prec="f32")
 
 
 def test_dropout_epilogue_statistics_and_determinism():
