@@ -160,6 +160,21 @@ def load():
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),
+        "actmi_op_maxpool3x3s2_idx": ([vp, vp, vp, i32, i32, i32, i32, vp], i32),
+        "actmi_op_maxpool3x3s2_bwd": ([vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp], i32),
+        "actmi_op_relu_bn_bwd": ([vp, vp, vp, vp, vp, vp, i32, i64, i32, vp, vp], i32),
+        "actmi_op_act_losses": ([vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, vp], i32),
+        "actmi_op_l1_bwd": ([vp, vp, vp, vp, i32, i32, i32, f32, vp], i32),
+        "actmi_op_reparam": ([vp, vp, vp, vp, vp, i32, i32, vp], i32),
+        "actmi_op_reparam_kl_bwd": ([vp, vp, vp, vp, i32, i32, f32, vp], i32),
+        "actmi_op_vq_bwd": ([vp, vp, vp, i32, i32, i32, vp], i32),
+        "actmi_op_dropout_bwd": ([vp, vp, i64, f32, C.c_uint64, vp], i32),
+        "actmi_op_attn_delta": ([vp, vp, vp, i32, i32, i32, i32, vp], i32),
+        "actmi_op_attn_drop": ([vp, vp, C.c_uint64, f32, i32, i32, i32, i32, vp], i32),
+        "actmi_op_attn_ds_drop": ([vp, vp, vp, f32, C.c_uint64, f32, i32, i32, i32, i32, vp], i32),
+        "actmi_op_zero_cols": ([vp, i64, i32, i32, vp], i32),
+        "actmi_op_adamw_groups": ([vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, i64, vp, C.c_uint32, vp], i32),
+        "actmi_op_layernorm_bwd_ex": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, i64, vp, vp], i32),
         "actmi_op_last_error": ([], C.c_char_p),
         "actmi_debug_tensor": ([vp, C.c_char_p, C.POINTER(vp), C.POINTER(i64)], i32),
         "actmi_debug_stop_after": ([vp, C.c_char_p], i32),

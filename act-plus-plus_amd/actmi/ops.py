@@ -564,10 +564,11 @@ def layernorm_bwd(x, w, dy, dw, db, ws, dx_add=None, eps=1e-5):
     return dx
 
 
-def colsum(src, out, ws):
-    """out[n] += sum_m src[m][n]"""
+def colsum(src, out, ws=None):
+    """out[n] += sum_m src[m][n]; src may be a column view of a wider matrix (row stride = its stride(0))"""
     M, N = src.shape
-    L.check(L.load().actmi_op_colsum(_p(src), src.stride(0), _p(out), M, N, _p(ws), ws.numel(), L.current_stream_ptr()), None, "op_colsum")
+    L.check(L.load().actmi_op_colsum(_p(src), src.stride(0), _p(out), M, N, _p(ws), ws.numel() if ws is not None else 0,
+                                     L.current_stream_ptr()), None, "op_colsum")
 
 
 def pcd_embed(xyz, rgb, w0, b0):
@@ -603,6 +604,135 @@ def sum_batch(src, dst, accumulate=False):
 def adamw(p, g, m, v, lr, weight_decay, step, betas=(0.9, 0.999), eps=1e-8):
     L.check(L.load().actmi_op_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(weight_decay), float(betas[0]),
                                     float(betas[1]), float(eps), int(step), L.current_stream_ptr()), None, "op_adamw")
+
+
+# ---- the non-GEMM kernels of the ACT training step (csrc/bwd.hip, csrc/pool.hip), one wrapper per launcher ---------------
+def _st():
+    return L.current_stream_ptr()
+
+
+def maxpool3x3s2_idx(x):
+    """x [n,H,W,C] NHWC -> (out [n,Ho,Wo,C], codes uint8 [n,Ho,Wo,C]): code r*3+s = the window position of the maximum."""
+    n, H, W, Cc = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty((n, Ho, Wo, Cc), dtype=torch.float32, device=x.device)
+    codes = torch.empty((n, Ho, Wo, Cc), dtype=torch.uint8, device=x.device)
+    L.check(L.load().actmi_op_maxpool3x3s2_idx(_p(x), _p(y), _p(codes), n, H, W, Cc, _st()), None, "op_maxpool3x3s2_idx")
+    return y, codes
+
+
+def maxpool3x3s2_bwd(codes, dy, H, W, relu_x=None, bn_scale=None, imgs_per_group=1, amax_out=None):
+    """dx [n,H,W,C] from the codes and dy [n,Ho,Wo,C]; relu_x [n,H,W,C] + bn_scale [groups,C]: the fused ReLU + FrozenBN form,
+    amax_out (one int32 word) raised to the bits of max |dx|."""
+    n, _, _, Cc = dy.shape
+    dx = torch.empty((n, H, W, Cc), dtype=torch.float32, device=dy.device)
+    L.check(L.load().actmi_op_maxpool3x3s2_bwd(_p(codes), _p(dy), _p(dx), n, H, W, Cc, _p(relu_x), _p(bn_scale), int(imgs_per_group),
+                                               _p(amax_out), _st()), None, "op_maxpool3x3s2_bwd")
+    return dx
+
+
+def relu_bn_bwd(x, C_, add=None, mask=None, scale=None, want_plain=True, want_scaled=True, amax_out=None):
+    """x [G, per_group] (NHWC maps of C_ channels, flattened): v = where(mask > 0, x + add, 0); -> (y_plain = v or None,
+    y_scaled = v * scale[g][c] or None)"""
+    G, per_group = x.shape
+    yp = torch.empty_like(x) if want_plain else None
+    ys = torch.empty_like(x) if want_scaled else None
+    L.check(L.load().actmi_op_relu_bn_bwd(_p(x), _p(add), _p(mask), _p(scale), _p(yp), _p(ys), G, per_group, int(C_), _p(amax_out),
+                                          _st()), None, "op_relu_bn_bwd")
+    return yp, ys
+
+
+def act_losses(a_hat, actions, is_pad, latent_info=None, kl_weight=0.0, L_=0, buf=None):
+    """-> tensor [l1, kl, loss] (a view of the 516-float buffer the kernels reduce in); is_pad uint8 [B,Q]"""
+    B, Q, A = a_hat.shape
+    if buf is None:
+        buf = torch.empty(3 + 1 + 512, dtype=torch.float32, device=a_hat.device)
+    L.check(L.load().actmi_op_act_losses(_p(a_hat), _p(actions), _p(is_pad), _p(latent_info), _p(buf), buf.numel(), B, Q, A, int(L_),
+                                         float(kl_weight), _st()), None, "op_act_losses")
+    return buf[:3]
+
+
+def l1_bwd(a_hat, actions, is_pad, gscale=1.0):
+    B, Q, A = a_hat.shape
+    d = torch.empty_like(a_hat)
+    L.check(L.load().actmi_op_l1_bwd(_p(a_hat), _p(actions), _p(is_pad), _p(d), B, Q, A, float(gscale), _st()), None, "op_l1_bwd")
+    return d
+
+
+def reparam(latent_info, eps, want_stats=False):
+    """latent_info [B, 2L] (mu | logvar), eps [B, L] -> z (and copies of mu, logvar)"""
+    B, L2 = latent_info.shape
+    z = torch.empty_like(eps)
+    mu, lv = (torch.empty_like(eps), torch.empty_like(eps)) if want_stats else (None, None)
+    L.check(L.load().actmi_op_reparam(_p(latent_info), _p(eps), _p(z), _p(mu), _p(lv), B, L2 // 2, _st()), None, "op_reparam")
+    return (z, mu, lv) if want_stats else z
+
+
+def reparam_kl_bwd(latent_info, eps, dz, klw_scaled):
+    B, L2 = latent_info.shape
+    d = torch.empty_like(latent_info)
+    L.check(L.load().actmi_op_reparam_kl_bwd(_p(latent_info), _p(eps), _p(dz), _p(d), B, L2 // 2, float(klw_scaled), _st()), None,
+            "op_reparam_kl_bwd")
+    return d
+
+
+def vq_bwd(probs, g):
+    """probs, g [B, VC, VD] -> dlogits"""
+    B, VC, VD = probs.shape
+    d = torch.empty_like(probs)
+    L.check(L.load().actmi_op_vq_bwd(_p(probs), _p(g), _p(d), B, VC, VD, _st()), None, "op_vq_bwd")
+    return d
+
+
+def dropout_bwd(dy, p, seed):
+    dz = torch.empty_like(dy)
+    L.check(L.load().actmi_op_dropout_bwd(_p(dy), _p(dz), dy.numel(), float(p), int(seed), _st()), None, "op_dropout_bwd")
+    return dz
+
+
+def attn_delta(dO, O, nheads):
+    """dO, O [B, Nq, H*HD] -> delta [B, H, Nq]"""
+    B, Nq, D = dO.shape
+    delta = torch.empty((B, nheads, Nq), dtype=torch.float32, device=dO.device)
+    L.check(L.load().actmi_op_attn_delta(_p(dO), _p(O), _p(delta), B, nheads, Nq, D // nheads, _st()), None, "op_attn_delta")
+    return delta
+
+
+def attn_drop(P, Pd, Nk, p, seed):
+    """P, Pd [..., Nq, ldp] (G = the product of the leading dimensions): Pd = P * keep / (1 - p), columns >= Nk zero"""
+    Nq, ldp = P.shape[-2:]
+    L.check(L.load().actmi_op_attn_drop(_p(P), _p(Pd), int(seed), float(p), P.numel() // (Nq * ldp), Nq, int(Nk), ldp, _st()), None,
+            "op_attn_drop")
+
+
+def attn_ds_drop(P, dP, delta, scale, Nk, p, seed):
+    """in place: dP = P * (dP * keep / (1 - p) - delta) * scale, columns >= Nk zero"""
+    Nq, ldp = P.shape[-2:]
+    L.check(L.load().actmi_op_attn_ds_drop(_p(P), _p(dP), _p(delta), float(scale), int(seed), float(p), P.numel() // (Nq * ldp), Nq,
+                                           int(Nk), ldp, _st()), None, "op_attn_ds_drop")
+
+
+def zero_cols(x, c0):
+    """x [..., ld]: the columns c0 .. ld-1 of every row = 0"""
+    ld = x.shape[-1]
+    L.check(L.load().actmi_op_zero_cols(_p(x), x.numel() // ld, ld, int(c0), _st()), None, "op_zero_cols")
+
+
+def adamw_groups(p, g, m, v, group, lr, lr_backbone, weight_decay, step, betas=(0.9, 0.999), eps=1e-8, flags=None, skip_mask=0):
+    """the engine's AdamW: group uint8 per 64-float slot (0 untouched, 1 lr, 2 lr_backbone); flags (one int32 word) & skip_mask
+    non-zero skips the update on the device"""
+    L.check(L.load().actmi_op_adamw_groups(_p(p), _p(g), _p(m), _p(v), _p(group), p.numel(), float(lr), float(lr_backbone),
+                                           float(weight_decay), float(betas[0]), float(betas[1]), float(eps), int(step), _p(flags),
+                                           int(skip_mask), _st()), None, "op_adamw_groups")
+
+
+def layernorm_bwd_ex(x, w, dy, dw, db, ws=None, dx_add=None, eps=1e-5, dx_amax=None):
+    """layernorm_bwd with the dx_amax word (one int32) and an optional workspace"""
+    M, D = x.shape
+    dx = torch.empty_like(x)
+    L.check(L.load().actmi_op_layernorm_bwd_ex(_p(x), _p(w), _p(dy), _p(dx_add), _p(dx), _p(dw), _p(db), M, D, eps, _p(ws),
+                                               ws.numel() if ws is not None else 0, _p(dx_amax), _st()), None, "op_layernorm_bwd_ex")
+    return dx
 
 
 class TemporalEnsemble:

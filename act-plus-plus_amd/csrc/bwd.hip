@@ -705,11 +705,13 @@ int launch_reparam_kl_bwd(const float* latent_info, const float* eps, const floa
 
 int launch_adamw(float* p, const float* g, float* m, float* v, const uint8_t* group, int64_t n, float lr, float lr_bb,
                  float wd, float b1, float b2, float eps, int64_t step, hipStream_t st, const uint32_t* flags, uint32_t skip_mask) {
-    const float bc1 = 1.f - powf(b1, (float)step);
-    const float bc2 = 1.f - powf(b2, (float)step);
+    // bias corrections in double, cast afterwards: 1 - powf(b2, step) in fp32 cancels to ~6e-8 / (step * (1 - b2)) relative, 3e-5 of
+    // bc2 at step 2, which reached the update
+    const float bc1 = (float)(1.0 - pow((double)b1, (double)step));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)step));
     prof_begin("adamw_kernel", 0.0, 28.0 * (double)n, st);
     hipLaunchKernelGGL(adamw_kernel, dim3(256 * 8), dim3(256), 0, st, p, g, m, v, group, n, lr, lr_bb, wd, b1, b2, eps, bc1,
-                       sqrtf(bc2), flags, skip_mask);
+                       bc2_sqrt, flags, skip_mask);
     prof_end(st);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -538,6 +538,106 @@ int actmi_op_adamw(float* p, const float* g, float* m, float* v, int64_t n, floa
     OPCHK(p && g && m && v && n >= 0 && step >= 1, "adamw: bad argument (step counts from 1)");
     OPRC(launch_adamw_flat(p, g, m, v, n, lr, weight_decay, beta1, beta2, eps, step, S(stream)), "adamw launch failed");
 }
+// ---- the non-GEMM kernels of the ACT training step (bwd.hip, pool.hip), one entry per launcher: test surface --------
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline bool fits_i32(int64_t v) { return v >= 0 && v < ((int64_t)1 << 31); }
+
+int actmi_op_maxpool3x3s2_idx(const float* in, float* out, uint8_t* codes, int nimg, int H, int W, int C, void* stream) {
+    OPCHK(in && out && codes && nimg >= 1 && H >= 1 && W >= 1 && C >= 4, "maxpool3x3s2_idx: null pointer or empty shape");
+    OPCHK(al16(in) && al16(out) && ((uintptr_t)codes & 3) == 0, "maxpool3x3s2_idx: in / out must be 16-byte aligned, codes 4-byte aligned");
+    OPRC(launch_maxpool_idx(in, out, codes, nimg, H, W, C, (H - 1) / 2 + 1, (W - 1) / 2 + 1, S(stream)),
+         "maxpool3x3s2_idx: C must be a multiple of 4 and nimg*Ho*Wo*C/4 < 2^31");
+}
+int actmi_op_maxpool3x3s2_bwd(const uint8_t* codes, const float* dy, float* dx, int nimg, int H, int W, int C, const float* relu_x,
+                              const float* bn_scale, int imgs_per_group, uint32_t* amax_out, void* stream) {
+    OPCHK(codes && dy && dx && nimg >= 1 && H >= 1 && W >= 1 && C >= 4, "maxpool3x3s2_bwd: null pointer or empty shape");
+    OPCHK(al16(dy) && al16(dx) && al16(relu_x) && al16(bn_scale) && ((uintptr_t)codes & 3) == 0,
+          "maxpool3x3s2_bwd: dy, dx, relu_x and bn_scale must be 16-byte aligned, codes 4-byte aligned");
+    OPCHK((relu_x != nullptr) == (bn_scale != nullptr), "maxpool3x3s2_bwd: relu_x and bn_scale come together");
+    OPCHK(!relu_x || imgs_per_group >= 1, "maxpool3x3s2_bwd: imgs_per_group must be >= 1");
+    OPCHK(!amax_out || relu_x, "maxpool3x3s2_bwd: amax_out is collected by the fused form only (relu_x, bn_scale)");
+    OPRC(launch_maxpool_bwd_idx(codes, dy, dx, nimg, H, W, C, (H - 1) / 2 + 1, (W - 1) / 2 + 1, S(stream), relu_x, bn_scale,
+                                imgs_per_group, amax_out),
+         "maxpool3x3s2_bwd: C must be a multiple of 4 and nimg*H*W*C/4 < 2^31");
+}
+int actmi_op_relu_bn_bwd(const float* x, const float* add, const float* mask, const float* scale, float* y_plain, float* y_scaled,
+                         int G, int64_t per_group, int C, uint32_t* amax_out, void* stream) {
+    OPCHK(x && (y_plain || y_scaled) && G >= 1 && per_group >= 0 && C >= 1, "relu_bn_bwd: null pointer or bad shape");
+    OPCHK(!y_scaled || scale, "relu_bn_bwd: y_scaled needs scale [G][C]");
+    OPCHK(!amax_out || y_scaled, "relu_bn_bwd: amax_out is the maximum of y_scaled");
+    OPCHK(al16(x) && al16(add) && al16(mask) && al16(scale) && al16(y_plain) && al16(y_scaled), "relu_bn_bwd: pointers must be 16-byte aligned");
+    if ((C & 3) || (per_group & 3) || per_group % C) {
+        g_op_error = "relu_bn_bwd: C and per_group must be multiples of 4, per_group a multiple of C";
+        return ACTMI_E_SHAPE;
+    }
+    OPRC(launch_relu_bn_bwd(x, add, mask, scale, y_plain, y_scaled, G, per_group, C, S(stream), amax_out),
+         "relu_bn_bwd: C and per_group must be multiples of 4, per_group / 4 < 2^32, G <= 65535");
+}
+int actmi_op_act_losses(const float* a_hat, const float* actions, const uint8_t* is_pad, const float* latent_info, float* losses,
+                        int64_t losses_floats, int B, int Q, int A, int L, float kl_weight, void* stream) {
+    OPCHK(a_hat && actions && is_pad && losses && B >= 1 && Q >= 1 && A >= 1, "act_losses: null pointer or empty shape");
+    OPCHK(losses_floats >= 3 + 1 + 512, "act_losses: losses must hold 3 results + 1 + 512 floats of block partials");
+    OPCHK(!latent_info || (L >= 1 && fits_i32((int64_t)B * 2 * L)), "act_losses: latent_info [B][2*L] needs L >= 1");
+    OPRC(launch_losses(a_hat, actions, is_pad, latent_info, losses, B, Q, A, L, kl_weight, S(stream)), "act_losses launch failed");
+}
+int actmi_op_l1_bwd(const float* a_hat, const float* actions, const uint8_t* is_pad, float* d_a_hat, int B, int Q, int A, float gscale,
+                    void* stream) {
+    OPCHK(a_hat && actions && is_pad && d_a_hat && B >= 1 && Q >= 1 && A >= 1, "l1_bwd: null pointer or empty shape");
+    OPRC(launch_l1_bwd(a_hat, actions, is_pad, d_a_hat, B, Q, A, gscale, S(stream)), "l1_bwd launch failed");
+}
+int actmi_op_reparam(const float* latent_info, const float* eps, float* z, float* mu_out, float* logvar_out, int B, int L, void* stream) {
+    OPCHK(latent_info && eps && z && B >= 1 && L >= 1 && fits_i32((int64_t)B * 2 * L), "reparam: null pointer or bad shape");
+    OPRC(launch_reparam(latent_info, eps, z, mu_out, logvar_out, B, L, S(stream)), "reparam launch failed");
+}
+int actmi_op_reparam_kl_bwd(const float* latent_info, const float* eps, const float* dz, float* d_latent_info, int B, int L,
+                            float klw_scaled, void* stream) {
+    OPCHK(latent_info && eps && dz && d_latent_info && B >= 1 && L >= 1 && fits_i32((int64_t)B * 2 * L),
+          "reparam_kl_bwd: null pointer or bad shape");
+    OPRC(launch_reparam_kl_bwd(latent_info, eps, dz, d_latent_info, B, L, klw_scaled, S(stream)), "reparam_kl_bwd launch failed");
+}
+int actmi_op_vq_bwd(const float* probs, const float* g, float* dlogits, int B, int VC, int VD, void* stream) {
+    OPCHK(probs && g && dlogits && B >= 1 && VC >= 1 && VD >= 1 && fits_i32((int64_t)B * VC), "vq_bwd: null pointer or bad shape");
+    OPRC(launch_vq_bwd(probs, g, dlogits, B, VC, VD, S(stream)), "vq_bwd launch failed");
+}
+int actmi_op_dropout_bwd(const float* dy, float* dz, int64_t n, float p, uint64_t seed, void* stream) {
+    OPCHK(dy && dz && n >= 0 && p >= 0.f && p < 1.f, "dropout_bwd: bad argument (0 <= p < 1)");
+    OPRC(launch_dropout_bwd(dy, dz, seed, p, n, S(stream)), "dropout_bwd launch failed");
+}
+int actmi_op_attn_delta(const float* d_o, const float* o, float* delta, int B, int H, int Nq, int HD, void* stream) {
+    OPCHK(d_o && o && delta && B >= 1 && H >= 1 && Nq >= 1 && HD >= 1, "attn_delta: null pointer or empty shape");
+    OPRC(launch_attn_delta(d_o, o, delta, B, H, Nq, HD, S(stream)), "attn_delta launch failed");
+}
+int actmi_op_attn_drop(const float* P, float* Pd, uint64_t seed, float p, int G, int Nq, int Nk, int ldp, void* stream) {
+    OPCHK(P && Pd && G >= 1 && Nq >= 1 && Nk >= 1 && ldp >= Nk && p >= 0.f && p < 1.f,
+          "attn_drop: null pointer, empty shape, ldp < Nk or p outside [0, 1)");
+    OPRC(launch_attn_drop(P, Pd, seed, p, G, Nq, Nk, ldp, S(stream)), "attn_drop launch failed");
+}
+int actmi_op_attn_ds_drop(const float* P, float* dP, const float* delta, float scale, uint64_t seed, float p, int G, int Nq, int Nk,
+                          int ldp, void* stream) {
+    OPCHK(P && dP && delta && G >= 1 && Nq >= 1 && Nk >= 1 && ldp >= Nk && p >= 0.f && p < 1.f,
+          "attn_ds_drop: null pointer, empty shape, ldp < Nk or p outside [0, 1)");
+    OPRC(launch_attn_ds_drop(P, dP, delta, scale, seed, p, G, Nq, Nk, ldp, S(stream)), "attn_ds_drop launch failed");
+}
+int actmi_op_zero_cols(float* x, int64_t rows, int ld, int c0, void* stream) {
+    OPCHK(x && rows >= 0 && ld >= 1 && c0 >= 0 && c0 <= ld, "zero_cols: needs 0 <= c0 <= ld");
+    OPRC(launch_zero_cols(x, rows, ld, c0, S(stream)), "zero_cols launch failed");
+}
+int actmi_op_adamw_groups(float* p, const float* g, float* m, float* v, const uint8_t* group, int64_t n, float lr, float lr_backbone,
+                          float weight_decay, float beta1, float beta2, float eps, int64_t step, const uint32_t* flags,
+                          uint32_t skip_mask, void* stream) {
+    OPCHK(p && g && m && v && group && n >= 0 && step >= 1, "adamw_groups: bad argument (step counts from 1)");
+    OPCHK(((uintptr_t)flags & 3) == 0, "adamw_groups: flags must be 4-byte aligned");
+    if (n == 0) return ACTMI_OK;
+    OPRC(launch_adamw(p, g, m, v, group, n, lr, lr_backbone, weight_decay, beta1, beta2, eps, step, S(stream), flags, skip_mask),
+         "adamw_groups launch failed");
+}
+int actmi_op_layernorm_bwd_ex(const float* x, const float* w, const float* dy, const float* dx_add, float* dx, float* dw, float* db,
+                              int M, int D, float eps, float* ws, int64_t ws_floats, uint32_t* dx_amax, void* stream) {
+    OPCHK(x && w && dy && dx && dw && db && M >= 0 && ws_floats >= 0, "layernorm_bwd_ex: null pointer");
+    OPCHK(al16(x) && al16(w) && al16(dy) && al16(dx_add) && al16(dx), "layernorm_bwd_ex: x, w, dy, dx_add and dx must be 16-byte aligned");
+    OPRC(launch_ln_bwd(x, w, dy, dx_add, dx, dw, db, M, D, eps, S(stream), ws, ws_floats, dx_amax),
+         "layernorm_bwd_ex: D must be a multiple of 4 and <= 2048");
+}
 #undef OPCHK
 #undef OPRC
 

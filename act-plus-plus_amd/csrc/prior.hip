@@ -273,9 +273,11 @@ int launch_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, f
                       int64_t step, hipStream_t st) {
     if (n <= 0) return 0;
     if (step < 1) return -2;
-    const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
+    // in double, cast afterwards (launch_adamw: the fp32 difference cancels at small step counts)
+    const float bc1 = (float)(1.0 - pow((double)b1, (double)step));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)step));
     int blocks = (int)((n + 255) / 256);
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adamw_flat_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, wd, b1, b2, eps, bc1, sqrtf(bc2));
+    hipLaunchKernelGGL(adamw_flat_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, wd, b1, b2, eps, bc1, bc2_sqrt);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -459,6 +459,56 @@ int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float
 /* torch.optim.AdamW update of one flat fp32 tensor (decoupled decay, bias correction with `step` counted from 1) */
 int actmi_op_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float weight_decay, float beta1, float beta2,
                    float eps, int64_t step, void* stream);
+/* ---- the non-GEMM kernels of the ACT training step, one entry per launcher (kernel-level parity tests; the engine calls the
+ * launchers directly).  Device pointers; float maps 16-byte aligned; every entry validates its arguments (actmi_op_last_error). */
+/* 3x3 / s2 / p1 max pool of the training forward: out [nimg][Ho][Wo][C] and, per output element, the code r*3+s of the window
+ * position that held the maximum (the first one in scan order: ATen's tie rule), Ho = (H-1)/2+1, Wo = (W-1)/2+1; C % 4 == 0 */
+int actmi_op_maxpool3x3s2_idx(const float* in_nhwc, float* out_nhwc, uint8_t* codes, int nimg, int H, int W, int C, void* stream);
+/* its backward on the recorded codes: dx [nimg][H][W][C] = the sum of dy over the (at most four) windows whose code names the
+ * element, windows visited ho outer, wo inner.  relu_x [nimg][H][W][C] + bn_scale [ceil(nimg / imgs_per_group)][C] (both or
+ * neither): dx = relu_x > 0 ? dx * bn_scale[img / imgs_per_group][c] : 0 (the stem's ReLU + FrozenBN backward), and amax_out
+ * (optional, that form only) is raised to the bits of the largest |dx| written */
+int actmi_op_maxpool3x3s2_bwd(const uint8_t* codes, const float* dy, float* dx, int nimg, int H, int W, int C, const float* relu_x,
+                              const float* bn_scale, int imgs_per_group, uint32_t* amax_out, void* stream);
+/* ReLU + FrozenBN backward on G NHWC maps of per_group floats each (per_group % C == 0, C % 4 == 0): v = x (+ add), zeroed where
+ * mask <= 0 (mask optional); y_plain = v, y_scaled = v * scale[g][c] (either may be NULL, not both; y_scaled needs scale);
+ * amax_out (optional): raised to the bits of max |y_scaled| */
+int actmi_op_relu_bn_bwd(const float* x, const float* add, const float* mask, const float* scale, float* y_plain, float* y_scaled,
+                         int G, int64_t per_group, int C, uint32_t* amax_out, void* stream);
+/* ACTPolicy's training losses (policy.py:310-320): losses[0] = mean over ALL B*Q*A elements of |actions - a_hat| * !is_pad[b][q],
+ * losses[1] = kl of latent_info [B][mu(L) | logvar(L)] (0 when latent_info is NULL), losses[2] = l1 + kl_weight * kl.
+ * losses: 3 results followed by 1 + 512 floats of block partials (losses_floats >= 516); fixed-order sums, bitwise repeatable */
+int actmi_op_act_losses(const float* a_hat, const float* actions, const uint8_t* is_pad, const float* latent_info, float* losses,
+                        int64_t losses_floats, int B, int Q, int A, int L, float kl_weight, void* stream);
+/* d_a_hat = sign(a_hat - actions) * !is_pad * gscale / (B*Q*A) */
+int actmi_op_l1_bwd(const float* a_hat, const float* actions, const uint8_t* is_pad, float* d_a_hat, int B, int Q, int A, float gscale,
+                    void* stream);
+/* z = mu + exp(logvar / 2) * eps from latent_info [B][mu(L) | logvar(L)] (detr_vae.py:19-22); mu_out / logvar_out optional copies */
+int actmi_op_reparam(const float* latent_info, const float* eps, float* z, float* mu_out, float* logvar_out, int B, int L, void* stream);
+/* gradient of sum(z * dz) + klw_scaled * kl with respect to latent_info */
+int actmi_op_reparam_kl_bwd(const float* latent_info, const float* eps, const float* dz, float* d_latent_info, int B, int L,
+                            float klw_scaled, void* stream);
+/* softmax backward per (sample, class) of the VQ latent: dlogits = probs * (g - sum(probs * g)) over vq_dim; [B][VC][VD] */
+int actmi_op_vq_bwd(const float* probs, const float* g, float* dlogits, int B, int VC, int VD, void* stream);
+/* backward of an epilogue dropout: dz[i] = keep(seed, i) ? dy[i] / (1 - p) : 0 */
+int actmi_op_dropout_bwd(const float* dy, float* dz, int64_t n, float p, uint64_t seed, void* stream);
+/* pieces of the attention backward through materialised probabilities (train.hip: attn_bwd).  delta [B][H][Nq] = sum_d d_o * o over
+ * each head's HD columns of [B][Nq][H*HD]; attn_drop: Pd = P * keep / (1-p) on [G][Nq][ldp] buffers (columns >= Nk zero), keep
+ * indexed ((g*Nq + q)*Nk + key) as in the forward; attn_ds_drop: dP <- P * (dP * keep / (1-p) - delta[g][q]) * scale in place
+ * (columns >= Nk zero); zero_cols: x[r][c0 .. ld) = 0 for `rows` rows */
+int actmi_op_attn_delta(const float* d_o, const float* o, float* delta, int B, int H, int Nq, int HD, void* stream);
+int actmi_op_attn_drop(const float* P, float* Pd, uint64_t seed, float p, int G, int Nq, int Nk, int ldp, void* stream);
+int actmi_op_attn_ds_drop(const float* P, float* dP, const float* delta, float scale, uint64_t seed, float p, int G, int Nq, int Nk,
+                          int ldp, void* stream);
+int actmi_op_zero_cols(float* x, int64_t rows, int ld, int c0, void* stream);
+/* the engine's AdamW over a parameter arena: group holds one byte per 64-float slot (ceil(n / 64) bytes; 0 = untouched, 1 = lr,
+ * 2 = lr_backbone); flags / skip_mask (optional): while *flags & skip_mask is non-zero the whole update is skipped on the device */
+int actmi_op_adamw_groups(float* p, const float* g, float* m, float* v, const uint8_t* group, int64_t n, float lr, float lr_backbone,
+                          float weight_decay, float beta1, float beta2, float eps, int64_t step, const uint32_t* flags,
+                          uint32_t skip_mask, void* stream);
+/* actmi_op_layernorm_bwd with the operand-scale word of the training path: dx_amax (optional) is raised to the bits of max |dx| */
+int actmi_op_layernorm_bwd_ex(const float* x, const float* w, const float* dy, const float* dx_add, float* dx, float* dw, float* db,
+                              int M, int D, float eps, float* ws, int64_t ws_floats, uint32_t* dx_amax, void* stream);
 const char* actmi_op_last_error(void);
 
 /* intermediate activations of the last forward (parity tests): name in {"conv1","maxpool","layer1".."layer4",

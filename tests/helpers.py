@@ -46,6 +46,37 @@ def rel_err(got, exp):
     return float((got - exp).abs().max() / (exp.abs().max() + 1e-30))
 
 
+def host_mix32(x):
+    """actmi_mix32 of csrc/dropout.h on a uint32 array (wrap-around arithmetic)"""
+    x = np.asarray(x, dtype=np.uint32).copy()
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7feb352d)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846ca68b)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def host_u01(seed, idx):
+    """actmi_u01(seed, idx) for an array of element indices: float32 in [0, 1) with 24 bits"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    idx = np.asarray(idx, dtype=np.uint64)
+    lo = (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    hi = (idx >> np.uint64(32)).astype(np.uint32)
+    h = host_mix32(lo ^ np.uint32(seed & 0xFFFFFFFF))
+    h = host_mix32(h ^ hi ^ np.uint32(seed >> 32) ^ np.uint32(0x9E3779B9))
+    return (h >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+def host_keep(seed, idx, p):
+    """Host transcription of actmi_keep(seed, idx, p) (csrc/dropout.h): a bool array, True = the element is kept.
+
+    Pinned against the device through actmi_op_dropout for element indices 0 .. 100002 only: that op takes no index base, so the
+    comparison covers the low word of the index alone.  The `hi` word path of actmi_u01 (indices at or above 2^32) is transcribed
+    here but NOT proven against the device; every test that uses this mask stays below 2^32."""
+    return host_u01(seed, idx) >= np.float32(p)
+
+
 def gemm_desc(**kw):
     """an actmi_gemm_desc from keyword fields; tensors become their device addresses (the caller keeps them alive)"""
     from actmi import lib as L
