@@ -51,6 +51,14 @@ class ACTConfig:
     use_pcd: bool = False
     pcd_hidden_dim: int = 512
     pcd_output_dim: int = 512
+    # depth cameras (reference backbone.py:115-134, detr_vae.py:188-202): one 1-channel ResNet18 per depth camera, their tokens
+    # appended after the RGB tokens.  The reference's camera loop indexes them by the RGB camera: one per RGB camera
+    use_depth: bool = False
+    depth_camera_names: Optional[List[str]] = None
+
+    @property
+    def num_depth_cams(self) -> int:
+        return len(self.depth_camera_names) if self.use_depth and self.depth_camera_names else 0
 
     @property
     def num_extra_tokens(self) -> int:
@@ -90,7 +98,7 @@ class ACTConfig:
     @property
     def num_tokens(self) -> int:
         fh, fw = self.feat_hw
-        return self.num_extra_tokens + self.num_cams * fh * fw
+        return self.num_extra_tokens + (self.num_cams + self.num_depth_cams) * fh * fw
 
     def validate(self):
         if self.backbone != "resnet18":
@@ -105,6 +113,14 @@ class ACTConfig:
         if self.use_pcd and (self.pcd_hidden_dim % 32 or self.pcd_output_dim % 32 or self.hidden_dim % 32
                              or self.pcd_hidden_dim <= 0 or self.pcd_output_dim <= 0):
             raise ValueError("use_pcd needs pcd_hidden_dim, pcd_output_dim and hidden_dim to be multiples of 32")
+        if self.use_depth:
+            if not self.depth_camera_names:
+                raise NotImplementedError("use_depth needs depth_camera_names (one depth camera per RGB camera)")
+            if len(self.depth_camera_names) != len(self.camera_names):
+                raise NotImplementedError("use_depth needs one depth camera per RGB camera: the reference indexes its depth "
+                                          "backbones by the RGB camera (detr_vae.py:188-202)")
+            if self.use_pcd:
+                raise NotImplementedError("use_depth together with use_pcd is not supported")
         if self.pre_norm:
             raise NotImplementedError("pre_norm is never enabled by the reference CLI")
         if self.hidden_dim % self.nheads:
@@ -121,6 +137,8 @@ class ACTConfig:
         kw = {k: v for k, v in d.items() if k in known}
         if "camera_names" in kw:
             kw["camera_names"] = list(kw["camera_names"])
+        if kw.get("depth_camera_names") is not None:
+            kw["depth_camera_names"] = list(kw["depth_camera_names"])
         return ACTConfig(**kw).validate()
 
 

@@ -54,6 +54,9 @@ class ACTEngine:
                 pc = L.ActmiPcdConfig(struct_size=C.sizeof(L.ActmiPcdConfig), max_points=self.max_points,
                                       hidden_dim=cfg.pcd_hidden_dim, output_dim=cfg.pcd_output_dim)
                 rc = self.lib.actmi_create_ex(C.byref(c), C.byref(pc), C.byref(h))
+            elif cfg.num_depth_cams:
+                dc = L.ActmiDepthConfig(struct_size=C.sizeof(L.ActmiDepthConfig), num_depth_cams=cfg.num_depth_cams)
+                rc = self.lib.actmi_create_ex2(C.byref(c), None, C.byref(dc), C.byref(h))
             else:
                 rc = self.lib.actmi_create(C.byref(c), C.byref(h))
         if rc != 0:
@@ -188,8 +191,38 @@ class ACTEngine:
                 "set_pointcloud")
         return xyz, rgb
 
+    def _depth_shape(self, B: int):
+        cfg = self.cfg
+        return (B, cfg.num_depth_cams, 1, cfg.image_h, cfg.image_w)
+
+    def _bind_depth(self, depth_img, B: int):
+        """Check the depth batch of a use_depth engine (float32 [B, Cd, 1, image_h, image_w], contiguous, on the engine's device,
+        un-normalised: the stem applies (d - 0.5) / 0.5) and bind it for the next forward (actmi_set_depth).  Returns the tensor
+        the library will read."""
+        if not self.cfg.num_depth_cams:
+            if depth_img is not None:
+                raise ValueError("depth_img given to an engine whose config has use_depth=False")
+            return None
+        want = self._depth_shape(B)
+        if depth_img is None:
+            raise ValueError(f"a use_depth engine needs depth_img float32 {list(want)} = [B, Cd, 1, H, W]")
+        if not isinstance(depth_img, torch.Tensor) or not depth_img.is_cuda:
+            raise ValueError("depth_img must be a CUDA tensor on the engine's device")
+        self._check_dev(depth_img=depth_img)
+        if depth_img.dtype != torch.float32:
+            raise TypeError(f"depth_img dtype {depth_img.dtype} not supported (float32)")
+        if depth_img.dim() == 4:
+            raise ValueError(f"depth_img is 4-D {tuple(depth_img.shape)}: the depth batch is 5-D [B, Cd, 1, H, W] = {list(want)} "
+                             "(one channel axis per depth camera, as the reference's depth dataset produces it)")
+        if tuple(depth_img.shape) != want:
+            raise ValueError(f"depth_img shape {tuple(depth_img.shape)} != {want} = [B, Cd, 1, H, W]")
+        if not depth_img.is_contiguous():
+            raise ValueError("depth_img must be contiguous")
+        L.check(self.lib.actmi_set_depth(self.h, C.c_void_p(depth_img.data_ptr()), B), self.h, "set_depth")
+        return depth_img
+
     def forward_infer(self, qpos: torch.Tensor, image: torch.Tensor, out: torch.Tensor = None,
-                      vq_sample: torch.Tensor = None, pointcloud=None) -> torch.Tensor:
+                      vq_sample: torch.Tensor = None, pointcloud=None, depth_img=None) -> torch.Tensor:
         if not self._finalized:
             self.finalize()
         cfg = self.cfg
@@ -207,6 +240,7 @@ class ACTEngine:
             raise ValueError(f"qpos shape {tuple(qpos.shape)} != {(B, cfg.state_dim)}")
         if out is None:
             out = torch.empty((B, cfg.num_queries, cfg.action_dim), dtype=torch.float32, device=qpos.device)
+        depth = self._bind_depth(depth_img, B)                # (after every other check: a binding is consumed by the forward)
         if cfg.vq:
             # VQ-ACT: the latent code comes from the caller (the latent prior model's sample, imitate_episodes.py:393-394)
             if vq_sample is None:
@@ -247,6 +281,9 @@ class ACTEngine:
             s_qpos = torch.zeros((batch, cfg.state_dim), dtype=torch.float32, device=dev)
             s_img = torch.zeros(shape, dtype=image_dtype, device=dev)
             s_out = torch.empty((batch, cfg.num_queries, cfg.action_dim), dtype=torch.float32, device=dev)
+        s_depth = None
+        if cfg.num_depth_cams:
+            s_depth = torch.zeros(self._depth_shape(batch), dtype=torch.float32, device=dev)
         s_cloud = None
         if cfg.use_pcd:
             npts = self.max_points if num_points is None else int(num_points)
@@ -256,7 +293,7 @@ class ACTEngine:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(2):
-                self.forward_infer(s_qpos, s_img, out=s_out, pointcloud=s_cloud)
+                self.forward_infer(s_qpos, s_img, out=s_out, pointcloud=s_cloud, depth_img=s_depth)
                 if with_ensemble is not None:
                     with_ensemble.step(s_out)
         torch.cuda.current_stream(dev).wait_stream(side)
@@ -269,7 +306,7 @@ class ACTEngine:
         try:
             # thread_local: calls made by other threads (e.g. the RCCL watchdog of a multi-rank bench) must not void the capture
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                self.forward_infer(s_qpos, s_img, out=s_out, pointcloud=s_cloud)
+                self.forward_infer(s_qpos, s_img, out=s_out, pointcloud=s_cloud, depth_img=s_depth)
                 if with_ensemble is not None and phase != 1:
                     ens_out = with_ensemble.step(s_out)
         finally:
@@ -277,12 +314,21 @@ class ACTEngine:
         if with_ensemble is not None:
             with_ensemble.reset()               # the capture itself does not execute, but keep the state explicit
 
-        def replay(qpos, image, pointcloud=None):
+        def replay(qpos, image, pointcloud=None, depth_img=None):
             # a caller that owns the step's inputs writes them straight into replay.static (H2D copies land there): no copy
             if qpos.data_ptr() != s_qpos.data_ptr():
                 s_qpos.copy_(qpos, non_blocking=True)
             if image.data_ptr() != s_img.data_ptr():
                 s_img.copy_(image, non_blocking=True)
+            if s_depth is not None:
+                if depth_img is None:
+                    raise ValueError("a use_depth engine needs depth_img [B, Cd, 1, H, W]")
+                if tuple(depth_img.shape) != tuple(s_depth.shape):
+                    raise ValueError(f"depth_img shape {tuple(depth_img.shape)} != the captured {tuple(s_depth.shape)}")
+                if depth_img.data_ptr() != s_depth.data_ptr():
+                    s_depth.copy_(depth_img, non_blocking=True)
+            elif depth_img is not None:
+                raise ValueError("depth_img given to an engine whose config has use_depth=False")
             if s_cloud is not None:
                 if pointcloud is None:
                     raise ValueError("a use_pcd engine needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]}")
@@ -298,11 +344,12 @@ class ACTEngine:
         replay.graph = graph
         replay.static = (s_qpos, s_img, s_out)
         replay.static_cloud = s_cloud
+        replay.static_depth = s_depth
         return replay
 
     # ---- training -----------------------------------------------------------------------------
     def forward_train(self, qpos, image, actions, is_pad, eps=None, dropout_p: float = 0.0, dropout_seed: int = 0,
-                      vq_code=None, pointcloud=None):
+                      vq_code=None, pointcloud=None, depth_img=None):
         """ACTPolicy.__call__ training branch (policy.py:288-320). Returns dict(l1, kl, loss, a_hat, mu, logvar) of
         device tensors.  ``eps`` replaces the normal_() draw of reparametrize (detr_vae.py:19-22).
         VQ-ACT (cfg.vq): ``vq_code`` [B, vq_class, vq_dim] replaces the multinomial draw of detr_vae.py:140 (None: drawn
@@ -341,7 +388,8 @@ class ACTEngine:
         mu = torch.empty((B, Lz), dtype=torch.float32, device=dev)
         logvar = torch.empty((B, Lz), dtype=torch.float32, device=dev)
         cloud = self._bind_pointcloud(pointcloud, B)
-        self._keep = (qpos, image, actions, is_pad_u8, eps, cloud)        # the library reads qpos and the clouds again in backward
+        depth = self._bind_depth(depth_img, B)
+        self._keep = (qpos, image, actions, is_pad_u8, eps, cloud, depth)        # the library reads qpos and the clouds again in backward
         L.check(self.lib.actmi_forward_train(
             self.h, C.c_void_p(qpos.data_ptr()), C.c_void_p(image.data_ptr()), fmt, C.c_void_p(actions.data_ptr()),
             C.c_void_p(is_pad_u8.data_ptr()), C.c_void_p(eps.data_ptr() if eps is not None else 0), C.c_uint64(dropout_seed),
@@ -611,6 +659,8 @@ class InferPipeline:
     def __init__(self, engine: "ACTEngine", batch: int, with_ensemble=None, image_dtype=torch.uint8, copy_stream_candidates: int = 8):
         if engine.cfg.use_pcd:
             raise NotImplementedError("InferPipeline has no host feed for point clouds yet (use capture_infer)")
+        if engine.cfg.num_depth_cams:
+            raise NotImplementedError("InferPipeline has no host feed for depth frames yet (use capture_infer)")
         self.engine, self.dev = engine, engine.device
         cfg, dev = engine.cfg, engine.device
         shape = (batch, cfg.num_cams, cfg.image_h, cfg.image_w, 3) if image_dtype == torch.uint8 else \

@@ -30,6 +30,11 @@ class ActmiPcdConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_points", C.c_int32), ("hidden_dim", C.c_int32), ("output_dim", C.c_int32)]
 
 
+class ActmiDepthConfig(C.Structure):
+    # the depth cameras of a handle (actmi_create_ex2); struct_size guards it like ActmiConfig's
+    _fields_ = [("struct_size", C.c_uint32), ("num_depth_cams", C.c_int32)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("lda", C.c_int64), ("mode", C.c_int32),
@@ -100,6 +105,8 @@ def load():
         "actmi_create": ([C.POINTER(ActmiConfig), C.POINTER(vp)], i32),
         "actmi_create_ex": ([C.POINTER(ActmiConfig), C.POINTER(ActmiPcdConfig), C.POINTER(vp)], i32),
         "actmi_set_pointcloud": ([vp, vp, vp, i32, i32], i32),
+        "actmi_create_ex2": ([C.POINTER(ActmiConfig), C.POINTER(ActmiPcdConfig), C.POINTER(ActmiDepthConfig), C.POINTER(vp)], i32),
+        "actmi_set_depth": ([vp, vp, i32], i32),
         "actmi_destroy": ([vp], i32),
         "actmi_last_error": ([vp], C.c_char_p),
         "actmi_num_params": ([vp], i32),
@@ -134,6 +141,7 @@ def load():
         "actmi_op_layernorm": ([vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp], i32),
         "actmi_op_maxpool3x3s2": ([vp, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_conv1": ([vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
+        "actmi_op_conv1_depth": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
         "actmi_op_conv1_workspace_floats": ([i32, i32], C.c_int64),
         "actmi_op_conv1_prepare": ([vp, vp, i32, i32, i32, vp], i32),
         "actmi_op_conv1_prepared": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),

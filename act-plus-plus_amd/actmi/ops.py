@@ -386,6 +386,23 @@ def conv1(image, w_oihw, scale, bias, prec=None):
     return out
 
 
+def conv1_depth(depth, w_oihw, scale, bias, out=None, out_cam0=0):
+    """depth stem: depth f32 [B, Cd, 1, H, W] un-normalised; w [Cd, Cout, 1, 7, 7]; scale / bias [Cd, Cout].  Returns the
+    camera-major map [Cd, B, Ho, Wo, Cout], or writes cameras out_cam0 .. out_cam0 + Cd - 1 of a given `out` [Ct, B, Ho, Wo, Cout]."""
+    lib = L.load()
+    depth, w_oihw, scale, bias = depth.contiguous(), w_oihw.contiguous(), scale.contiguous(), bias.contiguous()
+    B, Cd, one, H, W = depth.shape
+    Cout = w_oihw.shape[1]
+    assert one == 1 and tuple(w_oihw.shape) == (Cd, Cout, 1, 7, 7) and tuple(scale.shape) == (Cd, Cout) == tuple(bias.shape)
+    Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    if out is None:
+        out = torch.empty((Cd, B, Ho, Wo, Cout), dtype=torch.float32, device=depth.device)
+    assert out.is_contiguous() and tuple(out.shape[1:]) == (B, Ho, Wo, Cout) and 0 <= out_cam0 and out_cam0 + Cd <= out.shape[0]
+    L.check(lib.actmi_op_conv1_depth(_p(depth), _p(w_oihw), _p(scale), _p(bias), _p(out), B, Cd, H, W, Cout, int(out_cam0),
+                                     L.current_stream_ptr()), None, "op_conv1_depth")
+    return out
+
+
 # ---- DiffusionPolicy path (reference policy.py:20-241): the non-GEMM ops, channel-last ---------------------------------
 ACT = {None: 0, "none": 0, "relu": 1, "mish": 2}
 

@@ -107,10 +107,12 @@ def resnet18_layout(base_width=64):
     return convs
 
 
-def _backbone(prefix, base_width, out):
+def _backbone(prefix, base_width, out, in_channels=3):
     for name, cin, cout, k, _, _ in resnet18_layout(base_width):
         if name.endswith("downsample.0"):
             continue  # emitted after bn2 of the block, below
+        if name == "conv1":
+            cin = in_channels
         out[prefix + name + ".weight"] = (cout, cin, k, k)
         bn = name.replace("conv", "bn") if name != "conv1" else "bn1"
         _fbn(prefix + bn + ".", cout, out)
@@ -144,6 +146,10 @@ def act_state_dict_spec(cfg: ACTConfig, prefix: str = "") -> "OrderedDict[str, t
     for c in range(cfg.num_cams):
         _backbone(f"backbones.{c}.0.body.", cfg.base_width, o)
     o["input_proj_robot_state.weight"] = (D, S); o["input_proj_robot_state.bias"] = (D,)
+    if cfg.num_depth_cams:                                          # detr_vae.py:359-361, backbone.py:115-134
+        o["input_proj_depth.weight"] = (D, C4, 1, 1); o["input_proj_depth.bias"] = (D,)
+        for c in range(cfg.num_depth_cams):
+            _backbone(f"depth_backbones.{c}.0.body.", cfg.base_width, o, in_channels=1)
     if cfg.use_pcd:                                                 # detr_vae.py:64-65
         o["input_proj_pointnet.weight"] = (D, cfg.pcd_output_dim); o["input_proj_pointnet.bias"] = (D,)
     o["cls_embed.weight"] = (1, D)
@@ -159,6 +165,8 @@ def act_state_dict_spec(cfg: ACTConfig, prefix: str = "") -> "OrderedDict[str, t
             o[f"pcl_backbone.pointnet._mlp.{i}.weight"] = (n_out, n_in)
             o[f"pcl_backbone.pointnet._mlp.{i}.bias"] = (n_out,)
     o["additional_pos_embed.weight"] = (cfg.num_extra_tokens, D)     # detr_vae.py:100-102
+    if cfg.num_depth_cams:
+        o["depth_pos_embed.weight"] = (1, D)                         # registered by the reference, read by nothing
     if prefix:
         o = OrderedDict((prefix + k, v) for k, v in o.items())
     return o
@@ -258,6 +266,10 @@ def generate_inputs(cfg: ACTConfig, batch: int, seed: int = 1234, with_actions: 
                 is_pad[b, Q - npad[b]:] = True
         out["is_pad"] = is_pad
         out["eps"] = normal(seed, "eps", batch * cfg.latent_dim).astype(np.float32).reshape(batch, cfg.latent_dim)
+    if cfg.num_depth_cams:
+        # depth frames [B, Cd, 1, H, W] in [0, 1), the range utils_arm_gripper_all.py:189 normalises to
+        shape = (batch, cfg.num_depth_cams, 1, cfg.image_h, cfg.image_w)
+        out["depth"] = uniform01(seed, "depth", int(np.prod(shape))).astype(np.float32).reshape(shape)
     return out
 
 

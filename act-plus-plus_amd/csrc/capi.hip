@@ -31,11 +31,25 @@ int actmi_create(const actmi_config* cfg, actmi_handle* out) {
 }
 
 int actmi_create_ex(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_handle* out) {
+    return actmi_create_ex2(cfg, pcd, nullptr, out);
+}
+
+int actmi_create_ex2(const actmi_config* cfg, const actmi_pcd_config* pcd, const actmi_depth_config* depth, actmi_handle* out) {
     try {
-        return engine_create(cfg, pcd, out);
+        return engine_create(cfg, pcd, depth, out);
     } catch (const std::exception& e) {
         return ACTMI_E_NOMEM;
     }
+}
+
+int actmi_set_depth(actmi_handle h, const float* depth, int B) {
+    if (!h) return ACTMI_E_INVALID;
+    ENTER(h);
+    if (!h->Cd) return bad(h, "handle was created without a depth config (actmi_create_ex2)", ACTMI_E_STATE);
+    if (!depth) return bad(h, "null pointer");
+    if (B < 1 || B > h->cfg.max_batch) return bad(h, "batch exceeds max_batch");
+    h->depth_img = depth; h->depth_B = B;
+    return ACTMI_OK;
 }
 
 int actmi_set_pointcloud(actmi_handle h, const float* xyz, const float* rgb, int B, int P) {
@@ -337,6 +351,15 @@ int actmi_op_conv1(const void* image, int image_fmt, const float* w_oihw, const 
 
 // workspace layout of the prepared stem: [C*Cout*148 repacked weights][768 lut][C*Cout ones][C*Cout zeros][C * wimg bytes]
 static int64_t conv1_ws_off_lut(int C, int Cout) { return (int64_t)C * Cout * 148; }
+int actmi_op_conv1_depth(const float* depth, const float* w_oihw, const float* scale, const float* bias, float* out, int B,
+                         int Cd, int H, int W, int Cout, int out_cam0, void* stream) {
+    g_op_error.clear();
+    Conv1DepthArgs a;
+    a.depth = depth; a.w = w_oihw; a.w_cam_stride = (int64_t)Cout * 49; a.scale = scale; a.bias = bias; a.out = out;
+    a.B = B; a.Cd = Cd; a.H = H; a.W = W; a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1; a.Cout = Cout; a.out_cam0 = out_cam0;
+    const int rc = launch_conv1_depth(a, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
 int64_t actmi_op_conv1_workspace_floats(int C, int Cout) {
     return conv1_ws_off_lut(C, Cout) + 768 + 2 * (int64_t)C * Cout + (int64_t)C * ((conv1_wimg_bytes() + 3) / 4) + 16;
 }

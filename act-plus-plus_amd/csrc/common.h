@@ -73,6 +73,21 @@ int64_t conv1_wimg_bytes();
 int launch_conv1_wimg(const float* w, void* img, int C, int Cout, hipStream_t st, float wscale = 256.f);
 int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err);
 
+// ---- depth stem: conv1 7x7/s2, 1 -> Cout channels + FrozenBN + ReLU, fp32 products (conv1_depth.hip) ----
+struct Conv1DepthArgs {
+    const float* depth;   // f32 [B][Cd][1][H][W], raw (the loader applies (d - 0.5) / 0.5)
+    const float* w;       // camera 0's [Cout][49] weights (the OIHW parameter itself)
+    int64_t w_cam_stride; // floats between the weights of consecutive cameras
+    const float* scale;   // [Cd][Cout]
+    const float* bias;    // [Cd][Cout]
+    float* out;           // camera-major NHWC [..][B][Ho][Wo][Cout]; depth camera k writes camera out_cam0 + k
+    int B, Cd, H, W, Ho, Wo, Cout;
+    int out_cam0;
+};
+int launch_conv1_depth(const Conv1DepthArgs& a, hipStream_t st, std::string* err);
+// normalised depth -> channel 0 of a camera-major NHWC4 image [Cd][B][H][W][4] (zeros elsewhere), for the stem's weight gradient
+int launch_depth_nhwc4(const float* depth, float* out, int B, int Cd, int H, int W, hipStream_t st);
+
 // ---- direct 3x3 / stride 1 / pad 1 convolution, 64 -> 64 channels, f16x3 (conv3.hip) ----------
 struct Conv3Args {
     const float* x;       // camera-major NHWC [G][B][H][W][64]

@@ -127,6 +127,12 @@ struct actmi_ctx {
     int* pcd_arg = nullptr;                                // [max_batch][O] winning point of every column
     float* pcd_ws = nullptr;                               // candidates of the split column maximum
     int64_t pcd_ws_floats = 0;
+    // depth cameras (actmi_create_ex2): cameras C .. Ct-1 of the trunk, Ct = C + Cd; their stem is conv1_depth.hip and their
+    // layer4 maps go through input_proj_depth into the token rows behind the RGB tokens (detr_vae.py:188-202, transformer.py:64-86)
+    int Cd = 0, Ct = 0;
+    const float* depth_img = nullptr;                      // batch bound for the next forward (actmi_set_depth), then cleared
+    int depth_B = 0;
+    float ip_d_a_scale = 1.f;                              // activation pre-scale of input_proj_depth's operand (ip_a_scale's twin)
     int device = 0;                    // HIP device the handle was created on (all its memory lives there)
     std::string err;
     std::vector<Param> params;
@@ -233,7 +239,13 @@ int dev_alloc(actmi_ctx* ctx, T** p, int64_t count) {
 // precision of the GEMMs issued right now: the training override (PrecScope) while a training call runs, else the handle's
 inline int engine_prec(const actmi_ctx* ctx) { return ctx->prec_override ? ctx->prec_override : ctx->gemm_prec; }
 
-int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_ctx** out);
+int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, const actmi_depth_config* depth, actmi_ctx** out);
+// the depth batch of this forward: checks the binding of a depth handle against B (ACTMI_E_STATE with a message) and consumes it
+int engine_take_depth(actmi_ctx* ctx, int B, const float** depth);
+// state_dict prefix of trunk camera cam: "backbones.k.0.body." for cam < C, "depth_backbones.(cam - C).0.body." behind them
+std::string trunk_cam_prefix(const actmi_ctx* ctx, int cam);
+// the depth stem of B samples into cameras C.. of ctx->act1
+int engine_depth_stem(actmi_ctx* ctx, const float* depth, int B, hipStream_t st);
 // the clouds of this forward: checks the binding of a point-cloud handle against B (ACTMI_E_STATE with a message) and consumes it
 int engine_take_pointcloud(actmi_ctx* ctx, int B, const float** xyz, const float** rgb, int* P);
 // PointNet + input_proj_pointnet of B clouds of P points -> token row 2 of ctx->X, features / winners in ctx->pcd_feat / pcd_arg
@@ -277,8 +289,10 @@ AttnArgs cross_attn_args(const actmi_ctx* ctx, const float* q, bool per_sample_q
 // u8 -> float table [3][256] of the stem: x = float(v / 255.0 in f64) (imitate_episodes.py:212), then (x - mean) / std in f32
 // (policy.py:268-272) when normalize, else x alone
 void u8_lut(float* lut, bool normalize);
-// arena distance between same-named parameters of consecutive backbones (one launch per layer covers all cameras)
+// arena distance between same-named parameters of consecutive backbones (one launch per layer covers all cameras), and the
+// same for the depth backbones (uniform inside each of the two ranges)
 int64_t backbone_cam_stride(actmi_ctx* ctx);
+int64_t depth_cam_stride(actmi_ctx* ctx);
 // precision of the GEMMs issued while a training call is running (restored on every exit path)
 struct PrecScope {
     actmi_ctx* c;
@@ -292,7 +306,9 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step = fal
 int engine_calibrate_weight_scales(actmi_ctx* ctx, hipStream_t st);
 int engine_calibrate_activations(actmi_ctx* ctx, hipStream_t st);
 int engine_measure_act_scale(actmi_ctx* ctx, const float* x, int64_t rows, int cols, hipStream_t st, float* out);
-int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream_t st);
+// token row of every feature row of the trunk's layer4 maps for batch B (ctx->rowmap; rebuilt when B changes)
+int engine_build_rowmap(actmi_ctx* ctx, int B, hipStream_t st);
+int engine_backbone(actmi_ctx* ctx, const void* image, const float* depth, int fmt, int B, hipStream_t st);
 float engine_weight_scale(const actmi_ctx* ctx, const float* w);
 int train_create(actmi_ctx* ctx);
 int train_fit_prec(actmi_ctx* ctx);

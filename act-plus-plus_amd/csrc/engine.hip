@@ -84,9 +84,8 @@ void build_spec(actmi_ctx* c) {
     add_param(c, "query_embed.weight", {Q, D}, false);
     add_param(c, "input_proj.weight", {D, 8 * w0, 1, 1}, false);
     add_param(c, "input_proj.bias", {D}, false);
-    for (int cam = 0; cam < g.num_cams; ++cam) {
-        std::string p = "backbones." + std::to_string(cam) + ".0.body.";
-        add_param(c, p + "conv1.weight", {w0, 3, 7, 7}, false);
+    auto add_backbone = [&](const std::string& p, int in_ch) {
+        add_param(c, p + "conv1.weight", {w0, in_ch, 7, 7}, false);
         add_fbn(c, p + "bn1.", w0);
         int cin = w0;
         for (int li = 1; li <= 4; ++li) {
@@ -104,9 +103,15 @@ void build_spec(actmi_ctx* c) {
                 cin = cout;
             }
         }
-    }
+    };
+    for (int cam = 0; cam < g.num_cams; ++cam) add_backbone("backbones." + std::to_string(cam) + ".0.body.", 3);
     add_param(c, "input_proj_robot_state.weight", {D, S}, false);
     add_param(c, "input_proj_robot_state.bias", {D}, false);
+    if (c->Cd) {                                        // detr_vae.py:359-361, backbone.py:115-134
+        add_param(c, "input_proj_depth.weight", {D, 8 * w0, 1, 1}, false);
+        add_param(c, "input_proj_depth.bias", {D}, false);
+        for (int cam = 0; cam < c->Cd; ++cam) add_backbone("depth_backbones." + std::to_string(cam) + ".0.body.", 1);
+    }
     if (c->has_pcd) {                                   // detr_vae.py:64-65
         add_param(c, "input_proj_pointnet.weight", {D, c->pcd.output_dim}, false);
         add_param(c, "input_proj_pointnet.bias", {D}, false);
@@ -133,6 +138,7 @@ void build_spec(actmi_ctx* c) {
         }
     }
     add_param(c, "additional_pos_embed.weight", {c->n_extra, D}, false);
+    if (c->Cd) add_param(c, "depth_pos_embed.weight", {1, D}, false);      // registered by the reference, read by nothing
 }
 
 }  // namespace
@@ -276,9 +282,9 @@ int engine_calibrate_weight_scales(actmi_ctx* ctx, hipStream_t st) {
     };
     ctx->conv1_wscale = 4096.f;
     for (auto& cl : ctx->convs) cl.w16_scale = 4096.f;
-    for (int cam = 0; cam < ctx->cfg.num_cams; ++cam) {
-        const std::string p = "backbones." + std::to_string(cam) + ".0.body.";
-        ctx->conv1_wscale = std::min(ctx->conv1_wscale, key_scale(p + "conv1.weight"));
+    for (int cam = 0; cam < ctx->Ct; ++cam) {
+        const std::string p = trunk_cam_prefix(ctx, cam);
+        if (cam < ctx->cfg.num_cams) ctx->conv1_wscale = std::min(ctx->conv1_wscale, key_scale(p + "conv1.weight"));
         for (auto& cl : ctx->convs) cl.w16_scale = std::min(cl.w16_scale, key_scale(p + cl.name + ".weight"));
     }
     // weights split on the fly in the backward GEMMs share one static scale
@@ -443,6 +449,16 @@ int64_t backbone_cam_stride(actmi_ctx* ctx) {
     return ctx->P(p1 + "conv1.weight") - ctx->P("backbones.0.0.body.conv1.weight");
 }
 
+int64_t depth_cam_stride(actmi_ctx* ctx) {
+    const std::string p1 = "depth_backbones." + std::to_string(ctx->Cd > 1 ? 1 : 0) + ".0.body.";
+    return ctx->P(p1 + "conv1.weight") - ctx->P("depth_backbones.0.0.body.conv1.weight");
+}
+
+std::string trunk_cam_prefix(const actmi_ctx* ctx, int cam) {
+    const int C = ctx->cfg.num_cams;
+    return cam < C ? "backbones." + std::to_string(cam) + ".0.body." : "depth_backbones." + std::to_string(cam - C) + ".0.body.";
+}
+
 float* actmi_ctx::P(const std::string& key) {
     auto it = index.find(key);
     if (it == index.end()) return nullptr;
@@ -510,7 +526,7 @@ int create_device_state(actmi_ctx* ctx) {
     resolve_layers(ctx);
 
     // ---- conv layer table + packed weights
-    const int C = g.num_cams, w0 = g.base_width;
+    const int C = g.num_cams, Ct = ctx->Ct, w0 = g.base_width;
     {
         int cin = w0, H = ctx->H2, W = ctx->W2;
         for (int li = 1; li <= 4; ++li) {
@@ -541,24 +557,24 @@ int create_device_state(actmi_ctx* ctx) {
                 ds.name.find("downsample") != std::string::npos && (k2.cin % 32) == 0 && (ds.cin % 32) == 0) {
                 k2.ds_index = (int)i + 2;
                 k2.Kx = ds.cin;
-                ALLOC(k2.wf, (int64_t)C * k2.cout * (k2.K + k2.Kx)); ALLOC(k2.wf16, (int64_t)C * k2.cout * (k2.K + k2.Kx));
-                ALLOC(k2.bias_f, (int64_t)C * k2.cout);
+                ALLOC(k2.wf, (int64_t)Ct * k2.cout * (k2.K + k2.Kx)); ALLOC(k2.wf16, (int64_t)Ct * k2.cout * (k2.K + k2.Kx));
+                ALLOC(k2.bias_f, (int64_t)Ct * k2.cout);
             }
         }
         for (auto& cl : ctx->convs) {
-            ALLOC(cl.w, (int64_t)C * cl.cout * cl.K); ALLOC(cl.w16, (int64_t)C * cl.cout * cl.K);
-            ALLOC(cl.scale, (int64_t)C * cl.cout); ALLOC(cl.bias, (int64_t)C * cl.cout);
+            ALLOC(cl.w, (int64_t)Ct * cl.cout * cl.K); ALLOC(cl.w16, (int64_t)Ct * cl.cout * cl.K);
+            ALLOC(cl.scale, (int64_t)Ct * cl.cout); ALLOC(cl.bias, (int64_t)Ct * cl.cout);
         }
     }
     const int D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N, B = g.max_batch;
     ALLOC(ctx->conv1_w, (int64_t)C * w0 * 148);
     // (whatever the precision at create: actmi_set_gemm_prec may select f16x3 later)
     ALLOC(ctx->conv1_wimg, (int64_t)C * conv1_wimg_bytes());
-    ALLOC(ctx->conv1_scale, (int64_t)C * w0); ALLOC(ctx->conv1_bias, (int64_t)C * w0); ALLOC(ctx->lut, 768);
+    ALLOC(ctx->conv1_scale, (int64_t)Ct * w0); ALLOC(ctx->conv1_bias, (int64_t)Ct * w0); ALLOC(ctx->lut, 768);
     ALLOC(ctx->pos_tokens, (int64_t)N * D); ALLOC(ctx->dec_t1, D); ALLOC(ctx->dec_q, (int64_t)Q * D); ALLOC(ctx->dec_sa, D);
     ALLOC(ctx->act_scale_slot, 2); ALLOC(ctx->wf_scale_slots, 2 * (int64_t)ctx->convs.size());
     ALLOC(ctx->act_scale_dev, (int64_t)ctx->convs.size() + 4);
-    ALLOC(ctx->rowmap, (int64_t)B * C * ctx->P_);
+    ALLOC(ctx->rowmap, (int64_t)B * Ct * ctx->P_);
     ctx->rowmap_B = -1;
     if (ctx->has_pcd) {
         const int64_t Hp = ctx->pcd.hidden_dim, Op = ctx->pcd.output_dim, rows = (int64_t)B * ctx->pcd.max_points;
@@ -568,8 +584,8 @@ int create_device_state(actmi_ctx* ctx) {
         ALLOC(ctx->pcd_ws, ctx->pcd_ws_floats);
     }
     // ---- activations (camera-major NHWC maps, token-major [B][N][D])
-    ALLOC(ctx->act1, (int64_t)C * B * ctx->H1 * ctx->W1 * w0);
-    for (int i = 0; i < 3; ++i) ALLOC(ctx->buf[i], (int64_t)C * B * ctx->H2 * ctx->W2 * w0);
+    ALLOC(ctx->act1, (int64_t)Ct * B * ctx->H1 * ctx->W1 * w0);
+    for (int i = 0; i < 3; ++i) ALLOC(ctx->buf[i], (int64_t)Ct * B * ctx->H2 * ctx->W2 * w0);
     const int64_t BN_ = (int64_t)B * N, BQ = (int64_t)B * Q;
     ALLOC(ctx->X, BN_ * D); ALLOC(ctx->X1, BN_ * D); ALLOC(ctx->XP, BN_ * D); ALLOC(ctx->Y, BN_ * D);
     ALLOC(ctx->ATT, BN_ * D); ALLOC(ctx->QKV, BN_ * 3 * D); ALLOC(ctx->Hb, BN_ * F);
@@ -594,12 +610,17 @@ int create_device_state(actmi_ctx* ctx) {
 
 }  // namespace
 
-int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_ctx** out) {
+int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, const actmi_depth_config* depth, actmi_ctx** out) {
     if (!cfg || !out) { g_create_error = "null argument"; return ACTMI_E_INVALID; }
     const actmi_config& g = *cfg;
     if (pcd && pcd->struct_size != (uint32_t)sizeof(actmi_pcd_config)) {
         g_create_error = "actmi_pcd_config.struct_size is " + std::to_string(pcd->struct_size) + ", this library expects " +
                          std::to_string(sizeof(actmi_pcd_config)) + " (binding built against a different include/actmi.h)";
+        return ACTMI_E_INVALID;
+    }
+    if (depth && depth->struct_size != (uint32_t)sizeof(actmi_depth_config)) {
+        g_create_error = "actmi_depth_config.struct_size is " + std::to_string(depth->struct_size) + ", this library expects " +
+                         std::to_string(sizeof(actmi_depth_config)) + " (binding built against a different include/actmi.h)";
         return ACTMI_E_INVALID;
     }
     if (g.struct_size != (uint32_t)sizeof(actmi_config)) {
@@ -628,8 +649,17 @@ int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_ct
             return ACTMI_E_INVALID;
         }
     }
+    if (depth && pcd) { g_create_error = "depth cameras together with a point-cloud branch are not supported"; return ACTMI_E_INVALID; }
+    if (depth && depth->num_depth_cams != g.num_cams) {
+        // the reference's camera loop indexes the depth backbones by the RGB camera (detr_vae.py:188-202)
+        g_create_error = "num_depth_cams is " + std::to_string(depth->num_depth_cams) + " but num_cams is " + std::to_string(g.num_cams) +
+                         ": one depth camera per RGB camera";
+        return ACTMI_E_INVALID;
+    }
     actmi_ctx* ctx = new actmi_ctx();
     ctx->cfg = g;
+    ctx->Cd = depth ? depth->num_depth_cams : 0;
+    ctx->Ct = g.num_cams + ctx->Cd;
     if (pcd) { ctx->has_pcd = true; ctx->pcd = *pcd; ctx->n_extra = 3; }
     if (hipGetDevice(&ctx->device) != hipSuccess) { g_create_error = "hipGetDevice failed"; delete ctx; return ACTMI_E_LAUNCH; }
     ctx->ptotal = 0;
@@ -641,7 +671,7 @@ int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_ct
     for (int i = 0; i < 3; ++i) { h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1); }
     ctx->fh = h; ctx->fw = w;
     ctx->P_ = h * w;
-    ctx->N = ctx->n_extra + g.num_cams * h * w;
+    ctx->N = ctx->n_extra + ctx->Ct * h * w;
     if (h < 1 || w < 1) { g_create_error = "image too small"; delete ctx; return ACTMI_E_INVALID; }
 
     read_switches(ctx);
@@ -678,7 +708,7 @@ const char* engine_create_error() { return g_create_error.c_str(); }
 // first where the layer's images are stored taps-inner; flag (optional): raised when a weight leaves the fp16 range of the image
 static int split_conv_image(actmi_ctx* ctx, const ConvLayer& cl, const float* w, float* w16, int K, float scale, uint32_t* flag,
                             hipStream_t st) {
-    const int64_t rows = (int64_t)ctx->cfg.num_cams * cl.cout;
+    const int64_t rows = (int64_t)ctx->Ct * cl.cout;
     if (cl.k_tap_inner) {
         CHK(launch_permute_conv_k(w, ctx->splitk_ws, rows, cl.k * cl.k, cl.cin, K, st));
         w = ctx->splitk_ws;
@@ -696,10 +726,12 @@ static int build_pos_tokens(actmi_ctx* ctx) {
     const float eps = 1e-6f, scale = (float)(2.0 * M_PI);
     std::vector<float> dim_t(npf);
     for (int k = 0; k < npf; ++k) dim_t[k] = powf(10000.f, (2.f * (float)(k / 2)) / (float)npf);
+    // (the depth tokens behind the RGB ones carry the same table: transformer.py:64-86 adds pos to both)
+    for (int grp = 0; grp < (ctx->Cd ? 2 : 1); ++grp)
     for (int hh = 0; hh < fh; ++hh)
-        for (int cam = 0; cam < C; ++cam)
+        for (int cam = 0; cam < (grp ? ctx->Cd : C); ++cam)
             for (int ww = 0; ww < fw; ++ww) {
-                float* row = &pos[(size_t)(ctx->n_extra + hh * (fw * C) + cam * fw + ww) * D];
+                float* row = &pos[(size_t)(ctx->n_extra + grp * C * fh * fw + hh * (fw * (grp ? ctx->Cd : C)) + cam * fw + ww) * D];
                 const float y = (float)(hh + 1) / ((float)fh + eps) * scale;
                 const float x = (float)(ww + 1) / ((float)fw + eps) * scale;
                 for (int k = 0; k < npf; ++k) {
@@ -725,11 +757,18 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
         for (auto& cl : ctx->convs)
             CHK(launch_repack_conv_w(ctx->P(p0 + cl.name + ".weight"), cl.w, C, cl.cout, cl.cin, cl.k, cl.k, cam_stride,
                                      (int64_t)cl.cout * cl.K, cl.K, st));
+        if (ctx->Cd) {                      // the depth backbones fill cameras C.. (their conv1 is read in place by its kernel)
+            const std::string d0 = "depth_backbones.0.0.body.";
+            const int64_t dstride = depth_cam_stride(ctx);
+            for (auto& cl : ctx->convs)
+                CHK(launch_repack_conv_w(ctx->P(d0 + cl.name + ".weight"), cl.w + (int64_t)C * cl.cout * cl.K, ctx->Cd, cl.cout, cl.cin,
+                                         cl.k, cl.k, dstride, (int64_t)cl.cout * cl.K, cl.K, st));
+        }
     }
     // FrozenBN -> scale / bias: buffers the optimizer never touches (reference backbone.py:21-57), so not redone after a step
     if (!after_step)
-        for (int cam = 0; cam < C; ++cam) {
-            std::string p = "backbones." + std::to_string(cam) + ".0.body.";
+        for (int cam = 0; cam < ctx->Ct; ++cam) {
+            std::string p = trunk_cam_prefix(ctx, cam);
             CHK(launch_bn_fold(ctx->P(p + "bn1.weight"), ctx->P(p + "bn1.bias"), ctx->P(p + "bn1.running_mean"),
                                ctx->P(p + "bn1.running_var"), ctx->conv1_scale + cam * w0, ctx->conv1_bias + cam * w0, w0, st));
             for (auto& cl : ctx->convs)
@@ -746,7 +785,7 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
             // K order of the image: channel blocks outer, taps inner, for the convolutions of the implicit-GEMM kernel (L2 reuse of
             // the input patch); the direct kernel of layer1 reads (r, s, c)
             cl.k_tap_inner = cl.k == 3 && (cl.cin % 32) == 0 && !cl.direct &&
-                             (int64_t)C * cl.cout * (cl.K + cl.Kx) <= ctx->splitk_ws_floats;
+                             (int64_t)ctx->Ct * cl.cout * (cl.K + cl.Kx) <= ctx->splitk_ws_floats;
             CHK(split_conv_image(ctx, cl, cl.w, cl.w16, cl.K, cl.w16_scale, ctx->flags, st));
         }
         // blocks with a downsample branch: [bn2.scale * conv2.w | bn_ds.scale * ds.w] and the summed bias (FrozenBN statistics
@@ -754,7 +793,7 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
         for (const ConvLayer& cl : ctx->convs)
             if (cl.wf) {
                 const ConvLayer& ds = ctx->convs[cl.ds_index];
-                CHK(launch_fold_cat_w(cl.w, cl.scale, cl.bias, ds.w, ds.scale, ds.bias, cl.wf, cl.bias_f, C, cl.cout, cl.K, cl.Kx, st));
+                CHK(launch_fold_cat_w(cl.w, cl.scale, cl.bias, ds.w, ds.scale, ds.bias, cl.wf, cl.bias_f, ctx->Ct, cl.cout, cl.K, cl.Kx, st));
                 // (at finalize the scale is measured right after this and the image split again: no overflow report from the
                 // provisional one)
                 CHK(split_conv_image(ctx, cl, cl.wf, cl.wf16, cl.K + cl.Kx, cl.wf16_scale, after_step ? ctx->flags : nullptr, st));
@@ -779,7 +818,7 @@ int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
 
 int engine_finalize(actmi_ctx* ctx, hipStream_t st) {
     ctx->err.clear();
-    const int C = ctx->cfg.num_cams;
+    const int C = ctx->Ct;
     // 1. training scratch for the current precision (actmi_set_gemm_prec may have changed it since create)
     if (ctx->train) CHK(train_fit_prec(ctx));
     // 2. u8 -> normalised float LUT with the reference's arithmetic
@@ -850,7 +889,7 @@ int engine_measure_act_scale(actmi_ctx* ctx, const float* x, int64_t rows, int c
 
 int engine_calibrate_activations(actmi_ctx* ctx, hipStream_t st) {
     for (auto& cl : ctx->convs) cl.a_scale = 1.f;
-    ctx->ip_a_scale = 1.f;
+    ctx->ip_a_scale = ctx->ip_d_a_scale = 1.f;
     if (ctx->gemm_prec != ACTMI_PREC_F16X3 || !ctx->act_calib) return 0;
     const actmi_config& g = ctx->cfg;
     const size_t nbytes = (size_t)g.num_cams * g.image_h * g.image_w * 3;
@@ -860,16 +899,25 @@ int engine_calibrate_activations(actmi_ctx* ctx, hipStream_t st) {
     void* dimg = nullptr;
     if (hipMalloc(&dimg, nbytes) != hipSuccess) { ctx->err = "hipMalloc (calibration frame)"; return ACTMI_E_NOMEM; }
     int rc = hipMemcpy(dimg, img.data(), nbytes, hipMemcpyHostToDevice) == hipSuccess ? 0 : ACTMI_E_LAUNCH;
+    float* ddep = nullptr;
+    if (rc == 0 && ctx->Cd) {                   // a fixed noise depth frame in [0, 1)
+        const size_t nd = (size_t)ctx->Cd * g.image_h * g.image_w;
+        std::vector<float> dep(nd);
+        for (size_t i = 0; i < nd; ++i) { x = x * 1664525u + 1013904223u; dep[i] = (float)(x >> 8) * (1.f / 16777216.f); }
+        if (hipMalloc(reinterpret_cast<void**>(&ddep), nd * sizeof(float)) != hipSuccess) { ctx->err = "hipMalloc (calibration frame)"; rc = ACTMI_E_NOMEM; }
+        else if (hipMemcpy(ddep, dep.data(), nd * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = ACTMI_E_LAUNCH;
+    }
     if (rc == 0) {
         ctx->calibrating = true;
         const std::string keep = ctx->stop_stage;
         ctx->stop_stage.clear();
-        rc = engine_backbone(ctx, dimg, ACTMI_IMG_U8_NHWC, 1, st);
+        rc = engine_backbone(ctx, dimg, ddep, ACTMI_IMG_U8_NHWC, 1, st);
         ctx->stop_stage = keep;
         ctx->calibrating = false;
         if (hipStreamSynchronize(st) != hipSuccess && rc == 0) rc = ACTMI_E_LAUNCH;
     }
     (void)hipFree(dimg);
+    if (ddep) (void)hipFree(ddep);
     ctx->dbg.clear();
     return rc;
 }
@@ -911,18 +959,42 @@ static int run_branches(actmi_ctx* ctx, int nb, hipStream_t st, Body body) {
     return 0;
 }
 
+// feature row m = ((cam*B + b)*fh + h)*fw + w of the trunk's layer4 maps -> its token row: the RGB cameras first, the depth
+// cameras' tokens behind all of them (transformer.py:64-86)
+int engine_build_rowmap(actmi_ctx* ctx, int B, hipStream_t st) {
+    if (ctx->rowmap_B == B) return 0;
+    const int C = ctx->cfg.num_cams;
+    CHK(launch_build_rowmap(ctx->rowmap, B, C, ctx->fh, ctx->fw, ctx->N, ctx->n_extra, st));
+    if (ctx->Cd)
+        CHK(launch_build_rowmap(ctx->rowmap + (int64_t)C * B * ctx->P_, B, ctx->Cd, ctx->fh, ctx->fw, ctx->N, ctx->n_extra + C * ctx->P_, st));
+    ctx->rowmap_B = B;
+    return 0;
+}
+
 // multi-camera ResNet18 trunk + input_proj -> token rows n_extra.. of X   (backbone.py:66-71, detr_vae.py:180-185)
-int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream_t st) {
+int engine_depth_stem(actmi_ctx* ctx, const float* depth, int B, hipStream_t st) {
     const actmi_config& g = ctx->cfg;
-    const int C = g.num_cams, w0 = g.base_width, D = g.hidden_dim;
+    const int C = g.num_cams, w0 = g.base_width;
+    Conv1DepthArgs d;
+    d.depth = depth; d.w = ctx->P("depth_backbones.0.0.body.conv1.weight"); d.w_cam_stride = depth_cam_stride(ctx);
+    d.scale = ctx->conv1_scale + (int64_t)C * w0; d.bias = ctx->conv1_bias + (int64_t)C * w0; d.out = ctx->act1;
+    d.B = B; d.Cd = ctx->Cd; d.H = g.image_h; d.W = g.image_w; d.Ho = ctx->H1; d.Wo = ctx->W1; d.Cout = w0; d.out_cam0 = C;
+    return launch_conv1_depth(d, st, &ctx->err) == 0 ? 0 : ACTMI_E_LAUNCH;
+}
+
+int engine_backbone(actmi_ctx* ctx, const void* image, const float* depth, int fmt, int B, hipStream_t st) {
+    const actmi_config& g = ctx->cfg;
+    const int Crgb = g.num_cams, C = ctx->Ct, w0 = g.base_width, D = g.hidden_dim;
     Conv1Args c1 = stem_args(ctx, image, fmt, B);
     // inference never needs conv1's own map: the stem emits the vertical half of the max pool (half the bytes) and a
     // row-wise pass finishes it.  Same maxima, so the result is bit-identical to conv1 -> 3x3 pool.
-    const bool vpool = ctx->conv1_vpool && ctx->stop_stage != "conv1" && ctx->gemm_prec == ACTMI_PREC_F16X3 && (ctx->H1 & 1) == 0 &&
+    // (a depth handle keeps the two-kernel form: the depth stem writes conv1's own map)
+    const bool vpool = ctx->conv1_vpool && !ctx->Cd && ctx->stop_stage != "conv1" && ctx->gemm_prec == ACTMI_PREC_F16X3 && (ctx->H1 & 1) == 0 &&
                        (w0 & 3) == 0 && ctx->H2 == ctx->H1 / 2;
     // stem (conv1 + pool) of all cameras, ahead of the branches
     c1.vpool = vpool ? 1 : 0;
     CHK(launch_conv1(c1, st, &ctx->err));
+    if (ctx->Cd) CHK(engine_depth_stem(ctx, depth, B, st));                // cameras Crgb.. of the same map
     if (vpool) CHK(launch_hpool(ctx->act1, ctx->buf[0], C * B * ctx->H2, ctx->W1, w0, ctx->W2, st));
     else CHK(launch_maxpool(ctx->act1, ctx->buf[0], C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st));
     ctx->dbg.clear();
@@ -1013,21 +1085,26 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
                 }
             }
         }
-        // input_proj (1x1 convolution, detr_vae.py:184) of the range's layer4 maps, rows scattered to their tokens
-        GemmArgs ip = linear_args(cur, 8 * w0, nc * B * ctx->P_, 8 * w0, ctx->P("input_proj.weight"), D, ctx->P("input_proj.bias"),
-                                  ctx->X, D);
-        ip.rowmap = ctx->rowmap + (int64_t)c0 * B * ctx->P_;
-        if (ctx->calibrating) {
-            CHK(engine_measure_act_scale(ctx, cur, (int64_t)nc * B * ctx->P_, 8 * w0, ls, &ctx->ip_a_scale));
-            HIPCHK(hipStreamSynchronize(ls));
+        // input_proj (1x1 convolution, detr_vae.py:184) of the range's layer4 maps, rows scattered to their tokens; the depth
+        // cameras of the range go through input_proj_depth (detr_vae.py:196-198), each projection with its own pre-scale
+        for (int part = 0; part < 2; ++part) {
+            const int p0 = part ? std::max(c0, Crgb) : c0, p1 = part ? c0 + nc : std::min(c0 + nc, Crgb);
+            if (p1 <= p0) continue;
+            const float* maps = cur + (int64_t)(p0 - c0) * B * ctx->P_ * 8 * w0;
+            float& a_scale = part ? ctx->ip_d_a_scale : ctx->ip_a_scale;
+            GemmArgs ip = linear_args(maps, 8 * w0, (p1 - p0) * B * ctx->P_, 8 * w0, ctx->P(part ? "input_proj_depth.weight" : "input_proj.weight"),
+                                      D, ctx->P(part ? "input_proj_depth.bias" : "input_proj.bias"), ctx->X, D);
+            ip.rowmap = ctx->rowmap + (int64_t)p0 * B * ctx->P_;
+            if (ctx->calibrating) {
+                CHK(engine_measure_act_scale(ctx, maps, (int64_t)(p1 - p0) * B * ctx->P_, 8 * w0, ls, &a_scale));
+                HIPCHK(hipStreamSynchronize(ls));
+            }
+            if (ctx->gemm_prec == ACTMI_PREC_F16X3 && a_scale != 1.f) ip.a_scale = a_scale;
+            CHK(ctx_gemm(ctx, ip, ls, half));
         }
-        if (ctx->gemm_prec == ACTMI_PREC_F16X3 && ctx->ip_a_scale != 1.f) ip.a_scale = ctx->ip_a_scale;
-        return ctx_gemm(ctx, ip, ls, half);
+        return 0;
     };
-    if (ctx->rowmap_B != B) {
-        CHK(launch_build_rowmap(ctx->rowmap, B, C, ctx->fh, ctx->fw, ctx->N, ctx->n_extra, st));
-        ctx->rowmap_B = B;
-    }
+    CHK(engine_build_rowmap(ctx, B, st));
     if (pipe) {
         // two camera halves as two parallel branches: when one half's launch runs out of workgroups (layer3: 300 per half on
         // 512 slots) the other half's current launch fills the CUs, and no launch boundary drains the whole chip
@@ -1042,6 +1119,22 @@ int engine_backbone(actmi_ctx* ctx, const void* image, int fmt, int B, hipStream
         const int rc = run_layers(0, C, st, -1);
         if (rc != 0) return rc;
     }
+    return 0;
+}
+
+int engine_take_depth(actmi_ctx* ctx, int B, const float** depth) {
+    *depth = nullptr;
+    if (!ctx->Cd) return 0;
+    if (!ctx->depth_img) {
+        ctx->err = "this handle has depth cameras: bind the depth batch of every forward with actmi_set_depth";
+        return ACTMI_E_STATE;
+    }
+    if (ctx->depth_B != B) {
+        ctx->err = "forward of batch " + std::to_string(B) + " but the bound depth batch holds " + std::to_string(ctx->depth_B) + " samples";
+        return ACTMI_E_STATE;
+    }
+    *depth = ctx->depth_img;
+    ctx->depth_img = nullptr;                           // one binding, one forward
     return 0;
 }
 
@@ -1205,13 +1298,15 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
     const int D = g.hidden_dim, N = ctx->N;
     const float *pc_xyz = nullptr, *pc_rgb = nullptr;
     int pc_P = 0;
+    const float* depth = nullptr;
     if (ctx->fwd_phase != 2) CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_P));     // (before anything is launched)
+    if (ctx->fwd_phase != 2) CHK(engine_take_depth(ctx, B, &depth));
     // actmi_set_forward_phase: the step as two halves a caller can capture into two graphs -- the trunk with the token assembly
     // (the only reader of `image` and `qpos`, and the HBM-heavy part) and the transformer -- so that the host-to-device copy of the
     // NEXT frame hangs on an ordinary stream event between them and runs beside the transformer.  Phase 2 continues from the tokens
     // phase 1 left in ctx->X.
     if (ctx->fwd_phase != 2) {
-        const int rc = engine_backbone(ctx, image, fmt, B, st);
+        const int rc = engine_backbone(ctx, image, depth, fmt, B, st);
         if (rc == 1) return 0;
         if (rc != 0) return rc;
         // token 0: latent_input = latent_out_proj(0) = bias (detr_vae.py:158-159), or latent_out_proj(code) for VQ-ACT

@@ -367,7 +367,7 @@ int enc_bwd(actmi_ctx* ctx, const EncW& w, const EncSave& s, const float* dOut, 
 int conv_wgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, const float* dys_scale, const float* x, int B,
                hipStream_t st) {
     TrainState& T = *ctx->train;
-    const int C = ctx->cfg.num_cams;
+    const int C = ctx->Ct;
     if (ctx->gemm_prec == ACTMI_PREC_F16X3 && cl.direct && T.det_ws_floats >= (int64_t)C * 64 * 576) {
         // layer1: the direct kernel (wgrad3.hip), accumulating into the packed gradient like autograd
         if (launch_wgrad3x3_c64(dys, x, T.conv_gw[li], 1, T.det_ws, T.det_ws_floats, dys_scale, C, B, cl.H, cl.W, st) != 0) {
@@ -399,7 +399,7 @@ bool dgrad_direct(const actmi_ctx* ctx, const ConvLayer& cl) {
 int conv_dgrad(actmi_ctx* ctx, const ConvLayer& cl, int li, const float* dys, const float* dys_scale, float* dx, const float* res,
                const float* mask, const float* scale, int B, hipStream_t st, unsigned* dx_amax = nullptr) {
     TrainState& T = *ctx->train;
-    const int C = ctx->cfg.num_cams;
+    const int C = ctx->Ct;
     if (dgrad_direct(ctx, cl) && T.conv_wd16[li]) {
         Conv3Args c{};
         c.x = dys; c.w16 = T.conv_wd16[li]; c.res = res; c.out = dx; c.G = C; c.B = B; c.H = cl.H; c.W = cl.W; c.relu = 0;
@@ -443,17 +443,17 @@ int train_create(actmi_ctx* ctx) {
     const actmi_config& g = ctx->cfg;
     ctx->train = new TrainState();
     TrainState& T = *ctx->train;
-    const int B = g.max_batch, C = g.num_cams, D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N,
+    const int B = g.max_batch, C = ctx->Ct, D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N,
               w0 = g.base_width, H = g.nheads, L = g.latent_dim, A = g.action_dim;
     ALLOC(T.gbase, ctx->ptotal); ALLOC(T.mbase, ctx->ptotal); ALLOC(T.vbase, ctx->ptotal);
     if (hipMemset(T.gbase, 0, ctx->ptotal * 4) != hipSuccess || hipMemset(T.mbase, 0, ctx->ptotal * 4) != hipSuccess ||
         hipMemset(T.vbase, 0, ctx->ptotal * 4) != hipSuccess) { ctx->err = "hipMemset failed"; return ACTMI_E_LAUNCH; }
     {
-        // optimizer group per 64-float slot: 0 skip (buffers; is_pad_head never gets a grad), 1 lr, 2 lr_backbone
+        // optimizer group per 64-float slot: 0 skip (buffers; is_pad_head and depth_pos_embed never get a grad), 1 lr, 2 lr_backbone
         std::vector<uint8_t> grp((size_t)(ctx->ptotal / 64), 0);
         for (const Param& p : ctx->params) {
             uint8_t gcode = 0;
-            if (!p.is_buffer && p.key.rfind("is_pad_head", 0) != 0) gcode = p.key.find("backbone") != std::string::npos ? 2 : 1;
+            if (!p.is_buffer && p.key.rfind("is_pad_head", 0) != 0 && p.key.rfind("depth_pos_embed", 0) != 0) gcode = p.key.find("backbone") != std::string::npos ? 2 : 1;
             for (int64_t c = p.off / 64; c < (p.off + ((p.numel + 63) & ~int64_t(63))) / 64; ++c) grp[(size_t)c] = gcode;
         }
         ALLOC(T.group, (int64_t)grp.size());
@@ -562,7 +562,7 @@ int train_create(actmi_ctx* ctx) {
 int train_fit_prec(actmi_ctx* ctx) {
     const actmi_config& g = ctx->cfg;
     TrainState& T = *ctx->train;
-    const int B = g.max_batch, C = g.num_cams, D = g.hidden_dim, H = g.nheads, Q = g.num_queries, N = ctx->N;
+    const int B = g.max_batch, C = ctx->Ct, D = g.hidden_dim, H = g.nheads, Q = g.num_queries, N = ctx->N;
     auto release = [&](float*& p) {           // (hipFree waits for the device: no launch in flight still uses p)
         ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), (void*)p), ctx->allocs.end());
         (void)hipFree(p);
@@ -603,10 +603,12 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
     const float *pc_xyz = nullptr, *pc_rgb = nullptr;
     int pc_P = 0;
     CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_P));            // (before anything is launched)
+    const float* depth = nullptr;
+    CHK(engine_take_depth(ctx, B, &depth));
     PrecScope prec_scope(ctx);               // the opt-in bf16 product mode covers the GEMMs of this call only
     TrainState& T = *ctx->train;
     const actmi_config& g = ctx->cfg;
-    const int C = g.num_cams, D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N, w0 = g.base_width,
+    const int Crgb = g.num_cams, C = ctx->Ct, D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N, w0 = g.base_width,
               L = g.latent_dim, A = g.action_dim, S = g.state_dim, hd = D / g.nheads;
     T.B = B; T.fmt = fmt; T.drop_p = dropout_p; T.drop_seed = dropout_seed;
     const Drop dr_dec{dropout_p, dropout_seed, 200};
@@ -652,8 +654,14 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
     }
 
     // ---- backbone with saved maps
-    CHK(launch_normalize_pad(image, fmt, ctx->lut, T.xn4, B, C, g.image_h, g.image_w, st));
+    CHK(launch_normalize_pad(image, fmt, ctx->lut, T.xn4, B, Crgb, g.image_h, g.image_w, st));
     CHK(launch_conv1(stem_args(ctx, image, fmt, B), st, &ctx->err));
+    if (ctx->Cd) {
+        // depth cameras: cameras Crgb.. of the same maps.  The stem's weight gradient reads the normalised depth as channel 0 of
+        // an NHWC4 image like the RGB one (three quarters of that contraction multiply zeros)
+        CHK(launch_depth_nhwc4(depth, T.xn4 + (int64_t)Crgb * B * g.image_h * g.image_w * 4, B, ctx->Cd, g.image_h, g.image_w, st));
+        CHK(engine_depth_stem(ctx, depth, B, st));
+    }
     CHK(launch_maxpool_idx(ctx->act1, T.pool, T.pool_arg, C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st));
     // (no activation pre-scales: those are calibrated for the inference forward)
     auto run_conv = [&](const ConvLayer& cl, const float* in, float* out, const float* res, int relu) -> int {
@@ -672,13 +680,17 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
         CHK(run_conv(ctx->convs[bs.c2], bs.y1, bs.out, idt, 1));
         x = bs.out;
     }
-    if (ctx->rowmap_B != B) {
-        CHK(launch_build_rowmap(ctx->rowmap, B, C, ctx->fh, ctx->fw, N, ctx->n_extra, st));
-        ctx->rowmap_B = B;
-    }
+    CHK(engine_build_rowmap(ctx, B, st));
     {
-        GemmArgs ip = linear_args(x, 8 * w0, C * B * ctx->P_, 8 * w0, ctx->P("input_proj.weight"), D, ctx->P("input_proj.bias"), ctx->X, D);
+        GemmArgs ip = linear_args(x, 8 * w0, Crgb * B * ctx->P_, 8 * w0, ctx->P("input_proj.weight"), D, ctx->P("input_proj.bias"), ctx->X, D);
         ip.rowmap = ctx->rowmap;
+        CHK(tgemm(ctx, ip, st));
+    }
+    if (ctx->Cd) {
+        const int64_t r0 = (int64_t)Crgb * B * ctx->P_;
+        GemmArgs ip = linear_args(x + r0 * 8 * w0, 8 * w0, ctx->Cd * B * ctx->P_, 8 * w0, ctx->P("input_proj_depth.weight"), D,
+                                  ctx->P("input_proj_depth.bias"), ctx->X, D);
+        ip.rowmap = ctx->rowmap + r0;
         CHK(tgemm(ctx, ip, st));
     }
     CHK(launch_small_linear(qpos, S, ctx->P("input_proj_robot_state.weight"), ctx->P("input_proj_robot_state.bias"),
@@ -779,7 +791,7 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     PrecScope prec_scope(ctx);
     TrainState& T = *ctx->train;
     const actmi_config& g = ctx->cfg;
-    const int B = T.B, C = g.num_cams, D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N,
+    const int B = T.B, Crgb = g.num_cams, C = ctx->Ct, D = g.hidden_dim, F = g.dim_feedforward, Q = g.num_queries, N = ctx->N,
               w0 = g.base_width, L = g.latent_dim, A = g.action_dim, S = g.state_dim, hd = D / g.nheads, H = g.nheads;
     auto Gp = [&](const float* p) { return T.gbase + (p - ctx->pbase); };
     auto GP = [&](const char* key) { return T.gbase + (ctx->P(key) - ctx->pbase); };
@@ -946,8 +958,13 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     CHK(launch_gather_rows(dX, ctx->rowmap, T.dXg, MP, D, st));
     const BlockSave& last = T.blocks.back();
     float* gcur = T.gbuf[0];                // grad wrt the current block output
-    CHK(lin_bwd(ctx, measured(ctx, T.dXg, D, MP, D, st), ctx->P("input_proj.weight"), 8 * w0, last.out, 8 * w0, gcur, 8 * w0,
+    const int MPr = Crgb * B * ctx->P_;      // the RGB cameras' rows; the depth cameras' rows follow (input_proj_depth)
+    CHK(lin_bwd(ctx, measured(ctx, T.dXg, D, MPr, D, st), ctx->P("input_proj.weight"), 8 * w0, last.out, 8 * w0, gcur, 8 * w0,
                 GP("input_proj.weight"), GP("input_proj.bias"), st));
+    if (ctx->Cd)
+        CHK(lin_bwd(ctx, measured(ctx, T.dXg + (int64_t)MPr * D, D, MP - MPr, D, st), ctx->P("input_proj_depth.weight"), 8 * w0,
+                    last.out + (int64_t)MPr * 8 * w0, 8 * w0, gcur + (int64_t)MPr * 8 * w0, 8 * w0, GP("input_proj_depth.weight"),
+                    GP("input_proj_depth.bias"), st));
 
     // ---- backbone: BasicBlocks in reverse.  Frozen BN: y = conv * scale + bias  =>  dconv = dy * scale.
     for (size_t li = 0; li < ctx->convs.size(); ++li) {
@@ -1016,11 +1033,22 @@ int train_backward(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
     {
         const std::string p0 = "backbones.0.0.body.";
         const int64_t cam_stride = backbone_cam_stride(ctx);
-        CHK(launch_unpack_wgrad(T.conv1_gw, GP((p0 + "conv1.weight").c_str()), w0, 3, 7, 7, 196, 4, st, C, (int64_t)w0 * 196, cam_stride));
+        CHK(launch_unpack_wgrad(T.conv1_gw, GP((p0 + "conv1.weight").c_str()), w0, 3, 7, 7, 196, 4, st, Crgb, (int64_t)w0 * 196, cam_stride));
         for (size_t li = 0; li < ctx->convs.size(); ++li) {
             const ConvLayer& cl = ctx->convs[li];
             CHK(launch_unpack_wgrad(T.conv_gw[li], GP((p0 + cl.name + ".weight").c_str()), cl.cout, cl.cin, cl.k, cl.k, cl.K, cl.cin, st,
-                                    C, (int64_t)cl.cout * cl.K, cam_stride));
+                                    Crgb, (int64_t)cl.cout * cl.K, cam_stride));
+        }
+        if (ctx->Cd) {                      // cameras Crgb..: the depth backbones' range of the arena (conv1 with cin = 1)
+            const std::string d0 = "depth_backbones.0.0.body.";
+            const int64_t dstride = depth_cam_stride(ctx);
+            CHK(launch_unpack_wgrad(T.conv1_gw + (int64_t)Crgb * w0 * 196, GP((d0 + "conv1.weight").c_str()), w0, 1, 7, 7, 196, 4, st, ctx->Cd,
+                                    (int64_t)w0 * 196, dstride));
+            for (size_t li = 0; li < ctx->convs.size(); ++li) {
+                const ConvLayer& cl = ctx->convs[li];
+                CHK(launch_unpack_wgrad(T.conv_gw[li] + (int64_t)Crgb * cl.cout * cl.K, GP((d0 + cl.name + ".weight").c_str()), cl.cout, cl.cin,
+                                        cl.k, cl.k, cl.K, cl.cin, st, ctx->Cd, (int64_t)cl.cout * cl.K, dstride));
+            }
         }
     }
 

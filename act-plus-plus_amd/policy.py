@@ -72,8 +72,7 @@ class ACTPolicy:
         self.use_depth = args_override.get("use_depth", False)
         self.use_pcd = args_override.get("use_pcd", False)
         self.depth_camera_names = args_override.get("depth_camera_names", None)
-        if self.use_depth:
-            raise NotImplementedError("depth inputs are outside the accelerated ACT path")
+        # use_depth needs depth_camera_names, one per RGB camera (ACTConfig.validate raises NotImplementedError otherwise)
         self.cfg = ACTConfig.from_policy_config(args_override)
         self.kl_weight = args_override["kl_weight"]
         self.vq = args_override.get("vq", False)
@@ -98,6 +97,10 @@ class ACTPolicy:
         if self.use_pcd and pointcloud is None:
             raise ValueError("a use_pcd policy needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]}")
         pointcloud = pointcloud if self.use_pcd else None       # reference policy.py:301, 329
+        if self.use_depth and depth_img is None:
+            # (the reference would silently run RGB-only with a shorter sequence; the handle's token count is fixed at create)
+            raise ValueError("a use_depth policy needs depth_img float32 [B, Cd, 1, H, W]")
+        depth_img = depth_img if self.use_depth else None       # reference policy.py:275-286: ignored without use_depth
         if actions is not None:                                # training / validation (policy.py:288-320)
             eps = getattr(self, "next_eps", None)
             self.next_eps = None
@@ -108,13 +111,13 @@ class ACTPolicy:
             self.next_vq_code = None
             out = self.model.forward_train(qpos, image, actions, is_pad, eps=eps, dropout_p=p,
                                            dropout_seed=(self.dropout_seed << 20) + self._drop_step, vq_code=code,
-                                           pointcloud=pointcloud)
+                                           pointcloud=pointcloud, depth_img=depth_img)
             loss_dict = {"l1": out["l1"], "kl": out["kl"], "loss": _Loss.wrap(out["loss"], self)}
             if self.vq:                                         # policy.py:311-312 (logged, not part of the loss)
                 loss_dict["vq_discrepancy"] = out["vq_discrepancy"]
             return loss_dict
         # inference: ImageNet normalisation (policy.py:268-272) is fused into the conv1 loader
-        return self.model.forward_infer(qpos, image, vq_sample=vq_sample, pointcloud=pointcloud)
+        return self.model.forward_infer(qpos, image, vq_sample=vq_sample, pointcloud=pointcloud, depth_img=depth_img)
 
     # ---- nn.Module-like surface used by imitate_episodes.py ---------------------------------------
     def cuda(self):

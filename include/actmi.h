@@ -233,6 +233,31 @@ int actmi_create_ex(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_
  * until actmi_backward) has been enqueued.  A forward of a point-cloud handle without bound clouds, or with another B, returns
  * ACTMI_E_STATE; so does this call on a handle created without a point-cloud config. */
 int actmi_set_pointcloud(actmi_handle h, const float* xyz, const float* rgb, int B, int P);
+
+/* Depth-camera input (reference use_depth: backbone.py:115-134, detr_vae.py:188-202, 359-361, transformer.py:64-86): one
+ * FrozenBN ResNet18 per depth camera whose conv1 is Conv2d(1, w, 7, 2, 3) (depth_backbones.k.0.body.*, conv1.weight
+ * [w][1][7][7], everything else with the RGB backbone's shapes), the shared 1x1 convolution input_proj_depth ([D][8w][1][1] +
+ * bias) on every layer4 map, the maps concatenated along the width like the RGB ones and their tokens appended after the RGB
+ * tokens: [latent, proprio, rgb (h, cam, w) ..., depth (h, cam, w) ...], N = 2 + (num_cams + num_depth_cams) * fh * fw.  The
+ * depth tokens' position rows repeat the RGB tokens' (the same sine table); depth_pos_embed.weight [1][D] is a parameter of the
+ * state_dict that nothing reads (no gradient, skipped by the optimizer).  The reference's camera loop indexes the depth
+ * backbones by the RGB camera index, so num_depth_cams must equal actmi_config.num_cams.  In the handle the depth cameras are
+ * cameras num_cams .. num_cams + num_depth_cams - 1 of the trunk: the map debug tensors ("conv1", "maxpool", "layer1".."layer4")
+ * cover all of them, camera-major, and "src" / "memory" are [B][N][D] with the N above.  The depth stem forms fp32 products in
+ * every precision mode. */
+typedef struct actmi_depth_config {
+    uint32_t struct_size;      /* sizeof(actmi_depth_config), same guard as actmi_config */
+    int32_t num_depth_cams;    /* must equal actmi_config.num_cams */
+} actmi_depth_config;
+/* actmi_create_ex plus the depth cameras; depth == NULL is exactly actmi_create_ex.  num_depth_cams != cfg->num_cams, or a
+ * non-NULL pcd together with a non-NULL depth, is ACTMI_E_INVALID with a message. */
+int actmi_create_ex2(const actmi_config* cfg, const actmi_pcd_config* pcd, const actmi_depth_config* depth, actmi_handle* out);
+/* binds the depth batch that the NEXT actmi_forward_infer / _infer_vq / _forward_train reads (forward phase 2 reads none):
+ * depth [B][num_depth_cams][1][image_h][image_w] f32 device, un-normalised (the stem applies (d - 0.5) / 0.5, policy.py:275-286;
+ * values are expected in about [0, 1]); the pointer must stay valid until that forward (and, for training, until
+ * actmi_backward) has been enqueued.  A forward of a depth handle without a binding, or with another B, returns ACTMI_E_STATE
+ * before anything is launched; so does this call on a handle created without a depth config. */
+int actmi_set_depth(actmi_handle h, const float* depth, int B);
 int actmi_destroy(actmi_handle h);
 const char* actmi_last_error(actmi_handle h);   /* h may be NULL: last error of a failed create */
 
@@ -357,6 +382,11 @@ int actmi_op_maxpool3x3s2(const float* in_nhwc, float* out_nhwc, int nimg, int H
 int actmi_op_conv1(const void* image, int image_fmt, const float* w_oihw, const float* scale, const float* bias,
                    float* out, float* workspace /* >= C*Cout*148 + 768 floats */, int B, int C, int H, int W, int Cout,
                    int prec /* ACTMI_PREC_*, 0 = environment / native fp32 */, void* stream);
+/* depth stem (one launch): depth f32 [B][Cd][1][H][W] un-normalised, w the torch OIHW [Cd][Cout][1][7][7] weight, scale / bias
+ * [Cd][Cout] the folded FrozenBN; out camera-major NHWC [..][B][Ho][Wo][Cout], depth camera k written as camera out_cam0 + k.
+ * Cout a multiple of 4, <= 64; out 16-byte aligned.  fp32 products. */
+int actmi_op_conv1_depth(const float* depth, const float* w_oihw, const float* scale, const float* bias, float* out, int B,
+                         int Cd, int H, int W, int Cout, int out_cam0, void* stream);
 /* The same stem for callers that keep its prepared weights (and may want it without the ACT path's ImageNet normalisation or
  * ReLU: the DiffusionPolicy trunk applies GroupNorm between the convolution and the ReLU and feeds x / 255 un-normalised,
  * policy.py:150-170): actmi_op_conv1_prepare fills `workspace` (>= actmi_op_conv1_workspace_floats(C, Cout) floats) once --
@@ -514,7 +544,9 @@ const char* actmi_op_last_error(void);
 /* intermediate activations of the last forward (parity tests): name in {"conv1","maxpool","layer1".."layer4",
  * "src","memory","hs"}; camera-major NHWC for the maps, [B][N][D] for tokens.  A point-cloud handle adds "pcd_feat" [B][O]
  * (the pooled PointNet features) and "pcd_argmax" [B][O] (int32 bits: the winning point of every column), and after actmi_backward
- * "pcd_dtoken" [B][D], the gradient that reached the point-cloud token. */
+ * "pcd_dtoken" [B][D], the gradient that reached the point-cloud token.  On a depth handle (actmi_create_ex2) the map names
+ * cover all num_cams + num_depth_cams cameras, camera-major with the depth cameras last, and "src" / "memory" are [B][N][D] with
+ * N = 2 + (num_cams + num_depth_cams) * fh * fw. */
 int actmi_debug_tensor(actmi_handle h, const char* name, const float** dev_ptr, int64_t* numel);
 /* debug: make the next forwards return right after the named stage ("" = run everything); the maps of the
  * trunk live in rotating buffers, so a stage is only readable when the forward stopped there. */
