@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -25,7 +26,7 @@ static constexpr float W16_SCALE = 256.f;
 struct ConvLayer {
     std::string name, bn;
     int cin, cout, k, stride, pad, H, W, Ho, Wo;
-    int K = 0;
+    int K = 0;                // contraction length k * k * cin
     float* w = nullptr;       // [cam][cout][K], K index (r,s,c)
     float* w16 = nullptr;     // the same, fp16-split (f16x3 GEMM), built with w16_scale
     float w16_scale = W16_SCALE;
@@ -49,6 +50,55 @@ struct ConvLayer {
     bool direct = false;
 };
 
+struct Block { int c1, c2, ds; };      // one BasicBlock of the trunk: indices into actmi_ctx::convs (ds = -1: no downsample branch)
+inline int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
+
+// layer1 .. layer4 of a ResNet18 of width w0 on an H x W pooled map: the convolutions in state_dict order and the blocks that
+// own them.  The one place that knows which blocks carry a downsample branch (torchvision resnet.py: _make_layer)
+inline void build_trunk_tables(int w0, int H, int W, std::vector<ConvLayer>* convs, std::vector<Block>* blocks) {
+    int cin = w0;
+    for (int li = 1; li <= 4; ++li) {
+        const int cout = w0 << (li - 1);
+        for (int bi = 0; bi < 2; ++bi) {
+            const bool down = (bi == 0 && li > 1);
+            const int s = down ? 2 : 1, n = (int)convs->size();
+            const std::string bp = "layer" + std::to_string(li) + "." + std::to_string(bi) + ".";
+            ConvLayer c1{bp + "conv1", bp + "bn1.", cin, cout, 3, s, 1, H, W, conv_out(H, 3, s, 1), conv_out(W, 3, s, 1), 9 * cin};
+            convs->push_back(c1);
+            convs->push_back(ConvLayer{bp + "conv2", bp + "bn2.", cout, cout, 3, 1, 1, c1.Ho, c1.Wo, c1.Ho, c1.Wo, 9 * cout});
+            if (down) convs->push_back(ConvLayer{bp + "downsample.0", bp + "downsample.1.", cin, cout, 1, s, 0, H, W, c1.Ho, c1.Wo, cin});
+            blocks->push_back(Block{n, n + 1, down ? n + 2 : -1});
+            cin = cout; H = c1.Ho; W = c1.Wo;
+        }
+    }
+    for (auto& cl : *convs) cl.direct = cl.k == 3 && cl.stride == 1 && cl.pad == 1 && cl.cin == 64 && cl.cout == 64;
+}
+
+// One group of trunk cameras: the RGB cameras and, on a depth handle, the depth cameras behind them (detr_vae.py:188-202).
+// Maps, packed weights and packed gradients are camera-major, so a group is a camera range and a block of token rows
+struct CamGroup {
+    int c0, n;                          // first trunk camera, number of cameras
+    bool depth;                         // depth_backbones.* / input_proj_depth and the 1-channel stem; else backbones.* / input_proj
+    int stem_cin, token0;               // input channels of the stem (3 / 1); token row at which the group's tokens start
+    int64_t cam_stride = 0;             // arena distance between same-named parameters of the group's consecutive cameras
+    float *ip_w = nullptr, *ip_b = nullptr;     // the group's input_proj (detr_vae.py:184, 196-198)
+    float ip_a_scale = 1.f;             // activation pre-scale of that projection's operand (like ConvLayer::a_scale)
+    std::string prefix(int k) const { return (depth ? "depth_backbones." : "backbones.") + std::to_string(k) + ".0.body."; }
+    int64_t row0(int B, int P) const { return (int64_t)c0 * B * P; }            // first feature row ([cam][B][P] rows)
+    int64_t woff(int cout, int K) const { return (int64_t)c0 * cout * K; }      // into a layer's [cam][cout][K] weights / gradients
+};
+// the groups of a handle with C RGB and Cd depth cameras, n_extra tokens in front of the image tokens, P tokens per camera
+inline std::vector<CamGroup> build_cam_groups(int C, int Cd, int n_extra, int P) {
+    std::vector<CamGroup> g{{0, C, false, 3, n_extra}};
+    if (Cd) g.push_back({C, Cd, true, 1, n_extra + C * P});
+    return g;
+}
+// the cameras of [a, a + na) that belong to group g: {first camera, count}, count 0 when there are none
+inline std::pair<int, int> cam_overlap(const CamGroup& g, int a, int na) {
+    const int p0 = std::max(a, g.c0);
+    return {p0, std::max(0, std::min(a + na, g.c0 + g.n) - p0)};
+}
+
 struct MhaW { float *in_w, *in_b, *out_w, *out_b; };
 struct EncW { MhaW attn; float *l1w, *l1b, *l2w, *l2b, *n1w, *n1b, *n2w, *n2b; };
 struct DecW { MhaW self_attn, cross; float *l1w, *l1b, *l2w, *l2b, *n1w, *n1b, *n2w, *n2b, *n3w, *n3b; };
@@ -57,7 +107,7 @@ struct DbgView { const float* ptr; int64_t numel; };
 
 // saved activations of one encoder layer (training)
 struct EncSave { float *x_in, *QKV, *lse, *ATT, *Y1, *X1, *Hb, *Y2; };
-struct BlockSave { int c1, c2, ds; float *y1, *out; };
+struct BlockSave { float *y1, *out; };      // the saved maps of one BasicBlock (training), indexed like actmi_ctx::blocks
 
 struct TrainState {
     int B = 0, fmt = 0;
@@ -68,7 +118,7 @@ struct TrainState {
     // backbone
     float *xn4 = nullptr, *pool = nullptr, *g_act1 = nullptr, *gbuf[4] = {nullptr, nullptr, nullptr, nullptr};
     float* conv1_gw = nullptr;
-    std::vector<BlockSave> blocks;
+    std::vector<BlockSave> saves;
     std::vector<float*> conv_gw, conv_wd;
     std::vector<float*> conv_wd16;                 // layer1 (64 -> 64, 3x3 / s1): split image of the flipped data-gradient weights, else NULL
     // transformer
@@ -132,7 +182,7 @@ struct actmi_ctx {
     int Cd = 0, Ct = 0;
     const float* depth_img = nullptr;                      // batch bound for the next forward (actmi_set_depth), then cleared
     int depth_B = 0;
-    float ip_d_a_scale = 1.f;                              // activation pre-scale of input_proj_depth's operand (ip_a_scale's twin)
+    std::vector<CamGroup> cam_groups;                      // RGB group, then the depth group (engine_create)
     int device = 0;                    // HIP device the handle was created on (all its memory lives there)
     std::string err;
     std::vector<Param> params;
@@ -173,7 +223,6 @@ struct actmi_ctx {
     int policy_mult = 1;               // split-K policy counts the tiles of the WHOLE camera set while a half is being launched
     bool act_calib = true;             // activation pre-scales measured at finalize (ACTMI_ACT_CALIB=0: off)
     bool calibrating = false;          // engine_backbone is running the calibration forward
-    float ip_a_scale = 1.f;            // the same for input_proj's operand (the layer4 maps)
     float* act_scale_dev = nullptr;    // device copies [convs.size() + 1] for the kernels that take a device scale (conv3.hip)
     int64_t ptotal = 0;
     bool finalized = false;
@@ -181,6 +230,7 @@ struct actmi_ctx {
     int H1, W1, H2, W2, fh, fw, P_, N;
     // prepared weights
     std::vector<ConvLayer> convs;
+    std::vector<Block> blocks;
     float *conv1_w = nullptr, *conv1_scale = nullptr, *conv1_bias = nullptr, *lut = nullptr;
     unsigned char* conv1_wimg = nullptr;   // f16x3: conv1's LDS weight image per camera (launch_conv1_wimg), rebuilt with the weights
     float *pos_tokens = nullptr, *dec_t1 = nullptr, *dec_q = nullptr;
@@ -242,8 +292,6 @@ inline int engine_prec(const actmi_ctx* ctx) { return ctx->prec_override ? ctx->
 int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, const actmi_depth_config* depth, actmi_ctx** out);
 // the depth batch of this forward: checks the binding of a depth handle against B (ACTMI_E_STATE with a message) and consumes it
 int engine_take_depth(actmi_ctx* ctx, int B, const float** depth);
-// state_dict prefix of trunk camera cam: "backbones.k.0.body." for cam < C, "depth_backbones.(cam - C).0.body." behind them
-std::string trunk_cam_prefix(const actmi_ctx* ctx, int cam);
 // the depth stem of B samples into cameras C.. of ctx->act1
 int engine_depth_stem(actmi_ctx* ctx, const float* depth, int B, hipStream_t st);
 // the clouds of this forward: checks the binding of a point-cloud handle against B (ACTMI_E_STATE with a message) and consumes it
@@ -268,6 +316,8 @@ int ctx_gemm(actmi_ctx* ctx, GemmArgs a, hipStream_t st, int ws_half = -1, LnFus
 int gemm_slices(actmi_ctx* ctx, const GemmArgs& a, int S, float* ws, hipStream_t st, LnFuse* ln = nullptr);
 
 // ---- launch descriptors shared by the inference forward, the training step and the op entry points (engine.hip)
+// all fields zero, one group
+GemmArgs gemm_args0();
 // y[M][N] = A[M][K] W[N][K]^T + bias
 GemmArgs linear_args(const float* A, int64_t lda, int M, int K, const float* W, int N, const float* bias, float* C, int64_t ldc);
 // one trunk convolution over the cameras [c0, c0 + nc) (in / out / res point at camera c0's camera-major NHWC map): the
@@ -289,10 +339,6 @@ AttnArgs cross_attn_args(const actmi_ctx* ctx, const float* q, bool per_sample_q
 // u8 -> float table [3][256] of the stem: x = float(v / 255.0 in f64) (imitate_episodes.py:212), then (x - mean) / std in f32
 // (policy.py:268-272) when normalize, else x alone
 void u8_lut(float* lut, bool normalize);
-// arena distance between same-named parameters of consecutive backbones (one launch per layer covers all cameras), and the
-// same for the depth backbones (uniform inside each of the two ranges)
-int64_t backbone_cam_stride(actmi_ctx* ctx);
-int64_t depth_cam_stride(actmi_ctx* ctx);
 // precision of the GEMMs issued while a training call is running (restored on every exit path)
 struct PrecScope {
     actmi_ctx* c;

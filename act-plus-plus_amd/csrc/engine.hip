@@ -14,8 +14,6 @@ namespace {
 
 thread_local std::string g_create_error;
 
-int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
-
 void add_param(actmi_ctx* c, const std::string& key, std::vector<int64_t> shape, bool is_buffer) {
     Param p;
     p.key = key;
@@ -84,33 +82,25 @@ void build_spec(actmi_ctx* c) {
     add_param(c, "query_embed.weight", {Q, D}, false);
     add_param(c, "input_proj.weight", {D, 8 * w0, 1, 1}, false);
     add_param(c, "input_proj.bias", {D}, false);
-    auto add_backbone = [&](const std::string& p, int in_ch) {
-        add_param(c, p + "conv1.weight", {w0, in_ch, 7, 7}, false);
-        add_fbn(c, p + "bn1.", w0);
-        int cin = w0;
-        for (int li = 1; li <= 4; ++li) {
-            const int cout = w0 << (li - 1);
-            for (int bi = 0; bi < 2; ++bi) {
-                std::string bp = p + "layer" + std::to_string(li) + "." + std::to_string(bi) + ".";
-                add_param(c, bp + "conv1.weight", {cout, cin, 3, 3}, false);
-                add_fbn(c, bp + "bn1.", cout);
-                add_param(c, bp + "conv2.weight", {cout, cout, 3, 3}, false);
-                add_fbn(c, bp + "bn2.", cout);
-                if (bi == 0 && li > 1) {
-                    add_param(c, bp + "downsample.0.weight", {cout, cin, 1, 1}, false);
-                    add_fbn(c, bp + "downsample.1.", cout);
-                }
-                cin = cout;
+    // the backbones of one camera group: stem, then the trunk's convolutions in the order of ctx->convs, each with its FrozenBN
+    auto add_backbones = [&](const CamGroup& grp) {
+        for (int k = 0; k < grp.n; ++k) {
+            const std::string p = grp.prefix(k);
+            add_param(c, p + "conv1.weight", {w0, grp.stem_cin, 7, 7}, false);
+            add_fbn(c, p + "bn1.", w0);
+            for (const ConvLayer& cl : c->convs) {
+                add_param(c, p + cl.name + ".weight", {cl.cout, cl.cin, cl.k, cl.k}, false);
+                add_fbn(c, p + cl.bn, cl.cout);
             }
         }
     };
-    for (int cam = 0; cam < g.num_cams; ++cam) add_backbone("backbones." + std::to_string(cam) + ".0.body.", 3);
+    add_backbones(c->cam_groups[0]);
     add_param(c, "input_proj_robot_state.weight", {D, S}, false);
     add_param(c, "input_proj_robot_state.bias", {D}, false);
     if (c->Cd) {                                        // detr_vae.py:359-361, backbone.py:115-134
         add_param(c, "input_proj_depth.weight", {D, 8 * w0, 1, 1}, false);
         add_param(c, "input_proj_depth.bias", {D}, false);
-        for (int cam = 0; cam < c->Cd; ++cam) add_backbone("depth_backbones." + std::to_string(cam) + ".0.body.", 1);
+        add_backbones(c->cam_groups[1]);
     }
     if (c->has_pcd) {                                   // detr_vae.py:64-65
         add_param(c, "input_proj_pointnet.weight", {D, c->pcd.output_dim}, false);
@@ -282,11 +272,12 @@ int engine_calibrate_weight_scales(actmi_ctx* ctx, hipStream_t st) {
     };
     ctx->conv1_wscale = 4096.f;
     for (auto& cl : ctx->convs) cl.w16_scale = 4096.f;
-    for (int cam = 0; cam < ctx->Ct; ++cam) {
-        const std::string p = trunk_cam_prefix(ctx, cam);
-        if (cam < ctx->cfg.num_cams) ctx->conv1_wscale = std::min(ctx->conv1_wscale, key_scale(p + "conv1.weight"));
-        for (auto& cl : ctx->convs) cl.w16_scale = std::min(cl.w16_scale, key_scale(p + cl.name + ".weight"));
-    }
+    for (const CamGroup& g : ctx->cam_groups)
+        for (int k = 0; k < g.n; ++k) {
+            const std::string p = g.prefix(k);
+            if (!g.depth) ctx->conv1_wscale = std::min(ctx->conv1_wscale, key_scale(p + "conv1.weight"));
+            for (auto& cl : ctx->convs) cl.w16_scale = std::min(cl.w16_scale, key_scale(p + cl.name + ".weight"));
+        }
     // weights split on the fly in the backward GEMMs share one static scale
     ctx->bwd_wscale = W16_SCALE;
     while (gmax * ctx->bwd_wscale >= 16384.f && ctx->bwd_wscale > 1.f / 65536.f) ctx->bwd_wscale *= 0.5f;
@@ -332,6 +323,11 @@ void resolve_layers(actmi_ctx* c) {
         d.n3w = c->P(p + "norm3.weight"); d.n3b = c->P(p + "norm3.bias");
         c->dec.push_back(d);
     }
+    for (CamGroup& grp : c->cam_groups) {
+        grp.cam_stride = c->P(grp.prefix(grp.n > 1 ? 1 : 0) + "conv1.weight") - c->P(grp.prefix(0) + "conv1.weight");
+        grp.ip_w = c->P(grp.depth ? "input_proj_depth.weight" : "input_proj.weight");
+        grp.ip_b = c->P(grp.depth ? "input_proj_depth.bias" : "input_proj.bias");
+    }
     if (c->has_pcd) {
         const std::string p = "pcl_backbone.pointnet._mlp.";
         c->pcdw = PcdW{c->P(p + "0.weight"), c->P(p + "0.bias"), c->P(p + "3.weight"), c->P(p + "3.bias"),
@@ -342,12 +338,17 @@ void resolve_layers(actmi_ctx* c) {
 
 }  // namespace
 
-GemmArgs linear_args(const float* A, int64_t lda, int M, int K, const float* W, int N, const float* bias, float* C,
-                     int64_t ldc) {
+GemmArgs gemm_args0() {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.M = M; a.K = K; a.N = N; a.Bw = W; a.ldb = K; a.bias = bias; a.C = C; a.ldc = ldc;
     a.groups = 1;
+    return a;
+}
+
+GemmArgs linear_args(const float* A, int64_t lda, int M, int K, const float* W, int N, const float* bias, float* C,
+                     int64_t ldc) {
+    GemmArgs a = gemm_args0();
+    a.A = A; a.lda = lda; a.M = M; a.K = K; a.N = N; a.Bw = W; a.ldb = K; a.bias = bias; a.C = C; a.ldc = ldc;
     return a;
 }
 
@@ -356,8 +357,7 @@ GemmArgs linear_args(const float* A, int64_t lda, int M, int K, const float* W, 
 // under f16x3 the split image w16 with its scale and K order, else the plain matrix w
 static GemmArgs conv_args(const actmi_ctx* ctx, const ConvLayer& cl, int B, int c0, int nc, const float* in, float* out, int K,
                           const float* w, const float* w16, float w16_scale) {
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
+    GemmArgs a = gemm_args0();
     a.mode = 1;
     a.A = in; a.H = cl.H; a.W = cl.W; a.Cin = cl.cin; a.KH = a.KW = cl.k; a.stride = cl.stride; a.pad = cl.pad;
     a.Ho = cl.Ho; a.Wo = cl.Wo; a.img_stride = (int64_t)cl.H * cl.W * cl.cin;
@@ -444,21 +444,6 @@ void u8_lut(float* lut, bool normalize) {
         }
 }
 
-int64_t backbone_cam_stride(actmi_ctx* ctx) {
-    const std::string p1 = "backbones." + std::to_string(ctx->cfg.num_cams > 1 ? 1 : 0) + ".0.body.";
-    return ctx->P(p1 + "conv1.weight") - ctx->P("backbones.0.0.body.conv1.weight");
-}
-
-int64_t depth_cam_stride(actmi_ctx* ctx) {
-    const std::string p1 = "depth_backbones." + std::to_string(ctx->Cd > 1 ? 1 : 0) + ".0.body.";
-    return ctx->P(p1 + "conv1.weight") - ctx->P("depth_backbones.0.0.body.conv1.weight");
-}
-
-std::string trunk_cam_prefix(const actmi_ctx* ctx, int cam) {
-    const int C = ctx->cfg.num_cams;
-    return cam < C ? "backbones." + std::to_string(cam) + ".0.body." : "depth_backbones." + std::to_string(cam - C) + ".0.body.";
-}
-
 float* actmi_ctx::P(const std::string& key) {
     auto it = index.find(key);
     if (it == index.end()) return nullptr;
@@ -525,37 +510,16 @@ int create_device_state(actmi_ctx* ctx) {
     }
     resolve_layers(ctx);
 
-    // ---- conv layer table + packed weights
+    // ---- packed weights of the conv layer table (ctx->convs, built by engine_create)
     const int C = g.num_cams, Ct = ctx->Ct, w0 = g.base_width;
     {
-        int cin = w0, H = ctx->H2, W = ctx->W2;
-        for (int li = 1; li <= 4; ++li) {
-            const int cout = w0 << (li - 1);
-            for (int bi = 0; bi < 2; ++bi) {
-                const int s = (bi == 0 && li > 1) ? 2 : 1;
-                std::string bp = "layer" + std::to_string(li) + "." + std::to_string(bi) + ".";
-                ConvLayer c1{bp + "conv1", bp + "bn1.", cin, cout, 3, s, 1, H, W, conv_out(H, 3, s, 1), conv_out(W, 3, s, 1)};
-                ConvLayer c2{bp + "conv2", bp + "bn2.", cout, cout, 3, 1, 1, c1.Ho, c1.Wo, c1.Ho, c1.Wo};
-                ctx->convs.push_back(c1);
-                ctx->convs.push_back(c2);
-                if (bi == 0 && li > 1) {
-                    ConvLayer ds{bp + "downsample.0", bp + "downsample.1.", cin, cout, 1, s, 0, H, W, c1.Ho, c1.Wo};
-                    ctx->convs.push_back(ds);
-                }
-                cin = cout; H = c1.Ho; W = c1.Wo;
-            }
-        }
-        for (auto& cl : ctx->convs) {
-            cl.K = cl.k * cl.k * cl.cin;
-            cl.direct = cl.k == 3 && cl.stride == 1 && cl.pad == 1 && cl.cin == 64 && cl.cout == 64;
-        }
         // conv2 of every block with a downsample branch carries the branch in its own contraction (inference, f16x3)
-        for (size_t i = 0; i + 2 < ctx->convs.size(); ++i) {
-            ConvLayer& k2 = ctx->convs[i + 1];
-            const ConvLayer& ds = ctx->convs[i + 2];
-            if (ds.k == 1 && ds.stride == 2 && k2.k == 3 && k2.stride == 1 && ds.cout == k2.cout && ds.Ho == k2.Ho && ds.Wo == k2.Wo &&
-                ds.name.find("downsample") != std::string::npos && (k2.cin % 32) == 0 && (ds.cin % 32) == 0) {
-                k2.ds_index = (int)i + 2;
+        for (const Block& bk : ctx->blocks) {
+            if (bk.ds < 0) continue;
+            ConvLayer& k2 = ctx->convs[bk.c2];
+            const ConvLayer& ds = ctx->convs[bk.ds];
+            if ((k2.cin % 32) == 0 && (ds.cin % 32) == 0) {
+                k2.ds_index = bk.ds;
                 k2.Kx = ds.cin;
                 ALLOC(k2.wf, (int64_t)Ct * k2.cout * (k2.K + k2.Kx)); ALLOC(k2.wf16, (int64_t)Ct * k2.cout * (k2.K + k2.Kx));
                 ALLOC(k2.bias_f, (int64_t)Ct * k2.cout);
@@ -613,22 +577,17 @@ int create_device_state(actmi_ctx* ctx) {
 int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, const actmi_depth_config* depth, actmi_ctx** out) {
     if (!cfg || !out) { g_create_error = "null argument"; return ACTMI_E_INVALID; }
     const actmi_config& g = *cfg;
-    if (pcd && pcd->struct_size != (uint32_t)sizeof(actmi_pcd_config)) {
-        g_create_error = "actmi_pcd_config.struct_size is " + std::to_string(pcd->struct_size) + ", this library expects " +
-                         std::to_string(sizeof(actmi_pcd_config)) + " (binding built against a different include/actmi.h)";
+    // the first field is readable whatever the caller's struct looks like; nothing else is trusted before this check
+    auto size_ok = [](const char* name, uint32_t got, size_t want) {
+        if (got != (uint32_t)want)
+            g_create_error = std::string(name) + ".struct_size is " + std::to_string(got) + ", this library expects " +
+                             std::to_string(want) + " (binding built against a different include/actmi.h)";
+        return got == (uint32_t)want;
+    };
+    if ((pcd && !size_ok("actmi_pcd_config", pcd->struct_size, sizeof(actmi_pcd_config))) ||
+        (depth && !size_ok("actmi_depth_config", depth->struct_size, sizeof(actmi_depth_config))) ||
+        !size_ok("actmi_config", g.struct_size, sizeof(actmi_config)))
         return ACTMI_E_INVALID;
-    }
-    if (depth && depth->struct_size != (uint32_t)sizeof(actmi_depth_config)) {
-        g_create_error = "actmi_depth_config.struct_size is " + std::to_string(depth->struct_size) + ", this library expects " +
-                         std::to_string(sizeof(actmi_depth_config)) + " (binding built against a different include/actmi.h)";
-        return ACTMI_E_INVALID;
-    }
-    if (g.struct_size != (uint32_t)sizeof(actmi_config)) {
-        // the first field is readable whatever the caller's struct looks like; nothing else is trusted before this check
-        g_create_error = "actmi_config.struct_size is " + std::to_string(g.struct_size) + ", this library expects " +
-                         std::to_string(sizeof(actmi_config)) + " (binding built against a different include/actmi.h)";
-        return ACTMI_E_INVALID;
-    }
     if (g.num_cams < 1 || g.max_batch < 1 || g.hidden_dim % g.nheads || (g.hidden_dim & 3) || (g.dim_feedforward & 3) ||
         (g.base_width & 3) || g.base_width > 64 || g.enc_layers < 1 || g.dec_layers < 1) {
         g_create_error = "unsupported configuration";
@@ -662,8 +621,6 @@ int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, const ac
     ctx->Ct = g.num_cams + ctx->Cd;
     if (pcd) { ctx->has_pcd = true; ctx->pcd = *pcd; ctx->n_extra = 3; }
     if (hipGetDevice(&ctx->device) != hipSuccess) { g_create_error = "hipGetDevice failed"; delete ctx; return ACTMI_E_LAUNCH; }
-    ctx->ptotal = 0;
-    build_spec(ctx);
     // geometry
     ctx->H1 = conv_out(g.image_h, 7, 2, 3); ctx->W1 = conv_out(g.image_w, 7, 2, 3);
     ctx->H2 = conv_out(ctx->H1, 3, 2, 1); ctx->W2 = conv_out(ctx->W1, 3, 2, 1);
@@ -673,6 +630,11 @@ int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, const ac
     ctx->P_ = h * w;
     ctx->N = ctx->n_extra + ctx->Ct * h * w;
     if (h < 1 || w < 1) { g_create_error = "image too small"; delete ctx; return ACTMI_E_INVALID; }
+    // the model as the host code sees it: camera groups, trunk layers and blocks; then the state_dict spec that names them
+    ctx->cam_groups = build_cam_groups(g.num_cams, ctx->Cd, ctx->n_extra, ctx->P_);
+    build_trunk_tables(g.base_width, ctx->H2, ctx->W2, &ctx->convs, &ctx->blocks);
+    ctx->ptotal = 0;
+    build_spec(ctx);
 
     read_switches(ctx);
     const int rc = create_device_state(ctx);
@@ -720,18 +682,18 @@ static int split_conv_image(actmi_ctx* ctx, const ConvLayer& cl, const float* w,
 // position table per token: rows 0 .. n_extra-1 = additional_pos_embed (transformer.py:91-92); rows n_extra.. =
 // PositionEmbeddingSine(normalize=True) (position_encoding.py:30-52), identical for every camera
 static int build_pos_tokens(actmi_ctx* ctx) {
-    const int C = ctx->cfg.num_cams, D = ctx->cfg.hidden_dim, fh = ctx->fh, fw = ctx->fw, N = ctx->N, npf = D / 2;
+    const int D = ctx->cfg.hidden_dim, fh = ctx->fh, fw = ctx->fw, N = ctx->N, npf = D / 2;
     std::vector<float> pos((size_t)N * D, 0.f);
     HIPCHK(hipMemcpy(pos.data(), ctx->P("additional_pos_embed.weight"), (size_t)ctx->n_extra * D * sizeof(float), hipMemcpyDeviceToHost));
     const float eps = 1e-6f, scale = (float)(2.0 * M_PI);
     std::vector<float> dim_t(npf);
     for (int k = 0; k < npf; ++k) dim_t[k] = powf(10000.f, (2.f * (float)(k / 2)) / (float)npf);
     // (the depth tokens behind the RGB ones carry the same table: transformer.py:64-86 adds pos to both)
-    for (int grp = 0; grp < (ctx->Cd ? 2 : 1); ++grp)
+    for (const CamGroup& g : ctx->cam_groups)
     for (int hh = 0; hh < fh; ++hh)
-        for (int cam = 0; cam < (grp ? ctx->Cd : C); ++cam)
+        for (int cam = 0; cam < g.n; ++cam)
             for (int ww = 0; ww < fw; ++ww) {
-                float* row = &pos[(size_t)(ctx->n_extra + grp * C * fh * fw + hh * (fw * (grp ? ctx->Cd : C)) + cam * fw + ww) * D];
+                float* row = &pos[(size_t)(g.token0 + hh * (fw * g.n) + cam * fw + ww) * D];
                 const float y = (float)(hh + 1) / ((float)fh + eps) * scale;
                 const float x = (float)(ww + 1) / ((float)fw + eps) * scale;
                 for (int k = 0; k < npf; ++k) {
@@ -748,27 +710,21 @@ static int build_pos_tokens(actmi_ctx* ctx) {
 int engine_prepare_weights(actmi_ctx* ctx, hipStream_t st, bool after_step) {
     const actmi_config& g = ctx->cfg;
     const int C = g.num_cams, w0 = g.base_width, D = g.hidden_dim, Q = g.num_queries;
-    // conv weights OIHW -> [cam][O][(r,s,c)]: one launch per layer over the cameras (same-named parameters of consecutive
-    // backbones are a constant stride apart in the arena)
-    {
-        const std::string p0 = "backbones.0.0.body.";
-        const int64_t cam_stride = backbone_cam_stride(ctx);
-        CHK(launch_repack_conv_w(ctx->P(p0 + "conv1.weight"), ctx->conv1_w, C, w0, 3, 7, 7, cam_stride, (int64_t)w0 * 148, 148, st));
+    // conv weights OIHW -> [cam][O][(r,s,c)]: one launch per layer and camera group (same-named parameters of a group's
+    // consecutive backbones are a constant stride apart in the arena)
+    for (const CamGroup& grp : ctx->cam_groups) {
+        const std::string p0 = grp.prefix(0);
+        if (!grp.depth)                     // (the depth stem's conv1 is read in place by its kernel)
+            CHK(launch_repack_conv_w(ctx->P(p0 + "conv1.weight"), ctx->conv1_w, grp.n, w0, 3, 7, 7, grp.cam_stride, (int64_t)w0 * 148, 148, st));
         for (auto& cl : ctx->convs)
-            CHK(launch_repack_conv_w(ctx->P(p0 + cl.name + ".weight"), cl.w, C, cl.cout, cl.cin, cl.k, cl.k, cam_stride,
-                                     (int64_t)cl.cout * cl.K, cl.K, st));
-        if (ctx->Cd) {                      // the depth backbones fill cameras C.. (their conv1 is read in place by its kernel)
-            const std::string d0 = "depth_backbones.0.0.body.";
-            const int64_t dstride = depth_cam_stride(ctx);
-            for (auto& cl : ctx->convs)
-                CHK(launch_repack_conv_w(ctx->P(d0 + cl.name + ".weight"), cl.w + (int64_t)C * cl.cout * cl.K, ctx->Cd, cl.cout, cl.cin,
-                                         cl.k, cl.k, dstride, (int64_t)cl.cout * cl.K, cl.K, st));
-        }
+            CHK(launch_repack_conv_w(ctx->P(p0 + cl.name + ".weight"), cl.w + grp.woff(cl.cout, cl.K), grp.n, cl.cout, cl.cin, cl.k, cl.k,
+                                     grp.cam_stride, (int64_t)cl.cout * cl.K, cl.K, st));
     }
     // FrozenBN -> scale / bias: buffers the optimizer never touches (reference backbone.py:21-57), so not redone after a step
     if (!after_step)
-        for (int cam = 0; cam < ctx->Ct; ++cam) {
-            std::string p = trunk_cam_prefix(ctx, cam);
+        for (const CamGroup& grp : ctx->cam_groups)
+        for (int cam = grp.c0; cam < grp.c0 + grp.n; ++cam) {
+            const std::string p = grp.prefix(cam - grp.c0);
             CHK(launch_bn_fold(ctx->P(p + "bn1.weight"), ctx->P(p + "bn1.bias"), ctx->P(p + "bn1.running_mean"),
                                ctx->P(p + "bn1.running_var"), ctx->conv1_scale + cam * w0, ctx->conv1_bias + cam * w0, w0, st));
             for (auto& cl : ctx->convs)
@@ -889,7 +845,7 @@ int engine_measure_act_scale(actmi_ctx* ctx, const float* x, int64_t rows, int c
 
 int engine_calibrate_activations(actmi_ctx* ctx, hipStream_t st) {
     for (auto& cl : ctx->convs) cl.a_scale = 1.f;
-    ctx->ip_a_scale = ctx->ip_d_a_scale = 1.f;
+    for (CamGroup& grp : ctx->cam_groups) grp.ip_a_scale = 1.f;
     if (ctx->gemm_prec != ACTMI_PREC_F16X3 || !ctx->act_calib) return 0;
     const actmi_config& g = ctx->cfg;
     const size_t nbytes = (size_t)g.num_cams * g.image_h * g.image_w * 3;
@@ -959,14 +915,12 @@ static int run_branches(actmi_ctx* ctx, int nb, hipStream_t st, Body body) {
     return 0;
 }
 
-// feature row m = ((cam*B + b)*fh + h)*fw + w of the trunk's layer4 maps -> its token row: the RGB cameras first, the depth
-// cameras' tokens behind all of them (transformer.py:64-86)
+// feature row m = ((cam*B + b)*fh + h)*fw + w of the trunk's layer4 maps -> its token row: group by group, the depth cameras'
+// tokens behind all the RGB ones (transformer.py:64-86)
 int engine_build_rowmap(actmi_ctx* ctx, int B, hipStream_t st) {
     if (ctx->rowmap_B == B) return 0;
-    const int C = ctx->cfg.num_cams;
-    CHK(launch_build_rowmap(ctx->rowmap, B, C, ctx->fh, ctx->fw, ctx->N, ctx->n_extra, st));
-    if (ctx->Cd)
-        CHK(launch_build_rowmap(ctx->rowmap + (int64_t)C * B * ctx->P_, B, ctx->Cd, ctx->fh, ctx->fw, ctx->N, ctx->n_extra + C * ctx->P_, st));
+    for (const CamGroup& g : ctx->cam_groups)
+        CHK(launch_build_rowmap(ctx->rowmap + g.row0(B, ctx->P_), B, g.n, ctx->fh, ctx->fw, ctx->N, g.token0, st));
     ctx->rowmap_B = B;
     return 0;
 }
@@ -974,17 +928,18 @@ int engine_build_rowmap(actmi_ctx* ctx, int B, hipStream_t st) {
 // multi-camera ResNet18 trunk + input_proj -> token rows n_extra.. of X   (backbone.py:66-71, detr_vae.py:180-185)
 int engine_depth_stem(actmi_ctx* ctx, const float* depth, int B, hipStream_t st) {
     const actmi_config& g = ctx->cfg;
-    const int C = g.num_cams, w0 = g.base_width;
+    const int w0 = g.base_width;
+    const CamGroup& grp = ctx->cam_groups.back();          // (the caller checked that the handle has depth cameras)
     Conv1DepthArgs d;
-    d.depth = depth; d.w = ctx->P("depth_backbones.0.0.body.conv1.weight"); d.w_cam_stride = depth_cam_stride(ctx);
-    d.scale = ctx->conv1_scale + (int64_t)C * w0; d.bias = ctx->conv1_bias + (int64_t)C * w0; d.out = ctx->act1;
-    d.B = B; d.Cd = ctx->Cd; d.H = g.image_h; d.W = g.image_w; d.Ho = ctx->H1; d.Wo = ctx->W1; d.Cout = w0; d.out_cam0 = C;
+    d.depth = depth; d.w = ctx->P(grp.prefix(0) + "conv1.weight"); d.w_cam_stride = grp.cam_stride;
+    d.scale = ctx->conv1_scale + (int64_t)grp.c0 * w0; d.bias = ctx->conv1_bias + (int64_t)grp.c0 * w0; d.out = ctx->act1;
+    d.B = B; d.Cd = grp.n; d.H = g.image_h; d.W = g.image_w; d.Ho = ctx->H1; d.Wo = ctx->W1; d.Cout = w0; d.out_cam0 = grp.c0;
     return launch_conv1_depth(d, st, &ctx->err) == 0 ? 0 : ACTMI_E_LAUNCH;
 }
 
 int engine_backbone(actmi_ctx* ctx, const void* image, const float* depth, int fmt, int B, hipStream_t st) {
     const actmi_config& g = ctx->cfg;
-    const int Crgb = g.num_cams, C = ctx->Ct, w0 = g.base_width, D = g.hidden_dim;
+    const int C = ctx->Ct, w0 = g.base_width, D = g.hidden_dim;
     Conv1Args c1 = stem_args(ctx, image, fmt, B);
     // inference never needs conv1's own map: the stem emits the vertical half of the max pool (half the bytes) and a
     // row-wise pass finishes it.  Same maxima, so the result is bit-identical to conv1 -> 3x3 pool.
@@ -994,7 +949,7 @@ int engine_backbone(actmi_ctx* ctx, const void* image, const float* depth, int f
     // stem (conv1 + pool) of all cameras, ahead of the branches
     c1.vpool = vpool ? 1 : 0;
     CHK(launch_conv1(c1, st, &ctx->err));
-    if (ctx->Cd) CHK(engine_depth_stem(ctx, depth, B, st));                // cameras Crgb.. of the same map
+    if (ctx->Cd) CHK(engine_depth_stem(ctx, depth, B, st));                // the depth group's cameras of the same map
     if (vpool) CHK(launch_hpool(ctx->act1, ctx->buf[0], C * B * ctx->H2, ctx->W1, w0, ctx->W2, st));
     else CHK(launch_maxpool(ctx->act1, ctx->buf[0], C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st));
     ctx->dbg.clear();
@@ -1037,69 +992,64 @@ int engine_backbone(actmi_ctx* ctx, const void* image, const float* depth, int f
         auto run_conv = [&](ConvLayer& cl, const float* in, float* out, const float* res, int relu) -> int {
             return run_conv_on(cl, in, out, res, relu, ls, c0, nc, half);
         };
-        size_t ci = 0;
-        for (int li = 1; li <= 4; ++li) {
-            for (int bi = 0; bi < 2; ++bi) {
-                ConvLayer& k1 = ctx->convs[ci++];
-                ConvLayer& k2 = ctx->convs[ci++];
-                const bool has_ds = (bi == 0 && li > 1);
-                if (has_ds && k2.wf && ctx->gemm_prec == ACTMI_PREC_F16X3 && !ctx->calibrating && k2.a_scale == 1.f &&
-                    ctx->convs[k2.ds_index].a_scale == 1.f) {
-                    // the downsample branch rides in conv2's contraction (second source = the block input at stride 2):
-                    // two launches instead of three, and the branch's map is neither written nor read back
-                    ++ci;                                        // (the downsample layer's own entry)
-                    CHK(run_conv(k1, cur, s1, nullptr, 1));
-                    CHK(ctx_gemm(ctx, conv_fused_args(ctx, k2, B, c0, nc, s1, cur, s2), ls, half));
-                    std::swap(cur, s2);                          // x stays live until conv2 has read it: the output goes to s2
-                } else if (has_ds) {
-                    ConvLayer& ds = ctx->convs[ci++];
-                    if (fork_ds) {
-                        // the 1x1 / stride-2 downsample (23-50 us, HBM bound, few workgroups) only needs the block input: it
-                        // runs on a second stream beside the block's first 3x3 convolution (fork / join through events: in a
-                        // captured graph these are two parallel branches) and fills CUs that launch leaves idle
-                        HIPCHK(hipEventRecord(ctx->ev_fork, ls));
-                        HIPCHK(hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
-                        // from here the side stream is forked: join it whatever happens, then report the first error
-                        const int r1 = run_conv_on(ds, cur, s2, nullptr, 0, ctx->side_stream, c0, nc, half);
-                        const hipError_t e1 = hipEventRecord(ctx->ev_join, ctx->side_stream);
-                        const int r2 = r1 == 0 ? run_conv(k1, cur, s1, nullptr, 1) : 0;
-                        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(ls, ctx->ev_join, 0) : e1;
-                        CHK(r1);
-                        CHK(r2);
-                        HIPCHK(e1);
-                        HIPCHK(e2);
-                    } else {
-                        CHK(run_conv(k1, cur, s1, nullptr, 1));
-                        CHK(run_conv(ds, cur, s2, nullptr, 0));
-                    }
-                    CHK(run_conv(k2, s1, cur, s2, 1));       // x is dead: reuse its buffer for the block output
+        for (size_t bi = 0; bi < ctx->blocks.size(); ++bi) {
+            const Block& bk = ctx->blocks[bi];
+            ConvLayer& k1 = ctx->convs[bk.c1];
+            ConvLayer& k2 = ctx->convs[bk.c2];
+            const bool has_ds = bk.ds >= 0;
+            if (has_ds && k2.wf && ctx->gemm_prec == ACTMI_PREC_F16X3 && !ctx->calibrating && k2.a_scale == 1.f &&
+                ctx->convs[k2.ds_index].a_scale == 1.f) {
+                // the downsample branch rides in conv2's contraction (second source = the block input at stride 2):
+                // two launches instead of three, and the branch's map is neither written nor read back
+                CHK(run_conv(k1, cur, s1, nullptr, 1));
+                CHK(ctx_gemm(ctx, conv_fused_args(ctx, k2, B, c0, nc, s1, cur, s2), ls, half));
+                std::swap(cur, s2);                          // x stays live until conv2 has read it: the output goes to s2
+            } else if (has_ds) {
+                ConvLayer& ds = ctx->convs[bk.ds];
+                if (fork_ds) {
+                    // the 1x1 / stride-2 downsample (23-50 us, HBM bound, few workgroups) only needs the block input: it
+                    // runs on a second stream beside the block's first 3x3 convolution (fork / join through events: in a
+                    // captured graph these are two parallel branches) and fills CUs that launch leaves idle
+                    HIPCHK(hipEventRecord(ctx->ev_fork, ls));
+                    HIPCHK(hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
+                    // from here the side stream is forked: join it whatever happens, then report the first error
+                    const int r1 = run_conv_on(ds, cur, s2, nullptr, 0, ctx->side_stream, c0, nc, half);
+                    const hipError_t e1 = hipEventRecord(ctx->ev_join, ctx->side_stream);
+                    const int r2 = r1 == 0 ? run_conv(k1, cur, s1, nullptr, 1) : 0;
+                    const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(ls, ctx->ev_join, 0) : e1;
+                    CHK(r1);
+                    CHK(r2);
+                    HIPCHK(e1);
+                    HIPCHK(e2);
                 } else {
                     CHK(run_conv(k1, cur, s1, nullptr, 1));
-                    CHK(run_conv(k2, s1, s2, cur, 1));
-                    std::swap(cur, s2);
+                    CHK(run_conv(ds, cur, s2, nullptr, 0));
                 }
-                if (bi == 1 && c0 == 0) {
-                    const std::string nm = "layer" + std::to_string(li);
-                    ctx->dbg[nm] = {cur, (int64_t)C * B * k2.Ho * k2.Wo * k2.cout};
-                    if (ctx->stop_stage == nm) return 1;    // debug early-out: buffers rotate, views alias
-                }
+                CHK(run_conv(k2, s1, cur, s2, 1));       // x is dead: reuse its buffer for the block output
+            } else {
+                CHK(run_conv(k1, cur, s1, nullptr, 1));
+                CHK(run_conv(k2, s1, s2, cur, 1));
+                std::swap(cur, s2);
+            }
+            if ((bi & 1) && c0 == 0) {                    // the second of a layer's two blocks
+                const std::string nm = "layer" + std::to_string(bi / 2 + 1);
+                ctx->dbg[nm] = {cur, (int64_t)C * B * k2.Ho * k2.Wo * k2.cout};
+                if (ctx->stop_stage == nm) return 1;    // debug early-out: buffers rotate, views alias
             }
         }
-        // input_proj (1x1 convolution, detr_vae.py:184) of the range's layer4 maps, rows scattered to their tokens; the depth
-        // cameras of the range go through input_proj_depth (detr_vae.py:196-198), each projection with its own pre-scale
-        for (int part = 0; part < 2; ++part) {
-            const int p0 = part ? std::max(c0, Crgb) : c0, p1 = part ? c0 + nc : std::min(c0 + nc, Crgb);
-            if (p1 <= p0) continue;
+        // input_proj (1x1 convolution, detr_vae.py:184, 196-198) of the range's layer4 maps, rows scattered to their tokens: each
+        // camera group's part of the range through the group's own projection, with its own pre-scale
+        for (CamGroup& grp : ctx->cam_groups) {
+            const auto [p0, pn] = cam_overlap(grp, c0, nc);
+            if (pn == 0) continue;
             const float* maps = cur + (int64_t)(p0 - c0) * B * ctx->P_ * 8 * w0;
-            float& a_scale = part ? ctx->ip_d_a_scale : ctx->ip_a_scale;
-            GemmArgs ip = linear_args(maps, 8 * w0, (p1 - p0) * B * ctx->P_, 8 * w0, ctx->P(part ? "input_proj_depth.weight" : "input_proj.weight"),
-                                      D, ctx->P(part ? "input_proj_depth.bias" : "input_proj.bias"), ctx->X, D);
+            GemmArgs ip = linear_args(maps, 8 * w0, pn * B * ctx->P_, 8 * w0, grp.ip_w, D, grp.ip_b, ctx->X, D);
             ip.rowmap = ctx->rowmap + (int64_t)p0 * B * ctx->P_;
             if (ctx->calibrating) {
-                CHK(engine_measure_act_scale(ctx, maps, (int64_t)(p1 - p0) * B * ctx->P_, 8 * w0, ls, &a_scale));
+                CHK(engine_measure_act_scale(ctx, maps, (int64_t)pn * B * ctx->P_, 8 * w0, ls, &grp.ip_a_scale));
                 HIPCHK(hipStreamSynchronize(ls));
             }
-            if (ctx->gemm_prec == ACTMI_PREC_F16X3 && a_scale != 1.f) ip.a_scale = a_scale;
+            if (ctx->gemm_prec == ACTMI_PREC_F16X3 && grp.ip_a_scale != 1.f) ip.a_scale = grp.ip_a_scale;
             CHK(ctx_gemm(ctx, ip, ls, half));
         }
         return 0;

@@ -282,6 +282,33 @@ def test_depth_graph_replay_branches_and_small_batch():
         InferPipeline(two, MB)
 
 
+@pytest.mark.parametrize("ncam", [2, 3])
+def test_depth_src_is_bitwise_equal_with_and_without_camera_branches(ncam):
+    """The trunk's camera ranges against the RGB / depth camera groups: with the branches off ONE range [0, Ct) crosses the
+    group boundary and issues one projection per group; with ACTMI_BRANCHES=3 the ranges are [0,1) [1,2) [2,4) for 2 + 2
+    cameras (every range inside one group) and [0,2) [2,4) [4,6) for 3 + 3 (the middle range straddles the boundary at 3).
+    f32 products, so the split-K policy cannot differ between the modes: the token matrix must be the same bits."""
+    names = ["a", "b", "c"][:ncam]
+    cfg = tiny_config(camera_names=names, use_depth=True, depth_camera_names=list(names))
+    sd_np = _fixture("tiny_depth")[2] if ncam == 2 else W.generate_state_dict(cfg, seed=0)
+    B = 3
+    qpos, img, depth = _dev_inputs(W.generate_inputs(cfg, B, seed=31), torch.device("cuda", 0))
+
+    def src_of(env):
+        eng = _engine(cfg, sd_np, B, "f32", env=env)
+        # (a debug stop turns the branches off: run the trunk as forward phase 1, then stop phase 2 at the tokens it left)
+        eng.set_forward_phase(1)
+        eng.forward_infer(qpos, img, depth_img=depth)
+        eng.set_forward_phase(2)
+        src = _src(eng, qpos, img, depth)
+        assert eng.read_flags() == 0
+        return src
+    off = src_of({"ACTMI_CAM_PIPE": "0"})
+    on = src_of({"ACTMI_CAM_PIPE": "1", "ACTMI_BRANCHES": "3"})
+    assert torch.isfinite(off).all() and float(off[:, 2 + ncam * cfg.feat_hw[0] * cfg.feat_hw[1]:].abs().max()) > 0.05
+    assert torch.equal(on.view(torch.int32), off.view(torch.int32)), f"{int((on != off).sum())} elements differ"
+
+
 def _raw_config(max_batch=1):
     return L.ActmiConfig(struct_size=C.sizeof(L.ActmiConfig), num_cams=2, image_h=64, image_w=96, base_width=8, hidden_dim=64, nheads=4,
                          dim_feedforward=128, enc_layers=2, dec_layers=2, num_queries=8, state_dim=14, action_dim=16, latent_dim=32,
