@@ -8,6 +8,10 @@ Mirrors, with the reference's names and argument meaning:
 Differences, all on the host side of the step:
 * images stay **u8 NHWC** ``[C, H, W, 3]`` (the engine's fast input format; the ``/255`` and the ImageNet normalisation are
   fused into the conv1 loader) — ``f32_images=True`` reproduces the reference contract (f32 ``[C, 3, H, W]`` in [0, 1]);
+* depth frames (``use_depth``; ``/observations/depth_images/<cam>``) stay **raw uint16** ``[Cd, 1, H, W]`` when the episode
+  stores an unsigned integer of at most 16 bits: the engine finds every sample's min / max on the device and fuses the
+  reference's per-sample ``(d - min) / (max - min + 1e-6)`` into the depth stem's loader -- ``f32_depth=True`` (and any other
+  stored dtype) reproduces the reference contract, f32 normalised on the host;
 * batches are collated into **pinned** buffers and handed to the device by ``DevicePrefetcher`` on a side stream while
   the previous step computes (the reference moves 944 MB of f32 images per batch-64 step synchronously);
 * episode files are opened through ``open_episode``: HDF5 via ``h5py`` when it is importable (the reference's format:
@@ -141,10 +145,12 @@ def BatchSampler(batch_size, episode_len_l, sample_weights, rng=None):
 # ---------------------------------------------------------------------------------------------------------------------
 class EpisodicDataset(torch.utils.data.Dataset):
     """utils.py:41-174.  ``__getitem__`` returns (image, qpos, action, is_pad); image is u8 ``[C,H,W,3]`` unless
-    ``f32_images``."""
+    ``f32_images``.  With ``use_depth`` (the fork's depth dataset) a fifth entry follows: the frames of ``depth_camera_names``,
+    raw uint16 ``[Cd,1,H,W]`` when the episode stores an unsigned integer of at most 16 bits, else (or with ``f32_depth``)
+    float32 normalised by the sample's own minimum and maximum over all depth cameras."""
 
     def __init__(self, dataset_path_list, camera_names, norm_stats, episode_ids, episode_len, chunk_size, policy_class,
-                 f32_images=False):
+                 f32_images=False, depth_camera_names=None, use_depth=False, f32_depth=False):
         self.episode_ids = episode_ids
         self.dataset_path_list = dataset_path_list
         self.camera_names = camera_names
@@ -155,6 +161,11 @@ class EpisodicDataset(torch.utils.data.Dataset):
         self.max_episode_len = max(episode_len)
         self.policy_class = policy_class
         self.f32_images = f32_images
+        self.use_depth = bool(use_depth)
+        self.depth_camera_names = list(depth_camera_names) if depth_camera_names else []
+        self.f32_depth = f32_depth
+        if self.use_depth and not self.depth_camera_names:
+            raise ValueError("use_depth needs depth_camera_names (the task config's list of /observations/depth_images/<cam>)")
         if policy_class == "Diffusion":
             raise NotImplementedError("the Diffusion augmentations (torchvision transforms) are outside this path")
         self._stats_t = {k: torch.as_tensor(np.asarray(norm_stats[k]), dtype=torch.float32)
@@ -182,8 +193,12 @@ class EpisodicDataset(torch.utils.data.Dataset):
             episode_len = original_action_shape[0]
             qpos = np.asarray(root["/observations/qpos"][start_ts])
             images = [np.asarray(root[f"/observations/images/{cam}"][start_ts]) for cam in self.camera_names]
+            depths = [np.asarray(root[f"/observations/depth_images/{cam}"][start_ts]) for cam in self.depth_camera_names] \
+                if self.use_depth else None
         if compressed:                                            # utils.py:104-107
             images = [imdecode_bgr(buf) for buf in images]
+            if depths is not None:                                # three equal channels of an 8-bit decode; channel 0 is kept below
+                depths = [imdecode_bgr(buf) for buf in depths]
         if is_sim:
             action = action[start_ts:]
             action_len = episode_len - start_ts
@@ -205,7 +220,18 @@ class EpisodicDataset(torch.utils.data.Dataset):
         t = self._stats_t
         action_data = (action_data - t["action_mean"]) / t["action_std"]
         qpos_data = (qpos_data - t["qpos_mean"]) / t["qpos_std"]
+        if depths is not None:
+            return image_data, qpos_data, action_data, is_pad, self._depth_data(depths)
         return image_data, qpos_data, action_data, is_pad
+
+    def _depth_data(self, depths):
+        """the depth frames of one sample -> [Cd, 1, H, W]: a 3-D frame keeps channel 0; raw uint16 for the device-side
+        normalisation, or the reference's float32 (d - min) / (max - min + 1e-6) over all depth cameras of the sample"""
+        d = np.stack([f[:, :, 0] if f.ndim == 3 else f for f in depths], axis=0)[:, None]
+        if not self.f32_depth and d.dtype.kind == "u" and d.dtype.itemsize <= 2:
+            return torch.from_numpy(np.ascontiguousarray(d, dtype=np.uint16))
+        d = torch.from_numpy(np.ascontiguousarray(d, dtype=np.float32))        # torch.from_numpy(...).float(), utils_arm_gripper_all.py:147
+        return (d - d.min()) / (d.max() - d.min() + 1e-6)
 
 
 def flatten_list(l):
@@ -214,8 +240,10 @@ def flatten_list(l):
 
 def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_size_val, chunk_size,
               skip_mirrored_data=False, load_pretrain=False, policy_class=None, stats_dir_l=None, sample_weights=None,
-              train_ratio=0.99, num_workers=2, f32_images=False, rng=None):
-    """utils.py:249-301.  Returns (train_dataloader, val_dataloader, norm_stats, is_sim)."""
+              train_ratio=0.99, num_workers=2, f32_images=False, rng=None, depth_camera_names=None, use_depth=False,
+              f32_depth=False):
+    """utils.py:249-301.  Returns (train_dataloader, val_dataloader, norm_stats, is_sim).  ``use_depth``: the batches are
+    5-tuples that end in the depth frames of ``depth_camera_names`` (EpisodicDataset)."""
     rng = rng or np.random
     if isinstance(dataset_dir_l, str):
         dataset_dir_l = [dataset_dir_l]
@@ -246,9 +274,9 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
     norm_stats, _ = get_norm_stats(flatten_list([find_all_hdf5(d, skip_mirrored_data) for d in stats_dir_l]))
     print(f"Norm stats from: {stats_dir_l}")
     train_dataset = EpisodicDataset(dataset_path_list, camera_names, norm_stats, train_episode_ids, train_episode_len,
-                                    chunk_size, policy_class, f32_images)
+                                    chunk_size, policy_class, f32_images, depth_camera_names, use_depth, f32_depth)
     val_dataset = EpisodicDataset(dataset_path_list, camera_names, norm_stats, val_episode_ids, val_episode_len,
-                                  chunk_size, policy_class, f32_images)
+                                  chunk_size, policy_class, f32_images, depth_camera_names, use_depth, f32_depth)
     from torch.utils.data import DataLoader
     kw = dict(pin_memory=torch.cuda.is_available(), num_workers=num_workers)
     if num_workers > 0:

@@ -196,21 +196,22 @@ class ACTEngine:
         return (B, cfg.num_depth_cams, 1, cfg.image_h, cfg.image_w)
 
     def _bind_depth(self, depth_img, B: int):
-        """Check the depth batch of a use_depth engine (float32 [B, Cd, 1, image_h, image_w], contiguous, on the engine's device,
-        un-normalised: the stem applies (d - 0.5) / 0.5) and bind it for the next forward (actmi_set_depth).  Returns the tensor
-        the library will read."""
+        """Check the depth batch of a use_depth engine ([B, Cd, 1, image_h, image_w], contiguous, on the engine's device; float32
+        in about [0, 1]: the stem applies (d - 0.5) / 0.5; or raw uint16: the library normalises every sample with its own
+        min / max on the device first, as the reference's dataset does on the host) and bind it for the next forward
+        (actmi_set_depth / actmi_set_depth_u16).  Returns the tensor the library will read."""
         if not self.cfg.num_depth_cams:
             if depth_img is not None:
                 raise ValueError("depth_img given to an engine whose config has use_depth=False")
             return None
         want = self._depth_shape(B)
         if depth_img is None:
-            raise ValueError(f"a use_depth engine needs depth_img float32 {list(want)} = [B, Cd, 1, H, W]")
+            raise ValueError(f"a use_depth engine needs depth_img float32 or uint16 {list(want)} = [B, Cd, 1, H, W]")
         if not isinstance(depth_img, torch.Tensor) or not depth_img.is_cuda:
             raise ValueError("depth_img must be a CUDA tensor on the engine's device")
         self._check_dev(depth_img=depth_img)
-        if depth_img.dtype != torch.float32:
-            raise TypeError(f"depth_img dtype {depth_img.dtype} not supported (float32)")
+        if depth_img.dtype not in (torch.float32, torch.uint16):
+            raise TypeError(f"depth_img dtype {depth_img.dtype} not supported (float32, or raw uint16)")
         if depth_img.dim() == 4:
             raise ValueError(f"depth_img is 4-D {tuple(depth_img.shape)}: the depth batch is 5-D [B, Cd, 1, H, W] = {list(want)} "
                              "(one channel axis per depth camera, as the reference's depth dataset produces it)")
@@ -218,7 +219,10 @@ class ACTEngine:
             raise ValueError(f"depth_img shape {tuple(depth_img.shape)} != {want} = [B, Cd, 1, H, W]")
         if not depth_img.is_contiguous():
             raise ValueError("depth_img must be contiguous")
-        L.check(self.lib.actmi_set_depth(self.h, C.c_void_p(depth_img.data_ptr()), B), self.h, "set_depth")
+        if depth_img.dtype == torch.uint16:
+            L.check(self.lib.actmi_set_depth_u16(self.h, C.c_void_p(depth_img.data_ptr()), B), self.h, "set_depth_u16")
+        else:
+            L.check(self.lib.actmi_set_depth(self.h, C.c_void_p(depth_img.data_ptr()), B), self.h, "set_depth")
         return depth_img
 
     def forward_infer(self, qpos: torch.Tensor, image: torch.Tensor, out: torch.Tensor = None,
@@ -264,10 +268,12 @@ class ACTEngine:
         L.check(self.lib.actmi_set_forward_phase(self.h, int(phase)), self.h, "set_forward_phase")
 
     def capture_infer(self, batch: int, image_dtype=torch.uint8, with_ensemble=None, statics=None, phase: int = 0,
-                      num_points: int = None):
+                      num_points: int = None, depth_dtype=torch.float32, static_depth=None):
         """Capture one forward (optionally + the temporal-ensemble kernel) into a hipGraph and return
         ``replay(qpos, image) -> a_hat`` that copies into static inputs and replays.  A use_pcd engine captures static
-        xyz / rgb buffers of ``num_points`` points (default max_points) and replays ``replay(qpos, image, pointcloud)``.  The forward path allocates
+        xyz / rgb buffers of ``num_points`` points (default max_points) and replays ``replay(qpos, image, pointcloud)``.  A use_depth
+        engine captures a static depth buffer of ``depth_dtype`` (float32 or uint16; or the caller's ``static_depth``) and replays
+        ``replay(qpos, image, depth_img=...)`` with a batch of exactly that dtype.  The forward path allocates
         nothing and never synchronises, so the whole step is one graph launch (removes ~60 kernel-launch gaps; matters
         at small batch where the step is launch-bound)."""
         if not self._finalized:
@@ -283,7 +289,12 @@ class ACTEngine:
             s_out = torch.empty((batch, cfg.num_queries, cfg.action_dim), dtype=torch.float32, device=dev)
         s_depth = None
         if cfg.num_depth_cams:
-            s_depth = torch.zeros(self._depth_shape(batch), dtype=torch.float32, device=dev)
+            if static_depth is not None:
+                s_depth = static_depth
+            else:
+                if depth_dtype not in (torch.float32, torch.uint16):
+                    raise TypeError(f"depth_dtype {depth_dtype} not supported (float32, or raw uint16)")
+                s_depth = torch.zeros(self._depth_shape(batch), dtype=depth_dtype, device=dev)
         s_cloud = None
         if cfg.use_pcd:
             npts = self.max_points if num_points is None else int(num_points)
@@ -325,6 +336,8 @@ class ACTEngine:
                     raise ValueError("a use_depth engine needs depth_img [B, Cd, 1, H, W]")
                 if tuple(depth_img.shape) != tuple(s_depth.shape):
                     raise ValueError(f"depth_img shape {tuple(depth_img.shape)} != the captured {tuple(s_depth.shape)}")
+                if depth_img.dtype != s_depth.dtype:
+                    raise ValueError(f"depth_img dtype {depth_img.dtype} != the captured {s_depth.dtype} (capture_infer(depth_dtype=...))")
                 if depth_img.data_ptr() != s_depth.data_ptr():
                     s_depth.copy_(depth_img, non_blocking=True)
             elif depth_img is not None:
@@ -652,26 +665,40 @@ class InferPipeline:
         for t in range(T):
             a_hat, raw = pipe.step(next_inputs=(qpos_host[t + 1], frames_host[t + 1]) if t + 1 < T else None)
 
+    A use_depth engine takes ``depth_dtype`` (torch.uint16: raw sensor frames, normalised on the device; or torch.float32): every
+    slot then owns a device depth buffer that both of its graphs share, ``feed(qpos, image, depth_host=...)`` copies it with the
+    frame, and ``next_inputs`` is (qpos_host, image_host, depth_host).
+
     No host synchronisation anywhere; the pinned host tensors of a feed must stay untouched until the step AFTER the one they were
     passed to has been issued and `pipe.copied(k)` has completed (or simply use one host buffer per step in flight).  Outputs of
     step t stay valid until step t + 2 is issued."""
 
-    def __init__(self, engine: "ACTEngine", batch: int, with_ensemble=None, image_dtype=torch.uint8, copy_stream_candidates: int = 8):
+    def __init__(self, engine: "ACTEngine", batch: int, with_ensemble=None, image_dtype=torch.uint8, copy_stream_candidates: int = 8,
+                 depth_dtype=None):
         if engine.cfg.use_pcd:
             raise NotImplementedError("InferPipeline has no host feed for point clouds yet (use capture_infer)")
-        if engine.cfg.num_depth_cams:
-            raise NotImplementedError("InferPipeline has no host feed for depth frames yet (use capture_infer)")
+        if engine.cfg.num_depth_cams and depth_dtype is None:
+            raise NotImplementedError("InferPipeline has no host feed for depth frames yet (use capture_infer), unless "
+                                      "depth_dtype=torch.uint16 / torch.float32 asks for one")
+        if depth_dtype is not None and not engine.cfg.num_depth_cams:
+            raise ValueError("depth_dtype given for an engine whose config has use_depth=False")
+        if depth_dtype not in (None, torch.float32, torch.uint16):
+            raise TypeError(f"depth_dtype {depth_dtype} not supported (float32, or raw uint16)")
         self.engine, self.dev = engine, engine.device
         cfg, dev = engine.cfg, engine.device
         shape = (batch, cfg.num_cams, cfg.image_h, cfg.image_w, 3) if image_dtype == torch.uint8 else \
                 (batch, cfg.num_cams, 3, cfg.image_h, cfg.image_w)
         self.slots = []
+        self.depth = []                                             # slot k's device depth buffer (depth engines)
         for _ in range(2):
             st = (torch.zeros((batch, cfg.state_dim), dtype=torch.float32, device=dev), torch.zeros(shape, dtype=image_dtype, device=dev),
                   torch.empty((batch, cfg.num_queries, cfg.action_dim), dtype=torch.float32, device=dev))
-            trunk = engine.capture_infer(batch, image_dtype=image_dtype, statics=st, phase=1)
-            rest = engine.capture_infer(batch, image_dtype=image_dtype, with_ensemble=with_ensemble, statics=st, phase=2)
+            s_depth = torch.zeros(engine._depth_shape(batch), dtype=depth_dtype, device=dev) if depth_dtype is not None else None
+            trunk = engine.capture_infer(batch, image_dtype=image_dtype, statics=st, phase=1, static_depth=s_depth)
+            rest = engine.capture_infer(batch, image_dtype=image_dtype, with_ensemble=with_ensemble, statics=st, phase=2,
+                                        static_depth=s_depth)
             self.slots.append((st, trunk, rest))
+            self.depth.append(s_depth)
         self.ev_copy = [torch.cuda.Event() for _ in range(2)]       # slot k's inputs have landed
         self.ev_trunk = [torch.cuda.Event() for _ in range(2)]      # slot k's trunk has run: its inputs are dead
         self.fed = [False, False]
@@ -692,6 +719,8 @@ class InferPipeline:
             return torch.cuda.Stream(device=dev), []
         (q0, im0, _), _, _ = self.slots[0]
         hq, him = torch.zeros(q0.shape, dtype=q0.dtype).pin_memory(), torch.zeros(im0.shape, dtype=im0.dtype).pin_memory()
+        d0 = self.depth[0]
+        nxt = (hq, him) if d0 is None else (hq, him, torch.zeros(d0.shape, dtype=d0.dtype).pin_memory())
         trials = []
         for _ in range(n_cand):
             self.copy_stream = cs = torch.cuda.Stream(device=dev)
@@ -699,9 +728,9 @@ class InferPipeline:
             for rep in range(2):                                    # (the first round also warms the graphs up)
                 torch.cuda.synchronize(dev)
                 t0 = time.perf_counter()
-                self.feed(hq, him)
+                self.feed(*nxt[:2], depth_host=nxt[2] if d0 is not None else None)
                 for i in range(12):
-                    self.step(next_inputs=(hq, him) if i < 11 else None)
+                    self.step(next_inputs=nxt if i < 11 else None)
                 torch.cuda.synchronize(dev)
                 dt.append((time.perf_counter() - t0) / 12)
             trials.append((dt[1], cs))
@@ -711,11 +740,22 @@ class InferPipeline:
         best = min(trials, key=lambda t: t[0])
         return best[1], [round(t[0] * 1e3, 4) for t in trials]
 
-    def feed(self, qpos_host, image_host, slot=None):
+    def feed(self, qpos_host, image_host, slot=None, *, depth_host=None):
         """enqueue the copy of one step's inputs (pinned host tensors) into slot `slot` (default: the slot the next step() runs
-        from); it starts once the trunk that read the slot last has run AND the step in flight has left its own trunk"""
+        from); it starts once the trunk that read the slot last has run AND the step in flight has left its own trunk.  A depth
+        pipeline needs `depth_host` [B, Cd, 1, H, W] of the pipeline's depth_dtype: it crosses between the same events as the frame"""
         k = self.k_run if slot is None else slot
         s_qpos, s_img, _ = self.slots[k][0]
+        s_depth = self.depth[k]
+        if s_depth is None:
+            if depth_host is not None:
+                raise ValueError("depth_host given to a pipeline without a depth feed")
+        else:
+            if depth_host is None:
+                raise ValueError("this pipeline feeds a use_depth engine: feed(qpos_host, image_host, depth_host=...)")
+            if depth_host.dtype != s_depth.dtype or tuple(depth_host.shape) != tuple(s_depth.shape):
+                raise ValueError(f"depth_host is {depth_host.dtype} {tuple(depth_host.shape)}, the pipeline's depth buffer "
+                                 f"{s_depth.dtype} {tuple(s_depth.shape)}")
         cs = self.copy_stream
         if self.ran[k]:
             cs.wait_event(self.ev_trunk[k])
@@ -724,6 +764,8 @@ class InferPipeline:
         with torch.cuda.stream(cs):
             s_qpos.copy_(qpos_host, non_blocking=True)
             s_img.copy_(image_host, non_blocking=True)
+            if s_depth is not None:
+                s_depth.copy_(depth_host, non_blocking=True)
             self.ev_copy[k].record(cs)
         self.fed[k] = True
 
@@ -732,21 +774,24 @@ class InferPipeline:
         self.ev_copy[k].synchronize()
 
     def step(self, next_inputs=None):
-        """run one step from the current slot; `next_inputs` = (qpos_host, image_host) of the FOLLOWING step, copied into the
-        other slot beside this step's transformer"""
+        """run one step from the current slot; `next_inputs` = (qpos_host, image_host) of the FOLLOWING step -- (qpos_host,
+        image_host, depth_host) for a depth pipeline --, copied into the other slot beside this step's transformer"""
         k = self.k_run
         if not self.fed[k]:
             raise RuntimeError("InferPipeline.step: no inputs were fed for this step")
         (s_qpos, s_img, _), trunk, rest = self.slots[k]
         cur = torch.cuda.current_stream(self.dev)
         cur.wait_event(self.ev_copy[k])
-        trunk(s_qpos, s_img)
+        s_depth = self.depth[k]
+        trunk(s_qpos, s_img, depth_img=s_depth)
         self.ev_trunk[k].record(cur)
         self.ran[k] = True
         self.fed[k] = False
         if next_inputs is not None:
-            self.feed(next_inputs[0], next_inputs[1], slot=k ^ 1)
-        out = rest(s_qpos, s_img)
+            if s_depth is not None and len(next_inputs) != 3:
+                raise ValueError("this pipeline feeds a use_depth engine: next_inputs = (qpos_host, image_host, depth_host)")
+            self.feed(next_inputs[0], next_inputs[1], slot=k ^ 1, depth_host=next_inputs[2] if s_depth is not None else None)
+        out = rest(s_qpos, s_img, depth_img=s_depth)
         self.k_run ^= 1
         return out
 

@@ -107,6 +107,7 @@ def load():
         "actmi_set_pointcloud": ([vp, vp, vp, i32, i32], i32),
         "actmi_create_ex2": ([C.POINTER(ActmiConfig), C.POINTER(ActmiPcdConfig), C.POINTER(ActmiDepthConfig), C.POINTER(vp)], i32),
         "actmi_set_depth": ([vp, vp, i32], i32),
+        "actmi_set_depth_u16": ([vp, vp, i32], i32),
         "actmi_destroy": ([vp], i32),
         "actmi_last_error": ([vp], C.c_char_p),
         "actmi_num_params": ([vp], i32),
@@ -142,6 +143,8 @@ def load():
         "actmi_op_maxpool3x3s2": ([vp, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_conv1": ([vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
         "actmi_op_conv1_depth": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
+        "actmi_op_depth_minmax_u16": ([vp, vp, i32, i64, vp], i32),
+        "actmi_op_conv1_depth_u16": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
         "actmi_op_conv1_workspace_floats": ([i32, i32], C.c_int64),
         "actmi_op_conv1_prepare": ([vp, vp, i32, i32, i32, vp], i32),
         "actmi_op_conv1_prepared": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),

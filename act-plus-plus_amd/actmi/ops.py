@@ -386,10 +386,34 @@ def conv1(image, w_oihw, scale, bias, prec=None):
     return out
 
 
-def conv1_depth(depth, w_oihw, scale, bias, out=None, out_cam0=0):
-    """depth stem: depth f32 [B, Cd, 1, H, W] un-normalised; w [Cd, Cout, 1, 7, 7]; scale / bias [Cd, Cout].  Returns the
-    camera-major map [Cd, B, Ho, Wo, Cout], or writes cameras out_cam0 .. out_cam0 + Cd - 1 of a given `out` [Ct, B, Ho, Wo, Cout]."""
+def depth_minmax(depth_u16, out=None):
+    """per-sample extremes of a raw depth batch: depth uint16 [B, ...] (contiguous; everything behind the batch axis is one
+    sample) -> float32 [B, 2] = (min, max), exact; no host synchronisation."""
     lib = L.load()
+    if depth_u16.dtype != torch.uint16:
+        raise TypeError(f"depth_minmax: dtype {depth_u16.dtype} not supported (uint16)")
+    depth_u16 = depth_u16.contiguous()
+    B = depth_u16.shape[0]
+    n = depth_u16.numel() // B if B else 0
+    if out is None:
+        out = torch.empty((B, 2), dtype=torch.float32, device=depth_u16.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, 2)
+    L.check(lib.actmi_op_depth_minmax_u16(_p(depth_u16), _p(out), B, n, L.current_stream_ptr()), None, "op_depth_minmax_u16")
+    return out
+
+
+def conv1_depth(depth, w_oihw, scale, bias, out=None, out_cam0=0, lohi=None):
+    """depth stem: depth f32 [B, Cd, 1, H, W] un-normalised; w [Cd, Cout, 1, 7, 7]; scale / bias [Cd, Cout].  Returns the
+    camera-major map [Cd, B, Ho, Wo, Cout], or writes cameras out_cam0 .. out_cam0 + Cd - 1 of a given `out` [Ct, B, Ho, Wo, Cout].
+    A raw uint16 `depth` needs lohi = depth_minmax(depth) ([B, 2]): the loader normalises every sample with its extremes first."""
+    lib = L.load()
+    if depth.dtype == torch.uint16:
+        if lohi is None:
+            raise ValueError("conv1_depth: a uint16 depth batch needs lohi=depth_minmax(depth)")
+    elif depth.dtype != torch.float32:
+        raise TypeError(f"conv1_depth: depth dtype {depth.dtype} not supported (float32 or uint16)")
+    elif lohi is not None:
+        raise ValueError("conv1_depth: lohi goes with a uint16 depth batch")
     depth, w_oihw, scale, bias = depth.contiguous(), w_oihw.contiguous(), scale.contiguous(), bias.contiguous()
     B, Cd, one, H, W = depth.shape
     Cout = w_oihw.shape[1]
@@ -398,6 +422,12 @@ def conv1_depth(depth, w_oihw, scale, bias, out=None, out_cam0=0):
     if out is None:
         out = torch.empty((Cd, B, Ho, Wo, Cout), dtype=torch.float32, device=depth.device)
     assert out.is_contiguous() and tuple(out.shape[1:]) == (B, Ho, Wo, Cout) and 0 <= out_cam0 and out_cam0 + Cd <= out.shape[0]
+    if lohi is not None:
+        lohi = lohi.contiguous()
+        assert lohi.dtype == torch.float32 and tuple(lohi.shape) == (B, 2)
+        L.check(lib.actmi_op_conv1_depth_u16(_p(depth), _p(lohi), _p(w_oihw), _p(scale), _p(bias), _p(out), B, Cd, H, W, Cout,
+                                             int(out_cam0), L.current_stream_ptr()), None, "op_conv1_depth_u16")
+        return out
     L.check(lib.actmi_op_conv1_depth(_p(depth), _p(w_oihw), _p(scale), _p(bias), _p(out), B, Cd, H, W, Cout, int(out_cam0),
                                      L.current_stream_ptr()), None, "op_conv1_depth")
     return out

@@ -48,7 +48,17 @@ int actmi_set_depth(actmi_handle h, const float* depth, int B) {
     if (!h->Cd) return bad(h, "handle was created without a depth config (actmi_create_ex2)", ACTMI_E_STATE);
     if (!depth) return bad(h, "null pointer");
     if (B < 1 || B > h->cfg.max_batch) return bad(h, "batch exceeds max_batch");
-    h->depth_img = depth; h->depth_B = B;
+    h->depth_img = depth; h->depth_u16 = false; h->depth_B = B;
+    return ACTMI_OK;
+}
+
+int actmi_set_depth_u16(actmi_handle h, const uint16_t* depth, int B) {
+    if (!h) return ACTMI_E_INVALID;
+    ENTER(h);
+    if (!h->Cd) return bad(h, "handle was created without a depth config (actmi_create_ex2)", ACTMI_E_STATE);
+    if (!depth) return bad(h, "null pointer");
+    if (B < 1 || B > h->cfg.max_batch) return bad(h, "batch exceeds max_batch");
+    h->depth_img = depth; h->depth_u16 = true; h->depth_B = B;
     return ACTMI_OK;
 }
 
@@ -356,6 +366,22 @@ int actmi_op_conv1_depth(const float* depth, const float* w_oihw, const float* s
     g_op_error.clear();
     Conv1DepthArgs a;
     a.depth = depth; a.w = w_oihw; a.w_cam_stride = (int64_t)Cout * 49; a.scale = scale; a.bias = bias; a.out = out;
+    a.B = B; a.Cd = Cd; a.H = H; a.W = W; a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1; a.Cout = Cout; a.out_cam0 = out_cam0;
+    const int rc = launch_conv1_depth(a, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int64_t n_per_sample, void* stream) {
+    g_op_error.clear();
+    const int rc = launch_depth_minmax_u16(depth, lohi_out, B, n_per_sample, S(stream));
+    if (rc == -2) g_op_error = "depth_minmax_u16: null or misaligned pointer, B outside 1..65535 or n_per_sample < 1";
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+int actmi_op_conv1_depth_u16(const uint16_t* depth, const float* lohi, const float* w_oihw, const float* scale, const float* bias, float* out,
+                             int B, int Cd, int H, int W, int Cout, int out_cam0, void* stream) {
+    g_op_error.clear();
+    Conv1DepthArgs a;
+    a.depth = depth; a.src_u16 = 1; a.lohi = lohi;
+    a.w = w_oihw; a.w_cam_stride = (int64_t)Cout * 49; a.scale = scale; a.bias = bias; a.out = out;
     a.B = B; a.Cd = Cd; a.H = H; a.W = W; a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1; a.Cout = Cout; a.out_cam0 = out_cam0;
     const int rc = launch_conv1_depth(a, S(stream), &g_op_error);
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);

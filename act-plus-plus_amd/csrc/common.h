@@ -74,8 +74,16 @@ int launch_conv1_wimg(const float* w, void* img, int C, int Cout, hipStream_t st
 int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err);
 
 // ---- depth stem: conv1 7x7/s2, 1 -> Cout channels + FrozenBN + ReLU, fp32 products (conv1_depth.hip) ----
+// a depth batch as the forward was given it: f32 in about [0, 1], or raw u16 with the [B][2] table of its per-sample extremes
+struct DepthSrc {
+    const void* p = nullptr;      // f32 or u16 [B][Cd][1][H][W]
+    bool u16 = false;
+    const float* lohi = nullptr;  // u16: (min, max) per sample, on the device (launch_depth_minmax_u16)
+};
 struct Conv1DepthArgs {
-    const float* depth;   // f32 [B][Cd][1][H][W], raw (the loader applies (d - 0.5) / 0.5)
+    const void* depth;    // f32 [B][Cd][1][H][W] in about [0, 1] (the loader applies (d - 0.5) / 0.5), or raw u16 (src_u16)
+    int src_u16 = 0;      // depth is uint16: the loader applies (d - lo_b) / ((hi_b - lo_b) + 1e-6) per sample first
+    const float* lohi = nullptr;  // src_u16: [B][2] = (lo_b, hi_b) on the device
     const float* w;       // camera 0's [Cout][49] weights (the OIHW parameter itself)
     int64_t w_cam_stride; // floats between the weights of consecutive cameras
     const float* scale;   // [Cd][Cout]
@@ -86,7 +94,9 @@ struct Conv1DepthArgs {
 };
 int launch_conv1_depth(const Conv1DepthArgs& a, hipStream_t st, std::string* err);
 // normalised depth -> channel 0 of a camera-major NHWC4 image [Cd][B][H][W][4] (zeros elsewhere), for the stem's weight gradient
-int launch_depth_nhwc4(const float* depth, float* out, int B, int Cd, int H, int W, hipStream_t st);
+int launch_depth_nhwc4(const DepthSrc& depth, float* out, int B, int Cd, int H, int W, hipStream_t st);
+// per-sample (min, max) of a raw u16 batch [B][n] -> lohi [B][2] floats (exact); no workspace, no synchronisation, capturable
+int launch_depth_minmax_u16(const uint16_t* depth, float* lohi, int B, int64_t n, hipStream_t st);
 
 // ---- direct 3x3 / stride 1 / pad 1 convolution, 64 -> 64 channels, f16x3 (conv3.hip) ----------
 struct Conv3Args {

@@ -180,8 +180,10 @@ struct actmi_ctx {
     // depth cameras (actmi_create_ex2): cameras C .. Ct-1 of the trunk, Ct = C + Cd; their stem is conv1_depth.hip and their
     // layer4 maps go through input_proj_depth into the token rows behind the RGB tokens (detr_vae.py:188-202, transformer.py:64-86)
     int Cd = 0, Ct = 0;
-    const float* depth_img = nullptr;                      // batch bound for the next forward (actmi_set_depth), then cleared
+    const void* depth_img = nullptr;                       // batch bound for the next forward (actmi_set_depth / _u16), then cleared
+    bool depth_u16 = false;                                // the binding is raw uint16 (actmi_set_depth_u16)
     int depth_B = 0;
+    float* depth_lohi = nullptr;                           // [max_batch][2] per-sample (min, max) of a u16 binding, refilled by every forward that reads one
     std::vector<CamGroup> cam_groups;                      // RGB group, then the depth group (engine_create)
     int device = 0;                    // HIP device the handle was created on (all its memory lives there)
     std::string err;
@@ -291,9 +293,11 @@ inline int engine_prec(const actmi_ctx* ctx) { return ctx->prec_override ? ctx->
 
 int engine_create(const actmi_config* cfg, const actmi_pcd_config* pcd, const actmi_depth_config* depth, actmi_ctx** out);
 // the depth batch of this forward: checks the binding of a depth handle against B (ACTMI_E_STATE with a message) and consumes it
-int engine_take_depth(actmi_ctx* ctx, int B, const float** depth);
+int engine_take_depth(actmi_ctx* ctx, int B, DepthSrc* depth);
+// a u16 batch: its per-sample extremes into ctx->depth_lohi, ahead of the kernels that normalise with them (f32: nothing)
+int engine_depth_minmax(actmi_ctx* ctx, const DepthSrc& depth, int B, hipStream_t st);
 // the depth stem of B samples into cameras C.. of ctx->act1
-int engine_depth_stem(actmi_ctx* ctx, const float* depth, int B, hipStream_t st);
+int engine_depth_stem(actmi_ctx* ctx, const DepthSrc& depth, int B, hipStream_t st);
 // the clouds of this forward: checks the binding of a point-cloud handle against B (ACTMI_E_STATE with a message) and consumes it
 int engine_take_pointcloud(actmi_ctx* ctx, int B, const float** xyz, const float** rgb, int* P);
 // PointNet + input_proj_pointnet of B clouds of P points -> token row 2 of ctx->X, features / winners in ctx->pcd_feat / pcd_arg
@@ -354,7 +358,7 @@ int engine_calibrate_activations(actmi_ctx* ctx, hipStream_t st);
 int engine_measure_act_scale(actmi_ctx* ctx, const float* x, int64_t rows, int cols, hipStream_t st, float* out);
 // token row of every feature row of the trunk's layer4 maps for batch B (ctx->rowmap; rebuilt when B changes)
 int engine_build_rowmap(actmi_ctx* ctx, int B, hipStream_t st);
-int engine_backbone(actmi_ctx* ctx, const void* image, const float* depth, int fmt, int B, hipStream_t st);
+int engine_backbone(actmi_ctx* ctx, const void* image, const DepthSrc& depth, int fmt, int B, hipStream_t st);
 float engine_weight_scale(const actmi_ctx* ctx, const float* w);
 int train_create(actmi_ctx* ctx);
 int train_fit_prec(actmi_ctx* ctx);

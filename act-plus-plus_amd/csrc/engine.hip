@@ -540,6 +540,7 @@ int create_device_state(actmi_ctx* ctx) {
     ALLOC(ctx->act_scale_dev, (int64_t)ctx->convs.size() + 4);
     ALLOC(ctx->rowmap, (int64_t)B * Ct * ctx->P_);
     ctx->rowmap_B = -1;
+    if (ctx->Cd) ALLOC(ctx->depth_lohi, 2 * (int64_t)B);
     if (ctx->has_pcd) {
         const int64_t Hp = ctx->pcd.hidden_dim, Op = ctx->pcd.output_dim, rows = (int64_t)B * ctx->pcd.max_points;
         for (int i = 0; i < 2; ++i) ALLOC(ctx->pcd_act[i], rows * std::max(Hp, Op));
@@ -867,7 +868,9 @@ int engine_calibrate_activations(actmi_ctx* ctx, hipStream_t st) {
         ctx->calibrating = true;
         const std::string keep = ctx->stop_stage;
         ctx->stop_stage.clear();
-        rc = engine_backbone(ctx, dimg, ddep, ACTMI_IMG_U8_NHWC, 1, st);
+        DepthSrc dsrc;
+        dsrc.p = ddep;
+        rc = engine_backbone(ctx, dimg, dsrc, ACTMI_IMG_U8_NHWC, 1, st);
         ctx->stop_stage = keep;
         ctx->calibrating = false;
         if (hipStreamSynchronize(st) != hipSuccess && rc == 0) rc = ACTMI_E_LAUNCH;
@@ -926,18 +929,29 @@ int engine_build_rowmap(actmi_ctx* ctx, int B, hipStream_t st) {
 }
 
 // multi-camera ResNet18 trunk + input_proj -> token rows n_extra.. of X   (backbone.py:66-71, detr_vae.py:180-185)
-int engine_depth_stem(actmi_ctx* ctx, const float* depth, int B, hipStream_t st) {
+int engine_depth_minmax(actmi_ctx* ctx, const DepthSrc& depth, int B, hipStream_t st) {
+    if (!depth.u16) return 0;
+    const actmi_config& g = ctx->cfg;
+    if (launch_depth_minmax_u16(static_cast<const uint16_t*>(depth.p), ctx->depth_lohi, B, (int64_t)ctx->Cd * g.image_h * g.image_w, st) != 0) {
+        ctx->err = "depth_minmax_u16 launch failed";
+        return ACTMI_E_LAUNCH;
+    }
+    return 0;
+}
+
+int engine_depth_stem(actmi_ctx* ctx, const DepthSrc& depth, int B, hipStream_t st) {
     const actmi_config& g = ctx->cfg;
     const int w0 = g.base_width;
     const CamGroup& grp = ctx->cam_groups.back();          // (the caller checked that the handle has depth cameras)
     Conv1DepthArgs d;
-    d.depth = depth; d.w = ctx->P(grp.prefix(0) + "conv1.weight"); d.w_cam_stride = grp.cam_stride;
+    d.depth = depth.p; d.src_u16 = depth.u16 ? 1 : 0; d.lohi = depth.lohi;
+    d.w = ctx->P(grp.prefix(0) + "conv1.weight"); d.w_cam_stride = grp.cam_stride;
     d.scale = ctx->conv1_scale + (int64_t)grp.c0 * w0; d.bias = ctx->conv1_bias + (int64_t)grp.c0 * w0; d.out = ctx->act1;
     d.B = B; d.Cd = grp.n; d.H = g.image_h; d.W = g.image_w; d.Ho = ctx->H1; d.Wo = ctx->W1; d.Cout = w0; d.out_cam0 = grp.c0;
     return launch_conv1_depth(d, st, &ctx->err) == 0 ? 0 : ACTMI_E_LAUNCH;
 }
 
-int engine_backbone(actmi_ctx* ctx, const void* image, const float* depth, int fmt, int B, hipStream_t st) {
+int engine_backbone(actmi_ctx* ctx, const void* image, const DepthSrc& depth, int fmt, int B, hipStream_t st) {
     const actmi_config& g = ctx->cfg;
     const int C = ctx->Ct, w0 = g.base_width, D = g.hidden_dim;
     Conv1Args c1 = stem_args(ctx, image, fmt, B);
@@ -948,6 +962,7 @@ int engine_backbone(actmi_ctx* ctx, const void* image, const float* depth, int f
                        (w0 & 3) == 0 && ctx->H2 == ctx->H1 / 2;
     // stem (conv1 + pool) of all cameras, ahead of the branches
     c1.vpool = vpool ? 1 : 0;
+    if (ctx->Cd) CHK(engine_depth_minmax(ctx, depth, B, st));              // (2 bytes per pixel, ahead of the RGB stem: the depth stem's re-read finds them cached)
     CHK(launch_conv1(c1, st, &ctx->err));
     if (ctx->Cd) CHK(engine_depth_stem(ctx, depth, B, st));                // the depth group's cameras of the same map
     if (vpool) CHK(launch_hpool(ctx->act1, ctx->buf[0], C * B * ctx->H2, ctx->W1, w0, ctx->W2, st));
@@ -1072,18 +1087,18 @@ int engine_backbone(actmi_ctx* ctx, const void* image, const float* depth, int f
     return 0;
 }
 
-int engine_take_depth(actmi_ctx* ctx, int B, const float** depth) {
-    *depth = nullptr;
+int engine_take_depth(actmi_ctx* ctx, int B, DepthSrc* depth) {
+    *depth = DepthSrc();
     if (!ctx->Cd) return 0;
     if (!ctx->depth_img) {
-        ctx->err = "this handle has depth cameras: bind the depth batch of every forward with actmi_set_depth";
+        ctx->err = "this handle has depth cameras: bind the depth batch of every forward with actmi_set_depth or actmi_set_depth_u16";
         return ACTMI_E_STATE;
     }
     if (ctx->depth_B != B) {
         ctx->err = "forward of batch " + std::to_string(B) + " but the bound depth batch holds " + std::to_string(ctx->depth_B) + " samples";
         return ACTMI_E_STATE;
     }
-    *depth = ctx->depth_img;
+    depth->p = ctx->depth_img; depth->u16 = ctx->depth_u16; depth->lohi = ctx->depth_u16 ? ctx->depth_lohi : nullptr;
     ctx->depth_img = nullptr;                           // one binding, one forward
     return 0;
 }
@@ -1248,7 +1263,7 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
     const int D = g.hidden_dim, N = ctx->N;
     const float *pc_xyz = nullptr, *pc_rgb = nullptr;
     int pc_P = 0;
-    const float* depth = nullptr;
+    DepthSrc depth;
     if (ctx->fwd_phase != 2) CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_P));     // (before anything is launched)
     if (ctx->fwd_phase != 2) CHK(engine_take_depth(ctx, B, &depth));
     // actmi_set_forward_phase: the step as two halves a caller can capture into two graphs -- the trunk with the token assembly

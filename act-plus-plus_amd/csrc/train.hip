@@ -500,7 +500,7 @@ int cvae_bwd(actmi_ctx* ctx, float loss_scale, hipStream_t st) {
 }
 
 // ---- trunk with saved maps: stems, max pool, the BasicBlocks of ctx->blocks; the layer4 maps are T.saves.back().out
-int trunk_fwd(actmi_ctx* ctx, const void* image, const float* depth, int fmt, int B, hipStream_t st) {
+int trunk_fwd(actmi_ctx* ctx, const void* image, const DepthSrc& depth, int fmt, int B, hipStream_t st) {
     TrainState& T = *ctx->train;
     const actmi_config& g = ctx->cfg;
     const int C = ctx->Ct, w0 = g.base_width;
@@ -510,6 +510,7 @@ int trunk_fwd(actmi_ctx* ctx, const void* image, const float* depth, int fmt, in
         // depth cameras: the depth group's cameras of the same maps.  The stem's weight gradient reads the normalised depth as
         // channel 0 of an NHWC4 image like the RGB one (three quarters of that contraction multiply zeros)
         const int64_t cam_floats = (int64_t)B * g.image_h * g.image_w * 4;
+        CHK(engine_depth_minmax(ctx, depth, B, st));
         CHK(launch_depth_nhwc4(depth, T.xn4 + ctx->cam_groups.back().c0 * cam_floats, B, ctx->Cd, g.image_h, g.image_w, st));
         CHK(engine_depth_stem(ctx, depth, B, st));
     }
@@ -1032,7 +1033,7 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
     const float *pc_xyz = nullptr, *pc_rgb = nullptr;
     int pc_P = 0;
     CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_P));            // (before anything is launched)
-    const float* depth = nullptr;
+    DepthSrc depth;
     CHK(engine_take_depth(ctx, B, &depth));
     PrecScope prec_scope(ctx);               // the opt-in bf16 product mode covers the GEMMs of this call only
     TrainState& T = *ctx->train;

@@ -114,6 +114,11 @@ def eval_bc(config, ckpt_name, save_episode=True, num_rollouts=50, policy=None, 
     state_dim = config["state_dim"]
     policy_class = config["policy_class"]
     policy_config = config["policy_config"]
+    if policy_config.get("use_depth") or getattr(policy, "use_depth", False):
+        # the simulators here render no depth and the reference's depth rollouts read ROS camera topics; rolling the policy out on
+        # RGB alone would report the success rate of a different model
+        raise NotImplementedError("eval_bc cannot roll out a use_depth policy: no environment here produces depth frames "
+                                  "(train with --use_depth, evaluate on the robot's own loop)")
     camera_names = config["camera_names"]
     max_timesteps = int(config["episode_len"])
     task_name = config["task_name"]
@@ -338,10 +343,17 @@ def eval_bc(config, ckpt_name, save_episode=True, num_rollouts=50, policy=None, 
 
 
 def forward_pass(data, policy):
-    """reference imitate_episodes.py:529-532."""
-    image_data, qpos_data, action_data, is_pad = data
+    """reference imitate_episodes.py:529-532; a 5-tuple ends in the depth frames of a use_depth dataset (the fork's
+    train_single_arm_gripper_all.py:568-588)."""
+    depth_data = None
+    if len(data) == 5:
+        image_data, qpos_data, action_data, is_pad, depth_data = data
+    else:
+        image_data, qpos_data, action_data, is_pad = data
     dev = getattr(getattr(policy, "model", None), "device", None) or "cuda"
     image_data, qpos_data, action_data, is_pad = (t.to(dev, non_blocking=True) for t in (image_data, qpos_data, action_data, is_pad))
+    if depth_data is not None:
+        return policy(qpos_data, image_data, action_data, is_pad, depth_img=depth_data.to(dev, non_blocking=True))
     return policy(qpos_data, image_data, action_data, is_pad)
 
 
@@ -353,6 +365,9 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
     policy_class = config["policy_class"]
     policy_config = config["policy_config"]
     eval_every = config.get("eval_every") or 0
+    if eval_every and policy_config.get("use_depth"):
+        print("use_depth: no environment here produces depth frames, the periodic rollouts (--eval_every) are skipped")
+        eval_every = 0
     validate_every = config["validate_every"]
     save_every = config["save_every"]
     # data parallel (one process per GPU under torch.distributed.run): every rank builds the same initial policy on its own
@@ -453,12 +468,19 @@ def build_config(args):
                          "camera_names": camera_names, "vq": args.get("use_vq", False), "vq_class": args.get("vq_class"),
                          "vq_dim": args.get("vq_dim"), "action_dim": 16, "no_encoder": args.get("no_encoder", False),
                          "state_dim": 14, "max_batch": args.get("max_batch") or args["batch_size"]}
+        if args.get("use_depth"):                    # the fork's train_single_arm_gripper_all.py:66: the names come from the task
+            depth_camera_names = task_config.get("depth_camera_names")
+            if not depth_camera_names:
+                raise ValueError(f"--use_depth: the task config of {task_name!r} lists no depth_camera_names")
+            policy_config.update(use_depth=True, depth_camera_names=list(depth_camera_names))
     elif policy_class == "Diffusion":                # reference :95-106
         policy_config = {"lr": args["lr"], "camera_names": camera_names, "action_dim": 16, "observation_horizon": 1,
                          "action_horizon": 8, "prediction_horizon": args["chunk_size"], "num_queries": args["chunk_size"],
                          "num_inference_timesteps": 10, "ema_power": 0.75, "vq": False}
     else:
         raise NotImplementedError(f"policy_class {policy_class} is outside the accelerated path (SURVEY §2)")
+    if args.get("use_depth") and policy_class != "ACT":
+        raise NotImplementedError("--use_depth: depth cameras belong to the ACT policy")
     return {"num_steps": args["num_steps"], "eval_every": args["eval_every"], "validate_every": args["validate_every"],
             "save_every": args["save_every"], "ckpt_dir": args["ckpt_dir"], "resume_ckpt_path": args.get("resume_ckpt_path"),
             "episode_len": task_config["episode_len"], "state_dim": 14, "lr": args["lr"],
@@ -491,6 +513,10 @@ def main(args):
     task_config = SIM_TASK_CONFIGS[args["task_name"]]
     camera_names, policy_class = config["camera_names"], config["policy_class"]
     dataset_dir = args.get("dataset_dir") or task_config.get("dataset_dir")
+    use_depth = bool(config["policy_config"].get("use_depth"))
+    if use_depth and not (dataset_dir and os.path.isdir(dataset_dir)):
+        raise ValueError("--use_depth needs episode files with /observations/depth_images/<cam> (--dataset_dir): the synthetic "
+                         "stand-in dataset holds no depth frames")
     if dataset_dir and os.path.isdir(dataset_dir):
         # reference imitate_episodes.py:141-147: episodes on disk (HDF5 via h5py, or .npz with the same keys), z-scored
         # qpos / actions, u8 images; batches reach the device through pinned staging on a side stream
@@ -500,7 +526,9 @@ def main(args):
                                                args.get("chunk_size") or 100, args.get("skip_mirrored_data", False),
                                                policy_class=policy_class, stats_dir_l=task_config.get("stats_dir"),
                                                sample_weights=task_config.get("sample_weights"),
-                                               train_ratio=task_config.get("train_ratio", 0.99))
+                                               train_ratio=task_config.get("train_ratio", 0.99),
+                                               depth_camera_names=config["policy_config"].get("depth_camera_names"),
+                                               use_depth=use_depth)
     else:
         train_dl = SyntheticDataset(cfg, args["batch_size"], 8, seed=args["seed"] * world + rank)     # disjoint per rank
         val_dl = SyntheticDataset(cfg, args["batch_size"], 2, seed=args["seed"] * world + rank + 100003)
@@ -543,6 +571,9 @@ if __name__ == "__main__":
     parser.add_argument("--vq_class", action="store", type=int)
     parser.add_argument("--vq_dim", action="store", type=int)
     parser.add_argument("--no_encoder", action="store_true")
+    parser.add_argument("--use_depth", action="store_true",
+                        help="ACT with one depth camera per RGB camera: the task config's depth_camera_names, raw 16-bit frames "
+                             "from /observations/depth_images/<cam>")
     # additions (rollouts count hard-coded to 10 in the reference, :156)
     parser.add_argument("--num_rollouts", action="store", type=int, default=50)
     parser.add_argument("--max_batch", action="store", type=int, default=None)

@@ -99,7 +99,7 @@ class ACTPolicy:
         pointcloud = pointcloud if self.use_pcd else None       # reference policy.py:301, 329
         if self.use_depth and depth_img is None:
             # (the reference would silently run RGB-only with a shorter sequence; the handle's token count is fixed at create)
-            raise ValueError("a use_depth policy needs depth_img float32 [B, Cd, 1, H, W]")
+            raise ValueError("a use_depth policy needs depth_img [B, Cd, 1, H, W] (float32 in about [0, 1], or raw uint16)")
         depth_img = depth_img if self.use_depth else None       # reference policy.py:275-286: ignored without use_depth
         if actions is not None:                                # training / validation (policy.py:288-320)
             eps = getattr(self, "next_eps", None)

@@ -258,6 +258,13 @@ int actmi_create_ex2(const actmi_config* cfg, const actmi_pcd_config* pcd, const
  * actmi_backward) has been enqueued.  A forward of a depth handle without a binding, or with another B, returns ACTMI_E_STATE
  * before anything is launched; so does this call on a handle created without a depth config. */
 int actmi_set_depth(actmi_handle h, const float* depth, int B);
+/* The same binding for RAW depth: uint16 [B][num_depth_cams][1][image_h][image_w] device, as sensors and episode files hold it.
+ * The forward that consumes it first finds (min, max) over all depth cameras of every sample on the device (a handle-owned
+ * [max_batch][2] table, no synchronisation, capturable), and the stem's loader applies the reference dataset's per-sample
+ * n = (d - min) / ((max - min) + 1e-6) in fp32 ahead of (n - 0.5) / 0.5: bit for bit what actmi_set_depth computes from a batch
+ * normalised that way on the host, at half the bytes.  The rules of actmi_set_depth hold; a handle may alternate the two from
+ * call to call (the last binding before a forward is the one it reads). */
+int actmi_set_depth_u16(actmi_handle h, const uint16_t* depth, int B);
 int actmi_destroy(actmi_handle h);
 const char* actmi_last_error(actmi_handle h);   /* h may be NULL: last error of a failed create */
 
@@ -387,6 +394,13 @@ int actmi_op_conv1(const void* image, int image_fmt, const float* w_oihw, const 
  * Cout a multiple of 4, <= 64; out 16-byte aligned.  fp32 products. */
 int actmi_op_conv1_depth(const float* depth, const float* w_oihw, const float* scale, const float* bias, float* out, int B,
                          int Cd, int H, int W, int Cout, int out_cam0, void* stream);
+/* per-sample extremes of a raw depth batch: depth u16 [B][n_per_sample] (any n_per_sample >= 1, any 2-byte aligned address),
+ * lohi_out f32 [B][2] = (min, max), exact.  Two small launches, no workspace, no synchronisation; B <= 65535. */
+int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int64_t n_per_sample, void* stream);
+/* the depth stem on raw u16 input: as actmi_op_conv1_depth, the loader normalising sample b with lohi[b] = (min, max) first
+ * ((d - min) / ((max - min) + 1e-6), then (n - 0.5) / 0.5, fp32) */
+int actmi_op_conv1_depth_u16(const uint16_t* depth, const float* lohi, const float* w_oihw, const float* scale, const float* bias,
+                             float* out, int B, int Cd, int H, int W, int Cout, int out_cam0, void* stream);
 /* The same stem for callers that keep its prepared weights (and may want it without the ACT path's ImageNet normalisation or
  * ReLU: the DiffusionPolicy trunk applies GroupNorm between the convolution and the ReLU and feeds x / 255 un-normalised,
  * policy.py:150-170): actmi_op_conv1_prepare fills `workspace` (>= actmi_op_conv1_workspace_floats(C, Cout) floats) once --
