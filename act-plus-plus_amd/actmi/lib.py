@@ -140,6 +140,8 @@ def load():
         "actmi_op_attention": ([C.POINTER(AttnDesc), vp], i32),
         "actmi_op_attention_bwd": ([C.POINTER(AttnBwdDesc), vp], i32),
         "actmi_op_layernorm": ([vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp], i32),
+        "actmi_op_layernorm_ex": ([vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, C.c_uint32, i32, i32,
+                                   f32, vp], i32),
         "actmi_op_maxpool3x3s2": ([vp, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_conv1": ([vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
         "actmi_op_conv1_depth": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),

@@ -62,8 +62,9 @@ def auto_splitk(M, N, K):
 
 def gemm(A, W, bias=None, scale=None, res=None, res_mod=0, relu=False, a_add=None, add_mod=0, add_ncols=0, rowmap=None,
          out=None, out_rows=None, drop_p=0.0, drop_seed=0, prec=None, w_split=False, a_scale=0.0, b_scale=0.0,
-         a_scale_dev=None, b_scale_dev=None, splitk=0):
+         a_scale_dev=None, b_scale_dev=None, splitk=0, tile_hint=0):
     """out[rowmap(m)] = act((A' @ W.T) * scale + bias + res[m % res_mod]); A [M,K], W [N,K] row-major f32 cuda.
+    tile_hint: actmi_gemm_desc.tile_hint (0 = chosen per launch shape, 1 = 128x128, 2 = 128x64, 3 = 64x64).
     splitk > 1: the contraction is split into that many plain slices which a combine pass sums in a fixed order before
     the epilogue (what the engine does for small grids); no rowmap / res_mod / dropout in that form."""
     lib = L.load()
@@ -85,6 +86,7 @@ def gemm(A, W, bias=None, scale=None, res=None, res_mod=0, relu=False, a_add=Non
         d.splitk, d.split_stride = int(splitk), M * N
         d.prec, d.b_split, d.b_scale = PREC[prec], 1 if w_split else 0, float(w_split) if w_split else float(b_scale)
         d.a_scale = float(a_scale)
+        d.tile_hint = int(tile_hint)
         L.check(lib.actmi_op_gemm(C.byref(d), L.current_stream_ptr()), None, "op_gemm")
         if out is None:
             out = torch.empty((M, N), dtype=torch.float32, device=A.device)
@@ -113,14 +115,16 @@ def gemm(A, W, bias=None, scale=None, res=None, res_mod=0, relu=False, a_add=Non
     d.a_scale = float(a_scale)
     d.a_scale_dev = a_scale_dev.data_ptr() if a_scale_dev is not None else None
     d.b_scale_dev = b_scale_dev.data_ptr() if b_scale_dev is not None else None
+    d.tile_hint = int(tile_hint)
     L.check(lib.actmi_op_gemm(C.byref(d), L.current_stream_ptr()), None, "op_gemm")
     return out
 
 
-def conv2d_with_second_source(y1, x, wf_split, w_scale, bias, stride_x=2, relu=True, splitk=0, k_tap_inner=False):
+def conv2d_with_second_source(y1, x, wf_split, w_scale, bias, stride_x=2, relu=True, splitk=0, k_tap_inner=False, tile_hint=0):
     """A ResNet block's conv2 with the block's 1x1 / stride-2 downsample branch in the same contraction (gemm.hip second
     source): y1 [G,B,H,W,C] is convolved 3x3 / s1 / p1, x [G,B,Hx,Wx,Cx] joins at stride_x as extra columns of the contraction.
-    wf_split: split16 image (built with w_scale) of [G][Cout][9*C + Cx]; bias [G,Cout].  f16x3 only.  Returns [G,B,H,W,Cout]."""
+    wf_split: split16 image (built with w_scale) of [G][Cout][9*C + Cx]; bias [G,Cout].  f16x3 only.  tile_hint as in gemm.
+    Returns [G,B,H,W,Cout]."""
     lib = L.load()
     G, B, H, W, Cc = y1.shape
     _, _, Hx, Wx, Cx = x.shape
@@ -141,6 +145,7 @@ def conv2d_with_second_source(y1, x, wf_split, w_scale, bias, stride_x=2, relu=T
         d.gA, d.gB, d.gSB, d.gC = B * H * W * Cc, Cout * Kf, Cout, gC
         d.prec, d.b_split, d.b_scale = PREC["f16x3"], 1, float(w_scale)
         d.k_tap_inner = 1 if k_tap_inner else 0
+        d.tile_hint = int(tile_hint)
         return d
     out = torch.empty((G, B, H, W, Cout), dtype=torch.float32, device=y1.device)
     if splitk and splitk > 1:
@@ -160,9 +165,9 @@ def conv2d_with_second_source(y1, x, wf_split, w_scale, bias, stride_x=2, relu=T
 
 
 def conv2d_nhwc(x, w_ohwi, scale=None, bias=None, res=None, relu=False, stride=1, pad=1, prec=None, w_split=False, b_scale=0.0,
-                k_tap_inner=False):
+                k_tap_inner=False, tile_hint=0):
     """x [G,B,H,W,Cin] camera-major NHWC; w_ohwi [G,Cout,KH,KW,Cin]; scale/bias [G,Cout]; returns [G,B,Ho,Wo,Cout].
-    k_tap_inner: the rows of w_ohwi were re-ordered by permute_conv_k (channel blocks outer, taps inner)."""
+    k_tap_inner: the rows of w_ohwi were re-ordered by permute_conv_k (channel blocks outer, taps inner); tile_hint as in gemm."""
     lib = L.load()
     G, B, H, W, Cin = x.shape
     _, Cout, KH, KW, _ = w_ohwi.shape
@@ -185,6 +190,7 @@ def conv2d_nhwc(x, w_ohwi, scale=None, bias=None, res=None, relu=False, stride=1
     # f16x3: w_split = scale of a pre-split weight image; b_scale = power-of-two scale applied to plain fp32 weights on the fly
     d.prec, d.b_split, d.b_scale = PREC[prec], 1 if w_split else 0, float(w_split) if w_split else float(b_scale)
     d.k_tap_inner = 1 if k_tap_inner else 0
+    d.tile_hint = int(tile_hint)
     L.check(lib.actmi_op_gemm(C.byref(d), L.current_stream_ptr()), None, "op_gemm(conv)")
     return out
 
@@ -355,6 +361,26 @@ def layernorm(x, w, b, res=None, res_mod=0, w2=None, b2=None, eps=1e-5):
     L.check(lib.actmi_op_layernorm(_p(x), _p(res), res_mod, _p(w), _p(b), _p(w2), _p(b2), _p(y), M, D, eps,
                                    L.current_stream_ptr()), None, "op_layernorm")
     return y
+
+
+def layernorm_ex(x, w, b, M, D, nsplit=1, split_stride=0, bias=None, res=None, res_mod=0, w2=None, b2=None, eps=1e-5, add2=None,
+                 add2_mod=0, head_w=None, head_b=None, head_n=0, flag=None, flag_bit=0, want_y2=None, want_head=None):
+    """actmi_op_layernorm_ex: LayerNorm with the fused forms of the engine.  x holds nsplit slices [M, D], slice s at element
+    offset s * split_stride, summed by the row loader (+ bias [D], + res[m % res_mod]).  add2 [rows, D]: also y2 = y +
+    add2[m % add2_mod]; head_w [head_n, D] (+ head_b): also head = y @ head_w.T + head_b, `flag` (one int32 word) gaining
+    flag_bit when a head output is not finite.  want_y2 / want_head force the outputs on without their operands (the launcher's
+    rejections).  Returns y, or (y, y2, head) with None for an absent output."""
+    lib = L.load()
+    y = torch.empty((M, D), dtype=torch.float32, device=x.device)
+    y2 = torch.empty((M, D), dtype=torch.float32, device=x.device) if (add2 is not None if want_y2 is None else want_y2) else None
+    with_head = head_w is not None if want_head is None else want_head
+    if head_w is not None and not head_n:
+        head_n = head_w.shape[0]
+    head = torch.empty((M, max(int(head_n), 1)), dtype=torch.float32, device=x.device) if with_head else None
+    L.check(lib.actmi_op_layernorm_ex(_p(x), int(nsplit), int(split_stride), _p(bias), _p(res), int(res_mod), _p(w), _p(b), _p(w2),
+                                      _p(b2), _p(y), _p(y2), _p(add2), int(add2_mod), _p(head), _p(head_w), _p(head_b), int(head_n),
+                                      _p(flag), int(flag_bit), int(M), int(D), eps, L.current_stream_ptr()), None, "op_layernorm_ex")
+    return y if (y2 is None and head is None) else (y, y2, head)
 
 
 def maxpool3x3s2(x):

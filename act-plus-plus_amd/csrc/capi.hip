@@ -337,6 +337,19 @@ int actmi_op_layernorm(const float* x, const float* res, int res_mod, const floa
     return launch_layernorm(x, res, res_mod, w, b, w2, b2, y, M, D, eps, S(stream), &g_op_error);
 }
 
+int actmi_op_layernorm_ex(const float* x, int nsplit, int64_t split_stride, const float* bias, const float* res, int res_mod,
+                          const float* w, const float* b, const float* w2, const float* b2, float* y, float* y2, const float* add2,
+                          int add2_mod, float* head_out, const float* head_w, const float* head_b, int head_n, uint32_t* flag,
+                          uint32_t flag_bit, int M, int D, float eps, void* stream) {
+    g_op_error.clear();
+    if (!x || !w || !b || !y || nsplit < 1 || res_mod < 0 || add2_mod < 0) { g_op_error = "layernorm_ex: bad argument"; return ACTMI_E_INVALID; }
+    LnExtra ex;
+    ex.y2 = y2; ex.add2 = add2; ex.add2_mod = add2_mod;
+    ex.head_out = head_out; ex.head_w = head_w; ex.head_b = head_b; ex.head_n = head_n;
+    ex.flag = flag; ex.flag_bit = flag_bit;
+    return launch_layernorm(x, res, res_mod, w, b, w2, b2, y, M, D, eps, S(stream), &g_op_error, nsplit, split_stride, bias, &ex);
+}
+
 int actmi_op_maxpool3x3s2(const float* in, float* out, int nimg, int H, int W, int C, void* stream) {
     return launch_maxpool(in, out, nimg, H, W, C, (H + 2 - 3) / 2 + 1, (W + 2 - 3) / 2 + 1, S(stream));
 }

@@ -1100,6 +1100,17 @@ int launch_modes(const GemmArgs& a, hipStream_t st) {
         };
         eL = eff(128, 128, 1.00); eM = eff(128, 64, 0.95); eS = eff(64, 64, 0.88);
     }
+    // the addend is applied per column BLOCK (use_add = n0 < add_ncols in the kernel): a tile width that does not divide
+    // add_ncols would hand the addend to the columns add_ncols .. n0 + BN - 1 as well.  Only widths BN with add_ncols % BN == 0
+    // (or add_ncols >= N: every column takes it) are candidates; launch_gemm has made sure that 64 always is one.  A forced or
+    // hinted 128-wide tile that cannot be honoured falls back to the widest width that can (128x64).
+    const bool wide_ok = AMODE != A_NADD || a.add_ncols % 128 == 0 || a.add_ncols >= a.N;
+    auto launch_tile = [&](char c) {
+        if (c == 'L' && !wide_ok) c = 'M';
+        if (c == 'L') return launch_cfg<128, 128, 64, 64, AMODE, BMODE, PREC>(a, st);
+        if (c == 'M') return launch_cfg<128, 64, 64, 32, AMODE, BMODE, PREC>(a, st);
+        return launch_cfg<64, 64, 32, 32, AMODE, BMODE, PREC>(a, st);
+    };
     // tuning aid: per-shape tile overrides "M,N,K=L|M|S;..." (ACTMI_TILE_HINTS), e.g. "4808,512,512=S;9616,512,512=M"
     static const std::string hints = getenv("ACTMI_TILE_HINTS") ? getenv("ACTMI_TILE_HINTS") : "";
     if (!hints.empty() && a.tile_hint == 0) {
@@ -1108,21 +1119,14 @@ int launch_modes(const GemmArgs& a, hipStream_t st) {
         const size_t pos = hints.find(key);
         if (pos != std::string::npos && (pos == 0 || hints[pos - 1] == ';')) {
             const char c = hints[pos + strlen(key)];
-            if (c == 'L') return launch_cfg<128, 128, 64, 64, AMODE, BMODE, PREC>(a, st);
-            if (c == 'M') return launch_cfg<128, 64, 64, 32, AMODE, BMODE, PREC>(a, st);
-            if (c == 'S') return launch_cfg<64, 64, 32, 32, AMODE, BMODE, PREC>(a, st);
+            if (c == 'L' || c == 'M' || c == 'S') return launch_tile(c);
         }
     }
     static const char* force = getenv("ACTMI_GEMM_CFG");      // tuning aid: L / M / S
-    if (force && force[0] == 'L') return launch_cfg<128, 128, 64, 64, AMODE, BMODE, PREC>(a, st);
-    if (force && force[0] == 'M') return launch_cfg<128, 64, 64, 32, AMODE, BMODE, PREC>(a, st);
-    if (force && force[0] == 'S') return launch_cfg<64, 64, 32, 32, AMODE, BMODE, PREC>(a, st);
-    if (a.tile_hint == 1) return launch_cfg<128, 128, 64, 64, AMODE, BMODE, PREC>(a, st);
-    if (a.tile_hint == 2) return launch_cfg<128, 64, 64, 32, AMODE, BMODE, PREC>(a, st);
-    if (a.tile_hint == 3) return launch_cfg<64, 64, 32, 32, AMODE, BMODE, PREC>(a, st);
-    if (eL >= eM && eL >= eS) return launch_cfg<128, 128, 64, 64, AMODE, BMODE, PREC>(a, st);
-    if (eM >= eS) return launch_cfg<128, 64, 64, 32, AMODE, BMODE, PREC>(a, st);
-    return launch_cfg<64, 64, 32, 32, AMODE, BMODE, PREC>(a, st);
+    if (force && (force[0] == 'L' || force[0] == 'M' || force[0] == 'S')) return launch_tile(force[0]);
+    if (a.tile_hint >= 1 && a.tile_hint <= 3) return launch_tile("LMS"[a.tile_hint - 1]);
+    if (wide_ok && eL >= eM && eL >= eS) return launch_tile('L');
+    return launch_tile(eM >= eS ? 'M' : 'S');
 }
 
 }  // namespace
@@ -1199,6 +1203,8 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t st, std::string* err) {
             // zero-filled beyond K, so the pad never contributes)
             if ((a.K & 3) && a.lda < ((a.K + 3) & ~3)) return fail("K % 4 != 0 needs rows padded to a multiple of 4");
             if (a.A_add && ((a.ld_add & 3) || a.add_mod <= 0 || ((uintptr_t)a.A_add & 15))) return fail("bad addend");
+            // the addend is applied per column block and the narrowest block is 64 columns wide (launch_modes)
+            if (a.A_add && a.add_ncols > 0 && a.add_ncols < a.N && (a.add_ncols % 64)) return fail("add_ncols must be a multiple of 64 unless it covers every column (add_ncols >= N)");
             if (a.A_alt && (a.A_add || a.a_rowmap || (a.alt_ncols % 128) || ((uintptr_t)a.A_alt & 15))) return fail("A_alt: no addend / row gather, alt_ncols a multiple of 128");
             amode = A_N;
         } else if (a.mode == 1) {

@@ -77,6 +77,9 @@ typedef struct actmi_gemm_desc {
     const float* A_add;        /* optional: A'[m][k] = A[m][k] + A_add[m % add_mod][k] for columns n < add_ncols */
     int64_t ld_add;
     int32_t add_mod;
+    /* the addend is applied per column block of the tile: add_ncols must be a multiple of 64 unless it covers every column
+     * (add_ncols >= N), else the launch is rejected with ACTMI_E_SHAPE; the 128-wide tiles are only chosen (or honoured as a
+     * hint) when add_ncols is a multiple of 128 or covers every column */
     int32_t add_ncols;
     const float* Bw;           /* [N][K] row-major (torch Linear layout) unless tb */
     int64_t ldb;
@@ -384,6 +387,18 @@ typedef struct actmi_attn_bwd_desc {
 int actmi_op_attention_bwd(const actmi_attn_bwd_desc* d, void* stream);
 int actmi_op_layernorm(const float* x, const float* res, int res_mod, const float* w, const float* b, const float* w2,
                        const float* b2, float* y, int M, int D, float eps, void* stream);
+/* actmi_op_layernorm with the fused forms the engine launches (csrc/layernorm.hip):
+ *   x given as nsplit slices of a sliced split-K product, slice s at x + s*split_stride ([M][D] each; split_stride a multiple of
+ *   4, ignored when nsplit == 1): the row loader sums them in slice order, then adds bias[D] (optional), then res -- the sequence
+ *   of actmi_op_splitk_combine, so y has the bits of combine followed by actmi_op_layernorm;
+ *   y2 (optional, needs add2): y2[m] = y[m] + add2[m % add2_mod] (add2_mod = 0: add2[m]), the x + pos operand of the next block;
+ *   head_out (optional, needs head_w [head_n][D], head_n >= 1; head_b [head_n] or NULL): head_out[m][n] = y[m] . head_w[n] +
+ *   head_b[n] in fp32 FMAs on the row in registers; flag (optional): flag_bit is ORed into *flag when a head output is NaN or
+ *   infinite.  y2, add2 and head_w must be 16-byte aligned. */
+int actmi_op_layernorm_ex(const float* x, int nsplit, int64_t split_stride, const float* bias, const float* res, int res_mod,
+                          const float* w, const float* b, const float* w2, const float* b2, float* y, float* y2, const float* add2,
+                          int add2_mod, float* head_out, const float* head_w, const float* head_b, int head_n, uint32_t* flag,
+                          uint32_t flag_bit, int M, int D, float eps, void* stream);
 int actmi_op_maxpool3x3s2(const float* in_nhwc, float* out_nhwc, int nimg, int H, int W, int C, void* stream);
 /* conv1: w is the torch OIHW [C][Cout][3][7][7] weight, scale/bias the folded FrozenBN; out camera-major NHWC */
 int actmi_op_conv1(const void* image, int image_fmt, const float* w_oihw, const float* scale, const float* bias,

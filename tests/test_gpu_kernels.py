@@ -574,3 +574,80 @@ def test_attention_backward_dropout_masks_match_the_forward():
         fd, an = float((fp - fm) / (2 * eps)), float((gx.double() * d.double()).sum())
         assert abs(fd - an) <= 5e-3 * max(1.0, abs(an)), (idx, fd, an)
 
+
+
+# ---- attention forward: the split-KV path at its edges ----------------------------------------------------------------------
+def attn_split_rule(B, H, Nq, Nk):
+    """launch_attention's split rule (attn.hip) restated: aim at 1024 workgroups, at most 8 splits, at most tiles / 2, each split
+    ceil(tiles / nsplit) key tiles of 64.  -> (tiles, nsplit, chunk).  A retune of the dispatcher must show up here: the cases
+    below assert on it that they still reach the path they were written for."""
+    blocks = ((Nq + 127) // 128) * H * B
+    tiles = (Nk + 63) // 64
+    nsplit = max(1, min(8, (1024 + blocks - 1) // blocks))
+    if nsplit > tiles // 2:
+        nsplit = max(1, tiles // 2)
+    return tiles, nsplit, (tiles + nsplit - 1) // nsplit * 64
+
+
+def _attn_ref64(q, k, v, H, hd, dead):
+    """float64 softmax(q k^T / sqrt(hd) + mask) v and its log-sum-exp; q [B,Nq,D], k / v [B,Nk,D], dead broadcastable to
+    [B,H,Nq,Nk] (True = masked)"""
+    B, Nq, _ = q.shape
+    Nk = k.shape[1]
+    qq = q.double().view(B, Nq, H, hd).transpose(1, 2)
+    kk = k.double().reshape(B, Nk, H, hd).transpose(1, 2)
+    vv = v.double().reshape(B, Nk, H, hd).transpose(1, 2)
+    s = (qq @ kk.transpose(-1, -2) / hd ** 0.5).masked_fill(dead, float("-inf"))
+    return (torch.softmax(s, -1) @ vv).transpose(1, 2).reshape(B, Nq, H * hd), torch.logsumexp(s, -1)
+
+
+@pytest.mark.parametrize("hd", [16, 32, 64])
+@pytest.mark.parametrize("prec", PRECS)
+def test_attention_split_kv_with_key_padding_mask(prec, hd):
+    """Nk = 530 is 9 key tiles in 4 splits of 3 tiles (chunk 192): split 3 begins at key 576 and owns NO key.  Batch 0 masks a
+    ragged tail; batch 1 masks all of keys 192 .. 383 -- split 1 hands (m = -inf, l = 0) to the combine pass -- plus the tail.
+    Output and log-sum-exp finite and within 3e-6 of float64, with the split, without it, and with a shared query."""
+    B, H, Nq, Nk = 2, 2, 40, 530
+    tiles, nsplit, chunk = attn_split_rule(B, H, Nq, Nk)
+    assert (tiles, nsplit, chunk) == (9, 4, 192) and (nsplit - 1) * chunk >= Nk, "the case must keep a split that owns no key"
+    g = torch.Generator().manual_seed(hd)
+    D = H * hd
+    q = torch.randn(B, Nq, D, generator=g)
+    kv = torch.randn(B, Nk, 2 * D, generator=g)                   # interleaved K | V rows: row stride 2 * D
+    kpm = torch.zeros(B, Nk, dtype=torch.bool)
+    kpm[0, 517:] = True
+    kpm[1, chunk:2 * chunk] = True                                 # the whole key range of split 1
+    kpm[1, 501:] = True
+    assert bool((~kpm).any(1).all()) and bool(kpm[1, chunk:2 * chunk].all())
+    d = dev()
+    kvd, kd = kv.to(d), kpm.to(torch.uint8).to(d)
+    for shared in (False, True):
+        qs = q[0] if shared else q
+        exp, lse_exp = _attn_ref64(qs.unsqueeze(0).expand(B, -1, -1) if shared else qs, kv[..., :D], kv[..., D:], H, hd,
+                                   kpm.view(B, 1, 1, Nk))
+        assert bool(torch.isfinite(exp).all())
+        for split in (True, False):
+            got, lse = ops.attention(qs.to(d), kvd[..., :D], kvd[..., D:], H, kpm=kd, q_shared=shared, want_lse=True, split=split,
+                                     prec=prec)
+            e, el = rel_err(got, exp), rel_err(lse, lse_exp)
+            print(f"attention mask + split-KV {prec} hd={hd} shared={shared} split={split}: out {e:.2e}, lse {el:.2e} (bound 3.0e-06)")
+            assert bool(torch.isfinite(got).all()) and bool(torch.isfinite(lse).all())
+            assert e < 3e-6 and el < 3e-6
+
+
+@pytest.mark.parametrize("hd", [16, 32, 64])
+@pytest.mark.parametrize("prec", PRECS)
+def test_attention_split_kv_causal(prec, hd):
+    """N = 200 is 4 key tiles in 2 splits of 128 keys: the queries 0 .. 127 see nothing of the second split"""
+    B, H, N = 1, 2, 200
+    tiles, nsplit, chunk = attn_split_rule(B, H, N, N)
+    assert (tiles, nsplit, chunk) == (4, 2, 128), "the case must split, with a second split that is dead for the first queries"
+    g = torch.Generator().manual_seed(100 + hd)
+    D = H * hd
+    q, k, v = (torch.randn(B, N, D, generator=g) for _ in range(3))
+    exp, _ = _attn_ref64(q, k, v, H, hd, torch.triu(torch.ones(N, N, dtype=torch.bool), diagonal=1))
+    d = dev()
+    got = ops.attention(q.to(d), k.to(d), v.to(d), H, causal=True, prec=prec)
+    e = rel_err(got, exp)
+    print(f"attention causal + split-KV {prec} hd={hd}: {e:.2e} (bound 3.0e-06)")
+    assert bool(torch.isfinite(got).all()) and e < 3e-6
