@@ -12,6 +12,13 @@ Differences, all on the host side of the step:
   stores an unsigned integer of at most 16 bits: the engine finds every sample's min / max on the device and fuses the
   reference's per-sample ``(d - min) / (max - min + 1e-6)`` into the depth stem's loader -- ``f32_depth=True`` (and any other
   stored dtype) reproduces the reference contract, f32 normalised on the host;
+* point clouds (``use_pcd``; the fork's ``/observations/pointcloud/<name>/{xyz, rgb, padding_mask}``, one fused cloud) come
+  with their **valid count**: the recorder pads every frame's cloud with zero rows up to the episode's largest, and the stored
+  ``padding_mask`` (True = a point) says how many rows are points.  The fork's dataset ignores the mask, so its policy sees the
+  zero rows as points; here the mask is honoured unless ``pcd_ignore_mask=True``, because the live cloud of deployment has no
+  padding.  ``collate_pcd`` pads a batch's clouds with zero rows to the batch's largest stored row count and the batch becomes
+  the 7-tuple ``(image, qpos, action, is_pad, pcd_xyz [B, P, 3] f32, pcd_rgb [B, P, 3] f32, pcd_n [B] int32)``; the engine
+  takes the maximum over the first ``pcd_n`` rows of every sample only;
 * batches are collated into **pinned** buffers and handed to the device by ``DevicePrefetcher`` on a side stream while
   the previous step computes (the reference moves 944 MB of f32 images per batch-64 step synchronously);
 * episode files are opened through ``open_episode``: HDF5 via ``h5py`` when it is importable (the reference's format:
@@ -147,10 +154,15 @@ class EpisodicDataset(torch.utils.data.Dataset):
     """utils.py:41-174.  ``__getitem__`` returns (image, qpos, action, is_pad); image is u8 ``[C,H,W,3]`` unless
     ``f32_images``.  With ``use_depth`` (the fork's depth dataset) a fifth entry follows: the frames of ``depth_camera_names``,
     raw uint16 ``[Cd,1,H,W]`` when the episode stores an unsigned integer of at most 16 bits, else (or with ``f32_depth``)
-    float32 normalised by the sample's own minimum and maximum over all depth cameras."""
+    float32 normalised by the sample's own minimum and maximum over all depth cameras.  With ``use_pcd`` (the fork's point-cloud
+    dataset, utils_arm_gripper_all.py:90-99, 153-156) three entries follow the first four instead: xyz ``[N, 3]`` and rgb ``[N, 3]``
+    float32 (colours stay 0..255) of the one cloud in ``pointcloud_names``, every stored row of it, and the int64 scalar ``n``, the
+    number of rows that are points (the stored ``padding_mask``'s count, or N without a mask or with ``pcd_ignore_mask``); batch
+    such samples with ``collate_pcd``."""
 
     def __init__(self, dataset_path_list, camera_names, norm_stats, episode_ids, episode_len, chunk_size, policy_class,
-                 f32_images=False, depth_camera_names=None, use_depth=False, f32_depth=False):
+                 f32_images=False, depth_camera_names=None, use_depth=False, f32_depth=False, pointcloud_names=None, use_pcd=False,
+                 max_points=None, pcd_ignore_mask=False):
         self.episode_ids = episode_ids
         self.dataset_path_list = dataset_path_list
         self.camera_names = camera_names
@@ -166,6 +178,17 @@ class EpisodicDataset(torch.utils.data.Dataset):
         self.f32_depth = f32_depth
         if self.use_depth and not self.depth_camera_names:
             raise ValueError("use_depth needs depth_camera_names (the task config's list of /observations/depth_images/<cam>)")
+        self.use_pcd = bool(use_pcd)
+        self.pointcloud_names = list(pointcloud_names) if pointcloud_names else []
+        self.max_points = None if max_points is None else int(max_points)
+        self.pcd_ignore_mask = bool(pcd_ignore_mask)
+        if self.use_pcd:
+            if len(self.pointcloud_names) != 1:
+                # the fork's training step takes the one fused cloud (train_single_arm_gripper_all.py:576-591)
+                raise ValueError(f"use_pcd needs exactly one pointcloud name (/observations/pointcloud/<name>), got "
+                                 f"{self.pointcloud_names}")
+            if self.use_depth:
+                raise NotImplementedError("use_depth together with use_pcd is not supported")
         if policy_class == "Diffusion":
             raise NotImplementedError("the Diffusion augmentations (torchvision transforms) are outside this path")
         self._stats_t = {k: torch.as_tensor(np.asarray(norm_stats[k]), dtype=torch.float32)
@@ -195,6 +218,7 @@ class EpisodicDataset(torch.utils.data.Dataset):
             images = [np.asarray(root[f"/observations/images/{cam}"][start_ts]) for cam in self.camera_names]
             depths = [np.asarray(root[f"/observations/depth_images/{cam}"][start_ts]) for cam in self.depth_camera_names] \
                 if self.use_depth else None
+            cloud = self._read_cloud(root, start_ts, dataset_path) if self.use_pcd else None
         if compressed:                                            # utils.py:104-107
             images = [imdecode_bgr(buf) for buf in images]
             if depths is not None:                                # three equal channels of an 8-bit decode; channel 0 is kept below
@@ -222,7 +246,34 @@ class EpisodicDataset(torch.utils.data.Dataset):
         qpos_data = (qpos_data - t["qpos_mean"]) / t["qpos_std"]
         if depths is not None:
             return image_data, qpos_data, action_data, is_pad, self._depth_data(depths)
+        if cloud is not None:
+            return (image_data, qpos_data, action_data, is_pad) + cloud
         return image_data, qpos_data, action_data, is_pad
+
+    def _read_cloud(self, root, start_ts, dataset_path):
+        """the cloud of one sample: (xyz [N, 3] f32, rgb [N, 3] f32, n) -- every stored row, and how many of them are points"""
+        base = f"/observations/pointcloud/{self.pointcloud_names[0]}"
+        xyz = np.asarray(root[f"{base}/xyz"][start_ts])
+        rgb = np.asarray(root[f"{base}/rgb"][start_ts])
+        where = f"{dataset_path} (timestep {start_ts})"
+        if xyz.ndim != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape:
+            raise ValueError(f"{where}: point cloud xyz {xyz.shape} / rgb {rgb.shape}, expected two [N, 3] arrays")
+        N = xyz.shape[0]
+        n = N
+        if not self.pcd_ignore_mask and f"{base}/padding_mask" in root:
+            mask = np.asarray(root[f"{base}/padding_mask"][start_ts]).astype(bool).reshape(-1)
+            if mask.shape[0] != N:
+                raise ValueError(f"{where}: padding_mask of {mask.shape[0]} rows for a cloud of {N}")
+            n = int(mask.sum())
+            if not mask[:n].all():                                 # the recorder writes the points first, then the zero rows
+                raise ValueError(f"{where}: padding_mask is not a prefix (True rows first): the valid points cannot be given as a count")
+        if n == 0:
+            raise ValueError(f"{where}: the point cloud has no valid point")
+        if self.max_points is not None and N > self.max_points:
+            raise ValueError(f"{where}: the point cloud stores {N} rows, more than max_points {self.max_points} (no silent truncation: "
+                             "raise --max_points or down-sample the recording)")
+        return (torch.from_numpy(np.ascontiguousarray(xyz, dtype=np.float32)),       # .float(), utils_arm_gripper_all.py:153-156
+                torch.from_numpy(np.ascontiguousarray(rgb, dtype=np.float32)), torch.tensor(n, dtype=torch.int64))
 
     def _depth_data(self, depths):
         """the depth frames of one sample -> [Cd, 1, H, W]: a 3-D frame keeps channel 0; raw uint16 for the device-side
@@ -234,6 +285,21 @@ class EpisodicDataset(torch.utils.data.Dataset):
         return (d - d.min()) / (d.max() - d.min() + 1e-6)
 
 
+def collate_pcd(samples):
+    """Batches the 7-entry samples of a ``use_pcd`` dataset: the first four entries as the default collation does, the clouds padded
+    with ZERO rows to the batch's largest stored row count P (episodes differ in theirs) -> (image, qpos, action, is_pad,
+    pcd_xyz [B, P, 3] f32, pcd_rgb [B, P, 3] f32, pcd_n [B] int32)."""
+    from torch.utils.data import default_collate
+    head = default_collate([s[:4] for s in samples])
+    B, P = len(samples), max(int(s[4].shape[0]) for s in samples)
+    xyz, rgb = torch.zeros((B, P, 3), dtype=torch.float32), torch.zeros((B, P, 3), dtype=torch.float32)
+    for b, s in enumerate(samples):
+        xyz[b, :s[4].shape[0]] = s[4]
+        rgb[b, :s[5].shape[0]] = s[5]
+    n = torch.tensor([int(s[6]) for s in samples], dtype=torch.int32)
+    return tuple(head) + (xyz, rgb, n)
+
+
 def flatten_list(l):
     return [item for sublist in l for item in sublist]
 
@@ -241,9 +307,10 @@ def flatten_list(l):
 def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_size_val, chunk_size,
               skip_mirrored_data=False, load_pretrain=False, policy_class=None, stats_dir_l=None, sample_weights=None,
               train_ratio=0.99, num_workers=2, f32_images=False, rng=None, depth_camera_names=None, use_depth=False,
-              f32_depth=False):
+              f32_depth=False, pointcloud_names=None, use_pcd=False, max_points=None, pcd_ignore_mask=False):
     """utils.py:249-301.  Returns (train_dataloader, val_dataloader, norm_stats, is_sim).  ``use_depth``: the batches are
-    5-tuples that end in the depth frames of ``depth_camera_names`` (EpisodicDataset)."""
+    5-tuples that end in the depth frames of ``depth_camera_names`` (EpisodicDataset).  ``use_pcd``: 7-tuples that end in the
+    padded clouds and their valid counts (collate_pcd)."""
     rng = rng or np.random
     if isinstance(dataset_dir_l, str):
         dataset_dir_l = [dataset_dir_l]
@@ -273,14 +340,17 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
         stats_dir_l = [stats_dir_l]
     norm_stats, _ = get_norm_stats(flatten_list([find_all_hdf5(d, skip_mirrored_data) for d in stats_dir_l]))
     print(f"Norm stats from: {stats_dir_l}")
+    pcd_kw = dict(pointcloud_names=pointcloud_names, use_pcd=use_pcd, max_points=max_points, pcd_ignore_mask=pcd_ignore_mask)
     train_dataset = EpisodicDataset(dataset_path_list, camera_names, norm_stats, train_episode_ids, train_episode_len,
-                                    chunk_size, policy_class, f32_images, depth_camera_names, use_depth, f32_depth)
+                                    chunk_size, policy_class, f32_images, depth_camera_names, use_depth, f32_depth, **pcd_kw)
     val_dataset = EpisodicDataset(dataset_path_list, camera_names, norm_stats, val_episode_ids, val_episode_len,
-                                  chunk_size, policy_class, f32_images, depth_camera_names, use_depth, f32_depth)
+                                  chunk_size, policy_class, f32_images, depth_camera_names, use_depth, f32_depth, **pcd_kw)
     from torch.utils.data import DataLoader
     kw = dict(pin_memory=torch.cuda.is_available(), num_workers=num_workers)
     if num_workers > 0:
         kw["prefetch_factor"] = 2
+    if use_pcd:
+        kw["collate_fn"] = collate_pcd
     train_dataloader = DataLoader(train_dataset, batch_sampler=BatchSampler(batch_size_train, train_episode_len_l,
                                                                              sample_weights, rng), **kw)
     val_dataloader = DataLoader(val_dataset, batch_sampler=BatchSampler(batch_size_val, val_episode_len_l, None, rng), **kw)

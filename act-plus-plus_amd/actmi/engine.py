@@ -165,7 +165,10 @@ class ACTEngine:
 
     def _bind_pointcloud(self, pointcloud, B: int):
         """Check the clouds of a use_pcd engine ({"xyz": [B, P, 3], "rgb": [B, P, 3]} float32 device tensors) and bind them for
-        the next forward (actmi_set_pointcloud).  Returns the tensors the library will read."""
+        the next forward (actmi_set_pointcloud_n).  Returns the tensors the library will read.  Ragged clouds padded to a common P
+        carry "n": int32 [B] on the engine's device, the number of points of every sample (rows at or behind it: finite padding,
+        zeros by convention).  The library reads it on the device; its values are not checked here -- that would synchronise --
+        and are clamped to [1, P] where they are read."""
         if not self.cfg.use_pcd:
             if pointcloud is not None:
                 raise ValueError("pointcloud given to an engine whose config has use_pcd=False")
@@ -186,10 +189,19 @@ class ACTEngine:
             raise ValueError(f"pointcloud['rgb'] shape {tuple(rgb.shape)} != {(B, P, 3)}")
         if P < 1 or P > self.max_points:
             raise ValueError(f"{P} points per sample: needs 1 <= P <= max_points {self.max_points}")
+        n = pointcloud.get("n")
+        if n is not None:
+            if not isinstance(n, torch.Tensor) or n.dtype != torch.int32:
+                raise TypeError(f"pointcloud['n'] must be an int32 tensor, got {getattr(n, 'dtype', type(n))}")
+            if not n.is_cuda:
+                raise ValueError("pointcloud['n'] must be a CUDA tensor on the engine's device")
+            self._check_dev(**{"pointcloud['n']": n})
+            if tuple(n.shape) != (B,) or not n.is_contiguous():
+                raise ValueError(f"pointcloud['n'] shape {tuple(n.shape)} != {(B,)} (contiguous)")
         xyz, rgb = xyz.contiguous(), rgb.contiguous()
-        L.check(self.lib.actmi_set_pointcloud(self.h, C.c_void_p(xyz.data_ptr()), C.c_void_p(rgb.data_ptr()), B, P), self.h,
-                "set_pointcloud")
-        return xyz, rgb
+        L.check(self.lib.actmi_set_pointcloud_n(self.h, C.c_void_p(xyz.data_ptr()), C.c_void_p(rgb.data_ptr()),
+                                                C.c_void_p(n.data_ptr() if n is not None else 0), B, P), self.h, "set_pointcloud_n")
+        return xyz, rgb, n
 
     def _depth_shape(self, B: int):
         cfg = self.cfg
@@ -268,10 +280,12 @@ class ACTEngine:
         L.check(self.lib.actmi_set_forward_phase(self.h, int(phase)), self.h, "set_forward_phase")
 
     def capture_infer(self, batch: int, image_dtype=torch.uint8, with_ensemble=None, statics=None, phase: int = 0,
-                      num_points: int = None, depth_dtype=torch.float32, static_depth=None):
+                      num_points: int = None, depth_dtype=torch.float32, static_depth=None, static_cloud=None):
         """Capture one forward (optionally + the temporal-ensemble kernel) into a hipGraph and return
         ``replay(qpos, image) -> a_hat`` that copies into static inputs and replays.  A use_pcd engine captures static
-        xyz / rgb buffers of ``num_points`` points (default max_points) and replays ``replay(qpos, image, pointcloud)``.  A use_depth
+        xyz / rgb buffers of ``num_points`` points (default max_points) and a static int32 counts buffer ``n`` (filled with
+        ``num_points``), and replays ``replay(qpos, image, pointcloud)``: ``pointcloud["n"]``, when given, is copied into the counts
+        buffer, otherwise the buffer is refilled with ``num_points`` (every row a point).  A use_depth
         engine captures a static depth buffer of ``depth_dtype`` (float32 or uint16; or the caller's ``static_depth``) and replays
         ``replay(qpos, image, depth_img=...)`` with a batch of exactly that dtype.  The forward path allocates
         nothing and never synchronises, so the whole step is one graph launch (removes ~60 kernel-launch gaps; matters
@@ -298,7 +312,12 @@ class ACTEngine:
         s_cloud = None
         if cfg.use_pcd:
             npts = self.max_points if num_points is None else int(num_points)
-            s_cloud = {k: torch.zeros((batch, npts, 3), dtype=torch.float32, device=dev) for k in ("xyz", "rgb")}
+            if static_cloud is not None:
+                s_cloud = static_cloud
+                npts = s_cloud["xyz"].shape[1]
+            else:
+                s_cloud = {k: torch.zeros((batch, npts, 3), dtype=torch.float32, device=dev) for k in ("xyz", "rgb")}
+                s_cloud["n"] = torch.full((batch,), npts, dtype=torch.int32, device=dev)
         # warm-up on a side stream (first launches set function attributes; not allowed during capture)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -351,6 +370,16 @@ class ACTEngine:
                                          f"{tuple(s_cloud[k].shape)}")
                     if pointcloud[k].data_ptr() != s_cloud[k].data_ptr():
                         s_cloud[k].copy_(pointcloud[k], non_blocking=True)
+                n = pointcloud.get("n")
+                if n is None:
+                    s_cloud["n"].fill_(npts)                  # (the graph reads the buffer on the device: every row a point)
+                else:
+                    if n.dtype != torch.int32:
+                        raise TypeError(f"pointcloud['n'] must be an int32 tensor, got {n.dtype}")
+                    if tuple(n.shape) != tuple(s_cloud["n"].shape):
+                        raise ValueError(f"pointcloud['n'] shape {tuple(n.shape)} != the captured {tuple(s_cloud['n'].shape)}")
+                    if n.data_ptr() != s_cloud["n"].data_ptr():
+                        s_cloud["n"].copy_(n, non_blocking=True)
             graph.replay()
             return (s_out, ens_out) if with_ensemble is not None else s_out
 
@@ -669,14 +698,25 @@ class InferPipeline:
     slot then owns a device depth buffer that both of its graphs share, ``feed(qpos, image, depth_host=...)`` copies it with the
     frame, and ``next_inputs`` is (qpos_host, image_host, depth_host).
 
+    A use_pcd engine takes ``num_points=P``: every slot then owns device clouds ``xyz`` / ``rgb`` [B, P, 3] f32 and counts ``n`` [B]
+    int32 that both of its graphs share (the PointNet runs in forward phase 1), ``feed(qpos, image, cloud_host={"xyz", "rgb",
+    "n"})`` copies them with the frame -- pinned host tensors, clouds padded to P with zero rows, ``n`` int32 with 1 <= n <= P,
+    checked on the host -- and ``next_inputs`` is (qpos_host, image_host, cloud_host).  B * P * 24 + 4 B bytes a step: 786 KB at
+    B = 8, P = 4096, beside 29.5 MB of frames.
+
     No host synchronisation anywhere; the pinned host tensors of a feed must stay untouched until the step AFTER the one they were
     passed to has been issued and `pipe.copied(k)` has completed (or simply use one host buffer per step in flight).  Outputs of
     step t stay valid until step t + 2 is issued."""
 
     def __init__(self, engine: "ACTEngine", batch: int, with_ensemble=None, image_dtype=torch.uint8, copy_stream_candidates: int = 8,
-                 depth_dtype=None):
-        if engine.cfg.use_pcd:
-            raise NotImplementedError("InferPipeline has no host feed for point clouds yet (use capture_infer)")
+                 depth_dtype=None, num_points: int = None):
+        if engine.cfg.use_pcd and num_points is None:
+            raise NotImplementedError("InferPipeline feeds no point clouds (use capture_infer), unless num_points=P asks for "
+                                      "cloud buffers of P points per sample")
+        if num_points is not None and not engine.cfg.use_pcd:
+            raise ValueError("num_points given for an engine whose config has use_pcd=False")
+        if num_points is not None and not 1 <= int(num_points) <= engine.max_points:
+            raise ValueError(f"num_points {num_points}: needs 1 <= P <= max_points {engine.max_points}")
         if engine.cfg.num_depth_cams and depth_dtype is None:
             raise NotImplementedError("InferPipeline has no host feed for depth frames yet (use capture_infer), unless "
                                       "depth_dtype=torch.uint16 / torch.float32 asks for one")
@@ -690,15 +730,23 @@ class InferPipeline:
                 (batch, cfg.num_cams, 3, cfg.image_h, cfg.image_w)
         self.slots = []
         self.depth = []                                             # slot k's device depth buffer (depth engines)
+        self.cloud = []                                             # slot k's device clouds and counts {"xyz", "rgb", "n"} (use_pcd)
+        P = int(num_points) if num_points is not None else None
         for _ in range(2):
             st = (torch.zeros((batch, cfg.state_dim), dtype=torch.float32, device=dev), torch.zeros(shape, dtype=image_dtype, device=dev),
                   torch.empty((batch, cfg.num_queries, cfg.action_dim), dtype=torch.float32, device=dev))
             s_depth = torch.zeros(engine._depth_shape(batch), dtype=depth_dtype, device=dev) if depth_dtype is not None else None
-            trunk = engine.capture_infer(batch, image_dtype=image_dtype, statics=st, phase=1, static_depth=s_depth)
+            s_cloud = None
+            if P is not None:
+                s_cloud = {k: torch.zeros((batch, P, 3), dtype=torch.float32, device=dev) for k in ("xyz", "rgb")}
+                s_cloud["n"] = torch.full((batch,), P, dtype=torch.int32, device=dev)
+            trunk = engine.capture_infer(batch, image_dtype=image_dtype, statics=st, phase=1, static_depth=s_depth,
+                                         static_cloud=s_cloud)
             rest = engine.capture_infer(batch, image_dtype=image_dtype, with_ensemble=with_ensemble, statics=st, phase=2,
-                                        static_depth=s_depth)
+                                        static_depth=s_depth, static_cloud=s_cloud)
             self.slots.append((st, trunk, rest))
             self.depth.append(s_depth)
+            self.cloud.append(s_cloud)
         self.ev_copy = [torch.cuda.Event() for _ in range(2)]       # slot k's inputs have landed
         self.ev_trunk = [torch.cuda.Event() for _ in range(2)]      # slot k's trunk has run: its inputs are dead
         self.fed = [False, False]
@@ -721,6 +769,11 @@ class InferPipeline:
         hq, him = torch.zeros(q0.shape, dtype=q0.dtype).pin_memory(), torch.zeros(im0.shape, dtype=im0.dtype).pin_memory()
         d0 = self.depth[0]
         nxt = (hq, him) if d0 is None else (hq, him, torch.zeros(d0.shape, dtype=d0.dtype).pin_memory())
+        c0 = self.cloud[0]
+        if c0 is not None:                                          # the clouds cross with the frame: time them with it
+            hc = {k: torch.zeros(c0[k].shape, dtype=c0[k].dtype).pin_memory() for k in ("xyz", "rgb")}
+            hc["n"] = torch.full(c0["n"].shape, c0["xyz"].shape[1], dtype=torch.int32).pin_memory()
+            nxt = (hq, him, hc)
         trials = []
         for _ in range(n_cand):
             self.copy_stream = cs = torch.cuda.Stream(device=dev)
@@ -728,7 +781,7 @@ class InferPipeline:
             for rep in range(2):                                    # (the first round also warms the graphs up)
                 torch.cuda.synchronize(dev)
                 t0 = time.perf_counter()
-                self.feed(*nxt[:2], depth_host=nxt[2] if d0 is not None else None)
+                self.feed(*nxt[:2], depth_host=nxt[2] if d0 is not None else None, cloud_host=nxt[2] if c0 is not None else None)
                 for i in range(12):
                     self.step(next_inputs=nxt if i < 11 else None)
                 torch.cuda.synchronize(dev)
@@ -740,10 +793,12 @@ class InferPipeline:
         best = min(trials, key=lambda t: t[0])
         return best[1], [round(t[0] * 1e3, 4) for t in trials]
 
-    def feed(self, qpos_host, image_host, slot=None, *, depth_host=None):
+    def feed(self, qpos_host, image_host, slot=None, *, depth_host=None, cloud_host=None):
         """enqueue the copy of one step's inputs (pinned host tensors) into slot `slot` (default: the slot the next step() runs
         from); it starts once the trunk that read the slot last has run AND the step in flight has left its own trunk.  A depth
-        pipeline needs `depth_host` [B, Cd, 1, H, W] of the pipeline's depth_dtype: it crosses between the same events as the frame"""
+        pipeline needs `depth_host` [B, Cd, 1, H, W] of the pipeline's depth_dtype: it crosses between the same events as the frame.
+        A point-cloud pipeline needs `cloud_host` {"xyz", "rgb": [B, P, 3] f32, "n": [B] int32}: clouds padded to the pipeline's P
+        with zero rows, 1 <= n <= P (a host tensor: checked here); the three copies cross between those events too"""
         k = self.k_run if slot is None else slot
         s_qpos, s_img, _ = self.slots[k][0]
         s_depth = self.depth[k]
@@ -756,6 +811,24 @@ class InferPipeline:
             if depth_host.dtype != s_depth.dtype or tuple(depth_host.shape) != tuple(s_depth.shape):
                 raise ValueError(f"depth_host is {depth_host.dtype} {tuple(depth_host.shape)}, the pipeline's depth buffer "
                                  f"{s_depth.dtype} {tuple(s_depth.shape)}")
+        s_cloud = self.cloud[k]
+        if s_cloud is None:
+            if cloud_host is not None:
+                raise ValueError("cloud_host given to a pipeline without a point-cloud feed")
+        else:
+            if cloud_host is None:
+                raise ValueError("this pipeline feeds a use_pcd engine: feed(qpos_host, image_host, cloud_host={'xyz', 'rgb', 'n'})")
+            for key in ("xyz", "rgb", "n"):
+                t = cloud_host[key]
+                if t.dtype != s_cloud[key].dtype or tuple(t.shape) != tuple(s_cloud[key].shape):
+                    raise ValueError(f"cloud_host[{key!r}] is {t.dtype} {tuple(t.shape)}, the pipeline's buffer "
+                                     f"{s_cloud[key].dtype} {tuple(s_cloud[key].shape)}")
+            if cloud_host["n"].is_cuda:
+                raise ValueError("cloud_host['n'] must be a host tensor")
+            P = s_cloud["xyz"].shape[1]
+            lo, hi = int(cloud_host["n"].min()), int(cloud_host["n"].max())
+            if lo < 1 or hi > P:
+                raise ValueError(f"cloud_host['n'] holds counts in [{lo}, {hi}]: needs 1 <= n <= P = {P}")
         cs = self.copy_stream
         if self.ran[k]:
             cs.wait_event(self.ev_trunk[k])
@@ -766,6 +839,9 @@ class InferPipeline:
             s_img.copy_(image_host, non_blocking=True)
             if s_depth is not None:
                 s_depth.copy_(depth_host, non_blocking=True)
+            if s_cloud is not None:
+                for key in ("xyz", "rgb", "n"):
+                    s_cloud[key].copy_(cloud_host[key], non_blocking=True)
             self.ev_copy[k].record(cs)
         self.fed[k] = True
 
@@ -775,23 +851,27 @@ class InferPipeline:
 
     def step(self, next_inputs=None):
         """run one step from the current slot; `next_inputs` = (qpos_host, image_host) of the FOLLOWING step -- (qpos_host,
-        image_host, depth_host) for a depth pipeline --, copied into the other slot beside this step's transformer"""
+        image_host, depth_host) for a depth pipeline, (qpos_host, image_host, cloud_host) for a point-cloud pipeline --, copied
+        into the other slot beside this step's transformer"""
         k = self.k_run
         if not self.fed[k]:
             raise RuntimeError("InferPipeline.step: no inputs were fed for this step")
         (s_qpos, s_img, _), trunk, rest = self.slots[k]
         cur = torch.cuda.current_stream(self.dev)
         cur.wait_event(self.ev_copy[k])
-        s_depth = self.depth[k]
-        trunk(s_qpos, s_img, depth_img=s_depth)
+        s_depth, s_cloud = self.depth[k], self.cloud[k]
+        trunk(s_qpos, s_img, pointcloud=s_cloud, depth_img=s_depth)
         self.ev_trunk[k].record(cur)
         self.ran[k] = True
         self.fed[k] = False
         if next_inputs is not None:
             if s_depth is not None and len(next_inputs) != 3:
                 raise ValueError("this pipeline feeds a use_depth engine: next_inputs = (qpos_host, image_host, depth_host)")
-            self.feed(next_inputs[0], next_inputs[1], slot=k ^ 1, depth_host=next_inputs[2] if s_depth is not None else None)
-        out = rest(s_qpos, s_img, depth_img=s_depth)
+            if s_cloud is not None and len(next_inputs) != 3:
+                raise ValueError("this pipeline feeds a use_pcd engine: next_inputs = (qpos_host, image_host, cloud_host)")
+            self.feed(next_inputs[0], next_inputs[1], slot=k ^ 1, depth_host=next_inputs[2] if s_depth is not None else None,
+                      cloud_host=next_inputs[2] if s_cloud is not None else None)
+        out = rest(s_qpos, s_img, pointcloud=s_cloud, depth_img=s_depth)
         self.k_run ^= 1
         return out
 

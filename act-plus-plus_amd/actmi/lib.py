@@ -105,6 +105,7 @@ def load():
         "actmi_create": ([C.POINTER(ActmiConfig), C.POINTER(vp)], i32),
         "actmi_create_ex": ([C.POINTER(ActmiConfig), C.POINTER(ActmiPcdConfig), C.POINTER(vp)], i32),
         "actmi_set_pointcloud": ([vp, vp, vp, i32, i32], i32),
+        "actmi_set_pointcloud_n": ([vp, vp, vp, vp, i32, i32], i32),
         "actmi_create_ex2": ([C.POINTER(ActmiConfig), C.POINTER(ActmiPcdConfig), C.POINTER(ActmiDepthConfig), C.POINTER(vp)], i32),
         "actmi_set_depth": ([vp, vp, i32], i32),
         "actmi_set_depth_u16": ([vp, vp, i32], i32),
@@ -170,6 +171,7 @@ def load():
         "actmi_op_colsum": ([vp, C.c_int64, vp, i32, i32, vp, C.c_int64, vp], i32),
         "actmi_op_pcd_embed": ([vp, vp, vp, vp, vp, C.c_int64, i32, vp], i32),
         "actmi_op_colmax": ([vp, i32, i32, i32, C.c_int64, vp, vp, vp, C.c_int64, vp], i32),
+        "actmi_op_colmax_n": ([vp, i32, i32, i32, C.c_int64, vp, vp, vp, vp, C.c_int64, vp], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

@@ -654,14 +654,21 @@ def pcd_embed(xyz, rgb, w0, b0):
     return out
 
 
-def colmax(x, O=None, split=True):
+def colmax(x, O=None, split=True, counts=None):
     """x [B, P, ld] -> (max over the points [B, O], int32 index of the winner [B, O]) for the columns < O (default ld); the
-    lowest index wins a tie, a NaN propagates.  split=False: one block column per sample (no workspace)."""
+    lowest index wins a tie, a NaN propagates.  split=False: one block column per sample (no workspace).  counts (int32 [B] on
+    x's device): sample b's points are its rows [0, clamp(counts[b], 1, P)); the rows behind them are never read."""
     B, P, ld = x.shape
     O = ld if O is None else O
     out = torch.empty((B, O), dtype=torch.float32, device=x.device)
     arg = torch.empty((B, O), dtype=torch.int32, device=x.device)
     ws = torch.empty(2 * B * 64 * O, dtype=torch.float32, device=x.device) if split else None
+    if counts is not None:
+        if counts.dtype != torch.int32 or tuple(counts.shape) != (B,) or counts.device != x.device or not counts.is_contiguous():
+            raise ValueError(f"colmax: counts must be a contiguous int32 [{B}] tensor on {x.device}")
+        L.check(L.load().actmi_op_colmax_n(_p(x), B, P, O, ld, _p(counts), _p(out), _p(arg), _p(ws), ws.numel() if split else 0,
+                                           L.current_stream_ptr()), None, "op_colmax_n")
+        return out, arg
     L.check(L.load().actmi_op_colmax(_p(x), B, P, O, ld, _p(out), _p(arg), _p(ws), ws.numel() if split else 0,
                                      L.current_stream_ptr()), None, "op_colmax")
     return out, arg

@@ -63,6 +63,10 @@ int actmi_set_depth_u16(actmi_handle h, const uint16_t* depth, int B) {
 }
 
 int actmi_set_pointcloud(actmi_handle h, const float* xyz, const float* rgb, int B, int P) {
+    return actmi_set_pointcloud_n(h, xyz, rgb, nullptr, B, P);
+}
+
+int actmi_set_pointcloud_n(actmi_handle h, const float* xyz, const float* rgb, const int32_t* counts, int B, int P) {
     if (!h) return ACTMI_E_INVALID;
     ENTER(h);
     if (!h->has_pcd) return bad(h, "handle was created without a point-cloud config (actmi_create_ex)", ACTMI_E_STATE);
@@ -70,7 +74,7 @@ int actmi_set_pointcloud(actmi_handle h, const float* xyz, const float* rgb, int
     if (B < 1 || B > h->cfg.max_batch) return bad(h, "batch exceeds max_batch");
     if (P < 1 || P > h->pcd.max_points)
         return bad(h, "point clouds of " + std::to_string(P) + " points: needs 1 <= P <= max_points " + std::to_string(h->pcd.max_points));
-    h->pcd_xyz = xyz; h->pcd_rgb = rgb; h->pcd_B = B; h->pcd_P = P;
+    h->pcd_xyz = xyz; h->pcd_rgb = rgb; h->pcd_counts = counts; h->pcd_B = B; h->pcd_P = P;
     return ACTMI_OK;
 }
 
@@ -587,8 +591,14 @@ int actmi_op_pcd_embed(const float* xyz, const float* rgb, const float* w0, cons
 int actmi_op_colmax(const float* x, int B, int P, int O, int64_t ld, float* out, int32_t* argmax, float* ws, int64_t ws_floats,
                     void* stream) {
     OPCHK(x && out && argmax && B >= 0 && P >= 1 && O >= 0 && ws_floats >= 0, "colmax: bad argument");
-    OPRC(launch_colmax(x, B, P, O, ld, out, argmax, ws, ws_floats, S(stream)),
+    OPRC(launch_colmax(x, B, P, O, ld, nullptr, out, argmax, ws, ws_floats, S(stream)),
          "colmax: O and ld must be multiples of 4, ld >= O, x 16-byte aligned");
+}
+int actmi_op_colmax_n(const float* x, int B, int P, int O, int64_t ld, const int32_t* counts, float* out, int32_t* argmax, float* ws,
+                      int64_t ws_floats, void* stream) {
+    OPCHK(x && out && argmax && B >= 0 && P >= 1 && O >= 0 && ws_floats >= 0, "colmax_n: bad argument");
+    OPRC(launch_colmax(x, B, P, O, ld, counts, out, argmax, ws, ws_floats, S(stream)),
+         "colmax_n: O and ld must be multiples of 4, ld >= O, x 16-byte aligned");
 }
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream) {

@@ -188,9 +188,10 @@ int launch_fold_cat_w(const float* w2, const float* s2, const float* b2, const f
 // receives the pre-activation
 int launch_pcd_embed(const float* xyz, const float* rgb, const int* rowmap, const float* w0, const float* b0, float* out, float* pre,
                      int64_t rows, int H, hipStream_t st);
-// out[b][c] = max_p x[b][p][c], argmax = the lowest index that attains it (NaN propagates); ws: (value, index) of the splits
-int launch_colmax(const float* x, int B, int P, int O, int64_t ld, float* out, int* argmax, float* ws, int64_t ws_floats,
-                  hipStream_t st);
+// out[b][c] = max_p x[b][p][c], argmax = the lowest index that attains it (NaN propagates); ws: (value, index) of the splits.
+// counts (device [B], may be null): only the rows [0, clamp(counts[b], 1, P)) of sample b are points
+int launch_colmax(const float* x, int B, int P, int O, int64_t ld, const int* counts, float* out, int* argmax, float* ws,
+                  int64_t ws_floats, hipStream_t st);
 // rows[b * O + c] = b * P + argmax[b][c]
 int launch_pcd_winner_rows(const int* argmax, int* rows, int B, int P, int O, hipStream_t st);
 // last PointNet layer, backward over the winner rows: dA[(b,c)][:] = g[b][c] * w[c][:], dW[c][:] += sum_b g[b][c] * a[(b,c)][:]

@@ -170,7 +170,8 @@ struct actmi_ctx {
     actmi_pcd_config pcd{};
     int n_extra = 2;
     PcdW pcdw{};
-    const float *pcd_xyz = nullptr, *pcd_rgb = nullptr;    // clouds bound for the next forward (actmi_set_pointcloud), then cleared
+    const float *pcd_xyz = nullptr, *pcd_rgb = nullptr;    // clouds bound for the next forward (actmi_set_pointcloud[_n]), then cleared
+    const int* pcd_counts = nullptr;                       // device [pcd_B] valid points per sample of that binding, or null: all pcd_P
     int pcd_B = 0, pcd_P = 0;
     float *pcd_act[2] = {nullptr, nullptr};                // ping-pong activations [max_batch * max_points][max(H, O)]
     float* pcd_feat = nullptr;                             // [max_batch][O] pooled features
@@ -299,9 +300,10 @@ int engine_depth_minmax(actmi_ctx* ctx, const DepthSrc& depth, int B, hipStream_
 // the depth stem of B samples into cameras C.. of ctx->act1
 int engine_depth_stem(actmi_ctx* ctx, const DepthSrc& depth, int B, hipStream_t st);
 // the clouds of this forward: checks the binding of a point-cloud handle against B (ACTMI_E_STATE with a message) and consumes it
-int engine_take_pointcloud(actmi_ctx* ctx, int B, const float** xyz, const float** rgb, int* P);
-// PointNet + input_proj_pointnet of B clouds of P points -> token row 2 of ctx->X, features / winners in ctx->pcd_feat / pcd_arg
-int engine_pointnet(actmi_ctx* ctx, const float* xyz, const float* rgb, int B, int P, hipStream_t st);
+int engine_take_pointcloud(actmi_ctx* ctx, int B, const float** xyz, const float** rgb, const int** counts, int* P);
+// PointNet + input_proj_pointnet of B clouds of P rows -> token row 2 of ctx->X, features / winners in ctx->pcd_feat / pcd_arg.
+// counts (device [B], may be null): the maximum of sample b runs over its first counts[b] rows; the dense layers run over all P
+int engine_pointnet(actmi_ctx* ctx, const float* xyz, const float* rgb, const int* counts, int B, int P, hipStream_t st);
 // forward GEMMs of a handle go through here: applies the precision in force and, for a B operand inside the parameter arena
 // that does not already name a split image (b_split), swaps in the arena's image (same offset into p16base)
 // LayerNorm that follows a product (y = LN(C), optionally a second LN on top): when the product's contraction is split, the

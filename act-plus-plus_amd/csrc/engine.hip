@@ -1103,27 +1103,31 @@ int engine_take_depth(actmi_ctx* ctx, int B, DepthSrc* depth) {
     return 0;
 }
 
-int engine_take_pointcloud(actmi_ctx* ctx, int B, const float** xyz, const float** rgb, int* P) {
+int engine_take_pointcloud(actmi_ctx* ctx, int B, const float** xyz, const float** rgb, const int** counts, int* P) {
     *xyz = *rgb = nullptr;
+    *counts = nullptr;
     *P = 0;
     if (!ctx->has_pcd) return 0;
     if (!ctx->pcd_xyz || !ctx->pcd_rgb) {
-        ctx->err = "this handle has a point-cloud branch: bind the clouds of every forward with actmi_set_pointcloud";
+        ctx->err = "this handle has a point-cloud branch: bind the clouds of every forward with actmi_set_pointcloud / actmi_set_pointcloud_n";
         return ACTMI_E_STATE;
     }
     if (ctx->pcd_B != B) {
         ctx->err = "forward of batch " + std::to_string(B) + " but the bound point clouds hold " + std::to_string(ctx->pcd_B) + " samples";
         return ACTMI_E_STATE;
     }
-    *xyz = ctx->pcd_xyz; *rgb = ctx->pcd_rgb; *P = ctx->pcd_P;
+    *xyz = ctx->pcd_xyz; *rgb = ctx->pcd_rgb; *counts = ctx->pcd_counts; *P = ctx->pcd_P;
     ctx->pcd_xyz = ctx->pcd_rgb = nullptr;              // one binding, one forward
+    ctx->pcd_counts = nullptr;
     return 0;
 }
 
 // Point-cloud token (detr_vae.py:205-207): PointNet over the B * P points, maximum over the points of a sample, input_proj_pointnet
 // into token row 2.  Layer 0 runs in fp32 FMAs; the H x H / O x H / D x O layers are GEMMs of the handle's precision with the
 // bias + GELU epilogue, their weights arena parameters like the transformer's FFN (split images and scales come with them).
-int engine_pointnet(actmi_ctx* ctx, const float* xyz, const float* rgb, int B, int P, hipStream_t st) {
+// counts: the dense layers still run over all B * P rows (a row's result depends on that row alone, so padding rows cost time in
+// proportion to their number and nothing else); only the maximum reads the counts, on the device.
+int engine_pointnet(actmi_ctx* ctx, const float* xyz, const float* rgb, const int* counts, int B, int P, hipStream_t st) {
     const int Hp = ctx->pcd.hidden_dim, Op = ctx->pcd.output_dim, D = ctx->cfg.hidden_dim, R = B * P;
     const PcdW& w = ctx->pcdw;
     float *a = ctx->pcd_act[0], *b = ctx->pcd_act[1];
@@ -1135,7 +1139,7 @@ int engine_pointnet(actmi_ctx* ctx, const float* xyz, const float* rgb, int B, i
     l6.relu = 2;
     CHK(ctx_gemm(ctx, l6, st));
     CHK(ctx_gemm(ctx, linear_args(a, Hp, R, Hp, w.w9, Op, w.b9, b, Op), st));
-    if (launch_colmax(b, B, P, Op, Op, ctx->pcd_feat, ctx->pcd_arg, ctx->pcd_ws, ctx->pcd_ws_floats, st) != 0) {
+    if (launch_colmax(b, B, P, Op, Op, counts, ctx->pcd_feat, ctx->pcd_arg, ctx->pcd_ws, ctx->pcd_ws_floats, st) != 0) {
         ctx->err = "colmax launch failed";
         return ACTMI_E_LAUNCH;
     }
@@ -1262,9 +1266,10 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
     const actmi_config& g = ctx->cfg;
     const int D = g.hidden_dim, N = ctx->N;
     const float *pc_xyz = nullptr, *pc_rgb = nullptr;
+    const int* pc_n = nullptr;
     int pc_P = 0;
     DepthSrc depth;
-    if (ctx->fwd_phase != 2) CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_P));     // (before anything is launched)
+    if (ctx->fwd_phase != 2) CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_n, &pc_P));     // (before anything is launched)
     if (ctx->fwd_phase != 2) CHK(engine_take_depth(ctx, B, &depth));
     // actmi_set_forward_phase: the step as two halves a caller can capture into two graphs -- the trunk with the token assembly
     // (the only reader of `image` and `qpos`, and the HBM-heavy part) and the transformer -- so that the host-to-device copy of the
@@ -1289,7 +1294,7 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
                                 ctx->P("input_proj_robot_state.bias"), ctx->X + D, (int64_t)N * D, B, D, g.state_dim, st, fill_dst,
                                 ctx->P("latent_out_proj.bias"), 0));
         // token 2: the point cloud (detr_vae.py:205-207), part of phase 1 like the trunk
-        if (ctx->has_pcd) CHK(engine_pointnet(ctx, pc_xyz, pc_rgb, B, pc_P, st));
+        if (ctx->has_pcd) CHK(engine_pointnet(ctx, pc_xyz, pc_rgb, pc_n, B, pc_P, st));
         if (ctx->fwd_phase == 1) { ctx->last_B = B; return 0; }
     } else if (B != ctx->last_B) {
         ctx->err = "forward phase 2 without a phase 1 of the same batch before it";

@@ -70,16 +70,20 @@ __device__ __forceinline__ bool col_better(float v, int i, float m, int mi) {
 // sample.  CG threads side by side own four columns each (one 16-byte load per row), RL row lanes stride the chunk; the lanes'
 // candidates meet in LDS in lane order.  The (value, index) of the split goes to pv / pi [B][S][O]; a column that only ever saw
 // -inf keeps the index INT_MAX (finish: index 0, as torch.max gives).
-__global__ __launch_bounds__(256) void colmax_part_kernel(const float* __restrict__ x, int P, int O, int64_t ld, int CG, int RL,
-                                                          int chunk, int S, float* __restrict__ pv, int* __restrict__ pi,
-                                                          int finish) {
+// counts (may be null: every sample has P points): sample b's points are the rows [0, n_b), n_b = clamp(counts[b], 1, P); the
+// rows behind them are padding and are never read.  A split that lies wholly behind n_b hands on (-inf, INT_MAX), which loses to
+// every real candidate under col_better -- a real -inf included, whose index is lower.
+__global__ __launch_bounds__(256) void colmax_part_kernel(const float* __restrict__ x, const int* __restrict__ counts, int P, int O,
+                                                          int64_t ld, int CG, int RL, int chunk, int S, float* __restrict__ pv,
+                                                          int* __restrict__ pi, int finish) {
     __shared__ float s_v[1024];
     __shared__ int s_i[1024];
     const int tid = threadIdx.x, cx = tid % CG, rl = tid / CG;
     const int b = blockIdx.z, s = blockIdx.y;
     const int col = (blockIdx.x * CG + cx) * 4;
     const bool active = rl < RL && col < O;
-    const int r0 = s * chunk, r1 = min(P, r0 + chunk);
+    const int n = counts ? min(max(counts[b], 1), P) : P;
+    const int r0 = s * chunk, r1 = min(n, r0 + chunk);
     float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     int mi[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
     if (active) {
@@ -219,7 +223,7 @@ int launch_pcd_embed(const float* xyz, const float* rgb, const int* rowmap, cons
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int launch_colmax(const float* x, int B, int P, int O, int64_t ld, float* out, int* argmax, float* ws, int64_t ws_floats,
+int launch_colmax(const float* x, int B, int P, int O, int64_t ld, const int* counts, float* out, int* argmax, float* ws, int64_t ws_floats,
                   hipStream_t st) {
     if (B <= 0 || O <= 0) return 0;
     if (P < 1 || (O & 3) || (ld & 3) || ld < O || !aligned16(x)) return -2;
@@ -236,8 +240,8 @@ int launch_colmax(const float* x, int B, int P, int O, int64_t ld, float* out, i
     float* pv = S > 1 ? ws : out;
     int* pi = S > 1 ? reinterpret_cast<int*>(ws + (int64_t)B * S * O) : argmax;
     prof_begin("colmax_part_kernel", 0.0, 4.0 * B * (double)P * O, st);
-    hipLaunchKernelGGL(colmax_part_kernel, dim3(colgroups, (unsigned)S, B), dim3(256), 0, st, x, P, O, ld, CG, RL, chunk, (int)S, pv, pi,
-                       S > 1 ? 0 : 1);
+    hipLaunchKernelGGL(colmax_part_kernel, dim3(colgroups, (unsigned)S, B), dim3(256), 0, st, x, counts, P, O, ld, CG, RL, chunk, (int)S, pv,
+                       pi, S > 1 ? 0 : 1);
     prof_end(st);
     if (hipGetLastError() != hipSuccess) return -3;
     if (S > 1) {

@@ -611,7 +611,7 @@ int trunk_bwd(actmi_ctx* ctx, float* gcur, hipStream_t st) {
 
 // ---- token assembly: input_proj (1x1 convolution) of every camera group's layer4 maps, rows scattered to the group's tokens; token 1,
 // proprio = W_s qpos + b_s (detr_vae.py:213); token 2 on a point-cloud handle.  (Token 0, the latent: cvae_fwd, where z is made.)
-int tokens_fwd(actmi_ctx* ctx, const float* qpos, const float* xyz, const float* rgb, int P, int B, hipStream_t st) {
+int tokens_fwd(actmi_ctx* ctx, const float* qpos, const float* xyz, const float* rgb, const int* counts, int P, int B, hipStream_t st) {
     const int D = ctx->cfg.hidden_dim, S = ctx->cfg.state_dim, w8 = 8 * ctx->cfg.base_width;
     const float* maps = ctx->train->saves.back().out;
     CHK(engine_build_rowmap(ctx, B, st));
@@ -626,9 +626,10 @@ int tokens_fwd(actmi_ctx* ctx, const float* qpos, const float* xyz, const float*
     if (ctx->has_pcd) {
         // token 2: the point cloud = input_proj_pointnet(max over the points of the PointNet).  The dense forward keeps nothing: only
         // the point that won a column carries gradient through the maximum, so the B * O winners are gathered and layers 0-6 run again
-        // for those rows alone, saving their pre-activations (the backward treats every (sample, column) pair as a row of its own)
+        // for those rows alone, saving their pre-activations (the backward treats every (sample, column) pair as a row of its own).
+        // With per-sample counts the winners are rows below the count by construction: nothing behind here reads the counts
         TrainState& T = *ctx->train;
-        CHK(engine_pointnet(ctx, xyz, rgb, B, P, st));
+        CHK(engine_pointnet(ctx, xyz, rgb, counts, B, P, st));
         const PcdW& w = ctx->pcdw;
         const int Hp = ctx->pcd.hidden_dim, Op = ctx->pcd.output_dim, R2 = B * Op;
         T.pcd_xyz = xyz; T.pcd_rgb = rgb; T.pcd_P = P;
@@ -1031,8 +1032,9 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
     if (B < 1 || B > ctx->cfg.max_batch) { ctx->err = "batch exceeds max_batch"; return ACTMI_E_INVALID; }
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) { ctx->err = "dropout_p must be in [0, 1)"; return ACTMI_E_INVALID; }
     const float *pc_xyz = nullptr, *pc_rgb = nullptr;
+    const int* pc_n = nullptr;
     int pc_P = 0;
-    CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_P));            // (before anything is launched)
+    CHK(engine_take_pointcloud(ctx, B, &pc_xyz, &pc_rgb, &pc_n, &pc_P));            // (before anything is launched)
     DepthSrc depth;
     CHK(engine_take_depth(ctx, B, &depth));
     PrecScope prec_scope(ctx);               // the opt-in bf16 product mode covers the GEMMs of this call only
@@ -1044,7 +1046,7 @@ int train_forward(actmi_ctx* ctx, const float* qpos, const void* image, int fmt,
     T.qpos = qpos;
     CHK(cvae_fwd(ctx, qpos, eps, B, mu_out, logvar_out, st));                // token 0
     CHK(trunk_fwd(ctx, image, depth, fmt, B, st));
-    CHK(tokens_fwd(ctx, qpos, pc_xyz, pc_rgb, pc_P, B, st));                 // tokens n_extra.., 1, 2
+    CHK(tokens_fwd(ctx, qpos, pc_xyz, pc_rgb, pc_n, pc_P, B, st));                 // tokens n_extra.., 1, 2
     for (int l = 0; l < g.enc_layers; ++l) {
         float* out = (l + 1 < g.enc_layers) ? T.en[l + 1].x_in : T.mem;
         CHK(enc_fwd(ctx, ctx->enc[l], T.en[l], out, ctx->pos_tokens, B, ctx->N, nullptr, Drop{dropout_p, dropout_seed, (uint32_t)(100 + 8 * l)}, st));

@@ -119,6 +119,10 @@ def eval_bc(config, ckpt_name, save_episode=True, num_rollouts=50, policy=None, 
         # RGB alone would report the success rate of a different model
         raise NotImplementedError("eval_bc cannot roll out a use_depth policy: no environment here produces depth frames "
                                   "(train with --use_depth, evaluate on the robot's own loop)")
+    if policy_config.get("use_pcd") or getattr(policy, "use_pcd", False):
+        # likewise: no simulator here produces point clouds, the fork's rollouts read the robot's fused live cloud
+        raise NotImplementedError("eval_bc cannot roll out a use_pcd policy: no environment here produces point clouds "
+                                  "(train with --use_pcd, evaluate on the robot's own loop)")
     camera_names = config["camera_names"]
     max_timesteps = int(config["episode_len"])
     task_name = config["task_name"]
@@ -344,8 +348,15 @@ def eval_bc(config, ckpt_name, save_episode=True, num_rollouts=50, policy=None, 
 
 def forward_pass(data, policy):
     """reference imitate_episodes.py:529-532; a 5-tuple ends in the depth frames of a use_depth dataset (the fork's
-    train_single_arm_gripper_all.py:568-588)."""
+    train_single_arm_gripper_all.py:568-588), a 7-tuple in the padded clouds of a use_pcd dataset and their valid counts
+    (pcd_xyz, pcd_rgb, pcd_n; the fork's :576-591 passes the one fused cloud)."""
     depth_data = None
+    if len(data) == 7:
+        image_data, qpos_data, action_data, is_pad, pcd_xyz, pcd_rgb, pcd_n = data
+        dev = getattr(getattr(policy, "model", None), "device", None) or "cuda"
+        image_data, qpos_data, action_data, is_pad, pcd_xyz, pcd_rgb, pcd_n = (
+            t.to(dev, non_blocking=True) for t in (image_data, qpos_data, action_data, is_pad, pcd_xyz, pcd_rgb, pcd_n))
+        return policy(qpos_data, image_data, action_data, is_pad, pointcloud={"xyz": pcd_xyz, "rgb": pcd_rgb, "n": pcd_n})
     if len(data) == 5:
         image_data, qpos_data, action_data, is_pad, depth_data = data
     else:
@@ -367,6 +378,9 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
     eval_every = config.get("eval_every") or 0
     if eval_every and policy_config.get("use_depth"):
         print("use_depth: no environment here produces depth frames, the periodic rollouts (--eval_every) are skipped")
+        eval_every = 0
+    if eval_every and policy_config.get("use_pcd"):
+        print("use_pcd: no environment here produces point clouds, the periodic rollouts (--eval_every) are skipped")
         eval_every = 0
     validate_every = config["validate_every"]
     save_every = config["save_every"]
@@ -473,6 +487,11 @@ def build_config(args):
             if not depth_camera_names:
                 raise ValueError(f"--use_depth: the task config of {task_name!r} lists no depth_camera_names")
             policy_config.update(use_depth=True, depth_camera_names=list(depth_camera_names))
+        if args.get("use_pcd"):                      # the fork's one fused cloud: its name comes from the task as well
+            pointcloud_names = task_config.get("pointcloud_names")
+            if not pointcloud_names:
+                raise ValueError(f"--use_pcd: the task config of {task_name!r} lists no pointcloud_names")
+            policy_config.update(use_pcd=True, max_points=int(args.get("max_points") or 4096))
     elif policy_class == "Diffusion":                # reference :95-106
         policy_config = {"lr": args["lr"], "camera_names": camera_names, "action_dim": 16, "observation_horizon": 1,
                          "action_horizon": 8, "prediction_horizon": args["chunk_size"], "num_queries": args["chunk_size"],
@@ -481,7 +500,9 @@ def build_config(args):
         raise NotImplementedError(f"policy_class {policy_class} is outside the accelerated path (SURVEY §2)")
     if args.get("use_depth") and policy_class != "ACT":
         raise NotImplementedError("--use_depth: depth cameras belong to the ACT policy")
-    return {"num_steps": args["num_steps"], "eval_every": args["eval_every"], "validate_every": args["validate_every"],
+    if args.get("use_pcd") and policy_class != "ACT":
+        raise NotImplementedError("--use_pcd: the point-cloud token belongs to the ACT policy")
+    config = {"num_steps": args["num_steps"], "eval_every": args["eval_every"], "validate_every": args["validate_every"],
             "save_every": args["save_every"], "ckpt_dir": args["ckpt_dir"], "resume_ckpt_path": args.get("resume_ckpt_path"),
             "episode_len": task_config["episode_len"], "state_dim": 14, "lr": args["lr"],
             "policy_class": args["policy_class"], "onscreen_render": args.get("onscreen_render", False),
@@ -489,6 +510,9 @@ def build_config(args):
             "temporal_agg": args["temporal_agg"], "camera_names": camera_names, "real_robot": False,
             "load_pretrain": bool(args.get("load_pretrain", False)), "pretrain_ckpt_path": args.get("pretrain_ckpt_path"),
             "synthetic_env": bool(args.get("synthetic_env", False))}
+    if args.get("use_pcd"):
+        config["pointcloud_names"] = list(task_config["pointcloud_names"])
+    return config
 
 
 def main(args):
@@ -517,6 +541,10 @@ def main(args):
     if use_depth and not (dataset_dir and os.path.isdir(dataset_dir)):
         raise ValueError("--use_depth needs episode files with /observations/depth_images/<cam> (--dataset_dir): the synthetic "
                          "stand-in dataset holds no depth frames")
+    use_pcd = bool(config["policy_config"].get("use_pcd"))
+    if use_pcd and not (dataset_dir and os.path.isdir(dataset_dir)):
+        raise ValueError("--use_pcd needs episode files with /observations/pointcloud/<name>/{xyz, rgb} (--dataset_dir): the "
+                         "synthetic stand-in dataset holds no point clouds")
     if dataset_dir and os.path.isdir(dataset_dir):
         # reference imitate_episodes.py:141-147: episodes on disk (HDF5 via h5py, or .npz with the same keys), z-scored
         # qpos / actions, u8 images; batches reach the device through pinned staging on a side stream
@@ -528,7 +556,8 @@ def main(args):
                                                sample_weights=task_config.get("sample_weights"),
                                                train_ratio=task_config.get("train_ratio", 0.99),
                                                depth_camera_names=config["policy_config"].get("depth_camera_names"),
-                                               use_depth=use_depth)
+                                               use_depth=use_depth, pointcloud_names=config.get("pointcloud_names"),
+                                               use_pcd=use_pcd, max_points=config["policy_config"].get("max_points"))
     else:
         train_dl = SyntheticDataset(cfg, args["batch_size"], 8, seed=args["seed"] * world + rank)     # disjoint per rank
         val_dl = SyntheticDataset(cfg, args["batch_size"], 2, seed=args["seed"] * world + rank + 100003)
@@ -574,6 +603,11 @@ if __name__ == "__main__":
     parser.add_argument("--use_depth", action="store_true",
                         help="ACT with one depth camera per RGB camera: the task config's depth_camera_names, raw 16-bit frames "
                              "from /observations/depth_images/<cam>")
+    parser.add_argument("--use_pcd", action="store_true",
+                        help="ACT with a point-cloud token: the task config's one pointcloud_names entry, ragged clouds from "
+                             "/observations/pointcloud/<name>/{xyz, rgb, padding_mask}")
+    parser.add_argument("--max_points", action="store", type=int, default=4096,
+                        help="--use_pcd: the largest stored cloud (rows per frame) the engine's workspace is sized for")
     # additions (rollouts count hard-coded to 10 in the reference, :156)
     parser.add_argument("--num_rollouts", action="store", type=int, default=50)
     parser.add_argument("--max_batch", action="store", type=int, default=None)

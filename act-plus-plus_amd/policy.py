@@ -95,7 +95,7 @@ class ACTPolicy:
 
     def __call__(self, qpos, image, actions=None, is_pad=None, vq_sample=None, depth_img=None, pointcloud=None):
         if self.use_pcd and pointcloud is None:
-            raise ValueError("a use_pcd policy needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]}")
+            raise ValueError("a use_pcd policy needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]} (ragged clouds: + 'n': int32 [B])")
         pointcloud = pointcloud if self.use_pcd else None       # reference policy.py:301, 329
         if self.use_depth and depth_img is None:
             # (the reference would silently run RGB-only with a shorter sequence; the handle's token count is fixed at create)

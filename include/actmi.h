@@ -236,6 +236,14 @@ int actmi_create_ex(const actmi_config* cfg, const actmi_pcd_config* pcd, actmi_
  * until actmi_backward) has been enqueued.  A forward of a point-cloud handle without bound clouds, or with another B, returns
  * ACTMI_E_STATE; so does this call on a handle created without a point-cloud config. */
 int actmi_set_pointcloud(actmi_handle h, const float* xyz, const float* rgb, int B, int P);
+/* actmi_set_pointcloud for RAGGED clouds padded to a common P: counts [B] int32 device (NULL: exactly actmi_set_pointcloud), the
+ * number of points of every sample.  Sample b's points are its rows [0, n_b), n_b = clamp(counts[b], 1, P); the maximum over the
+ * points runs over those rows alone, so the token, the losses and every gradient are those of the un-padded cloud, whatever the
+ * rows behind n_b hold -- as long as they hold FINITE values (the dense layers still run over all P rows; zero-fill them).  The
+ * counts are read on the device when the forward runs, never on the host: a captured forward with a static counts buffer sees
+ * the buffer's contents of every replay.  Same binding rules and return codes as actmi_set_pointcloud; counts must stay valid
+ * until the forward has run. */
+int actmi_set_pointcloud_n(actmi_handle h, const float* xyz, const float* rgb, const int32_t* counts, int B, int P);
 
 /* Depth-camera input (reference use_depth: backbone.py:115-134, detr_vae.py:188-202, 359-361, transformer.py:64-86): one
  * FrozenBN ResNet18 per depth camera whose conv1 is Conv2d(1, w, 7, 2, 3) (depth_backbones.k.0.body.*, conv1.weight
@@ -512,6 +520,10 @@ int actmi_op_pcd_embed(const float* xyz, const float* rgb, const float* w0, cons
  * points are split over blocks and the candidates merged in split order: bitwise repeatable.  O % 4 == 0, ld % 4 == 0 */
 int actmi_op_colmax(const float* x, int B, int P, int O, int64_t ld, float* out, int32_t* argmax, float* ws, int64_t ws_floats,
                     void* stream);
+/* actmi_op_colmax over the rows [0, clamp(counts[b], 1, P)) of every sample b (counts [B] int32 device; NULL: actmi_op_colmax):
+ * rows at or behind the count are never read, every argmax is below it; same grid, same split, same merge order */
+int actmi_op_colmax_n(const float* x, int B, int P, int O, int64_t ld, const int32_t* counts, float* out, int32_t* argmax, float* ws,
+                      int64_t ws_floats, void* stream);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
