@@ -218,15 +218,43 @@ def conv1_prepare(w_oihw, lut_mode=1):
     return ws
 
 
-def conv1_prepared(image_u8, ws, Cout, relu=False, scale=None, bias=None):
-    """the 7x7 / s2 stem on prepared weights: image u8 [B, C, H, W, 3] -> [C, B, Ho, Wo, Cout] (f16x3); launch only."""
+def conv1_prepared(image, ws, Cout, relu=False, scale=None, bias=None, vpool=False, cam0=0, ncam=0, out=None, prec=None):
+    """the 7x7 / s2 stem on prepared weights (actmi_op_conv1_prepared_ex): image u8 [B, C, H, W, 3] or f32 [B, C, 3, H, W] (the
+    f32 form is ImageNet-normalised in the loader) -> [C, B, Ho, Wo, Cout], or [C, B, Ho/2, Wo, Cout] under vpool (max over conv
+    rows 2a-1, 2a, 2a+1); launch only.  cam0 / ncam: compute that camera range only, into the whole-tensor `out` given."""
     lib = L.load()
-    image_u8 = image_u8.contiguous()
-    B, Cc, H, W, _ = image_u8.shape
-    out = torch.empty((Cc, B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cout), dtype=torch.float32, device=image_u8.device)
-    L.check(lib.actmi_op_conv1_prepared(_p(image_u8), _p(ws), _p(scale), _p(bias), _p(out), B, Cc, H, W, Cout, 1 if relu else 0,
-                                        L.current_stream_ptr()), None, "op_conv1_prepared")
+    image = image.contiguous()
+    if image.dtype == torch.uint8:
+        B, Cc, H, W, _ = image.shape
+        fmt = L.IMG_U8_NHWC
+    elif image.dtype == torch.float32:
+        B, Cc, _, H, W = image.shape
+        fmt = L.IMG_F32_NCHW
+    else:
+        raise TypeError(f"conv1_prepared: image dtype {image.dtype} not supported (uint8 or float32)")
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    shape = (Cc, B, Ho // 2 if vpool else Ho, Wo, Cout)
+    if out is None:
+        if ncam:
+            raise ValueError("conv1_prepared: a camera range writes into a caller-supplied whole-tensor out")
+        out = torch.empty(shape, dtype=torch.float32, device=image.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"conv1_prepared: out must be a contiguous float32 tensor of shape {shape}")
+    L.check(lib.actmi_op_conv1_prepared_ex(_p(image), fmt, _p(ws), _p(scale), _p(bias), _p(out), B, Cc, H, W, Cout, 1 if relu else 0,
+                                           1 if vpool else 0, int(cam0), int(ncam), PREC[prec], L.current_stream_ptr()),
+            None, "op_conv1_prepared")
     return out
+
+
+def hpool(x):
+    """horizontal half of the 3x3 / s2 / p1 max pool: x [..., W, C] NHWC rows -> [..., Wo, C], max over columns 2pw-1 .. 2pw+1."""
+    lib = L.load()
+    x = x.contiguous()
+    W, Cc = x.shape[-2], x.shape[-1]
+    nrows = x.numel() // (W * Cc) if W * Cc else 0
+    y = torch.empty(tuple(x.shape[:-2]) + ((W - 1) // 2 + 1, Cc), dtype=torch.float32, device=x.device)
+    L.check(lib.actmi_op_hpool(_p(x), _p(y), nrows, W, Cc, L.current_stream_ptr()), None, "op_hpool")
+    return y
 
 
 def conv3x3_c64(x, w_ohwi, scale=None, bias=None, res=None, relu=False, w_scale=256.0, w16=None):

@@ -425,21 +425,47 @@ int actmi_op_conv1_prepare(const float* w_oihw, float* workspace, int C, int Cou
     if (hipStreamSynchronize(S(stream)) != hipSuccess) return ACTMI_E_LAUNCH;
     return 0;
 }
-int actmi_op_conv1_prepared(const void* image_u8, const float* workspace, const float* scale, const float* bias, float* out, int B,
-                            int C, int H, int W, int Cout, int relu, void* stream) {
+int actmi_op_conv1_prepared_ex(const void* image, int image_fmt, const float* workspace, const float* scale, const float* bias,
+                               float* out, int B, int C, int H, int W, int Cout, int relu, int vpool, int cam0, int ncam, int prec,
+                               void* stream) {
     g_op_error.clear();
-    if (!image_u8 || !workspace || !out) { g_op_error = "conv1_prepared: null pointer"; return ACTMI_E_INVALID; }
+    if (!image || !workspace || !out) { g_op_error = "conv1_prepared: null pointer"; return ACTMI_E_INVALID; }
+    if (image_fmt != ACTMI_IMG_U8_NHWC && image_fmt != ACTMI_IMG_F32_NCHW) { g_op_error = "conv1_prepared: unknown image format"; return ACTMI_E_INVALID; }
+    if (B < 1 || C < 1 || H < 1 || W < 1 || Cout < 1 || Cout > 64) { g_op_error = "conv1_prepared: empty shape or Cout outside 1..64"; return ACTMI_E_INVALID; }
+    if (prec != 0 && prec != ACTMI_PREC_F32 && prec != ACTMI_PREC_F16X3) { g_op_error = "conv1_prepared: prec must be 0, f32 or f16x3"; return ACTMI_E_INVALID; }
+    if (prec == 0) prec = ACTMI_PREC_F16X3;
+    if (!relu && (vpool || prec != ACTMI_PREC_F16X3)) {
+        g_op_error = "conv1_prepared: the form without ReLU is the plain f16x3 one (vpool and the fp32 kernel always apply it)";
+        return ACTMI_E_SHAPE;
+    }
+    if ((Cout & 3) == 0 && ((uintptr_t)out & 15)) { g_op_error = "conv1_prepared: out must be 16-byte aligned"; return ACTMI_E_SHAPE; }
     const float* lut = workspace + conv1_ws_off_lut(C, Cout);
     const float* ones = lut + 768;
     const float* zeros = ones + (int64_t)C * Cout;
     const float* wimg = zeros + (int64_t)C * Cout;
     wimg = reinterpret_cast<const float*>((reinterpret_cast<uintptr_t>(wimg) + 15) & ~(uintptr_t)15);
     Conv1Args a;
-    a.image = image_u8; a.fmt = ACTMI_IMG_U8_NHWC; a.lut = lut; a.w = workspace; a.scale = scale ? scale : ones; a.bias = bias ? bias : zeros;
+    a.image = image; a.fmt = image_fmt; a.lut = lut; a.w = workspace; a.scale = scale ? scale : ones; a.bias = bias ? bias : zeros;
     a.out = out; a.B = B; a.C = C; a.H = H; a.W = W; a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1; a.Cout = Cout;
-    a.prec = ACTMI_PREC_F16X3; a.wimg = reinterpret_cast<const unsigned char*>(wimg); a.wscale = 256.f;
+    a.prec = prec; a.wimg = reinterpret_cast<const unsigned char*>(wimg); a.wscale = 256.f;
     a.relu_floor = relu ? 0.f : -__builtin_inff();
-    return launch_conv1(a, S(stream), &g_op_error);
+    a.vpool = vpool ? 1 : 0; a.cam0 = cam0; a.ncam = ncam;
+    const int rc = launch_conv1(a, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_SHAPE : ACTMI_E_LAUNCH);
+}
+int actmi_op_conv1_prepared(const void* image_u8, const float* workspace, const float* scale, const float* bias, float* out, int B,
+                            int C, int H, int W, int Cout, int relu, void* stream) {
+    return actmi_op_conv1_prepared_ex(image_u8, ACTMI_IMG_U8_NHWC, workspace, scale, bias, out, B, C, H, W, Cout, relu, 0, 0, 0,
+                                      ACTMI_PREC_F16X3, stream);
+}
+int actmi_op_hpool(const float* in, float* out, int nrows, int W, int C, void* stream) {
+    g_op_error.clear();
+    if (nrows < 0 || W < 1 || C < 1 || (nrows > 0 && (!in || !out))) { g_op_error = "hpool: null pointer or bad shape"; return ACTMI_E_INVALID; }
+    if (((uintptr_t)in | (uintptr_t)out) & 15) { g_op_error = "hpool: in / out must be 16-byte aligned"; return ACTMI_E_SHAPE; }
+    const int rc = launch_hpool(in, out, nrows, W, C, (W - 1) / 2 + 1, S(stream));
+    if (rc == -2) g_op_error = "hpool: C must be a multiple of 4";
+    else if (rc) g_op_error = "hpool: launch failed";
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_SHAPE : ACTMI_E_LAUNCH);
 }
 
 int actmi_op_conv3x3_c64(const float* x, const float* w16, float w_scale, const float* scale, const float* bias,

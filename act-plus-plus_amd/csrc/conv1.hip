@@ -12,6 +12,7 @@
 // camera's weights (row stride 149 floats: conflict-free).  Blocks are persistent over tiles so the 37 KB
 // weight image is staged once per block.
 #include "common.h"
+#include "conv1_u8_loader.h"
 #include <cstdlib>
 
 namespace {
@@ -75,21 +76,16 @@ __global__ __launch_bounds__(256) void conv1_kernel(Conv1Args p, int tiles_per_r
         const int hi0 = 2 * ho - 3, wi0 = 2 * wo0 - 3;
         if (FMT == 0) {
             // row r of the patch = 399 consecutive bytes starting at byte (hi*W + wi0)*3 of the image; fetched as
-            // 101 aligned 4-byte words (clamped into the image; out-of-image bytes are discarded in commit())
+            // 101 4-byte words (conv1_u8_loader.h: moved into the image; out-of-image bytes are discarded in commit())
             const uint8_t* src = reinterpret_cast<const uint8_t*>(p.image) + img * (int64_t)p.H * p.W * 3;
-            const int64_t img_bytes = (int64_t)p.H * p.W * 3;
 #pragma unroll
             for (int i = 0; i < NS; ++i) {
                 const int e = t + 256 * i;
                 const int r = e / 101, j = e - r * 101;
-                const int hi = hi0 + r;
                 uint32_t v = 0;
-                if (r < 7 && (unsigned)hi < (unsigned)p.H) {
-                    const int64_t a0 = ((int64_t)hi * p.W + wi0) * 3;          // may be negative / past the row: clamp below
-                    int64_t wa = ((a0 >> 2) + j) << 2;                          // aligned word address (floor for negatives)
-                    if (wa < 0) wa = 0;
-                    if (wa > img_bytes - 4) wa = (img_bytes - 4) & ~int64_t(3);
-                    v = *reinterpret_cast<const uint32_t*>(src + wa);
+                if (r < 7) {
+                    const conv1_u8::Slot sl = conv1_u8::slot(hi0 + r, wi0, j, p.H, p.W);
+                    if (sl.row_ok) v = *reinterpret_cast<const uint32_t*>(src + sl.wl);
                 }
                 sreg[i] = v;
             }
@@ -113,34 +109,20 @@ __global__ __launch_bounds__(256) void conv1_kernel(Conv1Args p, int tiles_per_r
         tile_coords(tile, b, ho, wo0);
         const int hi0 = 2 * ho - 3, wi0 = 2 * wo0 - 3;
         if (FMT == 0) {
-            const int64_t img_bytes = (int64_t)p.H * p.W * 3;
 #pragma unroll
             for (int i = 0; i < NS; ++i) {
                 const int e = t + 256 * i;
                 const int r = e / 101, j = e - r * 101;
-                const int hi = hi0 + r;
                 if (r >= 7) continue;
-                const bool row_ok = (unsigned)hi < (unsigned)p.H;
-                const int64_t a0 = ((int64_t)hi * p.W + wi0) * 3;
-                int64_t wa = ((a0 >> 2) + j) << 2;
-                const int64_t wa_req = wa;
-                if (wa < 0) wa = 0;
-                if (wa > img_bytes - 4) wa = (img_bytes - 4) & ~int64_t(3);
+                const conv1_u8::Slot sl = conv1_u8::slot(hi0 + r, wi0, j, p.H, p.W);
+                const uint32_t word = sreg[i] >> conv1_u8::align_shift(sl);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const int64_t ba = wa_req + k;                 // byte address this slot stands for
-                    const int x = (int)(ba - a0);                  // position inside the 399-byte patch row
-                    if (x < 0 || x >= PCOLS * 3) continue;
-                    const int pc = x / 3, c = x - pc * 3;
-                    const int wi = wi0 + pc;
+                    int x;
+                    bool in_image;
+                    if (!conv1_u8::byte_of(sl, k, wi0, p.W, x, in_image)) continue;
                     float v = 0.f;
-                    // the word was clamped only when it lies (partly) outside the image: such bytes are padding anyway
-                    if (row_ok && (unsigned)wi < (unsigned)p.W && wa == wa_req)
-                        v = s_lut[c * 256 + ((sreg[i] >> (8 * k)) & 0xFF)];
-                    else if (row_ok && (unsigned)wi < (unsigned)p.W) {
-                        const int64_t sh = ba - wa;                // clamped word still contains this byte if 0 <= sh < 4
-                        if (sh >= 0 && sh < 4) v = s_lut[c * 256 + ((sreg[i] >> (8 * sh)) & 0xFF)];
-                    }
+                    if (in_image) v = s_lut[(x % 3) * 256 + ((word >> (8 * k)) & 0xFF)];
                     patch[r * PSTRIDE + x] = v;
                 }
             }
@@ -332,19 +314,14 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
         const int hi0 = 2 * ho0 - 3, wi0 = 2 * wo0 - 3;
         if (FMT == 0) {
             const uint8_t* src = reinterpret_cast<const uint8_t*>(p.image) + img * (int64_t)p.H * p.W * 3;
-            const int64_t img_bytes = (int64_t)p.H * p.W * 3;
 #pragma unroll
             for (int i = 0; i < NS; ++i) {
                 const int e = t + 256 * i;
                 const int r = e / 101, j = e - r * 101;
-                const int hi = hi0 + r;
                 uint32_t v = 0;
-                if (r < F_PROWS && (unsigned)hi < (unsigned)p.H) {
-                    const int64_t a0 = ((int64_t)hi * p.W + wi0) * 3;
-                    int64_t wa = ((a0 >> 2) + j) << 2;
-                    if (wa < 0) wa = 0;
-                    if (wa > img_bytes - 4) wa = (img_bytes - 4) & ~int64_t(3);
-                    v = *reinterpret_cast<const uint32_t*>(src + wa);
+                if (r < F_PROWS) {
+                    const conv1_u8::Slot sl = conv1_u8::slot(hi0 + r, wi0, j, p.H, p.W);
+                    if (sl.row_ok) v = *reinterpret_cast<const uint32_t*>(src + sl.wl);
                 }
                 sreg[i] = v;
             }
@@ -372,31 +349,20 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
         tile_coords(tile, b, ho0, wo0);
         const int hi0 = 2 * ho0 - 3, wi0 = 2 * wo0 - 3;
         if (FMT == 0) {
-            const int64_t img_bytes = (int64_t)p.H * p.W * 3;
 #pragma unroll
             for (int i = 0; i < NS; ++i) {
                 const int e = t + 256 * i;
                 const int r = e / 101, j = e - r * 101;
-                const int hi = hi0 + r;
                 if (r >= F_PROWS) continue;
-                const bool row_ok = (unsigned)hi < (unsigned)p.H;
-                const int64_t a0 = ((int64_t)hi * p.W + wi0) * 3;
-                int64_t wa = ((a0 >> 2) + j) << 2;
-                const int64_t wa_req = wa;
-                if (wa < 0) wa = 0;
-                if (wa > img_bytes - 4) wa = (img_bytes - 4) & ~int64_t(3);
+                const conv1_u8::Slot sl = conv1_u8::slot(hi0 + r, wi0, j, p.H, p.W);
+                const uint32_t word = sreg[i] >> conv1_u8::align_shift(sl);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const int64_t ba = wa_req + k;
-                    const int x = (int)(ba - a0);
-                    if (x < 0 || x >= PCOLS * 3) continue;
-                    const int pc = x / 3, c = x - pc * 3;
-                    const int wi = wi0 + pc;
+                    int x;
+                    bool in_image;
+                    if (!conv1_u8::byte_of(sl, k, wi0, p.W, x, in_image)) continue;
                     uint32_t hl = 0u;
-                    if (row_ok && (unsigned)wi < (unsigned)p.W) {
-                        const int64_t sh = ba - wa;            // the (possibly clamped) word holds this byte if 0 <= sh < 4
-                        if (sh >= 0 && sh < 4) hl = s_lut[c * 256 + ((sreg[i] >> (8 * sh)) & 0xFF)];
-                    }
+                    if (in_image) hl = s_lut[(x % 3) * 256 + ((word >> (8 * k)) & 0xFF)];
                     put(patch, r, x, hl);
                 }
             }
@@ -574,6 +540,14 @@ int launch_conv1_wimg(const float* w, void* img, int C, int Cout, hipStream_t st
 int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err) {
     if (a.Cout > 64 || a.Cout < 1) { if (err) *err = "conv1: Cout must be in 1..64"; return -2; }
     if (a.Ho != (a.H + 6 - 7) / 2 + 1 || a.Wo != (a.W + 6 - 7) / 2 + 1) { if (err) *err = "conv1: bad output size"; return -2; }
+    if (a.cam0 < 0 || a.ncam < 0 || (a.ncam == 0 && a.cam0 != 0) || a.cam0 + a.ncam > a.C) {
+        if (err) *err = "conv1: camera range outside 0..C (ncam = 0 means all C cameras from cam0 = 0)";
+        return -2;
+    }
+    if (a.fmt == 0 && !conv1_u8::frame_ok((int64_t)a.H * a.W * 3)) {
+        if (err) *err = "conv1: a u8 frame needs at least 4 bytes (the loader fetches whole words inside the image)";
+        return -2;
+    }
     static const int env_prec = env_gemm_prec(ACTMI_PREC_F32);
     const int prec = a.prec ? a.prec : env_prec;
     if (prec == ACTMI_PREC_F16X3) {

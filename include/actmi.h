@@ -434,6 +434,24 @@ int64_t actmi_op_conv1_workspace_floats(int C, int Cout);
 int actmi_op_conv1_prepare(const float* w_oihw, float* workspace, int C, int Cout, int lut_mode, void* stream);
 int actmi_op_conv1_prepared(const void* image_u8, const float* workspace, const float* scale, const float* bias, float* out,
                             int B, int C, int H, int W, int Cout, int relu, void* stream);
+/* The prepared stem with every launch form of the kernel (kernel-level parity tests; actmi_op_conv1_prepared is this entry with
+ * u8 input, vpool 0, all cameras, f16x3):
+ *   image_fmt  ACTMI_IMG_U8_NHWC (normalised by the workspace's lookup table) or ACTMI_IMG_F32_NCHW (always normalised with the
+ *              ImageNet mean / std in the loader, whatever lut_mode the workspace was prepared with);
+ *   vpool 1    out [C][B][Ho/2][Wo][Cout] = max over conv rows (2a-1, 2a, 2a+1) of the ReLU output, rows outside the map skipped
+ *              (the vertical half of the 3x3 / s2 / p1 pool; actmi_op_hpool finishes it): f16x3, relu 1, even Ho, Cout % 4 == 0;
+ *   cam0, ncam the launch computes cameras cam0 .. cam0 + ncam - 1 only (ncam 0: all C, with cam0 0); image, workspace, scale,
+ *              bias and out stay whole-tensor pointers and the other cameras' part of out is not touched;
+ *   prec       0 or ACTMI_PREC_F16X3, or ACTMI_PREC_F32 (plain form with relu 1 only).
+ * A u8 frame needs H * W * 3 >= 4 bytes.  out 16-byte aligned when Cout % 4 == 0.  What the launcher refuses comes back as
+ * ACTMI_E_SHAPE with its message in actmi_op_last_error. */
+int actmi_op_conv1_prepared_ex(const void* image, int image_fmt, const float* workspace, const float* scale, const float* bias,
+                               float* out, int B, int C, int H, int W, int Cout, int relu, int vpool, int cam0, int ncam, int prec,
+                               void* stream);
+/* horizontal half of the 3x3 / s2 / p1 max pool on nrows independent NHWC rows: in [nrows][W][C] -> out [nrows][Wo][C],
+ * out[.][pw] = max(in[.][2pw-1 .. 2pw+1]) over the columns inside the row, Wo = (W-1)/2+1; C % 4 == 0 (else ACTMI_E_SHAPE),
+ * in / out 16-byte aligned; nrows = 0 is a no-op */
+int actmi_op_hpool(const float* in, float* out, int nrows, int W, int C, void* stream);
 /* direct 3x3 / stride 1 / pad 1 convolution for 64 -> 64 channels (ResNet18 layer1), f16x3: x camera-major NHWC
  * [G][B][H][W][64]; w16 = actmi_op_split16 image (built with w_scale) of the weights [G][64][3][3][64] (cout, r, s, cin);
  * out = act(conv * scale + bias (+ res)) */

@@ -336,10 +336,16 @@ def test_layernorm(M, D):
     assert rel_err(g1, e1) < 2e-6 and rel_err(g2, e2) < 4e-6
 
 
-@pytest.mark.parametrize("H,W", [(23, 31), (24, 32), (22, 29), (240, 320)])
-def test_maxpool_bit_exact(H, W):
+# the first four keep their ids; then C = 4 and 8, maps one or two pixels high or wide, and 3 x 130 x 170 x 16 = 1 060 800 float4
+# outputs against the grid cap of 4096 x 256 threads, so that the grid-stride loop takes a second pass
+@pytest.mark.parametrize("n,C,H,W", [(3, 64, 23, 31), (3, 64, 24, 32), (3, 64, 22, 29), (3, 64, 240, 320),
+                                     (3, 4, 23, 31), (2, 8, 22, 29), (3, 64, 1, 31), (3, 8, 2, 32), (3, 8, 23, 1), (2, 4, 24, 2),
+                                     (3, 4, 1, 1), (2, 8, 2, 2), (3, 64, 260, 340)],
+                         ids=["23-31", "24-32", "22-29", "240-320", "c4-23-31", "c8-22-29", "1-31", "c8-2-32", "c8-23-1", "c4-24-2",
+                              "c4-1-1", "c8-2-2", "260-340"])
+def test_maxpool_bit_exact(n, C, H, W):
     g = torch.Generator().manual_seed(1)
-    x = torch.randn(3, 64, H, W, generator=g)
+    x = torch.randn(n, C, H, W, generator=g)
     exp = F.max_pool2d(x, 3, 2, 1)
     got = ops.maxpool3x3s2(x.permute(0, 2, 3, 1).contiguous().to(dev()))
     assert torch.equal(got.permute(0, 3, 1, 2).cpu(), exp)      # max is order independent: bit exact

@@ -62,7 +62,8 @@ def test_host_mask_equals_the_device_mask(seed, p):
 # 1. max pool with codes, and its backward
 # ---------------------------------------------------------------------------------------------------------------------------
 POOL_CASES = [(1, 1, 1, 4, False), (2, 2, 3, 4, False), (3, 7, 9, 8, False), (2, 8, 10, 64, False), (4, 23, 31, 64, False),
-              (3, 7, 9, 8, True)]                      # the last: one whole image of zeros (every window of it tied)
+              (3, 7, 9, 8, True),                      # one whole image of zeros (every window of it tied)
+              (3, 260, 340, 64, False)]                # 1 060 800 float4 outputs against 4096 x 256 threads: the kernels' loops run twice
 
 
 def _tie_rule_is_tested(tied, H, W):
