@@ -70,6 +70,8 @@ class ACTEngine:
             L.check(self.lib.actmi_set_train_prec(self.h, {"f32": 1, "f16x3": 2, "bf16": 3}[train_prec]), self.h, "set_train_prec")
         self.spec = act_state_dict_spec(cfg)
         self._finalized = False
+        self._fusion = None            # ops.RGBDFusion registered by set_rgbd_fusion: pointcloud={"depth": u16 frames} is fused on the device
+        self._phase = 0
         # attributes imitate_episodes.py touches on policy.model
         self.num_queries = cfg.num_queries
         self.encoder = None if cfg.no_encoder else True
@@ -163,18 +165,54 @@ class ACTEngine:
             raise ValueError(f"image shape {tuple(image.shape)} != {want}")
         return fmt
 
-    def _bind_pointcloud(self, pointcloud, B: int):
+    def set_rgbd_fusion(self, fusion):
+        """Register an ops.RGBDFusion (None: remove it).  From then on ``pointcloud={"depth": depth_u16}`` -- raw depth frames
+        [B, K, H, W] or [B, K, 1, H, W] uint16 on the engine's device -- is accepted wherever ``pointcloud=`` is: the cloud is
+        built from them and from the call's own uint8 frame batch on the device (actmi_op_rgbd_cloud), on the caller's stream
+        right in front of the forward, and bound through actmi_set_pointcloud_n.  Ready-made clouds keep working as before."""
+        if fusion is not None:
+            if not self.cfg.use_pcd:
+                raise ValueError("set_rgbd_fusion on an engine whose config has use_pcd=False")
+            if fusion.device != self.device:
+                raise ValueError(f"the fusion lives on {fusion.device} but this engine is bound to {self.device}")
+            if (fusion.H, fusion.W) != (self.cfg.image_h, self.cfg.image_w):
+                raise ValueError(f"the fusion's frames are {fusion.H} x {fusion.W}, the engine's {self.cfg.image_h} x {self.cfg.image_w}")
+            if max(fusion.cam_index) >= self.cfg.num_cams:
+                raise ValueError(f"the fusion's cam_index {fusion.cam_index} names a camera outside 0..{self.cfg.num_cams - 1}")
+            if fusion.P > self.max_points:
+                raise ValueError(f"the fusion's sum(quota) = {fusion.P} points per sample > max_points {self.max_points}")
+        self._fusion = fusion
+
+    def _fuse_cloud(self, pointcloud, image, B: int):
+        """pointcloud={"depth": u16 frames}: the cloud the registered fusion builds from them and from `image`.  Forward phase 2
+        reads no cloud, so there only the fusion's buffers are bound and nothing is launched."""
+        if self._fusion is None:
+            raise ValueError("pointcloud={'depth': ...} needs a registered fusion: engine.set_rgbd_fusion(ops.RGBDFusion(...))")
+        if B > self._fusion.max_batch:
+            raise ValueError(f"batch {B} > the fusion's max_batch {self._fusion.max_batch}")
+        if not isinstance(image, torch.Tensor) or not image.is_cuda:
+            raise ValueError("qpos and image must be CUDA tensors on the engine's device")
+        image = image.contiguous()
+        depth = self._fusion.check_inputs(image, pointcloud["depth"], B)
+        if self._phase == 2:
+            return self._fusion.outputs(B)
+        return self._fusion.fuse(image, depth, B)
+
+    def _bind_pointcloud(self, pointcloud, B: int, image=None):
         """Check the clouds of a use_pcd engine ({"xyz": [B, P, 3], "rgb": [B, P, 3]} float32 device tensors) and bind them for
         the next forward (actmi_set_pointcloud_n).  Returns the tensors the library will read.  Ragged clouds padded to a common P
         carry "n": int32 [B] on the engine's device, the number of points of every sample (rows at or behind it: finite padding,
         zeros by convention).  The library reads it on the device; its values are not checked here -- that would synchronise --
-        and are clamped to [1, P] where they are read."""
+        and are clamped to [1, P] where they are read.  {"depth": uint16 frames} (set_rgbd_fusion) is first fused into such a
+        cloud from `image`, the call's uint8 frame batch."""
         if not self.cfg.use_pcd:
             if pointcloud is not None:
                 raise ValueError("pointcloud given to an engine whose config has use_pcd=False")
             return None
         if pointcloud is None:
             raise ValueError("a use_pcd engine needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]}")
+        if "depth" in pointcloud:
+            pointcloud = self._fuse_cloud(pointcloud, image, B)
         xyz, rgb = pointcloud["xyz"], pointcloud["rgb"]
         for name, t in (("pointcloud['xyz']", xyz), ("pointcloud['rgb']", rgb)):
             if not t.is_cuda:
@@ -248,9 +286,9 @@ class ACTEngine:
         if not (qpos.is_cuda and image.is_cuda):
             raise ValueError("qpos and image must be CUDA tensors on the engine's device")
         self._check_dev(qpos=qpos, image=image, out=out)
-        cloud = self._bind_pointcloud(pointcloud, B)          # (kept alive until the forward below has been enqueued)
-        qpos = qpos.to(torch.float32).contiguous()
         image = image.contiguous()
+        cloud = self._bind_pointcloud(pointcloud, B, image)   # (kept alive until the forward below has been enqueued)
+        qpos = qpos.to(torch.float32).contiguous()
         fmt = self._image_fmt(image, B)
         if tuple(qpos.shape) != (B, cfg.state_dim):
             raise ValueError(f"qpos shape {tuple(qpos.shape)} != {(B, cfg.state_dim)}")
@@ -278,9 +316,11 @@ class ACTEngine:
     def set_forward_phase(self, phase: int):
         """0: forward_infer runs the whole step; 1: trunk + token assembly only; 2: transformer only (actmi_set_forward_phase)"""
         L.check(self.lib.actmi_set_forward_phase(self.h, int(phase)), self.h, "set_forward_phase")
+        self._phase = int(phase)
 
     def capture_infer(self, batch: int, image_dtype=torch.uint8, with_ensemble=None, statics=None, phase: int = 0,
-                      num_points: int = None, depth_dtype=torch.float32, static_depth=None, static_cloud=None):
+                      num_points: int = None, depth_dtype=torch.float32, static_depth=None, static_cloud=None,
+                      fuse_depth: bool = False):
         """Capture one forward (optionally + the temporal-ensemble kernel) into a hipGraph and return
         ``replay(qpos, image) -> a_hat`` that copies into static inputs and replays.  A use_pcd engine captures static
         xyz / rgb buffers of ``num_points`` points (default max_points) and a static int32 counts buffer ``n`` (filled with
@@ -289,10 +329,20 @@ class ACTEngine:
         engine captures a static depth buffer of ``depth_dtype`` (float32 or uint16; or the caller's ``static_depth``) and replays
         ``replay(qpos, image, depth_img=...)`` with a batch of exactly that dtype.  The forward path allocates
         nothing and never synchronises, so the whole step is one graph launch (removes ~60 kernel-launch gaps; matters
-        at small batch where the step is launch-bound)."""
+        at small batch where the step is launch-bound).  ``fuse_depth=True`` (a use_pcd engine with a registered fusion,
+        set_rgbd_fusion): the graph owns a static uint16 depth buffer [B, K, H, W] (``replay.static_cloud["depth"]``), the fusion
+        op is captured ahead of the forward, and the graph replays ``replay(qpos, image, pointcloud={"depth": frames})``; the
+        fusion's parameter block and seed are read on the device, so set_extrinsics / set_seed between replays take effect."""
         if not self._finalized:
             self.finalize()
         cfg, dev = self.cfg, self.device
+        if fuse_depth:
+            if not cfg.use_pcd or self._fusion is None:
+                raise ValueError("capture_infer(fuse_depth=True) needs a use_pcd engine with a registered fusion (set_rgbd_fusion)")
+            if image_dtype != torch.uint8:
+                raise ValueError("capture_infer(fuse_depth=True) needs uint8 frames: the cloud's colours are their bytes")
+            if static_cloud is None:
+                static_cloud = {"depth": torch.zeros((batch, self._fusion.K, cfg.image_h, cfg.image_w), dtype=torch.uint16, device=dev)}
         shape = (batch, cfg.num_cams, cfg.image_h, cfg.image_w, 3) if image_dtype == torch.uint8 else \
                 (batch, cfg.num_cams, 3, cfg.image_h, cfg.image_w)
         if statics is not None:
@@ -314,7 +364,7 @@ class ACTEngine:
             npts = self.max_points if num_points is None else int(num_points)
             if static_cloud is not None:
                 s_cloud = static_cloud
-                npts = s_cloud["xyz"].shape[1]
+                npts = s_cloud["xyz"].shape[1] if "depth" not in s_cloud else self._fusion.P
             else:
                 s_cloud = {k: torch.zeros((batch, npts, 3), dtype=torch.float32, device=dev) for k in ("xyz", "rgb")}
                 s_cloud["n"] = torch.full((batch,), npts, dtype=torch.int32, device=dev)
@@ -364,6 +414,17 @@ class ACTEngine:
             if s_cloud is not None:
                 if pointcloud is None:
                     raise ValueError("a use_pcd engine needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]}")
+                if "depth" in s_cloud:
+                    d = pointcloud.get("depth")
+                    if d is None:
+                        raise ValueError("this graph fuses depth frames: replay(qpos, image, pointcloud={'depth': uint16 frames})")
+                    if d.dtype != torch.uint16 or d.numel() != s_cloud["depth"].numel() or d.shape[:2] != s_cloud["depth"].shape[:2]:
+                        raise ValueError(f"pointcloud['depth'] is {d.dtype} {tuple(d.shape)}, the captured buffer uint16 "
+                                         f"{tuple(s_cloud['depth'].shape)}")
+                    if d.data_ptr() != s_cloud["depth"].data_ptr():
+                        s_cloud["depth"].copy_(d.reshape(s_cloud["depth"].shape), non_blocking=True)
+                    graph.replay()
+                    return (s_out, ens_out) if with_ensemble is not None else s_out
                 for k in ("xyz", "rgb"):
                     if tuple(pointcloud[k].shape) != tuple(s_cloud[k].shape):
                         raise ValueError(f"pointcloud[{k!r}] shape {tuple(pointcloud[k].shape)} != the captured "
@@ -429,7 +490,7 @@ class ACTEngine:
         a_hat = torch.empty((B, Q, A), dtype=torch.float32, device=dev)
         mu = torch.empty((B, Lz), dtype=torch.float32, device=dev)
         logvar = torch.empty((B, Lz), dtype=torch.float32, device=dev)
-        cloud = self._bind_pointcloud(pointcloud, B)
+        cloud = self._bind_pointcloud(pointcloud, B, image)
         depth = self._bind_depth(depth_img, B)
         self._keep = (qpos, image, actions, is_pad_u8, eps, cloud, depth)        # the library reads qpos and the clouds again in backward
         L.check(self.lib.actmi_forward_train(
@@ -704,13 +765,25 @@ class InferPipeline:
     checked on the host -- and ``next_inputs`` is (qpos_host, image_host, cloud_host).  B * P * 24 + 4 B bytes a step: 786 KB at
     B = 8, P = 4096, beside 29.5 MB of frames.
 
+    ``fuse_depth=True`` (a use_pcd engine with a registered fusion, set_rgbd_fusion) feeds raw depth instead of clouds: every slot
+    owns a uint16 depth buffer [B, K, H, W], ``feed(qpos, image, depth_host=...)`` copies it beside the frame, the trunk graph
+    (forward phase 1) captures the fusion op and then the PointNet, and ``next_inputs`` is (qpos_host, image_host, depth_host):
+    2 bytes per depth pixel cross the bus and nothing else of the cloud.
+
     No host synchronisation anywhere; the pinned host tensors of a feed must stay untouched until the step AFTER the one they were
     passed to has been issued and `pipe.copied(k)` has completed (or simply use one host buffer per step in flight).  Outputs of
     step t stay valid until step t + 2 is issued."""
 
     def __init__(self, engine: "ACTEngine", batch: int, with_ensemble=None, image_dtype=torch.uint8, copy_stream_candidates: int = 8,
-                 depth_dtype=None, num_points: int = None):
-        if engine.cfg.use_pcd and num_points is None:
+                 depth_dtype=None, num_points: int = None, fuse_depth: bool = False):
+        if fuse_depth:
+            if not engine.cfg.use_pcd or engine._fusion is None:
+                raise ValueError("InferPipeline(fuse_depth=True) needs a use_pcd engine with a registered fusion (set_rgbd_fusion)")
+            if num_points is not None:
+                raise ValueError("fuse_depth=True builds the clouds on the device: num_points goes with a host feed of ready clouds")
+            if image_dtype != torch.uint8:
+                raise ValueError("InferPipeline(fuse_depth=True) needs uint8 frames: the cloud's colours are their bytes")
+        elif engine.cfg.use_pcd and num_points is None:
             raise NotImplementedError("InferPipeline feeds no point clouds (use capture_infer), unless num_points=P asks for "
                                       "cloud buffers of P points per sample")
         if num_points is not None and not engine.cfg.use_pcd:
@@ -740,6 +813,8 @@ class InferPipeline:
             if P is not None:
                 s_cloud = {k: torch.zeros((batch, P, 3), dtype=torch.float32, device=dev) for k in ("xyz", "rgb")}
                 s_cloud["n"] = torch.full((batch,), P, dtype=torch.int32, device=dev)
+            elif fuse_depth:                                        # the slot's raw depth frames; the trunk graph fuses them
+                s_cloud = {"depth": torch.zeros((batch, engine._fusion.K, cfg.image_h, cfg.image_w), dtype=torch.uint16, device=dev)}
             trunk = engine.capture_infer(batch, image_dtype=image_dtype, statics=st, phase=1, static_depth=s_depth,
                                          static_cloud=s_cloud)
             rest = engine.capture_infer(batch, image_dtype=image_dtype, with_ensemble=with_ensemble, statics=st, phase=2,
@@ -770,7 +845,9 @@ class InferPipeline:
         d0 = self.depth[0]
         nxt = (hq, him) if d0 is None else (hq, him, torch.zeros(d0.shape, dtype=d0.dtype).pin_memory())
         c0 = self.cloud[0]
-        if c0 is not None:                                          # the clouds cross with the frame: time them with it
+        if c0 is not None and "depth" in c0:                        # fused on the device: the raw depth frames cross with the frame
+            nxt = (hq, him, torch.zeros(c0["depth"].shape, dtype=torch.uint16).pin_memory())
+        elif c0 is not None:                                        # the clouds cross with the frame: time them with it
             hc = {k: torch.zeros(c0[k].shape, dtype=c0[k].dtype).pin_memory() for k in ("xyz", "rgb")}
             hc["n"] = torch.full(c0["n"].shape, c0["xyz"].shape[1], dtype=torch.int32).pin_memory()
             nxt = (hq, him, hc)
@@ -781,7 +858,8 @@ class InferPipeline:
             for rep in range(2):                                    # (the first round also warms the graphs up)
                 torch.cuda.synchronize(dev)
                 t0 = time.perf_counter()
-                self.feed(*nxt[:2], depth_host=nxt[2] if d0 is not None else None, cloud_host=nxt[2] if c0 is not None else None)
+                self.feed(*nxt[:2], depth_host=nxt[2] if (d0 is not None or (c0 is not None and "depth" in c0)) else None,
+                          cloud_host=nxt[2] if (c0 is not None and "depth" not in c0) else None)
                 for i in range(12):
                     self.step(next_inputs=nxt if i < 11 else None)
                 torch.cuda.synchronize(dev)
@@ -802,16 +880,20 @@ class InferPipeline:
         k = self.k_run if slot is None else slot
         s_qpos, s_img, _ = self.slots[k][0]
         s_depth = self.depth[k]
+        s_cloud = self.cloud[k]
+        if s_cloud is not None and "depth" in s_cloud:              # fuse_depth: the depth frames feed the fusion, no clouds cross
+            s_depth, s_cloud = s_cloud["depth"], None
+            if depth_host is not None and depth_host.dim() == 5 and depth_host.shape[2] == 1:
+                depth_host = depth_host.reshape(depth_host.shape[:2] + depth_host.shape[3:])
         if s_depth is None:
             if depth_host is not None:
                 raise ValueError("depth_host given to a pipeline without a depth feed")
         else:
             if depth_host is None:
-                raise ValueError("this pipeline feeds a use_depth engine: feed(qpos_host, image_host, depth_host=...)")
+                raise ValueError("this pipeline feeds depth frames: feed(qpos_host, image_host, depth_host=...)")
             if depth_host.dtype != s_depth.dtype or tuple(depth_host.shape) != tuple(s_depth.shape):
                 raise ValueError(f"depth_host is {depth_host.dtype} {tuple(depth_host.shape)}, the pipeline's depth buffer "
                                  f"{s_depth.dtype} {tuple(s_depth.shape)}")
-        s_cloud = self.cloud[k]
         if s_cloud is None:
             if cloud_host is not None:
                 raise ValueError("cloud_host given to a pipeline without a point-cloud feed")
@@ -860,17 +942,18 @@ class InferPipeline:
         cur = torch.cuda.current_stream(self.dev)
         cur.wait_event(self.ev_copy[k])
         s_depth, s_cloud = self.depth[k], self.cloud[k]
+        fused = s_cloud is not None and "depth" in s_cloud
         trunk(s_qpos, s_img, pointcloud=s_cloud, depth_img=s_depth)
         self.ev_trunk[k].record(cur)
         self.ran[k] = True
         self.fed[k] = False
         if next_inputs is not None:
-            if s_depth is not None and len(next_inputs) != 3:
-                raise ValueError("this pipeline feeds a use_depth engine: next_inputs = (qpos_host, image_host, depth_host)")
-            if s_cloud is not None and len(next_inputs) != 3:
+            if (s_depth is not None or fused) and len(next_inputs) != 3:
+                raise ValueError("this pipeline feeds depth frames: next_inputs = (qpos_host, image_host, depth_host)")
+            if s_cloud is not None and not fused and len(next_inputs) != 3:
                 raise ValueError("this pipeline feeds a use_pcd engine: next_inputs = (qpos_host, image_host, cloud_host)")
-            self.feed(next_inputs[0], next_inputs[1], slot=k ^ 1, depth_host=next_inputs[2] if s_depth is not None else None,
-                      cloud_host=next_inputs[2] if s_cloud is not None else None)
+            self.feed(next_inputs[0], next_inputs[1], slot=k ^ 1, depth_host=next_inputs[2] if (s_depth is not None or fused) else None,
+                      cloud_host=next_inputs[2] if (s_cloud is not None and not fused) else None)
         out = rest(s_qpos, s_img, pointcloud=s_cloud, depth_img=s_depth)
         self.k_run ^= 1
         return out

@@ -86,6 +86,26 @@ class AttnDesc(C.Structure):
     ]
 
 
+RGBD_MAX_CAMS = 8
+
+
+class RgbdCam(C.Structure):
+    # one fusion camera of the device parameter block (actmi_rgbd_cam): 20 words
+    _fields_ = [("cam_index", C.c_int32), ("quota", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("depth_scale", C.c_float), ("T", C.c_float * 12), ("reserved", C.c_float)]
+
+
+class RgbdCalib(C.Structure):
+    _fields_ = [("cam", RgbdCam * RGBD_MAX_CAMS), ("box", C.c_float * 6), ("reserved", C.c_float * 2)]
+
+
+class RgbdDesc(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("image", C.c_void_p), ("calib", C.c_void_p), ("seed", C.c_void_p), ("xyz", C.c_void_p),
+                ("rgb", C.c_void_p), ("n", C.c_void_p), ("src_idx", C.c_void_p), ("survivors", C.c_void_p), ("ws", C.c_void_p),
+                ("ws_bytes", C.c_int64)] + [(k, C.c_int32) for k in ("B", "K", "C", "H", "W", "P")] + \
+               [("quota", C.c_int32 * RGBD_MAX_CAMS), ("cam_index", C.c_int32 * RGBD_MAX_CAMS)]
+
+
 _lib = None
 
 
@@ -174,6 +194,8 @@ def load():
         "actmi_op_pcd_embed": ([vp, vp, vp, vp, vp, C.c_int64, i32, vp], i32),
         "actmi_op_colmax": ([vp, i32, i32, i32, C.c_int64, vp, vp, vp, C.c_int64, vp], i32),
         "actmi_op_colmax_n": ([vp, i32, i32, i32, C.c_int64, vp, vp, vp, vp, C.c_int64, vp], i32),
+        "actmi_op_rgbd_cloud_workspace_bytes": ([i32, i32, i32, i32], C.c_int64),
+        "actmi_op_rgbd_cloud": ([C.POINTER(RgbdDesc), vp], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

@@ -843,6 +843,203 @@ def layernorm_bwd_ex(x, w, dy, dw, db, ws=None, dx_add=None, eps=1e-5, dx_amax=N
     return dx
 
 
+# ---- RGB-D frames -> the point cloud of a use_pcd policy (csrc/rgbd_cloud.hip; contract at actmi_rgbd_desc in actmi.h) ----------
+def rgbd_select_key(seed, b, k, pixel, H, W):
+    """The selection key of actmi_op_rgbd_cloud in numpy: a seeded bijection of [0, 2^m), m = max(1, ceil(log2(H * W))), of which
+    camera k of sample b keeps the quota[k] survivors with the smallest values.  pixel: integers (any shape) -> uint32."""
+    import numpy as np
+    m = max(1, int(H * W - 1).bit_length())
+    M64 = (1 << 64) - 1
+
+    def mix(z):
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+        return z ^ (z >> 31)
+    s0 = mix((int(seed) + 0x9E3779B97F4A7C15 * (int(b) * 8 + int(k) + 1)) & M64)
+    s1 = mix((s0 + 0x9E3779B97F4A7C15) & M64)
+    s2 = mix((s1 + 0x9E3779B97F4A7C15) & M64)
+    c0, adds = s0 & 0xFFFFFFFF, (s0 >> 32, s1 & 0xFFFFFFFF, s1 >> 32, s2 & 0xFFFFFFFF)
+    mask, h = np.uint64((1 << m) - 1), np.uint64((m + 1) // 2)
+    x = (np.asarray(pixel).astype(np.uint64) ^ np.uint64(c0)) & mask
+    for g, a in zip((0x9E3779B1, 0x85EBCA6B, 0xC2B2AE35, 0x27D4EB2F), adds):
+        x = (x * np.uint64(g)) & mask                  # (x < 2^20, g < 2^32: no 64-bit overflow)
+        x ^= x >> h
+        x = (x + np.uint64(a)) & mask
+    return x.astype(np.uint32)
+
+
+class RGBDFusion:
+    """Builds the cloud of a use_pcd policy from raw depth frames on the device (actmi_op_rgbd_cloud), in place of the reference's
+    host-side fusion node (aloha_scripts/jie_aloha_scripts/pcd_fusion.py:186-243, 278-279).  Owns the device parameter block, the
+    seed word, the workspace and the output buffers.
+
+    engine_or_device: an ACTEngine (its num_cams, image size, max_points and device are checked against) or a device.
+    K fusion cameras of H x W pixels; cam_index[k]: the colour frame registered to depth camera k; intrinsics [K, 4] = (fx, fy,
+    cx, cy); depth_scale: metres per depth unit (a number or [K]); extrinsics [K, 3, 4] or [K, 4, 4]: camera optical frame ->
+    base; box = (xmin, xmax, ymin, ymax, zmin, zmax), ends included; quota [K] >= 1: points kept per camera at most, P =
+    sum(quota) rows per sample; max_batch sizes the buffers (default: the engine's).
+
+    fuse(image_u8, depth_u16, B) -> {"xyz", "rgb": [B, P, 3] f32, "n": [B] int32}: views of the fusion's own buffers, valid until
+    the next fuse.  Everything is validated on the host, before any device call (ValueError)."""
+
+    def __init__(self, engine_or_device, K, H, W, cam_index, intrinsics, depth_scale, extrinsics, box, quota, max_batch=None,
+                 num_cams=None, seed=0):
+        import numpy as np
+        eng = engine_or_device if hasattr(engine_or_device, "max_points") else None
+        self.device = torch.device(eng.device if eng is not None else engine_or_device)
+        if self.device.type != "cuda":
+            raise ValueError(f"RGBDFusion: device must be a cuda device, got {self.device}")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        K, H, W = int(K), int(H), int(W)
+        if not 1 <= K <= L.RGBD_MAX_CAMS:
+            raise ValueError(f"RGBDFusion: K = {K} fusion cameras: needs 1 <= K <= {L.RGBD_MAX_CAMS}")
+        if H < 1 or W < 1 or not 2 <= H * W <= 1 << 20:
+            raise ValueError(f"RGBDFusion: frames of {H} x {W}: needs 2 <= H * W <= 2^20")
+        if eng is not None:
+            num_cams = eng.cfg.num_cams
+            if (H, W) != (eng.cfg.image_h, eng.cfg.image_w):
+                raise ValueError(f"RGBDFusion: depth frames of {H} x {W}, the engine's colour frames {eng.cfg.image_h} x "
+                                 f"{eng.cfg.image_w}: the depth is registered to the colour frame and has its size")
+            if max_batch is None:
+                max_batch = eng.max_batch
+        self.K, self.H, self.W = K, H, W
+        self.num_cams = None if num_cams is None else int(num_cams)
+        self.max_batch = int(max_batch if max_batch is not None else 8)
+        if self.max_batch < 1:
+            raise ValueError(f"RGBDFusion: max_batch {max_batch} < 1")
+        ci = np.asarray(cam_index)
+        if ci.shape != (K,) or ci.dtype.kind not in "iu":
+            raise ValueError(f"RGBDFusion: cam_index must hold {K} integers, got {ci.dtype} {ci.shape}")
+        if ci.min() < 0 or (self.num_cams is not None and ci.max() >= self.num_cams):
+            raise ValueError(f"RGBDFusion: cam_index {ci.tolist()} outside 0..{'C-1' if self.num_cams is None else self.num_cams - 1}")
+        q = np.asarray(quota)
+        if q.shape != (K,) or q.dtype.kind not in "iu" or q.min() < 1:
+            raise ValueError(f"RGBDFusion: quota must hold {K} integers >= 1, got {q.dtype} {q.shape} {q.tolist() if q.size <= 8 else ''}")
+        self.P = int(q.sum())
+        if eng is not None and self.P > eng.max_points:
+            raise ValueError(f"RGBDFusion: sum(quota) = {self.P} points per sample > the engine's max_points {eng.max_points}")
+        intr = np.asarray(intrinsics, dtype=np.float64)
+        if intr.shape != (K, 4) or not np.isfinite(intr).all() or (intr[:, :2] == 0).any():
+            raise ValueError(f"RGBDFusion: intrinsics must be finite [{K}, 4] = (fx, fy, cx, cy) with fx, fy != 0, got {intr.shape}")
+        ds = np.broadcast_to(np.asarray(depth_scale, dtype=np.float64), (K,)) if np.ndim(depth_scale) <= 1 and \
+            np.size(depth_scale) in (1, K) else None
+        if ds is None or not np.isfinite(ds).all() or (ds <= 0).any():
+            raise ValueError(f"RGBDFusion: depth_scale must be a positive number or [{K}] of them")
+        bx = np.asarray(box, dtype=np.float64)
+        if bx.shape != (6,) or not np.isfinite(bx).all() or (bx[0::2] > bx[1::2]).any():
+            raise ValueError("RGBDFusion: box must be 6 finite numbers (xmin, xmax, ymin, ymax, zmin, zmax) with min <= max")
+        self.cam_index, self.quota = [int(v) for v in ci], [int(v) for v in q]
+        self._host = L.RgbdCalib()
+        for k in range(K):
+            c = self._host.cam[k]
+            c.cam_index, c.quota = self.cam_index[k], self.quota[k]
+            c.fx, c.fy, c.cx, c.cy = (float(v) for v in intr[k])
+            c.depth_scale = float(ds[k])
+        for i in range(6):
+            self._host.box[i] = float(bx[i])
+        self._fill_extrinsics(extrinsics)
+        self._seed_host = int(seed) & ((1 << 64) - 1)
+        self._calib = None                             # device buffers: made on the first use of a GPU (the checks above need none)
+        if torch.cuda.is_available():
+            self._alloc()
+
+    def _fill_extrinsics(self, extrinsics):
+        import numpy as np
+        T = np.asarray(extrinsics, dtype=np.float64)
+        if T.shape not in ((self.K, 3, 4), (self.K, 4, 4)) or not np.isfinite(T).all():
+            raise ValueError(f"RGBDFusion: extrinsics must be finite [{self.K}, 3, 4] or [{self.K}, 4, 4], got {T.shape}")
+        for k in range(self.K):
+            for i, v in enumerate(T[k, :3].reshape(12)):
+                self._host.cam[k].T[i] = float(v)
+
+    def _alloc(self):
+        dev, MB, P, K = self.device, self.max_batch, self.P, self.K
+        nbytes = int(L.load().actmi_op_rgbd_cloud_workspace_bytes(MB, K, self.H, self.W))
+        if nbytes < 0:
+            raise ValueError(f"RGBDFusion: shape B = {MB}, K = {K}, {self.H} x {self.W} not supported by actmi_op_rgbd_cloud")
+        self._ws = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        self._calib = torch.zeros(C.sizeof(L.RgbdCalib), dtype=torch.uint8, device=dev)
+        self._seed = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.xyz = torch.zeros((MB, P, 3), dtype=torch.float32, device=dev)
+        self.rgb = torch.zeros((MB, P, 3), dtype=torch.float32, device=dev)
+        self.n = torch.zeros((MB,), dtype=torch.int32, device=dev)
+        self.src_idx = torch.full((MB, P), -1, dtype=torch.int32, device=dev)
+        self.survivors = torch.zeros((MB, K), dtype=torch.int32, device=dev)
+        self._push_calib()
+        self.set_seed(self._seed_host)
+
+    def _push_calib(self):
+        if self._calib is not None:                    # a copy on the current stream: launches enqueued behind it, captured ones too, see it
+            host = torch.frombuffer(bytearray(bytes(self._host)), dtype=torch.uint8)
+            with torch.cuda.device(self.device):
+                self._calib.copy_(host)
+
+    def set_extrinsics(self, extrinsics):
+        """new camera -> base transforms [K, 3, 4] or [K, 4, 4], copied into the device block on the current stream"""
+        self._fill_extrinsics(extrinsics)
+        self._push_calib()
+
+    def set_seed(self, seed):
+        """the 64-bit seed of the subset drawn where a camera has more survivors than its quota; a copy on the current stream"""
+        self._seed_host = int(seed) & ((1 << 64) - 1)
+        if self._calib is not None:
+            v = self._seed_host - (1 << 64) if self._seed_host >= 1 << 63 else self._seed_host
+            with torch.cuda.device(self.device):
+                self._seed.copy_(torch.tensor([v], dtype=torch.int64))
+
+    def check_inputs(self, image_u8, depth_u16, B):
+        """the host-side checks of fuse(); returns depth as [B, K, H, W]"""
+        K, H, W = self.K, self.H, self.W
+        B = int(B)
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"RGBDFusion: B = {B}: needs 1 <= B <= max_batch {self.max_batch}")
+        if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8:
+            raise ValueError(f"RGBDFusion: the image batch must be a uint8 [B, C, H, W, 3] tensor (the colours are its bytes), got "
+                             f"{getattr(image_u8, 'dtype', type(image_u8))}")
+        if image_u8.dim() != 5 or image_u8.shape[0] != B or tuple(image_u8.shape[2:]) != (H, W, 3):
+            raise ValueError(f"RGBDFusion: image shape {tuple(image_u8.shape)} != {(B, 'C', H, W, 3)}")
+        Cn = image_u8.shape[1]
+        if (self.num_cams is not None and Cn != self.num_cams) or max(self.cam_index) >= Cn:
+            raise ValueError(f"RGBDFusion: image holds {Cn} cameras; cam_index {self.cam_index}, num_cams {self.num_cams}")
+        if not isinstance(depth_u16, torch.Tensor) or depth_u16.dtype != torch.uint16:
+            raise ValueError(f"RGBDFusion: depth must be a uint16 tensor, got {getattr(depth_u16, 'dtype', type(depth_u16))}")
+        if tuple(depth_u16.shape) == (B, K, 1, H, W):
+            depth_u16 = depth_u16.view(B, K, H, W) if depth_u16.is_contiguous() else depth_u16.reshape(B, K, H, W)
+        if tuple(depth_u16.shape) != (B, K, H, W):
+            raise ValueError(f"RGBDFusion: depth shape {tuple(depth_u16.shape)} != {(B, K, H, W)} (or {(B, K, 1, H, W)})")
+        if not (image_u8.is_contiguous() and depth_u16.is_contiguous()):
+            raise ValueError("RGBDFusion: image and depth must be contiguous")
+        for name, t in (("image", image_u8), ("depth", depth_u16)):
+            if not t.is_cuda or t.device != self.device:
+                raise ValueError(f"RGBDFusion: {name} lives on {t.device}, the fusion on {self.device}")
+        return depth_u16
+
+    def outputs(self, B):
+        """the views fuse() returns, without a launch"""
+        if self._calib is None:
+            self._alloc()
+        return {"xyz": self.xyz[:B], "rgb": self.rgb[:B], "n": self.n[:B]}
+
+    def fuse(self, image_u8, depth_u16, B=None):
+        B = int(depth_u16.shape[0] if B is None else B)
+        depth_u16 = self.check_inputs(image_u8, depth_u16, B)
+        if self._calib is None:
+            self._alloc()
+        d = L.RgbdDesc()
+        d.depth, d.image, d.calib, d.seed = depth_u16.data_ptr(), image_u8.data_ptr(), self._calib.data_ptr(), self._seed.data_ptr()
+        d.xyz, d.rgb, d.n = self.xyz.data_ptr(), self.rgb.data_ptr(), self.n.data_ptr()
+        d.src_idx, d.survivors = self.src_idx.data_ptr(), self.survivors.data_ptr()
+        d.ws, d.ws_bytes = self._ws.data_ptr(), self._ws.numel() * 8
+        d.B, d.K, d.C, d.H, d.W, d.P = B, self.K, image_u8.shape[1], self.H, self.W, self.P
+        for k in range(self.K):
+            d.quota[k], d.cam_index[k] = self.quota[k], self.cam_index[k]
+        with torch.cuda.device(self.device):
+            L.check(L.load().actmi_op_rgbd_cloud(C.byref(d), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), None,
+                    "op_rgbd_cloud")
+        return self.outputs(B)
+
+
 class TemporalEnsemble:
     """Batched temporal ensembling state for E episodes (reference imitate_episodes.py:338-339, 402-411).
     Ring buffer [E,Q,Q,A] instead of the reference's [T,T+Q,A] per episode: only the last Q chunks can

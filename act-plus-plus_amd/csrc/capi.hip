@@ -387,6 +387,15 @@ int actmi_op_conv1_depth(const float* depth, const float* w_oihw, const float* s
     const int rc = launch_conv1_depth(a, S(stream), &g_op_error);
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
 }
+int64_t actmi_op_rgbd_cloud_workspace_bytes(int B, int K, int H, int W) { return rgbd_cloud_workspace_bytes(B, K, H, W); }
+
+int actmi_op_rgbd_cloud(const actmi_rgbd_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "rgbd_cloud: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_rgbd_cloud(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int64_t n_per_sample, void* stream) {
     g_op_error.clear();
     const int rc = launch_depth_minmax_u16(depth, lohi_out, B, n_per_sample, S(stream));

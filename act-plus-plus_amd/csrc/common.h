@@ -200,6 +200,10 @@ int launch_pcd_head_bwd(const float* g, const float* w, const float* a, float* d
 int launch_pcd_wgrad0(const float* dz, const float* xyz, const float* rgb, const int* rows, float* dW, int R, int H, float* ws,
                       int64_t ws_floats, hipStream_t st);
 
+// ---- RGB-D frames -> ordered, downsampled point cloud (rgbd_cloud.hip; contract at actmi_rgbd_desc in actmi.h) ----------
+int64_t rgbd_cloud_workspace_bytes(int B, int K, int H, int W);
+int launch_rgbd_cloud(const actmi_rgbd_desc& a, hipStream_t st, std::string* err);
+
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------
 bool prof_enabled();
 void prof_begin(const char* name, double flops, double bytes, hipStream_t st);

@@ -95,7 +95,8 @@ class ACTPolicy:
 
     def __call__(self, qpos, image, actions=None, is_pad=None, vq_sample=None, depth_img=None, pointcloud=None):
         if self.use_pcd and pointcloud is None:
-            raise ValueError("a use_pcd policy needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]} (ragged clouds: + 'n': int32 [B])")
+            raise ValueError("a use_pcd policy needs pointcloud={'xyz': [B, P, 3], 'rgb': [B, P, 3]} (ragged clouds: + 'n': int32 [B]; "
+                             "or {'depth': uint16 frames} after set_rgbd_fusion)")
         pointcloud = pointcloud if self.use_pcd else None       # reference policy.py:301, 329
         if self.use_depth and depth_img is None:
             # (the reference would silently run RGB-only with a shorter sequence; the handle's token count is fixed at create)
@@ -118,6 +119,11 @@ class ACTPolicy:
             return loss_dict
         # inference: ImageNet normalisation (policy.py:268-272) is fused into the conv1 loader
         return self.model.forward_infer(qpos, image, vq_sample=vq_sample, pointcloud=pointcloud, depth_img=depth_img)
+
+    def set_rgbd_fusion(self, fusion):
+        """register an actmi.ops.RGBDFusion: ``pointcloud={"depth": uint16 frames}`` is then fused into the cloud on the device
+        (ACTEngine.set_rgbd_fusion); the reference builds it in a host-side node (jie_aloha_scripts/pcd_fusion.py)"""
+        self.model.set_rgbd_fusion(fusion)
 
     # ---- nn.Module-like surface used by imitate_episodes.py ---------------------------------------
     def cuda(self):

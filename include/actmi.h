@@ -542,6 +542,75 @@ int actmi_op_colmax(const float* x, int B, int P, int O, int64_t ld, float* out,
  * rows at or behind the count are never read, every argmax is below it; same grid, same split, same merge order */
 int actmi_op_colmax_n(const float* x, int B, int P, int O, int64_t ld, const int32_t* counts, float* out, int32_t* argmax, float* ws,
                       int64_t ws_floats, void* stream);
+/* ---- RGB-D frames -> the point cloud of a use_pcd policy, on the device (csrc/rgbd_cloud.hip).
+ * Replaces the host-side fusion node that builds the cloud in the reference (aloha_scripts/jie_aloha_scripts/pcd_fusion.py:186-243,
+ * 278-279): per depth camera deproject, transform camera -> base_link, crop to spatial_cutoff (both ends inclusive), draw a random
+ * subset of downsample_N points, concatenate the cameras.
+ *
+ * Per pixel (v, u) of fusion camera k of sample b, d = depth[b][k][v][u]: dropped when d == 0; otherwise, all in fp32 with one
+ * rounding per operation (no contraction),
+ *     z = d * depth_scale,  x = (u - cx) / fx * z,  y = (v - cy) / fy * z          (pinhole, no distortion)
+ *     p_i = ((T[4i] * x + T[4i+1] * y) + T[4i+2] * z) + T[4i+3],  i = 0, 1, 2       (T: 3x4 row-major, camera optical frame -> base)
+ * and the pixel SURVIVES when box[0] <= p_0 <= box[1], box[2] <= p_1 <= box[3], box[4] <= p_2 <= box[5].  Its colour is the three
+ * bytes image[b][cam_index[k]][v][u][0..2] in stored order as floats 0..255 (exact; what the PointNet branch is fed).
+ *
+ * Downsampling: with M survivors, camera k keeps all of them when M <= quota[k], else exactly the quota[k] survivors with the
+ * smallest key(seed, b, k, pixel), pixel = v * W + u.  key is a seeded bijection of [0, 2^m), m = max(1, ceil(log2(H * W))): no
+ * ties, no duplicates, and nothing depends on the launch geometry.  In 64-bit and 32-bit unsigned arithmetic:
+ *     mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *     s0 = mix(seed + 0x9E3779B97F4A7C15 * (b * 8 + k + 1)),  s1 = mix(s0 + 0x9E3779B97F4A7C15),  s2 = mix(s1 + 0x9E3779B97F4A7C15)
+ *     c0 = low32(s0),  a = (high32(s0), low32(s1), high32(s1), low32(s2)),  mask = 2^m - 1,  h = (m + 1) / 2
+ *     x = (pixel ^ c0) & mask;  then for (g, a_i) in zip((0x9E3779B1, 0x85EBCA6B, 0xC2B2AE35, 0x27D4EB2F), a):
+ *         x = (x * g) & mask;  x ^= x >> h;  x = (x + a_i) & mask;                                     key = x
+ * Every step is invertible modulo 2^m (an odd multiplier, a xor-shift, an addition), hence the bijection.
+ * (actmi.ops.rgbd_select_key is the same function in numpy).
+ *
+ * Outputs: xyz, rgb [B][P][3] f32 with P = sum(quota); n [B] int32; optional src_idx [B][P] int32 = k * H * W + pixel of every row
+ * (-1 at and behind n[b]); optional survivors [B][K] int32 = M before downsampling.  The rows of a sample ascend by (camera, pixel):
+ * camera 0's points first, no gap between cameras, and every row at or behind n[b] is zero -- the finite padding that
+ * actmi_set_pointcloud_n requires.  n[b] is the TRUE count and may be 0; that binding clamps it to 1, so a sample without a point
+ * is the single point (0, 0, 0) with colour (0, 0, 0).  The write is ordered (counts per 1024-pixel tile, a scan, then the write;
+ * integer atomics for counts and histograms only), so the outputs are bitwise repeatable from run to run.
+ *
+ * Everything the kernels read lives on the device -- `calib` and `seed` included, so a captured launch sees what a stream-ordered
+ * copy wrote into them since.  The op runs on one stream (five small launches), allocates nothing, never synchronises and reads
+ * no count on the host.  quota[] and cam_index[] of the descriptor are the HOST's copy of the block's values, used to validate the
+ * call (quota[k] >= 1 summing to P, 0 <= cam_index[k] < C); the kernels read the block and clamp what they find there to those
+ * ranges.  1 <= K <= 8, 2 <= H * W <= 2^20; depth and seed 8-byte aligned.  ws: actmi_op_rgbd_cloud_workspace_bytes(B, K, H, W)
+ * bytes of scratch (no state is kept in it between calls). */
+#define ACTMI_RGBD_MAX_CAMS 8
+typedef struct actmi_rgbd_cam {
+    int32_t cam_index;         /* which of the C colour frames is registered to this depth camera */
+    int32_t quota;             /* points kept at most */
+    float fx, fy, cx, cy;
+    float depth_scale;         /* metres per depth unit */
+    float T[12];               /* 3x4 row-major */
+    float reserved;
+} actmi_rgbd_cam;
+typedef struct actmi_rgbd_calib {              /* the DEVICE parameter block */
+    actmi_rgbd_cam cam[ACTMI_RGBD_MAX_CAMS];
+    float box[6];              /* xmin, xmax, ymin, ymax, zmin, zmax */
+    float reserved[2];
+} actmi_rgbd_calib;
+typedef struct actmi_rgbd_desc {
+    const uint16_t* depth;     /* [B][K][H][W] */
+    const uint8_t* image;      /* [B][C][H][W][3], the forward's own frame batch */
+    const actmi_rgbd_calib* calib;
+    const uint64_t* seed;      /* one device word */
+    float* xyz;
+    float* rgb;
+    int32_t* n;
+    int32_t* src_idx;          /* optional */
+    int32_t* survivors;        /* optional */
+    void* ws;
+    int64_t ws_bytes;
+    int32_t B, K, C, H, W, P;
+    int32_t quota[ACTMI_RGBD_MAX_CAMS];
+    int32_t cam_index[ACTMI_RGBD_MAX_CAMS];
+} actmi_rgbd_desc;
+/* bytes of workspace of a launch of that shape; negative when the shape is not supported */
+int64_t actmi_op_rgbd_cloud_workspace_bytes(int B, int K, int H, int W);
+int actmi_op_rgbd_cloud(const actmi_rgbd_desc* d, void* stream);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
