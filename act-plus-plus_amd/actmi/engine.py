@@ -168,8 +168,9 @@ class ACTEngine:
     def set_rgbd_fusion(self, fusion):
         """Register an ops.RGBDFusion (None: remove it).  From then on ``pointcloud={"depth": depth_u16}`` -- raw depth frames
         [B, K, H, W] or [B, K, 1, H, W] uint16 on the engine's device -- is accepted wherever ``pointcloud=`` is: the cloud is
-        built from them and from the call's own uint8 frame batch on the device (actmi_op_rgbd_cloud), on the caller's stream
-        right in front of the forward, and bound through actmi_set_pointcloud_n.  Ready-made clouds keep working as before."""
+        built from them and from the call's own uint8 frame batch on the device (actmi_op_rgbd_cloud, or
+        actmi_op_rgbd_cloud_fps for a fusion made with sampling="fps"), on the caller's stream right in front of the forward,
+        and bound through actmi_set_pointcloud_n.  Ready-made clouds keep working as before."""
         if fusion is not None:
             if not self.cfg.use_pcd:
                 raise ValueError("set_rgbd_fusion on an engine whose config has use_pcd=False")

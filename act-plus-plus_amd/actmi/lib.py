@@ -106,6 +106,14 @@ class RgbdDesc(C.Structure):
                [("quota", C.c_int32 * RGBD_MAX_CAMS), ("cam_index", C.c_int32 * RGBD_MAX_CAMS)]
 
 
+RGBD_FPS_MAX_POOL = 16384      # ACTMI_RGBD_FPS_MAX_POOL
+
+
+class RgbdFpsDesc(C.Structure):
+    # actmi_rgbd_fps_desc: the key draw's descriptor, the candidate pool per camera, the optional pick-order output
+    _fields_ = [("base", RgbdDesc), ("pool", C.c_int32), ("reserved", C.c_int32), ("order", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -196,6 +204,8 @@ def load():
         "actmi_op_colmax_n": ([vp, i32, i32, i32, C.c_int64, vp, vp, vp, vp, C.c_int64, vp], i32),
         "actmi_op_rgbd_cloud_workspace_bytes": ([i32, i32, i32, i32], C.c_int64),
         "actmi_op_rgbd_cloud": ([C.POINTER(RgbdDesc), vp], i32),
+        "actmi_op_rgbd_cloud_fps_workspace_bytes": ([i32, i32, i32, i32, i32], C.c_int64),
+        "actmi_op_rgbd_cloud_fps": ([C.POINTER(RgbdFpsDesc), vp], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

@@ -868,6 +868,45 @@ def rgbd_select_key(seed, b, k, pixel, H, W):
     return x.astype(np.uint32)
 
 
+def rgbd_fps_select(xyz_f32, key, quota, pool):
+    """Which survivors of one camera actmi_op_rgbd_cloud_fps keeps, in numpy: the definition at actmi_rgbd_fps_desc in actmi.h,
+    stated once more -- the oracle of the device op, not a fallback for it.
+
+    xyz_f32 [M, 3]: the survivors' coordinates in pixel order (the fp32 values of the device); key [M]: their selection keys
+    (rgbd_select_key).  -> (kept, sequence): the kept indices into the M survivors in ascending order, and the same indices in
+    the order they were picked.  M <= quota: every survivor, picked in pixel order.  Otherwise the pool is every survivor
+    (M <= pool) or the `pool` smallest keys, in pixel order; the start is the pool's smallest key; then `quota - 1` times: the
+    picked point's distance becomes -1 for good, every other dist = min(dist, ((dx * dx) + (dy * dy)) + (dz * dz)) in float32,
+    and the next pick is the largest dist, the lowest index among equals."""
+    import numpy as np
+    p = np.ascontiguousarray(xyz_f32, dtype=np.float32).reshape(-1, 3)
+    key = np.asarray(key).reshape(-1)
+    M, quota, pool = len(p), int(quota), int(pool)
+    if key.shape != (M,) or quota < 1 or pool < quota:
+        raise ValueError(f"rgbd_fps_select: {M} points, {key.shape} keys, quota {quota}, pool {pool}: needs a key per point and "
+                         f"1 <= quota <= pool")
+    if M <= quota:
+        every = np.arange(M, dtype=np.int64)
+        return every, every.copy()
+    members = np.arange(M, dtype=np.int64) if M <= pool else np.sort(np.argsort(key, kind="stable")[:pool])
+    px, py, pz = (np.ascontiguousarray(p[members, i]) for i in range(3))
+    dist = np.full(len(members), np.inf, dtype=np.float32)
+    seq = np.empty(quota, dtype=np.int64)
+    s = int(np.argmin(key[members]))
+    minus_one = np.float32(-1.0)
+    with np.errstate(over="ignore"):
+        for it in range(quota):
+            seq[it] = s
+            dist[s] = minus_one
+            if it + 1 == quota:
+                break
+            dx, dy, dz = px - px[s], py - py[s], pz - pz[s]
+            np.minimum(dist, ((dx * dx) + (dy * dy)) + (dz * dz), out=dist)      # float32 throughout; a picked point stays at -1
+            s = int(np.argmax(dist))                                            # the first maximum: the lowest index among equals
+    picked = members[seq]
+    return np.sort(picked), picked
+
+
 class RGBDFusion:
     """Builds the cloud of a use_pcd policy from raw depth frames on the device (actmi_op_rgbd_cloud), in place of the reference's
     host-side fusion node (aloha_scripts/jie_aloha_scripts/pcd_fusion.py:186-243, 278-279).  Owns the device parameter block, the
@@ -879,12 +918,23 @@ class RGBDFusion:
     base; box = (xmin, xmax, ymin, ymax, zmin, zmax), ends included; quota [K] >= 1: points kept per camera at most, P =
     sum(quota) rows per sample; max_batch sizes the buffers (default: the engine's).
 
+    sampling: which survivors a camera keeps when it has more than its quota.  "key" (default): the quota smallest values of the
+    seeded key (actmi_op_rgbd_cloud; the reference's np.random.choice branch).  "fps": farthest-point sampling
+    (actmi_op_rgbd_cloud_fps; what the reference's node runs under --use_fps), over the fps_pool smallest keys of the camera,
+    started at the smallest; fps_pool defaults to min(ACTMI_RGBD_FPS_MAX_POOL, 4 * max(quota)); ``order`` [max_batch, P] int32
+    then holds the iteration at which every row was picked (-1 behind n[b]).  rgbd_fps_select is the same selection in numpy.
+
     fuse(image_u8, depth_u16, B) -> {"xyz", "rgb": [B, P, 3] f32, "n": [B] int32}: views of the fusion's own buffers, valid until
     the next fuse.  Everything is validated on the host, before any device call (ValueError)."""
 
     def __init__(self, engine_or_device, K, H, W, cam_index, intrinsics, depth_scale, extrinsics, box, quota, max_batch=None,
-                 num_cams=None, seed=0):
+                 num_cams=None, seed=0, sampling="key", fps_pool=None):
         import numpy as np
+        if sampling not in ("key", "fps"):
+            raise ValueError(f"RGBDFusion: sampling must be 'key' or 'fps', got {sampling!r}")
+        if sampling == "key" and fps_pool is not None:
+            raise ValueError("RGBDFusion: fps_pool given with sampling='key' (the pool belongs to sampling='fps')")
+        self.sampling = sampling
         eng = engine_or_device if hasattr(engine_or_device, "max_points") else None
         self.device = torch.device(eng.device if eng is not None else engine_or_device)
         if self.device.type != "cuda":
@@ -917,6 +967,16 @@ class RGBDFusion:
         if q.shape != (K,) or q.dtype.kind not in "iu" or q.min() < 1:
             raise ValueError(f"RGBDFusion: quota must hold {K} integers >= 1, got {q.dtype} {q.shape} {q.tolist() if q.size <= 8 else ''}")
         self.P = int(q.sum())
+        self.fps_pool = None
+        if sampling == "fps":
+            if fps_pool is None:
+                fps_pool = min(L.RGBD_FPS_MAX_POOL, 4 * int(q.max()))
+            if isinstance(fps_pool, bool) or not isinstance(fps_pool, (int, np.integer)):
+                raise ValueError(f"RGBDFusion: fps_pool must be an integer, got {fps_pool!r}")
+            if not int(q.max()) <= fps_pool <= L.RGBD_FPS_MAX_POOL:
+                raise ValueError(f"RGBDFusion: fps_pool = {fps_pool}: needs max(quota) = {int(q.max())} <= fps_pool <= "
+                                 f"{L.RGBD_FPS_MAX_POOL} (ACTMI_RGBD_FPS_MAX_POOL)")
+            self.fps_pool = int(fps_pool)
         if eng is not None and self.P > eng.max_points:
             raise ValueError(f"RGBDFusion: sum(quota) = {self.P} points per sample > the engine's max_points {eng.max_points}")
         intr = np.asarray(intrinsics, dtype=np.float64)
@@ -955,7 +1015,10 @@ class RGBDFusion:
 
     def _alloc(self):
         dev, MB, P, K = self.device, self.max_batch, self.P, self.K
-        nbytes = int(L.load().actmi_op_rgbd_cloud_workspace_bytes(MB, K, self.H, self.W))
+        if self.sampling == "fps":
+            nbytes = int(L.load().actmi_op_rgbd_cloud_fps_workspace_bytes(MB, K, self.H, self.W, self.fps_pool))
+        else:
+            nbytes = int(L.load().actmi_op_rgbd_cloud_workspace_bytes(MB, K, self.H, self.W))
         if nbytes < 0:
             raise ValueError(f"RGBDFusion: shape B = {MB}, K = {K}, {self.H} x {self.W} not supported by actmi_op_rgbd_cloud")
         self._ws = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=dev)
@@ -966,6 +1029,7 @@ class RGBDFusion:
         self.n = torch.zeros((MB,), dtype=torch.int32, device=dev)
         self.src_idx = torch.full((MB, P), -1, dtype=torch.int32, device=dev)
         self.survivors = torch.zeros((MB, K), dtype=torch.int32, device=dev)
+        self.order = torch.full((MB, P), -1, dtype=torch.int32, device=dev) if self.sampling == "fps" else None
         self._push_calib()
         self.set_seed(self._seed_host)
 
@@ -1035,8 +1099,13 @@ class RGBDFusion:
         for k in range(self.K):
             d.quota[k], d.cam_index[k] = self.quota[k], self.cam_index[k]
         with torch.cuda.device(self.device):
-            L.check(L.load().actmi_op_rgbd_cloud(C.byref(d), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), None,
-                    "op_rgbd_cloud")
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            if self.sampling == "fps":
+                f = L.RgbdFpsDesc()
+                f.base, f.pool, f.order = d, self.fps_pool, self.order.data_ptr()
+                L.check(L.load().actmi_op_rgbd_cloud_fps(C.byref(f), st), None, "op_rgbd_cloud_fps")
+            else:
+                L.check(L.load().actmi_op_rgbd_cloud(C.byref(d), st), None, "op_rgbd_cloud")
         return self.outputs(B)
 
 

@@ -396,6 +396,17 @@ int actmi_op_rgbd_cloud(const actmi_rgbd_desc* d, void* stream) {
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
 }
 
+int64_t actmi_op_rgbd_cloud_fps_workspace_bytes(int B, int K, int H, int W, int pool) {
+    return rgbd_cloud_fps_workspace_bytes(B, K, H, W, pool);
+}
+
+int actmi_op_rgbd_cloud_fps(const actmi_rgbd_fps_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "rgbd_cloud_fps: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_rgbd_cloud_fps(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int64_t n_per_sample, void* stream) {
     g_op_error.clear();
     const int rc = launch_depth_minmax_u16(depth, lohi_out, B, n_per_sample, S(stream));

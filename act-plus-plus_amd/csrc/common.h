@@ -203,6 +203,9 @@ int launch_pcd_wgrad0(const float* dz, const float* xyz, const float* rgb, const
 // ---- RGB-D frames -> ordered, downsampled point cloud (rgbd_cloud.hip; contract at actmi_rgbd_desc in actmi.h) ----------
 int64_t rgbd_cloud_workspace_bytes(int B, int K, int H, int W);
 int launch_rgbd_cloud(const actmi_rgbd_desc& a, hipStream_t st, std::string* err);
+// the same cloud with farthest-point sampling where a camera has more survivors than its quota (actmi_rgbd_fps_desc)
+int64_t rgbd_cloud_fps_workspace_bytes(int B, int K, int H, int W, int pool);
+int launch_rgbd_cloud_fps(const actmi_rgbd_fps_desc& a, hipStream_t st, std::string* err);
 
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------
 bool prof_enabled();

@@ -32,12 +32,17 @@ constexpr int RC_HI_MAX = 8;                                                // h
 
 struct RcShape {
     int B, K, C, H, W, P, HW, NT, m, hi_bits, lo_bits;
+    int pool;                  // 0: the key draw (a camera keeps its quota); > 0: the passes select the candidate pool of the FPS op
 };
 
 // workspace (int32 words): hist [B][K][256] | cand [B][K][2^lo_bits] | tile_cnt, tile_lt, tile_off [B][K][NT] | bound [B][K]
+// the FPS op adds: pool_cnt, surv_m [B][K] | stage [B][K][pool] (x, y, z, 2^m - 1 - key: 16 bytes) | pixel, pick [B][K][pool]
 struct RcWs {
     unsigned *hist, *cand, *tile_cnt, *tile_lt, *tile_off, *bound;
     int64_t zero_words, words;
+    unsigned *pool_cnt, *surv_m;
+    float4* stage;
+    int *pixel, *pick;
 };
 
 inline int rc_log2_ceil(int64_t n) { int m = 0; while (((int64_t)1 << m) < n) ++m; return m < 1 ? 1 : m; }
@@ -54,6 +59,16 @@ inline RcWs rc_carve(void* ws, const RcShape& s) {
     w.tile_off = p; p += bk * s.NT;
     w.bound = p; p += bk;
     w.words = p - static_cast<unsigned*>(ws);
+    w.pool_cnt = w.surv_m = nullptr; w.stage = nullptr; w.pixel = w.pick = nullptr;
+    if (s.pool > 0) {
+        w.pool_cnt = p; p += bk;
+        w.surv_m = p; p += bk;
+        p += (4 - (p - static_cast<unsigned*>(ws)) % 4) % 4;           // stage entries are read as 16-byte words
+        w.stage = reinterpret_cast<float4*>(p); p += bk * s.pool * 4;
+        w.pixel = reinterpret_cast<int*>(p); p += bk * s.pool;
+        w.pick = reinterpret_cast<int*>(p); p += bk * s.pool;
+        w.words = p - static_cast<unsigned*>(ws);
+    }
     return w;
 }
 
@@ -113,6 +128,9 @@ struct RcCam {
         return px >= box[0] && px <= box[1] && py >= box[2] && py <= box[3] && pz >= box[4] && pz <= box[5];
     }
 };
+
+// how many survivors the count / select / scan passes single out per camera: its quota, or the candidate pool of the FPS op
+__device__ __forceinline__ int rc_keep(const RcCam& cam, const RcShape& s) { return s.pool > 0 ? s.pool : cam.quota; }
 
 // the four pixels of thread t in the tile: pixel index pix0 + i, raw depth d[i] (0 behind the plane's end)
 __device__ __forceinline__ void rc_load4(const uint16_t* __restrict__ plane, int pix0, int HW, bool aligned8, unsigned d[RC_PIX]) {
@@ -202,8 +220,9 @@ __global__ __launch_bounds__(RC_BLOCK) void rgbd_select_kernel(const uint16_t* _
     const int64_t bk = (int64_t)b * s.K + k;
     const RcCam cam(cal, k, s.C, s.P);
     unsigned M, b1, below;
-    rc_find_bin(w.hist + bk * 256, cam.quota, s_scan, s_pick, M, b1, below);
-    if (M <= (unsigned)cam.quota) return;              // every survivor is kept: the scan pass uses tile_cnt (uniform exit)
+    const int keep = rc_keep(cam, s);
+    rc_find_bin(w.hist + bk * 256, keep, s_scan, s_pick, M, b1, below);
+    if (M <= (unsigned)keep) return;              // every survivor is kept: the scan pass uses tile_cnt (uniform exit)
     const RcKey key(*seed, b, k, s.m);
     const uint16_t* plane = depth + bk * s.HW;
     const int pix0 = tile * RC_TILE + t * RC_PIX;
@@ -236,13 +255,14 @@ __global__ __launch_bounds__(RC_BLOCK) void rgbd_scan_kernel(const actmi_rgbd_ca
         const int64_t bk = (int64_t)b * s.K + k;
         const RcCam cam(cal, k, s.C, s.P);
         unsigned M, b1, below;
-        rc_find_bin(w.hist + bk * 256, cam.quota, s_scan, s_pick, M, b1, below);
-        const bool all = M <= (unsigned)cam.quota;
+        const int keep = rc_keep(cam, s);
+        rc_find_bin(w.hist + bk * 256, keep, s_scan, s_pick, M, b1, below);
+        const bool all = M <= (unsigned)keep;
         unsigned* cnt = (all ? w.tile_cnt : w.tile_lt) + bk * s.NT;
         unsigned bound = 0xffffffffu;
         if (!all) {
             // the r smallest candidates of bin b1, in ascending order of their low bits
-            const unsigned r = (unsigned)cam.quota - below;
+            const unsigned r = (unsigned)keep - below;
             const unsigned* cand = w.cand + (bk << s.lo_bits);
             unsigned seen = 0;
             __syncthreads();
@@ -277,9 +297,13 @@ __global__ __launch_bounds__(RC_BLOCK) void rgbd_scan_kernel(const actmi_rgbd_ca
             if (tile < s.NT) w.tile_off[bk * s.NT + tile] = run + ex;
             run += total;
         }
-        base = run;
+        if (s.pool > 0) {                                  // the FPS op stages every camera's pool on its own: offsets from 0
+            if (t == 0) { w.pool_cnt[bk] = run; w.surv_m[bk] = M; }
+        } else {
+            base = run;
+        }
     }
-    if (t == 0) n_out[b] = (int)(base > (unsigned)s.P ? (unsigned)s.P : base);
+    if (n_out && t == 0) n_out[b] = (int)(base > (unsigned)s.P ? (unsigned)s.P : base);
 }
 
 __global__ __launch_bounds__(RC_BLOCK) void rgbd_write_kernel(const uint16_t* __restrict__ depth, const uint8_t* __restrict__ image,
@@ -337,6 +361,278 @@ __global__ __launch_bounds__(RC_BLOCK) void rgbd_write_kernel(const uint16_t* __
     }
 }
 
+// ---- farthest-point sampling (actmi_op_rgbd_cloud_fps; definition in include/actmi.h) ---------------------------------------------
+// The passes above run with `pool` in place of the quota and leave, per camera, the key bound of its candidate pool and the pool's
+// per-tile offsets.  rgbd_stage_kernel writes the pool in pixel order into the workspace (x, y, z and 2^m - 1 - key: 16 bytes a
+// point; the pixels beside them), and ONE workgroup of 1024 threads per (sample, camera) does the rest on chip: thread t holds the
+// PT = pool / 1024 (rounded up to a power of two, at least 2) points j = t * PT + i and their running distances in registers.  An
+// iteration is a distance update, the thread's own maximum, a wave maximum by DPP, one LDS word per wave and a barrier, the
+// maximum of the 16 words in every wave, then the winning wave alone finds its point and publishes it behind a second barrier.
+// Distances are compared as the int32 bits of non-negative floats (a picked or absent point is -1: below them all); the tie rule
+// "lowest j" needs no index in the compare because j ascends with (wave, lane, i) and every level takes the first maximum.
+constexpr int FP_BLOCK = 1024, FP_WAVES = FP_BLOCK / 64;
+constexpr int FP_NONE = (int)0x80000000;
+
+template <int CTRL>
+__device__ __forceinline__ int fp_dpp_max(int v) {
+    const int o = __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false);
+    return o > v ? o : v;
+}
+// the maximum over the 64 lanes of the wave, uniform.  Every lane must be active.
+__device__ __forceinline__ int fp_wave_max(int v) {
+    v = fp_dpp_max<0xB1>(v);                           // quad_perm [1, 0, 3, 2]
+    v = fp_dpp_max<0x4E>(v);                           // quad_perm [2, 3, 0, 1]
+    v = fp_dpp_max<0x141>(v);                          // row_half_mirror
+    v = fp_dpp_max<0x140>(v);                          // row_mirror: every lane holds the maximum of its row of 16
+    const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16), c = __builtin_amdgcn_readlane(v, 32),
+              d = __builtin_amdgcn_readlane(v, 48);
+    const int ab = a > b ? a : b, cd = c > d ? c : d;
+    return ab > cd ? ab : cd;
+}
+
+// Two points share a register pair, so that the distance update is packed fp32 arithmetic (v_pk_add_f32 / v_pk_mul_f32) on the
+// registers the points live in: left to itself the compiler vectorises the update too, but keeps a second, scalar copy of every
+// coordinate for the winner's lookup, and 16 points a thread then spill.
+typedef float fp_v2 __attribute__((ext_vector_type(2)));
+
+// the first maximum over the workgroup of the values val[] of every thread, compared as int32 bits, in (wave, lane, i) order =
+// ascending j, with its index and point.  The waves publish their maxima; behind the barrier every wave reduces the 16 of them, and
+// the ONE wave that holds the first maximum has its first such lane look up which of its points it is and publish the point behind
+// a second barrier.  (One barrier a call -- every wave's first lane looks its point up ahead of it, two alternating sets of
+// records -- was measured as well: the lookup is five selects a point, and with 16 waves doing it the call took up to 1.5 times
+// as long)  s_val is written ahead of the first barrier by waves that have passed the previous call's second one,
+// which every reader of s_val reaches only with its value in hand; s_rec is written behind the first barrier, which every reader
+// of the previous call's s_rec has passed.  Uniform result.
+template <int PH>
+__device__ __forceinline__ void fp_block_argmax(const fp_v2 (&val)[PH], const fp_v2 (&x)[PH], const fp_v2 (&y)[PH], const fp_v2 (&z)[PH],
+                                                int j0, int* s_val, float4* s_rec, int& win, int& wj, float& wx, float& wy, float& wz) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int best = FP_NONE;
+#pragma unroll
+    for (int h = 0; h < PH; ++h) {
+        const int a = __float_as_int(val[h].x), c = __float_as_int(val[h].y);
+        best = a > best ? a : best;
+        best = c > best ? c : best;
+    }
+    const int wm = fp_wave_max(best);
+    if (lane == 0) s_val[wave] = wm;
+    __syncthreads();
+    const int v = lane < FP_WAVES ? s_val[lane] : FP_NONE;
+    win = fp_wave_max(v);
+    const int ww = (__ffsll(__ballot(v == win)) - 1) & (FP_WAVES - 1);
+    if (wave == ww) {                                                        // (wave-uniform)
+        const unsigned long long mine = __ballot(best == win);
+        if (lane == __ffsll(mine) - 1) {
+            int bi = 0;
+            float bx = 0.f, by = 0.f, bz = 0.f;
+#pragma unroll
+            for (int h = PH - 1; h >= 0; --h) {
+                const bool e1 = __float_as_int(val[h].y) == win;
+                bi = e1 ? 2 * h + 1 : bi; bx = e1 ? x[h].y : bx; by = e1 ? y[h].y : by; bz = e1 ? z[h].y : bz;
+                const bool e0 = __float_as_int(val[h].x) == win;
+                bi = e0 ? 2 * h : bi; bx = e0 ? x[h].x : bx; by = e0 ? y[h].x : by; bz = e0 ? z[h].x : bz;
+            }
+            s_rec[0] = make_float4(bx, by, bz, __int_as_float(j0 + bi));
+        }
+    }
+    __syncthreads();
+    const float4 e = s_rec[0];
+    wx = e.x; wy = e.y; wz = e.z; wj = __float_as_int(e.w);
+}
+
+// the squared distance of the definition, of two points at once: ((dx * dx) + (dy * dy)) + (dz * dz), one rounding per operation
+__device__ __forceinline__ fp_v2 fp_dist2(fp_v2 x, fp_v2 y, fp_v2 z, float sx, float sy, float sz) {
+#pragma clang fp contract(off)
+    const fp_v2 dx = x - sx, dy = y - sy, dz = z - sz;
+    return ((dx * dx) + (dy * dy)) + (dz * dz);
+}
+
+// exclusive prefix of v over the 1024 threads of the block, and the block total; s: FP_WAVES words of LDS
+__device__ __forceinline__ unsigned fp_block_scan(unsigned v, unsigned* s, unsigned& total) {
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned up = (unsigned)__shfl_up((int)inc, o);
+        if (lane >= o) inc += up;
+    }
+    __syncthreads();
+    if (lane == 63) s[w] = inc;
+    __syncthreads();
+    unsigned before = 0, all = 0;
+#pragma unroll
+    for (int i = 0; i < FP_WAVES; ++i) { const unsigned x = s[i]; all += x; if (i < w) before += x; }
+    total = all;
+    return before + inc - v;
+}
+
+// the pool of every camera in pixel order: stage[b][k][j] = (x, y, z, 2^m - 1 - key) and pixel[b][k][j] for j < pool_cnt[b][k]
+__global__ __launch_bounds__(RC_BLOCK) void rgbd_stage_kernel(const uint16_t* __restrict__ depth, const actmi_rgbd_calib* __restrict__ cal,
+                                                             const uint64_t* __restrict__ seed, RcShape s, RcWs w) {
+    __shared__ unsigned s_scan[RC_BLOCK / 64];
+    const int tile = blockIdx.x, k = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+    const int64_t bk = (int64_t)b * s.K + k;
+    if (w.tile_cnt[bk * s.NT + tile] == 0u) return;    // no survivor in this tile (uniform)
+    const RcCam cam(cal, k, s.C, s.P);
+    const RcKey key(*seed, b, k, s.m);
+    const unsigned bound = w.bound[bk];
+    const uint16_t* plane = depth + bk * s.HW;
+    const int pix0 = tile * RC_TILE + t * RC_PIX;
+    unsigned d[RC_PIX];
+    rc_load4(plane, pix0, s.HW, ((bk * s.HW) & 3) == 0, d);
+    float px[RC_PIX], py[RC_PIX], pz[RC_PIX];
+    unsigned kv[RC_PIX];
+    unsigned keep = 0, cnt = 0;
+#pragma unroll
+    for (int i = 0; i < RC_PIX; ++i) {
+        if (!d[i]) continue;
+        const int pix = pix0 + i;
+        kv[i] = key((unsigned)pix);
+        if (cam.point(d[i], pix / s.W, pix % s.W, px[i], py[i], pz[i]) && kv[i] < bound) { keep |= 1u << i; ++cnt; }
+    }
+    unsigned total;
+    unsigned j = w.tile_off[bk * s.NT + tile] + rc_block_scan(cnt, s_scan, total);
+    float4* stage = w.stage + bk * s.pool;
+    int* pixel = w.pixel + bk * s.pool;
+#pragma unroll
+    for (int i = 0; i < RC_PIX; ++i) {
+        if (!(keep & (1u << i))) continue;
+        if (j < (unsigned)s.pool) {
+            // the fourth word: 2^m - 1 - key as bits, so that the smallest key is the largest word (the start of the selection)
+            stage[j] = make_float4(px[i], py[i], pz[i], __int_as_float((int)(key.mask - kv[i])));
+            pixel[j] = pix0 + i;
+        }
+        ++j;
+    }
+}
+
+// one workgroup per (sample, camera): the selection over the staged pool, then the camera's rows and a share of the padding
+template <int PT>
+__global__ __launch_bounds__(FP_BLOCK) void rgbd_fps_kernel(const uint8_t* __restrict__ image, const actmi_rgbd_calib* __restrict__ cal,
+                                                            RcShape s, RcWs w, float* __restrict__ xyz,
+                                                            float* __restrict__ rgb, int* __restrict__ n_out, int* __restrict__ src_idx,
+                                                            int* __restrict__ order) {
+    __shared__ int s_val[FP_WAVES];
+    __shared__ float4 s_rec[1];
+    __shared__ unsigned s_scan[FP_WAVES];
+    const int k = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const int64_t bk = (int64_t)b * s.K + k;
+    const int64_t row0 = (int64_t)b * s.P;
+    const RcCam cam(cal, k, s.C, s.P);
+    // the device block's quota, held to what the host validated (quota <= pool)
+    const int q = cam.quota < s.pool ? cam.quota : s.pool;
+    // rows of the cameras in front, and n[b]
+    unsigned base = 0, all_rows = 0;
+    for (int kk = 0; kk < s.K; ++kk) {
+        int qq = cal->cam[kk].quota;
+        qq = qq < 1 ? 1 : (qq > s.P ? s.P : qq);
+        qq = qq < s.pool ? qq : s.pool;
+        const unsigned mm = w.surv_m[(int64_t)b * s.K + kk];
+        const unsigned c = mm < (unsigned)qq ? mm : (unsigned)qq;
+        if (kk < k) base += c;
+        all_rows += c;
+    }
+    const int nb = (int)(all_rows > (unsigned)s.P ? (unsigned)s.P : all_rows);
+    if (k == 0 && t == 0) n_out[b] = nb;
+    for (int r = nb + k * FP_BLOCK + t; r < s.P; r += s.K * FP_BLOCK) {    // a share of the padding
+        float* a = xyz + (row0 + r) * 3;
+        float* c = rgb + (row0 + r) * 3;
+        a[0] = a[1] = a[2] = 0.f;
+        c[0] = c[1] = c[2] = 0.f;
+        if (src_idx) src_idx[row0 + r] = -1;
+        if (order) order[row0 + r] = -1;
+    }
+    const unsigned M = w.surv_m[bk];
+    const unsigned pc = w.pool_cnt[bk];
+    const int Mp = (int)(pc < (unsigned)s.pool ? pc : (unsigned)s.pool);
+    if (Mp == 0) return;                               // (uniform)
+    const float4* stage = w.stage + bk * s.pool;
+    int* pick = w.pick + bk * s.pool;
+    constexpr int PH = PT / 2;
+    fp_v2 x[PH], y[PH], z[PH], dist[PH];
+    const int j0 = t * PT;
+    // the points of this thread: 2h and 2h + 1 in pair h.  Until the start is found dist[] holds the staged word 2^m - 1 - key of
+    // every point, as bits: the start is the pool member with the smallest key (keys are distinct and below 2^20), found by the
+    // same argmax as every later pick.  Branch-free: an absent point reads the pool's last member, is -1 and takes part in nothing.
+#pragma unroll
+    for (int h = 0; h < PH; ++h) {
+        const bool have0 = j0 + 2 * h < Mp, have1 = j0 + 2 * h + 1 < Mp;
+        const float4 e0 = stage[have0 ? j0 + 2 * h : Mp - 1], e1 = stage[have1 ? j0 + 2 * h + 1 : Mp - 1];
+        x[h].x = e0.x; y[h].x = e0.y; z[h].x = e0.z; dist[h].x = have0 ? e0.w : -1.f;
+        x[h].y = e1.x; y[h].y = e1.y; z[h].y = e1.z; dist[h].y = have1 ? e1.w : -1.f;
+    }
+    const bool run = M > (unsigned)q;                  // otherwise every survivor is kept (then Mp = M <= q); uniform
+    if (run) {
+        int win, cur;
+        float sx, sy, sz;
+        fp_block_argmax<PH>(dist, x, y, z, j0, s_val, s_rec, win, cur, sx, sy, sz);
+#pragma unroll
+        for (int h = 0; h < PH; ++h) {
+            dist[h].x = j0 + 2 * h < Mp ? __builtin_inff() : -1.f;
+            dist[h].y = j0 + 2 * h + 1 < Mp ? __builtin_inff() : -1.f;
+        }
+        // at most pool picks whatever the device block says: q <= pool
+#pragma unroll 1
+        for (int it = 0; it < s.pool; ++it) {
+            const int rel = cur - j0;                  // the owner of the pick marks it and records its turn
+            if (rel >= 0 && rel < PT) {                // (one thread: 15 of the 16 waves branch around this)
+#pragma unroll
+                for (int h = 0; h < PH; ++h) {
+                    dist[h].x = rel == 2 * h ? -1.f : dist[h].x;
+                    dist[h].y = rel == 2 * h + 1 ? -1.f : dist[h].y;
+                }
+                pick[cur] = it;
+            }
+            if (it + 1 >= q) break;                    // (uniform)
+#pragma unroll
+            for (int h = 0; h < PH; ++h) {
+                const fp_v2 dd = fp_dist2(x[h], y[h], z[h], sx, sy, sz);
+                // min(dist, dd) on the int32 bits, one instruction: dd is a sum of squares, +0 or above, where bits order as
+                // values, and a picked or absent point's -1 is a negative word and stays
+                const int mx = __float_as_int(dist[h].x) < __float_as_int(dd.x) ? __float_as_int(dist[h].x) : __float_as_int(dd.x);
+                const int my = __float_as_int(dist[h].y) < __float_as_int(dd.y) ? __float_as_int(dist[h].y) : __float_as_int(dd.y);
+                dist[h].x = __int_as_float(mx);
+                dist[h].y = __int_as_float(my);
+            }
+            // non-negative floats order as their bits, and -1 is below them all
+            fp_block_argmax<PH>(dist, x, y, z, j0, s_val, s_rec, win, cur, sx, sy, sz);
+            if (win < 0 || cur < 0 || cur >= Mp) break;                      // nothing left to pick (uniform; not with a valid block)
+        }
+    }
+    // the rows: kept pool members in pool order = pixel order.  The thread's first index goes through an empty asm so that the
+    // compiler derives the indices below from it here, and does not carry PT of them in registers across the selection.
+    int je = t * PT;
+    asm volatile("" : "+v"(je));
+    unsigned cnt = 0;
+#pragma unroll
+    for (int i = 0; i < PT; ++i) cnt += (je + i < Mp && (!run || dist[i / 2][i & 1] < 0.f)) ? 1u : 0u;
+    unsigned total;
+    unsigned row = base + fp_block_scan(cnt, s_scan, total);
+    const uint8_t* frame = image + ((int64_t)b * s.C + cam.cam) * s.HW * 3;
+#pragma unroll
+    for (int i = 0; i < PT; ++i) {
+        if (!(je + i < Mp && (!run || dist[i / 2][i & 1] < 0.f))) continue;
+        if (row < (unsigned)s.P) {
+            int pix = w.pixel[bk * s.pool + je + i];
+            pix = pix < 0 ? 0 : (pix >= s.HW ? s.HW - 1 : pix);
+            float* a = xyz + (row0 + row) * 3;
+            float* c = rgb + (row0 + row) * 3;
+            const uint8_t* p = frame + (int64_t)pix * 3;
+            a[0] = x[i / 2][i & 1]; a[1] = y[i / 2][i & 1]; a[2] = z[i / 2][i & 1];
+            c[0] = (float)p[0]; c[1] = (float)p[1]; c[2] = (float)p[2];
+            if (src_idx) src_idx[row0 + row] = k * s.HW + pix;
+            if (order) order[row0 + row] = run ? pick[je + i] : je + i;
+        }
+        ++row;
+    }
+}
+
+template <int PT>
+void fp_launch(const actmi_rgbd_desc& a, int* order, const RcShape& s, const RcWs& w, hipStream_t st) {
+    hipLaunchKernelGGL(rgbd_fps_kernel<PT>, dim3((unsigned)s.K, (unsigned)s.B), dim3(FP_BLOCK), 0, st, a.image, a.calib, s, w, a.xyz,
+                       a.rgb, a.n, a.src_idx, order);
+}
+
 int rc_shape(int B, int K, int C, int H, int W, int P, RcShape* s, std::string* err) {
     auto fail = [&](const char* m) { if (err) *err = m; return -2; };
     if (K < 1 || K > ACTMI_RGBD_MAX_CAMS) return fail("rgbd_cloud: K outside 1..8");
@@ -351,6 +647,27 @@ int rc_shape(int B, int K, int C, int H, int W, int P, RcShape* s, std::string* 
     s->m = rc_log2_ceil(HW);
     s->hi_bits = (s->m + 1) / 2 < RC_HI_MAX ? (s->m + 1) / 2 : RC_HI_MAX;
     s->lo_bits = s->m - s->hi_bits;
+    s->pool = 0;
+    return 0;
+}
+
+// everything of a descriptor but its workspace: the shape, the pointers and the host's copy of quota / cam_index
+int rc_validate(const actmi_rgbd_desc& a, RcShape* s, std::string* err) {
+    auto fail = [&](const char* m) { if (err) *err = m; return -2; };
+    const int rc = rc_shape(a.B, a.K, a.C, a.H, a.W, a.P, s, err);
+    if (rc != 0) return rc;
+    if (!a.depth || !a.image || !a.calib || !a.seed || !a.xyz || !a.rgb || !a.n || !a.ws) return fail("rgbd_cloud: null pointer");
+    if ((reinterpret_cast<uintptr_t>(a.depth) & 7) || (reinterpret_cast<uintptr_t>(a.calib) & 3) || (reinterpret_cast<uintptr_t>(a.seed) & 7) ||
+        (reinterpret_cast<uintptr_t>(a.xyz) & 3) || (reinterpret_cast<uintptr_t>(a.rgb) & 3) || (reinterpret_cast<uintptr_t>(a.n) & 3) ||
+        (reinterpret_cast<uintptr_t>(a.ws) & 3) || (reinterpret_cast<uintptr_t>(a.src_idx) & 3) || (reinterpret_cast<uintptr_t>(a.survivors) & 3))
+        return fail("rgbd_cloud: misaligned pointer (depth and seed 8 bytes, the others 4)");
+    int64_t sum = 0;
+    for (int k = 0; k < a.K; ++k) {
+        if (a.quota[k] < 1) return fail("rgbd_cloud: quota[k] < 1");
+        if (a.cam_index[k] < 0 || a.cam_index[k] >= a.C) return fail("rgbd_cloud: cam_index[k] outside 0..C-1");
+        sum += a.quota[k];
+    }
+    if (sum != a.P) return fail("rgbd_cloud: the quotas do not sum to P");
     return 0;
 }
 
@@ -365,20 +682,8 @@ int64_t rgbd_cloud_workspace_bytes(int B, int K, int H, int W) {
 int launch_rgbd_cloud(const actmi_rgbd_desc& a, hipStream_t st, std::string* err) {
     auto fail = [&](const char* m) { if (err) *err = m; return -2; };
     RcShape s;
-    const int rc = rc_shape(a.B, a.K, a.C, a.H, a.W, a.P, &s, err);
+    const int rc = rc_validate(a, &s, err);
     if (rc != 0) return rc;
-    if (!a.depth || !a.image || !a.calib || !a.seed || !a.xyz || !a.rgb || !a.n || !a.ws) return fail("rgbd_cloud: null pointer");
-    if ((reinterpret_cast<uintptr_t>(a.depth) & 7) || (reinterpret_cast<uintptr_t>(a.calib) & 3) || (reinterpret_cast<uintptr_t>(a.seed) & 7) ||
-        (reinterpret_cast<uintptr_t>(a.xyz) & 3) || (reinterpret_cast<uintptr_t>(a.rgb) & 3) || (reinterpret_cast<uintptr_t>(a.n) & 3) ||
-        (reinterpret_cast<uintptr_t>(a.ws) & 3) || (reinterpret_cast<uintptr_t>(a.src_idx) & 3) || (reinterpret_cast<uintptr_t>(a.survivors) & 3))
-        return fail("rgbd_cloud: misaligned pointer (depth and seed 8 bytes, the others 4)");
-    int64_t sum = 0;
-    for (int k = 0; k < a.K; ++k) {
-        if (a.quota[k] < 1) return fail("rgbd_cloud: quota[k] < 1");
-        if (a.cam_index[k] < 0 || a.cam_index[k] >= a.C) return fail("rgbd_cloud: cam_index[k] outside 0..C-1");
-        sum += a.quota[k];
-    }
-    if (sum != a.P) return fail("rgbd_cloud: the quotas do not sum to P");
     const RcWs w = rc_carve(a.ws, s);
     if (a.ws_bytes < w.words * (int64_t)sizeof(unsigned)) return fail("rgbd_cloud: workspace too small (actmi_op_rgbd_cloud_workspace_bytes)");
     const dim3 grid((unsigned)s.NT, (unsigned)s.K, (unsigned)s.B), block(RC_BLOCK);
@@ -391,5 +696,45 @@ int launch_rgbd_cloud(const actmi_rgbd_desc& a, hipStream_t st, std::string* err
     hipLaunchKernelGGL(rgbd_write_kernel, grid, block, 0, st, a.depth, a.image, a.calib, a.seed, s, w, a.xyz, a.rgb, a.n, a.src_idx);
     prof_end(st);
     if (hipGetLastError() != hipSuccess) { if (err) *err = "rgbd_cloud: launch failed"; return -3; }
+    return 0;
+}
+
+int64_t rgbd_cloud_fps_workspace_bytes(int B, int K, int H, int W, int pool) {
+    RcShape s;
+    if (rc_shape(B, K, 1, H, W, 1, &s, nullptr) != 0 || pool < 1 || pool > ACTMI_RGBD_FPS_MAX_POOL) return -1;
+    s.pool = pool;
+    return rc_carve(nullptr, s).words * (int64_t)sizeof(unsigned);
+}
+
+int launch_rgbd_cloud_fps(const actmi_rgbd_fps_desc& f, hipStream_t st, std::string* err) {
+    auto fail = [&](const char* m) { if (err) *err = m; return -2; };
+    const actmi_rgbd_desc& a = f.base;
+    RcShape s;
+    const int rc = rc_validate(a, &s, err);
+    if (rc != 0) return rc;
+    if (f.pool < 1 || f.pool > ACTMI_RGBD_FPS_MAX_POOL) return fail("rgbd_cloud_fps: pool outside 1..ACTMI_RGBD_FPS_MAX_POOL");
+    for (int k = 0; k < a.K; ++k)
+        if (a.quota[k] > f.pool) return fail("rgbd_cloud_fps: quota[k] > pool");
+    if ((reinterpret_cast<uintptr_t>(a.ws) & 15) || (reinterpret_cast<uintptr_t>(f.order) & 3))
+        return fail("rgbd_cloud_fps: misaligned pointer (ws 16 bytes, order 4)");
+    s.pool = f.pool;
+    const RcWs w = rc_carve(a.ws, s);
+    if (a.ws_bytes < w.words * (int64_t)sizeof(unsigned))
+        return fail("rgbd_cloud_fps: workspace too small (actmi_op_rgbd_cloud_fps_workspace_bytes)");
+    const dim3 grid((unsigned)s.NT, (unsigned)s.K, (unsigned)s.B), block(RC_BLOCK);
+    const double px = (double)s.B * s.K * s.HW, pts = (double)s.B * s.K * s.pool;
+    prof_begin("rgbd_cloud_fps", 80.0 * px + 12.0 * pts * (double)s.P / s.K, 4.0 * 2.0 * px + 40.0 * pts + 31.0 * s.B * (double)s.P, st);
+    hipLaunchKernelGGL(rgbd_zero_kernel, dim3((unsigned)((w.zero_words + RC_BLOCK - 1) / RC_BLOCK)), block, 0, st, w.hist, w.zero_words);
+    hipLaunchKernelGGL(rgbd_count_kernel, grid, block, 0, st, a.depth, a.calib, a.seed, s, w);
+    hipLaunchKernelGGL(rgbd_select_kernel, grid, block, 0, st, a.depth, a.calib, a.seed, s, w);
+    hipLaunchKernelGGL(rgbd_scan_kernel, dim3((unsigned)s.B), block, 0, st, a.calib, s, w, (int*)nullptr, a.survivors);
+    hipLaunchKernelGGL(rgbd_stage_kernel, grid, block, 0, st, a.depth, a.calib, a.seed, s, w);
+    const int per = (s.pool + FP_BLOCK - 1) / FP_BLOCK;        // points per thread: the next power of two, from 2 (pairs)
+    if (per <= 2) fp_launch<2>(a, f.order, s, w, st);
+    else if (per <= 4) fp_launch<4>(a, f.order, s, w, st);
+    else if (per <= 8) fp_launch<8>(a, f.order, s, w, st);
+    else fp_launch<16>(a, f.order, s, w, st);
+    prof_end(st);
+    if (hipGetLastError() != hipSuccess) { if (err) *err = "rgbd_cloud_fps: launch failed"; return -3; }
     return 0;
 }

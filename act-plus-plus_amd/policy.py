@@ -122,7 +122,8 @@ class ACTPolicy:
 
     def set_rgbd_fusion(self, fusion):
         """register an actmi.ops.RGBDFusion: ``pointcloud={"depth": uint16 frames}`` is then fused into the cloud on the device
-        (ACTEngine.set_rgbd_fusion); the reference builds it in a host-side node (jie_aloha_scripts/pcd_fusion.py)"""
+        (ACTEngine.set_rgbd_fusion); the reference builds it in a host-side node (jie_aloha_scripts/pcd_fusion.py).  A fusion made
+        with sampling="fps" downsamples by farthest-point sampling, as that node does under --use_fps"""
         self.model.set_rgbd_fusion(fusion)
 
     # ---- nn.Module-like surface used by imitate_episodes.py ---------------------------------------

@@ -611,6 +611,46 @@ typedef struct actmi_rgbd_desc {
 /* bytes of workspace of a launch of that shape; negative when the shape is not supported */
 int64_t actmi_op_rgbd_cloud_workspace_bytes(int B, int K, int H, int W);
 int actmi_op_rgbd_cloud(const actmi_rgbd_desc* d, void* stream);
+/* ---- the same cloud with FARTHEST-POINT SAMPLING in place of the key draw (csrc/rgbd_cloud.hip): what the reference's fusion node
+ * runs in every command it ships (pcd_fusion.py:229-235 under --use_fps; fpsample.bucket_fps_kdline_sampling).  Bit parity with
+ * that package is not claimed: exact farthest-point sampling is defined here and pinned to actmi.ops.rgbd_fps_select, the same
+ * definition in numpy.
+ *
+ * Survivorship, coordinates, colours and the layout of xyz / rgb / n / src_idx / survivors are those of actmi_op_rgbd_cloud
+ * (rows ascend by (camera, pixel), no gap between cameras, zeros behind n[b]); `base` has the same meaning and validation.  Only
+ * WHICH survivors camera k keeps when it has M > quota[k] of them differs:
+ *   pool       all M survivors when M <= pool, else the `pool` survivors with the smallest key(seed, b, k, pixel) -- the key draw
+ *              above with `pool` for the quota.  Pool members are indexed j = 0, 1, .. in ascending pixel order; p_j are their fp32
+ *              coordinates as defined above, same bits.
+ *   start      the pool member with the smallest key
+ *   iteration  dist[j] = +inf at first.  After picking s: dist[s] = -1 (excluded for good) and for every other j
+ *              dist[j] = min(dist[j], ((dx * dx) + (dy * dy)) + (dz * dz)),  d = p_j - p_s, in fp32 with one rounding per operation
+ *              (no contraction).  The next pick is the j with the largest dist, the lowest such j among equals.  quota[k] picks.
+ * Coincident points never give a duplicate: once every remaining distance is 0, picks go to the lowest unpicked indices.  The kept
+ * rows are written in ascending pixel order like the key draw's (src_idx stays strictly increasing); `order` (optional, [B][P]
+ * int32) holds the iteration at which a row was picked: 0 for the start, 1 for the next pick, ..; -1 at and behind n[b].  A camera
+ * with M <= quota[k] keeps every survivor, and order = the rank in pixel order.  Nothing depends on the launch geometry; the
+ * outputs are bitwise repeatable.
+ *
+ * ACTMI_RGBD_FPS_MAX_POOL = 16384: four times the 4096 points a camera keeps in the reference's commands, and 16 points per thread
+ * of the one 1024-thread workgroup that runs a camera's selection with its points and distances in registers (64 of the 128
+ * registers such a workgroup's threads may hold); 16384 points of 16 bytes would not fit the 160 KiB of LDS either.
+ * max(quota) <= pool <= ACTMI_RGBD_FPS_MAX_POOL.  A pool above max(quota) costs registers and time per iteration, not iterations.
+ *
+ * Like actmi_op_rgbd_cloud: one stream (six launches), nothing allocated, no synchronisation, nothing read on the host, calib and
+ * seed read from the device, capturable.  base.ws: actmi_op_rgbd_cloud_fps_workspace_bytes(B, K, H, W, pool) bytes, 16-byte
+ * aligned.  Refused with a code and a message (actmi_op_last_error), nothing launched: what actmi_op_rgbd_cloud refuses, pool out
+ * of range, quota[k] > pool, a misaligned ws or order, a workspace that is too small. */
+#define ACTMI_RGBD_FPS_MAX_POOL 16384
+typedef struct actmi_rgbd_fps_desc {
+    actmi_rgbd_desc base;      /* everything actmi_op_rgbd_cloud takes, same meaning and validation */
+    int32_t pool;              /* candidate pool per camera, max(quota) <= pool <= ACTMI_RGBD_FPS_MAX_POOL */
+    int32_t reserved;
+    int32_t* order;            /* optional [B][P] int32: the iteration at which a row was picked, -1 behind n[b] */
+} actmi_rgbd_fps_desc;
+/* bytes of workspace of a launch of that shape and pool; negative when they are not supported */
+int64_t actmi_op_rgbd_cloud_fps_workspace_bytes(int B, int K, int H, int W, int pool);
+int actmi_op_rgbd_cloud_fps(const actmi_rgbd_fps_desc* d, void* stream);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
