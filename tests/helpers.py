@@ -77,6 +77,189 @@ def host_keep(seed, idx, p):
     return host_u01(seed, idx) >= np.float32(p)
 
 
+BIG_SEED = (0x5A17 << 32) | 0x9E3779B1           # above 2^32: the high seed word takes part
+
+
+# ---- float64 references of the kernels of csrc/diffusion.hip and csrc/prior.hip, shared by the GPU parity files and
+#      test_kernel_refs_cpu.py (which proves them against torch's own operators) ------------------------------------------------
+ACTS = {None: lambda v: v, "relu": torch.relu, "mish": torch.nn.functional.mish}
+GN_EPILOGUES = ["plain", "res", "film", "film+res_after"]
+
+
+def groupnorm_ref(x, w, b, G, act=None, res=None, film=None, res_after=False, eps=1e-5):
+    """channel-last x [n, ..., C]: F.group_norm in float64 on the channel-first permutation, then the epilogue documented in
+    csrc/diffusion.hip: act(GN(x) + res), or with res_after act(GN(x)) * film_scale + film_bias + res"""
+    n, C = x.shape[0], x.shape[-1]
+    xc = x.double().reshape(n, -1, C).permute(0, 2, 1)
+    # torch.group_norm is the operator behind F.group_norm, without the latter's refusal of one value per channel (n * P == 1)
+    v = torch.group_norm(xc, G, w.double(), b.double(), eps, False).permute(0, 2, 1)
+    if res is not None and not res_after:
+        v = v + res.double().reshape(n, -1, C)
+    v = ACTS[act](v)
+    if film is not None:
+        v = v * film[0].double()[:, None] + film[1].double()[:, None]
+    if res is not None and res_after:
+        v = v + res.double().reshape(n, -1, C)
+    return v.reshape(x.shape)
+
+
+def gn_epilogue_args(name, res, film):
+    """keyword arguments (for ops.groupnorm and groupnorm_ref alike) of one of GN_EPILOGUES"""
+    return {"plain": {}, "res": {"res": res}, "film": {"film": film},
+            "film+res_after": {"film": film, "res": res, "res_after": True}}[name]
+
+
+def gn_ramp(n, P, C, gen):
+    """x = randn + 40 p / P: a ramp along the positions, so that the chunk means of the large-map path differ and Chan's
+    between-chunk term carries most of the variance"""
+    return torch.randn(n, P, C, generator=gen) + 40.0 * torch.arange(P, dtype=torch.float32).view(1, P, 1) / P
+
+
+def gn_chunks(n, G, per):
+    """the chunk count actmi_op_groupnorm picks for `per` values per (sample, group)"""
+    return max(1, min(per // 16384, 2048 // (n * G) + 1, 256))
+
+
+def gn_chunked_variance(x, G, nch, between=True):
+    """biased variance per (sample, group) of channel-last x [n, P, C] in float64, combined from `nch` position chunks
+    [P ch / nch, P (ch + 1) / nch) as gn_apply_kernel combines them (Chan's update); between=False drops the between-chunk
+    term d * d * (cnt * cb / ct) -- the wrong rule the ramp case must catch"""
+    n, P, C = x.shape
+    xg = x.double().reshape(n, P, G, C // G)
+    cnt, mean, m2 = 0.0, torch.zeros(n, G, dtype=torch.float64), torch.zeros(n, G, dtype=torch.float64)
+    for ch in range(nch):
+        part = xg[:, P * ch // nch:P * (ch + 1) // nch]
+        cb = part.shape[1] * part.shape[3]
+        if cb == 0:
+            continue
+        mb = part.mean((1, 3))
+        qb = ((part - mb[:, None, :, None]) ** 2).sum((1, 3))
+        ct, d = cnt + cb, mb - mean
+        mean = mean + d * (cb / ct)
+        m2 = m2 + qb + (d * d * (cnt * cb / ct) if between else 0.0)
+        cnt = ct
+    return m2 / cnt
+
+
+def mish_inputs():
+    """float32 inputs of the Mish check: a dense sweep, the softplus threshold 20 and its neighbours, the ends of expf's range,
+    tiny values and both zeros"""
+    t20 = np.float32(20.0)
+    extra = [t20, np.nextafter(t20, np.float32(np.inf)), np.nextafter(t20, np.float32(-np.inf)), 88.0, 1e4, -60.0, 1e-20, -1e-20,
+             0.0, -0.0]
+    return torch.cat([torch.linspace(-30, 30, 6001), torch.tensor(np.array(extra, dtype=np.float32))])
+
+
+def elem_rel_err(got, exp):
+    """worst elementwise |got - exp| / |exp| over the elements whose expected value is non-zero, in float64"""
+    got, exp = got.detach().cpu().double().reshape(-1), exp.detach().cpu().double().reshape(-1)
+    nz = exp != 0
+    return float(((got[nz] - exp[nz]).abs() / exp[nz].abs()).max())
+
+
+def keypoint_grid(H, W):
+    """(x, y) coordinates [H*W] each of robomimic's SpatialSoftmax: np.linspace(-1, 1, W) along a row, np.linspace(-1, 1, H) down
+    a column (a single-element linspace is [-1])"""
+    px, py = np.meshgrid(np.linspace(-1.0, 1.0, W), np.linspace(-1.0, 1.0, H))
+    return torch.from_numpy(px.reshape(-1).copy()), torch.from_numpy(py.reshape(-1).copy())
+
+
+def spatial_softmax_ref(logits, H, W, temperature=1.0):
+    """logits [n, H*W, K] -> float64 [n, K, 2]: softmax over the positions of logits / temperature, expectation of the grid"""
+    att = torch.softmax(logits.double().permute(0, 2, 1) / temperature, dim=-1)
+    px, py = keypoint_grid(H, W)
+    return torch.stack([(att * px).sum(-1), (att * py).sum(-1)], -1)
+
+
+def unfold1d_out_len(T, k, stride, pad, transposed=False):
+    return (T - 1) * stride - 2 * pad + k if transposed else (T + 2 * pad - k) // stride + 1
+
+
+def unfold1d_ref(x, k, stride, pad, transposed=False):
+    """the gather csrc/diffusion.hip states for unfold1d, by index arithmetic: x [B, T, C] -> [B, To, k*C] in x's dtype.
+    out[b][to][j][c] = x[b][to*stride - pad + j][c] or 0; transposed: out[b][t][j][c] = x[b][(t + pad - j) / stride][c] when
+    divisible and in range, else 0"""
+    B, T, C = x.shape
+    To = unfold1d_out_len(T, k, stride, pad, transposed)
+    out = torch.zeros(B, To, k, C, dtype=x.dtype)
+    for to in range(To):
+        for j in range(k):
+            if transposed:
+                num = to + pad - j
+                ok, ti = num >= 0 and num % stride == 0 and num // stride < T, num // stride
+            else:
+                ti = to * stride - pad + j
+                ok = 0 <= ti < T
+            if ok:
+                out[:, to, j] = x[:, ti]
+    return out.reshape(B, To, k * C)
+
+
+UNFOLD_FWD = [(5, 1, 2, 16), (3, 2, 1, 16), (1, 1, 0, 8), (3, 1, 1, 7), (5, 1, 2, 1), (3, 2, 1, 2), (7, 3, 0, 20)]   # k, stride, pad, T
+UNFOLD_TRANSPOSED = [(4, 2, 1, 8), (4, 2, 1, 1), (3, 1, 1, 7), (5, 3, 2, 6), (2, 2, 0, 5)]
+
+
+def attention_keep(seed, n, H, T, p):
+    """bool [n, H, T, T]: the keep mask of the small attention kernels, element index ((g*T + q)*T + key) with g = b*H + h"""
+    cnt = n * H * T * T
+    assert cnt < 2 ** 32
+    return torch.from_numpy(host_keep(seed, np.arange(cnt, dtype=np.uint64), p)).view(n, H, T, T)
+
+
+def masked_attention_ref(qkv, H, causal, keep=None, p=0.0):
+    """qkv [n, T, 3D] (q | k | v as nn.MultiheadAttention's in_proj leaves it; float64, may require grad) -> [n, T, D]:
+    (softmax(q k^T / sqrt(HD)) * keep / (1 - p)) @ v per head, the weight dropout of nn.MultiheadAttention under a given mask"""
+    n, T, D3 = qkv.shape
+    Dm = D3 // 3
+    HD = Dm // H
+    q, k, v = (t.reshape(n, T, H, HD).transpose(1, 2) for t in qkv.split(Dm, dim=-1))
+    s = (q @ k.transpose(-1, -2)) / HD ** 0.5
+    if causal:
+        s = s.masked_fill(torch.triu(torch.ones(T, T, dtype=torch.bool), diagonal=1), float("-inf"))
+    w = s.softmax(-1)
+    if keep is not None:
+        w = w * keep.to(w.dtype) / (1.0 - p)
+    return (w @ v).transpose(1, 2).reshape(n, T, Dm)
+
+
+def fully_dropped_rows(keep, causal):
+    """(sample, head, query) index triples whose every live key is dropped"""
+    T = keep.shape[-1]
+    live = torch.tril(torch.ones(T, T, dtype=torch.bool)) if causal else torch.ones(T, T, dtype=torch.bool)
+    return torch.nonzero(~((keep & live).any(-1)))
+
+
+def argmax_tie_case(rows, V, seed):
+    """float32 logits [rows, V] and soft targets for the L1 metric: in every third row the maximum is copied into one or two
+    later columns, and in every second of those rows the maximum first moves to the LAST column and is copied into an earlier
+    one too, so ties lie on both sides of the column a plain scan meets first.  -> (x, target, rows that hold a tie)"""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(rows, V, generator=g) * 3
+    tg = torch.rand(rows, V, generator=g)
+    tied = torch.zeros(rows, dtype=torch.bool)
+    if V > 1:
+        for r in range(0, rows, 3) if rows >= 12 else range(rows):
+            m = float(x[r].max())
+            a = int(torch.argmax(x[r]))
+            if (r // 3) % 2 == 1 or a == V - 1:            # the maximum to the last column, copies before it
+                x[r, a] = m - 1.0
+                x[r, V - 1] = m
+                cols = torch.randperm(V - 1, generator=g)[:2 if V > 2 else 1]
+            else:                                          # copies behind it
+                cols = a + 1 + torch.randperm(V - 1 - a, generator=g)[:2 if V - 1 - a > 1 and r % 2 == 0 else 1]
+            x[r, cols] = m
+            tied[r] = True
+    return x, tg, tied
+
+
+def argmax_l1_ref(x, tg, last=False):
+    """mean |one_hot(argmax) - target| in float64 with torch.argmax on the float32 values (the FIRST maximum); last=True takes the
+    last maximum instead: the wrong tie rule"""
+    V = x.shape[-1]
+    idx = V - 1 - torch.argmax(x.flip(-1), dim=-1) if last else torch.argmax(x, dim=-1)
+    return float((torch.nn.functional.one_hot(idx, V).double() - tg.double()).abs().mean())
+
+
 def gemm_desc(**kw):
     """an actmi_gemm_desc from keyword fields; tensors become their device addresses (the caller keeps them alive)"""
     from actmi import lib as L
