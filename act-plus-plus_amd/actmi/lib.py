@@ -114,6 +114,18 @@ class RgbdFpsDesc(C.Structure):
     _fields_ = [("base", RgbdDesc), ("pool", C.c_int32), ("reserved", C.c_int32), ("order", C.c_void_p)]
 
 
+class AugmentRecord(C.Structure):
+    # actmi_augment_record: the device parameter record of one sample, 32 bytes
+    _fields_ = [("top", C.c_int32), ("left", C.c_int32), ("order", C.c_int32), ("cos", C.c_float), ("sin", C.c_float),
+                ("fb", C.c_float), ("fc", C.c_float), ("fs", C.c_float)]
+
+
+class AugmentDesc(C.Structure):
+    # actmi_augment_desc: actmi_op_augment_u8 and actmi_op_warp_u16 take the same descriptor
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("records", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)] + \
+               [(k, C.c_int32) for k in ("B", "K", "H", "W", "ch", "cw")]
+
+
 _lib = None
 
 
@@ -206,6 +218,9 @@ def load():
         "actmi_op_rgbd_cloud": ([C.POINTER(RgbdDesc), vp], i32),
         "actmi_op_rgbd_cloud_fps_workspace_bytes": ([i32, i32, i32, i32, i32], C.c_int64),
         "actmi_op_rgbd_cloud_fps": ([C.POINTER(RgbdFpsDesc), vp], i32),
+        "actmi_op_augment_workspace_bytes": ([i32, i32, i32, i32], C.c_int64),
+        "actmi_op_augment_u8": ([C.POINTER(AugmentDesc), vp], i32),
+        "actmi_op_warp_u16": ([C.POINTER(AugmentDesc), vp], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

@@ -1109,6 +1109,263 @@ class RGBDFusion:
         return self.outputs(B)
 
 
+# ---- training-time image augmentation (csrc/augment.hip; contract at actmi_augment_desc in actmi.h) ------------------------------
+AUGMENT_ORDERS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))      # 0 brightness, 1 contrast, 2 saturation
+
+
+def augment_record_dtype():
+    """actmi_augment_record as a numpy structured dtype (32 bytes)"""
+    import numpy as np
+    return np.dtype([("top", "<i4"), ("left", "<i4"), ("order", "<i4"), ("cos", "<f4"), ("sin", "<f4"), ("fb", "<f4"), ("fc", "<f4"),
+                     ("fs", "<f4")])
+
+
+def augment_records(B, top=0, left=0, angle=0.0, order=0, fb=1.0, fc=1.0, fs=1.0):
+    """[B] records from numbers or [B] arrays; angle in degrees, counter-clockwise (torchvision's sign): cos and sin are taken in
+    double on the host and rounded to float32.  The defaults are the identity when the crop is the whole frame."""
+    import numpy as np
+    r = np.zeros(int(B), dtype=augment_record_dtype())
+    a = np.deg2rad(np.broadcast_to(np.asarray(angle, dtype=np.float64), (int(B),)))
+    r["top"], r["left"], r["order"] = top, left, order
+    r["cos"], r["sin"] = np.cos(a), np.sin(a)
+    r["fb"], r["fc"], r["fs"] = fb, fc, fs
+    return r
+
+
+def _augment_geometry(H, W, ch, cw, rec):
+    """the gather of one record in numpy float32: (inside [H, W] bool, y0, y1, x0, x1 int, wy, wx float32, top, left) -- and sx, sy
+    for the tests that want to know how close a pixel sits to a rounding boundary"""
+    import numpy as np
+    f = np.float32
+    cs, sn = f(rec["cos"]), f(rec["sin"])
+    top = min(max(int(rec["top"]), 0), H - ch)
+    left = min(max(int(rec["left"]), 0), W - cw)
+    hw, hh = f(W) * f(0.5), f(H) * f(0.5)
+    x = ((np.arange(W, dtype=f) + f(0.5)) - hw)[None, :]
+    y = ((np.arange(H, dtype=f) + f(0.5)) - hh)[:, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        sx = ((x * cs) - (y * sn)) + (hw - f(0.5))
+        sy = ((x * sn) + (y * cs)) + (hh - f(0.5))
+        fj, fi = np.rint(sx), np.rint(sy)
+        inside = (fj >= 0) & (fj < W) & (fi >= 0) & (fi < H)
+    rj = np.where(inside, fj, 0).astype(np.int64)
+    ri = np.where(inside, fi, 0).astype(np.int64)
+
+    def taps(r, n_in, n_out):
+        c = np.maximum((r.astype(f) + f(0.5)) * (f(n_in) / f(n_out)) - f(0.5), f(0))
+        i0 = np.minimum(np.floor(c).astype(np.int64), n_in - 1)
+        return i0, np.minimum(i0 + 1, n_in - 1), c - i0.astype(f)
+    y0, y1, wy = taps(ri, ch, H)
+    x0, x1, wx = taps(rj, cw, W)
+    return inside, y0, y1, x0, x1, wy, wx, top, left, sx, sy
+
+
+def _augment_warp(planes, H, W, ch, cw, rec):
+    """planes [..., H, W] (any integer dtype) -> the warped planes as float32 whole numbers (before the cast)"""
+    import numpy as np
+    f = np.float32
+    inside, y0, y1, x0, x1, wy, wx, top, left, _, _ = _augment_geometry(H, W, ch, cw, rec)
+    v = planes.astype(f)
+    v00, v01 = v[..., top + y0, left + x0], v[..., top + y0, left + x1]
+    v10, v11 = v[..., top + y1, left + x0], v[..., top + y1, left + x1]
+    t0 = (v00 * (f(1) - wx)) + (v01 * wx)
+    t1 = (v10 * (f(1) - wx)) + (v11 * wx)
+    out = np.rint((t0 * (f(1) - wy)) + (t1 * wy))
+    return np.where(inside, out, f(0))
+
+
+def _augment_jitter(x, rec):
+    """x [K, H, W, 3] float32 whole numbers 0..255 -> the same after the record's three ops"""
+    import numpy as np
+    f = np.float32
+
+    def gray(a):
+        return np.trunc(((f(0.2989) * a[..., 0]) + (f(0.587) * a[..., 1])) + (f(0.114) * a[..., 2]))[..., None]
+
+    def blend(a, b, r):
+        r = f(r)
+        return np.trunc(np.clip((r * a) + ((f(1) - r) * b), f(0), f(255)))
+    for op in AUGMENT_ORDERS[min(max(int(rec["order"]), 0), 5)]:
+        if op == 0:
+            x = blend(x, f(0), rec["fb"])
+        elif op == 1:
+            g = gray(x)
+            total = g.astype(np.int64).sum(axis=(1, 2, 3), keepdims=True)                   # per camera image, exact
+            mean = (total.astype(np.float64) / float(g.shape[1] * g.shape[2])).astype(f)
+            x = blend(x, mean, rec["fc"])
+        else:
+            x = blend(x, gray(x), rec["fs"])
+    return x
+
+
+def image_augment_ref(image_u8, records, ch, cw):
+    """actmi_op_augment_u8 in numpy: the definition at actmi_augment_desc in actmi.h stated once more -- the oracle of the device
+    op, not a fallback for it.  image_u8 [B, K, H, W, 3] uint8 (numpy or a CPU tensor), records [B] (augment_record_dtype) ->
+    numpy uint8 of the same shape."""
+    import numpy as np
+    img = np.asarray(image_u8)
+    B, K, H, W, _ = img.shape
+    ch, cw = int(ch), int(cw)
+    if img.dtype != np.uint8 or img.shape[4] != 3 or len(records) != B or not (1 <= ch <= H and 1 <= cw <= W):
+        raise ValueError(f"image_augment_ref: frames {img.dtype} {img.shape}, {len(records)} records, crop {ch} x {cw}")
+    out = np.empty_like(img)
+    for b in range(B):
+        planes = np.moveaxis(img[b], -1, 1)                                                  # [K, 3, H, W]
+        warped = np.moveaxis(_augment_warp(planes, H, W, ch, cw, records[b]), 1, -1)         # [K, H, W, 3]
+        out[b] = _augment_jitter(warped, records[b]).astype(np.uint8)
+    return out
+
+
+def depth_warp_ref(depth_u16, records, ch, cw):
+    """actmi_op_warp_u16 in numpy: the geometric steps of image_augment_ref on uint16 [B, Kd, H, W] (or [B, Kd, 1, H, W]) frames"""
+    import numpy as np
+    d = np.asarray(depth_u16)
+    H, W = d.shape[-2:]
+    ch, cw = int(ch), int(cw)
+    if d.dtype != np.uint16 or d.ndim not in (4, 5) or len(records) != d.shape[0] or not (1 <= ch <= H and 1 <= cw <= W):
+        raise ValueError(f"depth_warp_ref: frames {d.dtype} {d.shape}, {len(records)} records, crop {ch} x {cw}")
+    out = np.empty_like(d)
+    for b in range(d.shape[0]):
+        out[b] = np.clip(_augment_warp(d[b], H, W, ch, cw, records[b]), 0, 65535).astype(np.uint16)
+    return out
+
+
+class ImageAugment:
+    """The reference dataset's training augmentation (utils.py:141-156: RandomCrop at `ratio`, Resize back with antialias,
+    RandomRotation within `degrees`, ColorJitter) as one device op over the u8 batch of a training step (actmi_op_augment_u8), and
+    the three geometric steps over the raw uint16 depth frames of a use_depth batch with the SAME draws (actmi_op_warp_u16).  Owns
+    the output buffers, the workspace, and the records: a ring of pinned host blocks and one device block.
+
+    engine_or_device: an ACTEngine (its device) or a device.  K cameras (Kd depth cameras, 0: none) of H x W pixels.  One draw per
+    SAMPLE: top, left uniform integers over the crop's positions, angle U[-degrees, degrees], factors U[1 - x, 1 + x] (not below
+    0), order uniform over the 6 -- from a numpy.random.Generator seeded with `seed`.  The distributions are torchvision's;
+    draw-for-draw parity with torchvision's generator is not claimed.
+
+    draw(B) fills and uploads records; run(image_u8, depth_u16, B) launches with the records on the device; apply = draw + run.
+    The returned tensors are views of the augmenter's own buffers, valid until the next run."""
+    RING = 4
+
+    def __init__(self, engine_or_device, K, H, W, max_batch, ratio=0.95, degrees=5.0, brightness=0.3, contrast=0.4, saturation=0.5,
+                 seed=0, Kd=0):
+        import numpy as np
+        eng = engine_or_device if hasattr(engine_or_device, "cfg") else None
+        self.device = torch.device(eng.device if eng is not None else engine_or_device)
+        if self.device.type != "cuda":
+            raise ValueError(f"ImageAugment: device must be a cuda device, got {self.device}")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self.K, self.Kd, self.H, self.W, self.max_batch = int(K), int(Kd), int(H), int(W), int(max_batch)
+        if self.K < 1 or self.Kd < 0 or self.H < 1 or self.W < 1 or self.max_batch < 1:
+            raise ValueError(f"ImageAugment: K = {K}, Kd = {Kd}, {H} x {W}, max_batch = {max_batch}")
+        if not 0.0 < ratio <= 1.0 or degrees < 0 or min(brightness, contrast, saturation) < 0:
+            raise ValueError(f"ImageAugment: ratio {ratio} outside (0, 1], or a negative range")
+        self.ch, self.cw = max(1, int(self.H * ratio)), max(1, int(self.W * ratio))           # utils.py:147
+        self.degrees = float(degrees)
+        self.ranges = tuple((max(0.0, 1.0 - float(x)), 1.0 + float(x)) for x in (brightness, contrast, saturation))
+        self._np = np
+        self.set_seed(seed)
+        self._host = None                                  # device and pinned buffers: made on the first use of a GPU
+        self._last = np.zeros(0, dtype=augment_record_dtype())
+        if torch.cuda.is_available():
+            self._alloc()
+
+    def _alloc(self):
+        dev, MB = self.device, self.max_batch
+        nbytes = max(int(L.load().actmi_op_augment_workspace_bytes(MB, k, self.H, self.W)) for k in (self.K, max(self.Kd, 1)))
+        if nbytes < 0:
+            raise ValueError(f"ImageAugment: shape B = {MB}, K = {self.K}, {self.H} x {self.W} not supported by actmi_op_augment_u8")
+        self._ws = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+        self._rec = torch.zeros(MB * 32, dtype=torch.uint8, device=dev)
+        self._host = [torch.zeros(MB * 32, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
+        self._events = [None] * self.RING
+        self._slot = 0
+        self.out = torch.zeros((MB, self.K, self.H, self.W, 3), dtype=torch.uint8, device=dev)
+        self.depth_out = torch.zeros((MB, self.Kd, 1, self.H, self.W), dtype=torch.uint16, device=dev) if self.Kd else None
+
+    def set_seed(self, seed):
+        """restart the generator of the draws"""
+        self._rng = self._np.random.default_rng(int(seed))
+
+    def draw_records(self, B):
+        """[B] fresh records on the host (nothing is uploaded)"""
+        rng, B = self._rng, int(B)
+        top = rng.integers(0, self.H - self.ch + 1, size=B)
+        left = rng.integers(0, self.W - self.cw + 1, size=B)
+        angle = rng.uniform(-self.degrees, self.degrees, size=B)
+        fb, fc, fs = (rng.uniform(lo, hi, size=B) for lo, hi in self.ranges)
+        order = rng.integers(0, 6, size=B)
+        return augment_records(B, top, left, angle, order, fb, fc, fs)
+
+    def set_records(self, records):
+        """upload [B] records (augment_record_dtype) on the current stream: launches enqueued behind it, captured ones too, see
+        them.  The pinned block a copy reads from is not rewritten before that copy has run (a ring of blocks, an event each)."""
+        np = self._np
+        rec = np.ascontiguousarray(records, dtype=augment_record_dtype())
+        B = len(rec)
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"ImageAugment: {B} records: needs 1 <= B <= max_batch {self.max_batch}")
+        self._last = rec.copy()
+        if self._host is None:
+            self._alloc()
+        i = self._slot
+        self._slot = (i + 1) % self.RING
+        if self._events[i] is not None:
+            self._events[i].synchronize()
+        self._host[i].numpy()[:B * 32] = rec.view(np.uint8)
+        with torch.cuda.device(self.device):
+            self._rec[:B * 32].copy_(self._host[i][:B * 32], non_blocking=True)
+            self._events[i] = torch.cuda.Event()
+            self._events[i].record(torch.cuda.current_stream(self.device))
+
+    def records(self):
+        """the records of the last draw / set_records, on the host"""
+        return self._last.copy()
+
+    def draw(self, B):
+        self.set_records(self.draw_records(B))
+
+    def _check(self, name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise NotImplementedError(f"ImageAugment: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))} (the "
+                                      f"augmentation runs on the raw frames)")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"ImageAugment: {name} shape {tuple(t.shape)} != {shape}")
+        if not t.is_cuda or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f"ImageAugment: {name} must be contiguous on {self.device} (it is on {t.device})")
+
+    def run(self, image_u8, depth_u16=None, B=None):
+        """launch with the records on the device -> the augmented image batch, or (image, depth) when depth frames are given"""
+        B = int(image_u8.shape[0] if B is None else B)
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"ImageAugment: B = {B}: needs 1 <= B <= max_batch {self.max_batch}")
+        self._check("image", image_u8, torch.uint8, (B, self.K, self.H, self.W, 3))
+        if depth_u16 is not None:
+            if not self.Kd:
+                raise ValueError("ImageAugment: depth frames given to an augmenter built with Kd = 0")
+            if isinstance(depth_u16, torch.Tensor) and tuple(depth_u16.shape) == (B, self.Kd, self.H, self.W):
+                depth_u16 = depth_u16.unsqueeze(2)
+            self._check("depth", depth_u16, torch.uint16, (B, self.Kd, 1, self.H, self.W))
+        if self._host is None:
+            self._alloc()
+        d = L.AugmentDesc()
+        d.records, d.ws, d.ws_bytes = self._rec.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 4
+        d.B, d.H, d.W, d.ch, d.cw = B, self.H, self.W, self.ch, self.cw
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            d.in_, d.out, d.K = image_u8.data_ptr(), self.out.data_ptr(), self.K
+            L.check(L.load().actmi_op_augment_u8(C.byref(d), st), None, "op_augment_u8")
+            if depth_u16 is None:
+                return self.out[:B]
+            d.in_, d.out, d.K = depth_u16.data_ptr(), self.depth_out.data_ptr(), self.Kd
+            L.check(L.load().actmi_op_warp_u16(C.byref(d), st), None, "op_warp_u16")
+        return self.out[:B], self.depth_out[:B]
+
+    def apply(self, image_u8, depth_u16=None, B=None):
+        """one fresh draw per sample, then run"""
+        self.draw(int(image_u8.shape[0] if B is None else B))
+        return self.run(image_u8, depth_u16, B)
+
+
 class TemporalEnsemble:
     """Batched temporal ensembling state for E episodes (reference imitate_episodes.py:338-339, 402-411).
     Ring buffer [E,Q,Q,A] instead of the reference's [T,T+Q,A] per episode: only the last Q chunks can

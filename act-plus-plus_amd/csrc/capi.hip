@@ -407,6 +407,22 @@ int actmi_op_rgbd_cloud_fps(const actmi_rgbd_fps_desc* d, void* stream) {
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
 }
 
+int64_t actmi_op_augment_workspace_bytes(int B, int K, int H, int W) { return augment_workspace_bytes(B, K, H, W); }
+
+int actmi_op_augment_u8(const actmi_augment_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "augment: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_augment_u8(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
+int actmi_op_warp_u16(const actmi_augment_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "warp_u16: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_warp_u16(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int64_t n_per_sample, void* stream) {
     g_op_error.clear();
     const int rc = launch_depth_minmax_u16(depth, lohi_out, B, n_per_sample, S(stream));

@@ -207,6 +207,12 @@ int launch_rgbd_cloud(const actmi_rgbd_desc& a, hipStream_t st, std::string* err
 int64_t rgbd_cloud_fps_workspace_bytes(int B, int K, int H, int W, int pool);
 int launch_rgbd_cloud_fps(const actmi_rgbd_fps_desc& a, hipStream_t st, std::string* err);
 
+// ---- training-time image augmentation (augment.hip; contract at actmi_augment_desc in actmi.h) -------------------------
+int64_t augment_workspace_bytes(int B, int K, int H, int W);
+int launch_augment_u8(const actmi_augment_desc& a, hipStream_t st, std::string* err);
+// the geometric steps alone on one-channel u16 frames (raw depth), same records
+int launch_warp_u16(const actmi_augment_desc& a, hipStream_t st, std::string* err);
+
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------
 bool prof_enabled();
 void prof_begin(const char* name, double flops, double bytes, hipStream_t st);

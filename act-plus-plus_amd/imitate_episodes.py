@@ -346,16 +346,37 @@ def eval_bc(config, ckpt_name, save_episode=True, num_rollouts=50, policy=None, 
     return success_rate, avg_return
 
 
-def forward_pass(data, policy):
+def _augment_frames(augment, image_data, depth_data=None):
+    """the frames of a training batch through ``augment.apply`` (actmi.ops.ImageAugment): the raw u8 image batch, and with it --
+    in ONE call, so that both see the same draws -- the raw uint16 depth frames of a use_depth batch"""
+    if image_data.dtype != torch.uint8:
+        raise NotImplementedError(f"--augment_images runs on the raw u8 [B, K, H, W, 3] frames, not on a {image_data.dtype} image "
+                                  "batch (f32_images)")
+    if depth_data is None:
+        return augment.apply(image_data), None
+    if depth_data.dtype != torch.uint16:
+        raise NotImplementedError(f"--augment_images warps raw uint16 depth frames, not a {depth_data.dtype} depth batch (f32_depth)")
+    return augment.apply(image_data, depth_data)
+
+
+def forward_pass(data, policy, augment=None):
     """reference imitate_episodes.py:529-532; a 5-tuple ends in the depth frames of a use_depth dataset (the fork's
     train_single_arm_gripper_all.py:568-588), a 7-tuple in the padded clouds of a use_pcd dataset and their valid counts
-    (pcd_xyz, pcd_rgb, pcd_n; the fork's :576-591 passes the one fused cloud)."""
+    (pcd_xyz, pcd_rgb, pcd_n; the fork's :576-591 passes the one fused cloud).
+
+    ``augment`` (an actmi.ops.ImageAugment; None: nothing changes): the batch's frames go through its ``apply`` on the device
+    before the policy sees them -- the reference's dataset augmentation (utils.py:141-156), one draw per sample.  The raw depth
+    frames of a use_depth batch are warped with the SAME draws; the fork draws a second time for depth
+    (utils_arm_gripper_all.py:180-184), which moves depth and colour apart -- the intent, registered frames, is followed here.
+    The clouds of a use_pcd batch are left alone."""
     depth_data = None
     if len(data) == 7:
         image_data, qpos_data, action_data, is_pad, pcd_xyz, pcd_rgb, pcd_n = data
         dev = getattr(getattr(policy, "model", None), "device", None) or "cuda"
         image_data, qpos_data, action_data, is_pad, pcd_xyz, pcd_rgb, pcd_n = (
             t.to(dev, non_blocking=True) for t in (image_data, qpos_data, action_data, is_pad, pcd_xyz, pcd_rgb, pcd_n))
+        if augment is not None:
+            image_data, _ = _augment_frames(augment, image_data)
         return policy(qpos_data, image_data, action_data, is_pad, pointcloud={"xyz": pcd_xyz, "rgb": pcd_rgb, "n": pcd_n})
     if len(data) == 5:
         image_data, qpos_data, action_data, is_pad, depth_data = data
@@ -364,8 +385,24 @@ def forward_pass(data, policy):
     dev = getattr(getattr(policy, "model", None), "device", None) or "cuda"
     image_data, qpos_data, action_data, is_pad = (t.to(dev, non_blocking=True) for t in (image_data, qpos_data, action_data, is_pad))
     if depth_data is not None:
-        return policy(qpos_data, image_data, action_data, is_pad, depth_img=depth_data.to(dev, non_blocking=True))
+        depth_data = depth_data.to(dev, non_blocking=True)
+        if augment is not None:
+            image_data, depth_data = _augment_frames(augment, image_data, depth_data)
+        return policy(qpos_data, image_data, action_data, is_pad, depth_img=depth_data)
+    if augment is not None:
+        image_data, _ = _augment_frames(augment, image_data)
     return policy(qpos_data, image_data, action_data, is_pad)
+
+
+def make_augment(config, policy, seed):
+    """the ImageAugment of a --augment_images run, sized from the policy's engine; None without the flag"""
+    if not config.get("augment_images"):
+        return None
+    from actmi.ops import ImageAugment
+    eng = policy.model
+    cfg = eng.cfg
+    return ImageAugment(eng, cfg.num_cams, cfg.image_h, cfg.image_w, eng.max_batch, seed=seed,
+                        Kd=cfg.num_depth_cams)
 
 
 def train_bc(train_dataloader, val_dataloader, config, log=None):
@@ -410,6 +447,9 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
     os.makedirs(ckpt_dir, exist_ok=True)
     from actmi.data import DevicePrefetcher
     train_dataloader = DevicePrefetcher(repeater(train_dataloader))      # next batch's H2D copy overlaps this step
+    # --augment_images: one device pass over the TRAINING batches just before the stem.  Validation stays un-augmented, so that
+    # validation losses of runs with and without the flag compare (the reference's validation set is augmented too: utils.py:153)
+    augment = make_augment(config, policy, seed + rank)
     for step in range(num_steps + 1):
         if step % validate_every == 0:
             policy.eval()
@@ -440,7 +480,7 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
         policy.train()
         optimizer.zero_grad()
         data = next(train_dataloader)
-        forward_dict = forward_pass(data, policy)
+        forward_dict = forward_pass(data, policy, augment)
         loss = forward_dict["loss"]
         loss.backward()
         optimizer.step()
@@ -502,6 +542,9 @@ def build_config(args):
         raise NotImplementedError("--use_depth: depth cameras belong to the ACT policy")
     if args.get("use_pcd") and policy_class != "ACT":
         raise NotImplementedError("--use_pcd: the point-cloud token belongs to the ACT policy")
+    if args.get("augment_images") and policy_class != "ACT":
+        raise NotImplementedError("--augment_images: the device-side augmentation belongs to the ACT training path (Diffusion "
+                                  "training is outside the accelerated path)")
     config = {"num_steps": args["num_steps"], "eval_every": args["eval_every"], "validate_every": args["validate_every"],
             "save_every": args["save_every"], "ckpt_dir": args["ckpt_dir"], "resume_ckpt_path": args.get("resume_ckpt_path"),
             "episode_len": task_config["episode_len"], "state_dim": 14, "lr": args["lr"],
@@ -512,6 +555,8 @@ def build_config(args):
             "synthetic_env": bool(args.get("synthetic_env", False))}
     if args.get("use_pcd"):
         config["pointcloud_names"] = list(task_config["pointcloud_names"])
+    if args.get("augment_images"):
+        config["augment_images"] = True
     return config
 
 
@@ -572,7 +617,8 @@ def main(args):
     dist_utils.barrier()
 
 
-if __name__ == "__main__":
+def make_parser():
+    """the CLI of reference imitate_episodes.py:633-666 and this path's additions"""
     parser = argparse.ArgumentParser()
     parser.add_argument("--eval", action="store_true")
     parser.add_argument("--onscreen_render", action="store_true")
@@ -616,4 +662,12 @@ if __name__ == "__main__":
                              "(throughput / plumbing runs; its success rates are not task results)")
     parser.add_argument("--dataset_dir", action="store", type=str, default=None,
                         help="episode files (reference HDF5 layout, or .npz with the same keys); default: the task's dataset_dir")
-    main(vars(parser.parse_args()))
+    parser.add_argument("--augment_images", action="store_true",
+                        help="ACT training only, opt-in: the reference dataset's augmentation (random 0.95 crop resized back, rotation "
+                             "within 5 degrees, brightness / contrast / saturation jitter) on the device, for training batches; the "
+                             "reference switches it on for Diffusion alone, which is outside this path")
+    return parser
+
+
+if __name__ == "__main__":
+    main(vars(make_parser().parse_args()))

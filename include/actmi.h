@@ -651,6 +651,64 @@ typedef struct actmi_rgbd_fps_desc {
 /* bytes of workspace of a launch of that shape and pool; negative when they are not supported */
 int64_t actmi_op_rgbd_cloud_fps_workspace_bytes(int B, int K, int H, int W, int pool);
 int actmi_op_rgbd_cloud_fps(const actmi_rgbd_fps_desc* d, void* stream);
+/* ---- training-time image augmentation on the device (csrc/augment.hip): the four torchvision transforms of the reference's
+ * dataset (utils.py:141-156) -- RandomCrop at ratio 0.95, Resize back to the frame size with antialias=True, RandomRotation within
+ * 5 degrees, ColorJitter(brightness, contrast, saturation) -- as one op over the u8 batch the training step already holds on the
+ * device.  The host draws; the device reads ONE 32-byte record per SAMPLE (all K cameras of a sample share its draw, as the
+ * reference transforms the [K, 3, H, W] stack in one call).  actmi.ops.image_augment_ref / depth_warp_ref are this definition in
+ * numpy; parity with torchvision's own arithmetic is to 1 LSB per step (tests/test_augment_cpu.py), with its generator: none.
+ *
+ * actmi_op_augment_u8: in, out u8 [B][K][H][W][3].  Per output pixel (i, j) of every camera image, every product and sum rounded to
+ * fp32 on its own, in the order written (no contraction into FMAs):
+ *   rotation     nearest sample, expand = False, fill 0, about the centre.
+ *                x = (j + 0.5) - W/2,  y = (i + 0.5) - H/2
+ *                sx = (x*cos - y*sin) + (W/2 - 0.5),  sy = (x*sin + y*cos) + (H/2 - 0.5)
+ *                rj = rint(sx), ri = rint(sy), half to even.  Outside [0, W) x [0, H) the pixel is 0 and skips the next step (the
+ *                jitter still runs over it).
+ *   crop+resize  evaluated at (ri, rj) only: bilinear, align_corners = False -- for an upscale that is what antialias=True computes.
+ *                Per axis (r, n_in, n_out) = (ri, ch, H) and (rj, cw, W):
+ *                c = max((r + 0.5) * (f32(n_in) / f32(n_out)) - 0.5, 0),  i0 = min(floor(c), n_in-1),  i1 = min(i0+1, n_in-1),  w = c - i0
+ *                horizontal first, t = v0*(1-wx) + v1*wx for the rows y0 and y1, then v = t0*(1-wy) + t1*wy, then rint to u8.
+ *                The taps are in[top + y.][left + x.].
+ *   jitter       three ops in the order the record names, each on the u8 result of the one before:
+ *                blend(a, b, r) = trunc(clamp(r*a + (1-r)*b, 0, 255)),  gray = trunc((0.2989 r + 0.587 g) + 0.114 b)
+ *                brightness = blend(img, 0, fb);  saturation = blend(img, gray, fs);  contrast = blend(img, mean, fc), mean = the mean
+ *                of gray over that ONE camera image as it stands when contrast's turn comes: the exact integer sum, divided in double,
+ *                rounded to fp32.
+ * `order` 0..5 indexes the lexicographic permutations of (0 = brightness, 1 = contrast, 2 = saturation): 012 021 102 120 201 210.
+ * The mean is a reduction over a whole image, so the op is two launches: the gather and the ops ahead of contrast, with gray summed on
+ * chip to one integer per workgroup; then contrast and the ops behind it, in place on `out`.  Integer sums: the result does not
+ * depend on arrival order and is bitwise repeatable.
+ *
+ * actmi_op_warp_u16: the two geometric steps alone on raw depth, in / out uint16 [B][K][H][W] (K = the depth cameras), same records,
+ * same arithmetic, rint to u16, fill 0; the whole 0..65535 range survives.
+ *
+ * The kernels hold what they read from a record to the ranges that keep every address inside the frame: top to [0, H-ch], left to
+ * [0, W-cw], order to 0..5; a factor, cos or sin that is not a number gives zeros, never a wild address.  Both ops run on one
+ * stream, allocate nothing, never synchronise and read nothing on the host: capturable, and a captured launch sees the records a
+ * stream-ordered copy wrote since.  1 <= ch <= H, 1 <= cw <= W, B * K <= 65535, H * W <= 2^24.  ws: 4-byte aligned,
+ * actmi_op_augment_workspace_bytes(B, K, H, W) bytes of scratch (the warp validates it like the augment op -- one descriptor serves
+ * both -- and keeps nothing in it).  Refused with a code and a message (actmi_op_last_error), nothing launched: a null pointer, `out`
+ * overlapping `in` (the op is a gather), ch / cw out of range, an unsupported shape, a misaligned or short workspace. */
+typedef struct actmi_augment_record {          /* the DEVICE parameter record of one sample: 32 bytes */
+    int32_t top, left;         /* the crop's corner */
+    int32_t order;             /* 0..5 */
+    float cos, sin;            /* of the rotation angle (counter-clockwise, as torchvision's), computed on the host */
+    float fb, fc, fs;          /* brightness, contrast, saturation factors */
+} actmi_augment_record;
+typedef struct actmi_augment_desc {
+    const void* in;            /* u8 [B][K][H][W][3] (augment_u8) or uint16 [B][K][H][W] (warp_u16) */
+    void* out;                 /* same shape, no overlap with in */
+    const actmi_augment_record* records;       /* [B], on the device */
+    void* ws;
+    int64_t ws_bytes;
+    int32_t B, K, H, W;
+    int32_t ch, cw;            /* the crop's size */
+} actmi_augment_desc;
+/* bytes of workspace of a launch of that shape; negative when the shape is not supported */
+int64_t actmi_op_augment_workspace_bytes(int B, int K, int H, int W);
+int actmi_op_augment_u8(const actmi_augment_desc* d, void* stream);
+int actmi_op_warp_u16(const actmi_augment_desc* d, void* stream);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
