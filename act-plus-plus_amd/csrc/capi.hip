@@ -376,16 +376,20 @@ int actmi_op_conv1(const void* image, int image_fmt, const float* w_oihw, const 
     return launch_conv1(a, S(stream), &g_op_error);
 }
 
-// workspace layout of the prepared stem: [C*Cout*148 repacked weights][768 lut][C*Cout ones][C*Cout zeros][C * wimg bytes]
-static int64_t conv1_ws_off_lut(int C, int Cout) { return (int64_t)C * Cout * 148; }
-int actmi_op_conv1_depth(const float* depth, const float* w_oihw, const float* scale, const float* bias, float* out, int B,
-                         int Cd, int H, int W, int Cout, int out_cam0, void* stream) {
+// the depth stem on an f32 batch (lohi = NULL) or a raw u16 one
+static int op_conv1_depth(const void* depth, bool u16, const float* lohi, const float* w_oihw, const float* scale, const float* bias,
+                          float* out, int B, int Cd, int H, int W, int Cout, int out_cam0, void* stream) {
     g_op_error.clear();
     Conv1DepthArgs a;
-    a.depth = depth; a.w = w_oihw; a.w_cam_stride = (int64_t)Cout * 49; a.scale = scale; a.bias = bias; a.out = out;
+    a.depth = depth; a.src_u16 = u16; a.lohi = lohi;
+    a.w = w_oihw; a.w_cam_stride = (int64_t)Cout * 49; a.scale = scale; a.bias = bias; a.out = out;
     a.B = B; a.Cd = Cd; a.H = H; a.W = W; a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1; a.Cout = Cout; a.out_cam0 = out_cam0;
     const int rc = launch_conv1_depth(a, S(stream), &g_op_error);
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+int actmi_op_conv1_depth(const float* depth, const float* w_oihw, const float* scale, const float* bias, float* out, int B,
+                         int Cd, int H, int W, int Cout, int out_cam0, void* stream) {
+    return op_conv1_depth(depth, false, nullptr, w_oihw, scale, bias, out, B, Cd, H, W, Cout, out_cam0, stream);
 }
 int64_t actmi_op_rgbd_cloud_workspace_bytes(int B, int K, int H, int W) { return rgbd_cloud_workspace_bytes(B, K, H, W); }
 
@@ -431,32 +435,36 @@ int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int
 }
 int actmi_op_conv1_depth_u16(const uint16_t* depth, const float* lohi, const float* w_oihw, const float* scale, const float* bias, float* out,
                              int B, int Cd, int H, int W, int Cout, int out_cam0, void* stream) {
-    g_op_error.clear();
-    Conv1DepthArgs a;
-    a.depth = depth; a.src_u16 = 1; a.lohi = lohi;
-    a.w = w_oihw; a.w_cam_stride = (int64_t)Cout * 49; a.scale = scale; a.bias = bias; a.out = out;
-    a.B = B; a.Cd = Cd; a.H = H; a.W = W; a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1; a.Cout = Cout; a.out_cam0 = out_cam0;
-    const int rc = launch_conv1_depth(a, S(stream), &g_op_error);
-    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+    return op_conv1_depth(depth, true, lohi, w_oihw, scale, bias, out, B, Cd, H, W, Cout, out_cam0, stream);
 }
-int64_t actmi_op_conv1_workspace_floats(int C, int Cout) {
-    return conv1_ws_off_lut(C, Cout) + 768 + 2 * (int64_t)C * Cout + (int64_t)C * ((conv1_wimg_bytes() + 3) / 4) + 16;
-}
+// workspace of the prepared stem: [C*Cout*148 repacked weights][768 lut][C*Cout ones][C*Cout zeros][up to 16 B][C * wimg bytes];
+// the weight image starts at the next 16-byte boundary of the ADDRESS (the workspace itself need not be aligned)
+struct Conv1Workspace {
+    float *w, *lut, *ones, *zeros;
+    unsigned char* wimg;
+    Conv1Workspace(const float* ws, int C, int Cout) {
+        w = const_cast<float*>(ws);
+        lut = w + (int64_t)C * Cout * 148;
+        ones = lut + 768;
+        zeros = ones + (int64_t)C * Cout;
+        wimg = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(zeros + (int64_t)C * Cout) + 15) & ~(uintptr_t)15);
+    }
+    static int64_t floats(int C, int Cout) {
+        return (int64_t)C * Cout * 148 + 768 + 2 * (int64_t)C * Cout + 16 + (int64_t)C * ((conv1_wimg_bytes() + 3) / 4);
+    }
+};
+int64_t actmi_op_conv1_workspace_floats(int C, int Cout) { return Conv1Workspace::floats(C, Cout); }
 int actmi_op_conv1_prepare(const float* w_oihw, float* workspace, int C, int Cout, int lut_mode, void* stream) {
     g_op_error.clear();
     if (!w_oihw || !workspace || C < 1 || Cout < 1 || Cout > 64) { g_op_error = "conv1_prepare: bad argument"; return ACTMI_E_INVALID; }
-    float* lut = workspace + conv1_ws_off_lut(C, Cout);
-    float* ones = lut + 768;
-    float* zeros = ones + (int64_t)C * Cout;
-    float* wimg = zeros + (int64_t)C * Cout;
-    wimg = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(wimg) + 15) & ~(uintptr_t)15);
-    int rc = launch_repack_conv_w(w_oihw, workspace, C, Cout, 3, 7, 7, (int64_t)Cout * 147, (int64_t)Cout * 148, 148, S(stream));
+    const Conv1Workspace ws(workspace, C, Cout);
+    int rc = launch_repack_conv_w(w_oihw, ws.w, C, Cout, 3, 7, 7, (int64_t)Cout * 147, (int64_t)Cout * 148, 148, S(stream));
     if (rc) return ACTMI_E_LAUNCH;
     std::vector<float> host(768 + 2 * (size_t)C * Cout);
     u8_lut(host.data(), lut_mode == 0);
     for (int i = 0; i < C * Cout; ++i) { host[768 + i] = 1.f; host[768 + C * Cout + i] = 0.f; }
-    if (hipMemcpyAsync(lut, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, S(stream)) != hipSuccess) return ACTMI_E_LAUNCH;
-    rc = launch_conv1_wimg(workspace, wimg, C, Cout, S(stream), 256.f);
+    if (hipMemcpyAsync(ws.lut, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, S(stream)) != hipSuccess) return ACTMI_E_LAUNCH;
+    rc = launch_conv1_wimg(ws.w, ws.wimg, C, Cout, S(stream), 256.f);
     if (rc) return ACTMI_E_LAUNCH;
     if (hipStreamSynchronize(S(stream)) != hipSuccess) return ACTMI_E_LAUNCH;
     return 0;
@@ -475,15 +483,11 @@ int actmi_op_conv1_prepared_ex(const void* image, int image_fmt, const float* wo
         return ACTMI_E_SHAPE;
     }
     if ((Cout & 3) == 0 && ((uintptr_t)out & 15)) { g_op_error = "conv1_prepared: out must be 16-byte aligned"; return ACTMI_E_SHAPE; }
-    const float* lut = workspace + conv1_ws_off_lut(C, Cout);
-    const float* ones = lut + 768;
-    const float* zeros = ones + (int64_t)C * Cout;
-    const float* wimg = zeros + (int64_t)C * Cout;
-    wimg = reinterpret_cast<const float*>((reinterpret_cast<uintptr_t>(wimg) + 15) & ~(uintptr_t)15);
+    const Conv1Workspace ws(workspace, C, Cout);
     Conv1Args a;
-    a.image = image; a.fmt = image_fmt; a.lut = lut; a.w = workspace; a.scale = scale ? scale : ones; a.bias = bias ? bias : zeros;
+    a.image = image; a.fmt = image_fmt; a.lut = ws.lut; a.w = ws.w; a.scale = scale ? scale : ws.ones; a.bias = bias ? bias : ws.zeros;
     a.out = out; a.B = B; a.C = C; a.H = H; a.W = W; a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1; a.Cout = Cout;
-    a.prec = prec; a.wimg = reinterpret_cast<const unsigned char*>(wimg); a.wscale = 256.f;
+    a.prec = prec; a.wimg = ws.wimg; a.wscale = 256.f;
     a.relu_floor = relu ? 0.f : -__builtin_inff();
     a.vpool = vpool ? 1 : 0; a.cam0 = cam0; a.ncam = ncam;
     const int rc = launch_conv1(a, S(stream), &g_op_error);

@@ -72,6 +72,14 @@ struct Conv1Args {
 int64_t conv1_wimg_bytes();
 int launch_conv1_wimg(const float* w, void* img, int C, int Cout, hipStream_t st, float wscale = 256.f);
 int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err);
+// grid of a stem kernel whose blocks are persistent over tiles: at most `cap` blocks (at least one), then no more blocks than
+// still give the busiest block as few tiles
+inline int balanced_grid(int tiles, int cap) {
+    if (cap < 1) cap = 1;
+    const int gx = tiles < cap ? tiles : cap;
+    const int per = (tiles + gx - 1) / gx;
+    return (tiles + per - 1) / per;
+}
 
 // ---- depth stem: conv1 7x7/s2, 1 -> Cout channels + FrozenBN + ReLU, fp32 products (conv1_depth.hip) ----
 // a depth batch as the forward was given it: f32 in about [0, 1], or raw u16 with the [B][2] table of its per-sample extremes

@@ -11,23 +11,44 @@
 // reading its A operand straight from the patch (im2col on the fly) and B from an LDS copy of the
 // camera's weights (row stride 149 floats: conflict-free).  Blocks are persistent over tiles so the 37 KB
 // weight image is staged once per block.
+//
+// Both kernels of this file stage their patch through conv1_loader.h: the tile decomposition and the per-thread fetch / commit
+// loops live there once; a kernel brings its patch-row count and a sink (how a value reaches its patch).
 #include "common.h"
-#include "conv1_u8_loader.h"
-#include <cstdlib>
+#include "conv1_loader.h"
 
 namespace {
 
+namespace ld = conv1_loader;
+using ld::TILE_P;                          // 64 output pixels per tile row, 133 input columns
 constexpr int KREAL = 147, KPAD = 148, WSTRIDE = 149;
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-constexpr int TILE_P = 64;                 // output pixels per tile
-constexpr int PCOLS = 2 * TILE_P + 5;      // 133 input columns
 constexpr int PSTRIDE = 400;               // floats per patch row (133*3 = 399, padded)
 constexpr int PROWS = 8;                   // 7 real rows + 1 zero row for the K pad
+constexpr int P_SMEM = (64 * WSTRIDE + 2 * PROWS * PSTRIDE + 3 * 256) * 4;
 
 __host__ __device__ constexpr int koff(int k) { return (k / 21) * PSTRIDE + (k % 21); }
 
-// number of per-thread staging registers: u8 rows are fetched as 4-byte words (7 rows x 101 words), f32 as scalars
-template <int FMT> struct StageN { static constexpr int value = (FMT == 0) ? 3 : 11; };
+// load(offset) of the loader's fetch() on image `img` of the launch ([B][C] layout of the caller): u8 words by byte offset
+// (a patch row is 399 consecutive bytes of the NHWC image), f32 elements of the NCHW image as their bits
+template <int FMT>
+__device__ __forceinline__ auto image_load(const Conv1Args& p, int64_t img) {
+    if constexpr (FMT == 0) {
+        const uint8_t* src = reinterpret_cast<const uint8_t*>(p.image) + img * (int64_t)p.H * p.W * 3;
+        return [src](int64_t o) { return *reinterpret_cast<const uint32_t*>(src + o); };
+    } else {
+        const float* src = reinterpret_cast<const float*>(p.image) + img * 3 * (int64_t)p.H * p.W;
+        return [src](int64_t o) { return __float_as_uint(src[o]); };
+    }
+}
+
+// how a value reaches conv1_kernel's patch: one float; the lookup table holds floats
+struct PatchF32 {
+    using value = float;
+    float* patch;
+    const float* lut;
+    __device__ float from_f32(float v) const { return v; }
+    __device__ void put(int r, int x, float v) const { patch[r * PSTRIDE + x] = v; }
+};
 
 template <int FMT>
 __global__ __launch_bounds__(256) void conv1_kernel(Conv1Args p, int tiles_per_row, int tiles_per_cam) {
@@ -49,8 +70,6 @@ __global__ __launch_bounds__(256) void conv1_kernel(Conv1Args p, int tiles_per_r
     }
     for (int e = t; e < 3 * 256; e += 256) s_lut[e] = (FMT == 0) ? p.lut[e] : 0.f;
     for (int e = t; e < 2 * PROWS * PSTRIDE; e += 256) (&s_patch[0][0])[e] = 0.f;
-    const float mean[3] = {0.485f, 0.456f, 0.406f};
-    const float stdv[3] = {0.229f, 0.224f, 0.225f};
     __syncthreads();
 
     const bool active = ntile * 32 < p.Cout;
@@ -61,85 +80,17 @@ __global__ __launch_bounds__(256) void conv1_kernel(Conv1Args p, int tiles_per_r
 
     // ---- staging of one tile's 7 x 133 x 3 patch, split in two phases so that the global loads of tile i+1 fly while the
     //      MFMAs of tile i run: fetch() issues the loads into registers, commit() normalises and writes LDS.
-    constexpr int NS = StageN<FMT>::value;
-    uint32_t sreg[NS];
-    auto tile_coords = [&](int tile, int& b, int& ho, int& wo0) {
-        b = tile / (p.Ho * tiles_per_row);
-        const int rem = tile - b * (p.Ho * tiles_per_row);
-        ho = rem / tiles_per_row;
-        wo0 = (rem - ho * tiles_per_row) * TILE_P;
-    };
+    ld::Staged<FMT, 7, 256> sreg;
+    auto tile_coords = [&](int tile, int& b, int& ho, int& wo0) { ld::tile_coords<1>(tile, p.Ho, tiles_per_row, b, ho, wo0); };
     auto fetch = [&](int tile) {
         int b, ho, wo0;
         tile_coords(tile, b, ho, wo0);
-        const int64_t img = (int64_t)b * p.C + cam;       // input image index ([B][C] layout of the caller)
-        const int hi0 = 2 * ho - 3, wi0 = 2 * wo0 - 3;
-        if (FMT == 0) {
-            // row r of the patch = 399 consecutive bytes starting at byte (hi*W + wi0)*3 of the image; fetched as
-            // 101 4-byte words (conv1_u8_loader.h: moved into the image; out-of-image bytes are discarded in commit())
-            const uint8_t* src = reinterpret_cast<const uint8_t*>(p.image) + img * (int64_t)p.H * p.W * 3;
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int e = t + 256 * i;
-                const int r = e / 101, j = e - r * 101;
-                uint32_t v = 0;
-                if (r < 7) {
-                    const conv1_u8::Slot sl = conv1_u8::slot(hi0 + r, wi0, j, p.H, p.W);
-                    if (sl.row_ok) v = *reinterpret_cast<const uint32_t*>(src + sl.wl);
-                }
-                sreg[i] = v;
-            }
-        } else {
-            const float* src = reinterpret_cast<const float*>(p.image) + img * 3 * (int64_t)p.H * p.W;
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int e = t + 256 * i;
-                const int rc = e / PCOLS, pc = e - rc * PCOLS;
-                const int r = rc / 3, c = rc - r * 3;
-                const int hi = hi0 + r, wi = wi0 + pc;
-                float v = 0.f;
-                if (e < 7 * 3 * PCOLS && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W)
-                    v = src[((int64_t)c * p.H + hi) * p.W + wi];
-                sreg[i] = __float_as_uint(v);
-            }
-        }
+        ld::fetch<FMT, 7, 256>(sreg, t, 2 * ho - 3, 2 * wo0 - 3, p.H, p.W, image_load<FMT>(p, (int64_t)b * p.C + cam));
     };
     auto commit = [&](int tile, float* patch) {
         int b, ho, wo0;
         tile_coords(tile, b, ho, wo0);
-        const int hi0 = 2 * ho - 3, wi0 = 2 * wo0 - 3;
-        if (FMT == 0) {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int e = t + 256 * i;
-                const int r = e / 101, j = e - r * 101;
-                if (r >= 7) continue;
-                const conv1_u8::Slot sl = conv1_u8::slot(hi0 + r, wi0, j, p.H, p.W);
-                const uint32_t word = sreg[i] >> conv1_u8::align_shift(sl);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    int x;
-                    bool in_image;
-                    if (!conv1_u8::byte_of(sl, k, wi0, p.W, x, in_image)) continue;
-                    float v = 0.f;
-                    if (in_image) v = s_lut[(x % 3) * 256 + ((word >> (8 * k)) & 0xFF)];
-                    patch[r * PSTRIDE + x] = v;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int e = t + 256 * i;
-                if (e >= 7 * 3 * PCOLS) continue;
-                const int rc = e / PCOLS, pc = e - rc * PCOLS;
-                const int r = rc / 3, c = rc - r * 3;
-                const int hi = hi0 + r, wi = wi0 + pc;
-                float v = 0.f;
-                if ((unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W)
-                    v = (__uint_as_float(sreg[i]) - mean[c]) / stdv[c];
-                patch[r * PSTRIDE + pc * 3 + c] = v;
-            }
-        }
+        ld::commit<FMT, 7, 256>(sreg, t, 2 * ho - 3, 2 * wo0 - 3, p.H, p.W, PatchF32{patch, s_lut});
     };
 
     int tile = blockIdx.x;
@@ -197,14 +148,14 @@ __global__ __launch_bounds__(256) void conv1_kernel(Conv1Args p, int tiles_per_r
 //   B     = this camera's weights x 2^8 (keeps the lo pieces normal fp16 numbers; undone in the epilogue scale) as
 //           [n][22 groups][8 halfs] hi | lo, row stride 368 B (conflict-free ds_read_b128).
 // 66 MFMAs of 32 cycles per wave and 128 output pixels, against 74 of 64 cycles per 64 pixels for the fp32 kernel.
-constexpr int F_TP = 64, F_ROWS = 2, F_PROWS = 2 * F_ROWS + 5;      // 9 input rows
+typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
+constexpr int F_ROWS = 2, F_PROWS = 2 * F_ROWS + 5;                // 9 input rows
 constexpr int F_RB = 816;                                          // bytes per half-row (408 halfs)
 constexpr int F_PATCH = F_PROWS * 2 * F_RB;                        // bytes per patch buffer
 constexpr int F_NG = 22;                                           // contraction groups incl. the zero one
 constexpr int F_WROW = 368;                                        // bytes per channel row of one weight piece
 constexpr int F_WBYTES = 64 * F_WROW;
 constexpr int F_SMEM = 2 * F_WBYTES + 2 * F_PATCH + 3 * 256 * 4;
-constexpr float F_WSCALE = 256.f;      // default of Conv1Args::wscale
 
 // 4x4 transpose across a quad of lanes: before, lane j of the quad holds (r0..r3) = row j; after, lane k holds column k
 // as (r0..r3) = (row0[k], row1[k], row2[k], row3[k]).  Two exchange stages on DPP quad permutes (no LDS traffic).
@@ -229,6 +180,19 @@ __device__ __forceinline__ uint32_t split1(float v) {              // (hi | lo <
     const _Float16 l = (_Float16)(v - (float)h);
     return (uint32_t)__builtin_bit_cast(uint16_t, h) | ((uint32_t)__builtin_bit_cast(uint16_t, l) << 16);
 }
+
+// how a value reaches conv1_f16x3_kernel's patch: the (hi, lo) halfs of a split word, to the two half-rows of its patch row;
+// the lookup table holds split words
+struct PatchF16x3 {
+    using value = uint32_t;
+    unsigned char* patch;
+    const uint32_t* lut;
+    __device__ uint32_t from_f32(float v) const { return split1(v); }
+    __device__ void put(int r, int x, uint32_t hl) const {
+        *reinterpret_cast<uint16_t*>(patch + r * 2 * F_RB + x * 2) = (uint16_t)(hl & 0xffffu);
+        *reinterpret_cast<uint16_t*>(patch + r * 2 * F_RB + F_RB + x * 2) = (uint16_t)(hl >> 16);
+    }
+};
 
 // one entry of the weight image: element e = (n, group gi = r*3+g, j) -> (hi, lo) halfs of w[n][r*21 + 8g + j] * 2^8
 __device__ __forceinline__ void conv1_wimg_entry(const float* wg, int Cout, int e, float wscale, uint16_t& h, uint16_t& l) {
@@ -285,8 +249,6 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
     }
     for (int e = t; e < 3 * 256; e += 256) s_lut[e] = (FMT == 0) ? split1(p.lut[e]) : 0u;
     for (int e = t; e < 2 * F_PATCH / 4; e += 256) reinterpret_cast<uint32_t*>(s_patch)[e] = 0u;
-    const float mean[3] = {0.485f, 0.456f, 0.406f};
-    const float stdv[3] = {0.229f, 0.224f, 0.225f};
     __syncthreads();
 
     float sc[2], bi[2];
@@ -297,89 +259,18 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
         bi[nt] = (n < p.Cout) ? p.bias[cam * p.Cout + n] : 0.f;
     }
 
-    constexpr int NS = (FMT == 0) ? (F_PROWS * 101 + 255) / 256 : (F_PROWS * 3 * PCOLS + 255) / 256;
-    uint32_t sreg[NS];
+    ld::Staged<FMT, F_PROWS, 256> sreg;
     const int hpairs = (p.Ho + F_ROWS - 1) / F_ROWS;
-    auto tile_coords = [&](int tile, int& b, int& ho0, int& wo0) {
-        b = tile / (hpairs * tiles_per_row);
-        const int rem = tile - b * (hpairs * tiles_per_row);
-        const int hp = rem / tiles_per_row;
-        ho0 = hp * F_ROWS;
-        wo0 = (rem - hp * tiles_per_row) * F_TP;
-    };
+    auto tile_coords = [&](int tile, int& b, int& ho0, int& wo0) { ld::tile_coords<F_ROWS>(tile, hpairs, tiles_per_row, b, ho0, wo0); };
     auto fetch = [&](int tile) {
         int b, ho0, wo0;
         tile_coords(tile, b, ho0, wo0);
-        const int64_t img = (int64_t)b * p.C + cam;
-        const int hi0 = 2 * ho0 - 3, wi0 = 2 * wo0 - 3;
-        if (FMT == 0) {
-            const uint8_t* src = reinterpret_cast<const uint8_t*>(p.image) + img * (int64_t)p.H * p.W * 3;
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int e = t + 256 * i;
-                const int r = e / 101, j = e - r * 101;
-                uint32_t v = 0;
-                if (r < F_PROWS) {
-                    const conv1_u8::Slot sl = conv1_u8::slot(hi0 + r, wi0, j, p.H, p.W);
-                    if (sl.row_ok) v = *reinterpret_cast<const uint32_t*>(src + sl.wl);
-                }
-                sreg[i] = v;
-            }
-        } else {
-            const float* src = reinterpret_cast<const float*>(p.image) + img * 3 * (int64_t)p.H * p.W;
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int e = t + 256 * i;
-                const int rc = e / PCOLS, pc = e - rc * PCOLS;
-                const int r = rc / 3, c = rc - r * 3;
-                const int hi = hi0 + r, wi = wi0 + pc;
-                float v = 0.f;
-                if (e < F_PROWS * 3 * PCOLS && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W)
-                    v = src[((int64_t)c * p.H + hi) * p.W + wi];
-                sreg[i] = __float_as_uint(v);
-            }
-        }
-    };
-    auto put = [&](unsigned char* patch, int r, int x, uint32_t hl) {
-        *reinterpret_cast<uint16_t*>(patch + r * 2 * F_RB + x * 2) = (uint16_t)(hl & 0xffffu);
-        *reinterpret_cast<uint16_t*>(patch + r * 2 * F_RB + F_RB + x * 2) = (uint16_t)(hl >> 16);
+        ld::fetch<FMT, F_PROWS, 256>(sreg, t, 2 * ho0 - 3, 2 * wo0 - 3, p.H, p.W, image_load<FMT>(p, (int64_t)b * p.C + cam));
     };
     auto commit = [&](int tile, unsigned char* patch) {
         int b, ho0, wo0;
         tile_coords(tile, b, ho0, wo0);
-        const int hi0 = 2 * ho0 - 3, wi0 = 2 * wo0 - 3;
-        if (FMT == 0) {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int e = t + 256 * i;
-                const int r = e / 101, j = e - r * 101;
-                if (r >= F_PROWS) continue;
-                const conv1_u8::Slot sl = conv1_u8::slot(hi0 + r, wi0, j, p.H, p.W);
-                const uint32_t word = sreg[i] >> conv1_u8::align_shift(sl);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    int x;
-                    bool in_image;
-                    if (!conv1_u8::byte_of(sl, k, wi0, p.W, x, in_image)) continue;
-                    uint32_t hl = 0u;
-                    if (in_image) hl = s_lut[(x % 3) * 256 + ((word >> (8 * k)) & 0xFF)];
-                    put(patch, r, x, hl);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int e = t + 256 * i;
-                if (e >= F_PROWS * 3 * PCOLS) continue;
-                const int rc = e / PCOLS, pc = e - rc * PCOLS;
-                const int r = rc / 3, c = rc - r * 3;
-                const int hi = hi0 + r, wi = wi0 + pc;
-                float v = 0.f;
-                if ((unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W)
-                    v = (__uint_as_float(sreg[i]) - mean[c]) / stdv[c];
-                put(patch, r, pc * 3 + c, split1(v));
-            }
-        }
+        ld::commit<FMT, F_PROWS, 256>(sreg, t, 2 * ho0 - 3, 2 * wo0 - 3, p.H, p.W, PatchF16x3{patch, s_lut});
     };
 
     // Tile walk.  Plain mode: tiles blockIdx.x, +gridDim.x, ... in any order.  vpool mode (inference): a workgroup owns a
@@ -436,10 +327,9 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
 #pragma unroll
             for (int s = 0; s < 11; ++s) {
                 // this lane half's contraction group 2s+lh -> (filter row, 8-wide window); the 22nd group has zero weights
-                constexpr int NOFF = 0;
                 const int g0 = 2 * s, g1 = (2 * s + 1 < 21) ? 2 * s + 1 : 20;
                 const int off0 = (g0 / 3) * 2 * F_RB + (g0 % 3) * 16, off1 = (g1 / 3) * 2 * F_RB + (g1 % 3) * 16;
-                const unsigned char* ap = abase + (lh ? off1 : off0) + NOFF;
+                const unsigned char* ap = abase + (lh ? off1 : off0);
                 uint4 ah, al;
                 ah.x = *reinterpret_cast<const uint32_t*>(ap + 0);  ah.y = *reinterpret_cast<const uint32_t*>(ap + 4);
                 ah.z = *reinterpret_cast<const uint32_t*>(ap + 8);  ah.w = *reinterpret_cast<const uint32_t*>(ap + 12);
@@ -544,70 +434,50 @@ int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err) {
         if (err) *err = "conv1: camera range outside 0..C (ncam = 0 means all C cameras from cam0 = 0)";
         return -2;
     }
-    if (a.fmt == 0 && !conv1_u8::frame_ok((int64_t)a.H * a.W * 3)) {
+    if (a.fmt == 0 && !ld::frame_ok((int64_t)a.H * a.W * 3)) {
         if (err) *err = "conv1: a u8 frame needs at least 4 bytes (the loader fetches whole words inside the image)";
         return -2;
     }
     static const int env_prec = env_gemm_prec(ACTMI_PREC_F32);
-    const int prec = a.prec ? a.prec : env_prec;
-    if (prec == ACTMI_PREC_F16X3) {
-        const int tiles_per_row = (a.Wo + F_TP - 1) / F_TP;
-        const int tiles_per_cam = a.B * ((a.Ho + F_ROWS - 1) / F_ROWS) * tiles_per_row;
-        constexpr int blocks_target = 512;   // measured best at B = 1, 2, 8 against 256, 1024 and 2048 (commit 3680fa5)
-        int cap = blocks_target / (a.C > 0 ? a.C : 1);
-        if (cap < 1) cap = 1;
-        int gx = tiles_per_cam < cap ? tiles_per_cam : cap;
-        const int per = (tiles_per_cam + gx - 1) / gx;
-        gx = (tiles_per_cam + per - 1) / per;
-        Conv1Args av = a;
-        if (a.vpool) {
-            if ((a.Ho & 1) || (a.Cout & 3)) { if (err) *err = "conv1: vpool needs an even output height and Cout % 4 == 0"; return -2; }
-            const int hpairs = a.Ho / 2;
-            const int nc_l = a.ncam > 0 ? a.ncam : a.C;
-            int nseg = blocks_target / (nc_l * a.B * tiles_per_row > 0 ? nc_l * a.B * tiles_per_row : 1);
-            if (nseg > hpairs / 4) nseg = hpairs / 4;            // chains of >= 4 row pairs (+1 halo step); only B = 1 gets there
-            if (nseg < 1) nseg = 1;
-            av.vpool_nseg = nseg;
-            gx = a.B * tiles_per_row * nseg;
-        }
-        dim3 grid(gx, a.ncam > 0 ? a.ncam : a.C);
-        prof_begin(a.fmt == 0 ? "conv1_f16x3_kernel<0>" : "conv1_f16x3_kernel<1>", 2.0 * a.B * a.C * a.Ho * a.Wo * a.Cout * 147.0,
-                   (double)a.B * a.C * ((double)a.H * a.W * 3 * (a.fmt == 0 ? 1 : 4) + 4.0 * a.Ho * a.Wo * a.Cout), st);
-        static bool attr16 = false;
-        if (!attr16) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, F_SMEM) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, F_SMEM) != hipSuccess) {
+    const bool f16 = (a.prec ? a.prec : env_prec) == ACTMI_PREC_F16X3;
+    if (a.vpool && !f16) { if (err) *err = "conv1: vpool needs prec f16x3"; return -2; }
+    // the two precisions differ in tile geometry, LDS size and kernel
+    struct Form {
+        void (*kernel[2])(Conv1Args, int, int);     // by input format
+        const char* name[2];
+        int rows, smem;                             // output rows per tile, dynamic LDS bytes
+        bool lds_raised;
+    };
+    static Form forms[2] = {{{conv1_kernel<0>, conv1_kernel<1>}, {"conv1_kernel<0>", "conv1_kernel<1>"}, 1, P_SMEM, false},
+                            {{conv1_f16x3_kernel<0>, conv1_f16x3_kernel<1>}, {"conv1_f16x3_kernel<0>", "conv1_f16x3_kernel<1>"}, F_ROWS, F_SMEM, false}};
+    Form& form = forms[f16];
+    const int fmt = a.fmt == 0 ? 0 : 1, ncam = a.ncam > 0 ? a.ncam : a.C;
+    const int tiles_per_row = (a.Wo + TILE_P - 1) / TILE_P;
+    const int tiles_per_cam = a.B * ((a.Ho + form.rows - 1) / form.rows) * tiles_per_row;
+    // 512 blocks measured best at B = 1, 2, 8 against 256, 1024 and 2048 (commit 3680fa5): over all cameras for f16x3, per camera for fp32
+    constexpr int blocks_target = 512;
+    int gx = balanced_grid(tiles_per_cam, f16 ? blocks_target / (a.C > 0 ? a.C : 1) : blocks_target);
+    Conv1Args av = a;
+    if (a.vpool) {
+        if ((a.Ho & 1) || (a.Cout & 3)) { if (err) *err = "conv1: vpool needs an even output height and Cout % 4 == 0"; return -2; }
+        const int hpairs = a.Ho / 2;
+        int nseg = blocks_target / (ncam * a.B * tiles_per_row > 0 ? ncam * a.B * tiles_per_row : 1);
+        if (nseg > hpairs / 4) nseg = hpairs / 4;            // chains of >= 4 row pairs (+1 halo step); only B = 1 gets there
+        if (nseg < 1) nseg = 1;
+        av.vpool_nseg = nseg;
+        gx = a.B * tiles_per_row * nseg;
+    }
+    if (!form.lds_raised) {
+        for (auto k : form.kernel)
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, form.smem) != hipSuccess) {
                 if (err) *err = "conv1: cannot raise the dynamic LDS limit";
                 return -3;
             }
-            attr16 = true;
-        }
-        if (a.fmt == 0) hipLaunchKernelGGL(conv1_f16x3_kernel<0>, grid, dim3(256), F_SMEM, st, av, tiles_per_row, tiles_per_cam);
-        else hipLaunchKernelGGL(conv1_f16x3_kernel<1>, grid, dim3(256), F_SMEM, st, av, tiles_per_row, tiles_per_cam);
-    } else {
-    if (a.vpool) { if (err) *err = "conv1: vpool needs prec f16x3"; return -2; }
-    const int tiles_per_row = (a.Wo + TILE_P - 1) / TILE_P;
-    const int tiles_per_cam = a.B * a.Ho * tiles_per_row;
-    int gx = tiles_per_cam < 512 ? tiles_per_cam : 512;
-    // keep tiles-per-block balanced
-    const int per = (tiles_per_cam + gx - 1) / gx;
-    gx = (tiles_per_cam + per - 1) / per;
-    dim3 grid(gx, a.ncam > 0 ? a.ncam : a.C);
-    prof_begin(a.fmt == 0 ? "conv1_kernel<0>" : "conv1_kernel<1>", 2.0 * a.B * a.C * a.Ho * a.Wo * a.Cout * 147.0,
-               (double)a.B * a.C * ((double)a.H * a.W * 3 * (a.fmt == 0 ? 1 : 4) + 4.0 * a.Ho * a.Wo * a.Cout), st);
-    constexpr int smem = (64 * WSTRIDE + 2 * PROWS * PSTRIDE + 3 * 256) * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-            if (err) *err = "conv1: cannot raise the dynamic LDS limit";
-            return -3;
-        }
-        attr_set = true;
+        form.lds_raised = true;
     }
-    if (a.fmt == 0) hipLaunchKernelGGL(conv1_kernel<0>, grid, dim3(256), smem, st, a, tiles_per_row, tiles_per_cam);
-    else hipLaunchKernelGGL(conv1_kernel<1>, grid, dim3(256), smem, st, a, tiles_per_row, tiles_per_cam);
-    }
+    prof_begin(form.name[fmt], 2.0 * a.B * a.C * a.Ho * a.Wo * a.Cout * 147.0,
+               (double)a.B * a.C * ((double)a.H * a.W * 3 * (fmt == 0 ? 1 : 4) + 4.0 * a.Ho * a.Wo * a.Cout), st);
+    hipLaunchKernelGGL(form.kernel[fmt], dim3(gx, ncam), dim3(256), form.smem, st, av, tiles_per_row, tiles_per_cam);
     prof_end(st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { if (err) *err = std::string("conv1 launch: ") + hipGetErrorString(e); return -3; }

@@ -20,13 +20,17 @@
 // GEMM is laid out channels x pixels, so a lane ends up with 4 consecutive channels of one pixel: the tile leaves through LDS
 // ([pixel][Cout + 4]: conflict-free 16-byte writes) and goes to memory as one contiguous run of 64 * Cout floats, 16 bytes
 // per lane, 1 KB per wave and store instruction.
+//
+// The tile decomposition is the RGB stem's (conv1_loader.h, one output row per tile); the loader itself -- one channel, even / odd
+// column split, u16 normalisation -- is this kernel's own.
 #include "common.h"
+#include "conv1_loader.h"
 
 namespace {
 
 constexpr int D_K = 49, D_KPAD = 50, D_WS = 51;    // taps, padded contraction, LDS row stride of the weights (odd: conflict-free)
-constexpr int D_TP = 64;                           // output pixels per tile
-constexpr int D_PCOLS = 2 * D_TP + 5;              // 133 input columns
+constexpr int D_TP = conv1_loader::TILE_P;         // 64 output pixels per tile
+constexpr int D_PCOLS = conv1_loader::PATCH_COLS;  // 133 input columns
 constexpr int D_PH = 68;                           // a patch row holds its even columns, then its odd columns (68 floats each):
 constexpr int D_PS = 2 * D_PH;                     // the 32 pixels of a half-wave read consecutive floats, whatever the tap
 constexpr int D_PROWS = 8;                         // 7 real rows + 1 zero row for the K pad
@@ -65,18 +69,12 @@ __global__ __launch_bounds__(256) void conv1_depth_kernel(Conv1DepthArgs p, int 
     for (int e = t; e < 2 * D_PROWS * D_PS; e += 256) (&s_patch[0][0])[e] = 0.f;
     __syncthreads();
 
-    auto tile_coords = [&](int tile, int& b, int& ho, int& wo0) {
-        b = tile / (p.Ho * tiles_per_row);
-        const int rem = tile - b * (p.Ho * tiles_per_row);
-        ho = rem / tiles_per_row;
-        wo0 = (rem - ho * tiles_per_row) * D_TP;
-    };
     Staged sreg[D_NS];
     float lo = 0.f, den = 1.f;                              // RAW: the fetched tile's sample minimum and (max - min) + 1e-6
     // the tile's patch: fetch() issues the loads, commit() normalises ((d - 0.5) / 0.5, zero outside the image) and writes LDS
     auto fetch = [&](int tile) {
         int b, ho, wo0;
-        tile_coords(tile, b, ho, wo0);
+        conv1_loader::tile_coords<1>(tile, p.Ho, tiles_per_row, b, ho, wo0);
         const T* src = static_cast<const T*>(p.depth) + ((int64_t)b * p.Cd + cam) * (int64_t)p.H * p.W;
         if constexpr (RAW) {
             lo = p.lohi[2 * b];
@@ -120,7 +118,7 @@ __global__ __launch_bounds__(256) void conv1_depth_kernel(Conv1DepthArgs p, int 
         const bool has_next = next < tiles_per_cam;
         if (has_next) fetch(next);
         int b, ho, wo0;
-        tile_coords(tile, b, ho, wo0);
+        conv1_loader::tile_coords<1>(tile, p.Ho, tiles_per_row, b, ho, wo0);
         if (active) {
             const float* b_base = s_patch[cur] + ptile * 32 + li;
             f32x16 acc;
@@ -289,11 +287,7 @@ int launch_conv1_depth(const Conv1DepthArgs& a, hipStream_t st, std::string* err
     const int64_t tiles = (int64_t)a.B * a.Ho * tiles_per_row;
     if (tiles > 0x7fffffff) { if (err) *err = "conv1_depth: too many tiles"; return -2; }
     const int tiles_per_cam = (int)tiles;
-    int cap = 1024 / a.Cd;                                 // 4 resident blocks per CU (38 KB of LDS each) on 256 CUs
-    if (cap < 1) cap = 1;
-    int gx = tiles_per_cam < cap ? tiles_per_cam : cap;
-    const int per = (tiles_per_cam + gx - 1) / gx;         // keep tiles-per-block balanced
-    gx = (tiles_per_cam + per - 1) / per;
+    const int gx = balanced_grid(tiles_per_cam, 1024 / a.Cd);     // 4 resident blocks per CU (38 KB of LDS each) on 256 CUs
     prof_begin(a.src_u16 ? "conv1_depth_u16_kernel" : "conv1_depth_kernel", 2.0 * a.B * a.Cd * a.Ho * a.Wo * a.Cout * 49.0,
                (double)a.B * a.Cd * ((a.src_u16 ? 2.0 : 4.0) * a.H * a.W + 4.0 * a.Ho * a.Wo * a.Cout), st);
     if (a.src_u16) hipLaunchKernelGGL(conv1_depth_kernel<uint16_t>, dim3(gx, a.Cd), dim3(256), 0, st, a, tiles_per_row, tiles_per_cam);

@@ -23,7 +23,7 @@ error with the bound.
 
 Worst errors measured on an MI355X (bound 2e-6): a. 6.8e-7 (fp32 kernel, 30 x 43), 3.0e-7 f16x3; b. 4.0e-7; c. 4.0e-7;
 d. 3.5e-7 prepared, 3.7e-7 without normalisation / ReLU; e. / f. plain outputs 3.9e-7, everything else bit-equal.  With the
-tail word rounded down to a multiple of 4 (the loader before conv1_u8_loader.h) all ten cases of (a) fail in both kernels: u8
+tail word rounded down to a multiple of 4 (the loader before conv1_loader.h's tail-word rule) all ten cases of (a) fail in both kernels: u8
 against float64 9.5e-2 (7 x 9), 1.4e-1 (30 x 43), 2.3e-1 (13 x 17), 7.2e-2 (35 x 150), every time in the bottom-right corner,
 with the f32 input form unchanged.
 """
