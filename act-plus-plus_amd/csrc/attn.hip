@@ -24,6 +24,13 @@ namespace {
 // three waves spill).
 constexpr bool ATTN_NOPF = true;
 constexpr int KT = 64;   // keys per LDS tile
+// f16x3 kernel: fixed power-of-two up-scales of q * scale * log2(e) and of v before their split (see the kernel's header)
+constexpr float Q_UP = 4.f, V_UP = 16.f;
+
+// two packed half pairs -> the pair of their low halfs / of their high halfs, one v_perm_b32 each (selector bytes 0-3 name the bytes
+// of the second source, 4-7 those of the first)
+__device__ __forceinline__ uint32_t pack_lo16(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }   // (a & 0xffff) | (b << 16)
+__device__ __forceinline__ uint32_t pack_hi16(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }   // (a >> 16) | (b & 0xffff0000)
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 
 // XCD-aware block order: the hardware deals consecutive block ids round-robin over the 8 XCDs (each with its own 4 MB L2), so
@@ -239,8 +246,22 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(AttnArgs p, int nsplit, i
 // (rows (e&3) + 8(e>>2) + 4*half) are 16 contiguous bytes: the probabilities go from accumulator registers straight
 // into the B operand of the second product, as in the fp32 kernel.  A 32-key step is 24 MFMAs of 32 cycles per wave
 // (768) against 64 of 64 cycles (4096) for the fp32 instruction.
+// The probabilities are split too, and the lo piece of the split is a NORMAL fp16 number only down to about 2^-2 of the
+// largest representable scale: with P = 2^(S - max) <= 1 every weight below 2^-2 carried the absolute error 2^-25 of the
+// subnormal grid, which shows as soon as the largest-weight key does not dominate the output (an attention sink with a
+// small value vector: errors of 1e-4 .. 6e-3 at a score margin of 10 .. 14).  So the running reference of the online
+// softmax is kept `pbias` BELOW the running maximum, m' = max - pbias: P = 2^(S - m') <= 2^pbias, and l, O carry the same
+// factor, which cancels in O / l; alpha, the (m', l) pair of a partial result and the combine pass use m' as they used the
+// maximum (any reference is exact as long as it is the same one everywhere).  Only the log-sum-exp takes the bias out
+// again, so that it is not formed as the difference of two numbers pbias * ln 2 larger than itself.  pbias is chosen per
+// launch (attn_p_bias below).
+// q and v get fixed up-scales for the same reason, the lo piece of an element below 2^-2 being subnormal: q * scale * log2(e)
+// (0.18 .. 0.36 of q) is split at Q_UP = 4, and the exponent's subtraction becomes the multiply-add S / Q_UP - m' (exact, no
+// instruction more); v is split at V_UP = 16 and O gives the factor back where it is written.  The operand window of the
+// kernel is then |q| * scale * log2(e) < 16376 and |v| < 4094 (above: fp16 overflow), with the absolute floor of the split at
+// 2^-27 for q * scale * log2(e), 2^-29 for v and 2^-25 for k.
 template <int HD>
-__global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nsplit, int chunk) {
+__global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nsplit, int chunk, float pbias) {
     constexpr int NS = HD / 16;           // 16-deep steps of the QK^T contraction
     constexpr int DT = (HD + 31) / 32;    // 32-wide output tiles along d
     constexpr int VD = DT * 32;
@@ -268,7 +289,7 @@ __global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nspl
     for (int s = 0; s < NS; ++s) {
         f32x4 v0 = *reinterpret_cast<const f32x4*>(Qp + s * 16);
         f32x4 v1 = *reinterpret_cast<const f32x4*>(Qp + s * 16 + 4);
-        const float sc = qok ? qscale : 0.f;
+        const float sc = qok ? qscale * Q_UP : 0.f;
         v0 *= sc; v1 *= sc;
         uint2 h0, l0, h1, l1;
         split16(v0, h0, l0);
@@ -285,7 +306,7 @@ __global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nspl
     for (int d = 0; d < DT; ++d)
 #pragma unroll
         for (int e = 0; e < 16; ++e) O[d][e] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
+    float m_run = -INFINITY, l_run = 0.f, smax_run = -INFINITY;     // smax_run: the running maximum of S as accumulated (it carries Q_UP)
 
     if (HD < VD) {      // d rows beyond the head dim contribute zeros
         for (int e = t; e < VD * VROW / 4; e += 256) reinterpret_cast<uint32_t*>(s_vt)[e] = 0u;
@@ -323,7 +344,9 @@ __global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nspl
                 const int key = kt0 + 2 * kp + u;
                 const bool ok = e < KT / 2 * C4 && key < k_end;
                 const f32x4 vv = *reinterpret_cast<const f32x4*>(Vb + (ok ? (int64_t)key * p.v_rs + c * 4 : 0));
-                pv[i][u] = ok ? vv : z;
+                // one multiply scales the row and zeroes a row beyond the key range (the address of such a row is row 0's, whose
+                // values take part in the product anyway: a non-finite value there reaches the output with or without this)
+                pv[i][u] = vv * (ok ? V_UP : 0.f);
             }
         }
     };
@@ -354,14 +377,14 @@ __global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nspl
                 const int pos = (kl & ~15) | (r & 3) | ((r & 8) >> 1) | ((r & 4) << 1);      // permuted key slot (even)
                 unsigned char* dst = s_vt + (c * 4) * VROW + pos * 2;
                 // d = 4c+j: low half = key 2kp, high half = key 2kp+1
-                *reinterpret_cast<uint32_t*>(dst + 0 * VROW) = (ha.x & 0xffffu) | (hb.x << 16);
-                *reinterpret_cast<uint32_t*>(dst + 1 * VROW) = (ha.x >> 16) | (hb.x & 0xffff0000u);
-                *reinterpret_cast<uint32_t*>(dst + 2 * VROW) = (ha.y & 0xffffu) | (hb.y << 16);
-                *reinterpret_cast<uint32_t*>(dst + 3 * VROW) = (ha.y >> 16) | (hb.y & 0xffff0000u);
-                *reinterpret_cast<uint32_t*>(dst + 0 * VROW + 2 * KT) = (la.x & 0xffffu) | (lb.x << 16);
-                *reinterpret_cast<uint32_t*>(dst + 1 * VROW + 2 * KT) = (la.x >> 16) | (lb.x & 0xffff0000u);
-                *reinterpret_cast<uint32_t*>(dst + 2 * VROW + 2 * KT) = (la.y & 0xffffu) | (lb.y << 16);
-                *reinterpret_cast<uint32_t*>(dst + 3 * VROW + 2 * KT) = (la.y >> 16) | (lb.y & 0xffff0000u);
+                *reinterpret_cast<uint32_t*>(dst + 0 * VROW) = pack_lo16(ha.x, hb.x);
+                *reinterpret_cast<uint32_t*>(dst + 1 * VROW) = pack_hi16(ha.x, hb.x);
+                *reinterpret_cast<uint32_t*>(dst + 2 * VROW) = pack_lo16(ha.y, hb.y);
+                *reinterpret_cast<uint32_t*>(dst + 3 * VROW) = pack_hi16(ha.y, hb.y);
+                *reinterpret_cast<uint32_t*>(dst + 0 * VROW + 2 * KT) = pack_lo16(la.x, lb.x);
+                *reinterpret_cast<uint32_t*>(dst + 1 * VROW + 2 * KT) = pack_hi16(la.x, lb.x);
+                *reinterpret_cast<uint32_t*>(dst + 2 * VROW + 2 * KT) = pack_lo16(la.y, lb.y);
+                *reinterpret_cast<uint32_t*>(dst + 3 * VROW + 2 * KT) = pack_hi16(la.y, lb.y);
             }
         }
         const bool ragged = kt0 + KT > k_end || kpm != nullptr;    // block-uniform: masking only where needed
@@ -401,18 +424,21 @@ __global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nspl
 #pragma unroll
                 for (int e = 1; e < 16; ++e) mt = fmaxf(mt, S[e]);
                 mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-                const float m_new = fmaxf(m_run, mt);
+                // the row reference, pbias below the maximum: P <= 2^pbias.  S carries Q_UP; the multiply-adds take it out exactly
+                const float smax_new = fmaxf(smax_run, mt);
+                const float m_new = fmaf(smax_new, 1.f / Q_UP, -pbias);
                 const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
                 const float alpha = __builtin_amdgcn_exp2f(m_run - m_safe);
                 float rs = 0.f;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    S[e] = __builtin_amdgcn_exp2f(S[e] - m_safe);
+                    S[e] = __builtin_amdgcn_exp2f(fmaf(S[e], 1.f / Q_UP, -m_safe));
                     rs += S[e];
                 }
                 rs += __shfl_xor(rs, 32, 64);
                 l_run = l_run * alpha + rs;          // the normaliser uses the UN-dropped weights
                 m_run = m_new;
+                smax_run = smax_new;
                 if (p.drop_p > 0.f) {
                     const float ds = 1.f / (1.f - p.drop_p);
                     const uint64_t rowbase = (((uint64_t)b * p.H + h) * p.Nq + (qok ? q : 0)) * (uint64_t)p.Nk;
@@ -455,7 +481,7 @@ __global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nspl
     }
     if (qok) {
         if (nsplit == 1) {
-            const float inv = 1.f / l_run;
+            const float inv = (1.f / V_UP) / l_run;
             float* Op = p.O + (int64_t)b * p.o_bs + (int64_t)q * p.o_rs + h * HD;
 #pragma unroll
             for (int d = 0; d < DT; ++d)
@@ -467,9 +493,10 @@ __global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nspl
                         *reinterpret_cast<f32x4*>(Op + d0) = o;
                     }
                 }
-            if (p.lse && lh == 0) p.lse[((int64_t)b * p.H + h) * p.Nq + q] = m_run * 0.6931471805599453f + logf(l_run);
+            if (p.lse && lh == 0)          // m_run + pbias is the maximum again, l_run * 2^-pbias (exact) the sum relative to it
+                p.lse[((int64_t)b * p.H + h) * p.Nq + q] = (m_run + pbias) * 0.6931471805599453f + logf(l_run * __builtin_amdgcn_exp2f(-pbias));
         } else {
-            // partial result of this key range: un-normalised O plus (running max, running sum)
+            // partial result of this key range: un-normalised O plus (running reference m', running sum), all relative to m'
             const int64_t row = (((int64_t)split * p.B + b) * p.H + h) * p.Nq + q;
             float* Op = p.ws + row * HD;
             float* ml = p.ws + (int64_t)nsplit * p.B * p.H * p.Nq * HD + row * 2;
@@ -480,6 +507,7 @@ __global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nspl
                     const int d0 = d * 32 + 8 * g + 4 * lh;
                     if (d0 < HD) {
                         f32x4 o = {O[d][4 * g], O[d][4 * g + 1], O[d][4 * g + 2], O[d][4 * g + 3]};
+                        o *= 1.f / V_UP;
                         *reinterpret_cast<f32x4*>(Op + d0) = o;
                     }
                 }
@@ -489,8 +517,9 @@ __global__ __launch_bounds__(256, 3) void attn_f16x3_kernel(AttnArgs p, int nspl
 }
 
 
-// merge the nsplit partial results: m = max m_s, L = sum l_s 2^(m_s - m), O = sum O_s 2^(m_s - m) / L
-__global__ void attn_combine_kernel(AttnArgs p, int nsplit, int HD) {
+// merge the nsplit partial results: m = max m_s, L = sum l_s 2^(m_s - m), O = sum O_s 2^(m_s - m) / L.  The f16x3 partials are
+// relative to a reference pbias below their maximum (0 for the fp32 kernel): O / L does not see it, the log-sum-exp takes it out
+__global__ void attn_combine_kernel(AttnArgs p, int nsplit, int HD, float pbias) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;          // over (b, h, q, d4)
     const int D4 = HD / 4;
     const int64_t total = (int64_t)p.B * p.H * p.Nq * D4;
@@ -514,7 +543,20 @@ __global__ void attn_combine_kernel(AttnArgs p, int nsplit, int HD) {
     }
     const float inv = 1.f / L;
     *reinterpret_cast<f32x4*>(p.O + (int64_t)b * p.o_bs + (int64_t)q * p.o_rs + h * HD + d4 * 4) = acc * inv;
-    if (p.lse && d4 == 0) p.lse[bhq] = msafe * 0.6931471805599453f + logf(L);
+    if (p.lse && d4 == 0) p.lse[bhq] = (msafe + pbias) * 0.6931471805599453f + logf(L * __builtin_amdgcn_exp2f(-pbias));
+}
+
+// Exponent bias of the f16x3 probabilities: the largest split value is 2^pbias / (1 - drop_p) (a kept weight of the row's largest
+// key under the weight dropout) and must stay a finite fp16 number (< 65504; 65000 leaves room for the rounding of m' = max - pbias
+// and of v_exp_f32), and the larger pbias the further down the lo piece of a weight stays a normal fp16 number (weights down to
+// 2^-(pbias + 2) of the row's largest).  So: the largest integer <= 15 that holds the first constraint -- 15 without dropout and
+// up to p = 0.49, 14 at 0.5, 12 at 0.9.  -1: no bias holds it (drop_p above 0.99998, or not below 1): the launch is refused.
+int attn_p_bias(float drop_p) {
+    if (!(drop_p < 1.f)) return -1;
+    const float ds = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+    int b = 15;
+    while (b >= 0 && ldexpf(ds, b) > 65000.f) --b;
+    return b;
 }
 
 }  // namespace
@@ -534,6 +576,9 @@ int launch_attention(const AttnArgs& a, hipStream_t st, std::string* err) {
     const int prec = a.prec ? a.prec : env_prec;
     if (prec != ACTMI_PREC_F32 && prec != ACTMI_PREC_F16X3) return fail("bad prec");
     const bool f16 = prec == ACTMI_PREC_F16X3;
+    const int pbias_i = f16 ? attn_p_bias(a.drop_p) : 0;
+    if (pbias_i < 0) return fail("drop_p must be below 0.99998 for prec f16x3 (the kept weights are split into fp16 pieces)");
+    const float pbias = (float)pbias_i;
     const int qblocks = (a.Nq + 127) / 128;
     const int tiles = (a.Nk + KT - 1) / KT;
     int nsplit = 1;
@@ -557,9 +602,9 @@ int launch_attention(const AttnArgs& a, hipStream_t st, std::string* err) {
     }
     if (f16) {
         switch (a.HD) {
-            case 64: hipLaunchKernelGGL(attn_f16x3_kernel<64>, grid, dim3(256), 0, st, a, nsplit, chunk); break;
-            case 32: hipLaunchKernelGGL(attn_f16x3_kernel<32>, grid, dim3(256), 0, st, a, nsplit, chunk); break;
-            case 16: hipLaunchKernelGGL(attn_f16x3_kernel<16>, grid, dim3(256), 0, st, a, nsplit, chunk); break;
+            case 64: hipLaunchKernelGGL(attn_f16x3_kernel<64>, grid, dim3(256), 0, st, a, nsplit, chunk, pbias); break;
+            case 32: hipLaunchKernelGGL(attn_f16x3_kernel<32>, grid, dim3(256), 0, st, a, nsplit, chunk, pbias); break;
+            case 16: hipLaunchKernelGGL(attn_f16x3_kernel<16>, grid, dim3(256), 0, st, a, nsplit, chunk, pbias); break;
             default: return fail("head_dim must be 16, 32 or 64");
         }
     } else
@@ -571,7 +616,7 @@ int launch_attention(const AttnArgs& a, hipStream_t st, std::string* err) {
     }
     if (nsplit > 1) {
         const int64_t total = (int64_t)a.B * a.H * a.Nq * (a.HD / 4);
-        hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, nsplit, a.HD);
+        hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, nsplit, a.HD, pbias);
     }
     prof_end(st);
     hipError_t e = hipGetLastError();

@@ -202,10 +202,12 @@ typedef struct actmi_attn_desc {
      * nsplit * B * Nq * (H*HD + 2*H); ws = NULL disables splitting. */
     float* ws;
     int64_t ws_floats;
-    /* dropout on the attention weights (nn.MultiheadAttention dropout): mask = f(drop_seed, ((b*H+h)*Nq+q)*Nk+key) */
+    /* dropout on the attention weights (nn.MultiheadAttention dropout): mask = f(drop_seed, ((b*H+h)*Nq+q)*Nk+key).
+     * Under f16x3 the kept weights, times 1/(1-drop_p), are split into fp16 pieces: drop_p above 0.99998 is rejected */
     float drop_p;
     uint64_t drop_seed;
-    /* product precision, as in actmi_gemm_desc.prec (0 = ACTMI_GEMM_PREC from the environment, else native fp32) */
+    /* product precision, as in actmi_gemm_desc.prec (0 = ACTMI_GEMM_PREC from the environment, else native fp32).
+     * f16x3 operand window: |q| * scale * log2(e) < 16376, |v| < 4094 */
     int32_t prec;
     /* 1: causal mask, key j visible to query i only for j <= i (needs Nq == Nk) */
     int32_t causal;

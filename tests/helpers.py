@@ -275,3 +275,125 @@ def run_gemm(what, **kw):
     from actmi import lib as L
     desc = gemm_desc(**kw)
     L.check(L.load().actmi_op_gemm(C.byref(desc), L.current_stream_ptr()), None, what)
+
+
+# ---- the fp16 operand split of csrc/split16.h and the operand rounding of attn_f16x3_kernel (csrc/attn.hip), modelled on the
+#      CPU; test_kernel_refs_cpu.py proves that the sink cases of test_gpu_attention_envelope.py bite --------------------------
+LOG2E = 1.4426950408889634
+
+
+def split16_model(x):
+    """(hi, lo) of split16: hi = rn16(x), lo = rn16(x - hi), both fp16 with subnormals kept (torch's CPU conversion rounds to
+    nearest even and keeps them, as v_cvt_f16_f32 does with denormals on)"""
+    x = x.float()
+    hi = x.half()
+    return hi, (x - hi.float()).half()
+
+
+def prod3_model(ah, al, bh, bl):
+    """the three kept products of two split operands, hi hi + hi lo + lo hi (lo lo dropped), contracted over the last axis
+    of a and the first of b^T in float64: the exact sum the fp16 MFMAs accumulate, before any fp32 accumulation rounding"""
+    ah, al, bh, bl = (t.double() for t in (ah, al, bh, bl))
+    return ah @ bh + ah @ bl + al @ bh
+
+
+def attn_p_bias(drop_p=0.0):
+    """launch_attention's exponent bias of the f16x3 probabilities: the largest b <= 15 with 2^b / (1 - drop_p) <= 65000, in
+    fp32 as the host computes it; None where no b >= 0 holds (the launch is refused)"""
+    ds = np.float32(1.0) / (np.float32(1.0) - np.float32(drop_p)) if drop_p > 0 else np.float32(1.0)
+    b = 15
+    while b >= 0 and np.float32(np.ldexp(ds, b)) > np.float32(65000.0):
+        b -= 1
+    return b if b >= 0 else None
+
+
+def _heads(t, H, hd):
+    return t.reshape(t.shape[0], t.shape[1], H, hd).transpose(1, 2)
+
+
+def attn_ref64(q, k, v, H, hd, dead=None, keep=None, drop_p=0.0, exact_products=True):
+    """float64 softmax(q k^T / sqrt(hd) + mask) (* keep / (1 - p)) v and the log-sum-exp of the masked scores.  q [B,Nq,D],
+    k / v [B,Nk,D], dead / keep broadcastable to [B,H,Nq,Nk] (dead: True = masked).  exact_products=False is the CONTROL of
+    the sink cases: the same operation with q pre-scaled in fp32, every product rounded to fp32 (sums exact) and exp2
+    evaluated in fp32, i.e. the operation at fp32 operand precision, which no fp32 kernel can beat -> (out [B,Nq,D], lse [B,H,Nq])"""
+    B, Nq = q.shape[0], q.shape[1]
+    if exact_products:
+        qq, kk, vv = (_heads(t.double(), H, hd) for t in (q, k, v))
+        s = qq @ kk.transpose(-1, -2) / hd ** 0.5
+        if dead is not None:
+            s = s.masked_fill(dead, float("-inf"))
+        w = torch.softmax(s, -1)
+        if keep is not None:
+            w = w * keep.double() / (1.0 - drop_p)
+        return (w @ vv).transpose(1, 2).reshape(B, Nq, H * hd), torch.logsumexp(s, -1)
+    qs = _heads(q.float(), H, hd) * np.float32(np.float32(1.0 / hd ** 0.5) * np.float32(LOG2E))
+    kk, vv = _heads(k.float(), H, hd), _heads(v.float(), H, hd)
+    s = (qs.unsqueeze(-2) * kk.unsqueeze(-3)).double().sum(-1).float()      # every product rounded to fp32, summed exactly
+    if dead is not None:
+        s = s.masked_fill(dead, float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    p = torch.exp2(s - m)
+    l = p.double().sum(-1, keepdim=True)
+    if keep is not None:
+        p = p * keep.float() * (np.float32(1.0) / (np.float32(1.0) - np.float32(drop_p)))
+    o = (p.unsqueeze(-1) * vv.unsqueeze(-3)).double().sum(-2) / l
+    return o.transpose(1, 2).reshape(B, Nq, H * hd), (m.double() / LOG2E + torch.log(l)).squeeze(-1)
+
+
+ATTN_Q_UP, ATTN_V_UP = 2, 4          # log2 of the fixed up-scales attn_f16x3_kernel gives q * scale * log2 e and v before their split
+
+
+def attn_f16x3_model(q, k, v, H, hd, p_bias=0, dead=None, keep=None, drop_p=0.0, q_up=0, v_up=0):
+    """The operand rounding of attn_f16x3_kernel, in the kernel's order and without its schedule (no key tiles, no online
+    rescale: one maximum per row):
+      q * (scale * log2 e * 2^q_up) in fp32, split; k split; the three-product score in float64, rounded to fp32 (it
+      carries 2^q_up, which the exponent's fused multiply-add takes out exactly);
+      the row reference m' = max - p_bias and P = exp2(S - m') in fp32 (P <= 2^p_bias); the fp32 row sum of the un-dropped P;
+      P (* 1 / (1 - p) where kept, else 0) split; v * 2^v_up split; the three-product P V in float64; division by the fp32 row
+      sum (and 2^v_up).
+    p_bias = q_up = v_up = 0 is the kernel before the scales (P <= 1, lo pieces of every p < 2^-2 subnormal); the shipped
+    kernel uses attn_p_bias(drop_p), ATTN_Q_UP, ATTN_V_UP.  -> (out [B,Nq,D] float64, lse [B,H,Nq] float64, the natural-log sum with the bias taken out)"""
+    B, Nq = q.shape[0], q.shape[1]
+    qscale = np.float32(np.float32(1.0 / hd ** 0.5) * np.float32(LOG2E))
+    qh, ql = split16_model(_heads(q.float(), H, hd) * np.float32(qscale * np.float32(2.0 ** q_up)))
+    kh, kl = split16_model(_heads(k.float(), H, hd).transpose(-1, -2))
+    s = prod3_model(qh, ql, kh, kl).float() * np.float32(2.0 ** -q_up)
+    if dead is not None:
+        s = s.masked_fill(dead, float("-inf"))
+    m = s.amax(-1, keepdim=True) - np.float32(p_bias)
+    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+    p = torch.exp2(s - m)
+    l = p.double().sum(-1, keepdim=True).float()
+    if keep is not None:
+        p = torch.where(keep, p * (np.float32(1.0) / (np.float32(1.0) - np.float32(drop_p))), torch.zeros_like(p))
+    assert float(p.max()) < 65504.0, "the biased probabilities leave the fp16 range"
+    ph, pl = split16_model(p)
+    vh, vl = split16_model(_heads(v.float(), H, hd) * np.float32(2.0 ** v_up))
+    o = prod3_model(ph, pl, vh, vl) / (l.double() * 2.0 ** v_up)
+    lse = (m.double() + p_bias) / LOG2E + torch.log(l.double() * 2.0 ** -p_bias)
+    return o.transpose(1, 2).reshape(B, Nq, H * hd), lse.squeeze(-1)
+
+
+def attn_f16x3_shipped(q, k, v, H, hd, dead=None, keep=None, drop_p=0.0):
+    """attn_f16x3_model with the scales of the kernel as it ships: the exponent bias of the launch and the fixed q / v up-scales"""
+    return attn_f16x3_model(q, k, v, H, hd, p_bias=attn_p_bias(drop_p), dead=dead, keep=keep, drop_p=drop_p, q_up=ATTN_Q_UP,
+                            v_up=ATTN_V_UP)
+
+
+def attn_sink_case(B, H, Nq, Nk, hd, margin, seed, v_sink=0.0, sink=0):
+    """The attention-sink inputs: q, k, v ~ randn; per head, component 0 of every key is zero and key `sink` is e_0;
+    q[..., 0] = margin * sqrt(hd), so the sink's score is `margin` (natural units) and every other score is N(0,1) (its
+    component 0 contributes nothing); v[sink] = v_sink (a float, or a tensor broadcastable to [B, H*hd]).  The output is then
+    the sum over the NON-sink keys, whose weights are e^-margin and smaller.
+    -> (q [B,Nq,D], k [B,Nk,D], v [B,Nk,D], share of the softmax mass off the sink: float64 [B,H,Nq])"""
+    g = torch.Generator().manual_seed(seed)
+    D = H * hd
+    q, k, v = torch.randn(B, Nq, D, generator=g), torch.randn(B, Nk, D, generator=g), torch.randn(B, Nk, D, generator=g)
+    k.view(B, Nk, H, hd)[..., 0] = 0.0
+    k[:, sink] = 0.0
+    k.view(B, Nk, H, hd)[:, sink, :, 0] = 1.0
+    q.view(B, Nq, H, hd)[..., 0] = margin * hd ** 0.5
+    v[:, sink] = v_sink
+    s = _heads(q.double(), H, hd) @ _heads(k.double(), H, hd).transpose(-1, -2) / hd ** 0.5
+    off = 1.0 - torch.softmax(s, -1)[..., sink]
+    return q, k, v, off

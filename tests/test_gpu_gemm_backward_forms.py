@@ -391,11 +391,18 @@ def unheads(t, n):
 
 
 @functools.lru_cache(maxsize=None)
-def _attn_case(NK):
+def _attn_case(NK, margin=None):
+    """margin: the scores carry an attention sink (helpers.attn_sink_case): per head, component 0 of every key is zero, key 0
+    (visible under both masks) is e_0 with a zero value vector, q[..., 0] = margin * sqrt(HD)"""
     g = torch.Generator().manual_seed(41 + NK)
     q = torch.randn(AB, NQ, AD, generator=g)
     kv = torch.randn(AB, NK, 2 * AD, generator=g)                   # interleaved K | V rows: k_rs = v_rs = 2 * D
     dO = torch.randn(AB, NQ, AD, generator=g) * DO_MAG
+    if margin is not None:
+        kv[..., :AD].view(AB, NK, AH, HD)[..., 0] = 0.0
+        kv[:, 0] = 0.0
+        kv[:, 0, :AD].view(AB, AH, HD)[..., 0] = 1.0
+        q.view(AB, NQ, AH, HD)[..., 0] = margin * HD ** 0.5
     kpm = torch.zeros(AB, NK, dtype=torch.bool)
     kpm[0, 44:] = True                                              # the mask differs per batch
     kpm[1, 5] = True

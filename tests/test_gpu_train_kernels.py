@@ -610,7 +610,19 @@ def test_attention_materialised_chain_with_dropout(NK, prec, p):
     (epi 1), zero_cols, attn_delta, attn_drop into the dP buffer, dV = Pd^T dO, dP = dO V^T, attn_ds_drop in place, dQ, dK.  delta,
     Pd and dS against float64 under the host mask (elementwise: the project's 3e-6), dq / dk / dv against float64 autograd at that
     test's 2e-5; the pad columns Nk .. ldp-1 of both buffers, pre-filled with a sentinel, are exactly zero afterwards."""
-    c = GB._attn_case(NK)
+    _chain_with_dropout(GB._attn_case(NK), NK, prec, p)
+
+
+@pytest.mark.parametrize("p", [0.1, 0.5])
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("NK", GB.NKS)
+def test_attention_materialised_chain_with_dropout_at_a_sink(NK, prec, p):
+    """the same chain with an attention sink in the scores (margin 10: key 0 holds all but e^-10 * Nk of every row's mass and has
+    a zero value vector), same per-stage bounds"""
+    _chain_with_dropout(GB._attn_case(NK, margin=10), NK, prec, p, what="chain with dropout at a sink")
+
+
+def _chain_with_dropout(c, NK, prec, p, what="chain with dropout"):
     AB, AH, HD, NQ, AD = GB.AB, GB.AH, GB.HD, GB.NQ, GB.AD
     d = dev()
     tile = 3
@@ -655,11 +667,11 @@ def test_attention_materialised_chain_with_dropout(NK, prec, p):
              gB=NK * 2 * AD, gB2=HD, gC=NQ * 3 * AD, gC2=HD, a_scale_dev=dS_sc, **common)
     run_gemm("dK", A=dP, lda=ldp, ta=1, M=NK, K=NQ, Bw=q, ldb=AD, tb=1, N=HD, C=gkv[..., AD:], ldc=3 * AD, gA=pg * AH, gA2=pg,
              gB=NQ * AD, gB2=HD, gC=NK * 3 * AD, gC2=HD, a_scale_dev=dS_sc, **common)
-    print(f"6. chain with dropout Nk={NK} {prec} p={p}: delta {e_delta:.2e}, Pd {e_pd:.2e}, dS {e_ds:.2e} (bound 3.0e-06)")
+    print(f"6. {what} Nk={NK} {prec} p={p}: delta {e_delta:.2e}, Pd {e_pd:.2e}, dS {e_ds:.2e} (bound 3.0e-06)")
     assert e_delta < 3e-6 and e_pd < 3e-6 and e_ds < 3e-6
     for name, got, exp in (("dQ", gq[..., :AD], dq), ("dK", gkv[..., AD:2 * AD], dk), ("dV", gkv[..., 2 * AD:], dv)):
         e = rel_err(got, exp)
-        print(f"6. chain with dropout Nk={NK} {prec} p={p} {name} against float64 autograd: {e:.2e} (bound 2.0e-05)")
+        print(f"6. {what} Nk={NK} {prec} p={p} {name} against float64 autograd: {e:.2e} (bound 2.0e-05)")
         assert e < 2e-5, name
 
 

@@ -183,3 +183,84 @@ def test_tie_case_catches_a_last_maximum_rule(rows, V):
     assert bool((a_first[tied] < V - 1).all())
     print(f"argmax tie case rows={rows} V={V}: first {first:.6f}, last {last:.6f}, moved by {abs(first - last):.2e} (bound 1e-6)")
     assert abs(first - last) > 100 * 1e-6
+
+
+# ---- attention at a peaked softmax: the CPU model of attn_f16x3_kernel's operand rounding (helpers.attn_f16x3_model) -----------
+def test_split16_model_is_the_exact_two_piece_split():
+    g = torch.Generator().manual_seed(1)
+    x = torch.cat([torch.randn(4096, generator=g) * s for s in (1e-6, 1e-3, 1.0, 300.0, 3e3)])
+    hi, lo = Hh.split16_model(x)
+    assert hi.dtype == lo.dtype == torch.float16
+    err = (hi.double() + lo.double() - x.double()).abs()
+    # relative 2^-22 while lo is a normal number, else the 2^-25 rounding error of the subnormal grid: subnormals are KEPT
+    assert bool((err <= torch.maximum(x.double().abs() * 2.0 ** -22, torch.tensor(2.0 ** -25, dtype=torch.float64))).all())
+    tiny = x.abs() < 1e-5
+    assert bool((hi[tiny] != 0).any()), "fp16 subnormals must not be flushed"
+
+
+@pytest.mark.parametrize("p,bias", [(0.0, 15), (0.1, 15), (0.49, 15), (0.5, 14), (0.9, 12), (0.99998, 0), (0.99999, None), (1.0, None)])
+def test_attn_p_bias_holds_the_fp16_range(p, bias):
+    assert Hh.attn_p_bias(p) == bias
+    if bias is not None:
+        top = 2.0 ** bias / (1.0 - p)
+        assert top <= 65000.0 and (bias == 15 or 2.0 * top > 65000.0)
+
+
+SINK_CPU = [(hd, Nk, margin) for hd in (16, 32, 64) for Nk in (200,) for margin in (10, 14)] + [(64, 1202, 10), (64, 1202, 14)]
+
+
+@pytest.mark.parametrize("hd,Nk,margin", SINK_CPU)
+def test_sink_case_bites_the_unbiased_split_and_not_the_shipped_one(hd, Nk, margin):
+    """The three facts the GPU sink tests rest on, max-relative against float64 with the GPU tests' bound of 3e-6:
+    the operation itself at fp32 operand precision (the control) stays under 1e-6, so the bound need not move for these inputs;
+    the kernel's operand rounding WITHOUT the exponent bias misses the bound by 10x and more, so the cases are not vacuous;
+    with the bias launch_attention picks (and the kernel's fixed q / v up-scales) it holds the bound."""
+    B, H, Nq = 1, 2, 40
+    q, k, v, off = Hh.attn_sink_case(B, H, Nq, Nk, hd, margin, seed=hd + Nk + margin)
+    assert 0.0 < float(off.max()) < 0.2, "the sink must hold nearly all the mass"
+    exp, lse = Hh.attn_ref64(q, k, v, H, hd)
+    ctl, ctl_lse = Hh.attn_ref64(q, k, v, H, hd, exact_products=False)
+    raw, raw_lse = Hh.attn_f16x3_model(q, k, v, H, hd, p_bias=0)
+    fix, fix_lse = Hh.attn_f16x3_shipped(q, k, v, H, hd)
+    e_ctl, e_raw, e_fix = rel_err(ctl, exp), rel_err(raw, exp), rel_err(fix, exp)
+    print(f"sink hd={hd} Nk={Nk} margin={margin} off-sink mass {float(off.max()):.1e}: control {e_ctl:.2e}, split with P <= 1 "
+          f"{e_raw:.2e}, with P <= 2^15 {e_fix:.2e} (bound 3.0e-06)")
+    assert e_ctl < 1e-6 and rel_err(ctl_lse, lse) < 1e-6
+    assert e_raw > 10 * 3e-6
+    assert e_fix < 3e-6
+    assert rel_err(raw_lse, lse) < 3e-6 and rel_err(fix_lse, lse) < 3e-6        # the row sum is dominated by the sink either way
+
+
+@pytest.mark.parametrize("p", [0.1, 0.5, 0.9])
+def test_sink_case_with_dropout_keeps_the_split_in_range(p):
+    """the largest split value is 2^bias / (1 - p): attn_f16x3_model asserts it finite; the bound holds down to bias 12 (p = 0.9)"""
+    B, H, Nq, Nk, hd, margin = 1, 2, 40, 200, 64, 10
+    q, k, v, _ = Hh.attn_sink_case(B, H, Nq, Nk, hd, margin, seed=7)
+    keep = torch.from_numpy(Hh.host_keep(Hh.BIG_SEED, np.arange(B * H * Nq * Nk, dtype=np.uint64), p)).view(B, H, Nq, Nk)
+    exp, _ = Hh.attn_ref64(q, k, v, H, hd, keep=keep, drop_p=p)
+    raw, _ = Hh.attn_f16x3_model(q, k, v, H, hd, p_bias=0, keep=keep, drop_p=p)
+    fix, _ = Hh.attn_f16x3_shipped(q, k, v, H, hd, keep=keep, drop_p=p)
+    print(f"sink with dropout p={p}: P <= 1 {rel_err(raw, exp):.2e}, P <= 2^{Hh.attn_p_bias(p)} {rel_err(fix, exp):.2e}")
+    assert rel_err(raw, exp) > 3e-6 and rel_err(fix, exp) < 3e-6
+
+
+@pytest.mark.parametrize("hd", [16, 32, 64])
+def test_small_sink_value_and_traded_q_k_need_the_operand_scales(hd):
+    """the two in-range cases of test_gpu_attention_envelope.py that the exponent bias alone does not carry: a sink value vector
+    of 1e-3 (its lo pieces subnormal: absolute error 2^-25 on an output of 3e-3) and q / 16 against 16 k (the lo pieces of
+    q * scale * log2 e subnormal).  With v split at 2^4 and q at 2^2 the model holds the bound with room."""
+    B, H, Nq, Nk, margin = 1, 2, 40, 200, 14
+    vs = 1e-3 * torch.randn(B, H * hd, generator=torch.Generator().manual_seed(hd))
+    q, k, v, _ = Hh.attn_sink_case(B, H, Nq, Nk, hd, margin, seed=hd, v_sink=vs)
+    exp, _ = Hh.attn_ref64(q, k, v, H, hd)
+    bias_only = rel_err(Hh.attn_f16x3_model(q, k, v, H, hd, p_bias=15)[0], exp)
+    shipped = rel_err(Hh.attn_f16x3_shipped(q, k, v, H, hd)[0], exp)
+    print(f"small sink value hd={hd}: bias only {bias_only:.2e}, with the operand scales {shipped:.2e} (bound 3.0e-06)")
+    assert bias_only > 3e-6 and shipped < 1.5e-6
+    q, k, v, _ = Hh.attn_sink_case(B, H, Nq, Nk, hd, 10, seed=hd)
+    q, k = q / 16, k * 16
+    exp, _ = Hh.attn_ref64(q, k, v, H, hd)
+    bias_only = rel_err(Hh.attn_f16x3_model(q, k, v, H, hd, p_bias=15)[0], exp)
+    shipped = rel_err(Hh.attn_f16x3_shipped(q, k, v, H, hd)[0], exp)
+    print(f"q / 16, 16 k hd={hd}: bias only {bias_only:.2e}, with the operand scales {shipped:.2e} (bound 3.0e-06)")
+    assert shipped < 1.5e-6 and shipped < bias_only
