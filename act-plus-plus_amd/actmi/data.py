@@ -28,7 +28,9 @@ Differences, all on the host side of the step:
 * compressed episodes (attr ``compress``: every frame a zero-padded JPEG byte string, utils.py:104-107) are decoded with PIL
   (libjpeg, like cv2) and flipped to the B, G, R channel order ``cv2.imdecode(buf, 1)`` returns -- **parity unpinned** against
   cv2 itself (absent here); the Diffusion-only augmentations (torchvision transforms, utils.py:141-156) are not handled.
-  Everything else is checked against an independent restatement in ``tests/test_data_pipeline_cpu.py``."""
+  Everything else is checked against an independent restatement in ``tests/test_data_pipeline_cpu.py``;
+* ``EpisodeReplay`` reads ONE episode in time order for the open-loop replay evaluation (``imitate_episodes.replay_bc``): the
+  same tensors as ``EpisodicDataset.__getitem__`` without the action chunk, in batches of consecutive steps."""
 import fnmatch
 import os
 
@@ -298,6 +300,77 @@ def collate_pcd(samples):
         rgb[b, :s[5].shape[0]] = s[5]
     n = torch.tensor([int(s[6]) for s in samples], dtype=torch.int32)
     return tuple(head) + (xyz, rgb, n)
+
+
+class _EpisodeArrays:
+    """an open episode whose entries are fetched once: an ``.npz`` member is decompressed whole on every access, an HDF5 entry
+    is a handle that reads what is sliced"""
+
+    def __init__(self, root):
+        self.root, self.attrs, self._got = root, root.attrs, {}
+
+    def __contains__(self, key):
+        return key in self.root
+
+    def __getitem__(self, key):
+        if key not in self._got:
+            self._got[key] = self.root[key]
+        return self._got[key]
+
+
+class EpisodeReplay:
+    """One recorded episode in time order, for open-loop replay: iterating gives batches of ``batch`` consecutive replayed steps
+    (the last one ragged) in the layout the policy's inference call takes, the tensors of ``EpisodicDataset.__getitem__`` for the
+    same steps without the action chunk: ``(image u8 [b, K, H, W, 3], qpos f32 [b, S] z-scored)``, then with ``use_depth`` the
+    depth frames ``[b, Cd, 1, H, W]`` (raw uint16 where the episode stores them so), or with ``use_pcd`` ``(xyz [b, N, 3] f32,
+    rgb [b, N, 3] f32, n [b] int32)`` through ``_read_cloud``'s rules.  Compressed episodes are decoded with ``imdecode_bgr``.
+    Nothing is augmented.  ``stride``: only the steps 0, stride, 2 * stride, ... are replayed (a policy without temporal
+    ensembling is queried once per chunk).  ``batch`` is the caller's: the clouds of a 4096-point batch of 50 are 16 MB.
+
+    ``.actions`` [T, A] f32 in file units (with ``/base_action`` appended as the dataset does), ``.is_sim``, ``.T``, ``.steps``."""
+
+    def __init__(self, dataset_path, camera_names, norm_stats, batch, depth_camera_names=None, use_depth=False, f32_depth=False,
+                 pointcloud_names=None, use_pcd=False, max_points=None, pcd_ignore_mask=False, stride=1):
+        self.dataset_path, self.batch, self.stride = dataset_path, int(batch), int(stride)
+        if self.batch < 1 or self.stride < 1:
+            raise ValueError(f"batch {batch} and stride {stride} must be at least 1")
+        with open_episode(dataset_path) as root:
+            attrs = root.attrs
+            self.is_sim = bool(attrs["sim"]) if "sim" in attrs else False
+            self.compressed = bool(attrs.get("compress", False))
+            self.actions = np.ascontiguousarray(_read_action(root), dtype=np.float32)
+        self.T = int(self.actions.shape[0])
+        self.steps = list(range(0, self.T, self.stride))
+        # the switches, their checks and the per-sample depth / cloud rules are the dataset's
+        self._ds = EpisodicDataset([dataset_path], camera_names, norm_stats, [0], [self.T], 1, "ACT", False, depth_camera_names,
+                                   use_depth, f32_depth, pointcloud_names, use_pcd, max_points, pcd_ignore_mask)
+
+    def __len__(self):
+        return (len(self.steps) + self.batch - 1) // self.batch
+
+    def __iter__(self):
+        ds = self._ds
+        t = ds._stats_t
+        with open_episode(self.dataset_path) as raw:
+            root = _EpisodeArrays(raw)
+            for b0 in range(0, len(self.steps), self.batch):
+                steps = self.steps[b0:b0 + self.batch]
+                sel = slice(steps[0], steps[-1] + 1) if self.stride == 1 else steps
+                qpos = torch.from_numpy(np.asarray(root["/observations/qpos"][sel])).float()
+                frames = [np.asarray(root[f"/observations/images/{cam}"][sel]) for cam in ds.camera_names]
+                if self.compressed:                            # utils.py:104-107, frame by frame
+                    frames = [np.stack([imdecode_bgr(buf) for buf in f]) for f in frames]
+                out = [torch.from_numpy(np.stack(frames, axis=1)), (qpos - t["qpos_mean"]) / t["qpos_std"]]
+                if ds.use_depth:
+                    depths = [np.asarray(root[f"/observations/depth_images/{cam}"][sel]) for cam in ds.depth_camera_names]
+                    if self.compressed:
+                        depths = [np.stack([imdecode_bgr(buf) for buf in d]) for d in depths]
+                    out.append(torch.stack([ds._depth_data([d[i] for d in depths]) for i in range(len(steps))]))
+                if ds.use_pcd:
+                    clouds = [ds._read_cloud(root, ts, self.dataset_path) for ts in steps]
+                    out += [torch.stack([c[0] for c in clouds]), torch.stack([c[1] for c in clouds]),
+                            torch.tensor([int(c[2]) for c in clouds], dtype=torch.int32)]
+                yield tuple(out)
 
 
 def flatten_list(l):

@@ -172,6 +172,8 @@ def load():
         "actmi_grad_phase_range": ([vp, i32, C.POINTER(i64), C.POINTER(i64)], i32),
         "actmi_wait_grad_phase": ([vp, i32, vp], i32),
         "actmi_ensemble_step": ([vp, vp, vp, f64, vp, vp, i32, i32, i32, vp], i32),
+        "actmi_op_ensemble_episode": ([vp, vp, f64, vp, vp, i32, i32, i32, i32, vp], i32),
+        "actmi_op_action_error": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], i32),
         "actmi_op_gemm": ([C.POINTER(GemmDesc), vp], i32),
         "actmi_op_split16": ([vp, vp, C.c_int64, C.c_float, vp], i32),
         "actmi_op_permute_conv_k": ([vp, vp, C.c_int64, i32, i32, i32, vp], i32),

@@ -1393,3 +1393,96 @@ class TemporalEnsemble:
             L.check(lib.actmi_ensemble_step(_p(self.ring), _p(self.t), _p(a), self.k, _p(self.out), _p(self.populated),
                                             self.E, self.Q, self.A, L.current_stream_ptr()), None, "ensemble_step")
         return self.out
+
+
+# ---- open-loop replay of recorded episodes (csrc/replay_eval.hip) --------------------------------------------------------------
+def _lengths_i32(lengths, E, T, device):
+    if lengths is None:
+        return None
+    ln = torch.as_tensor(lengths).to(device=device, dtype=torch.int32).contiguous()
+    if tuple(ln.shape) != (E,):
+        raise ValueError(f"lengths has shape {tuple(ln.shape)}, expected ({E},)")
+    return ln
+
+
+def episode_ensemble(chunks, lengths=None, k=0.01, want_populated=False):
+    """The temporal ensemble of every step of every episode in one launch (actmi_op_ensemble_episode).  chunks [E, T, Q, A] f32
+    cuda: row (e, r) is the chunk predicted from frame r; lengths [E] (valid steps per episode; None: all T) -> raw [E, T, A]
+    f64, and with ``want_populated`` the u8 mask [E, T, Q] of the rows that counted (row j of step t is r = t-(Q-1)+j).  Step t
+    of episode e is bit for bit what the t-th ``TemporalEnsemble.step`` gives on the same chunks; rows t >= lengths[e] are
+    zeros."""
+    if chunks.dim() != 4 or chunks.dtype != torch.float32 or not chunks.is_cuda:
+        raise ValueError(f"chunks must be a float32 cuda tensor [E, T, Q, A], got {chunks.dtype} {tuple(chunks.shape)} on {chunks.device}")
+    chunks = chunks.contiguous()
+    E, T, Q, A = (int(v) for v in chunks.shape)
+    dev = chunks.device
+    ln = _lengths_i32(lengths, E, T, dev)
+    out = torch.empty((E, T, A), dtype=torch.float64, device=dev)
+    pop = torch.empty((E, T, Q), dtype=torch.uint8, device=dev) if want_populated else None
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_ensemble_episode(_p(chunks), _p(ln), float(k), _p(out), _p(pop), E, T, Q, A,
+                                                   L.current_stream_ptr()), None, "op_ensemble_episode")
+    return (out, pop) if want_populated else out
+
+
+def episode_ensemble_ref(chunks, lengths=None, k=0.01, want_populated=False):
+    """numpy statement of ``episode_ensemble`` (reference imitate_episodes.py:402-411 for every step at once); needs no library.
+    chunks: ndarray or CPU tensor [E, T, Q, A] -> raw [E, T, A] float64 (and the bool mask [E, T, Q])."""
+    import numpy as np
+    c = np.asarray(chunks, dtype=np.float32)
+    E, T, Q, A = c.shape
+    ln = np.full(E, T, dtype=np.int64) if lengths is None else np.clip(np.asarray(lengths, dtype=np.int64), 0, T)
+    out = np.zeros((E, T, A), dtype=np.float64)
+    pop = np.zeros((E, T, Q), dtype=bool)
+    for e in range(E):
+        for t in range(int(ln[e])):
+            j = np.arange(max(0, Q - 1 - t), Q)             # the candidate rows that exist: r = t-(Q-1)+j >= 0
+            r = t - (Q - 1) + j
+            rows = c[e, r, t - r]                           # [n, A], oldest first
+            ok = np.all(rows != 0, axis=1)
+            pop[e, t, j] = ok
+            rows = rows[ok]
+            if len(rows):
+                w = np.exp(-float(k) * np.arange(len(rows)))
+                out[e, t] = (rows.astype(np.float64) * (w / w.sum())[:, None]).sum(axis=0)
+    return (out, pop) if want_populated else out
+
+
+def action_error(raw, target, lengths, mean, std, want_pred=True):
+    """Un-normalise and compare with the recording on the device (actmi_op_action_error).  raw [E, T, A] f64 cuda, target
+    [E, T, A] f32 (file units, already aligned), lengths [E] or None, mean / std [A] -> (pred [E, T, A] f64 = raw * std + mean
+    or None, stats [E, 3, A] f64 = sum |d|, sum d^2, max |d| over t < lengths[e], d = pred - target)."""
+    if raw.dim() != 3 or raw.dtype != torch.float64 or not raw.is_cuda:
+        raise ValueError(f"raw must be a float64 cuda tensor [E, T, A], got {raw.dtype} {tuple(raw.shape)} on {raw.device}")
+    raw = raw.contiguous()
+    E, T, A = (int(v) for v in raw.shape)
+    dev = raw.device
+    target = torch.as_tensor(target).to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(target.shape) != (E, T, A):
+        raise ValueError(f"target has shape {tuple(target.shape)}, expected {(E, T, A)}")
+    mean, std = (torch.as_tensor(v).to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for v in (mean, std))
+    if mean.numel() != A or std.numel() != A:
+        raise ValueError(f"mean / std hold {mean.numel()} / {std.numel()} values for action_dim {A}")
+    ln = _lengths_i32(lengths, E, T, dev)
+    pred = torch.empty((E, T, A), dtype=torch.float64, device=dev) if want_pred else None
+    stats = torch.empty((E, 3, A), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_action_error(_p(raw), _p(target), _p(ln), _p(mean), _p(std), _p(pred), _p(stats), E, T, A,
+                                               L.current_stream_ptr()), None, "op_action_error")
+    return pred, stats
+
+
+def action_error_ref(raw, target, lengths, mean, std, want_pred=True):
+    """numpy statement of ``action_error`` (float64); needs no library.  -> (pred, stats) as ndarrays."""
+    import numpy as np
+    raw = np.asarray(raw, dtype=np.float64)
+    E, T, A = raw.shape
+    pred = raw * np.asarray(std, dtype=np.float64).reshape(1, 1, A) + np.asarray(mean, dtype=np.float64).reshape(1, 1, A)
+    d = np.abs(pred - np.asarray(target, dtype=np.float32).astype(np.float64))
+    ln = np.full(E, T, dtype=np.int64) if lengths is None else np.clip(np.asarray(lengths, dtype=np.int64), 0, T)
+    stats = np.zeros((E, 3, A), dtype=np.float64)
+    for e in range(E):
+        de = d[e, :int(ln[e])]
+        if len(de):
+            stats[e] = np.stack([de.sum(axis=0), (de * de).sum(axis=0), de.max(axis=0)])
+    return (pred if want_pred else None), stats

@@ -265,6 +265,31 @@ int actmi_ensemble_step(float* ring, int32_t* tcount, const float* chunk, double
     return launch_ensemble(ring, tcount, chunk, k, out, populated, E, Q, A, S(stream));
 }
 
+int actmi_op_ensemble_episode(const float* chunks, const int32_t* lengths, double k, double* out, uint8_t* populated, int E, int T,
+                              int Q, int A, void* stream) {
+    g_op_error.clear();
+    if (!chunks || !out || E < 0 || T < 0) { g_op_error = "ensemble_episode: null chunks / out or a negative extent"; return ACTMI_E_INVALID; }
+    if (A < 1 || A > 64) { g_op_error = "ensemble_episode: action_dim must be in 1..64 (one lane group per row, as actmi_ensemble_step)"; return ACTMI_E_INVALID; }
+    if (Q < 1 || Q > kEnsembleMaxQ) {
+        g_op_error = "ensemble_episode: num_queries must be in 1.." + std::to_string(kEnsembleMaxQ) + " (the weights of a step live in LDS)";
+        return ACTMI_E_INVALID;
+    }
+    if (E > 65535) { g_op_error = "ensemble_episode: more than 65535 episodes in one launch"; return ACTMI_E_INVALID; }
+    const int rc = launch_ensemble_episode(chunks, lengths, k, out, populated, E, T, Q, A, S(stream));
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
+int actmi_op_action_error(const double* raw, const float* target, const int32_t* lengths, const double* mean, const double* stdv,
+                          double* pred, double* stats, int E, int T, int A, void* stream) {
+    g_op_error.clear();
+    if (!raw || !target || !mean || !stdv || !stats || E < 0 || T < 0 || A < 1 || E > 65535) {
+        g_op_error = "action_error: null argument, a negative extent, action_dim < 1 or more than 65535 episodes";
+        return ACTMI_E_INVALID;
+    }
+    const int rc = launch_action_error(raw, target, lengths, mean, stdv, pred, stats, E, T, A, S(stream));
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_gemm(const actmi_gemm_desc* d, void* stream) {
     if (!d) return ACTMI_E_INVALID;
     g_op_error.clear();

@@ -183,6 +183,13 @@ int launch_repack_conv_w(const float* w_oihw, float* w_ohwi, int G, int O, int I
                          int64_t g_out, int kpad, hipStream_t st);
 int launch_ensemble(float* ring, int* tcount, const float* chunk, double k, double* out, uint8_t* populated, int E,
                     int Q, int A, hipStream_t st);
+// the largest Q whose weights (Q doubles) fit next to the fixed scratch in a 64 KB workgroup allocation
+constexpr int kEnsembleMaxQ = (65536 - 4096) / 8;
+// every step of every episode at once over the chunk table [E][T][Q][A], and the error against the recording (replay_eval.hip)
+int launch_ensemble_episode(const float* chunks, const int32_t* lengths, double k, double* out, uint8_t* populated, int E, int T,
+                            int Q, int A, hipStream_t st);
+int launch_action_error(const double* raw, const float* target, const int32_t* lengths, const double* mean, const double* stdv,
+                        double* pred, double* stats, int E, int T, int A, hipStream_t st);
 int launch_bn_fold(const float* w, const float* b, const float* rm, const float* rv, float* scale, float* bias, int n,
                    hipStream_t st);
 int launch_build_rowmap(int* map, int B, int C, int fh, int fw, int N, int n_extra, hipStream_t st);

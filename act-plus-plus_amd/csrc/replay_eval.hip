@@ -1,0 +1,108 @@
+// Open-loop replay evaluation of recorded episodes: the temporal ensemble of every step of every episode in one launch, and
+// the error of the executed actions against the recording, reduced on the device.
+#include "common.h"
+#include "ensemble_core.h"
+
+namespace {
+
+// chunks [E][T][Q][A]: row (e, r) is the chunk predicted from frame r.  One workgroup per (t, e); step t reads the rows
+// r = t-(Q-1)+j straight from the table (consecutive j lie (Q-1)*A floats apart), with the arithmetic of the step kernel
+// (ensemble_core.h).  Steps t >= lengths[e] give zeros; chunk rows r >= lengths[e] are never read.
+__global__ __launch_bounds__(256) void ensemble_episode_kernel(const float* __restrict__ chunks, const int32_t* __restrict__ lengths,
+                                                               double k, double* __restrict__ out, uint8_t* __restrict__ populated,
+                                                               int T, int Q, int A) {
+    extern __shared__ __attribute__((aligned(8))) unsigned char s_raw[];
+    __shared__ int s_cnt[4];
+    __shared__ double s_ws[4];
+    __shared__ double s_acc[256];
+    const EnsembleLds lds{reinterpret_cast<double*>(s_raw), s_cnt, s_ws, s_acc};
+    const int t = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
+    int Te = lengths ? lengths[e] : T;
+    Te = Te < 0 ? 0 : (Te > T ? T : Te);
+    double* o = out + ((int64_t)e * T + t) * A;
+    uint8_t* p = populated ? populated + ((int64_t)e * T + t) * Q : nullptr;
+    if (t >= Te) {                                         // uniform over the workgroup
+        if (tid < A) o[tid] = 0.0;
+        if (p) for (int j = tid; j < Q; j += 256) p[j] = 0;
+        return;
+    }
+    const float* ce = chunks + (int64_t)e * T * Q * A;
+    auto row = [&](int j) -> const float* {
+        const int r = t - (Q - 1) + j;                     // 0 <= r <= t < Te
+        return ce + ((int64_t)r * Q + (t - r)) * A;
+    };
+    ensemble_step_rows(row, t, k, Q, A, lds, o, p);
+}
+
+// pred = raw * std + mean (two roundings, as numpy) and, per (episode, action component) over t < lengths[e], the sums of
+// |d| and d^2 and the maximum of |d| with d = pred - (double)target.  One workgroup per (block of `per` components, episode):
+// thread (a, g) walks t = g, g + ng, ... in order, the ng partial results are combined in index order -- a fixed shape, so two
+// runs give the same bits.
+__global__ __launch_bounds__(256) void action_error_kernel(const double* __restrict__ raw, const float* __restrict__ target,
+                                                           const int32_t* __restrict__ lengths, const double* __restrict__ mean,
+                                                           const double* __restrict__ stdv, double* __restrict__ pred,
+                                                           double* __restrict__ stats, int T, int A, int per) {
+    __shared__ double s_part[3][256];
+    const int e = blockIdx.y, tid = threadIdx.x;
+    const int al = tid % per, g = tid / per, ng = 256 / per;
+    const int a = blockIdx.x * per + al;
+    int Te = lengths ? lengths[e] : T;
+    Te = Te < 0 ? 0 : (Te > T ? T : Te);
+    double s1 = 0.0, s2 = 0.0, mx = 0.0;
+    if (a < A) {
+        const double sd = stdv[a], mu = mean[a];
+        for (int t = g; t < T; t += ng) {
+            const int64_t i = ((int64_t)e * T + t) * A + a;
+            double p;
+            {
+#pragma clang fp contract(off)                             // product and sum rounded separately: a fused multiply-add differs
+                const double prod = raw[i] * sd;           // from numpy by many ulps where raw * std nearly cancels the mean
+                p = prod + mu;
+            }
+            if (pred) pred[i] = p;
+            if (t < Te) {
+                const double d = fabs(p - (double)target[i]);
+                s1 += d;
+                s2 += d * d;
+                mx = fmax(mx, d);
+            }
+        }
+    }
+    s_part[0][tid] = s1;
+    s_part[1][tid] = s2;
+    s_part[2][tid] = mx;
+    __syncthreads();
+    if (tid < per && a < A) {
+        double t1 = 0.0, t2 = 0.0, tm = 0.0;
+        for (int gg = 0; gg < ng; ++gg) {
+            t1 += s_part[0][gg * per + tid];
+            t2 += s_part[1][gg * per + tid];
+            tm = fmax(tm, s_part[2][gg * per + tid]);
+        }
+        double* st = stats + (int64_t)e * 3 * A;
+        st[a] = t1;
+        st[A + a] = t2;
+        st[2 * A + a] = tm;
+    }
+}
+
+}  // namespace
+
+int launch_ensemble_episode(const float* chunks, const int32_t* lengths, double k, double* out, uint8_t* populated, int E, int T,
+                            int Q, int A, hipStream_t st) {
+    if (E <= 0 || T <= 0) return 0;
+    if (A < 1 || A > 64 || Q < 1 || Q > kEnsembleMaxQ || E > 65535) return -2;
+    hipLaunchKernelGGL(ensemble_episode_kernel, dim3(T, E), dim3(256), ensemble_lds_bytes(Q), st, chunks, lengths, k, out, populated,
+                       T, Q, A);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_action_error(const double* raw, const float* target, const int32_t* lengths, const double* mean, const double* stdv,
+                        double* pred, double* stats, int E, int T, int A, hipStream_t st) {
+    if (E <= 0 || A <= 0) return 0;
+    if (E > 65535 || T < 0) return -2;
+    const int per = A <= 16 ? 16 : (A <= 32 ? 32 : 64);
+    hipLaunchKernelGGL(action_error_kernel, dim3((A + per - 1) / per, E), dim3(256), 0, st, raw, target, lengths, mean, stdv, pred,
+                       stats, T, A, per);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}

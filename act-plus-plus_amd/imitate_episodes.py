@@ -7,7 +7,9 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
   episodes one after another with batch 1, :319-353);
 * episodes SHARD across ranks (one process per GPU): poses are pre-drawn in the reference's RNG order, every rank
   takes a contiguous slice, a single all-gather of (episode_return, highest_reward) ends the run;
-* the 10 warm-up queries per rollout and the real-time sleep (:377-382, :467-470) are off by default.
+* the 10 warm-up queries per rollout and the real-time sleep (:377-382, :467-470) are off by default;
+* ``replay_bc`` (``--eval --replay``) evaluates open loop on recorded episodes instead -- the one evaluation of use_depth /
+  use_pcd policies and of policies trained on real-robot episodes: queries batched over TIME, one ensemble launch per episode.
 """
 import argparse
 import os
@@ -101,40 +103,13 @@ def _default_stats(state_dim, action_dim=16):
             "action_min": -np.ones(action_dim), "action_max": np.ones(action_dim)}
 
 
-def eval_bc(config, ckpt_name, save_episode=True, num_rollouts=50, policy=None, ensemble_factory=None,
-            env_factory=None, stats=None, max_parallel=None, warmup_queries=0, realtime=False, verbose=True,
-            trace=None, vq_sampler=None, pipeline_groups=None):
-    """reference imitate_episodes.py:228-526, batched + sharded.  Returns (success_rate, avg_return).
-
-    VQ-ACT: the reference samples the latent code from its prior model each query
-    (``latent_model.generate(1, temperature=1)``, imitate_episodes.py:252-262,393-394): ``actmi.latent_model`` mirrors it
-    on the library's kernels; ``vq_sampler(n) -> [n, vq_class, vq_dim]`` overrides the source of the codes."""
-    set_seed(1000)
+def _load_policy_and_stats(config, ckpt_name, policy, stats, dev, verbose):
+    """the policy and the dataset statistics of an evaluation: a given ``policy`` / ``stats`` is used as it is, otherwise the
+    checkpoint ``ckpt_name`` and ``dataset_stats.pkl`` of ``ckpt_dir`` are read (reference imitate_episodes.py:241-251)"""
     ckpt_dir = config["ckpt_dir"]
-    state_dim = config["state_dim"]
-    policy_class = config["policy_class"]
-    policy_config = config["policy_config"]
-    if policy_config.get("use_depth") or getattr(policy, "use_depth", False):
-        # the simulators here render no depth and the reference's depth rollouts read ROS camera topics; rolling the policy out on
-        # RGB alone would report the success rate of a different model
-        raise NotImplementedError("eval_bc cannot roll out a use_depth policy: no environment here produces depth frames "
-                                  "(train with --use_depth, evaluate on the robot's own loop)")
-    if policy_config.get("use_pcd") or getattr(policy, "use_pcd", False):
-        # likewise: no simulator here produces point clouds, the fork's rollouts read the robot's fused live cloud
-        raise NotImplementedError("eval_bc cannot roll out a use_pcd policy: no environment here produces point clouds "
-                                  "(train with --use_pcd, evaluate on the robot's own loop)")
-    camera_names = config["camera_names"]
-    max_timesteps = int(config["episode_len"])
-    task_name = config["task_name"]
-    temporal_agg = config["temporal_agg"]
-    rank, world, local_rank = dist_utils.init_from_env()
-    on_gpu = torch.cuda.is_available()
-    # one process per GPU: everything of this rank (engine arena, streams, frames, ensemble ring) lives on cuda:LOCAL_RANK
-    dev = torch.device("cuda", local_rank if world > 1 else torch.cuda.current_device()) if on_gpu else torch.device("cpu")
-
     if policy is None:
         # inference-only handle (no grad buffers), built on this rank's device
-        policy = make_policy(policy_class, dict(policy_config, training=False), device=str(dev))
+        policy = make_policy(config["policy_class"], dict(config["policy_config"], training=False), device=str(dev))
         ckpt_path = os.path.join(ckpt_dir, ckpt_name)
         if os.path.isfile(ckpt_path):
             loading_status = policy.deserialize(torch.load(ckpt_path, weights_only=True))
@@ -150,30 +125,70 @@ def eval_bc(config, ckpt_name, save_episode=True, num_rollouts=50, policy=None, 
             with open(stats_path, "rb") as f:
                 stats = pickle.load(f)               # written by this program's own main()
         else:
-            stats = _default_stats(state_dim)
+            stats = _default_stats(config["state_dim"])
+    return policy, stats
+
+
+def _make_vq_sampler(policy_config, ckpt_dir, dev, rank, verbose):
+    """reference imitate_episodes.py:252-262: the latent prior, weights from latent_model_last.ckpt next to the policy;
+    -> ``vq_sampler(n)``, n codes [n, vq_class, vq_dim] (:393: latent_model.generate(1, temperature=1, x=None))"""
+    from actmi.latent_model import LatentModelTransformer, latent_model_spec
+    from actmi.weights import generate_latent_model_state_dict
+    vq_dim, vq_class = policy_config["vq_dim"], policy_config["vq_class"]
+    latent_model = LatentModelTransformer(vq_dim, vq_dim, vq_class, device=str(dev))
+    lm_path = os.path.join(ckpt_dir, "latent_model_last.ckpt")
+    if os.path.isfile(lm_path):
+        latent_model.load_state_dict(torch.load(lm_path, weights_only=True))
+    else:
+        if verbose:
+            print(f"no latent model at {lm_path}: sampling codes from a random-init prior")
+        latent_model.load_state_dict(generate_latent_model_state_dict(latent_model_spec(vq_dim, vq_dim, vq_class), 0))
+    draws = [0]
+
+    def vq_sampler(n):
+        draws[0] += 1
+        return latent_model.generate(n, temperature=1, x=None, seed=1000 * rank + draws[0])
+    return vq_sampler
+
+
+def eval_bc(config, ckpt_name, save_episode=True, num_rollouts=50, policy=None, ensemble_factory=None,
+            env_factory=None, stats=None, max_parallel=None, warmup_queries=0, realtime=False, verbose=True,
+            trace=None, vq_sampler=None, pipeline_groups=None):
+    """reference imitate_episodes.py:228-526, batched + sharded.  Returns (success_rate, avg_return).
+
+    VQ-ACT: the reference samples the latent code from its prior model each query
+    (``latent_model.generate(1, temperature=1)``, imitate_episodes.py:252-262,393-394): ``actmi.latent_model`` mirrors it
+    on the library's kernels; ``vq_sampler(n) -> [n, vq_class, vq_dim]`` overrides the source of the codes."""
+    set_seed(1000)
+    ckpt_dir = config["ckpt_dir"]
+    policy_class = config["policy_class"]
+    policy_config = config["policy_config"]
+    if policy_config.get("use_depth") or getattr(policy, "use_depth", False):
+        # the simulators here render no depth and the reference's depth rollouts read ROS camera topics; rolling the policy out on
+        # RGB alone would report the success rate of a different model
+        raise NotImplementedError("eval_bc cannot roll out a use_depth policy: no environment here produces depth frames "
+                                  "(train with --use_depth, evaluate on the robot's own loop or `--replay` on recorded episodes)")
+    if policy_config.get("use_pcd") or getattr(policy, "use_pcd", False):
+        # likewise: no simulator here produces point clouds, the fork's rollouts read the robot's fused live cloud
+        raise NotImplementedError("eval_bc cannot roll out a use_pcd policy: no environment here produces point clouds "
+                                  "(train with --use_pcd, evaluate on the robot's own loop or `--replay` on recorded episodes)")
+    camera_names = config["camera_names"]
+    max_timesteps = int(config["episode_len"])
+    task_name = config["task_name"]
+    temporal_agg = config["temporal_agg"]
+    rank, world, local_rank = dist_utils.init_from_env()
+    on_gpu = torch.cuda.is_available()
+    # one process per GPU: everything of this rank (engine arena, streams, frames, ensemble ring) lives on cuda:LOCAL_RANK
+    dev = torch.device("cuda", local_rank if world > 1 else torch.cuda.current_device()) if on_gpu else torch.device("cpu")
+
+    policy, stats = _load_policy_and_stats(config, ckpt_name, policy, stats, dev, verbose)
     pre_process = lambda s_qpos: (s_qpos - stats["qpos_mean"]) / stats["qpos_std"]          # noqa: E731
     post_process = make_post_process(policy_class, stats)
     is_diffusion = policy_class == "Diffusion"
 
     use_vq = bool(policy_config.get("vq", False))
     if use_vq and vq_sampler is None:
-        # reference imitate_episodes.py:252-262: the latent prior, weights from latent_model_last.ckpt next to the policy
-        from actmi.latent_model import LatentModelTransformer, latent_model_spec
-        from actmi.weights import generate_latent_model_state_dict
-        vq_dim, vq_class = policy_config["vq_dim"], policy_config["vq_class"]
-        latent_model = LatentModelTransformer(vq_dim, vq_dim, vq_class, device=str(dev))
-        lm_path = os.path.join(ckpt_dir, "latent_model_last.ckpt")
-        if os.path.isfile(lm_path):
-            latent_model.load_state_dict(torch.load(lm_path, weights_only=True))
-        else:
-            if verbose:
-                print(f"no latent model at {lm_path}: sampling codes from a random-init prior")
-            latent_model.load_state_dict(generate_latent_model_state_dict(latent_model_spec(vq_dim, vq_dim, vq_class), 0))
-        _draws = [0]
-
-        def vq_sampler(n):                       # imitate_episodes.py:393: latent_model.generate(1, temperature=1, x=None)
-            _draws[0] += 1
-            return latent_model.generate(n, temperature=1, x=None, seed=1000 * rank + _draws[0])
+        vq_sampler = _make_vq_sampler(policy_config, ckpt_dir, dev, rank, verbose)
     num_queries = policy_config["num_queries"]
     query_frequency = 1 if temporal_agg else num_queries
     action_dim = policy_config.get("action_dim", 16)
@@ -344,6 +359,182 @@ def eval_bc(config, ckpt_name, save_episode=True, num_rollouts=50, policy=None, 
             f.write("\n\n")
             f.write(repr(highest_rewards.tolist()))
     return success_rate, avg_return
+
+
+def _replay_query(policy, data, use_depth, use_pcd, vq_sampler):
+    """one policy query on a batch of an actmi.data.EpisodeReplay: (image, qpos[, depth | xyz, rgb, n]) -> a_hat [b, Q, A]"""
+    image, qpos = data[0], data[1]
+    kw = {}
+    if use_depth:
+        kw["depth_img"] = data[2]
+    if use_pcd:
+        kw["pointcloud"] = {"xyz": data[2], "rgb": data[3], "n": data[4]}
+    if vq_sampler is not None:
+        kw["vq_sample"] = vq_sampler(qpos.shape[0])
+    return policy(qpos, image, **kw)
+
+
+def replay_metrics(rows, action_dim):
+    """rows [n, 1 + 3A] float64 = (T, sum |d| [A], sum d^2 [A], max |d| [A]) per episode -> the per-episode and the pooled
+    figures.  Pooled: the sums are added and divided by the total step count (never an average of averages)."""
+    A = action_dim
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 1 + 3 * A)
+
+    def figures(T, s1, s2, mx):
+        T = max(float(T), 1.0)
+        mae, rmse = s1 / T, np.sqrt(s2 / T)
+        return {"mae": mae.tolist(), "rmse": rmse.tolist(), "max": mx.tolist(), "mae_mean": float(mae.mean()),
+                "rmse_mean": float(rmse.mean()), "max_max": float(mx.max()) if len(mx) else 0.0}
+
+    episodes = [dict(figures(r[0], r[1:1 + A], r[1 + A:1 + 2 * A], r[1 + 2 * A:]), T=int(r[0])) for r in rows]
+    total = rows[:, 0].sum() if len(rows) else 0.0
+    s1 = rows[:, 1:1 + A].sum(axis=0) if len(rows) else np.zeros(A)
+    s2 = rows[:, 1 + A:1 + 2 * A].sum(axis=0) if len(rows) else np.zeros(A)
+    mx = rows[:, 1 + 2 * A:].max(axis=0) if len(rows) else np.zeros(A)
+    return dict(figures(total, s1, s2, mx), episodes=episodes, steps=int(total))
+
+
+def _gather_rows_f64(local, counts):
+    """dist_utils.all_gather_rows moves float32 rows; float64 rows travel as their bit pattern (two float32 words per value: the
+    collective only copies), so the pooled sums are the same bits with one rank or many"""
+    local = local.to(torch.float64).contiguous().cpu()
+    k = local.shape[1]
+    out = dist_utils.all_gather_rows(local.view(torch.float32), counts)
+    return out.contiguous().view(torch.float64).reshape(-1, k)
+
+
+def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=None, episode_ensemble=None, align="train",
+              save_episode=True, verbose=True, action_error=None, vq_sampler=None):
+    """Open-loop replay evaluation on recorded episodes (the fork's eval_arm_gripper_depth.py:343-418 without its plots): the
+    policy is queried on an episode's recorded observations, the chunks are ensembled over time (``temporal_agg``) or executed
+    chunk by chunk, un-normalised, and compared with the recorded ``/action``.  Serves what ``eval_bc`` cannot roll out --
+    use_depth and use_pcd policies, and policies trained on real-robot episodes.
+
+    The observation at step t does not depend on the action at t-1, so the queries of an episode are independent: they run
+    ``batch`` frames at a time (default: the engine's max_batch), the batches reach the device through ``DevicePrefetcher``, the
+    chunks land in a device table [1, T, Q, A], ONE ``ops.episode_ensemble`` launch ensembles every step and ``ops.action_error``
+    reduces the error on the device.  Without ``temporal_agg`` only the frames t % Q == 0 are queried and
+    raw[t] = chunk[t - t % Q][t % Q] (reference :392).
+
+    ``episodes``: None = every file ``find_all_hdf5(config["dataset_dir"])`` finds (sorted), an int n = the first n; they are
+    sharded over the ranks.  ``align``: "train" compares step t with action[t] of a sim episode and action[max(0, t-1)] of a
+    real one (the shift the dataset trains slot 0 on), "none" with action[t] as the fork's plot does.  ``policy``,
+    ``episode_ensemble`` and ``action_error`` can be given (CPU stand-ins: ops.episode_ensemble_ref, ops.action_error_ref).
+    Returns {"episodes": [...], "mae": [A], "rmse": [A], "max": [A], "mae_mean", "rmse_mean", "max_max", "steps", ...} in
+    action units; with ``save_episode`` rank 0 writes replay_<ckpt>.json and per episode replay_<ckpt>_ep<i>.npz (pred, target)."""
+    import json
+    from actmi.data import DevicePrefetcher, EpisodeReplay, find_all_hdf5
+    ckpt_dir = config["ckpt_dir"]
+    policy_class = config["policy_class"]
+    policy_config = config["policy_config"]
+    if policy_class == "Diffusion":
+        raise NotImplementedError("replay_bc: the Diffusion policy has no temporal ensemble and its crop-resize input path is not "
+                                  "part of the replay")
+    if align not in ("train", "none"):
+        raise ValueError(f"align must be 'train' or 'none', got {align!r}")
+    camera_names = config["camera_names"]
+    temporal_agg = config["temporal_agg"]
+    rank, world, local_rank = dist_utils.init_from_env()
+    on_gpu = torch.cuda.is_available()
+    dev = torch.device("cuda", local_rank if world > 1 else torch.cuda.current_device()) if on_gpu else torch.device("cpu")
+    policy, stats = _load_policy_and_stats(config, ckpt_name, policy, stats, dev, verbose)
+    use_vq = bool(policy_config.get("vq", False))
+    if use_vq and vq_sampler is None:
+        vq_sampler = _make_vq_sampler(policy_config, ckpt_dir, dev, rank, verbose)
+    if not use_vq:
+        vq_sampler = None
+    use_depth = bool(policy_config.get("use_depth") or getattr(policy, "use_depth", False))
+    use_pcd = bool(policy_config.get("use_pcd") or getattr(policy, "use_pcd", False))
+    Q = int(policy_config["num_queries"])
+    A = int(policy_config.get("action_dim", 16))
+    engine = getattr(policy, "model", None)
+    if batch is None:
+        batch = getattr(engine, "max_batch", None) or 8
+    if episode_ensemble is None or action_error is None:
+        from actmi import ops
+        episode_ensemble = episode_ensemble or ops.episode_ensemble
+        action_error = action_error or ops.action_error
+    dataset_dir = config.get("dataset_dir")
+    if not (dataset_dir and os.path.isdir(dataset_dir)):
+        raise ValueError(f"replay_bc needs recorded episodes: config['dataset_dir'] = {dataset_dir!r} is not a directory (--dataset_dir)")
+    files = find_all_hdf5(dataset_dir, bool(config.get("skip_mirrored_data", False)))
+    if episodes is not None:
+        files = files[:int(episodes)]
+    if not files:
+        raise ValueError(f"replay_bc: no episode files under {dataset_dir}")
+    n = len(files)
+    lo, hi = shard_range(n, rank, world)
+    spans = [shard_range(n, r, world) for r in range(world)]
+    mean = np.asarray(stats["action_mean"], dtype=np.float64).reshape(-1)
+    std = np.asarray(stats["action_std"], dtype=np.float64).reshape(-1)
+    if mean.shape[0] != A or std.shape[0] != A:
+        raise ValueError(f"the dataset statistics hold {mean.shape[0]} action components, the policy's action_dim is {A}")
+
+    local_rows, local_pt = [], []
+    time0, n_frames = time.time(), 0
+    for i in range(lo, hi):
+        ep = EpisodeReplay(files[i], camera_names, stats, batch, depth_camera_names=policy_config.get("depth_camera_names"),
+                           use_depth=use_depth, pointcloud_names=config.get("pointcloud_names"), use_pcd=use_pcd,
+                           max_points=policy_config.get("max_points"), pcd_ignore_mask=bool(config.get("pcd_ignore_mask", False)),
+                           stride=1 if temporal_agg else Q)
+        if ep.actions.shape[1] != A:
+            raise ValueError(f"{files[i]}: the recorded actions are {ep.actions.shape[1]} wide, the policy's action_dim is {A}")
+        T = ep.T
+        # the chunk of replayed step s: row s of the table (temporal_agg: s = t, every frame; else s = t // Q)
+        table = torch.zeros((1, len(ep.steps), Q, A), dtype=torch.float32, device=dev)
+        s0 = 0
+        for data in DevicePrefetcher(ep, device=dev if on_gpu else None):
+            a_hat = _replay_query(policy, data, use_depth, use_pcd, vq_sampler)
+            table[0, s0:s0 + a_hat.shape[0]] = a_hat
+            s0 += a_hat.shape[0]
+        n_frames += s0
+        if temporal_agg:
+            raw = torch.as_tensor(episode_ensemble(table, None, 0.01)).to(torch.float64)            # [1, T, A]
+        else:
+            raw = table.reshape(1, -1, A)[:, :T].to(torch.float64)                                  # reference :392
+        idx = np.arange(T)
+        if align == "train" and not ep.is_sim:
+            idx = np.maximum(0, idx - 1)                                                             # utils.py:112-114
+        target = np.ascontiguousarray(ep.actions[idx])[None]                                         # [1, T, A] f32, file units
+        pred, st = action_error(raw, torch.from_numpy(target), None, mean, std)
+        st = torch.as_tensor(st).to(torch.float64).cpu().reshape(1, 3 * A)
+        local_rows.append(torch.cat([torch.tensor([[float(T)]], dtype=torch.float64), st], dim=1))
+        if save_episode:
+            local_pt.append(torch.cat([torch.as_tensor(pred).to(torch.float64).cpu().reshape(T, A),
+                                       torch.from_numpy(target[0]).to(torch.float64)], dim=1))
+        if engine is not None and hasattr(engine, "check_flags") and on_gpu:
+            engine.check_flags()
+    if verbose and n_frames:
+        print(f"rank {rank}: replayed episodes {lo}..{hi - 1}, {n_frames} queries in batches of {batch}, "
+              f"{n_frames / max(time.time() - time0, 1e-9):.1f} frames/s")
+
+    local = torch.cat(local_rows, dim=0) if local_rows else torch.zeros((0, 1 + 3 * A), dtype=torch.float64)
+    rows = _gather_rows_f64(local, [b - a for a, b in spans]).numpy()
+    result = replay_metrics(rows, A)
+    result.update(align=align, temporal_agg=bool(temporal_agg), num_queries=Q, files=[os.path.relpath(f, dataset_dir) for f in files])
+    if save_episode:
+        Ts = rows[:, 0].astype(np.int64)
+        per_rank = [int(Ts[a:b].sum()) for a, b in spans]
+        mine = torch.cat(local_pt, dim=0) if local_pt else torch.zeros((0, 2 * A), dtype=torch.float64)
+        allpt = _gather_rows_f64(mine, per_rank).numpy()
+        if rank == 0:
+            os.makedirs(ckpt_dir, exist_ok=True)
+            stem = "replay_" + ckpt_name.split(".")[0]
+            off = 0
+            for i, T in enumerate(Ts):
+                np.savez(os.path.join(ckpt_dir, f"{stem}_ep{i}.npz"), pred=allpt[off:off + T, :A],
+                         target=allpt[off:off + T, A:].astype(np.float32))
+                off += int(T)
+            with open(os.path.join(ckpt_dir, stem + ".json"), "w") as f:
+                json.dump(result, f, indent=1)
+    if verbose and rank == 0:
+        print(f"\nOpen-loop replay of {n} episodes ({result['steps']} steps, align={align}, "
+              f"{'temporal ensemble' if temporal_agg else 'chunk by chunk'}), action units:")
+        print("joint      MAE       RMSE        max")
+        for a in range(A):
+            print(f"{a:5d} {result['mae'][a]:10.5f} {result['rmse'][a]:10.5f} {result['max'][a]:10.5f}")
+        print(f" mean {result['mae_mean']:10.5f} {result['rmse_mean']:10.5f} {result['max_max']:10.5f} (max)")
+    return result
 
 
 def _augment_frames(augment, image_data, depth_data=None):
@@ -552,7 +743,9 @@ def build_config(args):
             "policy_config": policy_config, "task_name": task_name, "seed": args["seed"],
             "temporal_agg": args["temporal_agg"], "camera_names": camera_names, "real_robot": False,
             "load_pretrain": bool(args.get("load_pretrain", False)), "pretrain_ckpt_path": args.get("pretrain_ckpt_path"),
-            "synthetic_env": bool(args.get("synthetic_env", False))}
+            "synthetic_env": bool(args.get("synthetic_env", False)),
+            "dataset_dir": args.get("dataset_dir") or task_config.get("dataset_dir"),
+            "skip_mirrored_data": bool(args.get("skip_mirrored_data", False))}
     if args.get("use_pcd"):
         config["pointcloud_names"] = list(task_config["pointcloud_names"])
     if args.get("augment_images"):
@@ -568,6 +761,11 @@ def main(args):
     if rank == 0:
         with open(os.path.join(config["ckpt_dir"], "config.pkl"), "wb") as f:
             pickle.dump(config, f)
+    if args["eval"] and args.get("replay"):
+        # open-loop replay on recorded episodes: what a use_depth / use_pcd policy (no simulator renders its inputs) and a policy
+        # trained on real-robot episodes can be evaluated with
+        return replay_bc(config, "policy_last.ckpt", episodes=args.get("replay_episodes"),
+                         align=args.get("replay_align") or "train", save_episode=True)
     if args["eval"]:
         results = []
         for ckpt_name in ["policy_last.ckpt"]:
@@ -662,6 +860,13 @@ def make_parser():
                              "(throughput / plumbing runs; its success rates are not task results)")
     parser.add_argument("--dataset_dir", action="store", type=str, default=None,
                         help="episode files (reference HDF5 layout, or .npz with the same keys); default: the task's dataset_dir")
+    parser.add_argument("--replay", action="store_true",
+                        help="with --eval: open-loop replay on the recorded episodes of --dataset_dir (replay_bc) instead of simulator "
+                             "rollouts: per-joint MAE / RMSE / max of the executed against the recorded actions")
+    parser.add_argument("--replay_episodes", action="store", type=int, default=None, help="--replay: only the first N episode files")
+    parser.add_argument("--replay_align", action="store", type=str, default="train", choices=["train", "none"],
+                        help="--replay: compare step t with the action the dataset trains slot 0 on (train: action[t-1] for "
+                             "real-robot episodes) or with action[t] (none)")
     parser.add_argument("--augment_images", action="store_true",
                         help="ACT training only, opt-in: the reference dataset's augmentation (random 0.95 crop resized back, rotation "
                              "within 5 degrees, brightness / contrast / saturation jitter) on the device, for training batches; the "

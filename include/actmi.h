@@ -352,6 +352,20 @@ int actmi_wait_grad_phase(actmi_handle h, int phase, void* stream);
 int actmi_ensemble_step(float* ring, int32_t* tcount, const float* chunk, double k, double* out, uint8_t* populated,
                         int E, int Q, int A, void* stream);
 
+/* ---- open-loop replay of recorded episodes ------------------------------------------------------------ */
+/* The ensemble of EVERY step of E episodes in one launch.  chunks [E][T][Q][A] f32: row (e, r) is the chunk predicted from
+ * frame r; lengths [E] i32, the valid steps T_e <= T of each episode (NULL: all T); out [E][T][A] f64; populated [E][T][Q] u8
+ * or NULL (row j of step t is r = t-(Q-1)+j, oldest first).  Step t of episode e equals the t-th actmi_ensemble_step call
+ * on the same chunks bit for bit (one device function serves both); rows t >= T_e of out and populated are zeros.
+ * A <= 64 and the Q doubles of a step's weights in LDS (Q <= 7680), else ACTMI_E_INVALID with a message; nothing is truncated. */
+int actmi_op_ensemble_episode(const float* chunks, const int32_t* lengths, double k, double* out, uint8_t* populated,
+                              int E, int T, int Q, int A, void* stream);
+/* raw [E][T][A] f64 (normalised actions), target [E][T][A] f32 (recorded actions in file units, already aligned), mean / std
+ * [A] f64; pred [E][T][A] f64 or NULL = raw * std + mean (two roundings); stats [E][3][A] f64 = sum |d|, sum d^2, max |d| over
+ * t < T_e with d = pred - (double)target.  Sums have a fixed shape: two runs give the same bits.  T_e = 0 gives zeros. */
+int actmi_op_action_error(const double* raw, const float* target, const int32_t* lengths, const double* mean, const double* std,
+                          double* pred, double* stats, int E, int T, int A, void* stream);
+
 /* ---- kernel-level entry points (unit tests, external callers) --------------------------------------- */
 int actmi_op_gemm(const actmi_gemm_desc* d, void* stream);
 /* weight preparation for actmi_gemm_desc.b_split: dst = fp16-split image of src * scale (device pointers, may not
