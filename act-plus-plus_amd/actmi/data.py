@@ -30,7 +30,10 @@ Differences, all on the host side of the step:
   cv2 itself (absent here); the Diffusion-only augmentations (torchvision transforms, utils.py:141-156) are not handled.
   Everything else is checked against an independent restatement in ``tests/test_data_pipeline_cpu.py``;
 * ``EpisodeReplay`` reads ONE episode in time order for the open-loop replay evaluation (``imitate_episodes.replay_bc``): the
-  same tensors as ``EpisodicDataset.__getitem__`` without the action chunk, in batches of consecutive steps."""
+  same tensors as ``EpisodicDataset.__getitem__`` without the action chunk, in batches of consecutive steps;
+* ``DeviceEpisodeStore`` (``load_data(..., device_dataset=True)``, opt-in) reads every episode ONCE into a device arena; a
+  training batch is then two device gathers (three with depth) that give the tensors of ``EpisodicDataset.__getitem__`` + the
+  default collation bit for bit, with no host work, loader worker or PCIe traffic per step."""
 import fnmatch
 import os
 
@@ -53,6 +56,20 @@ class _NpzEpisode:
 
     def __getitem__(self, key):
         return self._z[key]          # ndarray: supports [()] and [index] like an h5py dataset
+
+    def meta(self, key):
+        """(shape, dtype) of an entry from its ``.npy`` header: nothing is decompressed"""
+        from numpy.lib import format as fmt
+        with self._z.zip.open(key + ".npy") as f:
+            version = fmt.read_magic(f)
+            if version == (1, 0):
+                shape, _, dtype = fmt.read_array_header_1_0(f)
+            elif version == (2, 0):
+                shape, _, dtype = fmt.read_array_header_2_0(f)
+            else:                                                  # a header this reader does not know: load the entry
+                a = self._z[key]
+                shape, dtype = a.shape, a.dtype
+        return tuple(int(v) for v in shape), np.dtype(dtype)
 
     def __enter__(self):
         return self
@@ -380,10 +397,23 @@ def flatten_list(l):
 def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_size_val, chunk_size,
               skip_mirrored_data=False, load_pretrain=False, policy_class=None, stats_dir_l=None, sample_weights=None,
               train_ratio=0.99, num_workers=2, f32_images=False, rng=None, depth_camera_names=None, use_depth=False,
-              f32_depth=False, pointcloud_names=None, use_pcd=False, max_points=None, pcd_ignore_mask=False):
+              f32_depth=False, pointcloud_names=None, use_pcd=False, max_points=None, pcd_ignore_mask=False,
+              device_dataset=False, device=None, device_budget_bytes=None):
     """utils.py:249-301.  Returns (train_dataloader, val_dataloader, norm_stats, is_sim).  ``use_depth``: the batches are
     5-tuples that end in the depth frames of ``depth_camera_names`` (EpisodicDataset).  ``use_pcd``: 7-tuples that end in the
-    padded clouds and their valid counts (collate_pcd)."""
+    padded clouds and their valid counts (collate_pcd).  ``device_dataset``: both loaders come from ONE ``DeviceEpisodeStore``
+    on ``device`` (default: the current cuda device) that holds the train and validation episodes; the split, the norm stats
+    and the samplers are built as without the flag, so the same ``rng`` gives the same episodes and the same draws, and the
+    batches are the same tensors, already on the device (``loader.on_device``)."""
+    if device_dataset:                                            # refused before any file is read
+        if use_pcd:
+            raise NotImplementedError("--device_dataset with use_pcd: point clouds through the device-resident store are not "
+                                      "implemented (ragged clouds stay on the host loader); drop --device_dataset")
+        if policy_class not in (None, "ACT"):
+            raise NotImplementedError(f"--device_dataset: the device-resident store feeds the ACT training path, not {policy_class!r}")
+        if f32_images or f32_depth:
+            raise NotImplementedError("--device_dataset keeps raw u8 frames and raw uint16 depth: f32_images / f32_depth belong to "
+                                      "the host loader")
     rng = rng or np.random
     if isinstance(dataset_dir_l, str):
         dataset_dir_l = [dataset_dir_l]
@@ -418,6 +448,15 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
                                     chunk_size, policy_class, f32_images, depth_camera_names, use_depth, f32_depth, **pcd_kw)
     val_dataset = EpisodicDataset(dataset_path_list, camera_names, norm_stats, val_episode_ids, val_episode_len,
                                   chunk_size, policy_class, f32_images, depth_camera_names, use_depth, f32_depth, **pcd_kw)
+    if device_dataset:
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        store = DeviceEpisodeStore(dataset_path_list, np.concatenate([train_episode_ids, val_episode_ids]), camera_names, norm_stats,
+                                   device, depth_camera_names, use_depth, device_budget_bytes, use_pcd, policy_class)
+        train_loader = store.loader(train_episode_ids, train_episode_len, chunk_size,
+                                    BatchSampler(batch_size_train, train_episode_len_l, sample_weights, rng))
+        val_loader = store.loader(val_episode_ids, val_episode_len, chunk_size, BatchSampler(batch_size_val, val_episode_len_l, None, rng))
+        return train_loader, val_loader, norm_stats, train_dataset.is_sim
     from torch.utils.data import DataLoader
     kw = dict(pin_memory=torch.cuda.is_available(), num_workers=num_workers)
     if num_workers > 0:
@@ -477,3 +516,337 @@ class DevicePrefetcher:
                 t.record_stream(torch.cuda.current_stream(self.device))
         self._push()
         return batch
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# device-resident episode store (load_data(..., device_dataset=True); DESIGN.md "Device-resident episode store")
+# ---------------------------------------------------------------------------------------------------------------------
+ARENA_ALIGN = 256            # every block of the frame arena (one camera of one episode) starts at a multiple of this
+# Device memory the default budget leaves free: the training handle is created AFTER the loaders (imitate_episodes.main), and
+# with it come the batches, the augmenter's buffers and the allocator's cache.  Measured at B = 64, 4 cameras of 480x640: the
+# free memory drops by 51.5 GB (48 GiB) between the loaded store and the running training step
+# (profiles/device_dataset_time.json, memory_beside_the_store_bytes); 64 GiB leaves a third on top.  Pass budget_bytes /
+# --device_dataset_gb to decide otherwise (a larger batch needs a larger reserve).
+DEVICE_STORE_RESERVE_BYTES = 64 << 30
+
+
+def arena_layout(block_bytes, align=ARENA_ALIGN):
+    """Blocks of ``block_bytes[i]`` bytes back to back, every start padded to ``align`` -> (int64 offsets, total bytes).  Frame t of
+    block i lies at ``offsets[i] + t * frame_bytes``: a multiple of 16 whenever ``frame_bytes`` is one."""
+    offs, total = np.zeros(len(block_bytes), dtype=np.int64), 0
+    for i, n in enumerate(block_bytes):
+        offs[i] = total
+        total += (int(n) + align - 1) // align * align
+    return offs, int(total)
+
+
+def locate_transitions(indices, episode_len):
+    """``EpisodicDataset._locate_transition`` for a batch of flat indices -> (position in ``episode_len`` [B], start_ts [B])"""
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    lens = np.asarray(episode_len, dtype=np.int64)
+    cum = np.cumsum(lens)
+    if len(idx) and (idx.min() < 0 or idx.max() >= cum[-1]):
+        raise IndexError(f"flat index outside [0, {int(cum[-1])})")
+    ei = np.searchsorted(cum, idx, side="right")                  # the first episode whose cumulative length exceeds the index
+    return ei, idx - (cum[ei] - lens[ei])
+
+
+def _entry_meta(root, key):
+    """(shape, dtype) of an episode entry without reading it where the format allows (an .npy header, an h5py handle)"""
+    if hasattr(root, "meta"):
+        return root.meta(key)
+    d = root[key]
+    return tuple(int(v) for v in d.shape), np.dtype(d.dtype)
+
+
+class DeviceEpisodeStore:
+    """Every frame of the named episodes in ONE device arena, read from the files once; a training batch is then a device-to-device
+    gather (``actmi.ops.gather_frames`` / ``gather_chunks``) and equals what ``EpisodicDataset.__getitem__`` + the default
+    collation give for the same flat indices, bit for bit and dtype for dtype.
+
+    Arena: per episode (in ``episode_ids`` order, duplicates dropped), per camera of ``camera_names`` one u8 ``[T, H, W, 3]`` block,
+    then with ``use_depth`` per depth camera one raw uint16 ``[T, H, W]`` block (channel 0 of 3-D frames, as ``_depth_data`` keeps);
+    block starts padded to 256 bytes (``arena_layout``).  Compressed episodes are decoded once (``imdecode_bgr``).  The blocks reach
+    the device through two bounded pinned staging buffers of ``stage_bytes``, never a pinned copy of an episode.  Actions and qpos
+    (float32 as the dataset converts them, ``/base_action`` columns included), the episode table and the four stat vectors are
+    small device arrays.
+
+    Refused before anything large is allocated: ``use_pcd`` and a policy class other than ACT (``NotImplementedError``), depth that
+    is not an unsigned integer of at most 16 bits, cameras or episodes whose frame sizes differ (``ValueError``), and a dataset
+    larger than the budget (``MemoryError`` naming both numbers).  ``budget_bytes`` None: the device's free memory now minus
+    ``DEVICE_STORE_RESERVE_BYTES``.  The sizes come from the entries' headers (the first episode's frame shape for a compressed
+    dataset) and every block is checked against them again as it is loaded.
+
+    Every rank of a data-parallel run holds its own full store."""
+
+    RING = 4                 # pinned index blocks in flight: a block is rewritten only after its copy has executed
+
+    def __init__(self, dataset_path_list, episode_ids, camera_names, norm_stats, device, depth_camera_names=None, use_depth=False,
+                 budget_bytes=None, use_pcd=False, policy_class="ACT", stage_bytes=64 << 20):
+        if use_pcd:
+            raise NotImplementedError("--device_dataset with use_pcd: point clouds through the device-resident store are not "
+                                      "implemented (ragged clouds stay on the host loader); drop --device_dataset")
+        if policy_class not in (None, "ACT"):
+            raise NotImplementedError(f"--device_dataset: the device-resident store feeds the ACT training path, not {policy_class!r}")
+        self.camera_names = list(camera_names)
+        self.use_depth = bool(use_depth)
+        self.depth_camera_names = list(depth_camera_names) if depth_camera_names else []
+        if self.use_depth and not self.depth_camera_names:
+            raise ValueError("use_depth needs depth_camera_names (the task config's list of /observations/depth_images/<cam>)")
+        if not self.camera_names:
+            raise ValueError("DeviceEpisodeStore: no camera names")
+        self.episode_ids = list(dict.fromkeys(int(i) for i in episode_ids))
+        if not self.episode_ids:
+            raise ValueError("DeviceEpisodeStore: no episodes")
+        self.paths = [dataset_path_list[i] for i in self.episode_ids]
+        self._local_of = {e: i for i, e in enumerate(self.episode_ids)}
+        self.device = device
+        self.stage_bytes = int(stage_bytes)
+        self._plan()
+        if budget_bytes is None:
+            free, _total = torch.cuda.mem_get_info(torch.device(device))
+            budget_bytes = free - DEVICE_STORE_RESERVE_BYTES
+        self.budget_bytes = int(budget_bytes)
+        if self.nbytes > self.budget_bytes:
+            raise MemoryError(f"DeviceEpisodeStore: {len(self.paths)} episodes need {self.nbytes} bytes on the device "
+                              f"({self.nbytes / 2**30:.2f} GiB), the budget is {self.budget_bytes} bytes "
+                              f"({self.budget_bytes / 2**30:.2f} GiB): train without --device_dataset, or raise --device_dataset_gb")
+        self._load(norm_stats)
+
+    # ---- sizes, from the headers ---------------------------------------------------------------------------------
+    def _plan(self):
+        K, Kd = len(self.camera_names), len(self.depth_camera_names) if self.use_depth else 0
+        self.T = np.zeros(len(self.paths), dtype=np.int64)
+        self.frame_shape = self.depth_shape = None
+        self.compressed = []
+        for i, path in enumerate(self.paths):
+            with open_episode(path) as root:
+                compressed = bool(root.attrs.get("compress", False))
+                self.compressed.append(compressed)
+                self.T[i] = _entry_meta(root, "/action")[0][0]
+                if self.T[i] < 1:
+                    raise ValueError(f"{path}: empty episode")
+                for kind, cams, want in (("images", self.camera_names, 4), ("depth_images", self.depth_camera_names[:Kd], None)):
+                    for cam in cams:
+                        key = f"/observations/{kind}/{cam}"
+                        shape, dtype = _entry_meta(root, key)
+                        if shape[0] != self.T[i]:
+                            raise ValueError(f"{path}: {key} holds {shape[0]} frames for an episode of {int(self.T[i])} steps")
+                        if compressed:
+                            if i > 0:
+                                continue                           # sized by the first episode's frames; checked as it is decoded
+                            fshape, dtype = imdecode_bgr(np.asarray(root[key][0])).shape, np.dtype(np.uint8)
+                        else:
+                            fshape = shape[1:]
+                        if kind == "images":
+                            if dtype != np.uint8 or len(fshape) != 3 or fshape[2] != 3:
+                                raise ValueError(f"{path}: {key} frames are {dtype} {fshape}, expected uint8 [H, W, 3]")
+                            fshape = tuple(fshape)
+                            if self.frame_shape not in (None, fshape):
+                                raise ValueError(f"{path}: {key} frames are {fshape}, others {self.frame_shape}: one batch shape only")
+                            self.frame_shape = fshape
+                        else:
+                            if dtype.kind != "u" or dtype.itemsize > 2:
+                                raise ValueError(f"{path}: {key} is {dtype}: the device-resident store keeps raw depth, an unsigned "
+                                                 f"integer of at most 16 bits (float depth is normalised on the host: train "
+                                                 f"without --device_dataset)")
+                            if len(fshape) not in (2, 3):
+                                raise ValueError(f"{path}: {key} frames are {fshape}, expected [H, W] or [H, W, C]")
+                            fshape = tuple(fshape[:2])
+                            if self.depth_shape not in (None, fshape):
+                                raise ValueError(f"{path}: {key} frames are {fshape}, others {self.depth_shape}: one batch shape only")
+                            self.depth_shape = fshape
+        self.K, self.Kd = K, Kd
+        self.frame_bytes = int(np.prod(self.frame_shape))
+        self.depth_bytes = int(np.prod(self.depth_shape)) * 2 if Kd else 0
+        blocks = []
+        for T in self.T:
+            blocks += [int(T) * self.frame_bytes] * K + [int(T) * self.depth_bytes] * Kd
+        offs, self.nbytes = arena_layout(blocks)
+        offs = offs.reshape(len(self.paths), K + Kd)
+        self.block_off, self.depth_block_off = offs[:, :K].copy(), offs[:, K:].copy()
+        # the statement the gather's launcher cannot check for itself (actmi_op_gather_frames, `aligned`)
+        self.aligned = 1 if self.frame_bytes % 16 == 0 else 0
+        self.depth_aligned = 1 if Kd and self.depth_bytes % 16 == 0 else 0
+        self.row0 = np.concatenate([[0], np.cumsum(self.T)[:-1]]).astype(np.int64)
+
+    # ---- the one read of every episode ----------------------------------------------------------------------------
+    def _load(self, norm_stats):
+        from . import ops
+        import time
+        dev = torch.device(self.device)
+        t_begin = time.perf_counter()
+        self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        stage = max(self.stage_bytes, self.frame_bytes, self.depth_bytes)
+        self._pin = [torch.empty(stage, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self._pin_ev, self._pin_i = [None, None], 0
+        actions, qposes, sims = [], [], []
+        for i, path in enumerate(self.paths):
+            T = int(self.T[i])
+            with open_episode(path) as raw:
+                root = _EpisodeArrays(raw)
+                attrs = root.attrs
+                sims.append(bool(attrs["sim"]) if "sim" in attrs else False)
+                action = np.asarray(_read_action(root))
+                qpos = np.asarray(root["/observations/qpos"][()])
+                if action.ndim != 2 or action.shape[0] != T or qpos.ndim != 2 or qpos.shape[0] != T:
+                    raise ValueError(f"{path}: action {action.shape} / qpos {qpos.shape} for an episode of {T} steps")
+                actions.append(action.astype(np.float32))            # padded_action is float32: the assignment converts
+                qposes.append(torch.from_numpy(qpos).float().numpy())
+                for k, cam in enumerate(self.camera_names):
+                    self._load_block(root[f"/observations/images/{cam}"], T, self.compressed[i], int(self.block_off[i, k]), False,
+                                     f"{path}: /observations/images/{cam}")
+                for k, cam in enumerate(self.depth_camera_names[:self.Kd]):
+                    self._load_block(root[f"/observations/depth_images/{cam}"], T, self.compressed[i],
+                                     int(self.depth_block_off[i, k]), True, f"{path}: /observations/depth_images/{cam}")
+        A, S = actions[0].shape[1], qposes[0].shape[1]
+        if any(a.shape[1] != A for a in actions) or any(q.shape[1] != S for q in qposes):
+            raise ValueError("DeviceEpisodeStore: episodes differ in their action or qpos width")
+        self.A, self.S = int(A), int(S)
+        self.actions = torch.from_numpy(np.concatenate(actions, axis=0)).to(dev)
+        self.qpos = torch.from_numpy(np.concatenate(qposes, axis=0)).to(dev)
+        rec = np.zeros(len(self.paths), dtype=ops.episode_rec_dtype())
+        rec["row0"], rec["T"], rec["is_sim"] = self.row0, self.T, np.asarray(sims, dtype=np.int32)
+        self.is_sim = sims
+        self.episodes = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+        self._stats = [torch.as_tensor(np.asarray(norm_stats[k]), dtype=torch.float32).reshape(-1).contiguous().to(dev)
+                       for k in ("action_mean", "action_std", "qpos_mean", "qpos_std")]
+        if self._stats[0].numel() != self.A or self._stats[2].numel() != self.S:
+            raise ValueError(f"DeviceEpisodeStore: norm stats of {self._stats[0].numel()} action / {self._stats[2].numel()} qpos "
+                             f"values for episodes of {self.A} / {self.S}")
+        torch.cuda.synchronize(dev)
+        self._pin = self._pin_ev = None                               # the staging buffers are the load's alone
+        self.load_seconds = time.perf_counter() - t_begin
+        self._host, self._host_ev, self._slot = [None] * self.RING, [None] * self.RING, 0
+
+    def _stage(self, dst_off, nbytes, fill):
+        """one piece through the staging pair: ``fill(view)`` writes `nbytes` bytes into the pinned view, which is then copied to
+        the arena; a buffer is refilled only after the copy that read it has executed"""
+        j = self._pin_i
+        self._pin_i = 1 - j
+        if self._pin_ev[j] is not None:
+            self._pin_ev[j].synchronize()
+        fill(self._pin[j].numpy()[:nbytes])
+        self.arena[dst_off:dst_off + nbytes].copy_(self._pin[j][:nbytes], non_blocking=True)
+        self._pin_ev[j] = torch.cuda.Event()
+        self._pin_ev[j].record(torch.cuda.current_stream(self.arena.device))
+
+    def _load_block(self, entry, T, compressed, dst_off, depth, where):
+        fb = self.depth_bytes if depth else self.frame_bytes
+        shape = self.depth_shape if depth else self.frame_shape
+        per = max(1, self._pin[0].numel() // fb)
+        for t0 in range(0, T, per):
+            t1 = min(T, t0 + per)
+            piece = np.asarray(entry[t0:t1])
+            if compressed:                                            # utils.py:104-107, frame by frame
+                piece = np.stack([imdecode_bgr(buf) for buf in piece])
+            if depth:
+                if piece.dtype.kind != "u" or piece.dtype.itemsize > 2:
+                    raise ValueError(f"{where} is {piece.dtype}: not raw depth (an unsigned integer of at most 16 bits)")
+                if piece.ndim == 4:
+                    piece = piece[..., 0]                             # _depth_data: a 3-D frame keeps channel 0
+                piece = piece.astype(np.uint16, copy=False)
+            if piece.shape != (t1 - t0,) + tuple(shape) or (not depth and piece.dtype != np.uint8):
+                raise ValueError(f"{where}: frames {piece.dtype} {piece.shape[1:]}, the store was sized for {tuple(shape)}")
+            n = (t1 - t0) * fb
+            if dst_off + t0 * fb + n > self.nbytes:                  # cannot happen with the sizes checked above
+                raise MemoryError(f"{where}: block leaves the arena of {self.nbytes} bytes")
+            flat = np.ascontiguousarray(piece).reshape(-1).view(np.uint8)
+            self._stage(dst_off + t0 * fb, n, lambda view, flat=flat: np.copyto(view, flat))
+
+    # ---- batches --------------------------------------------------------------------------------------------------
+    def device_bytes(self):
+        """bytes of device memory the store holds"""
+        return int(self.arena.numel() + self.actions.numel() * 4 + self.qpos.numel() * 4 + self.episodes.numel() +
+                   sum(s.numel() * 4 for s in self._stats))
+
+    def frame_offsets(self, local_episode, t):
+        """byte offsets into the arena of the frames of samples (local_episode[b], t[b]) -> ([B, K], [B, Kd]) int64"""
+        e, t = np.asarray(local_episode, dtype=np.int64), np.asarray(t, dtype=np.int64)
+        return (self.block_off[e] + t[:, None] * self.frame_bytes,
+                self.depth_block_off[e] + t[:, None] * self.depth_bytes)
+
+    def _upload(self, table):
+        """the int64 index table of one batch -> a device tensor, by a stream-ordered copy from a pinned block of a ring"""
+        n = len(table)
+        i = self._slot
+        self._slot = (i + 1) % self.RING
+        if self._host_ev[i] is not None:
+            self._host_ev[i].synchronize()                             # the copy that last read this block has executed
+        if self._host[i] is None or self._host[i].numel() < n:
+            self._host[i] = torch.empty(max(n, 1024), dtype=torch.int64, pin_memory=True)
+        self._host[i].numpy()[:n] = table
+        dev = self.arena.device
+        tab = torch.empty(n, dtype=torch.int64, device=dev)
+        tab.copy_(self._host[i][:n], non_blocking=True)
+        self._host_ev[i] = torch.cuda.Event()
+        self._host_ev[i].record(torch.cuda.current_stream(dev))
+        return tab
+
+    def gather(self, local_episode, t, Q, nontemporal=True):
+        """the batch of samples (local_episode[b], t[b]) with chunks of Q steps, on the current stream of the store's device:
+        (image u8 [B, K, H, W, 3], qpos f32 [B, S], action f32 [B, Q, A], is_pad bool [B, Q][, depth uint16 [B, Kd, 1, H, W]]).
+        ``nontemporal``: the 16-byte form reads the arena with non-temporal loads -- measured 0.77-0.87 of the plain loads' time at
+        B = 64 and level with them at B = 8 (profiles/device_dataset_time.json); the bytes are the same either way"""
+        from . import ops
+        e, t = np.asarray(local_episode, dtype=np.int64).reshape(-1), np.asarray(t, dtype=np.int64).reshape(-1)
+        B = len(e)
+        if B < 1 or len(t) != B:
+            raise ValueError(f"DeviceEpisodeStore.gather: {B} episodes, {len(t)} steps")
+        if e.min() < 0 or e.max() >= len(self.paths) or t.min() < 0 or np.any(t >= self.T[e]):
+            raise IndexError("DeviceEpisodeStore.gather: a sample outside the stored episodes")
+        off, doff = self.frame_offsets(e, t)
+        samples = np.ascontiguousarray(np.stack([e, t], axis=1).astype(np.int32)).view(np.int64).reshape(-1)
+        nk, nd = B * self.K, B * self.Kd
+        dev = self.arena.device
+        with torch.cuda.device(dev):
+            tab = self._upload(np.concatenate([off.reshape(-1), doff.reshape(-1), samples]))
+            image = torch.empty((B, self.K) + tuple(self.frame_shape), dtype=torch.uint8, device=dev)
+            ops.gather_frames(self.arena, tab[:nk], self.frame_bytes, out=image,
+                              aligned=2 if (nontemporal and self.aligned) else self.aligned)
+            qpos, action, is_pad = ops.gather_chunks(self.actions, self.qpos, self.episodes, tab[nk + nd:].view(torch.int32).view(B, 2),
+                                                     *self._stats, Q)
+            if not self.Kd:
+                return image, qpos, action, is_pad
+            depth = torch.empty((B, self.Kd, 1) + tuple(self.depth_shape), dtype=torch.uint16, device=dev)
+            ops.gather_frames(self.arena, tab[nk:nk + nd], self.depth_bytes, out=depth,
+                              aligned=2 if (nontemporal and self.depth_aligned) else self.depth_aligned)
+        return image, qpos, action, is_pad, depth
+
+    def loader(self, episode_ids, episode_len, chunk_size, batch_sampler):
+        return DeviceBatchLoader(self, episode_ids, episode_len, chunk_size, batch_sampler)
+
+
+class DeviceBatchLoader:
+    """The iterable ``DeviceEpisodeStore.loader`` returns: what a ``DataLoader`` over an ``EpisodicDataset`` of ``episode_ids`` /
+    ``episode_len`` / ``chunk_size`` with this ``batch_sampler`` delivers, as device tensors.  Exactly one index batch is drawn
+    from the sampler per batch delivered, when it is asked for (no look-ahead): samplers that share a generator, as the train and
+    validation samplers of ``load_data`` do, see the same stream of draws as on the host path with ``num_workers=0``."""
+
+    on_device = True
+
+    def __init__(self, store, episode_ids, episode_len, chunk_size, batch_sampler):
+        self.store = store
+        ids = [int(i) for i in episode_ids]
+        missing = [i for i in ids if i not in store._local_of]
+        if missing:
+            raise ValueError(f"DeviceBatchLoader: episodes {missing} are not in the store")
+        self.local = np.asarray([store._local_of[i] for i in ids], dtype=np.int64)
+        self.episode_len = [int(n) for n in episode_len]
+        if len(self.episode_len) != len(ids) or np.any(store.T[self.local] != np.asarray(self.episode_len)):
+            raise ValueError("DeviceBatchLoader: episode_len does not match the stored episodes")
+        # padded_action[:chunk_size] of a max_episode_len-row table (EpisodicDataset.__getitem__)
+        self.Q = min(int(chunk_size), max(self.episode_len))
+        self.batch_sampler = iter(batch_sampler)
+
+    def locate(self, indices):
+        """flat dataset indices -> (the store's episode numbers, start_ts), as ``EpisodicDataset._locate_transition``"""
+        ei, t = locate_transitions(indices, self.episode_len)
+        return self.local[ei], t
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        e, t = self.locate(next(self.batch_sampler))
+        return self.store.gather(e, t, self.Q)

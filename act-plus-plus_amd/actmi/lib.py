@@ -126,6 +126,18 @@ class AugmentDesc(C.Structure):
                [(k, C.c_int32) for k in ("B", "K", "H", "W", "ch", "cw")]
 
 
+class EpisodeRec(C.Structure):
+    # actmi_episode_rec: one entry of the device episode table, 16 bytes
+    _fields_ = [("row0", C.c_int64), ("T", C.c_int32), ("is_sim", C.c_int32)]
+
+
+class GatherChunksDesc(C.Structure):
+    # actmi_gather_chunks_desc
+    _fields_ = [(k, C.c_void_p) for k in ("actions", "qpos", "episodes", "samples", "action_mean", "action_std", "qpos_mean",
+                                          "qpos_std", "qpos_out", "action_out", "is_pad")] + \
+               [("n_rows", C.c_int64)] + [(k, C.c_int32) for k in ("n_episodes", "B", "A", "S", "Q")]
+
+
 _lib = None
 
 
@@ -223,6 +235,8 @@ def load():
         "actmi_op_augment_workspace_bytes": ([i32, i32, i32, i32], C.c_int64),
         "actmi_op_augment_u8": ([C.POINTER(AugmentDesc), vp], i32),
         "actmi_op_warp_u16": ([C.POINTER(AugmentDesc), vp], i32),
+        "actmi_op_gather_frames": ([vp, i64, vp, vp, i64, i64, i32, vp], i32),
+        "actmi_op_gather_chunks": ([C.POINTER(GatherChunksDesc), vp], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

@@ -1486,3 +1486,102 @@ def action_error_ref(raw, target, lengths, mean, std, want_pred=True):
         if len(de):
             stats[e] = np.stack([de.sum(axis=0), (de * de).sum(axis=0), de.max(axis=0)])
     return (pred if want_pred else None), stats
+
+
+# ---- device-resident episode store (csrc/episode_store.hip; contracts at actmi_op_gather_frames / actmi_op_gather_chunks) ------
+def episode_rec_dtype():
+    """actmi_episode_rec as a numpy structured dtype (16 bytes)"""
+    import numpy as np
+    return np.dtype([("row0", np.int64), ("T", np.int32), ("is_sim", np.int32)])
+
+
+def gather_frames(arena, src_off, item_bytes, out=None, aligned=0):
+    """actmi_op_gather_frames: arena 1-D uint8 cuda, src_off [n] int64 cuda (byte offsets into the arena) -> out [n, item_bytes]
+    uint8 (or the caller's contiguous cuda tensor of n * item_bytes bytes, any dtype and shape).  aligned: 0 general, 1 the
+    caller vouches that every offset is a multiple of 16 (item_bytes, arena and out must be), 2 the same with non-temporal loads."""
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_cuda or not arena.is_contiguous():
+        raise ValueError(f"gather_frames: arena must be a contiguous 1-D uint8 cuda tensor, got {arena.dtype} {tuple(arena.shape)}")
+    if src_off.dtype != torch.int64 or src_off.dim() != 1 or src_off.device != arena.device or not src_off.is_contiguous():
+        raise ValueError("gather_frames: src_off must be a contiguous 1-D int64 tensor on the arena's device")
+    n, item_bytes = int(src_off.numel()), int(item_bytes)
+    if out is None:
+        out = torch.empty((n, item_bytes), dtype=torch.uint8, device=arena.device)
+    elif out.device != arena.device or not out.is_contiguous() or out.numel() * out.element_size() != n * item_bytes:
+        raise ValueError(f"gather_frames: out must be contiguous on {arena.device} and hold {n} x {item_bytes} bytes")
+    with torch.cuda.device(arena.device):
+        L.check(L.load().actmi_op_gather_frames(_p(arena), int(arena.numel()), _p(src_off), _p(out), n, item_bytes, int(aligned),
+                                                L.current_stream_ptr()), None, "op_gather_frames")
+    return out
+
+
+def gather_frames_ref(arena, src_off, item_bytes):
+    """numpy statement of ``gather_frames``; needs no library.  arena: 1-D uint8 ndarray (or CPU tensor), src_off [n] -> [n, item_bytes]
+    uint8; an item whose range leaves the arena is zeros."""
+    import numpy as np
+    a = np.asarray(arena).reshape(-1).view(np.uint8)
+    off = np.asarray(src_off, dtype=np.int64).reshape(-1)
+    n = int(item_bytes)
+    out = np.zeros((len(off), n), dtype=np.uint8)
+    for i, o in enumerate(off):
+        if 0 <= o and o + n <= a.size:
+            out[i] = a[o:o + n]
+    return out
+
+
+def gather_chunks(actions, qpos, episodes, samples, action_mean, action_std, qpos_mean, qpos_std, Q):
+    """actmi_op_gather_chunks.  actions [R, A] / qpos [R, S] f32 cuda (all episodes' rows back to back), episodes: uint8 cuda
+    tensor holding [E] records (episode_rec_dtype), samples [B, 2] int32 cuda (episode, t), the four stat vectors f32 cuda ->
+    (qpos [B, S] f32, action [B, Q, A] f32, is_pad [B, Q] bool)."""
+    dev = actions.device
+    for name, t, dt in (("actions", actions, torch.float32), ("qpos", qpos, torch.float32), ("episodes", episodes, torch.uint8),
+                        ("samples", samples, torch.int32), ("action_mean", action_mean, torch.float32),
+                        ("action_std", action_std, torch.float32), ("qpos_mean", qpos_mean, torch.float32),
+                        ("qpos_std", qpos_std, torch.float32)):
+        if t.dtype != dt or not t.is_cuda or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"gather_chunks: {name} must be a contiguous {dt} tensor on {dev}, got {t.dtype} on {t.device}")
+    if actions.dim() != 2 or qpos.dim() != 2 or qpos.shape[0] != actions.shape[0]:
+        raise ValueError(f"gather_chunks: actions {tuple(actions.shape)} and qpos {tuple(qpos.shape)} must be [R, A] and [R, S]")
+    R, A, S = int(actions.shape[0]), int(actions.shape[1]), int(qpos.shape[1])
+    if samples.dim() != 2 or samples.shape[1] != 2 or episodes.numel() % 16 or episodes.numel() == 0:
+        raise ValueError("gather_chunks: samples must be [B, 2] and episodes a whole number of 16-byte records")
+    if action_mean.numel() != A or action_std.numel() != A or qpos_mean.numel() != S or qpos_std.numel() != S:
+        raise ValueError(f"gather_chunks: the stat vectors must hold {A} (action) and {S} (qpos) values")
+    B, Q = int(samples.shape[0]), int(Q)
+    qpos_out = torch.empty((B, S), dtype=torch.float32, device=dev)
+    action_out = torch.empty((B, Q, A), dtype=torch.float32, device=dev)
+    is_pad = torch.empty((B, Q), dtype=torch.bool, device=dev)
+    d = L.GatherChunksDesc()
+    d.actions, d.qpos, d.episodes, d.samples = actions.data_ptr(), qpos.data_ptr(), episodes.data_ptr(), samples.data_ptr()
+    d.action_mean, d.action_std, d.qpos_mean, d.qpos_std = (t.data_ptr() for t in (action_mean, action_std, qpos_mean, qpos_std))
+    d.qpos_out, d.action_out, d.is_pad = qpos_out.data_ptr(), action_out.data_ptr(), is_pad.data_ptr()
+    d.n_rows, d.n_episodes, d.B, d.A, d.S, d.Q = R, episodes.numel() // 16, B, A, S, Q
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_gather_chunks(C.byref(d), L.current_stream_ptr()), None, "op_gather_chunks")
+    return qpos_out, action_out, is_pad
+
+
+def gather_chunks_ref(actions, qpos, episodes, samples, action_mean, action_std, qpos_mean, qpos_std, Q):
+    """numpy statement of ``gather_chunks`` (EpisodicDataset.__getitem__ without the frames, for B samples); needs no library.
+    episodes: [E] records (episode_rec_dtype) or rows (row0, T, is_sim); samples [B, 2] -> (qpos [B, S] f32, action [B, Q, A] f32,
+    is_pad [B, Q] bool).  float32 subtract, then float32 divide: numpy's are the IEEE operations torch's are."""
+    import numpy as np
+    a, q = np.asarray(actions, dtype=np.float32), np.asarray(qpos, dtype=np.float32)
+    ep = np.asarray(episodes)
+    if ep.dtype.names:
+        ep = np.stack([ep["row0"].astype(np.int64), ep["T"].astype(np.int64), ep["is_sim"].astype(np.int64)], axis=1)
+    smp = np.asarray(samples, dtype=np.int64).reshape(-1, 2)
+    am, asd, qm, qsd = (np.asarray(v, dtype=np.float32).reshape(-1) for v in (action_mean, action_std, qpos_mean, qpos_std))
+    B, Q, A = len(smp), int(Q), a.shape[1]
+    qpos_out = np.empty((B, q.shape[1]), dtype=np.float32)
+    action_out = np.empty((B, Q, A), dtype=np.float32)
+    is_pad = np.zeros((B, Q), dtype=bool)
+    for b, (e, t) in enumerate(smp):
+        row0, T, is_sim = (int(v) for v in ep[e])
+        s = t if is_sim else max(0, t - 1)
+        n = min(T - s, Q)
+        rows = np.zeros((Q, A), dtype=np.float32)
+        rows[:n] = a[row0 + s:row0 + s + n]
+        qpos_out[b] = (q[row0 + t] - qm) / qsd
+        action_out[b] = (rows - am) / asd
+        is_pad[b, n:] = True
+    return qpos_out, action_out, is_pad

@@ -452,6 +452,20 @@ int actmi_op_warp_u16(const actmi_augment_desc* d, void* stream) {
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
 }
 
+int actmi_op_gather_frames(const void* arena, int64_t arena_bytes, const int64_t* src_off, void* out, int64_t n_items,
+                           int64_t item_bytes, int aligned, void* stream) {
+    g_op_error.clear();
+    const int rc = launch_gather_frames(arena, arena_bytes, src_off, out, n_items, item_bytes, aligned, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
+int actmi_op_gather_chunks(const actmi_gather_chunks_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "gather_chunks: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_gather_chunks(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int64_t n_per_sample, void* stream) {
     g_op_error.clear();
     const int rc = launch_depth_minmax_u16(depth, lohi_out, B, n_per_sample, S(stream));

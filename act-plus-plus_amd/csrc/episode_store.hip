@@ -1,0 +1,169 @@
+// Device-resident episode store: a training batch gathered on the device (actmi_op_gather_frames, actmi_op_gather_chunks; the
+// contract is at their declarations in actmi.h).  The frames of every episode sit in one u8 arena; a batch is n_items contiguous
+// pieces of it copied to a contiguous output, plus the z-scored qpos rows and action chunks EpisodicDataset.__getitem__ computes.
+#include "common.h"
+
+namespace {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int GF_BLOCK = 256;
+constexpr int GF_UNROLL = 4;                               // 16-byte loads a lane has in flight
+constexpr int64_t GF_STEP = (int64_t)GF_BLOCK * GF_UNROLL; // 16-byte words one workgroup moves per loop step (16 KiB)
+
+// the bytes [b0, b1) of one item, byte by byte: any address
+__device__ __forceinline__ void gf_copy_bytes(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int64_t b0, int64_t b1) {
+    for (int64_t i = b0 + threadIdx.x; i < b1; i += GF_BLOCK) dst[i] = src[i];
+}
+
+// the share [lo, hi) of `n` units that split `s` of `ns` takes, in whole multiples of `quantum` units (the last share takes the rest)
+__device__ __forceinline__ void gf_share(int64_t n, int64_t quantum, int s, int ns, int64_t* lo, int64_t* hi) {
+    const int64_t per = ((n + ns - 1) / ns + quantum - 1) / quantum * quantum;
+    const int64_t a = per * s, b = a + per;
+    *lo = a < n ? a : n;
+    *hi = b < n ? b : n;
+}
+
+// grid (splits, items).  An item whose source range leaves the arena is zero-filled, never read.  Fast form: item_bytes % 16 == 0 and
+// 16-byte aligned base pointers are the launcher's; the offset is looked at here, and an item whose offset is not a multiple of
+// 16 goes byte by byte like the general form (uniform over the workgroup).
+template <bool NT>
+__global__ __launch_bounds__(GF_BLOCK) void gather_frames_v16_kernel(const uint8_t* __restrict__ arena, int64_t arena_bytes,
+                                                                     const int64_t* __restrict__ src_off, uint8_t* __restrict__ out,
+                                                                     int64_t item_bytes) {
+    const int64_t item = blockIdx.y;
+    const int64_t off = src_off[item];
+    uint8_t* dst = out + item * item_bytes;
+    const bool inside = off >= 0 && off <= arena_bytes - item_bytes;
+    const int64_t nvec = item_bytes >> 4;
+    int64_t v0, v1;
+    gf_share(nvec, GF_BLOCK, blockIdx.x, gridDim.x, &v0, &v1);
+    if (!inside) {
+        u32x4* d = reinterpret_cast<u32x4*>(dst);
+        for (int64_t v = v0 + threadIdx.x; v < v1; v += GF_BLOCK) d[v] = u32x4{0u, 0u, 0u, 0u};
+        return;
+    }
+    const uint8_t* src = arena + off;
+    if (off & 15) {
+        gf_copy_bytes(src, dst, v0 << 4, v1 << 4);
+        return;
+    }
+    const u32x4* s = reinterpret_cast<const u32x4*>(src);
+    u32x4* d = reinterpret_cast<u32x4*>(dst);
+    int64_t v = v0 + threadIdx.x;
+    for (; v + (GF_UNROLL - 1) * GF_BLOCK < v1; v += GF_STEP) {
+        u32x4 r[GF_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GF_UNROLL; ++u) r[u] = NT ? __builtin_nontemporal_load(s + v + u * GF_BLOCK) : s[v + u * GF_BLOCK];
+#pragma unroll
+        for (int u = 0; u < GF_UNROLL; ++u) d[v + u * GF_BLOCK] = r[u];
+    }
+    for (; v < v1; v += GF_BLOCK) d[v] = NT ? __builtin_nontemporal_load(s + v) : s[v];
+}
+
+__global__ __launch_bounds__(GF_BLOCK) void gather_frames_bytes_kernel(const uint8_t* __restrict__ arena, int64_t arena_bytes,
+                                                                       const int64_t* __restrict__ src_off, uint8_t* __restrict__ out,
+                                                                       int64_t item_bytes) {
+    const int64_t item = blockIdx.y;
+    const int64_t off = src_off[item];
+    uint8_t* dst = out + item * item_bytes;
+    int64_t b0, b1;
+    gf_share(item_bytes, GF_BLOCK, blockIdx.x, gridDim.x, &b0, &b1);
+    if (off < 0 || off > arena_bytes - item_bytes) {
+        for (int64_t i = b0 + threadIdx.x; i < b1; i += GF_BLOCK) dst[i] = 0;
+        return;
+    }
+    gf_copy_bytes(arena + off, dst, b0, b1);
+}
+
+// One workgroup per sample.  Every value is one fp32 subtract and one correctly rounded fp32 divide, as torch computes
+// (x - mean) / std on the host: no reciprocal, nothing fused.
+__global__ __launch_bounds__(256) void gather_chunks_kernel(const float* __restrict__ actions, const float* __restrict__ qpos,
+                                                            const actmi_episode_rec* __restrict__ episodes, int n_episodes,
+                                                            int64_t n_rows, const int32_t* __restrict__ samples,
+                                                            const float* __restrict__ action_mean, const float* __restrict__ action_std,
+                                                            const float* __restrict__ qpos_mean, const float* __restrict__ qpos_std,
+                                                            float* __restrict__ qpos_out, float* __restrict__ action_out,
+                                                            uint8_t* __restrict__ is_pad, int A, int S, int Q) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    // what the sample table names is held to the episode table and the row arrays: a wild entry reads a valid row, never past one
+    int e = samples[2 * b], t = samples[2 * b + 1];
+    e = e < 0 ? 0 : (e >= n_episodes ? n_episodes - 1 : e);
+    const actmi_episode_rec ep = episodes[e];
+    int64_t row0 = ep.row0 < 0 ? 0 : (ep.row0 >= n_rows ? n_rows - 1 : ep.row0);
+    int64_t T = ep.T < 1 ? 1 : ep.T;
+    if (T > n_rows - row0) T = n_rows - row0;
+    t = t < 0 ? 0 : (t >= T ? (int)(T - 1) : t);
+    const int s = ep.is_sim ? t : (t > 0 ? t - 1 : 0);
+    const int64_t len = T - s;
+    const float* qrow = qpos + (row0 + t) * S;
+    for (int i = tid; i < S; i += 256) qpos_out[(int64_t)b * S + i] = __fdiv_rn(__fsub_rn(qrow[i], qpos_mean[i]), qpos_std[i]);
+    const float* arow = actions + (row0 + s) * A;
+    float* ao = action_out + (int64_t)b * Q * A;
+    for (int i = tid; i < Q * A; i += 256) {
+        const int j = i / A, c = i - j * A;
+        const float x = j < len ? arow[(int64_t)j * A + c] : 0.f;      // the dataset normalises its zero padding too
+        ao[i] = __fdiv_rn(__fsub_rn(x, action_mean[c]), action_std[c]);
+    }
+    for (int j = tid; j < Q; j += 256) is_pad[(int64_t)b * Q + j] = j >= len ? 1 : 0;
+}
+
+}  // namespace
+
+int launch_gather_frames(const void* arena, int64_t arena_bytes, const int64_t* src_off, void* out, int64_t n_items,
+                         int64_t item_bytes, int aligned, hipStream_t st, std::string* err) {
+    auto fail = [&](const char* m) { if (err) *err = m; return -2; };
+    if (n_items == 0 || item_bytes == 0) return 0;
+    if (n_items < 0 || item_bytes < 0 || arena_bytes < 0) return fail("gather_frames: negative size");
+    if (!arena || !src_off || !out) return fail("gather_frames: null pointer");
+    if (n_items > 65535) return fail("gather_frames: n_items > 65535");
+    if ((uintptr_t)src_off & 7) return fail("gather_frames: src_off must be 8-byte aligned");
+    if (aligned < 0 || aligned > 2) return fail("gather_frames: aligned must be 0, 1 or 2");
+    if (aligned && ((item_bytes & 15) || ((uintptr_t)arena & 15) || ((uintptr_t)out & 15)))
+        return fail("gather_frames: the aligned form needs item_bytes, arena and out to be multiples of 16");
+    // enough workgroups that a batch of 8 fills the chip (about 2048 in all), none with less than one 16 KiB loop step
+    const int64_t units = aligned ? item_bytes >> 4 : item_bytes;
+    const int64_t max_splits = (units + GF_STEP - 1) / GF_STEP;
+    int64_t splits = (2048 + n_items - 1) / n_items;
+    splits = splits > max_splits ? max_splits : splits;
+    splits = splits < 1 ? 1 : splits;
+    const dim3 grid((unsigned)splits, (unsigned)n_items), block(GF_BLOCK);
+    const uint8_t* a = static_cast<const uint8_t*>(arena);
+    uint8_t* o = static_cast<uint8_t*>(out);
+    const double bytes = 2.0 * (double)n_items * (double)item_bytes;
+    if (aligned == 2) {
+        prof_begin("gather_frames_v16_nt", 0.0, bytes, st);
+        hipLaunchKernelGGL(gather_frames_v16_kernel<true>, grid, block, 0, st, a, arena_bytes, src_off, o, item_bytes);
+    } else if (aligned == 1) {
+        prof_begin("gather_frames_v16", 0.0, bytes, st);
+        hipLaunchKernelGGL(gather_frames_v16_kernel<false>, grid, block, 0, st, a, arena_bytes, src_off, o, item_bytes);
+    } else {
+        prof_begin("gather_frames_bytes", 0.0, bytes, st);
+        hipLaunchKernelGGL(gather_frames_bytes_kernel, grid, block, 0, st, a, arena_bytes, src_off, o, item_bytes);
+    }
+    prof_end(st);
+    if (hipGetLastError() != hipSuccess) { if (err) *err = "gather_frames: launch failed"; return -3; }
+    return 0;
+}
+
+int launch_gather_chunks(const actmi_gather_chunks_desc& d, hipStream_t st, std::string* err) {
+    auto fail = [&](const char* m) { if (err) *err = m; return -2; };
+    if (d.B == 0) return 0;
+    if (d.B < 0 || d.A < 1 || d.S < 1 || d.Q < 1 || d.n_episodes < 1 || d.n_rows < 1)
+        return fail("gather_chunks: B, A, S, Q, n_episodes and n_rows must be positive");
+    if ((int64_t)d.Q * d.A > ((int64_t)1 << 30)) return fail("gather_chunks: Q * A > 2^30");
+    if (!d.actions || !d.qpos || !d.episodes || !d.samples || !d.action_mean || !d.action_std || !d.qpos_mean || !d.qpos_std ||
+        !d.qpos_out || !d.action_out || !d.is_pad)
+        return fail("gather_chunks: null pointer");
+    if (((uintptr_t)d.actions | (uintptr_t)d.qpos | (uintptr_t)d.samples | (uintptr_t)d.action_mean | (uintptr_t)d.action_std |
+         (uintptr_t)d.qpos_mean | (uintptr_t)d.qpos_std | (uintptr_t)d.qpos_out | (uintptr_t)d.action_out) & 3)
+        return fail("gather_chunks: misaligned pointer (f32 and int32 arrays 4 bytes)");
+    if ((uintptr_t)d.episodes & 7) return fail("gather_chunks: misaligned pointer (episode table 8 bytes)");
+    prof_begin("gather_chunks", 2.0 * d.B * ((double)d.Q * d.A + d.S), 8.0 * d.B * ((double)d.Q * d.A + d.S), st);
+    hipLaunchKernelGGL(gather_chunks_kernel, dim3(d.B), dim3(256), 0, st, d.actions, d.qpos, d.episodes, d.n_episodes, d.n_rows,
+                       d.samples, d.action_mean, d.action_std, d.qpos_mean, d.qpos_std, d.qpos_out, d.action_out, d.is_pad, d.A, d.S,
+                       d.Q);
+    prof_end(st);
+    if (hipGetLastError() != hipSuccess) { if (err) *err = "gather_chunks: launch failed"; return -3; }
+    return 0;
+}

@@ -637,7 +637,10 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
     best_ckpt_info = None
     os.makedirs(ckpt_dir, exist_ok=True)
     from actmi.data import DevicePrefetcher
-    train_dataloader = DevicePrefetcher(repeater(train_dataloader))      # next batch's H2D copy overlaps this step
+    if getattr(train_dataloader, "on_device", False):
+        train_dataloader = iter(train_dataloader)        # --device_dataset: the batches are gathered on the device, nothing to pin or copy
+    else:
+        train_dataloader = DevicePrefetcher(repeater(train_dataloader))      # next batch's H2D copy overlaps this step
     # --augment_images: one device pass over the TRAINING batches just before the stem.  Validation stays un-augmented, so that
     # validation losses of runs with and without the flag compare (the reference's validation set is augmented too: utils.py:153)
     augment = make_augment(config, policy, seed + rank)
@@ -750,13 +753,22 @@ def build_config(args):
         config["pointcloud_names"] = list(task_config["pointcloud_names"])
     if args.get("augment_images"):
         config["augment_images"] = True
+    if args.get("device_dataset"):
+        if policy_class != "ACT":
+            raise NotImplementedError("--device_dataset: the device-resident episode store feeds the ACT training path")
+        if args.get("use_pcd"):
+            raise NotImplementedError("--device_dataset with --use_pcd: point clouds through the device-resident store are not "
+                                      "implemented; drop --device_dataset")
+        config["device_dataset"] = True
+        if args.get("device_dataset_gb") is not None:
+            config["device_dataset_gb"] = float(args["device_dataset_gb"])
     return config
 
 
 def main(args):
     set_seed(1)
     config = build_config(args)
-    rank, world, _ = dist_utils.init_from_env()          # one process per GPU when a launcher set WORLD_SIZE
+    rank, world, local_rank = dist_utils.init_from_env()          # one process per GPU when a launcher set WORLD_SIZE
     os.makedirs(config["ckpt_dir"], exist_ok=True)
     if rank == 0:
         with open(os.path.join(config["ckpt_dir"], "config.pkl"), "wb") as f:
@@ -788,6 +800,9 @@ def main(args):
     if use_pcd and not (dataset_dir and os.path.isdir(dataset_dir)):
         raise ValueError("--use_pcd needs episode files with /observations/pointcloud/<name>/{xyz, rgb} (--dataset_dir): the "
                          "synthetic stand-in dataset holds no point clouds")
+    device_dataset = bool(config.get("device_dataset"))
+    if device_dataset and not (dataset_dir and os.path.isdir(dataset_dir)):
+        raise ValueError("--device_dataset needs episode files (--dataset_dir): the synthetic stand-in dataset is generated, not stored")
     if dataset_dir and os.path.isdir(dataset_dir):
         # reference imitate_episodes.py:141-147: episodes on disk (HDF5 via h5py, or .npz with the same keys), z-scored
         # qpos / actions, u8 images; batches reach the device through pinned staging on a side stream
@@ -800,7 +815,12 @@ def main(args):
                                                train_ratio=task_config.get("train_ratio", 0.99),
                                                depth_camera_names=config["policy_config"].get("depth_camera_names"),
                                                use_depth=use_depth, pointcloud_names=config.get("pointcloud_names"),
-                                               use_pcd=use_pcd, max_points=config["policy_config"].get("max_points"))
+                                               use_pcd=use_pcd, max_points=config["policy_config"].get("max_points"),
+                                               # --device_dataset: every rank holds its own full store on its own device
+                                               device_dataset=device_dataset,
+                                               device=f"cuda:{local_rank}" if world > 1 else None,     # train_bc's device
+                                               device_budget_bytes=(int(config["device_dataset_gb"] * 2**30)
+                                                                    if config.get("device_dataset_gb") is not None else None))
     else:
         train_dl = SyntheticDataset(cfg, args["batch_size"], 8, seed=args["seed"] * world + rank)     # disjoint per rank
         val_dl = SyntheticDataset(cfg, args["batch_size"], 2, seed=args["seed"] * world + rank + 100003)
@@ -871,6 +891,12 @@ def make_parser():
                         help="ACT training only, opt-in: the reference dataset's augmentation (random 0.95 crop resized back, rotation "
                              "within 5 degrees, brightness / contrast / saturation jitter) on the device, for training batches; the "
                              "reference switches it on for Diffusion alone, which is outside this path")
+    parser.add_argument("--device_dataset", action="store_true",
+                        help="ACT training from --dataset_dir, opt-in: read every episode once into device memory and gather the "
+                             "training batches there (actmi.data.DeviceEpisodeStore): the same batches as the host loader, no loader "
+                             "workers; every rank holds the whole dataset; not with --use_pcd")
+    parser.add_argument("--device_dataset_gb", action="store", type=float, default=None,
+                        help="--device_dataset: device memory the store may take, in GiB (default: what is free minus a 64 GiB reserve)")
     return parser
 
 

@@ -725,6 +725,54 @@ typedef struct actmi_augment_desc {
 int64_t actmi_op_augment_workspace_bytes(int B, int K, int H, int W);
 int actmi_op_augment_u8(const actmi_augment_desc* d, void* stream);
 int actmi_op_warp_u16(const actmi_augment_desc* d, void* stream);
+/* ---- device-resident episode store: a training batch gathered on the device (csrc/episode_store.hip; actmi.data.DeviceEpisodeStore)
+ * actmi_op_gather_frames: out is n_items contiguous items of item_bytes each; item i becomes the item_bytes bytes at
+ * arena + src_off[i] (src_off [n_items] int64 ON THE DEVICE, 8-byte aligned; the same source may be named more than once).  One
+ * launch serves u8 RGB frames (item = one camera frame of one sample, n_items = B * K) and raw uint16 depth frames alike.  All
+ * offset arithmetic is 64-bit.  arena_bytes is the arena's size: an item with src_off[i] < 0 or src_off[i] + item_bytes > arena_bytes
+ * is ZERO-FILLED and nothing of it is read, so a wrong table cannot produce an address outside the arena.  No byte outside
+ * out[0 .. n_items * item_bytes) is written.  out must not overlap the arena.
+ * `aligned` is the caller's statement about its layout -- the launcher cannot see the offsets:
+ *   0  general form: any item_bytes and any alignment of arena, out and offsets, moved byte by byte (correct, not tuned);
+ *   1  every offset is a multiple of 16: 16-byte loads and stores, four in flight per lane.  item_bytes, arena and out must be
+ *      multiples of 16 (checked, ACTMI_E_INVALID otherwise); an item whose offset turns out not to be one is still copied
+ *      correctly, byte by byte;
+ *   2  as 1 with non-temporal loads of the read-once source: the same bytes, measured 0.77-0.87 of form 1's time at B = 64, K = 4
+ *      frames of 480 x 640 and level with it at B = 8 (tools/device_dataset_time.py).
+ * The store pads every block of its arena to 256 bytes and states 2 when the frame size is a multiple of 16 (480 x 640 x 3 and
+ * 480 x 640 x 2 are), 0 otherwise.  n_items <= 65535.  Capturable: one stream, no allocation, no synchronisation, nothing read on the host. */
+int actmi_op_gather_frames(const void* arena, int64_t arena_bytes, const int64_t* src_off, void* out, int64_t n_items,
+                           int64_t item_bytes, int aligned, void* stream);
+/* actmi_op_gather_chunks: the rest of EpisodicDataset.__getitem__ for B samples, bit for bit.  actions [n_rows][A] and qpos
+ * [n_rows][S] hold all episodes' rows back to back, already f32 as the dataset converts them (/base_action columns included);
+ * episodes [n_episodes] says where each starts; samples [B][2] int32 = (episode, t) on the device.  With s = is_sim ? t :
+ * max(0, t-1) and len = T - s:
+ *   qpos_out[b][:]      = (qpos[row0 + t] - qpos_mean) / qpos_std
+ *   action_out[b][j][:] = ((j < len ? actions[row0 + s + j] : 0) - action_mean) / action_std      j < Q  (the padding is z-scored too)
+ *   is_pad[b][j]        = j >= len                                                                 one byte, 0 or 1
+ * Every value is one fp32 subtract and one correctly rounded fp32 divide (no reciprocal, nothing fused): equal to torch's CPU
+ * result bit for bit.  Q is the caller's min(chunk_size, max_episode_len).  What the tables name is held to their sizes
+ * (episode to [0, n_episodes), the rows of an episode to [0, n_rows), t to [0, T)), so no entry gives an address outside the
+ * arrays.  Capturable like actmi_op_gather_frames. */
+typedef struct actmi_episode_rec {
+    int64_t row0;              /* first row of the episode in actions / qpos */
+    int32_t T;                 /* its length in steps */
+    int32_t is_sim;            /* the episode's `sim` attribute: 0 = chunks start at action[t-1] (utils.py:112-114) */
+} actmi_episode_rec;
+typedef struct actmi_gather_chunks_desc {
+    const float* actions;      /* [n_rows][A] */
+    const float* qpos;         /* [n_rows][S] */
+    const actmi_episode_rec* episodes;         /* [n_episodes], on the device */
+    const int32_t* samples;    /* [B][2] (episode, t), on the device */
+    const float *action_mean, *action_std;     /* [A] */
+    const float *qpos_mean, *qpos_std;         /* [S] */
+    float* qpos_out;           /* [B][S] */
+    float* action_out;         /* [B][Q][A] */
+    uint8_t* is_pad;           /* [B][Q] */
+    int64_t n_rows;
+    int32_t n_episodes, B, A, S, Q;
+} actmi_gather_chunks_desc;
+int actmi_op_gather_chunks(const actmi_gather_chunks_desc* d, void* stream);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
