@@ -293,34 +293,55 @@ def conv3x3_c64_dgrad(dy, wd_ohwi, dy_scale=None, res=None, mask=None, post_scal
     return dx
 
 
-def wgrad3x3_c64(dy, x, dy_scale=None):
-    """dW [G][64][3][3][64] (O, kh, kw, I) of the 64 -> 64 channel 3x3 / s1 / p1 convolution from dy, x [G][B][H][W][64]."""
+def _wgrad_buffers(G, slice_floats, default_partials, dw_shape, device, max_partials, out, accumulate, ws):
+    """workspace and result of the two direct weight-gradient ops: ws sized for max_partials partials per group (default: the
+    launcher's own cap, one unit per workgroup), or the caller's; dw a fresh tensor, or the caller's `out` (dense, fp32; any float
+    alignment)"""
+    if ws is None:
+        k = default_partials if max_partials is None else int(max_partials)
+        ws = torch.empty(G * k * slice_floats, device=device, dtype=torch.float32)
+    else:
+        assert max_partials is None, "max_partials sizes the op's own workspace; a caller's ws has its size"
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.device == device
+    if out is None:
+        assert not accumulate, "accumulate adds into out"
+        out = torch.empty(dw_shape, device=device, dtype=torch.float32)
+    else:
+        assert out.dtype == torch.float32 and tuple(out.shape) == tuple(dw_shape) and out.is_contiguous() and out.device == device
+    return ws, out
+
+
+def wgrad3x3_c64(dy, x, dy_scale=None, max_partials=None, out=None, accumulate=False, ws=None):
+    """dW [G][64][3][3][64] (O, kh, kw, I) of the 64 -> 64 channel 3x3 / s1 / p1 convolution from dy, x [G][B][H][W][64].
+    max_partials: size the workspace for this many partials per group (fewer than the default = several (image, strip) units
+    per workgroup); ws: a caller's workspace instead (the first G * nwg slices of 64 * 576 floats are written); out: a caller's
+    dw; accumulate: out += dW (the training step's form)."""
     G, B, H, W, Cc = x.shape
     assert Cc == 64 and dy.shape == x.shape
     nwg = max(1, min(256 // G, B * ((W + 31) // 32)))
-    ws = torch.empty(G * nwg * 64 * 576, device=x.device, dtype=torch.float32)
-    dw = torch.empty(G, 64, 3, 3, 64, device=x.device, dtype=torch.float32)
+    ws, dw = _wgrad_buffers(G, 64 * 576, nwg, (G, 64, 3, 3, 64), x.device, max_partials, out, accumulate, ws)
     lib = L.load()
-    L.check(lib.actmi_op_wgrad3x3_c64(_p(dy.contiguous()), _p(x.contiguous()), _p(dw), _p(ws), ws.numel(),
-                                      _p(dy_scale) if dy_scale is not None else None, G, B, H, W, L.current_stream_ptr()),
+    L.check(lib.actmi_op_wgrad3x3_c64_ex(_p(dy.contiguous()), _p(x.contiguous()), _p(dw), _p(ws), ws.numel(),
+                                         _p(dy_scale) if dy_scale is not None else None, G, B, H, W, 1 if accumulate else 0,
+                                         L.current_stream_ptr()),
             None, "op_wgrad3x3_c64")
     return dw
 
 
-def wgrad7x7s2(dy, x4, dy_scale=None):
-    """dW [G][64][7][7][4] (O, kh, kw, I) of the stem convolution (7x7 / s2 / p3) from dy [G][B][Ho][Wo][64], x4 [G][B][H][W][4]."""
+def wgrad7x7s2(dy, x4, dy_scale=None, max_partials=None, out=None, accumulate=False, ws=None):
+    """dW [G][64][7][7][4] (O, kh, kw, I) of the stem convolution (7x7 / s2 / p3) from dy [G][B][Ho][Wo][64], x4 [G][B][H][W][4].
+    max_partials / ws / out / accumulate as in wgrad3x3_c64 (slices of 64 * 196 floats)."""
     G, B, H, W, Cc = x4.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     assert Cc == 4 and tuple(dy.shape) == (G, B, Ho, Wo, 64)
     nwg = max(1, min(512 // G, B * ((Wo + 31) // 32)))
-    ws = torch.empty(G * nwg * 64 * 196, device=x4.device, dtype=torch.float32)
-    dw = torch.empty(G, 64, 7, 7, 4, device=x4.device, dtype=torch.float32)
+    ws, dw = _wgrad_buffers(G, 64 * 196, nwg, (G, 64, 7, 7, 4), x4.device, max_partials, out, accumulate, ws)
     lib = L.load()
-    L.check(lib.actmi_op_wgrad7x7s2(_p(dy.contiguous()), _p(x4.contiguous()), _p(dw), _p(ws), ws.numel(),
-                                    _p(dy_scale) if dy_scale is not None else None, G, B, H, W, L.current_stream_ptr()),
+    L.check(lib.actmi_op_wgrad7x7s2_ex(_p(dy.contiguous()), _p(x4.contiguous()), _p(dw), _p(ws), ws.numel(),
+                                       _p(dy_scale) if dy_scale is not None else None, G, B, H, W, 1 if accumulate else 0,
+                                       L.current_stream_ptr()),
             None, "op_wgrad7x7s2")
     return dw
-
 
 
 def attention(q, k, v, nheads, kpm=None, q_shared=False, want_lse=False, split=True, drop_p=0.0, drop_seed=0, prec=None,

@@ -571,21 +571,33 @@ int actmi_op_conv3x3_c64_dgrad(const float* dy, const float* w16, float w_scale,
     return launch_conv3x3_c64(a, S(stream), &g_op_error);
 }
 
+int actmi_op_wgrad3x3_c64_ex(const float* dy, const float* x, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev,
+                             int G, int B, int H, int W, int accumulate, void* stream) {
+    g_op_error.clear();
+    if (!dy || !x || !dw || !ws) { g_op_error = "wgrad3x3_c64: dy, x, dw and ws are required"; return ACTMI_E_INVALID; }
+    const int rc = launch_wgrad3x3_c64(dy, x, dw, accumulate ? 1 : 0, ws, ws_floats, dy_scale_dev, G, B, H, W, S(stream));
+    if (rc != 0) { g_op_error = "wgrad3x3_c64: bad arguments or launch failure"; return rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH; }
+    return 0;
+}
+
 int actmi_op_wgrad3x3_c64(const float* dy, const float* x, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev, int G,
                           int B, int H, int W, void* stream) {
+    return actmi_op_wgrad3x3_c64_ex(dy, x, dw, ws, ws_floats, dy_scale_dev, G, B, H, W, 0, stream);
+}
+
+int actmi_op_wgrad7x7s2_ex(const float* dy, const float* x4, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev,
+                           int G, int B, int H, int W, int accumulate, void* stream) {
     g_op_error.clear();
-    const int rc = launch_wgrad3x3_c64(dy, x, dw, 0, ws, ws_floats, dy_scale_dev, G, B, H, W, S(stream));
-    if (rc != 0) { g_op_error = "wgrad3x3_c64: bad arguments or launch failure"; return rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH; }
+    if (!dy || !x4 || !dw || !ws) { g_op_error = "wgrad7x7s2: dy, x4, dw and ws are required"; return ACTMI_E_INVALID; }
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const int rc = launch_wgrad7x7s2(dy, x4, dw, accumulate ? 1 : 0, ws, ws_floats, dy_scale_dev, G, B, H, W, Ho, Wo, S(stream));
+    if (rc != 0) { g_op_error = "wgrad7x7s2: bad arguments or launch failure"; return rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH; }
     return 0;
 }
 
 int actmi_op_wgrad7x7s2(const float* dy, const float* x4, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev, int G,
                         int B, int H, int W, void* stream) {
-    g_op_error.clear();
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int rc = launch_wgrad7x7s2(dy, x4, dw, 0, ws, ws_floats, dy_scale_dev, G, B, H, W, Ho, Wo, S(stream));
-    if (rc != 0) { g_op_error = "wgrad7x7s2: bad arguments or launch failure"; return rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH; }
-    return 0;
+    return actmi_op_wgrad7x7s2_ex(dy, x4, dw, ws, ws_floats, dy_scale_dev, G, B, H, W, 0, stream);
 }
 
 const char* actmi_op_last_error(void) { return g_op_error.c_str(); }

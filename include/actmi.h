@@ -494,6 +494,17 @@ int actmi_op_wgrad3x3_c64(const float* dy, const float* x, float* dw, float* ws,
  * 196 * min(512 / G, B * ceil(Wo/32)) floats of per-workgroup partials (fixed-order sum); dy_scale_dev as above */
 int actmi_op_wgrad7x7s2(const float* dy, const float* x4, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev, int G,
                         int B, int H, int W, void* stream);
+/* the two weight-gradient entries with the training step's accumulating form: accumulate != 0 adds the result to dw
+ * (dw = dw + sum of the partials, the old dw added last) instead of overwriting it.  Both kernels run min(256 / G or 512 / G,
+ * units) persistent workgroups over the units = B * ceil(W/32 or Wo/32) (image, 32-column strip) pairs, lowered to the
+ * largest count within a quarter that divides the units and then to what ws holds; ANY ws of >= G * 64 * 576 (or 196) floats
+ * is therefore accepted, a smaller one than documented above only means more units per workgroup.  Exactly the first G * nwg
+ * partials of ws are written.  dy, x and ws 16-byte aligned; dw needs float alignment only.  ACTMI_E_INVALID, with nothing
+ * launched, for a null pointer, a misaligned operand, B <= 0 or a ws below one partial per group. */
+int actmi_op_wgrad3x3_c64_ex(const float* dy, const float* x, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev,
+                             int G, int B, int H, int W, int accumulate, void* stream);
+int actmi_op_wgrad7x7s2_ex(const float* dy, const float* x4, float* dw, float* ws, int64_t ws_floats, const float* dy_scale_dev,
+                           int G, int B, int H, int W, int accumulate, void* stream);
 
 /* ---- DiffusionPolicy inference path (reference policy.py:20-241, imitate_episodes.py:100-118,420-426).
  * The non-GEMM pieces of what the reference delegates to robomimic (ResNet18Conv with BatchNorm -> GroupNorm, SpatialSoftmax,
