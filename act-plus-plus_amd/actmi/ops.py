@@ -373,22 +373,39 @@ def attention(q, k, v, nheads, kpm=None, q_shared=False, want_lse=False, split=T
     return (out, lse) if want_lse else out
 
 
-def attention_bwd(q, k, v, out, lse, dout, nheads, kpm=None, drop_p=0.0, drop_seed=0, do_scale=None, want_amax=False):
+def attention_bwd(q, k, v, o, lse, dout, nheads, kpm=None, drop_p=0.0, drop_seed=0, do_scale=None, want_amax=False, out=None,
+                  amax_out=None):
     """dq, dk, dv of ``attention`` (f16x3, no materialised scores): q [B,Nq,D], k / v [B,Nk,D] (row-strided views allowed),
-    out / dout [B,Nq,D] contiguous, lse [B,H,Nq] from ``attention(..., want_lse=True)``."""
+    o / dout [B,Nq,D] contiguous (the forward's output and its gradient), lse [B,H,Nq] from ``attention(..., want_lse=True)``.
+    out: a (dq, dk, dv) triple of float32 tensors or views of shapes [B,Nq,D], [B,Nk,D], [B,Nk,D] with last-dim stride 1 that
+    the kernels write through their own batch and row strides (the packed gradient buffer of the training step); without it
+    dense tensors are allocated.  amax_out: one int32 word that the three gradients raise to the bits of their largest
+    magnitude (a running maximum: the caller seeds it); it is returned as the fourth value, as with want_amax."""
     lib = L.load()
     B, Nk, D = k.shape
     Nq = q.shape[1]
-    dq = torch.empty((B, Nq, D), dtype=torch.float32, device=k.device)
-    dk = torch.empty((B, Nk, D), dtype=torch.float32, device=k.device)
-    dv = torch.empty((B, Nk, D), dtype=torch.float32, device=k.device)
+    if out is None:
+        dq = torch.empty((B, Nq, D), dtype=torch.float32, device=k.device)
+        dk = torch.empty((B, Nk, D), dtype=torch.float32, device=k.device)
+        dv = torch.empty((B, Nk, D), dtype=torch.float32, device=k.device)
+    else:
+        dq, dk, dv = out
+        for name, t, n in (("dq", dq, Nq), ("dk", dk, Nk), ("dv", dv, Nk)):
+            if tuple(t.shape) != (B, n, D) or t.dtype != torch.float32 or t.device != k.device or t.stride(2) != 1:
+                raise ValueError(f"attention_bwd: out {name} must be float32 [{B},{n},{D}] on {k.device} with last-dim stride 1, "
+                                 f"got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
     ws = torch.empty(B * nheads * Nq, dtype=torch.float32, device=k.device)
-    amax = torch.zeros(1, dtype=torch.int32, device=k.device) if want_amax else None
+    if amax_out is not None:
+        if amax_out.dtype != torch.int32 or amax_out.numel() != 1 or amax_out.device != k.device:
+            raise ValueError("attention_bwd: amax_out must be one int32 word on the operands' device")
+        amax = amax_out
+    else:
+        amax = torch.zeros(1, dtype=torch.int32, device=k.device) if want_amax else None
     d = L.AttnBwdDesc()
     d.q, d.q_bs, d.q_rs = q.data_ptr(), q.stride(0), q.stride(1)
     d.k, d.k_bs, d.k_rs = k.data_ptr(), k.stride(0), k.stride(1)
     d.v, d.v_bs, d.v_rs = v.data_ptr(), v.stride(0), v.stride(1)
-    d.o, d.d_o, d.lse = out.data_ptr(), dout.data_ptr(), lse.data_ptr()
+    d.o, d.d_o, d.lse = o.data_ptr(), dout.data_ptr(), lse.data_ptr()
     d.dq, d.dq_bs, d.dq_rs = dq.data_ptr(), dq.stride(0), dq.stride(1)
     d.dk, d.dk_bs, d.dk_rs = dk.data_ptr(), dk.stride(0), dk.stride(1)
     d.dv, d.dv_bs, d.dv_rs = dv.data_ptr(), dv.stride(0), dv.stride(1)
@@ -400,7 +417,7 @@ def attention_bwd(q, k, v, out, lse, dout, nheads, kpm=None, drop_p=0.0, drop_se
     d.do_scale = do_scale.data_ptr() if do_scale is not None else None
     d.amax_out = amax.data_ptr() if amax is not None else None
     L.check(lib.actmi_op_attention_bwd(C.byref(d), L.current_stream_ptr()), None, "op_attention_bwd")
-    return (dq, dk, dv, amax) if want_amax else (dq, dk, dv)
+    return (dq, dk, dv, amax) if amax is not None else (dq, dk, dv)
 
 
 def layernorm(x, w, b, res=None, res_mod=0, w2=None, b2=None, eps=1e-5):

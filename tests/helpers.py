@@ -397,3 +397,148 @@ def attn_sink_case(B, H, Nq, Nk, hd, margin, seed, v_sink=0.0, sink=0):
     s = _heads(q.double(), H, hd) @ _heads(k.double(), H, hd).transpose(-1, -2) / hd ** 0.5
     off = 1.0 - torch.softmax(s, -1)[..., sink]
     return q, k, v, off
+
+
+# ---- the operand rounding of the fused attention backward (csrc/attn_bwd.hip), modelled on the CPU; test_kernel_refs_cpu.py
+#      proves it against float64 autograd and shows that a dropped cross product bites; test_gpu_attention_bwd_forms.py takes
+#      its tight bound from it ---------------------------------------------------------------------------------------------------
+ATTN_BWD_PRODUCTS = ("S_dq", "T_dq", "dQ", "S_dkv", "T_dkv", "dK", "dV")     # the seven three-product contractions
+ATTN_BWD_DROPS = [(w, piece) for w in ATTN_BWD_PRODUCTS for piece in ("hl", "lh")]
+ATTN_BWD_E_UP = 10                   # log2 of the fixed scale the dK / dV kernel gives the (dropped) softmax weights before their split
+
+
+def attn_bwd_ref64(q, k, v, dout, H, hd, dead=None, keep=None, drop_p=0.0):
+    """float64 autograd through attn_ref64 -> (dq, dk, dv, out, lse [B,H,Nq], delta [B,H,Nq] = sum over the head of dout * out)"""
+    qd, kd, vd = (t.detach().double().requires_grad_(True) for t in (q, k, v))
+    out, lse = attn_ref64(qd, kd, vd, H, hd, dead=dead, keep=keep, drop_p=drop_p)
+    out.backward(dout.double())
+    out = out.detach()
+    delta = _heads(dout.double() * out, H, hd).sum(-1)
+    return qd.grad, kd.grad, vd.grad, out, lse.detach(), delta
+
+
+def _prod3_drop(ah, al, bh, bl, piece=None):
+    """prod3_model of a @ b with one cross product removable: piece "hl" leaves out a_hi b_lo, "lh" leaves out a_lo b_hi"""
+    ah, al, bh, bl = (t.double() for t in (ah, al, bh, bl))
+    out = ah @ bh
+    if piece != "hl":
+        out = out + ah @ bl
+    if piece != "lh":
+        out = out + al @ bh
+    return out
+
+
+def _prod3_acc32(ah, al, bh, bl, first, piece=None):
+    """the same three products as the MFMA chain of score_tile accumulates them: the contraction axis in steps of 16, per step
+    the cross product named `first` ("hl" or "lh"), the other cross product, then hi hi; each MFMA adds the exact sum of its 16
+    products to the fp32 accumulator and rounds once (how the hardware rounds inside one MFMA is not specified; this is the
+    model's reading)"""
+    ah, al, bh, bl = (t.double() for t in (ah, al, bh, bl))
+    acc = torch.zeros(*ah.shape[:-1], bh.shape[-1], dtype=torch.float32)
+    for s0 in range(0, ah.shape[-1], 16):
+        sl = slice(s0, s0 + 16)
+        parts = {"hl": (ah[..., sl], bl[..., sl, :]), "lh": (al[..., sl], bh[..., sl, :])}
+        for name in (first, "lh" if first == "hl" else "hl"):
+            if name != piece:
+                acc = (acc.double() + parts[name][0] @ parts[name][1]).float()
+        acc = (acc.double() + ah[..., sl] @ bh[..., sl, :]).float()
+    return acc
+
+
+def attn_delta_fp32_model(dout, o, H, hd):
+    """attn_delta_kernel (csrc/bwd.hip) bit for bit for hd <= 64: one fp32 product dout * o per lane, summed by the wave's xor
+    butterfly (lane i += lane i ^ 32, ^ 16, .. ^ 1) in fp32 -> float32 [B,H,Nq]"""
+    assert hd <= 64
+    B, Nq = dout.shape[0], dout.shape[1]
+    x = torch.nn.functional.pad((dout.float() * o.float()).reshape(B, Nq, H, hd), (0, 64 - hd))
+    w = 32
+    while w >= 1:
+        x = x[..., :w] + x[..., w:2 * w]
+        w //= 2
+    return x[..., 0].transpose(1, 2)
+
+
+def column_scale_model(ds):
+    """dS as acc_to_frags sees it behind column_scale: float32 ds [..., n], the last axis walked in steps of 32 from index 0.
+    Per step the power of two s = 2^(140 - ex), ex the biased exponent of the step's largest magnitude clamped to [40, 230]
+    (largest element in [2^13, 2^14)); ds * s in fp32, split; -> the two pieces in float64 with 1 / s taken out again (exact),
+    so that one contraction over the whole axis equals the kernel's sum of per-step products times their inverse scales"""
+    n = ds.shape[-1]
+    x = torch.nn.functional.pad(ds.float(), (0, (-n) % 32)).reshape(*ds.shape[:-1], -1, 32)
+    mx = x.abs().amax(-1, keepdim=True).contiguous()
+    ex = ((mx.view(torch.int32) >> 23) & 0xff).clamp(40, 230)
+    hi, lo = split16_model(x * torch.ldexp(torch.ones_like(mx), 140 - ex))
+    inv = torch.ldexp(torch.ones_like(mx, dtype=torch.float64), ex - 140)
+    return tuple((t.double() * inv).reshape(*ds.shape[:-1], -1)[..., :n] for t in (hi, lo))
+
+
+def attn_bwd_f16x3_model(q, k, v, dout, lse, delta, H, hd, dead=None, keep=None, drop_p=0.0, do_scale=1.0, drop=None,
+                         mfma_acc=False):
+    """The operand rounding of attn_bwd_dq_kernel and attn_bwd_dkv_kernel, in the kernels' order and without their schedule (no
+    tiles, every contraction summed in float64; the per-32-step scale of dS is kept, it is arithmetic and not schedule):
+      dQ kernel: q * (scale * log2 e) in fp32, split; k, v split as they are; dout * do_scale (a power of two) in fp32, split;
+      S = q k^T and T = dout v^T as three products, rounded to fp32; E = exp2(S - lse * log2 e) in fp32, zero on dead keys;
+      dS = E * (T' - delta * do_scale) * scale in fp32 with T' = T / (1 - p) where kept, else 0; dS scaled per (query, 32-key
+      step) by column_scale_model, split; dQ = dS k as three products, times 1 / do_scale.
+      dK / dV kernel: k * (scale * log2 e) in fp32, split; q split as it is; S, T, E, dS as above from these pieces; the dropped
+      weights E' = E / (1 - p) where kept times 2^10, split; dV = E'^T dout; dS scaled per (key, 32-query step), split;
+      dK = dS^T q; both times 1 / do_scale (dV also 2^-10).
+    q [B,Nq,D], k / v [B,Nk,D], dout [B,Nq,D], lse / delta [B,H,Nq] (rounded to fp32 here, as the kernels read them), dead /
+    keep broadcastable to [B,H,Nq,Nk].  drop = (one of ATTN_BWD_PRODUCTS, "hl" | "lh") removes one cross product of that
+    contraction, the factors named as written above: "hl" is left-hi right-lo.  mfma_acc=True accumulates S and T as the
+    kernels' MFMA chains do (_prod3_acc32: fp32 after every MFMA, the products in each kernel's order) instead of rounding
+    the exact sum once: T - delta cancels where few keys are alive, and the accumulation's rounding then shows in dS.
+    -> float64 dq [B,Nq,D], dk, dv [B,Nk,D]"""
+    f32 = np.float32
+    B, Nq, Nk = q.shape[0], q.shape[1], k.shape[1]
+    which, piece = drop if drop is not None else (None, None)
+    assert which in ATTN_BWD_PRODUCTS + (None,) and piece in ("hl", "lh", None)
+
+    def pc(name):
+        return piece if which == name else None
+    scale = f32(1.0) / np.sqrt(f32(hd))
+    qscale, scale = float(f32(scale * f32(LOG2E))), float(scale)
+    sdo = float(f32(do_scale))
+    dsc = float(f32(1.0) / (f32(1.0) - f32(drop_p))) if drop_p > 0 else 1.0
+    qq, kk, vv, gg = (_heads(t.float(), H, hd) for t in (q, k, v, dout))
+    gh, gl = split16_model(gg * sdo)
+    vh, vl = split16_model(vv)
+    lse2 = (lse.float() * float(f32(LOG2E))).unsqueeze(-1)
+    dlt = (delta.float() * sdo).unsqueeze(-1)
+
+    def weights(S, T):
+        E = torch.exp2(S - lse2)
+        if dead is not None:
+            E = torch.where(dead, torch.zeros_like(E), E)
+        dp, Ed = T, E
+        if keep is not None:
+            dp = torch.where(keep, T * dsc, torch.zeros_like(T))
+            Ed = torch.where(keep, E * dsc, torch.zeros_like(E))
+        return Ed, E * (dp - dlt) * scale
+
+    def t_(x):
+        return x.transpose(-1, -2)
+
+    def score(ah, al, bh, bl, first, name):
+        """S or T of one kernel; `first` is the cross product its MFMA chain issues first (the LDS rows' lo piece leads)"""
+        if mfma_acc:
+            return _prod3_acc32(ah, al, t_(bh), t_(bl), first, pc(name))
+        return _prod3_drop(ah, al, t_(bh), t_(bl), pc(name)).float()
+    # dQ kernel
+    qh, ql = split16_model(qq * qscale)
+    kh, kl = split16_model(kk)
+    S = score(qh, ql, kh, kl, "hl", "S_dq")                 # the streamed k and v rows come from LDS: k_lo q_hi first
+    T = score(gh, gl, vh, vl, "hl", "T_dq")
+    dsh, dsl = column_scale_model(weights(S, T)[1])
+    dq = _prod3_drop(dsh, dsl, kh, kl, pc("dQ")) / sdo
+    # dK / dV kernel
+    kh, kl = split16_model(kk * qscale)
+    qh, ql = split16_model(qq)
+    S = score(qh, ql, kh, kl, "lh", "S_dkv")                # the streamed q and dout rows come from LDS: q_lo k_hi first
+    T = score(gh, gl, vh, vl, "lh", "T_dkv")
+    Ed, dS = weights(S, T)
+    eh, el = split16_model(Ed * float(2.0 ** ATTN_BWD_E_UP))
+    dv = _prod3_drop(t_(eh), t_(el), gh, gl, pc("dV")) / (sdo * 2.0 ** ATTN_BWD_E_UP)
+    dsh, dsl = column_scale_model(t_(dS).contiguous())
+    dk = _prod3_drop(dsh, dsl, qh, ql, pc("dK")) / sdo
+    return tuple(t.transpose(1, 2).reshape(B, n, H * hd) for t, n in ((dq, Nq), (dk, Nk), (dv, Nk)))

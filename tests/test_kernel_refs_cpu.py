@@ -2,6 +2,8 @@
 compare the kernels with, proven here against torch's own operators (no GPU), and the proofs that the hard cases bite: a
 wrong rule (chunk variance without the between-chunk term, the last maximum on a tie, log(1 + exp(x)) for log1p(exp(x)),
 no max subtraction before expf) misses the bound of its GPU test by a wide margin."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -264,3 +266,58 @@ def test_small_sink_value_and_traded_q_k_need_the_operand_scales(hd):
     shipped = rel_err(Hh.attn_f16x3_shipped(q, k, v, H, hd)[0], exp)
     print(f"q / 16, 16 k hd={hd}: bias only {bias_only:.2e}, with the operand scales {shipped:.2e} (bound 3.0e-06)")
     assert shipped < 1.5e-6 and shipped < bias_only
+
+
+# ---- the fused attention backward: the CPU model of attn_bwd.hip's operand rounding (helpers.attn_bwd_f16x3_model) -------------
+BWD_CPU = [(Nq, Nk, hd) for (Nq, Nk) in ((33, 63), (129, 257)) for hd in (16, 64)]
+
+
+@functools.lru_cache(maxsize=None)
+def _bwd_cpu_case(Nq, Nk, hd):
+    """randn inputs (B = 1, H = 2) and their float64 gradients, log-sum-exp and delta, computed once"""
+    B, H = 1, 2
+    g = torch.Generator().manual_seed(100 * hd + Nq + Nk)
+    q, k, v, dout = (torch.randn(B, n, H * hd, generator=g) for n in (Nq, Nk, Nk, Nq))
+    dq, dk, dv, _, lse, delta = Hh.attn_bwd_ref64(q, k, v, dout, H, hd)
+    return q, k, v, dout, lse, delta, (dq, dk, dv)
+
+
+@pytest.mark.parametrize("Nq,Nk,hd", BWD_CPU)
+def test_attention_backward_model_holds_2e6_and_every_dropped_product_bites(Nq, Nk, hd):
+    """The two facts the tight bound of test_gpu_attention_bwd_forms.py rests on, max-relative per gradient against float64
+    autograd with lse and delta from float64: the full operand rounding of the kernels stays under 2e-6 (measured 2.6e-7 ..
+    6.4e-7), and leaving out any one cross product (hi lo or lo hi) of any of the seven contractions raises at least one
+    gradient above 1e-4 (measured 1.6e-4 .. 8.0e-4).  The variant the GPU tests use (delta as attn_delta_kernel forms it in
+    fp32, S and T accumulated in fp32 along their MFMA chains) holds the same 2e-6 (measured 2.3e-7 .. 7.2e-7)."""
+    H = 2
+    q, k, v, dout, lse, delta, ref = _bwd_cpu_case(Nq, Nk, hd)
+    full = [rel_err(a, b) for a, b in zip(Hh.attn_bwd_f16x3_model(q, k, v, dout, lse, delta, H, hd), ref)]
+    print(f"attention bwd model {Nq}x{Nk} hd={hd}: dq {full[0]:.2e} dk {full[1]:.2e} dv {full[2]:.2e} (bound 2.0e-06)")
+    assert max(full) < 2e-6
+    # the GPU tests' variant: delta as attn_delta_kernel forms it in fp32, S and T accumulated in fp32 along the MFMA chains
+    out64 = Hh.attn_ref64(q, k, v, H, hd)[0]
+    delta32 = Hh.attn_delta_fp32_model(dout, out64.float(), H, hd)
+    assert delta32.dtype == torch.float32 and rel_err(delta32, delta) < 1e-6
+    chain = [rel_err(a, b) for a, b in zip(Hh.attn_bwd_f16x3_model(q, k, v, dout, lse, delta32, H, hd, mfma_acc=True), ref)]
+    print(f"  with the fp32 delta and the MFMA-chain accumulation: dq {chain[0]:.2e} dk {chain[1]:.2e} dv {chain[2]:.2e}")
+    assert max(chain) < 2e-6
+    for drop in Hh.ATTN_BWD_DROPS:
+        errs = [rel_err(a, b) for a, b in zip(Hh.attn_bwd_f16x3_model(q, k, v, dout, lse, delta, H, hd, drop=drop), ref)]
+        print(f"  without {drop[0]} {drop[1]}: dq {errs[0]:.2e} dk {errs[1]:.2e} dv {errs[2]:.2e} (must pass 1.0e-04)")
+        assert max(errs) > 1e-4, drop
+
+
+def test_attention_backward_model_masked_and_dropped():
+    """tail padding and weight dropout at p = 0.5 (the host mask of csrc/dropout.h), a power-of-two dO scale: the same 2e-6"""
+    B, H, Nq, Nk, hd, p = 1, 2, 129, 257, 64, 0.5
+    g = torch.Generator().manual_seed(5)
+    q, k, v, dout = (torch.randn(B, n, H * hd, generator=g) for n in (Nq, Nk, Nk, Nq))
+    dead = torch.zeros(B, 1, 1, Nk, dtype=torch.bool)
+    dead[..., Nk - 37:] = True
+    keep = torch.from_numpy(Hh.host_keep(Hh.BIG_SEED, np.arange(B * H * Nq * Nk, dtype=np.uint64), p)).view(B, H, Nq, Nk)
+    dq, dk, dv, _, lse, delta = Hh.attn_bwd_ref64(q, k, v, dout, H, hd, dead=dead, keep=keep, drop_p=p)
+    got = Hh.attn_bwd_f16x3_model(q, k, v, dout, lse, delta, H, hd, dead=dead, keep=keep, drop_p=p, do_scale=2.0 ** 12)
+    errs = [rel_err(a, b) for a, b in zip(got, (dq, dk, dv))]
+    print(f"attention bwd model masked, p={p}: dq {errs[0]:.2e} dk {errs[1]:.2e} dv {errs[2]:.2e} (bound 2.0e-06)")
+    assert max(errs) < 2e-6
+    assert bool((got[1][:, Nk - 37:] == 0).all()) and bool((got[2][:, Nk - 37:] == 0).all())
