@@ -206,6 +206,8 @@ def load():
         "actmi_op_conv1_prepare": ([vp, vp, i32, i32, i32, vp], i32),
         "actmi_op_conv1_prepared": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
         "actmi_op_conv1_prepared_ex": ([vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+        "actmi_op_conv1_seam_floats": ([i32, i32, i32, i32, i32], C.c_int64),
+        "actmi_op_conv1_pooled": ([vp, i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
         "actmi_op_hpool": ([vp, vp, i32, i32, i32, vp], i32),
         "actmi_op_conv3x3_c64": ([vp, vp, C.c_float, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
         "actmi_op_conv3x3_c64_dgrad": ([vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
@@ -269,6 +271,8 @@ def load():
         "actmi_profile_report": ([C.c_char_p, i32], i32),
     }
     for name, (args, res) in sigs.items():
+        if os.environ.get("ACTMI_LIB") and not hasattr(lib, name):
+            continue                     # an A/B run against an older build: it lacks the newer entries (calling one fails there)
         fn = getattr(lib, name)          # AttributeError here = header and library disagree
         fn.argtypes = args
         fn.restype = res

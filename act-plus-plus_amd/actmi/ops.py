@@ -246,6 +246,45 @@ def conv1_prepared(image, ws, Cout, relu=False, scale=None, bias=None, vpool=Fal
     return out
 
 
+def conv1_seam_floats(B, Cc, H, W, Cout):
+    """floats of the seam workspace conv1_pooled needs for frames of H x W (0 when the conv map is at most 64 columns wide)"""
+    return int(L.load().actmi_op_conv1_seam_floats(int(B), int(Cc), int(H), int(W), int(Cout)))
+
+
+def conv1_pooled(image, ws, Cout, relu=True, scale=None, bias=None, cam0=0, ncam=0, out=None, seam="auto", prec=None):
+    """the 7x7 / s2 stem with the whole 3x3 / s2 / p1 max pool fused (actmi_op_conv1_pooled): image as conv1_prepared ->
+    [C, B, Ho/2, (Wo-1)//2+1, Cout], bit-equal to hpool(conv1_prepared(..., vpool=True)); launch only.  seam: the float32
+    workspace of at least conv1_seam_floats(...) elements that a conv map wider than 64 columns needs ("auto": allocated
+    here; None: none is passed).  cam0 / ncam: compute that camera range only, into the whole-tensor `out` (and `seam`) given."""
+    lib = L.load()
+    image = image.contiguous()
+    if image.dtype == torch.uint8:
+        B, Cc, H, W, _ = image.shape
+        fmt = L.IMG_U8_NHWC
+    elif image.dtype == torch.float32:
+        B, Cc, _, H, W = image.shape
+        fmt = L.IMG_F32_NCHW
+    else:
+        raise TypeError(f"conv1_pooled: image dtype {image.dtype} not supported (uint8 or float32)")
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    shape = (Cc, B, Ho // 2, (Wo - 1) // 2 + 1, Cout)
+    if out is None:
+        if ncam:
+            raise ValueError("conv1_pooled: a camera range writes into a caller-supplied whole-tensor out")
+        out = torch.empty(shape, dtype=torch.float32, device=image.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"conv1_pooled: out must be a contiguous float32 tensor of shape {shape}")
+    if isinstance(seam, str):
+        n = conv1_seam_floats(B, Cc, H, W, Cout)
+        seam = torch.empty(n, dtype=torch.float32, device=image.device) if n else None
+    elif seam is not None and (seam.dtype != torch.float32 or not seam.is_contiguous()):
+        raise ValueError("conv1_pooled: seam must be a contiguous float32 tensor")
+    L.check(lib.actmi_op_conv1_pooled(_p(image), fmt, _p(ws), _p(scale), _p(bias), _p(out), _p(seam), seam.numel() if seam is not None else 0,
+                                      B, Cc, H, W, Cout, 1 if relu else 0, int(cam0), int(ncam), PREC[prec], L.current_stream_ptr()),
+            None, "op_conv1_pooled")
+    return out
+
+
 def hpool(x):
     """horizontal half of the 3x3 / s2 / p1 max pool: x [..., W, C] NHWC rows -> [..., Wo, C], max over columns 2pw-1 .. 2pw+1."""
     lib = L.load()

@@ -508,9 +508,10 @@ int actmi_op_conv1_prepare(const float* w_oihw, float* workspace, int C, int Cou
     if (hipStreamSynchronize(S(stream)) != hipSuccess) return ACTMI_E_LAUNCH;
     return 0;
 }
-int actmi_op_conv1_prepared_ex(const void* image, int image_fmt, const float* workspace, const float* scale, const float* bias,
-                               float* out, int B, int C, int H, int W, int Cout, int relu, int vpool, int cam0, int ncam, int prec,
-                               void* stream) {
+// every form of the prepared stem: vpool 0 / 1 (actmi_op_conv1_prepared_ex) or 2 with its seam workspace (actmi_op_conv1_pooled)
+static int op_conv1_prepared(const void* image, int image_fmt, const float* workspace, const float* scale, const float* bias,
+                             float* out, float* seam, int64_t seam_floats, int B, int C, int H, int W, int Cout, int relu, int vpool,
+                             int cam0, int ncam, int prec, void* stream) {
     g_op_error.clear();
     if (!image || !workspace || !out) { g_op_error = "conv1_prepared: null pointer"; return ACTMI_E_INVALID; }
     if (image_fmt != ACTMI_IMG_U8_NHWC && image_fmt != ACTMI_IMG_F32_NCHW) { g_op_error = "conv1_prepared: unknown image format"; return ACTMI_E_INVALID; }
@@ -528,9 +529,27 @@ int actmi_op_conv1_prepared_ex(const void* image, int image_fmt, const float* wo
     a.out = out; a.B = B; a.C = C; a.H = H; a.W = W; a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1; a.Cout = Cout;
     a.prec = prec; a.wimg = ws.wimg; a.wscale = 256.f;
     a.relu_floor = relu ? 0.f : -__builtin_inff();
-    a.vpool = vpool ? 1 : 0; a.cam0 = cam0; a.ncam = ncam;
-    const int rc = launch_conv1(a, S(stream), &g_op_error);
+    a.vpool = vpool; a.cam0 = cam0; a.ncam = ncam; a.seam = seam; a.seam_floats = seam_floats;
+    int rc = launch_conv1(a, S(stream), &g_op_error);
+    if (rc == 0 && vpool == 2 && launch_conv1_seam(a, S(stream)) != 0) { g_op_error = "conv1_pooled: seam pass launch failed"; rc = -3; }
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_SHAPE : ACTMI_E_LAUNCH);
+}
+int actmi_op_conv1_prepared_ex(const void* image, int image_fmt, const float* workspace, const float* scale, const float* bias,
+                               float* out, int B, int C, int H, int W, int Cout, int relu, int vpool, int cam0, int ncam, int prec,
+                               void* stream) {
+    return op_conv1_prepared(image, image_fmt, workspace, scale, bias, out, nullptr, 0, B, C, H, W, Cout, relu, vpool ? 1 : 0, cam0, ncam,
+                             prec, stream);
+}
+int64_t actmi_op_conv1_seam_floats(int B, int C, int H, int W, int Cout) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || Cout < 1) return 0;
+    return conv1_seam_floats(B, C, (H - 1) / 2 + 1, (W - 1) / 2 + 1, Cout);
+}
+int actmi_op_conv1_pooled(const void* image, int image_fmt, const float* workspace, const float* scale, const float* bias, float* out,
+                          float* seam, int64_t seam_floats, int B, int C, int H, int W, int Cout, int relu, int cam0, int ncam, int prec,
+                          void* stream) {
+    if (seam && ((uintptr_t)seam & 15)) { g_op_error = "conv1_pooled: seam must be 16-byte aligned"; return ACTMI_E_SHAPE; }
+    return op_conv1_prepared(image, image_fmt, workspace, scale, bias, out, seam, seam ? seam_floats : 0, B, C, H, W, Cout, relu, 2, cam0,
+                             ncam, prec, stream);
 }
 int actmi_op_conv1_prepared(const void* image_u8, const float* workspace, const float* scale, const float* bias, float* out, int B,
                             int C, int H, int W, int Cout, int relu, void* stream) {

@@ -64,7 +64,11 @@ struct Conv1Args {
     int prec = 0;         // ACTMI_PREC_* (0 = environment / native fp32)
     const unsigned char* wimg = nullptr;   // f16x3 only, optional: launch_conv1_wimg's image of w (C x conv1_wimg_bytes())
     int vpool = 0;        // f16x3 only: write max over conv rows (2a-1, 2a, 2a+1) -> out [C][B][Ho/2][Wo][Cout] (pool's vertical half)
+                          // 2: write the finished 3x3 / s2 / p1 max pool -> out [C][B][Ho/2][(Wo-1)/2+1][Cout]; pooled columns 32, 64, ..
+                          // hold the max of their own strip's columns only until launch_conv1_seam has run
     int vpool_nseg = 1;   // set by the launcher
+    float* seam = nullptr;       // vpool 2, Wo > 64: [C][B][Ho/2][strips-1][Cout], the last vertically pooled column of every
+    int64_t seam_floats = 0;     // 64-column strip but the last (conv1_seam_floats), whole-tensor pointer like out
     float wscale = 256.f; // f16x3 only: power of two the split weight image was built with (undone in the epilogue)
     int cam0 = 0, ncam = 0;   // camera range of this launch (ncam = 0: all C); image / w / scale / bias / out stay whole-tensor pointers
     float relu_floor = 0.f;   // f16x3, plain (non-vpool) form: out = max(acc * scale + bias, relu_floor); -inf = no ReLU
@@ -72,6 +76,10 @@ struct Conv1Args {
 int64_t conv1_wimg_bytes();
 int launch_conv1_wimg(const float* w, void* img, int C, int Cout, hipStream_t st, float wscale = 256.f);
 int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err);
+// the vpool 2 form's seam: workspace size, and the pass that finishes the pooled columns at the strip boundaries of the launch's
+// camera range (out[c] = max(out[c], seam) on those columns only; nothing is launched when a row is one strip)
+int64_t conv1_seam_floats(int B, int C, int Ho, int Wo, int Cout);
+int launch_conv1_seam(const Conv1Args& a, hipStream_t st);
 // grid of a stem kernel whose blocks are persistent over tiles: at most `cap` blocks (at least one), then no more blocks than
 // still give the busiest block as few tiles
 inline int balanced_grid(int tiles, int cap) {
@@ -130,6 +138,8 @@ int launch_conv3x3_c64(const Conv3Args& a, hipStream_t st, std::string* err);
 int launch_maxpool(const float* in, float* out, int nimg, int H, int W, int C, int Ho, int Wo, hipStream_t st);
 // horizontal half of the 3x3/s2/p1 pool on a vertically pooled map: out[h][pw] = max(in[h][2pw-1 .. 2pw+1])
 int launch_hpool(const float* in, float* out, int nrows, int W, int C, int Wo, hipStream_t st);
+// seam pass of the stem's full-pool form: out [nrows][Wp][C], side [nrows][nseam][C]; out[r][period * (s+1)] = max(itself, side[r][s])
+int launch_pool_seam(float* out, const float* side, int64_t nrows, int Wp, int C, int nseam, int period, hipStream_t st);
 int launch_maxpool_idx(const float* in, float* out, uint8_t* arg, int nimg, int H, int W, int C, int Ho, int Wo, hipStream_t st);
 int launch_maxpool_bwd_idx(const uint8_t* arg, const float* dy, float* dx, int nimg, int H, int W, int C, int Ho, int Wo,
                            hipStream_t st, const float* relu_x = nullptr, const float* bn_scale = nullptr, int imgs_per_group = 1,

@@ -155,7 +155,9 @@ constexpr int F_PATCH = F_PROWS * 2 * F_RB;                        // bytes per 
 constexpr int F_NG = 22;                                           // contraction groups incl. the zero one
 constexpr int F_WROW = 368;                                        // bytes per channel row of one weight piece
 constexpr int F_WBYTES = 64 * F_WROW;
+constexpr int F_EDGE = 2 * 3 * 64 * 4;                             // full-pool form: 3 wave boundaries x 64 channels, two step parities
 constexpr int F_SMEM = 2 * F_WBYTES + 2 * F_PATCH + 3 * 256 * 4;
+constexpr int F_SMEM_POOL = F_SMEM + F_EDGE;
 
 // 4x4 transpose across a quad of lanes: before, lane j of the quad holds (r0..r3) = row j; after, lane k holds column k
 // as (r0..r3) = (row0[k], row1[k], row2[k], row3[k]).  Two exchange stages on DPP quad permutes (no LDS traffic).
@@ -173,6 +175,14 @@ __device__ __forceinline__ void quad_transpose(float& r0, float& r1, float& r2, 
     if (o2) r0 = t; else r2 = t;
     t = dpp_xor2(o2 ? r1 : r3);
     if (o2) r1 = t; else r3 = t;
+}
+
+// the value of lane ^ 32 (the other half of the wave): one v_permlane32_swap, which exchanges the upper half of its first
+// operand with the lower half of its second
+__device__ __forceinline__ float half_swap(float v, int lh) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return __builtin_bit_cast(float, lh ? r[0] : r[1]);
 }
 
 __device__ __forceinline__ uint32_t split1(float v) {              // (hi | lo << 16) of one value
@@ -219,13 +229,17 @@ __global__ __launch_bounds__(256) void conv1_wimg_kernel(const float* __restrict
     *reinterpret_cast<uint16_t*>(dst + F_WBYTES + n * F_WROW + rem * 2) = l;
 }
 
-template <int FMT>
+// POOL: the full-pool form (vpool 2) is an instantiation of its own, so that the plain and vpool 1 forms compile to what they
+// were without it
+template <int FMT, bool POOL>
 __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles_per_row, int tiles_per_cam) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     unsigned char* s_wh = reinterpret_cast<unsigned char*>(smem_raw);
     unsigned char* s_wl = s_wh + F_WBYTES;
     unsigned char* s_patch = s_wl + F_WBYTES;                      // two buffers of F_PATCH bytes
     uint32_t* s_lut = reinterpret_cast<uint32_t*>(s_patch + 2 * F_PATCH);
+    float* s_edge = reinterpret_cast<float*>(s_lut + 3 * 256);     // POOL: [step parity][wave 0..2][64 channels]
+    const bool chain = POOL || p.vpool;                            // the vpool walk (POOL: known at compile time)
     const int cam = blockIdx.y + p.cam0;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int li = lane & 31, lh = lane >> 5;
@@ -279,8 +293,10 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
     // formed in the epilogue and only the vertically pooled map [Ho/2][Wo][Cout] is written -- half the bytes, and the
     // pool pass that follows reads half as much.  A chain that does not start at the top first computes the row pair above
     // it without storing (halo).  Values are post-ReLU (>= 0), so 0 stands in for the padded row above the image.
+    // vpool == 2 (inference) walks the same chains and also forms the horizontal 3-max: it writes the finished pool
+    // [Ho/2][(Wo-1)/2+1][Cout], a quarter of the bytes, and the last column of every strip but the last to p.seam.
     int tile = blockIdx.x, tile_stride = gridDim.x, tile_end = tiles_per_cam, store_from = 0;
-    if (p.vpool) {
+    if (chain) {
         const int chains_per_img = tiles_per_row * p.vpool_nseg;
         const int b = blockIdx.x / chains_per_img, rem = blockIdx.x - b * chains_per_img;
         const int strip = rem / p.vpool_nseg, seg = rem - strip * p.vpool_nseg;
@@ -306,6 +322,8 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
         for (int b_ = 0; b_ < 2; ++b_)
 #pragma unroll
             for (int c_ = 0; c_ < 4; ++c_) prev[a_][b_][c_] = 0.f;
+    float pool4[2][4] = {};               // full pool: this lane's 4 pooled columns of the step, finished behind the barrier
+    int epar = 0;                         // full pool: parity of the step (which half of s_edge it writes)
     for (; tile < tile_end; tile += tile_stride) {
         const int next = tile + tile_stride;
         const bool has_next = next < tile_end;
@@ -316,7 +334,7 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
         {
             // plain: wave = (row, 32-column half), lane pixel = column.  vpool: wave = 16-column quarter, lane pixel =
             // (row = li >> 4, column = li & 15), so that both rows of a column sit in the same lane's accumulators
-            const unsigned char* abase = p.vpool
+            const unsigned char* abase = chain
                 ? s_patch + cur * F_PATCH + (2 * (li >> 4)) * 2 * F_RB + 12 * (wave * 16 + (li & 15))
                 : s_patch + cur * F_PATCH + (2 * prow) * 2 * F_RB + 12 * (phalf * 32 + li);
             f32x16 acc[2];
@@ -345,7 +363,49 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
                     acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, yh, acc[nt], 0, 0, 0);
                 }
             }
-            if (p.vpool) {
+            if constexpr (POOL) {
+                // full pool, first half: the vertical 3-max as below, then the horizontal one.  After the vertical max this
+                // lane holds, per (nt, gq), conv columns cb .. cb+3 of one channel, cb = wo0 + 16*wave + 8*gq + 4*lh: pooled
+                // column cb/2 + 1 (columns cb+1 .. cb+3) is local, pooled column cb/2 needs column cb-1 = the i = 3 value of
+                // the other lane half (one exchange), of the previous wave (s_edge, read after the step's barrier) or of the
+                // strip to the left (the seam pass, pool.hip).  Columns outside the map count as 0 (values are >= 0).
+                const bool do_store = tile >= store_from;            // block-uniform
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    float v[2][4];
+#pragma unroll
+                    for (int gq = 0; gq < 2; ++gq)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float up = fmaxf(acc[nt][4 * gq + i] * sc[nt] + bi[nt], 0.f);
+                            const float lo = fmaxf(acc[nt][4 * (gq + 2) + i] * sc[nt] + bi[nt], 0.f);
+                            const float m = fmaxf(prev[nt][gq][i], fmaxf(up, lo));
+                            prev[nt][gq][i] = lo;
+                            v[gq][i] = m;
+                        }
+                    if (wo0 + TILE_P > p.Wo) {                       // ragged last strip only (block-uniform)
+#pragma unroll
+                        for (int gq = 0; gq < 2; ++gq)
+#pragma unroll
+                            for (int i = 0; i < 4; ++i)
+                                if (wo0 + wave * 16 + 8 * gq + 4 * lh + i >= p.Wo) v[gq][i] = 0.f;
+                    }
+                    const float x0 = half_swap(v[0][3], lh), x1 = half_swap(v[1][3], lh);
+                    // upper half: columns cb-1 of both gq sit in the lower half; lower half: gq 1's is gq 0's of the upper half
+                    pool4[nt][0] = fmaxf(lh ? x0 : 0.f, fmaxf(v[0][0], v[0][1]));
+                    pool4[nt][1] = fmaxf(v[0][1], fmaxf(v[0][2], v[0][3]));
+                    pool4[nt][2] = fmaxf(lh ? x1 : x0, fmaxf(v[1][0], v[1][1]));
+                    pool4[nt][3] = fmaxf(v[1][1], fmaxf(v[1][2], v[1][3]));
+                    const int n = nt * 32 + li;
+                    if (lh) {
+                        // the wave's last column: the next wave's left neighbour, or the next strip's (side buffer)
+                        if (wave < 3) s_edge[(epar * 3 + wave) * 64 + n] = v[1][3];
+                        else if (do_store && wo0 + TILE_P < p.Wo && n < p.Cout)
+                            p.seam[((oimg * (p.Ho >> 1) + (ho0 >> 1)) * (int64_t)(tiles_per_row - 1) + wo0 / TILE_P) * p.Cout + n] = v[1][3];
+                    }
+                }
+            }
+            if (!POOL && p.vpool) {
                 // accumulator register e = 4*gq + i holds pixel 8*gq + 4*lh + i: gq 0,1 = upper row, gq 2,3 = lower row
                 const int q4 = (li >> 2) * 4, k = li & 3;
                 const bool do_store = tile >= store_from;            // block-uniform
@@ -373,7 +433,7 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
                 }
             }
             const int ho = ho0 + prow;
-            if (!p.vpool && ho < p.Ho) {
+            if (!chain && ho < p.Ho) {
                 // C layout: lane = channel, registers = pixels.  A 4x4 transpose inside each quad of lanes (4 channels x
                 // 4 consecutive pixels, two DPP quad-permute stages) gives every lane 4 consecutive channels of ONE
                 // pixel: 16-byte stores instead of 4-byte ones (the scalar form ran this epilogue at ~1.5 TB/s).
@@ -412,12 +472,46 @@ __global__ __launch_bounds__(256) void conv1_f16x3_kernel(Conv1Args p, int tiles
         if (has_next) commit(next, s_patch + (cur ^ 1) * F_PATCH);
         __syncthreads();
         cur ^= 1;
+        if constexpr (POOL) {
+            // full pool, second half, behind the step's own barrier (no extra one): the previous wave's last column is in
+            // s_edge now.  The next step writes the other parity, and the one after it is a barrier away, so no wave can
+            // overwrite what a slower one still reads.  Wave 0 of a strip > 0 stores the partial max of its first pooled
+            // column (columns 2c, 2c+1); the seam pass adds the left strip's column.
+            const int q4 = (li >> 2) * 4, k = li & 3;
+            const int pc = (wo0 >> 1) + 8 * wave + 2 * lh + 4 * (k >> 1) + (k & 1);     // the pooled column this lane stores
+            const int Wp = (p.Wo - 1) / 2 + 1;
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                if (!lh && wave > 0) pool4[nt][0] = fmaxf(pool4[nt][0], s_edge[(epar * 3 + wave - 1) * 64 + nt * 32 + li]);
+                quad_transpose(pool4[nt][0], pool4[nt][1], pool4[nt][2], pool4[nt][3], k);
+                const int nb = nt * 32 + q4;
+                if (tile >= store_from && pc < Wp && nb < p.Cout) {
+                    float* dst = p.out + ((oimg * (p.Ho >> 1) + (ho0 >> 1)) * (int64_t)Wp + pc) * p.Cout + nb;
+                    *reinterpret_cast<f32x4*>(dst) = f32x4{pool4[nt][0], pool4[nt][1], pool4[nt][2], pool4[nt][3]};
+                }
+            }
+            epar ^= 1;
+        }
     }
 }
 
 }  // namespace
 
 int64_t conv1_wimg_bytes() { return 2 * F_WBYTES; }
+
+int64_t conv1_seam_floats(int B, int C, int Ho, int Wo, int Cout) {
+    const int strips = (Wo + TILE_P - 1) / TILE_P;
+    return (int64_t)C * B * (Ho / 2) * (strips - 1) * Cout;
+}
+
+int launch_conv1_seam(const Conv1Args& a, hipStream_t st) {
+    const int strips = (a.Wo + TILE_P - 1) / TILE_P, ncam = a.ncam > 0 ? a.ncam : a.C;
+    if (strips < 2) return 0;                                      // one strip per row: no seam, no launch
+    const int64_t row0 = (int64_t)a.cam0 * a.B * (a.Ho / 2);        // both maps are camera-major: a camera range is a run of rows
+    const int Wp = (a.Wo - 1) / 2 + 1;
+    return launch_pool_seam(a.out + row0 * Wp * a.Cout, a.seam + row0 * (strips - 1) * a.Cout, (int64_t)ncam * a.B * (a.Ho / 2), Wp, a.Cout,
+                            strips - 1, TILE_P / 2, st);
+}
 
 int launch_conv1_wimg(const float* w, void* img, int C, int Cout, hipStream_t st, float wscale) {
     // the pad bytes of each row (22 groups x 16 B = 352 of 368) are never read; zeroed so that the image is deterministic
@@ -440,6 +534,7 @@ int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err) {
     }
     static const int env_prec = env_gemm_prec(ACTMI_PREC_F32);
     const bool f16 = (a.prec ? a.prec : env_prec) == ACTMI_PREC_F16X3;
+    if (a.vpool < 0 || a.vpool > 2) { if (err) *err = "conv1: vpool must be 0, 1 or 2"; return -2; }
     if (a.vpool && !f16) { if (err) *err = "conv1: vpool needs prec f16x3"; return -2; }
     // the two precisions differ in tile geometry, LDS size and kernel
     struct Form {
@@ -448,9 +543,11 @@ int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err) {
         int rows, smem;                             // output rows per tile, dynamic LDS bytes
         bool lds_raised;
     };
-    static Form forms[2] = {{{conv1_kernel<0>, conv1_kernel<1>}, {"conv1_kernel<0>", "conv1_kernel<1>"}, 1, P_SMEM, false},
-                            {{conv1_f16x3_kernel<0>, conv1_f16x3_kernel<1>}, {"conv1_f16x3_kernel<0>", "conv1_f16x3_kernel<1>"}, F_ROWS, F_SMEM, false}};
-    Form& form = forms[f16];
+    // (the full-pool instantiation reports under the f16x3 kernel's name: one stem row per image format in a profile)
+    static Form forms[3] = {{{conv1_kernel<0>, conv1_kernel<1>}, {"conv1_kernel<0>", "conv1_kernel<1>"}, 1, P_SMEM, false},
+                            {{conv1_f16x3_kernel<0, false>, conv1_f16x3_kernel<1, false>}, {"conv1_f16x3_kernel<0>", "conv1_f16x3_kernel<1>"}, F_ROWS, F_SMEM, false},
+                            {{conv1_f16x3_kernel<0, true>, conv1_f16x3_kernel<1, true>}, {"conv1_f16x3_kernel<0>", "conv1_f16x3_kernel<1>"}, F_ROWS, F_SMEM_POOL, false}};
+    Form& form = forms[a.vpool == 2 ? 2 : f16];
     const int fmt = a.fmt == 0 ? 0 : 1, ncam = a.ncam > 0 ? a.ncam : a.C;
     const int tiles_per_row = (a.Wo + TILE_P - 1) / TILE_P;
     const int tiles_per_cam = a.B * ((a.Ho + form.rows - 1) / form.rows) * tiles_per_row;
@@ -466,6 +563,10 @@ int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err) {
         if (nseg < 1) nseg = 1;
         av.vpool_nseg = nseg;
         gx = a.B * tiles_per_row * nseg;
+        if (a.vpool == 2 && tiles_per_row > 1 && (!a.seam || a.seam_floats < conv1_seam_floats(a.B, a.C, a.Ho, a.Wo, a.Cout))) {
+            if (err) *err = "conv1: the full pool of a map wider than one strip needs a seam workspace of conv1_seam_floats()";
+            return -2;
+        }
     }
     if (!form.lds_raised) {
         for (auto k : form.kernel)
@@ -475,8 +576,10 @@ int launch_conv1(const Conv1Args& a, hipStream_t st, std::string* err) {
             }
         form.lds_raised = true;
     }
+    // (the full pool writes [Ho/2][(Wo-1)/2+1] pixels and one seam column per strip boundary)
+    const double out_px = a.vpool == 2 ? (double)(a.Ho / 2) * ((a.Wo - 1) / 2 + 1 + tiles_per_row - 1) : (double)a.Ho * a.Wo;
     prof_begin(form.name[fmt], 2.0 * a.B * a.C * a.Ho * a.Wo * a.Cout * 147.0,
-               (double)a.B * a.C * ((double)a.H * a.W * 3 * (fmt == 0 ? 1 : 4) + 4.0 * a.Ho * a.Wo * a.Cout), st);
+               (double)a.B * a.C * ((double)a.H * a.W * 3 * (fmt == 0 ? 1 : 4) + 4.0 * out_px * a.Cout), st);
     hipLaunchKernelGGL(form.kernel[fmt], dim3(gx, ncam), dim3(256), form.smem, st, av, tiles_per_row, tiles_per_cam);
     prof_end(st);
     hipError_t e = hipGetLastError();

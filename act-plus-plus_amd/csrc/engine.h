@@ -210,7 +210,9 @@ struct actmi_ctx {
     uint32_t* flags = nullptr;         // device flag word (ACTMI_FLAG_*)
     float* splitk_ws = nullptr;        // slices of the forward GEMMs whose contraction is split to fill the chip
     int64_t splitk_ws_floats = 0;
-    int conv1_vpool = 1;               // inference: conv1 emits the vertical half of the max pool (ACTMI_CONV1_VPOOL=0: off)
+    int conv1_vpool = 1;               // inference: conv1 writes the finished 3x3 / s2 max pool (ACTMI_CONV1_VPOOL=0: conv1 -> maxpool)
+    float* conv1_seam = nullptr;       // its seam workspace for max_batch (conv1_seam_floats)
+    int64_t conv1_seam_floats = 0;
     int fwd_splitk = 1;                // 0: never split a forward contraction (ACTMI_FWD_SPLITK=0)
     hipStream_t side_stream = nullptr; // downsample branch of the ResNet blocks (engine_backbone)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;

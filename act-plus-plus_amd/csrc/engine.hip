@@ -550,6 +550,8 @@ int create_device_state(actmi_ctx* ctx) {
     }
     // ---- activations (camera-major NHWC maps, token-major [B][N][D])
     ALLOC(ctx->act1, (int64_t)Ct * B * ctx->H1 * ctx->W1 * w0);
+    ctx->conv1_seam_floats = conv1_seam_floats(B, Ct, ctx->H1, ctx->W1, w0);
+    if (ctx->conv1_seam_floats > 0) ALLOC(ctx->conv1_seam, ctx->conv1_seam_floats);
     for (int i = 0; i < 3; ++i) ALLOC(ctx->buf[i], (int64_t)Ct * B * ctx->H2 * ctx->W2 * w0);
     const int64_t BN_ = (int64_t)B * N, BQ = (int64_t)B * Q;
     ALLOC(ctx->X, BN_ * D); ALLOC(ctx->X1, BN_ * D); ALLOC(ctx->XP, BN_ * D); ALLOC(ctx->Y, BN_ * D);
@@ -955,20 +957,25 @@ int engine_backbone(actmi_ctx* ctx, const void* image, const DepthSrc& depth, in
     const actmi_config& g = ctx->cfg;
     const int C = ctx->Ct, w0 = g.base_width, D = g.hidden_dim;
     Conv1Args c1 = stem_args(ctx, image, fmt, B);
-    // inference never needs conv1's own map: the stem emits the vertical half of the max pool (half the bytes) and a
-    // row-wise pass finishes it.  Same maxima, so the result is bit-identical to conv1 -> 3x3 pool.
+    // inference never needs conv1's own map: the stem writes the finished 3x3 / s2 max pool straight into buf[0] (a quarter
+    // of the bytes, nothing read back) and a pass over the strip-boundary columns alone closes the seams.  Same maxima, so the
+    // result is bit-identical to conv1 -> 3x3 pool.
     // (a depth handle keeps the two-kernel form: the depth stem writes conv1's own map)
-    const bool vpool = ctx->conv1_vpool && !ctx->Cd && ctx->stop_stage != "conv1" && ctx->gemm_prec == ACTMI_PREC_F16X3 && (ctx->H1 & 1) == 0 &&
-                       (w0 & 3) == 0 && ctx->H2 == ctx->H1 / 2;
+    const bool pooled = ctx->conv1_vpool && !ctx->Cd && ctx->stop_stage != "conv1" && ctx->gemm_prec == ACTMI_PREC_F16X3 && (ctx->H1 & 1) == 0 &&
+                        (w0 & 3) == 0 && ctx->H2 == ctx->H1 / 2 && ctx->W2 == (ctx->W1 - 1) / 2 + 1;
     // stem (conv1 + pool) of all cameras, ahead of the branches
-    c1.vpool = vpool ? 1 : 0;
     if (ctx->Cd) CHK(engine_depth_minmax(ctx, depth, B, st));              // (2 bytes per pixel, ahead of the RGB stem: the depth stem's re-read finds them cached)
-    CHK(launch_conv1(c1, st, &ctx->err));
-    if (ctx->Cd) CHK(engine_depth_stem(ctx, depth, B, st));                // the depth group's cameras of the same map
-    if (vpool) CHK(launch_hpool(ctx->act1, ctx->buf[0], C * B * ctx->H2, ctx->W1, w0, ctx->W2, st));
-    else CHK(launch_maxpool(ctx->act1, ctx->buf[0], C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st));
     ctx->dbg.clear();
-    ctx->dbg["conv1"] = {ctx->act1, (int64_t)C * B * ctx->H1 * ctx->W1 * w0};
+    if (pooled) {
+        c1.vpool = 2; c1.out = ctx->buf[0]; c1.seam = ctx->conv1_seam; c1.seam_floats = ctx->conv1_seam_floats;
+        CHK(launch_conv1(c1, st, &ctx->err));
+        CHK(launch_conv1_seam(c1, st));
+    } else {
+        CHK(launch_conv1(c1, st, &ctx->err));
+        if (ctx->Cd) CHK(engine_depth_stem(ctx, depth, B, st));            // the depth group's cameras of the same map
+        CHK(launch_maxpool(ctx->act1, ctx->buf[0], C * B, ctx->H1, ctx->W1, w0, ctx->H2, ctx->W2, st));
+        ctx->dbg["conv1"] = {ctx->act1, (int64_t)C * B * ctx->H1 * ctx->W1 * w0};      // (only where conv1's own map exists)
+    }
     ctx->dbg["maxpool"] = {ctx->buf[0], (int64_t)C * B * ctx->H2 * ctx->W2 * w0};
     if (ctx->stop_stage == "conv1" || ctx->stop_stage == "maxpool") return 1;
     // one convolution of the trunk for the cameras [c0, c0 + nc) (feature maps and weights are camera-major, so a camera range

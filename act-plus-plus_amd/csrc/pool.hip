@@ -51,6 +51,23 @@ __global__ __launch_bounds__(256) void hpool_kernel(const float* __restrict__ in
         reinterpret_cast<f32x4*>(out)[idx] = m;
     }
 }
+// seam of the stem's full-pool form (conv1.hip, vpool 2): a pooled column at a strip boundary was stored as the max of its own
+// strip's conv columns; the left strip's last column waits in `side`.  Touches those columns only: each thread 4 channels of one.
+__global__ __launch_bounds__(256) void pool_seam_kernel(float* __restrict__ out, const float* __restrict__ side, int Wp, int C4,
+                                                        int nseam, int period, int64_t total) {
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+        const int c4 = (int)(idx % C4);
+        const int64_t t = idx / C4;
+        const int s = (int)(t % nseam);
+        const int64_t row = t / nseam;
+        f32x4* dst = reinterpret_cast<f32x4*>(out) + (row * Wp + (int64_t)period * (s + 1)) * C4 + c4;
+        const f32x4 v = reinterpret_cast<const f32x4*>(side)[idx];
+        f32x4 m = *dst;
+        m[0] = fmaxf(m[0], v[0]); m[1] = fmaxf(m[1], v[1]); m[2] = fmaxf(m[2], v[2]); m[3] = fmaxf(m[3], v[3]);
+        *dst = m;
+    }
+}
 // training variant: also records, per output element, WHICH of the 9 window positions (r*3+s) held the maximum (the
 // first one in scan order, ATen's tie rule) so that the backward pass is a gather of at most 4 (byte, float) pairs per
 // input element instead of recomputing four 9-element maxima
@@ -106,6 +123,18 @@ int launch_maxpool(const float* in, float* out, int nimg, int H, int W, int C, i
     if (blocks > 256 * 16) blocks = 256 * 16;
     prof_begin("maxpool_kernel", 0.0, 4.0 * nimg * C * ((double)H * W + (double)Ho * Wo), st);
     hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out, H, W, C / 4, Ho, Wo, total);
+    prof_end(st);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_pool_seam(float* out, const float* side, int64_t nrows, int Wp, int C, int nseam, int period, hipStream_t st) {
+    if ((C & 3) || nseam < 0 || period < 1 || (int64_t)period * nseam >= Wp) return -2;
+    const int64_t total = nrows * nseam * (C / 4);
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    if (blocks < 1) return 0;
+    prof_begin("pool_seam_kernel", 0.0, 12.0 * nrows * nseam * C, st);
+    hipLaunchKernelGGL(pool_seam_kernel, dim3((unsigned)blocks), dim3(256), 0, st, out, side, Wp, C / 4, nseam, period, total);
     prof_end(st);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -464,6 +464,17 @@ int actmi_op_conv1_prepared(const void* image_u8, const float* workspace, const 
 int actmi_op_conv1_prepared_ex(const void* image, int image_fmt, const float* workspace, const float* scale, const float* bias,
                                float* out, int B, int C, int H, int W, int Cout, int relu, int vpool, int cam0, int ncam, int prec,
                                void* stream);
+/* The prepared stem with the whole 3x3 / s2 / p1 max pool fused (what inference runs): out [C][B][Ho/2][Wp][Cout], Wp = (Wo-1)/2+1,
+ * element (a, c) = max over conv rows 2a-1 .. 2a+1 and conv columns 2c-1 .. 2c+1 of the ReLU output, rows and columns outside the
+ * map skipped: bit for bit actmi_op_hpool of the vpool 1 form.  Same arguments and conditions as that form (f16x3, relu 1, even Ho,
+ * Cout % 4 == 0, camera range).  The kernel works in strips of 64 conv columns; where Wo > 64 it needs `seam`, a caller-owned
+ * 16-byte aligned workspace of seam_floats >= actmi_op_conv1_seam_floats(B, C, H, W, Cout) floats (whole-tensor like out: a camera
+ * range touches its cameras' part only), and a second small launch finishes the pooled columns 32, 64, .. from it.  A null or
+ * too small workspace is ACTMI_E_SHAPE then; with Wo <= 64 seam may be NULL and nothing more is launched. */
+int64_t actmi_op_conv1_seam_floats(int B, int C, int H, int W, int Cout);
+int actmi_op_conv1_pooled(const void* image, int image_fmt, const float* workspace, const float* scale, const float* bias, float* out,
+                          float* seam, int64_t seam_floats, int B, int C, int H, int W, int Cout, int relu, int cam0, int ncam, int prec,
+                          void* stream);
 /* horizontal half of the 3x3 / s2 / p1 max pool on nrows independent NHWC rows: in [nrows][W][C] -> out [nrows][Wo][C],
  * out[.][pw] = max(in[.][2pw-1 .. 2pw+1]) over the columns inside the row, Wo = (W-1)/2+1; C % 4 == 0 (else ACTMI_E_SHAPE),
  * in / out 16-byte aligned; nrows = 0 is a no-op */

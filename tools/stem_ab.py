@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""Stem kernel times of two builds of the library on one GPU, for checking a change to the stem's loader against the build it
-started from.  The kernels' own times come from the library profiler (the conv1_* rows, microseconds per launch over a window
-of eager forwards) at the benchmark's shape: B = 8, 4 cameras, 480 x 640.
+"""Stem kernel times of two builds of the library on one GPU, for checking a change to the stem against the build it started
+from.  The kernels' own times come from the library profiler (microseconds per launch over a window of eager forwards) at the
+benchmark's shape: B = 8, 4 cameras, 480 x 640: the conv1_* rows, the pool launches behind the stem (hpool_kernel,
+maxpool_kernel, maxpool_idx_kernel, pool_seam_kernel) and, per case, a `stem total` row = microseconds per forward of all of
+them together.
 
-  f16x3 handle   training forward (plain form, u8), inference (vpool form, u8 and f32 images)
+  f16x3 handle   training forward (plain form, u8), inference (pooled form, u8 and f32 images)
   f32 handle     inference (conv1_kernel<0> on u8 images, conv1_kernel<1> on f32 images)
   depth handle   inference with f32 and with raw u16 depth (conv1_depth_kernel, conv1_depth_u16_kernel)
 
 The builds alternate, each repeat in a fresh child process (one library per process).  No threshold is fixed in advance: the
 margin is the first build's own spread (max - min of its repeats), and the second build passes a row when its median is no
-higher than the first build's median plus that spread.
+higher than the first build's median plus that spread (`faster`: lower than the median minus that spread).  A row that only one
+build has (a launch the other does not make) is listed without a verdict; the case's `stem total` carries it.
 
     python tools/stem_ab.py parent=<libactmi.so of the parent> new=<libactmi.so of this tree> [--repeats 3] > profiles/stem_loader_ab.json
 """
@@ -20,6 +23,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B, WINDOW = 8, 20
+POOL_ROWS = ("hpool_kernel", "maxpool_kernel", "maxpool_idx_kernel", "pool_seam_kernel")
 
 
 def child():
@@ -42,9 +46,12 @@ def child():
         torch.cuda.synchronize(dev)
         rep = L.profile_report()
         L.profile_enable(False)
+        total = 0.0
         for r in rep:
-            if r["name"].startswith("conv1_") and r["count"]:
+            if (r["name"].startswith("conv1_") or r["name"] in POOL_ROWS) and r["count"]:
                 rows[f"{label}: {r['name']}"] = round(r["ms"] / r["count"] * 1e3, 2)
+                total += r["ms"]
+        rows[f"{label}: stem total"] = round(total / WINDOW * 1e3, 2)
 
     def engine(cfg, **kw):
         eng = ACTEngine(cfg, max_batch=B, device=str(dev), **kw)
@@ -96,12 +103,17 @@ def main():
     med = lambda v: sorted(v)[len(v) // 2]
     (a, _), (b, _) = builds
     out = {"batch": B, "window_forwards": WINDOW, "unit": "us per launch", "builds": [a, b], "rows": {}}
-    for row in runs[a][0]:
+    for row in list(runs[a][0]) + [r for r in runs[b][0] if r not in runs[a][0]]:
+        if row not in runs[a][0] or row not in runs[b][0]:
+            name = a if row in runs[a][0] else b
+            v = [r[row] for r in runs[name]]
+            out["rows"][row] = {name: v, f"{name}_median": med(v), "only_in": name}
+            continue
         va, vb = [r[row] for r in runs[a]], [r[row] for r in runs[b]]
         spread = round(max(va) - min(va), 2)
         out["rows"][row] = {a: va, b: vb, f"{a}_median": med(va), f"{b}_median": med(vb), f"{a}_spread": spread,
-                            "pass": med(vb) <= med(va) + spread}
-    out["all_pass"] = all(r["pass"] for r in out["rows"].values())
+                            "pass": med(vb) <= med(va) + spread, "faster": med(vb) < med(va) - spread}
+    out["all_pass"] = all(r["pass"] for r in out["rows"].values() if "pass" in r)
     print(json.dumps(out, indent=1))
 
 
