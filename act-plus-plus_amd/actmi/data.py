@@ -33,7 +33,9 @@ Differences, all on the host side of the step:
   same tensors as ``EpisodicDataset.__getitem__`` without the action chunk, in batches of consecutive steps;
 * ``DeviceEpisodeStore`` (``load_data(..., device_dataset=True)``, opt-in) reads every episode ONCE into a device arena; a
   training batch is then two device gathers (three with depth) that give the tensors of ``EpisodicDataset.__getitem__`` + the
-  default collation bit for bit, with no host work, loader worker or PCIe traffic per step."""
+  default collation bit for bit, with no host work, loader worker or PCIe traffic per step;
+* ``DeviceEpisodeReplay`` is ``EpisodeReplay`` out of such a store (``DeviceEpisodeStore.replay_batch``): one stored episode in
+  time order, the same tensors bit for bit, already on the device -- what ``--replay_every`` replays while training."""
 import fnmatch
 import os
 
@@ -709,6 +711,7 @@ class DeviceEpisodeStore:
         rec["row0"], rec["T"], rec["is_sim"] = self.row0, self.T, np.asarray(sims, dtype=np.int32)
         self.is_sim = sims
         self.episodes = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+        self.norm_stats = norm_stats                                  # as given: what a replay out of the store un-normalises with
         self._stats = [torch.as_tensor(np.asarray(norm_stats[k]), dtype=torch.float32).reshape(-1).contiguous().to(dev)
                        for k in ("action_mean", "action_std", "qpos_mean", "qpos_std")]
         if self._stats[0].numel() != self.A or self._stats[2].numel() != self.S:
@@ -813,8 +816,64 @@ class DeviceEpisodeStore:
                               aligned=2 if (nontemporal and self.depth_aligned) else self.depth_aligned)
         return image, qpos, action, is_pad, depth
 
+    def replay_batch(self, local_episode, steps):
+        """the steps ``steps`` of ONE stored episode in the layout the policy's inference call takes, on the current stream of
+        the store's device: (image u8 [b, K, H, W, 3], qpos f32 [b, S] z-scored[, depth uint16 [b, Kd, 1, H, W]]) -- what
+        ``EpisodeReplay`` yields for these steps, bit for bit.  The two gathers of ``gather`` serve it (the qpos rows come from
+        ``gather_chunks`` with a chunk of one step, which is dropped)."""
+        steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+        if len(steps) * max(self.K, self.Kd) > 65535:
+            raise ValueError(f"DeviceEpisodeStore.replay_batch: {len(steps)} steps of {max(self.K, self.Kd)} cameras are more than "
+                             "the 65535 items of one frame gather")
+        out = self.gather(np.full(len(steps), int(local_episode), dtype=np.int64), steps, 1)
+        return (out[0], out[1]) + tuple(out[4:])
+
     def loader(self, episode_ids, episode_len, chunk_size, batch_sampler):
         return DeviceBatchLoader(self, episode_ids, episode_len, chunk_size, batch_sampler)
+
+
+class DeviceEpisodeReplay:
+    """``EpisodeReplay`` out of a ``DeviceEpisodeStore``: one stored episode (``episode_id`` as the store was given it) in time
+    order, ``batch`` replayed steps at a time (the last batch ragged), only every ``stride``-th step.  The same iterable with the
+    same attributes -- ``.T``, ``.steps``, ``.is_sim``, ``.actions`` (host [T, A] f32 in file units, copied from the device when
+    first asked for), ``__len__`` -- and the tensors it yields are bit for bit those ``EpisodeReplay`` yields for the same file,
+    batch and stride, but already on the device (``on_device``): no file is opened and nothing is pinned or copied from the host.
+    ``.actions_device``: the episode's action rows [T, A] f32, a view of the store's."""
+
+    on_device = True
+
+    def __init__(self, store, episode_id, batch, stride=1):
+        self.store, self.batch, self.stride = store, int(batch), int(stride)
+        if self.batch < 1 or self.stride < 1:
+            raise ValueError(f"batch {batch} and stride {stride} must be at least 1")
+        if int(episode_id) not in store._local_of:
+            raise ValueError(f"DeviceEpisodeReplay: episode {episode_id} is not in the store (it holds {store.episode_ids})")
+        cams = max(store.K, store.Kd)
+        if self.batch * cams > 65535:
+            raise ValueError(f"DeviceEpisodeReplay: a batch of {self.batch} steps of {cams} cameras is more than the 65535 items of "
+                             f"one frame gather: at most {65535 // cams}")
+        self.episode_id = int(episode_id)
+        self.local = store._local_of[self.episode_id]
+        self.dataset_path = store.paths[self.local]
+        self.T = int(store.T[self.local])
+        self.is_sim = bool(store.is_sim[self.local])
+        self.steps = list(range(0, self.T, self.stride))
+        row0 = int(store.row0[self.local])
+        self.actions_device = store.actions[row0:row0 + self.T]
+        self._actions = None
+
+    @property
+    def actions(self):
+        if self._actions is None:
+            self._actions = np.ascontiguousarray(self.actions_device.cpu().numpy(), dtype=np.float32)
+        return self._actions
+
+    def __len__(self):
+        return (len(self.steps) + self.batch - 1) // self.batch
+
+    def __iter__(self):
+        for b0 in range(0, len(self.steps), self.batch):
+            yield self.store.replay_batch(self.local, self.steps[b0:b0 + self.batch])
 
 
 class DeviceBatchLoader:
@@ -828,6 +887,7 @@ class DeviceBatchLoader:
     def __init__(self, store, episode_ids, episode_len, chunk_size, batch_sampler):
         self.store = store
         ids = [int(i) for i in episode_ids]
+        self.episode_ids = ids                 # as the store was given them (train_bc replays the validation loader's)
         missing = [i for i in ids if i not in store._local_of]
         if missing:
             raise ValueError(f"DeviceBatchLoader: episodes {missing} are not in the store")

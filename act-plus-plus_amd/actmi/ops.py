@@ -1565,6 +1565,64 @@ def action_error_ref(raw, target, lengths, mean, std, want_pred=True):
     return (pred if want_pred else None), stats
 
 
+def chunk_error(chunks, actions, lengths, shift, mean, std, stride=1):
+    """The error along the predicted chunk on the device (actmi_op_chunk_error).  chunks [E, S, Q, A] f32 cuda (normalised
+    a_hat): row s is the chunk predicted from frame r = s * stride; actions [E, T, A] f32 (file units, NOT aligned); lengths [E]
+    or None (= T); shift [E] of 0 / 1 or None (= 0; 1: a real-robot episode under align="train"); mean / std [A].  Slot j of row
+    s is compared with actions[e, max(0, r - shift[e]) + j] while r and that index are below the length: the entries the dataset
+    trains the slot on.  -> (stats [E, Q, 3, A] f64 = sum |d|, sum d^2, max |d|, count [E, Q] int32 pairs per slot)."""
+    if chunks.dim() != 4 or chunks.dtype != torch.float32 or not chunks.is_cuda:
+        raise ValueError(f"chunks must be a float32 cuda tensor [E, S, Q, A], got {chunks.dtype} {tuple(chunks.shape)} on {chunks.device}")
+    chunks = chunks.contiguous()
+    E, S, Q, A = (int(v) for v in chunks.shape)
+    dev = chunks.device
+    actions = torch.as_tensor(actions).to(device=dev, dtype=torch.float32).contiguous()
+    if actions.dim() != 3 or int(actions.shape[0]) != E or int(actions.shape[2]) != A:
+        raise ValueError(f"actions has shape {tuple(actions.shape)}, expected ({E}, T, {A})")
+    T, stride = int(actions.shape[1]), int(stride)
+    if E > 65535 or Q > 65535 or Q < 1 or A < 1 or T < 1 or stride < 1:
+        raise ValueError(f"chunk_error: E {E} and Q {Q} must be at most 65535, Q, A {A}, T {T} and stride {stride} at least 1")
+    mean, std = (torch.as_tensor(v).to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for v in (mean, std))
+    if mean.numel() != A or std.numel() != A:
+        raise ValueError(f"mean / std hold {mean.numel()} / {std.numel()} values for action_dim {A}")
+    ln = _lengths_i32(lengths, E, T, dev)
+    sh = _lengths_i32(shift, E, T, dev)
+    if not (E and S):                            # nothing is launched: the zeros are the answer
+        return torch.zeros((E, Q, 3, A), dtype=torch.float64, device=dev), torch.zeros((E, Q), dtype=torch.int32, device=dev)
+    stats = torch.empty((E, Q, 3, A), dtype=torch.float64, device=dev)      # the kernel writes every entry, the empty slots' zeros too
+    count = torch.empty((E, Q), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_chunk_error(_p(chunks), _p(actions), _p(ln), _p(sh), _p(mean), _p(std), stride, _p(stats),
+                                              _p(count), E, S, T, Q, A, L.current_stream_ptr()), None, "op_chunk_error")
+    return stats, count
+
+
+def chunk_error_ref(chunks, actions, lengths, shift, mean, std, stride=1):
+    """numpy statement of ``chunk_error`` (float64); needs no library.  -> (stats [E, Q, 3, A], count [E, Q] int32) as ndarrays."""
+    import numpy as np
+    c = np.asarray(chunks, dtype=np.float32).astype(np.float64)
+    a = np.asarray(actions, dtype=np.float32).astype(np.float64)
+    E, S, Q, A = c.shape
+    T, stride = a.shape[1], int(stride)
+    if a.shape[0] != E or a.shape[2] != A or T < 1 or stride < 1:
+        raise ValueError(f"chunk_error_ref: chunks {c.shape}, actions {a.shape}, stride {stride}")
+    ln = np.full(E, T, dtype=np.int64) if lengths is None else np.clip(np.asarray(lengths, dtype=np.int64), 0, T)
+    sh = np.zeros(E, dtype=np.int64) if shift is None else (np.asarray(shift, dtype=np.int64) > 0).astype(np.int64)
+    sd, mu = np.asarray(std, dtype=np.float64).reshape(1, A), np.asarray(mean, dtype=np.float64).reshape(1, A)
+    stats = np.zeros((E, Q, 3, A), dtype=np.float64)
+    count = np.zeros((E, Q), dtype=np.int32)
+    r = np.arange(S, dtype=np.int64) * stride
+    for e in range(E):
+        base = np.maximum(0, r - sh[e])
+        for j in range(Q):
+            ok = (r < ln[e]) & (base + j < ln[e])
+            if ok.any():
+                d = np.abs(c[e, ok, j] * sd + mu - a[e, base[ok] + j])
+                stats[e, j] = np.stack([d.sum(axis=0), (d * d).sum(axis=0), d.max(axis=0)])
+                count[e, j] = int(ok.sum())
+    return stats, count
+
+
 # ---- device-resident episode store (csrc/episode_store.hip; contracts at actmi_op_gather_frames / actmi_op_gather_chunks) ------
 def episode_rec_dtype():
     """actmi_episode_rec as a numpy structured dtype (16 bytes)"""

@@ -290,6 +290,22 @@ int actmi_op_action_error(const double* raw, const float* target, const int32_t*
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
 }
 
+int actmi_op_chunk_error(const float* chunks, const float* actions, const int32_t* lengths, const int32_t* shift, const double* mean,
+                         const double* stdv, int stride, double* stats, int32_t* count, int E, int n_rows, int T, int Q, int A,
+                         void* stream) {
+    g_op_error.clear();
+    if (E < 0 || n_rows < 0 || E > 65535 || Q < 1 || Q > 65535 || A < 1 || stride < 1 || T < 1) {
+        g_op_error = "chunk_error: E and Q must be at most 65535 (grid extents), Q, A, T and stride at least 1, E and S not negative";
+        return ACTMI_E_INVALID;
+    }
+    if (!chunks || !actions || !mean || !stdv || !stats || !count) {
+        g_op_error = "chunk_error: null chunks, actions, mean, std, stats or count";
+        return ACTMI_E_INVALID;
+    }
+    const int rc = launch_chunk_error(chunks, actions, lengths, shift, mean, stdv, stride, stats, count, E, n_rows, T, Q, A, S(stream));
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_gemm(const actmi_gemm_desc* d, void* stream) {
     if (!d) return ACTMI_E_INVALID;
     g_op_error.clear();

@@ -200,6 +200,9 @@ int launch_ensemble_episode(const float* chunks, const int32_t* lengths, double 
                             int Q, int A, hipStream_t st);
 int launch_action_error(const double* raw, const float* target, const int32_t* lengths, const double* mean, const double* stdv,
                         double* pred, double* stats, int E, int T, int A, hipStream_t st);
+int launch_chunk_error(const float* chunks, const float* actions, const int32_t* lengths, const int32_t* shift, const double* mean,
+                       const double* stdv, int stride, double* stats, int32_t* count, int E, int S, int T, int Q, int A,
+                       hipStream_t st);
 int launch_bn_fold(const float* w, const float* b, const float* rm, const float* rv, float* scale, float* bias, int n,
                    hipStream_t st);
 int launch_build_rowmap(int* map, int B, int C, int fh, int fw, int N, int n_extra, hipStream_t st);

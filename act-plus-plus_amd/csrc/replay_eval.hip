@@ -86,6 +86,74 @@ __global__ __launch_bounds__(256) void action_error_kernel(const double* __restr
     }
 }
 
+// The error along the predicted chunk: chunks [E][S][Q][A], row s of episode e is the chunk predicted from frame r = s * stride, and
+// its slot j is compared with actions[e][max(0, r - shift[e]) + j] -- the entry gather_chunks_kernel trains that slot on -- while
+// r < len and max(0, r - shift) + j < len (the entries whose is_pad is 0).  d = |chunk * std + mean - action| in float64, product
+// and sum rounded separately as in action_error_kernel.  One workgroup per (block of `per` components, slot, episode): thread (a, g)
+// walks s = g, g + ng, ... in order, the ng partial results are combined in index order -- a fixed shape, so two runs give the
+// same bits.  Every index is held to its array.
+__global__ __launch_bounds__(256) void chunk_error_kernel(const float* __restrict__ chunks, const float* __restrict__ actions,
+                                                          const int32_t* __restrict__ lengths, const int32_t* __restrict__ shift,
+                                                          const double* __restrict__ mean, const double* __restrict__ stdv,
+                                                          int stride, double* __restrict__ stats, int32_t* __restrict__ count,
+                                                          int S, int T, int Q, int A, int per) {
+    __shared__ double s_part[3][256];
+    __shared__ int s_n[256];
+    const int e = blockIdx.z, j = blockIdx.y, tid = threadIdx.x;
+    const int al = tid % per, g = tid / per, ng = 256 / per;
+    const int a = blockIdx.x * per + al;
+    int Te = lengths ? lengths[e] : T;
+    Te = Te < 0 ? 0 : (Te > T ? T : Te);
+    const int sh = shift ? (shift[e] > 0 ? 1 : 0) : 0;
+    const bool live = a < A;
+    const double sd = live ? stdv[a] : 0.0, mu = live ? mean[a] : 0.0;
+    const float* ce = chunks + (int64_t)e * S * Q * A;
+    const float* ae = actions + (int64_t)e * T * A;
+    double s1 = 0.0, s2 = 0.0, mx = 0.0;
+    int n = 0;
+    for (int s = g; s < S; s += ng) {
+        const int64_t r = (int64_t)s * stride;
+        const int64_t i = (r > sh ? r - sh : 0) + j;               // grows with s: once it leaves the episode, so do the later rows
+        if (r >= Te || i >= Te) break;
+        ++n;
+        if (live) {
+            const int64_t ii = i < T ? i : T - 1;                  // i < Te <= T already
+            double p;
+            {
+#pragma clang fp contract(off)
+                const double prod = (double)ce[((int64_t)s * Q + j) * A + a] * sd;
+                p = prod + mu;
+            }
+            const double d = fabs(p - (double)ae[ii * A + a]);
+            s1 += d;
+            s2 += d * d;
+            mx = fmax(mx, d);
+        }
+    }
+    s_part[0][tid] = s1;
+    s_part[1][tid] = s2;
+    s_part[2][tid] = mx;
+    s_n[tid] = n;
+    __syncthreads();
+    if (tid < per && live) {
+        double t1 = 0.0, t2 = 0.0, tm = 0.0;
+        for (int gg = 0; gg < ng; ++gg) {
+            t1 += s_part[0][gg * per + tid];
+            t2 += s_part[1][gg * per + tid];
+            tm = fmax(tm, s_part[2][gg * per + tid]);
+        }
+        double* st = stats + ((int64_t)e * Q + j) * 3 * A;
+        st[a] = t1;
+        st[A + a] = t2;
+        st[2 * A + a] = tm;
+    }
+    if (tid == 0 && blockIdx.x == 0) {
+        int tn = 0;
+        for (int gg = 0; gg < ng; ++gg) tn += s_n[gg * per];
+        count[(int64_t)e * Q + j] = tn;
+    }
+}
+
 }  // namespace
 
 int launch_ensemble_episode(const float* chunks, const int32_t* lengths, double k, double* out, uint8_t* populated, int E, int T,
@@ -104,5 +172,17 @@ int launch_action_error(const double* raw, const float* target, const int32_t* l
     const int per = A <= 16 ? 16 : (A <= 32 ? 32 : 64);
     hipLaunchKernelGGL(action_error_kernel, dim3((A + per - 1) / per, E), dim3(256), 0, st, raw, target, lengths, mean, stdv, pred,
                        stats, T, A, per);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_chunk_error(const float* chunks, const float* actions, const int32_t* lengths, const int32_t* shift, const double* mean,
+                       const double* stdv, int stride, double* stats, int32_t* count, int E, int S, int T, int Q, int A,
+                       hipStream_t st) {
+    if (E < 0 || S < 0 || E > 65535 || Q < 1 || Q > 65535 || A < 1 || stride < 1 || T < 1) return -2;
+    if (!chunks || !actions || !mean || !stdv || !stats || !count) return -2;
+    if (E == 0 || S == 0) return 0;
+    const int per = A <= 16 ? 16 : (A <= 32 ? 32 : 64);
+    hipLaunchKernelGGL(chunk_error_kernel, dim3((A + per - 1) / per, Q, E), dim3(256), 0, st, chunks, actions, lengths, shift, mean,
+                       stdv, stride, stats, count, S, T, Q, A, per);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -9,7 +9,9 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
   takes a contiguous slice, a single all-gather of (episode_return, highest_reward) ends the run;
 * the 10 warm-up queries per rollout and the real-time sleep (:377-382, :467-470) are off by default;
 * ``replay_bc`` (``--eval --replay``) evaluates open loop on recorded episodes instead -- the one evaluation of use_depth /
-  use_pcd policies and of policies trained on real-robot episodes: queries batched over TIME, one ensemble launch per episode.
+  use_pcd policies and of policies trained on real-robot episodes: queries batched over TIME, one ensemble launch per episode;
+* ``--device_dataset --replay_every N`` runs that replay on held-out episodes every N training steps, out of the device-resident
+  store the batches come from (no file read); ``--replay_horizon`` adds the error along the predicted chunk.
 """
 import argparse
 import os
@@ -394,6 +396,27 @@ def replay_metrics(rows, action_dim):
     return dict(figures(total, s1, s2, mx), episodes=episodes, steps=int(total))
 
 
+def horizon_slots(Q):
+    """the five slots of a chunk the horizon figures are printed and logged for"""
+    return [0, Q // 4, Q // 2, 3 * Q // 4, Q - 1]
+
+
+def horizon_metrics(rows, num_queries, action_dim):
+    """rows [n, Q * (1 + 3A)] float64 = per episode (pairs [Q], then per slot sum |d| [A], sum d^2 [A], max |d| [A]) -> the pooled
+    error of slot j of a predicted chunk against the action j steps ahead.  Sums and counts are added over the episodes and then
+    divided (never an average of averages); a slot without a pair gives zeros."""
+    Q, A = num_queries, action_dim
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, Q * (1 + 3 * A))
+    count = rows[:, :Q].sum(axis=0)
+    st = rows[:, Q:].reshape(-1, Q, 3, A)
+    s1, s2 = st[:, :, 0].sum(axis=0), st[:, :, 1].sum(axis=0)
+    mx = st[:, :, 2].max(axis=0) if len(rows) else np.zeros((Q, A))
+    n = np.maximum(count, 1.0)[:, None]
+    mae, rmse = s1 / n, np.sqrt(s2 / n)
+    return {"mae": mae.tolist(), "rmse": rmse.tolist(), "max": mx.tolist(), "mae_mean": mae.mean(axis=1).tolist(),
+            "count": [int(c) for c in count]}
+
+
 def _gather_rows_f64(local, counts):
     """dist_utils.all_gather_rows moves float32 rows; float64 rows travel as their bit pattern (two float32 words per value: the
     collective only copies), so the pooled sums are the same bits with one rank or many"""
@@ -404,7 +427,7 @@ def _gather_rows_f64(local, counts):
 
 
 def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=None, episode_ensemble=None, align="train",
-              save_episode=True, verbose=True, action_error=None, vq_sampler=None):
+              save_episode=True, verbose=True, action_error=None, vq_sampler=None, store=None, horizon=False, chunk_error=None):
     """Open-loop replay evaluation on recorded episodes (the fork's eval_arm_gripper_depth.py:343-418 without its plots): the
     policy is queried on an episode's recorded observations, the chunks are ensembled over time (``temporal_agg``) or executed
     chunk by chunk, un-normalised, and compared with the recorded ``/action``.  Serves what ``eval_bc`` cannot roll out --
@@ -420,10 +443,21 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     sharded over the ranks.  ``align``: "train" compares step t with action[t] of a sim episode and action[max(0, t-1)] of a
     real one (the shift the dataset trains slot 0 on), "none" with action[t] as the fork's plot does.  ``policy``,
     ``episode_ensemble`` and ``action_error`` can be given (CPU stand-ins: ops.episode_ensemble_ref, ops.action_error_ref).
+
+    ``store`` (an actmi.data.DeviceEpisodeStore, as ``--device_dataset`` training holds): the episodes are replayed out of device
+    memory through ``DeviceEpisodeReplay`` -- no file is opened, nothing is pinned or copied from the host, the target rows are
+    taken on the device from the store's action rows; everything after the queries is unchanged.  ``episodes`` may then also be a
+    list of episode ids of the store (None: all it holds, an int n: the first n).
+
+    ``horizon``: one ``ops.chunk_error`` launch per episode on the table the replay already holds (``chunk_error=``:
+    ops.chunk_error_ref is the CPU stand-in) gives the error of slot j of a predicted chunk against the action j steps ahead, the
+    entry the dataset trains that slot on under ``align="train"``; the rows are pooled over the episodes like the others and
+    returned as ``result["horizon"] = {"mae": [Q][A], "rmse": [Q][A], "max": [Q][A], "mae_mean": [Q], "count": [Q]}``.  Without
+    ``horizon`` the result and the files have no such key.
     Returns {"episodes": [...], "mae": [A], "rmse": [A], "max": [A], "mae_mean", "rmse_mean", "max_max", "steps", ...} in
     action units; with ``save_episode`` rank 0 writes replay_<ckpt>.json and per episode replay_<ckpt>_ep<i>.npz (pred, target)."""
     import json
-    from actmi.data import DevicePrefetcher, EpisodeReplay, find_all_hdf5
+    from actmi.data import DeviceEpisodeReplay, DevicePrefetcher, EpisodeReplay, find_all_hdf5
     ckpt_dir = config["ckpt_dir"]
     policy_class = config["policy_class"]
     policy_config = config["policy_config"]
@@ -437,6 +471,8 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     rank, world, local_rank = dist_utils.init_from_env()
     on_gpu = torch.cuda.is_available()
     dev = torch.device("cuda", local_rank if world > 1 else torch.cuda.current_device()) if on_gpu else torch.device("cpu")
+    if stats is None and store is not None:
+        stats = getattr(store, "norm_stats", None)                   # the statistics the store z-scores its qpos rows with
     policy, stats = _load_policy_and_stats(config, ckpt_name, policy, stats, dev, verbose)
     use_vq = bool(policy_config.get("vq", False))
     if use_vq and vq_sampler is None:
@@ -454,14 +490,33 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
         from actmi import ops
         episode_ensemble = episode_ensemble or ops.episode_ensemble
         action_error = action_error or ops.action_error
+    if horizon and chunk_error is None:
+        from actmi import ops
+        chunk_error = ops.chunk_error
     dataset_dir = config.get("dataset_dir")
-    if not (dataset_dir and os.path.isdir(dataset_dir)):
-        raise ValueError(f"replay_bc needs recorded episodes: config['dataset_dir'] = {dataset_dir!r} is not a directory (--dataset_dir)")
-    files = find_all_hdf5(dataset_dir, bool(config.get("skip_mirrored_data", False)))
-    if episodes is not None:
-        files = files[:int(episodes)]
-    if not files:
-        raise ValueError(f"replay_bc: no episode files under {dataset_dir}")
+    if store is not None:
+        if use_pcd:
+            raise NotImplementedError("replay_bc: the device-resident store holds no point clouds (use_pcd)")
+        if episodes is None or isinstance(episodes, (int, np.integer)):
+            ids = list(store.episode_ids)[:None if episodes is None else int(episodes)]
+        else:
+            ids = [int(i) for i in episodes]
+        if not ids:
+            raise ValueError("replay_bc: no episodes to replay out of the store")
+        missing = [i for i in ids if i not in store._local_of]
+        if missing:
+            raise ValueError(f"replay_bc: episodes {missing} are not in the store (it holds {list(store.episode_ids)})")
+        files = [store.paths[store._local_of[i]] for i in ids]
+    else:
+        if not (dataset_dir and os.path.isdir(dataset_dir)):
+            raise ValueError(f"replay_bc needs recorded episodes: config['dataset_dir'] = {dataset_dir!r} is not a directory (--dataset_dir)")
+        files = find_all_hdf5(dataset_dir, bool(config.get("skip_mirrored_data", False)))
+        if episodes is not None:
+            if not isinstance(episodes, (int, np.integer)):
+                raise ValueError("replay_bc: a list of episode ids names episodes of a store (store=...)")
+            files = files[:int(episodes)]
+        if not files:
+            raise ValueError(f"replay_bc: no episode files under {dataset_dir}")
     n = len(files)
     lo, hi = shard_range(n, rank, world)
     spans = [shard_range(n, r, world) for r in range(world)]
@@ -470,20 +525,26 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     if mean.shape[0] != A or std.shape[0] != A:
         raise ValueError(f"the dataset statistics hold {mean.shape[0]} action components, the policy's action_dim is {A}")
 
-    local_rows, local_pt = [], []
+    local_rows, local_pt, local_hz = [], [], []
     time0, n_frames = time.time(), 0
+    stride = 1 if temporal_agg else Q
     for i in range(lo, hi):
-        ep = EpisodeReplay(files[i], camera_names, stats, batch, depth_camera_names=policy_config.get("depth_camera_names"),
-                           use_depth=use_depth, pointcloud_names=config.get("pointcloud_names"), use_pcd=use_pcd,
-                           max_points=policy_config.get("max_points"), pcd_ignore_mask=bool(config.get("pcd_ignore_mask", False)),
-                           stride=1 if temporal_agg else Q)
-        if ep.actions.shape[1] != A:
-            raise ValueError(f"{files[i]}: the recorded actions are {ep.actions.shape[1]} wide, the policy's action_dim is {A}")
+        if store is not None:
+            ep = DeviceEpisodeReplay(store, ids[i], batch, stride=stride)
+            actions = ep.actions_device                                                              # [T, A] f32, file units
+        else:
+            ep = EpisodeReplay(files[i], camera_names, stats, batch, depth_camera_names=policy_config.get("depth_camera_names"),
+                               use_depth=use_depth, pointcloud_names=config.get("pointcloud_names"), use_pcd=use_pcd,
+                               max_points=policy_config.get("max_points"), pcd_ignore_mask=bool(config.get("pcd_ignore_mask", False)),
+                               stride=stride)
+            actions = torch.from_numpy(ep.actions)
+        if actions.shape[1] != A:
+            raise ValueError(f"{files[i]}: the recorded actions are {actions.shape[1]} wide, the policy's action_dim is {A}")
         T = ep.T
         # the chunk of replayed step s: row s of the table (temporal_agg: s = t, every frame; else s = t // Q)
         table = torch.zeros((1, len(ep.steps), Q, A), dtype=torch.float32, device=dev)
         s0 = 0
-        for data in DevicePrefetcher(ep, device=dev if on_gpu else None):
+        for data in (ep if store is not None else DevicePrefetcher(ep, device=dev if on_gpu else None)):
             a_hat = _replay_query(policy, data, use_depth, use_pcd, vq_sampler)
             table[0, s0:s0 + a_hat.shape[0]] = a_hat
             s0 += a_hat.shape[0]
@@ -492,16 +553,19 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
             raw = torch.as_tensor(episode_ensemble(table, None, 0.01)).to(torch.float64)            # [1, T, A]
         else:
             raw = table.reshape(1, -1, A)[:, :T].to(torch.float64)                                  # reference :392
-        idx = np.arange(T)
-        if align == "train" and not ep.is_sim:
-            idx = np.maximum(0, idx - 1)                                                             # utils.py:112-114
-        target = np.ascontiguousarray(ep.actions[idx])[None]                                         # [1, T, A] f32, file units
-        pred, st = action_error(raw, torch.from_numpy(target), None, mean, std)
+        shift = 1 if (align == "train" and not ep.is_sim) else 0                                     # utils.py:112-114
+        # [1, T, A] f32, file units: row t is action[max(0, t - shift)] (taken where the rows are: on the device with a store)
+        target = (torch.cat([actions[:1], actions[:T - 1]], dim=0) if shift else actions)[None]
+        pred, st = action_error(raw, target, None, mean, std)
         st = torch.as_tensor(st).to(torch.float64).cpu().reshape(1, 3 * A)
         local_rows.append(torch.cat([torch.tensor([[float(T)]], dtype=torch.float64), st], dim=1))
+        if horizon:
+            hst, hcnt = chunk_error(table, actions[None], None, [shift], mean, std, stride)
+            local_hz.append(torch.cat([torch.as_tensor(hcnt).to(torch.float64).cpu().reshape(1, Q),
+                                       torch.as_tensor(hst).to(torch.float64).cpu().reshape(1, Q * 3 * A)], dim=1))
         if save_episode:
             local_pt.append(torch.cat([torch.as_tensor(pred).to(torch.float64).cpu().reshape(T, A),
-                                       torch.from_numpy(target[0]).to(torch.float64)], dim=1))
+                                       target[0].to(torch.float64).cpu()], dim=1))
         if engine is not None and hasattr(engine, "check_flags") and on_gpu:
             engine.check_flags()
     if verbose and n_frames:
@@ -511,7 +575,11 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     local = torch.cat(local_rows, dim=0) if local_rows else torch.zeros((0, 1 + 3 * A), dtype=torch.float64)
     rows = _gather_rows_f64(local, [b - a for a, b in spans]).numpy()
     result = replay_metrics(rows, A)
-    result.update(align=align, temporal_agg=bool(temporal_agg), num_queries=Q, files=[os.path.relpath(f, dataset_dir) for f in files])
+    result.update(align=align, temporal_agg=bool(temporal_agg), num_queries=Q,
+                  files=[os.path.relpath(f, dataset_dir) if dataset_dir else f for f in files])
+    if horizon:
+        mine = torch.cat(local_hz, dim=0) if local_hz else torch.zeros((0, Q * (1 + 3 * A)), dtype=torch.float64)
+        result["horizon"] = horizon_metrics(_gather_rows_f64(mine, [b - a for a, b in spans]).numpy(), Q, A)
     if save_episode:
         Ts = rows[:, 0].astype(np.int64)
         per_rank = [int(Ts[a:b].sum()) for a, b in spans]
@@ -534,6 +602,11 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
         for a in range(A):
             print(f"{a:5d} {result['mae'][a]:10.5f} {result['rmse'][a]:10.5f} {result['max'][a]:10.5f}")
         print(f" mean {result['mae_mean']:10.5f} {result['rmse_mean']:10.5f} {result['max_max']:10.5f} (max)")
+        if horizon:
+            hz = result["horizon"]
+            for j in horizon_slots(Q):
+                print(f"slot {j:4d}: MAE {hz['mae_mean'][j]:10.5f} over the joints, {hz['count'][j]} pairs "
+                      f"(the action {j} steps ahead of the query)")
     return result
 
 
@@ -612,6 +685,17 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
         eval_every = 0
     validate_every = config["validate_every"]
     save_every = config["save_every"]
+    # --replay_every: open-loop replay of validation episodes out of the device-resident store the loaders share
+    replay_every = int(config.get("replay_every") or 0)
+    replay_store = getattr(train_dataloader, "store", None)
+    replay_ids = list(getattr(val_dataloader, "episode_ids", []))
+    if replay_every:
+        if replay_store is None or not replay_ids:
+            raise ValueError("--replay_every replays validation episodes out of the device-resident store: it needs the loaders of "
+                             "--device_dataset (load_data(..., device_dataset=True))")
+        if config.get("replay_episodes") is not None:
+            replay_ids = replay_ids[:int(config["replay_episodes"])]
+    replay_history, best_replay = [], None
     # data parallel (one process per GPU under torch.distributed.run): every rank builds the same initial policy on its own
     # device, draws ITS OWN batches and dropout masks (seed + rank), averages gradients over RCCL in loss.backward(); only
     # rank 0 writes checkpoints
@@ -671,6 +755,24 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
                                  verbose=(rank == 0))
             if log:
                 log({"success": success}, step)
+        if replay_every and step > 0 and step % replay_every == 0:
+            # every rank replays its share of the episodes and all of them pool the figures.  The queries run on the training
+            # handle: its prepared weights (split images, repacked and fused convolutions, decoder constants) are rebuilt by every
+            # optimizer step, so they are the weights of this step.  Nothing is drawn from the batch sampler, the dropout counter
+            # or the augmenter, and replay_bc reads the range guard's flags after every episode (a raised flag is an error there).
+            policy.eval()
+            res = replay_bc(config, None, policy=policy, stats=replay_store.norm_stats, store=replay_store, episodes=replay_ids,
+                            align=config.get("replay_align") or "train", save_episode=False, verbose=(rank == 0),
+                            horizon=bool(config.get("replay_horizon")))
+            figures = {"replay_mae_mean": res["mae_mean"], "replay_rmse_mean": res["rmse_mean"], "replay_max_max": res["max_max"]}
+            if "horizon" in res:
+                for j in horizon_slots(int(policy_config["num_queries"])):
+                    figures[f"replay_h{j}_mae"] = res["horizon"]["mae_mean"][j]
+            replay_history.append(dict(figures, step=step, steps=res["steps"], episodes=len(res["episodes"])))
+            if best_replay is None or res["mae_mean"] < best_replay[1]:
+                best_replay = (step, res["mae_mean"], deepcopy(policy.serialize()))
+            if log:
+                log(figures, step)
         policy.train()
         optimizer.zero_grad()
         data = next(train_dataloader)
@@ -689,6 +791,13 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
         torch.save(policy.serialize(), os.path.join(ckpt_dir, "policy_last.ckpt"))
         torch.save(best_state_dict, os.path.join(ckpt_dir, f"policy_step_{best_step}_seed_{seed}.ckpt"))
         print(f"Training finished:\nSeed {seed}, val loss {min_val_loss:.6f} at step {best_step}")
+        if replay_every:
+            import json
+            with open(os.path.join(ckpt_dir, "replay_history.json"), "w") as f:
+                json.dump(replay_history, f, indent=1)
+            if best_replay is not None:
+                torch.save(best_replay[2], os.path.join(ckpt_dir, "policy_best_replay.ckpt"))
+                print(f"Best open-loop replay: MAE {best_replay[1]:.6f} at step {best_replay[0]}")
     dist_utils.barrier()                # checkpoints are on disk before any rank goes on to read them
     return best_ckpt_info
 
@@ -762,6 +871,19 @@ def build_config(args):
         config["device_dataset"] = True
         if args.get("device_dataset_gb") is not None:
             config["device_dataset_gb"] = float(args["device_dataset_gb"])
+    if args.get("replay_every"):
+        if int(args["replay_every"]) < 0:
+            raise ValueError("--replay_every must not be negative")
+        if policy_class != "ACT":
+            raise NotImplementedError("--replay_every: the periodic open-loop replay belongs to the ACT training path")
+        if args.get("use_pcd"):
+            raise NotImplementedError("--replay_every with --use_pcd: the device-resident store holds no point clouds; evaluate "
+                                      "with --eval --replay afterwards")
+        if not args.get("device_dataset"):
+            raise ValueError("--replay_every replays validation episodes out of the device-resident store: it needs "
+                             "--device_dataset")
+        config.update(replay_every=int(args["replay_every"]), replay_episodes=args.get("replay_episodes"),
+                      replay_align=args.get("replay_align") or "train", replay_horizon=bool(args.get("replay_horizon")))
     return config
 
 
@@ -777,7 +899,7 @@ def main(args):
         # open-loop replay on recorded episodes: what a use_depth / use_pcd policy (no simulator renders its inputs) and a policy
         # trained on real-robot episodes can be evaluated with
         return replay_bc(config, "policy_last.ckpt", episodes=args.get("replay_episodes"),
-                         align=args.get("replay_align") or "train", save_episode=True)
+                         align=args.get("replay_align") or "train", save_episode=True, horizon=bool(args.get("replay_horizon")))
     if args["eval"]:
         results = []
         for ckpt_name in ["policy_last.ckpt"]:
@@ -887,6 +1009,13 @@ def make_parser():
     parser.add_argument("--replay_align", action="store", type=str, default="train", choices=["train", "none"],
                         help="--replay: compare step t with the action the dataset trains slot 0 on (train: action[t-1] for "
                              "real-robot episodes) or with action[t] (none)")
+    parser.add_argument("--replay_every", action="store", type=int, default=0,
+                        help="ACT training with --device_dataset: every N steps replay the validation episodes (at most "
+                             "--replay_episodes, aligned by --replay_align) open loop out of the device-resident store; the figures "
+                             "go to replay_history.json, the weights with the lowest mean MAE to policy_best_replay.ckpt (0: off)")
+    parser.add_argument("--replay_horizon", action="store_true",
+                        help="--replay_every and --eval --replay: also the error of slot j of a predicted chunk against the action j "
+                             "steps ahead (how the error grows along the chunk)")
     parser.add_argument("--augment_images", action="store_true",
                         help="ACT training only, opt-in: the reference dataset's augmentation (random 0.95 crop resized back, rotation "
                              "within 5 degrees, brightness / contrast / saturation jitter) on the device, for training batches; the "

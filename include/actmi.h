@@ -365,6 +365,19 @@ int actmi_op_ensemble_episode(const float* chunks, const int32_t* lengths, doubl
  * t < T_e with d = pred - (double)target.  Sums have a fixed shape: two runs give the same bits.  T_e = 0 gives zeros. */
 int actmi_op_action_error(const double* raw, const float* target, const int32_t* lengths, const double* mean, const double* std,
                           double* pred, double* stats, int E, int T, int A, void* stream);
+/* The error along the predicted chunk.  chunks [E][S][Q][A] f32 (normalised a_hat): row s of episode e is the chunk predicted
+ * from frame r = s * stride; actions [E][T][A] f32 (recorded actions in file units, NOT aligned); lengths [E] i32 or NULL = T;
+ * shift [E] i32 or NULL = 0, each 0 or 1 (1: a real-robot episode, whose slot 0 the dataset trains on action[t - 1]); mean / std
+ * [A] f64.  Slot j of row s is compared with actions[e][max(0, r - shift[e]) + j], the entry the dataset and
+ * actmi_op_gather_chunks train that slot on, while r < len and max(0, r - shift) + j < len (the entries whose is_pad is 0).
+ * d = |(double)chunk * std + mean - (double)action| (two roundings).  stats [E][Q][3][A] f64 = sum d, sum d^2, max d per
+ * (episode, slot, component); count [E][Q] i32 = the pairs of a slot; a slot without a pair gives zeros and 0.  Sums have a
+ * fixed shape: two runs give the same bits.  ACTMI_E_INVALID, before anything runs: E > 65535, Q > 65535 (grid extents), A < 1,
+ * Q < 1, stride < 1, T < 1, a negative E or S, or a null chunks / actions / mean / std / stats / count.  E == 0 or S == 0:
+ * ACTMI_OK without a launch, nothing is written. */
+int actmi_op_chunk_error(const float* chunks, const float* actions, const int32_t* lengths, const int32_t* shift,
+                         const double* mean, const double* std, int stride, double* stats, int32_t* count,
+                         int E, int S, int T, int Q, int A, void* stream);
 
 /* ---- kernel-level entry points (unit tests, external callers) --------------------------------------- */
 int actmi_op_gemm(const actmi_gemm_desc* d, void* stream);
