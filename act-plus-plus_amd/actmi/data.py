@@ -35,7 +35,14 @@ Differences, all on the host side of the step:
   training batch is then two device gathers (three with depth) that give the tensors of ``EpisodicDataset.__getitem__`` + the
   default collation bit for bit, with no host work, loader worker or PCIe traffic per step;
 * ``DeviceEpisodeReplay`` is ``EpisodeReplay`` out of such a store (``DeviceEpisodeStore.replay_batch``): one stored episode in
-  time order, the same tensors bit for bit, already on the device -- what ``--replay_every`` replays while training."""
+  time order, the same tensors bit for bit, already on the device -- what ``--replay_every`` replays while training;
+* ``load_data(..., mirror_twins=True)`` joins every episode file by its **mirrored twin** (``MirrorTwinPath``, ``MirrorSpec``): the
+  episode the reference's ``postprocess_episodes.py`` writes beside it -- arms swapped with a per-joint sign vector, the base's
+  turn rate negated, the wrist cameras swapped and flipped, the top camera flipped -- computed from the file as it is read
+  instead of stored.  Two deviations from the reference's files: the twin is the exact mirror image (the script re-encodes every
+  mirrored frame as JPEG at quality 50) and its rows are float32.  Depth cameras, which the reference does not mirror, follow
+  their RGB camera.  In a ``DeviceEpisodeStore`` a twin shares its source's frames: ``actmi_op_gather_frames_mirror`` flips them
+  inside the batch's gather."""
 import fnmatch
 import os
 
@@ -81,7 +88,233 @@ class _NpzEpisode:
         return False
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# mirrored twin episodes (``load_data(..., mirror_twins=True)``; DESIGN.md "Mirrored twin episodes")
+# ---------------------------------------------------------------------------------------------------------------------
+class MirrorSpec:
+    """What the mirror image of a two-arm episode is (the reference's postprocess_episodes.py:15-19, 67-86).
+
+    ``swap``: pairs of cameras that change places; ``flip``: the cameras whose frames are flipped along W (a swapped camera is
+    named by the place it ends up in; the reference flips both of a pair); every other camera passes through.  A state row
+    (qpos, qvel, action) becomes ``x[:, state_perm] * state_sign`` and a ``/base_action`` row ``x * base_sign``, as float32."""
+
+    STATE_MULTIPLY = (-1, 1, 1, -1, 1, -1, 1)                    # MIRROR_STATE_MULTIPLY, per arm
+    BASE_MULTIPLY = (1, -1)                                      # MIRROR_BASE_MULTIPLY: the base's turn rate changes sign
+
+    def __init__(self, swap=(), flip=(), state_perm=None, state_sign=None, base_sign=None):
+        self.swap = tuple((str(a), str(b)) for a, b in swap)
+        self.flip = frozenset(str(c) for c in flip)
+        self.state_perm = np.asarray(list(range(7, 14)) + list(range(7)) if state_perm is None else state_perm, dtype=np.int64)
+        self.state_sign = np.asarray(self.STATE_MULTIPLY * 2 if state_sign is None else state_sign, dtype=np.float32)
+        self.base_sign = np.asarray(self.BASE_MULTIPLY if base_sign is None else base_sign, dtype=np.float32)
+        if self.state_perm.shape != self.state_sign.shape or self.state_perm.ndim != 1 or \
+                sorted(self.state_perm.tolist()) != list(range(len(self.state_perm))):
+            raise ValueError("MirrorSpec: state_perm must be a permutation and state_sign as long as it")
+        names = [c for pair in self.swap for c in pair]
+        if len(set(names)) != len(names):
+            raise ValueError(f"MirrorSpec: a camera is named in more than one swap pair: {self.swap}")
+        self._source = {a: b for a, b in self.swap}
+        self._source.update({b: a for a, b in self.swap})
+
+    @classmethod
+    def from_camera_names(cls, camera_names):
+        """the reference's rule for the cameras an episode holds: the wrist pair is swapped and both are flipped, the top camera
+        is flipped, any other camera passes through; no wrist pair or no top camera: ValueError (the script raises there)"""
+        names = list(camera_names)
+        for pair in (("left_wrist", "right_wrist"), ("cam_left_wrist", "cam_right_wrist")):
+            if pair[0] in names:
+                if pair[1] not in names:
+                    raise ValueError(f"mirror twins: {pair[0]} without {pair[1]} among the cameras {names}")
+                break
+        else:
+            raise ValueError(f"mirror twins: no left_wrist or cam_left_wrist among the cameras {names}")
+        for top in ("top", "cam_high"):
+            if top in names:
+                break
+        else:
+            raise ValueError(f"mirror twins: no top or cam_high among the cameras {names}")
+        return cls(swap=(pair,), flip=pair + (top,))
+
+    def source_camera(self, cam):
+        """the camera of the source episode whose frames the twin shows as ``cam``"""
+        return self._source.get(cam, cam)
+
+    def flips(self, cam):
+        return cam in self.flip
+
+    def mirror_state(self, x, where=""):
+        x = np.asarray(x)
+        if x.ndim != 2 or x.shape[1] != len(self.state_perm):
+            raise ValueError(f"{where}: a mirror twin needs state rows {len(self.state_perm)} wide, got {x.shape}")
+        return np.ascontiguousarray(x[:, self.state_perm] * self.state_sign, dtype=np.float32)
+
+    def mirror_base(self, x, where=""):
+        x = np.asarray(x)
+        if x.ndim != 2 or x.shape[1] != len(self.base_sign):
+            raise ValueError(f"{where}: a mirror twin needs /base_action rows {len(self.base_sign)} wide, got {x.shape}")
+        return np.ascontiguousarray(x * self.base_sign, dtype=np.float32)
+
+
+class MirrorTwinPath(str):
+    """The handle of the mirrored twin of an episode file: a ``str`` whose value is the virtual path ``<dir>/mirror_<basename>``
+    (where postprocess_episodes.py writes the twin, so filters, sorting and printing treat it like that file) and which carries
+    ``.source`` (the file it is the image of), ``.spec`` (a ``MirrorSpec``, or None: the reference's rule for the cameras the file
+    holds) and ``.depth_follows`` (depth camera -> the RGB camera whose swap and flip it shares; None: the camera of its own
+    name).  ``open_episode`` gives a view of the source file; nothing is written."""
+
+    def __new__(cls, source, spec=None, depth_follows=None):
+        source = str(source)
+        self = super().__new__(cls, os.path.join(os.path.dirname(source), "mirror_" + os.path.basename(source)))
+        self.source, self.spec = source, spec
+        self.depth_follows = dict(depth_follows) if depth_follows else None
+        return self
+
+    def __reduce__(self):                                        # loader workers receive the dataset pickled
+        return (MirrorTwinPath, (self.source, self.spec, self.depth_follows))
+
+
+class _MirrorFrames:
+    """the frames of one camera of a twin: the source entry, read where it is indexed, decoded where the source is compressed,
+    flipped along W where the spec says so"""
+
+    def __init__(self, entry, flip, compressed, meta=None):
+        self._entry, self._flip, self._compressed, self._meta = entry, bool(flip), bool(compressed), meta
+
+    def _frames(self, raw):
+        raw = np.asarray(raw)
+        if self._compressed:                                      # utils.py:104-107: one zero-padded JPEG per frame
+            raw = imdecode_bgr(raw) if raw.ndim == 1 else np.stack([imdecode_bgr(buf) for buf in raw])
+            fdim = 3
+        else:
+            fdim = len(self._entry.shape) - 1
+        if self._flip:
+            raw = np.flip(raw, axis=raw.ndim - fdim + 1)          # axis 1 of a frame [H, W(, C)]
+        return np.ascontiguousarray(raw)
+
+    def __getitem__(self, sel):
+        return self._frames(self._entry[sel])
+
+    def __array__(self, dtype=None, copy=None):
+        a = self[()]
+        return a if dtype is None else a.astype(dtype)
+
+    def __len__(self):
+        return int(self._entry.shape[0])
+
+    @property
+    def shape(self):
+        if self._compressed:
+            return (len(self),) + tuple(imdecode_bgr(np.asarray(self._entry[0])).shape)
+        return tuple(int(v) for v in self._entry.shape)
+
+    @property
+    def dtype(self):
+        return np.dtype(np.uint8) if self._compressed else np.dtype(self._entry.dtype)
+
+
+class _MirrorEpisode:
+    """read-only view of the mirrored twin of an episode file: the entries postprocess_episodes.py writes (qpos, qvel, action,
+    ``/base_action`` when the source has it, the cameras) computed from the source as they are read, as an UNCOMPRESSED episode
+    with float32 rows; depth cameras follow their RGB camera.  ``attrs``: the source's without ``compress``."""
+
+    STATE_KEYS = ("/observations/qpos", "/observations/qvel", "/action")
+    IMG, DEPTH = "/observations/images/", "/observations/depth_images/"
+
+    def __init__(self, twin):
+        self.path, self.source = twin, twin.source
+        self._root = open_episode(twin.source)
+        try:
+            self._compressed = bool(self._root.attrs.get("compress", False))
+            self.attrs = {k: v for k, v in dict(self._root.attrs).items() if k != "compress"}
+            self.cameras = self._names(self.IMG)
+            self.spec = twin.spec if twin.spec is not None else MirrorSpec.from_camera_names(self.cameras)
+            self.depth_follows = twin.depth_follows or {}
+            back = {}
+            for d in self._names(self.DEPTH):
+                rgb = self.depth_follows.get(d, d)
+                if rgb in back:
+                    raise ValueError(f"{twin}: depth cameras {back[rgb]} and {d} both follow {rgb}")
+                back[rgb] = d
+            self._depth_of = back                                 # RGB camera -> the depth camera that follows it
+        except Exception:
+            self._root.__exit__(None, None, None)
+            raise
+
+    def _names(self, prefix):
+        root = self._root
+        if isinstance(root, _NpzEpisode):
+            return [k[len(prefix):] for k in root._z.files if k.startswith(prefix)]
+        return list(root[prefix].keys()) if prefix in root else []
+
+    def _resolve(self, key):
+        """-> (kind, source key, flip) of an entry the twin holds, None of one it does not"""
+        if key in self.STATE_KEYS:
+            return ("state", key, False) if key in self._root else None
+        if key == "/base_action":
+            return ("base", key, False) if key in self._root else None
+        if key.startswith(self.IMG):
+            cam = key[len(self.IMG):]
+            src = self.IMG + self.spec.source_camera(cam)
+            return ("frames", src, self.spec.flips(cam)) if key in self._root and src in self._root else None
+        if key.startswith(self.DEPTH):
+            cam = key[len(self.DEPTH):]
+            rgb = self.depth_follows.get(cam, cam)
+            src_rgb = self.spec.source_camera(rgb)
+            src = self._depth_of.get(src_rgb) if src_rgb != rgb else cam
+            if src is None:
+                raise ValueError(f"{self.path}: depth camera {cam} follows {rgb}, whose mirror image is {src_rgb}: no depth camera "
+                                 f"follows that one")
+            return ("frames", self.DEPTH + src, self.spec.flips(rgb)) if key in self._root and self.DEPTH + src in self._root else None
+        return None
+
+    def __contains__(self, key):
+        return self._resolve(key) is not None
+
+    def keys(self):
+        names = [k for k in self.STATE_KEYS + ("/base_action",) if k in self]
+        return names + [self.IMG + c for c in self.cameras] + [self.DEPTH + d for d in self._names(self.DEPTH)]
+
+    def __getitem__(self, key):
+        r = self._resolve(key)
+        if r is None:
+            raise KeyError(f"{self.path}: a mirror twin holds no {key}")
+        kind, src, flip = r
+        if kind == "state":
+            return self.spec.mirror_state(self._root[src][()], f"{self.path}: {key}")
+        if kind == "base":
+            return self.spec.mirror_base(self._root[src][()], f"{self.path}: {key}")
+        return _MirrorFrames(self._root[src], flip, self._compressed)
+
+    def meta(self, key):
+        """(shape, dtype) of an entry from the source's headers (a compressed source: its first frame is decoded)"""
+        r = self._resolve(key)
+        if r is None:
+            raise KeyError(f"{self.path}: a mirror twin holds no {key}")
+        kind, src, _flip = r
+        shape, dtype = _entry_meta(self._root, src)
+        if kind != "frames":
+            return shape, np.dtype(np.float32)
+        if self._compressed:
+            return (shape[0],) + tuple(imdecode_bgr(np.asarray(self._root[src][0])).shape), np.dtype(np.uint8)
+        return shape, dtype
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self._root.__exit__(*a)
+        return False
+
+
+def mirror_twin_paths(files, spec=None, depth_follows=None):
+    """`files` and the twin of every one of them, sorted by path as ``find_all_hdf5`` sorts: the list a directory gives in which
+    postprocess_episodes.py has written ``mirror_<name>`` beside every ``<name>``"""
+    return sorted(list(files) + [MirrorTwinPath(f, spec, depth_follows) for f in files])
+
+
 def open_episode(path):
+    if isinstance(path, MirrorTwinPath):
+        return _MirrorEpisode(path)
     if path.endswith(".npz"):
         return _NpzEpisode(path)
     try:
@@ -114,7 +347,7 @@ def _read_action(root):
     return root["/action"][()]
 
 
-def find_all_hdf5(dataset_dir, skip_mirrored_data):
+def _list_hdf5(dataset_dir, skip_mirrored_data):
     files = []
     for root, _dirs, names in os.walk(dataset_dir):
         for pat in ("*.hdf5", "*.npz"):
@@ -125,8 +358,28 @@ def find_all_hdf5(dataset_dir, skip_mirrored_data):
                     continue
                 files.append(os.path.join(root, filename))
     files.sort()                                                 # os.walk order is file-system dependent
+    return files
+
+
+def find_all_hdf5(dataset_dir, skip_mirrored_data):
+    files = _list_hdf5(dataset_dir, skip_mirrored_data)
     print(f"Found {len(files)} hdf5 files")
     return files
+
+
+def find_all_hdf5_with_twins(dataset_dir, skip_mirrored_data, spec=None, depth_follows=None):
+    """``find_all_hdf5`` for ``mirror_twins``: the directory's own files (mirrored ones skipped) and the twin of every one of them,
+    sorted by path -- the list ``find_all_hdf5(dataset_dir, False)`` gives once postprocess_episodes.py has run there.  Mirrored
+    files that are listed (present, and not skipped) are refused: twins of twins and duplicates are never wanted."""
+    files = _list_hdf5(dataset_dir, True)
+    print(f"Found {len(files)} hdf5 files, each joined by its mirrored twin")
+    if not skip_mirrored_data:
+        own = set(files)
+        listed = [f for f in _list_hdf5(dataset_dir, False) if f not in own]
+        if listed:
+            raise ValueError(f"mirror_twins: {dataset_dir} already holds {len(listed)} mirrored episode files ({listed[0]}, ...): pass "
+                             f"skip_mirrored_data (--skip_mirrored_data) to serve their twins from the originals instead")
+    return mirror_twin_paths(files, spec, depth_follows)
 
 
 def get_norm_stats(dataset_path_list):
@@ -210,6 +463,8 @@ class EpisodicDataset(torch.utils.data.Dataset):
                                  f"{self.pointcloud_names}")
             if self.use_depth:
                 raise NotImplementedError("use_depth together with use_pcd is not supported")
+            if any(isinstance(p, MirrorTwinPath) for p in dataset_path_list):
+                raise ValueError("use_pcd with mirror twins: a stored point cloud has no mirror rule")
         if policy_class == "Diffusion":
             raise NotImplementedError("the Diffusion augmentations (torchvision transforms) are outside this path")
         self._stats_t = {k: torch.as_tensor(np.asarray(norm_stats[k]), dtype=torch.float32)
@@ -400,13 +655,19 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
               skip_mirrored_data=False, load_pretrain=False, policy_class=None, stats_dir_l=None, sample_weights=None,
               train_ratio=0.99, num_workers=2, f32_images=False, rng=None, depth_camera_names=None, use_depth=False,
               f32_depth=False, pointcloud_names=None, use_pcd=False, max_points=None, pcd_ignore_mask=False,
-              device_dataset=False, device=None, device_budget_bytes=None):
+              device_dataset=False, device=None, device_budget_bytes=None, mirror_twins=False, mirror_spec=None):
     """utils.py:249-301.  Returns (train_dataloader, val_dataloader, norm_stats, is_sim).  ``use_depth``: the batches are
     5-tuples that end in the depth frames of ``depth_camera_names`` (EpisodicDataset).  ``use_pcd``: 7-tuples that end in the
     padded clouds and their valid counts (collate_pcd).  ``device_dataset``: both loaders come from ONE ``DeviceEpisodeStore``
     on ``device`` (default: the current cuda device) that holds the train and validation episodes; the split, the norm stats
     and the samplers are built as without the flag, so the same ``rng`` gives the same episodes and the same draws, and the
-    batches are the same tensors, already on the device (``loader.on_device``)."""
+    batches are the same tensors, already on the device (``loader.on_device``).  ``mirror_twins``: every episode file is joined by
+    its mirrored twin (``MirrorTwinPath``; ``mirror_spec`` None: the reference's rule for the cameras each file holds), computed
+    from the file as it is read -- the results are those of the same call without the flag on a directory in which the twin files
+    exist (uncompressed, float32 rows): the same episode ids, stats, draws and batches.  With ``device_dataset`` the twins take no
+    frame memory."""
+    if mirror_twins and use_pcd:
+        raise ValueError("mirror_twins with use_pcd: a stored point cloud has no mirror rule")
     if device_dataset:                                            # refused before any file is read
         if use_pcd:
             raise NotImplementedError("--device_dataset with use_pcd: point clouds through the device-resident store are not "
@@ -419,7 +680,16 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
     rng = rng or np.random
     if isinstance(dataset_dir_l, str):
         dataset_dir_l = [dataset_dir_l]
-    dataset_path_list_list = [find_all_hdf5(d, skip_mirrored_data) for d in dataset_dir_l]
+    if mirror_twins:
+        # depth camera i shares the swap and the flip of RGB camera i (the config demands one depth camera per RGB camera)
+        follows = dict(zip(depth_camera_names or [], camera_names)) if use_depth else None
+
+        def list_files(d):
+            return find_all_hdf5_with_twins(d, skip_mirrored_data, mirror_spec, follows)
+    else:
+        def list_files(d):
+            return find_all_hdf5(d, skip_mirrored_data)
+    dataset_path_list_list = [list_files(d) for d in dataset_dir_l]
     num_episodes_0 = len(dataset_path_list_list[0])
     dataset_path_list = [n for n in flatten_list(dataset_path_list_list) if name_filter(n)]
     num_episodes_l = [len(l) for l in dataset_path_list_list]
@@ -443,7 +713,7 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
         stats_dir_l = dataset_dir_l
     elif isinstance(stats_dir_l, str):
         stats_dir_l = [stats_dir_l]
-    norm_stats, _ = get_norm_stats(flatten_list([find_all_hdf5(d, skip_mirrored_data) for d in stats_dir_l]))
+    norm_stats, _ = get_norm_stats(flatten_list([list_files(d) for d in stats_dir_l]))
     print(f"Norm stats from: {stats_dir_l}")
     pcd_kw = dict(pointcloud_names=pointcloud_names, use_pcd=use_pcd, max_points=max_points, pcd_ignore_mask=pcd_ignore_mask)
     train_dataset = EpisodicDataset(dataset_path_list, camera_names, norm_stats, train_episode_ids, train_episode_len,
@@ -579,6 +849,13 @@ class DeviceEpisodeStore:
     ``DEVICE_STORE_RESERVE_BYTES``.  The sizes come from the entries' headers (the first episode's frame shape for a compressed
     dataset) and every block is checked against them again as it is loaded.
 
+    Mirrored twins (``MirrorTwinPath`` entries of ``dataset_path_list``) add no frame bytes: ``sources`` are the files whose frames
+    the arena holds, each once (a twin's source is loaded for its sake alone when it is not listed itself), a twin's camera blocks
+    are its source's, permuted by its spec (``block_off``), with a flag per camera that is flipped (``flip`` / ``depth_flip``), and
+    ``nbytes`` counts every source once.  A twin has its own rows in ``actions`` / ``qpos`` (the mirrored ones) and its own episode
+    record.  A store that holds a twin gathers frames and depth with ``ops.gather_frames_mirror``; one without launches what it
+    always did.  A twin whose source camera is not among ``camera_names`` is refused (``ValueError``).
+
     Every rank of a data-parallel run holds its own full store."""
 
     RING = 4                 # pinned index blocks in flight: a block is rewritten only after its copy has executed
@@ -602,6 +879,14 @@ class DeviceEpisodeStore:
             raise ValueError("DeviceEpisodeStore: no episodes")
         self.paths = [dataset_path_list[i] for i in self.episode_ids]
         self._local_of = {e: i for i, e in enumerate(self.episode_ids)}
+        # the files whose frames the arena holds, each once: an episode file is its own source, a mirrored twin's is the file it is
+        # the image of (loaded for the twin's sake alone when it is not listed itself)
+        self.twin = [isinstance(p, MirrorTwinPath) for p in self.paths]
+        self.has_twins = any(self.twin)
+        srcs = [p.source if tw else str(p) for p, tw in zip(self.paths, self.twin)]
+        self.sources = list(dict.fromkeys(srcs))
+        where = {s: j for j, s in enumerate(self.sources)}
+        self._src_of = np.asarray([where[s] for s in srcs], dtype=np.int64)
         self.device = device
         self.stage_bytes = int(stage_bytes)
         self._plan()
@@ -618,22 +903,22 @@ class DeviceEpisodeStore:
     # ---- sizes, from the headers ---------------------------------------------------------------------------------
     def _plan(self):
         K, Kd = len(self.camera_names), len(self.depth_camera_names) if self.use_depth else 0
-        self.T = np.zeros(len(self.paths), dtype=np.int64)
+        src_T = np.zeros(len(self.sources), dtype=np.int64)
         self.frame_shape = self.depth_shape = None
-        self.compressed = []
-        for i, path in enumerate(self.paths):
+        src_compressed = []
+        for i, path in enumerate(self.sources):
             with open_episode(path) as root:
                 compressed = bool(root.attrs.get("compress", False))
-                self.compressed.append(compressed)
-                self.T[i] = _entry_meta(root, "/action")[0][0]
-                if self.T[i] < 1:
+                src_compressed.append(compressed)
+                src_T[i] = _entry_meta(root, "/action")[0][0]
+                if src_T[i] < 1:
                     raise ValueError(f"{path}: empty episode")
                 for kind, cams, want in (("images", self.camera_names, 4), ("depth_images", self.depth_camera_names[:Kd], None)):
                     for cam in cams:
                         key = f"/observations/{kind}/{cam}"
                         shape, dtype = _entry_meta(root, key)
-                        if shape[0] != self.T[i]:
-                            raise ValueError(f"{path}: {key} holds {shape[0]} frames for an episode of {int(self.T[i])} steps")
+                        if shape[0] != src_T[i]:
+                            raise ValueError(f"{path}: {key} holds {shape[0]} frames for an episode of {int(src_T[i])} steps")
                         if compressed:
                             if i > 0:
                                 continue                           # sized by the first episode's frames; checked as it is decoded
@@ -662,11 +947,34 @@ class DeviceEpisodeStore:
         self.frame_bytes = int(np.prod(self.frame_shape))
         self.depth_bytes = int(np.prod(self.depth_shape)) * 2 if Kd else 0
         blocks = []
-        for T in self.T:
+        for T in src_T:
             blocks += [int(T) * self.frame_bytes] * K + [int(T) * self.depth_bytes] * Kd
-        offs, self.nbytes = arena_layout(blocks)
-        offs = offs.reshape(len(self.paths), K + Kd)
-        self.block_off, self.depth_block_off = offs[:, :K].copy(), offs[:, K:].copy()
+        offs, self.nbytes = arena_layout(blocks)                       # every source once: a twin adds no frame bytes
+        offs = offs.reshape(len(self.sources), K + Kd)
+        self._src_block_off, self._src_depth_block_off, self._src_T = offs[:, :K].copy(), offs[:, K:].copy(), src_T
+        self._src_compressed = src_compressed
+        # per episode: its source's length and blocks; a twin's cameras are its source's, permuted and flagged by its spec
+        self.T = src_T[self._src_of]
+        self.compressed = [src_compressed[j] for j in self._src_of]
+        self.block_off, self.depth_block_off = self._src_block_off[self._src_of], self._src_depth_block_off[self._src_of]
+        self.flip, self.depth_flip = np.zeros(self.block_off.shape, dtype=np.uint8), np.zeros(self.depth_block_off.shape, dtype=np.uint8)
+        for i, path in enumerate(self.paths):
+            if not self.twin[i]:
+                continue
+            j = self._src_of[i]
+            with open_episode(path) as view:
+                for kind, cams, off, src_off, flip in (
+                        ("images", self.camera_names, self.block_off, self._src_block_off, self.flip),
+                        ("depth_images", self.depth_camera_names[:Kd], self.depth_block_off, self._src_depth_block_off, self.depth_flip)):
+                    for k, cam in enumerate(cams):
+                        found = view._resolve(f"/observations/{kind}/{cam}")
+                        if found is None:
+                            raise ValueError(f"{path}: the mirror twin holds no /observations/{kind}/{cam}")
+                        src_cam = found[1].rsplit("/", 1)[1]
+                        if src_cam not in cams:
+                            raise ValueError(f"{path}: /observations/{kind}/{cam} of the twin is the source's {src_cam}, which is not "
+                                             f"among the store's cameras {list(cams)}")
+                        off[i, k], flip[i, k] = src_off[j, list(cams).index(src_cam)], 1 if found[2] else 0
         # the statement the gather's launcher cannot check for itself (actmi_op_gather_frames, `aligned`)
         self.aligned = 1 if self.frame_bytes % 16 == 0 else 0
         self.depth_aligned = 1 if Kd and self.depth_bytes % 16 == 0 else 0
@@ -683,10 +991,11 @@ class DeviceEpisodeStore:
         self._pin = [torch.empty(stage, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         self._pin_ev, self._pin_i = [None, None], 0
         actions, qposes, sims = [], [], []
+        loaded = set()
         for i, path in enumerate(self.paths):
             T = int(self.T[i])
             with open_episode(path) as raw:
-                root = _EpisodeArrays(raw)
+                root = _EpisodeArrays(raw)                            # a twin: the view, whose rows are the mirrored ones
                 attrs = root.attrs
                 sims.append(bool(attrs["sim"]) if "sim" in attrs else False)
                 action = np.asarray(_read_action(root))
@@ -695,12 +1004,13 @@ class DeviceEpisodeStore:
                     raise ValueError(f"{path}: action {action.shape} / qpos {qpos.shape} for an episode of {T} steps")
                 actions.append(action.astype(np.float32))            # padded_action is float32: the assignment converts
                 qposes.append(torch.from_numpy(qpos).float().numpy())
-                for k, cam in enumerate(self.camera_names):
-                    self._load_block(root[f"/observations/images/{cam}"], T, self.compressed[i], int(self.block_off[i, k]), False,
-                                     f"{path}: /observations/images/{cam}")
-                for k, cam in enumerate(self.depth_camera_names[:self.Kd]):
-                    self._load_block(root[f"/observations/depth_images/{cam}"], T, self.compressed[i],
-                                     int(self.depth_block_off[i, k]), True, f"{path}: /observations/depth_images/{cam}")
+                if not self.twin[i]:
+                    self._load_source(root, int(self._src_of[i]))
+                    loaded.add(int(self._src_of[i]))
+        for j in range(len(self.sources)):                            # the sources only twins name
+            if j not in loaded:
+                with open_episode(self.sources[j]) as raw:
+                    self._load_source(_EpisodeArrays(raw), j)
         A, S = actions[0].shape[1], qposes[0].shape[1]
         if any(a.shape[1] != A for a in actions) or any(q.shape[1] != S for q in qposes):
             raise ValueError("DeviceEpisodeStore: episodes differ in their action or qpos width")
@@ -721,6 +1031,16 @@ class DeviceEpisodeStore:
         self._pin = self._pin_ev = None                               # the staging buffers are the load's alone
         self.load_seconds = time.perf_counter() - t_begin
         self._host, self._host_ev, self._slot = [None] * self.RING, [None] * self.RING, 0
+
+    def _load_source(self, root, j):
+        """the frames of source file j, open as `root`, into its blocks of the arena"""
+        path, T = self.sources[j], int(self._src_T[j])
+        for k, cam in enumerate(self.camera_names):
+            self._load_block(root[f"/observations/images/{cam}"], T, self._src_compressed[j], int(self._src_block_off[j, k]), False,
+                             f"{path}: /observations/images/{cam}")
+        for k, cam in enumerate(self.depth_camera_names[:self.Kd]):
+            self._load_block(root[f"/observations/depth_images/{cam}"], T, self._src_compressed[j],
+                             int(self._src_depth_block_off[j, k]), True, f"{path}: /observations/depth_images/{cam}")
 
     def _stage(self, dst_off, nbytes, fill):
         """one piece through the staging pair: ``fill(view)`` writes `nbytes` bytes into the pinned view, which is then copied to
@@ -800,6 +1120,8 @@ class DeviceEpisodeStore:
             raise IndexError("DeviceEpisodeStore.gather: a sample outside the stored episodes")
         off, doff = self.frame_offsets(e, t)
         samples = np.ascontiguousarray(np.stack([e, t], axis=1).astype(np.int32)).view(np.int64).reshape(-1)
+        if self.has_twins:
+            return self._gather_mirror(e, off, doff, samples, B, Q, nontemporal)
         nk, nd = B * self.K, B * self.Kd
         dev = self.arena.device
         with torch.cuda.device(dev):
@@ -814,6 +1136,35 @@ class DeviceEpisodeStore:
             depth = torch.empty((B, self.Kd, 1) + tuple(self.depth_shape), dtype=torch.uint16, device=dev)
             ops.gather_frames(self.arena, tab[nk:nk + nd], self.depth_bytes, out=depth,
                               aligned=2 if (nontemporal and self.depth_aligned) else self.depth_aligned)
+        return image, qpos, action, is_pad, depth
+
+    def _gather_mirror(self, e, off, doff, samples, B, Q, nontemporal):
+        """``gather`` of a store that holds mirrored twins: the frames (and the depth) come from ``gather_frames_mirror``, whose
+        flip flags -- one per item, the twin's cameras that are flipped -- travel in the same index upload, packed eight to a word
+        behind the offsets"""
+        from . import ops
+        nk, nd = B * self.K, B * self.Kd
+        dev = self.arena.device
+        flags = np.concatenate([self.flip[e].reshape(-1), self.depth_flip[e].reshape(-1)])
+        words = np.zeros((len(flags) + 7) // 8 * 8, dtype=np.uint8)
+        words[:len(flags)] = flags
+        H, W = self.frame_shape[:2]
+        # the aligned form's statement: frames at multiples of 16 (the arena's layout) and rows of whole 16- / 8-pixel groups
+        aligned = self.aligned if W % 16 == 0 else 0
+        with torch.cuda.device(dev):
+            tab = self._upload(np.concatenate([off.reshape(-1), doff.reshape(-1), samples, words.view(np.int64)]))
+            fl = tab[nk + nd + B:].view(torch.uint8)
+            image = torch.empty((B, self.K) + tuple(self.frame_shape), dtype=torch.uint8, device=dev)
+            ops.gather_frames_mirror(self.arena, tab[:nk], fl[:nk], H, W, 3, out=image, aligned=2 if (nontemporal and aligned) else aligned)
+            qpos, action, is_pad = ops.gather_chunks(self.actions, self.qpos, self.episodes, tab[nk + nd:nk + nd + B].view(torch.int32).view(B, 2),
+                                                     *self._stats, Q)
+            if not self.Kd:
+                return image, qpos, action, is_pad
+            Hd, Wd = self.depth_shape
+            aligned = self.depth_aligned if Wd % 8 == 0 else 0
+            depth = torch.empty((B, self.Kd, 1) + tuple(self.depth_shape), dtype=torch.uint16, device=dev)
+            ops.gather_frames_mirror(self.arena, tab[nk:nk + nd], fl[nk:nk + nd], Hd, Wd, 2, out=depth,
+                                     aligned=2 if (nontemporal and aligned) else aligned)
         return image, qpos, action, is_pad, depth
 
     def replay_batch(self, local_episode, steps):

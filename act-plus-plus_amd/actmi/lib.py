@@ -138,6 +138,12 @@ class GatherChunksDesc(C.Structure):
                [("n_rows", C.c_int64)] + [(k, C.c_int32) for k in ("n_episodes", "B", "A", "S", "Q")]
 
 
+class GatherMirrorDesc(C.Structure):
+    # actmi_gather_mirror_desc
+    _fields_ = [("arena", C.c_void_p), ("arena_bytes", C.c_int64), ("src_off", C.c_void_p), ("flip", C.c_void_p), ("out", C.c_void_p),
+                ("n_items", C.c_int64)] + [(k, C.c_int32) for k in ("H", "W", "px_bytes", "aligned")]
+
+
 _lib = None
 
 
@@ -241,6 +247,7 @@ def load():
         "actmi_op_augment_u8": ([C.POINTER(AugmentDesc), vp], i32),
         "actmi_op_warp_u16": ([C.POINTER(AugmentDesc), vp], i32),
         "actmi_op_gather_frames": ([vp, i64, vp, vp, i64, i64, i32, vp], i32),
+        "actmi_op_gather_frames_mirror": ([C.POINTER(GatherMirrorDesc), vp], i32),
         "actmi_op_gather_chunks": ([C.POINTER(GatherChunksDesc), vp], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),

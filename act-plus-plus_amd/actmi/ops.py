@@ -1663,6 +1663,44 @@ def gather_frames_ref(arena, src_off, item_bytes):
     return out
 
 
+def gather_frames_mirror(arena, src_off, flip, H, W, px_bytes, out=None, aligned=0):
+    """actmi_op_gather_frames_mirror: ``gather_frames`` for items that are frames of H rows of W pixels of px_bytes bytes (3: u8
+    BGR, 2: raw uint16 depth), item i mirrored along W where flip[i] != 0 and copied where it is 0.  arena 1-D uint8 cuda, src_off
+    [n] int64 and flip [n] uint8 on its device -> out [n, H, W, px_bytes] uint8 (or the caller's contiguous cuda tensor of that
+    many bytes, any dtype and shape).  aligned: as for ``gather_frames``; 1 and 2 also state that W is a multiple of 16 (px 3) or
+    8 (px 2)."""
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_cuda or not arena.is_contiguous():
+        raise ValueError(f"gather_frames_mirror: arena must be a contiguous 1-D uint8 cuda tensor, got {arena.dtype} {tuple(arena.shape)}")
+    if src_off.dtype != torch.int64 or src_off.dim() != 1 or src_off.device != arena.device or not src_off.is_contiguous():
+        raise ValueError("gather_frames_mirror: src_off must be a contiguous 1-D int64 tensor on the arena's device")
+    n, H, W, px = int(src_off.numel()), int(H), int(W), int(px_bytes)
+    if flip.dtype != torch.uint8 or flip.dim() != 1 or flip.device != arena.device or not flip.is_contiguous() or flip.numel() != n:
+        raise ValueError(f"gather_frames_mirror: flip must be a contiguous 1-D uint8 tensor of {n} flags on the arena's device")
+    if out is None:
+        out = torch.empty((n, H, W, px), dtype=torch.uint8, device=arena.device)
+    elif out.device != arena.device or not out.is_contiguous() or out.numel() * out.element_size() != n * H * W * px:
+        raise ValueError(f"gather_frames_mirror: out must be contiguous on {arena.device} and hold {n} x {H} x {W} x {px} bytes")
+    d = L.GatherMirrorDesc()
+    d.arena, d.arena_bytes, d.src_off, d.flip, d.out = arena.data_ptr(), int(arena.numel()), src_off.data_ptr(), flip.data_ptr(), out.data_ptr()
+    d.n_items, d.H, d.W, d.px_bytes, d.aligned = n, H, W, px, int(aligned)
+    with torch.cuda.device(arena.device):
+        L.check(L.load().actmi_op_gather_frames_mirror(C.byref(d), L.current_stream_ptr()), None, "op_gather_frames_mirror")
+    return out
+
+
+def gather_frames_mirror_ref(arena, src_off, flip, H, W, px_bytes):
+    """numpy statement of ``gather_frames_mirror``; needs no library.  -> [n, H, W, px_bytes] uint8: item i is the frame at
+    arena[src_off[i]:], its pixels in reverse order along W where flip[i] != 0; an item whose range leaves the arena is zeros."""
+    import numpy as np
+    H, W, px = int(H), int(W), int(px_bytes)
+    out = gather_frames_ref(arena, src_off, H * W * px).reshape(-1, H, W, px)
+    fl = np.asarray(flip).reshape(-1) != 0
+    if len(fl) != len(out):
+        raise ValueError(f"gather_frames_mirror_ref: {len(fl)} flags for {len(out)} items")
+    out[fl] = out[fl][:, :, ::-1]
+    return out
+
+
 def gather_chunks(actions, qpos, episodes, samples, action_mean, action_std, qpos_mean, qpos_std, Q):
     """actmi_op_gather_chunks.  actions [R, A] / qpos [R, S] f32 cuda (all episodes' rows back to back), episodes: uint8 cuda
     tensor holding [E] records (episode_rec_dtype), samples [B, 2] int32 cuda (episode, t), the four stat vectors f32 cuda ->

@@ -475,6 +475,13 @@ int actmi_op_gather_frames(const void* arena, int64_t arena_bytes, const int64_t
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
 }
 
+int actmi_op_gather_frames_mirror(const actmi_gather_mirror_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "gather_frames_mirror: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_gather_frames_mirror(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_gather_chunks(const actmi_gather_chunks_desc* d, void* stream) {
     g_op_error.clear();
     if (!d) { g_op_error = "gather_chunks: null descriptor"; return ACTMI_E_INVALID; }

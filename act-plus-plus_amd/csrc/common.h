@@ -244,6 +244,7 @@ int launch_warp_u16(const actmi_augment_desc& a, hipStream_t st, std::string* er
 // ---- device-resident episode store (episode_store.hip; contract at actmi_op_gather_frames / actmi_op_gather_chunks in actmi.h) ----
 int launch_gather_frames(const void* arena, int64_t arena_bytes, const int64_t* src_off, void* out, int64_t n_items,
                          int64_t item_bytes, int aligned, hipStream_t st, std::string* err);
+int launch_gather_frames_mirror(const actmi_gather_mirror_desc& d, hipStream_t st, std::string* err);
 int launch_gather_chunks(const actmi_gather_chunks_desc& d, hipStream_t st, std::string* err);
 
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------

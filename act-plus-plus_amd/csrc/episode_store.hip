@@ -1,5 +1,5 @@
-// Device-resident episode store: a training batch gathered on the device (actmi_op_gather_frames, actmi_op_gather_chunks; the
-// contract is at their declarations in actmi.h).  The frames of every episode sit in one u8 arena; a batch is n_items contiguous
+// Device-resident episode store: a training batch gathered on the device (actmi_op_gather_frames, actmi_op_gather_frames_mirror,
+// actmi_op_gather_chunks; the contract is at their declarations in actmi.h).  The frames of every episode sit in one u8 arena; a batch is n_items contiguous
 // pieces of it copied to a contiguous output, plus the z-scored qpos rows and action chunks EpisodicDataset.__getitem__ computes.
 #include "common.h"
 
@@ -22,6 +22,20 @@ __device__ __forceinline__ void gf_share(int64_t n, int64_t quantum, int s, int 
     const int64_t a = per * s, b = a + per;
     *lo = a < n ? a : n;
     *hi = b < n ? b : n;
+}
+
+// the 16-byte words [v0, v1) of one item, four loads in flight per lane
+template <bool NT>
+__device__ __forceinline__ void gf_copy_v16(const u32x4* __restrict__ s, u32x4* __restrict__ d, int64_t v0, int64_t v1) {
+    int64_t v = v0 + threadIdx.x;
+    for (; v + (GF_UNROLL - 1) * GF_BLOCK < v1; v += GF_STEP) {
+        u32x4 r[GF_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GF_UNROLL; ++u) r[u] = NT ? __builtin_nontemporal_load(s + v + u * GF_BLOCK) : s[v + u * GF_BLOCK];
+#pragma unroll
+        for (int u = 0; u < GF_UNROLL; ++u) d[v + u * GF_BLOCK] = r[u];
+    }
+    for (; v < v1; v += GF_BLOCK) d[v] = NT ? __builtin_nontemporal_load(s + v) : s[v];
 }
 
 // grid (splits, items).  An item whose source range leaves the arena is zero-filled, never read.  Fast form: item_bytes % 16 == 0 and
@@ -48,17 +62,7 @@ __global__ __launch_bounds__(GF_BLOCK) void gather_frames_v16_kernel(const uint8
         gf_copy_bytes(src, dst, v0 << 4, v1 << 4);
         return;
     }
-    const u32x4* s = reinterpret_cast<const u32x4*>(src);
-    u32x4* d = reinterpret_cast<u32x4*>(dst);
-    int64_t v = v0 + threadIdx.x;
-    for (; v + (GF_UNROLL - 1) * GF_BLOCK < v1; v += GF_STEP) {
-        u32x4 r[GF_UNROLL];
-#pragma unroll
-        for (int u = 0; u < GF_UNROLL; ++u) r[u] = NT ? __builtin_nontemporal_load(s + v + u * GF_BLOCK) : s[v + u * GF_BLOCK];
-#pragma unroll
-        for (int u = 0; u < GF_UNROLL; ++u) d[v + u * GF_BLOCK] = r[u];
-    }
-    for (; v < v1; v += GF_BLOCK) d[v] = NT ? __builtin_nontemporal_load(s + v) : s[v];
+    gf_copy_v16<NT>(reinterpret_cast<const u32x4*>(src), reinterpret_cast<u32x4*>(dst), v0, v1);
 }
 
 __global__ __launch_bounds__(GF_BLOCK) void gather_frames_bytes_kernel(const uint8_t* __restrict__ arena, int64_t arena_bytes,
@@ -74,6 +78,128 @@ __global__ __launch_bounds__(GF_BLOCK) void gather_frames_bytes_kernel(const uin
         return;
     }
     gf_copy_bytes(arena + off, dst, b0, b1);
+}
+
+// ---- mirrored gather (actmi_op_gather_frames_mirror): item i is H rows of W pixels of PX bytes; with flip[i] the pixels of every
+// row come out in reverse order (rows in order, the bytes of a pixel in order), without it the item is copied.
+
+// 4 pixels of 3 bytes in the words a, b, c (bytes 0..11) -> the same pixels in reverse order: bytes 9 10 11 6 | 7 8 3 4 | 5 0 1 2
+__host__ __device__ __forceinline__ void gm_rev4px3(uint32_t a, uint32_t b, uint32_t c, uint32_t* o) {
+    o[0] = (c >> 8) | ((b << 8) & 0xff000000u);
+    o[1] = (b >> 24) | ((c & 0xffu) << 8) | ((a >> 8) & 0x00ff0000u) | (b << 24);
+    o[2] = ((b >> 8) & 0xffu) | (a << 8);
+}
+
+// one group in registers: 16 pixels of 3 bytes (three 16-byte words) or 8 pixels of 2 bytes (one), pixel order reversed
+template <int PX>
+__host__ __device__ __forceinline__ void gm_reverse_group(u32x4* v) {
+    if (PX == 3) {
+        uint32_t w[12], o[12];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { w[4 * j] = v[j].x; w[4 * j + 1] = v[j].y; w[4 * j + 2] = v[j].z; w[4 * j + 3] = v[j].w; }
+#pragma unroll
+        for (int m = 0; m < 4; ++m) gm_rev4px3(w[9 - 3 * m], w[10 - 3 * m], w[11 - 3 * m], o + 3 * m);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) v[j] = u32x4{o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]};
+    } else {
+        const u32x4 s = v[0];
+        v[0] = u32x4{(s.w >> 16) | (s.w << 16), (s.z >> 16) | (s.z << 16), (s.y >> 16) | (s.y << 16), (s.x >> 16) | (s.x << 16)};
+    }
+}
+
+// the bytes [b0, b1) of one item, byte by byte: any address and any W
+__device__ __forceinline__ void gm_move_bytes(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int64_t b0, int64_t b1,
+                                              bool fl, int64_t row_bytes, int px) {
+    for (int64_t i = b0 + threadIdx.x; i < b1; i += GF_BLOCK) {
+        int64_t j = i;
+        if (fl) {
+            const int64_t r = i / row_bytes, xb = i - r * row_bytes;
+            const int64_t x = xb / px, c = xb - x * px;
+            j = r * row_bytes + row_bytes - (x + 1) * px + c;
+        }
+        dst[i] = src[j];
+    }
+}
+
+// grid (splits, items).  The unit of work is one group: 48 bytes (PX 3) or 16 (PX 2), gpr of them in a row; a lane reads the group
+// at the mirrored place of the row with 16-byte loads, reverses its pixels in registers and writes 16-byte words.  The launcher
+// vouches for 16-byte aligned bases and rows that are whole groups; the offset is looked at here, and an item whose offset is
+// not a multiple of 16 goes byte by byte (uniform over the workgroup).  An item that leaves the arena is zero-filled, never read.
+template <int PX, bool NT>
+__global__ __launch_bounds__(GF_BLOCK) void gather_mirror_v16_kernel(const uint8_t* __restrict__ arena, int64_t arena_bytes,
+                                                                     const int64_t* __restrict__ src_off,
+                                                                     const uint8_t* __restrict__ flip, uint8_t* __restrict__ out,
+                                                                     int64_t item_bytes, uint32_t gpr) {
+    constexpr int NV = PX == 3 ? 3 : 1;                        // 16-byte words of a group
+    constexpr int UN = PX == 3 ? 2 : 4;                        // groups a lane has in flight
+    const int64_t item = blockIdx.y;
+    const int64_t off = src_off[item];
+    const bool fl = flip[item] != 0;
+    uint8_t* dst = out + item * item_bytes;
+    const bool inside = off >= 0 && off <= arena_bytes - item_bytes;
+    int64_t g0, g1;
+    gf_share(item_bytes / (16 * NV), GF_BLOCK, blockIdx.x, gridDim.x, &g0, &g1);
+    u32x4* d = reinterpret_cast<u32x4*>(dst);
+    if (!inside) {
+        for (int64_t v = g0 * NV + threadIdx.x; v < g1 * NV; v += GF_BLOCK) d[v] = u32x4{0u, 0u, 0u, 0u};
+        return;
+    }
+    const uint8_t* src = arena + off;
+    if (off & 15) {
+        gm_move_bytes(src, dst, g0 * 16 * NV, g1 * 16 * NV, fl, (int64_t)gpr * 16 * NV, PX);
+        return;
+    }
+    const u32x4* s = reinterpret_cast<const u32x4*>(src);
+    if (!fl) {                                                 // a copy: consecutive lanes move consecutive words, as gather_frames
+        gf_copy_v16<NT>(s, d, g0 * NV, g1 * NV);
+        return;
+    }
+    // the group that output group g is read from: the one at the mirrored place of its row (an item holds fewer than 2^31 bytes)
+    auto from = [&](int64_t g) -> int64_t {
+        const uint32_t x = (uint32_t)g % gpr;
+        return g + (int64_t)gpr - 1 - 2 * (int64_t)x;
+    };
+    int64_t g = g0 + threadIdx.x;
+    for (; g + (UN - 1) * GF_BLOCK < g1; g += UN * GF_BLOCK) {
+        u32x4 r[UN][NV];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const u32x4* p = s + from(g + u * GF_BLOCK) * NV;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) r[u][j] = NT ? __builtin_nontemporal_load(p + j) : p[j];
+        }
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            gm_reverse_group<PX>(r[u]);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) d[(g + u * GF_BLOCK) * NV + j] = r[u][j];
+        }
+    }
+    for (; g < g1; g += GF_BLOCK) {
+        u32x4 r[NV];
+        const u32x4* p = s + from(g) * NV;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) r[j] = NT ? __builtin_nontemporal_load(p + j) : p[j];
+        gm_reverse_group<PX>(r);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) d[g * NV + j] = r[j];
+    }
+}
+
+__global__ __launch_bounds__(GF_BLOCK) void gather_mirror_bytes_kernel(const uint8_t* __restrict__ arena, int64_t arena_bytes,
+                                                                       const int64_t* __restrict__ src_off,
+                                                                       const uint8_t* __restrict__ flip, uint8_t* __restrict__ out,
+                                                                       int64_t item_bytes, int64_t row_bytes, int px) {
+    const int64_t item = blockIdx.y;
+    const int64_t off = src_off[item];
+    uint8_t* dst = out + item * item_bytes;
+    int64_t b0, b1;
+    gf_share(item_bytes, GF_BLOCK, blockIdx.x, gridDim.x, &b0, &b1);
+    if (off < 0 || off > arena_bytes - item_bytes) {
+        for (int64_t i = b0 + threadIdx.x; i < b1; i += GF_BLOCK) dst[i] = 0;
+        return;
+    }
+    gm_move_bytes(arena + off, dst, b0, b1, flip[item] != 0, row_bytes, px);
 }
 
 // One workgroup per sample.  Every value is one fp32 subtract and one correctly rounded fp32 divide, as torch computes
@@ -143,6 +269,53 @@ int launch_gather_frames(const void* arena, int64_t arena_bytes, const int64_t* 
     }
     prof_end(st);
     if (hipGetLastError() != hipSuccess) { if (err) *err = "gather_frames: launch failed"; return -3; }
+    return 0;
+}
+
+int launch_gather_frames_mirror(const actmi_gather_mirror_desc& d, hipStream_t st, std::string* err) {
+    auto fail = [&](const char* m) { if (err) *err = m; return -2; };
+    if (d.n_items == 0) return 0;
+    if (d.n_items < 0 || d.H < 0 || d.W < 0 || d.arena_bytes < 0) return fail("gather_frames_mirror: negative size");
+    if (d.px_bytes != 2 && d.px_bytes != 3) return fail("gather_frames_mirror: px_bytes must be 3 (u8 BGR) or 2 (uint16 depth)");
+    if (d.n_items > 65535) return fail("gather_frames_mirror: n_items > 65535");
+    if (d.aligned < 0 || d.aligned > 2) return fail("gather_frames_mirror: aligned must be 0, 1 or 2");
+    const int64_t row_bytes = (int64_t)d.W * d.px_bytes, item_bytes = row_bytes * d.H;
+    if (item_bytes > 0x7fffffff) return fail("gather_frames_mirror: one item of more than 2^31 - 1 bytes");
+    if (d.aligned && d.W % (d.px_bytes == 3 ? 16 : 8))
+        return fail("gather_frames_mirror: the aligned form needs W to be a multiple of 16 (px_bytes 3) or 8 (px_bytes 2)");
+    if (item_bytes == 0) return 0;
+    if (!d.arena || !d.src_off || !d.flip || !d.out) return fail("gather_frames_mirror: null pointer");
+    if ((uintptr_t)d.src_off & 7) return fail("gather_frames_mirror: src_off must be 8-byte aligned");
+    if (d.aligned && (((uintptr_t)d.arena & 15) || ((uintptr_t)d.out & 15)))
+        return fail("gather_frames_mirror: the aligned form needs arena and out to be multiples of 16");
+    // as launch_gather_frames: about 2048 workgroups in all, none with less than 16 KiB of its item
+    const int64_t max_splits = (item_bytes + 16383) / 16384;
+    int64_t splits = (2048 + d.n_items - 1) / d.n_items;
+    splits = splits > max_splits ? max_splits : splits;
+    splits = splits < 1 ? 1 : splits;
+    const dim3 grid((unsigned)splits, (unsigned)d.n_items), block(GF_BLOCK);
+    const uint8_t* a = static_cast<const uint8_t*>(d.arena);
+    uint8_t* o = static_cast<uint8_t*>(d.out);
+    const double bytes = 2.0 * (double)d.n_items * (double)item_bytes;
+    if (d.aligned) {
+        const uint32_t gpr = (uint32_t)(d.W / (d.px_bytes == 3 ? 16 : 8));
+        const bool nt = d.aligned == 2;
+        prof_begin(nt ? "gather_mirror_v16_nt" : "gather_mirror_v16", 0.0, bytes, st);
+        if (d.px_bytes == 3 && nt)
+            hipLaunchKernelGGL((gather_mirror_v16_kernel<3, true>), grid, block, 0, st, a, d.arena_bytes, d.src_off, d.flip, o, item_bytes, gpr);
+        else if (d.px_bytes == 3)
+            hipLaunchKernelGGL((gather_mirror_v16_kernel<3, false>), grid, block, 0, st, a, d.arena_bytes, d.src_off, d.flip, o, item_bytes, gpr);
+        else if (nt)
+            hipLaunchKernelGGL((gather_mirror_v16_kernel<2, true>), grid, block, 0, st, a, d.arena_bytes, d.src_off, d.flip, o, item_bytes, gpr);
+        else
+            hipLaunchKernelGGL((gather_mirror_v16_kernel<2, false>), grid, block, 0, st, a, d.arena_bytes, d.src_off, d.flip, o, item_bytes, gpr);
+    } else {
+        prof_begin("gather_mirror_bytes", 0.0, bytes, st);
+        hipLaunchKernelGGL(gather_mirror_bytes_kernel, grid, block, 0, st, a, d.arena_bytes, d.src_off, d.flip, o, item_bytes, row_bytes,
+                           (int)d.px_bytes);
+    }
+    prof_end(st);
+    if (hipGetLastError() != hipSuccess) { if (err) *err = "gather_frames_mirror: launch failed"; return -3; }
     return 0;
 }
 

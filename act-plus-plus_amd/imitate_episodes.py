@@ -11,7 +11,9 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
 * ``replay_bc`` (``--eval --replay``) evaluates open loop on recorded episodes instead -- the one evaluation of use_depth /
   use_pcd policies and of policies trained on real-robot episodes: queries batched over TIME, one ensemble launch per episode;
 * ``--device_dataset --replay_every N`` runs that replay on held-out episodes every N training steps, out of the device-resident
-  store the batches come from (no file read); ``--replay_horizon`` adds the error along the predicted chunk.
+  store the batches come from (no file read); ``--replay_horizon`` adds the error along the predicted chunk;
+* ``--mirror_twins`` joins every episode file by its mirrored twin (postprocess_episodes.py's definition), computed as it is read:
+  ``actmi.data.load_data(..., mirror_twins=True)``; with ``--device_dataset`` the twins share their sources' frames.
 """
 import argparse
 import os
@@ -871,6 +873,12 @@ def build_config(args):
         config["device_dataset"] = True
         if args.get("device_dataset_gb") is not None:
             config["device_dataset_gb"] = float(args["device_dataset_gb"])
+    if args.get("mirror_twins"):
+        if policy_class != "ACT":
+            raise NotImplementedError("--mirror_twins: the mirrored twin episodes feed the ACT training path")
+        if args.get("use_pcd"):
+            raise ValueError("--mirror_twins with --use_pcd: a stored point cloud has no mirror rule")
+        config["mirror_twins"] = True
     if args.get("replay_every"):
         if int(args["replay_every"]) < 0:
             raise ValueError("--replay_every must not be negative")
@@ -925,6 +933,8 @@ def main(args):
     device_dataset = bool(config.get("device_dataset"))
     if device_dataset and not (dataset_dir and os.path.isdir(dataset_dir)):
         raise ValueError("--device_dataset needs episode files (--dataset_dir): the synthetic stand-in dataset is generated, not stored")
+    if config.get("mirror_twins") and not (dataset_dir and os.path.isdir(dataset_dir)):
+        raise ValueError("--mirror_twins needs episode files (--dataset_dir): the synthetic stand-in dataset has no arms to swap")
     if dataset_dir and os.path.isdir(dataset_dir):
         # reference imitate_episodes.py:141-147: episodes on disk (HDF5 via h5py, or .npz with the same keys), z-scored
         # qpos / actions, u8 images; batches reach the device through pinned staging on a side stream
@@ -939,7 +949,7 @@ def main(args):
                                                use_depth=use_depth, pointcloud_names=config.get("pointcloud_names"),
                                                use_pcd=use_pcd, max_points=config["policy_config"].get("max_points"),
                                                # --device_dataset: every rank holds its own full store on its own device
-                                               device_dataset=device_dataset,
+                                               device_dataset=device_dataset, mirror_twins=bool(config.get("mirror_twins")),
                                                device=f"cuda:{local_rank}" if world > 1 else None,     # train_bc's device
                                                device_budget_bytes=(int(config["device_dataset_gb"] * 2**30)
                                                                     if config.get("device_dataset_gb") is not None else None))
@@ -1024,6 +1034,11 @@ def make_parser():
                         help="ACT training from --dataset_dir, opt-in: read every episode once into device memory and gather the "
                              "training batches there (actmi.data.DeviceEpisodeStore): the same batches as the host loader, no loader "
                              "workers; every rank holds the whole dataset; not with --use_pcd")
+    parser.add_argument("--mirror_twins", action="store_true",
+                        help="ACT training on episode files: join every episode by its mirrored twin (arms and wrist cameras "
+                             "swapped, frames flipped, as postprocess_episodes.py defines it), computed as it is read; with "
+                             "--device_dataset the twins take no frame memory; not with --use_pcd, and a directory that already "
+                             "holds mirrored files needs --skip_mirrored_data")
     parser.add_argument("--device_dataset_gb", action="store", type=float, default=None,
                         help="--device_dataset: device memory the store may take, in GiB (default: what is free minus a 64 GiB reserve)")
     return parser

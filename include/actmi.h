@@ -778,6 +778,27 @@ int actmi_op_warp_u16(const actmi_augment_desc* d, void* stream);
  * 480 x 640 x 2 are), 0 otherwise.  n_items <= 65535.  Capturable: one stream, no allocation, no synchronisation, nothing read on the host. */
 int actmi_op_gather_frames(const void* arena, int64_t arena_bytes, const int64_t* src_off, void* out, int64_t n_items,
                            int64_t item_bytes, int aligned, void* stream);
+/* actmi_op_gather_frames_mirror: actmi_op_gather_frames for items that are frames, H rows of W pixels of px_bytes bytes, each
+ * either copied or MIRRORED: with flip[i] == 0 item i is the H * W * px_bytes bytes at arena + src_off[i] (the bytes
+ * actmi_op_gather_frames gives), otherwise out[i][r][x][c] = src[i][r][W-1-x][c]: the pixels of every row in reverse order, rows
+ * in order, the bytes of a pixel in order (what numpy's frame[:, ::-1] is).  Copied and mirrored items mix freely in one launch
+ * (flip [n_items] uint8 ON THE DEVICE).  px_bytes is 3 (u8 BGR frames) or 2 (raw uint16 depth); anything else is refused, as is an
+ * item of more than 2^31 - 1 bytes.  n_items <= 65535, 64-bit offsets, zero fill of an item that leaves the arena and nothing
+ * written outside out[0 .. n_items * H * W * px_bytes): as actmi_op_gather_frames.  `aligned` has its meaning there, and states
+ * besides that W is a multiple of 16 (px_bytes 3) or 8 (px_bytes 2), which is checked with the bases: a lane then moves one group
+ * of 16 pixels (three 16-byte loads at the mirrored place of the row, a byte permute in registers, three 16-byte stores) or of 8
+ * (one 16-byte word).  An item whose offset is not a multiple of 16 is still moved correctly, byte by byte; the general form (0)
+ * moves every item so: any W, any address, correct, not tuned.  Capturable like actmi_op_gather_frames. */
+typedef struct actmi_gather_mirror_desc {
+    const void* arena;
+    int64_t arena_bytes;
+    const int64_t* src_off;    /* [n_items] byte offsets into the arena, on the device, 8-byte aligned */
+    const uint8_t* flip;       /* [n_items] 0 = copy, otherwise mirror, on the device */
+    void* out;                 /* [n_items][H][W][px_bytes] */
+    int64_t n_items;
+    int32_t H, W, px_bytes, aligned;
+} actmi_gather_mirror_desc;
+int actmi_op_gather_frames_mirror(const actmi_gather_mirror_desc* d, void* stream);
 /* actmi_op_gather_chunks: the rest of EpisodicDataset.__getitem__ for B samples, bit for bit.  actions [n_rows][A] and qpos
  * [n_rows][S] hold all episodes' rows back to back, already f32 as the dataset converts them (/base_action columns included);
  * episodes [n_episodes] says where each starts; samples [B][2] int32 = (episode, t) on the device.  With s = is_sim ? t :
