@@ -126,6 +126,18 @@ class AugmentDesc(C.Structure):
                [(k, C.c_int32) for k in ("B", "K", "H", "W", "ch", "cw")]
 
 
+class CloudAugmentRecord(C.Structure):
+    # actmi_cloud_augment_record: the device parameter record of one sample, 56 bytes
+    _fields_ = [(k, C.c_float) for k in ("cos", "sin", "scale", "tx", "ty", "tz", "jitter", "drop", "fb", "fc", "fs")] + \
+               [("order", C.c_int32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)]
+
+
+class CloudAugmentDesc(C.Structure):
+    # actmi_cloud_augment_desc
+    _fields_ = [(k, C.c_void_p) for k in ("xyz", "rgb", "counts", "records", "out_xyz", "out_rgb", "out_counts")] + \
+               [("pivot", C.c_float * 3), ("B", C.c_int32), ("P", C.c_int32)]
+
+
 class EpisodeRec(C.Structure):
     # actmi_episode_rec: one entry of the device episode table, 16 bytes
     _fields_ = [("row0", C.c_int64), ("T", C.c_int32), ("is_sim", C.c_int32)]
@@ -246,6 +258,7 @@ def load():
         "actmi_op_augment_workspace_bytes": ([i32, i32, i32, i32], C.c_int64),
         "actmi_op_augment_u8": ([C.POINTER(AugmentDesc), vp], i32),
         "actmi_op_warp_u16": ([C.POINTER(AugmentDesc), vp], i32),
+        "actmi_op_cloud_augment": ([C.POINTER(CloudAugmentDesc), vp], i32),
         "actmi_op_gather_frames": ([vp, i64, vp, vp, i64, i64, i32, vp], i32),
         "actmi_op_gather_frames_mirror": ([C.POINTER(GatherMirrorDesc), vp], i32),
         "actmi_op_gather_chunks": ([C.POINTER(GatherChunksDesc), vp], i32),

@@ -1307,11 +1307,37 @@ def depth_warp_ref(depth_u16, records, ch, cw):
     return out
 
 
+class _RecordRing:
+    """The device block of an augmenter's records, one per sample, and the ring of pinned host blocks it is fed through: an upload
+    is stream-ordered, and the pinned block a copy reads from is not rewritten before that copy has run (an event each)."""
+    RING = 4
+
+    def __init__(self, device, nbytes):
+        self.device = device
+        self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        self._host = [torch.zeros(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
+        self._events = [None] * self.RING
+        self._slot = 0
+
+    def upload(self, rec):
+        """rec: a contiguous numpy record array -> the front of the device block, on the current stream"""
+        n = rec.nbytes
+        i = self._slot
+        self._slot = (i + 1) % self.RING
+        if self._events[i] is not None:
+            self._events[i].synchronize()
+        self._host[i].numpy()[:n] = rec.view("u1")
+        with torch.cuda.device(self.device):
+            self.dev[:n].copy_(self._host[i][:n], non_blocking=True)
+            self._events[i] = torch.cuda.Event()
+            self._events[i].record(torch.cuda.current_stream(self.device))
+
+
 class ImageAugment:
     """The reference dataset's training augmentation (utils.py:141-156: RandomCrop at `ratio`, Resize back with antialias,
     RandomRotation within `degrees`, ColorJitter) as one device op over the u8 batch of a training step (actmi_op_augment_u8), and
     the three geometric steps over the raw uint16 depth frames of a use_depth batch with the SAME draws (actmi_op_warp_u16).  Owns
-    the output buffers, the workspace, and the records: a ring of pinned host blocks and one device block.
+    the output buffers, the workspace, and the records (a _RecordRing).
 
     engine_or_device: an ACTEngine (its device) or a device.  K cameras (Kd depth cameras, 0: none) of H x W pixels.  One draw per
     SAMPLE: top, left uniform integers over the crop's positions, angle U[-degrees, degrees], factors U[1 - x, 1 + x] (not below
@@ -1320,7 +1346,6 @@ class ImageAugment:
 
     draw(B) fills and uploads records; run(image_u8, depth_u16, B) launches with the records on the device; apply = draw + run.
     The returned tensors are views of the augmenter's own buffers, valid until the next run."""
-    RING = 4
 
     def __init__(self, engine_or_device, K, H, W, max_batch, ratio=0.95, degrees=5.0, brightness=0.3, contrast=0.4, saturation=0.5,
                  seed=0, Kd=0):
@@ -1341,7 +1366,7 @@ class ImageAugment:
         self.ranges = tuple((max(0.0, 1.0 - float(x)), 1.0 + float(x)) for x in (brightness, contrast, saturation))
         self._np = np
         self.set_seed(seed)
-        self._host = None                                  # device and pinned buffers: made on the first use of a GPU
+        self._ring = None                                  # device and pinned buffers: made on the first use of a GPU
         self._last = np.zeros(0, dtype=augment_record_dtype())
         if torch.cuda.is_available():
             self._alloc()
@@ -1352,10 +1377,7 @@ class ImageAugment:
         if nbytes < 0:
             raise ValueError(f"ImageAugment: shape B = {MB}, K = {self.K}, {self.H} x {self.W} not supported by actmi_op_augment_u8")
         self._ws = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=dev)
-        self._rec = torch.zeros(MB * 32, dtype=torch.uint8, device=dev)
-        self._host = [torch.zeros(MB * 32, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
-        self._events = [None] * self.RING
-        self._slot = 0
+        self._ring = _RecordRing(dev, MB * 32)
         self.out = torch.zeros((MB, self.K, self.H, self.W, 3), dtype=torch.uint8, device=dev)
         self.depth_out = torch.zeros((MB, self.Kd, 1, self.H, self.W), dtype=torch.uint16, device=dev) if self.Kd else None
 
@@ -1376,23 +1398,14 @@ class ImageAugment:
     def set_records(self, records):
         """upload [B] records (augment_record_dtype) on the current stream: launches enqueued behind it, captured ones too, see
         them.  The pinned block a copy reads from is not rewritten before that copy has run (a ring of blocks, an event each)."""
-        np = self._np
-        rec = np.ascontiguousarray(records, dtype=augment_record_dtype())
+        rec = self._np.ascontiguousarray(records, dtype=augment_record_dtype())
         B = len(rec)
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"ImageAugment: {B} records: needs 1 <= B <= max_batch {self.max_batch}")
         self._last = rec.copy()
-        if self._host is None:
+        if self._ring is None:
             self._alloc()
-        i = self._slot
-        self._slot = (i + 1) % self.RING
-        if self._events[i] is not None:
-            self._events[i].synchronize()
-        self._host[i].numpy()[:B * 32] = rec.view(np.uint8)
-        with torch.cuda.device(self.device):
-            self._rec[:B * 32].copy_(self._host[i][:B * 32], non_blocking=True)
-            self._events[i] = torch.cuda.Event()
-            self._events[i].record(torch.cuda.current_stream(self.device))
+        self._ring.upload(rec)
 
     def records(self):
         """the records of the last draw / set_records, on the host"""
@@ -1422,10 +1435,10 @@ class ImageAugment:
             if isinstance(depth_u16, torch.Tensor) and tuple(depth_u16.shape) == (B, self.Kd, self.H, self.W):
                 depth_u16 = depth_u16.unsqueeze(2)
             self._check("depth", depth_u16, torch.uint16, (B, self.Kd, 1, self.H, self.W))
-        if self._host is None:
+        if self._ring is None:
             self._alloc()
         d = L.AugmentDesc()
-        d.records, d.ws, d.ws_bytes = self._rec.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 4
+        d.records, d.ws, d.ws_bytes = self._ring.dev.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 4
         d.B, d.H, d.W, d.ch, d.cw = B, self.H, self.W, self.ch, self.cw
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -1441,6 +1454,274 @@ class ImageAugment:
         """one fresh draw per sample, then run"""
         self.draw(int(image_u8.shape[0] if B is None else B))
         return self.run(image_u8, depth_u16, B)
+
+
+# ---- training-time point-cloud augmentation (csrc/cloud_augment.hip; contract at actmi_cloud_augment_desc in actmi.h) ------------
+def cloud_augment_record_dtype():
+    """actmi_cloud_augment_record as a numpy structured dtype (56 bytes)"""
+    import numpy as np
+    return np.dtype([(k, "<f4") for k in ("cos", "sin", "scale", "tx", "ty", "tz", "jitter", "drop", "fb", "fc", "fs")] +
+                    [("order", "<i4"), ("seed_lo", "<u4"), ("seed_hi", "<u4")])
+
+
+def cloud_augment_records(B, angle=0.0, scale=1.0, shift=(0, 0, 0), jitter=0.0, drop=0.0, order=0, fb=1.0, fc=1.0, fs=1.0, seed=0):
+    """[B] records from numbers or [B] arrays (shift: 3 numbers or [B, 3]; seed: 64-bit integers); angle in degrees about +z,
+    counter-clockwise seen from above: cos and sin are taken in double on the host and rounded to float32.  The defaults are the
+    identity."""
+    import numpy as np
+    B = int(B)
+    r = np.zeros(B, dtype=cloud_augment_record_dtype())
+    a = np.deg2rad(np.broadcast_to(np.asarray(angle, dtype=np.float64), (B,)))
+    r["cos"], r["sin"] = np.cos(a), np.sin(a)
+    r["scale"], r["jitter"], r["drop"], r["order"] = scale, jitter, drop, order
+    t = np.broadcast_to(np.asarray(shift, dtype=np.float64), (B, 3))
+    r["tx"], r["ty"], r["tz"] = t[:, 0], t[:, 1], t[:, 2]
+    r["fb"], r["fc"], r["fs"] = fb, fc, fs
+    s = np.broadcast_to(np.asarray(seed, dtype=np.uint64), (B,))
+    r["seed_lo"], r["seed_hi"] = s & np.uint64(0xFFFFFFFF), s >> np.uint64(32)
+    return r
+
+
+def _mix32(x):
+    """actmi_mix32 of csrc/dropout.h on a uint32 array (products wrap)"""
+    import numpy as np
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def u01_ref(seed, idx):
+    """actmi_u01 of csrc/dropout.h in numpy: seed a 64-bit integer, idx an array of 64-bit element indices -> float32 in [0, 1),
+    24 bits each"""
+    import numpy as np
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    idx = np.asarray(idx, dtype=np.uint64)
+    lo, hi = (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32), (idx >> np.uint64(32)).astype(np.uint32)
+    h = _mix32(lo ^ np.uint32(seed & 0xFFFFFFFF))
+    h = _mix32(h ^ hi ^ np.uint32(seed >> 32) ^ np.uint32(0x9E3779B9))
+    return (h >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+def _cloud_counts(n, B, P):
+    import numpy as np
+    if n is None:
+        return np.full(B, P, np.int64)
+    n = np.asarray(n).astype(np.int64).reshape(-1)
+    if len(n) != B:
+        raise ValueError(f"cloud_augment_ref: {len(n)} counts for {B} samples")
+    return np.clip(n, 1, P)
+
+
+def cloud_augment_ref(xyz, rgb, n, records, pivot):
+    """actmi_op_cloud_augment in numpy: the definition at actmi_cloud_augment_desc in actmi.h stated once more -- the oracle of the
+    device op, not a fallback for it.  xyz, rgb [B, P, 3] float32 (numpy or CPU tensors), n [B] integers or None (P everywhere),
+    records [B] (cloud_augment_record_dtype), pivot 3 numbers -> (xyz, rgb [B, P, 3] float32, counts [B] int32), numpy."""
+    import numpy as np
+    f = np.float32
+    xyz, rgb = np.asarray(xyz), np.asarray(rgb)
+    if xyz.dtype != f or rgb.dtype != f or xyz.ndim != 3 or xyz.shape[2] != 3 or rgb.shape != xyz.shape or len(records) != len(xyz):
+        raise ValueError(f"cloud_augment_ref: xyz {xyz.dtype} {xyz.shape}, rgb {rgb.dtype} {rgb.shape}, {len(records)} records")
+    B, P, _ = xyz.shape
+    counts = _cloud_counts(n, B, P)
+    pv = np.asarray(pivot, dtype=f).reshape(3)
+    out_xyz, out_rgb, out_n = np.zeros_like(xyz), np.zeros_like(rgb), np.zeros(B, np.int32)
+
+    def gray(c):
+        return ((f(0.2989) * c[:, 0]) + (f(0.587) * c[:, 1])) + (f(0.114) * c[:, 2])
+
+    def blend(a, b, r):
+        return np.fmin(np.fmax((r * a) + ((f(1) - r) * b), f(0)), f(255))       # fmax / fmin: the operand that is a number
+
+    with np.errstate(all="ignore"):
+        for b in range(B):
+            rec, m = records[b], int(counts[b])
+            seed = int(rec["seed_lo"]) | int(rec["seed_hi"]) << 32
+            u = u01_ref(seed, np.arange(4 * m, dtype=np.uint64)).reshape(m, 4)
+            d = xyz[b, :m] - pv
+            cs, sn = f(rec["cos"]), f(rec["sin"])
+            r = np.stack([(d[:, 0] * cs) - (d[:, 1] * sn), (d[:, 0] * sn) + (d[:, 1] * cs), d[:, 2]], axis=1)
+            t = np.array([rec["tx"], rec["ty"], rec["tz"]], dtype=f)
+            j = ((u[:, :3] + u[:, :3]) - f(1)) * f(rec["jitter"])
+            q = (((r * f(rec["scale"])) + pv) + t) + j
+            c = rgb[b, :m]
+            for op in AUGMENT_ORDERS[min(max(int(rec["order"]), 0), 5)]:
+                if op == 0:
+                    c = blend(c, f(0), f(rec["fb"]))
+                elif op == 1:
+                    total = int(np.trunc(np.fmin(np.fmax(gray(c), f(0)), f(255))).astype(np.int64).sum())       # exact
+                    c = blend(c, f(np.float64(total) / np.float64(m)), f(rec["fc"]))
+                else:
+                    c = blend(c, gray(c)[:, None], f(rec["fs"]))
+            keep = u[:, 3] >= f(rec["drop"])
+            if not keep.any():
+                keep[0] = True
+            k = int(keep.sum())
+            out_xyz[b, :k], out_rgb[b, :k], out_n[b] = q[keep], c[keep], k
+    return out_xyz, out_rgb, out_n
+
+
+def _cloud_check(name, t, B, P, device=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError(f"cloud_augment: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != 3 or t.shape[2] != 3 or (B is not None and tuple(t.shape) != (B, P, 3)):
+        raise ValueError(f"cloud_augment: {name} shape {tuple(t.shape)} != {(B if B is not None else 'B', P if B is not None else 'P', 3)}")
+    if not t.is_cuda or not t.is_contiguous() or (device is not None and t.device != device):
+        raise ValueError(f"cloud_augment: {name} must be contiguous on {device or 'a cuda device'} (it is on {t.device})")
+
+
+def _cloud_counts_check(n, B, device):
+    if n is None:
+        return
+    if not isinstance(n, torch.Tensor) or n.dtype != torch.int32:
+        raise TypeError(f"cloud_augment: n must be an int32 tensor, got {getattr(n, 'dtype', type(n))}")
+    if tuple(n.shape) != (B,) or not n.is_contiguous() or n.device != device:
+        raise ValueError(f"cloud_augment: n shape {tuple(n.shape)} on {n.device} != {(B,)} (contiguous) on {device}")
+
+
+def _cloud_launch(xyz, rgb, n, rec_ptr, pivot, out_xyz, out_rgb, out_n, B, P):
+    d = L.CloudAugmentDesc()
+    d.xyz, d.rgb, d.counts, d.records = xyz.data_ptr(), rgb.data_ptr(), (n.data_ptr() if n is not None else None), rec_ptr
+    d.out_xyz, d.out_rgb, d.out_counts = out_xyz.data_ptr(), out_rgb.data_ptr(), out_n.data_ptr()
+    d.pivot[0], d.pivot[1], d.pivot[2] = (float(v) for v in pivot)
+    d.B, d.P = B, P
+    with torch.cuda.device(xyz.device):
+        st = C.c_void_p(torch.cuda.current_stream(xyz.device).cuda_stream)
+        L.check(L.load().actmi_op_cloud_augment(C.byref(d), st), None, "op_cloud_augment")
+
+
+def cloud_augment(xyz, rgb, n, records, pivot, out=None):
+    """actmi_op_cloud_augment, the raw op: xyz, rgb [B, P, 3] float32 on the device, n int32 [B] on the device or None, records
+    [B] -- a numpy array of cloud_augment_record_dtype (uploaded here, which waits for the copy) or a uint8 device tensor of B * 56
+    bytes -- and the pivot's 3 numbers -> (xyz, rgb, counts) in `out` (three tensors of those shapes) or in fresh ones."""
+    import numpy as np
+    _cloud_check("xyz", xyz, None, None)
+    B, P, _ = xyz.shape
+    _cloud_check("rgb", rgb, B, P, xyz.device)
+    _cloud_counts_check(n, B, xyz.device)
+    if not isinstance(records, torch.Tensor):
+        rec = np.ascontiguousarray(records, dtype=cloud_augment_record_dtype())
+        records = torch.from_numpy(rec.view(np.uint8).copy()).to(xyz.device)
+    if records.dtype != torch.uint8 or records.numel() != B * 56 or records.device != xyz.device or not records.is_contiguous():
+        raise ValueError(f"cloud_augment: records must be {B} x 56 bytes (uint8, contiguous) on {xyz.device}")
+    if out is None:
+        out = (torch.empty_like(xyz), torch.empty_like(rgb), torch.empty(B, dtype=torch.int32, device=xyz.device))
+    out_xyz, out_rgb, out_n = out
+    _cloud_check("out xyz", out_xyz, B, P, xyz.device)
+    _cloud_check("out rgb", out_rgb, B, P, xyz.device)
+    _cloud_counts_check(out_n, B, xyz.device)
+    _cloud_launch(xyz, rgb, n, records.data_ptr(), pivot, out_xyz, out_rgb, out_n, B, P)
+    return out_xyz, out_rgb, out_n
+
+
+class CloudAugment:
+    """Training augmentation for the stored clouds of a use_pcd batch, as one device op (actmi_op_cloud_augment): a yaw about +z
+    of the cloud's frame, an isotropic scale about `pivot`, a shift, a per-point uniform jitter, random point dropout, and
+    ImageAugment's colour jitter on the points' colours (0..255 floats).  Owns the output buffers and the records (a _RecordRing),
+    as ImageAugment does.
+
+    engine_or_device: an ACTEngine (its device) or a device.  Clouds of up to `max_points` points, batches of up to `max_batch`.
+    One draw per SAMPLE from a numpy.random.Generator seeded with `seed`: angle U[-degrees, degrees], scale U[1 - scale, 1 + scale],
+    each shift component U[-shift, shift] (the cloud's units: metres for the recorder's clouds), the three colour factors
+    U[1 - x, 1 + x] (not below 0) and the order uniform over the 6 as ImageAugment draws them, and 64 seed bits for the per-point
+    draws; `jitter` (the half width of the per-coordinate uniform jitter) and `drop` (the probability that a point is dropped) go
+    into every record as they are.
+
+    The defaults are choices, not measurements: the image augmentation's 5 degrees and colour ranges, 5 % of scale, a centimetre
+    of shift, 2 mm of jitter -- about a depth camera's noise at arm's length -- and a tenth of the points dropped.  No training run
+    has tuned them; the reference has no cloud augmentation to take them from.
+
+    draw(B) fills and uploads records; run(xyz, rgb, n) launches with the records on the device; apply = draw + run.  The
+    returned tensors are views of the augmenter's own buffers, valid until the next run."""
+    REC = 56
+
+    def __init__(self, engine_or_device, max_points, max_batch, pivot=(0, 0, 0), degrees=5.0, scale=0.05, shift=0.01, jitter=0.002,
+                 drop=0.1, brightness=0.3, contrast=0.4, saturation=0.5, seed=0):
+        import numpy as np
+        eng = engine_or_device if hasattr(engine_or_device, "cfg") else None
+        self.device = torch.device(eng.device if eng is not None else engine_or_device)
+        if self.device.type != "cuda":
+            raise ValueError(f"CloudAugment: device must be a cuda device, got {self.device}")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self.max_points, self.max_batch = int(max_points), int(max_batch)
+        if self.max_points < 1 or not 1 <= self.max_batch <= 65535:
+            raise ValueError(f"CloudAugment: max_points = {max_points}, max_batch = {max_batch}")
+        self.pivot = tuple(float(v) for v in pivot)
+        if len(self.pivot) != 3 or not all(np.isfinite(self.pivot)):
+            raise ValueError(f"CloudAugment: pivot {pivot} is not 3 finite numbers")
+        if min(degrees, scale, shift, jitter, brightness, contrast, saturation) < 0 or scale >= 1 or not 0.0 <= drop < 1.0:
+            raise ValueError("CloudAugment: a negative range, scale >= 1, or drop outside [0, 1)")
+        self.degrees, self.scale, self.shift, self.jitter, self.drop = (float(v) for v in (degrees, scale, shift, jitter, drop))
+        self.ranges = tuple((max(0.0, 1.0 - float(x)), 1.0 + float(x)) for x in (brightness, contrast, saturation))
+        self._np = np
+        self.set_seed(seed)
+        self._ring = None                                  # device and pinned buffers: made on the first use of a GPU
+        self._last = np.zeros(0, dtype=cloud_augment_record_dtype())
+        if torch.cuda.is_available():
+            self._alloc()
+
+    def _alloc(self):
+        dev, MB = self.device, self.max_batch
+        self._ring = _RecordRing(dev, MB * self.REC)
+        self.out_xyz = torch.zeros(MB * self.max_points * 3, dtype=torch.float32, device=dev)
+        self.out_rgb = torch.zeros(MB * self.max_points * 3, dtype=torch.float32, device=dev)
+        self.out_n = torch.zeros(MB, dtype=torch.int32, device=dev)
+
+    def set_seed(self, seed):
+        """restart the generator of the draws"""
+        self._rng = self._np.random.default_rng(int(seed))
+
+    def draw_records(self, B):
+        """[B] fresh records on the host (nothing is uploaded)"""
+        rng, B = self._rng, int(B)
+        angle = rng.uniform(-self.degrees, self.degrees, size=B)
+        scale = rng.uniform(1.0 - self.scale, 1.0 + self.scale, size=B)
+        shift = rng.uniform(-self.shift, self.shift, size=(B, 3))
+        fb, fc, fs = (rng.uniform(lo, hi, size=B) for lo, hi in self.ranges)
+        order = rng.integers(0, 6, size=B)
+        seed = rng.integers(0, 1 << 64, size=B, dtype=self._np.uint64)
+        return cloud_augment_records(B, angle, scale, shift, self.jitter, self.drop, order, fb, fc, fs, seed)
+
+    def set_records(self, records):
+        """upload [B] records (cloud_augment_record_dtype) on the current stream: launches enqueued behind it, captured ones too,
+        see them.  The pinned block a copy reads from is not rewritten before that copy has run (a ring of blocks, an event each)."""
+        rec = self._np.ascontiguousarray(records, dtype=cloud_augment_record_dtype())
+        B = len(rec)
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"CloudAugment: {B} records: needs 1 <= B <= max_batch {self.max_batch}")
+        self._last = rec.copy()
+        if self._ring is None:
+            self._alloc()
+        self._ring.upload(rec)
+
+    def records(self):
+        """the records of the last draw / set_records, on the host"""
+        return self._last.copy()
+
+    def draw(self, B):
+        self.set_records(self.draw_records(B))
+
+    def run(self, xyz, rgb, n=None):
+        """launch with the records on the device -> (xyz, rgb [B, P, 3], n int32 [B]): the kept points in front, zeros behind"""
+        _cloud_check("xyz", xyz, None, None, self.device)
+        B, P, _ = xyz.shape
+        if not 1 <= B <= self.max_batch or P > self.max_points:
+            raise ValueError(f"CloudAugment: clouds {tuple(xyz.shape)}: needs B <= max_batch {self.max_batch}, 1 <= P <= max_points "
+                             f"{self.max_points}")
+        _cloud_check("rgb", rgb, B, P, self.device)
+        _cloud_counts_check(n, B, self.device)
+        if self._ring is None:
+            self._alloc()
+        out = self.out_xyz[:B * P * 3].view(B, P, 3), self.out_rgb[:B * P * 3].view(B, P, 3), self.out_n[:B]
+        _cloud_launch(xyz, rgb, n, self._ring.dev.data_ptr(), self.pivot, *out, B, P)
+        return out
+
+    def apply(self, xyz, rgb, n=None):
+        """one fresh draw per sample, then run -> (xyz, rgb, n) for the policy's pointcloud"""
+        self.draw(int(xyz.shape[0]))
+        return self.run(xyz, rgb, n)
 
 
 class TemporalEnsemble:

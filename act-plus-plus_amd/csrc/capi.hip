@@ -468,6 +468,13 @@ int actmi_op_warp_u16(const actmi_augment_desc* d, void* stream) {
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
 }
 
+int actmi_op_cloud_augment(const actmi_cloud_augment_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "cloud_augment: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_cloud_augment(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_gather_frames(const void* arena, int64_t arena_bytes, const int64_t* src_off, void* out, int64_t n_items,
                            int64_t item_bytes, int aligned, void* stream) {
     g_op_error.clear();

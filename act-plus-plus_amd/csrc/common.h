@@ -241,6 +241,9 @@ int launch_augment_u8(const actmi_augment_desc& a, hipStream_t st, std::string* 
 // the geometric steps alone on one-channel u16 frames (raw depth), same records
 int launch_warp_u16(const actmi_augment_desc& a, hipStream_t st, std::string* err);
 
+// ---- training-time point-cloud augmentation (cloud_augment.hip; contract at actmi_cloud_augment_desc in actmi.h) -----------
+int launch_cloud_augment(const actmi_cloud_augment_desc& a, hipStream_t st, std::string* err);
+
 // ---- device-resident episode store (episode_store.hip; contract at actmi_op_gather_frames / actmi_op_gather_chunks in actmi.h) ----
 int launch_gather_frames(const void* arena, int64_t arena_bytes, const int64_t* src_off, void* out, int64_t n_items,
                          int64_t item_bytes, int aligned, hipStream_t st, std::string* err);

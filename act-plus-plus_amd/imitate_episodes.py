@@ -13,7 +13,9 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
 * ``--device_dataset --replay_every N`` runs that replay on held-out episodes every N training steps, out of the device-resident
   store the batches come from (no file read); ``--replay_horizon`` adds the error along the predicted chunk;
 * ``--mirror_twins`` joins every episode file by its mirrored twin (postprocess_episodes.py's definition), computed as it is read:
-  ``actmi.data.load_data(..., mirror_twins=True)``; with ``--device_dataset`` the twins share their sources' frames.
+  ``actmi.data.load_data(..., mirror_twins=True)``; with ``--device_dataset`` the twins share their sources' frames;
+* ``--augment_images`` and, for the stored clouds of ``--use_pcd``, ``--augment_clouds`` augment the TRAINING batches on the
+  device (actmi.ops.ImageAugment / CloudAugment), each from draws of its own.
 """
 import argparse
 import os
@@ -625,7 +627,7 @@ def _augment_frames(augment, image_data, depth_data=None):
     return augment.apply(image_data, depth_data)
 
 
-def forward_pass(data, policy, augment=None):
+def forward_pass(data, policy, augment=None, cloud_augment=None):
     """reference imitate_episodes.py:529-532; a 5-tuple ends in the depth frames of a use_depth dataset (the fork's
     train_single_arm_gripper_all.py:568-588), a 7-tuple in the padded clouds of a use_pcd dataset and their valid counts
     (pcd_xyz, pcd_rgb, pcd_n; the fork's :576-591 passes the one fused cloud).
@@ -634,7 +636,11 @@ def forward_pass(data, policy, augment=None):
     before the policy sees them -- the reference's dataset augmentation (utils.py:141-156), one draw per sample.  The raw depth
     frames of a use_depth batch are warped with the SAME draws; the fork draws a second time for depth
     (utils_arm_gripper_all.py:180-184), which moves depth and colour apart -- the intent, registered frames, is followed here.
-    The clouds of a use_pcd batch are left alone."""
+    The clouds of a use_pcd batch are left alone unless ``cloud_augment`` is given.
+
+    ``cloud_augment`` (an actmi.ops.CloudAugment; None: nothing changes): the clouds and counts of a 7-tuple go through its
+    ``apply`` on the device -- yaw, scale, shift, jitter, point dropout, colour jitter, one draw per sample -- and the policy gets
+    what it returns: the kept points in front, zeros behind, the new counts.  It draws independently of ``augment``."""
     depth_data = None
     if len(data) == 7:
         image_data, qpos_data, action_data, is_pad, pcd_xyz, pcd_rgb, pcd_n = data
@@ -643,6 +649,8 @@ def forward_pass(data, policy, augment=None):
             t.to(dev, non_blocking=True) for t in (image_data, qpos_data, action_data, is_pad, pcd_xyz, pcd_rgb, pcd_n))
         if augment is not None:
             image_data, _ = _augment_frames(augment, image_data)
+        if cloud_augment is not None:
+            pcd_xyz, pcd_rgb, pcd_n = cloud_augment.apply(pcd_xyz.contiguous(), pcd_rgb.contiguous(), pcd_n)
         return policy(qpos_data, image_data, action_data, is_pad, pointcloud={"xyz": pcd_xyz, "rgb": pcd_rgb, "n": pcd_n})
     if len(data) == 5:
         image_data, qpos_data, action_data, is_pad, depth_data = data
@@ -669,6 +677,20 @@ def make_augment(config, policy, seed):
     cfg = eng.cfg
     return ImageAugment(eng, cfg.num_cams, cfg.image_h, cfg.image_w, eng.max_batch, seed=seed,
                         Kd=cfg.num_depth_cams)
+
+
+# seed + rank of a run, mixed with a constant of its own: the cloud augmenter's generator must not repeat the image augmenter's
+CLOUD_AUGMENT_SEED_MIX = 0x636C6F7564
+
+
+def make_cloud_augment(config, policy, seed):
+    """the CloudAugment of a --augment_clouds run, sized from the policy's engine (max_points, max_batch), about the config's
+    cloud_pivot; None without the flag"""
+    if not config.get("augment_clouds"):
+        return None
+    from actmi.ops import CloudAugment
+    eng = policy.model
+    return CloudAugment(eng, eng.max_points, eng.max_batch, pivot=tuple(config.get("cloud_pivot") or (0.0, 0.0, 0.0)), seed=seed)
 
 
 def train_bc(train_dataloader, val_dataloader, config, log=None):
@@ -730,6 +752,9 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
     # --augment_images: one device pass over the TRAINING batches just before the stem.  Validation stays un-augmented, so that
     # validation losses of runs with and without the flag compare (the reference's validation set is augmented too: utils.py:153)
     augment = make_augment(config, policy, seed + rank)
+    # --augment_clouds: the same for the stored clouds of a use_pcd batch, training batches only for the same reason; its draws come
+    # from a generator of its own (another seed), so the two streams are independent
+    cloud_augment = make_cloud_augment(config, policy, (seed + rank) ^ CLOUD_AUGMENT_SEED_MIX)
     for step in range(num_steps + 1):
         if step % validate_every == 0:
             policy.eval()
@@ -778,7 +803,7 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
         policy.train()
         optimizer.zero_grad()
         data = next(train_dataloader)
-        forward_dict = forward_pass(data, policy, augment)
+        forward_dict = forward_pass(data, policy, augment, cloud_augment)
         loss = forward_dict["loss"]
         loss.backward()
         optimizer.step()
@@ -850,6 +875,14 @@ def build_config(args):
     if args.get("augment_images") and policy_class != "ACT":
         raise NotImplementedError("--augment_images: the device-side augmentation belongs to the ACT training path (Diffusion "
                                   "training is outside the accelerated path)")
+    if args.get("augment_clouds"):
+        if policy_class != "ACT":
+            raise NotImplementedError("--augment_clouds: the point-cloud token and its augmentation belong to the ACT training path")
+        if not args.get("use_pcd"):
+            raise ValueError("--augment_clouds augments the stored clouds of a --use_pcd run: there are none without --use_pcd")
+        pivot = args.get("cloud_pivot") or (0.0, 0.0, 0.0)
+        if len(pivot) != 3 or not all(np.isfinite(float(v)) for v in pivot):
+            raise ValueError(f"--cloud_pivot {pivot}: needs 3 finite numbers")
     config = {"num_steps": args["num_steps"], "eval_every": args["eval_every"], "validate_every": args["validate_every"],
             "save_every": args["save_every"], "ckpt_dir": args["ckpt_dir"], "resume_ckpt_path": args.get("resume_ckpt_path"),
             "episode_len": task_config["episode_len"], "state_dim": 14, "lr": args["lr"],
@@ -864,6 +897,9 @@ def build_config(args):
         config["pointcloud_names"] = list(task_config["pointcloud_names"])
     if args.get("augment_images"):
         config["augment_images"] = True
+    if args.get("augment_clouds"):
+        config["augment_clouds"] = True
+        config["cloud_pivot"] = [float(v) for v in (args.get("cloud_pivot") or (0.0, 0.0, 0.0))]
     if args.get("device_dataset"):
         if policy_class != "ACT":
             raise NotImplementedError("--device_dataset: the device-resident episode store feeds the ACT training path")
@@ -1030,6 +1066,13 @@ def make_parser():
                         help="ACT training only, opt-in: the reference dataset's augmentation (random 0.95 crop resized back, rotation "
                              "within 5 degrees, brightness / contrast / saturation jitter) on the device, for training batches; the "
                              "reference switches it on for Diffusion alone, which is outside this path")
+    parser.add_argument("--augment_clouds", action="store_true",
+                        help="ACT training with --use_pcd, opt-in: augment the stored clouds of the training batches on the device "
+                             "(yaw within 5 degrees about +z, 5 %% scale, 1 cm shift, 2 mm per-point jitter, a tenth of the points "
+                             "dropped, the colour jitter of --augment_images); composes with --augment_images, draws of its own")
+    parser.add_argument("--cloud_pivot", action="store", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"),
+                        help="--augment_clouds: the point of the clouds' frame the yaw and the scale are taken about (default: the "
+                             "base frame's origin)")
     parser.add_argument("--device_dataset", action="store_true",
                         help="ACT training from --dataset_dir, opt-in: read every episode once into device memory and gather the "
                              "training batches there (actmi.data.DeviceEpisodeStore): the same batches as the host loader, no loader "

@@ -760,6 +760,59 @@ typedef struct actmi_augment_desc {
 int64_t actmi_op_augment_workspace_bytes(int B, int K, int H, int W);
 int actmi_op_augment_u8(const actmi_augment_desc* d, void* stream);
 int actmi_op_warp_u16(const actmi_augment_desc* d, void* stream);
+/* ---- training-time point-cloud augmentation on the device (csrc/cloud_augment.hip): what actmi_op_augment_u8 is for the frames
+ * of a training batch, for the stored clouds of a use_pcd batch -- a yaw about +z, an isotropic scale about a pivot, a translation,
+ * a per-point uniform jitter, random point dropout and the colour jitter of the image op -- as one op over the padded [B][P][3]
+ * clouds and their valid counts.  The host draws; the device reads ONE 56-byte record per sample.  actmi.ops.cloud_augment_ref is
+ * this definition in numpy.
+ *
+ * Every fp32 operation below is rounded on its own, in the order the brackets give; nothing is contracted into an FMA.
+ * For sample b, n = clamp(counts[b], 1, P) -- the clamp of actmi_set_pointcloud_n; counts == NULL: n = P.  Rows at and behind n are
+ * never read, so they may hold anything, NaN included.  For row i < n, with seed = seed_lo | seed_hi << 32 and u_k = the
+ * actmi_u01 draw of csrc/dropout.h at (seed, 4*i + k) -- 24 bits in [0, 1):
+ *   geometry   d = p - pivot
+ *              rx = (d.x*cos) - (d.y*sin),  ry = (d.x*sin) + (d.y*cos),  rz = d.z
+ *              j_k = ((u_k + u_k) - 1) * jitter     for k = 0, 1, 2: uniform in [-jitter, jitter)
+ *              q = (((r * scale) + pivot) + t) + j   per coordinate
+ *   colour     three ops in the order the record names, each on the result of the one before (floats: nothing is truncated):
+ *              blend(a, b, r) = min(max((r*a) + ((1-r)*b), 0), 255),  gray = ((0.2989 r) + (0.587 g)) + (0.114 b)
+ *              brightness = blend(c, 0, fb);  saturation = blend(c, gray, fs);  contrast = blend(c, mean, fc), mean = the exact
+ *              INTEGER sum of trunc(clamp(gray, 0, 255)) over the sample's n rows (dropped ones too) as they stand when
+ *              contrast's turn comes, divided by n in double, rounded to fp32: it does not depend on arrival order.
+ *              min and max return the other operand when one is not a number.
+ *   dropout    row i is kept iff u_3 >= drop.  If no row of the sample is kept, row 0 is.
+ * `order` 0..5 indexes the permutation table of actmi_augment_record: 0 = brightness, 1 = contrast, 2 = saturation; out of range,
+ * it is held to 0..5.
+ * Output: the kept rows, transformed, in input order at the front of out_xyz[b] / out_rgb[b]; out_counts[b] = their number;
+ * every row at or behind it is zero in both outputs -- the finite padding actmi_set_pointcloud_n requires.
+ * The identity record (cos 1, sin 0, scale 1, t 0, jitter 0, drop 0, factors 1) with pivot 0 returns the valid rows value for
+ * value (-0.0 comes back as +0.0).
+ *
+ * One workgroup per sample walks the rows in tiles, twice (the grey sum, then the transform with a wave-level prefix for the stable
+ * compaction).  The op runs on one stream, allocates nothing, never synchronises and reads nothing on the host: capturable, and a
+ * captured launch sees the records and counts a stream-ordered copy wrote since.  Refused with a code and a message
+ * (actmi_op_last_error), nothing launched: a null pointer (counts may be NULL), a pointer off a 4-byte boundary, any output
+ * overlapping an input or another output, B < 1 or B > 65535, P < 1 or 3 * P beyond int32. */
+typedef struct actmi_cloud_augment_record {   /* the DEVICE record of one sample: 56 bytes */
+    float cos, sin;            /* yaw about +z of the cloud's frame; taken in double on the host, rounded to fp32 */
+    float scale;               /* isotropic, about the pivot */
+    float tx, ty, tz;          /* translation */
+    float jitter;              /* half width of the per-point, per-coordinate uniform jitter; 0 = none */
+    float drop;                /* a point is dropped when its draw is < drop; 0 = none */
+    float fb, fc, fs;          /* brightness, contrast, saturation factors */
+    int32_t order;             /* 0..5, the permutation table of actmi_augment_record */
+    uint32_t seed_lo, seed_hi; /* the sample's 64-bit seed for the per-point draws */
+} actmi_cloud_augment_record;
+typedef struct actmi_cloud_augment_desc {
+    const float *xyz, *rgb;                       /* [B][P][3] f32 */
+    const int32_t* counts;                        /* [B] on the device, or NULL = P everywhere */
+    const actmi_cloud_augment_record* records;    /* [B] on the device */
+    float *out_xyz, *out_rgb;                     /* [B][P][3], no overlap with the inputs */
+    int32_t* out_counts;                          /* [B] */
+    float pivot[3];
+    int32_t B, P;
+} actmi_cloud_augment_desc;
+int actmi_op_cloud_augment(const actmi_cloud_augment_desc* d, void* stream);
 /* ---- device-resident episode store: a training batch gathered on the device (csrc/episode_store.hip; actmi.data.DeviceEpisodeStore)
  * actmi_op_gather_frames: out is n_items contiguous items of item_bytes each; item i becomes the item_bytes bytes at
  * arena + src_off[i] (src_off [n_items] int64 ON THE DEVICE, 8-byte aligned; the same source may be named more than once).  One
