@@ -72,6 +72,7 @@ class ACTEngine:
         self._finalized = False
         self._fusion = None            # ops.RGBDFusion registered by set_rgbd_fusion: pointcloud={"depth": u16 frames} is fused on the device
         self._phase = 0
+        self.attention_out = None      # the tensor bound by bind_attention (kept alive here)
         # attributes imitate_episodes.py touches on policy.model
         self.num_queries = cfg.num_queries
         self.encoder = None if cfg.no_encoder else True
@@ -314,6 +315,36 @@ class ACTEngine:
                                      "(ACTMI_GEMM_PREC=f32)")
         return out
 
+    # ---- the decoder's cross-attention map ----------------------------------------------------
+    def attention_layout(self):
+        """The token order of the map's N columns (actmi_attention_layout) as an attention_maps.AttentionLayout."""
+        from .attention_maps import AttentionLayout
+        lay = L.AttnLayout()
+        L.check(self.lib.actmi_attention_layout(self.h, C.byref(lay)), self.h, "attention_layout")
+        return AttentionLayout(lay.Q, lay.N, lay.n_extra, lay.K, lay.Kd, lay.fh, lay.fw).check()
+
+    def bind_attention(self, buf):
+        """Bind a float32 [B, num_queries, num_tokens] device tensor (None: unbind).  While one is bound every forward_infer of
+        at most B samples leaves the decoder's head-averaged cross-attention weights of its samples in buf[:batch]
+        (actmi_bind_attention_out); a larger batch is refused.  The engine keeps the tensor alive.  a_hat does not depend on the
+        binding, and unbound the forward launches what it always did.  A captured graph (capture_infer) keeps the binding it was
+        captured with: binding or unbinding afterwards reaches eager forwards only -- capture again to change a graph, as with
+        set_rgbd_fusion's fusion, which a graph also takes in at capture.  forward_train ignores the binding."""
+        if buf is None:
+            L.check(self.lib.actmi_bind_attention_out(self.h, None, 0), self.h, "bind_attention_out")
+            self.attention_out = None
+            return
+        cfg = self.cfg
+        if not isinstance(buf, torch.Tensor) or not buf.is_cuda:
+            raise ValueError("the attention buffer must be a CUDA tensor on the engine's device")
+        self._check_dev(attention=buf)
+        if buf.dtype != torch.float32 or buf.dim() != 3 or tuple(buf.shape[1:]) != (cfg.num_queries, cfg.num_tokens) \
+                or buf.shape[0] < 1 or not buf.is_contiguous():
+            raise ValueError(f"the attention buffer must be a contiguous float32 [B, {cfg.num_queries}, {cfg.num_tokens}] tensor, "
+                             f"got {buf.dtype} {tuple(buf.shape)}")
+        L.check(self.lib.actmi_bind_attention_out(self.h, C.c_void_p(buf.data_ptr()), buf.shape[0]), self.h, "bind_attention_out")
+        self.attention_out = buf
+
     def set_forward_phase(self, phase: int):
         """0: forward_infer runs the whole step; 1: trunk + token assembly only; 2: transformer only (actmi_set_forward_phase)"""
         L.check(self.lib.actmi_set_forward_phase(self.h, int(phase)), self.h, "set_forward_phase")
@@ -321,7 +352,7 @@ class ACTEngine:
 
     def capture_infer(self, batch: int, image_dtype=torch.uint8, with_ensemble=None, statics=None, phase: int = 0,
                       num_points: int = None, depth_dtype=torch.float32, static_depth=None, static_cloud=None,
-                      fuse_depth: bool = False):
+                      fuse_depth: bool = False, attention: bool = False):
         """Capture one forward (optionally + the temporal-ensemble kernel) into a hipGraph and return
         ``replay(qpos, image) -> a_hat`` that copies into static inputs and replays.  A use_pcd engine captures static
         xyz / rgb buffers of ``num_points`` points (default max_points) and a static int32 counts buffer ``n`` (filled with
@@ -333,10 +364,15 @@ class ACTEngine:
         at small batch where the step is launch-bound).  ``fuse_depth=True`` (a use_pcd engine with a registered fusion,
         set_rgbd_fusion): the graph owns a static uint16 depth buffer [B, K, H, W] (``replay.static_cloud["depth"]``), the fusion
         op is captured ahead of the forward, and the graph replays ``replay(qpos, image, pointcloud={"depth": frames})``; the
-        fusion's parameter block and seed are read on the device, so set_extrinsics / set_seed between replays take effect."""
+        fusion's parameter block and seed are read on the device, so set_extrinsics / set_seed between replays take effect.
+        ``attention=True``: a static [batch, num_queries, num_tokens] buffer is bound (bind_attention) ahead of the warm-up and the
+        capture, stays bound afterwards as ``engine.attention_out`` (also ``replay.attention``), and holds the map of the last
+        replay.  A binding already in place at capture is captured likewise; one changed later does not reach this graph."""
         if not self._finalized:
             self.finalize()
         cfg, dev = self.cfg, self.device
+        if attention:
+            self.bind_attention(torch.zeros((batch, cfg.num_queries, cfg.num_tokens), dtype=torch.float32, device=dev))
         if fuse_depth:
             if not cfg.use_pcd or self._fusion is None:
                 raise ValueError("capture_infer(fuse_depth=True) needs a use_pcd engine with a registered fusion (set_rgbd_fusion)")
@@ -449,6 +485,7 @@ class ACTEngine:
         replay.static = (s_qpos, s_img, s_out)
         replay.static_cloud = s_cloud
         replay.static_depth = s_depth
+        replay.attention = self.attention_out
         return replay
 
     # ---- training -----------------------------------------------------------------------------

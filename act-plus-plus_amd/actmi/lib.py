@@ -86,6 +86,11 @@ class AttnDesc(C.Structure):
     ]
 
 
+class AttnLayout(C.Structure):
+    # actmi_attn_layout: the token order of the decoder's cross-attention map
+    _fields_ = [(k, C.c_int32) for k in ("Q", "N", "n_extra", "K", "Kd", "fh", "fw", "rgb0", "depth0")]
+
+
 RGBD_MAX_CAMS = 8
 
 
@@ -212,6 +217,10 @@ def load():
         "actmi_op_pow2_scale": ([vp, C.c_int64, i32, i32, vp, vp], i32),
         "actmi_op_splitk_combine": ([vp, i32, C.c_int64, C.c_int64, i32, i32, vp, vp, vp, C.c_int64, i32, vp, C.c_int64, vp], i32),
         "actmi_op_attention": ([C.POINTER(AttnDesc), vp], i32),
+        "actmi_op_attn_weights": ([C.POINTER(AttnDesc), vp, i64, i64, vp], i32),
+        "actmi_op_heat_overlay_u8": ([vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
+        "actmi_bind_attention_out": ([vp, vp, i32], i32),
+        "actmi_attention_layout": ([vp, C.POINTER(AttnLayout)], i32),
         "actmi_op_attention_bwd": ([C.POINTER(AttnBwdDesc), vp], i32),
         "actmi_op_layernorm": ([vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp], i32),
         "actmi_op_layernorm_ex": ([vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, C.c_uint32, i32, i32,

@@ -412,6 +412,99 @@ def attention(q, k, v, nheads, kpm=None, q_shared=False, want_lse=False, split=T
     return (out, lse) if want_lse else out
 
 
+def attention_weights(q, k, nheads, kpm=None, q_shared=False, prec=None, causal=False, out=None):
+    """Head-averaged softmax weights of ``attention`` on the same views (actmi_op_attn_weights): q [B,Nq,D] (or [Nq,D] when
+    q_shared), k [B,Nk,D] (row-strided views allowed) -> [B,Nq,Nk] float32, what nn.MultiheadAttention(need_weights=True)
+    returns beside its output.  out: a float32 tensor or view of that shape with last-dim stride 1 to write into."""
+    lib = L.load()
+    B, Nk, D = k.shape
+    Nq = q.shape[-2]
+    hd = D // nheads
+    if out is None:
+        out = torch.empty((B, Nq, Nk), dtype=torch.float32, device=k.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Nq, Nk) or out.stride(2) != 1 or out.device != k.device:
+        raise ValueError(f"out must be a float32 [{B}, {Nq}, {Nk}] tensor on {k.device} with last-dim stride 1")
+    d = L.AttnDesc()
+    d.Q, d.q_bs, d.q_rs = q.data_ptr(), (0 if q_shared else q.stride(0)), q.stride(-2)
+    d.K, d.k_bs, d.k_rs = k.data_ptr(), k.stride(0), k.stride(1)
+    if kpm is not None:
+        d.kpm, d.kpm_bs = kpm.data_ptr(), kpm.stride(0)
+    d.B, d.H, d.Nq, d.Nk, d.HD = B, nheads, Nq, Nk, hd
+    d.scale = 1.0 / (hd ** 0.5)
+    d.prec = PREC[prec]
+    d.causal = 1 if causal else 0
+    L.check(lib.actmi_op_attn_weights(C.byref(d), out.data_ptr(), out.stride(0), out.stride(1), L.current_stream_ptr()), None,
+            "op_attn_weights")
+    return out
+
+
+def heat_ramp():
+    """The fixed 256-entry colour table of the attention overlays, u8 [256, 3]: black - blue - magenta - orange - yellow -
+    white, piecewise linear between six anchors, built in numpy (no plotting library)."""
+    import numpy as np
+    anchors = np.array([[0, 0, 0], [20, 20, 160], [180, 30, 150], [250, 120, 30], [255, 230, 60], [255, 255, 255]], np.float64)
+    x = np.arange(256, dtype=np.float64) / 255.0 * (len(anchors) - 1)
+    i0 = np.minimum(x.astype(np.int64), len(anchors) - 2)
+    w = (x - i0)[:, None]
+    return np.floor(anchors[i0] * (1 - w) + anchors[i0 + 1] * w + 0.5).astype(np.uint8)
+
+
+def heat_overlay(frames, heat, lut, alpha=0.5):
+    """actmi_op_heat_overlay_u8: frames u8 [B,K,H,W,3] and heat f32 [B,K,fh,fw] (>= 0, finite) on one device, lut u8 [256,3]
+    (tensor or array), -> the blended frames, a new u8 tensor.  The arithmetic is defined in include/actmi.h."""
+    import numpy as np
+    lib = L.load()
+    if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous uint8 [B, K, H, W, 3] tensor")
+    B, K, H, W, _ = frames.shape
+    if heat.dtype != torch.float32 or heat.dim() != 4 or tuple(heat.shape[:2]) != (B, K) or not heat.is_contiguous() \
+            or heat.device != frames.device:
+        raise ValueError(f"heat must be a contiguous float32 [{B}, {K}, fh, fw] tensor on {frames.device}")
+    lut_t = torch.as_tensor(np.ascontiguousarray(lut) if isinstance(lut, np.ndarray) else lut)
+    if lut_t.dtype != torch.uint8 or tuple(lut_t.shape) != (256, 3):
+        raise ValueError("lut must be uint8 [256, 3]")
+    lut_t = lut_t.to(frames.device).contiguous()
+    out = torch.empty_like(frames)
+    ws = torch.empty(B, dtype=torch.float32, device=frames.device)
+    L.check(lib.actmi_op_heat_overlay_u8(frames.data_ptr(), heat.data_ptr(), lut_t.data_ptr(), float(alpha), out.data_ptr(),
+                                         ws.data_ptr(), B, K, H, W, heat.shape[2], heat.shape[3], L.current_stream_ptr()),
+            None, "op_heat_overlay_u8")
+    return out
+
+
+def heat_overlay_ref(frames, heat, lut, alpha=0.5):
+    """heat_overlay on the host, numpy float32 with one rounding per operation in the order include/actmi.h gives: the same
+    bytes as the device.  frames u8 [B,K,H,W,3], heat f32 [B,K,fh,fw], lut u8 [256,3] (arrays)."""
+    import numpy as np
+    f32 = np.float32
+    frames, heat, lut = np.asarray(frames), np.asarray(heat, dtype=f32), np.asarray(lut)
+    B, K, H, W, _ = frames.shape
+    fh, fw = heat.shape[2:]
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("alpha must lie in [0, 1]")
+    alpha = f32(alpha)
+
+    def taps(n_out, n_in):
+        scale = f32(n_in) / f32(n_out)
+        c = np.maximum((np.arange(n_out, dtype=f32) + f32(0.5)) * scale - f32(0.5), f32(0))
+        i0 = np.minimum(np.floor(c).astype(np.int64), n_in - 1)
+        return i0, np.minimum(i0 + 1, n_in - 1), (c - i0.astype(f32)).astype(f32)
+
+    y0, y1, wy = taps(H, fh)
+    x0, x1, wx = taps(W, fw)
+    m = np.maximum(heat.reshape(B, -1).max(1), f32(0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = np.where(m[:, None, None, None] > 0, heat / m[:, None, None, None], f32(0)).astype(f32)
+    wx_, wy_ = wx[None, None, None, :], wy[None, None, :, None]
+    t0 = g[:, :, y0][:, :, :, x0] * (f32(1) - wx_) + g[:, :, y0][:, :, :, x1] * wx_
+    t1 = g[:, :, y1][:, :, :, x0] * (f32(1) - wx_) + g[:, :, y1][:, :, :, x1] * wx_
+    gp = (t0 * (f32(1) - wy_) + t1 * wy_).astype(f32)                                   # [B, K, H, W]
+    idx = np.clip(np.floor(gp * f32(255) + f32(0.5)), 0, 255).astype(np.int64)
+    a = (alpha * gp)[..., None]
+    v = np.floor(frames.astype(f32) * (f32(1) - a) + lut[idx].astype(f32) * a + f32(0.5))
+    return np.clip(v, 0, 255).astype(np.uint8)
+
+
 def attention_bwd(q, k, v, o, lse, dout, nheads, kpm=None, drop_p=0.0, drop_seed=0, do_scale=None, want_amax=False, out=None,
                   amax_out=None):
     """dq, dk, dv of ``attention`` (f16x3, no materialised scores): q [B,Nq,D], k / v [B,Nk,D] (row-strided views allowed),

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "dropout.h"
 #include "split16.h"
+#include "attn_tile.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -23,32 +24,14 @@ namespace {
 // wave per SIMD hides the global latency instead (measured 136 -> 116 us on the encoder shape; with the prefetch kept,
 // three waves spill).
 constexpr bool ATTN_NOPF = true;
-constexpr int KT = 64;   // keys per LDS tile
 // f16x3 kernel: fixed power-of-two up-scales of q * scale * log2(e) and of v before their split (see the kernel's header)
-constexpr float Q_UP = 4.f, V_UP = 16.f;
+// (Q_UP: attn_tile.h)
+constexpr float V_UP = 16.f;
 
 // two packed half pairs -> the pair of their low halfs / of their high halfs, one v_perm_b32 each (selector bytes 0-3 name the bytes
 // of the second source, 4-7 those of the first)
 __device__ __forceinline__ uint32_t pack_lo16(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }   // (a & 0xffff) | (b << 16)
 __device__ __forceinline__ uint32_t pack_hi16(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }   // (a >> 16) | (b & 0xffff0000)
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
-// XCD-aware block order: the hardware deals consecutive block ids round-robin over the 8 XCDs (each with its own 4 MB L2), so
-// the query blocks of one (batch, head) -- which all stream the same K / V -- used to land on all eight and each L2 fetched
-// that K / V again (201 MB of fabric reads per encoder launch against 79 MB of operands, PMC round 3).  The bijective remap
-// gives every XCD a contiguous run of (batch, head, query block) triples, as gemm.hip does for its tiles.
-__device__ __forceinline__ void attn_block_coords(int& bx, int& by, int& bz) {
-    const int gx = gridDim.x, gy = gridDim.y;
-    const int total = gx * gy * (int)gridDim.z;
-    const int lin = ((int)blockIdx.z * gy + (int)blockIdx.y) * gx + (int)blockIdx.x;
-    const int xcd = lin & 7, q = total >> 3, r = total & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int flat = base + (lin >> 3);
-    bx = flat % gx;
-    const int rest = flat / gx;
-    by = rest % gy;
-    bz = rest / gy;
-}
 
 template <int HD>
 __global__ __launch_bounds__(256) void attn_f32_kernel(AttnArgs p, int nsplit, int chunk) {

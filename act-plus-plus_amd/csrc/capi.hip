@@ -78,6 +78,25 @@ int actmi_set_pointcloud_n(actmi_handle h, const float* xyz, const float* rgb, c
     return ACTMI_OK;
 }
 
+int actmi_bind_attention_out(actmi_handle h, float* w, int B) {
+    if (!h) return ACTMI_E_INVALID;
+    ENTER(h);
+    if (!w) { h->attn_out = nullptr; h->attn_out_B = 0; return ACTMI_OK; }
+    if (B < 1) return bad(h, "attention buffer of less than one sample");
+    if ((uintptr_t)w & 3) return bad(h, "attention buffer must be 4-byte aligned");
+    h->attn_out = w; h->attn_out_B = B;
+    return ACTMI_OK;
+}
+
+int actmi_attention_layout(actmi_handle h, actmi_attn_layout* out) {
+    if (!h || !out) return ACTMI_E_INVALID;
+    ENTER(h);
+    out->Q = h->cfg.num_queries; out->N = h->N; out->n_extra = h->n_extra;
+    out->K = h->cfg.num_cams; out->Kd = h->Cd; out->fh = h->fh; out->fw = h->fw;
+    out->rgb0 = h->n_extra; out->depth0 = h->n_extra + h->cfg.num_cams * h->fh * h->fw;
+    return ACTMI_OK;
+}
+
 int actmi_destroy(actmi_handle h) {
     if (!h) return 0;
     DevGuard g(h->device);
@@ -359,6 +378,18 @@ int actmi_op_attention(const actmi_attn_desc* d, void* stream) {
     if (!d) return ACTMI_E_INVALID;
     g_op_error.clear();
     return launch_attention(*d, S(stream), &g_op_error);
+}
+
+int actmi_op_attn_weights(const actmi_attn_desc* d, float* w, int64_t w_bs, int64_t w_rs, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "attn_weights: null descriptor"; return ACTMI_E_INVALID; }
+    return launch_attn_weights(*d, w, w_bs, w_rs, S(stream), &g_op_error);
+}
+
+int actmi_op_heat_overlay_u8(const uint8_t* frames, const float* heat, const uint8_t* lut, float alpha, uint8_t* out, float* ws,
+                             int B, int K, int H, int W, int fh, int fw, void* stream) {
+    g_op_error.clear();
+    return launch_heat_overlay(frames, heat, lut, alpha, out, ws, B, K, H, W, fh, fw, S(stream), &g_op_error);
 }
 
 int actmi_op_attention_bwd(const actmi_attn_bwd_desc* d, void* stream) {

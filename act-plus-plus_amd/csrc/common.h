@@ -167,6 +167,12 @@ int launch_layernorm(const float* x, const float* res, int res_mod, const float*
 // ---- attention (attn.hip) -----------------------------------------------------------------------
 typedef actmi_attn_desc AttnArgs;
 int launch_attention(const AttnArgs& a, hipStream_t st, std::string* err);
+// head-averaged probabilities of the same softmax (attn_weights.hip): w[b][i][j], batch / row strides w_bs / w_rs in floats.
+// Reads Q, K, kpm, scale, the sizes, prec and causal of `a`; returns an ACTMI_E_* code
+int launch_attn_weights(const AttnArgs& a, float* w, int64_t w_bs, int64_t w_rs, hipStream_t st, std::string* err);
+// heat [B][K][fh][fw] over frames u8 [B][K][H][W][3] through the colour table lut u8 [256][3] (heat_overlay.hip); ws: [B] floats
+int launch_heat_overlay(const uint8_t* frames, const float* heat, const uint8_t* lut, float alpha, uint8_t* out, float* ws, int B,
+                        int K, int H, int W, int fh, int fw, hipStream_t st, std::string* err);
 // attention backward without materialised scores (attn_bwd.hip): dQ, dK, dV from Q, K, V, dO, the forward's log-sum-exp and
 // delta[b][h][q] = dO[q] . O[q].  dO_scale (optional, device): the power of two dO is multiplied with on its way into fp16 pieces.
 struct AttnBwdArgs {

@@ -1162,6 +1162,7 @@ struct TView {
     float *X, *XP, *QKV, *ATT, *Y, *X1, *Hb, *dO, *dY, *dT2, *dH, *hs, *attn_ws;
     int64_t attn_ws_floats;
     int half;
+    int b0;            // first sample of the view
 };
 static TView make_view(const actmi_ctx* ctx, int b0, int nb, int half) {
     const actmi_config& g = ctx->cfg;
@@ -1174,6 +1175,7 @@ static TView make_view(const actmi_ctx* ctx, int b0, int nb, int half) {
     v.hs = ctx->hs + b0 * Q * D;
     v.attn_ws = ctx->attn_ws + b0 * ws_per; v.attn_ws_floats = (half < 0) ? ctx->attn_ws_floats : nb * ws_per;
     v.half = half;
+    v.b0 = b0;
     return v;
 }
 
@@ -1228,6 +1230,10 @@ int engine_decoder_infer(actmi_ctx* ctx, const TView& V, int B, float* a_hat, hi
     at.ws = V.attn_ws; at.ws_floats = V.attn_ws_floats;
     at.prec = ctx->gemm_prec;
     CHK(launch_attention(at, st, &ctx->err));
+    // the bound map (actmi_bind_attention_out): the head-averaged probabilities of the softmax just run, from the same operands;
+    // this view's samples write their own rows of the caller's buffer
+    if (ctx->attn_out)
+        CHK(launch_attn_weights(at, ctx->attn_out + (int64_t)V.b0 * Q * N, (int64_t)Q * N, N, st, &ctx->err));
     const int M = B * Q;
     GemmArgs op = linear_args(V.dO, D, M, D, d.cross.out_w, D, d.cross.out_b, V.dY, D);
     op.res = ctx->dec_t1; op.ldres = D; op.res_mod = 1;
@@ -1272,6 +1278,10 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
     if (fmt != ACTMI_IMG_U8_NHWC && fmt != ACTMI_IMG_F32_NCHW) { ctx->err = "bad image format"; return ACTMI_E_INVALID; }
     const actmi_config& g = ctx->cfg;
     const int D = g.hidden_dim, N = ctx->N;
+    if (ctx->attn_out && ctx->fwd_phase != 1 && ctx->attn_out_B < B) {     // (before anything is launched, and before a binding is consumed)
+        ctx->err = "the bound attention buffer holds " + std::to_string(ctx->attn_out_B) + " samples, the forward has " + std::to_string(B);
+        return ACTMI_E_STATE;
+    }
     const float *pc_xyz = nullptr, *pc_rgb = nullptr;
     const int* pc_n = nullptr;
     int pc_P = 0;

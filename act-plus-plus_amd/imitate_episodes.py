@@ -431,7 +431,8 @@ def _gather_rows_f64(local, counts):
 
 
 def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=None, episode_ensemble=None, align="train",
-              save_episode=True, verbose=True, action_error=None, vq_sampler=None, store=None, horizon=False, chunk_error=None):
+              save_episode=True, verbose=True, action_error=None, vq_sampler=None, store=None, horizon=False, chunk_error=None,
+              attention=False, attention_slots=None, attention_frames=False):
     """Open-loop replay evaluation on recorded episodes (the fork's eval_arm_gripper_depth.py:343-418 without its plots): the
     policy is queried on an episode's recorded observations, the chunks are ensembled over time (``temporal_agg``) or executed
     chunk by chunk, un-normalised, and compared with the recorded ``/action``.  Serves what ``eval_bc`` cannot roll out --
@@ -458,6 +459,15 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     entry the dataset trains that slot on under ``align="train"``; the rows are pooled over the episodes like the others and
     returned as ``result["horizon"] = {"mae": [Q][A], "rmse": [Q][A], "max": [Q][A], "mae_mean": [Q], "count": [Q]}``.  Without
     ``horizon`` the result and the files have no such key.
+    ``attention`` (``--replay_attention``): one [batch, Q, N] buffer is bound to the policy's engine for the replay's queries
+    (ACTEngine.bind_attention), so every query also leaves the decoder's cross-attention map, which is cut by the engine's token
+    layout on the device (actmi.attention_maps.split_attention; ``attention_slots = (q0, q1)``: the mean over those action slots,
+    default all).  Per episode i the rank that replayed it writes replay_<ckpt>_ep<i>_attn.npz -- ``rgb`` [S, K, fh, fw], ``depth``
+    [S, Kd, fh, fw], ``extra`` [S, n_extra], ``share`` [S, n_sources] (float32, one row per queried step), ``steps`` [S] and
+    ``sources`` (the names of share's columns) -- and ``result["attention"] = {"sources", "share_mean", "slots", "steps"}`` pools
+    the share over all queried steps (sums divided by the count).  ``attention_frames``: also the queried steps' uint8 frames
+    with the RGB maps laid over them (ops.heat_overlay with ops.heat_ramp) as replay_<ckpt>_ep<i>_attn_frames.npy
+    [S, K, H, W, 3].  The queries, and with them every error figure, are the same bits with or without it.
     Returns {"episodes": [...], "mae": [A], "rmse": [A], "max": [A], "mae_mean", "rmse_mean", "max_max", "steps", ...} in
     action units; with ``save_episode`` rank 0 writes replay_<ckpt>.json and per episode replay_<ckpt>_ep<i>.npz (pred, target)."""
     import json
@@ -497,6 +507,17 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     if horizon and chunk_error is None:
         from actmi import ops
         chunk_error = ops.chunk_error
+    attn = None
+    if attention_frames and not attention:
+        raise ValueError("replay_bc: attention_frames overlays the attention maps: it needs attention=True")
+    if attention:
+        from actmi import ops
+        from actmi.attention_maps import check_slots, source_names, split_attention
+        if engine is None or not hasattr(engine, "bind_attention"):
+            raise ValueError("replay_bc(attention=True) needs an ACT policy on the engine (policy.model.bind_attention)")
+        layout = engine.attention_layout()
+        attn = {"layout": layout, "slots": check_slots(layout, attention_slots), "lut": ops.heat_ramp(),
+                "sources": source_names(layout, camera_names, policy_config.get("depth_camera_names") if use_depth else None)}
     dataset_dir = config.get("dataset_dir")
     if store is not None:
         if use_pcd:
@@ -529,9 +550,14 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     if mean.shape[0] != A or std.shape[0] != A:
         raise ValueError(f"the dataset statistics hold {mean.shape[0]} action components, the policy's action_dim is {A}")
 
-    local_rows, local_pt, local_hz = [], [], []
+    local_rows, local_pt, local_hz, local_share = [], [], [], []
     time0, n_frames = time.time(), 0
     stride = 1 if temporal_agg else Q
+    stem = "replay_" + ckpt_name.split(".")[0] if save_episode else None          # (a periodic replay saves nothing and has no name)
+    if attn is not None:
+        attn_before = engine.attention_out
+        attn_buf = torch.empty((batch, layout.Q, layout.N), dtype=torch.float32, device=dev)
+        engine.bind_attention(attn_buf)
     for i in range(lo, hi):
         if store is not None:
             ep = DeviceEpisodeReplay(store, ids[i], batch, stride=stride)
@@ -548,11 +574,29 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
         # the chunk of replayed step s: row s of the table (temporal_agg: s = t, every frame; else s = t // Q)
         table = torch.zeros((1, len(ep.steps), Q, A), dtype=torch.float32, device=dev)
         s0 = 0
+        ep_maps, ep_frames = [], []
         for data in (ep if store is not None else DevicePrefetcher(ep, device=dev if on_gpu else None)):
             a_hat = _replay_query(policy, data, use_depth, use_pcd, vq_sampler)
             table[0, s0:s0 + a_hat.shape[0]] = a_hat
+            if attn is not None:
+                m = split_attention(attn_buf[:a_hat.shape[0]], layout, attn["slots"])
+                ep_maps.append({k: m[k].cpu() for k in ("rgb", "depth", "extra", "share")})
+                if attention_frames:
+                    if data[0].dtype != torch.uint8:
+                        raise NotImplementedError("replay_bc(attention_frames=True) overlays the raw uint8 frames of a batch")
+                    ep_frames.append(ops.heat_overlay(data[0].contiguous(), m["rgb"].contiguous(), attn["lut"], 0.5).cpu())
             s0 += a_hat.shape[0]
         n_frames += s0
+        if attn is not None:
+            maps = {k: torch.cat([m[k] for m in ep_maps], dim=0).numpy() for k in ("rgb", "depth", "extra", "share")}
+            local_share.append(torch.cat([torch.tensor([float(s0)], dtype=torch.float64),
+                                          torch.from_numpy(maps["share"]).to(torch.float64).sum(0)])[None])
+            if save_episode:                                     # (every rank writes the episodes it replayed)
+                os.makedirs(ckpt_dir, exist_ok=True)
+                np.savez(os.path.join(ckpt_dir, f"{stem}_ep{i}_attn.npz"), steps=np.asarray(ep.steps, dtype=np.int64),
+                         sources=np.asarray(attn["sources"]), **maps)
+                if attention_frames:
+                    np.save(os.path.join(ckpt_dir, f"{stem}_ep{i}_attn_frames.npy"), torch.cat(ep_frames, dim=0).numpy())
         if temporal_agg:
             raw = torch.as_tensor(episode_ensemble(table, None, 0.01)).to(torch.float64)            # [1, T, A]
         else:
@@ -572,6 +616,8 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
                                        target[0].to(torch.float64).cpu()], dim=1))
         if engine is not None and hasattr(engine, "check_flags") and on_gpu:
             engine.check_flags()
+    if attn is not None:
+        engine.bind_attention(attn_before)
     if verbose and n_frames:
         print(f"rank {rank}: replayed episodes {lo}..{hi - 1}, {n_frames} queries in batches of {batch}, "
               f"{n_frames / max(time.time() - time0, 1e-9):.1f} frames/s")
@@ -584,6 +630,13 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     if horizon:
         mine = torch.cat(local_hz, dim=0) if local_hz else torch.zeros((0, Q * (1 + 3 * A)), dtype=torch.float64)
         result["horizon"] = horizon_metrics(_gather_rows_f64(mine, [b - a for a, b in spans]).numpy(), Q, A)
+    if attn is not None:
+        ns = layout.n_sources
+        mine = torch.cat(local_share, dim=0) if local_share else torch.zeros((0, 1 + ns), dtype=torch.float64)
+        sh = _gather_rows_f64(mine, [b - a for a, b in spans]).numpy()
+        count = float(sh[:, 0].sum())
+        result["attention"] = {"sources": attn["sources"], "share_mean": (sh[:, 1:].sum(0) / max(count, 1.0)).tolist(),
+                               "slots": list(attn["slots"]), "steps": int(count)}
     if save_episode:
         Ts = rows[:, 0].astype(np.int64)
         per_rank = [int(Ts[a:b].sum()) for a, b in spans]
@@ -591,7 +644,6 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
         allpt = _gather_rows_f64(mine, per_rank).numpy()
         if rank == 0:
             os.makedirs(ckpt_dir, exist_ok=True)
-            stem = "replay_" + ckpt_name.split(".")[0]
             off = 0
             for i, T in enumerate(Ts):
                 np.savez(os.path.join(ckpt_dir, f"{stem}_ep{i}.npz"), pred=allpt[off:off + T, :A],
@@ -611,6 +663,11 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
             for j in horizon_slots(Q):
                 print(f"slot {j:4d}: MAE {hz['mae_mean'][j]:10.5f} over the joints, {hz['count'][j]} pairs "
                       f"(the action {j} steps ahead of the query)")
+        if attn is not None:
+            at = result["attention"]
+            print(f"attention share per source, action slots {at['slots'][0]}..{at['slots'][1] - 1}, mean over {at['steps']} queries:")
+            for name, v in zip(at["sources"], at["share_mean"]):
+                print(f"{name:>20s} {v:8.4f}")
     return result
 
 
@@ -928,6 +985,22 @@ def build_config(args):
                              "--device_dataset")
         config.update(replay_every=int(args["replay_every"]), replay_episodes=args.get("replay_episodes"),
                       replay_align=args.get("replay_align") or "train", replay_horizon=bool(args.get("replay_horizon")))
+    if args.get("replay_attention_slots") is not None and not args.get("replay_attention"):
+        raise ValueError("--replay_attention_slots selects the action slots of --replay_attention")
+    if args.get("replay_attention_frames") and not args.get("replay_attention"):
+        raise ValueError("--replay_attention_frames overlays the maps of --replay_attention")
+    if args.get("replay_attention"):
+        if not (args.get("eval") and args.get("replay")):
+            raise ValueError("--replay_attention records the attention maps of an open-loop replay: it needs --eval --replay")
+        if policy_class != "ACT":
+            raise NotImplementedError("--replay_attention: the cross-attention map belongs to the ACT policy's decoder")
+        slots = args.get("replay_attention_slots")
+        if slots is not None:
+            slots = [int(s) for s in slots]
+            if len(slots) != 2 or not 0 <= slots[0] < slots[1] <= int(args["chunk_size"]):
+                raise ValueError(f"--replay_attention_slots {slots}: needs 0 <= Q0 < Q1 <= chunk_size {args['chunk_size']}")
+        config.update(replay_attention=True, replay_attention_slots=slots,
+                      replay_attention_frames=bool(args.get("replay_attention_frames")))
     return config
 
 
@@ -943,7 +1016,9 @@ def main(args):
         # open-loop replay on recorded episodes: what a use_depth / use_pcd policy (no simulator renders its inputs) and a policy
         # trained on real-robot episodes can be evaluated with
         return replay_bc(config, "policy_last.ckpt", episodes=args.get("replay_episodes"),
-                         align=args.get("replay_align") or "train", save_episode=True, horizon=bool(args.get("replay_horizon")))
+                         align=args.get("replay_align") or "train", save_episode=True, horizon=bool(args.get("replay_horizon")),
+                         attention=bool(config.get("replay_attention")), attention_slots=config.get("replay_attention_slots"),
+                         attention_frames=bool(config.get("replay_attention_frames")))
     if args["eval"]:
         results = []
         for ckpt_name in ["policy_last.ckpt"]:
@@ -1059,6 +1134,13 @@ def make_parser():
                         help="ACT training with --device_dataset: every N steps replay the validation episodes (at most "
                              "--replay_episodes, aligned by --replay_align) open loop out of the device-resident store; the figures "
                              "go to replay_history.json, the weights with the lowest mean MAE to policy_best_replay.ckpt (0: off)")
+    parser.add_argument("--replay_attention", action="store_true",
+                        help="--eval --replay: also record the decoder's cross-attention map of every query, cut per camera and "
+                             "source (replay_<ckpt>_ep<i>_attn.npz), and print / log the attention share per source")
+    parser.add_argument("--replay_attention_slots", action="store", type=int, nargs=2, default=None, metavar=("Q0", "Q1"),
+                        help="--replay_attention: the mean over the action slots Q0 .. Q1-1 of a chunk (default: all)")
+    parser.add_argument("--replay_attention_frames", action="store_true",
+                        help="--replay_attention: also write the queried frames with the maps laid over them (..._attn_frames.npy)")
     parser.add_argument("--replay_horizon", action="store_true",
                         help="--replay_every and --eval --replay: also the error of slot j of a predicted chunk against the action j "
                              "steps ahead (how the error grows along the chunk)")

@@ -120,8 +120,29 @@ class ACTPolicy:
         # inference: ImageNet normalisation (policy.py:268-272) is fused into the conv1 loader
         return self.model.forward_infer(qpos, image, vq_sample=vq_sample, pointcloud=pointcloud, depth_img=depth_img)
 
+    def attention(self, qpos, image, depth_img=None, pointcloud=None, slots=None, vq_sample=None):
+        """One inference query that also says what the policy looked at: -> (a_hat, maps).  maps["tokens"] [B, Q, N] is the
+        decoder's head-averaged cross-attention (the reference's nn.MultiheadAttention computes and discards it); "rgb"
+        [B, K, fh, fw], "depth" [B, Kd, fh, fw] and "extra" [B, n_extra] are its mean over the query slots ``slots = (q0, q1)``
+        (default all) cut by the engine's token layout, and "share" [B, n_extra + K + Kd] the attention mass per source (latent,
+        proprio, (cloud), every RGB camera, every depth camera; rows sum to 1) -- all device tensors.  The buffer is bound for
+        this query only; an earlier binding of the engine is put back afterwards."""
+        from actmi.attention_maps import split_attention, check_slots
+        eng = self.model
+        layout = eng.attention_layout()
+        check_slots(layout, slots)                              # (before anything runs)
+        B = qpos.shape[0]
+        buf = torch.empty((B, layout.Q, layout.N), dtype=torch.float32, device=eng.device)
+        before = eng.attention_out
+        eng.bind_attention(buf)
+        try:
+            a_hat = self(qpos, image, vq_sample=vq_sample, depth_img=depth_img, pointcloud=pointcloud)
+        finally:
+            eng.bind_attention(before)
+        return a_hat, split_attention(buf, layout, slots)
+
     def set_rgbd_fusion(self, fusion):
-        """register an actmi.ops.RGBDFusion: ``pointcloud={"depth": uint16 frames}`` is then fused into the cloud on the device
+        """register an actmi.ops.RGBDFusion:``pointcloud={"depth": uint16 frames}`` is then fused into the cloud on the device
         (ACTEngine.set_rgbd_fusion); the reference builds it in a host-side node (jie_aloha_scripts/pcd_fusion.py).  A fusion made
         with sampling="fps" downsamples by farthest-point sampling, as that node does under --use_fps"""
         self.model.set_rgbd_fusion(fusion)

@@ -311,6 +311,40 @@ int actmi_set_forward_phase(actmi_handle h, int phase);
 int actmi_forward_infer_vq(actmi_handle h, const float* qpos, const void* image, int image_fmt, int B,
                            const float* vq_sample, float* a_hat, void* stream);
 
+/* ---- the decoder's cross-attention map: what the policy reads of its observation ------------------------------------
+ * Only decoder layer 0 reaches the action head (the hs[0] quirk), so the head-averaged weights of its one cross-attention --
+ * w [B][Q][N], what nn.MultiheadAttention(need_weights=True) would return at transformer.py:286-289 and the reference discards
+ * -- are the policy's whole read of its N memory tokens by its Q = num_queries action slots.
+ *
+ * actmi_bind_attention_out: w is a device buffer [B][Q][N] f32 (NULL unbinds).  While one is bound, every forward that runs the
+ * inference decoder -- actmi_forward_infer and actmi_forward_infer_vq (one function behind both), whole or phase 2 -- launches
+ * actmi_op_attn_weights right after its attention launch, on the constant decoder queries ([Q][D], batch stride 0) and the K
+ * columns of the packed [B*N][2D] K|V buffer that launch read, in the handle's precision.  With the batch split over concurrent
+ * branches (the default for B >= 2) every branch writes the rows of its own samples; the bits are those of the un-split run
+ * (ACTMI_CAM_PIPE=0), a sample's map depending on nothing but that sample.  Rows [batch, B) of w are left alone.
+ * B is the capacity of w in samples: a forward of a larger batch returns ACTMI_E_STATE before it launches anything (and before
+ * it consumes a cloud or depth binding).  The binding persists until replaced or unbound; w must stay valid that long.
+ * Unbound (the default) the forward launches exactly what it launched before this entry existed and allocates nothing for it:
+ * same kernels, same bits.  a_hat does not depend on the binding either way.
+ * Graph capture: the binding is read on the host when the forward is enqueued, so a buffer bound before the capture is written
+ * by every replay of that graph, and a bind or unbind made after the capture does not reach the captured graph (capture again
+ * to change it) -- the same rule as any other argument of the captured forward.
+ * actmi_forward_train ignores the binding: the training decoder is a separate path (per-sample queries, dropout), not queried.
+ *
+ * actmi_attention_layout: the token order of the N columns, so that callers never restate it:
+ *   [latent, proprio, (pcl), rgb (h, cam, w) ..., depth (h, cam, w) ...],  N = n_extra + (K + Kd) * fh * fw
+ *   RGB token of camera k at grid (y, x):    rgb0   + (y * K  + k) * fw + x,   rgb0   = n_extra
+ *   depth token of camera k at grid (y, x):  depth0 + (y * Kd + k) * fw + x,   depth0 = n_extra + K * fh * fw */
+typedef struct actmi_attn_layout {
+    int32_t Q, N;              /* action slots (num_queries), memory tokens */
+    int32_t n_extra;           /* tokens in front of the image tokens: 2, or 3 with a point-cloud branch */
+    int32_t K, Kd;             /* RGB cameras, depth cameras (0 without a depth config) */
+    int32_t fh, fw;            /* layer4 grid of one camera */
+    int32_t rgb0, depth0;      /* first RGB token, first depth token (== N when Kd == 0) */
+} actmi_attn_layout;
+int actmi_bind_attention_out(actmi_handle h, float* w, int B);
+int actmi_attention_layout(actmi_handle h, actmi_attn_layout* out);
+
 /* ---- training: ACTPolicy.__call__(qpos, image, actions, is_pad) -> {l1, kl, loss} (policy.py:288-320) -- */
 int actmi_forward_train(actmi_handle h, const float* qpos, const void* image, int image_fmt,
                         const float* actions /*[B][Q][A]*/, const uint8_t* is_pad /*[B][Q]*/,
@@ -401,6 +435,40 @@ int actmi_op_splitk_combine(const float* part, int nsplit, int64_t split_stride,
 int actmi_op_sample_onehot(const float* logits, int n, int V, float temperature, uint64_t seed, float* probs, float* code,
                            void* stream);
 int actmi_op_attention(const actmi_attn_desc* d, void* stream);
+/* Head-averaged attention probabilities of the softmax actmi_op_attention runs on the same descriptor:
+ *   w[b][i][j] = (1/H) sum_h softmax_j(scale * q_{b,h,i} . k_{b,h,j} [+ key padding mask] [+ causal mask]),
+ * nn.MultiheadAttention(need_weights=True, average_attn_weights=True)'s second result.  w: device f32, element (b, i, j) at
+ * w + b * w_bs + i * w_rs + j (strides in floats; w_rs >= Nk, and for B > 1 w_bs >= (Nq - 1) * w_rs + Nk; 4-byte aligned);
+ * floats of w outside the [Nq][Nk] blocks are not touched.  Read from d: Q / K with their strides (multiples of 4 floats,
+ * 16-byte aligned; q_bs = 0 shares the queries), kpm, scale, B, H, Nq, Nk, HD, prec, causal.  V, O, lse and ws are ignored
+ * (there is no split over the keys); drop_p must be 0 (ACTMI_E_INVALID): the map is the softmax before the weight dropout.
+ * HD is 16, 32 or 64 as for actmi_op_attention, H at most 64, else ACTMI_E_SHAPE like a bad stride or alignment; a null
+ * pointer or a size below 1 is ACTMI_E_INVALID.  No refused call launches anything.
+ * Arithmetic (csrc/attn_weights.hip): the scores are formed again by the forward's own products for d->prec -- fp32 MFMA on
+ * q * scale * log2(e), or under f16x3 the three fp16 MFMA products of the exact hi / lo pieces of k and of
+ * q * scale * log2(e) * 4 -- so the map is the softmax the forward used up to the order of the row sum.  Two passes over the
+ * keys (row maximum and sum, then p = 2^(s - max) * (1 / sum)); the heads are summed in one register in head order and divided
+ * by H once.  One workgroup owns 32 query rows of a sample over all heads and keys, nothing is accumulated atomically: two
+ * launches give the same bits.
+ * A masked key gets exactly 0.0f.  A row whose every key is masked is NaN in all its Nk entries -- 0 * (1 / 0), as
+ * actmi_op_attention's output row of such a query is NaN (0 / 0) and as torch's is. */
+int actmi_op_attn_weights(const actmi_attn_desc* d, float* w, int64_t w_bs, int64_t w_rs, void* stream);
+/* A coarse heat map shown on the frames it belongs to (csrc/heat_overlay.hip): frames u8 [B][K][H][W][3], heat f32
+ * [B][K][fh][fw] (finite, >= 0: an attention map split by actmi_attention_layout), lut u8 [256][3] a caller-supplied colour
+ * table, 0 <= alpha <= 1, out u8 like frames (another buffer: it must not overlap frames), ws [B] floats of scratch.  Two launches: every sample's
+ * maximum over ALL its cameras, m_b = max(0, max heat[b]), then the blend.  Per pixel (i, j) of camera k, every fp32
+ * operation rounded on its own, in this order (sy = f32(fh) / f32(H), sx = f32(fw) / f32(W)):
+ *   g(y, x)  = heat[b][k][y][x] / m_b, or 0 when m_b == 0
+ *   cy = max((i + 0.5) * sy - 0.5, 0), y0 = min(floor(cy), fh - 1), y1 = min(y0 + 1, fh - 1), wy = cy - y0; likewise x0, x1, wx
+ *       (half-pixel centres with edge clamp: F.interpolate(mode="bilinear", align_corners=False))
+ *   t0 = g(y0,x0) * (1 - wx) + g(y0,x1) * wx, t1 = g(y1,x0) * (1 - wx) + g(y1,x1) * wx, g = t0 * (1 - wy) + t1 * wy
+ *   idx = clamp(floor(g * 255 + 0.5), 0, 255), a = alpha * g
+ *   out_c = clamp(floor(frame_c * (1 - a) + lut[idx][c] * a + 0.5), 0, 255)
+ * actmi.ops.heat_overlay_ref restates this in numpy and gives the same bytes.  16-byte loads and stores where W * 3 is a
+ * multiple of 16 and frames / out are 16-byte aligned, single bytes otherwise.  A null pointer, a size below 1 or an alpha
+ * outside [0, 1] is ACTMI_E_INVALID and launches nothing. */
+int actmi_op_heat_overlay_u8(const uint8_t* frames, const float* heat, const uint8_t* lut, float alpha, uint8_t* out, float* ws,
+                             int B, int K, int H, int W, int fh, int fw, void* stream);
 /* Attention backward without materialised scores (training step, long sequences; csrc/attn_bwd.hip): dq / dk / dv of
  * out = softmax(scale * q k^T [+ key padding mask]) v per (batch, head), from the forward's operands, its output `o`, its
  * log-sum-exp `lse` [B][H][Nq] (actmi_attn_desc.lse) and the output gradient `d_o`.  q / k / v / dq / dk / dv are addressed by
