@@ -42,7 +42,12 @@ Differences, all on the host side of the step:
   instead of stored.  Two deviations from the reference's files: the twin is the exact mirror image (the script re-encodes every
   mirrored frame as JPEG at quality 50) and its rows are float32.  Depth cameras, which the reference does not mirror, follow
   their RGB camera.  In a ``DeviceEpisodeStore`` a twin shares its source's frames: ``actmi_op_gather_frames_mirror`` flips them
-  inside the batch's gather."""
+  inside the batch's gather;
+* ``load_data(..., device_clouds=True)`` (with ``device_dataset`` and ``use_pcd``, opt-in) puts the stored clouds into the store as
+  well: the device loaders then deliver ``collate_pcd``'s 7-tuples, the clouds gathered by ``actmi_op_gather_clouds``; and a stored
+  cloud gets a **mirror rule** (``MirrorTwinPath(..., cloud_mirror=(axis, offset))``, ``load_data(..., cloud_mirror=...)``: one
+  coordinate reflected across a plane of the clouds' frame), with which ``mirror_twins`` and ``use_pcd`` go together, on the host
+  loader and in the store alike."""
 import fnmatch
 import os
 
@@ -160,17 +165,74 @@ class MirrorTwinPath(str):
     (where postprocess_episodes.py writes the twin, so filters, sorting and printing treat it like that file) and which carries
     ``.source`` (the file it is the image of), ``.spec`` (a ``MirrorSpec``, or None: the reference's rule for the cameras the file
     holds) and ``.depth_follows`` (depth camera -> the RGB camera whose swap and flip it shares; None: the camera of its own
-    name).  ``open_episode`` gives a view of the source file; nothing is written."""
+    name) and ``.cloud_mirror`` (``(axis, offset)``: the twin's stored point clouds are the source's reflected across the plane
+    ``x[axis] = offset`` of the clouds' frame, ``cloud_mirror_rule``; None: the twin holds no clouds).  ``open_episode`` gives a view
+    of the source file; nothing is written."""
 
-    def __new__(cls, source, spec=None, depth_follows=None):
+    def __new__(cls, source, spec=None, depth_follows=None, cloud_mirror=None):
         source = str(source)
         self = super().__new__(cls, os.path.join(os.path.dirname(source), "mirror_" + os.path.basename(source)))
         self.source, self.spec = source, spec
         self.depth_follows = dict(depth_follows) if depth_follows else None
+        self.cloud_mirror = None if cloud_mirror is None else cloud_mirror_rule(cloud_mirror)[:2]
         return self
 
     def __reduce__(self):                                        # loader workers receive the dataset pickled
-        return (MirrorTwinPath, (self.source, self.spec, self.depth_follows))
+        return (MirrorTwinPath, (self.source, self.spec, self.depth_follows, self.cloud_mirror))
+
+
+def cloud_mirror_rule(cloud_mirror):
+    """``(axis, offset)`` checked -> (axis 0..2, offset as a float, c2 = float32(2 * offset)).  The mirror image of a stored cloud:
+    ``xyz[..., axis] -> c2 - xyz[..., axis]`` over EVERY stored row (the recorder's zero rows too), one float32 subtract; colours
+    and ``padding_mask`` are unchanged."""
+    try:
+        axis, offset = cloud_mirror
+        axis = {"x": 0, "y": 1, "z": 2}.get(axis, axis)
+        ok = int(axis) == axis and 0 <= int(axis) <= 2 and bool(np.isfinite(float(offset)))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"cloud_mirror must be (axis 0..2 or 'x' / 'y' / 'z', a finite offset), got {cloud_mirror!r}")
+    with np.errstate(over="ignore"):
+        c2 = np.float32(2.0 * float(offset))
+    if not np.isfinite(c2):
+        raise ValueError(f"cloud_mirror: 2 * offset {offset!r} is not a finite float32")
+    return int(axis), float(offset), c2
+
+
+def mirror_cloud_xyz(xyz, cloud_mirror):
+    """the xyz rows of a twin's cloud: float32, coordinate ``axis`` of every row reflected (``cloud_mirror_rule``)"""
+    axis, _offset, c2 = cloud_mirror_rule(cloud_mirror)
+    out = np.array(xyz, dtype=np.float32)                        # a copy, float32 as the dataset converts
+    if out.ndim < 1 or out.shape[-1] != 3:
+        raise ValueError(f"a point cloud's xyz ends in 3 coordinates, got {out.shape}")
+    out[..., axis] = c2 - out[..., axis]
+    return out
+
+
+class _MirrorCloud:
+    """the xyz entry of a twin's cloud: the source entry, read where it is indexed and reflected there"""
+
+    def __init__(self, entry, cloud_mirror):
+        self._entry, self._rule = entry, cloud_mirror
+
+    def __getitem__(self, sel):
+        return mirror_cloud_xyz(self._entry[sel], self._rule)
+
+    def __array__(self, dtype=None, copy=None):
+        a = self[()]
+        return a if dtype is None else a.astype(dtype)
+
+    def __len__(self):
+        return int(self._entry.shape[0])
+
+    @property
+    def shape(self):
+        return tuple(int(v) for v in self._entry.shape)
+
+    @property
+    def dtype(self):
+        return np.dtype(np.float32)
 
 
 class _MirrorFrames:
@@ -218,7 +280,7 @@ class _MirrorEpisode:
     with float32 rows; depth cameras follow their RGB camera.  ``attrs``: the source's without ``compress``."""
 
     STATE_KEYS = ("/observations/qpos", "/observations/qvel", "/action")
-    IMG, DEPTH = "/observations/images/", "/observations/depth_images/"
+    IMG, DEPTH, PCD = "/observations/images/", "/observations/depth_images/", "/observations/pointcloud/"
 
     def __init__(self, twin):
         self.path, self.source = twin, twin.source
@@ -229,6 +291,7 @@ class _MirrorEpisode:
             self.cameras = self._names(self.IMG)
             self.spec = twin.spec if twin.spec is not None else MirrorSpec.from_camera_names(self.cameras)
             self.depth_follows = twin.depth_follows or {}
+            self.cloud_mirror = getattr(twin, "cloud_mirror", None)
             back = {}
             for d in self._names(self.DEPTH):
                 rgb = self.depth_follows.get(d, d)
@@ -265,6 +328,12 @@ class _MirrorEpisode:
                 raise ValueError(f"{self.path}: depth camera {cam} follows {rgb}, whose mirror image is {src_rgb}: no depth camera "
                                  f"follows that one")
             return ("frames", self.DEPTH + src, self.spec.flips(rgb)) if key in self._root and self.DEPTH + src in self._root else None
+        if key.startswith(self.PCD) and self.cloud_mirror is not None and key in self._root:
+            leaf = key.rsplit("/", 1)[1]                           # a twin without a cloud rule holds no clouds
+            if leaf == "xyz":
+                return ("cloud", key, False)
+            if leaf in ("rgb", "padding_mask"):
+                return ("same", key, False)
         return None
 
     def __contains__(self, key):
@@ -272,7 +341,11 @@ class _MirrorEpisode:
 
     def keys(self):
         names = [k for k in self.STATE_KEYS + ("/base_action",) if k in self]
-        return names + [self.IMG + c for c in self.cameras] + [self.DEPTH + d for d in self._names(self.DEPTH)]
+        clouds = []                                               # an .npz lists <name>/<leaf>, an HDF5 group its <name>s
+        for k in self._names(self.PCD):
+            leaves = [k] if "/" in k else [f"{k}/{leaf}" for leaf in ("xyz", "rgb", "padding_mask")]
+            clouds += [self.PCD + c for c in leaves if self.PCD + c in self]
+        return names + [self.IMG + c for c in self.cameras] + [self.DEPTH + d for d in self._names(self.DEPTH)] + clouds
 
     def __getitem__(self, key):
         r = self._resolve(key)
@@ -283,6 +356,10 @@ class _MirrorEpisode:
             return self.spec.mirror_state(self._root[src][()], f"{self.path}: {key}")
         if kind == "base":
             return self.spec.mirror_base(self._root[src][()], f"{self.path}: {key}")
+        if kind == "cloud":
+            return _MirrorCloud(self._root[src], self.cloud_mirror)
+        if kind == "same":
+            return self._root[src]
         return _MirrorFrames(self._root[src], flip, self._compressed)
 
     def meta(self, key):
@@ -292,6 +369,8 @@ class _MirrorEpisode:
             raise KeyError(f"{self.path}: a mirror twin holds no {key}")
         kind, src, _flip = r
         shape, dtype = _entry_meta(self._root, src)
+        if kind == "same":
+            return shape, dtype
         if kind != "frames":
             return shape, np.dtype(np.float32)
         if self._compressed:
@@ -306,10 +385,10 @@ class _MirrorEpisode:
         return False
 
 
-def mirror_twin_paths(files, spec=None, depth_follows=None):
+def mirror_twin_paths(files, spec=None, depth_follows=None, cloud_mirror=None):
     """`files` and the twin of every one of them, sorted by path as ``find_all_hdf5`` sorts: the list a directory gives in which
     postprocess_episodes.py has written ``mirror_<name>`` beside every ``<name>``"""
-    return sorted(list(files) + [MirrorTwinPath(f, spec, depth_follows) for f in files])
+    return sorted(list(files) + [MirrorTwinPath(f, spec, depth_follows, cloud_mirror) for f in files])
 
 
 def open_episode(path):
@@ -367,7 +446,7 @@ def find_all_hdf5(dataset_dir, skip_mirrored_data):
     return files
 
 
-def find_all_hdf5_with_twins(dataset_dir, skip_mirrored_data, spec=None, depth_follows=None):
+def find_all_hdf5_with_twins(dataset_dir, skip_mirrored_data, spec=None, depth_follows=None, cloud_mirror=None):
     """``find_all_hdf5`` for ``mirror_twins``: the directory's own files (mirrored ones skipped) and the twin of every one of them,
     sorted by path -- the list ``find_all_hdf5(dataset_dir, False)`` gives once postprocess_episodes.py has run there.  Mirrored
     files that are listed (present, and not skipped) are refused: twins of twins and duplicates are never wanted."""
@@ -379,7 +458,7 @@ def find_all_hdf5_with_twins(dataset_dir, skip_mirrored_data, spec=None, depth_f
         if listed:
             raise ValueError(f"mirror_twins: {dataset_dir} already holds {len(listed)} mirrored episode files ({listed[0]}, ...): pass "
                              f"skip_mirrored_data (--skip_mirrored_data) to serve their twins from the originals instead")
-    return mirror_twin_paths(files, spec, depth_follows)
+    return mirror_twin_paths(files, spec, depth_follows, cloud_mirror)
 
 
 def get_norm_stats(dataset_path_list):
@@ -463,8 +542,9 @@ class EpisodicDataset(torch.utils.data.Dataset):
                                  f"{self.pointcloud_names}")
             if self.use_depth:
                 raise NotImplementedError("use_depth together with use_pcd is not supported")
-            if any(isinstance(p, MirrorTwinPath) for p in dataset_path_list):
-                raise ValueError("use_pcd with mirror twins: a stored point cloud has no mirror rule")
+            if any(isinstance(p, MirrorTwinPath) and getattr(p, "cloud_mirror", None) is None for p in dataset_path_list):
+                raise ValueError("use_pcd with mirror twins: a stored point cloud has no mirror rule (MirrorTwinPath(..., "
+                                 "cloud_mirror=(axis, offset)) gives it one)")
         if policy_class == "Diffusion":
             raise NotImplementedError("the Diffusion augmentations (torchvision transforms) are outside this path")
         self._stats_t = {k: torch.as_tensor(np.asarray(norm_stats[k]), dtype=torch.float32)
@@ -655,7 +735,8 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
               skip_mirrored_data=False, load_pretrain=False, policy_class=None, stats_dir_l=None, sample_weights=None,
               train_ratio=0.99, num_workers=2, f32_images=False, rng=None, depth_camera_names=None, use_depth=False,
               f32_depth=False, pointcloud_names=None, use_pcd=False, max_points=None, pcd_ignore_mask=False,
-              device_dataset=False, device=None, device_budget_bytes=None, mirror_twins=False, mirror_spec=None):
+              device_dataset=False, device=None, device_budget_bytes=None, mirror_twins=False, mirror_spec=None,
+              device_clouds=False, cloud_mirror=None):
     """utils.py:249-301.  Returns (train_dataloader, val_dataloader, norm_stats, is_sim).  ``use_depth``: the batches are
     5-tuples that end in the depth frames of ``depth_camera_names`` (EpisodicDataset).  ``use_pcd``: 7-tuples that end in the
     padded clouds and their valid counts (collate_pcd).  ``device_dataset``: both loaders come from ONE ``DeviceEpisodeStore``
@@ -665,11 +746,20 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
     its mirrored twin (``MirrorTwinPath``; ``mirror_spec`` None: the reference's rule for the cameras each file holds), computed
     from the file as it is read -- the results are those of the same call without the flag on a directory in which the twin files
     exist (uncompressed, float32 rows): the same episode ids, stats, draws and batches.  With ``device_dataset`` the twins take no
-    frame memory."""
-    if mirror_twins and use_pcd:
-        raise ValueError("mirror_twins with use_pcd: a stored point cloud has no mirror rule")
+    frame memory.  ``cloud_mirror`` ``(axis, offset)``: the mirror rule of the stored clouds (``cloud_mirror_rule``), which
+    ``mirror_twins`` with ``use_pcd`` needs.  ``device_clouds``: the stored clouds of a ``use_pcd`` dataset go into the store as well
+    and the device loaders deliver the 7-tuples of ``collate_pcd``, gathered by ``actmi_op_gather_clouds``."""
+    if mirror_twins and use_pcd and cloud_mirror is None:
+        raise ValueError("mirror_twins with use_pcd: a stored point cloud has no mirror rule (cloud_mirror=(axis, offset) gives it one)")
+    if cloud_mirror is not None:
+        if not (mirror_twins and use_pcd):
+            raise ValueError("cloud_mirror is the mirror rule of the stored clouds of mirror_twins with use_pcd")
+        cloud_mirror = cloud_mirror_rule(cloud_mirror)[:2]
+    if device_clouds and not (device_dataset and use_pcd):
+        raise ValueError("device_clouds puts the stored clouds of a use_pcd dataset into the device-resident store: it needs "
+                         "device_dataset and use_pcd")
     if device_dataset:                                            # refused before any file is read
-        if use_pcd:
+        if use_pcd and not device_clouds:
             raise NotImplementedError("--device_dataset with use_pcd: point clouds through the device-resident store are not "
                                       "implemented (ragged clouds stay on the host loader); drop --device_dataset")
         if policy_class not in (None, "ACT"):
@@ -685,7 +775,7 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
         follows = dict(zip(depth_camera_names or [], camera_names)) if use_depth else None
 
         def list_files(d):
-            return find_all_hdf5_with_twins(d, skip_mirrored_data, mirror_spec, follows)
+            return find_all_hdf5_with_twins(d, skip_mirrored_data, mirror_spec, follows, cloud_mirror)
     else:
         def list_files(d):
             return find_all_hdf5(d, skip_mirrored_data)
@@ -724,7 +814,9 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         store = DeviceEpisodeStore(dataset_path_list, np.concatenate([train_episode_ids, val_episode_ids]), camera_names, norm_stats,
-                                   device, depth_camera_names, use_depth, device_budget_bytes, use_pcd, policy_class)
+                                   device, depth_camera_names, use_depth, device_budget_bytes, use_pcd, policy_class,
+                                   **(dict(pointcloud_names=pointcloud_names, max_points=max_points, pcd_ignore_mask=pcd_ignore_mask)
+                                      if device_clouds else {}))
         train_loader = store.loader(train_episode_ids, train_episode_len, chunk_size,
                                     BatchSampler(batch_size_train, train_episode_len_l, sample_weights, rng))
         val_loader = store.loader(val_episode_ids, val_episode_len, chunk_size, BatchSampler(batch_size_val, val_episode_len_l, None, rng))
@@ -831,6 +923,29 @@ def _entry_meta(root, key):
     return tuple(int(v) for v in d.shape), np.dtype(d.dtype)
 
 
+def stored_cloud_counts(root, base, path, T, N, pcd_ignore_mask=False):
+    """the valid count of every step of an episode's stored cloud ``base`` ([T, N, 3]) -> int32 [T], by ``_read_cloud``'s rules for
+    all steps at once: ``padding_mask`` must be T x N with its True rows first and at least one of them per step (``ValueError``
+    naming the file and the first offending timestep); without a mask, or with ``pcd_ignore_mask``, every stored row counts"""
+    counts = np.full(T, N, dtype=np.int32)
+    if not pcd_ignore_mask and f"{base}/padding_mask" in root:
+        mask = np.asarray(root[f"{base}/padding_mask"][()]).astype(bool)
+        if mask.shape[0] != T:
+            raise ValueError(f"{path}: padding_mask of {mask.shape[0]} steps for an episode of {T}")
+        mask = mask.reshape(T, -1)
+        if mask.shape[1] != N:
+            raise ValueError(f"{path} (timestep 0): padding_mask of {mask.shape[1]} rows for a cloud of {N}")
+        counts = mask.sum(axis=1).astype(np.int32)
+        bad = np.nonzero((mask != (np.arange(N)[None, :] < counts[:, None])).any(axis=1))[0]
+        if len(bad):
+            raise ValueError(f"{path} (timestep {int(bad[0])}): padding_mask is not a prefix (True rows first): the valid points "
+                             "cannot be given as a count")
+    empty = np.nonzero(counts == 0)[0]
+    if len(empty):
+        raise ValueError(f"{path} (timestep {int(empty[0])}): the point cloud has no valid point")
+    return counts
+
+
 class DeviceEpisodeStore:
     """Every frame of the named episodes in ONE device arena, read from the files once; a training batch is then a device-to-device
     gather (``actmi.ops.gather_frames`` / ``gather_chunks``) and equals what ``EpisodicDataset.__getitem__`` + the default
@@ -856,13 +971,31 @@ class DeviceEpisodeStore:
     record.  A store that holds a twin gathers frames and depth with ``ops.gather_frames_mirror``; one without launches what it
     always did.  A twin whose source camera is not among ``camera_names`` is refused (``ValueError``).
 
+    Stored point clouds (``use_pcd`` with exactly one name in ``pointcloud_names``; ``has_clouds``): per source file, behind its
+    frame blocks, one float32 ``[T, N, 3]`` xyz block and one colour block ``[T, N, 3]`` -- uint8 when every source stores uint8,
+    float32 everywhere otherwise (``cloud_rgb_fmt``) -- padded to 256 bytes like every block and counted in ``nbytes``; N may differ
+    between episodes.  The valid count of every stored step (``_read_cloud``'s rules on ``padding_mask``, raised at load with the
+    file and the timestep) is a host int32 array, ``cloud_n``.  ``gather`` then returns the 7-tuple of ``collate_pcd`` (P = the
+    batch's largest stored row count) with ONE more launch, ``ops.gather_clouds``, whose item records ride in the batch's one index
+    upload.  A twin's clouds are its source's blocks with the mirror flag set: no bytes; its ``cloud_mirror`` rule -- one for the
+    whole store -- is the launch's.  ``use_pcd`` without names keeps the refusal above.
+
     Every rank of a data-parallel run holds its own full store."""
 
     RING = 4                 # pinned index blocks in flight: a block is rewritten only after its copy has executed
 
     def __init__(self, dataset_path_list, episode_ids, camera_names, norm_stats, device, depth_camera_names=None, use_depth=False,
-                 budget_bytes=None, use_pcd=False, policy_class="ACT", stage_bytes=64 << 20):
-        if use_pcd:
+                 budget_bytes=None, use_pcd=False, policy_class="ACT", stage_bytes=64 << 20, pointcloud_names=None, max_points=None,
+                 pcd_ignore_mask=False):
+        self.pointcloud_names = list(pointcloud_names) if pointcloud_names else []
+        self.has_clouds = bool(use_pcd) and bool(self.pointcloud_names)
+        if self.has_clouds and len(self.pointcloud_names) != 1:
+            raise ValueError(f"use_pcd needs exactly one pointcloud name (/observations/pointcloud/<name>), got {self.pointcloud_names}")
+        if self.has_clouds and use_depth:
+            raise NotImplementedError("use_depth together with use_pcd is not supported")
+        self.max_points = None if max_points is None else int(max_points)
+        self.pcd_ignore_mask = bool(pcd_ignore_mask)
+        if use_pcd and not self.has_clouds:
             raise NotImplementedError("--device_dataset with use_pcd: point clouds through the device-resident store are not "
                                       "implemented (ragged clouds stay on the host loader); drop --device_dataset")
         if policy_class not in (None, "ACT"):
@@ -887,6 +1020,15 @@ class DeviceEpisodeStore:
         self.sources = list(dict.fromkeys(srcs))
         where = {s: j for j, s in enumerate(self.sources)}
         self._src_of = np.asarray([where[s] for s in srcs], dtype=np.int64)
+        self.cloud_mirror = None                                      # (axis, offset, c2): the one rule of the twins' clouds
+        if self.has_clouds and self.has_twins:
+            rules = {getattr(p, "cloud_mirror", None) for p, tw in zip(self.paths, self.twin) if tw}
+            if None in rules:
+                raise ValueError("use_pcd with mirror twins: a stored point cloud has no mirror rule (MirrorTwinPath(..., "
+                                 "cloud_mirror=(axis, offset)) gives it one)")
+            if len(rules) != 1:
+                raise ValueError(f"DeviceEpisodeStore: the twins carry different cloud mirror rules {sorted(rules)}: one gather takes one")
+            self.cloud_mirror = cloud_mirror_rule(rules.pop())
         self.device = device
         self.stage_bytes = int(stage_bytes)
         self._plan()
@@ -906,6 +1048,7 @@ class DeviceEpisodeStore:
         src_T = np.zeros(len(self.sources), dtype=np.int64)
         self.frame_shape = self.depth_shape = None
         src_compressed = []
+        src_N, rgb_u8 = np.zeros(len(self.sources), dtype=np.int64), True
         for i, path in enumerate(self.sources):
             with open_episode(path) as root:
                 compressed = bool(root.attrs.get("compress", False))
@@ -913,6 +1056,20 @@ class DeviceEpisodeStore:
                 src_T[i] = _entry_meta(root, "/action")[0][0]
                 if src_T[i] < 1:
                     raise ValueError(f"{path}: empty episode")
+                if self.has_clouds:                                   # _read_cloud's checks of the shapes, from the headers
+                    base = f"/observations/pointcloud/{self.pointcloud_names[0]}"
+                    if f"{base}/xyz" not in root or f"{base}/rgb" not in root:
+                        raise ValueError(f"{path}: no {base}/xyz and {base}/rgb")
+                    (xs, _xdt), (cs, cdt) = _entry_meta(root, f"{base}/xyz"), _entry_meta(root, f"{base}/rgb")
+                    if len(xs) != 3 or xs[2] != 3 or tuple(cs) != tuple(xs) or xs[1] < 1:
+                        raise ValueError(f"{path}: point cloud xyz {tuple(xs)} / rgb {tuple(cs)}, expected two [T, N, 3] arrays")
+                    if xs[0] != src_T[i]:
+                        raise ValueError(f"{path}: {base}/xyz holds {xs[0]} clouds for an episode of {int(src_T[i])} steps")
+                    if self.max_points is not None and xs[1] > self.max_points:
+                        raise ValueError(f"{path}: the point cloud stores {xs[1]} rows, more than max_points {self.max_points} (no "
+                                         "silent truncation: raise --max_points or down-sample the recording)")
+                    src_N[i] = xs[1]
+                    rgb_u8 = rgb_u8 and cdt == np.uint8
                 for kind, cams, want in (("images", self.camera_names, 4), ("depth_images", self.depth_camera_names[:Kd], None)):
                     for cam in cams:
                         key = f"/observations/{kind}/{cam}"
@@ -946,12 +1103,18 @@ class DeviceEpisodeStore:
         self.K, self.Kd = K, Kd
         self.frame_bytes = int(np.prod(self.frame_shape))
         self.depth_bytes = int(np.prod(self.depth_shape)) * 2 if Kd else 0
+        nc = 2 if self.has_clouds else 0                               # an xyz and a colour block per source, behind its frames
+        self.cloud_rgb_fmt = 0 if rgb_u8 else 1                        # uint8 colours when every source stores them, f32 otherwise
+        self.cloud_rgb_bytes = 3 if rgb_u8 else 12                     # bytes of one stored colour row
         blocks = []
-        for T in src_T:
-            blocks += [int(T) * self.frame_bytes] * K + [int(T) * self.depth_bytes] * Kd
+        for T, N in zip(src_T, src_N):
+            blocks += [int(T) * self.frame_bytes] * K + [int(T) * self.depth_bytes] * Kd + \
+                      [int(T) * int(N) * 12, int(T) * int(N) * self.cloud_rgb_bytes][:nc]
         offs, self.nbytes = arena_layout(blocks)                       # every source once: a twin adds no frame bytes
-        offs = offs.reshape(len(self.sources), K + Kd)
-        self._src_block_off, self._src_depth_block_off, self._src_T = offs[:, :K].copy(), offs[:, K:].copy(), src_T
+        offs = offs.reshape(len(self.sources), K + Kd + nc)
+        self._src_block_off, self._src_depth_block_off, self._src_T = offs[:, :K].copy(), offs[:, K:K + Kd].copy(), src_T
+        self._src_N, self._src_cloud_off = src_N, offs[:, K + Kd:].copy()
+        self._src_row0 = np.concatenate([[0], np.cumsum(src_T)[:-1]]).astype(np.int64)   # of a source's steps in cloud_n
         self._src_compressed = src_compressed
         # per episode: its source's length and blocks; a twin's cameras are its source's, permuted and flagged by its spec
         self.T = src_T[self._src_of]
@@ -987,7 +1150,8 @@ class DeviceEpisodeStore:
         dev = torch.device(self.device)
         t_begin = time.perf_counter()
         self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
-        stage = max(self.stage_bytes, self.frame_bytes, self.depth_bytes)
+        stage = max(self.stage_bytes, self.frame_bytes, self.depth_bytes, int(self._src_N.max()) * 12 if self.has_clouds else 0)
+        self.cloud_n = np.zeros(int(self._src_T.sum()) if self.has_clouds else 0, dtype=np.int32)   # valid rows of every stored step
         self._pin = [torch.empty(stage, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         self._pin_ev, self._pin_i = [None, None], 0
         actions, qposes, sims = [], [], []
@@ -1041,6 +1205,34 @@ class DeviceEpisodeStore:
         for k, cam in enumerate(self.depth_camera_names[:self.Kd]):
             self._load_block(root[f"/observations/depth_images/{cam}"], T, self._src_compressed[j],
                              int(self._src_depth_block_off[j, k]), True, f"{path}: /observations/depth_images/{cam}")
+        if self.has_clouds:
+            self._load_clouds(root, j)
+
+    def _load_clouds(self, root, j):
+        """the clouds of source file j into its two blocks, and the valid count of every step by ``_read_cloud``'s rules"""
+        path, T, N = self.sources[j], int(self._src_T[j]), int(self._src_N[j])
+        base = f"/observations/pointcloud/{self.pointcloud_names[0]}"
+        f32c = self.cloud_rgb_fmt == 1
+        for leaf, off, rb in (("xyz", int(self._src_cloud_off[j, 0]), 12), ("rgb", int(self._src_cloud_off[j, 1]), self.cloud_rgb_bytes)):
+            entry = root[f"{base}/{leaf}"]
+            per = max(1, self._pin[0].numel() // (N * rb))
+            for t0 in range(0, T, per):
+                t1 = min(T, t0 + per)
+                piece = np.asarray(entry[t0:t1])
+                if piece.shape != (t1 - t0, N, 3):
+                    raise ValueError(f"{path} (timestep {t0}): point cloud {leaf} {piece.shape[1:]}, the store was sized for {(N, 3)}")
+                if leaf == "rgb" and not f32c:
+                    if piece.dtype != np.uint8:
+                        raise ValueError(f"{path}: {base}/rgb is {piece.dtype}, its header said uint8")
+                    flat = np.ascontiguousarray(piece).reshape(-1)
+                else:                                                 # np.ascontiguousarray(..., dtype=np.float32), as _read_cloud
+                    flat = np.ascontiguousarray(piece, dtype=np.float32).reshape(-1).view(np.uint8)
+                n = (t1 - t0) * N * rb
+                if off + t0 * N * rb + n > self.nbytes:               # cannot happen with the sizes checked in _plan
+                    raise MemoryError(f"{path}: cloud block leaves the arena of {self.nbytes} bytes")
+                self._stage(off + t0 * N * rb, n, lambda view, flat=flat: np.copyto(view, flat))
+        counts = stored_cloud_counts(root, base, path, T, N, self.pcd_ignore_mask)
+        self.cloud_n[int(self._src_row0[j]):int(self._src_row0[j]) + T] = counts
 
     def _stage(self, dst_off, nbytes, fill):
         """one piece through the staging pair: ``fill(view)`` writes `nbytes` bytes into the pinned view, which is then copied to
@@ -1120,17 +1312,25 @@ class DeviceEpisodeStore:
             raise IndexError("DeviceEpisodeStore.gather: a sample outside the stored episodes")
         off, doff = self.frame_offsets(e, t)
         samples = np.ascontiguousarray(np.stack([e, t], axis=1).astype(np.int32)).view(np.int64).reshape(-1)
+        items = self._cloud_items(e, t) if self.has_clouds else None
         if self.has_twins:
-            return self._gather_mirror(e, off, doff, samples, B, Q, nontemporal)
+            return self._gather_mirror(e, off, doff, samples, B, Q, nontemporal, items)
         nk, nd = B * self.K, B * self.Kd
         dev = self.arena.device
         with torch.cuda.device(dev):
-            tab = self._upload(np.concatenate([off.reshape(-1), doff.reshape(-1), samples]))
+            if items is not None:                                     # the item records ride behind the samples in the one upload
+                tab = self._upload(np.concatenate([off.reshape(-1), doff.reshape(-1), samples, items.view(np.int64)]))
+                clouds = self._gather_clouds(tab[nk + nd + B:], items, nontemporal)
+                tab = tab[:nk + nd + B]
+            else:
+                tab = self._upload(np.concatenate([off.reshape(-1), doff.reshape(-1), samples]))
             image = torch.empty((B, self.K) + tuple(self.frame_shape), dtype=torch.uint8, device=dev)
             ops.gather_frames(self.arena, tab[:nk], self.frame_bytes, out=image,
                               aligned=2 if (nontemporal and self.aligned) else self.aligned)
             qpos, action, is_pad = ops.gather_chunks(self.actions, self.qpos, self.episodes, tab[nk + nd:].view(torch.int32).view(B, 2),
                                                      *self._stats, Q)
+            if items is not None:
+                return (image, qpos, action, is_pad) + clouds
             if not self.Kd:
                 return image, qpos, action, is_pad
             depth = torch.empty((B, self.Kd, 1) + tuple(self.depth_shape), dtype=torch.uint16, device=dev)
@@ -1138,7 +1338,29 @@ class DeviceEpisodeStore:
                               aligned=2 if (nontemporal and self.depth_aligned) else self.depth_aligned)
         return image, qpos, action, is_pad, depth
 
-    def _gather_mirror(self, e, off, doff, samples, B, Q, nontemporal):
+    def _cloud_items(self, e, t):
+        """the records (``ops.cloud_item_dtype``) of the clouds of samples (e[b], t[b]): where the step's rows lie in its source's two
+        blocks, how many there are, how many are points, and the mirror flag of a twin"""
+        from . import ops
+        j = self._src_of[e]
+        N = self._src_N[j]
+        items = np.zeros(len(e), dtype=ops.cloud_item_dtype())
+        items["xyz_off"] = self._src_cloud_off[j, 0] + t * N * 12
+        items["rgb_off"] = self._src_cloud_off[j, 1] + t * N * self.cloud_rgb_bytes
+        items["rows"], items["n"] = N, self.cloud_n[self._src_row0[j] + t]
+        items["flags"] = np.asarray(self.twin, dtype=np.int32)[e]
+        return items
+
+    def _gather_clouds(self, tab, items, nontemporal):
+        """the one launch of a batch's clouds -> (xyz [B, P, 3] f32, rgb [B, P, 3] f32, n [B] int32), P the batch's largest stored
+        row count as ``collate_pcd`` pads; the 16-byte form where P allows it (torch's allocations are 16-byte aligned)"""
+        from . import ops
+        P = int(items["rows"].max())
+        aligned = (2 if nontemporal else 1) if P % 4 == 0 else 0
+        mirror = None if self.cloud_mirror is None else (self.cloud_mirror[0], self.cloud_mirror[2])
+        return ops.gather_clouds(self.arena, tab, P, self.cloud_rgb_fmt, mirror=mirror, aligned=aligned)
+
+    def _gather_mirror(self, e, off, doff, samples, B, Q, nontemporal, items=None):
         """``gather`` of a store that holds mirrored twins: the frames (and the depth) come from ``gather_frames_mirror``, whose
         flip flags -- one per item, the twin's cameras that are flipped -- travel in the same index upload, packed eight to a word
         behind the offsets"""
@@ -1152,12 +1374,20 @@ class DeviceEpisodeStore:
         # the aligned form's statement: frames at multiples of 16 (the arena's layout) and rows of whole 16- / 8-pixel groups
         aligned = self.aligned if W % 16 == 0 else 0
         with torch.cuda.device(dev):
-            tab = self._upload(np.concatenate([off.reshape(-1), doff.reshape(-1), samples, words.view(np.int64)]))
+            if items is not None:
+                nw = len(words) // 8
+                tab = self._upload(np.concatenate([off.reshape(-1), doff.reshape(-1), samples, words.view(np.int64), items.view(np.int64)]))
+                clouds = self._gather_clouds(tab[nk + nd + B + nw:], items, nontemporal)
+                tab = tab[:nk + nd + B + nw]
+            else:
+                tab = self._upload(np.concatenate([off.reshape(-1), doff.reshape(-1), samples, words.view(np.int64)]))
             fl = tab[nk + nd + B:].view(torch.uint8)
             image = torch.empty((B, self.K) + tuple(self.frame_shape), dtype=torch.uint8, device=dev)
             ops.gather_frames_mirror(self.arena, tab[:nk], fl[:nk], H, W, 3, out=image, aligned=2 if (nontemporal and aligned) else aligned)
             qpos, action, is_pad = ops.gather_chunks(self.actions, self.qpos, self.episodes, tab[nk + nd:nk + nd + B].view(torch.int32).view(B, 2),
                                                      *self._stats, Q)
+            if items is not None:
+                return (image, qpos, action, is_pad) + clouds
             if not self.Kd:
                 return image, qpos, action, is_pad
             Hd, Wd = self.depth_shape

@@ -161,6 +161,18 @@ class GatherMirrorDesc(C.Structure):
                 ("n_items", C.c_int64)] + [(k, C.c_int32) for k in ("H", "W", "px_bytes", "aligned")]
 
 
+class CloudItem(C.Structure):
+    # actmi_cloud_item: the device record of one sample of actmi_op_gather_clouds, 32 bytes
+    _fields_ = [("xyz_off", C.c_int64), ("rgb_off", C.c_int64)] + [(k, C.c_int32) for k in ("rows", "n", "flags", "pad")]
+
+
+class GatherCloudsDesc(C.Structure):
+    # actmi_gather_clouds_desc
+    _fields_ = [("arena", C.c_void_p), ("arena_bytes", C.c_int64), ("items", C.c_void_p), ("out_xyz", C.c_void_p), ("out_rgb", C.c_void_p),
+                ("out_n", C.c_void_p)] + [(k, C.c_int32) for k in ("B", "P", "rgb_fmt", "mirror_axis")] + \
+               [("mirror_c2", C.c_float), ("aligned", C.c_int32)]
+
+
 _lib = None
 
 
@@ -270,6 +282,7 @@ def load():
         "actmi_op_cloud_augment": ([C.POINTER(CloudAugmentDesc), vp], i32),
         "actmi_op_gather_frames": ([vp, i64, vp, vp, i64, i64, i32, vp], i32),
         "actmi_op_gather_frames_mirror": ([C.POINTER(GatherMirrorDesc), vp], i32),
+        "actmi_op_gather_clouds": ([C.POINTER(GatherCloudsDesc), vp], i32),
         "actmi_op_gather_chunks": ([C.POINTER(GatherChunksDesc), vp], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),

@@ -2075,6 +2075,71 @@ def gather_frames_mirror_ref(arena, src_off, flip, H, W, px_bytes):
     return out
 
 
+def cloud_item_dtype():
+    """actmi_cloud_item as a numpy structured dtype (32 bytes)"""
+    import numpy as np
+    return np.dtype([("xyz_off", np.int64), ("rgb_off", np.int64), ("rows", np.int32), ("n", np.int32), ("flags", np.int32),
+                     ("pad", np.int32)])
+
+
+def gather_clouds(arena, items, P, rgb_fmt, mirror=None, out=None, aligned=0):
+    """actmi_op_gather_clouds: arena 1-D uint8 cuda; items: a contiguous cuda tensor (uint8 or int64) on its device holding [B]
+    records (cloud_item_dtype) -> (xyz [B, P, 3] f32, rgb [B, P, 3] f32, n [B] int32), or the caller's ``out`` triple.  rgb_fmt: 0
+    the arena holds uint8 colours, 1 f32.  mirror: (axis, c2) for the items whose flags carry bit 0 (c2 is taken as float32), None
+    when no item does.  aligned: 0 general; 1 the outputs are 16-byte aligned and P % 4 == 0 (checked); 2 the same with
+    non-temporal loads."""
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_cuda or not arena.is_contiguous():
+        raise ValueError(f"gather_clouds: arena must be a contiguous 1-D uint8 cuda tensor, got {arena.dtype} {tuple(arena.shape)}")
+    nb = items.numel() * items.element_size()
+    if items.dtype not in (torch.uint8, torch.int64) or items.device != arena.device or not items.is_contiguous() or nb % 32:
+        raise ValueError("gather_clouds: items must be a contiguous uint8 or int64 tensor of whole 32-byte records on the arena's device")
+    B, P = nb // 32, int(P)
+    dev = arena.device
+    if out is None:
+        out = (torch.empty((B, P, 3), dtype=torch.float32, device=dev), torch.empty((B, P, 3), dtype=torch.float32, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev))
+    xyz, rgb, n = out
+    for name, t, dt, numel in (("xyz", xyz, torch.float32, B * P * 3), ("rgb", rgb, torch.float32, B * P * 3), ("n", n, torch.int32, B)):
+        if t.dtype != dt or t.device != dev or not t.is_contiguous() or t.numel() != numel:
+            raise ValueError(f"gather_clouds: out {name} must be a contiguous {dt} tensor of {numel} values on {dev}")
+    axis, c2 = (0, 0.0) if mirror is None else (int(mirror[0]), float(mirror[1]))
+    d = L.GatherCloudsDesc()
+    d.arena, d.arena_bytes, d.items = arena.data_ptr(), int(arena.numel()), items.data_ptr()
+    d.out_xyz, d.out_rgb, d.out_n = xyz.data_ptr(), rgb.data_ptr(), n.data_ptr()
+    d.B, d.P, d.rgb_fmt, d.mirror_axis, d.mirror_c2, d.aligned = B, P, int(rgb_fmt), axis, c2, int(aligned)
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_gather_clouds(C.byref(d), L.current_stream_ptr()), None, "op_gather_clouds")
+    return xyz, rgb, n
+
+
+def gather_clouds_ref(arena, items, P, rgb_fmt, mirror=None):
+    """numpy statement of ``gather_clouds``; needs no library.  arena: 1-D uint8 ndarray, items: [B] records (cloud_item_dtype)
+    -> (xyz [B, P, 3] f32, rgb [B, P, 3] f32, n [B] int32).  With r = clamp(rows, 0, P): rows [0, r) are the stored ones (uint8
+    colours converted), the rest zero; flags & 1: xyz[..., axis] = float32(c2) - xyz[..., axis] over the copied rows; an item either
+    of whose source ranges leaves the arena is zeros with n = 0."""
+    import numpy as np
+    a = np.asarray(arena).reshape(-1).view(np.uint8)
+    it = np.asarray(items).reshape(-1)
+    P, f32c = int(P), bool(rgb_fmt)
+    xyz, rgb = np.zeros((len(it), P, 3), dtype=np.float32), np.zeros((len(it), P, 3), dtype=np.float32)
+    n = np.zeros(len(it), dtype=np.int32)
+    for b, rec in enumerate(it):
+        xo, co, r = int(rec["xyz_off"]), int(rec["rgb_off"]), min(max(int(rec["rows"]), 0), P)
+        xb, cb = r * 12, r * (12 if f32c else 3)
+        if xo < 0 or co < 0 or xo + xb > a.size or co + cb > a.size:
+            continue
+        n[b] = rec["n"]
+        x = np.frombuffer(a[xo:xo + xb].tobytes(), dtype=np.float32).reshape(r, 3).copy()
+        if int(rec["flags"]) & 1:
+            if mirror is None:
+                raise ValueError("gather_clouds_ref: an item is flagged and no mirror rule is given")
+            x[:, int(mirror[0])] = np.float32(mirror[1]) - x[:, int(mirror[0])]
+        xyz[b, :r] = x
+        c = a[co:co + cb]
+        rgb[b, :r] = (np.frombuffer(c.tobytes(), dtype=np.float32) if f32c else c.astype(np.float32)).reshape(r, 3)
+    return xyz, rgb, n
+
+
 def gather_chunks(actions, qpos, episodes, samples, action_mean, action_std, qpos_mean, qpos_std, Q):
     """actmi_op_gather_chunks.  actions [R, A] / qpos [R, S] f32 cuda (all episodes' rows back to back), episodes: uint8 cuda
     tensor holding [E] records (episode_rec_dtype), samples [B, 2] int32 cuda (episode, t), the four stat vectors f32 cuda ->

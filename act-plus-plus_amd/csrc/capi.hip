@@ -520,6 +520,13 @@ int actmi_op_gather_frames_mirror(const actmi_gather_mirror_desc* d, void* strea
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
 }
 
+int actmi_op_gather_clouds(const actmi_gather_clouds_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "gather_clouds: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_gather_clouds(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_gather_chunks(const actmi_gather_chunks_desc* d, void* stream) {
     g_op_error.clear();
     if (!d) { g_op_error = "gather_chunks: null descriptor"; return ACTMI_E_INVALID; }

@@ -254,6 +254,7 @@ int launch_cloud_augment(const actmi_cloud_augment_desc& a, hipStream_t st, std:
 int launch_gather_frames(const void* arena, int64_t arena_bytes, const int64_t* src_off, void* out, int64_t n_items,
                          int64_t item_bytes, int aligned, hipStream_t st, std::string* err);
 int launch_gather_frames_mirror(const actmi_gather_mirror_desc& d, hipStream_t st, std::string* err);
+int launch_gather_clouds(const actmi_gather_clouds_desc& d, hipStream_t st, std::string* err);
 int launch_gather_chunks(const actmi_gather_chunks_desc& d, hipStream_t st, std::string* err);
 
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------

@@ -1,5 +1,5 @@
 // Device-resident episode store: a training batch gathered on the device (actmi_op_gather_frames, actmi_op_gather_frames_mirror,
-// actmi_op_gather_chunks; the contract is at their declarations in actmi.h).  The frames of every episode sit in one u8 arena; a batch is n_items contiguous
+// actmi_op_gather_clouds, actmi_op_gather_chunks; the contract is at their declarations in actmi.h).  The frames of every episode sit in one u8 arena; a batch is n_items contiguous
 // pieces of it copied to a contiguous output, plus the z-scored qpos rows and action chunks EpisodicDataset.__getitem__ computes.
 #include "common.h"
 
@@ -202,6 +202,124 @@ __global__ __launch_bounds__(GF_BLOCK) void gather_mirror_bytes_kernel(const uin
     gm_move_bytes(arena + off, dst, b0, b1, flip[item] != 0, row_bytes, px);
 }
 
+// ---- stored point clouds (actmi_op_gather_clouds): item b is `rows` stored rows of xyz f32 and of colours (u8 or f32), padded
+// with zero rows to the batch's P; with flags & 1 one coordinate of every copied xyz row becomes c2 - v.
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// one f32 at any address: a source that is not 4-byte aligned is put together from its bytes
+__device__ __forceinline__ float gc_load_f32(const uint8_t* p, bool al) {
+    if (al) return *reinterpret_cast<const float*>(p);
+    return __uint_as_float((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+}
+
+// the elements [e0, e1) of both outputs of one item, one at a time: any address, any row count.  ne = 3 * (rows copied), 0 for an
+// item that is not read at all
+__device__ __forceinline__ void gc_move_elems(const uint8_t* __restrict__ sx, const uint8_t* __restrict__ sc, float* __restrict__ ox,
+                                              float* __restrict__ oc, int64_t e0, int64_t e1, int64_t ne, bool fl, int axis, float c2,
+                                              int rgb_fmt) {
+    const bool ax = ((uintptr_t)sx & 3) == 0, ac = ((uintptr_t)sc & 3) == 0;
+    for (int64_t i = e0 + threadIdx.x; i < e1; i += GF_BLOCK) {
+        float x = 0.f, c = 0.f;
+        if (i < ne) {
+            x = gc_load_f32(sx + 4 * i, ax);
+            if (fl && (int)(i % 3) == axis) x = __fsub_rn(c2, x);
+            c = rgb_fmt ? gc_load_f32(sc + 4 * i, ac) : (float)sc[i];
+        }
+        ox[i] = x;
+        oc[i] = c;
+    }
+}
+
+// what every form does first: the item's record, the rows it copies, whether its two source ranges lie in the arena, its count
+struct gc_item {
+    const uint8_t *sx, *sc;
+    float *ox, *oc;
+    int64_t r, ne;
+    bool fl;
+};
+__device__ __forceinline__ gc_item gc_open(const actmi_gather_clouds_desc& d) {
+    const int64_t b = blockIdx.y, P = d.P;
+    const actmi_cloud_item it = d.items[b];
+    gc_item g;
+    g.r = it.rows < 0 ? 0 : (it.rows > P ? P : (int64_t)it.rows);
+    const int64_t xb = g.r * 12, cb = d.rgb_fmt ? g.r * 12 : g.r * 3;
+    const bool inside = it.xyz_off >= 0 && it.xyz_off <= d.arena_bytes - xb && it.rgb_off >= 0 && it.rgb_off <= d.arena_bytes - cb;
+    if (blockIdx.x == 0 && threadIdx.x == 0) d.out_n[b] = inside ? it.n : 0;
+    const uint8_t* a = static_cast<const uint8_t*>(d.arena);
+    g.sx = inside ? a + it.xyz_off : a;                           // an item that leaves the arena forms no address from its offsets
+    g.sc = inside ? a + it.rgb_off : a;
+    g.ne = inside ? g.r * 3 : 0;
+    g.ox = d.out_xyz + b * P * 3;
+    g.oc = d.out_rgb + b * P * 3;
+    g.fl = (it.flags & 1) != 0;
+    return g;
+}
+
+__global__ __launch_bounds__(GF_BLOCK) void gather_clouds_elems_kernel(const actmi_gather_clouds_desc d) {
+    const gc_item g = gc_open(d);
+    int64_t e0, e1;
+    gf_share((int64_t)d.P * 3, GF_BLOCK, blockIdx.x, gridDim.x, &e0, &e1);
+    gc_move_elems(g.sx, g.sc, g.ox, g.oc, e0, e1, g.ne, g.fl, d.mirror_axis, d.mirror_c2, d.rgb_fmt);
+}
+
+// grid (splits, B).  The launcher vouches for 16-byte aligned output bases and P % 4 == 0, so both outputs of an item are 3P/4
+// 16-byte words; a workgroup takes the same share of words of both.  An item whose offsets are multiples of 16 and whose row
+// count is a multiple of 4 moves in 16-byte words (component of float j of word v: (4v + j) % 3); any other item goes element by
+// element (uniform over the workgroup).  One 16-byte word of u8 colours becomes four 16-byte stores.
+template <bool NT>
+__global__ __launch_bounds__(GF_BLOCK) void gather_clouds_v16_kernel(const actmi_gather_clouds_desc d) {
+    const gc_item g = gc_open(d);
+    int64_t v0, v1;
+    gf_share((int64_t)d.P * 3 / 4, GF_BLOCK, blockIdx.x, gridDim.x, &v0, &v1);
+    if (g.ne > 0 && ((((uintptr_t)g.sx | (uintptr_t)g.sc) & 15) || (g.r & 3))) {
+        gc_move_elems(g.sx, g.sc, g.ox, g.oc, v0 * 4, v1 * 4, g.ne, g.fl, d.mirror_axis, d.mirror_c2, d.rgb_fmt);
+        return;
+    }
+    const int64_t cw = g.ne >> 2;                                  // words copied of each output; [cw, 3P/4) are zero
+    const int64_t c1 = v1 < cw ? v1 : cw;
+    const f32x4* sx = reinterpret_cast<const f32x4*>(g.sx);
+    f32x4* ox = reinterpret_cast<f32x4*>(g.ox);
+    f32x4* oc = reinterpret_cast<f32x4*>(g.oc);
+    const int axis = d.mirror_axis;
+    const float c2 = d.mirror_c2;
+    const bool f32c = d.rgb_fmt != 0;
+    const f32x4* scf = reinterpret_cast<const f32x4*>(g.sc);
+    for (int64_t v = v0 + threadIdx.x; v < c1; v += GF_BLOCK) {
+        f32x4 x = NT ? __builtin_nontemporal_load(sx + v) : sx[v];
+        f32x4 c;
+        if (f32c) c = NT ? __builtin_nontemporal_load(scf + v) : scf[v];
+        if (g.fl) {
+            const int k = (int)((uint64_t)(4 * v) % 3);            // the component of x.x; x.y is k + 1, ... (mod 3)
+            const int j = axis - k < 0 ? axis - k + 3 : axis - k;   // the first float of the word that is the mirrored component
+            if (j == 0) { x.x = __fsub_rn(c2, x.x); x.w = __fsub_rn(c2, x.w); }
+            else if (j == 1) x.y = __fsub_rn(c2, x.y);
+            else x.z = __fsub_rn(c2, x.z);
+        }
+        ox[v] = x;
+        if (f32c) oc[v] = c;
+    }
+    if (!f32c) {
+        const u32x4* s16 = reinterpret_cast<const u32x4*>(g.sc);
+        const uint32_t* s4 = reinterpret_cast<const uint32_t*>(g.sc);
+        auto widen = [](uint32_t w) { return f32x4{(float)(w & 0xffu), (float)((w >> 8) & 0xffu), (float)((w >> 16) & 0xffu), (float)(w >> 24)}; };
+        const int64_t g1 = c1 >> 2;                                // whole 16-byte source words below c1 (v0 is a multiple of 4)
+        for (int64_t q = (v0 >> 2) + threadIdx.x; q < g1; q += GF_BLOCK) {
+            const u32x4 w = NT ? __builtin_nontemporal_load(s16 + q) : s16[q];
+            oc[4 * q] = widen(w.x);
+            oc[4 * q + 1] = widen(w.y);
+            oc[4 * q + 2] = widen(w.z);
+            oc[4 * q + 3] = widen(w.w);
+        }
+        const int64_t t0 = (g1 << 2) > v0 ? (g1 << 2) : v0;        // the last 4, 8 or 12 colour bytes below c1
+        for (int64_t v = t0 + threadIdx.x; v < c1; v += GF_BLOCK) oc[v] = widen(s4[v]);
+    }
+    for (int64_t v = (v0 > cw ? v0 : cw) + threadIdx.x; v < v1; v += GF_BLOCK) {
+        ox[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+        oc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
 // One workgroup per sample.  Every value is one fp32 subtract and one correctly rounded fp32 divide, as torch computes
 // (x - mean) / std on the host: no reciprocal, nothing fused.
 __global__ __launch_bounds__(256) void gather_chunks_kernel(const float* __restrict__ actions, const float* __restrict__ qpos,
@@ -316,6 +434,43 @@ int launch_gather_frames_mirror(const actmi_gather_mirror_desc& d, hipStream_t s
     }
     prof_end(st);
     if (hipGetLastError() != hipSuccess) { if (err) *err = "gather_frames_mirror: launch failed"; return -3; }
+    return 0;
+}
+
+int launch_gather_clouds(const actmi_gather_clouds_desc& d, hipStream_t st, std::string* err) {
+    auto fail = [&](const char* m) { if (err) *err = m; return -2; };
+    if (d.B == 0) return 0;
+    if (d.B < 0 || d.B > 65535) return fail("gather_clouds: B outside 0..65535");
+    if (d.P < 1 || d.P > (1 << 27)) return fail("gather_clouds: P outside 1..2^27");
+    if (d.arena_bytes < 0) return fail("gather_clouds: negative arena size");
+    if (d.rgb_fmt != 0 && d.rgb_fmt != 1) return fail("gather_clouds: rgb_fmt must be 0 (uint8 colours) or 1 (f32)");
+    if (d.mirror_axis < 0 || d.mirror_axis > 2) return fail("gather_clouds: mirror_axis must be 0, 1 or 2");
+    if (d.aligned < 0 || d.aligned > 2) return fail("gather_clouds: aligned must be 0, 1 or 2");
+    if (!d.arena || !d.items || !d.out_xyz || !d.out_rgb || !d.out_n) return fail("gather_clouds: null pointer");
+    if ((uintptr_t)d.items & 7) return fail("gather_clouds: items must be 8-byte aligned");
+    if (((uintptr_t)d.out_xyz | (uintptr_t)d.out_rgb | (uintptr_t)d.out_n) & 3) return fail("gather_clouds: misaligned output (4 bytes)");
+    if (d.aligned && ((d.P & 3) || (((uintptr_t)d.out_xyz | (uintptr_t)d.out_rgb) & 15)))
+        return fail("gather_clouds: the aligned form needs P % 4 == 0 and out_xyz, out_rgb at multiples of 16");
+    // about 2048 workgroups in all, none with less than one pass of the workgroup over each output
+    const int64_t units = d.aligned ? (int64_t)d.P * 3 / 4 : (int64_t)d.P * 3;
+    const int64_t max_splits = (units + GF_BLOCK - 1) / GF_BLOCK;
+    int64_t splits = (2048 + d.B - 1) / d.B;
+    splits = splits > max_splits ? max_splits : splits;
+    splits = splits < 1 ? 1 : splits;
+    const dim3 grid((unsigned)splits, (unsigned)d.B), block(GF_BLOCK);
+    const double bytes = (double)d.B * d.P * (24.0 + 12.0 + (d.rgb_fmt ? 12.0 : 3.0));
+    if (d.aligned == 2) {
+        prof_begin("gather_clouds_v16_nt", 0.0, bytes, st);
+        hipLaunchKernelGGL(gather_clouds_v16_kernel<true>, grid, block, 0, st, d);
+    } else if (d.aligned == 1) {
+        prof_begin("gather_clouds_v16", 0.0, bytes, st);
+        hipLaunchKernelGGL(gather_clouds_v16_kernel<false>, grid, block, 0, st, d);
+    } else {
+        prof_begin("gather_clouds_elems", 0.0, bytes, st);
+        hipLaunchKernelGGL(gather_clouds_elems_kernel, grid, block, 0, st, d);
+    }
+    prof_end(st);
+    if (hipGetLastError() != hipSuccess) { if (err) *err = "gather_clouds: launch failed"; return -3; }
     return 0;
 }
 

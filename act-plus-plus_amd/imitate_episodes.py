@@ -12,6 +12,9 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
   use_pcd policies and of policies trained on real-robot episodes: queries batched over TIME, one ensemble launch per episode;
 * ``--device_dataset --replay_every N`` runs that replay on held-out episodes every N training steps, out of the device-resident
   store the batches come from (no file read); ``--replay_horizon`` adds the error along the predicted chunk;
+* ``--device_dataset --use_pcd --device_clouds`` puts the task's stored point clouds into that store as well (the batches' clouds are
+  gathered on the device; ``--replay_every`` then serves point-cloud policies), and ``--mirror_twins --use_pcd --cloud_mirror_axis
+  {x,y,z} [--cloud_mirror_offset C]`` gives a stored cloud the mirror rule the twins need;
 * ``--mirror_twins`` joins every episode file by its mirrored twin (postprocess_episodes.py's definition), computed as it is read:
   ``actmi.data.load_data(..., mirror_twins=True)``; with ``--device_dataset`` the twins share their sources' frames;
 * ``--augment_images`` and, for the stored clouds of ``--use_pcd``, ``--augment_clouds`` augment the TRAINING batches on the
@@ -520,8 +523,9 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
                 "sources": source_names(layout, camera_names, policy_config.get("depth_camera_names") if use_depth else None)}
     dataset_dir = config.get("dataset_dir")
     if store is not None:
-        if use_pcd:
-            raise NotImplementedError("replay_bc: the device-resident store holds no point clouds (use_pcd)")
+        if use_pcd and not getattr(store, "has_clouds", False):
+            raise NotImplementedError("replay_bc: the device-resident store holds no point clouds (use_pcd); one built with "
+                                      "--device_clouds does")
         if episodes is None or isinstance(episodes, (int, np.integer)):
             ids = list(store.episode_ids)[:None if episodes is None else int(episodes)]
         else:
@@ -960,26 +964,42 @@ def build_config(args):
     if args.get("device_dataset"):
         if policy_class != "ACT":
             raise NotImplementedError("--device_dataset: the device-resident episode store feeds the ACT training path")
-        if args.get("use_pcd"):
+        if args.get("use_pcd") and not args.get("device_clouds"):
             raise NotImplementedError("--device_dataset with --use_pcd: point clouds through the device-resident store are not "
-                                      "implemented; drop --device_dataset")
+                                      "implemented; drop --device_dataset (or put the stored clouds into the store: --device_clouds)")
         config["device_dataset"] = True
         if args.get("device_dataset_gb") is not None:
             config["device_dataset_gb"] = float(args["device_dataset_gb"])
+    if args.get("device_clouds"):
+        if not (args.get("device_dataset") and args.get("use_pcd")):
+            raise ValueError("--device_clouds puts the stored clouds of a --use_pcd dataset into the device-resident store: it needs "
+                             "--device_dataset and --use_pcd")
+        config["device_clouds"] = True
+    cloud_axis = args.get("cloud_mirror_axis")
+    if cloud_axis is None and args.get("cloud_mirror_offset"):
+        raise ValueError("--cloud_mirror_offset is the plane of --cloud_mirror_axis")
+    if cloud_axis is not None:
+        if not (args.get("mirror_twins") and args.get("use_pcd")):
+            raise ValueError("--cloud_mirror_axis is the mirror rule of the stored clouds of --mirror_twins with --use_pcd")
+        offset = float(args.get("cloud_mirror_offset") or 0.0)
+        if cloud_axis not in ("x", "y", "z") or not np.isfinite(offset) or abs(2.0 * offset) > float(np.finfo(np.float32).max):
+            raise ValueError(f"--cloud_mirror_axis {cloud_axis!r} --cloud_mirror_offset {offset!r}: needs x, y or z and a finite offset")
     if args.get("mirror_twins"):
         if policy_class != "ACT":
             raise NotImplementedError("--mirror_twins: the mirrored twin episodes feed the ACT training path")
-        if args.get("use_pcd"):
-            raise ValueError("--mirror_twins with --use_pcd: a stored point cloud has no mirror rule")
+        if args.get("use_pcd") and cloud_axis is None:
+            raise ValueError("--mirror_twins with --use_pcd: a stored point cloud has no mirror rule (--cloud_mirror_axis gives it one)")
         config["mirror_twins"] = True
+        if cloud_axis is not None:
+            config["cloud_mirror"] = ["xyz".index(cloud_axis), offset]
     if args.get("replay_every"):
         if int(args["replay_every"]) < 0:
             raise ValueError("--replay_every must not be negative")
         if policy_class != "ACT":
             raise NotImplementedError("--replay_every: the periodic open-loop replay belongs to the ACT training path")
-        if args.get("use_pcd"):
-            raise NotImplementedError("--replay_every with --use_pcd: the device-resident store holds no point clouds; evaluate "
-                                      "with --eval --replay afterwards")
+        if args.get("use_pcd") and not args.get("device_clouds"):
+            raise NotImplementedError("--replay_every with --use_pcd: the device-resident store holds no point clouds (--device_clouds "
+                                      "puts them there); evaluate with --eval --replay afterwards")
         if not args.get("device_dataset"):
             raise ValueError("--replay_every replays validation episodes out of the device-resident store: it needs "
                              "--device_dataset")
@@ -1061,6 +1081,8 @@ def main(args):
                                                use_pcd=use_pcd, max_points=config["policy_config"].get("max_points"),
                                                # --device_dataset: every rank holds its own full store on its own device
                                                device_dataset=device_dataset, mirror_twins=bool(config.get("mirror_twins")),
+                                               device_clouds=bool(config.get("device_clouds")),
+                                               cloud_mirror=tuple(config["cloud_mirror"]) if config.get("cloud_mirror") else None,
                                                device=f"cuda:{local_rank}" if world > 1 else None,     # train_bc's device
                                                device_budget_bytes=(int(config["device_dataset_gb"] * 2**30)
                                                                     if config.get("device_dataset_gb") is not None else None))
@@ -1158,11 +1180,20 @@ def make_parser():
     parser.add_argument("--device_dataset", action="store_true",
                         help="ACT training from --dataset_dir, opt-in: read every episode once into device memory and gather the "
                              "training batches there (actmi.data.DeviceEpisodeStore): the same batches as the host loader, no loader "
-                             "workers; every rank holds the whole dataset; not with --use_pcd")
+                             "workers; every rank holds the whole dataset; with --use_pcd only together with --device_clouds")
+    parser.add_argument("--device_clouds", action="store_true",
+                        help="--device_dataset --use_pcd, opt-in: the task's stored point clouds go into the device-resident store "
+                             "and every batch's clouds are gathered on the device; lifts the refusal of --device_dataset (and of "
+                             "--replay_every) with --use_pcd")
+    parser.add_argument("--cloud_mirror_axis", action="store", type=str, choices=("x", "y", "z"), default=None,
+                        help="--mirror_twins --use_pcd: the twin's stored cloud is the source's reflected across a plane normal to "
+                             "this axis of the clouds' frame; lifts the refusal of --mirror_twins with --use_pcd")
+    parser.add_argument("--cloud_mirror_offset", action="store", type=float, default=0.0,
+                        help="--cloud_mirror_axis: where that plane lies, coordinate -> 2 * offset - coordinate (default 0)")
     parser.add_argument("--mirror_twins", action="store_true",
                         help="ACT training on episode files: join every episode by its mirrored twin (arms and wrist cameras "
                              "swapped, frames flipped, as postprocess_episodes.py defines it), computed as it is read; with "
-                             "--device_dataset the twins take no frame memory; not with --use_pcd, and a directory that already "
+                             "--device_dataset the twins take no frame memory; with --use_pcd only under --cloud_mirror_axis, and a directory that already "
                              "holds mirrored files needs --skip_mirrored_data")
     parser.add_argument("--device_dataset_gb", action="store", type=float, default=None,
                         help="--device_dataset: device memory the store may take, in GiB (default: what is free minus a 64 GiB reserve)")

@@ -920,6 +920,50 @@ typedef struct actmi_gather_mirror_desc {
     int32_t H, W, px_bytes, aligned;
 } actmi_gather_mirror_desc;
 int actmi_op_gather_frames_mirror(const actmi_gather_mirror_desc* d, void* stream);
+/* actmi_op_gather_clouds: the stored point clouds of B samples out of the arena, as the padded batch the engine takes
+ * (actmi_set_pointcloud_n): out_xyz [B][P][3] f32, out_rgb [B][P][3] f32, out_n [B] int32.  items [B] ON THE DEVICE, 8-byte
+ * aligned, one record per sample.  With r = clamp(rows, 0, P), for item b:
+ *   rows [0, r) of out_xyz[b] are the f32 values at arena + xyz_off, value for value: every stored row, the recorder's zero rows
+ *     included, as EpisodicDataset._read_cloud copies them;
+ *   rows [0, r) of out_rgb[b] are the stored colours: rgb_fmt 0 = the arena holds [rows][3] uint8 at arena + rgb_off, each
+ *     converted to f32 (exact; numpy's ascontiguousarray(rgb, dtype=float32)), rgb_fmt 1 = [rows][3] f32, copied;
+ *   rows [r, P) of both are zero (collate_pcd's padding);  out_n[b] = n;
+ *   with flags & 1 the coordinate mirror_axis (0..2) of every copied xyz row becomes mirror_c2 - v: ONE fp32 subtract, rounded on
+ *     its own (0 - 0 gives +0); colours and counts are untouched.  Mirrored and plain items mix freely in one launch.
+ * An item either of whose source ranges (r * 12 bytes of xyz; r * 3 or r * 12 bytes of colours) leaves the arena -- a negative
+ * offset, or offset + bytes > arena_bytes -- is not read at all: both outputs are ZERO over all P rows and out_n[b] = 0.  All
+ * offset arithmetic is 64-bit; nothing is written outside the three outputs, which must not overlap the arena.  Sources may sit
+ * at ANY byte address (a value off a 4-byte boundary is put together from its bytes).
+ * `aligned` is the caller's statement about its layout, as for actmi_op_gather_frames:
+ *   0  general form: every item element by element -- any P, outputs 4-byte aligned (correct, not tuned);
+ *   1  out_xyz and out_rgb are 16-byte aligned and P % 4 == 0 (checked, ACTMI_E_INVALID otherwise).  The kernel looks at each
+ *      item itself: one whose two offsets are multiples of 16 and whose r % 4 == 0 moves as a flat stream of 16-byte words (the
+ *      mirrored component of float j of word v is the one with (4 v + j) % 3 == mirror_axis; one 16-byte word of uint8 colours
+ *      becomes four 16-byte stores); any other item goes element by element, the choice uniform over the workgroup;
+ *   2  as 1 with non-temporal loads of the read-once source.
+ * Grid (splits, B).  ACTMI_E_INVALID before anything runs: B < 0 or B > 65535, P < 1, a null pointer, rgb_fmt, mirror_axis or
+ * aligned out of range.  B == 0: success, nothing launched.  Capturable: one stream, no allocation, no synchronisation, nothing
+ * read on the host. */
+typedef struct actmi_cloud_item {  /* the DEVICE record of one sample: 32 bytes */
+    int64_t xyz_off;           /* byte offset into the arena of the sample's [rows][3] f32 xyz */
+    int64_t rgb_off;           /* ... of its [rows][3] colours (uint8 or f32, rgb_fmt) */
+    int32_t rows;              /* stored rows */
+    int32_t n;                 /* how many of them are points: what out_n receives */
+    int32_t flags;             /* bit 0: mirror */
+    int32_t pad;
+} actmi_cloud_item;
+typedef struct actmi_gather_clouds_desc {
+    const void* arena;
+    int64_t arena_bytes;
+    const actmi_cloud_item* items;   /* [B], on the device */
+    float* out_xyz;            /* [B][P][3] */
+    float* out_rgb;            /* [B][P][3] */
+    int32_t* out_n;            /* [B] */
+    int32_t B, P, rgb_fmt, mirror_axis;
+    float mirror_c2;
+    int32_t aligned;
+} actmi_gather_clouds_desc;
+int actmi_op_gather_clouds(const actmi_gather_clouds_desc* d, void* stream);
 /* actmi_op_gather_chunks: the rest of EpisodicDataset.__getitem__ for B samples, bit for bit.  actions [n_rows][A] and qpos
  * [n_rows][S] hold all episodes' rows back to back, already f32 as the dataset converts them (/base_action columns included);
  * episodes [n_episodes] says where each starts; samples [B][2] int32 = (episode, t) on the device.  With s = is_sim ? t :
