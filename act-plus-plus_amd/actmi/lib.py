@@ -222,6 +222,8 @@ def load():
         "actmi_op_ensemble_episode": ([vp, vp, f64, vp, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_action_error": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], i32),
         "actmi_op_chunk_error": ([vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+        "actmi_op_ensemble_sweep": ([vp, i32, vp, vp, vp, i32, i32, i32, i32, vp], i32),
+        "actmi_op_sweep_error": ([vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp], i32),
         "actmi_op_gemm": ([C.POINTER(GemmDesc), vp], i32),
         "actmi_op_split16": ([vp, vp, C.c_int64, C.c_float, vp], i32),
         "actmi_op_permute_conv_k": ([vp, vp, C.c_int64, i32, i32, i32, vp], i32),

@@ -1997,6 +1997,184 @@ def chunk_error_ref(chunks, actions, lengths, shift, mean, std, stride=1):
     return stats, count
 
 
+# ---- replay schedule sweep: G execution schedules read off one chunk table (csrc/replay_eval.hip; contract at actmi_schedule) -----
+SCHEDULE_ENSEMBLE, SCHEDULE_LATEST = 0, 1
+SCHEDULE_MODES = ("ensemble", "latest")
+
+
+def schedule_dtype():
+    """actmi_schedule as a numpy structured dtype (24 bytes)"""
+    import numpy as np
+    return np.dtype([("every", np.int32), ("horizon", np.int32), ("mode", np.int32), ("reserved", np.int32), ("k", np.float64)])
+
+
+def check_schedules(schedules, Q):
+    """The refusals of a schedule grid for chunks of Q slots, before anything is launched -> the grid as a contiguous
+    ``schedule_dtype()`` array.  ValueError: an empty grid, every < 1, horizon outside [1, Q], horizon < every (such a schedule
+    leaves steps without an action), an unknown mode, a non-finite k, |k| * Q > 700 (exp leaves the float64 range)."""
+    import numpy as np
+    S = np.ascontiguousarray(np.asarray(schedules, dtype=schedule_dtype()).reshape(-1))
+    Q = int(Q)
+    if len(S) == 0:
+        raise ValueError("schedules: the grid is empty")
+    for g, s in enumerate(S):
+        f, h, mode, k = int(s["every"]), int(s["horizon"]), int(s["mode"]), float(s["k"])
+        if f < 1:
+            raise ValueError(f"schedule {g}: every {f} must be at least 1")
+        if not 1 <= h <= Q:
+            raise ValueError(f"schedule {g}: horizon {h} must be in 1..{Q} (the slots of a chunk)")
+        if h < f:
+            raise ValueError(f"schedule {g}: horizon {h} < every {f} leaves steps without an action")
+        if mode not in (SCHEDULE_ENSEMBLE, SCHEDULE_LATEST):
+            raise ValueError(f"schedule {g}: mode {mode} is neither ensemble (0) nor latest (1)")
+        if not np.isfinite(k) or abs(k) * Q > 700.0:
+            raise ValueError(f"schedule {g}: k {k} must be finite with |k| * Q <= 700 (exp(-k * i) stays in the float64 range)")
+    return S
+
+
+def make_schedules(Q, every=(1,), horizon=None, k=(0.01,), latest=True):
+    """The product grid every x horizon x k of ensemble schedules for chunks of Q slots, in that nesting order and without
+    repeats, then (``latest``) one latest-chunk schedule per (every, horizon) pair.  Pairs with horizon < every are left out of
+    the product (they leave steps without an action); every value is checked on its own (``check_schedules``), and a grid in
+    which no pair remains is refused.  horizon None: Q.  -> a ``schedule_dtype()`` array [G]."""
+    import numpy as np
+    Q = int(Q)
+    every = [int(f) for f in np.atleast_1d(every)]
+    horizon = [Q] if horizon is None else [int(h) for h in np.atleast_1d(horizon)]
+    ks = [float(v) for v in np.atleast_1d(k)]
+    if not (every and horizon and ks):
+        raise ValueError("make_schedules: every, horizon and k each need a value")
+    for h in horizon:                                     # (a horizon below 1 would drop out of the pairs unnoticed)
+        if not 1 <= h <= Q:
+            raise ValueError(f"make_schedules: horizon {h} must be in 1..{Q} (the slots of a chunk)")
+    pairs = list(dict.fromkeys((f, h) for f in every for h in horizon if h >= f))
+    if not pairs:
+        raise ValueError(f"make_schedules: every {every} x horizon {horizon} holds no pair with horizon >= every")
+    grid = list(dict.fromkeys((f, h, SCHEDULE_ENSEMBLE, 0, kk) for f, h in pairs for kk in ks))
+    if latest:
+        grid += [(f, h, SCHEDULE_LATEST, 0, 0.0) for f, h in pairs]
+    return check_schedules(grid, Q)
+
+
+def schedules_as_dicts(schedules):
+    """-> [{"every", "horizon", "mode": "ensemble" | "latest", "k"}] (what the replay's result and its JSON hold)"""
+    return [{"every": int(s["every"]), "horizon": int(s["horizon"]), "mode": SCHEDULE_MODES[int(s["mode"])], "k": float(s["k"])}
+            for s in schedules]
+
+
+def device_schedules(schedules, Q, device):
+    """``check_schedules`` and one copy to the device -> uint8 cuda tensor [G, 24], what ``ensemble_sweep`` takes without
+    checking or copying again (a replay uploads its grid once for all episodes)"""
+    S = check_schedules(schedules, Q)
+    return torch.from_numpy(S.view("u1").reshape(len(S), schedule_dtype().itemsize).copy()).to(device)
+
+
+def ensemble_sweep(chunks, schedules, length=None, want_empty=False):
+    """G execution schedules read off one episode's chunk table in one launch (actmi_op_ensemble_sweep).  chunks [T, Q, A] f32
+    cuda: row r is the chunk predicted from frame r; schedules: a ``schedule_dtype()`` array (checked and copied here) or the
+    tensor of ``device_schedules``; length: the valid steps (None: all T) -> raw [G, T, A] f64, and with ``want_empty`` the
+    int32 [G] count of the steps t < length of an ensemble schedule that found no populated live row (they are zeros).  An
+    ensemble schedule (every, horizon, k) gives the bits of ``episode_ensemble`` with that k on the table whose dead entries
+    (r % every != 0 or slot >= horizon) are zeroed; rows t >= length are zeros."""
+    if chunks.dim() != 3 or chunks.dtype != torch.float32 or not chunks.is_cuda:
+        raise ValueError(f"chunks must be a float32 cuda tensor [T, Q, A], got {chunks.dtype} {tuple(chunks.shape)} on {chunks.device}")
+    chunks = chunks.contiguous()
+    T, Q, A = (int(v) for v in chunks.shape)
+    dev = chunks.device
+    if A < 1 or A > 64 or Q < 1 or Q > 7680:
+        raise ValueError(f"ensemble_sweep: action_dim {A} must be in 1..64 and num_queries {Q} in 1..7680 (as episode_ensemble)")
+    if not torch.is_tensor(schedules):
+        schedules = device_schedules(schedules, Q, dev)
+    if (schedules.dtype != torch.uint8 or schedules.dim() != 2 or int(schedules.shape[1]) != schedule_dtype().itemsize
+            or schedules.device != dev or not schedules.is_contiguous()):
+        raise ValueError("ensemble_sweep: schedules must be a schedule_dtype() array or the tensor of device_schedules on the chunks' device")
+    G = int(schedules.shape[0])
+    if G < 1 or G > 65535:
+        raise ValueError(f"ensemble_sweep: {G} schedules, one launch holds 1..65535")
+    n = T if length is None else int(length)
+    raw = torch.empty((G, T, A), dtype=torch.float64, device=dev)
+    empty = torch.empty((G,), dtype=torch.int32, device=dev) if want_empty else None
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_ensemble_sweep(_p(chunks), n, _p(schedules), _p(raw), _p(empty), G, T, Q, A,
+                                                 L.current_stream_ptr()), None, "op_ensemble_sweep")
+    return (raw, empty) if want_empty else raw
+
+
+def ensemble_sweep_ref(chunks, schedules, length=None, want_empty=False):
+    """numpy statement of ``ensemble_sweep``; needs no library.  chunks: ndarray or CPU tensor [T, Q, A]; schedules as
+    ``check_schedules`` takes them -> raw [G, T, A] float64 (and empty [G] int32).  The live rows of a step are selected
+    directly: r in (t - horizon, t], r % every == 0, oldest first."""
+    import numpy as np
+    c = np.asarray(chunks, dtype=np.float32)
+    T, Q, A = c.shape
+    S = check_schedules(schedules, Q)
+    n = T if length is None else int(np.clip(int(length), 0, T))
+    raw = np.zeros((len(S), T, A), dtype=np.float64)
+    empty = np.zeros(len(S), dtype=np.int32)
+    for g, s in enumerate(S):
+        f, h, k = int(s["every"]), int(s["horizon"]), float(s["k"])
+        for t in range(n):
+            if int(s["mode"]) == SCHEDULE_LATEST:
+                r = (t // f) * f
+                raw[g, t] = c[r, t - r].astype(np.float64)
+                continue
+            lo = max(0, t - h + 1)
+            r = np.arange(-(-lo // f) * f, t + 1, f)              # the live frames: multiples of f in [lo, t], oldest first
+            rows = c[r, t - r]                                     # [n, A]
+            rows = rows[np.all(rows != 0, axis=1)]
+            if len(rows):
+                w = np.exp(-k * np.arange(len(rows)))
+                raw[g, t] = (rows.astype(np.float64) * (w / w.sum())[:, None]).sum(axis=0)
+            else:
+                empty[g] += 1
+    return (raw, empty) if want_empty else raw
+
+
+def sweep_error(raw, target, length, mean, std, want_pred=True):
+    """Un-normalise G trajectories and compare each with the ONE recording on the device (actmi_op_sweep_error).  raw [G, T, A]
+    f64 cuda, target [T, A] f32 (file units, already aligned; read by every g, never expanded), length or None (= T), mean / std
+    [A] -> (pred [G, T, A] f64 = raw * std + mean or None, stats [G, 4, A] f64: rows 0-2 = sum |d|, sum d^2, max |d| over
+    t < length, the bits of ``action_error`` on raw[g]; row 3 = sum over 1 <= t < length of |pred[t] - pred[t-1]|, the
+    roughness of the executed trajectory)."""
+    if raw.dim() != 3 or raw.dtype != torch.float64 or not raw.is_cuda:
+        raise ValueError(f"raw must be a float64 cuda tensor [G, T, A], got {raw.dtype} {tuple(raw.shape)} on {raw.device}")
+    raw = raw.contiguous()
+    G, T, A = (int(v) for v in raw.shape)
+    dev = raw.device
+    if G < 1 or G > 65535 or A < 1:
+        raise ValueError(f"sweep_error: {G} schedules (one launch holds 1..65535), action_dim {A}")
+    target = torch.as_tensor(target).to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(target.shape) != (T, A):
+        raise ValueError(f"target has shape {tuple(target.shape)}, expected {(T, A)}")
+    mean, std = (torch.as_tensor(v).to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for v in (mean, std))
+    if mean.numel() != A or std.numel() != A:
+        raise ValueError(f"mean / std hold {mean.numel()} / {std.numel()} values for action_dim {A}")
+    n = T if length is None else int(length)
+    pred = torch.empty((G, T, A), dtype=torch.float64, device=dev) if want_pred else None
+    stats = torch.empty((G, 4, A), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_sweep_error(_p(raw), _p(target), n, _p(mean), _p(std), _p(stats), _p(pred), G, T, A,
+                                              L.current_stream_ptr()), None, "op_sweep_error")
+    return pred, stats
+
+
+def sweep_error_ref(raw, target, length, mean, std, want_pred=True):
+    """numpy statement of ``sweep_error`` (float64); needs no library.  -> (pred, stats [G, 4, A]) as ndarrays."""
+    import numpy as np
+    raw = np.asarray(raw, dtype=np.float64)
+    G, T, A = raw.shape
+    pred = raw * np.asarray(std, dtype=np.float64).reshape(1, 1, A) + np.asarray(mean, dtype=np.float64).reshape(1, 1, A)
+    d = np.abs(pred - np.asarray(target, dtype=np.float32).astype(np.float64).reshape(1, T, A))
+    n = T if length is None else int(np.clip(int(length), 0, T))
+    stats = np.zeros((G, 4, A), dtype=np.float64)
+    for g in range(G):
+        dg = d[g, :n]
+        if len(dg):
+            stats[g, :3] = np.stack([dg.sum(axis=0), (dg * dg).sum(axis=0), dg.max(axis=0)])
+            stats[g, 3] = np.abs(np.diff(pred[g, :n], axis=0)).sum(axis=0)
+    return (pred if want_pred else None), stats
+
+
 # ---- device-resident episode store (csrc/episode_store.hip; contracts at actmi_op_gather_frames / actmi_op_gather_chunks) ------
 def episode_rec_dtype():
     """actmi_episode_rec as a numpy structured dtype (16 bytes)"""

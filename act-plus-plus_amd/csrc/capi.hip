@@ -325,6 +325,31 @@ int actmi_op_chunk_error(const float* chunks, const float* actions, const int32_
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
 }
 
+int actmi_op_ensemble_sweep(const float* chunks, int len, const actmi_schedule* schedules, double* raw, int32_t* empty, int G, int T,
+                            int Q, int A, void* stream) {
+    g_op_error.clear();
+    if (!chunks || !schedules || !raw || T < 0) { g_op_error = "ensemble_sweep: null chunks / schedules / raw or a negative T"; return ACTMI_E_INVALID; }
+    if (A < 1 || A > 64) { g_op_error = "ensemble_sweep: action_dim must be in 1..64 (one lane group per row, as ensemble_episode)"; return ACTMI_E_INVALID; }
+    if (Q < 1 || Q > kEnsembleMaxQ) {
+        g_op_error = "ensemble_sweep: num_queries must be in 1.." + std::to_string(kEnsembleMaxQ) + " (the weights of a step live in LDS)";
+        return ACTMI_E_INVALID;
+    }
+    if (G < 1 || G > 65535) { g_op_error = "ensemble_sweep: the number of schedules must be in 1..65535 (a grid extent)"; return ACTMI_E_INVALID; }
+    const int rc = launch_ensemble_sweep(chunks, len, schedules, raw, empty, G, T, Q, A, S(stream));
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
+int actmi_op_sweep_error(const double* raw, const float* target, int len, const double* mean, const double* stdv, double* stats,
+                         double* pred, int G, int T, int A, void* stream) {
+    g_op_error.clear();
+    if (!raw || !target || !mean || !stdv || !stats || T < 0 || A < 1 || G < 1 || G > 65535) {
+        g_op_error = "sweep_error: null argument, a negative T, action_dim < 1 or a number of schedules outside 1..65535";
+        return ACTMI_E_INVALID;
+    }
+    const int rc = launch_sweep_error(raw, target, len, mean, stdv, stats, pred, G, T, A, S(stream));
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
 int actmi_op_gemm(const actmi_gemm_desc* d, void* stream) {
     if (!d) return ACTMI_E_INVALID;
     g_op_error.clear();

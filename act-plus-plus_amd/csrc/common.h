@@ -209,6 +209,11 @@ int launch_action_error(const double* raw, const float* target, const int32_t* l
 int launch_chunk_error(const float* chunks, const float* actions, const int32_t* lengths, const int32_t* shift, const double* mean,
                        const double* stdv, int stride, double* stats, int32_t* count, int E, int S, int T, int Q, int A,
                        hipStream_t st);
+// G execution schedules read off one episode's table, and their errors against the one recording (replay_eval.hip)
+int launch_ensemble_sweep(const float* chunks, int len, const actmi_schedule* schedules, double* raw, int32_t* empty, int G, int T,
+                          int Q, int A, hipStream_t st);
+int launch_sweep_error(const double* raw, const float* target, int len, const double* mean, const double* stdv, double* stats,
+                       double* pred, int G, int T, int A, hipStream_t st);
 int launch_bn_fold(const float* w, const float* b, const float* rm, const float* rv, float* scale, float* bias, int n,
                    hipStream_t st);
 int launch_build_rowmap(int* map, int B, int C, int fh, int fw, int N, int n_extra, hipStream_t st);

@@ -1,6 +1,7 @@
 // One step of temporal ensembling (reference imitate_episodes.py:402-411) for one 256-thread workgroup: the weights and the
-// accumulation shared by the step kernel (misc.hip: rows from a ring) and the whole-episode kernel (replay_eval.hip: rows
-// straight from the [T][Q][A] table).  Both get the same instructions in the same order, so the same rows give the same bits.
+// accumulation shared by the step kernel (misc.hip: rows from a ring), the whole-episode kernel and the schedule sweep
+// (replay_eval.hip: rows straight from the [T][Q][A] table).  All get the same instructions in the same order, so the same rows
+// give the same bits.
 #pragma once
 #include "common.h"
 
@@ -12,14 +13,21 @@ struct EnsembleLds {
     double* acc;              // [256]
 };
 
+struct EnsembleAllLive {
+    __device__ __forceinline__ bool operator()(int) const { return true; }
+};
+
 // Step t over the candidate rows j = 0..Q-1 (oldest first, r = t-(Q-1)+j, rows with r < 0 do not exist); row(j) -> the A floats
 // chunk_r[t-r].  A row counts only when ALL its A values are != 0 ("actions_populated"); weights exp(-k*i), i = 0 for the OLDEST
 // populated row, normalised; products and sum in float64 as in the reference (numpy float64 weights promote the float32
 // actions).  Every sum has a fixed shape (lane / wave / row-class order), so a step is bitwise repeatable.
+// live(j) -> whether candidate row j takes part at all: it only feeds `pop`, so a row that is not live has weight 0, takes no rank
+// and is never read -- what a row of zeros would do.  The step and episode kernels pass EnsembleAllLive, which folds away.
 // out: A doubles; populated: Q bytes or nullptr.  All 256 threads of the workgroup call it; A <= 64.
-template <typename RowFn>
-__device__ __forceinline__ void ensemble_step_rows(RowFn row, int t, double k, int Q, int A, const EnsembleLds& s,
-                                                   double* __restrict__ out, uint8_t* __restrict__ populated) {
+// -> the number of populated rows (the same value in every thread).
+template <typename RowFn, typename LiveFn>
+__device__ __forceinline__ int ensemble_step_rows(RowFn row, LiveFn live, int t, double k, int Q, int A, const EnsembleLds& s,
+                                                  double* __restrict__ out, uint8_t* __restrict__ populated) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // populated = all A values non-zero (imitate_episodes.py:405-406); weight exp(-k*i) with i = rank of the row among the
     // populated ones (:407-409)
@@ -29,7 +37,7 @@ __device__ __forceinline__ void ensemble_step_rows(RowFn row, int t, double k, i
         const int j = j0 + tid;
         const int r = t - (Q - 1) + j;
         bool pop = false;
-        if (j < Q && r >= 0) {
+        if (j < Q && r >= 0 && live(j)) {
             const float* rw = row(j);
             pop = true;
             for (int a = 0; a < A; ++a) pop = pop && (rw[a] != 0.f);
@@ -71,6 +79,7 @@ __device__ __forceinline__ void ensemble_step_rows(RowFn row, int t, double k, i
         for (int gg = 0; gg < ng; ++gg) tot += s.acc[gg * per + tid];
         out[tid] = tot;
     }
+    return base;
 }
 
 // dynamic LDS the two kernels ask for (Q <= kEnsembleMaxQ, common.h)

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void ensemble_kernel(float* __restrict__ ring,
         const int r = t - (Q - 1) + j;
         return rg + ((int64_t)(r % Q) * Q + (t - r)) * A;
     };
-    ensemble_step_rows(row, t, k, Q, A, lds, out + (int64_t)e * A, populated ? populated + (int64_t)e * Q : nullptr);
+    ensemble_step_rows(row, EnsembleAllLive{}, t, k, Q, A, lds, out + (int64_t)e * A, populated ? populated + (int64_t)e * Q : nullptr);
     if (tid == 0) tcount[e] = t + 1;
 }
 

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void ensemble_episode_kernel(const float* __re
         const int r = t - (Q - 1) + j;                     // 0 <= r <= t < Te
         return ce + ((int64_t)r * Q + (t - r)) * A;
     };
-    ensemble_step_rows(row, t, k, Q, A, lds, o, p);
+    ensemble_step_rows(row, EnsembleAllLive{}, t, k, Q, A, lds, o, p);
 }
 
 // pred = raw * std + mean (two roundings, as numpy) and, per (episode, action component) over t < lengths[e], the sums of
@@ -154,7 +154,126 @@ __global__ __launch_bounds__(256) void chunk_error_kernel(const float* __restric
     }
 }
 
+// G execution schedules read off one episode's chunk table [T][Q][A] (actmi.h: actmi_schedule).  One workgroup per (t, g).
+// Ensemble: candidate row j (r = t-(Q-1)+j) is live iff r % every == 0 and t - r < horizon; the weights and sums are
+// ensemble_step_rows over the live rows, so schedule (1, Q, k) runs the instructions of ensemble_episode_kernel and any other
+// schedule gives the bits of that kernel on the table whose dead entries are zeroed.  Latest: the slot t - r of the chunk of
+// r = (t / every) * every, widened.  A step without a populated live row adds 1 to empty[g] (an integer atomic: exact).
+// 0 <= r <= t < Te <= T and 0 <= t - r < Q for every row that is read, whatever the schedule record says.
+__global__ __launch_bounds__(256) void ensemble_sweep_kernel(const float* __restrict__ chunks, int Te,
+                                                             const actmi_schedule* __restrict__ schedules,
+                                                             double* __restrict__ raw, int32_t* __restrict__ empty, int T, int Q,
+                                                             int A) {
+    extern __shared__ __attribute__((aligned(8))) unsigned char s_raw[];
+    __shared__ int s_cnt[4];
+    __shared__ double s_ws[4];
+    __shared__ double s_acc[256];
+    const EnsembleLds lds{reinterpret_cast<double*>(s_raw), s_cnt, s_ws, s_acc};
+    const int t = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+    double* o = raw + ((int64_t)g * T + t) * A;
+    if (t >= Te) {                                         // uniform over the workgroup
+        if (tid < A) o[tid] = 0.0;
+        return;
+    }
+    const actmi_schedule sc = schedules[g];
+    const int every = sc.every < 1 ? 1 : sc.every;
+    const int horizon = sc.horizon < 1 ? 1 : (sc.horizon > Q ? Q : sc.horizon);
+    if (sc.mode == ACTMI_SCHEDULE_LATEST) {
+        const int r = (t / every) * every, i = t - r;      // 0 <= r <= t; i < every, held to the chunk
+        if (tid < A) o[tid] = i < Q ? (double)chunks[((int64_t)r * Q + i) * A + tid] : 0.0;
+        return;
+    }
+    auto row = [&](int j) -> const float* {
+        const int r = t - (Q - 1) + j;                     // 0 <= r <= t < Te
+        return chunks + ((int64_t)r * Q + (t - r)) * A;
+    };
+    auto live = [&](int j) -> bool {
+        const int r = t - (Q - 1) + j;
+        return r % every == 0 && t - r < horizon;
+    };
+    const int n = ensemble_step_rows(row, live, t, sc.k, Q, A, lds, o, nullptr);
+    if (empty && tid == 0 && n == 0) atomicAdd(empty + g, 1);
+}
+
+// action_error_kernel for G trajectories against ONE target [T][A]: thread shape, walk and unfused arithmetic are that kernel's,
+// so rows 0-2 of stats [G][4][A] are its bits on raw[g].  Row 3: sum over 1 <= t < Te of |pred[t] - pred[t-1]| (pred[t-1] is
+// computed again with the same two roundings), walked and combined in the same fixed order.
+__global__ __launch_bounds__(256) void sweep_error_kernel(const double* __restrict__ raw, const float* __restrict__ target, int Te,
+                                                          const double* __restrict__ mean, const double* __restrict__ stdv,
+                                                          double* __restrict__ pred, double* __restrict__ stats, int T, int A,
+                                                          int per) {
+    __shared__ double s_part[4][256];
+    const int e = blockIdx.y, tid = threadIdx.x;
+    const int al = tid % per, g = tid / per, ng = 256 / per;
+    const int a = blockIdx.x * per + al;
+    double s1 = 0.0, s2 = 0.0, mx = 0.0, s3 = 0.0;
+    if (a < A) {
+        const double sd = stdv[a], mu = mean[a];
+        for (int t = g; t < T; t += ng) {
+            const int64_t i = ((int64_t)e * T + t) * A + a;
+            double p, q = 0.0;
+            {
+#pragma clang fp contract(off)                             // as action_error_kernel: product and sum rounded separately
+                const double prod = raw[i] * sd;
+                p = prod + mu;
+                if (t >= 1) {
+                    const double prev = raw[i - A] * sd;
+                    q = prev + mu;
+                }
+            }
+            if (pred) pred[i] = p;
+            if (t < Te) {
+                const double d = fabs(p - (double)target[(int64_t)t * A + a]);
+                s1 += d;
+                s2 += d * d;
+                mx = fmax(mx, d);
+                if (t >= 1) s3 += fabs(p - q);
+            }
+        }
+    }
+    s_part[0][tid] = s1;
+    s_part[1][tid] = s2;
+    s_part[2][tid] = mx;
+    s_part[3][tid] = s3;
+    __syncthreads();
+    if (tid < per && a < A) {
+        double t1 = 0.0, t2 = 0.0, tm = 0.0, t3 = 0.0;
+        for (int gg = 0; gg < ng; ++gg) {
+            t1 += s_part[0][gg * per + tid];
+            t2 += s_part[1][gg * per + tid];
+            tm = fmax(tm, s_part[2][gg * per + tid]);
+            t3 += s_part[3][gg * per + tid];
+        }
+        double* st = stats + (int64_t)e * 4 * A;
+        st[a] = t1;
+        st[A + a] = t2;
+        st[2 * A + a] = tm;
+        st[3 * A + a] = t3;
+    }
+}
+
 }  // namespace
+
+int launch_ensemble_sweep(const float* chunks, int len, const actmi_schedule* schedules, double* raw, int32_t* empty, int G, int T,
+                          int Q, int A, hipStream_t st) {
+    if (A < 1 || A > 64 || Q < 1 || Q > kEnsembleMaxQ || G < 1 || G > 65535 || T < 0) return -2;
+    if (empty && hipMemsetAsync(empty, 0, (size_t)G * sizeof(int32_t), st) != hipSuccess) return -3;
+    if (T == 0) return 0;
+    const int Te = len < 0 ? 0 : (len > T ? T : len);
+    hipLaunchKernelGGL(ensemble_sweep_kernel, dim3(T, G), dim3(256), ensemble_lds_bytes(Q), st, chunks, Te, schedules, raw, empty, T,
+                       Q, A);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_sweep_error(const double* raw, const float* target, int len, const double* mean, const double* stdv, double* stats,
+                       double* pred, int G, int T, int A, hipStream_t st) {
+    if (G < 1 || G > 65535 || T < 0 || A < 1) return -2;
+    const int Te = len < 0 ? 0 : (len > T ? T : len);
+    const int per = A <= 16 ? 16 : (A <= 32 ? 32 : 64);
+    hipLaunchKernelGGL(sweep_error_kernel, dim3((A + per - 1) / per, G), dim3(256), 0, st, raw, target, Te, mean, stdv, pred, stats,
+                       T, A, per);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 int launch_ensemble_episode(const float* chunks, const int32_t* lengths, double k, double* out, uint8_t* populated, int E, int T,
                             int Q, int A, hipStream_t st) {

@@ -12,6 +12,8 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
   use_pcd policies and of policies trained on real-robot episodes: queries batched over TIME, one ensemble launch per episode;
 * ``--device_dataset --replay_every N`` runs that replay on held-out episodes every N training steps, out of the device-resident
   store the batches come from (no file read); ``--replay_horizon`` adds the error along the predicted chunk;
+* ``--replay_sweep`` reads a grid of execution schedules (query rate, executed horizon, ensemble weight, or the latest chunk
+  alone) off the chunk tables either replay already holds: two more launches per episode, no further policy query;
 * ``--device_dataset --use_pcd --device_clouds`` puts the task's stored point clouds into that store as well (the batches' clouds are
   gathered on the device; ``--replay_every`` then serves point-cloud policies), and ``--mirror_twins --use_pcd --cloud_mirror_axis
   {x,y,z} [--cloud_mirror_offset C]`` gives a stored cloud the mirror rule the twins need;
@@ -424,6 +426,40 @@ def horizon_metrics(rows, num_queries, action_dim):
             "count": [int(c) for c in count]}
 
 
+def replay_sweep_schedules(num_queries, k=None, every=None, horizon=None):
+    """the grid of ``--replay_sweep`` for chunks of Q slots (ops.make_schedules).  The defaults -- k in {-0.1, 0, 0.01, 0.05, 0.25},
+    every in {1, Q/4, Q/2, Q}, horizon in {Q, Q/2}, plus the latest-chunk schedules -- are choices that bracket the reference's
+    two schedules, not measurements"""
+    from actmi.ops import make_schedules
+    Q = int(num_queries)
+    return make_schedules(Q, every=every if every else (1, max(1, Q // 4), max(1, Q // 2), Q),
+                          horizon=horizon if horizon else (Q, max(1, Q // 2)),
+                          k=k if k else (-0.1, 0.0, 0.01, 0.05, 0.25), latest=True)
+
+
+def sweep_metrics(rows, schedules, num_queries, action_dim):
+    """rows [n, 1 + G + 4GA] float64 = per episode (T, the empty steps [G], then per schedule sum |d| [A], sum d^2 [A], max |d| [A],
+    sum |pred[t] - pred[t-1]| [A]) -> the pooled figures of every schedule, in action units.  Sums and counts are added over the
+    episodes and then divided (never an average of averages): the errors by the steps, the roughness by the T - 1 differences of
+    every episode.  ``best``: the lowest mae_mean (the lowest index among equals); ``default``: the index of the schedule the
+    un-swept replay runs, (1, Q, ensemble, 0.01), or None when the grid does not hold it."""
+    from actmi.ops import schedules_as_dicts
+    G, A = len(schedules), action_dim
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 1 + G + 4 * G * A)
+    steps = max(float(rows[:, 0].sum()), 1.0)
+    diffs = max(float(np.maximum(rows[:, 0] - 1.0, 0.0).sum()), 1.0)
+    empty = rows[:, 1:1 + G].sum(axis=0)
+    st = rows[:, 1 + G:].reshape(-1, G, 4, A)
+    s1, s2, s3 = st[:, :, 0].sum(axis=0), st[:, :, 1].sum(axis=0), st[:, :, 3].sum(axis=0)
+    mx = st[:, :, 2].max(axis=0) if len(rows) else np.zeros((G, A))
+    mae_mean = (s1 / steps).mean(axis=1)
+    names = schedules_as_dicts(schedules)
+    default = [g for g, d in enumerate(names) if (d["every"], d["horizon"], d["mode"], d["k"]) == (1, num_queries, "ensemble", 0.01)]
+    return {"schedules": names, "mae_mean": mae_mean.tolist(), "rmse_mean": np.sqrt(s2 / steps).mean(axis=1).tolist(),
+            "max_max": mx.max(axis=1).tolist(), "rough_mean": (s3 / diffs).mean(axis=1).tolist(),
+            "empty": [int(v) for v in empty], "best": int(np.argmin(mae_mean)), "default": default[0] if default else None}
+
+
 def _gather_rows_f64(local, counts):
     """dist_utils.all_gather_rows moves float32 rows; float64 rows travel as their bit pattern (two float32 words per value: the
     collective only copies), so the pooled sums are the same bits with one rank or many"""
@@ -435,7 +471,7 @@ def _gather_rows_f64(local, counts):
 
 def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=None, episode_ensemble=None, align="train",
               save_episode=True, verbose=True, action_error=None, vq_sampler=None, store=None, horizon=False, chunk_error=None,
-              attention=False, attention_slots=None, attention_frames=False):
+              attention=False, attention_slots=None, attention_frames=False, sweep=None, ensemble_sweep=None, sweep_error=None):
     """Open-loop replay evaluation on recorded episodes (the fork's eval_arm_gripper_depth.py:343-418 without its plots): the
     policy is queried on an episode's recorded observations, the chunks are ensembled over time (``temporal_agg``) or executed
     chunk by chunk, un-normalised, and compared with the recorded ``/action``.  Serves what ``eval_bc`` cannot roll out --
@@ -471,6 +507,16 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     the share over all queried steps (sums divided by the count).  ``attention_frames``: also the queried steps' uint8 frames
     with the RGB maps laid over them (ops.heat_overlay with ops.heat_ramp) as replay_<ckpt>_ep<i>_attn_frames.npy
     [S, K, H, W, 3].  The queries, and with them every error figure, are the same bits with or without it.
+    ``sweep`` (``--replay_sweep``; an ``ops.schedule_dtype()`` array, see ``ops.make_schedules``): G execution schedules -- query
+    every f frames, execute the first h slots of a chunk, ensemble weight k or just the latest chunk -- read off the table the
+    replay already holds, with no further policy query: per episode one ``ops.ensemble_sweep`` and one ``ops.sweep_error`` launch
+    after the existing ones (``ensemble_sweep=``, ``sweep_error=``: ops.ensemble_sweep_ref and ops.sweep_error_ref are the CPU
+    stand-ins).  It needs ``temporal_agg`` -- the table must hold a chunk for every frame, and the stride-Q table is not derived
+    from it: a frame's a_hat is not promised to be independent of its batch mates -- else ValueError.  The rows are pooled over
+    the episodes and ranks like the others into ``result["sweep"] = {"schedules": [{every, horizon, mode, k}], "mae_mean" [G],
+    "rmse_mean" [G], "max_max" [G], "rough_mean" [G] (the mean |pred[t] - pred[t-1]| per step and joint: the smoothness a schedule
+    gives up), "empty" [G] (steps without a populated live row), "best", "default"}`` (``sweep_metrics``), in action units.  Every
+    other key, file and printed figure is the same bits with or without it.
     Returns {"episodes": [...], "mae": [A], "rmse": [A], "max": [A], "mae_mean", "rmse_mean", "max_max", "steps", ...} in
     action units; with ``save_episode`` rank 0 writes replay_<ckpt>.json and per episode replay_<ckpt>_ep<i>.npz (pred, target)."""
     import json
@@ -510,6 +556,17 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     if horizon and chunk_error is None:
         from actmi import ops
         chunk_error = ops.chunk_error
+    sched = None
+    if sweep is not None:
+        from actmi import ops
+        if not temporal_agg:
+            raise ValueError("replay_bc(sweep=...) reads the schedules off the table of a chunk for EVERY frame: it needs temporal_agg "
+                             "(--temporal_agg)")
+        sweep = ops.check_schedules(sweep, Q)
+        if ensemble_sweep is None:
+            sched = ops.device_schedules(sweep, Q, dev)              # checked and uploaded once for all episodes
+        ensemble_sweep = ensemble_sweep or ops.ensemble_sweep
+        sweep_error = sweep_error or ops.sweep_error
     attn = None
     if attention_frames and not attention:
         raise ValueError("replay_bc: attention_frames overlays the attention maps: it needs attention=True")
@@ -554,7 +611,7 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     if mean.shape[0] != A or std.shape[0] != A:
         raise ValueError(f"the dataset statistics hold {mean.shape[0]} action components, the policy's action_dim is {A}")
 
-    local_rows, local_pt, local_hz, local_share = [], [], [], []
+    local_rows, local_pt, local_hz, local_share, local_sw = [], [], [], [], []
     time0, n_frames = time.time(), 0
     stride = 1 if temporal_agg else Q
     stem = "replay_" + ckpt_name.split(".")[0] if save_episode else None          # (a periodic replay saves nothing and has no name)
@@ -615,6 +672,12 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
             hst, hcnt = chunk_error(table, actions[None], None, [shift], mean, std, stride)
             local_hz.append(torch.cat([torch.as_tensor(hcnt).to(torch.float64).cpu().reshape(1, Q),
                                        torch.as_tensor(hst).to(torch.float64).cpu().reshape(1, Q * 3 * A)], dim=1))
+        if sweep is not None:
+            sraw, sempty = ensemble_sweep(table[0], sweep if sched is None else sched, None, want_empty=True)
+            _, sst = sweep_error(torch.as_tensor(sraw).to(torch.float64), target[0], None, mean, std, want_pred=False)
+            local_sw.append(torch.cat([torch.tensor([[float(T)]], dtype=torch.float64),
+                                       torch.as_tensor(sempty).to(torch.float64).cpu().reshape(1, -1),
+                                       torch.as_tensor(sst).to(torch.float64).cpu().reshape(1, -1)], dim=1))
         if save_episode:
             local_pt.append(torch.cat([torch.as_tensor(pred).to(torch.float64).cpu().reshape(T, A),
                                        target[0].to(torch.float64).cpu()], dim=1))
@@ -634,6 +697,10 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     if horizon:
         mine = torch.cat(local_hz, dim=0) if local_hz else torch.zeros((0, Q * (1 + 3 * A)), dtype=torch.float64)
         result["horizon"] = horizon_metrics(_gather_rows_f64(mine, [b - a for a, b in spans]).numpy(), Q, A)
+    if sweep is not None:
+        G = len(sweep)
+        mine = torch.cat(local_sw, dim=0) if local_sw else torch.zeros((0, 1 + G + 4 * G * A), dtype=torch.float64)
+        result["sweep"] = sweep_metrics(_gather_rows_f64(mine, [b - a for a, b in spans]).numpy(), sweep, Q, A)
     if attn is not None:
         ns = layout.n_sources
         mine = torch.cat(local_share, dim=0) if local_share else torch.zeros((0, 1 + ns), dtype=torch.float64)
@@ -667,6 +734,14 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
             for j in horizon_slots(Q):
                 print(f"slot {j:4d}: MAE {hz['mae_mean'][j]:10.5f} over the joints, {hz['count'][j]} pairs "
                       f"(the action {j} steps ahead of the query)")
+        if sweep is not None:
+            sw = result["sweep"]
+            print(f"\nSchedule sweep, {len(sw['schedules'])} schedules read off the same chunk tables (mean over the joints, action units):")
+            print("   g every horizon     mode        k        MAE       RMSE        max  roughness  empty")
+            for g, d in enumerate(sw["schedules"]):
+                mark = " ".join(m for m, i in (("<- best", sw["best"]), ("<- default", sw["default"])) if i == g)
+                print(f"{g:4d} {d['every']:5d} {d['horizon']:7d} {d['mode']:>8s} {d['k']:8.4f} {sw['mae_mean'][g]:10.5f} "
+                      f"{sw['rmse_mean'][g]:10.5f} {sw['max_max'][g]:10.5f} {sw['rough_mean'][g]:10.5f} {sw['empty'][g]:6d} {mark}")
         if attn is not None:
             at = result["attention"]
             print(f"attention share per source, action slots {at['slots'][0]}..{at['slots'][1] - 1}, mean over {at['steps']} queries:")
@@ -781,6 +856,8 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
         if config.get("replay_episodes") is not None:
             replay_ids = replay_ids[:int(config["replay_episodes"])]
     replay_history, best_replay = [], None
+    replay_sweep = (replay_sweep_schedules(policy_config["num_queries"], **config["replay_sweep"])
+                    if replay_every and config.get("replay_sweep") is not None else None)
     # data parallel (one process per GPU under torch.distributed.run): every rank builds the same initial policy on its own
     # device, draws ITS OWN batches and dropout masks (seed + rank), averages gradients over RCCL in loss.backward(); only
     # rank 0 writes checkpoints
@@ -851,12 +928,18 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
             policy.eval()
             res = replay_bc(config, None, policy=policy, stats=replay_store.norm_stats, store=replay_store, episodes=replay_ids,
                             align=config.get("replay_align") or "train", save_episode=False, verbose=(rank == 0),
-                            horizon=bool(config.get("replay_horizon")))
+                            horizon=bool(config.get("replay_horizon")), sweep=replay_sweep)
             figures = {"replay_mae_mean": res["mae_mean"], "replay_rmse_mean": res["rmse_mean"], "replay_max_max": res["max_max"]}
             if "horizon" in res:
                 for j in horizon_slots(int(policy_config["num_queries"])):
                     figures[f"replay_h{j}_mae"] = res["horizon"]["mae_mean"][j]
-            replay_history.append(dict(figures, step=step, steps=res["steps"], episodes=len(res["episodes"])))
+            if "sweep" in res:                                   # (the best checkpoint stays chosen by the default schedule's MAE)
+                sw = res["sweep"]
+                figures.update(replay_sweep_best_mae=sw["mae_mean"][sw["best"]], replay_sweep_best=sw["best"])
+                if sw["default"] is not None:
+                    figures["replay_sweep_default_mae"] = sw["mae_mean"][sw["default"]]
+            replay_history.append(dict(figures, step=step, steps=res["steps"], episodes=len(res["episodes"]),
+                                       **({"sweep": res["sweep"]} if "sweep" in res else {})))
             if best_replay is None or res["mae_mean"] < best_replay[1]:
                 best_replay = (step, res["mae_mean"], deepcopy(policy.serialize()))
             if log:
@@ -1021,6 +1104,16 @@ def build_config(args):
                 raise ValueError(f"--replay_attention_slots {slots}: needs 0 <= Q0 < Q1 <= chunk_size {args['chunk_size']}")
         config.update(replay_attention=True, replay_attention_slots=slots,
                       replay_attention_frames=bool(args.get("replay_attention_frames")))
+    sweep_lists = {key: args.get("replay_sweep_" + key) for key in ("k", "every", "horizon")}
+    if any(v is not None for v in sweep_lists.values()) and not args.get("replay_sweep"):
+        raise ValueError("--replay_sweep_k, --replay_sweep_every and --replay_sweep_horizon are the grid of --replay_sweep")
+    if args.get("replay_sweep"):
+        if not ((args.get("eval") and args.get("replay")) or args.get("replay_every")):
+            raise ValueError("--replay_sweep reads execution schedules off an open-loop replay: it needs --eval --replay or --replay_every")
+        if not args.get("temporal_agg"):
+            raise ValueError("--replay_sweep needs --temporal_agg: the schedules are read off the table of a chunk for every frame")
+        replay_sweep_schedules(int(args["chunk_size"]), **sweep_lists)          # the grid's refusals, before anything is loaded
+        config["replay_sweep"] = sweep_lists
     return config
 
 
@@ -1038,7 +1131,9 @@ def main(args):
         return replay_bc(config, "policy_last.ckpt", episodes=args.get("replay_episodes"),
                          align=args.get("replay_align") or "train", save_episode=True, horizon=bool(args.get("replay_horizon")),
                          attention=bool(config.get("replay_attention")), attention_slots=config.get("replay_attention_slots"),
-                         attention_frames=bool(config.get("replay_attention_frames")))
+                         attention_frames=bool(config.get("replay_attention_frames")),
+                         sweep=(replay_sweep_schedules(config["policy_config"]["num_queries"], **config["replay_sweep"])
+                                if config.get("replay_sweep") is not None else None))
     if args["eval"]:
         results = []
         for ckpt_name in ["policy_last.ckpt"]:
@@ -1166,6 +1261,18 @@ def make_parser():
     parser.add_argument("--replay_horizon", action="store_true",
                         help="--replay_every and --eval --replay: also the error of slot j of a predicted chunk against the action j "
                              "steps ahead (how the error grows along the chunk)")
+    parser.add_argument("--replay_sweep", action="store_true",
+                        help="--eval --replay and --replay_every, with --temporal_agg: read a grid of execution schedules (query every "
+                             "F frames, execute the first H slots of a chunk, ensemble weight K or just the latest chunk) off the "
+                             "chunk tables the replay already holds -- two more launches per episode, no further policy query -- and "
+                             "report the error and the roughness of each.  Default grid: K in {-0.1, 0, 0.01, 0.05, 0.25}, F in "
+                             "{1, Q/4, Q/2, Q}, H in {Q, Q/2}, plus the latest-chunk schedules: choices, not measurements")
+    parser.add_argument("--replay_sweep_k", action="store", type=float, nargs="+", default=None, metavar="K",
+                        help="--replay_sweep: the ensemble weights exp(-K * i) of the grid (K < 0 favours the newest chunk)")
+    parser.add_argument("--replay_sweep_every", action="store", type=int, nargs="+", default=None, metavar="F",
+                        help="--replay_sweep: the query rates of the grid (a chunk from every F-th frame)")
+    parser.add_argument("--replay_sweep_horizon", action="store", type=int, nargs="+", default=None, metavar="H",
+                        help="--replay_sweep: the executed slots of a chunk (F <= H <= chunk_size; pairs with H < F are left out)")
     parser.add_argument("--augment_images", action="store_true",
                         help="ACT training only, opt-in: the reference dataset's augmentation (random 0.95 crop resized back, rotation "
                              "within 5 degrees, brightness / contrast / saturation jitter) on the device, for training batches; the "

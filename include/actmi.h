@@ -413,6 +413,37 @@ int actmi_op_chunk_error(const float* chunks, const float* actions, const int32_
                          const double* mean, const double* std, int stride, double* stats, int32_t* count,
                          int E, int S, int T, int Q, int A, void* stream);
 
+/* ---- replay schedule sweep: G execution schedules read off ONE chunk table ------------------------------ */
+/* A schedule executes the chunks of every `every`-th frame for `horizon` slots.  The chunk predicted from frame r is LIVE at
+ * step t for slot t - r iff r % every == 0, 0 <= t - r < horizon and r < len.
+ * mode ACTMI_SCHEDULE_ENSEMBLE: step t is the temporal ensemble of actmi_op_ensemble_episode over the live rows only -- a row
+ * counts when it is live and all its A values are non-zero, weights exp(-k * i) with i the rank among those rows, oldest
+ * first, float64 products and sums -- which is that op with weight k on the table whose dead entries are zeroed
+ * (M[r][i] = chunk[r][i] if r % every == 0 and i < horizon, else 0): a zero row is not populated and takes no rank.
+ * mode ACTMI_SCHEDULE_LATEST: raw[t] = (double)chunk[r][t - r] with r = (t / every) * every, no populated test, k unused. */
+enum { ACTMI_SCHEDULE_ENSEMBLE = 0, ACTMI_SCHEDULE_LATEST = 1 };
+typedef struct actmi_schedule {                   /* the DEVICE record of one schedule: 24 bytes */
+    int32_t every;                                /* query every `every` frames, >= 1 */
+    int32_t horizon;                              /* execute the first `horizon` slots of a chunk, every <= horizon <= Q */
+    int32_t mode;                                 /* ACTMI_SCHEDULE_* */
+    int32_t reserved;                             /* 0 */
+    double k;                                     /* the ensemble weight; k < 0 favours the newest chunk */
+} actmi_schedule;
+/* One episode: chunks [T][Q][A] f32 (row r is the chunk predicted from frame r), len valid steps (clamped to 0..T), schedules
+ * [G] on the DEVICE; raw [G][T][A] f64; empty [G] i32 or NULL = the steps t < len of an ensemble schedule without a populated
+ * live row (they give zeros; 0 for a latest schedule).  One workgroup per (t, g); a dead row is never read; rows t >= len are
+ * zeros.  The HOST vouches for the schedules (every >= 1, every <= horizon <= Q, finite k with |k| * Q <= 700); the kernel
+ * holds every index to the table whatever they say.  ACTMI_E_INVALID with a message: A > 64, Q > 7680 (as
+ * actmi_op_ensemble_episode), G > 65535 or G < 1, a null chunks / schedules / raw.  T == 0: ACTMI_OK without a launch. */
+int actmi_op_ensemble_sweep(const float* chunks, int len, const actmi_schedule* schedules, double* raw, int32_t* empty,
+                            int G, int T, int Q, int A, void* stream);
+/* raw [G][T][A] f64, target [T][A] f32 (file units, already aligned; ONE copy, read by every g), mean / std [A] f64; pred
+ * [G][T][A] f64 or NULL = raw * std + mean; stats [G][4][A] f64: rows 0-2 = sum |d|, sum d^2, max |d| over t < len with the
+ * thread shape and arithmetic of actmi_op_action_error (the same bits as that op on raw[g]), row 3 = the roughness of the
+ * executed trajectory, sum over 1 <= t < len of |pred[t] - pred[t-1]|, combined in the same fixed order. */
+int actmi_op_sweep_error(const double* raw, const float* target, int len, const double* mean, const double* std,
+                         double* stats, double* pred, int G, int T, int A, void* stream);
+
 /* ---- kernel-level entry points (unit tests, external callers) --------------------------------------- */
 int actmi_op_gemm(const actmi_gemm_desc* d, void* stream);
 /* weight preparation for actmi_gemm_desc.b_split: dst = fp16-split image of src * scale (device pointers, may not
