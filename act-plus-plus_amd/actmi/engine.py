@@ -73,6 +73,7 @@ class ACTEngine:
         self._fusion = None            # ops.RGBDFusion registered by set_rgbd_fusion: pointcloud={"depth": u16 frames} is fused on the device
         self._phase = 0
         self.attention_out = None      # the tensor bound by bind_attention (kept alive here)
+        self.features_out = None       # the tensor bound by bind_features (kept alive here)
         # attributes imitate_episodes.py touches on policy.model
         self.num_queries = cfg.num_queries
         self.encoder = None if cfg.no_encoder else True
@@ -344,6 +345,33 @@ class ACTEngine:
                              f"got {buf.dtype} {tuple(buf.shape)}")
         L.check(self.lib.actmi_bind_attention_out(self.h, C.c_void_p(buf.data_ptr()), buf.shape[0]), self.h, "bind_attention_out")
         self.attention_out = buf
+
+    # ---- the trunk embedding ------------------------------------------------------------------
+    @property
+    def feature_dim(self):
+        """columns of the bound feature buffer: the RGB cameras times the channels of a layer4 map"""
+        return len(self.cfg.camera_names) * 8 * self.cfg.base_width
+
+    def bind_features(self, buf):
+        """Bind a float32 [B, feature_dim] device tensor (None: unbind).  While one is bound every forward_infer of at most B samples
+        that runs the trunk (whole, or phase 1 of set_forward_phase) leaves the spatial mean of each RGB camera's layer4 map of its
+        samples in buf[:batch], camera c in columns [c * F, (c + 1) * F), F = 8 * base_width (actmi_bind_features_out; depth
+        cameras are left out); a larger batch is refused.  The engine keeps the tensor alive.  a_hat does not depend on the
+        binding, and unbound the forward launches what it always did.  A captured graph keeps the binding it was captured with,
+        as with bind_attention: every replay writes the tensor it was captured with, so the caller keeps that tensor alive for as
+        long as the graph is replayed -- unbinding releases only the engine's own reference."""
+        if buf is None:
+            L.check(self.lib.actmi_bind_features_out(self.h, None, 0), self.h, "bind_features_out")
+            self.features_out = None
+            return
+        if not isinstance(buf, torch.Tensor) or not buf.is_cuda:
+            raise ValueError("the feature buffer must be a CUDA tensor on the engine's device")
+        self._check_dev(features=buf)
+        if buf.dtype != torch.float32 or buf.dim() != 2 or buf.shape[1] != self.feature_dim or buf.shape[0] < 1 or not buf.is_contiguous():
+            raise ValueError(f"the feature buffer must be a contiguous float32 [B, {self.feature_dim}] tensor, "
+                             f"got {buf.dtype} {tuple(buf.shape)}")
+        L.check(self.lib.actmi_bind_features_out(self.h, C.c_void_p(buf.data_ptr()), buf.shape[0]), self.h, "bind_features_out")
+        self.features_out = buf
 
     def set_forward_phase(self, phase: int):
         """0: forward_infer runs the whole step; 1: trunk + token assembly only; 2: transformer only (actmi_set_forward_phase)"""

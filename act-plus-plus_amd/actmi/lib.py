@@ -235,6 +235,11 @@ def load():
         "actmi_op_heat_overlay_u8": ([vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
         "actmi_bind_attention_out": ([vp, vp, i32], i32),
         "actmi_attention_layout": ([vp, C.POINTER(AttnLayout)], i32),
+        "actmi_bind_features_out": ([vp, vp, i32], i32),
+        "actmi_op_knn_workspace_bytes": ([i64, i64], i64),
+        "actmi_op_knn_topk": ([vp, vp, vp, vp, vp, vp, f32, i32, i64, i64, i32, i32, vp, vp, vp, vp, i64, vp], i32),
+        "actmi_op_knn_predict": ([vp, vp, vp, i32, i32, vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, i64, vp], i32),
+        "actmi_op_knn_ksweep": ([vp, vp, vp, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, i64, vp], i32),
         "actmi_op_attention_bwd": ([C.POINTER(AttnBwdDesc), vp], i32),
         "actmi_op_layernorm": ([vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp], i32),
         "actmi_op_layernorm_ex": ([vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, C.c_uint32, i32, i32,

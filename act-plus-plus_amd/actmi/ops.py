@@ -2375,3 +2375,261 @@ def gather_chunks_ref(actions, qpos, episodes, samples, action_mean, action_std,
         action_out[b] = (rows - am) / asd
         is_pad[b, n:] = True
     return qpos_out, action_out, is_pad
+
+
+# ---- nearest-neighbour action retrieval (csrc/knn.hip; contracts at actmi_op_knn_topk / _predict / _ksweep) ------------------
+KNN_MAX_K = 512
+
+
+def check_knn_args(K, state_weight, support_rows=None):
+    """The refusals every kNN entry shares, raised before anything is launched: K in [1, 512] and at most the support rows (when
+    given), state_weight finite and not negative.  -> (K, state_weight)"""
+    import math
+    if isinstance(K, bool) or int(K) != K or not 1 <= int(K) <= KNN_MAX_K:
+        raise ValueError(f"kNN: K must be an integer in [1, {KNN_MAX_K}], got {K!r}")
+    K = int(K)
+    if support_rows is not None and K > int(support_rows):
+        raise ValueError(f"kNN: K = {K} exceeds the {int(support_rows)} support rows")
+    w = float(state_weight)
+    if not math.isfinite(w) or w < 0:
+        raise ValueError(f"kNN: state_weight must be finite and not negative, got {state_weight!r}")
+    return K, w
+
+
+def _knn_sqnorm_ref(a, b):
+    """[Nq, Ns] fp32 squared distances in the ABI's summation order: partial sum j takes the dimensions d = j (mod 4) ascending,
+    one subtract, one multiply and one add per term, and the four combine as (p0 + p1) + (p2 + p3)."""
+    import numpy as np
+    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
+    p = np.zeros((4, a.shape[0], b.shape[0]), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        for d in range(a.shape[1]):
+            diff = a[:, None, d] - b[None, :, d]
+            p[d & 3] = p[d & 3] + diff * diff
+        return (p[0] + p[1]) + (p[2] + p[3])
+
+
+def knn_topk_ref(qv, qs, sv, ss, K, state_weight=1.0, sep=None, exclude=None):
+    """numpy statement of ``knn_topk``: fp32 distances in the stated order, the K eligible rows of smallest (distance bits, index).
+    -> (idx [Nq, K] int32, dist [Nq, K] f32, n [Nq] int32); needs no library."""
+    import numpy as np
+    qv, sv = np.asarray(qv, dtype=np.float32), np.asarray(sv, dtype=np.float32)
+    Nq, Ns = qv.shape[0], sv.shape[0]
+    K = int(K)
+    with np.errstate(all="ignore"):
+        dv = np.sqrt(_knn_sqnorm_ref(qv, sv))
+        if qs is not None and np.asarray(qs).shape[1] > 0:
+            dsn = np.sqrt(_knn_sqnorm_ref(qs, ss))
+        else:
+            dsn = np.zeros((Nq, Ns), dtype=np.float32)
+        d = (dv + np.float32(state_weight) * dsn).astype(np.float32)
+    ok = np.isfinite(d)
+    if exclude is not None:
+        ex = np.asarray(exclude, dtype=np.int64).reshape(Nq, 1)
+        ok &= ~((ex >= 0) & (np.asarray(sep, dtype=np.int64).reshape(1, Ns) == ex))
+    idx = np.full((Nq, K), -1, dtype=np.int32)
+    dist = np.full((Nq, K), np.inf, dtype=np.float32)
+    n = np.zeros(Nq, dtype=np.int32)
+    for q in range(Nq):
+        rows = np.nonzero(ok[q])[0]
+        key = (d[q, rows].view(np.uint32).astype(np.uint64) << np.uint64(32)) | rows.astype(np.uint64)
+        order = rows[np.argsort(key, kind="stable")][:K]
+        n[q] = len(order)
+        idx[q, :len(order)] = order
+        dist[q, :len(order)] = d[q, order]
+    return idx, dist, n
+
+
+def knn_predict_ref(idx, dist, n, k, actions, off, left, Q, mean=None, std=None):
+    """numpy statement of ``knn_predict`` (float64, neighbour order; needs no library) -> (chunk [Nq, Q, A] f32, empty)."""
+    import numpy as np
+    idx, n = np.asarray(idx, dtype=np.int64), np.asarray(n, dtype=np.int64)
+    dist = np.asarray(dist, dtype=np.float32).astype(np.float64)
+    actions = np.asarray(actions, dtype=np.float32).astype(np.float64)
+    off, left = np.asarray(off, dtype=np.int64), np.asarray(left, dtype=np.int64)
+    Nq, A, Q = idx.shape[0], actions.shape[1], int(Q)
+    out = np.zeros((Nq, Q, A), dtype=np.float32)
+    empty = 0
+    j = np.arange(Q)
+    for q in range(Nq):
+        m = int(min(int(k), n[q]))
+        if m <= 0:
+            empty += 1
+            continue
+        e = np.exp(-(dist[q, :m] - dist[q, 0]))
+        num, den = np.zeros((Q, A)), 0.0
+        for i in range(m):
+            s = idx[q, i]
+            rows = off[s] + np.minimum(j, max(int(left[s]), 1) - 1)
+            num = num + e[i] * actions[rows]
+            den = den + e[i]
+        v = num / den
+        if mean is not None:
+            v = (v - np.asarray(mean, dtype=np.float64).reshape(1, A)) / np.asarray(std, dtype=np.float64).reshape(1, A)
+        out[q] = v.astype(np.float32)
+    return out, empty
+
+
+def knn_ksweep_ref(idx, dist, n, actions, off, target, mean=None, std=None, want_partial=False):
+    """numpy statement of ``knn_ksweep``: sse [K] float64, sse[k - 1] = the squared error of slot 0 of ``knn_predict_ref`` at k
+    against target [Nq, A], the queries added in order.  ``want_partial``: also the per-query terms [Nq, K]."""
+    import numpy as np
+    idx = np.asarray(idx)
+    Nq, K = idx.shape
+    target = np.asarray(target, dtype=np.float32).astype(np.float64)
+    left = np.ones(len(np.asarray(off)), dtype=np.int64)
+    partial = np.zeros((Nq, K), dtype=np.float64)
+    for k in range(1, K + 1):
+        pred, _ = knn_predict_ref(idx, dist, n, k, actions, off, left, 1, mean, std)
+        d = pred[:, 0].astype(np.float64) - target
+        dd = d * d
+        s = np.zeros(Nq)
+        for a in range(dd.shape[1]):
+            s = s + dd[:, a]
+        partial[:, k - 1] = s
+    sse = np.zeros(K)
+    for q in range(Nq):
+        sse = sse + partial[q]
+    return (sse, partial) if want_partial else sse
+
+
+def pooled_features_ref(layer4, B, C, fh, fw):
+    """numpy statement of the bound trunk embedding (actmi_bind_features_out): layer4 camera-major [C, B, fh, fw, F] (any shape of
+    that many values) -> [B, C * F] f32: an fp32 sum over the fh * fw positions in row-major order, one add at a time, then one
+    fp32 divide by float(fh * fw)."""
+    import numpy as np
+    m = np.asarray(layer4, dtype=np.float32).reshape(C, B, fh * fw, -1)
+    s = np.zeros((C, B, m.shape[3]), dtype=np.float32)
+    for p in range(fh * fw):
+        s = s + m[:, :, p]
+    s = s / np.float32(fh * fw)
+    return np.ascontiguousarray(s.transpose(1, 0, 2).reshape(B, -1))
+
+
+def _knn_f32(name, t, dev, cols=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or (dev is not None and t.device != dev):
+        raise ValueError(f"knn: {name} must be a 2-D float32 cuda tensor on one device")
+    if cols is not None and t.shape[1] != cols:
+        raise ValueError(f"knn: {name} has {t.shape[1]} columns, expected {cols}")
+    return t.contiguous()
+
+
+def knn_topk(qv, qs, sv, ss, K, state_weight=1.0, sep=None, exclude=None, ws=None):
+    """actmi_op_knn_topk.  qv [Nq, Dv], qs [Nq, S] or None, sv [Ns, Dv], ss [Ns, S] or None (f32 cuda), sep [Ns] / exclude [Nq]
+    int32 cuda or None -> (idx [Nq, K] int32, dist [Nq, K] f32, n [Nq] int32).  ``ws``: a uint8 cuda tensor of at least
+    ``knn_workspace_bytes(Nq, Ns)`` bytes to reuse between calls."""
+    K, w = check_knn_args(K, state_weight)
+    qv = _knn_f32("qv", qv, None)
+    dev = qv.device
+    sv = _knn_f32("sv", sv, dev, qv.shape[1])
+    Nq, Ns, Dv = int(qv.shape[0]), int(sv.shape[0]), int(qv.shape[1])
+    if Nq < 1 or Ns < 1 or Dv < 1:
+        raise ValueError(f"knn_topk: Nq = {Nq}, Ns = {Ns}, Dv = {Dv} must each be at least 1")
+    S = 0
+    if qs is not None and qs.shape[1] > 0:
+        qs = _knn_f32("qs", qs, dev)
+        S = int(qs.shape[1])
+        ss = _knn_f32("ss", ss, dev, S)
+        if qs.shape[0] != Nq or ss.shape[0] != Ns:
+            raise ValueError("knn_topk: the state rows do not match the feature rows")
+    else:
+        qs = ss = None
+    if exclude is not None:
+        if sep is None:
+            raise ValueError("knn_topk: exclude needs the support rows' episode ids (sep)")
+        for name, t, rows in (("sep", sep, Ns), ("exclude", exclude, Nq)):
+            if t.dtype != torch.int32 or t.device != dev or t.numel() != rows or not t.is_contiguous():
+                raise ValueError(f"knn_topk: {name} must be a contiguous int32 tensor of {rows} values on {dev}")
+    else:
+        sep = None
+    lib = L.load()
+    need = int(lib.actmi_op_knn_workspace_bytes(Nq, Ns))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif ws.dtype != torch.uint8 or ws.device != dev or ws.numel() < need:
+        raise ValueError(f"knn_topk: the workspace must be a uint8 tensor of at least {need} bytes on {dev}")
+    idx = torch.empty((Nq, K), dtype=torch.int32, device=dev)
+    dist = torch.empty((Nq, K), dtype=torch.float32, device=dev)
+    n = torch.empty(Nq, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.actmi_op_knn_topk(_p(qv), _p(qs), _p(sv), _p(ss), _p(sep), _p(exclude), w, K, Nq, Ns, Dv, S, _p(idx), _p(dist),
+                                      _p(n), _p(ws), ws.numel(), L.current_stream_ptr()), None, "op_knn_topk")
+    return idx, dist, n
+
+
+def knn_workspace_bytes(Nq, Ns):
+    return int(L.load().actmi_op_knn_workspace_bytes(int(Nq), int(Ns)))
+
+
+def _knn_neighbours(idx, dist, n):
+    dev = idx.device
+    if idx.dtype != torch.int32 or dist.dtype != torch.float32 or n.dtype != torch.int32 or idx.dim() != 2 or dist.shape != idx.shape \
+            or n.numel() != idx.shape[0] or not idx.is_cuda or dist.device != dev or n.device != dev:
+        raise ValueError("knn: idx [Nq, K] int32, dist [Nq, K] float32 and n [Nq] int32 must be cuda tensors of one device")
+    return idx.contiguous(), dist.contiguous(), n.contiguous()
+
+
+def _knn_stats(mean, std, A, dev):
+    if (mean is None) != (std is None):
+        raise ValueError("knn: mean and std come together")
+    if mean is None:
+        return None, None
+    mean, std = (torch.as_tensor(v).to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for v in (mean, std))
+    if mean.numel() != A or std.numel() != A:
+        raise ValueError(f"knn: mean / std hold {mean.numel()} / {std.numel()} values for action_dim {A}")
+    return mean, std
+
+
+def _knn_rows(actions, off, left, dev):
+    if actions.dtype != torch.float32 or actions.dim() != 2 or actions.device != dev or not actions.is_contiguous():
+        raise ValueError("knn: actions must be a contiguous float32 [R, A] tensor on the neighbours' device")
+    if off.dtype != torch.int64 or off.device != dev or off.dim() != 1 or not off.is_contiguous():
+        raise ValueError("knn: off must be a contiguous int64 [Ns] tensor on the neighbours' device")
+    if left is not None and (left.dtype != torch.int32 or left.device != dev or left.shape != off.shape or not left.is_contiguous()):
+        raise ValueError("knn: left must be a contiguous int32 [Ns] tensor on the neighbours' device")
+
+
+def knn_predict(idx, dist, n, k, actions, off, left, Q, mean=None, std=None, empty=None):
+    """actmi_op_knn_predict.  idx / dist / n from ``knn_topk``; actions [R, A] f32, off [Ns] int64, left [Ns] int32 (cuda); mean / std
+    [A] or None -> (chunk [Nq, Q, A] f32, empty: an int32 cuda word counting the queries without a neighbour; pass one in to
+    keep counting)."""
+    idx, dist, n = _knn_neighbours(idx, dist, n)
+    dev = idx.device
+    Nq, K = (int(v) for v in idx.shape)
+    if not 1 <= int(k) <= K <= KNN_MAX_K:
+        raise ValueError(f"knn_predict: need 1 <= k <= K <= {KNN_MAX_K}, got k = {k}, K = {K}")
+    if left is None:
+        raise ValueError("knn_predict: left (the rows that remain in each support row's episode, int32 [Ns]) is required")
+    _knn_rows(actions, off, left, dev)
+    R, A, Q = int(actions.shape[0]), int(actions.shape[1]), int(Q)
+    if Nq < 1 or R < 1 or Q < 1 or off.numel() < 1:
+        raise ValueError("knn_predict: empty operand")
+    mean, std = _knn_stats(mean, std, A, dev)
+    if empty is None:
+        empty = torch.zeros(1, dtype=torch.int32, device=dev)
+    chunk = torch.empty((Nq, Q, A), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_knn_predict(_p(idx), _p(dist), _p(n), K, int(k), _p(actions), R, _p(off), _p(left), off.numel(), Q, A,
+                                              _p(mean), _p(std), _p(chunk), _p(empty), Nq, L.current_stream_ptr()), None,
+                "op_knn_predict")
+    return chunk, empty
+
+
+def knn_ksweep(idx, dist, n, actions, off, target, mean=None, std=None, want_partial=False):
+    """actmi_op_knn_ksweep.  target [Nq, A] f32 cuda (in the units of the prediction: z-scored when mean / std are given) ->
+    sse [K] float64 cuda (and the per-query terms [Nq, K] with ``want_partial``)."""
+    idx, dist, n = _knn_neighbours(idx, dist, n)
+    dev = idx.device
+    Nq, K = (int(v) for v in idx.shape)
+    _knn_rows(actions, off, None, dev)
+    R, A = int(actions.shape[0]), int(actions.shape[1])
+    if target.dtype != torch.float32 or target.device != dev or tuple(target.shape) != (Nq, A):
+        raise ValueError(f"knn_ksweep: target must be a float32 [{Nq}, {A}] tensor on {dev}")
+    target = target.contiguous()
+    mean, std = _knn_stats(mean, std, A, dev)
+    partial = torch.empty((Nq, K), dtype=torch.float64, device=dev)
+    sse = torch.empty(K, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_knn_ksweep(_p(idx), _p(dist), _p(n), K, _p(actions), R, _p(off), off.numel(), A, _p(mean), _p(std),
+                                             _p(target), _p(partial), _p(sse), Nq, L.current_stream_ptr()), None, "op_knn_ksweep")
+    return (sse, partial) if want_partial else sse

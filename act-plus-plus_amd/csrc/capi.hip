@@ -88,6 +88,16 @@ int actmi_bind_attention_out(actmi_handle h, float* w, int B) {
     return ACTMI_OK;
 }
 
+int actmi_bind_features_out(actmi_handle h, float* feat, int B) {
+    if (!h) return ACTMI_E_INVALID;
+    ENTER(h);
+    if (!feat) { h->feat_out = nullptr; h->feat_out_B = 0; return ACTMI_OK; }
+    if (B < 1) return bad(h, "feature buffer of less than one sample");
+    if ((uintptr_t)feat & 3) return bad(h, "feature buffer must be 4-byte aligned");
+    h->feat_out = feat; h->feat_out_B = B;
+    return ACTMI_OK;
+}
+
 int actmi_attention_layout(actmi_handle h, actmi_attn_layout* out) {
     if (!h || !out) return ACTMI_E_INVALID;
     ENTER(h);
@@ -348,6 +358,31 @@ int actmi_op_sweep_error(const double* raw, const float* target, int len, const 
     }
     const int rc = launch_sweep_error(raw, target, len, mean, stdv, stats, pred, G, T, A, S(stream));
     return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
+int64_t actmi_op_knn_workspace_bytes(int64_t Nq, int64_t Ns) { return knn_workspace_bytes(Nq, Ns); }
+
+int actmi_op_knn_topk(const float* qv, const float* qs, const float* sv, const float* ss, const int32_t* sep, const int32_t* exclude,
+                      float state_weight, int K, int64_t Nq, int64_t Ns, int Dv, int Sd, int32_t* idx, float* dist, int32_t* n,
+                      void* ws, int64_t ws_bytes, void* stream) {
+    g_op_error.clear();
+    return launch_knn_topk(qv, qs, sv, ss, sep, exclude, state_weight, K, Nq, Ns, Dv, Sd, idx, dist, n, ws, ws_bytes, S(stream),
+                           &g_op_error);
+}
+
+int actmi_op_knn_predict(const int32_t* idx, const float* dist, const int32_t* n, int K, int k, const float* actions, int64_t R,
+                         const int64_t* off, const int32_t* left, int64_t Ns, int Q, int A, const double* mean, const double* std,
+                         float* chunk, int32_t* empty, int64_t Nq, void* stream) {
+    g_op_error.clear();
+    return launch_knn_predict(idx, dist, n, K, k, actions, R, off, left, Ns, Q, A, mean, std, chunk, empty, Nq, S(stream),
+                              &g_op_error);
+}
+
+int actmi_op_knn_ksweep(const int32_t* idx, const float* dist, const int32_t* n, int K, const float* actions, int64_t R,
+                        const int64_t* off, int64_t Ns, int A, const double* mean, const double* std, const float* target,
+                        double* partial, double* sse, int64_t Nq, void* stream) {
+    g_op_error.clear();
+    return launch_knn_ksweep(idx, dist, n, K, actions, R, off, Ns, A, mean, std, target, partial, sse, Nq, S(stream), &g_op_error);
 }
 
 int actmi_op_gemm(const actmi_gemm_desc* d, void* stream) {

@@ -214,6 +214,19 @@ int launch_ensemble_sweep(const float* chunks, int len, const actmi_schedule* sc
                           int Q, int A, hipStream_t st);
 int launch_sweep_error(const double* raw, const float* target, int len, const double* mean, const double* stdv, double* stats,
                        double* pred, int G, int T, int A, hipStream_t st);
+// nearest-neighbour retrieval (knn.hip): contracts at actmi_op_knn_topk / actmi_op_knn_predict / actmi_op_knn_ksweep
+int64_t knn_workspace_bytes(int64_t Nq, int64_t Ns);
+int launch_knn_topk(const float* qv, const float* qs, const float* sv, const float* ss, const int32_t* sep, const int32_t* exclude,
+                    float state_weight, int K, int64_t Nq, int64_t Ns, int Dv, int S, int32_t* idx, float* dist, int32_t* n,
+                    void* ws, int64_t ws_bytes, hipStream_t st, std::string* err);
+int launch_knn_predict(const int32_t* idx, const float* dist, const int32_t* n, int K, int k, const float* actions, int64_t R,
+                       const int64_t* off, const int32_t* left, int64_t Ns, int Q, int A, const double* mean, const double* stdv,
+                       float* chunk, int32_t* empty, int64_t Nq, hipStream_t st, std::string* err);
+int launch_knn_ksweep(const int32_t* idx, const float* dist, const int32_t* n, int K, const float* actions, int64_t R,
+                      const int64_t* off, int64_t Ns, int A, const double* mean, const double* stdv, const float* target,
+                      double* partial, double* sse, int64_t Nq, hipStream_t st, std::string* err);
+// the spatial mean of the layer4 maps [nc][B][P][Cch] of a camera range -> feat[b][(c0 + c) * Cch + ch], rows of ld floats (knn.hip)
+int launch_mean_features(const float* maps, float* feat, int B, int nc, int P, int Cch, int c0, int64_t ld, hipStream_t st);
 int launch_bn_fold(const float* w, const float* b, const float* rm, const float* rv, float* scale, float* bias, int n,
                    hipStream_t st);
 int launch_build_rowmap(int* map, int B, int C, int fh, int fw, int N, int n_extra, hipStream_t st);

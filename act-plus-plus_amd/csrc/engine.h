@@ -201,6 +201,10 @@ struct actmi_ctx {
     // written by every inference forward that runs the decoder while it is bound (null: nothing is launched for it)
     float* attn_out = nullptr;
     int attn_out_B = 0;
+    // actmi_bind_features_out: the caller's [feat_out_B][C * 8 * base_width] f32 buffer for the spatial mean of every RGB camera's
+    // layer4 map, written by every inference forward that runs the trunk while it is bound (null: nothing is launched for it)
+    float* feat_out = nullptr;
+    int feat_out_B = 0;
     int fwd_phase = 0;                 // actmi_set_forward_phase: 0 whole inference forward, 1 trunk + token assembly only, 2 transformer only
     // range guard of the f16x3 forward: one power-of-two scale per parameter for its split image, chosen at
     // finalize so that max|w| * scale lands in [2^13, 2^14) (capped at 2^12); device copies for the split kernel

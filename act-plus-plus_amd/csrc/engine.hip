@@ -1074,6 +1074,16 @@ int engine_backbone(actmi_ctx* ctx, const void* image, const DepthSrc& depth, in
             if (ctx->gemm_prec == ACTMI_PREC_F16X3 && grp.ip_a_scale != 1.f) ip.a_scale = grp.ip_a_scale;
             CHK(ctx_gemm(ctx, ip, ls, half));
         }
+        // the bound trunk embedding (actmi_bind_features_out): the spatial mean of the range's RGB layer4 maps, each branch its own
+        // columns of the caller's rows, by a sum whose order does not know the range
+        if (ctx->feat_out && !ctx->calibrating) {
+            const auto [p0, pn] = cam_overlap(ctx->cam_groups.front(), c0, nc);
+            if (pn > 0 && launch_mean_features(cur + (int64_t)(p0 - c0) * B * ctx->P_ * 8 * w0, ctx->feat_out, B, pn, ctx->P_, 8 * w0, p0,
+                                               (int64_t)g.num_cams * 8 * w0, ls) != 0) {
+                ctx->err = "mean_features launch failed";
+                return ACTMI_E_LAUNCH;
+            }
+        }
         return 0;
     };
     CHK(engine_build_rowmap(ctx, B, st));
@@ -1280,6 +1290,10 @@ int engine_forward_infer(actmi_ctx* ctx, const float* qpos, const void* image, i
     const int D = g.hidden_dim, N = ctx->N;
     if (ctx->attn_out && ctx->fwd_phase != 1 && ctx->attn_out_B < B) {     // (before anything is launched, and before a binding is consumed)
         ctx->err = "the bound attention buffer holds " + std::to_string(ctx->attn_out_B) + " samples, the forward has " + std::to_string(B);
+        return ACTMI_E_STATE;
+    }
+    if (ctx->feat_out && ctx->fwd_phase != 2 && ctx->feat_out_B < B) {
+        ctx->err = "the bound feature buffer holds " + std::to_string(ctx->feat_out_B) + " samples, the forward has " + std::to_string(B);
         return ACTMI_E_STATE;
     }
     const float *pc_xyz = nullptr, *pc_rgb = nullptr;

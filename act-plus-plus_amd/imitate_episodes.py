@@ -14,6 +14,8 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
   store the batches come from (no file read); ``--replay_horizon`` adds the error along the predicted chunk;
 * ``--replay_sweep`` reads a grid of execution schedules (query rate, executed horizon, ensemble weight, or the latest chunk
   alone) off the chunk tables either replay already holds: two more launches per episode, no further policy query;
+* ``--eval --replay --device_dataset --replay_knn K`` replays the same validation episodes once more through a nearest-neighbour
+  lookup over the training episodes (VINN with the policy's own trunk as the embedding, actmi.vinn) and prints both errors;
 * ``--device_dataset --use_pcd --device_clouds`` puts the task's stored point clouds into that store as well (the batches' clouds are
   gathered on the device; ``--replay_every`` then serves point-cloud policies), and ``--mirror_twins --use_pcd --cloud_mirror_axis
   {x,y,z} [--cloud_mirror_offset C]`` gives a stored cloud the mirror rule the twins need;
@@ -469,9 +471,64 @@ def _gather_rows_f64(local, counts):
     return out.contiguous().view(torch.float64).reshape(-1, k)
 
 
+def check_replay_knn(knn, store, policy_class, policy_config, episodes=None):
+    """The refusals of ``replay_bc(knn=...)`` / ``--replay_knn``, raised before anything is launched: no store, K outside
+    [1, 512] or above the support rows, a non-finite or negative state weight, use_pcd and Diffusion policies.  ``knn``: an int K
+    or a dict {"k", "state_weight" (1.0), "select_k" (None: no sweep; KMAX), "support_ids" (None: the store's episodes beyond the
+    replayed ones, all of them when there are none), "exclude_self" (None: True exactly when a replayed episode is a support
+    episode)}; a dict may carry a ready "policy" (and "support_rows"), which is then replayed as it is.  -> the completed dict"""
+    from actmi import ops, vinn
+    knn = dict(knn) if isinstance(knn, dict) else {"k": knn}
+    vinn.check_policy_class(policy_class, policy_config)
+    if store is None:
+        raise ValueError("--replay_knn looks demonstrations up in the device-resident store: it needs --device_dataset (store=...)")
+    if "k" not in knn:
+        raise ValueError("replay_bc(knn=...): no k")
+    if episodes is None or isinstance(episodes, (int, np.integer)):
+        replayed = list(store.episode_ids)[:None if episodes is None else int(episodes)]
+    else:
+        replayed = [int(i) for i in episodes]
+    if knn.get("support_ids") is None:
+        rest = [i for i in store.episode_ids if i not in set(replayed)]
+        knn["support_ids"] = rest or list(store.episode_ids)
+    knn["support_ids"] = [int(i) for i in knn["support_ids"]]
+    missing = [i for i in knn["support_ids"] if i not in store._local_of]
+    if missing or not knn["support_ids"]:
+        raise ValueError(f"replay_bc(knn=...): support episodes {missing} are not in the store (it holds {list(store.episode_ids)})")
+    if knn.get("support_rows") is None:
+        knn["support_rows"] = int(sum(int(store.T[store._local_of[i]]) for i in knn["support_ids"]))
+    knn["k"], knn["state_weight"] = ops.check_knn_args(knn["k"], knn.get("state_weight", 1.0), knn["support_rows"])
+    if knn.get("select_k") is not None:
+        knn["select_k"], _ = ops.check_knn_args(knn["select_k"], knn["state_weight"], knn["support_rows"])
+    if knn.get("exclude_self") is None:
+        knn["exclude_self"] = bool(set(replayed) & set(knn["support_ids"]))
+    return knn
+
+
+def _replay_knn(config, ckpt_name, knn, policy, stats, store, ids, batch, episode_ensemble, action_error, align, engine):
+    """the second replay of ``replay_bc(knn=...)``: the same episodes through the nearest-neighbour policy -> result["knn"]"""
+    vp = knn.get("policy")
+    sel = None
+    if vp is None:
+        from actmi import vinn
+        support = knn.get("support") or vinn.SupportSet.from_store(store, policy, knn["support_ids"], batch, align)
+        vp = vinn.VINNPolicy(support, knn["k"], knn["state_weight"], engine, exclude_self=knn["exclude_self"], stats=stats)
+        if knn.get("select_k") is not None:
+            sel = vinn.select_k(support, store, ids, knn["select_k"], policy, knn["state_weight"], batch)
+    sub = replay_bc(config, ckpt_name, episodes=ids, policy=vp, stats=stats, batch=batch, episode_ensemble=episode_ensemble,
+                    align=align, save_episode=False, verbose=False, action_error=action_error, store=store)
+    out = {"k": knn["k"], "state_weight": knn["state_weight"], "support_rows": knn["support_rows"],
+           "mae_mean": sub["mae_mean"], "rmse_mean": sub["rmse_mean"], "max_max": sub["max_max"], "mae": sub["mae"],
+           "empty": int(vp.empty_count()) if hasattr(vp, "empty_count") else 0}
+    if sel is not None:
+        out["select_k"] = {"mse": sel["mse"], "best_k": sel["best_k"]}
+    return out
+
+
 def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=None, episode_ensemble=None, align="train",
               save_episode=True, verbose=True, action_error=None, vq_sampler=None, store=None, horizon=False, chunk_error=None,
-              attention=False, attention_slots=None, attention_frames=False, sweep=None, ensemble_sweep=None, sweep_error=None):
+              attention=False, attention_slots=None, attention_frames=False, sweep=None, ensemble_sweep=None, sweep_error=None,
+              knn=None):
     """Open-loop replay evaluation on recorded episodes (the fork's eval_arm_gripper_depth.py:343-418 without its plots): the
     policy is queried on an episode's recorded observations, the chunks are ensembled over time (``temporal_agg``) or executed
     chunk by chunk, un-normalised, and compared with the recorded ``/action``.  Serves what ``eval_bc`` cannot roll out --
@@ -517,6 +574,14 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     "rmse_mean" [G], "max_max" [G], "rough_mean" [G] (the mean |pred[t] - pred[t-1]| per step and joint: the smoothness a schedule
     gives up), "empty" [G] (steps without a populated live row), "best", "default"}`` (``sweep_metrics``), in action units.  Every
     other key, file and printed figure is the same bits with or without it.
+    ``knn`` (``--replay_knn K``; ``{"k", "state_weight", "select_k", "support_ids", "exclude_self"}``, see ``check_replay_knn``):
+    after the policy's replay the SAME episodes are replayed once more through ``actmi.vinn.VINNPolicy`` -- the k nearest frames of
+    the store's episodes ``support_ids`` (default: those it holds beyond the replayed ones, the training split) by the policy's
+    own trunk features and z-scored qpos, and the softmax-weighted mean of their action chunks -- with the same ensemble and error
+    code, and ``result["knn"] = {"k", "state_weight", "support_rows", "mae_mean", "rmse_mean", "max_max", "mae", "empty"[,
+    "select_k": {"mse", "best_k"}]}`` says what a lookup achieves where the policy achieved ``result["mae_mean"]``.  It needs a
+    ``store`` and an ACT policy without use_pcd, else ValueError before anything is launched.  Every other key, file and printed
+    figure is the same bits with or without it.
     Returns {"episodes": [...], "mae": [A], "rmse": [A], "max": [A], "mae_mean", "rmse_mean", "max_max", "steps", ...} in
     action units; with ``save_episode`` rank 0 writes replay_<ckpt>.json and per episode replay_<ckpt>_ep<i>.npz (pred, target)."""
     import json
@@ -524,6 +589,8 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     ckpt_dir = config["ckpt_dir"]
     policy_class = config["policy_class"]
     policy_config = config["policy_config"]
+    if knn is not None:
+        knn = check_replay_knn(knn, store, policy_class, policy_config, episodes)
     if policy_class == "Diffusion":
         raise NotImplementedError("replay_bc: the Diffusion policy has no temporal ensemble and its crop-resize input path is not "
                                   "part of the replay")
@@ -623,6 +690,8 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
         if store is not None:
             ep = DeviceEpisodeReplay(store, ids[i], batch, stride=stride)
             actions = ep.actions_device                                                              # [T, A] f32, file units
+            if getattr(policy, "exclude_self", False):           # (an actmi.vinn.VINNPolicy: leave-one-episode-out)
+                policy.set_exclude(ids[i])
         else:
             ep = EpisodeReplay(files[i], camera_names, stats, batch, depth_camera_names=policy_config.get("depth_camera_names"),
                                use_depth=use_depth, pointcloud_names=config.get("pointcloud_names"), use_pcd=use_pcd,
@@ -708,6 +777,9 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
         count = float(sh[:, 0].sum())
         result["attention"] = {"sources": attn["sources"], "share_mean": (sh[:, 1:].sum(0) / max(count, 1.0)).tolist(),
                                "slots": list(attn["slots"]), "steps": int(count)}
+    if knn is not None:
+        result["knn"] = _replay_knn(config, ckpt_name, knn, policy, stats, store, ids, batch, episode_ensemble, action_error, align,
+                                    engine)
     if save_episode:
         Ts = rows[:, 0].astype(np.int64)
         per_rank = [int(Ts[a:b].sum()) for a, b in spans]
@@ -742,6 +814,14 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
                 mark = " ".join(m for m, i in (("<- best", sw["best"]), ("<- default", sw["default"])) if i == g)
                 print(f"{g:4d} {d['every']:5d} {d['horizon']:7d} {d['mode']:>8s} {d['k']:8.4f} {sw['mae_mean'][g]:10.5f} "
                       f"{sw['rmse_mean'][g]:10.5f} {sw['max_max'][g]:10.5f} {sw['rough_mean'][g]:10.5f} {sw['empty'][g]:6d} {mark}")
+        if knn is not None:
+            kn = result["knn"]
+            print(f"nearest-neighbour baseline (k = {kn['k']}, state weight {kn['state_weight']:g}, {kn['support_rows']} support rows): "
+                  f"policy MAE {result['mae_mean']:.5f}, kNN MAE {kn['mae_mean']:.5f}, ratio "
+                  f"{result['mae_mean'] / kn['mae_mean'] if kn['mae_mean'] > 0 else float('inf'):.3f}, {kn['empty']} empty lookups")
+            if "select_k" in kn:
+                print(f"  select_k over k = 1..{len(kn['select_k']['mse'])}: best k = {kn['select_k']['best_k']} "
+                      f"(z-scored slot-0 MSE {min(kn['select_k']['mse']):.6f})")
         if attn is not None:
             at = result["attention"]
             print(f"attention share per source, action slots {at['slots'][0]}..{at['slots'][1] - 1}, mean over {at['steps']} queries:")
@@ -1044,6 +1124,22 @@ def build_config(args):
     if args.get("augment_clouds"):
         config["augment_clouds"] = True
         config["cloud_pivot"] = [float(v) for v in (args.get("cloud_pivot") or (0.0, 0.0, 0.0))]
+    if (args.get("knn_state_weight") is not None or args.get("knn_select_k") is not None) and args.get("replay_knn") is None:
+        raise ValueError("--knn_state_weight and --knn_select_k belong to --replay_knn")
+    if args.get("replay_knn") is not None:
+        from actmi import ops, vinn
+        if args.get("replay_every"):
+            raise ValueError("--replay_knn with --replay_every: inside training the trunk moves and the cached support features would "
+                             "be stale; evaluate with --eval --replay afterwards")
+        if not (args.get("eval") and args.get("replay")):
+            raise ValueError("--replay_knn replays the nearest-neighbour baseline beside an open-loop replay: it needs --eval --replay")
+        vinn.check_policy_class(policy_class, {"use_pcd": bool(args.get("use_pcd"))})
+        if not args.get("device_dataset"):
+            raise ValueError("--replay_knn looks demonstrations up in the device-resident store: it needs --device_dataset")
+        k, w = ops.check_knn_args(args["replay_knn"], 1.0 if args.get("knn_state_weight") is None else args["knn_state_weight"])
+        config["replay_knn"] = {"k": k, "state_weight": w}
+        if args.get("knn_select_k") is not None:
+            config["replay_knn"]["select_k"] = ops.check_knn_args(args["knn_select_k"], w)[0]
     if args.get("device_dataset"):
         if policy_class != "ACT":
             raise NotImplementedError("--device_dataset: the device-resident episode store feeds the ACT training path")
@@ -1117,6 +1213,28 @@ def build_config(args):
     return config
 
 
+def _load_episode_data(args, config, task_config, dataset_dir, world, local_rank):
+    """``load_data`` on the episode files of ``dataset_dir`` with the task's and the command line's settings: what training reads,
+    and, with ``--device_dataset``, the store an ``--eval --replay --replay_knn`` run looks its neighbours up in"""
+    from actmi.data import load_data
+    name_filter = task_config.get("name_filter", lambda n: True)
+    return load_data(dataset_dir, name_filter, config["camera_names"], args["batch_size"], args["batch_size"],
+                     args.get("chunk_size") or 100, args.get("skip_mirrored_data", False),
+                     policy_class=config["policy_class"], stats_dir_l=task_config.get("stats_dir"),
+                     sample_weights=task_config.get("sample_weights"),
+                     train_ratio=task_config.get("train_ratio", 0.99),
+                     depth_camera_names=config["policy_config"].get("depth_camera_names"),
+                     use_depth=bool(config["policy_config"].get("use_depth")), pointcloud_names=config.get("pointcloud_names"),
+                     use_pcd=bool(config["policy_config"].get("use_pcd")), max_points=config["policy_config"].get("max_points"),
+                     # --device_dataset: every rank holds its own full store on its own device
+                     device_dataset=bool(config.get("device_dataset")), mirror_twins=bool(config.get("mirror_twins")),
+                     device_clouds=bool(config.get("device_clouds")),
+                     cloud_mirror=tuple(config["cloud_mirror"]) if config.get("cloud_mirror") else None,
+                     device=f"cuda:{local_rank}" if world > 1 else None,     # train_bc's device
+                     device_budget_bytes=(int(config["device_dataset_gb"] * 2**30)
+                                          if config.get("device_dataset_gb") is not None else None))
+
+
 def main(args):
     set_seed(1)
     config = build_config(args)
@@ -1128,6 +1246,22 @@ def main(args):
     if args["eval"] and args.get("replay"):
         # open-loop replay on recorded episodes: what a use_depth / use_pcd policy (no simulator renders its inputs) and a policy
         # trained on real-robot episodes can be evaluated with
+        if config.get("replay_knn") is not None:
+            # the store --device_dataset training holds (the same split from the same seed): the validation episodes are replayed,
+            # the training episodes are the support set
+            task_config = SIM_TASK_CONFIGS[args["task_name"]]
+            dataset_dir = args.get("dataset_dir") or task_config.get("dataset_dir")
+            if not (dataset_dir and os.path.isdir(dataset_dir)):
+                raise ValueError("--replay_knn needs episode files (--dataset_dir)")
+            train_dl, val_dl, stats, _ = _load_episode_data(args, config, task_config, dataset_dir, world, local_rank)
+            n = args.get("replay_episodes")
+            return replay_bc(config, "policy_last.ckpt", episodes=list(val_dl.episode_ids)[:None if n is None else int(n)],
+                             align=args.get("replay_align") or "train", save_episode=True, horizon=bool(args.get("replay_horizon")),
+                             attention=bool(config.get("replay_attention")), attention_slots=config.get("replay_attention_slots"),
+                             attention_frames=bool(config.get("replay_attention_frames")),
+                             sweep=(replay_sweep_schedules(config["policy_config"]["num_queries"], **config["replay_sweep"])
+                                    if config.get("replay_sweep") is not None else None),
+                             store=val_dl.store, stats=stats, knn=dict(config["replay_knn"], support_ids=list(train_dl.episode_ids)))
         return replay_bc(config, "policy_last.ckpt", episodes=args.get("replay_episodes"),
                          align=args.get("replay_align") or "train", save_episode=True, horizon=bool(args.get("replay_horizon")),
                          attention=bool(config.get("replay_attention")), attention_slots=config.get("replay_attention_slots"),
@@ -1164,23 +1298,7 @@ def main(args):
     if dataset_dir and os.path.isdir(dataset_dir):
         # reference imitate_episodes.py:141-147: episodes on disk (HDF5 via h5py, or .npz with the same keys), z-scored
         # qpos / actions, u8 images; batches reach the device through pinned staging on a side stream
-        from actmi.data import load_data
-        name_filter = task_config.get("name_filter", lambda n: True)
-        train_dl, val_dl, stats, _ = load_data(dataset_dir, name_filter, camera_names, args["batch_size"], args["batch_size"],
-                                               args.get("chunk_size") or 100, args.get("skip_mirrored_data", False),
-                                               policy_class=policy_class, stats_dir_l=task_config.get("stats_dir"),
-                                               sample_weights=task_config.get("sample_weights"),
-                                               train_ratio=task_config.get("train_ratio", 0.99),
-                                               depth_camera_names=config["policy_config"].get("depth_camera_names"),
-                                               use_depth=use_depth, pointcloud_names=config.get("pointcloud_names"),
-                                               use_pcd=use_pcd, max_points=config["policy_config"].get("max_points"),
-                                               # --device_dataset: every rank holds its own full store on its own device
-                                               device_dataset=device_dataset, mirror_twins=bool(config.get("mirror_twins")),
-                                               device_clouds=bool(config.get("device_clouds")),
-                                               cloud_mirror=tuple(config["cloud_mirror"]) if config.get("cloud_mirror") else None,
-                                               device=f"cuda:{local_rank}" if world > 1 else None,     # train_bc's device
-                                               device_budget_bytes=(int(config["device_dataset_gb"] * 2**30)
-                                                                    if config.get("device_dataset_gb") is not None else None))
+        train_dl, val_dl, stats, _ = _load_episode_data(args, config, task_config, dataset_dir, world, local_rank)
     else:
         train_dl = SyntheticDataset(cfg, args["batch_size"], 8, seed=args["seed"] * world + rank)     # disjoint per rank
         val_dl = SyntheticDataset(cfg, args["batch_size"], 2, seed=args["seed"] * world + rank + 100003)
@@ -1251,6 +1369,16 @@ def make_parser():
                         help="ACT training with --device_dataset: every N steps replay the validation episodes (at most "
                              "--replay_episodes, aligned by --replay_align) open loop out of the device-resident store; the figures "
                              "go to replay_history.json, the weights with the lowest mean MAE to policy_best_replay.ckpt (0: off)")
+    parser.add_argument("--replay_knn", action="store", type=int, default=None, metavar="K",
+                        help="--eval --replay --device_dataset: after the policy's replay, replay the same (validation) episodes through "
+                             "a nearest-neighbour lookup (VINN) over the training episodes -- the K nearest frames by the policy's own "
+                             "trunk features and z-scored qpos, softmax-weighted mean of their action chunks -- and report both MAEs "
+                             "(result['knn']); K in 1..512")
+    parser.add_argument("--knn_state_weight", action="store", type=float, default=None, metavar="W",
+                        help="--replay_knn: weight of the z-scored qpos distance beside the feature distance (default 1.0: a choice, "
+                             "not a measurement; the reference's values are for raw qpos)")
+    parser.add_argument("--knn_select_k", action="store", type=int, default=None, metavar="KMAX",
+                        help="--replay_knn: also the slot-0 error of every k = 1..KMAX on the replayed episodes (vinn_select_k.py)")
     parser.add_argument("--replay_attention", action="store_true",
                         help="--eval --replay: also record the decoder's cross-attention map of every query, cut per camera and "
                              "source (replay_<ckpt>_ep<i>_attn.npz), and print / log the attention share per source")

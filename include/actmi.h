@@ -345,6 +345,23 @@ typedef struct actmi_attn_layout {
 int actmi_bind_attention_out(actmi_handle h, float* w, int B);
 int actmi_attention_layout(actmi_handle h, actmi_attn_layout* out);
 
+/* ---- the trunk embedding: what a nearest-neighbour baseline looks demonstrations up by ------------------------------
+ * actmi_bind_features_out: feat is a device buffer [B][C * F] f32, C = the RGB cameras, F = 8 * base_width (512 for ResNet18)
+ * the channels of a layer4 map (NULL unbinds).  While one is bound, every inference forward that runs the trunk (whole or
+ * phase 1; actmi_forward_infer and actmi_forward_infer_vq) leaves in feat[b][c * F + ch] the spatial mean of camera c's layer4
+ * map of sample b -- the maps are camera-major [C][B][fh][fw][F]:
+ *   s = 0;  for p = 0 .. fh * fw - 1 (row-major):  s = s + map[c][b][p][ch]      fp32, one add at a time
+ *   feat = s / float(fh * fw)                                                      one correctly rounded fp32 divide
+ * (actmi.ops.pooled_features_ref restates it in numpy).  One small launch per camera range behind the range's input
+ * projection, lanes over the channels: with the cameras split over concurrent branches every branch writes its own columns, and
+ * the bits are those of the un-split run.  Depth cameras are left out: their maps come from a separately trained 1-channel
+ * trunk and the baseline this serves looks frames up by what the RGB cameras see; the columns are the RGB cameras' alone.
+ * B is the capacity of feat in samples: a forward of a larger batch returns ACTMI_E_STATE before it launches anything.  Rows
+ * [batch, B) are left alone.  Unbound (the default) the forward launches exactly what it launched before this entry existed;
+ * a_hat does not depend on the binding.  Graph capture: the binding is read when the forward is enqueued, as with
+ * actmi_bind_attention_out.  actmi_forward_train and the calibration forward of actmi_finalize ignore the binding. */
+int actmi_bind_features_out(actmi_handle h, float* feat, int B);
+
 /* ---- training: ACTPolicy.__call__(qpos, image, actions, is_pad) -> {l1, kl, loss} (policy.py:288-320) -- */
 int actmi_forward_train(actmi_handle h, const float* qpos, const void* image, int image_fmt,
                         const float* actions /*[B][Q][A]*/, const uint8_t* is_pad /*[B][Q]*/,
@@ -412,6 +429,48 @@ int actmi_op_action_error(const double* raw, const float* target, const int32_t*
 int actmi_op_chunk_error(const float* chunks, const float* actions, const int32_t* lengths, const int32_t* shift,
                          const double* mean, const double* std, int stride, double* stats, int32_t* count,
                          int E, int S, int T, int Q, int A, void* stream);
+
+/* ---- nearest-neighbour action retrieval (csrc/knn.hip): the VINN baseline's lookup on the device ---------------------
+ * actmi_op_knn_topk: queries qv [Nq][Dv], qs [Nq][S]; support sv [Ns][Dv], ss [Ns][S], sep [Ns] int32 episode ids; exclude
+ * [Nq] int32 or NULL (-1: none); K in 1..512.  Outputs idx [Nq][K] int32, dist [Nq][K] f32, n [Nq] int32.
+ *   dist(q, s) = ||qv_q - sv_s||_2 + state_weight * ||qs_q - ss_s||_2                 (vinn_eval.py calculate_nearest_neighbors)
+ * in fp32, every operation rounded on its own and nothing fused: diff = a - b, sq = diff * diff, then THE summation order,
+ * which is part of this ABI and does not depend on Nq, Ns, K or the launch: four partial sums, p_j taking the dimensions
+ * d = j (mod 4) in ascending d, each p_j = p_j + sq starting from +0, combined as (p0 + p1) + (p2 + p3); then a correctly
+ * rounded square root of each norm, one multiply by state_weight, one add.  S = 0 gives a state norm of +0 (qs / ss may be NULL).
+ * A support row is eligible for query q when sep[s] != exclude[q] (or exclude is NULL / negative) and its distance is finite
+ * (a row holding NaN or inf never is).  The result is the K eligible rows of smallest key (distance bits, index) in ascending
+ * key order: among equal distances the lowest index first, so it is unique.  n[q] = min(K, eligible); the slots beyond it hold
+ * idx -1 and dist +inf.  K may exceed Ns.
+ * Two forms, the same bits: Nq <= 8 reads the support once, 32 rows per workgroup staged through LDS by 16-byte loads with
+ * four lanes on a row; more queries run 64 x 64 tiles of pairs with a 4 x 4 register tile per lane.  Both write the distances
+ * of up to 1024 queries to ws (actmi_op_knn_workspace_bytes(Nq, Ns) bytes, 4-byte aligned device memory); then one workgroup per
+ * query selects by radix on the 64-bit key and sorts at most 512 keys in LDS.  Only integer counters are updated atomically:
+ * two launches give the same bits.  state_weight must be finite and >= 0.  16-byte loads need Dv (S) a multiple of 4 and
+ * 16-byte aligned bases; otherwise the rows are read by single floats.  ACTMI_E_INVALID for a bad argument, nothing launched.
+ *
+ * actmi_op_knn_predict: chunk [Nq][Q][A] f32 from the neighbours: with m = min(k, n[q]), e_i = exp(-(dist_i - dist_0)) in
+ * float64 (softmax(-dist) over the SORTED distances of the first m neighbours),
+ *   chunk[q][j][a] = f32( ( (sum_i e_i * actions[off[idx_i] + min(j, left[idx_i] - 1)][a]) / (sum_i e_i)  - mean[a] ) / std[a] )
+ * sums in float64 in neighbour order, products and sums rounded separately; mean / std (double [A]) both NULL: no z-score.
+ * actions [R][A] f32 are the store's rows; off [Ns] int64 the row of each support frame's first action, left [Ns] int32 the rows
+ * that remain in its episode from there (slot j clamps to the episode's last action, as the reference pads); rows are held
+ * to [0, R).  m = 0 writes a zero chunk and adds one to *empty (int32, may be NULL).
+ *
+ * actmi_op_knn_ksweep: sse[k - 1] for k = 1..K at once = sum over the queries of sum_a (p - target[q][a])^2 in float64, p being
+ * slot 0 of what actmi_op_knn_predict writes at that k (the f32 value; vinn_select_k.py compares slot 0 only).  partial
+ * [Nq][K] double holds the per-query terms; sse adds them in query order in a second launch, so two calls give the same bits.
+ * K * (8 + 4 * A) bytes of LDS must fit 64 KiB (ACTMI_E_SHAPE). */
+int64_t actmi_op_knn_workspace_bytes(int64_t Nq, int64_t Ns);
+int actmi_op_knn_topk(const float* qv, const float* qs, const float* sv, const float* ss, const int32_t* sep, const int32_t* exclude,
+                      float state_weight, int K, int64_t Nq, int64_t Ns, int Dv, int S, int32_t* idx, float* dist, int32_t* n,
+                      void* ws, int64_t ws_bytes, void* stream);
+int actmi_op_knn_predict(const int32_t* idx, const float* dist, const int32_t* n, int K, int k, const float* actions, int64_t R,
+                         const int64_t* off, const int32_t* left, int64_t Ns, int Q, int A, const double* mean, const double* std,
+                         float* chunk, int32_t* empty, int64_t Nq, void* stream);
+int actmi_op_knn_ksweep(const int32_t* idx, const float* dist, const int32_t* n, int K, const float* actions, int64_t R,
+                        const int64_t* off, int64_t Ns, int A, const double* mean, const double* std, const float* target,
+                        double* partial, double* sse, int64_t Nq, void* stream);
 
 /* ---- replay schedule sweep: G execution schedules read off ONE chunk table ------------------------------ */
 /* A schedule executes the chunks of every `every`-th frame for `horizon` slots.  The chunk predicted from frame r is LIVE at
