@@ -736,7 +736,7 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
               train_ratio=0.99, num_workers=2, f32_images=False, rng=None, depth_camera_names=None, use_depth=False,
               f32_depth=False, pointcloud_names=None, use_pcd=False, max_points=None, pcd_ignore_mask=False,
               device_dataset=False, device=None, device_budget_bytes=None, mirror_twins=False, mirror_spec=None,
-              device_clouds=False, cloud_mirror=None):
+              device_clouds=False, cloud_mirror=None, device_decode=False):
     """utils.py:249-301.  Returns (train_dataloader, val_dataloader, norm_stats, is_sim).  ``use_depth``: the batches are
     5-tuples that end in the depth frames of ``depth_camera_names`` (EpisodicDataset).  ``use_pcd``: 7-tuples that end in the
     padded clouds and their valid counts (collate_pcd).  ``device_dataset``: both loaders come from ONE ``DeviceEpisodeStore``
@@ -748,7 +748,10 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
     exist (uncompressed, float32 rows): the same episode ids, stats, draws and batches.  With ``device_dataset`` the twins take no
     frame memory.  ``cloud_mirror`` ``(axis, offset)``: the mirror rule of the stored clouds (``cloud_mirror_rule``), which
     ``mirror_twins`` with ``use_pcd`` needs.  ``device_clouds``: the stored clouds of a ``use_pcd`` dataset go into the store as well
-    and the device loaders deliver the 7-tuples of ``collate_pcd``, gathered by ``actmi_op_gather_clouds``."""
+    and the device loaders deliver the 7-tuples of ``collate_pcd``, gathered by ``actmi_op_gather_clouds``.  ``device_decode``: the store
+    decodes the frames of compressed episodes on the device (``DeviceEpisodeStore``); the batches are the same bytes."""
+    if device_decode and not device_dataset:
+        raise ValueError("device_decode decodes the compressed frames of the device-resident store: it needs device_dataset")
     if mirror_twins and use_pcd and cloud_mirror is None:
         raise ValueError("mirror_twins with use_pcd: a stored point cloud has no mirror rule (cloud_mirror=(axis, offset) gives it one)")
     if cloud_mirror is not None:
@@ -815,6 +818,7 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
             device = torch.device("cuda", torch.cuda.current_device())
         store = DeviceEpisodeStore(dataset_path_list, np.concatenate([train_episode_ids, val_episode_ids]), camera_names, norm_stats,
                                    device, depth_camera_names, use_depth, device_budget_bytes, use_pcd, policy_class,
+                                   device_decode=device_decode,
                                    **(dict(pointcloud_names=pointcloud_names, max_points=max_points, pcd_ignore_mask=pcd_ignore_mask)
                                       if device_clouds else {}))
         train_loader = store.loader(train_episode_ids, train_episode_len, chunk_size,
@@ -980,13 +984,22 @@ class DeviceEpisodeStore:
     upload.  A twin's clouds are its source's blocks with the mirror flag set: no bytes; its ``cloud_mirror`` rule -- one for the
     whole store -- is the launch's.  ``use_pcd`` without names keeps the refusal above.
 
+    ``device_decode``: the frames of a compressed source are decoded on the device (``ops.JpegDecoder``, actmi_op_jpeg_decode)
+    instead of one by one through PIL: their headers are parsed on the host, the entropy segments go through the staging pair and
+    the op writes straight into the block's place in the arena, B, G, R for cameras and the uint16 form for depth, up to
+    ``decode_frames`` frames a launch.  A frame the parser refuses, one of another size and one whose status comes back nonzero
+    (read once per source file) is decoded by ``imdecode_bgr`` and copied as without the flag, before the store is handed out: the
+    flag changes neither what the arena holds nor which error a bad file raises.  ``decode_stats`` counts the frames of both
+    kinds.  The decoder's workspace and stream buffer live only during the load.
+
     Every rank of a data-parallel run holds its own full store."""
 
     RING = 4                 # pinned index blocks in flight: a block is rewritten only after its copy has executed
 
     def __init__(self, dataset_path_list, episode_ids, camera_names, norm_stats, device, depth_camera_names=None, use_depth=False,
                  budget_bytes=None, use_pcd=False, policy_class="ACT", stage_bytes=64 << 20, pointcloud_names=None, max_points=None,
-                 pcd_ignore_mask=False):
+                 pcd_ignore_mask=False, device_decode=False, decode_frames=256):
+        self.device_decode, self.decode_frames = bool(device_decode), int(decode_frames)
         self.pointcloud_names = list(pointcloud_names) if pointcloud_names else []
         self.has_clouds = bool(use_pcd) and bool(self.pointcloud_names)
         if self.has_clouds and len(self.pointcloud_names) != 1:
@@ -1111,6 +1124,8 @@ class DeviceEpisodeStore:
             blocks += [int(T) * self.frame_bytes] * K + [int(T) * self.depth_bytes] * Kd + \
                       [int(T) * int(N) * 12, int(T) * int(N) * self.cloud_rgb_bytes][:nc]
         offs, self.nbytes = arena_layout(blocks)                       # every source once: a twin adds no frame bytes
+        ends = [int(o) + int(b) for o, b in zip(offs, blocks)]
+        self._padding = [(e, int(n)) for e, n in zip(ends, list(offs[1:]) + [self.nbytes]) if n > e]   # the bytes no block holds
         offs = offs.reshape(len(self.sources), K + Kd + nc)
         self._src_block_off, self._src_depth_block_off, self._src_T = offs[:, :K].copy(), offs[:, K:K + Kd].copy(), src_T
         self._src_N, self._src_cloud_off = src_N, offs[:, K + Kd:].copy()
@@ -1150,10 +1165,17 @@ class DeviceEpisodeStore:
         dev = torch.device(self.device)
         t_begin = time.perf_counter()
         self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        for a, b in self._padding:                                    # the padding between blocks is zero: two stores of one
+            self.arena[a:b].zero_()                                   # dataset hold the same bytes everywhere
         stage = max(self.stage_bytes, self.frame_bytes, self.depth_bytes, int(self._src_N.max()) * 12 if self.has_clouds else 0)
         self.cloud_n = np.zeros(int(self._src_T.sum()) if self.has_clouds else 0, dtype=np.int32)   # valid rows of every stored step
         self._pin = [torch.empty(stage, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         self._pin_ev, self._pin_i = [None, None], 0
+        self.decode_stats = {"device": 0, "host": 0}
+        self.bus_bytes = 0                                            # bytes of frames and clouds that crossed to the device
+        self._decoders, self._pending, self._jpeg_stream = {}, [], None
+        if self.device_decode and any(self._src_compressed):
+            self._jpeg_stream = torch.empty(stage, dtype=torch.uint8, device=dev)
         actions, qposes, sims = [], [], []
         loaded = set()
         for i, path in enumerate(self.paths):
@@ -1193,6 +1215,7 @@ class DeviceEpisodeStore:
                              f"values for episodes of {self.A} / {self.S}")
         torch.cuda.synchronize(dev)
         self._pin = self._pin_ev = None                               # the staging buffers are the load's alone
+        self._decoders = self._jpeg_stream = None                     # and so are the decoder's workspace and stream buffer
         self.load_seconds = time.perf_counter() - t_begin
         self._host, self._host_ev, self._slot = [None] * self.RING, [None] * self.RING, 0
 
@@ -1205,6 +1228,7 @@ class DeviceEpisodeStore:
         for k, cam in enumerate(self.depth_camera_names[:self.Kd]):
             self._load_block(root[f"/observations/depth_images/{cam}"], T, self._src_compressed[j],
                              int(self._src_depth_block_off[j, k]), True, f"{path}: /observations/depth_images/{cam}")
+        self._finish_device_decode()
         if self.has_clouds:
             self._load_clouds(root, j)
 
@@ -1234,15 +1258,17 @@ class DeviceEpisodeStore:
         counts = stored_cloud_counts(root, base, path, T, N, self.pcd_ignore_mask)
         self.cloud_n[int(self._src_row0[j]):int(self._src_row0[j]) + T] = counts
 
-    def _stage(self, dst_off, nbytes, fill):
+    def _stage(self, dst_off, nbytes, fill, dst=None):
         """one piece through the staging pair: ``fill(view)`` writes `nbytes` bytes into the pinned view, which is then copied to
-        the arena; a buffer is refilled only after the copy that read it has executed"""
+        the arena (or to `dst`, another device buffer); a buffer is refilled only after the copy that read it has executed"""
+        dst = self.arena if dst is None else dst
+        self.bus_bytes += int(nbytes)
         j = self._pin_i
         self._pin_i = 1 - j
         if self._pin_ev[j] is not None:
             self._pin_ev[j].synchronize()
         fill(self._pin[j].numpy()[:nbytes])
-        self.arena[dst_off:dst_off + nbytes].copy_(self._pin[j][:nbytes], non_blocking=True)
+        dst[dst_off:dst_off + nbytes].copy_(self._pin[j][:nbytes], non_blocking=True)
         self._pin_ev[j] = torch.cuda.Event()
         self._pin_ev[j].record(torch.cuda.current_stream(self.arena.device))
 
@@ -1253,6 +1279,11 @@ class DeviceEpisodeStore:
         for t0 in range(0, T, per):
             t1 = min(T, t0 + per)
             piece = np.asarray(entry[t0:t1])
+            if compressed and self._jpeg_stream is not None and piece.ndim == 2 and piece.dtype == np.uint8:
+                host = self._decode_on_device(piece, dst_off + t0 * fb, depth)
+                for i in host:                                        # what the parser refused: as without the flag, frame by frame
+                    self._load_host_frame(piece[i], dst_off + (t0 + i) * fb, depth, where)
+                continue
             if compressed:                                            # utils.py:104-107, frame by frame
                 piece = np.stack([imdecode_bgr(buf) for buf in piece])
             if depth:
@@ -1268,6 +1299,86 @@ class DeviceEpisodeStore:
                 raise MemoryError(f"{where}: block leaves the arena of {self.nbytes} bytes")
             flat = np.ascontiguousarray(piece).reshape(-1).view(np.uint8)
             self._stage(dst_off + t0 * fb, n, lambda view, flat=flat: np.copyto(view, flat))
+
+    # ---- compressed frames decoded on the device (device_decode) -------------------------------------------------------
+    def _load_host_frame(self, buf, dst_off, depth, where):
+        """one compressed frame by the host path: ``_load_block``'s steps and refusals for a piece of one frame"""
+        fb = self.depth_bytes if depth else self.frame_bytes
+        shape = self.depth_shape if depth else self.frame_shape
+        frame = imdecode_bgr(buf)
+        if depth:
+            frame = frame[..., 0].astype(np.uint16, copy=False)
+        if frame.shape != tuple(shape):
+            raise ValueError(f"{where}: frames {frame.dtype} {frame.shape}, the store was sized for {tuple(shape)}")
+        flat = np.ascontiguousarray(frame).reshape(-1).view(np.uint8)
+        self._stage(dst_off, fb, lambda view, flat=flat: np.copyto(view, flat))
+        self.decode_stats["host"] += 1
+
+    def _decode_on_device(self, piece, dst_off, depth):
+        """the frames of `piece` ([n, L] u8, one zero-padded file each) that the parser accepts at the store's size: their entropy
+        segments through the staging pair, decoded into arena[dst_off + i * frame bytes]; -> the indices of the other frames.  The
+        statuses stay on the device until ``_finish_device_decode``."""
+        from . import ops
+        fb = self.depth_bytes if depth else self.frame_bytes
+        H, W = (self.depth_shape if depth else self.frame_shape)[:2]
+        dec = self._decoders.get((H, W))
+        if dec is None:
+            dec = self._decoders[(H, W)] = ops.JpegDecoder(self.device, H, W, max_frames=self.decode_frames)
+        host, todo = [], {}
+        for i, buf in enumerate(piece):
+            try:
+                info = dec.parse(buf)
+            except ops.JpegUnsupported:
+                host.append(i)
+                continue
+            if (info["H"], info["W"]) != (H, W):
+                host.append(i)
+                continue
+            todo.setdefault(info["mode"], []).append((i, info))
+        cap = int(self._jpeg_stream.numel())
+        for mode, items in todo.items():
+            k0 = 0
+            while k0 < len(items):                                    # as many frames as the stream buffer and one launch hold
+                k1, nbytes = k0, 0
+                while k1 < len(items) and k1 - k0 < dec.max_frames and nbytes + items[k1][1]["seg_len"] <= cap:
+                    nbytes += items[k1][1]["seg_len"]
+                    k1 += 1
+                if k1 == k0:                                          # one segment larger than the staging buffer
+                    host.append(items[k0][0])
+                    k0 += 1
+                    continue
+                part = items[k0:k1]
+                frames = np.zeros(len(part), dtype=ops.jpeg_frame_dtype())
+                lens = np.asarray([info["seg_len"] for _i, info in part], dtype=np.int64)
+                frames["seg_len"], frames["seg_off"] = lens, np.concatenate([[0], np.cumsum(lens)[:-1]])
+                frames["dst_off"] = [dst_off + i * fb for i, _info in part]
+                frames["restart_interval"] = [info["restart_interval"] for _i, info in part]
+                frames["table_set"] = [dec.table_index(info["tables"]) for _i, info in part]
+
+                def fill(view, part=part, frames=frames):
+                    for (i, info), o, n in zip(part, frames["seg_off"], frames["seg_len"]):
+                        view[o:o + n] = piece[i][info["seg_off"]:info["seg_off"] + n]
+                if nbytes:
+                    self._stage(0, nbytes, fill, self._jpeg_stream)
+                status = dec.decode(self._jpeg_stream, frames, mode, "u16" if depth else "bgr", self.arena)
+                self._pending.append((status, [(piece[i], int(o)) for (i, _info), o in zip(part, frames["dst_off"])], depth))
+                k0 = k1
+        return sorted(host)
+
+    def _finish_device_decode(self):
+        """the statuses of a source file's launches, read back once; a frame whose status is not 0 takes the host path"""
+        if not self._pending:
+            return
+        status = torch.cat([st for st, _frames, _depth in self._pending]).cpu().numpy()
+        k = 0
+        for _st, frames, depth in self._pending:
+            for buf, off in frames:
+                if status[k]:
+                    self._load_host_frame(buf, off, depth, f"a frame at arena byte {off}")
+                else:
+                    self.decode_stats["device"] += 1
+                k += 1
+        self._pending = []
 
     # ---- batches --------------------------------------------------------------------------------------------------
     def device_bytes(self):

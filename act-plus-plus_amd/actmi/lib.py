@@ -173,6 +173,13 @@ class GatherCloudsDesc(C.Structure):
                [("mirror_c2", C.c_float), ("aligned", C.c_int32)]
 
 
+class JpegDesc(C.Structure):
+    # actmi_jpeg_desc
+    _fields_ = [("stream", C.c_void_p), ("stream_bytes", C.c_int64), ("frames", C.c_void_p), ("tables", C.c_void_p), ("dst", C.c_void_p),
+                ("dst_bytes", C.c_int64), ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("status", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("n", "n_tables", "H", "W", "mode", "form")]
+
+
 _lib = None
 
 
@@ -291,6 +298,9 @@ def load():
         "actmi_op_gather_frames_mirror": ([C.POINTER(GatherMirrorDesc), vp], i32),
         "actmi_op_gather_clouds": ([C.POINTER(GatherCloudsDesc), vp], i32),
         "actmi_op_gather_chunks": ([C.POINTER(GatherChunksDesc), vp], i32),
+        "actmi_op_jpeg_workspace_bytes": ([i64, i32, i32, i32], i64),
+        "actmi_op_jpeg_decode": ([C.POINTER(JpegDesc), vp], i32),
+        "actmi_jpeg_decode_host": ([C.POINTER(JpegDesc)], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

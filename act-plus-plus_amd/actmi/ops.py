@@ -2633,3 +2633,577 @@ def knn_ksweep(idx, dist, n, actions, off, target, mean=None, std=None, want_par
         L.check(L.load().actmi_op_knn_ksweep(_p(idx), _p(dist), _p(n), K, _p(actions), R, _p(off), off.numel(), A, _p(mean), _p(std),
                                              _p(target), _p(partial), _p(sse), Nq, L.current_stream_ptr()), None, "op_knn_ksweep")
     return (sse, partial) if want_partial else sse
+
+
+# ---- baseline JPEG decode (csrc/jpeg_decode.hip, csrc/jpeg_core.h; the definition is at actmi_op_jpeg_decode in actmi.h) ---------
+JPEG_MODES = {"gray": 0, "444": 1, "422": 2, "420": 3}
+JPEG_FORMS = {"bgr": 0, "rgb": 1, "u16": 2}
+JPEG_STATUS = {0: "ok", 1: "overrun", 2: "invalid code", 3: "coefficient index out of range", 4: "restart marker missing or out of sequence",
+               5: "destination outside the buffer", 6: "table set outside the array"}
+_JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+
+
+class JpegUnsupported(ValueError):
+    """what ``jpeg_parse`` refuses: not a JPEG, or a JPEG outside what actmi_op_jpeg_decode accepts"""
+
+
+def jpeg_tables_dtype():
+    """actmi_jpeg_tables as a numpy structured dtype (1960 bytes)"""
+    import numpy as np
+    huff = np.dtype([("maxcode", np.int32, 17), ("valoff", np.int32, 17), ("vals", np.uint8, 256)])
+    return np.dtype([("q", np.uint16, (3, 64)), ("huff", huff, 4), ("dc_sel", np.uint8, 3), ("ac_sel", np.uint8, 3), ("reserved", np.uint8, 2)])
+
+
+def jpeg_frame_dtype():
+    """actmi_jpeg_frame as a numpy structured dtype (32 bytes)"""
+    import numpy as np
+    return np.dtype([("seg_off", np.int64), ("dst_off", np.int64), ("seg_len", np.int32), ("restart_interval", np.int32),
+                     ("table_set", np.int32), ("reserved", np.int32)])
+
+
+def jpeg_out_shape(H, W, form):
+    return (int(H), int(W)) if form == "u16" else (int(H), int(W), 3)
+
+
+def jpeg_parse(buf):
+    """The host parser of one JPEG file (1-D uint8 array or bytes; bytes after EOI are ignored) -> dict with ``H``, ``W``, ``mode``
+    ("gray", "444", "422", "420"), ``restart_interval``, ``tables`` (one ``jpeg_tables_dtype`` record: quantisation tables in natural
+    order per component, up to four Huffman tables and which of them each component uses), ``seg_off`` / ``seg_len`` (the entropy
+    segment: from the byte after the SOS header up to the marker that ends it, or the end of `buf` when there is none).  Raises
+    ``JpegUnsupported`` for everything actmi_op_jpeg_decode does not accept (see actmi.h)."""
+    import numpy as np
+    a = np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+    n = a.size
+    if n < 4 or a[0] != 0xFF or a[1] != 0xD8:
+        raise JpegUnsupported("not a JPEG (no SOI marker)")
+    qt, ht = {}, {}
+    frame = adobe_transform = None
+    ri = 0
+    pos = 2
+    while True:
+        if pos + 4 > n:
+            raise JpegUnsupported("the header ends before a scan begins")
+        if a[pos] != 0xFF:
+            raise JpegUnsupported(f"no marker at byte {pos}")
+        m = int(a[pos + 1])
+        if m == 0xFF:                                             # fill byte
+            pos += 1
+            continue
+        if m == 0xD8 or m == 0x01 or 0xD0 <= m <= 0xD7:
+            pos += 2
+            continue
+        if m == 0xD9:
+            raise JpegUnsupported("EOI before any scan")
+        ln = (int(a[pos + 2]) << 8) | int(a[pos + 3])
+        if ln < 2 or pos + 2 + ln > n:
+            raise JpegUnsupported("a header segment is cut short")
+        seg = a[pos + 4:pos + 2 + ln]
+        if m == 0xC0:
+            if frame is not None:
+                raise JpegUnsupported("more than one frame header")
+            if seg.size < 6 or seg[0] != 8:
+                raise JpegUnsupported("samples are not 8-bit")
+            H, W, nc = (int(seg[1]) << 8) | int(seg[2]), (int(seg[3]) << 8) | int(seg[4]), int(seg[5])
+            if nc not in (1, 3):
+                raise JpegUnsupported(f"{nc} components (1 or 3 are decoded)")
+            if seg.size < 6 + 3 * nc or H < 1 or W < 1:
+                raise JpegUnsupported("bad frame header")
+            frame = (H, W, [(int(seg[6 + 3 * i]), int(seg[7 + 3 * i]) >> 4, int(seg[7 + 3 * i]) & 15, int(seg[8 + 3 * i])) for i in range(nc)])
+        elif 0xC0 < m <= 0xCF and m not in (0xC4, 0xC8):
+            if m == 0xCC:
+                raise JpegUnsupported("arithmetic coding conditioning (DAC)")
+            raise JpegUnsupported(f"SOF{m - 0xC0} (only baseline SOF0 is decoded)")
+        elif m == 0xC4:
+            p = 0
+            while p < seg.size:
+                if p + 17 > seg.size:
+                    raise JpegUnsupported("a Huffman table is cut short")
+                tc, th = int(seg[p]) >> 4, int(seg[p]) & 15
+                counts = seg[p + 1:p + 17].astype(np.int64)
+                tot = int(counts.sum())
+                if tc > 1 or th > 3 or tot > 256 or p + 17 + tot > seg.size:
+                    raise JpegUnsupported("bad Huffman table (class above 1, index above 3 or more than 256 codes)")
+                vals = seg[p + 17:p + 17 + tot]
+                if tc == 0 and tot and int(vals.max()) > 15:
+                    raise JpegUnsupported("a DC Huffman table holds a category above 15")
+                ht[(tc, th)] = (counts, vals.copy())
+                p += 17 + tot
+        elif m == 0xDB:
+            p = 0
+            while p < seg.size:
+                pq, tq = int(seg[p]) >> 4, int(seg[p]) & 15
+                if pq != 0:
+                    raise JpegUnsupported("16-bit quantisation table")
+                if tq > 3 or p + 65 > seg.size:
+                    raise JpegUnsupported("bad quantisation table")
+                qt[tq] = seg[p + 1:p + 65].copy()
+                p += 65
+        elif m == 0xDD:
+            if seg.size < 2:
+                raise JpegUnsupported("bad DRI segment")
+            ri = (int(seg[0]) << 8) | int(seg[1])
+        elif m == 0xEE:
+            if seg.size >= 12 and bytes(seg[:5]) == b"Adobe":
+                adobe_transform = int(seg[11])
+        elif m == 0xDA:
+            break
+        pos += 2 + ln
+    if frame is None:
+        raise JpegUnsupported("a scan before the frame header")
+    H, W, comps = frame
+    if adobe_transform == 0 and len(comps) == 3:
+        raise JpegUnsupported("Adobe APP14 with transform 0 (the components are not YCbCr)")
+    ns = int(seg[0]) if seg.size else 0
+    if ns != len(comps) or seg.size < 1 + 2 * ns + 3:
+        raise JpegUnsupported("the scan does not hold every component (more than one scan)")
+    if int(seg[1 + 2 * ns]) != 0 or int(seg[2 + 2 * ns]) != 63 or int(seg[3 + 2 * ns]) != 0:
+        raise JpegUnsupported("spectral selection or successive approximation in a baseline scan")
+    if len(comps) == 1:
+        mode = "gray"
+    else:
+        samp = tuple((h, v) for _cid, h, v, _tq in comps)
+        mode = {((1, 1), (1, 1), (1, 1)): "444", ((2, 1), (1, 1), (1, 1)): "422", ((2, 2), (1, 1), (1, 1)): "420"}.get(samp)
+        if mode is None:
+            raise JpegUnsupported(f"sampling factors {samp}")
+    tb = np.zeros((), dtype=jpeg_tables_dtype())
+    slots = {}
+    zz = np.asarray(_JPEG_ZIGZAG)
+    for i, (cid, _h, _v, tq) in enumerate(comps):
+        if int(seg[1 + 2 * i]) != cid:
+            raise JpegUnsupported("the scan's components are not in the frame's order")
+        td, ta = int(seg[2 + 2 * i]) >> 4, int(seg[2 + 2 * i]) & 15
+        if tq > 3 or td > 3 or ta > 3:
+            raise JpegUnsupported("a table index above 3")
+        if tq not in qt or (0, td) not in ht or (1, ta) not in ht:
+            raise JpegUnsupported("a table the scan names is missing")
+        q = np.zeros(64, dtype=np.uint16)
+        q[zz] = qt[tq]
+        tb["q"][i] = q
+        for key, sel in (((0, td), "dc_sel"), ((1, ta), "ac_sel")):
+            if key not in slots:
+                if len(slots) == 4:
+                    raise JpegUnsupported("more than four Huffman tables in one scan")
+                slots[key] = len(slots)
+                counts, vals = ht[key]
+                h = tb["huff"][slots[key]]
+                h["maxcode"][:] = -1
+                code = k = 0
+                for l in range(1, 17):
+                    c = int(counts[l - 1])
+                    if c:
+                        h["valoff"][l] = k - code
+                        code += c
+                        k += c
+                        h["maxcode"][l] = code - 1
+                        if code > (1 << l):
+                            raise JpegUnsupported("a Huffman table with more codes than its lengths allow")
+                    code <<= 1
+                h["vals"][:len(vals)] = vals
+            tb[sel][i] = slots[key]
+    seg_off = pos + 2 + ln
+    tail = a[seg_off:]
+    # the segment ends at the first 0xFF that is followed by neither 0x00 nor RSTn
+    ff = np.flatnonzero(tail[:-1] == 0xFF) if tail.size > 1 else np.zeros(0, dtype=np.int64)
+    nxt = tail[ff + 1] if ff.size else ff
+    stop = ff[(nxt != 0) & ((nxt < 0xD0) | (nxt > 0xD7))] if ff.size else ff
+    if stop.size:
+        seg_len = int(stop[0])
+        if int(tail[seg_len + 1]) not in (0xD9, 0xFF):
+            raise JpegUnsupported(f"marker 0x{int(tail[seg_len + 1]):02x} after the scan (more than one scan, or DNL)")
+    else:
+        seg_len = int(tail.size)
+    return {"H": H, "W": W, "mode": mode, "restart_interval": ri, "tables": tb, "seg_off": int(seg_off), "seg_len": seg_len}
+
+
+class _JpegRefBits:
+    """the bit reader of ``jpeg_decode_ref``: the data bytes from `pos` up to the end of the data (a marker, 0xFF as the last byte,
+    the end of the segment), then zero bits; ``over`` once one of those is consumed"""
+
+    def __init__(self, data, end):
+        self.d, self.end = data, end
+        self.over = False
+        self.load(0)
+
+    def load(self, pos):
+        import numpy as np
+        d, end, out, after = self.d, self.end, bytearray(), []
+        i = pos
+        while i < end:
+            c = d[i]
+            if c != 0xFF:
+                out.append(c)
+                i += 1
+            elif i + 1 < end and d[i + 1] == 0:
+                out.append(0xFF)
+                i += 2
+            else:
+                break
+            after.append(i)
+        self.start, self.after = pos, after
+        self.bits = np.unpackbits(np.frombuffer(bytes(out), dtype=np.uint8)).tolist() + [0] * 32
+        self.nbits, self.cur = 8 * len(out), 0
+
+    def get(self, k):
+        v = 0
+        for b in self.bits[self.cur:self.cur + k]:
+            v = (v << 1) | b
+        self.cur += k
+        if self.cur > self.nbits:
+            self.over = True
+            self.bits += [0] * 32
+        return v
+
+    def byte_pos(self):
+        nb = (min(self.cur, self.nbits) + 7) // 8
+        return self.after[nb - 1] if nb else self.start
+
+
+def jpeg_decode_ref(buf, form="bgr", with_status=False, info=None):
+    """numpy statement of ``jpeg_decode`` for one file (the definition in actmi.h, step by step; needs no library): -> the frame, u8
+    [H, W, 3] (``form`` "bgr" or "rgb") or uint16 [H, W] ("u16").  ``with_status``: -> (frame, status) with the status the op gives
+    (a frame whose status is not 0 holds unspecified pixels); without it a damaged stream raises ``ValueError``.  ``info``: what
+    ``jpeg_parse`` said of `buf` before its entropy segment was changed (its ``seg_off`` / ``seg_len`` name bytes of `buf`)."""
+    import numpy as np
+    if form not in JPEG_FORMS:
+        raise ValueError(f"jpeg_decode_ref: form must be one of {sorted(JPEG_FORMS)}")
+    if info is None:
+        info = jpeg_parse(buf)
+    a = np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+    H, W, mode, tb = info["H"], info["W"], info["mode"], info["tables"]
+    nc = 1 if mode == "gray" else 3
+    hmax, vmax = {"gray": (1, 1), "444": (1, 1), "422": (2, 1), "420": (2, 2)}[mode]
+    hs, vs = [hmax, 1, 1][:nc], [vmax, 1, 1][:nc]
+    mx, my = -(-W // (8 * hmax)), -(-H // (8 * vmax))
+    coef = [np.zeros((my * vs[c], mx * hs[c], 64), dtype=np.int64) for c in range(nc)]
+    seg = bytes(a[info["seg_off"]:info["seg_off"] + info["seg_len"]])
+    rd = _JpegRefBits(seg, len(seg))
+    huff = []
+    for t in range(4):
+        h = tb["huff"][t]
+        huff.append(([int(x) for x in h["maxcode"]], [int(x) for x in h["valoff"]], [int(x) for x in h["vals"]]))
+
+    def sym(t):
+        maxcode, valoff, vals = huff[t]
+        code = 0
+        for l in range(1, 17):
+            code = (code << 1) | rd.get(1)
+            if code <= maxcode[l]:
+                return vals[(code + valoff[l]) & 255]
+        return None
+
+    def extend(t):
+        if t == 0:
+            return 0
+        v = rd.get(t)
+        return v - (1 << t) + 1 if v < (1 << (t - 1)) else v
+
+    status, pred, ri, togo, rst = 0, [0] * nc, info["restart_interval"], info["restart_interval"], 0
+    for m in range(mx * my):
+        if status:
+            break
+        if ri > 0 and togo == 0:
+            p = rd.byte_pos()
+            if rd.nbits - rd.cur >= 8 or p + 1 >= len(seg) or seg[p] != 0xFF or seg[p + 1] != 0xD0 + rst:
+                status = 4
+                break
+            rd.load(p + 2)
+            rst, pred, togo = (rst + 1) & 7, [0] * nc, ri
+        if ri > 0:
+            togo -= 1
+        myi, mxi = divmod(m, mx)
+        for c in range(nc):
+            for bv in range(vs[c]):
+                for bh in range(hs[c]):
+                    if status:
+                        break
+                    blk = coef[c][myi * vs[c] + bv, mxi * hs[c] + bh]
+                    t = sym(int(tb["dc_sel"][c]) & 3)
+                    if t is None or t > 15:
+                        status = 2
+                        break
+                    pred[c] = (pred[c] + extend(t) + 2 ** 31) % 2 ** 32 - 2 ** 31
+                    blk[0] = (pred[c] + 2 ** 15) % 2 ** 16 - 2 ** 15
+                    k = 1
+                    while k < 64:
+                        rs = sym(int(tb["ac_sel"][c]) & 3)
+                        if rs is None:
+                            status = 2
+                            break
+                        r, s = rs >> 4, rs & 15
+                        if s:
+                            k += r
+                            if k > 63:
+                                status = 3
+                                break
+                            blk[_JPEG_ZIGZAG[k]] = extend(s)
+                            k += 1
+                        elif r != 15:
+                            break
+                        else:
+                            k += 16
+                    if not status and rd.over:
+                        status = 1
+    if status and not with_status:
+        raise ValueError(f"jpeg_decode_ref: damaged entropy segment ({JPEG_STATUS[status]})")
+
+    def idct_1d(c, n):
+        z1 = (c[2] + c[6]) * 4433
+        t2, t3 = z1 - c[6] * 15137, z1 + c[2] * 6270
+        t0, t1 = (c[0] + c[4]) << 13, (c[0] - c[4]) << 13
+        t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+        t0, t1, t2, t3 = c[7], c[5], c[3], c[1]
+        z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+        z5 = (z3 + z4) * 9633
+        t0, t1, t2, t3 = t0 * 2446, t1 * 16819, t2 * 25172, t3 * 12299
+        z1, z2 = z1 * -7373, z2 * -20995
+        z3, z4 = z3 * -16069 + z5, z4 * -3196 + z5
+        t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+        r = 1 << (n - 1)
+        return [(x + r) >> n for x in (t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3)]
+
+    planes = []
+    for c in range(nc):
+        x = coef[c] * tb["q"][c].astype(np.int64)                 # [by, bx, 64]
+        x = x.reshape(x.shape[0], x.shape[1], 8, 8)
+        p1 = np.stack(idct_1d([x[:, :, k, :] for k in range(8)], 11), axis=2)                      # down the columns
+        p2 = np.stack(idct_1d([p1[:, :, :, k].astype(np.int32).astype(np.int64) for k in range(8)], 18), axis=3)   # along the rows
+        s = np.clip(p2 + 128, 0, 255)
+        planes.append(s.transpose(0, 2, 1, 3).reshape(s.shape[0] * 8, s.shape[1] * 8))
+    Y = planes[0][:H, :W]
+    if nc == 1:
+        R = G = B = Y
+    else:
+        dw, dh = -(-W // hmax), -(-H // vmax)
+        up = []
+        for p in planes[1:]:
+            p = p[:dh, :dw]
+            if hmax == 1:
+                o = p
+            elif dw <= 2:
+                o = np.repeat(np.repeat(p, vmax, axis=0), 2, axis=1)
+            else:
+                if vmax == 2:
+                    o = np.empty((2 * dh, 2 * dw), dtype=np.int64)
+                    above, below = np.concatenate([p[:1], p[:-1]]), np.concatenate([p[1:], p[-1:]])
+                    for v, far, b0, b1 in ((0, above, 8, 7), (1, below, 8, 7)):
+                        s = 3 * p + far
+                        left, right = np.concatenate([s[:, :1], s[:, :-1]], axis=1), np.concatenate([s[:, 1:], s[:, -1:]], axis=1)
+                        o[v::2, 0::2] = (3 * s + left + b0) >> 4
+                        o[v::2, 1::2] = (3 * s + right + b1) >> 4
+                else:
+                    o = np.empty((dh, 2 * dw), dtype=np.int64)
+                    left, right = np.concatenate([p[:, :1], p[:, :-1]], axis=1), np.concatenate([p[:, 1:], p[:, -1:]], axis=1)
+                    o[:, 0::2] = (3 * p + left + 1) >> 2
+                    o[:, 1::2] = (3 * p + right + 2) >> 2
+                    o[:, 0], o[:, -1] = p[:, 0], p[:, -1]
+            up.append(o[:H, :W])
+        cb, cr = up[0] - 128, up[1] - 128
+        R = np.clip(Y + ((91881 * cr + 32768) >> 16), 0, 255)
+        B = np.clip(Y + ((116130 * cb + 32768) >> 16), 0, 255)
+        G = np.clip(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16), 0, 255)
+    if form == "u16":
+        out = B.astype(np.uint16)
+    else:
+        out = np.stack([B, G, R] if form == "bgr" else [R, G, B], axis=-1).astype(np.uint8)
+    out = np.ascontiguousarray(out)
+    return (out, status) if with_status else out
+
+
+def _jpeg_bytes(buf):
+    import numpy as np
+    if isinstance(buf, (bytes, bytearray, memoryview)):
+        return np.frombuffer(buf, dtype=np.uint8)
+    return np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+
+
+def _jpeg_plan(bufs, infos, form, offsets, table_index):
+    """what one decode call takes, from the files: -> (H, W, mode, stream [bytes] u8, frames [n] records, frame_bytes).  The entropy
+    segments are laid back to back; frame i goes to offsets[i] (default: i * frame_bytes)."""
+    import numpy as np
+    if form not in JPEG_FORMS:
+        raise ValueError(f"jpeg_decode: form must be one of {sorted(JPEG_FORMS)}")
+    bufs = [_jpeg_bytes(b) for b in bufs]
+    if infos is None:
+        infos = [jpeg_parse(b) for b in bufs]
+    if not bufs or len(infos) != len(bufs):
+        raise ValueError("jpeg_decode: no frames, or not one parse per frame")
+    H, W, mode = infos[0]["H"], infos[0]["W"], infos[0]["mode"]
+    if any((i["H"], i["W"], i["mode"]) != (H, W, mode) for i in infos):
+        raise ValueError("jpeg_decode: one call decodes frames of one size and one sampling mode")
+    fb = H * W * (2 if form == "u16" else 3)
+    frames = np.zeros(len(bufs), dtype=jpeg_frame_dtype())
+    lens = np.asarray([i["seg_len"] for i in infos], dtype=np.int64)
+    frames["seg_len"] = lens
+    frames["seg_off"] = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    frames["dst_off"] = np.arange(len(bufs), dtype=np.int64) * fb if offsets is None else np.asarray(offsets, dtype=np.int64)
+    frames["restart_interval"] = [i["restart_interval"] for i in infos]
+    frames["table_set"] = [table_index(i["tables"]) for i in infos]
+    stream = np.concatenate([b[i["seg_off"]:i["seg_off"] + i["seg_len"]] for b, i in zip(bufs, infos)] + [np.zeros(1, dtype=np.uint8)])
+    return H, W, mode, stream, frames, fb
+
+
+class _JpegTableSets:
+    """table sets deduplicated by content (cv2 writes the same standard tables into every frame of a recording)"""
+
+    def __init__(self):
+        self.sets, self._index = [], {}
+
+    def index(self, tables):
+        key = tables.tobytes()
+        i = self._index.get(key)
+        if i is None:
+            i = self._index[key] = len(self.sets)
+            self.sets.append(key)
+        return i
+
+    def array(self):
+        import numpy as np
+        return np.frombuffer(b"".join(self.sets), dtype=np.uint8).copy()
+
+
+def _aligned_u8(nbytes, align=16):
+    import numpy as np
+    raw = np.empty(nbytes + align, dtype=np.uint8)
+    o = (-raw.ctypes.data) % align
+    return raw[o:o + nbytes]
+
+
+def jpeg_decode_host(bufs, out=None, offsets=None, form="bgr", infos=None, ws=None):
+    """actmi_jpeg_decode_host, the CPU twin of ``jpeg_decode`` (the same core, no device): `bufs` JPEG files of one size and
+    sampling mode -> (out, status): out u8 [n, H, W, 3] / uint16 [n, H, W], or the caller's contiguous 1-D uint8 array in which frame
+    i starts at byte offsets[i]; status int32 [n].  ``infos``: a parse per file that replaces ``jpeg_parse`` (tests change a
+    segment after it was parsed).  ``ws``: a 16-byte aligned uint8 array of at least ``jpeg_workspace_bytes`` bytes."""
+    import numpy as np
+    sets = _JpegTableSets()
+    H, W, mode, stream, frames, fb = _jpeg_plan(bufs, infos, form, offsets, sets.index)
+    n = len(frames)
+    if out is None:
+        if offsets is not None:
+            raise ValueError("jpeg_decode_host: offsets name places in the caller's out")
+        out = np.empty((n,) + jpeg_out_shape(H, W, form), dtype=np.uint16 if form == "u16" else np.uint8)
+    elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous:
+        raise ValueError("jpeg_decode_host: out must be a contiguous 1-D uint8 array")
+    lib = L.load()
+    need = int(lib.actmi_op_jpeg_workspace_bytes(n, H, W, JPEG_MODES[mode]))
+    if ws is None:
+        ws = _aligned_u8(need)
+    tables = _aligned_u8(len(sets.sets) * jpeg_tables_dtype().itemsize)
+    tables[:] = sets.array()
+    status = np.full(n, -1, dtype=np.int32)
+    d = L.JpegDesc()
+    d.stream, d.stream_bytes, d.frames, d.tables = stream.ctypes.data, stream.size - 1, frames.ctypes.data, tables.ctypes.data
+    d.dst, d.dst_bytes, d.ws, d.ws_bytes, d.status = out.ctypes.data, out.nbytes, ws.ctypes.data, ws.nbytes, status.ctypes.data
+    d.n, d.n_tables, d.H, d.W, d.mode, d.form = n, len(sets.sets), H, W, JPEG_MODES[mode], JPEG_FORMS[form]
+    L.check(lib.actmi_jpeg_decode_host(C.byref(d)), None, "jpeg_decode_host")
+    return out, status
+
+
+def jpeg_workspace_bytes(n, H, W, mode):
+    return int(L.load().actmi_op_jpeg_workspace_bytes(int(n), int(H), int(W), JPEG_MODES[mode]))
+
+
+class JpegDecoder:
+    """The device state of ``jpeg_decode`` for frames of one size: the workspace (``max_frames`` slots of the largest sampling mode
+    met so far), the table sets met so far, deduplicated by content and uploaded when a new one appears, and one parse cache (the
+    frames of a recording share their header bytes).  ``decode`` launches actmi_op_jpeg_decode for up to ``max_frames`` frames at a
+    time on the current stream and returns the statuses as a device tensor: nothing is read back here."""
+
+    def __init__(self, device, H, W, max_frames=64):
+        self.device, self.H, self.W, self.max_frames = torch.device(device), int(H), int(W), int(max_frames)
+        if self.max_frames < 1 or self.max_frames > 65535:
+            raise ValueError("JpegDecoder: max_frames must be in 1..65535")
+        self._sets, self._uploaded, self._tables = _JpegTableSets(), 0, None
+        self._ws, self._hdr = None, None
+
+    def parse(self, buf):
+        """``jpeg_parse`` of one file; a file that begins with the bytes of the last one's header reuses its parse"""
+        import numpy as np
+        a = _jpeg_bytes(buf)
+        if self._hdr is not None:
+            head, info = self._hdr
+            k = len(head)
+            if a.size > k + 1 and a[:k].tobytes() == head:
+                tail = a[k:]
+                ff = np.flatnonzero(tail[:-1] == 0xFF)
+                nxt = tail[ff + 1]
+                stop = ff[(nxt != 0) & ((nxt < 0xD0) | (nxt > 0xD7))]
+                if stop.size and int(tail[stop[0] + 1]) == 0xD9:
+                    return dict(info, seg_len=int(stop[0]))
+        info = jpeg_parse(a)
+        self._hdr = (a[:info["seg_off"]].tobytes(), info)
+        return info
+
+    def table_index(self, tables):
+        return self._sets.index(tables)
+
+    def workspace_bytes(self, mode):
+        return jpeg_workspace_bytes(self.max_frames, self.H, self.W, mode)
+
+    def decode(self, stream, frames, mode, form, dst):
+        """stream: 1-D uint8 tensor on the device holding the entropy segments; frames: ``jpeg_frame_dtype`` records (numpy); dst: a
+        contiguous tensor on the device (any dtype: offsets and the bound are bytes) -> status int32 [n] on the device"""
+        n = len(frames)
+        if n == 0:
+            return torch.zeros(0, dtype=torch.int32, device=self.device)
+        if stream.dtype != torch.uint8 or stream.dim() != 1 or stream.device != self.device or not stream.is_contiguous():
+            raise ValueError(f"JpegDecoder: stream must be a contiguous 1-D uint8 tensor on {self.device}")
+        if dst.device != self.device or not dst.is_contiguous():
+            raise ValueError(f"JpegDecoder: dst must be contiguous on {self.device}")
+        lib = L.load()
+        if len(self._sets.sets) != self._uploaded:
+            self._tables = torch.from_numpy(self._sets.array()).to(self.device)
+            self._uploaded = len(self._sets.sets)
+        if self._tables is None:
+            raise ValueError("JpegDecoder: no table set (table_index gives the frames' indices)")
+        need = self.workspace_bytes(mode)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        import numpy as np
+        rec = torch.from_numpy(np.ascontiguousarray(frames).view(np.uint8).reshape(-1).copy()).to(self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        d = L.JpegDesc()
+        d.stream, d.stream_bytes, d.tables, d.n_tables = stream.data_ptr(), int(stream.numel()), self._tables.data_ptr(), self._uploaded
+        d.dst, d.dst_bytes, d.ws, d.ws_bytes = dst.data_ptr(), int(dst.numel() * dst.element_size()), self._ws.data_ptr(), int(self._ws.numel())
+        d.H, d.W, d.mode, d.form = self.H, self.W, JPEG_MODES[mode], JPEG_FORMS[form]
+        with torch.cuda.device(self.device):
+            for i0 in range(0, n, self.max_frames):
+                m = min(self.max_frames, n - i0)
+                d.frames, d.status, d.n = rec.data_ptr() + 32 * i0, status.data_ptr() + 4 * i0, m
+                L.check(lib.actmi_op_jpeg_decode(C.byref(d), L.current_stream_ptr()), None, "op_jpeg_decode")
+        return status
+
+
+def jpeg_decode(bufs, out=None, offsets=None, form="bgr", infos=None, device=None, decoder=None):
+    """actmi_op_jpeg_decode: `bufs` JPEG files (1-D uint8 arrays or bytes) of one size and sampling mode, decoded on the device ->
+    (out, status): out u8 [n, H, W, 3] in B, G, R (``form`` "bgr") or R, G, B ("rgb") order, or uint16 [n, H, W] ("u16": channel 0 of
+    the B, G, R pixel) -- or the caller's contiguous cuda tensor, in which frame i starts at byte offsets[i]; status int32 [n] on the
+    device, 0 or the cause (``JPEG_STATUS``): the pixels of such a frame are unspecified, those of every other frame are
+    ``jpeg_decode_ref``'s bit for bit.  A file ``jpeg_parse`` refuses raises ``JpegUnsupported``: nothing is launched."""
+    import numpy as np
+    if out is not None:
+        device = out.device
+    elif device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    sets = decoder._sets if decoder is not None else _JpegTableSets()
+    H, W, mode, stream, frames, fb = _jpeg_plan(bufs, infos, form, offsets, sets.index)
+    n = len(frames)
+    if decoder is None:
+        decoder = JpegDecoder(device, H, W, max_frames=min(n, 256))
+        decoder._sets = sets
+    elif (decoder.H, decoder.W) != (H, W) or decoder.device != device:
+        raise ValueError(f"jpeg_decode: the decoder is for {decoder.H} x {decoder.W} frames on {decoder.device}")
+    if out is None:
+        if offsets is not None:
+            raise ValueError("jpeg_decode: offsets name places in the caller's out")
+        out = torch.empty((n,) + jpeg_out_shape(H, W, form), dtype=torch.uint16 if form == "u16" else torch.uint8, device=device)
+    elif not out.is_cuda or not out.is_contiguous():
+        raise ValueError("jpeg_decode: out must be a contiguous cuda tensor")
+    pinned = torch.empty(stream.size, dtype=torch.uint8, pin_memory=True)     # one byte more than the segments: never empty
+    pinned.numpy()[:] = stream
+    dev_stream = pinned.to(device, non_blocking=True)
+    status = decoder.decode(dev_stream, frames, mode, form, out)
+    torch.cuda.current_stream(device).synchronize()                # the pinned staging is this call's alone
+    return out, status

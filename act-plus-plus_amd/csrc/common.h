@@ -275,6 +275,11 @@ int launch_gather_frames_mirror(const actmi_gather_mirror_desc& d, hipStream_t s
 int launch_gather_clouds(const actmi_gather_clouds_desc& d, hipStream_t st, std::string* err);
 int launch_gather_chunks(const actmi_gather_chunks_desc& d, hipStream_t st, std::string* err);
 
+// ---- baseline JPEG decode (jpeg_decode.hip, jpeg_core.h; contract at actmi_op_jpeg_decode in actmi.h) ----------------------
+int64_t jpeg_workspace_bytes(int64_t n, int H, int W, int mode);
+int launch_jpeg_decode(const actmi_jpeg_desc& d, hipStream_t st, std::string* err);
+int jpeg_decode_host(const actmi_jpeg_desc& d, std::string* err);   // the same core on the CPU, host pointers
+
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------
 bool prof_enabled();
 void prof_begin(const char* name, double flops, double bytes, hipStream_t st);

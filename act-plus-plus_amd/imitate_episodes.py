@@ -19,6 +19,8 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
 * ``--device_dataset --use_pcd --device_clouds`` puts the task's stored point clouds into that store as well (the batches' clouds are
   gathered on the device; ``--replay_every`` then serves point-cloud policies), and ``--mirror_twins --use_pcd --cloud_mirror_axis
   {x,y,z} [--cloud_mirror_offset C]`` gives a stored cloud the mirror rule the twins need;
+* ``--device_dataset --device_decode`` decodes the JPEG frames of compressed episodes on the device as that store is loaded
+  (actmi_op_jpeg_decode, bit for bit the host's PIL decode); the store holds the same bytes;
 * ``--mirror_twins`` joins every episode file by its mirrored twin (postprocess_episodes.py's definition), computed as it is read:
   ``actmi.data.load_data(..., mirror_twins=True)``; with ``--device_dataset`` the twins share their sources' frames;
 * ``--augment_images`` and, for the stored clouds of ``--use_pcd``, ``--augment_clouds`` augment the TRAINING batches on the
@@ -1149,6 +1151,10 @@ def build_config(args):
         config["device_dataset"] = True
         if args.get("device_dataset_gb") is not None:
             config["device_dataset_gb"] = float(args["device_dataset_gb"])
+    if args.get("device_decode"):
+        if not args.get("device_dataset"):
+            raise ValueError("--device_decode decodes the compressed frames of the device-resident store: it needs --device_dataset")
+        config["device_decode"] = True
     if args.get("device_clouds"):
         if not (args.get("device_dataset") and args.get("use_pcd")):
             raise ValueError("--device_clouds puts the stored clouds of a --use_pcd dataset into the device-resident store: it needs "
@@ -1228,7 +1234,7 @@ def _load_episode_data(args, config, task_config, dataset_dir, world, local_rank
                      use_pcd=bool(config["policy_config"].get("use_pcd")), max_points=config["policy_config"].get("max_points"),
                      # --device_dataset: every rank holds its own full store on its own device
                      device_dataset=bool(config.get("device_dataset")), mirror_twins=bool(config.get("mirror_twins")),
-                     device_clouds=bool(config.get("device_clouds")),
+                     device_clouds=bool(config.get("device_clouds")), device_decode=bool(config.get("device_decode")),
                      cloud_mirror=tuple(config["cloud_mirror"]) if config.get("cloud_mirror") else None,
                      device=f"cuda:{local_rank}" if world > 1 else None,     # train_bc's device
                      device_budget_bytes=(int(config["device_dataset_gb"] * 2**30)
@@ -1420,6 +1426,9 @@ def make_parser():
                         help="--device_dataset --use_pcd, opt-in: the task's stored point clouds go into the device-resident store "
                              "and every batch's clouds are gathered on the device; lifts the refusal of --device_dataset (and of "
                              "--replay_every) with --use_pcd")
+    parser.add_argument("--device_decode", action="store_true",
+                        help="--device_dataset, opt-in: the JPEG frames of compressed episodes are decoded on the device as the store "
+                             "is loaded (actmi_op_jpeg_decode) instead of one by one on the host; the store holds the same bytes")
     parser.add_argument("--cloud_mirror_axis", action="store", type=str, choices=("x", "y", "z"), default=None,
                         help="--mirror_twins --use_pcd: the twin's stored cloud is the source's reflected across a plane normal to "
                              "this axis of the clouds' frame; lifts the refusal of --mirror_twins with --use_pcd")

@@ -1084,6 +1084,106 @@ typedef struct actmi_gather_chunks_desc {
     int32_t n_episodes, B, A, S, Q;
 } actmi_gather_chunks_desc;
 int actmi_op_gather_chunks(const actmi_gather_chunks_desc* d, void* stream);
+/* ---- baseline JPEG decode (csrc/jpeg_decode.hip, csrc/jpeg_core.h): the compressed frames of an episode file on the device ----
+ * The result is, bit for bit, what libjpeg-turbo with its defaults gives (integer "islow" inverse DCT, "fancy" chroma
+ * upsampling, integer YCbCr -> RGB): what PIL, and so data.imdecode_bgr, returns.  actmi.ops.jpeg_decode_ref states it in numpy.
+ *
+ * Accepted: baseline sequential JPEG (SOF0, 8-bit samples), ONE interleaved Huffman-coded scan, 1 component or 3 components taken
+ * as YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1 (4:4:4, 4:2:2, 4:2:0), optional DRI / RSTn restart markers; bytes
+ * after EOI are ignored (the files zero-pad every frame to a common length).  Everything else (SOF1, SOF2 and every other SOF,
+ * arithmetic coding, 4 components, an Adobe APP14 segment with transform 0, other sampling factors, more than one scan, a missing
+ * table, a table index above 3, 16-bit quantisation tables, not a JPEG at all) is refused by the HOST parser
+ * (actmi.ops.jpeg_parse, JpegUnsupported) before anything is launched: the library sees geometry, tables and entropy segments.
+ *
+ * Entropy decode: canonical Huffman codes from the DHT counts (actmi_jpeg_huff); a 0xFF 0x00 pair is the data byte 0xFF; any
+ * other byte after 0xFF, 0xFF as the last byte, and the end of the segment end the data: from there the reader supplies zero
+ * bits, and a frame that consumes one has status OVERRUN.  Per block: the DC difference extend(receive(t), t) is added to the
+ * component's predictor (stored as int16, as libjpeg does); the AC run/size symbols follow the baseline rule (0x00 ends the
+ * block, 0xF0 skips 16 coefficients; a position above 63 is status COEF); coefficients are stored in natural order through the
+ * zigzag table.  MCU order: row-major over MCUs, then components, then the component's v x h blocks.  The restart interval
+ * counts MCUs; at a restart fewer than 8 unread data bits may remain (they are dropped), the marker 0xFF 0xD0 + (k mod 8) must
+ * follow directly (else status RESTART), and the predictors return to 0.
+ * Dequantise: coef * q, q the component's table out of zigzag order.
+ * Inverse DCT: jidctint's "islow", CONST_BITS 13, PASS1_BITS 2, 64-bit integers; descale(x, n) = (x + (1 << (n-1))) >> n
+ * (arithmetic shift); pass 1 down the columns with n = 11, pass 2 along the rows of the pass-1 result with n = 18, sample =
+ * clamp(x + 128, 0, 255).  With c0..c7 one column / row:
+ *   even: z1 = (c2 + c6) * 4433; t2 = z1 - c6 * 15137; t3 = z1 + c2 * 6270; t0 = (c0 + c4) << 13; t1 = (c0 - c4) << 13;
+ *         t10 = t0 + t3; t13 = t0 - t3; t11 = t1 + t2; t12 = t1 - t2
+ *   odd:  t0 = c7; t1 = c5; t2 = c3; t3 = c1; z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2; z4 = t1 + t3; z5 = (z3 + z4) * 9633;
+ *         t0 *= 2446; t1 *= 16819; t2 *= 25172; t3 *= 12299; z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5;
+ *         z4 = z4 * -3196 + z5; t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4
+ *   out 0..7: t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3
+ * Chroma upsampling, on the component's real extent dw = ceil(W * h / hmax) by dh = ceil(H * v / vmax) (not the block-padded
+ * plane), p the chroma plane: dw <= 2: plain replication.  Otherwise 2x1: out[2i] = (3 p[i] + p[i-1] + 1) >> 2, out[2i+1] =
+ * (3 p[i] + p[i+1] + 2) >> 2, out[0] = p[0], out[2dw-1] = p[dw-1].  Otherwise 2x2: for output row 2r + v, s[i] = 3 p[r][i] +
+ * far[i], far = row r-1 (v = 0) or r+1 (v = 1), row -1 being row 0 and row dh row dh-1; out[2i] = (3 s[i] + s[i-1] + 8) >> 4,
+ * out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4, out[0] = (4 s[0] + 8) >> 4, out[2dw-1] = (4 s[dw-1] + 7) >> 4.  Cut to H x W.
+ * Colour, x = c - 128, arithmetic shifts: R = clamp(Y + ((91881 x_cr + 32768) >> 16)), B = clamp(Y + ((116130 x_cb + 32768) >>
+ * 16)), G = clamp(Y + ((-22554 x_cb + 32768 - 46802 x_cr) >> 16)); one component: R = G = B = Y.
+ * Output forms: u8 [H][W][3] in B, G, R order (imdecode_bgr; what the episode store keeps), u8 [H][W][3] in R, G, B order, and
+ * uint16 [H][W] = channel 0 of the B, G, R pixel (what the store keeps of a compressed depth frame).
+ *
+ * actmi_op_jpeg_decode decodes n frames of ONE geometry (H, W, mode) in three passes: entropy (one workgroup per frame, one lane
+ * decoding from an LDS window of the segment into the frame's pre-zeroed int16 coefficients), dequantise + IDCT (one lane per
+ * block, into u8 planes), upsampling + colour + packed stores (one lane per 4 pixels).  Frames of one launch may use different
+ * table sets and have different lengths.  Workspace: n slots of actmi_op_jpeg_workspace_bytes(1, H, W, mode) bytes, 16-byte
+ * aligned.  Safety holds for ANY segment bytes and ANY record: nothing is read outside a frame's [seg_off, seg_off + seg_len)
+ * (a range that leaves the stream is taken as empty), no coefficient index exceeds 63, no Huffman walk exceeds 16 bits, nothing
+ * is written outside the frame's destination extent [dst_off, dst_off + H * W * px) or outside its workspace slot, and every
+ * loop over stream content is bounded by the geometry (at most blocks * 64 symbols per frame).  status[i]: 0, or the FIRST
+ * cause met (ACTMI_JPEG_ST_*); the pixels of a frame with a nonzero status are unspecified, those of every other frame exact.
+ * ACTMI_E_INVALID before any launch: a null pointer, n < 0 or n > 65535, H or W outside [1, 65535], an unknown mode or form,
+ * n_tables < 1, a workspace or destination that cannot hold n frames, misaligned records / tables / workspace.  The records
+ * live in device memory, so a table index outside the array is status TABLE from the device; actmi_jpeg_decode_host, the same
+ * core run on the CPU over host pointers (what the non-GPU tests exercise), returns ACTMI_E_INVALID for it before it decodes. */
+#define ACTMI_JPEG_GRAY 0
+#define ACTMI_JPEG_444 1
+#define ACTMI_JPEG_422 2
+#define ACTMI_JPEG_420 3
+#define ACTMI_JPEG_FORM_BGR 0
+#define ACTMI_JPEG_FORM_RGB 1
+#define ACTMI_JPEG_FORM_U16 2
+#define ACTMI_JPEG_ST_OK 0
+#define ACTMI_JPEG_ST_OVERRUN 1    /* bits consumed past the end of the data */
+#define ACTMI_JPEG_ST_BADCODE 2    /* 16 bits that are no Huffman code, or a DC category above 15 */
+#define ACTMI_JPEG_ST_COEF 3       /* a coefficient position above 63 */
+#define ACTMI_JPEG_ST_RESTART 4    /* restart marker missing or out of sequence */
+#define ACTMI_JPEG_ST_DEST 5       /* the destination extent leaves the buffer: nothing written */
+#define ACTMI_JPEG_ST_TABLE 6      /* table_set outside [0, n_tables): nothing decoded */
+typedef struct actmi_jpeg_huff {   /* one Huffman table: 392 bytes */
+    int32_t maxcode[17];           /* [l], l = 1..16: the largest code of length l, -1 when there is none */
+    int32_t valoff[17];            /* [l]: index into vals of the first code of length l, minus that code */
+    uint8_t vals[256];             /* the symbols in code order */
+} actmi_jpeg_huff;
+typedef struct actmi_jpeg_tables { /* one table set: 1960 bytes */
+    uint16_t q[3][64];             /* per component, natural order */
+    actmi_jpeg_huff huff[4];
+    uint8_t dc_sel[3], ac_sel[3];  /* per component: which of huff[] (values are taken mod 4) */
+    uint8_t reserved[2];
+} actmi_jpeg_tables;
+typedef struct actmi_jpeg_frame {  /* one frame: 32 bytes */
+    int64_t seg_off;               /* of its entropy segment in `stream` */
+    int64_t dst_off;               /* of its output in `dst`, bytes; any value (odd ones take byte stores) */
+    int32_t seg_len;
+    int32_t restart_interval;      /* MCUs, 0 = none */
+    int32_t table_set;
+    int32_t reserved;
+} actmi_jpeg_frame;
+typedef struct actmi_jpeg_desc {
+    const uint8_t* stream;         /* the entropy segments */
+    int64_t stream_bytes;
+    const actmi_jpeg_frame* frames;    /* [n], 8-byte aligned */
+    const actmi_jpeg_tables* tables;   /* [n_tables], 8-byte aligned */
+    void* dst;
+    int64_t dst_bytes;
+    void* ws;                      /* 16-byte aligned */
+    int64_t ws_bytes;
+    int32_t* status;               /* [n] */
+    int32_t n, n_tables, H, W, mode, form;
+} actmi_jpeg_desc;
+int64_t actmi_op_jpeg_workspace_bytes(int64_t n, int H, int W, int mode);   /* -1 for a bad argument */
+int actmi_op_jpeg_decode(const actmi_jpeg_desc* d, void* stream);
+int actmi_jpeg_decode_host(const actmi_jpeg_desc* d);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
