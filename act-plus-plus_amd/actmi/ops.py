@@ -1847,6 +1847,25 @@ class TemporalEnsemble:
 
 
 # ---- open-loop replay of recorded episodes (csrc/replay_eval.hip) --------------------------------------------------------------
+def _device_table(name, t, dtype, dims):
+    """the operand ``name`` of a replay op: a cuda tensor of ``dtype`` with the dimensions ``dims`` ("E, T, Q, A") -> contiguous"""
+    if t.dim() != dims.count(",") + 1 or t.dtype != dtype or not t.is_cuda:
+        raise ValueError(f"{name} must be a {str(dtype)[6:]} cuda tensor [{dims}], got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t.contiguous()
+
+
+def _stats_f64(op, mean, std, A, dev, optional=False):
+    """mean / std of the A action components -> float64 [A] tensors on ``dev``; ``optional``: both may be None, together"""
+    if optional and (mean is None or std is None):
+        if (mean is None) != (std is None):
+            raise ValueError(f"{op}: mean and std come together")
+        return None, None
+    mean, std = (torch.as_tensor(v).to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for v in (mean, std))
+    if mean.numel() != A or std.numel() != A:
+        raise ValueError(f"{op}: mean / std hold {mean.numel()} / {std.numel()} values for action_dim {A}")
+    return mean, std
+
+
 def _lengths_i32(lengths, E, T, device):
     if lengths is None:
         return None
@@ -1862,9 +1881,7 @@ def episode_ensemble(chunks, lengths=None, k=0.01, want_populated=False):
     f64, and with ``want_populated`` the u8 mask [E, T, Q] of the rows that counted (row j of step t is r = t-(Q-1)+j).  Step t
     of episode e is bit for bit what the t-th ``TemporalEnsemble.step`` gives on the same chunks; rows t >= lengths[e] are
     zeros."""
-    if chunks.dim() != 4 or chunks.dtype != torch.float32 or not chunks.is_cuda:
-        raise ValueError(f"chunks must be a float32 cuda tensor [E, T, Q, A], got {chunks.dtype} {tuple(chunks.shape)} on {chunks.device}")
-    chunks = chunks.contiguous()
+    chunks = _device_table("chunks", chunks, torch.float32, "E, T, Q, A")
     E, T, Q, A = (int(v) for v in chunks.shape)
     dev = chunks.device
     ln = _lengths_i32(lengths, E, T, dev)
@@ -1903,17 +1920,13 @@ def action_error(raw, target, lengths, mean, std, want_pred=True):
     """Un-normalise and compare with the recording on the device (actmi_op_action_error).  raw [E, T, A] f64 cuda, target
     [E, T, A] f32 (file units, already aligned), lengths [E] or None, mean / std [A] -> (pred [E, T, A] f64 = raw * std + mean
     or None, stats [E, 3, A] f64 = sum |d|, sum d^2, max |d| over t < lengths[e], d = pred - target)."""
-    if raw.dim() != 3 or raw.dtype != torch.float64 or not raw.is_cuda:
-        raise ValueError(f"raw must be a float64 cuda tensor [E, T, A], got {raw.dtype} {tuple(raw.shape)} on {raw.device}")
-    raw = raw.contiguous()
+    raw = _device_table("raw", raw, torch.float64, "E, T, A")
     E, T, A = (int(v) for v in raw.shape)
     dev = raw.device
     target = torch.as_tensor(target).to(device=dev, dtype=torch.float32).contiguous()
     if tuple(target.shape) != (E, T, A):
         raise ValueError(f"target has shape {tuple(target.shape)}, expected {(E, T, A)}")
-    mean, std = (torch.as_tensor(v).to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for v in (mean, std))
-    if mean.numel() != A or std.numel() != A:
-        raise ValueError(f"mean / std hold {mean.numel()} / {std.numel()} values for action_dim {A}")
+    mean, std = _stats_f64("action_error", mean, std, A, dev)
     ln = _lengths_i32(lengths, E, T, dev)
     pred = torch.empty((E, T, A), dtype=torch.float64, device=dev) if want_pred else None
     stats = torch.empty((E, 3, A), dtype=torch.float64, device=dev)
@@ -1945,9 +1958,7 @@ def chunk_error(chunks, actions, lengths, shift, mean, std, stride=1):
     or None (= T); shift [E] of 0 / 1 or None (= 0; 1: a real-robot episode under align="train"); mean / std [A].  Slot j of row
     s is compared with actions[e, max(0, r - shift[e]) + j] while r and that index are below the length: the entries the dataset
     trains the slot on.  -> (stats [E, Q, 3, A] f64 = sum |d|, sum d^2, max |d|, count [E, Q] int32 pairs per slot)."""
-    if chunks.dim() != 4 or chunks.dtype != torch.float32 or not chunks.is_cuda:
-        raise ValueError(f"chunks must be a float32 cuda tensor [E, S, Q, A], got {chunks.dtype} {tuple(chunks.shape)} on {chunks.device}")
-    chunks = chunks.contiguous()
+    chunks = _device_table("chunks", chunks, torch.float32, "E, S, Q, A")
     E, S, Q, A = (int(v) for v in chunks.shape)
     dev = chunks.device
     actions = torch.as_tensor(actions).to(device=dev, dtype=torch.float32).contiguous()
@@ -1956,9 +1967,7 @@ def chunk_error(chunks, actions, lengths, shift, mean, std, stride=1):
     T, stride = int(actions.shape[1]), int(stride)
     if E > 65535 or Q > 65535 or Q < 1 or A < 1 or T < 1 or stride < 1:
         raise ValueError(f"chunk_error: E {E} and Q {Q} must be at most 65535, Q, A {A}, T {T} and stride {stride} at least 1")
-    mean, std = (torch.as_tensor(v).to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for v in (mean, std))
-    if mean.numel() != A or std.numel() != A:
-        raise ValueError(f"mean / std hold {mean.numel()} / {std.numel()} values for action_dim {A}")
+    mean, std = _stats_f64("chunk_error", mean, std, A, dev)
     ln = _lengths_i32(lengths, E, T, dev)
     sh = _lengths_i32(shift, E, T, dev)
     if not (E and S):                            # nothing is launched: the zeros are the answer
@@ -2076,9 +2085,7 @@ def ensemble_sweep(chunks, schedules, length=None, want_empty=False):
     int32 [G] count of the steps t < length of an ensemble schedule that found no populated live row (they are zeros).  An
     ensemble schedule (every, horizon, k) gives the bits of ``episode_ensemble`` with that k on the table whose dead entries
     (r % every != 0 or slot >= horizon) are zeroed; rows t >= length are zeros."""
-    if chunks.dim() != 3 or chunks.dtype != torch.float32 or not chunks.is_cuda:
-        raise ValueError(f"chunks must be a float32 cuda tensor [T, Q, A], got {chunks.dtype} {tuple(chunks.shape)} on {chunks.device}")
-    chunks = chunks.contiguous()
+    chunks = _device_table("chunks", chunks, torch.float32, "T, Q, A")
     T, Q, A = (int(v) for v in chunks.shape)
     dev = chunks.device
     if A < 1 or A > 64 or Q < 1 or Q > 7680:
@@ -2136,9 +2143,7 @@ def sweep_error(raw, target, length, mean, std, want_pred=True):
     [A] -> (pred [G, T, A] f64 = raw * std + mean or None, stats [G, 4, A] f64: rows 0-2 = sum |d|, sum d^2, max |d| over
     t < length, the bits of ``action_error`` on raw[g]; row 3 = sum over 1 <= t < length of |pred[t] - pred[t-1]|, the
     roughness of the executed trajectory)."""
-    if raw.dim() != 3 or raw.dtype != torch.float64 or not raw.is_cuda:
-        raise ValueError(f"raw must be a float64 cuda tensor [G, T, A], got {raw.dtype} {tuple(raw.shape)} on {raw.device}")
-    raw = raw.contiguous()
+    raw = _device_table("raw", raw, torch.float64, "G, T, A")
     G, T, A = (int(v) for v in raw.shape)
     dev = raw.device
     if G < 1 or G > 65535 or A < 1:
@@ -2146,9 +2151,7 @@ def sweep_error(raw, target, length, mean, std, want_pred=True):
     target = torch.as_tensor(target).to(device=dev, dtype=torch.float32).contiguous()
     if tuple(target.shape) != (T, A):
         raise ValueError(f"target has shape {tuple(target.shape)}, expected {(T, A)}")
-    mean, std = (torch.as_tensor(v).to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for v in (mean, std))
-    if mean.numel() != A or std.numel() != A:
-        raise ValueError(f"mean / std hold {mean.numel()} / {std.numel()} values for action_dim {A}")
+    mean, std = _stats_f64("sweep_error", mean, std, A, dev)
     n = T if length is None else int(length)
     pred = torch.empty((G, T, A), dtype=torch.float64, device=dev) if want_pred else None
     stats = torch.empty((G, 4, A), dtype=torch.float64, device=dev)
@@ -2182,14 +2185,20 @@ def episode_rec_dtype():
     return np.dtype([("row0", np.int64), ("T", np.int32), ("is_sim", np.int32)])
 
 
+def _store_arena(op, arena, src_off=None):
+    """the arena a store op gathers from -- a contiguous 1-D uint8 cuda tensor -- and, when given, the byte offsets into it"""
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_cuda or not arena.is_contiguous():
+        raise ValueError(f"{op}: arena must be a contiguous 1-D uint8 cuda tensor, got {arena.dtype} {tuple(arena.shape)}")
+    if src_off is not None and (src_off.dtype != torch.int64 or src_off.dim() != 1 or src_off.device != arena.device
+                                or not src_off.is_contiguous()):
+        raise ValueError(f"{op}: src_off must be a contiguous 1-D int64 tensor on the arena's device")
+
+
 def gather_frames(arena, src_off, item_bytes, out=None, aligned=0):
     """actmi_op_gather_frames: arena 1-D uint8 cuda, src_off [n] int64 cuda (byte offsets into the arena) -> out [n, item_bytes]
     uint8 (or the caller's contiguous cuda tensor of n * item_bytes bytes, any dtype and shape).  aligned: 0 general, 1 the
     caller vouches that every offset is a multiple of 16 (item_bytes, arena and out must be), 2 the same with non-temporal loads."""
-    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_cuda or not arena.is_contiguous():
-        raise ValueError(f"gather_frames: arena must be a contiguous 1-D uint8 cuda tensor, got {arena.dtype} {tuple(arena.shape)}")
-    if src_off.dtype != torch.int64 or src_off.dim() != 1 or src_off.device != arena.device or not src_off.is_contiguous():
-        raise ValueError("gather_frames: src_off must be a contiguous 1-D int64 tensor on the arena's device")
+    _store_arena("gather_frames", arena, src_off)
     n, item_bytes = int(src_off.numel()), int(item_bytes)
     if out is None:
         out = torch.empty((n, item_bytes), dtype=torch.uint8, device=arena.device)
@@ -2221,10 +2230,7 @@ def gather_frames_mirror(arena, src_off, flip, H, W, px_bytes, out=None, aligned
     [n] int64 and flip [n] uint8 on its device -> out [n, H, W, px_bytes] uint8 (or the caller's contiguous cuda tensor of that
     many bytes, any dtype and shape).  aligned: as for ``gather_frames``; 1 and 2 also state that W is a multiple of 16 (px 3) or
     8 (px 2)."""
-    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_cuda or not arena.is_contiguous():
-        raise ValueError(f"gather_frames_mirror: arena must be a contiguous 1-D uint8 cuda tensor, got {arena.dtype} {tuple(arena.shape)}")
-    if src_off.dtype != torch.int64 or src_off.dim() != 1 or src_off.device != arena.device or not src_off.is_contiguous():
-        raise ValueError("gather_frames_mirror: src_off must be a contiguous 1-D int64 tensor on the arena's device")
+    _store_arena("gather_frames_mirror", arena, src_off)
     n, H, W, px = int(src_off.numel()), int(H), int(W), int(px_bytes)
     if flip.dtype != torch.uint8 or flip.dim() != 1 or flip.device != arena.device or not flip.is_contiguous() or flip.numel() != n:
         raise ValueError(f"gather_frames_mirror: flip must be a contiguous 1-D uint8 tensor of {n} flags on the arena's device")
@@ -2266,8 +2272,7 @@ def gather_clouds(arena, items, P, rgb_fmt, mirror=None, out=None, aligned=0):
     the arena holds uint8 colours, 1 f32.  mirror: (axis, c2) for the items whose flags carry bit 0 (c2 is taken as float32), None
     when no item does.  aligned: 0 general; 1 the outputs are 16-byte aligned and P % 4 == 0 (checked); 2 the same with
     non-temporal loads."""
-    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_cuda or not arena.is_contiguous():
-        raise ValueError(f"gather_clouds: arena must be a contiguous 1-D uint8 cuda tensor, got {arena.dtype} {tuple(arena.shape)}")
+    _store_arena("gather_clouds", arena)
     nb = items.numel() * items.element_size()
     if items.dtype not in (torch.uint8, torch.int64) or items.device != arena.device or not items.is_contiguous() or nb % 32:
         raise ValueError("gather_clouds: items must be a contiguous uint8 or int64 tensor of whole 32-byte records on the arena's device")
@@ -2569,17 +2574,6 @@ def _knn_neighbours(idx, dist, n):
     return idx.contiguous(), dist.contiguous(), n.contiguous()
 
 
-def _knn_stats(mean, std, A, dev):
-    if (mean is None) != (std is None):
-        raise ValueError("knn: mean and std come together")
-    if mean is None:
-        return None, None
-    mean, std = (torch.as_tensor(v).to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for v in (mean, std))
-    if mean.numel() != A or std.numel() != A:
-        raise ValueError(f"knn: mean / std hold {mean.numel()} / {std.numel()} values for action_dim {A}")
-    return mean, std
-
-
 def _knn_rows(actions, off, left, dev):
     if actions.dtype != torch.float32 or actions.dim() != 2 or actions.device != dev or not actions.is_contiguous():
         raise ValueError("knn: actions must be a contiguous float32 [R, A] tensor on the neighbours' device")
@@ -2604,7 +2598,7 @@ def knn_predict(idx, dist, n, k, actions, off, left, Q, mean=None, std=None, emp
     R, A, Q = int(actions.shape[0]), int(actions.shape[1]), int(Q)
     if Nq < 1 or R < 1 or Q < 1 or off.numel() < 1:
         raise ValueError("knn_predict: empty operand")
-    mean, std = _knn_stats(mean, std, A, dev)
+    mean, std = _stats_f64("knn", mean, std, A, dev, optional=True)
     if empty is None:
         empty = torch.zeros(1, dtype=torch.int32, device=dev)
     chunk = torch.empty((Nq, Q, A), dtype=torch.float32, device=dev)
@@ -2626,7 +2620,7 @@ def knn_ksweep(idx, dist, n, actions, off, target, mean=None, std=None, want_par
     if target.dtype != torch.float32 or target.device != dev or tuple(target.shape) != (Nq, A):
         raise ValueError(f"knn_ksweep: target must be a float32 [{Nq}, {A}] tensor on {dev}")
     target = target.contiguous()
-    mean, std = _knn_stats(mean, std, A, dev)
+    mean, std = _stats_f64("knn", mean, std, A, dev, optional=True)
     partial = torch.empty((Nq, K), dtype=torch.float64, device=dev)
     sse = torch.empty(K, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):

@@ -4,6 +4,7 @@
 // give the same bits.
 #pragma once
 #include "common.h"
+#include "error_core.h"
 
 // LDS of one step: s_w = Q doubles (normalised weight of row j, 0 when the row is not populated) + fixed scratch
 struct EnsembleLds {
@@ -63,7 +64,7 @@ __device__ __forceinline__ int ensemble_step_rows(RowFn row, LiveFn live, int t,
     __syncthreads();
     const double wsum = (s.ws[0] + s.ws[1]) + (s.ws[2] + s.ws[3]);
     // threads (a, g): action component a, row class g (rows j = g mod ng); A <= 64
-    const int per = A <= 16 ? 16 : (A <= 32 ? 32 : 64);
+    const int per = error_per(A);
     const int a = tid % per, g = tid / per, ng = 256 / per;
     double acc = 0.0;
     if (a < A) {

@@ -2,6 +2,7 @@
 // the error of the executed actions against the recording, reduced on the device.
 #include "common.h"
 #include "ensemble_core.h"
+#include "error_core.h"
 
 namespace {
 
@@ -17,8 +18,7 @@ __global__ __launch_bounds__(256) void ensemble_episode_kernel(const float* __re
     __shared__ double s_acc[256];
     const EnsembleLds lds{reinterpret_cast<double*>(s_raw), s_cnt, s_ws, s_acc};
     const int t = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
-    int Te = lengths ? lengths[e] : T;
-    Te = Te < 0 ? 0 : (Te > T ? T : Te);
+    const int Te = clamp_length(lengths ? lengths[e] : T, T);
     double* o = out + ((int64_t)e * T + t) * A;
     uint8_t* p = populated ? populated + ((int64_t)e * T + t) * Q : nullptr;
     if (t >= Te) {                                         // uniform over the workgroup
@@ -34,122 +34,74 @@ __global__ __launch_bounds__(256) void ensemble_episode_kernel(const float* __re
     ensemble_step_rows(row, EnsembleAllLive{}, t, k, Q, A, lds, o, p);
 }
 
-// pred = raw * std + mean (two roundings, as numpy) and, per (episode, action component) over t < lengths[e], the sums of
-// |d| and d^2 and the maximum of |d| with d = pred - (double)target.  One workgroup per (block of `per` components, episode):
-// thread (a, g) walks t = g, g + ng, ... in order, the ng partial results are combined in index order -- a fixed shape, so two
-// runs give the same bits.
-__global__ __launch_bounds__(256) void action_error_kernel(const double* __restrict__ raw, const float* __restrict__ target,
-                                                           const int32_t* __restrict__ lengths, const double* __restrict__ mean,
-                                                           const double* __restrict__ stdv, double* __restrict__ pred,
-                                                           double* __restrict__ stats, int T, int A, int per) {
-    __shared__ double s_part[3][256];
-    const int e = blockIdx.y, tid = threadIdx.x;
-    const int al = tid % per, g = tid / per, ng = 256 / per;
-    const int a = blockIdx.x * per + al;
-    int Te = lengths ? lengths[e] : T;
-    Te = Te < 0 ? 0 : (Te > T ? T : Te);
-    double s1 = 0.0, s2 = 0.0, mx = 0.0;
-    if (a < A) {
-        const double sd = stdv[a], mu = mean[a];
-        for (int t = g; t < T; t += ng) {
-            const int64_t i = ((int64_t)e * T + t) * A + a;
-            double p;
-            {
-#pragma clang fp contract(off)                             // product and sum rounded separately: a fused multiply-add differs
-                const double prod = raw[i] * sd;           // from numpy by many ulps where raw * std nearly cancels the mean
-                p = prod + mu;
-            }
+// pred = raw * std + mean (two roundings, as numpy) and, per (trajectory, action component) over t < Te, the sums of |d| and d^2
+// and the maximum of |d| with d = pred - (double)target: the walk of error_core.h.  One workgroup per (block of `per` components,
+// trajectory e): thread (a, g) walks t = g, g + ng, ... in order.  action_error: Te = lengths[e] (len without lengths), the target
+// of trajectory e lies target_stride = T * A floats on, stats [E][3][A].  sweep_error (Rough): G trajectories against ONE target
+// (stride 0) of length len, stats [G][4][A] -- rows 0-2 are the instructions of action_error on raw[g]; row 3: the sum over
+// 1 <= t < Te of |pred[t] - pred[t-1]| (pred[t-1] is computed again with the same two roundings), walked and combined alike.
+template <bool Rough>
+__global__ __launch_bounds__(256) void walk_error_kernel(const double* __restrict__ raw, const float* __restrict__ target,
+                                                         const int32_t* __restrict__ lengths, int len, int64_t target_stride,
+                                                         const double* __restrict__ mean, const double* __restrict__ stdv,
+                                                         double* __restrict__ pred, double* __restrict__ stats, int T, int A, int per) {
+    constexpr int R = Rough ? 4 : 3;
+    const int e = blockIdx.y;
+    const ErrorThread th(per);
+    const int Te = clamp_length(lengths ? lengths[e] : len, T);
+    const float* tg = target + e * target_stride;
+    ErrorAcc acc;
+    if (th.a < A) {
+        const double sd = stdv[th.a], mu = mean[th.a];
+        for (int t = th.g; t < T; t += th.ng) {
+            const int64_t i = ((int64_t)e * T + t) * A + th.a;
+            const double p = unnormalise(raw[i], sd, mu);
             if (pred) pred[i] = p;
             if (t < Te) {
-                const double d = fabs(p - (double)target[i]);
-                s1 += d;
-                s2 += d * d;
-                mx = fmax(mx, d);
+                acc.add(p, (double)tg[(int64_t)t * A + th.a]);
+                if (Rough && t >= 1) acc.rough += fabs(p - unnormalise(raw[i - A], sd, mu));
             }
         }
     }
-    s_part[0][tid] = s1;
-    s_part[1][tid] = s2;
-    s_part[2][tid] = mx;
-    __syncthreads();
-    if (tid < per && a < A) {
-        double t1 = 0.0, t2 = 0.0, tm = 0.0;
-        for (int gg = 0; gg < ng; ++gg) {
-            t1 += s_part[0][gg * per + tid];
-            t2 += s_part[1][gg * per + tid];
-            tm = fmax(tm, s_part[2][gg * per + tid]);
-        }
-        double* st = stats + (int64_t)e * 3 * A;
-        st[a] = t1;
-        st[A + a] = t2;
-        st[2 * A + a] = tm;
-    }
+    error_combine_store<R>(acc, th, per, A, stats + (int64_t)e * R * A);
 }
 
 // The error along the predicted chunk: chunks [E][S][Q][A], row s of episode e is the chunk predicted from frame r = s * stride, and
 // its slot j is compared with actions[e][max(0, r - shift[e]) + j] -- the entry gather_chunks_kernel trains that slot on -- while
-// r < len and max(0, r - shift) + j < len (the entries whose is_pad is 0).  d = |chunk * std + mean - action| in float64, product
-// and sum rounded separately as in action_error_kernel.  One workgroup per (block of `per` components, slot, episode): thread (a, g)
-// walks s = g, g + ng, ... in order, the ng partial results are combined in index order -- a fixed shape, so two runs give the
-// same bits.  Every index is held to its array.
+// r < len and max(0, r - shift) + j < len (the entries whose is_pad is 0).  d = |chunk * std + mean - action| in float64, with the
+// un-normalisation, sums, combine and store of error_core.h.  One workgroup per (block of `per` components, slot, episode): thread
+// (a, g) walks s = g, g + ng, ... in order.  Every index is held to its array.
 __global__ __launch_bounds__(256) void chunk_error_kernel(const float* __restrict__ chunks, const float* __restrict__ actions,
                                                           const int32_t* __restrict__ lengths, const int32_t* __restrict__ shift,
                                                           const double* __restrict__ mean, const double* __restrict__ stdv,
                                                           int stride, double* __restrict__ stats, int32_t* __restrict__ count,
                                                           int S, int T, int Q, int A, int per) {
-    __shared__ double s_part[3][256];
     __shared__ int s_n[256];
     const int e = blockIdx.z, j = blockIdx.y, tid = threadIdx.x;
-    const int al = tid % per, g = tid / per, ng = 256 / per;
-    const int a = blockIdx.x * per + al;
-    int Te = lengths ? lengths[e] : T;
-    Te = Te < 0 ? 0 : (Te > T ? T : Te);
+    const ErrorThread th(per);
+    const int Te = clamp_length(lengths ? lengths[e] : T, T);
     const int sh = shift ? (shift[e] > 0 ? 1 : 0) : 0;
-    const bool live = a < A;
-    const double sd = live ? stdv[a] : 0.0, mu = live ? mean[a] : 0.0;
+    const bool live = th.a < A;
+    const double sd = live ? stdv[th.a] : 0.0, mu = live ? mean[th.a] : 0.0;
     const float* ce = chunks + (int64_t)e * S * Q * A;
     const float* ae = actions + (int64_t)e * T * A;
-    double s1 = 0.0, s2 = 0.0, mx = 0.0;
+    ErrorAcc acc;
     int n = 0;
-    for (int s = g; s < S; s += ng) {
+    for (int s = th.g; s < S; s += th.ng) {
         const int64_t r = (int64_t)s * stride;
         const int64_t i = (r > sh ? r - sh : 0) + j;               // grows with s: once it leaves the episode, so do the later rows
         if (r >= Te || i >= Te) break;
         ++n;
         if (live) {
             const int64_t ii = i < T ? i : T - 1;                  // i < Te <= T already
-            double p;
-            {
-#pragma clang fp contract(off)
-                const double prod = (double)ce[((int64_t)s * Q + j) * A + a] * sd;
-                p = prod + mu;
-            }
-            const double d = fabs(p - (double)ae[ii * A + a]);
-            s1 += d;
-            s2 += d * d;
-            mx = fmax(mx, d);
+            acc.add(unnormalise((double)ce[((int64_t)s * Q + j) * A + th.a], sd, mu), (double)ae[ii * A + th.a]);
         }
     }
-    s_part[0][tid] = s1;
-    s_part[1][tid] = s2;
-    s_part[2][tid] = mx;
     s_n[tid] = n;
-    __syncthreads();
-    if (tid < per && live) {
-        double t1 = 0.0, t2 = 0.0, tm = 0.0;
-        for (int gg = 0; gg < ng; ++gg) {
-            t1 += s_part[0][gg * per + tid];
-            t2 += s_part[1][gg * per + tid];
-            tm = fmax(tm, s_part[2][gg * per + tid]);
-        }
-        double* st = stats + ((int64_t)e * Q + j) * 3 * A;
-        st[a] = t1;
-        st[A + a] = t2;
-        st[2 * A + a] = tm;
-    }
+    error_combine_store<3>(acc, th, per, A, stats + ((int64_t)e * Q + j) * 3 * A);
     if (tid == 0 && blockIdx.x == 0) {
         int tn = 0;
-        for (int gg = 0; gg < ng; ++gg) tn += s_n[gg * per];
+        for (int gg = 0; gg < th.ng; ++gg) tn += s_n[gg * per];
         count[(int64_t)e * Q + j] = tn;
     }
 }
@@ -195,63 +147,6 @@ __global__ __launch_bounds__(256) void ensemble_sweep_kernel(const float* __rest
     if (empty && tid == 0 && n == 0) atomicAdd(empty + g, 1);
 }
 
-// action_error_kernel for G trajectories against ONE target [T][A]: thread shape, walk and unfused arithmetic are that kernel's,
-// so rows 0-2 of stats [G][4][A] are its bits on raw[g].  Row 3: sum over 1 <= t < Te of |pred[t] - pred[t-1]| (pred[t-1] is
-// computed again with the same two roundings), walked and combined in the same fixed order.
-__global__ __launch_bounds__(256) void sweep_error_kernel(const double* __restrict__ raw, const float* __restrict__ target, int Te,
-                                                          const double* __restrict__ mean, const double* __restrict__ stdv,
-                                                          double* __restrict__ pred, double* __restrict__ stats, int T, int A,
-                                                          int per) {
-    __shared__ double s_part[4][256];
-    const int e = blockIdx.y, tid = threadIdx.x;
-    const int al = tid % per, g = tid / per, ng = 256 / per;
-    const int a = blockIdx.x * per + al;
-    double s1 = 0.0, s2 = 0.0, mx = 0.0, s3 = 0.0;
-    if (a < A) {
-        const double sd = stdv[a], mu = mean[a];
-        for (int t = g; t < T; t += ng) {
-            const int64_t i = ((int64_t)e * T + t) * A + a;
-            double p, q = 0.0;
-            {
-#pragma clang fp contract(off)                             // as action_error_kernel: product and sum rounded separately
-                const double prod = raw[i] * sd;
-                p = prod + mu;
-                if (t >= 1) {
-                    const double prev = raw[i - A] * sd;
-                    q = prev + mu;
-                }
-            }
-            if (pred) pred[i] = p;
-            if (t < Te) {
-                const double d = fabs(p - (double)target[(int64_t)t * A + a]);
-                s1 += d;
-                s2 += d * d;
-                mx = fmax(mx, d);
-                if (t >= 1) s3 += fabs(p - q);
-            }
-        }
-    }
-    s_part[0][tid] = s1;
-    s_part[1][tid] = s2;
-    s_part[2][tid] = mx;
-    s_part[3][tid] = s3;
-    __syncthreads();
-    if (tid < per && a < A) {
-        double t1 = 0.0, t2 = 0.0, tm = 0.0, t3 = 0.0;
-        for (int gg = 0; gg < ng; ++gg) {
-            t1 += s_part[0][gg * per + tid];
-            t2 += s_part[1][gg * per + tid];
-            tm = fmax(tm, s_part[2][gg * per + tid]);
-            t3 += s_part[3][gg * per + tid];
-        }
-        double* st = stats + (int64_t)e * 4 * A;
-        st[a] = t1;
-        st[A + a] = t2;
-        st[2 * A + a] = tm;
-        st[3 * A + a] = t3;
-    }
-}
-
 }  // namespace
 
 int launch_ensemble_sweep(const float* chunks, int len, const actmi_schedule* schedules, double* raw, int32_t* empty, int G, int T,
@@ -259,19 +154,17 @@ int launch_ensemble_sweep(const float* chunks, int len, const actmi_schedule* sc
     if (A < 1 || A > 64 || Q < 1 || Q > kEnsembleMaxQ || G < 1 || G > 65535 || T < 0) return -2;
     if (empty && hipMemsetAsync(empty, 0, (size_t)G * sizeof(int32_t), st) != hipSuccess) return -3;
     if (T == 0) return 0;
-    const int Te = len < 0 ? 0 : (len > T ? T : len);
-    hipLaunchKernelGGL(ensemble_sweep_kernel, dim3(T, G), dim3(256), ensemble_lds_bytes(Q), st, chunks, Te, schedules, raw, empty, T,
-                       Q, A);
+    hipLaunchKernelGGL(ensemble_sweep_kernel, dim3(T, G), dim3(256), ensemble_lds_bytes(Q), st, chunks, clamp_length(len, T), schedules,
+                       raw, empty, T, Q, A);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 int launch_sweep_error(const double* raw, const float* target, int len, const double* mean, const double* stdv, double* stats,
                        double* pred, int G, int T, int A, hipStream_t st) {
     if (G < 1 || G > 65535 || T < 0 || A < 1) return -2;
-    const int Te = len < 0 ? 0 : (len > T ? T : len);
-    const int per = A <= 16 ? 16 : (A <= 32 ? 32 : 64);
-    hipLaunchKernelGGL(sweep_error_kernel, dim3((A + per - 1) / per, G), dim3(256), 0, st, raw, target, Te, mean, stdv, pred, stats,
-                       T, A, per);
+    const int per = error_per(A);
+    hipLaunchKernelGGL(walk_error_kernel<true>, dim3((A + per - 1) / per, G), dim3(256), 0, st, raw, target, nullptr, len, (int64_t)0,
+                       mean, stdv, pred, stats, T, A, per);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -288,9 +181,9 @@ int launch_action_error(const double* raw, const float* target, const int32_t* l
                         double* pred, double* stats, int E, int T, int A, hipStream_t st) {
     if (E <= 0 || A <= 0) return 0;
     if (E > 65535 || T < 0) return -2;
-    const int per = A <= 16 ? 16 : (A <= 32 ? 32 : 64);
-    hipLaunchKernelGGL(action_error_kernel, dim3((A + per - 1) / per, E), dim3(256), 0, st, raw, target, lengths, mean, stdv, pred,
-                       stats, T, A, per);
+    const int per = error_per(A);
+    hipLaunchKernelGGL(walk_error_kernel<false>, dim3((A + per - 1) / per, E), dim3(256), 0, st, raw, target, lengths, T,
+                       (int64_t)T * A, mean, stdv, pred, stats, T, A, per);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -300,7 +193,7 @@ int launch_chunk_error(const float* chunks, const float* actions, const int32_t*
     if (E < 0 || S < 0 || E > 65535 || Q < 1 || Q > 65535 || A < 1 || stride < 1 || T < 1) return -2;
     if (!chunks || !actions || !mean || !stdv || !stats || !count) return -2;
     if (E == 0 || S == 0) return 0;
-    const int per = A <= 16 ? 16 : (A <= 32 ? 32 : 64);
+    const int per = error_per(A);
     hipLaunchKernelGGL(chunk_error_kernel, dim3((A + per - 1) / per, Q, E), dim3(256), 0, st, chunks, actions, lengths, shift, mean,
                        stdv, stride, stats, count, S, T, Q, A, per);
     return hipGetLastError() == hipSuccess ? 0 : -3;

@@ -9,7 +9,8 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
   takes a contiguous slice, a single all-gather of (episode_return, highest_reward) ends the run;
 * the 10 warm-up queries per rollout and the real-time sleep (:377-382, :467-470) are off by default;
 * ``replay_bc`` (``--eval --replay``) evaluates open loop on recorded episodes instead -- the one evaluation of use_depth /
-  use_pcd policies and of policies trained on real-robot episodes: queries batched over TIME, one ensemble launch per episode;
+  use_pcd policies and of policies trained on real-robot episodes: queries batched over TIME, one ensemble launch per episode
+  (``replay_bc`` drives it; its analyses, their pooling, report and logged figures live in ``actmi.replay``);
 * ``--device_dataset --replay_every N`` runs that replay on held-out episodes every N training steps, out of the device-resident
   store the batches come from (no file read); ``--replay_horizon`` adds the error along the predicted chunk;
 * ``--replay_sweep`` reads a grid of execution schedules (query rate, executed horizon, ensemble weight, or the latest chunk
@@ -27,6 +28,7 @@ forward_pass :529, train_bc :535, repeater :624, CLI :633-666), re-designed for 
   device (actmi.ops.ImageAugment / CloudAugment), each from draws of its own.
 """
 import argparse
+import json
 import os
 import pickle
 import sys
@@ -45,6 +47,8 @@ if _HERE not in sys.path:
 from actmi.constants import FPS, SIM_TASK_CONFIGS  # noqa: E402
 from actmi.sim_utils import compute_dict_mean, draw_episode_poses, set_seed, shard_range  # noqa: E402
 from actmi import dist_utils  # noqa: E402
+from actmi import ops, replay  # noqa: E402
+from actmi.replay import horizon_metrics, horizon_slots, replay_metrics, replay_sweep_schedules, sweep_metrics  # noqa: E402,F401
 
 
 def make_policy(policy_class, policy_config, device=None):
@@ -389,90 +393,6 @@ def _replay_query(policy, data, use_depth, use_pcd, vq_sampler):
     return policy(qpos, image, **kw)
 
 
-def replay_metrics(rows, action_dim):
-    """rows [n, 1 + 3A] float64 = (T, sum |d| [A], sum d^2 [A], max |d| [A]) per episode -> the per-episode and the pooled
-    figures.  Pooled: the sums are added and divided by the total step count (never an average of averages)."""
-    A = action_dim
-    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 1 + 3 * A)
-
-    def figures(T, s1, s2, mx):
-        T = max(float(T), 1.0)
-        mae, rmse = s1 / T, np.sqrt(s2 / T)
-        return {"mae": mae.tolist(), "rmse": rmse.tolist(), "max": mx.tolist(), "mae_mean": float(mae.mean()),
-                "rmse_mean": float(rmse.mean()), "max_max": float(mx.max()) if len(mx) else 0.0}
-
-    episodes = [dict(figures(r[0], r[1:1 + A], r[1 + A:1 + 2 * A], r[1 + 2 * A:]), T=int(r[0])) for r in rows]
-    total = rows[:, 0].sum() if len(rows) else 0.0
-    s1 = rows[:, 1:1 + A].sum(axis=0) if len(rows) else np.zeros(A)
-    s2 = rows[:, 1 + A:1 + 2 * A].sum(axis=0) if len(rows) else np.zeros(A)
-    mx = rows[:, 1 + 2 * A:].max(axis=0) if len(rows) else np.zeros(A)
-    return dict(figures(total, s1, s2, mx), episodes=episodes, steps=int(total))
-
-
-def horizon_slots(Q):
-    """the five slots of a chunk the horizon figures are printed and logged for"""
-    return [0, Q // 4, Q // 2, 3 * Q // 4, Q - 1]
-
-
-def horizon_metrics(rows, num_queries, action_dim):
-    """rows [n, Q * (1 + 3A)] float64 = per episode (pairs [Q], then per slot sum |d| [A], sum d^2 [A], max |d| [A]) -> the pooled
-    error of slot j of a predicted chunk against the action j steps ahead.  Sums and counts are added over the episodes and then
-    divided (never an average of averages); a slot without a pair gives zeros."""
-    Q, A = num_queries, action_dim
-    rows = np.asarray(rows, dtype=np.float64).reshape(-1, Q * (1 + 3 * A))
-    count = rows[:, :Q].sum(axis=0)
-    st = rows[:, Q:].reshape(-1, Q, 3, A)
-    s1, s2 = st[:, :, 0].sum(axis=0), st[:, :, 1].sum(axis=0)
-    mx = st[:, :, 2].max(axis=0) if len(rows) else np.zeros((Q, A))
-    n = np.maximum(count, 1.0)[:, None]
-    mae, rmse = s1 / n, np.sqrt(s2 / n)
-    return {"mae": mae.tolist(), "rmse": rmse.tolist(), "max": mx.tolist(), "mae_mean": mae.mean(axis=1).tolist(),
-            "count": [int(c) for c in count]}
-
-
-def replay_sweep_schedules(num_queries, k=None, every=None, horizon=None):
-    """the grid of ``--replay_sweep`` for chunks of Q slots (ops.make_schedules).  The defaults -- k in {-0.1, 0, 0.01, 0.05, 0.25},
-    every in {1, Q/4, Q/2, Q}, horizon in {Q, Q/2}, plus the latest-chunk schedules -- are choices that bracket the reference's
-    two schedules, not measurements"""
-    from actmi.ops import make_schedules
-    Q = int(num_queries)
-    return make_schedules(Q, every=every if every else (1, max(1, Q // 4), max(1, Q // 2), Q),
-                          horizon=horizon if horizon else (Q, max(1, Q // 2)),
-                          k=k if k else (-0.1, 0.0, 0.01, 0.05, 0.25), latest=True)
-
-
-def sweep_metrics(rows, schedules, num_queries, action_dim):
-    """rows [n, 1 + G + 4GA] float64 = per episode (T, the empty steps [G], then per schedule sum |d| [A], sum d^2 [A], max |d| [A],
-    sum |pred[t] - pred[t-1]| [A]) -> the pooled figures of every schedule, in action units.  Sums and counts are added over the
-    episodes and then divided (never an average of averages): the errors by the steps, the roughness by the T - 1 differences of
-    every episode.  ``best``: the lowest mae_mean (the lowest index among equals); ``default``: the index of the schedule the
-    un-swept replay runs, (1, Q, ensemble, 0.01), or None when the grid does not hold it."""
-    from actmi.ops import schedules_as_dicts
-    G, A = len(schedules), action_dim
-    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 1 + G + 4 * G * A)
-    steps = max(float(rows[:, 0].sum()), 1.0)
-    diffs = max(float(np.maximum(rows[:, 0] - 1.0, 0.0).sum()), 1.0)
-    empty = rows[:, 1:1 + G].sum(axis=0)
-    st = rows[:, 1 + G:].reshape(-1, G, 4, A)
-    s1, s2, s3 = st[:, :, 0].sum(axis=0), st[:, :, 1].sum(axis=0), st[:, :, 3].sum(axis=0)
-    mx = st[:, :, 2].max(axis=0) if len(rows) else np.zeros((G, A))
-    mae_mean = (s1 / steps).mean(axis=1)
-    names = schedules_as_dicts(schedules)
-    default = [g for g, d in enumerate(names) if (d["every"], d["horizon"], d["mode"], d["k"]) == (1, num_queries, "ensemble", 0.01)]
-    return {"schedules": names, "mae_mean": mae_mean.tolist(), "rmse_mean": np.sqrt(s2 / steps).mean(axis=1).tolist(),
-            "max_max": mx.max(axis=1).tolist(), "rough_mean": (s3 / diffs).mean(axis=1).tolist(),
-            "empty": [int(v) for v in empty], "best": int(np.argmin(mae_mean)), "default": default[0] if default else None}
-
-
-def _gather_rows_f64(local, counts):
-    """dist_utils.all_gather_rows moves float32 rows; float64 rows travel as their bit pattern (two float32 words per value: the
-    collective only copies), so the pooled sums are the same bits with one rank or many"""
-    local = local.to(torch.float64).contiguous().cpu()
-    k = local.shape[1]
-    out = dist_utils.all_gather_rows(local.view(torch.float32), counts)
-    return out.contiguous().view(torch.float64).reshape(-1, k)
-
-
 def check_replay_knn(knn, store, policy_class, policy_config, episodes=None):
     """The refusals of ``replay_bc(knn=...)`` / ``--replay_knn``, raised before anything is launched: no store, K outside
     [1, 512] or above the support rows, a non-finite or negative state weight, use_pcd and Diffusion policies.  ``knn``: an int K
@@ -486,10 +406,7 @@ def check_replay_knn(knn, store, policy_class, policy_config, episodes=None):
         raise ValueError("--replay_knn looks demonstrations up in the device-resident store: it needs --device_dataset (store=...)")
     if "k" not in knn:
         raise ValueError("replay_bc(knn=...): no k")
-    if episodes is None or isinstance(episodes, (int, np.integer)):
-        replayed = list(store.episode_ids)[:None if episodes is None else int(episodes)]
-    else:
-        replayed = [int(i) for i in episodes]
+    replayed = replay.resolve_store_episodes(store, episodes)
     if knn.get("support_ids") is None:
         rest = [i for i in store.episode_ids if i not in set(replayed)]
         knn["support_ids"] = rest or list(store.episode_ids)
@@ -507,14 +424,14 @@ def check_replay_knn(knn, store, policy_class, policy_config, episodes=None):
     return knn
 
 
-def _replay_knn(config, ckpt_name, knn, policy, stats, store, ids, batch, episode_ensemble, action_error, align, engine):
+def _replay_knn(config, ckpt_name, knn, policy, stats, store, ids, batch, episode_ensemble, action_error, align):
     """the second replay of ``replay_bc(knn=...)``: the same episodes through the nearest-neighbour policy -> result["knn"]"""
     vp = knn.get("policy")
     sel = None
     if vp is None:
         from actmi import vinn
         support = knn.get("support") or vinn.SupportSet.from_store(store, policy, knn["support_ids"], batch, align)
-        vp = vinn.VINNPolicy(support, knn["k"], knn["state_weight"], engine, exclude_self=knn["exclude_self"], stats=stats)
+        vp = vinn.VINNPolicy(support, knn["k"], knn["state_weight"], getattr(policy, "model", None), exclude_self=knn["exclude_self"], stats=stats)
         if knn.get("select_k") is not None:
             sel = vinn.select_k(support, store, ids, knn["select_k"], policy, knn["state_weight"], batch)
     sub = replay_bc(config, ckpt_name, episodes=ids, policy=vp, stats=stats, batch=batch, episode_ensemble=episode_ensemble,
@@ -586,11 +503,8 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
     figure is the same bits with or without it.
     Returns {"episodes": [...], "mae": [A], "rmse": [A], "max": [A], "mae_mean", "rmse_mean", "max_max", "steps", ...} in
     action units; with ``save_episode`` rank 0 writes replay_<ckpt>.json and per episode replay_<ckpt>_ep<i>.npz (pred, target)."""
-    import json
     from actmi.data import DeviceEpisodeReplay, DevicePrefetcher, EpisodeReplay, find_all_hdf5
-    ckpt_dir = config["ckpt_dir"]
-    policy_class = config["policy_class"]
-    policy_config = config["policy_config"]
+    ckpt_dir, policy_class, policy_config = config["ckpt_dir"], config["policy_class"], config["policy_config"]
     if knn is not None:
         knn = check_replay_knn(knn, store, policy_class, policy_config, episodes)
     if policy_class == "Diffusion":
@@ -598,69 +512,42 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
                                   "part of the replay")
     if align not in ("train", "none"):
         raise ValueError(f"align must be 'train' or 'none', got {align!r}")
-    camera_names = config["camera_names"]
-    temporal_agg = config["temporal_agg"]
+    camera_names, temporal_agg = config["camera_names"], config["temporal_agg"]
     rank, world, local_rank = dist_utils.init_from_env()
     on_gpu = torch.cuda.is_available()
     dev = torch.device("cuda", local_rank if world > 1 else torch.cuda.current_device()) if on_gpu else torch.device("cpu")
     if stats is None and store is not None:
         stats = getattr(store, "norm_stats", None)                   # the statistics the store z-scores its qpos rows with
     policy, stats = _load_policy_and_stats(config, ckpt_name, policy, stats, dev, verbose)
-    use_vq = bool(policy_config.get("vq", False))
-    if use_vq and vq_sampler is None:
-        vq_sampler = _make_vq_sampler(policy_config, ckpt_dir, dev, rank, verbose)
-    if not use_vq:
+    if not policy_config.get("vq", False):
         vq_sampler = None
+    elif vq_sampler is None:
+        vq_sampler = _make_vq_sampler(policy_config, ckpt_dir, dev, rank, verbose)
     use_depth = bool(policy_config.get("use_depth") or getattr(policy, "use_depth", False))
     use_pcd = bool(policy_config.get("use_pcd") or getattr(policy, "use_pcd", False))
     Q = int(policy_config["num_queries"])
     A = int(policy_config.get("action_dim", 16))
     engine = getattr(policy, "model", None)
-    if batch is None:
-        batch = getattr(engine, "max_batch", None) or 8
-    if episode_ensemble is None or action_error is None:
-        from actmi import ops
-        episode_ensemble = episode_ensemble or ops.episode_ensemble
-        action_error = action_error or ops.action_error
-    if horizon and chunk_error is None:
-        from actmi import ops
-        chunk_error = ops.chunk_error
-    sched = None
+    batch = batch or getattr(engine, "max_batch", None) or 8
+    episode_ensemble, action_error = episode_ensemble or ops.episode_ensemble, action_error or ops.action_error
+    mean, std = (np.asarray(stats[k], dtype=np.float64).reshape(-1) for k in ("action_mean", "action_std"))
+    if mean.shape[0] != A or std.shape[0] != A:
+        raise ValueError(f"the dataset statistics hold {mean.shape[0]} action components, the policy's action_dim is {A}")
+    stride = 1 if temporal_agg else Q
+    # the optional analyses, in the order their rows are gathered over the ranks (every rank issues the same collectives)
+    parts = []
+    if horizon:
+        parts.append(replay.horizon_part(chunk_error, mean, std, stride, Q, A))
     if sweep is not None:
-        from actmi import ops
-        if not temporal_agg:
-            raise ValueError("replay_bc(sweep=...) reads the schedules off the table of a chunk for EVERY frame: it needs temporal_agg "
-                             "(--temporal_agg)")
-        sweep = ops.check_schedules(sweep, Q)
-        if ensemble_sweep is None:
-            sched = ops.device_schedules(sweep, Q, dev)              # checked and uploaded once for all episodes
-        ensemble_sweep = ensemble_sweep or ops.ensemble_sweep
-        sweep_error = sweep_error or ops.sweep_error
-    attn = None
+        parts.append(replay.sweep_part(sweep, ensemble_sweep, sweep_error, temporal_agg, mean, std, Q, A, dev))
     if attention_frames and not attention:
         raise ValueError("replay_bc: attention_frames overlays the attention maps: it needs attention=True")
-    if attention:
-        from actmi import ops
-        from actmi.attention_maps import check_slots, source_names, split_attention
-        if engine is None or not hasattr(engine, "bind_attention"):
-            raise ValueError("replay_bc(attention=True) needs an ACT policy on the engine (policy.model.bind_attention)")
-        layout = engine.attention_layout()
-        attn = {"layout": layout, "slots": check_slots(layout, attention_slots), "lut": ops.heat_ramp(),
-                "sources": source_names(layout, camera_names, policy_config.get("depth_camera_names") if use_depth else None)}
     dataset_dir = config.get("dataset_dir")
     if store is not None:
         if use_pcd and not getattr(store, "has_clouds", False):
             raise NotImplementedError("replay_bc: the device-resident store holds no point clouds (use_pcd); one built with "
                                       "--device_clouds does")
-        if episodes is None or isinstance(episodes, (int, np.integer)):
-            ids = list(store.episode_ids)[:None if episodes is None else int(episodes)]
-        else:
-            ids = [int(i) for i in episodes]
-        if not ids:
-            raise ValueError("replay_bc: no episodes to replay out of the store")
-        missing = [i for i in ids if i not in store._local_of]
-        if missing:
-            raise ValueError(f"replay_bc: episodes {missing} are not in the store (it holds {list(store.episode_ids)})")
+        ids = replay.resolve_store_episodes(store, episodes)
         files = [store.paths[store._local_of[i]] for i in ids]
     else:
         if not (dataset_dir and os.path.isdir(dataset_dir)):
@@ -672,22 +559,24 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
             files = files[:int(episodes)]
         if not files:
             raise ValueError(f"replay_bc: no episode files under {dataset_dir}")
-    n = len(files)
-    lo, hi = shard_range(n, rank, world)
-    spans = [shard_range(n, r, world) for r in range(world)]
-    mean = np.asarray(stats["action_mean"], dtype=np.float64).reshape(-1)
-    std = np.asarray(stats["action_std"], dtype=np.float64).reshape(-1)
-    if mean.shape[0] != A or std.shape[0] != A:
-        raise ValueError(f"the dataset statistics hold {mean.shape[0]} action components, the policy's action_dim is {A}")
-
-    local_rows, local_pt, local_hz, local_share, local_sw = [], [], [], [], []
-    time0, n_frames = time.time(), 0
-    stride = 1 if temporal_agg else Q
+    spans = [shard_range(len(files), r, world) for r in range(world)]
+    lo, hi = spans[rank]
     stem = "replay_" + ckpt_name.split(".")[0] if save_episode else None          # (a periodic replay saves nothing and has no name)
-    if attn is not None:
-        attn_before = engine.attention_out
-        attn_buf = torch.empty((batch, layout.Q, layout.N), dtype=torch.float32, device=dev)
-        engine.bind_attention(attn_buf)
+    local_pt, time0, n_frames = [], time.time(), 0
+
+    def base_episode(i, ep, table, raw, target, actions, shift):
+        pred, st = action_error(raw, target, None, mean, std)
+        if save_episode:
+            local_pt.append(torch.cat([torch.as_tensor(pred).to(torch.float64).cpu().reshape(ep.T, A),
+                                       target[0].to(torch.float64).cpu()], dim=1))
+        return replay.row(1 + 3 * A, float(ep.T), st)
+    about = dict(align=align, temporal_agg=bool(temporal_agg), num_queries=Q,
+                 files=[os.path.relpath(f, dataset_dir) if dataset_dir else f for f in files])
+    parts.insert(0, replay.Part(1 + 3 * A, base_episode, lambda rows: dict(replay_metrics(rows, A), **about)))
+    if attention:                                                # (last: it binds its buffer to the engine until end())
+        parts.append(replay.attention_part(engine, attention_slots, attention_frames, camera_names,
+                                           policy_config.get("depth_camera_names") if use_depth else None, batch, dev, ckpt_dir, stem))
+    rows = [[] for _ in parts]
     for i in range(lo, hi):
         if store is not None:
             ep = DeviceEpisodeReplay(store, ids[i], batch, stride=stride)
@@ -702,133 +591,49 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
             actions = torch.from_numpy(ep.actions)
         if actions.shape[1] != A:
             raise ValueError(f"{files[i]}: the recorded actions are {actions.shape[1]} wide, the policy's action_dim is {A}")
-        T = ep.T
         # the chunk of replayed step s: row s of the table (temporal_agg: s = t, every frame; else s = t // Q)
         table = torch.zeros((1, len(ep.steps), Q, A), dtype=torch.float32, device=dev)
         s0 = 0
-        ep_maps, ep_frames = [], []
         for data in (ep if store is not None else DevicePrefetcher(ep, device=dev if on_gpu else None)):
             a_hat = _replay_query(policy, data, use_depth, use_pcd, vq_sampler)
             table[0, s0:s0 + a_hat.shape[0]] = a_hat
-            if attn is not None:
-                m = split_attention(attn_buf[:a_hat.shape[0]], layout, attn["slots"])
-                ep_maps.append({k: m[k].cpu() for k in ("rgb", "depth", "extra", "share")})
-                if attention_frames:
-                    if data[0].dtype != torch.uint8:
-                        raise NotImplementedError("replay_bc(attention_frames=True) overlays the raw uint8 frames of a batch")
-                    ep_frames.append(ops.heat_overlay(data[0].contiguous(), m["rgb"].contiguous(), attn["lut"], 0.5).cpu())
+            for part in parts:
+                part.batch(data, a_hat.shape[0])
             s0 += a_hat.shape[0]
         n_frames += s0
-        if attn is not None:
-            maps = {k: torch.cat([m[k] for m in ep_maps], dim=0).numpy() for k in ("rgb", "depth", "extra", "share")}
-            local_share.append(torch.cat([torch.tensor([float(s0)], dtype=torch.float64),
-                                          torch.from_numpy(maps["share"]).to(torch.float64).sum(0)])[None])
-            if save_episode:                                     # (every rank writes the episodes it replayed)
-                os.makedirs(ckpt_dir, exist_ok=True)
-                np.savez(os.path.join(ckpt_dir, f"{stem}_ep{i}_attn.npz"), steps=np.asarray(ep.steps, dtype=np.int64),
-                         sources=np.asarray(attn["sources"]), **maps)
-                if attention_frames:
-                    np.save(os.path.join(ckpt_dir, f"{stem}_ep{i}_attn_frames.npy"), torch.cat(ep_frames, dim=0).numpy())
         if temporal_agg:
             raw = torch.as_tensor(episode_ensemble(table, None, 0.01)).to(torch.float64)            # [1, T, A]
         else:
-            raw = table.reshape(1, -1, A)[:, :T].to(torch.float64)                                  # reference :392
+            raw = table.reshape(1, -1, A)[:, :ep.T].to(torch.float64)                                # reference :392
         shift = 1 if (align == "train" and not ep.is_sim) else 0                                     # utils.py:112-114
         # [1, T, A] f32, file units: row t is action[max(0, t - shift)] (taken where the rows are: on the device with a store)
-        target = (torch.cat([actions[:1], actions[:T - 1]], dim=0) if shift else actions)[None]
-        pred, st = action_error(raw, target, None, mean, std)
-        st = torch.as_tensor(st).to(torch.float64).cpu().reshape(1, 3 * A)
-        local_rows.append(torch.cat([torch.tensor([[float(T)]], dtype=torch.float64), st], dim=1))
-        if horizon:
-            hst, hcnt = chunk_error(table, actions[None], None, [shift], mean, std, stride)
-            local_hz.append(torch.cat([torch.as_tensor(hcnt).to(torch.float64).cpu().reshape(1, Q),
-                                       torch.as_tensor(hst).to(torch.float64).cpu().reshape(1, Q * 3 * A)], dim=1))
-        if sweep is not None:
-            sraw, sempty = ensemble_sweep(table[0], sweep if sched is None else sched, None, want_empty=True)
-            _, sst = sweep_error(torch.as_tensor(sraw).to(torch.float64), target[0], None, mean, std, want_pred=False)
-            local_sw.append(torch.cat([torch.tensor([[float(T)]], dtype=torch.float64),
-                                       torch.as_tensor(sempty).to(torch.float64).cpu().reshape(1, -1),
-                                       torch.as_tensor(sst).to(torch.float64).cpu().reshape(1, -1)], dim=1))
-        if save_episode:
-            local_pt.append(torch.cat([torch.as_tensor(pred).to(torch.float64).cpu().reshape(T, A),
-                                       target[0].to(torch.float64).cpu()], dim=1))
+        target = (torch.cat([actions[:1], actions[:ep.T - 1]], dim=0) if shift else actions)[None]
+        for part, mine in zip(parts, rows):
+            mine.append(part.episode(i, ep, table, raw, target, actions, shift))
         if engine is not None and hasattr(engine, "check_flags") and on_gpu:
             engine.check_flags()
-    if attn is not None:
-        engine.bind_attention(attn_before)
+    for part in parts:
+        part.end()
     if verbose and n_frames:
         print(f"rank {rank}: replayed episodes {lo}..{hi - 1}, {n_frames} queries in batches of {batch}, "
               f"{n_frames / max(time.time() - time0, 1e-9):.1f} frames/s")
 
-    local = torch.cat(local_rows, dim=0) if local_rows else torch.zeros((0, 1 + 3 * A), dtype=torch.float64)
-    rows = _gather_rows_f64(local, [b - a for a, b in spans]).numpy()
-    result = replay_metrics(rows, A)
-    result.update(align=align, temporal_agg=bool(temporal_agg), num_queries=Q,
-                  files=[os.path.relpath(f, dataset_dir) if dataset_dir else f for f in files])
-    if horizon:
-        mine = torch.cat(local_hz, dim=0) if local_hz else torch.zeros((0, Q * (1 + 3 * A)), dtype=torch.float64)
-        result["horizon"] = horizon_metrics(_gather_rows_f64(mine, [b - a for a, b in spans]).numpy(), Q, A)
-    if sweep is not None:
-        G = len(sweep)
-        mine = torch.cat(local_sw, dim=0) if local_sw else torch.zeros((0, 1 + G + 4 * G * A), dtype=torch.float64)
-        result["sweep"] = sweep_metrics(_gather_rows_f64(mine, [b - a for a, b in spans]).numpy(), sweep, Q, A)
-    if attn is not None:
-        ns = layout.n_sources
-        mine = torch.cat(local_share, dim=0) if local_share else torch.zeros((0, 1 + ns), dtype=torch.float64)
-        sh = _gather_rows_f64(mine, [b - a for a, b in spans]).numpy()
-        count = float(sh[:, 0].sum())
-        result["attention"] = {"sources": attn["sources"], "share_mean": (sh[:, 1:].sum(0) / max(count, 1.0)).tolist(),
-                               "slots": list(attn["slots"]), "steps": int(count)}
+    result = {}
+    for part, mine in zip(parts, rows):
+        result.update(part.pooled(replay.gathered(mine, part.width, [b - a for a, b in spans])))
     if knn is not None:
-        result["knn"] = _replay_knn(config, ckpt_name, knn, policy, stats, store, ids, batch, episode_ensemble, action_error, align,
-                                    engine)
+        result["knn"] = _replay_knn(config, ckpt_name, knn, policy, stats, store, ids, batch, episode_ensemble, action_error, align)
     if save_episode:
-        Ts = rows[:, 0].astype(np.int64)
-        per_rank = [int(Ts[a:b].sum()) for a, b in spans]
-        mine = torch.cat(local_pt, dim=0) if local_pt else torch.zeros((0, 2 * A), dtype=torch.float64)
-        allpt = _gather_rows_f64(mine, per_rank).numpy()
+        Ts = [e["T"] for e in result["episodes"]]
+        allpt = replay.gathered(local_pt, 2 * A, [sum(Ts[a:b]) for a, b in spans])
         if rank == 0:
             os.makedirs(ckpt_dir, exist_ok=True)
-            off = 0
-            for i, T in enumerate(Ts):
-                np.savez(os.path.join(ckpt_dir, f"{stem}_ep{i}.npz"), pred=allpt[off:off + T, :A],
-                         target=allpt[off:off + T, A:].astype(np.float32))
-                off += int(T)
+            for i, pt in enumerate(np.split(allpt, np.cumsum(Ts)[:-1])):
+                np.savez(os.path.join(ckpt_dir, f"{stem}_ep{i}.npz"), pred=pt[:, :A], target=pt[:, A:].astype(np.float32))
             with open(os.path.join(ckpt_dir, stem + ".json"), "w") as f:
                 json.dump(result, f, indent=1)
     if verbose and rank == 0:
-        print(f"\nOpen-loop replay of {n} episodes ({result['steps']} steps, align={align}, "
-              f"{'temporal ensemble' if temporal_agg else 'chunk by chunk'}), action units:")
-        print("joint      MAE       RMSE        max")
-        for a in range(A):
-            print(f"{a:5d} {result['mae'][a]:10.5f} {result['rmse'][a]:10.5f} {result['max'][a]:10.5f}")
-        print(f" mean {result['mae_mean']:10.5f} {result['rmse_mean']:10.5f} {result['max_max']:10.5f} (max)")
-        if horizon:
-            hz = result["horizon"]
-            for j in horizon_slots(Q):
-                print(f"slot {j:4d}: MAE {hz['mae_mean'][j]:10.5f} over the joints, {hz['count'][j]} pairs "
-                      f"(the action {j} steps ahead of the query)")
-        if sweep is not None:
-            sw = result["sweep"]
-            print(f"\nSchedule sweep, {len(sw['schedules'])} schedules read off the same chunk tables (mean over the joints, action units):")
-            print("   g every horizon     mode        k        MAE       RMSE        max  roughness  empty")
-            for g, d in enumerate(sw["schedules"]):
-                mark = " ".join(m for m, i in (("<- best", sw["best"]), ("<- default", sw["default"])) if i == g)
-                print(f"{g:4d} {d['every']:5d} {d['horizon']:7d} {d['mode']:>8s} {d['k']:8.4f} {sw['mae_mean'][g]:10.5f} "
-                      f"{sw['rmse_mean'][g]:10.5f} {sw['max_max'][g]:10.5f} {sw['rough_mean'][g]:10.5f} {sw['empty'][g]:6d} {mark}")
-        if knn is not None:
-            kn = result["knn"]
-            print(f"nearest-neighbour baseline (k = {kn['k']}, state weight {kn['state_weight']:g}, {kn['support_rows']} support rows): "
-                  f"policy MAE {result['mae_mean']:.5f}, kNN MAE {kn['mae_mean']:.5f}, ratio "
-                  f"{result['mae_mean'] / kn['mae_mean'] if kn['mae_mean'] > 0 else float('inf'):.3f}, {kn['empty']} empty lookups")
-            if "select_k" in kn:
-                print(f"  select_k over k = 1..{len(kn['select_k']['mse'])}: best k = {kn['select_k']['best_k']} "
-                      f"(z-scored slot-0 MSE {min(kn['select_k']['mse']):.6f})")
-        if attn is not None:
-            at = result["attention"]
-            print(f"attention share per source, action slots {at['slots'][0]}..{at['slots'][1] - 1}, mean over {at['steps']} queries:")
-            for name, v in zip(at["sources"], at["share_mean"]):
-                print(f"{name:>20s} {v:8.4f}")
+        replay.report(result)
     return result
 
 
@@ -1011,15 +816,7 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
             res = replay_bc(config, None, policy=policy, stats=replay_store.norm_stats, store=replay_store, episodes=replay_ids,
                             align=config.get("replay_align") or "train", save_episode=False, verbose=(rank == 0),
                             horizon=bool(config.get("replay_horizon")), sweep=replay_sweep)
-            figures = {"replay_mae_mean": res["mae_mean"], "replay_rmse_mean": res["rmse_mean"], "replay_max_max": res["max_max"]}
-            if "horizon" in res:
-                for j in horizon_slots(int(policy_config["num_queries"])):
-                    figures[f"replay_h{j}_mae"] = res["horizon"]["mae_mean"][j]
-            if "sweep" in res:                                   # (the best checkpoint stays chosen by the default schedule's MAE)
-                sw = res["sweep"]
-                figures.update(replay_sweep_best_mae=sw["mae_mean"][sw["best"]], replay_sweep_best=sw["best"])
-                if sw["default"] is not None:
-                    figures["replay_sweep_default_mae"] = sw["mae_mean"][sw["default"]]
+            figures = replay.replay_figures(res)
             replay_history.append(dict(figures, step=step, steps=res["steps"], episodes=len(res["episodes"]),
                                        **({"sweep": res["sweep"]} if "sweep" in res else {})))
             if best_replay is None or res["mae_mean"] < best_replay[1]:
@@ -1045,7 +842,6 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
         torch.save(best_state_dict, os.path.join(ckpt_dir, f"policy_step_{best_step}_seed_{seed}.ckpt"))
         print(f"Training finished:\nSeed {seed}, val loss {min_val_loss:.6f} at step {best_step}")
         if replay_every:
-            import json
             with open(os.path.join(ckpt_dir, "replay_history.json"), "w") as f:
                 json.dump(replay_history, f, indent=1)
             if best_replay is not None:
@@ -1252,6 +1048,7 @@ def main(args):
     if args["eval"] and args.get("replay"):
         # open-loop replay on recorded episodes: what a use_depth / use_pcd policy (no simulator renders its inputs) and a policy
         # trained on real-robot episodes can be evaluated with
+        kw = dict(episodes=args.get("replay_episodes"))
         if config.get("replay_knn") is not None:
             # the store --device_dataset training holds (the same split from the same seed): the validation episodes are replayed,
             # the training episodes are the support set
@@ -1260,20 +1057,14 @@ def main(args):
             if not (dataset_dir and os.path.isdir(dataset_dir)):
                 raise ValueError("--replay_knn needs episode files (--dataset_dir)")
             train_dl, val_dl, stats, _ = _load_episode_data(args, config, task_config, dataset_dir, world, local_rank)
-            n = args.get("replay_episodes")
-            return replay_bc(config, "policy_last.ckpt", episodes=list(val_dl.episode_ids)[:None if n is None else int(n)],
-                             align=args.get("replay_align") or "train", save_episode=True, horizon=bool(args.get("replay_horizon")),
-                             attention=bool(config.get("replay_attention")), attention_slots=config.get("replay_attention_slots"),
-                             attention_frames=bool(config.get("replay_attention_frames")),
-                             sweep=(replay_sweep_schedules(config["policy_config"]["num_queries"], **config["replay_sweep"])
-                                    if config.get("replay_sweep") is not None else None),
-                             store=val_dl.store, stats=stats, knn=dict(config["replay_knn"], support_ids=list(train_dl.episode_ids)))
-        return replay_bc(config, "policy_last.ckpt", episodes=args.get("replay_episodes"),
-                         align=args.get("replay_align") or "train", save_episode=True, horizon=bool(args.get("replay_horizon")),
-                         attention=bool(config.get("replay_attention")), attention_slots=config.get("replay_attention_slots"),
+            kw = dict(episodes=list(val_dl.episode_ids)[:args.get("replay_episodes")], store=val_dl.store, stats=stats,
+                      knn=dict(config["replay_knn"], support_ids=list(train_dl.episode_ids)))
+        return replay_bc(config, "policy_last.ckpt", align=args.get("replay_align") or "train", save_episode=True,
+                         horizon=bool(args.get("replay_horizon")), attention=bool(config.get("replay_attention")),
+                         attention_slots=config.get("replay_attention_slots"),
                          attention_frames=bool(config.get("replay_attention_frames")),
                          sweep=(replay_sweep_schedules(config["policy_config"]["num_queries"], **config["replay_sweep"])
-                                if config.get("replay_sweep") is not None else None))
+                                if config.get("replay_sweep") is not None else None), **kw)
     if args["eval"]:
         results = []
         for ckpt_name in ["policy_last.ckpt"]:

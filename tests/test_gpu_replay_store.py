@@ -73,6 +73,27 @@ def test_chunk_error_against_numpy(i):
         assert np.array_equal(st3.cpu().numpy().view(np.int64), st.view(np.int64)) and np.array_equal(cnt3.cpu().numpy(), cnt)
 
 
+@pytest.mark.parametrize("shape,lengths", [((3, 20, 6, 64), [20, 0, 13]),           # a full, an empty and a cut episode
+                                           ((2, 310, 3, 33), None),                   # the block of 64: every thread walks many terms
+                                           ((2, 5, 10, 14), None)],                   # fewer steps than walk classes
+                         ids=lambda v: str(v))
+def test_chunk_error_slot_0_is_action_error(shape, lengths):
+    """shift 0, stride 1, a chunk for every frame: slot 0 of row t is compared with action[t] for t < length -- the terms of
+    action_error on the slot-0 trajectory, un-normalised, walked, combined and stored by the same code (csrc/error_core.h).
+    Equality is derived from that, not measured: torch.equal."""
+    E, T, Q, A = shape
+    rng = np.random.default_rng(900 + T)
+    chunks = torch.from_numpy(rng.standard_normal((E, T, Q, A)).astype(np.float32)).to(DEV)
+    actions = torch.from_numpy((rng.standard_normal((E, T, A)) * 2).astype(np.float32)).to(DEV)
+    mean, std = rng.standard_normal(A), 0.5 + rng.random(A)
+    st, cnt = ops.chunk_error(chunks, actions, lengths, None, mean, std, 1)
+    _, ref = ops.action_error(chunks[:, :, 0].double(), actions, lengths, mean, std, want_pred=False)
+    assert tuple(st.shape) == (E, Q, 3, A) and tuple(ref.shape) == (E, 3, A)
+    assert torch.equal(st[:, 0], ref)
+    assert cnt[:, 0].cpu().tolist() == [min(max(n, 0), T) for n in (lengths or [T] * E)]
+    assert bool(ref.any())                                            # (not an equality of zeros)
+
+
 def test_chunk_error_refuses_bad_arguments():
     ok = dict(chunks=torch.ones((2, 3, 4, 5), device=DEV), actions=torch.ones((2, 6, 5), device=DEV), lengths=None, shift=None,
               mean=np.zeros(5), std=np.ones(5), stride=1)
