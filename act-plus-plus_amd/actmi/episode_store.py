@@ -1,0 +1,756 @@
+"""Device-resident episode store (``load_data(..., device_dataset=True)``; DESIGN.md "Device-resident episode store"): every episode
+read ONCE into a device arena, a training batch then a few device gathers.
+
+Bottom up: ``probe_sources`` reads the files' headers, ``plan_store`` lays the arena out from them and ``batch_table`` builds the index
+table of one batch -- plain numpy, no device; ``DeviceEpisodeStore`` loads the arena by such a plan and launches the gathers over
+such tables; ``DeviceEpisodeReplay`` and ``DeviceBatchLoader`` are the iterables the training loop sees.  Episode files are read
+through ``episode_files``; ``data`` (the host dataset, ``load_data``) imports this module, never the other way round."""
+import time
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from .episode_files import MirrorTwinPath, _EpisodeArrays, _entry_meta, _read_action, cloud_mirror_rule, imdecode_bgr, open_episode
+
+ARENA_ALIGN = 256            # every block of the frame arena (one camera of one episode) starts at a multiple of this
+# Device memory the default budget leaves free: the training handle is created AFTER the loaders (imitate_episodes.main), and
+# with it come the batches, the augmenter's buffers and the allocator's cache.  Measured at B = 64, 4 cameras of 480x640: the
+# free memory drops by 51.5 GB (48 GiB) between the loaded store and the running training step
+# (profiles/device_dataset_time.json, memory_beside_the_store_bytes); 64 GiB leaves a third on top.  Pass budget_bytes /
+# --device_dataset_gb to decide otherwise (a larger batch needs a larger reserve).
+DEVICE_STORE_RESERVE_BYTES = 64 << 30
+
+
+def arena_layout(block_bytes, align=ARENA_ALIGN):
+    """Blocks of ``block_bytes[i]`` bytes back to back, every start padded to ``align`` -> (int64 offsets, total bytes).  Frame t of
+    block i lies at ``offsets[i] + t * frame_bytes``: a multiple of 16 whenever ``frame_bytes`` is one."""
+    offs, total = np.zeros(len(block_bytes), dtype=np.int64), 0
+    for i, n in enumerate(block_bytes):
+        offs[i] = total
+        total += (int(n) + align - 1) // align * align
+    return offs, int(total)
+
+
+def locate_transitions(indices, episode_len):
+    """``EpisodicDataset._locate_transition`` for a batch of flat indices -> (position in ``episode_len`` [B], start_ts [B])"""
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    lens = np.asarray(episode_len, dtype=np.int64)
+    cum = np.cumsum(lens)
+    if len(idx) and (idx.min() < 0 or idx.max() >= cum[-1]):
+        raise IndexError(f"flat index outside [0, {int(cum[-1])})")
+    ei = np.searchsorted(cum, idx, side="right")                  # the first episode whose cumulative length exceeds the index
+    return ei, idx - (cum[ei] - lens[ei])
+
+
+def stored_cloud_counts(root, base, path, T, N, pcd_ignore_mask=False):
+    """the valid count of every step of an episode's stored cloud ``base`` ([T, N, 3]) -> int32 [T], by ``_read_cloud``'s rules for
+    all steps at once: ``padding_mask`` must be T x N with its True rows first and at least one of them per step (``ValueError``
+    naming the file and the first offending timestep); without a mask, or with ``pcd_ignore_mask``, every stored row counts"""
+    counts = np.full(T, N, dtype=np.int32)
+    if not pcd_ignore_mask and f"{base}/padding_mask" in root:
+        mask = np.asarray(root[f"{base}/padding_mask"][()]).astype(bool)
+        if mask.shape[0] != T:
+            raise ValueError(f"{path}: padding_mask of {mask.shape[0]} steps for an episode of {T}")
+        mask = mask.reshape(T, -1)
+        if mask.shape[1] != N:
+            raise ValueError(f"{path} (timestep 0): padding_mask of {mask.shape[1]} rows for a cloud of {N}")
+        counts = mask.sum(axis=1).astype(np.int32)
+        bad = np.nonzero((mask != (np.arange(N)[None, :] < counts[:, None])).any(axis=1))[0]
+        if len(bad):
+            raise ValueError(f"{path} (timestep {int(bad[0])}): padding_mask is not a prefix (True rows first): the valid points "
+                             "cannot be given as a count")
+    empty = np.nonzero(counts == 0)[0]
+    if len(empty):
+        raise ValueError(f"{path} (timestep {int(empty[0])}): the point cloud has no valid point")
+    return counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the plan: headers -> layout -> the index table of a batch (numpy alone, no device)
+# ---------------------------------------------------------------------------------------------------------------------
+# One kind of frame a store holds -- the cameras' u8 B, G, R images or raw uint16 depth -- and, once planned, its blocks.
+# What the kind is: ``key``, the group of the episode files (/observations/<key>/<cam>); ``segment``, the name of its offsets in a
+# batch's index table; ``is_depth``; ``px_bytes``; ``torch_dtype`` of its tensor in a batch; ``row_unit``, the pixels of a row group
+# of the mirrored gather's 16-byte form; ``decode_as``, the device JPEG decoder's output form.
+# What ``plan_store`` adds: ``cams``; ``shape`` of a stored frame, (H, W, 3) / (H, W) (channel 0 of 3-D depth frames, as
+# ``_depth_data`` keeps); ``frame_bytes``; ``aligned``, 1 where every frame lies at a multiple of 16 bytes -- the statement the
+# gather's launcher cannot check for itself (actmi_op_gather_frames, `aligned`); ``src_block_off`` [sources, cams] int64, where each
+# camera's [T, *shape] block starts in the arena; ``block_off`` [episodes, cams], its source's, a twin's permuted by its spec;
+# ``flip`` [episodes, cams] uint8, 1 where a twin's camera is flipped along W.
+_FrameKind = namedtuple("_FrameKind", "key segment is_depth px_bytes torch_dtype row_unit decode_as cams shape frame_bytes aligned "
+                                      "src_block_off block_off flip", defaults=((), None, 0, 0, None, None, None))
+_KINDS = (_FrameKind("images", "frames", False, 3, torch.uint8, 16, "bgr"),
+          _FrameKind("depth_images", "depth", True, 2, torch.uint16, 8, "u16"))
+
+# What the plan needs of one source file, from its headers: ``T``; ``compressed``; ``cloud_rows``, N of its stored cloud [T, N, 3] (0:
+# the store holds no clouds) and ``cloud_rgb_dtype``; ``frames``, per kind (``_KINDS``) the (shape, dtype) of a frame, None where the
+# file did not size it
+SourceHeader = namedtuple("SourceHeader", "T compressed cloud_rows cloud_rgb_dtype frames", defaults=(0, None, (None, None)))
+
+
+def _checked_frame_shape(kind, path, key, dtype, fshape):
+    """the shape the store keeps of frames the headers call `dtype` `fshape`, or the ValueError of what it cannot keep"""
+    if not kind.is_depth:
+        if dtype != np.uint8 or len(fshape) != 3 or fshape[2] != 3:
+            raise ValueError(f"{path}: {key} frames are {dtype} {fshape}, expected uint8 [H, W, 3]")
+        return tuple(fshape)
+    if dtype.kind != "u" or dtype.itemsize > 2:
+        raise ValueError(f"{path}: {key} is {dtype}: the device-resident store keeps raw depth, an unsigned integer of at most 16 "
+                         f"bits (float depth is normalised on the host: train without --device_dataset)")
+    if len(fshape) not in (2, 3):
+        raise ValueError(f"{path}: {key} frames are {fshape}, expected [H, W] or [H, W, C]")
+    return tuple(fshape[:2])
+
+
+def probe_sources(sources, cams, cloud_base=None, max_points=None):
+    """Opens every source file once -> [SourceHeader].  `cams`: per kind the camera names; `cloud_base`: the stored cloud's group, None
+    without clouds.  The sizes come from the entries' headers (the first file's decoded frames for a compressed dataset: later
+    compressed files are checked as they are decoded).  Refused here, before anything large is allocated, each ``ValueError`` naming
+    the file: an empty episode, clouds that are not two [T, N, 3] arrays of T steps or store more than `max_points` rows
+    (``_read_cloud``'s checks, from the headers), frames that are not T, depth that is not an unsigned integer of at most 16 bits, and
+    cameras or files whose frame sizes differ -- checked as the walk reaches the file, so the first bad file is the one named."""
+    headers, sized = [], {}
+    for i, path in enumerate(sources):
+        with open_episode(path) as root:
+            compressed = bool(root.attrs.get("compress", False))
+            T = int(_entry_meta(root, "/action")[0][0])
+            if T < 1:
+                raise ValueError(f"{path}: empty episode")
+            N, cdt = 0, None
+            if cloud_base is not None:
+                if f"{cloud_base}/xyz" not in root or f"{cloud_base}/rgb" not in root:
+                    raise ValueError(f"{path}: no {cloud_base}/xyz and {cloud_base}/rgb")
+                (xs, _xdt), (cs, cdt) = _entry_meta(root, f"{cloud_base}/xyz"), _entry_meta(root, f"{cloud_base}/rgb")
+                if len(xs) != 3 or xs[2] != 3 or tuple(cs) != tuple(xs) or xs[1] < 1:
+                    raise ValueError(f"{path}: point cloud xyz {tuple(xs)} / rgb {tuple(cs)}, expected two [T, N, 3] arrays")
+                if xs[0] != T:
+                    raise ValueError(f"{path}: {cloud_base}/xyz holds {xs[0]} clouds for an episode of {T} steps")
+                if max_points is not None and xs[1] > max_points:
+                    raise ValueError(f"{path}: the point cloud stores {xs[1]} rows, more than max_points {max_points} (no "
+                                     "silent truncation: raise --max_points or down-sample the recording)")
+                N = int(xs[1])
+            frames = [None] * len(_KINDS)
+            for q, (kind, names) in enumerate(zip(_KINDS, cams)):
+                for cam in names:
+                    key = f"/observations/{kind.key}/{cam}"
+                    shape, dtype = _entry_meta(root, key)
+                    if shape[0] != T:
+                        raise ValueError(f"{path}: {key} holds {shape[0]} frames for an episode of {T} steps")
+                    if compressed:
+                        if i > 0:
+                            continue                               # sized by the first episode's frames; checked as it is decoded
+                        fshape, dtype = imdecode_bgr(np.asarray(root[key][0])).shape, np.dtype(np.uint8)
+                    else:
+                        fshape = shape[1:]
+                    fshape = _checked_frame_shape(kind, path, key, dtype, fshape)
+                    if sized.setdefault(kind.key, fshape) != fshape:
+                        raise ValueError(f"{path}: {key} frames are {fshape}, others {sized[kind.key]}: one batch shape only")
+                    frames[q] = (fshape, dtype)
+        headers.append(SourceHeader(T, compressed, N, cdt, tuple(frames)))
+    return headers
+
+
+def twin_camera_map(path, cams):
+    """Of the mirrored twin `path`, per kind and camera: (the place among `cams` of the source's camera whose frames it shows, whether
+    they are flipped).  A twin whose source camera is not among the store's cameras is refused (``ValueError``)."""
+    out = []
+    with open_episode(path) as view:
+        for kind, names in zip(_KINDS, cams):
+            row = []
+            for cam in names:
+                found = view._resolve(f"/observations/{kind.key}/{cam}")
+                if found is None:
+                    raise ValueError(f"{path}: the mirror twin holds no /observations/{kind.key}/{cam}")
+                src_cam = found[1].rsplit("/", 1)[1]
+                if src_cam not in names:
+                    raise ValueError(f"{path}: /observations/{kind.key}/{cam} of the twin is the source's {src_cam}, which is not "
+                                     f"among the store's cameras {list(names)}")
+                row.append((list(names).index(src_cam), bool(found[2])))
+            out.append(tuple(row))
+    return tuple(out)
+
+
+def _starts(lengths):
+    return np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+
+
+# What ``plan_store`` decides: where everything lies in the arena, per source file and -- indexed with ``src_of`` -- per episode.
+# ``all_kinds``: a _FrameKind per entry of ``_KINDS`` (one without cameras holds no block); ``nbytes``; ``padding``, the (begin, end)
+# byte ranges no block holds; ``src_of`` [episodes], the source file of each; ``twin`` [episodes] bool.  Per source: ``src_T``,
+# ``src_compressed``, ``src_N`` (stored rows of its clouds), ``src_cloud_off`` [sources, 2] (its xyz and its colour block; [sources,
+# 0] without clouds), ``src_row0`` (of its steps in the host array of valid counts, ``cloud_n``).  ``cloud_rgb_fmt``: 0 uint8 colours
+# (every source stores them so), 1 float32 everywhere; ``cloud_rgb_bytes`` of one stored colour row.  Per episode: ``T``,
+# ``compressed``, ``row0`` (of its rows in ``actions`` / ``qpos``).  ``kinds``: those of ``all_kinds`` that have cameras; ``has_twins``;
+# ``has_clouds``.
+StoreLayout = namedtuple("StoreLayout", "all_kinds nbytes padding src_of twin src_T src_compressed src_N src_cloud_off src_row0 "
+                                        "cloud_rgb_fmt cloud_rgb_bytes T compressed row0 kinds has_twins has_clouds")
+
+
+def plan_store(headers, cams, src_of, twin_cams=None):
+    """The arena of a store, from its sources' headers -> StoreLayout.  Per source file (each once, in order), per camera of
+    ``cams[0]`` one u8 ``[T, H, W, 3]`` block, then per depth camera (``cams[1]``) one raw uint16 ``[T, H, W]`` block, then -- where the
+    headers name clouds -- one float32 ``[T, N, 3]`` xyz block and one colour block ``[T, N, 3]``, uint8 when every source stores
+    uint8, float32 everywhere otherwise; N may differ between sources.  Every block start is padded to 256 bytes (``arena_layout``).
+
+    ``src_of[i]``: the source of episode i.  ``twin_cams[i]``: None for an episode file; for a mirrored twin its
+    ``twin_camera_map``.  A twin adds no bytes: its camera blocks are its source's, permuted, with a flag per camera that is flipped,
+    and its clouds are its source's blocks."""
+    src_of = np.asarray(src_of, dtype=np.int64)
+    twin_cams = [None] * len(src_of) if twin_cams is None else list(twin_cams)
+    src_T = np.asarray([h.T for h in headers], dtype=np.int64)
+    src_N = np.asarray([h.cloud_rows for h in headers], dtype=np.int64)
+    nc = 2 if headers[0].cloud_rows else 0                            # an xyz and a colour block per source, behind its frames
+    rgb_bytes = 3 if not nc or all(h.cloud_rgb_dtype == np.uint8 for h in headers) else 12
+    shapes = [next((h.frames[q][0] for h in headers if h.frames[q] is not None), None) for q in range(len(_KINDS))]
+    fbytes = [int(np.prod(s[:2])) * k.px_bytes if c else 0 for k, c, s in zip(_KINDS, cams, shapes)]
+    blocks = []
+    for T, N in zip(src_T.tolist(), src_N.tolist()):
+        for fb, c in zip(fbytes, cams):
+            blocks += [T * fb] * len(c)
+        blocks += [T * N * 12, T * N * rgb_bytes][:nc]
+    offs, nbytes = arena_layout(blocks)
+    ends = [int(o) + int(b) for o, b in zip(offs, blocks)]
+    padding = [(e, int(n)) for e, n in zip(ends, list(offs[1:]) + [nbytes]) if n > e]
+    offs = offs.reshape(len(headers), -1)
+    kinds, col = [], 0
+    for q, (proto, c, shape, fb) in enumerate(zip(_KINDS, cams, shapes, fbytes)):
+        src_off = offs[:, col:col + len(c)].copy()
+        col += len(c)
+        off, flip = src_off[src_of], np.zeros((len(src_of), len(c)), dtype=np.uint8)
+        for i, tw in enumerate(twin_cams):
+            for k, (src_k, flipped) in enumerate(tw[q] if tw is not None else ()):
+                off[i, k], flip[i, k] = src_off[src_of[i], src_k], 1 if flipped else 0
+        kinds.append(proto._replace(cams=tuple(c), shape=shape if c else None, frame_bytes=fb, aligned=1 if c and fb % 16 == 0 else 0,
+                                    src_block_off=src_off, block_off=off, flip=flip))
+    compressed, twin = [h.compressed for h in headers], [tw is not None for tw in twin_cams]
+    return StoreLayout(tuple(kinds), nbytes, padding, src_of, twin, src_T, compressed, src_N, offs[:, col:].copy(), _starts(src_T),
+                       0 if rgb_bytes == 3 else 1, rgb_bytes, src_T[src_of], [compressed[j] for j in src_of], _starts(src_T[src_of]),
+                       tuple(k for k in kinds if k.cams), any(twin), nc > 0)
+
+
+class BatchTable:
+    """Named numpy segments, in the order given, as the ONE int64 table a batch uploads (``host``); ``slices`` cuts the uploaded
+    tensor back into the segments by name (an empty segment has no slice).  Every segment is a whole number of 8-byte words."""
+
+    def __init__(self, segments):
+        self.bounds, parts, n = {}, [], 0
+        for name, v in segments.items():                              # plain Python: this runs once per training step
+            parts.append(np.ascontiguousarray(v).reshape(-1).view(np.int64))
+            self.bounds[name], n = (n, n + len(parts[-1])), n + len(parts[-1])
+        self.host = np.concatenate(parts)
+
+    def slices(self, tab):
+        return {name: tab[a:b] for name, (a, b) in self.bounds.items() if b > a}
+
+
+def cloud_items(layout, e, t, cloud_n):
+    """the records (``ops.cloud_item_dtype``) of the clouds of samples (e[b], t[b]): where the step's rows lie in its source's two
+    blocks, how many there are, how many are points (``cloud_n``, the valid count of every stored step), and the mirror flag of a
+    twin, whose clouds are its source's blocks"""
+    from . import ops
+    j = layout.src_of[e]
+    N = layout.src_N[j]
+    items = np.zeros(len(e), dtype=ops.cloud_item_dtype())
+    items["xyz_off"] = layout.src_cloud_off[j, 0] + t * N * 12
+    items["rgb_off"] = layout.src_cloud_off[j, 1] + t * N * layout.cloud_rgb_bytes
+    items["rows"], items["n"] = N, cloud_n[layout.src_row0[j] + t]
+    items["flags"] = np.asarray(layout.twin, dtype=np.int32)[e]
+    return items
+
+
+def batch_table(layout, e, t, cloud_n=None):
+    """The index table of the batch of samples (e[b], t[b]), int64 arrays: ``frames`` and ``depth``, the arena byte offset of every
+    camera's frame; ``samples``, the (e, t) pairs as int32; with twins ``flips``, a flag per frame and depth item packed eight to a
+    word; with clouds ``cloud_items``."""
+    seg = {k.segment: k.block_off[e] + t[:, None] * k.frame_bytes for k in layout.all_kinds}
+    seg["samples"] = np.stack([e, t], axis=1).astype(np.int32)
+    if layout.has_twins:
+        flags = np.concatenate([k.flip[e].reshape(-1) for k in layout.all_kinds])
+        seg["flips"] = np.zeros((len(flags) + 7) // 8 * 8, dtype=np.uint8)
+        seg["flips"][:len(flags)] = flags
+    if layout.has_clouds:
+        seg["cloud_items"] = cloud_items(layout, e, t, cloud_n)
+    return BatchTable(seg)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the store
+# ---------------------------------------------------------------------------------------------------------------------
+class DeviceEpisodeStore:
+    """Every frame of the named episodes (``episode_ids`` order, duplicates dropped) in ONE device arena, read from the files once; a
+    training batch is then a device-to-device gather (``gather``) and equals what ``EpisodicDataset.__getitem__`` + the default
+    collation (``collate_pcd`` with stored clouds) give for the same flat indices, bit for bit and dtype for dtype.  Actions and qpos
+    (float32 as the dataset converts them, ``/base_action`` columns included), the episode table and the four stat vectors are small
+    device arrays.  Mirrored twins (``MirrorTwinPath`` entries) add no frame bytes: ``sources`` are the files the arena holds, each
+    once; a twin has its own rows in ``actions`` / ``qpos`` and its own episode record.
+
+    Refused before anything large is allocated: ``use_pcd`` without exactly one cloud name and a policy class other than ACT
+    (``NotImplementedError``), what ``probe_sources`` and ``twin_camera_map`` refuse, and a dataset larger than the budget
+    (``MemoryError`` naming both numbers).  ``budget_bytes`` None: the device's free memory now minus ``DEVICE_STORE_RESERVE_BYTES``.
+    ``device_decode`` changes neither what the arena holds nor which error a bad file raises (``_decode_on_device``).
+
+    Every rank of a data-parallel run holds its own full store."""
+
+    RING = 4                 # pinned index blocks in flight: a block is rewritten only after its copy has executed
+
+    def __init__(self, dataset_path_list, episode_ids, camera_names, norm_stats, device, depth_camera_names=None, use_depth=False,
+                 budget_bytes=None, use_pcd=False, policy_class="ACT", stage_bytes=64 << 20, pointcloud_names=None, max_points=None,
+                 pcd_ignore_mask=False, device_decode=False, decode_frames=256):
+        self.device_decode, self.decode_frames = bool(device_decode), int(decode_frames)
+        self.pointcloud_names = list(pointcloud_names) if pointcloud_names else []
+        self.has_clouds = bool(use_pcd) and bool(self.pointcloud_names)
+        if self.has_clouds and len(self.pointcloud_names) != 1:
+            raise ValueError(f"use_pcd needs exactly one pointcloud name (/observations/pointcloud/<name>), got {self.pointcloud_names}")
+        if self.has_clouds and use_depth:
+            raise NotImplementedError("use_depth together with use_pcd is not supported")
+        self.max_points, self.pcd_ignore_mask = None if max_points is None else int(max_points), bool(pcd_ignore_mask)
+        if use_pcd and not self.has_clouds:
+            raise NotImplementedError("--device_dataset with use_pcd: point clouds through the device-resident store are not "
+                                      "implemented (ragged clouds stay on the host loader); drop --device_dataset")
+        if policy_class not in (None, "ACT"):
+            raise NotImplementedError(f"--device_dataset: the device-resident store feeds the ACT training path, not {policy_class!r}")
+        self.camera_names = list(camera_names)
+        self.use_depth = bool(use_depth)
+        self.depth_camera_names = list(depth_camera_names) if depth_camera_names else []
+        if self.use_depth and not self.depth_camera_names:
+            raise ValueError("use_depth needs depth_camera_names (the task config's list of /observations/depth_images/<cam>)")
+        if not self.camera_names:
+            raise ValueError("DeviceEpisodeStore: no camera names")
+        self.episode_ids = list(dict.fromkeys(int(i) for i in episode_ids))
+        if not self.episode_ids:
+            raise ValueError("DeviceEpisodeStore: no episodes")
+        self.paths = [dataset_path_list[i] for i in self.episode_ids]
+        self._local_of = {e: i for i, e in enumerate(self.episode_ids)}
+        # the files whose frames the arena holds, each once: an episode file is its own source, a mirrored twin's is the file it is
+        # the image of (loaded for the twin's sake alone when it is not listed itself)
+        self.twin = [isinstance(p, MirrorTwinPath) for p in self.paths]
+        self.has_twins = any(self.twin)
+        srcs = [p.source if tw else str(p) for p, tw in zip(self.paths, self.twin)]
+        self.sources = list(dict.fromkeys(srcs))
+        where = {s: j for j, s in enumerate(self.sources)}
+        self.cloud_mirror = None                                      # (axis, offset, c2): the one rule of the twins' clouds
+        if self.has_clouds and self.has_twins:
+            rules = {getattr(p, "cloud_mirror", None) for p, tw in zip(self.paths, self.twin) if tw}
+            if None in rules:
+                raise ValueError("use_pcd with mirror twins: a stored point cloud has no mirror rule (MirrorTwinPath(..., "
+                                 "cloud_mirror=(axis, offset)) gives it one)")
+            if len(rules) != 1:
+                raise ValueError(f"DeviceEpisodeStore: the twins carry different cloud mirror rules {sorted(rules)}: one gather takes one")
+            self.cloud_mirror = cloud_mirror_rule(rules.pop())
+        self.device, self.stage_bytes = device, int(stage_bytes)
+        cams = (tuple(self.camera_names), tuple(self.depth_camera_names) if self.use_depth else ())
+        self._cloud_base = f"/observations/pointcloud/{self.pointcloud_names[0]}" if self.has_clouds else None
+        headers = probe_sources(self.sources, cams, self._cloud_base, self.max_points)
+        self.layout = lay = plan_store(headers, cams, [where[s] for s in srcs],
+                                       [twin_camera_map(p, cams) if tw else None for p, tw in zip(self.paths, self.twin)])
+        self.kinds, (img, dep) = lay.kinds, lay.all_kinds
+        self.K, self.Kd = len(img.cams), len(dep.cams)
+        self.frame_shape, self.frame_bytes, self.aligned, self.block_off, self.flip = \
+            img.shape, img.frame_bytes, img.aligned, img.block_off, img.flip
+        self.depth_shape, self.depth_bytes, self.depth_aligned, self.depth_block_off, self.depth_flip = \
+            dep.shape, dep.frame_bytes, dep.aligned, dep.block_off, dep.flip
+        self.nbytes, self.T, self.row0, self.compressed = lay.nbytes, lay.T, lay.row0, lay.compressed
+        self.cloud_rgb_fmt, self.cloud_rgb_bytes = lay.cloud_rgb_fmt, lay.cloud_rgb_bytes
+        if budget_bytes is None:
+            free, _total = torch.cuda.mem_get_info(torch.device(device))
+            budget_bytes = free - DEVICE_STORE_RESERVE_BYTES
+        self.budget_bytes = int(budget_bytes)
+        if self.nbytes > self.budget_bytes:
+            raise MemoryError(f"DeviceEpisodeStore: {len(self.paths)} episodes need {self.nbytes} bytes on the device "
+                              f"({self.nbytes / 2**30:.2f} GiB), the budget is {self.budget_bytes} bytes "
+                              f"({self.budget_bytes / 2**30:.2f} GiB): train without --device_dataset, or raise --device_dataset_gb")
+        self._load(norm_stats)
+
+    # ---- the one read of every episode ----------------------------------------------------------------------------
+    def _load(self, norm_stats):
+        """The blocks reach the device through two bounded pinned staging buffers of ``stage_bytes``, never a pinned copy of an
+        episode, and every block is checked against the plan again as it is loaded."""
+        from . import ops
+        lay, dev = self.layout, torch.device(self.device)
+        t_begin = time.perf_counter()
+        self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        for a, b in lay.padding:                                      # the padding between blocks is zero: two stores of one
+            self.arena[a:b].zero_()                                   # dataset hold the same bytes everywhere
+        stage = max(self.stage_bytes, self.frame_bytes, self.depth_bytes, int(lay.src_N.max()) * 12 if self.has_clouds else 0)
+        self.cloud_n = np.zeros(int(lay.src_T.sum()) if self.has_clouds else 0, dtype=np.int32)   # valid rows of every stored step
+        self._pin = [torch.empty(stage, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self._pin_ev, self._pin_i = [None, None], 0
+        self.decode_stats = {"device": 0, "host": 0}
+        self.bus_bytes = 0                                            # bytes of frames and clouds that crossed to the device
+        self._decoders, self._pending, self._jpeg_stream = {}, [], None
+        if self.device_decode and any(lay.src_compressed):
+            self._jpeg_stream = torch.empty(stage, dtype=torch.uint8, device=dev)
+        actions, qposes, sims = [], [], []
+        loaded = set()
+        for i, path in enumerate(self.paths):
+            T = int(self.T[i])
+            with open_episode(path) as raw:
+                root = _EpisodeArrays(raw)                            # a twin: the view, whose rows are the mirrored ones
+                attrs = root.attrs
+                sims.append(bool(attrs["sim"]) if "sim" in attrs else False)
+                action = np.asarray(_read_action(root))
+                qpos = np.asarray(root["/observations/qpos"][()])
+                if action.ndim != 2 or action.shape[0] != T or qpos.ndim != 2 or qpos.shape[0] != T:
+                    raise ValueError(f"{path}: action {action.shape} / qpos {qpos.shape} for an episode of {T} steps")
+                actions.append(action.astype(np.float32))            # padded_action is float32: the assignment converts
+                qposes.append(torch.from_numpy(qpos).float().numpy())
+                if not self.twin[i]:
+                    self._load_source(root, int(lay.src_of[i]))
+                    loaded.add(int(lay.src_of[i]))
+        for j in range(len(self.sources)):                            # the sources only twins name
+            if j not in loaded:
+                with open_episode(self.sources[j]) as raw:
+                    self._load_source(_EpisodeArrays(raw), j)
+        A, S = actions[0].shape[1], qposes[0].shape[1]
+        if any(a.shape[1] != A for a in actions) or any(q.shape[1] != S for q in qposes):
+            raise ValueError("DeviceEpisodeStore: episodes differ in their action or qpos width")
+        self.A, self.S = int(A), int(S)
+        self.actions = torch.from_numpy(np.concatenate(actions, axis=0)).to(dev)
+        self.qpos = torch.from_numpy(np.concatenate(qposes, axis=0)).to(dev)
+        rec = np.zeros(len(self.paths), dtype=ops.episode_rec_dtype())
+        rec["row0"], rec["T"], rec["is_sim"] = self.row0, self.T, np.asarray(sims, dtype=np.int32)
+        self.is_sim = sims
+        self.episodes = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+        self.norm_stats = norm_stats                                  # as given: what a replay out of the store un-normalises with
+        self._stats = [torch.as_tensor(np.asarray(norm_stats[k]), dtype=torch.float32).reshape(-1).contiguous().to(dev)
+                       for k in ("action_mean", "action_std", "qpos_mean", "qpos_std")]
+        if self._stats[0].numel() != self.A or self._stats[2].numel() != self.S:
+            raise ValueError(f"DeviceEpisodeStore: norm stats of {self._stats[0].numel()} action / {self._stats[2].numel()} qpos "
+                             f"values for episodes of {self.A} / {self.S}")
+        torch.cuda.synchronize(dev)
+        self._pin = self._pin_ev = None                               # the staging buffers are the load's alone
+        self._decoders = self._jpeg_stream = None                     # and so are the decoder's workspace and stream buffer
+        self.load_seconds = time.perf_counter() - t_begin
+        self._host, self._host_ev, self._slot = [None] * self.RING, [None] * self.RING, 0
+
+    def _load_source(self, root, j):
+        """the frames of source file j, open as `root`, into its blocks of the arena"""
+        path, T, compressed = self.sources[j], int(self.layout.src_T[j]), self.layout.src_compressed[j]
+        for kind in self.kinds:
+            for k, cam in enumerate(kind.cams):
+                key = f"/observations/{kind.key}/{cam}"
+                self._load_block(root[key], kind, T, compressed, int(kind.src_block_off[j, k]), f"{path}: {key}")
+        self._finish_device_decode()
+        if self.has_clouds:
+            self._load_clouds(root, j)
+
+    def _load_clouds(self, root, j):
+        """the clouds of source file j into its two blocks, and the valid count of every step by ``_read_cloud``'s rules (raised
+        with the file and the timestep) into the host array ``cloud_n``"""
+        lay = self.layout
+        path, T, N, base = self.sources[j], int(lay.src_T[j]), int(lay.src_N[j]), self._cloud_base
+        f32c = self.cloud_rgb_fmt == 1
+        for leaf, off, rb in (("xyz", int(lay.src_cloud_off[j, 0]), 12), ("rgb", int(lay.src_cloud_off[j, 1]), self.cloud_rgb_bytes)):
+            entry = root[f"{base}/{leaf}"]
+            per = max(1, self._pin[0].numel() // (N * rb))
+            for t0 in range(0, T, per):
+                t1 = min(T, t0 + per)
+                piece = np.asarray(entry[t0:t1])
+                if piece.shape != (t1 - t0, N, 3):
+                    raise ValueError(f"{path} (timestep {t0}): point cloud {leaf} {piece.shape[1:]}, the store was sized for {(N, 3)}")
+                if leaf == "rgb" and not f32c:
+                    if piece.dtype != np.uint8:
+                        raise ValueError(f"{path}: {base}/rgb is {piece.dtype}, its header said uint8")
+                    flat = np.ascontiguousarray(piece).reshape(-1)
+                else:                                                 # np.ascontiguousarray(..., dtype=np.float32), as _read_cloud
+                    flat = np.ascontiguousarray(piece, dtype=np.float32).reshape(-1).view(np.uint8)
+                n = (t1 - t0) * N * rb
+                if off + t0 * N * rb + n > self.nbytes:               # cannot happen with the sizes the plan checked
+                    raise MemoryError(f"{path}: cloud block leaves the arena of {self.nbytes} bytes")
+                self._stage(off + t0 * N * rb, n, lambda view, flat=flat: np.copyto(view, flat))
+        counts = stored_cloud_counts(root, base, path, T, N, self.pcd_ignore_mask)
+        self.cloud_n[int(lay.src_row0[j]):int(lay.src_row0[j]) + T] = counts
+
+    def _stage(self, dst_off, nbytes, fill, dst=None):
+        """one piece through the staging pair: ``fill(view)`` writes `nbytes` bytes into the pinned view, which is then copied to
+        the arena (or to `dst`, another device buffer); a buffer is refilled only after the copy that read it has executed"""
+        dst = self.arena if dst is None else dst
+        self.bus_bytes += int(nbytes)
+        j = self._pin_i
+        self._pin_i = 1 - j
+        if self._pin_ev[j] is not None:
+            self._pin_ev[j].synchronize()
+        fill(self._pin[j].numpy()[:nbytes])
+        dst[dst_off:dst_off + nbytes].copy_(self._pin[j][:nbytes], non_blocking=True)
+        self._pin_ev[j] = torch.cuda.Event()
+        self._pin_ev[j].record(torch.cuda.current_stream(self.arena.device))
+
+    def _load_block(self, entry, kind, T, compressed, dst_off, where):
+        """one camera's block, a staging buffer's worth of frames at a time; compressed episodes are decoded once"""
+        fb = kind.frame_bytes
+        per = max(1, self._pin[0].numel() // fb)
+        for t0 in range(0, T, per):
+            t1 = min(T, t0 + per)
+            piece = np.asarray(entry[t0:t1])
+            if compressed and self._jpeg_stream is not None and piece.ndim == 2 and piece.dtype == np.uint8:
+                for i in self._decode_on_device(piece, dst_off + t0 * fb, kind):
+                    self._decode_on_host(piece[i], kind, dst_off + (t0 + i) * fb, where)    # what the parser refused
+                continue
+            if compressed:                                            # utils.py:104-107, frame by frame
+                piece = np.stack([imdecode_bgr(buf) for buf in piece])
+            self._stage_frames(piece, t1 - t0, kind, dst_off + t0 * fb, where)
+
+    def _stage_frames(self, piece, n, kind, dst_off, where):
+        """`n` decoded frames of one kind, checked against the plan, to arena[dst_off:]"""
+        if kind.is_depth:
+            if piece.dtype.kind != "u" or piece.dtype.itemsize > 2:
+                raise ValueError(f"{where} is {piece.dtype}: not raw depth (an unsigned integer of at most 16 bits)")
+            if piece.ndim == 4:
+                piece = piece[..., 0]                                 # _depth_data: a 3-D frame keeps channel 0
+            piece = piece.astype(np.uint16, copy=False)
+        if piece.shape != (n,) + tuple(kind.shape) or (not kind.is_depth and piece.dtype != np.uint8):
+            raise ValueError(f"{where}: frames {piece.dtype} {piece.shape[1:]}, the store was sized for {tuple(kind.shape)}")
+        if dst_off + n * kind.frame_bytes > self.nbytes:             # cannot happen with the sizes the plan checked
+            raise MemoryError(f"{where}: block leaves the arena of {self.nbytes} bytes")
+        flat = np.ascontiguousarray(piece).reshape(-1).view(np.uint8)
+        self._stage(dst_off, n * kind.frame_bytes, lambda view: np.copyto(view, flat))
+
+    # ---- compressed frames decoded on the device (device_decode) -------------------------------------------------------
+    def _decode_on_host(self, buf, kind, dst_off, where):
+        """one compressed frame by the host path, as without ``device_decode``"""
+        self._stage_frames(imdecode_bgr(buf)[None], 1, kind, dst_off, where)
+        self.decode_stats["host"] += 1
+
+    def _decode_on_device(self, piece, dst_off, kind):
+        """``device_decode``: the frames of a compressed source are decoded on the device (``ops.JpegDecoder``, actmi_op_jpeg_decode)
+        instead of one by one through PIL.  The frames of `piece` ([n, L] u8, one zero-padded file each) that the parser accepts at
+        the store's size: their entropy segments go through the staging pair and the op writes straight into
+        arena[dst_off + i * frame bytes], B, G, R for cameras and the uint16 form for depth, up to ``decode_frames`` frames a launch;
+        -> the indices of the other frames (refused by the parser, of another size, or larger than the staging buffer), which the
+        caller decodes on the host.  The statuses stay on the device until ``_finish_device_decode``.  The decoder's workspace and
+        stream buffer live only during the load."""
+        from . import ops
+        fb = kind.frame_bytes
+        H, W = kind.shape[:2]
+        dec = self._decoders.get((H, W))
+        if dec is None:
+            dec = self._decoders[(H, W)] = ops.JpegDecoder(self.device, H, W, max_frames=self.decode_frames)
+        host, todo = [], {}
+        for i, buf in enumerate(piece):
+            try:
+                info = dec.parse(buf)
+            except ops.JpegUnsupported:
+                host.append(i)
+                continue
+            if (info["H"], info["W"]) != (H, W):
+                host.append(i)
+                continue
+            todo.setdefault(info["mode"], []).append((i, info))
+        cap = int(self._jpeg_stream.numel())
+        for mode, items in todo.items():
+            k0 = 0
+            while k0 < len(items):                                    # as many frames as the stream buffer and one launch hold
+                k1, nbytes = k0, 0
+                while k1 < len(items) and k1 - k0 < dec.max_frames and nbytes + items[k1][1]["seg_len"] <= cap:
+                    nbytes += items[k1][1]["seg_len"]
+                    k1 += 1
+                if k1 == k0:                                          # one segment larger than the staging buffer
+                    host.append(items[k0][0])
+                    k0 += 1
+                    continue
+                part = items[k0:k1]
+                frames = np.zeros(len(part), dtype=ops.jpeg_frame_dtype())
+                lens = np.asarray([info["seg_len"] for _i, info in part], dtype=np.int64)
+                frames["seg_len"], frames["seg_off"] = lens, np.concatenate([[0], np.cumsum(lens)[:-1]])
+                frames["dst_off"] = [dst_off + i * fb for i, _info in part]
+                frames["restart_interval"] = [info["restart_interval"] for _i, info in part]
+                frames["table_set"] = [dec.table_index(info["tables"]) for _i, info in part]
+
+                def fill(view, part=part, frames=frames):
+                    for (i, info), o, n in zip(part, frames["seg_off"], frames["seg_len"]):
+                        view[o:o + n] = piece[i][info["seg_off"]:info["seg_off"] + n]
+                if nbytes:
+                    self._stage(0, nbytes, fill, self._jpeg_stream)
+                status = dec.decode(self._jpeg_stream, frames, mode, kind.decode_as, self.arena)
+                self._pending.append((status, [(piece[i], int(o)) for (i, _info), o in zip(part, frames["dst_off"])], kind))
+                k0 = k1
+        return sorted(host)
+
+    def _finish_device_decode(self):
+        """the statuses of a source file's launches, read back once; a frame whose status is not 0 takes the host path, before the
+        store is handed out.  ``decode_stats`` counts the frames of both paths."""
+        if not self._pending:
+            return
+        status = torch.cat([st for st, _frames, _kind in self._pending]).cpu().numpy()
+        k = 0
+        for _st, frames, kind in self._pending:
+            for buf, off in frames:
+                if status[k]:
+                    self._decode_on_host(buf, kind, off, f"a frame at arena byte {off}")
+                else:
+                    self.decode_stats["device"] += 1
+                k += 1
+        self._pending = []
+
+    # ---- batches --------------------------------------------------------------------------------------------------
+    def device_bytes(self):
+        """bytes of device memory the store holds"""
+        return int(self.arena.numel() + self.actions.numel() * 4 + self.qpos.numel() * 4 + self.episodes.numel() +
+                   sum(s.numel() * 4 for s in self._stats))
+
+    def frame_offsets(self, local_episode, t):
+        """byte offsets into the arena of the frames of samples (local_episode[b], t[b]) -> ([B, K], [B, Kd]) int64"""
+        e, t = np.asarray(local_episode, dtype=np.int64), np.asarray(t, dtype=np.int64)
+        return tuple(k.block_off[e] + t[:, None] * k.frame_bytes for k in self.layout.all_kinds)
+
+    def _upload(self, table):
+        """the int64 index table of one batch -> a device tensor, by a stream-ordered copy from a pinned block of a ring"""
+        n = len(table)
+        i = self._slot
+        self._slot = (i + 1) % self.RING
+        if self._host_ev[i] is not None:
+            self._host_ev[i].synchronize()                             # the copy that last read this block has executed
+        if self._host[i] is None or self._host[i].numel() < n:
+            self._host[i] = torch.empty(max(n, 1024), dtype=torch.int64, pin_memory=True)
+        self._host[i].numpy()[:n] = table
+        dev = self.arena.device
+        tab = torch.empty(n, dtype=torch.int64, device=dev)
+        tab.copy_(self._host[i][:n], non_blocking=True)
+        self._host_ev[i] = torch.cuda.Event()
+        self._host_ev[i].record(torch.cuda.current_stream(dev))
+        return tab
+
+    def gather(self, local_episode, t, Q, nontemporal=True):
+        """the batch of samples (local_episode[b], t[b]) with chunks of Q steps, on the current stream of the store's device:
+        (image u8 [B, K, H, W, 3], qpos f32 [B, S], action f32 [B, Q, A], is_pad bool [B, Q]), then with depth (depth uint16
+        [B, Kd, 1, H, W]), or with stored clouds the three entries of ``collate_pcd``.  ONE index upload (``batch_table``), then the
+        clouds' launch if any, the frames, the chunks, the depth frames if any.  A store that holds a twin gathers frames and depth with
+        ``ops.gather_frames_mirror``; one without launches what it always did.
+        ``nontemporal``: the 16-byte form reads the arena with non-temporal loads -- measured 0.77-0.87 of the plain loads' time at
+        B = 64 and level with them at B = 8 (profiles/device_dataset_time.json); the bytes are the same either way"""
+        from . import ops
+        e, t = np.asarray(local_episode, dtype=np.int64).reshape(-1), np.asarray(t, dtype=np.int64).reshape(-1)
+        B = len(e)
+        if B < 1 or len(t) != B:
+            raise ValueError(f"DeviceEpisodeStore.gather: {B} episodes, {len(t)} steps")
+        if e.min() < 0 or e.max() >= len(self.paths) or t.min() < 0 or np.any(t >= self.T[e]):
+            raise IndexError("DeviceEpisodeStore.gather: a sample outside the stored episodes")
+        lay = self.layout
+        table = batch_table(lay, e, t, self.cloud_n)
+        with torch.cuda.device(self.arena.device):
+            seg = table.slices(self._upload(table.host))
+            clouds = ()
+            if self.has_clouds:
+                # P: the batch's largest stored row count, as ``collate_pcd`` pads; the 16-byte form where P allows it (torch's
+                # allocations are 16-byte aligned).  The twins' ``cloud_mirror`` rule -- one for the whole store -- is the launch's
+                P = int(lay.src_N[lay.src_of[e]].max())
+                mirror = None if self.cloud_mirror is None else (self.cloud_mirror[0], self.cloud_mirror[2])
+                clouds = ops.gather_clouds(self.arena, seg["cloud_items"], P, self.cloud_rgb_fmt, mirror=mirror,
+                                           aligned=(2 if nontemporal else 1) if P % 4 == 0 else 0)
+            flips = seg["flips"].view(torch.uint8) if self.has_twins else None
+            image = self._gather_frames(self.kinds[0], seg, flips, 0, B, nontemporal)
+            qpos, action, is_pad = ops.gather_chunks(self.actions, self.qpos, self.episodes, seg["samples"].view(torch.int32).view(B, 2),
+                                                     *self._stats, Q)
+            depth = tuple(self._gather_frames(kind, seg, flips, B * self.K, B, nontemporal) for kind in self.kinds[1:])
+        return (image, qpos, action, is_pad) + clouds + depth
+
+    def _gather_frames(self, kind, seg, flips, flip0, B, nontemporal):
+        """the one launch of a batch's frames of `kind`; `flips`: the batch's flags (a store with twins), this kind's from `flip0`"""
+        from . import ops
+        out = torch.empty((B, len(kind.cams)) + ((1,) if kind.is_depth else ()) + kind.shape, dtype=kind.torch_dtype, device=self.arena.device)
+        # the mirrored gather's aligned form also states rows of whole 16- / 8-pixel groups
+        aligned = kind.aligned if not self.has_twins or kind.shape[1] % kind.row_unit == 0 else 0
+        aligned = 2 if (nontemporal and aligned) else aligned
+        if self.has_twins:
+            H, W = kind.shape[:2]
+            ops.gather_frames_mirror(self.arena, seg[kind.segment], flips[flip0:flip0 + B * len(kind.cams)], H, W, kind.px_bytes, out=out,
+                                     aligned=aligned)
+        else:
+            ops.gather_frames(self.arena, seg[kind.segment], kind.frame_bytes, out=out, aligned=aligned)
+        return out
+
+    def replay_batch(self, local_episode, steps):
+        """the steps ``steps`` of ONE stored episode in the layout the policy's inference call takes, on the current stream of
+        the store's device: (image u8 [b, K, H, W, 3], qpos f32 [b, S] z-scored[, depth uint16 [b, Kd, 1, H, W]]) -- what
+        ``EpisodeReplay`` yields for these steps, bit for bit.  The two gathers of ``gather`` serve it (the qpos rows come from
+        ``gather_chunks`` with a chunk of one step, which is dropped)."""
+        steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+        if len(steps) * max(self.K, self.Kd) > 65535:
+            raise ValueError(f"DeviceEpisodeStore.replay_batch: {len(steps)} steps of {max(self.K, self.Kd)} cameras are more than "
+                             "the 65535 items of one frame gather")
+        out = self.gather(np.full(len(steps), int(local_episode), dtype=np.int64), steps, 1)
+        return (out[0], out[1]) + tuple(out[4:])
+
+    def loader(self, episode_ids, episode_len, chunk_size, batch_sampler):
+        return DeviceBatchLoader(self, episode_ids, episode_len, chunk_size, batch_sampler)
+
+
+class DeviceEpisodeReplay:
+    """``EpisodeReplay`` out of a ``DeviceEpisodeStore``: one stored episode (``episode_id`` as the store was given it) in time
+    order, ``batch`` replayed steps at a time (the last batch ragged), only every ``stride``-th step.  The same iterable with the
+    same attributes -- ``.T``, ``.steps``, ``.is_sim``, ``.actions`` (host [T, A] f32 in file units, copied from the device when
+    first asked for), ``__len__`` -- and the tensors it yields are bit for bit those ``EpisodeReplay`` yields for the same file,
+    batch and stride, but already on the device (``on_device``): no file is opened and nothing is pinned or copied from the host.
+    ``.actions_device``: the episode's action rows [T, A] f32, a view of the store's."""
+
+    on_device = True
+
+    def __init__(self, store, episode_id, batch, stride=1):
+        self.store, self.batch, self.stride = store, int(batch), int(stride)
+        if self.batch < 1 or self.stride < 1:
+            raise ValueError(f"batch {batch} and stride {stride} must be at least 1")
+        if int(episode_id) not in store._local_of:
+            raise ValueError(f"DeviceEpisodeReplay: episode {episode_id} is not in the store (it holds {store.episode_ids})")
+        cams = max(store.K, store.Kd)
+        if self.batch * cams > 65535:
+            raise ValueError(f"DeviceEpisodeReplay: a batch of {self.batch} steps of {cams} cameras is more than the 65535 items of "
+                             f"one frame gather: at most {65535 // cams}")
+        self.episode_id = int(episode_id)
+        self.local = store._local_of[self.episode_id]
+        self.dataset_path = store.paths[self.local]
+        self.T = int(store.T[self.local])
+        self.is_sim = bool(store.is_sim[self.local])
+        self.steps = list(range(0, self.T, self.stride))
+        row0 = int(store.row0[self.local])
+        self.actions_device = store.actions[row0:row0 + self.T]
+        self._actions = None
+
+    @property
+    def actions(self):
+        if self._actions is None:
+            self._actions = np.ascontiguousarray(self.actions_device.cpu().numpy(), dtype=np.float32)
+        return self._actions
+
+    def __len__(self):
+        return (len(self.steps) + self.batch - 1) // self.batch
+
+    def __iter__(self):
+        for b0 in range(0, len(self.steps), self.batch):
+            yield self.store.replay_batch(self.local, self.steps[b0:b0 + self.batch])
+
+
+class DeviceBatchLoader:
+    """The iterable ``DeviceEpisodeStore.loader`` returns: what a ``DataLoader`` over an ``EpisodicDataset`` of ``episode_ids`` /
+    ``episode_len`` / ``chunk_size`` with this ``batch_sampler`` delivers, as device tensors.  Exactly one index batch is drawn
+    from the sampler per batch delivered, when it is asked for (no look-ahead): samplers that share a generator, as the train and
+    validation samplers of ``load_data`` do, see the same stream of draws as on the host path with ``num_workers=0``."""
+
+    on_device = True
+
+    def __init__(self, store, episode_ids, episode_len, chunk_size, batch_sampler):
+        self.store = store
+        ids = [int(i) for i in episode_ids]
+        self.episode_ids = ids                 # as the store was given them (train_bc replays the validation loader's)
+        missing = [i for i in ids if i not in store._local_of]
+        if missing:
+            raise ValueError(f"DeviceBatchLoader: episodes {missing} are not in the store")
+        self.local = np.asarray([store._local_of[i] for i in ids], dtype=np.int64)
+        self.episode_len = [int(n) for n in episode_len]
+        if len(self.episode_len) != len(ids) or np.any(store.T[self.local] != np.asarray(self.episode_len)):
+            raise ValueError("DeviceBatchLoader: episode_len does not match the stored episodes")
+        # padded_action[:chunk_size] of a max_episode_len-row table (EpisodicDataset.__getitem__)
+        self.Q = min(int(chunk_size), max(self.episode_len))
+        self.batch_sampler = iter(batch_sampler)
+
+    def locate(self, indices):
+        """flat dataset indices -> (the store's episode numbers, start_ts), as ``EpisodicDataset._locate_transition``"""
+        ei, t = locate_transitions(indices, self.episode_len)
+        return self.local[ei], t
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        e, t = self.locate(next(self.batch_sampler))
+        return self.store.gather(e, t, self.Q)
