@@ -78,15 +78,21 @@ def stored_cloud_counts(root, base, path, T, N, pcd_ignore_mask=False):
 # gather's launcher cannot check for itself (actmi_op_gather_frames, `aligned`); ``src_block_off`` [sources, cams] int64, where each
 # camera's [T, *shape] block starts in the arena; ``block_off`` [episodes, cams], its source's, a twin's permuted by its spec;
 # ``flip`` [episodes, cams] uint8, 1 where a twin's camera is flipped along W.
+# A store that stays compressed (``store_compressed``): ``src_block_off`` of a compressed source is its STREAM block (at most T * L
+# bytes, ``stream_cap`` [sources, cams]; 0 for a source kept raw), ``mark_off`` [sources, cams] its mark block behind it and
+# ``marks_per_frame`` the M + 1 records a frame has there; all None without the option.
 _FrameKind = namedtuple("_FrameKind", "key segment is_depth px_bytes torch_dtype row_unit decode_as cams shape frame_bytes aligned "
-                                      "src_block_off block_off flip", defaults=((), None, 0, 0, None, None, None))
+                                      "src_block_off block_off flip stream_cap mark_off marks_per_frame",
+                        defaults=((), None, 0, 0, None, None, None, None, None, None))
 _KINDS = (_FrameKind("images", "frames", False, 3, torch.uint8, 16, "bgr"),
           _FrameKind("depth_images", "depth", True, 2, torch.uint16, 8, "u16"))
 
 # What the plan needs of one source file, from its headers: ``T``; ``compressed``; ``cloud_rows``, N of its stored cloud [T, N, 3] (0:
 # the store holds no clouds) and ``cloud_rgb_dtype``; ``frames``, per kind (``_KINDS``) the (shape, dtype) of a frame, None where the
 # file did not size it
-SourceHeader = namedtuple("SourceHeader", "T compressed cloud_rows cloud_rgb_dtype frames", defaults=(0, None, (None, None)))
+# ``packed`` (``store_compressed`` and a compressed source; else None): per kind None or (L per camera, marks per frame), L the padded
+# file length of a frame, what the entry's header gives
+SourceHeader = namedtuple("SourceHeader", "T compressed cloud_rows cloud_rgb_dtype frames packed", defaults=(0, None, (None, None), None))
 
 
 def _checked_frame_shape(kind, path, key, dtype, fshape):
@@ -103,14 +109,14 @@ def _checked_frame_shape(kind, path, key, dtype, fshape):
     return tuple(fshape[:2])
 
 
-def probe_sources(sources, cams, cloud_base=None, max_points=None):
+def probe_sources(sources, cams, cloud_base=None, max_points=None, store_compressed=False, rows_per_mark=1):
     """Opens every source file once -> [SourceHeader].  `cams`: per kind the camera names; `cloud_base`: the stored cloud's group, None
     without clouds.  The sizes come from the entries' headers (the first file's decoded frames for a compressed dataset: later
     compressed files are checked as they are decoded).  Refused here, before anything large is allocated, each ``ValueError`` naming
     the file: an empty episode, clouds that are not two [T, N, 3] arrays of T steps or store more than `max_points` rows
     (``_read_cloud``'s checks, from the headers), frames that are not T, depth that is not an unsigned integer of at most 16 bits, and
     cameras or files whose frame sizes differ -- checked as the walk reaches the file, so the first bad file is the one named."""
-    headers, sized = [], {}
+    headers, sized, marks_of = [], {}, {}
     for i, path in enumerate(sources):
         with open_episode(path) as root:
             compressed = bool(root.attrs.get("compress", False))
@@ -130,25 +136,43 @@ def probe_sources(sources, cams, cloud_base=None, max_points=None):
                     raise ValueError(f"{path}: the point cloud stores {xs[1]} rows, more than max_points {max_points} (no "
                                      "silent truncation: raise --max_points or down-sample the recording)")
                 N = int(xs[1])
-            frames = [None] * len(_KINDS)
+            frames, packed = [None] * len(_KINDS), [None] * len(_KINDS)
             for q, (kind, names) in enumerate(zip(_KINDS, cams)):
+                lens = []
                 for cam in names:
                     key = f"/observations/{kind.key}/{cam}"
                     shape, dtype = _entry_meta(root, key)
                     if shape[0] != T:
                         raise ValueError(f"{path}: {key} holds {shape[0]} frames for an episode of {T} steps")
                     if compressed:
+                        lens.append(int(shape[1]) if len(shape) == 2 else 0)
                         if i > 0:
                             continue                               # sized by the first episode's frames; checked as it is decoded
-                        fshape, dtype = imdecode_bgr(np.asarray(root[key][0])).shape, np.dtype(np.uint8)
+                        first = np.asarray(root[key][0])
+                        fshape, dtype = imdecode_bgr(first).shape, np.dtype(np.uint8)
+                        if store_compressed and kind.key not in marks_of:
+                            marks_of[kind.key] = _marks_per_frame(first, fshape[0], rows_per_mark)
                     else:
                         fshape = shape[1:]
                     fshape = _checked_frame_shape(kind, path, key, dtype, fshape)
                     if sized.setdefault(kind.key, fshape) != fshape:
                         raise ValueError(f"{path}: {key} frames are {fshape}, others {sized[kind.key]}: one batch shape only")
                     frames[q] = (fshape, dtype)
-        headers.append(SourceHeader(T, compressed, N, cdt, tuple(frames)))
+                if store_compressed and compressed and names and all(lens):
+                    packed[q] = (tuple(lens), marks_of[kind.key])
+        headers.append(SourceHeader(T, compressed, N, cdt, tuple(frames), tuple(packed) if any(p is not None for p in packed) else None))
     return headers
+
+
+def _marks_per_frame(buf, H, rows_per_mark):
+    """M + 1 for the frames of a block, from its first frame: the MCU rows of that frame's sampling mode (a frame of a mode with more
+    rows becomes a spill frame), or of 8-line rows when the parser refuses it"""
+    from . import ops
+    try:
+        mode = ops.jpeg_parse(buf)["mode"]
+    except ops.JpegUnsupported:
+        mode = "444"
+    return ops.jpeg_mark_count(H, mode, rows_per_mark) + 1
 
 
 def twin_camera_map(path, cams):
@@ -183,8 +207,9 @@ def _starts(lengths):
 # (every source stores them so), 1 float32 everywhere; ``cloud_rgb_bytes`` of one stored colour row.  Per episode: ``T``,
 # ``compressed``, ``row0`` (of its rows in ``actions`` / ``qpos``).  ``kinds``: those of ``all_kinds`` that have cameras; ``has_twins``;
 # ``has_clouds``.
+# ``src_packed`` [sources] bool: the source's frames stay compressed (None: the store was planned without ``store_compressed``).
 StoreLayout = namedtuple("StoreLayout", "all_kinds nbytes padding src_of twin src_T src_compressed src_N src_cloud_off src_row0 "
-                                        "cloud_rgb_fmt cloud_rgb_bytes T compressed row0 kinds has_twins has_clouds")
+                                        "cloud_rgb_fmt cloud_rgb_bytes T compressed row0 kinds has_twins has_clouds src_packed", defaults=(None,))
 
 
 def plan_store(headers, cams, src_of, twin_cams=None):
@@ -204,10 +229,21 @@ def plan_store(headers, cams, src_of, twin_cams=None):
     rgb_bytes = 3 if not nc or all(h.cloud_rgb_dtype == np.uint8 for h in headers) else 12
     shapes = [next((h.frames[q][0] for h in headers if h.frames[q] is not None), None) for q in range(len(_KINDS))]
     fbytes = [int(np.prod(s[:2])) * k.px_bytes if c else 0 for k, c, s in zip(_KINDS, cams, shapes)]
+    # ``store_compressed`` (a header says so with ``packed``): a camera or depth block of a compressed source is one stream block of
+    # at most T * L bytes, L the padded file length, and behind it a mark block of T * (M + 1) * 32 bytes; a source kept raw has its
+    # [T, frame] block and an empty mark block, so that every source has the same number of blocks
+    option = any(h.packed is not None for h in headers)
     blocks = []
-    for T, N in zip(src_T.tolist(), src_N.tolist()):
-        for fb, c in zip(fbytes, cams):
-            blocks += [T * fb] * len(c)
+    for h, T, N in zip(headers, src_T.tolist(), src_N.tolist()):
+        for q, (fb, c) in enumerate(zip(fbytes, cams)):
+            pk = h.packed[q] if h.packed is not None else None
+            for k in range(len(c)):
+                if not option:
+                    blocks.append(T * fb)
+                elif pk is None:
+                    blocks += [T * fb, 0]
+                else:
+                    blocks += [T * pk[0][k], T * pk[1] * 32]
         blocks += [T * N * 12, T * N * rgb_bytes][:nc]
     offs, nbytes = arena_layout(blocks)
     ends = [int(o) + int(b) for o, b in zip(offs, blocks)]
@@ -215,18 +251,26 @@ def plan_store(headers, cams, src_of, twin_cams=None):
     offs = offs.reshape(len(headers), -1)
     kinds, col = [], 0
     for q, (proto, c, shape, fb) in enumerate(zip(_KINDS, cams, shapes, fbytes)):
-        src_off = offs[:, col:col + len(c)].copy()
-        col += len(c)
+        width = (2 if option else 1) * len(c)
+        src_off = offs[:, col:col + width:2 if option else 1].copy()
+        extra = {}
+        if option and c:
+            cap = np.asarray([[T * h.packed[q][0][k] if h.packed is not None and h.packed[q] is not None else 0 for k in range(len(c))]
+                              for h, T in zip(headers, src_T.tolist())], dtype=np.int64)
+            mpf = next((h.packed[q][1] for h in headers if h.packed is not None and h.packed[q] is not None), 0)
+            extra = dict(stream_cap=cap, mark_off=offs[:, col + 1:col + width:2].copy(), marks_per_frame=int(mpf))
+        col += width
         off, flip = src_off[src_of], np.zeros((len(src_of), len(c)), dtype=np.uint8)
         for i, tw in enumerate(twin_cams):
             for k, (src_k, flipped) in enumerate(tw[q] if tw is not None else ()):
                 off[i, k], flip[i, k] = src_off[src_of[i], src_k], 1 if flipped else 0
         kinds.append(proto._replace(cams=tuple(c), shape=shape if c else None, frame_bytes=fb, aligned=1 if c and fb % 16 == 0 else 0,
-                                    src_block_off=src_off, block_off=off, flip=flip))
+                                    src_block_off=src_off, block_off=off, flip=flip, **extra))
     compressed, twin = [h.compressed for h in headers], [tw is not None for tw in twin_cams]
     return StoreLayout(tuple(kinds), nbytes, padding, src_of, twin, src_T, compressed, src_N, offs[:, col:].copy(), _starts(src_T),
                        0 if rgb_bytes == 3 else 1, rgb_bytes, src_T[src_of], [compressed[j] for j in src_of], _starts(src_T[src_of]),
-                       tuple(k for k in kinds if k.cams), any(twin), nc > 0)
+                       tuple(k for k in kinds if k.cams), any(twin), nc > 0,
+                       np.asarray([h.packed is not None for h in headers]) if option else None)
 
 
 class BatchTable:
@@ -259,7 +303,7 @@ def cloud_items(layout, e, t, cloud_n):
     return items
 
 
-def batch_table(layout, e, t, cloud_n=None):
+def batch_table(layout, e, t, cloud_n=None, extra=None):
     """The index table of the batch of samples (e[b], t[b]), int64 arrays: ``frames`` and ``depth``, the arena byte offset of every
     camera's frame; ``samples``, the (e, t) pairs as int32; with twins ``flips``, a flag per frame and depth item packed eight to a
     word; with clouds ``cloud_items``."""
@@ -271,6 +315,8 @@ def batch_table(layout, e, t, cloud_n=None):
         seg["flips"][:len(flags)] = flags
     if layout.has_clouds:
         seg["cloud_items"] = cloud_items(layout, e, t, cloud_n)
+    if extra:                                                         # a compressed store: the batch's JPEG records and their marks
+        seg.update(extra)
     return BatchTable(seg)
 
 
@@ -289,6 +335,9 @@ class DeviceEpisodeStore:
     (``NotImplementedError``), what ``probe_sources`` and ``twin_camera_map`` refuse, and a dataset larger than the budget
     (``MemoryError`` naming both numbers).  ``budget_bytes`` None: the device's free memory now minus ``DEVICE_STORE_RESERVE_BYTES``.
     ``device_decode`` changes neither what the arena holds nor which error a bad file raises (``_decode_on_device``).
+    ``store_compressed`` (with ``device_decode``): the arena holds the entropy segments and, per frame, the marks of one index pass
+    (actmi_op_jpeg_index) instead of the decoded frames; a batch is decoded by actmi_op_jpeg_decode_marked and is bit for bit the
+    batch of the other stores.  Frames the device does not take stay raw in a spill tensor per kind (``_load_packed``).
 
     Every rank of a data-parallel run holds its own full store."""
 
@@ -296,8 +345,13 @@ class DeviceEpisodeStore:
 
     def __init__(self, dataset_path_list, episode_ids, camera_names, norm_stats, device, depth_camera_names=None, use_depth=False,
                  budget_bytes=None, use_pcd=False, policy_class="ACT", stage_bytes=64 << 20, pointcloud_names=None, max_points=None,
-                 pcd_ignore_mask=False, device_decode=False, decode_frames=256):
+                 pcd_ignore_mask=False, device_decode=False, decode_frames=256, store_compressed=False, rows_per_mark=1):
         self.device_decode, self.decode_frames = bool(device_decode), int(decode_frames)
+        self.store_compressed, self.rows_per_mark = bool(store_compressed), int(rows_per_mark)
+        if self.store_compressed and not self.device_decode:
+            raise ValueError("store_compressed keeps the frames the device decodes: it needs device_decode (and device_dataset)")
+        if self.store_compressed and self.rows_per_mark < 1:
+            raise ValueError("store_compressed: rows_per_mark must be at least 1")
         self.pointcloud_names = list(pointcloud_names) if pointcloud_names else []
         self.has_clouds = bool(use_pcd) and bool(self.pointcloud_names)
         if self.has_clouds and len(self.pointcloud_names) != 1:
@@ -341,7 +395,10 @@ class DeviceEpisodeStore:
         self.device, self.stage_bytes = device, int(stage_bytes)
         cams = (tuple(self.camera_names), tuple(self.depth_camera_names) if self.use_depth else ())
         self._cloud_base = f"/observations/pointcloud/{self.pointcloud_names[0]}" if self.has_clouds else None
-        headers = probe_sources(self.sources, cams, self._cloud_base, self.max_points)
+        headers = probe_sources(self.sources, cams, self._cloud_base, self.max_points, self.store_compressed, self.rows_per_mark)
+        if self.store_compressed and not all(h.packed is not None and all(p is not None for p, c in zip(h.packed, cams) if c) for h in headers):
+            raise NotImplementedError("store_compressed: every source must be a compressed episode (a store of compressed and raw "
+                                      "sources is planned by plan_store but not loaded); drop --store_compressed")
         self.layout = lay = plan_store(headers, cams, [where[s] for s in srcs],
                                        [twin_camera_map(p, cams) if tw else None for p, tw in zip(self.paths, self.twin)])
         self.kinds, (img, dep) = lay.kinds, lay.all_kinds
@@ -369,7 +426,8 @@ class DeviceEpisodeStore:
         from . import ops
         lay, dev = self.layout, torch.device(self.device)
         t_begin = time.perf_counter()
-        self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        # a compressed store's stream blocks are filled only as far as the segments reach, and a spill frame's marks not at all
+        self.arena = (torch.zeros if self.store_compressed else torch.empty)(self.nbytes, dtype=torch.uint8, device=dev)
         for a, b in lay.padding:                                      # the padding between blocks is zero: two stores of one
             self.arena[a:b].zero_()                                   # dataset hold the same bytes everywhere
         stage = max(self.stage_bytes, self.frame_bytes, self.depth_bytes, int(lay.src_N.max()) * 12 if self.has_clouds else 0)
@@ -379,7 +437,8 @@ class DeviceEpisodeStore:
         self.decode_stats = {"device": 0, "host": 0}
         self.bus_bytes = 0                                            # bytes of frames and clouds that crossed to the device
         self._decoders, self._pending, self._jpeg_stream = {}, [], None
-        if self.device_decode and any(lay.src_compressed):
+        self._init_packed()
+        if self.device_decode and any(lay.src_compressed) and not self.store_compressed:
             self._jpeg_stream = torch.empty(stage, dtype=torch.uint8, device=dev)
         actions, qposes, sims = [], [], []
         loaded = set()
@@ -420,7 +479,11 @@ class DeviceEpisodeStore:
                              f"values for episodes of {self.A} / {self.S}")
         torch.cuda.synchronize(dev)
         self._pin = self._pin_ev = None                               # the staging buffers are the load's alone
-        self._decoders = self._jpeg_stream = None                     # and so are the decoder's workspace and stream buffer
+        self._jpeg_stream = None                                      # and so are the decoder's workspace and stream buffer
+        if self.store_compressed:
+            self._seal_packed()                                       # a compressed store keeps its decoders: every batch decodes
+        else:
+            self._decoders = None
         self.load_seconds = time.perf_counter() - t_begin
         self._host, self._host_ev, self._slot = [None] * self.RING, [None] * self.RING, 0
 
@@ -430,8 +493,12 @@ class DeviceEpisodeStore:
         for kind in self.kinds:
             for k, cam in enumerate(kind.cams):
                 key = f"/observations/{kind.key}/{cam}"
-                self._load_block(root[key], kind, T, compressed, int(kind.src_block_off[j, k]), f"{path}: {key}")
+                if self.store_compressed:
+                    self._load_packed(root[key], kind, T, j, k, f"{path}: {key}")
+                else:
+                    self._load_block(root[key], kind, T, compressed, int(kind.src_block_off[j, k]), f"{path}: {key}")
         self._finish_device_decode()
+        self._finish_index()
         if self.has_clouds:
             self._load_clouds(root, j)
 
@@ -583,14 +650,227 @@ class DeviceEpisodeStore:
                 k += 1
         self._pending = []
 
+    # ---- a store that stays compressed (store_compressed) ---------------------------------------------------------------
+    def _init_packed(self):
+        """per kind the host tables of a compressed store, one row per stored frame (source j, camera k, step t at
+        ``_frame_row(q, j, k) + t``): its JPEG record (segment offset in the arena, length, restart interval, table set), the index of
+        its mark 0 among the arena's 32-byte words, its sampling mode (-1: a spill frame) and its row in the spill tensor"""
+        from . import ops
+        self._ptab, self._spill_host, self._spill, self._index_pending = [], [], [], []
+        self.stream_bytes_used, self._sticky, self._scratch = 0, None, {}
+        if not self.store_compressed:
+            return
+        lay = self.layout
+        for kind in lay.all_kinds:
+            n = int(lay.src_T.sum()) * len(kind.cams)
+            self._ptab.append(dict(rec=np.zeros(n, dtype=ops.jpeg_frame_dtype()), first=np.zeros(n, dtype=np.int64),
+                                   mode=np.full(n, -1, dtype=np.int8), spill=np.full(n, -1, dtype=np.int64)))
+            self._spill_host.append([])
+        # which of its source's cameras an episode's camera shows (a twin's are permuted): the column of its block
+        self._src_cam = [np.asarray([[int(np.nonzero(kind.src_block_off[lay.src_of[i]] == kind.block_off[i, k])[0][0])
+                                      for k in range(len(kind.cams))] for i in range(len(lay.src_of))], dtype=np.int64).reshape(len(lay.src_of), len(kind.cams))
+                         for kind in lay.all_kinds]
+
+    def _frame_row(self, q, j, k):
+        lay = self.layout
+        return lay.src_row0[j] * len(lay.all_kinds[q].cams) + k * lay.src_T[j]
+
+    def _load_packed(self, entry, kind, T, j, k, where):
+        """one camera's block of a compressed store: the entropy segments of the frames the parser accepts at the store's size go
+        back to back through the staging pair into the stream block, one index launch per up to ``decode_frames`` frames writes their
+        marks into the mark block; the other frames (refused by the parser, of another size or with more MCU rows than the block
+        has marks for, a segment larger than the staging buffer or than what is left of the block) are spill frames."""
+        from . import ops
+        q = self.layout.all_kinds.index(kind)
+        tab, fb = self._ptab[q], kind.frame_bytes
+        H, W = kind.shape[:2]
+        dec = self._decoders.get((H, W))
+        if dec is None:
+            dec = self._decoders[(H, W)] = ops.JpegDecoder(self.device, H, W, max_frames=self.decode_frames)
+        row0 = int(self._frame_row(q, j, k))
+        s0, cap = int(kind.src_block_off[j, k]), int(kind.stream_cap[j, k])
+        m0, mpf = int(kind.mark_off[j, k]), int(kind.marks_per_frame)
+        stage_cap, cursor = int(self._pin[0].numel()), 0
+        per = max(1, stage_cap // max(1, cap // max(T, 1)))
+        for t0 in range(0, T, per):
+            piece = np.asarray(entry[t0:min(T, t0 + per)])
+            todo = {}
+            for i, buf in enumerate(piece):
+                t, info = t0 + i, None
+                if piece.ndim == 2 and piece.dtype == np.uint8:
+                    try:
+                        info = dec.parse(buf)
+                    except ops.JpegUnsupported:
+                        info = None
+                if info is not None and ((info["H"], info["W"]) != (H, W) or info["seg_len"] > stage_cap or
+                                         ops.jpeg_mark_count(H, info["mode"], self.rows_per_mark) + 1 > mpf or
+                                         cursor + sum(x[2]["seg_len"] for v in todo.values() for x in v) + info["seg_len"] > cap):
+                    info = None
+                if info is None:
+                    self._spill_frame(q, row0 + t, buf, kind, where)
+                else:
+                    todo.setdefault(info["mode"], []).append((t, buf, info))
+            for mode, items in todo.items():
+                k0 = 0
+                while k0 < len(items):                                # as many frames as the staging buffer and one launch hold
+                    k1, nbytes = k0, 0
+                    while k1 < len(items) and k1 - k0 < dec.max_frames and nbytes + items[k1][2]["seg_len"] <= stage_cap:
+                        nbytes += items[k1][2]["seg_len"]
+                        k1 += 1
+                    part = items[k0:k1]
+                    rows = np.asarray([row0 + t for t, _b, _i in part], dtype=np.int64)
+                    lens = np.asarray([info["seg_len"] for _t, _b, info in part], dtype=np.int64)
+                    rec = tab["rec"]
+                    rec["seg_len"][rows] = lens
+                    rec["seg_off"][rows] = s0 + cursor + np.concatenate([[0], np.cumsum(lens)[:-1]])
+                    rec["restart_interval"][rows] = [info["restart_interval"] for _t, _b, info in part]
+                    rec["table_set"][rows] = [dec.table_index(info["tables"]) for _t, _b, info in part]
+                    tab["first"][rows] = [(m0 + t * mpf * 32) // 32 for t, _b, _i in part]
+                    tab["mode"][rows] = ops.JPEG_MODES[mode]
+
+                    def fill(view, part=part, lens=lens):
+                        o = 0
+                        for (_t, buf, info), n in zip(part, lens):
+                            view[o:o + n] = buf[info["seg_off"]:info["seg_off"] + n]
+                            o += int(n)
+                    if nbytes:
+                        self._stage(s0 + cursor, nbytes, fill)
+                    cursor += nbytes
+                    _marks, status = dec.index(self.arena, rec[rows], mode, marks=self.arena[:self.nbytes // 32 * 32], first=tab["first"][rows],
+                                               rows_per_mark=self.rows_per_mark)
+                    self._index_pending.append((status, q, rows, [b for _t, b, _i in part], kind, where))
+                    k0 = k1
+        self.stream_bytes_used += cursor
+
+    def _spill_frame(self, q, row, buf, kind, where):
+        """a frame the device does not take: decoded by ``imdecode_bgr`` (a bad file raises what it raises today), kept raw"""
+        piece = imdecode_bgr(buf)[None]
+        if kind.is_depth:
+            if piece.ndim == 4:
+                piece = piece[..., 0]
+            piece = piece.astype(np.uint16, copy=False)
+        if piece.shape != (1,) + tuple(kind.shape):
+            raise ValueError(f"{where}: frames {piece.dtype} {piece.shape[1:]}, the store was sized for {tuple(kind.shape)}")
+        tab = self._ptab[q]
+        tab["mode"][row], tab["spill"][row] = -1, len(self._spill_host[q])
+        self._spill_host[q].append(np.ascontiguousarray(piece).reshape(-1).view(np.uint8))
+        self.decode_stats["host"] += 1
+
+    def _finish_index(self):
+        """the statuses of a source file's index launches, read back once; a frame whose status is not 0 becomes a spill frame"""
+        if not self._index_pending:
+            return
+        status = torch.cat([p[0] for p in self._index_pending]).cpu().numpy()
+        n = 0
+        for _st, q, rows, bufs, kind, where in self._index_pending:
+            for row, buf in zip(rows, bufs):
+                if status[n]:
+                    self._spill_frame(q, int(row), buf, kind, where)
+                else:
+                    self.decode_stats["device"] += 1
+                n += 1
+        self._index_pending = []
+
+    def _seal_packed(self):
+        """after the load: the spill tensors, the sticky status word and the decoders' workspaces (the largest sampling mode's,
+        ``decode_frames`` slots), allocated once; the spill frames count against the budget like the arena"""
+        from . import ops
+        dev = self.arena.device
+        for kind, frames in zip(self.layout.all_kinds, self._spill_host):
+            flat = np.stack(frames) if frames else np.zeros((0, max(kind.frame_bytes, 1)), dtype=np.uint8)
+            self._spill.append(torch.from_numpy(flat).to(dev))
+        self._spill_host = None
+        self._sticky = torch.zeros(1, dtype=torch.int32, device=dev)
+        for dec in self._decoders.values():
+            need = max(dec.workspace_bytes(m) for m in ops.JPEG_MODES)
+            dec._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        spill = sum(int(s.numel()) for s in self._spill)
+        if self.nbytes + spill > self.budget_bytes:
+            raise MemoryError(f"DeviceEpisodeStore: the compressed store and its spill frames need {self.nbytes + spill} bytes on the "
+                              f"device, the budget is {self.budget_bytes} bytes: train without --store_compressed, or raise --device_dataset_gb")
+
+    def check_decoded(self):
+        """reads the sticky status word of every batch decoded so far (one small copy; call it where the step synchronises anyway):
+        ``RuntimeError`` naming the status if a marked decode flagged a frame"""
+        if self._sticky is None:
+            return
+        from . import ops
+        v = int(self._sticky.item())
+        if v:
+            raise RuntimeError(f"DeviceEpisodeStore: a batch of the compressed store was decoded with status {v} ({ops.JPEG_STATUS.get(v, '?')})")
+
+    def _packed_segments(self, e, t):
+        """the JPEG side of a batch's index table: per kind and sampling mode present the records (dst_off = item * frame bytes) and
+        the mark indices of the compressed items, with twins the scratch offsets of all items -> (segments, per kind the launches
+        (mode, records' name, firsts' name) and the (items, spill rows) of the spill items)"""
+        from . import ops
+        lay, seg, plan = self.layout, {}, []
+        modes = {v: m for m, v in ops.JPEG_MODES.items()}
+        j = lay.src_of[e]
+        for q, kind in enumerate(lay.all_kinds):
+            K = len(kind.cams)
+            if not K:
+                plan.append(([], None))
+                continue
+            ksrc = self._src_cam[q][e]                                                    # [B, K]
+            rows = (lay.src_row0[j][:, None] * K + ksrc * lay.src_T[j][:, None] + t[:, None]).reshape(-1)
+            tab = self._ptab[q]
+            mode = tab["mode"][rows]
+            launches = []
+            for m in np.unique(mode[mode >= 0]):
+                items = np.nonzero(mode == m)[0]
+                rec = tab["rec"][rows[items]]
+                rec["dst_off"] = items * kind.frame_bytes
+                seg[f"jpeg{q}_{m}"], seg[f"first{q}_{m}"] = rec, tab["first"][rows[items]]
+                launches.append((modes[int(m)], f"jpeg{q}_{m}", f"first{q}_{m}"))
+            sp = np.nonzero(mode < 0)[0]
+            if self.has_twins:
+                seg[f"scratch{q}"] = np.arange(len(rows), dtype=np.int64) * kind.frame_bytes
+            plan.append((launches, (sp, tab["spill"][rows[sp]]) if len(sp) else None))
+        return seg, plan
+
+    def _decode_frames(self, q, kind, seg, plan, flips, flip0, B, nontemporal):
+        """the frames of `kind` of a batch of a compressed store: one marked decode per sampling mode present, straight into the
+        batch tensor -- with twins into a persistent scratch block of its shape, which the mirrored gather then reads"""
+        from . import ops
+        dev = self.arena.device
+        K, fb = len(kind.cams), kind.frame_bytes
+        out = torch.empty((B, K) + ((1,) if kind.is_depth else ()) + kind.shape, dtype=kind.torch_dtype, device=dev)
+        target = out
+        if self.has_twins:
+            if q not in self._scratch or self._scratch[q].numel() < B * K * fb:
+                self._scratch[q] = torch.empty(B * K * fb, dtype=torch.uint8, device=dev)
+            target = self._scratch[q][:B * K * fb]
+        H, W = kind.shape[:2]
+        dec = self._decoders[(H, W)]
+        launches, spill = plan
+        marks = self.arena[:self.nbytes // 32 * 32]
+        for mode, rec, first in launches:
+            dec.decode_marked(self.arena, seg[rec].view(torch.uint8), marks, seg[first], mode, kind.decode_as, target, sticky=self._sticky,
+                              rows_per_mark=self.rows_per_mark)
+        if spill is not None:                                         # rare, and plumbing
+            items, srows = (torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in spill)
+            target.view(torch.uint8).view(B * K, fb)[items] = self._spill[q][srows]
+        if self.has_twins:
+            aligned = kind.aligned if kind.shape[1] % kind.row_unit == 0 else 0
+            aligned = 2 if (nontemporal and aligned) else aligned
+            ops.gather_frames_mirror(target, seg[f"scratch{q}"], flips[flip0:flip0 + B * K], H, W, kind.px_bytes, out=out, aligned=aligned)
+        return out
+
     # ---- batches --------------------------------------------------------------------------------------------------
     def device_bytes(self):
         """bytes of device memory the store holds"""
+        packed = 0
+        if self.store_compressed:
+            packed = sum(int(s.numel()) for s in self._spill) + 4 + sum(int(s.numel()) for s in self._scratch.values()) + \
+                sum(int(d._ws.numel()) + (int(d._tables.numel()) if d._tables is not None else 0) for d in self._decoders.values())
         return int(self.arena.numel() + self.actions.numel() * 4 + self.qpos.numel() * 4 + self.episodes.numel() +
-                   sum(s.numel() * 4 for s in self._stats))
+                   sum(s.numel() * 4 for s in self._stats)) + packed
 
     def frame_offsets(self, local_episode, t):
         """byte offsets into the arena of the frames of samples (local_episode[b], t[b]) -> ([B, K], [B, Kd]) int64"""
+        if self.store_compressed:
+            raise ValueError("DeviceEpisodeStore.frame_offsets: a compressed store holds no decoded frames to point at")
         e, t = np.asarray(local_episode, dtype=np.int64), np.asarray(t, dtype=np.int64)
         return tuple(k.block_off[e] + t[:, None] * k.frame_bytes for k in self.layout.all_kinds)
 
@@ -627,7 +907,8 @@ class DeviceEpisodeStore:
         if e.min() < 0 or e.max() >= len(self.paths) or t.min() < 0 or np.any(t >= self.T[e]):
             raise IndexError("DeviceEpisodeStore.gather: a sample outside the stored episodes")
         lay = self.layout
-        table = batch_table(lay, e, t, self.cloud_n)
+        extra, plan = self._packed_segments(e, t) if self.store_compressed else (None, None)
+        table = batch_table(lay, e, t, self.cloud_n, extra)
         with torch.cuda.device(self.arena.device):
             seg = table.slices(self._upload(table.host))
             clouds = ()
@@ -639,10 +920,16 @@ class DeviceEpisodeStore:
                 clouds = ops.gather_clouds(self.arena, seg["cloud_items"], P, self.cloud_rgb_fmt, mirror=mirror,
                                            aligned=(2 if nontemporal else 1) if P % 4 == 0 else 0)
             flips = seg["flips"].view(torch.uint8) if self.has_twins else None
-            image = self._gather_frames(self.kinds[0], seg, flips, 0, B, nontemporal)
+            if self.store_compressed:
+                image = self._decode_frames(0, self.kinds[0], seg, plan[0], flips, 0, B, nontemporal)
+            else:
+                image = self._gather_frames(self.kinds[0], seg, flips, 0, B, nontemporal)
             qpos, action, is_pad = ops.gather_chunks(self.actions, self.qpos, self.episodes, seg["samples"].view(torch.int32).view(B, 2),
                                                      *self._stats, Q)
-            depth = tuple(self._gather_frames(kind, seg, flips, B * self.K, B, nontemporal) for kind in self.kinds[1:])
+            if self.store_compressed:
+                depth = tuple(self._decode_frames(1, kind, seg, plan[1], flips, B * self.K, B, nontemporal) for kind in self.kinds[1:])
+            else:
+                depth = tuple(self._gather_frames(kind, seg, flips, B * self.K, B, nontemporal) for kind in self.kinds[1:])
         return (image, qpos, action, is_pad) + clouds + depth
 
     def _gather_frames(self, kind, seg, flips, flip0, B, nontemporal):

@@ -2633,7 +2633,7 @@ def knn_ksweep(idx, dist, n, actions, off, target, mean=None, std=None, want_par
 JPEG_MODES = {"gray": 0, "444": 1, "422": 2, "420": 3}
 JPEG_FORMS = {"bgr": 0, "rgb": 1, "u16": 2}
 JPEG_STATUS = {0: "ok", 1: "overrun", 2: "invalid code", 3: "coefficient index out of range", 4: "restart marker missing or out of sequence",
-               5: "destination outside the buffer", 6: "table set outside the array"}
+               5: "destination outside the buffer", 6: "table set outside the array", 7: "mark malformed or missed by its interval"}
 _JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
 
@@ -2654,6 +2654,12 @@ def jpeg_frame_dtype():
     import numpy as np
     return np.dtype([("seg_off", np.int64), ("dst_off", np.int64), ("seg_len", np.int32), ("restart_interval", np.int32),
                      ("table_set", np.int32), ("reserved", np.int32)])
+
+
+def jpeg_mark_dtype():
+    """actmi_jpeg_mark as a numpy structured dtype (32 bytes)"""
+    import numpy as np
+    return np.dtype([("byte_off", np.int64), ("bit", np.int32), ("pred", np.int32, 3), ("togo", np.int32), ("rst", np.int32)])
 
 
 def jpeg_out_shape(H, W, form):
@@ -2852,8 +2858,15 @@ class _JpegRefBits:
         nb = (min(self.cur, self.nbits) + 7) // 8
         return self.after[nb - 1] if nb else self.start
 
+    def mark_pos(self):
+        """the position convention of actmi_jpeg_mark -> (byte_off, bit): data byte cur // 8 of this load begins where the one
+        before it ends (``after``), or at ``start``; with every data bit consumed that is the offset of what follows"""
+        cur = min(self.cur, self.nbits)
+        k = cur // 8
+        return (self.after[k - 1] if k else self.start), cur % 8
 
-def jpeg_decode_ref(buf, form="bgr", with_status=False, info=None):
+
+def jpeg_decode_ref(buf, form="bgr", with_status=False, info=None, _at_mcu=None):
     """numpy statement of ``jpeg_decode`` for one file (the definition in actmi.h, step by step; needs no library): -> the frame, u8
     [H, W, 3] (``form`` "bgr" or "rgb") or uint16 [H, W] ("u16").  ``with_status``: -> (frame, status) with the status the op gives
     (a frame whose status is not 0 holds unspecified pixels); without it a damaged stream raises ``ValueError``.  ``info``: what
@@ -2896,6 +2909,8 @@ def jpeg_decode_ref(buf, form="bgr", with_status=False, info=None):
     for m in range(mx * my):
         if status:
             break
+        if _at_mcu is not None:                                     # jpeg_marks_ref: the state before any restart handling
+            _at_mcu(m, rd, pred, togo, rst)
         if ri > 0 and togo == 0:
             p = rd.byte_pos()
             if rd.nbits - rd.cur >= 8 or p + 1 >= len(seg) or seg[p] != 0xFF or seg[p + 1] != 0xD0 + rst:
@@ -2938,6 +2953,8 @@ def jpeg_decode_ref(buf, form="bgr", with_status=False, info=None):
                             k += 16
                     if not status and rd.over:
                         status = 1
+    if _at_mcu is not None and not status:
+        _at_mcu(mx * my, rd, pred, togo, rst)
     if status and not with_status:
         raise ValueError(f"jpeg_decode_ref: damaged entropy segment ({JPEG_STATUS[status]})")
 
@@ -3002,6 +3019,34 @@ def jpeg_decode_ref(buf, form="bgr", with_status=False, info=None):
         out = np.stack([B, G, R] if form == "bgr" else [R, G, B], axis=-1).astype(np.uint8)
     out = np.ascontiguousarray(out)
     return (out, status) if with_status else out
+
+
+def jpeg_marks_ref(buf, rows_per_mark=1, info=None):
+    """numpy statement of ``jpeg_index`` for one file (the definition is at actmi_jpeg_mark in actmi.h): the walk of
+    ``jpeg_decode_ref`` -> (marks, status): ``jpeg_mark_dtype`` records [M + 1], M = ceil(my / rows_per_mark), mark j the scan's state
+    at the entry of the first MCU of row j * rows_per_mark, before any restart handling of it, mark M the state after the last MCU.
+    The marks of a file whose status is not 0 are unspecified (here: zero from the failing row on)."""
+    import numpy as np
+    R = int(rows_per_mark)
+    if R < 1:
+        raise ValueError("jpeg_marks_ref: rows_per_mark must be at least 1")
+    if info is None:
+        info = jpeg_parse(buf)
+    hmax, vmax = {"gray": (1, 1), "444": (1, 1), "422": (2, 1), "420": (2, 2)}[info["mode"]]
+    mx, my = -(-info["W"] // (8 * hmax)), -(-info["H"] // (8 * vmax))
+    M = -(-my // R)
+    marks = np.zeros(M + 1, dtype=jpeg_mark_dtype())
+
+    def at_mcu(m, rd, pred, togo, rst):
+        row, col = divmod(m, mx)
+        if col or (row % R and row != my):
+            return
+        k = M if row == my else row // R
+        marks[k]["byte_off"], marks[k]["bit"] = rd.mark_pos()
+        marks[k]["pred"][:len(pred)] = pred
+        marks[k]["togo"], marks[k]["rst"] = togo, rst
+    _, status = jpeg_decode_ref(buf, with_status=True, info=info, _at_mcu=at_mcu)
+    return marks, status
 
 
 def _jpeg_bytes(buf):
@@ -3097,6 +3142,79 @@ def jpeg_workspace_bytes(n, H, W, mode):
     return int(L.load().actmi_op_jpeg_workspace_bytes(int(n), int(H), int(W), JPEG_MODES[mode]))
 
 
+def jpeg_mark_count(H, mode, rows_per_mark=1):
+    """M: a frame of H lines has M + 1 marks"""
+    if int(rows_per_mark) < 1:
+        raise ValueError("jpeg marks: rows_per_mark must be at least 1")
+    my = -(-int(H) // (16 if mode == "420" else 8))
+    return -(-my // int(rows_per_mark))
+
+
+def _host_desc(stream, frames, tables, n_tables, status, H, W, mode, form="bgr", out=None, ws=None):
+    d = L.JpegDesc()
+    d.stream, d.stream_bytes, d.frames, d.tables, d.status = stream.ctypes.data, stream.size - 1, frames.ctypes.data, tables.ctypes.data, status.ctypes.data
+    if out is not None:
+        d.dst, d.dst_bytes, d.ws, d.ws_bytes = out.ctypes.data, out.nbytes, ws.ctypes.data, ws.nbytes
+    d.n, d.n_tables, d.H, d.W, d.mode, d.form = len(frames), n_tables, H, W, JPEG_MODES[mode], JPEG_FORMS[form]
+    return d
+
+
+def jpeg_index_host(bufs, rows_per_mark=1, infos=None):
+    """actmi_jpeg_index_host, the CPU twin of ``jpeg_index``: `bufs` JPEG files of one size and sampling mode -> (marks, status):
+    ``jpeg_mark_dtype`` records [n, M + 1] (``jpeg_marks_ref`` of every file whose status is 0), status int32 [n]"""
+    import numpy as np
+    sets = _JpegTableSets()
+    H, W, mode, stream, frames, _fb = _jpeg_plan(bufs, infos, "bgr", None, sets.index)
+    n, M = len(frames), jpeg_mark_count(H, mode, rows_per_mark)
+    tables = _aligned_u8(len(sets.sets) * jpeg_tables_dtype().itemsize)
+    tables[:] = sets.array()
+    status = np.full(n, -1, dtype=np.int32)
+    marks = np.zeros((n, M + 1), dtype=jpeg_mark_dtype())
+    first = np.arange(n, dtype=np.int64) * (M + 1)
+    d = _host_desc(stream, frames, tables, len(sets.sets), status, H, W, mode)
+    m = L.JpegMarks()
+    m.marks, m.n_marks, m.first, m.rows_per_mark = marks.ctypes.data, marks.size, first.ctypes.data, int(rows_per_mark)
+    L.check(L.load().actmi_jpeg_index_host(C.byref(d), C.byref(m)), None, "jpeg_index_host")
+    return marks, status
+
+
+def jpeg_decode_marked_host(bufs, marks, first=None, rows_per_mark=1, out=None, offsets=None, form="bgr", infos=None, ws=None, sticky=None):
+    """actmi_jpeg_decode_marked_host, the CPU twin of ``jpeg_decode_marked``: as ``jpeg_decode_host``, every frame entered at its
+    marks.  `marks`: ``jpeg_mark_dtype`` records, [n, M + 1] or any flat array with first[i] the index of frame i's mark 0.
+    ``sticky``: an int32 array of one word that receives the largest status.  -> (out, status)"""
+    import numpy as np
+    sets = _JpegTableSets()
+    H, W, mode, stream, frames, fb = _jpeg_plan(bufs, infos, form, offsets, sets.index)
+    n = len(frames)
+    marks = np.ascontiguousarray(marks, dtype=jpeg_mark_dtype())
+    if first is None:
+        if marks.ndim != 2 or marks.shape[0] != n:
+            raise ValueError("jpeg_decode_marked_host: marks must be [n, M + 1] when first is not given")
+        first = np.arange(n, dtype=np.int64) * marks.shape[1]
+    first = np.ascontiguousarray(first, dtype=np.int64)
+    if first.shape != (n,):
+        raise ValueError("jpeg_decode_marked_host: first must hold one index per frame")
+    if out is None:
+        if offsets is not None:
+            raise ValueError("jpeg_decode_marked_host: offsets name places in the caller's out")
+        out = np.empty((n,) + jpeg_out_shape(H, W, form), dtype=np.uint16 if form == "u16" else np.uint8)
+    elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous:
+        raise ValueError("jpeg_decode_marked_host: out must be a contiguous 1-D uint8 array")
+    if sticky is not None and (not isinstance(sticky, np.ndarray) or sticky.dtype != np.int32 or sticky.size != 1):
+        raise ValueError("jpeg_decode_marked_host: sticky must be an int32 array of one word")
+    if ws is None:
+        ws = _aligned_u8(jpeg_workspace_bytes(n, H, W, mode))
+    tables = _aligned_u8(len(sets.sets) * jpeg_tables_dtype().itemsize)
+    tables[:] = sets.array()
+    status = np.full(n, -1, dtype=np.int32)
+    d = _host_desc(stream, frames, tables, len(sets.sets), status, H, W, mode, form, out, ws)
+    m = L.JpegMarks()
+    m.marks, m.n_marks, m.first, m.rows_per_mark = marks.ctypes.data if marks.size else None, marks.size, first.ctypes.data, int(rows_per_mark)
+    m.sticky = sticky.ctypes.data if sticky is not None else None
+    L.check(L.load().actmi_jpeg_decode_marked_host(C.byref(d), C.byref(m)), None, "jpeg_decode_marked_host")
+    return out, status
+
+
 class JpegDecoder:
     """The device state of ``jpeg_decode`` for frames of one size: the workspace (``max_frames`` slots of the largest sampling mode
     met so far), the table sets met so far, deduplicated by content and uploaded when a new one appears, and one parse cache (the
@@ -3168,6 +3286,88 @@ class JpegDecoder:
                 L.check(lib.actmi_op_jpeg_decode(C.byref(d), L.current_stream_ptr()), None, "op_jpeg_decode")
         return status
 
+    def _marked_args(self, what, stream, frames, marks, first):
+        """the checks and uploads the two mark ops share -> (records on the device, n, first on the device)"""
+        import numpy as np
+        if stream.dtype != torch.uint8 or stream.dim() != 1 or stream.device != self.device or not stream.is_contiguous():
+            raise ValueError(f"JpegDecoder.{what}: stream must be a contiguous 1-D uint8 tensor on {self.device}")
+        if torch.is_tensor(frames):
+            if frames.dtype != torch.uint8 or frames.device != self.device or not frames.is_contiguous() or frames.numel() % 32:
+                raise ValueError(f"JpegDecoder.{what}: frames on the device are contiguous uint8 records of 32 bytes")
+            rec = frames
+        else:
+            rec = torch.from_numpy(np.ascontiguousarray(frames, dtype=jpeg_frame_dtype()).view(np.uint8).reshape(-1).copy()).to(self.device)
+        n = rec.numel() // 32
+        if marks.dtype != torch.uint8 or marks.device != self.device or not marks.is_contiguous() or marks.numel() % 32 or marks.data_ptr() % 8:
+            raise ValueError(f"JpegDecoder.{what}: marks must be a contiguous, 8-byte aligned uint8 tensor of 32-byte records on {self.device}")
+        if first is None:
+            raise ValueError(f"JpegDecoder.{what}: marks come with first, the index of every frame's mark 0")
+        if not torch.is_tensor(first):
+            first = torch.from_numpy(np.ascontiguousarray(first, dtype=np.int64)).to(self.device)
+        if first.dtype != torch.int64 or first.device != self.device or not first.is_contiguous() or first.numel() != n:
+            raise ValueError(f"JpegDecoder.{what}: first must hold one int64 index per frame on {self.device}")
+        if len(self._sets.sets) != self._uploaded:
+            self._tables = torch.from_numpy(self._sets.array()).to(self.device)
+            self._uploaded = len(self._sets.sets)
+        if self._tables is None:
+            raise ValueError("JpegDecoder: no table set (table_index gives the frames' indices)")
+        return rec, n, first
+
+    def index(self, stream, frames, mode, marks=None, first=None, rows_per_mark=1):
+        """actmi_op_jpeg_index: the entropy walk alone.  stream, frames as ``decode`` (frames may also be records on the device).
+        ``marks``: a uint8 tensor of 32-byte ``jpeg_mark_dtype`` records on the device with first[i] the index of frame i's mark 0;
+        without it one of [n, M + 1, 32] is made.  -> (marks, status int32 [n] on the device)"""
+        M = jpeg_mark_count(self.H, mode, rows_per_mark)
+        if marks is None:
+            n = frames.numel() // 32 if torch.is_tensor(frames) else len(frames)
+            marks = torch.zeros((n, M + 1, 32), dtype=torch.uint8, device=self.device)
+            first = torch.arange(n, dtype=torch.int64, device=self.device) * (M + 1)
+        rec, n, first = self._marked_args("index", stream, frames, marks, first)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if n == 0:
+            return marks, status
+        d, m = L.JpegDesc(), L.JpegMarks()
+        d.stream, d.stream_bytes, d.tables, d.n_tables = stream.data_ptr(), int(stream.numel()), self._tables.data_ptr(), self._uploaded
+        d.H, d.W, d.mode = self.H, self.W, JPEG_MODES[mode]
+        m.marks, m.n_marks, m.rows_per_mark = marks.data_ptr(), marks.numel() // 32, int(rows_per_mark)
+        lib = L.load()
+        with torch.cuda.device(self.device):
+            for i0 in range(0, n, self.max_frames):
+                d.frames, d.status, d.n = rec.data_ptr() + 32 * i0, status.data_ptr() + 4 * i0, min(self.max_frames, n - i0)
+                m.first = first.data_ptr() + 8 * i0
+                L.check(lib.actmi_op_jpeg_index(C.byref(d), C.byref(m), L.current_stream_ptr()), None, "op_jpeg_index")
+        return marks, status
+
+    def decode_marked(self, stream, frames, marks, first, mode, form, dst, sticky=None, rows_per_mark=1):
+        """actmi_op_jpeg_decode_marked: ``decode`` with every frame entered at its marks (what ``index`` wrote, with the same
+        ``rows_per_mark``).  ``sticky``: an int32 tensor of one word on the device that receives the largest status of the launches.
+        -> status int32 [n] on the device"""
+        rec, n, first = self._marked_args("decode_marked", stream, frames, marks, first)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if n == 0:
+            return status
+        if dst.device != self.device or not dst.is_contiguous():
+            raise ValueError(f"JpegDecoder: dst must be contiguous on {self.device}")
+        if sticky is not None and (sticky.dtype != torch.int32 or sticky.numel() != 1 or sticky.device != self.device):
+            raise ValueError(f"JpegDecoder.decode_marked: sticky must be an int32 tensor of one word on {self.device}")
+        need = self.workspace_bytes(mode)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        d, m = L.JpegDesc(), L.JpegMarks()
+        d.stream, d.stream_bytes, d.tables, d.n_tables = stream.data_ptr(), int(stream.numel()), self._tables.data_ptr(), self._uploaded
+        d.dst, d.dst_bytes, d.ws, d.ws_bytes = dst.data_ptr(), int(dst.numel() * dst.element_size()), self._ws.data_ptr(), int(self._ws.numel())
+        d.H, d.W, d.mode, d.form = self.H, self.W, JPEG_MODES[mode], JPEG_FORMS[form]
+        m.marks, m.n_marks, m.rows_per_mark = marks.data_ptr(), marks.numel() // 32, int(rows_per_mark)
+        m.sticky = sticky.data_ptr() if sticky is not None else None
+        lib = L.load()
+        with torch.cuda.device(self.device):
+            for i0 in range(0, n, self.max_frames):
+                d.frames, d.status, d.n = rec.data_ptr() + 32 * i0, status.data_ptr() + 4 * i0, min(self.max_frames, n - i0)
+                m.first = first.data_ptr() + 8 * i0
+                L.check(lib.actmi_op_jpeg_decode_marked(C.byref(d), C.byref(m), L.current_stream_ptr()), None, "op_jpeg_decode_marked")
+        return status
+
 
 def jpeg_decode(bufs, out=None, offsets=None, form="bgr", infos=None, device=None, decoder=None):
     """actmi_op_jpeg_decode: `bufs` JPEG files (1-D uint8 arrays or bytes) of one size and sampling mode, decoded on the device ->
@@ -3200,4 +3400,48 @@ def jpeg_decode(bufs, out=None, offsets=None, form="bgr", infos=None, device=Non
     dev_stream = pinned.to(device, non_blocking=True)
     status = decoder.decode(dev_stream, frames, mode, form, out)
     torch.cuda.current_stream(device).synchronize()                # the pinned staging is this call's alone
+    return out, status
+
+
+def _jpeg_device_call(what, bufs, infos, form, offsets, device, decoder):
+    """what ``jpeg_index`` and ``jpeg_decode_marked`` share: the plan, the decoder and the segments on the device"""
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    sets = decoder._sets if decoder is not None else _JpegTableSets()
+    H, W, mode, stream, frames, _fb = _jpeg_plan(bufs, infos, form, offsets, sets.index)
+    if decoder is None:
+        decoder = JpegDecoder(device, H, W, max_frames=min(len(frames), 256))
+        decoder._sets = sets
+    elif (decoder.H, decoder.W) != (H, W) or decoder.device != device:
+        raise ValueError(f"{what}: the decoder is for {decoder.H} x {decoder.W} frames on {decoder.device}")
+    return decoder, mode, torch.from_numpy(stream).to(device), frames
+
+
+def jpeg_index(bufs, infos=None, device=None, decoder=None, rows_per_mark=1):
+    """actmi_op_jpeg_index: `bufs` JPEG files of one size and sampling mode, their entropy segments walked once on the device ->
+    (marks, status): marks uint8 [n, M + 1, 32] on the device (``jpeg_mark_dtype`` records: ``jpeg_marks_ref`` of every file whose
+    status is 0), status int32 [n] on the device"""
+    decoder, mode, stream, frames = _jpeg_device_call("jpeg_index", bufs, infos, "bgr", None, device, decoder)
+    return decoder.index(stream, frames, mode, rows_per_mark=rows_per_mark)
+
+
+def jpeg_decode_marked(bufs, marks, first=None, rows_per_mark=1, out=None, offsets=None, form="bgr", infos=None, device=None, decoder=None,
+                       sticky=None):
+    """actmi_op_jpeg_decode_marked: ``jpeg_decode`` with every frame entered at its marks (uint8 [n, M + 1, 32] on the device, or any
+    block of records with first[i] the index of frame i's mark 0) -> (out, status)"""
+    if out is not None:
+        device = out.device
+    decoder, mode, stream, frames = _jpeg_device_call("jpeg_decode_marked", bufs, infos, form, offsets, device, decoder)
+    n = len(frames)
+    if first is None:
+        if marks.dim() != 3 or marks.shape[0] != n:
+            raise ValueError("jpeg_decode_marked: marks must be [n, M + 1, 32] when first is not given")
+        first = torch.arange(n, dtype=torch.int64, device=decoder.device) * marks.shape[1]
+    if out is None:
+        if offsets is not None:
+            raise ValueError("jpeg_decode_marked: offsets name places in the caller's out")
+        out = torch.empty((n,) + jpeg_out_shape(decoder.H, decoder.W, form), dtype=torch.uint16 if form == "u16" else torch.uint8,
+                          device=decoder.device)
+    elif not out.is_cuda or not out.is_contiguous():
+        raise ValueError("jpeg_decode_marked: out must be a contiguous cuda tensor")
+    status = decoder.decode_marked(stream, frames, marks, first, mode, form, out, sticky=sticky, rows_per_mark=rows_per_mark)
     return out, status

@@ -279,6 +279,11 @@ int launch_gather_chunks(const actmi_gather_chunks_desc& d, hipStream_t st, std:
 int64_t jpeg_workspace_bytes(int64_t n, int H, int W, int mode);
 int launch_jpeg_decode(const actmi_jpeg_desc& d, hipStream_t st, std::string* err);
 int jpeg_decode_host(const actmi_jpeg_desc& d, std::string* err);   // the same core on the CPU, host pointers
+// marks (contract at actmi_jpeg_mark in actmi.h): the index pass and the decode that enters the scan at every mark
+int launch_jpeg_index(const actmi_jpeg_desc& d, const actmi_jpeg_marks& mk, hipStream_t st, std::string* err);
+int launch_jpeg_decode_marked(const actmi_jpeg_desc& d, const actmi_jpeg_marks& mk, hipStream_t st, std::string* err);
+int jpeg_index_host(const actmi_jpeg_desc& d, const actmi_jpeg_marks& mk, std::string* err);
+int jpeg_decode_marked_host(const actmi_jpeg_desc& d, const actmi_jpeg_marks& mk, std::string* err);
 
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------
 bool prof_enabled();

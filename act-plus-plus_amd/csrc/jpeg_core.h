@@ -181,8 +181,10 @@ JPEG_HD int jpeg_receive_extend(JpegBits* b, int t) {
     return v < (1 << (t - 1)) ? v - (1 << t) + 1 : v;
 }
 
-// one block into its 64 pre-zeroed coefficients (natural order) -> 0 or the status
-JPEG_HD int jpeg_decode_block(JpegBits* b, const actmi_jpeg_huff* dc, const uint16_t* dc_look, const actmi_jpeg_huff* ac,
+// one block into its 64 pre-zeroed coefficients (natural order) -> 0 or the status.  STORE false: the same walk, nothing stored
+// (the index pass; coef is not looked at)
+template <bool STORE>
+JPEG_HD int jpeg_decode_block_t(JpegBits* b, const actmi_jpeg_huff* dc, const uint16_t* dc_look, const actmi_jpeg_huff* ac,
                               const uint16_t* ac_look, const uint8_t* zigzag, int32_t* pred, int16_t* coef) {
     int bad = 0;
     int t = jpeg_huff_decode(b, dc, dc_look, &bad);
@@ -192,7 +194,7 @@ JPEG_HD int jpeg_decode_block(JpegBits* b, const actmi_jpeg_huff* dc, const uint
     }
     const int diff = jpeg_receive_extend(b, t);
     *pred = (int32_t)((uint32_t)*pred + (uint32_t)diff);
-    coef[0] = (int16_t)*pred;
+    if (STORE) coef[0] = (int16_t)*pred;
     int k = 1;
     for (int it = 0; it < 63 && k < 64 && !bad; ++it) {             // every turn advances k
         const int rs = jpeg_huff_decode(b, ac, ac_look, &bad);
@@ -200,7 +202,8 @@ JPEG_HD int jpeg_decode_block(JpegBits* b, const actmi_jpeg_huff* dc, const uint
         if (s) {
             k += r;
             if (k > 63) return ACTMI_JPEG_ST_COEF;
-            coef[zigzag[k] & 63] = (int16_t)jpeg_receive_extend(b, s);
+            const int v = jpeg_receive_extend(b, s);
+            if (STORE) coef[zigzag[k] & 63] = (int16_t)v;
             ++k;
         } else {
             if (r != 15) break;
@@ -209,6 +212,11 @@ JPEG_HD int jpeg_decode_block(JpegBits* b, const actmi_jpeg_huff* dc, const uint
     }
     if (bad) return ACTMI_JPEG_ST_BADCODE;
     return b->over ? ACTMI_JPEG_ST_OVERRUN : ACTMI_JPEG_ST_OK;
+}
+
+JPEG_HD int jpeg_decode_block(JpegBits* b, const actmi_jpeg_huff* dc, const uint16_t* dc_look, const actmi_jpeg_huff* ac,
+                              const uint16_t* ac_look, const uint8_t* zigzag, int32_t* pred, int16_t* coef) {
+    return jpeg_decode_block_t<true>(b, dc, dc_look, ac, ac_look, zigzag, pred, coef);
 }
 
 // ---- the scan, MCU by MCU
@@ -241,7 +249,8 @@ JPEG_HD bool jpeg_window_holds_mcu(const JpegBits* b, int64_t limit, int64_t len
 }
 
 // the next MCU (the caller counts them: mx * my in all) -> 0 or the status
-JPEG_HD int jpeg_scan_mcu(JpegScan* s, const JpegGeom* g, const actmi_jpeg_tables* tb, const JpegLook* lk, const uint8_t* zigzag,
+template <bool STORE>
+JPEG_HD int jpeg_scan_mcu_t(JpegScan* s, const JpegGeom* g, const actmi_jpeg_tables* tb, const JpegLook* lk, const uint8_t* zigzag,
                           int16_t* coef) {
     JpegBits* b = &s->bits;
     if (s->interval > 0 && s->togo == 0) {
@@ -268,7 +277,7 @@ JPEG_HD int jpeg_scan_mcu(JpegScan* s, const JpegGeom* g, const actmi_jpeg_table
         for (int bv = 0; bv < g->v[c]; ++bv)
             for (int bh = 0; bh < g->h[c]; ++bh) {
                 const int64_t blk = g->blk0[c] + (int64_t)(s->myi * g->v[c] + bv) * g->bw[c] + (s->mxi * g->h[c] + bh);
-                const int st = jpeg_decode_block(b, dc, lk->e[di], ac, lk->e[ai], zigzag, &s->pred[c], coef + blk * 64);
+                const int st = jpeg_decode_block_t<STORE>(b, dc, lk->e[di], ac, lk->e[ai], zigzag, &s->pred[c], STORE ? coef + blk * 64 : coef);
                 if (st) return st;
             }
     }
@@ -278,6 +287,87 @@ JPEG_HD int jpeg_scan_mcu(JpegScan* s, const JpegGeom* g, const actmi_jpeg_table
     }
     return ACTMI_JPEG_ST_OK;
 }
+
+JPEG_HD int jpeg_scan_mcu(JpegScan* s, const JpegGeom* g, const actmi_jpeg_tables* tb, const JpegLook* lk, const uint8_t* zigzag,
+                          int16_t* coef) {
+    return jpeg_scan_mcu_t<true>(s, g, tb, lk, zigzag, coef);
+}
+
+// ---- marks (the definition is at actmi_jpeg_mark in actmi.h): the scan's state in canonical form, and a scan opened from it
+JPEG_HD int jpeg_mark_count(const JpegGeom* g, int rows_per_mark) {             // M, for any rows_per_mark >= 1
+    return rows_per_mark >= g->my ? 1 : (g->my + rows_per_mark - 1) / rows_per_mark;
+}
+
+// The state of `s` between two MCUs.  The unread data bits are the tail of the last ceil(r / 8) data bytes behind pos; those bytes
+// were read by this reader, so every 0x00 that follows a 0xFF among them is that byte's stuffing.  The window must hold the 8
+// bytes behind pos (or start at 0).  That the form names a state uniquely (two readers at the same bit of the stream give the same
+// offset and bit, and the induction in actmi.h needs it) rests on two invariants of the reader: its unread real bits never span a
+// restart marker (jpeg_scan_mcu resets acc and n there, and a reader opened from a mark starts with none), so the walk back never
+// crosses one; and a 0xFF the reader has passed was followed by 0x00 (anything else stops it at the 0xFF), so among the bytes
+// behind pos a 0x00 directly after a 0xFF is always that byte's stuffing, never a data byte of its own.
+JPEG_HD void jpeg_mark_take(const JpegScan* s, actmi_jpeg_mark* m) {
+    const JpegBits* b = &s->bits;
+    int r = b->n - b->fake;
+    r = r < 0 ? 0 : (r > 32 ? 32 : r);
+    int64_t p = b->pos;
+    const int back = (r + 7) >> 3;
+    for (int i = 0; i < 4; ++i) {
+        if (i >= back) break;
+        if (p - 2 >= b->origin && p <= b->limit && b->win[p - 1 - b->origin] == 0 && b->win[p - 2 - b->origin] == 0xFFu) p -= 2;
+        else if (p - 1 >= b->origin) p -= 1;
+    }
+    m->byte_off = p;
+    m->bit = (8 - (r & 7)) & 7;
+    m->pred[0] = s->pred[0];
+    m->pred[1] = s->pred[1];
+    m->pred[2] = s->pred[2];
+    m->togo = s->togo;
+    m->rst = s->rst;
+}
+
+JPEG_HD bool jpeg_mark_equal(const actmi_jpeg_mark* a, const actmi_jpeg_mark* b) {
+    return a->byte_off == b->byte_off && a->bit == b->bit && a->pred[0] == b->pred[0] && a->pred[1] == b->pred[1] &&
+           a->pred[2] == b->pred[2] && a->togo == b->togo && a->rst == b->rst;
+}
+
+// One interval of a marked decode: rows [j * R, min((j + 1) * R, my)) of the frame whose marks are mk[0 .. M], from mark j, the end
+// state compared with mark j + 1 -> 0 or the status.  `win` holds the segment's bytes [0, len).
+JPEG_HD int jpeg_interval_decode(const actmi_jpeg_mark* mk, int j, int R, const uint8_t* win, int64_t len, int restart_interval,
+                                 const JpegGeom* g, const actmi_jpeg_tables* tb, const JpegLook* lk, const uint8_t* zigzag, int16_t* coef) {
+    const actmi_jpeg_mark m0 = mk[j];
+    JpegScan sc;
+    jpeg_scan_open(&sc, restart_interval);
+    if (m0.bit < 0 || m0.bit > 7 || m0.byte_off < 0 || m0.byte_off > len || m0.togo < 0 || m0.togo > sc.interval || m0.rst < 0 || m0.rst > 7)
+        return ACTMI_JPEG_ST_MARK;
+    if (j == 0 && (m0.byte_off != 0 || m0.bit != 0 || m0.pred[0] != 0 || m0.pred[1] != 0 || m0.pred[2] != 0 || m0.togo != sc.interval || m0.rst != 0))
+        return ACTMI_JPEG_ST_MARK;
+    jb_open(&sc.bits, win, 0, len, len);
+    sc.bits.pos = m0.byte_off;
+    if (m0.bit > 0) {
+        jb_fill(&sc.bits);
+        jb_drop(&sc.bits, m0.bit);
+        if (sc.bits.over) return ACTMI_JPEG_ST_MARK;              // byte_off names no data byte
+    }
+    sc.pred[0] = m0.pred[0];
+    sc.pred[1] = m0.pred[1];
+    sc.pred[2] = m0.pred[2];
+    sc.togo = m0.togo;
+    sc.rst = m0.rst;
+    const int r0 = j * R, r1 = r0 + R < g->my ? r0 + R : g->my;
+    sc.myi = r0;
+    const int64_t nmcu = (int64_t)(r1 - r0) * g->mx;
+    for (int64_t m = 0; m < nmcu; ++m) {
+        const int st = jpeg_scan_mcu(&sc, g, tb, lk, zigzag, coef);
+        if (st) return st;
+    }
+    actmi_jpeg_mark e;
+    jpeg_mark_take(&sc, &e);
+    const actmi_jpeg_mark m1 = mk[j + 1];
+    return jpeg_mark_equal(&e, &m1) ? ACTMI_JPEG_ST_OK : ACTMI_JPEG_ST_MARK;
+}
+
+// the frame's marks lie in the array
+JPEG_HD bool jpeg_marks_inside(int64_t first, int M, int64_t n_marks) { return first >= 0 && first <= n_marks - (int64_t)M - 1; }
 
 // ---- inverse DCT: one pass of jidctint's islow over c[0..7] -> o[0..7], descaled by n
 JPEG_HD void jpeg_idct_1d(const int32_t* c, int32_t* o, int n) {
@@ -392,27 +482,12 @@ JPEG_HD int64_t jpeg_segment_len(int64_t seg_off, int32_t seg_len, int64_t strea
     return seg_len;
 }
 
-// ---- the host twin's frame: entropy, IDCT and colour of frame f of a checked descriptor, on the CPU
-inline void jpeg_decode_frame_host(const actmi_jpeg_desc& d, const JpegGeom& g, int f, const uint8_t* h_zigzag) {
+// ---- the host twins' second half: IDCT and colour of frame f from the coefficients in its slot (the destination is inside)
+inline void jpeg_pixels_frame_host(const actmi_jpeg_desc& d, const JpegGeom& g, int f) {
     const int px = d.form == ACTMI_JPEG_FORM_U16 ? 2 : 3;
     const actmi_jpeg_frame& rec = d.frames[f];
     uint8_t* slot = static_cast<uint8_t*>(d.ws) + (int64_t)f * g.slot_bytes;
-    memset(slot, 0, (size_t)(g.nblocks * 128));
-    if (!jpeg_dest_inside(rec.dst_off, jpeg_out_bytes(d.H, d.W, d.form), d.dst_bytes)) {
-        d.status[f] = ACTMI_JPEG_ST_DEST;
-        return;
-    }
     const actmi_jpeg_tables* tb = d.tables + rec.table_set;
-    const int64_t len = jpeg_segment_len(rec.seg_off, rec.seg_len, d.stream_bytes);
-    JpegLook lk;
-    jpeg_look_build(tb, &lk, 0, 1);
-    JpegScan sc;
-    jpeg_scan_open(&sc, rec.restart_interval);
-    jb_open(&sc.bits, len > 0 ? d.stream + rec.seg_off : d.stream, 0, len, len);
-    int st = ACTMI_JPEG_ST_OK;
-    const int64_t nmcu = (int64_t)g.mx * g.my;
-    for (int64_t m = 0; m < nmcu && !st; ++m) st = jpeg_scan_mcu(&sc, &g, tb, &lk, h_zigzag, reinterpret_cast<int16_t*>(slot));
-    d.status[f] = st;
     for (int c = 0; c < g.ncomp; ++c) {
         const int64_t stride = (int64_t)g.bw[c] * 8;
         for (int64_t by = 0; by < g.bh[c]; ++by)
@@ -447,4 +522,77 @@ inline void jpeg_decode_frame_host(const actmi_jpeg_desc& d, const JpegGeom& g, 
                 q[2] = (uint8_t)bgr[2];
             }
         }
+}
+
+// ---- the host twin's frame: entropy, IDCT and colour of frame f of a checked descriptor, on the CPU
+inline void jpeg_decode_frame_host(const actmi_jpeg_desc& d, const JpegGeom& g, int f, const uint8_t* h_zigzag) {
+    const actmi_jpeg_frame& rec = d.frames[f];
+    uint8_t* slot = static_cast<uint8_t*>(d.ws) + (int64_t)f * g.slot_bytes;
+    memset(slot, 0, (size_t)(g.nblocks * 128));
+    if (!jpeg_dest_inside(rec.dst_off, jpeg_out_bytes(d.H, d.W, d.form), d.dst_bytes)) {
+        d.status[f] = ACTMI_JPEG_ST_DEST;
+        return;
+    }
+    const actmi_jpeg_tables* tb = d.tables + rec.table_set;
+    const int64_t len = jpeg_segment_len(rec.seg_off, rec.seg_len, d.stream_bytes);
+    JpegLook lk;
+    jpeg_look_build(tb, &lk, 0, 1);
+    JpegScan sc;
+    jpeg_scan_open(&sc, rec.restart_interval);
+    jb_open(&sc.bits, len > 0 ? d.stream + rec.seg_off : d.stream, 0, len, len);
+    int st = ACTMI_JPEG_ST_OK;
+    const int64_t nmcu = (int64_t)g.mx * g.my;
+    for (int64_t m = 0; m < nmcu && !st; ++m) st = jpeg_scan_mcu(&sc, &g, tb, &lk, h_zigzag, reinterpret_cast<int16_t*>(slot));
+    d.status[f] = st;
+    jpeg_pixels_frame_host(d, g, f);
+}
+
+// the index pass of frame f on the CPU: the same walk, the marks mk[0 .. M] and the status written, nothing else
+inline void jpeg_index_frame_host(const actmi_jpeg_desc& d, const actmi_jpeg_marks& mk, const JpegGeom& g, int f, const uint8_t* h_zigzag) {
+    const actmi_jpeg_frame& rec = d.frames[f];
+    const int R = mk.rows_per_mark, M = jpeg_mark_count(&g, R);
+    if (!jpeg_marks_inside(mk.first[f], M, mk.n_marks)) {
+        d.status[f] = ACTMI_JPEG_ST_MARK;
+        return;
+    }
+    actmi_jpeg_mark* out = mk.marks + mk.first[f];
+    const actmi_jpeg_tables* tb = d.tables + rec.table_set;
+    const int64_t len = jpeg_segment_len(rec.seg_off, rec.seg_len, d.stream_bytes);
+    JpegLook lk;
+    jpeg_look_build(tb, &lk, 0, 1);
+    JpegScan sc;
+    jpeg_scan_open(&sc, rec.restart_interval);
+    jb_open(&sc.bits, len > 0 ? d.stream + rec.seg_off : d.stream, 0, len, len);
+    int st = ACTMI_JPEG_ST_OK;
+    const int64_t nmcu = (int64_t)g.mx * g.my;
+    for (int64_t m = 0; m < nmcu && !st; ++m) {
+        if (sc.mxi == 0 && sc.myi % R == 0) jpeg_mark_take(&sc, &out[sc.myi / R]);
+        st = jpeg_scan_mcu_t<false>(&sc, &g, tb, &lk, h_zigzag, nullptr);
+    }
+    if (!st) jpeg_mark_take(&sc, &out[M]);
+    d.status[f] = st;
+}
+
+// the marked decode of frame f on the CPU: the intervals in order up to the first that fails, then IDCT and colour
+inline void jpeg_decode_marked_frame_host(const actmi_jpeg_desc& d, const actmi_jpeg_marks& mk, const JpegGeom& g, int f,
+                                          const uint8_t* h_zigzag) {
+    const actmi_jpeg_frame& rec = d.frames[f];
+    uint8_t* slot = static_cast<uint8_t*>(d.ws) + (int64_t)f * g.slot_bytes;
+    memset(slot, 0, (size_t)(g.nblocks * 128));
+    const int R = mk.rows_per_mark, M = jpeg_mark_count(&g, R);
+    int st = ACTMI_JPEG_ST_OK;
+    if (!jpeg_dest_inside(rec.dst_off, jpeg_out_bytes(d.H, d.W, d.form), d.dst_bytes)) st = ACTMI_JPEG_ST_DEST;
+    else if (!jpeg_marks_inside(mk.first[f], M, mk.n_marks)) st = ACTMI_JPEG_ST_MARK;
+    if (!st) {
+        const actmi_jpeg_tables* tb = d.tables + rec.table_set;
+        const int64_t len = jpeg_segment_len(rec.seg_off, rec.seg_len, d.stream_bytes);
+        JpegLook lk;
+        jpeg_look_build(tb, &lk, 0, 1);
+        for (int j = 0; j < M && !st; ++j)
+            st = jpeg_interval_decode(mk.marks + mk.first[f], j, R, len > 0 ? d.stream + rec.seg_off : d.stream, len, rec.restart_interval, &g,
+                                      tb, &lk, h_zigzag, reinterpret_cast<int16_t*>(slot));
+    }
+    d.status[f] = st;
+    if (mk.sticky && st > *mk.sticky) *mk.sticky = st;
+    if (st != ACTMI_JPEG_ST_DEST) jpeg_pixels_frame_host(d, g, f);
 }

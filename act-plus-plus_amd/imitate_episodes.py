@@ -612,6 +612,8 @@ def replay_bc(config, ckpt_name, episodes=None, policy=None, stats=None, batch=N
             mine.append(part.episode(i, ep, table, raw, target, actions, shift))
         if engine is not None and hasattr(engine, "check_flags") and on_gpu:
             engine.check_flags()
+        if store is not None and hasattr(store, "check_decoded"):
+            store.check_decoded()                                # a compressed store: the episode's batches decoded with status 0
     for part in parts:
         part.end()
     if verbose and n_frames:
@@ -788,6 +790,9 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
                 validation_dicts.append({k: v.detach().float().cpu() for k, v in forward_pass(data, policy).items()})
                 if batch_idx > 50:
                     break
+            for dl in (train_dataloader, val_dataloader):       # a compressed store: every batch so far decoded with status 0
+                if hasattr(getattr(dl, "store", None), "check_decoded"):
+                    dl.store.check_decoded()
             validation_summary = compute_dict_mean(validation_dicts)
             epoch_val_loss = float(validation_summary["loss"])
             if epoch_val_loss < min_val_loss:
@@ -837,6 +842,9 @@ def train_bc(train_dataloader, val_dataloader, config, log=None):
         if step % save_every == 0 and rank == 0:
             torch.save(policy.serialize(), os.path.join(ckpt_dir, f"policy_step_{step}_seed_{seed}.ckpt"))
     best_step, min_val_loss, best_state_dict = best_ckpt_info
+    for dl in (train_dataloader, val_dataloader):
+        if hasattr(getattr(dl, "store", None), "check_decoded"):
+            dl.store.check_decoded()
     if rank == 0:
         torch.save(policy.serialize(), os.path.join(ckpt_dir, "policy_last.ckpt"))
         torch.save(best_state_dict, os.path.join(ckpt_dir, f"policy_step_{best_step}_seed_{seed}.ckpt"))
@@ -951,6 +959,11 @@ def build_config(args):
         if not args.get("device_dataset"):
             raise ValueError("--device_decode decodes the compressed frames of the device-resident store: it needs --device_dataset")
         config["device_decode"] = True
+    if args.get("store_compressed"):
+        if not (args.get("device_dataset") and args.get("device_decode")):
+            raise ValueError("--store_compressed keeps the device-resident store's frames compressed and decodes every batch on the "
+                             "device: it needs --device_dataset --device_decode")
+        config["store_compressed"] = True
     if args.get("device_clouds"):
         if not (args.get("device_dataset") and args.get("use_pcd")):
             raise ValueError("--device_clouds puts the stored clouds of a --use_pcd dataset into the device-resident store: it needs "
@@ -1031,6 +1044,7 @@ def _load_episode_data(args, config, task_config, dataset_dir, world, local_rank
                      # --device_dataset: every rank holds its own full store on its own device
                      device_dataset=bool(config.get("device_dataset")), mirror_twins=bool(config.get("mirror_twins")),
                      device_clouds=bool(config.get("device_clouds")), device_decode=bool(config.get("device_decode")),
+                     store_compressed=bool(config.get("store_compressed")),
                      cloud_mirror=tuple(config["cloud_mirror"]) if config.get("cloud_mirror") else None,
                      device=f"cuda:{local_rank}" if world > 1 else None,     # train_bc's device
                      device_budget_bytes=(int(config["device_dataset_gb"] * 2**30)
@@ -1220,6 +1234,10 @@ def make_parser():
     parser.add_argument("--device_decode", action="store_true",
                         help="--device_dataset, opt-in: the JPEG frames of compressed episodes are decoded on the device as the store "
                              "is loaded (actmi_op_jpeg_decode) instead of one by one on the host; the store holds the same bytes")
+    parser.add_argument("--store_compressed", action="store_true",
+                        help="--device_dataset --device_decode, opt-in: the store keeps the frames' entropy segments and per-row marks "
+                             "(about 1/35 of the decoded bytes) and decodes every batch on the device (actmi_op_jpeg_decode_marked); the "
+                             "batches are the same bytes")
     parser.add_argument("--cloud_mirror_axis", action="store", type=str, choices=("x", "y", "z"), default=None,
                         help="--mirror_twins --use_pcd: the twin's stored cloud is the source's reflected across a plane normal to "
                              "this axis of the clouds' frame; lifts the refusal of --mirror_twins with --use_pcd")

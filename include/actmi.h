@@ -1184,6 +1184,56 @@ typedef struct actmi_jpeg_desc {
 int64_t actmi_op_jpeg_workspace_bytes(int64_t n, int H, int W, int mode);   /* -1 for a bad argument */
 int actmi_op_jpeg_decode(const actmi_jpeg_desc* d, void* stream);
 int actmi_jpeg_decode_host(const actmi_jpeg_desc* d);
+/* ---- marks: entering a scan at the start of an MCU row (csrc/jpeg_decode.hip, csrc/jpeg_core.h) -------------------------------
+ * A baseline scan can only be entered where the bit position and the DC predictors are known.  A MARK is that state at the entry
+ * of the first MCU of an MCU row, taken BEFORE any restart handling of that MCU (so with togo == 0 the restart marker still lies
+ * ahead).  Position convention, stated once: byte_off is the segment-relative offset of the raw byte in which the next unread data
+ * bit lies (for a stuffed 0xFF 0x00 pair: of the 0xFF) and bit, 0..7, counts the bits of that byte already consumed; when every
+ * data bit read so far is consumed, bit is 0 and byte_off is the offset of what follows (the next data byte, a marker's 0xFF, or
+ * seg_len).  actmi.ops.jpeg_marks_ref states it in numpy.
+ * With rows_per_mark = R >= 1 a frame of my MCU rows has M + 1 marks, M = ceil(my / R): mark j is the state before row j * R,
+ * mark 0 the initial state (offset 0, bit 0, predictors 0, togo = restart_interval, rst 0), mark M the state after the last MCU.
+ *
+ * actmi_op_jpeg_index is the entropy walk of actmi_op_jpeg_decode (one lane per frame, the same core functions) that writes the
+ * frame's marks to marks[first[f] .. first[f] + M] and its status, stores no coefficients and runs no IDCT or colour pass: dst and
+ * ws of the descriptor may be null and dst_off is not looked at.  The marks of a frame with a nonzero status are unspecified.
+ *
+ * actmi_op_jpeg_decode_marked is actmi_op_jpeg_decode with the entropy pass replaced: one workgroup per frame, lane j taking the
+ * intervals j, j + 64, ...  Interval j opens a bit reader at mark j (the accumulator rebuilt from byte_off / bit, predictors, togo
+ * and rst taken from the mark), decodes the MCUs of rows [jR, min((j+1)R, my)) into the frame's pre-zeroed coefficients with the
+ * serial op's MCU decode, and compares its end state, in the canonical form above, with mark j + 1.  IDCT and colour are the
+ * serial op's kernels.  Status ACTMI_JPEG_ST_MARK: mark 0 is not the initial state; a mark is malformed (bit outside 0..7, bit > 0
+ * where byte_off names no data byte, byte_off outside [0, seg_len], togo outside [0, restart_interval], rst outside 0..7, or the
+ * range first[f] .. first[f] + M leaves the array); or an interval does not end in the state its next mark names.  status[f] is
+ * 0 or the cause met by the LOWEST-NUMBERED failing interval (so the device and actmi_jpeg_decode_marked_host agree).  sticky,
+ * when not null, receives the maximum status of the launch by a vector atomic (it is never reset by the library).
+ *
+ * Contract.  The safety paragraph of actmi_op_jpeg_decode holds for ANY segment bytes, ANY records and ANY marks: reads stay
+ * inside the frame's segment and the mark array, writes inside its slot, its destination and its marks, every loop is bounded by
+ * the geometry.  Status 0 implies that the serial op gives status 0 and the same output bytes, by induction over the chained
+ * marks: mark 0 is checked to be the serial walk's initial state; if interval j starts in the serial walk's state before row jR,
+ * it runs the serial walk's steps on the same bytes, so its end state is the serial walk's before row (j+1)R, and that is what
+ * mark j + 1 was compared with and interval j + 1 starts from.  The canonical form names a reader state uniquely, so equality
+ * with the mark is equality of states. */
+#define ACTMI_JPEG_ST_MARK 7       /* a mark is malformed, mark 0 is not the initial state, or an interval misses its next mark */
+typedef struct actmi_jpeg_mark {   /* 32 bytes */
+    int64_t byte_off;
+    int32_t bit;
+    int32_t pred[3];
+    int32_t togo, rst;             /* MCUs until the next restart, the next marker's number */
+} actmi_jpeg_mark;
+typedef struct actmi_jpeg_marks {
+    actmi_jpeg_mark* marks;        /* [n_marks], 8-byte aligned; written by index, read by decode_marked */
+    int64_t n_marks;
+    const int64_t* first;          /* [n]: the index of each frame's mark 0 */
+    int32_t* sticky;               /* decode_marked: null, or one word that receives the launch's maximum status */
+    int32_t rows_per_mark;         /* R >= 1 */
+    int32_t reserved;
+} actmi_jpeg_marks;
+int actmi_op_jpeg_index(const actmi_jpeg_desc* d, const actmi_jpeg_marks* m, void* stream);
+int actmi_jpeg_index_host(const actmi_jpeg_desc* d, const actmi_jpeg_marks* m);
+int actmi_op_jpeg_decode_marked(const actmi_jpeg_desc* d, const actmi_jpeg_marks* m, void* stream);
+int actmi_jpeg_decode_marked_host(const actmi_jpeg_desc* d, const actmi_jpeg_marks* m);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
