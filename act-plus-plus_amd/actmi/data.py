@@ -49,6 +49,9 @@ Differences, all on the host side of the step:
   coordinate reflected across a plane of the clouds' frame), with which ``mirror_twins`` and ``use_pcd`` go together, on the host
   loader and in the store alike.
 
+* ``compress_episode`` (``compress_data.py``) turns a raw episode into a compressed one, its frames encoded on the device
+  (``episode_compress``; actmi_op_jpeg_encode writes libjpeg-turbo's bytes).
+
 What reads an episode file (``open_episode``, the mirror views, ``find_all_hdf5``) lives in ``episode_files`` and the store with its
 loaders in ``episode_store``; both are imported here by name, so ``actmi.data.<name>`` keeps resolving for every one of them."""
 import numpy as np
@@ -59,6 +62,7 @@ from .episode_files import (MirrorSpec, MirrorTwinPath, _EpisodeArrays, _entry_m
                             imdecode_bgr, mirror_cloud_xyz, mirror_twin_paths, open_episode, preprocess_base_action)
 from .episode_store import (ARENA_ALIGN, DEVICE_STORE_RESERVE_BYTES, DeviceBatchLoader, DeviceEpisodeReplay,  # noqa: F401
                             DeviceEpisodeStore, arena_layout, locate_transitions, stored_cloud_counts)
+from .episode_compress import compress_dataset_dir, compress_episode  # noqa: F401
 
 
 def get_norm_stats(dataset_path_list):

@@ -180,6 +180,13 @@ class JpegDesc(C.Structure):
                [(k, C.c_int32) for k in ("n", "n_tables", "H", "W", "mode", "form")]
 
 
+class JpegEncDesc(C.Structure):
+    # actmi_jpeg_enc_desc
+    _fields_ = [("src", C.c_void_p), ("src_bytes", C.c_int64), ("frames", C.c_void_p), ("dst", C.c_void_p), ("dst_bytes", C.c_int64),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("seg_len", C.c_void_p), ("status", C.c_void_p), ("q", C.c_uint16 * 64 * 2)] + \
+               [(k, C.c_int32) for k in ("n", "H", "W", "mode", "form")]
+
+
 class JpegMarks(C.Structure):
     # actmi_jpeg_marks
     _fields_ = [("marks", C.c_void_p), ("n_marks", C.c_int64), ("first", C.c_void_p), ("sticky", C.c_void_p), ("rows_per_mark", C.c_int32),
@@ -311,6 +318,10 @@ def load():
         "actmi_jpeg_index_host": ([C.POINTER(JpegDesc), C.POINTER(JpegMarks)], i32),
         "actmi_op_jpeg_decode_marked": ([C.POINTER(JpegDesc), C.POINTER(JpegMarks), vp], i32),
         "actmi_jpeg_decode_marked_host": ([C.POINTER(JpegDesc), C.POINTER(JpegMarks)], i32),
+        "actmi_op_jpeg_encode_workspace_bytes": ([i64, i32, i32, i32], i64),
+        "actmi_jpeg_encode_bound": ([i32, i32, i32], i64),
+        "actmi_op_jpeg_encode": ([C.POINTER(JpegEncDesc), vp], i32),
+        "actmi_jpeg_encode_host": ([C.POINTER(JpegEncDesc)], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

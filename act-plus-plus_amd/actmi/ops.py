@@ -3445,3 +3445,443 @@ def jpeg_decode_marked(bufs, marks, first=None, rows_per_mark=1, out=None, offse
         raise ValueError("jpeg_decode_marked: out must be a contiguous cuda tensor")
     status = decoder.decode_marked(stream, frames, marks, first, mode, form, out, sticky=sticky, rows_per_mark=rows_per_mark)
     return out, status
+
+
+# ---- baseline JPEG encode (csrc/jpeg_encode.hip, csrc/jpeg_enc_core.h; the definition is at actmi_op_jpeg_encode in actmi.h) -----
+JPEG_ST_DEST = 5
+_JPEG_STD_Q = (
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32)
+# the standard Huffman tables of Annex K in the order of the file's DHT segments: (class << 4 | index, counts per length, symbols)
+_JPEG_STD_DHT = (
+    (0x00, "00010501010101010100000000000000", "000102030405060708090a0b"),
+    (0x10, "0002010303020403050504040000017d",
+     "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748494a"
+     "535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7"
+     "c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"),
+    (0x01, "00030101010101010101010000000000", "000102030405060708090a0b"),
+    (0x11, "00020102040403040705040400010277",
+     "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a43444546474849"
+     "4a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5"
+     "c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"))
+
+
+def _jpeg_enc_args(mode, form=None, quality=None):
+    """the Python layer's refusals: the encoder takes 4:2:0 and 4:4:4, B, G, R or R, G, B pixels, a quality in 1..100"""
+    if mode not in ("420", "444"):
+        raise ValueError(f"jpeg_encode: mode must be '420' or '444' (4:2:2 and gray are not encoded), got {mode!r}")
+    if form is not None and form not in ("bgr", "rgb"):
+        raise ValueError(f"jpeg_encode: form must be 'bgr' or 'rgb', got {form!r}")
+    if quality is not None and not (int(quality) == quality and 1 <= int(quality) <= 100):
+        raise ValueError(f"jpeg_encode: quality must be an integer in 1..100, got {quality!r}")
+
+
+def jpeg_quant_tables(quality):
+    """the luma and chroma quantisation tables of a quality, uint16 [2, 64] in natural order: Annex K scaled as
+    ``jpeg_set_quality(quality, force_baseline)`` scales it"""
+    import numpy as np
+    _jpeg_enc_args("420", quality=quality)
+    q = int(quality)
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return np.clip((np.asarray(_JPEG_STD_Q, dtype=np.int64) * s + 50) // 100, 1, 255).astype(np.uint16)
+
+
+def jpeg_file_header(H, W, quality=50, mode="420"):
+    """everything ``Image.save(..., "JPEG", quality=quality, subsampling=...)`` writes ahead of the entropy segment of an H x W frame:
+    SOI, JFIF APP0, two DQT segments, SOF0, four DHT segments, SOS"""
+    import numpy as np
+    _jpeg_enc_args(mode, quality=quality)
+    H, W = int(H), int(W)
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError("jpeg_file_header: H and W must be in 1..65535")
+    q = jpeg_quant_tables(quality)
+    zz = np.asarray(_JPEG_ZIGZAG)
+    out = bytearray(b"\xff\xd8\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for t in range(2):
+        out += b"\xff\xdb\x00\x43" + bytes([t]) + q[t][zz].astype(np.uint8).tobytes()
+    out += b"\xff\xc0\x00\x11\x08" + bytes([H >> 8, H & 255, W >> 8, W & 255, 3, 1, 0x22 if mode == "420" else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1])
+    for tc_th, counts, vals in _JPEG_STD_DHT:
+        body = bytes([tc_th]) + bytes.fromhex(counts) + bytes.fromhex(vals)
+        out += b"\xff\xc4" + bytes([(len(body) + 2) >> 8, (len(body) + 2) & 255]) + body
+    out += b"\xff\xda\x00\x0c\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00"
+    return bytes(out)
+
+
+def jpeg_assemble(header, segment):
+    """the file: ``jpeg_file_header``'s bytes, the entropy segment (bytes or a uint8 array), EOI"""
+    import numpy as np
+    seg = segment if isinstance(segment, (bytes, bytearray)) else np.ascontiguousarray(segment, dtype=np.uint8).tobytes()
+    return bytes(header) + bytes(seg) + b"\xff\xd9"
+
+
+def _jpeg_std_codes():
+    """symbol -> (code, size) of the four standard tables, in ``_JPEG_STD_DHT``'s order"""
+    tables = []
+    for _id, counts, vals in _JPEG_STD_DHT:
+        counts, vals = bytes.fromhex(counts), bytes.fromhex(vals)
+        code, k, t = 0, 0, {}
+        for l in range(1, 17):
+            for _ in range(counts[l - 1]):
+                t[vals[k]] = (code, l)
+                code += 1
+                k += 1
+            code <<= 1
+        tables.append(t)
+    return tables
+
+
+def _jpeg_fdct_ref(d, pass1):
+    """one pass of jfdctint's islow along the last axis of int64 [..., 8]"""
+    import numpy as np
+    t0, t7, t1, t6 = d[..., 0] + d[..., 7], d[..., 0] - d[..., 7], d[..., 1] + d[..., 6], d[..., 1] - d[..., 6]
+    t2, t5, t3, t4 = d[..., 2] + d[..., 5], d[..., 2] - d[..., 5], d[..., 3] + d[..., 4], d[..., 3] - d[..., 4]
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    n = 11 if pass1 else 15
+    r = 1 << (n - 1)
+    o = np.empty_like(d)
+    if pass1:
+        o[..., 0], o[..., 4] = (t10 + t11) << 2, (t10 - t11) << 2
+    else:
+        o[..., 0], o[..., 4] = (t10 + t11 + 2) >> 2, (t10 - t11 + 2) >> 2
+    z1 = (t12 + t13) * 4433
+    o[..., 2], o[..., 6] = (z1 + t13 * 6270 + r) >> n, (z1 - t12 * 15137 + r) >> n
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * 9633
+    t4, t5, t6, t7 = t4 * 2446, t5 * 16819, t6 * 25172, t7 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    o[..., 7], o[..., 5], o[..., 3], o[..., 1] = (t4 + z1 + z3 + r) >> n, (t5 + z2 + z4 + r) >> n, (t6 + z2 + z3 + r) >> n, (t7 + z1 + z4 + r) >> n
+    return o
+
+
+def _jpeg_edge(p, rows, cols):
+    """`p` extended to rows x cols by repeating its last row and column"""
+    import numpy as np
+    return np.pad(p, ((0, rows - p.shape[0]), (0, cols - p.shape[1])), mode="edge")
+
+
+def jpeg_encode_segment_ref(frame, quality=50, mode="420", form="bgr", symbols=None):
+    """The numpy statement of actmi_op_jpeg_encode (the text is at its declaration in actmi.h): `frame` uint8 [H, W, 3] -> the
+    entropy segment as bytes.  ``symbols``: a list that receives (table, symbol) of every Huffman symbol emitted, table 0..3 in the
+    order of the file's DHT segments (DC luma, AC luma, DC chroma, AC chroma)."""
+    import numpy as np
+    _jpeg_enc_args(mode, form, quality)
+    f = np.asarray(frame)
+    if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
+        raise ValueError(f"jpeg_encode: a frame is uint8 [H, W, 3], got {f.dtype} {f.shape}")
+    H, W = f.shape[:2]
+    f = f.astype(np.int64)
+    R, G, B = (f[..., 0], f[..., 1], f[..., 2]) if form == "rgb" else (f[..., 2], f[..., 1], f[..., 0])
+    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
+    Cb = (-11059 * R - 21709 * G + 32768 * B + 8421375) >> 16
+    Cr = (32768 * R - 27439 * G - 5329 * B + 8421375) >> 16
+    hs = 2 if mode == "420" else 1
+    mw, mh = -(-W // (8 * hs)), -(-H // (8 * hs))
+    planes = [_jpeg_edge(Y, 8 * hs * mh, 8 * hs * mw)]
+    for p in (Cb, Cr):
+        if mode == "420":
+            p = _jpeg_edge(p, 2 * -(-H // 2), 16 * mw)
+            bias = np.tile(np.asarray([1, 2], dtype=np.int64), 4 * mw)
+            p = (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + bias) >> 2
+        planes.append(_jpeg_edge(p, 8 * mh, 8 * mw))
+    q = jpeg_quant_tables(quality).astype(np.int64)
+    zz = np.asarray(_JPEG_ZIGZAG)
+    coef = []                                                     # per component [block rows, block cols, 64] in zigzag order
+    for c, p in enumerate(planes):
+        b = (p - 128).reshape(p.shape[0] // 8, 8, p.shape[1] // 8, 8).transpose(0, 2, 1, 3)
+        b = _jpeg_fdct_ref(b, True)                               # along the rows
+        b = _jpeg_fdct_ref(b.swapaxes(-1, -2), False).swapaxes(-1, -2)   # down the columns
+        d = 8 * q[1 if c else 0].reshape(8, 8)
+        b = np.sign(b) * ((np.abs(b) + (d >> 1)) // d)
+        coef.append(b.reshape(b.shape[0], b.shape[1], 64)[..., zz])
+    tables = _jpeg_std_codes()
+    rbw, rbh = -(-W // 8), -(-H // 8)
+    bits, pred, last_dc = [], [0, 0, 0], 0
+
+    def put(code, size):
+        if size:
+            bits.append(format(code, f"0{size}b"))
+
+    def sym(t, s):
+        if symbols is not None:
+            symbols.append((t, s))
+        put(*tables[t][s])
+
+    def value(v, s):
+        put(v + (1 << s) - 1 if v < 0 else v, s)
+
+    for my in range(mh):
+        for mx in range(mw):
+            for c in range(3):
+                dc_t, ac_t = (0, 1) if c == 0 else (2, 3)
+                h = hs if c == 0 else 1
+                for bv in range(h):
+                    for bh in range(h):
+                        by, bx = my * h + bv, mx * h + bh
+                        blk = coef[c][by, bx]
+                        if c == 0 and (bx >= rbw or by >= rbh):   # a dummy block: the DC of the block emitted before it in Y
+                            blk = np.zeros(64, dtype=np.int64)
+                            blk[0] = last_dc
+                        if c == 0:
+                            last_dc = int(blk[0])
+                        diff = int(blk[0]) - pred[c]
+                        pred[c] = int(blk[0])
+                        s = abs(diff).bit_length()
+                        sym(dc_t, s)
+                        value(diff, s)
+                        run = 0
+                        for k in range(1, 64):
+                            v = int(blk[k])
+                            if v == 0:
+                                run += 1
+                                continue
+                            while run >= 16:
+                                sym(ac_t, 0xF0)
+                                run -= 16
+                            s = abs(v).bit_length()
+                            sym(ac_t, (run << 4) | s)
+                            value(v, s)
+                            run = 0
+                        if run:
+                            sym(ac_t, 0x00)
+    s = "".join(bits)
+    s += "1" * (-len(s) % 8)
+    return int(s, 2).to_bytes(len(s) // 8, "big").replace(b"\xff", b"\xff\x00")
+
+
+def jpeg_encode_ref(frame, quality=50, mode="420", form="bgr"):
+    """``jpeg_encode_segment_ref`` inside its file: the bytes ``Image.fromarray(rgb).save(buf, "JPEG", quality=quality,
+    subsampling=2 or 0)`` writes.  Pure numpy."""
+    seg = jpeg_encode_segment_ref(frame, quality, mode, form)
+    return jpeg_assemble(jpeg_file_header(frame.shape[0], frame.shape[1], quality, mode), seg)
+
+
+def jpeg_enc_frame_dtype():
+    """actmi_jpeg_enc_frame as a numpy structured dtype (32 bytes)"""
+    import numpy as np
+    return np.dtype([("src_off", np.int64), ("dst_off", np.int64), ("dst_cap", np.int32), ("reserved", np.int32, 3)])
+
+
+def jpeg_encode_bound(H, W, mode="420"):
+    """actmi_jpeg_encode_bound: bytes no entropy segment of an H x W frame can exceed"""
+    _jpeg_enc_args(mode)
+    return int(L.load().actmi_jpeg_encode_bound(int(H), int(W), JPEG_MODES[mode]))
+
+
+def jpeg_encode_workspace_bytes(n, H, W, mode="420"):
+    _jpeg_enc_args(mode)
+    return int(L.load().actmi_op_jpeg_encode_workspace_bytes(int(n), int(H), int(W), JPEG_MODES[mode]))
+
+
+def jpeg_enc_records(n, H, W, cap, src_off=None, dst_off=None):
+    """the records of n frames laid back to back in `src`, every segment in a window of `cap` bytes (or at the offsets given)"""
+    import numpy as np
+    rec = np.zeros(int(n), dtype=jpeg_enc_frame_dtype())
+    rec["src_off"] = np.arange(n, dtype=np.int64) * (int(H) * int(W) * 3) if src_off is None else np.asarray(src_off, dtype=np.int64)
+    rec["dst_off"] = np.arange(n, dtype=np.int64) * int(cap) if dst_off is None else np.asarray(dst_off, dtype=np.int64)
+    rec["dst_cap"] = cap
+    return rec
+
+
+def _jpeg_enc_desc(H, W, quality, mode, form, q=None):
+    import numpy as np
+    _jpeg_enc_args(mode, form, quality)
+    d = L.JpegEncDesc()
+    q = jpeg_quant_tables(quality) if q is None else np.ascontiguousarray(q, dtype=np.uint16).reshape(2, 64)
+    C.memmove(d.q, q.ctypes.data, 256)
+    d.H, d.W, d.mode, d.form = int(H), int(W), JPEG_MODES[mode], JPEG_FORMS[form]
+    return d
+
+
+def jpeg_encode_host_raw(src, records, dst, H, W, quality=50, mode="420", form="bgr", ws=None, q=None):
+    """actmi_jpeg_encode_host, the CPU twin of ``JpegEncoder.encode`` (the same core, no device), on the caller's buffers: `src` and
+    `dst` contiguous 1-D uint8 arrays, `records` ``jpeg_enc_frame_dtype`` -> (seg_len, status), int32 [n] each.  ``ws``: a 16-byte
+    aligned uint8 array of at least ``jpeg_encode_workspace_bytes`` bytes; ``q``: quantisation tables in place of the quality's."""
+    import numpy as np
+    for name, a in (("src", src), ("dst", dst)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
+            raise ValueError(f"jpeg_encode_host: {name} must be a contiguous 1-D uint8 array")
+    rec = np.ascontiguousarray(records, dtype=jpeg_enc_frame_dtype())
+    n = len(rec)
+    d = _jpeg_enc_desc(H, W, quality, mode, form, q)
+    lib = L.load()
+    if ws is None:
+        ws = _aligned_u8(max(16, int(lib.actmi_op_jpeg_encode_workspace_bytes(n, d.H, d.W, d.mode))))
+    seg_len, status = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+    d.src, d.src_bytes, d.frames, d.dst, d.dst_bytes = src.ctypes.data, src.size, rec.ctypes.data, dst.ctypes.data, dst.size
+    d.ws, d.ws_bytes, d.seg_len, d.status, d.n = ws.ctypes.data, ws.size, seg_len.ctypes.data, status.ctypes.data, n
+    L.check(lib.actmi_jpeg_encode_host(C.byref(d)), None, "jpeg_encode_host")
+    return seg_len, status
+
+
+def _jpeg_enc_frames(frames):
+    import numpy as np
+    f = np.ascontiguousarray(frames)
+    if f.ndim == 3:
+        f = f[None]
+    if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3 or 0 in f.shape:
+        raise ValueError(f"jpeg_encode: frames are uint8 [n, H, W, 3] (or one [H, W, 3]), got {f.dtype} {f.shape}")
+    return f
+
+
+def jpeg_encode_host(frames, quality=50, mode="420", form="bgr"):
+    """`frames` uint8 [n, H, W, 3] (numpy) encoded by the CPU twin -> one ``bytes`` per frame, each the whole file
+    (``jpeg_encode_ref``'s bytes)"""
+    import numpy as np
+    f = _jpeg_enc_frames(frames)
+    n, H, W = f.shape[:3]
+    cap = jpeg_encode_bound(H, W, mode)
+    dst = np.empty(n * cap, dtype=np.uint8)
+    seg_len, status = jpeg_encode_host_raw(f.reshape(-1), jpeg_enc_records(n, H, W, cap), dst, H, W, quality, mode, form)
+    if status.any():
+        raise RuntimeError(f"jpeg_encode_host: status {status.tolist()} with windows of the bound's size")
+    head = jpeg_file_header(H, W, quality, mode)
+    return [jpeg_assemble(head, dst[i * cap:i * cap + int(seg_len[i])]) for i in range(n)]
+
+
+def _pil_jpeg_file(frame, quality, mode, form):
+    """one frame through PIL: by the definition of the encode, the bytes the op's segment gives inside its header"""
+    import io
+    import numpy as np
+    from PIL import Image
+    rgb = np.ascontiguousarray(frame if form == "rgb" else frame[..., ::-1])
+    buf = io.BytesIO()
+    Image.fromarray(rgb).save(buf, "JPEG", quality=int(quality), subsampling=2 if mode == "420" else 0)
+    return buf.getvalue()
+
+
+class JpegHostEncoder:
+    """``JpegEncoder``'s ``files`` on the CPU twin (no device): what ``compress_episode`` takes as ``encoder=`` in tests"""
+
+    def __init__(self, H, W, max_frames=64, quality=50, mode="420"):
+        _jpeg_enc_args(mode, quality=quality)
+        self.device, self.H, self.W, self.max_frames, self.quality, self.mode = None, int(H), int(W), int(max_frames), int(quality), mode
+        self.stats = {"frames": 0, "fallback": 0}
+
+    def files(self, src, form="bgr"):
+        f = _jpeg_enc_frames(src.numpy() if torch.is_tensor(src) else src)
+        if f.shape[1:3] != (self.H, self.W):
+            raise ValueError(f"JpegHostEncoder: frames {f.shape[1:3]}, the encoder is for {self.H} x {self.W}")
+        self.stats["frames"] += len(f)
+        return jpeg_encode_host(f, self.quality, self.mode, form)
+
+
+class JpegEncoder:
+    """The device state of ``jpeg_encode`` for frames of one size, quality and sampling mode: the workspace of ``max_frames`` slots,
+    the records of the default layout (frames back to back in `src`, every segment in a window of ``cap`` bytes of `dst`; the
+    default leaves half a raw frame and 4 KiB, ``cap=encoder.bound`` what no frame exceeds) and the file header.  ``encode``
+    launches actmi_op_jpeg_encode for up to ``max_frames`` frames at a time on the current stream and reads nothing back;
+    ``files`` reads lengths and statuses back once and returns one file per frame.  ``stats``: frames encoded by ``files``, and how
+    many of them were re-encoded on the host because their status was not 0."""
+
+    def __init__(self, device, H, W, max_frames=64, quality=50, mode="420", cap=None):
+        _jpeg_enc_args(mode, quality=quality)
+        self.device, self.H, self.W, self.max_frames = torch.device(device), int(H), int(W), int(max_frames)
+        self.quality, self.mode = int(quality), mode
+        if self.max_frames < 1 or self.max_frames > 65535:
+            raise ValueError("JpegEncoder: max_frames must be in 1..65535")
+        self.bound = jpeg_encode_bound(self.H, self.W, mode)
+        if self.bound < 0:
+            raise ValueError("JpegEncoder: H and W must be in 1..65535")
+        self.frame_bytes = self.H * self.W * 3
+        self.default_cap = min(self.bound, self.frame_bytes // 2 + 4096 if cap is None else int(cap))
+        self.header = jpeg_file_header(self.H, self.W, quality, mode)
+        self._q = jpeg_quant_tables(quality)
+        self._ws = torch.empty(max(16, jpeg_encode_workspace_bytes(self.max_frames, self.H, self.W, mode)), dtype=torch.uint8, device=self.device)
+        self._rec_cap, self._rec = None, None
+        self.stats = {"frames": 0, "fallback": 0}
+
+    def _records(self, n, cap):
+        """the default layout's records on the device, kept for the largest n asked for with this cap"""
+        if self._rec_cap != cap or self._rec.numel() < 32 * n:
+            import numpy as np
+            rec = jpeg_enc_records(max(n, self.max_frames), self.H, self.W, cap)
+            self._rec, self._rec_cap = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(self.device), cap
+        return self._rec
+
+    def encode(self, src, dst=None, cap=None, form="bgr", records=None):
+        """src: contiguous uint8 tensor on the device, n frames [H, W, 3] back to back (``records`` None) -> (dst, seg_len, status):
+        dst uint8 [n * cap] on the device (``cap`` defaults to ``default_cap``; a frame that needs more has status DEST), seg_len
+        and status int32 [n] on the device.  ``records``: ``jpeg_enc_frame_dtype`` records (numpy) that place every frame in `src`
+        and its window in the caller's `dst` instead."""
+        import numpy as np
+        _jpeg_enc_args(self.mode, form)
+        if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.device != self.device or not src.is_contiguous():
+            raise ValueError(f"JpegEncoder: src must be a contiguous uint8 tensor on {self.device}")
+        if records is None:
+            if src.numel() % self.frame_bytes:
+                raise ValueError(f"JpegEncoder: src holds {src.numel()} bytes, not whole frames of {self.H} x {self.W} x 3")
+            n = src.numel() // self.frame_bytes
+            cap = self.default_cap if cap is None else int(cap)
+            if cap < 0 or cap > 0x7FFFFFFF:
+                raise ValueError("JpegEncoder: cap must be in 0..2^31-1")
+            if dst is None:
+                dst = torch.empty(max(1, n * cap), dtype=torch.uint8, device=self.device)
+            rec = self._records(n, cap)
+        else:
+            if dst is None:
+                raise ValueError("JpegEncoder: records name windows in the caller's dst")
+            rec = np.ascontiguousarray(records, dtype=jpeg_enc_frame_dtype())
+            n = len(rec)
+            rec = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(self.device)
+        if dst.dtype != torch.uint8 or dst.device != self.device or not dst.is_contiguous():
+            raise ValueError(f"JpegEncoder: dst must be a contiguous uint8 tensor on {self.device}")
+        seg_len = torch.empty(n, dtype=torch.int32, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if n == 0:
+            return dst, seg_len, status
+        d = _jpeg_enc_desc(self.H, self.W, self.quality, self.mode, form, self._q)
+        d.src, d.src_bytes, d.dst, d.dst_bytes = src.data_ptr(), int(src.numel()), dst.data_ptr(), int(dst.numel())
+        d.ws, d.ws_bytes = self._ws.data_ptr(), int(self._ws.numel())
+        lib = L.load()
+        with torch.cuda.device(self.device):
+            for i0 in range(0, n, self.max_frames):
+                d.frames, d.seg_len, d.status = rec.data_ptr() + 32 * i0, seg_len.data_ptr() + 4 * i0, status.data_ptr() + 4 * i0
+                d.n = min(self.max_frames, n - i0)
+                L.check(lib.actmi_op_jpeg_encode(C.byref(d), L.current_stream_ptr()), None, "op_jpeg_encode")
+        return dst, seg_len, status
+
+    def files(self, src, form="bgr"):
+        """`src` as ``encode`` (or uint8 [n, H, W, 3]) -> one ``bytes`` per frame, the whole file.  The lengths and statuses are read
+        back once, then the segments in one copy.  A frame with a nonzero status (its segment is longer than ``default_cap``) is
+        re-encoded on the host with PIL, which by definition gives the same bytes, and counted in ``stats``."""
+        dst, seg_len, status = self.encode(src, form=form)
+        n, cap = seg_len.numel(), self.default_cap
+        meta = torch.stack([seg_len, status]).cpu().numpy()
+        lens, st = meta[0], meta[1]
+        ok = [i for i in range(n) if st[i] == 0]
+        segs = torch.cat([dst[i * cap:i * cap + int(lens[i])] for i in ok]).cpu().numpy() if ok else None
+        out, pos, frames = [None] * n, 0, None
+        for i in range(n):
+            if st[i] == 0:
+                out[i] = jpeg_assemble(self.header, segs[pos:pos + int(lens[i])])
+                pos += int(lens[i])
+            else:
+                if frames is None:
+                    frames = src.reshape(n, self.H, self.W, 3)
+                out[i] = _pil_jpeg_file(frames[i].cpu().numpy(), self.quality, self.mode, form)
+                self.stats["fallback"] += 1
+        self.stats["frames"] += n
+        return out
+
+
+def jpeg_encode(frames, quality=50, mode="420", form="bgr", device=None, encoder=None):
+    """actmi_op_jpeg_encode: `frames` uint8 [n, H, W, 3] (numpy, or a tensor on any device) encoded on the device -> one ``bytes`` per
+    frame: the file PIL writes for it at this quality and subsampling (``jpeg_encode_ref``'s bytes)."""
+    _jpeg_enc_args(mode, form, quality)
+    if torch.is_tensor(frames):
+        t = frames if frames.dim() == 4 else frames[None]
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or 0 in t.shape:
+            raise ValueError(f"jpeg_encode: frames are uint8 [n, H, W, 3], got {t.dtype} {tuple(t.shape)}")
+    else:
+        t = torch.from_numpy(_jpeg_enc_frames(frames))
+    n, H, W = int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+    if encoder is None:
+        if device is None:
+            device = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        encoder = JpegEncoder(device, H, W, max_frames=min(n, 64), quality=quality, mode=mode)
+    elif (encoder.H, encoder.W, encoder.quality, encoder.mode) != (H, W, int(quality), mode):
+        raise ValueError(f"jpeg_encode: the encoder is for {encoder.H} x {encoder.W} frames at quality {encoder.quality}, mode {encoder.mode}")
+    if encoder.device is None:                                    # the host twin
+        return encoder.files(t, form)
+    return encoder.files(t.to(encoder.device).contiguous(), form)

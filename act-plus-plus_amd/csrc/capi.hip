@@ -635,6 +635,23 @@ int actmi_jpeg_decode_marked_host(const actmi_jpeg_desc* d, const actmi_jpeg_mar
     return jpeg_decode_marked_host(*d, *m, &g_op_error) == 0 ? ACTMI_OK : ACTMI_E_INVALID;
 }
 
+int64_t actmi_op_jpeg_encode_workspace_bytes(int64_t n, int H, int W, int mode) { return jpeg_encode_workspace_bytes(n, H, W, mode); }
+
+int64_t actmi_jpeg_encode_bound(int H, int W, int mode) { return jpeg_encode_bound(H, W, mode); }
+
+int actmi_op_jpeg_encode(const actmi_jpeg_enc_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "jpeg_encode: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_jpeg_encode(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
+int actmi_jpeg_encode_host(const actmi_jpeg_enc_desc* d) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "jpeg_encode: null descriptor"; return ACTMI_E_INVALID; }
+    return jpeg_encode_host(*d, &g_op_error) == 0 ? ACTMI_OK : ACTMI_E_INVALID;
+}
+
 int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int64_t n_per_sample, void* stream) {
     g_op_error.clear();
     const int rc = launch_depth_minmax_u16(depth, lohi_out, B, n_per_sample, S(stream));

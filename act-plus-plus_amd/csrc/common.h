@@ -285,6 +285,12 @@ int launch_jpeg_decode_marked(const actmi_jpeg_desc& d, const actmi_jpeg_marks& 
 int jpeg_index_host(const actmi_jpeg_desc& d, const actmi_jpeg_marks& mk, std::string* err);
 int jpeg_decode_marked_host(const actmi_jpeg_desc& d, const actmi_jpeg_marks& mk, std::string* err);
 
+// ---- baseline JPEG encode (jpeg_encode.hip, jpeg_enc_core.h; contract at actmi_op_jpeg_encode in actmi.h) ---------------------
+int64_t jpeg_encode_workspace_bytes(int64_t n, int H, int W, int mode);
+int64_t jpeg_encode_bound(int H, int W, int mode);
+int launch_jpeg_encode(const actmi_jpeg_enc_desc& d, hipStream_t st, std::string* err);
+int jpeg_encode_host(const actmi_jpeg_enc_desc& d, std::string* err);   // the same core on the CPU, host pointers
+
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------
 bool prof_enabled();
 void prof_begin(const char* name, double flops, double bytes, hipStream_t st);

@@ -1234,6 +1234,85 @@ int actmi_op_jpeg_index(const actmi_jpeg_desc* d, const actmi_jpeg_marks* m, voi
 int actmi_jpeg_index_host(const actmi_jpeg_desc* d, const actmi_jpeg_marks* m);
 int actmi_op_jpeg_decode_marked(const actmi_jpeg_desc* d, const actmi_jpeg_marks* m, void* stream);
 int actmi_jpeg_decode_marked_host(const actmi_jpeg_desc* d, const actmi_jpeg_marks* m);
+/* ---- baseline JPEG encode (csrc/jpeg_encode.hip, csrc/jpeg_enc_core.h): raw frames into the compressed frames of an episode file --
+ * The entropy segment is, byte for byte, what libjpeg-turbo writes with its defaults (integer RGB -> YCbCr, the h2v2 box
+ * downsampler, the integer "islow" forward DCT, the standard Huffman tables, no restart markers): what PIL's
+ * Image.save(..., "JPEG", quality=q, subsampling=s) puts between its SOS header and EOI.  actmi.ops.jpeg_encode_ref states it in
+ * numpy.  All arithmetic is integer, shifts are arithmetic.
+ *
+ * Input: u8 [H][W][3], form ACTMI_JPEG_FORM_BGR (what the episode store and imdecode_bgr keep) or ACTMI_JPEG_FORM_RGB.  Modes:
+ * ACTMI_JPEG_420 and ACTMI_JPEG_444; ACTMI_JPEG_422 and ACTMI_JPEG_GRAY are refused (ACTMI_E_INVALID).
+ * Colour: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16; Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16;
+ * Cr = (32768 R - 27439 G - 5329 B + 8421375) >> 16 (8421375 = (128 << 16) + 32767).
+ * Edges, 4:2:0, mw = ceil(W / 16), mh = ceil(H / 16): Y is extended to 16 mh x 16 mw by repeating its last column and row.  A
+ * chroma plane is extended to the right to 16 mw columns by repeating its last column and downwards only to 2 ceil(H / 2) rows by
+ * repeating its last row; then out[r][c] = (p[2r][2c] + p[2r][2c+1] + p[2r+1][2c] + p[2r+1][2c+1] + bias) >> 2, bias 1 for even c
+ * and 2 for odd c; only then is the downsampled plane extended to 8 mh rows by repeating its last row.  4:4:4: every plane is
+ * extended to multiples of 8 by repeating its last column and row.
+ * Forward DCT: jfdctint's "islow" on sample - 128, CONST_BITS 13, PASS1_BITS 2, 32-bit integers, descale(x, n) = (x + (1 <<
+ * (n-1))) >> n.  Pass 1 along the rows: out0 = (t10 + t11) << 2, out4 = (t10 - t11) << 2, every other output descale(x, 11); pass
+ * 2 down the columns of the pass-1 result: out0 and out4 descale(x, 2), the others descale(x, 15).  With d0..d7 one row / column:
+ *   t0..t3 = d0 + d7, d1 + d6, d2 + d5, d3 + d4; t7..t4 = d0 - d7, d1 - d6, d2 - d5, d3 - d4; t10 = t0 + t3; t13 = t0 - t3;
+ *   t11 = t1 + t2; t12 = t1 - t2
+ *   even: z1 = (t12 + t13) * 4433; out2 = z1 + t13 * 6270; out6 = z1 - t12 * 15137
+ *   odd:  z1 = t4 + t7; z2 = t5 + t6; z3 = t4 + t6; z4 = t5 + t7; z5 = (z3 + z4) * 9633; t4 *= 2446; t5 *= 16819; t6 *= 25172;
+ *         t7 *= 12299; z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+ *         out7 = t4 + z1 + z3; out5 = t5 + z2 + z4; out3 = t6 + z2 + z3; out1 = t7 + z1 + z4
+ * Quantise: q = sign(c) * ((|c| + (d >> 1)) / d), d = 8 * table[k]; component 0 uses q[0], components 1 and 2 use q[1].  The tables
+ * of a quality are the host's business (actmi.ops.jpeg_quant_tables: Annex K scaled as jpeg_set_quality does, s = 5000 / quality
+ * below 50, else 200 - 2 quality, entry = clamp((std * s + 50) / 100, 1, 255)).
+ * Blocks: row-major over MCUs, then components, then the component's v x h blocks.  A Y block outside the component's real block
+ * extent, ceil(W / 8) by ceil(H / 8), is a dummy block: all AC zero, DC the quantised DC of the block emitted just before it in Y.
+ * Entropy coding: the four standard Huffman tables of Annex K, no restart markers; DC as the category of the difference to the
+ * component's predictor and then the value bits, AC as run/size symbols in zigzag order with 0xF0 for every 16 zeros ahead of a
+ * nonzero coefficient and 0x00 when the block ends in zeros; a negative value v of category s is coded as v + (1 << s) - 1; bits
+ * most significant first, the last byte padded with 1 bits, every 0xFF data byte followed by 0x00.
+ * The file around the segment (SOI, JFIF APP0, DQT, SOF0, DHT, SOS ... EOI) is a host constant per (H, W, quality, mode):
+ * actmi.ops.jpeg_file_header and jpeg_assemble.
+ *
+ * actmi_op_jpeg_encode encodes n frames of ONE geometry in five passes: coefficients (one lane per 8x8 block: colour, edges,
+ * downsampling, FDCT, quantisation -> int16 coefficients in zigzag order and in scan order, dummy blocks included), bit counts
+ * (one lane per MCU row), bit offsets (one lane per frame: the exclusive scan of the row counts; the words that two rows share are
+ * zeroed), the unstuffed stream (one lane per MCU row writes its bits at its offset: whole words by stores, its first and last
+ * word by a vector atomic OR into the zeroed word, so the result does not depend on the order of arrival), and stuffing (one
+ * workgroup per frame: the 0xFF bytes of every 256-byte chunk are counted and scanned, seg_len is written, and the chunks are
+ * copied into dst with the 0x00 bytes inserted, cut at dst_cap).  Workspace: n slots of actmi_op_jpeg_encode_workspace_bytes(1, H,
+ * W, mode) bytes, 16-byte aligned.
+ * actmi_jpeg_encode_bound: no segment is longer.  A block has 64 coefficients and a coefficient costs at most 16 code bits and 11
+ * value bits, so the unstuffed stream holds at most blocks * 64 * 27 / 8 = blocks * 216 bytes and, with the pad bits, one more; every
+ * byte may be a stuffed 0xFF: bound = 2 * (blocks * 216 + 1), blocks = MCUs * (6 or 3).  A geometry whose bound does not fit
+ * int32 (seg_len's type) is refused by all four entries: -1 from the two size functions, ACTMI_E_INVALID from the ops.
+ * Contract.  seg_len[i] is always the true length of frame i's segment (0 for a frame whose pixels leave `src`).  status[i] 0: the
+ * segment fit and dst[dst_off .. dst_off + seg_len) is exact.  ACTMI_JPEG_ST_DEST: dst_cap is smaller than seg_len or negative, the
+ * window [dst_off, dst_off + dst_cap) leaves `dst`, or the frame's pixels [src_off, src_off + 3 H W) leave `src`; nothing is written
+ * outside the window (nothing at all when it leaves `dst`) and the bytes in it are unspecified.  Nothing is read outside the
+ * frame's pixels, and nothing is read or written outside the frame's workspace slot.  Every loop is bounded by the geometry, and
+ * two launches give the same bytes.  ACTMI_E_INVALID before any launch: a null pointer, n outside [0, 65535], H or W outside [1,
+ * 65535], a mode other than 420 / 444, a form other than BGR / RGB, a zero table entry, negative sizes, misaligned records or
+ * workspace, a workspace that cannot hold n slots.  actmi_jpeg_encode_host runs the same core serially over host pointers. */
+typedef struct actmi_jpeg_enc_frame {   /* 32 bytes */
+    int64_t src_off;               /* of the frame's pixels in `src`, bytes */
+    int64_t dst_off;               /* of its entropy segment in `dst` */
+    int32_t dst_cap;               /* bytes it may write there */
+    int32_t reserved[3];
+} actmi_jpeg_enc_frame;
+typedef struct actmi_jpeg_enc_desc {
+    const uint8_t* src;
+    int64_t src_bytes;
+    const actmi_jpeg_enc_frame* frames;   /* [n], 8-byte aligned */
+    uint8_t* dst;
+    int64_t dst_bytes;
+    void* ws;                      /* 16-byte aligned */
+    int64_t ws_bytes;
+    int32_t* seg_len;              /* [n] out */
+    int32_t* status;               /* [n] out */
+    uint16_t q[2][64];             /* luma and chroma quantisation tables, natural order, entries 1..255 */
+    int32_t n, H, W, mode, form;
+} actmi_jpeg_enc_desc;
+int64_t actmi_op_jpeg_encode_workspace_bytes(int64_t n, int H, int W, int mode);   /* -1 for a bad argument */
+int64_t actmi_jpeg_encode_bound(int H, int W, int mode);                           /* -1 for a bad argument or a bound above int32 */
+int actmi_op_jpeg_encode(const actmi_jpeg_enc_desc* d, void* stream);
+int actmi_jpeg_encode_host(const actmi_jpeg_enc_desc* d);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
