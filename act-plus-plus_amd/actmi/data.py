@@ -324,7 +324,7 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
               f32_depth=False, pointcloud_names=None, use_pcd=False, max_points=None, pcd_ignore_mask=False,
               device_dataset=False, device=None, device_budget_bytes=None, mirror_twins=False, mirror_spec=None,
               device_clouds=False, cloud_mirror=None, device_decode=False,
-              store_compressed=False, rows_per_mark=1):
+              store_compressed=False, rows_per_mark=1, store_encode=False, encode_quality=50, encode_subsampling="420"):
     """utils.py:249-301.  Returns (train_dataloader, val_dataloader, norm_stats, is_sim).  ``use_depth``: the batches are
     5-tuples that end in the depth frames of ``depth_camera_names`` (EpisodicDataset).  ``use_pcd``: 7-tuples that end in the
     padded clouds and their valid counts (collate_pcd).  ``device_dataset``: both loaders come from ONE ``DeviceEpisodeStore``
@@ -337,12 +337,17 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
     frame memory.  ``cloud_mirror`` ``(axis, offset)``: the mirror rule of the stored clouds (``cloud_mirror_rule``), which
     ``mirror_twins`` with ``use_pcd`` needs.  ``device_clouds``: the stored clouds of a ``use_pcd`` dataset go into the store as well
     and the device loaders deliver the 7-tuples of ``collate_pcd``, gathered by ``actmi_op_gather_clouds``.  ``device_decode``: the store
-    decodes the frames of compressed episodes on the device (``DeviceEpisodeStore``); the batches are the same bytes."""
+    decodes the frames of compressed episodes on the device (``DeviceEpisodeStore``); the batches are the same bytes.
+    ``store_encode`` (with ``store_compressed``): raw episodes are encoded on the device as the store reads them, at
+    ``encode_quality`` / ``encode_subsampling``; the batches are those of a compressed store of ``compress_dataset_dir``'s output."""
     if device_decode and not device_dataset:
         raise ValueError("device_decode decodes the compressed frames of the device-resident store: it needs device_dataset")
     if store_compressed and not (device_dataset and device_decode):
         raise ValueError("store_compressed keeps the device-resident store's frames compressed and decodes every batch on the device: "
                          "it needs device_dataset and device_decode")
+    if store_encode and not store_compressed:
+        raise ValueError("store_encode encodes raw episodes into the store that stays compressed: it needs store_compressed (and "
+                         "device_dataset, device_decode)")
     if mirror_twins and use_pcd and cloud_mirror is None:
         raise ValueError("mirror_twins with use_pcd: a stored point cloud has no mirror rule (cloud_mirror=(axis, offset) gives it one)")
     if cloud_mirror is not None:
@@ -410,6 +415,7 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
         store = DeviceEpisodeStore(dataset_path_list, np.concatenate([train_episode_ids, val_episode_ids]), camera_names, norm_stats,
                                    device, depth_camera_names, use_depth, device_budget_bytes, use_pcd, policy_class,
                                    device_decode=device_decode, store_compressed=store_compressed, rows_per_mark=rows_per_mark,
+                                   store_encode=store_encode, encode_quality=encode_quality, encode_subsampling=encode_subsampling,
                                    **(dict(pointcloud_names=pointcloud_names, max_points=max_points, pcd_ignore_mask=pcd_ignore_mask)
                                       if device_clouds else {}))
         train_loader = store.loader(train_episode_ids, train_episode_len, chunk_size,

@@ -92,7 +92,10 @@ _KINDS = (_FrameKind("images", "frames", False, 3, torch.uint8, 16, "bgr"),
 # file did not size it
 # ``packed`` (``store_compressed`` and a compressed source; else None): per kind None or (L per camera, marks per frame), L the padded
 # file length of a frame, what the entry's header gives
-SourceHeader = namedtuple("SourceHeader", "T compressed cloud_rows cloud_rgb_dtype frames packed", defaults=(0, None, (None, None), None))
+# ``encoded`` (``store_encode`` and a raw source, after the store's encode stage; else None): per kind None or (the exact stream bytes
+# of every camera's block, marks per frame)
+SourceHeader = namedtuple("SourceHeader", "T compressed cloud_rows cloud_rgb_dtype frames packed encoded",
+                          defaults=(0, None, (None, None), None, None))
 
 
 def _checked_frame_shape(kind, path, key, dtype, fshape):
@@ -109,13 +112,14 @@ def _checked_frame_shape(kind, path, key, dtype, fshape):
     return tuple(fshape[:2])
 
 
-def probe_sources(sources, cams, cloud_base=None, max_points=None, store_compressed=False, rows_per_mark=1):
+def probe_sources(sources, cams, cloud_base=None, max_points=None, store_compressed=False, rows_per_mark=1, store_encode=False):
     """Opens every source file once -> [SourceHeader].  `cams`: per kind the camera names; `cloud_base`: the stored cloud's group, None
     without clouds.  The sizes come from the entries' headers (the first file's decoded frames for a compressed dataset: later
     compressed files are checked as they are decoded).  Refused here, before anything large is allocated, each ``ValueError`` naming
     the file: an empty episode, clouds that are not two [T, N, 3] arrays of T steps or store more than `max_points` rows
     (``_read_cloud``'s checks, from the headers), frames that are not T, depth that is not an unsigned integer of at most 16 bits, and
-    cameras or files whose frame sizes differ -- checked as the walk reaches the file, so the first bad file is the one named."""
+    cameras or files whose frame sizes differ -- checked as the walk reaches the file, so the first bad file is the one named;
+    with ``store_encode`` a raw source's depth entry (an 8-bit JPEG cannot hold raw uint16 depth)."""
     headers, sized, marks_of = [], {}, {}
     for i, path in enumerate(sources):
         with open_episode(path) as root:
@@ -146,6 +150,9 @@ def probe_sources(sources, cams, cloud_base=None, max_points=None, store_compres
                         raise ValueError(f"{path}: {key} holds {shape[0]} frames for an episode of {T} steps")
                     if compressed:
                         lens.append(int(shape[1]) if len(shape) == 2 else 0)
+                        if i > 0 and kind.key in sized and store_compressed and kind.key not in marks_of:
+                            # the files before this one were raw (store_encode): the block's marks from this file's first frame
+                            marks_of[kind.key] = _marks_per_frame(np.asarray(root[key][0]), sized[kind.key][0], rows_per_mark)
                         if i > 0:
                             continue                               # sized by the first episode's frames; checked as it is decoded
                         first = np.asarray(root[key][0])
@@ -153,6 +160,9 @@ def probe_sources(sources, cams, cloud_base=None, max_points=None, store_compres
                         if store_compressed and kind.key not in marks_of:
                             marks_of[kind.key] = _marks_per_frame(first, fshape[0], rows_per_mark)
                     else:
+                        if store_encode and kind.is_depth:
+                            raise ValueError(f"{path}: {key} is raw depth, which an 8-bit JPEG cannot hold: store_encode takes raw "
+                                             "camera frames only (train this dataset without --store_encode)")
                         fshape = shape[1:]
                     fshape = _checked_frame_shape(kind, path, key, dtype, fshape)
                     if sized.setdefault(kind.key, fshape) != fshape:
@@ -232,18 +242,30 @@ def plan_store(headers, cams, src_of, twin_cams=None):
     # ``store_compressed`` (a header says so with ``packed``): a camera or depth block of a compressed source is one stream block of
     # at most T * L bytes, L the padded file length, and behind it a mark block of T * (M + 1) * 32 bytes; a source kept raw has its
     # [T, frame] block and an empty mark block, so that every source has the same number of blocks
-    option = any(h.packed is not None for h in headers)
+    # ``store_encode`` (``encoded``): a camera block of a raw source whose frames the store encoded is a stream block of exactly the
+    # bytes its segments take, aligned like every block, and a mark block of T * (M + 1) * 32 bytes
+    option = any(h.packed is not None or h.encoded is not None for h in headers)
+
+    def stream_bytes(h, q, k, T):                                    # of camera k's stream block, None for a block kept raw
+        if h.encoded is not None and h.encoded[q] is not None:
+            return int(h.encoded[q][0][k])
+        return T * h.packed[q][0][k] if h.packed is not None and h.packed[q] is not None else None
+
+    def marks_of(h, q):
+        pk = h.encoded[q] if h.encoded is not None and h.encoded[q] is not None else (h.packed[q] if h.packed is not None else None)
+        return None if pk is None else int(pk[1])
+    # one M + 1 per kind, the largest any source names (a frame with fewer marks uses the head of its records)
+    mpfs = [max([marks_of(h, q) or 0 for h in headers]) for q in range(len(_KINDS))]
     blocks = []
     for h, T, N in zip(headers, src_T.tolist(), src_N.tolist()):
         for q, (fb, c) in enumerate(zip(fbytes, cams)):
-            pk = h.packed[q] if h.packed is not None else None
             for k in range(len(c)):
                 if not option:
                     blocks.append(T * fb)
-                elif pk is None:
+                elif stream_bytes(h, q, k, T) is None:
                     blocks += [T * fb, 0]
                 else:
-                    blocks += [T * pk[0][k], T * pk[1] * 32]
+                    blocks += [stream_bytes(h, q, k, T), T * mpfs[q] * 32]
         blocks += [T * N * 12, T * N * rgb_bytes][:nc]
     offs, nbytes = arena_layout(blocks)
     ends = [int(o) + int(b) for o, b in zip(offs, blocks)]
@@ -255,9 +277,8 @@ def plan_store(headers, cams, src_of, twin_cams=None):
         src_off = offs[:, col:col + width:2 if option else 1].copy()
         extra = {}
         if option and c:
-            cap = np.asarray([[T * h.packed[q][0][k] if h.packed is not None and h.packed[q] is not None else 0 for k in range(len(c))]
-                              for h, T in zip(headers, src_T.tolist())], dtype=np.int64)
-            mpf = next((h.packed[q][1] for h in headers if h.packed is not None and h.packed[q] is not None), 0)
+            cap = np.asarray([[stream_bytes(h, q, k, T) or 0 for k in range(len(c))] for h, T in zip(headers, src_T.tolist())], dtype=np.int64)
+            mpf = mpfs[q]
             extra = dict(stream_cap=cap, mark_off=offs[:, col + 1:col + width:2].copy(), marks_per_frame=int(mpf))
         col += width
         off, flip = src_off[src_of], np.zeros((len(src_of), len(c)), dtype=np.uint8)
@@ -270,7 +291,7 @@ def plan_store(headers, cams, src_of, twin_cams=None):
     return StoreLayout(tuple(kinds), nbytes, padding, src_of, twin, src_T, compressed, src_N, offs[:, col:].copy(), _starts(src_T),
                        0 if rgb_bytes == 3 else 1, rgb_bytes, src_T[src_of], [compressed[j] for j in src_of], _starts(src_T[src_of]),
                        tuple(k for k in kinds if k.cams), any(twin), nc > 0,
-                       np.asarray([h.packed is not None for h in headers]) if option else None)
+                       np.asarray([h.packed is not None or h.encoded is not None for h in headers]) if option else None)
 
 
 class BatchTable:
@@ -338,6 +359,10 @@ class DeviceEpisodeStore:
     ``store_compressed`` (with ``device_decode``): the arena holds the entropy segments and, per frame, the marks of one index pass
     (actmi_op_jpeg_index) instead of the decoded frames; a batch is decoded by actmi_op_jpeg_decode_marked and is bit for bit the
     batch of the other stores.  Frames the device does not take stay raw in a spill tensor per kind (``_load_packed``).
+    ``store_encode`` (with ``store_compressed``): a source whose camera entries are raw uint8 ``[T, H, W, 3]`` is encoded on the device
+    as it is read (``_encode_sources``: B, G, R pixels at ``encode_quality`` / ``encode_subsampling``, as ``compress_episode`` encodes
+    them), its marks written by the encoder (actmi_op_jpeg_encode_marked) -- no index launch; raw and compressed sources may be mixed,
+    and the batches are those of a compressed store of ``compress_dataset_dir``'s output.  ``encode_stats``: the frames encoded.
 
     Every rank of a data-parallel run holds its own full store."""
 
@@ -345,9 +370,19 @@ class DeviceEpisodeStore:
 
     def __init__(self, dataset_path_list, episode_ids, camera_names, norm_stats, device, depth_camera_names=None, use_depth=False,
                  budget_bytes=None, use_pcd=False, policy_class="ACT", stage_bytes=64 << 20, pointcloud_names=None, max_points=None,
-                 pcd_ignore_mask=False, device_decode=False, decode_frames=256, store_compressed=False, rows_per_mark=1):
+                 pcd_ignore_mask=False, device_decode=False, decode_frames=256, store_compressed=False, rows_per_mark=1,
+                 store_encode=False, encode_quality=50, encode_subsampling="420"):
         self.device_decode, self.decode_frames = bool(device_decode), int(decode_frames)
         self.store_compressed, self.rows_per_mark = bool(store_compressed), int(rows_per_mark)
+        self.store_encode, self.encode_quality, self.encode_subsampling = bool(store_encode), encode_quality, str(encode_subsampling)
+        if self.store_encode and not self.store_compressed:
+            raise ValueError("store_encode encodes raw episodes into the store that stays compressed: it needs store_compressed (and "
+                             "device_decode, device_dataset)")
+        if self.store_encode:
+            from . import ops
+            ops._jpeg_enc_args(self.encode_subsampling, quality=encode_quality)
+            if self.decode_frames < 1 or self.decode_frames > 65535:
+                raise ValueError("store_encode: decode_frames must be in 1..65535")
         if self.store_compressed and not self.device_decode:
             raise ValueError("store_compressed keeps the frames the device decodes: it needs device_decode (and device_dataset)")
         if self.store_compressed and self.rows_per_mark < 1:
@@ -395,8 +430,19 @@ class DeviceEpisodeStore:
         self.device, self.stage_bytes = device, int(stage_bytes)
         cams = (tuple(self.camera_names), tuple(self.depth_camera_names) if self.use_depth else ())
         self._cloud_base = f"/observations/pointcloud/{self.pointcloud_names[0]}" if self.has_clouds else None
-        headers = probe_sources(self.sources, cams, self._cloud_base, self.max_points, self.store_compressed, self.rows_per_mark)
-        if self.store_compressed and not all(h.packed is not None and all(p is not None for p, c in zip(h.packed, cams) if c) for h in headers):
+        headers = probe_sources(self.sources, cams, self._cloud_base, self.max_points, self.store_compressed, self.rows_per_mark,
+                                self.store_encode)
+        if budget_bytes is None:
+            free, _total = torch.cuda.mem_get_info(torch.device(device))
+            budget_bytes = free - DEVICE_STORE_RESERVE_BYTES
+        self.budget_bytes = int(budget_bytes)
+        self.bus_bytes = 0                                            # bytes of frames and clouds that crossed to the device
+        self._pin, self._pin_ev, self._pin_i = None, [None, None], 0
+        self.encode_stats, self._held, self._held_bytes, self._encode_staging = {"device": 0}, {}, 0, 0
+        if self.store_encode:
+            headers = self._encode_sources(headers, cams)
+        if self.store_compressed and not all((h.packed is not None and all(p is not None for p, c in zip(h.packed, cams) if c)) or
+                                             h.encoded is not None for h in headers):
             raise NotImplementedError("store_compressed: every source must be a compressed episode (a store of compressed and raw "
                                       "sources is planned by plan_store but not loaded); drop --store_compressed")
         self.layout = lay = plan_store(headers, cams, [where[s] for s in srcs],
@@ -409,13 +455,13 @@ class DeviceEpisodeStore:
             dep.shape, dep.frame_bytes, dep.aligned, dep.block_off, dep.flip
         self.nbytes, self.T, self.row0, self.compressed = lay.nbytes, lay.T, lay.row0, lay.compressed
         self.cloud_rgb_fmt, self.cloud_rgb_bytes = lay.cloud_rgb_fmt, lay.cloud_rgb_bytes
-        if budget_bytes is None:
-            free, _total = torch.cuda.mem_get_info(torch.device(device))
-            budget_bytes = free - DEVICE_STORE_RESERVE_BYTES
-        self.budget_bytes = int(budget_bytes)
-        if self.nbytes > self.budget_bytes:
-            raise MemoryError(f"DeviceEpisodeStore: {len(self.paths)} episodes need {self.nbytes} bytes on the device "
-                              f"({self.nbytes / 2**30:.2f} GiB), the budget is {self.budget_bytes} bytes "
+        # with encoded sources the segments and marks the encode stage holds live beside the arena until they are copied in, and
+        # the stage's device staging counts as well (it is released before the arena is allocated: the check is the safe side)
+        need = self.nbytes + self._held_bytes + self._encode_staging
+        if need > self.budget_bytes:
+            self._held = {}
+            raise MemoryError(f"DeviceEpisodeStore: {len(self.paths)} episodes need {need} bytes on the device "
+                              f"({need / 2**30:.2f} GiB), the budget is {self.budget_bytes} bytes "
                               f"({self.budget_bytes / 2**30:.2f} GiB): train without --device_dataset, or raise --device_dataset_gb")
         self._load(norm_stats)
 
@@ -432,10 +478,8 @@ class DeviceEpisodeStore:
             self.arena[a:b].zero_()                                   # dataset hold the same bytes everywhere
         stage = max(self.stage_bytes, self.frame_bytes, self.depth_bytes, int(lay.src_N.max()) * 12 if self.has_clouds else 0)
         self.cloud_n = np.zeros(int(lay.src_T.sum()) if self.has_clouds else 0, dtype=np.int32)   # valid rows of every stored step
-        self._pin = [torch.empty(stage, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-        self._pin_ev, self._pin_i = [None, None], 0
+        self._open_staging(stage)
         self.decode_stats = {"device": 0, "host": 0}
-        self.bus_bytes = 0                                            # bytes of frames and clouds that crossed to the device
         self._decoders, self._pending, self._jpeg_stream = {}, [], None
         self._init_packed()
         if self.device_decode and any(lay.src_compressed) and not self.store_compressed:
@@ -493,7 +537,9 @@ class DeviceEpisodeStore:
         for kind in self.kinds:
             for k, cam in enumerate(kind.cams):
                 key = f"/observations/{kind.key}/{cam}"
-                if self.store_compressed:
+                if (j, k) in self._held and not kind.is_depth:
+                    self._load_encoded(kind, T, j, k)                 # read and encoded before the plan: not read again
+                elif self.store_compressed:
                     self._load_packed(root[key], kind, T, j, k, f"{path}: {key}")
                 else:
                     self._load_block(root[key], kind, T, compressed, int(kind.src_block_off[j, k]), f"{path}: {key}")
@@ -529,6 +575,16 @@ class DeviceEpisodeStore:
         counts = stored_cloud_counts(root, base, path, T, N, self.pcd_ignore_mask)
         self.cloud_n[int(lay.src_row0[j]):int(lay.src_row0[j]) + T] = counts
 
+    def _open_staging(self, nbytes):
+        """the pinned staging pair, of at least `nbytes` each"""
+        if self._pin is None or self._pin[0].numel() < nbytes:
+            for ev in self._pin_ev:
+                if ev is not None:
+                    ev.synchronize()
+            self._pin = None
+            self._pin = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            self._pin_ev, self._pin_i = [None, None], 0
+
     def _stage(self, dst_off, nbytes, fill, dst=None):
         """one piece through the staging pair: ``fill(view)`` writes `nbytes` bytes into the pinned view, which is then copied to
         the arena (or to `dst`, another device buffer); a buffer is refilled only after the copy that read it has executed"""
@@ -541,7 +597,7 @@ class DeviceEpisodeStore:
         fill(self._pin[j].numpy()[:nbytes])
         dst[dst_off:dst_off + nbytes].copy_(self._pin[j][:nbytes], non_blocking=True)
         self._pin_ev[j] = torch.cuda.Event()
-        self._pin_ev[j].record(torch.cuda.current_stream(self.arena.device))
+        self._pin_ev[j].record(torch.cuda.current_stream(dst.device))
 
     def _load_block(self, entry, kind, T, compressed, dst_off, where):
         """one camera's block, a staging buffer's worth of frames at a time; compressed episodes are decoded once"""
@@ -741,6 +797,112 @@ class DeviceEpisodeStore:
                     self._index_pending.append((status, q, rows, [b for _t, b, _i in part], kind, where))
                     k0 = k1
         self.stream_bytes_used += cursor
+
+    # ---- raw sources encoded at load (store_encode) --------------------------------------------------------------------
+    def _encode_sources(self, headers, cams):
+        """The encode stage, between ``probe_sources`` and ``plan_store``: the planner needs every stream block's bytes before the
+        arena exists.  Every camera entry of a raw source is read ONCE, at most ``decode_frames`` frames a piece, through the pinned
+        staging pair into a device buffer that holds the piece raw.  Per piece: one actmi_op_jpeg_encode launch with windows of 0
+        bytes gives every frame's true seg_len (its contract), the lengths are read back once, and one actmi_op_jpeg_encode_marked
+        launch with exact windows writes the segments back to back into a tensor of their size and the marks into a [n, M + 1, 32]
+        tensor.  The tensors are held until ``_load_encoded`` copies them into the arena.  A nonzero status of the second launch is
+        a bug (``RuntimeError``).  -> the headers, a raw source's with ``encoded``: the exact stream bytes per camera."""
+        from . import ops
+        dev = torch.device(self.device)
+        names = cams[0]
+        todo = [j for j, h in enumerate(headers) if not h.compressed and h.frames[0] is not None]
+        if not todo or not names:
+            return headers
+        (H, W, _c), mode = headers[todo[0]].frames[0][0], self.encode_subsampling
+        fb = H * W * 3
+        packed = [h.packed[0][1] for h in headers if h.packed is not None and h.packed[0] is not None]
+        mpf = max(packed + [ops.jpeg_mark_count(H, mode, self.rows_per_mark) + 1])
+        per = min(self.decode_frames, max(headers[j].T for j in todo))
+        ws_bytes = max(16, ops.jpeg_encode_workspace_bytes(per, H, W, mode))
+        self._encode_staging = per * fb + ws_bytes
+        if self._encode_staging > self.budget_bytes:
+            raise MemoryError(f"DeviceEpisodeStore: the encode stage of store_encode needs {self._encode_staging} bytes on the device "
+                              f"({self._encode_staging / 2**30:.2f} GiB) for {per} frames a launch, the budget is {self.budget_bytes} bytes "
+                              f"({self.budget_bytes / 2**30:.2f} GiB): lower decode_frames, or raise --device_dataset_gb")
+        enc = ops.JpegEncoder(dev, H, W, max_frames=per, quality=self.encode_quality, mode=mode)
+        raw = torch.empty(per * fb, dtype=torch.uint8, device=dev)
+        none = torch.empty(16, dtype=torch.uint8, device=dev)       # the windows of the first launch are empty
+        self._open_staging(max(self.stage_bytes, fb))
+        step = max(1, self._pin[0].numel() // fb)
+        self._encoder_tables = ops.jpeg_parse(ops.jpeg_assemble(enc.header, b""))["tables"]
+        out = list(headers)
+        for j in todo:
+            T, nbytes, checks = headers[j].T, [], []
+            with open_episode(self.sources[j]) as raw_root:
+                root = _EpisodeArrays(raw_root)
+                for k, cam in enumerate(names):
+                    key = f"/observations/images/{cam}"
+                    entry = root[key]
+                    streams, marks, lens = [], [], []
+                    for t0 in range(0, T, per):
+                        n = min(per, T - t0)
+                        piece = np.asarray(entry[t0:t0 + n])
+                        if piece.shape != (n, H, W, 3) or piece.dtype != np.uint8:
+                            raise ValueError(f"{self.sources[j]}: {key}: frames {piece.dtype} {piece.shape[1:]}, the store was sized for {(H, W, 3)}")
+                        for i0 in range(0, n, step):
+                            flat = np.ascontiguousarray(piece[i0:i0 + step]).reshape(-1)
+                            self._stage(i0 * fb, flat.size, lambda view, flat=flat: np.copyto(view, flat), raw)
+                        _d, seg_len, _st = enc.encode(raw[:n * fb], dst=none, records=ops.jpeg_enc_records(n, H, W, 0, dst_off=np.zeros(n, dtype=np.int64)))
+                        ln = seg_len.cpu().numpy().astype(np.int64)   # the one read-back of the launch
+                        if ln.min() < 1:
+                            raise RuntimeError(f"{self.sources[j]}: {key}: the encoder reports a segment of {int(ln.min())} bytes")
+                        rec = ops.jpeg_enc_records(n, H, W, 0, dst_off=_starts(ln))
+                        rec["dst_cap"] = ln
+                        stream = torch.empty(int(ln.sum()), dtype=torch.uint8, device=dev)
+                        mk = torch.zeros((n, mpf, 32), dtype=torch.uint8, device=dev)
+                        _d, seg_len2, status = enc.encode(raw[:n * fb], dst=stream, records=rec, marks=mk.view(-1),
+                                                          first=np.arange(n, dtype=np.int64) * mpf, rows_per_mark=self.rows_per_mark)
+                        checks.append((torch.stack([seg_len2, status]), ln, f"{self.sources[j]}: {key} from step {t0}"))
+                        streams.append(stream)
+                        marks.append(mk)
+                        lens.append(ln)
+                        self._held_bytes += int(stream.numel() + mk.numel())
+                        self.encode_stats["device"] += n
+                    self._held[(j, k)] = (streams, marks, np.concatenate(lens))
+                    nbytes.append(int(sum(int(l.sum()) for l in lens)))
+            for meta, ln, where in checks:                            # read back once per source
+                meta = meta.cpu().numpy()
+                if meta[1].any() or not np.array_equal(meta[0], ln):
+                    raise RuntimeError(f"{where}: the marked encode gave status {meta[1].tolist()} and lengths {meta[0].tolist()} in windows "
+                                       f"of the lengths {ln.tolist()} the first launch gave")
+            out[j] = headers[j]._replace(encoded=((tuple(nbytes), mpf), None))
+        torch.cuda.synchronize(dev)
+        return out
+
+    def _load_encoded(self, kind, T, j, k):
+        """one camera's block of an encoded source: the held segments and marks copied into its stream and mark block, device to
+        device, its rows of the frame tables filled; the held tensors are released"""
+        from . import ops
+        q = self.layout.all_kinds.index(kind)
+        tab = self._ptab[q]
+        H, W = kind.shape[:2]
+        dec = self._decoders.get((H, W))
+        if dec is None:
+            dec = self._decoders[(H, W)] = ops.JpegDecoder(self.device, H, W, max_frames=self.decode_frames)
+        streams, marks, lens = self._held.pop((j, k))
+        row0 = int(self._frame_row(q, j, k))
+        s0, cap = int(kind.src_block_off[j, k]), int(kind.stream_cap[j, k])
+        m0, mpf = int(kind.mark_off[j, k]), int(kind.marks_per_frame)
+        if len(lens) != T or int(lens.sum()) != cap or any(int(m.shape[1]) != mpf for m in marks) or m0 % 32:
+            raise RuntimeError(f"{self.sources[j]}: the encoded block of camera {k} does not fit the plan")
+        o, t = s0, 0
+        for stream, mk in zip(streams, marks):
+            self.arena[o:o + stream.numel()].copy_(stream)
+            self.arena[m0 + t * mpf * 32:m0 + (t + mk.shape[0]) * mpf * 32].copy_(mk.view(-1))
+            self._held_bytes -= int(stream.numel() + mk.numel())
+            o, t = o + int(stream.numel()), t + int(mk.shape[0])
+        rows = row0 + np.arange(T, dtype=np.int64)
+        rec = tab["rec"]
+        rec["seg_len"][rows], rec["seg_off"][rows] = lens, s0 + _starts(lens)
+        rec["restart_interval"][rows], rec["table_set"][rows] = 0, dec.table_index(self._encoder_tables)
+        tab["first"][rows] = (m0 + np.arange(T, dtype=np.int64) * mpf * 32) // 32
+        tab["mode"][rows] = ops.JPEG_MODES[self.encode_subsampling]
+        self.stream_bytes_used += cap
 
     def _spill_frame(self, q, row, buf, kind, where):
         """a frame the device does not take: decoded by ``imdecode_bgr`` (a bad file raises what it raises today), kept raw"""

@@ -322,6 +322,8 @@ def load():
         "actmi_jpeg_encode_bound": ([i32, i32, i32], i64),
         "actmi_op_jpeg_encode": ([C.POINTER(JpegEncDesc), vp], i32),
         "actmi_jpeg_encode_host": ([C.POINTER(JpegEncDesc)], i32),
+        "actmi_op_jpeg_encode_marked": ([C.POINTER(JpegEncDesc), C.POINTER(JpegMarks), vp], i32),
+        "actmi_jpeg_encode_marked_host": ([C.POINTER(JpegEncDesc), C.POINTER(JpegMarks)], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

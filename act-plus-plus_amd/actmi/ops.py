@@ -3560,10 +3560,11 @@ def _jpeg_edge(p, rows, cols):
     return np.pad(p, ((0, rows - p.shape[0]), (0, cols - p.shape[1])), mode="edge")
 
 
-def jpeg_encode_segment_ref(frame, quality=50, mode="420", form="bgr", symbols=None):
+def jpeg_encode_segment_ref(frame, quality=50, mode="420", form="bgr", symbols=None, row_states=None):
     """The numpy statement of actmi_op_jpeg_encode (the text is at its declaration in actmi.h): `frame` uint8 [H, W, 3] -> the
     entropy segment as bytes.  ``symbols``: a list that receives (table, symbol) of every Huffman symbol emitted, table 0..3 in the
-    order of the file's DHT segments (DC luma, AC luma, DC chroma, AC chroma)."""
+    order of the file's DHT segments (DC luma, AC luma, DC chroma, AC chroma).  ``row_states``: a list that receives, before every
+    MCU row and once after the last, (the data bits put so far, the three DC predictors); a last entry holds the unstuffed bytes."""
     import numpy as np
     _jpeg_enc_args(mode, form, quality)
     f = np.asarray(frame)
@@ -3596,11 +3597,12 @@ def jpeg_encode_segment_ref(frame, quality=50, mode="420", form="bgr", symbols=N
         coef.append(b.reshape(b.shape[0], b.shape[1], 64)[..., zz])
     tables = _jpeg_std_codes()
     rbw, rbh = -(-W // 8), -(-H // 8)
-    bits, pred, last_dc = [], [0, 0, 0], 0
+    bits, pred, last_dc, nbits = [], [0, 0, 0], 0, [0]
 
     def put(code, size):
         if size:
             bits.append(format(code, f"0{size}b"))
+            nbits[0] += size
 
     def sym(t, s):
         if symbols is not None:
@@ -3611,6 +3613,8 @@ def jpeg_encode_segment_ref(frame, quality=50, mode="420", form="bgr", symbols=N
         put(v + (1 << s) - 1 if v < 0 else v, s)
 
     for my in range(mh):
+        if row_states is not None:
+            row_states.append((nbits[0], tuple(pred)))
         for mx in range(mw):
             for c in range(3):
                 dc_t, ac_t = (0, 1) if c == 0 else (2, 3)
@@ -3646,7 +3650,34 @@ def jpeg_encode_segment_ref(frame, quality=50, mode="420", form="bgr", symbols=N
                             sym(ac_t, 0x00)
     s = "".join(bits)
     s += "1" * (-len(s) % 8)
-    return int(s, 2).to_bytes(len(s) // 8, "big").replace(b"\xff", b"\xff\x00")
+    unstuffed = int(s, 2).to_bytes(len(s) // 8, "big")
+    if row_states is not None:
+        row_states += [(nbits[0], tuple(pred)), unstuffed]
+    return unstuffed.replace(b"\xff", b"\xff\x00")
+
+
+def jpeg_encode_marks_ref(frame, quality=50, mode="420", form="bgr", rows_per_mark=1):
+    """numpy statement of the marks actmi_op_jpeg_encode_marked writes for one frame (the rule is at its declaration in actmi.h),
+    from the encoder's symbol walk and not from a decode of what it wrote: ``jpeg_mark_dtype`` records [M + 1], M = ceil(my /
+    rows_per_mark).  Mark j, the state before MCU row j * rows_per_mark (mark M: after the last MCU), with b the data bits put before
+    it and u = b >> 3: bit = b & 7, byte_off = u + the 0xFF bytes among the unstuffed bytes [0, u), pred the DC predictors the walk
+    holds there, togo = rst = 0."""
+    import numpy as np
+    R = int(rows_per_mark)
+    if R < 1:
+        raise ValueError("jpeg_encode_marks_ref: rows_per_mark must be at least 1")
+    states = []
+    jpeg_encode_segment_ref(frame, quality, mode, form, row_states=states)
+    unstuffed, states = np.frombuffer(states[-1], dtype=np.uint8), states[:-1]
+    my = len(states) - 1
+    M = -(-my // R)
+    marks = np.zeros(M + 1, dtype=jpeg_mark_dtype())
+    ff_before = np.concatenate([[0], np.cumsum(unstuffed == 0xFF)])   # [u]: 0xFF bytes among [0, u)
+    for j in range(M + 1):
+        b, pred = states[min(j * R, my)]
+        u = b >> 3
+        marks[j]["byte_off"], marks[j]["bit"], marks[j]["pred"] = u + int(ff_before[u]), b & 7, pred
+    return marks
 
 
 def jpeg_encode_ref(frame, quality=50, mode="420", form="bgr"):
@@ -3693,10 +3724,23 @@ def _jpeg_enc_desc(H, W, quality, mode, form, q=None):
     return d
 
 
-def jpeg_encode_host_raw(src, records, dst, H, W, quality=50, mode="420", form="bgr", ws=None, q=None):
+def _jpeg_enc_marks(what, marks, first, rows_per_mark, n):
+    """the three mark arguments of an encode come together or not at all -> whether they came"""
+    given = [a is not None for a in (marks, first, rows_per_mark)]
+    if any(given) and not all(given):
+        raise ValueError(f"{what}: marks, first and rows_per_mark come together")
+    if given[0] and int(rows_per_mark) < 1:
+        raise ValueError(f"{what}: rows_per_mark must be at least 1")
+    return given[0]
+
+
+def jpeg_encode_host_raw(src, records, dst, H, W, quality=50, mode="420", form="bgr", ws=None, q=None, marks=None, first=None,
+                         rows_per_mark=None):
     """actmi_jpeg_encode_host, the CPU twin of ``JpegEncoder.encode`` (the same core, no device), on the caller's buffers: `src` and
     `dst` contiguous 1-D uint8 arrays, `records` ``jpeg_enc_frame_dtype`` -> (seg_len, status), int32 [n] each.  ``ws``: a 16-byte
-    aligned uint8 array of at least ``jpeg_encode_workspace_bytes`` bytes; ``q``: quantisation tables in place of the quality's."""
+    aligned uint8 array of at least ``jpeg_encode_workspace_bytes`` bytes; ``q``: quantisation tables in place of the quality's.
+    ``marks`` (a contiguous 1-D ``jpeg_mark_dtype`` array, written in place), ``first`` (int64 [n]: the index of every frame's mark
+    0) and ``rows_per_mark``: actmi_jpeg_encode_marked_host instead, which also writes every frame's marks."""
     import numpy as np
     for name, a in (("src", src), ("dst", dst)):
         if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
@@ -3710,6 +3754,16 @@ def jpeg_encode_host_raw(src, records, dst, H, W, quality=50, mode="420", form="
     seg_len, status = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
     d.src, d.src_bytes, d.frames, d.dst, d.dst_bytes = src.ctypes.data, src.size, rec.ctypes.data, dst.ctypes.data, dst.size
     d.ws, d.ws_bytes, d.seg_len, d.status, d.n = ws.ctypes.data, ws.size, seg_len.ctypes.data, status.ctypes.data, n
+    if _jpeg_enc_marks("jpeg_encode_host", marks, first, rows_per_mark, n):
+        if not isinstance(marks, np.ndarray) or marks.dtype != jpeg_mark_dtype() or marks.ndim != 1 or not marks.flags.c_contiguous:
+            raise ValueError("jpeg_encode_host: marks must be a contiguous 1-D array of jpeg_mark_dtype records")
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        if first.shape != (n,):
+            raise ValueError("jpeg_encode_host: first must hold one index per frame")
+        m = L.JpegMarks()
+        m.marks, m.n_marks, m.first, m.rows_per_mark = marks.ctypes.data if marks.size else None, marks.size, first.ctypes.data, int(rows_per_mark)
+        L.check(lib.actmi_jpeg_encode_marked_host(C.byref(d), C.byref(m)), None, "jpeg_encode_marked_host")
+        return seg_len, status
     L.check(lib.actmi_jpeg_encode_host(C.byref(d)), None, "jpeg_encode_host")
     return seg_len, status
 
@@ -3799,11 +3853,14 @@ class JpegEncoder:
             self._rec, self._rec_cap = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(self.device), cap
         return self._rec
 
-    def encode(self, src, dst=None, cap=None, form="bgr", records=None):
+    def encode(self, src, dst=None, cap=None, form="bgr", records=None, marks=None, first=None, rows_per_mark=None):
         """src: contiguous uint8 tensor on the device, n frames [H, W, 3] back to back (``records`` None) -> (dst, seg_len, status):
         dst uint8 [n * cap] on the device (``cap`` defaults to ``default_cap``; a frame that needs more has status DEST), seg_len
         and status int32 [n] on the device.  ``records``: ``jpeg_enc_frame_dtype`` records (numpy) that place every frame in `src`
-        and its window in the caller's `dst` instead."""
+        and its window in the caller's `dst` instead.  ``marks`` (a contiguous, 8-byte aligned uint8 tensor of 32-byte
+        ``jpeg_mark_dtype`` records on the device; it may be a view of `dst`'s buffer), ``first`` (int64 [n], numpy or on the device:
+        the index of every frame's mark 0) and ``rows_per_mark``: actmi_op_jpeg_encode_marked instead, which also writes every
+        frame's marks (status MARK for a frame whose marks would leave the tensor)."""
         import numpy as np
         _jpeg_enc_args(self.mode, form)
         if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.device != self.device or not src.is_contiguous():
@@ -3834,11 +3891,26 @@ class JpegEncoder:
         d.src, d.src_bytes, d.dst, d.dst_bytes = src.data_ptr(), int(src.numel()), dst.data_ptr(), int(dst.numel())
         d.ws, d.ws_bytes = self._ws.data_ptr(), int(self._ws.numel())
         lib = L.load()
+        m = None
+        if _jpeg_enc_marks("JpegEncoder", marks, first, rows_per_mark, n):
+            if not torch.is_tensor(marks) or marks.dtype != torch.uint8 or marks.device != self.device or not marks.is_contiguous() or \
+                    marks.numel() % 32 or marks.data_ptr() % 8:
+                raise ValueError(f"JpegEncoder: marks must be a contiguous, 8-byte aligned uint8 tensor of 32-byte records on {self.device}")
+            if not torch.is_tensor(first):
+                first = torch.from_numpy(np.ascontiguousarray(first, dtype=np.int64)).to(self.device)
+            if first.dtype != torch.int64 or first.device != self.device or not first.is_contiguous() or first.numel() != n:
+                raise ValueError(f"JpegEncoder: first must hold one int64 index per frame on {self.device}")
+            m = L.JpegMarks()
+            m.marks, m.n_marks, m.rows_per_mark = marks.data_ptr(), marks.numel() // 32, int(rows_per_mark)
         with torch.cuda.device(self.device):
             for i0 in range(0, n, self.max_frames):
                 d.frames, d.seg_len, d.status = rec.data_ptr() + 32 * i0, seg_len.data_ptr() + 4 * i0, status.data_ptr() + 4 * i0
                 d.n = min(self.max_frames, n - i0)
-                L.check(lib.actmi_op_jpeg_encode(C.byref(d), L.current_stream_ptr()), None, "op_jpeg_encode")
+                if m is None:
+                    L.check(lib.actmi_op_jpeg_encode(C.byref(d), L.current_stream_ptr()), None, "op_jpeg_encode")
+                else:
+                    m.first = first.data_ptr() + 8 * i0
+                    L.check(lib.actmi_op_jpeg_encode_marked(C.byref(d), C.byref(m), L.current_stream_ptr()), None, "op_jpeg_encode_marked")
         return dst, seg_len, status
 
     def files(self, src, form="bgr"):

@@ -652,6 +652,19 @@ int actmi_jpeg_encode_host(const actmi_jpeg_enc_desc* d) {
     return jpeg_encode_host(*d, &g_op_error) == 0 ? ACTMI_OK : ACTMI_E_INVALID;
 }
 
+int actmi_op_jpeg_encode_marked(const actmi_jpeg_enc_desc* d, const actmi_jpeg_marks* m, void* stream) {
+    g_op_error.clear();
+    if (!d || !m) { g_op_error = "jpeg_encode_marked: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_jpeg_encode_marked(*d, *m, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
+int actmi_jpeg_encode_marked_host(const actmi_jpeg_enc_desc* d, const actmi_jpeg_marks* m) {
+    g_op_error.clear();
+    if (!d || !m) { g_op_error = "jpeg_encode_marked: null descriptor"; return ACTMI_E_INVALID; }
+    return jpeg_encode_marked_host(*d, *m, &g_op_error) == 0 ? ACTMI_OK : ACTMI_E_INVALID;
+}
+
 int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int64_t n_per_sample, void* stream) {
     g_op_error.clear();
     const int rc = launch_depth_minmax_u16(depth, lohi_out, B, n_per_sample, S(stream));

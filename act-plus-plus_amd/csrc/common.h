@@ -290,6 +290,9 @@ int64_t jpeg_encode_workspace_bytes(int64_t n, int H, int W, int mode);
 int64_t jpeg_encode_bound(int H, int W, int mode);
 int launch_jpeg_encode(const actmi_jpeg_enc_desc& d, hipStream_t st, std::string* err);
 int jpeg_encode_host(const actmi_jpeg_enc_desc& d, std::string* err);   // the same core on the CPU, host pointers
+// the encode that also writes each frame's marks (contract at actmi_op_jpeg_encode_marked)
+int launch_jpeg_encode_marked(const actmi_jpeg_enc_desc& d, const actmi_jpeg_marks& mk, hipStream_t st, std::string* err);
+int jpeg_encode_marked_host(const actmi_jpeg_enc_desc& d, const actmi_jpeg_marks& mk, std::string* err);
 
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------
 bool prof_enabled();

@@ -463,12 +463,44 @@ JPEG_HD void jpeg_enc_stuff(const uint32_t* words, int64_t i0, int64_t i1, int64
     }
 }
 
-// ---- the host twin's frame: every pass of frame f of a checked descriptor, serially
-inline void jpeg_encode_frame_host(const actmi_jpeg_enc_desc& d, const JpegEncGeom& g, const JpegEncHuff& hf, int f) {
+// ---- marks written by the encoder (the definition is at actmi_op_jpeg_encode_marked in actmi.h).  M for any rows_per_mark >= 1
+JPEG_HD int jpeg_enc_mark_count(const JpegEncGeom* g, int rows_per_mark) {
+    return rows_per_mark >= g->my ? 1 : (g->my + rows_per_mark - 1) / rows_per_mark;
+}
+
+// Mark j of a frame whose passes are done: the state before MCU row min(j R, my), from the row's bit offset, the chunks' 0xFF
+// prefix sums, the unstuffed words and the scan-order coefficients.  Every value read from the slot is clamped before it is used
+// as an index, so the reads stay inside the slot whatever it holds: the bit offset to the stream's size, which puts the chunk
+// index in [0, nchunks] and the byte walk (at most JPEG_ENC_CHUNK - 1 bytes) inside the words.
+JPEG_HD void jpeg_enc_mark(const JpegEncGeom* g, const int64_t* rows, const int16_t* coef, const uint32_t* words, const int32_t* chunks,
+                           int R, int j, actmi_jpeg_mark* out) {
+    int64_t row = (int64_t)j * R;
+    row = row < g->my ? row : g->my;
+    int64_t b = rows[row];
+    b = b < 0 ? 0 : (b > 8 * g->bits_bytes ? 8 * g->bits_bytes : b);
+    const int64_t u = b >> 3, c = u / JPEG_ENC_CHUNK;
+    actmi_jpeg_mark m;
+    m.byte_off = u + chunks[c] + jpeg_enc_count_ff(words, c * JPEG_ENC_CHUNK, u);
+    m.bit = (int32_t)(b & 7);
+    const int64_t blk0 = row * g->mx * g->bpm;                    // the row's first block; the blocks before it end with Y.., Cb, Cr
+    const int ny = g->hs * g->vs;
+    m.pred[0] = blk0 ? coef[(blk0 - g->bpm + ny - 1) * 64] : 0;
+    m.pred[1] = blk0 ? coef[(blk0 - 2) * 64] : 0;
+    m.pred[2] = blk0 ? coef[(blk0 - 1) * 64] : 0;
+    m.togo = 0;
+    m.rst = 0;
+    *out = m;
+}
+
+// ---- the host twin's frame: every pass of frame f of a checked descriptor, serially (mk: null, or where the frame's marks go as well)
+inline void jpeg_encode_frame_host(const actmi_jpeg_enc_desc& d, const JpegEncGeom& g, const JpegEncHuff& hf, int f,
+                                   const actmi_jpeg_marks* mk = nullptr) {
     const actmi_jpeg_enc_frame& rec = d.frames[f];
     d.seg_len[f] = 0;
+    const int M = mk ? jpeg_enc_mark_count(&g, mk->rows_per_mark) : 0;
+    const bool marked = mk && jpeg_marks_inside(mk->first[f], M, mk->n_marks);
     if (!jpeg_enc_src_inside(rec.src_off, &g, d.src_bytes)) {
-        d.status[f] = ACTMI_JPEG_ST_DEST;
+        d.status[f] = mk && !marked ? ACTMI_JPEG_ST_MARK : ACTMI_JPEG_ST_DEST;
         return;
     }
     uint8_t* slot = static_cast<uint8_t*>(d.ws) + (int64_t)f * g.slot_bytes;
@@ -495,4 +527,7 @@ inline void jpeg_encode_frame_host(const actmi_jpeg_enc_desc& d, const JpegEncGe
         const int64_t i1 = (c + 1) * JPEG_ENC_CHUNK < L ? (c + 1) * JPEG_ENC_CHUNK : L;
         jpeg_enc_stuff(words, c * JPEG_ENC_CHUNK, i1, chunks[c], inside ? d.dst + rec.dst_off : d.dst, cap);
     }
+    if (mk && !marked) d.status[f] = ACTMI_JPEG_ST_MARK;
+    if (marked)
+        for (int j = 0; j <= M; ++j) jpeg_enc_mark(&g, rows, coef, words, chunks, mk->rows_per_mark, j, mk->marks + mk->first[f] + j);
 }

@@ -5,6 +5,8 @@
 //   scan:   one lane per frame: row counts -> row offsets; the words two rows share are zeroed.
 //   pack:   one lane per MCU row: its bits at its offset; stores for the words it owns, atomic OR for its first and last word.
 //   stuff:  one workgroup per frame: 0xFF bytes per chunk, their scan, seg_len and status, the copy into dst with 0x00 inserted.
+// actmi_op_jpeg_encode_marked is the same five launches; its stuffing kernel also writes the frame's marks, lane j mark j, j + 256,
+// ..., from what the slot holds by then (jpeg_enc_mark).
 #include "common.h"
 #include "jpeg_enc_core.h"
 
@@ -71,14 +73,18 @@ __global__ __launch_bounds__(64) void jpeg_enc_scan_kernel(const actmi_jpeg_enc_
     jpeg_enc_scan_rows(&g, reinterpret_cast<int64_t*>(slot + g.rows_off), reinterpret_cast<uint32_t*>(slot + g.bits_off));
 }
 
-// grid n: one workgroup per frame, a lane the chunks tid, tid + 256, ...
-__global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_stuff_kernel(const actmi_jpeg_enc_desc d, const JpegEncGeom g) {
+// grid n: one workgroup per frame, a lane the chunks tid, tid + 256, ...; MARKS: and the marks tid, tid + 256, ...
+template <bool MARKS>
+__global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_stuff_kernel(const actmi_jpeg_enc_desc d, const JpegEncGeom g, const actmi_jpeg_marks mk) {
     const int f = blockIdx.x, tid = threadIdx.x;
     const actmi_jpeg_enc_frame rec = d.frames[f];
-    if (!jpeg_enc_src_inside(rec.src_off, &g, d.src_bytes)) {     // uniform over the workgroup
+    const int M = MARKS ? jpeg_enc_mark_count(&g, mk.rows_per_mark) : 0;
+    const int64_t first = MARKS ? mk.first[f] : 0;
+    const bool marked = MARKS && jpeg_marks_inside(first, M, mk.n_marks);   // uniform over the workgroup, as everything up to the loops
+    if (!jpeg_enc_src_inside(rec.src_off, &g, d.src_bytes)) {
         if (tid == 0) {
             d.seg_len[f] = 0;
-            d.status[f] = ACTMI_JPEG_ST_DEST;
+            d.status[f] = MARKS && !marked ? ACTMI_JPEG_ST_MARK : ACTMI_JPEG_ST_DEST;
         }
         return;
     }
@@ -108,13 +114,26 @@ __global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_stuff_kernel(const actmi_jp
     const int64_t cap = inside ? rec.dst_cap : 0;
     if (tid == 0) {
         d.seg_len[f] = (int32_t)len;
-        d.status[f] = inside && len <= cap ? ACTMI_JPEG_ST_OK : ACTMI_JPEG_ST_DEST;
+        d.status[f] = MARKS && !marked ? ACTMI_JPEG_ST_MARK : (inside && len <= cap ? ACTMI_JPEG_ST_OK : ACTMI_JPEG_ST_DEST);
     }
     uint8_t* out = inside ? d.dst + rec.dst_off : d.dst;
     for (int64_t c = tid; c < nch; c += JE_BLOCK) {
         const int64_t i1 = (c + 1) * JPEG_ENC_CHUNK < L ? (c + 1) * JPEG_ENC_CHUNK : L;
         jpeg_enc_stuff(words, c * JPEG_ENC_CHUNK, i1, chunks[c], out, cap);
     }
+    if (marked) {                                                 // first + j stays in [first, first + M], which lies in [0, n_marks)
+        const int16_t* coef = reinterpret_cast<const int16_t*>(slot + g.coef_off);
+        for (int j = tid; j <= M; j += JE_BLOCK) jpeg_enc_mark(&g, rows, coef, words, chunks, mk.rows_per_mark, j, mk.marks + first + j);
+    }
+}
+
+const char* jpeg_enc_marks_check(const actmi_jpeg_enc_desc& d, const actmi_jpeg_marks& mk) {
+    if (mk.rows_per_mark < 1) return "jpeg_encode_marked: rows_per_mark must be at least 1";
+    if (d.n == 0) return nullptr;
+    if (!mk.marks || !mk.first) return "jpeg_encode_marked: null marks or first";
+    if (mk.n_marks < 0) return "jpeg_encode_marked: negative n_marks";
+    if (((uintptr_t)mk.marks | (uintptr_t)mk.first) & 7) return "jpeg_encode_marked: marks and first must be 8-byte aligned";
+    return nullptr;
 }
 
 const char* jpeg_enc_check(const actmi_jpeg_enc_desc& d, JpegEncGeom* g) {
@@ -149,9 +168,12 @@ int64_t jpeg_encode_bound(int H, int W, int mode) {
     return jpeg_enc_bound(&g);
 }
 
-int launch_jpeg_encode(const actmi_jpeg_enc_desc& d, hipStream_t st, std::string* err) {
+// mk: null (actmi_op_jpeg_encode), or where the stuffing kernel writes the marks as well
+static int launch_jpeg_encode_passes(const actmi_jpeg_enc_desc& d, const actmi_jpeg_marks* mk, hipStream_t st, std::string* err) {
     JpegEncGeom g;
     if (const char* m = jpeg_enc_check(d, &g)) { if (err) *err = m; return -2; }
+    if (mk)
+        if (const char* m = jpeg_enc_marks_check(d, *mk)) { if (err) *err = m; return -2; }
     if (d.n == 0) return 0;
     const int64_t coef_groups = (g.nblocks + JE_BLOCK - 1) / JE_BLOCK;
     const int64_t row_groups = ((int64_t)d.n * g.my + 63) / 64;
@@ -170,10 +192,17 @@ int launch_jpeg_encode(const actmi_jpeg_enc_desc& d, hipStream_t st, std::string
     hipLaunchKernelGGL(jpeg_enc_rows_kernel<true>, dim3((unsigned)row_groups), dim3(64), 0, st, d, g);
     prof_end(st);
     prof_begin("jpeg_enc_stuff", 0.0, 0.0, st);
-    hipLaunchKernelGGL(jpeg_enc_stuff_kernel, dim3((unsigned)d.n), dim3(JE_BLOCK), 0, st, d, g);
+    if (mk) hipLaunchKernelGGL(jpeg_enc_stuff_kernel<true>, dim3((unsigned)d.n), dim3(JE_BLOCK), 0, st, d, g, *mk);
+    else hipLaunchKernelGGL(jpeg_enc_stuff_kernel<false>, dim3((unsigned)d.n), dim3(JE_BLOCK), 0, st, d, g, actmi_jpeg_marks{});
     prof_end(st);
     if (hipGetLastError() != hipSuccess) { if (err) *err = "jpeg_encode: launch failed"; return -3; }
     return 0;
+}
+
+int launch_jpeg_encode(const actmi_jpeg_enc_desc& d, hipStream_t st, std::string* err) { return launch_jpeg_encode_passes(d, nullptr, st, err); }
+
+int launch_jpeg_encode_marked(const actmi_jpeg_enc_desc& d, const actmi_jpeg_marks& mk, hipStream_t st, std::string* err) {
+    return launch_jpeg_encode_passes(d, &mk, st, err);
 }
 
 // the host twin: the same core, frame by frame
@@ -183,5 +212,15 @@ int jpeg_encode_host(const actmi_jpeg_enc_desc& d, std::string* err) {
     JpegEncHuff hf;
     jpeg_enc_huff_build(&hf);
     for (int f = 0; f < d.n; ++f) jpeg_encode_frame_host(d, g, hf, f);
+    return 0;
+}
+
+int jpeg_encode_marked_host(const actmi_jpeg_enc_desc& d, const actmi_jpeg_marks& mk, std::string* err) {
+    JpegEncGeom g;
+    if (const char* m = jpeg_enc_check(d, &g)) { if (err) *err = m; return -2; }
+    if (const char* m = jpeg_enc_marks_check(d, mk)) { if (err) *err = m; return -2; }
+    JpegEncHuff hf;
+    jpeg_enc_huff_build(&hf);
+    for (int f = 0; f < d.n; ++f) jpeg_encode_frame_host(d, g, hf, f, &mk);
     return 0;
 }

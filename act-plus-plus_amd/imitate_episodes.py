@@ -964,6 +964,13 @@ def build_config(args):
             raise ValueError("--store_compressed keeps the device-resident store's frames compressed and decodes every batch on the "
                              "device: it needs --device_dataset --device_decode")
         config["store_compressed"] = True
+    if args.get("store_encode"):
+        if not args.get("store_compressed"):
+            raise ValueError("--store_encode encodes raw episodes into the store that stays compressed: it needs --store_compressed "
+                             "(and --device_dataset --device_decode)")
+        config["store_encode"] = True
+        config["store_encode_quality"] = int(args.get("store_encode_quality") or 50)
+        config["store_encode_subsampling"] = str(args.get("store_encode_subsampling") or "420")
     if args.get("device_clouds"):
         if not (args.get("device_dataset") and args.get("use_pcd")):
             raise ValueError("--device_clouds puts the stored clouds of a --use_pcd dataset into the device-resident store: it needs "
@@ -1044,7 +1051,8 @@ def _load_episode_data(args, config, task_config, dataset_dir, world, local_rank
                      # --device_dataset: every rank holds its own full store on its own device
                      device_dataset=bool(config.get("device_dataset")), mirror_twins=bool(config.get("mirror_twins")),
                      device_clouds=bool(config.get("device_clouds")), device_decode=bool(config.get("device_decode")),
-                     store_compressed=bool(config.get("store_compressed")),
+                     store_compressed=bool(config.get("store_compressed")), store_encode=bool(config.get("store_encode")),
+                     encode_quality=config.get("store_encode_quality", 50), encode_subsampling=config.get("store_encode_subsampling", "420"),
                      cloud_mirror=tuple(config["cloud_mirror"]) if config.get("cloud_mirror") else None,
                      device=f"cuda:{local_rank}" if world > 1 else None,     # train_bc's device
                      device_budget_bytes=(int(config["device_dataset_gb"] * 2**30)
@@ -1238,6 +1246,13 @@ def make_parser():
                         help="--device_dataset --device_decode, opt-in: the store keeps the frames' entropy segments and per-row marks "
                              "(about 1/35 of the decoded bytes) and decodes every batch on the device (actmi_op_jpeg_decode_marked); the "
                              "batches are the same bytes")
+    parser.add_argument("--store_encode", action="store_true",
+                        help="--store_compressed, opt-in: raw episodes (uint8 camera frames) are encoded on the device as the store "
+                             "reads them (actmi_op_jpeg_encode_marked, which also writes the marks: no index pass); raw and compressed "
+                             "files may be mixed; the batches are those of compress_data.py followed by --store_compressed")
+    parser.add_argument("--store_encode_quality", action="store", type=int, default=50, help="--store_encode: JPEG quality, 1..100")
+    parser.add_argument("--store_encode_subsampling", action="store", type=str, choices=("420", "444"), default="420",
+                        help="--store_encode: chroma subsampling")
     parser.add_argument("--cloud_mirror_axis", action="store", type=str, choices=("x", "y", "z"), default=None,
                         help="--mirror_twins --use_pcd: the twin's stored cloud is the source's reflected across a plane normal to "
                              "this axis of the clouds' frame; lifts the refusal of --mirror_twins with --use_pcd")

@@ -1313,6 +1313,32 @@ int64_t actmi_op_jpeg_encode_workspace_bytes(int64_t n, int H, int W, int mode);
 int64_t actmi_jpeg_encode_bound(int H, int W, int mode);                           /* -1 for a bad argument or a bound above int32 */
 int actmi_op_jpeg_encode(const actmi_jpeg_enc_desc* d, void* stream);
 int actmi_jpeg_encode_host(const actmi_jpeg_enc_desc* d);
+/* ---- marks written by the encoder ----------------------------------------------------------------------------------------------
+ * actmi_op_jpeg_encode_marked is actmi_op_jpeg_encode (the same five launches, the same segment bytes, seg_len and contract) whose
+ * stuffing kernel also writes, for every frame f, the M + 1 marks of its segment, M = ceil(my / R), R = m->rows_per_mark, my the
+ * frame's MCU rows, to m->marks[first[f] .. first[f] + M], in the format and position convention of actmi_jpeg_mark.  m->sticky is
+ * not used.  DEFINITION: the marks of a frame with status 0 are, all 32 bytes of each, what actmi_op_jpeg_index writes for the
+ * segment the encoder wrote, taken with restart_interval 0, the standard tables and the same rows_per_mark; where the rule below
+ * and the index pass disagree, the index pass is right.  actmi.ops.jpeg_encode_marks_ref states the rule in numpy.
+ * The rule, from the encoder's side.  Mark j is the state before MCU row jR, mark M the state after the last MCU.  Let b be the
+ * number of data bits before that row (the scan pass's exclusive row offset; for mark M the total, before the pad bits), u = b >> 3:
+ *   bit = b & 7;   byte_off = u + (the number of 0xFF bytes among the unstuffed bytes [0, u))
+ * so byte_off is the 0xFF of a stuffed pair when bit > 0 and the data byte u is 0xFF, lies behind the pair's 0x00 when bit == 0 and
+ * byte u - 1 was 0xFF, and equals seg_len for a last mark at a byte boundary.  pred[c] is the quantised DC of the last block of
+ * component c that precedes the row in scan order, 0 for row 0 (a dummy Y block carries the DC of the block before it, so the
+ * last Y block of the MCU before the row is right whether it is real or not).  togo = 0 and rst = 0.
+ * Lane j of the frame's stuffing workgroup writes the marks j, j + 256, ... from what the slot holds after the passes: the row bit
+ * offsets, the 256-byte chunks' 0xFF prefix sums (the 0xFF bytes ahead of u are the prefix of u's chunk and a walk of at most 255
+ * bytes), the unstuffed words and the scan-order coefficients.  No launch is added.
+ * Contract, for ANY pixels and records: mark writes stay inside [first[f], first[f] + M]; a frame whose range leaves [0, n_marks)
+ * gets status ACTMI_JPEG_ST_MARK (whatever else is wrong with it) and none of its marks is written, its segment and seg_len are
+ * written as by actmi_op_jpeg_encode; the marks of a frame with another nonzero status are unspecified but in range; every value
+ * read from the slot is clamped before it indexes the slot.  marks and dst may be views of one buffer when the mark ranges and
+ * the segment windows are disjoint.  ACTMI_E_INVALID before any launch: what actmi_op_jpeg_encode refuses, rows_per_mark < 1, and,
+ * with n > 0, null marks or first, a negative n_marks, marks or first not 8-byte aligned.  actmi_jpeg_encode_marked_host runs the
+ * same core serially over host pointers. */
+int actmi_op_jpeg_encode_marked(const actmi_jpeg_enc_desc* d, const actmi_jpeg_marks* m, void* stream);
+int actmi_jpeg_encode_marked_host(const actmi_jpeg_enc_desc* d, const actmi_jpeg_marks* m);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
