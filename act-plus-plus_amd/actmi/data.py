@@ -324,7 +324,8 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
               f32_depth=False, pointcloud_names=None, use_pcd=False, max_points=None, pcd_ignore_mask=False,
               device_dataset=False, device=None, device_budget_bytes=None, mirror_twins=False, mirror_spec=None,
               device_clouds=False, cloud_mirror=None, device_decode=False,
-              store_compressed=False, rows_per_mark=1, store_encode=False, encode_quality=50, encode_subsampling="420"):
+              store_compressed=False, rows_per_mark=1, store_encode=False, encode_quality=50, encode_subsampling="420",
+              depth_pack=False):
     """utils.py:249-301.  Returns (train_dataloader, val_dataloader, norm_stats, is_sim).  ``use_depth``: the batches are
     5-tuples that end in the depth frames of ``depth_camera_names`` (EpisodicDataset).  ``use_pcd``: 7-tuples that end in the
     padded clouds and their valid counts (collate_pcd).  ``device_dataset``: both loaders come from ONE ``DeviceEpisodeStore``
@@ -339,7 +340,14 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
     and the device loaders deliver the 7-tuples of ``collate_pcd``, gathered by ``actmi_op_gather_clouds``.  ``device_decode``: the store
     decodes the frames of compressed episodes on the device (``DeviceEpisodeStore``); the batches are the same bytes.
     ``store_encode`` (with ``store_compressed``): raw episodes are encoded on the device as the store reads them, at
-    ``encode_quality`` / ``encode_subsampling``; the batches are those of a compressed store of ``compress_dataset_dir``'s output."""
+    ``encode_quality`` / ``encode_subsampling``; the batches are those of a compressed store of ``compress_dataset_dir``'s output.
+    ``depth_pack`` (with ``store_encode`` and ``use_depth``): the raw uint16 depth of raw episodes is packed losslessly on the device
+    and unpacked for every batch (``DeviceEpisodeStore``); the depth tensors are those of the decoded store."""
+    if depth_pack and not store_encode:
+        raise ValueError("depth_pack packs the raw depth of episodes the store encodes as it loads them: it needs store_encode "
+                         "(and store_compressed, device_decode, device_dataset)")
+    if depth_pack and not use_depth:
+        raise ValueError("depth_pack packs depth frames: it needs use_depth")
     if device_decode and not device_dataset:
         raise ValueError("device_decode decodes the compressed frames of the device-resident store: it needs device_dataset")
     if store_compressed and not (device_dataset and device_decode):
@@ -416,6 +424,7 @@ def load_data(dataset_dir_l, name_filter, camera_names, batch_size_train, batch_
                                    device, depth_camera_names, use_depth, device_budget_bytes, use_pcd, policy_class,
                                    device_decode=device_decode, store_compressed=store_compressed, rows_per_mark=rows_per_mark,
                                    store_encode=store_encode, encode_quality=encode_quality, encode_subsampling=encode_subsampling,
+                                   depth_pack=depth_pack,
                                    **(dict(pointcloud_names=pointcloud_names, max_points=max_points, pcd_ignore_mask=pcd_ignore_mask)
                                       if device_clouds else {}))
         train_loader = store.loader(train_episode_ids, train_episode_len, chunk_size,

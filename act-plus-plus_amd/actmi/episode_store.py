@@ -87,13 +87,17 @@ _FrameKind = namedtuple("_FrameKind", "key segment is_depth px_bytes torch_dtype
 _KINDS = (_FrameKind("images", "frames", False, 3, torch.uint8, 16, "bgr"),
           _FrameKind("depth_images", "depth", True, 2, torch.uint16, 8, "u16"))
 
+# ``tab["mode"]`` of a frame a compressed store keeps as packed depth (actmi_op_depth_pack), beside the JPEG sampling modes and -1
+DEPTH_PACK_MODE = 100
+
 # What the plan needs of one source file, from its headers: ``T``; ``compressed``; ``cloud_rows``, N of its stored cloud [T, N, 3] (0:
 # the store holds no clouds) and ``cloud_rgb_dtype``; ``frames``, per kind (``_KINDS``) the (shape, dtype) of a frame, None where the
 # file did not size it
 # ``packed`` (``store_compressed`` and a compressed source; else None): per kind None or (L per camera, marks per frame), L the padded
 # file length of a frame, what the entry's header gives
 # ``encoded`` (``store_encode`` and a raw source, after the store's encode stage; else None): per kind None or (the exact stream bytes
-# of every camera's block, marks per frame)
+# of every camera's block, marks per frame); with ``depth_pack`` the depth kind's entry is (the exact bytes of every depth camera's
+# packed streams, 0): a stream block of exactly those bytes and an empty mark block
 SourceHeader = namedtuple("SourceHeader", "T compressed cloud_rows cloud_rgb_dtype frames packed encoded",
                           defaults=(0, None, (None, None), None, None))
 
@@ -112,15 +116,18 @@ def _checked_frame_shape(kind, path, key, dtype, fshape):
     return tuple(fshape[:2])
 
 
-def probe_sources(sources, cams, cloud_base=None, max_points=None, store_compressed=False, rows_per_mark=1, store_encode=False):
+def probe_sources(sources, cams, cloud_base=None, max_points=None, store_compressed=False, rows_per_mark=1, store_encode=False,
+                  depth_pack=False):
     """Opens every source file once -> [SourceHeader].  `cams`: per kind the camera names; `cloud_base`: the stored cloud's group, None
     without clouds.  The sizes come from the entries' headers (the first file's decoded frames for a compressed dataset: later
     compressed files are checked as they are decoded).  Refused here, before anything large is allocated, each ``ValueError`` naming
     the file: an empty episode, clouds that are not two [T, N, 3] arrays of T steps or store more than `max_points` rows
     (``_read_cloud``'s checks, from the headers), frames that are not T, depth that is not an unsigned integer of at most 16 bits, and
     cameras or files whose frame sizes differ -- checked as the walk reaches the file, so the first bad file is the one named;
-    with ``store_encode`` a raw source's depth entry (an 8-bit JPEG cannot hold raw uint16 depth)."""
-    headers, sized, marks_of = [], {}, {}
+    with ``store_encode`` a raw source's depth entry (an 8-bit JPEG cannot hold raw uint16 depth) -- unless ``depth_pack`` admits it:
+    the store then packs it losslessly (``DEPTH_PACK_MODE``), and refuses a dataset that holds JPEG-compressed depth beside raw
+    depth, since one depth kind has one decode path."""
+    headers, sized, marks_of, depth_codec = [], {}, {}, {}
     for i, path in enumerate(sources):
         with open_episode(path) as root:
             compressed = bool(root.attrs.get("compress", False))
@@ -148,6 +155,12 @@ def probe_sources(sources, cams, cloud_base=None, max_points=None, store_compres
                     shape, dtype = _entry_meta(root, key)
                     if shape[0] != T:
                         raise ValueError(f"{path}: {key} holds {shape[0]} frames for an episode of {T} steps")
+                    if depth_pack and kind.is_depth:
+                        depth_codec.setdefault("JPEG-compressed" if compressed else "raw", path)
+                        if len(depth_codec) > 1:
+                            raise ValueError(f"{path}: {key} is {'JPEG-compressed' if compressed else 'raw'} depth and "
+                                             f"{depth_codec['raw' if compressed else 'JPEG-compressed']} holds "
+                                             f"{'raw' if compressed else 'JPEG-compressed'} depth: depth_pack keeps one depth codec per store")
                     if compressed:
                         lens.append(int(shape[1]) if len(shape) == 2 else 0)
                         if i > 0 and kind.key in sized and store_compressed and kind.key not in marks_of:
@@ -160,7 +173,7 @@ def probe_sources(sources, cams, cloud_base=None, max_points=None, store_compres
                         if store_compressed and kind.key not in marks_of:
                             marks_of[kind.key] = _marks_per_frame(first, fshape[0], rows_per_mark)
                     else:
-                        if store_encode and kind.is_depth:
+                        if store_encode and kind.is_depth and not depth_pack:
                             raise ValueError(f"{path}: {key} is raw depth, which an 8-bit JPEG cannot hold: store_encode takes raw "
                                              "camera frames only (train this dataset without --store_encode)")
                         fshape = shape[1:]
@@ -363,6 +376,10 @@ class DeviceEpisodeStore:
     as it is read (``_encode_sources``: B, G, R pixels at ``encode_quality`` / ``encode_subsampling``, as ``compress_episode`` encodes
     them), its marks written by the encoder (actmi_op_jpeg_encode_marked) -- no index launch; raw and compressed sources may be mixed,
     and the batches are those of a compressed store of ``compress_dataset_dir``'s output.  ``encode_stats``: the frames encoded.
+    ``depth_pack`` (with ``store_encode`` and ``use_depth``): the raw uint16 depth entries of raw sources, which ``store_encode`` alone
+    refuses, are packed losslessly on the device as they are read (``_pack_depth_sources``, actmi_op_depth_pack) and every batch's
+    depth is unpacked straight into its tensor by one actmi_op_depth_unpack launch, a twin's flip being the record's flag; the
+    depth tensors are bit for bit those of the decoded store.  ``depth_pack_stats``: frames, raw bytes and stream bytes.
 
     Every rank of a data-parallel run holds its own full store."""
 
@@ -371,8 +388,14 @@ class DeviceEpisodeStore:
     def __init__(self, dataset_path_list, episode_ids, camera_names, norm_stats, device, depth_camera_names=None, use_depth=False,
                  budget_bytes=None, use_pcd=False, policy_class="ACT", stage_bytes=64 << 20, pointcloud_names=None, max_points=None,
                  pcd_ignore_mask=False, device_decode=False, decode_frames=256, store_compressed=False, rows_per_mark=1,
-                 store_encode=False, encode_quality=50, encode_subsampling="420"):
+                 store_encode=False, encode_quality=50, encode_subsampling="420", depth_pack=False):
         self.device_decode, self.decode_frames = bool(device_decode), int(decode_frames)
+        self.depth_pack = bool(depth_pack)
+        if self.depth_pack and not store_encode:
+            raise ValueError("depth_pack packs the raw depth of episodes the store encodes as it loads them: it needs store_encode "
+                             "(and store_compressed, device_decode, device_dataset)")
+        if self.depth_pack and not use_depth:
+            raise ValueError("depth_pack packs depth frames: it needs use_depth")
         self.store_compressed, self.rows_per_mark = bool(store_compressed), int(rows_per_mark)
         self.store_encode, self.encode_quality, self.encode_subsampling = bool(store_encode), encode_quality, str(encode_subsampling)
         if self.store_encode and not self.store_compressed:
@@ -431,7 +454,7 @@ class DeviceEpisodeStore:
         cams = (tuple(self.camera_names), tuple(self.depth_camera_names) if self.use_depth else ())
         self._cloud_base = f"/observations/pointcloud/{self.pointcloud_names[0]}" if self.has_clouds else None
         headers = probe_sources(self.sources, cams, self._cloud_base, self.max_points, self.store_compressed, self.rows_per_mark,
-                                self.store_encode)
+                                self.store_encode, self.depth_pack)
         if budget_bytes is None:
             free, _total = torch.cuda.mem_get_info(torch.device(device))
             budget_bytes = free - DEVICE_STORE_RESERVE_BYTES
@@ -439,8 +462,11 @@ class DeviceEpisodeStore:
         self.bus_bytes = 0                                            # bytes of frames and clouds that crossed to the device
         self._pin, self._pin_ev, self._pin_i = None, [None, None], 0
         self.encode_stats, self._held, self._held_bytes, self._encode_staging = {"device": 0}, {}, 0, 0
+        self.depth_pack_stats, self._held_depth = {"frames": 0, "raw_bytes": 0, "stream_bytes": 0}, {}
         if self.store_encode:
             headers = self._encode_sources(headers, cams)
+        if self.depth_pack:
+            headers = self._pack_depth_sources(headers, cams)
         if self.store_compressed and not all((h.packed is not None and all(p is not None for p, c in zip(h.packed, cams) if c)) or
                                              h.encoded is not None for h in headers):
             raise NotImplementedError("store_compressed: every source must be a compressed episode (a store of compressed and raw "
@@ -459,7 +485,7 @@ class DeviceEpisodeStore:
         # the stage's device staging counts as well (it is released before the arena is allocated: the check is the safe side)
         need = self.nbytes + self._held_bytes + self._encode_staging
         if need > self.budget_bytes:
-            self._held = {}
+            self._held, self._held_depth = {}, {}
             raise MemoryError(f"DeviceEpisodeStore: {len(self.paths)} episodes need {need} bytes on the device "
                               f"({need / 2**30:.2f} GiB), the budget is {self.budget_bytes} bytes "
                               f"({self.budget_bytes / 2**30:.2f} GiB): train without --device_dataset, or raise --device_dataset_gb")
@@ -539,6 +565,8 @@ class DeviceEpisodeStore:
                 key = f"/observations/{kind.key}/{cam}"
                 if (j, k) in self._held and not kind.is_depth:
                     self._load_encoded(kind, T, j, k)                 # read and encoded before the plan: not read again
+                elif (j, k) in self._held_depth and kind.is_depth:
+                    self._load_packed_depth(kind, T, j, k)            # read and packed before the plan
                 elif self.store_compressed:
                     self._load_packed(root[key], kind, T, j, k, f"{path}: {key}")
                 else:
@@ -713,7 +741,7 @@ class DeviceEpisodeStore:
         its mark 0 among the arena's 32-byte words, its sampling mode (-1: a spill frame) and its row in the spill tensor"""
         from . import ops
         self._ptab, self._spill_host, self._spill, self._index_pending = [], [], [], []
-        self.stream_bytes_used, self._sticky, self._scratch = 0, None, {}
+        self.stream_bytes_used, self._sticky, self._scratch, self._depth_sticky = 0, None, {}, None
         if not self.store_compressed:
             return
         lay = self.layout
@@ -904,6 +932,101 @@ class DeviceEpisodeStore:
         tab["mode"][rows] = ops.JPEG_MODES[self.encode_subsampling]
         self.stream_bytes_used += cap
 
+    # ---- raw depth packed at load (depth_pack) ---------------------------------------------------------------------------
+    def _pack_depth_sources(self, headers, cams):
+        """The pack stage, beside ``_encode_sources`` and like it ahead of ``plan_store``.  Every depth entry of a raw source is read
+        ONCE, at most ``decode_frames`` frames a piece, converted as ``_stage_frames`` converts depth (an unsigned integer of at most
+        16 bits as uint16, channel 0 of 3-D frames) and staged through the pinned pair into a device buffer.  Per piece: one
+        actmi_op_depth_pack launch with empty windows gives every frame's true length, the lengths are read back once, and one launch
+        with exact windows writes the streams back to back into a tensor of their size, held until ``_load_packed_depth`` copies it
+        into the arena.  -> the headers, a raw source's ``encoded[1]``: (the exact stream bytes per depth camera, 0 marks)."""
+        from . import ops
+        dev = torch.device(self.device)
+        names, kind = cams[1], _KINDS[1]
+        todo = [j for j, h in enumerate(headers) if not h.compressed and h.frames[1] is not None]
+        if not todo or not names:
+            return headers
+        H, W = headers[todo[0]].frames[1][0]
+        fb = 2 * H * W
+        per = min(self.decode_frames, max(headers[j].T for j in todo))
+        staging = per * fb + max(4, ops.depth_pack_workspace_bytes(per, H))
+        self._encode_staging = max(self._encode_staging, staging)     # the camera stage's buffers are released by now
+        if staging > self.budget_bytes:
+            raise MemoryError(f"DeviceEpisodeStore: the pack stage of depth_pack needs {staging} bytes on the device "
+                              f"({staging / 2**30:.2f} GiB) for {per} frames a launch, the budget is {self.budget_bytes} bytes "
+                              f"({self.budget_bytes / 2**30:.2f} GiB): lower decode_frames, or raise --device_dataset_gb")
+        packer = ops.DepthPacker(dev, H, W, max_frames=per)
+        raw = torch.empty(per * fb, dtype=torch.uint8, device=dev)
+        self._open_staging(max(self.stage_bytes, fb))
+        step = max(1, self._pin[0].numel() // fb)
+        out = list(headers)
+        for j in todo:
+            T, nbytes, checks = headers[j].T, [], []
+            with open_episode(self.sources[j]) as raw_root:
+                root = _EpisodeArrays(raw_root)
+                for k, cam in enumerate(names):
+                    key = f"/observations/{kind.key}/{cam}"
+                    entry, where = root[key], f"{self.sources[j]}: {key}"
+                    streams, lens = [], []
+                    for t0 in range(0, T, per):
+                        n = min(per, T - t0)
+                        piece = np.asarray(entry[t0:t0 + n])
+                        if piece.dtype.kind != "u" or piece.dtype.itemsize > 2:
+                            raise ValueError(f"{where} is {piece.dtype}: not raw depth (an unsigned integer of at most 16 bits)")
+                        if piece.ndim == 4:
+                            piece = piece[..., 0]                     # _depth_data: a 3-D frame keeps channel 0
+                        piece = piece.astype(np.uint16, copy=False)
+                        if piece.shape != (n, H, W):
+                            raise ValueError(f"{where}: frames {piece.dtype} {piece.shape[1:]}, the store was sized for {(H, W)}")
+                        for i0 in range(0, n, step):
+                            flat = np.ascontiguousarray(piece[i0:i0 + step]).reshape(-1).view(np.uint8)
+                            self._stage(i0 * fb, flat.size, lambda view, flat=flat: np.copyto(view, flat), raw)
+                        ln = packer.sizes(raw[:n * fb], n)            # the one read-back of the piece
+                        rec = ops.depth_pack_records(n, H, W, 0, dst_off=_starts(ln))
+                        rec["dst_cap"] = ln
+                        stream = torch.empty(int(ln.sum()), dtype=torch.uint8, device=dev)
+                        seg_len2, status = packer.pack(raw[:n * fb], rec, stream)
+                        checks.append((torch.stack([seg_len2, status]), ln, f"{where} from step {t0}"))
+                        streams.append(stream)
+                        lens.append(ln)
+                        self._held_bytes += int(stream.numel())
+                        self.depth_pack_stats["frames"] += n
+                        self.depth_pack_stats["raw_bytes"] += n * fb
+                        self.depth_pack_stats["stream_bytes"] += int(ln.sum())
+                    self._held_depth[(j, k)] = (streams, np.concatenate(lens))
+                    nbytes.append(int(sum(int(l.sum()) for l in lens)))
+            for meta, ln, where in checks:                            # read back once per source
+                meta = meta.cpu().numpy()
+                if meta[1].any() or not np.array_equal(meta[0], ln):
+                    raise RuntimeError(f"{where}: the depth pack gave status {meta[1].tolist()} and lengths {meta[0].tolist()} in windows "
+                                       f"of the lengths {ln.tolist()} the first launch gave")
+            cam_part = out[j].encoded[0] if out[j].encoded is not None else None
+            out[j] = out[j]._replace(encoded=(cam_part, (tuple(nbytes), 0)))
+        torch.cuda.synchronize(dev)
+        return out
+
+    def _load_packed_depth(self, kind, T, j, k):
+        """one depth camera's block of a packed source: the held streams copied into its stream block, device to device, its rows of
+        the frame table filled (``DEPTH_PACK_MODE``: ``_packed_segments`` gives these rows to the depth unpack); the held tensors
+        are released"""
+        q = self.layout.all_kinds.index(kind)
+        tab = self._ptab[q]
+        streams, lens = self._held_depth.pop((j, k))
+        row0 = int(self._frame_row(q, j, k))
+        s0, cap = int(kind.src_block_off[j, k]), int(kind.stream_cap[j, k])
+        if len(lens) != T or int(lens.sum()) != cap:
+            raise RuntimeError(f"{self.sources[j]}: the packed block of depth camera {k} does not fit the plan")
+        o = s0
+        for stream in streams:
+            self.arena[o:o + stream.numel()].copy_(stream)
+            self._held_bytes -= int(stream.numel())
+            o += int(stream.numel())
+        rows = row0 + np.arange(T, dtype=np.int64)
+        tab["rec"]["seg_len"][rows], tab["rec"]["seg_off"][rows] = lens, s0 + _starts(lens)
+        tab["mode"][rows] = DEPTH_PACK_MODE
+        self.stream_bytes_used += cap
+        self.decode_stats["device"] += T
+
     def _spill_frame(self, q, row, buf, kind, where):
         """a frame the device does not take: decoded by ``imdecode_bgr`` (a bad file raises what it raises today), kept raw"""
         piece = imdecode_bgr(buf)[None]
@@ -943,6 +1066,7 @@ class DeviceEpisodeStore:
             self._spill.append(torch.from_numpy(flat).to(dev))
         self._spill_host = None
         self._sticky = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._depth_sticky = torch.zeros(1, dtype=torch.int32, device=dev) if self.depth_pack else None
         for dec in self._decoders.values():
             need = max(dec.workspace_bytes(m) for m in ops.JPEG_MODES)
             dec._ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -953,13 +1077,18 @@ class DeviceEpisodeStore:
 
     def check_decoded(self):
         """reads the sticky status word of every batch decoded so far (one small copy; call it where the step synchronises anyway):
-        ``RuntimeError`` naming the status if a marked decode flagged a frame"""
+        ``RuntimeError`` naming the status if a marked decode flagged a frame (``ops.JPEG_STATUS``), or -- the sticky word of the
+        packed depth, read beside it -- if a depth unpack flagged a row (``ops.DEPTH_PACK_STATUS``)"""
         if self._sticky is None:
             return
         from . import ops
         v = int(self._sticky.item())
         if v:
             raise RuntimeError(f"DeviceEpisodeStore: a batch of the compressed store was decoded with status {v} ({ops.JPEG_STATUS.get(v, '?')})")
+        v = int(self._depth_sticky.item()) if self._depth_sticky is not None else 0
+        if v:
+            raise RuntimeError(f"DeviceEpisodeStore: the packed depth of a batch was unpacked with status {v} "
+                               f"({ops.DEPTH_PACK_STATUS.get(v, '?')})")
 
     def _packed_segments(self, e, t):
         """the JPEG side of a batch's index table: per kind and sampling mode present the records (dst_off = item * frame bytes) and
@@ -981,12 +1110,20 @@ class DeviceEpisodeStore:
             launches = []
             for m in np.unique(mode[mode >= 0]):
                 items = np.nonzero(mode == m)[0]
+                if m == DEPTH_PACK_MODE:                              # packed depth: the unpack's records, a twin's flip as their flag
+                    rec = np.zeros(len(items), dtype=ops.depth_unpack_frame_dtype())
+                    src = tab["rec"][rows[items]]
+                    rec["seg_off"], rec["seg_len"], rec["dst_off"] = src["seg_off"], src["seg_len"], items * kind.frame_bytes
+                    rec["flags"] = kind.flip[e].reshape(-1)[items].astype(np.int32) * ops.DEPTH_FLIP
+                    seg[f"dpack{q}"] = rec
+                    launches.append((None, f"dpack{q}", None))
+                    continue
                 rec = tab["rec"][rows[items]]
                 rec["dst_off"] = items * kind.frame_bytes
                 seg[f"jpeg{q}_{m}"], seg[f"first{q}_{m}"] = rec, tab["first"][rows[items]]
                 launches.append((modes[int(m)], f"jpeg{q}_{m}", f"first{q}_{m}"))
             sp = np.nonzero(mode < 0)[0]
-            if self.has_twins:
+            if self.has_twins and not (len(mode) and (mode == DEPTH_PACK_MODE).all()):
                 seg[f"scratch{q}"] = np.arange(len(rows), dtype=np.int64) * kind.frame_bytes
             plan.append((launches, (sp, tab["spill"][rows[sp]]) if len(sp) else None))
         return seg, plan
@@ -999,13 +1136,18 @@ class DeviceEpisodeStore:
         K, fb = len(kind.cams), kind.frame_bytes
         out = torch.empty((B, K) + ((1,) if kind.is_depth else ()) + kind.shape, dtype=kind.torch_dtype, device=dev)
         target = out
+        launches, spill = plan
+        if len(launches) == 1 and launches[0][0] is None and spill is None:
+            # packed depth: ONE unpack launch straight into the batch tensor, mirrored rows by the records' flag -- no scratch block
+            ops.depth_unpack_raw(self.arena, seg[launches[0][1]].view(torch.uint8), out.view(torch.uint8).reshape(-1), kind.shape[0],
+                                 kind.shape[1], sticky=self._depth_sticky)
+            return out
         if self.has_twins:
             if q not in self._scratch or self._scratch[q].numel() < B * K * fb:
                 self._scratch[q] = torch.empty(B * K * fb, dtype=torch.uint8, device=dev)
             target = self._scratch[q][:B * K * fb]
         H, W = kind.shape[:2]
         dec = self._decoders[(H, W)]
-        launches, spill = plan
         marks = self.arena[:self.nbytes // 32 * 32]
         for mode, rec, first in launches:
             dec.decode_marked(self.arena, seg[rec].view(torch.uint8), marks, seg[first], mode, kind.decode_as, target, sticky=self._sticky,
@@ -1024,7 +1166,7 @@ class DeviceEpisodeStore:
         """bytes of device memory the store holds"""
         packed = 0
         if self.store_compressed:
-            packed = sum(int(s.numel()) for s in self._spill) + 4 + sum(int(s.numel()) for s in self._scratch.values()) + \
+            packed = sum(int(s.numel()) for s in self._spill) + 4 + (4 if self._depth_sticky is not None else 0) + sum(int(s.numel()) for s in self._scratch.values()) + \
                 sum(int(d._ws.numel()) + (int(d._tables.numel()) if d._tables is not None else 0) for d in self._decoders.values())
         return int(self.arena.numel() + self.actions.numel() * 4 + self.qpos.numel() * 4 + self.episodes.numel() +
                    sum(s.numel() * 4 for s in self._stats)) + packed

@@ -187,6 +187,19 @@ class JpegEncDesc(C.Structure):
                [(k, C.c_int32) for k in ("n", "H", "W", "mode", "form")]
 
 
+class DepthPackDesc(C.Structure):
+    # actmi_depth_pack_desc
+    _fields_ = [("src", C.c_void_p), ("src_bytes", C.c_int64), ("frames", C.c_void_p), ("dst", C.c_void_p), ("dst_bytes", C.c_int64),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("seg_len", C.c_void_p), ("status", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("n", "H", "W", "reserved")]
+
+
+class DepthUnpackDesc(C.Structure):
+    # actmi_depth_unpack_desc
+    _fields_ = [("stream", C.c_void_p), ("stream_bytes", C.c_int64), ("frames", C.c_void_p), ("dst", C.c_void_p), ("dst_bytes", C.c_int64),
+                ("status", C.c_void_p), ("sticky", C.c_void_p)] + [(k, C.c_int32) for k in ("n", "H", "W", "reserved")]
+
+
 class JpegMarks(C.Structure):
     # actmi_jpeg_marks
     _fields_ = [("marks", C.c_void_p), ("n_marks", C.c_int64), ("first", C.c_void_p), ("sticky", C.c_void_p), ("rows_per_mark", C.c_int32),
@@ -324,6 +337,12 @@ def load():
         "actmi_jpeg_encode_host": ([C.POINTER(JpegEncDesc)], i32),
         "actmi_op_jpeg_encode_marked": ([C.POINTER(JpegEncDesc), C.POINTER(JpegMarks), vp], i32),
         "actmi_jpeg_encode_marked_host": ([C.POINTER(JpegEncDesc), C.POINTER(JpegMarks)], i32),
+        "actmi_depth_pack_bound": ([i32, i32], i64),
+        "actmi_op_depth_pack_workspace_bytes": ([i64, i32], i64),
+        "actmi_op_depth_pack": ([C.POINTER(DepthPackDesc), vp], i32),
+        "actmi_depth_pack_host": ([C.POINTER(DepthPackDesc)], i32),
+        "actmi_op_depth_unpack": ([C.POINTER(DepthUnpackDesc), vp], i32),
+        "actmi_depth_unpack_host": ([C.POINTER(DepthUnpackDesc)], i32),
         "actmi_op_sum_batch": ([vp, C.c_int64, C.c_int64, vp, i32, i32, i32, i32, vp], i32),
         "actmi_op_adamw": ([vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp], i32),
         "actmi_op_u8_to_nhwc4": ([vp, vp, i32, i32, i32, i32, vp], i32),

@@ -3957,3 +3957,363 @@ def jpeg_encode(frames, quality=50, mode="420", form="bgr", device=None, encoder
     if encoder.device is None:                                    # the host twin
         return encoder.files(t, form)
     return encoder.files(t.to(encoder.device).contiguous(), form)
+
+
+# ---- packed depth: lossless uint16 frames (actmi_op_depth_pack / actmi_op_depth_unpack; the format is defined in actmi.h) ------------
+DEPTH_PACK_STATUS = {0: "ok", 1: "row table out of order, unaligned or outside the stream", 2: "invalid group header or mask byte",
+                     3: "row length differs from what its headers imply", 4: "destination extent leaves the buffer"}
+DEPTH_FLIP = 1
+
+
+def depth_pack_bound(H, W):
+    """actmi_depth_pack_bound in numpy's terms: bytes no stream of an H x W frame exceeds"""
+    H, W = int(H), int(W)
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError("depth_pack: H and W must be in 1..65535")
+    return 4 * (H + 1) + H * (2 * ((W + 7) // 8) + 2 * W + 3)
+
+
+def _depth_frame(frame):
+    import numpy as np
+    f = np.asarray(frame)
+    if f.dtype != np.uint16 or f.ndim != 2 or 0 in f.shape:
+        raise ValueError(f"depth_pack: a frame is uint16 [H, W], got {f.dtype} {f.shape}")
+    return f
+
+
+def depth_pack_row_ref(row):
+    """one row of ``depth_pack_ref``: headers, mask bytes, payloads, zero bytes up to a multiple of 4"""
+    import numpy as np
+    x = np.asarray(row, dtype=np.int64)
+    W = len(x)
+    valid = x != 0
+    xv = x[valid]
+    d = (xv - np.concatenate([[0], xv[:-1]])) & 0xFFFF             # the chain over the row's valid pixels, prev starts at 0
+    d = np.where(d >= 0x8000, d - 0x10000, d)                      # int16
+    zv = ((d << 1) ^ (d >> 15)) & 0xFFFF
+    z = np.zeros(W, dtype=np.int64)
+    z[valid] = zv
+    heads, masks, pays = bytearray(), bytearray(), bytearray()
+    for g0 in range(0, W, 8):
+        v, zz = valid[g0:g0 + 8], z[g0:g0 + 8]
+        zs = [int(t) for t in zz[v]]
+        w = max(zs).bit_length() if zs else 0
+        flagged = not v.all()
+        heads.append(w | (0x80 if flagged else 0))
+        if flagged:
+            masks.append(sum(1 << i for i in range(len(v)) if v[i]))
+        acc = 0
+        for j, t in enumerate(zs):
+            acc |= t << (j * w)
+        pays += acc.to_bytes((len(zs) * w + 7) // 8, "little")
+    out = bytes(heads) + bytes(masks) + bytes(pays)
+    return out + b"\0" * (-len(out) % 4)
+
+
+def depth_pack_ref(frame):
+    """The packed-depth stream of one uint16 [H, W] frame, stated in numpy: the definition actmi_op_depth_pack and
+    actmi_depth_pack_host are compared with byte for byte."""
+    import numpy as np
+    f = _depth_frame(frame)
+    H = f.shape[0]
+    rows = [depth_pack_row_ref(f[r]) for r in range(H)]
+    off = np.cumsum([4 * (H + 1)] + [len(r) for r in rows]).astype("<u4")
+    return off.tobytes() + b"".join(rows)
+
+
+def depth_unpack_ref(buf, H, W, flip=False):
+    """``depth_pack_ref`` undone, with actmi_op_depth_unpack's checks -> (frame uint16 [H, W], status).  A row that fails a check is
+    zeros; the status is the smallest nonzero one of the rows' (``DEPTH_PACK_STATUS``).  ``flip``: every row mirrored."""
+    import numpy as np
+    H, W = int(H), int(W)
+    s = bytes(buf)
+    L_, ng, table = len(s), (W + 7) // 8, 4 * (H + 1)
+    out = np.zeros((H, W), dtype=np.uint16)
+    if L_ < table + 4 or L_ > 0x7FFFFFFF:
+        return out, 1
+    off = np.frombuffer(s, dtype="<u4", count=H + 1).astype(np.int64)
+    if off[H] != L_:
+        return out, 1
+    codes = set()
+    for r in range(H):
+        a, b = int(off[r]), int(off[r + 1])
+        if a % 4 or b % 4 or a < table or not a < b or b > L_:
+            codes.add(1)
+            continue
+        at = lambda i: s[min(max(i, 0), L_ - 1)]                  # the kernels' clamped read  # noqa: E731
+        heads = [at(a + g) for g in range(ng)]
+        ns = [min(8, W - 8 * g) for g in range(ng)]
+        bad = any((h & 0x60) or (h & 0x1F) > 16 for h in heads)
+        masks, mpos = [], a + ng
+        for g, h in enumerate(heads):
+            if h & 0x80:
+                masks.append(at(mpos))
+                bad = bad or masks[-1] >> ns[g] != 0
+                mpos += 1
+            else:
+                masks.append((1 << ns[g]) - 1)
+        if bad:
+            codes.add(2)
+            continue
+        pbs = [(bin(m).count("1") * (h & 0x1F) + 7) // 8 for m, h in zip(masks, heads)]
+        if (ng + (mpos - a - ng) + sum(pbs) + 3) // 4 * 4 != b - a:
+            codes.add(3)
+            continue
+        prev, ppos = 0, mpos
+        for g, (h, m, pb) in enumerate(zip(heads, masks, pbs)):
+            w = h & 0x1F
+            acc = int.from_bytes(s[ppos:ppos + pb], "little")
+            ppos += pb
+            j = 0
+            for i in range(ns[g]):
+                if m >> i & 1:
+                    z = (acc >> (j * w)) & ((1 << w) - 1)
+                    prev = (prev + ((z >> 1) ^ -(z & 1))) & 0xFFFF
+                    out[r, 8 * g + i] = prev
+                    j += 1
+    return (out[:, ::-1].copy() if flip else out), min(codes, default=0)
+
+
+def depth_pack_frame_dtype():
+    """actmi_depth_pack_frame as a numpy structured dtype (32 bytes)"""
+    import numpy as np
+    return np.dtype([("src_off", np.int64), ("dst_off", np.int64), ("dst_cap", np.int32), ("reserved", np.int32, 3)])
+
+
+def depth_unpack_frame_dtype():
+    """actmi_depth_unpack_frame as a numpy structured dtype (32 bytes)"""
+    import numpy as np
+    return np.dtype([("seg_off", np.int64), ("dst_off", np.int64), ("seg_len", np.int32), ("flags", np.int32), ("reserved", np.int32, 2)])
+
+
+def depth_pack_workspace_bytes(n, H):
+    return int(L.load().actmi_op_depth_pack_workspace_bytes(int(n), int(H)))
+
+
+def depth_pack_records(n, H, W, cap, src_off=None, dst_off=None):
+    """the records of n frames laid back to back in `src`, every stream in a window of `cap` bytes (or at the offsets given)"""
+    import numpy as np
+    rec = np.zeros(int(n), dtype=depth_pack_frame_dtype())
+    rec["src_off"] = np.arange(n, dtype=np.int64) * (2 * int(H) * int(W)) if src_off is None else np.asarray(src_off, dtype=np.int64)
+    rec["dst_off"] = np.arange(n, dtype=np.int64) * int(cap) if dst_off is None else np.asarray(dst_off, dtype=np.int64)
+    rec["dst_cap"] = cap
+    return rec
+
+
+def depth_unpack_records(seg_off, seg_len, H, W, dst_off=None, flags=0):
+    """the records of the frames whose streams lie at `seg_off` / `seg_len`, decoded back to back into `dst` (or at the offsets given)"""
+    import numpy as np
+    n = len(seg_off)
+    rec = np.zeros(n, dtype=depth_unpack_frame_dtype())
+    rec["seg_off"], rec["seg_len"], rec["flags"] = seg_off, seg_len, flags
+    rec["dst_off"] = np.arange(n, dtype=np.int64) * (2 * int(H) * int(W)) if dst_off is None else np.asarray(dst_off, dtype=np.int64)
+    return rec
+
+
+def _depth_host_array(what, name, a):
+    import numpy as np
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
+        raise ValueError(f"{what}: {name} must be a contiguous 1-D uint8 array")
+    return a
+
+
+def depth_pack_host_raw(src, records, dst, H, W):
+    """actmi_depth_pack_host, the CPU twin of ``DepthPacker.pack`` (the same core, no device) on the caller's buffers: `src` (2-byte
+    aligned) and `dst` contiguous 1-D uint8 arrays, `records` ``depth_pack_frame_dtype`` -> (seg_len, status), int32 [n] each"""
+    import numpy as np
+    _depth_host_array("depth_pack_host", "src", src), _depth_host_array("depth_pack_host", "dst", dst)
+    rec = np.ascontiguousarray(records, dtype=depth_pack_frame_dtype())
+    n = len(rec)
+    seg_len, status = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+    d = L.DepthPackDesc()
+    one = np.zeros(1, dtype=np.uint8)                             # an empty array still has to name memory
+    d.src, d.src_bytes, d.frames = (src if src.size else one).ctypes.data, src.size, rec.ctypes.data
+    d.dst, d.dst_bytes = (dst if dst.size else one).ctypes.data, dst.size
+    d.seg_len, d.status, d.n, d.H, d.W = seg_len.ctypes.data, status.ctypes.data, n, int(H), int(W)
+    L.check(L.load().actmi_depth_pack_host(C.byref(d)), None, "depth_pack_host")
+    return seg_len, status
+
+
+def depth_unpack_host_raw(stream, records, dst, H, W, sticky=None):
+    """actmi_depth_unpack_host on the caller's buffers: `stream` and `dst` (2-byte aligned) contiguous 1-D uint8 arrays, `records`
+    ``depth_unpack_frame_dtype`` -> status int32 [n].  ``sticky``: an int32 [1] array that receives the largest status."""
+    import numpy as np
+    _depth_host_array("depth_unpack_host", "stream", stream), _depth_host_array("depth_unpack_host", "dst", dst)
+    rec = np.ascontiguousarray(records, dtype=depth_unpack_frame_dtype())
+    n = len(rec)
+    status = np.full(n, -1, dtype=np.int32)
+    d = L.DepthUnpackDesc()
+    one = np.zeros(2, dtype=np.uint8)
+    d.stream, d.stream_bytes, d.frames = (stream if stream.size else one).ctypes.data, stream.size, rec.ctypes.data
+    d.dst, d.dst_bytes = (dst if dst.size else one).ctypes.data, dst.size
+    d.status, d.sticky, d.n, d.H, d.W = status.ctypes.data, None if sticky is None else sticky.ctypes.data, n, int(H), int(W)
+    L.check(L.load().actmi_depth_unpack_host(C.byref(d)), None, "depth_unpack_host")
+    return status
+
+
+def _depth_frames(frames):
+    import numpy as np
+    f = np.ascontiguousarray(frames)
+    if f.ndim == 2:
+        f = f[None]
+    if f.dtype != np.uint16 or f.ndim != 3 or 0 in f.shape:
+        raise ValueError(f"depth_pack: frames are uint16 [n, H, W] (or one [H, W]), got {f.dtype} {f.shape}")
+    return f
+
+
+def depth_pack_host(frames):
+    """`frames` uint16 [n, H, W] (numpy) packed by the CPU twin -> one ``bytes`` per frame (``depth_pack_ref``'s bytes)"""
+    import numpy as np
+    f = _depth_frames(frames)
+    n, H, W = f.shape
+    cap = depth_pack_bound(H, W)
+    dst = np.empty(n * cap, dtype=np.uint8)
+    seg_len, status = depth_pack_host_raw(f.reshape(-1).view(np.uint8), depth_pack_records(n, H, W, cap), dst, H, W)
+    if status.any():
+        raise RuntimeError(f"depth_pack_host: status {status.tolist()} with windows of the bound's size")
+    return [dst[i * cap:i * cap + int(seg_len[i])].tobytes() for i in range(n)]
+
+
+def depth_unpack_host(bufs, H, W, flip=False):
+    """streams (one ``bytes`` per frame) decoded by the CPU twin -> (frames uint16 [n, H, W], status int32 [n])"""
+    import numpy as np
+    lens = np.array([len(b) for b in bufs], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]) if len(bufs) else lens
+    stream = np.frombuffer(b"".join(bytes(b) for b in bufs), dtype=np.uint8).copy()
+    out = np.full((len(bufs), int(H), int(W)), 0xABCD, dtype=np.uint16)
+    status = depth_unpack_host_raw(stream, depth_unpack_records(offs, lens, H, W, flags=DEPTH_FLIP if flip else 0),
+                                   out.reshape(-1).view(np.uint8), H, W)
+    return out, status
+
+
+def _depth_dev_tensor(what, name, t, device):
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous uint8 tensor on {device}")
+    return t
+
+
+def _records_to(rec, dtype, device):
+    import numpy as np
+    rec = np.ascontiguousarray(rec, dtype=dtype)
+    return len(rec), torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(device)
+
+
+class DepthPacker:
+    """The device state of ``depth_pack`` for frames of one size: the workspace of ``max_frames`` slots and the length and status
+    buffers of the last launch, as ``JpegEncoder`` holds them.  ``pack`` launches actmi_op_depth_pack for up to ``max_frames``
+    frames at a time on the current stream and reads nothing back; ``sizes`` is the launch with empty windows, read back."""
+
+    def __init__(self, device, H, W, max_frames=64):
+        self.device, self.H, self.W, self.max_frames = torch.device(device), int(H), int(W), int(max_frames)
+        if self.max_frames < 1 or self.max_frames > 65535:
+            raise ValueError("DepthPacker: max_frames must be in 1..65535")
+        self.bound = int(L.load().actmi_depth_pack_bound(self.H, self.W))
+        if self.bound < 0:
+            raise ValueError("DepthPacker: H and W must be in 1..65535 and the bound must fit int32")
+        self.frame_bytes = 2 * self.H * self.W
+        self._ws = torch.empty(max(4, depth_pack_workspace_bytes(self.max_frames, self.H)), dtype=torch.uint8, device=self.device)
+        self._one = torch.zeros(16, dtype=torch.uint8, device=self.device)   # what an empty dst names
+
+    def pack(self, src, records, dst):
+        """src: contiguous uint8 tensor on the device that holds the uint16 pixels; records: ``depth_pack_frame_dtype`` (numpy) that
+        place every frame in `src` and its window in `dst` -> (seg_len, status), int32 [n] on the device"""
+        _depth_dev_tensor("DepthPacker", "src", src, self.device), _depth_dev_tensor("DepthPacker", "dst", dst, self.device)
+        n, rec = _records_to(records, depth_pack_frame_dtype(), self.device)
+        seg_len = torch.empty(n, dtype=torch.int32, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if n == 0:
+            return seg_len, status
+        d = L.DepthPackDesc()
+        d.src, d.src_bytes = (src if src.numel() else self._one).data_ptr(), int(src.numel())
+        d.dst, d.dst_bytes = (dst if dst.numel() else self._one).data_ptr(), int(dst.numel())
+        d.ws, d.ws_bytes, d.H, d.W = self._ws.data_ptr(), int(self._ws.numel()), self.H, self.W
+        lib = L.load()
+        with torch.cuda.device(self.device):
+            for i0 in range(0, n, self.max_frames):
+                d.frames, d.seg_len, d.status = rec.data_ptr() + 32 * i0, seg_len.data_ptr() + 4 * i0, status.data_ptr() + 4 * i0
+                d.n = min(self.max_frames, n - i0)
+                L.check(lib.actmi_op_depth_pack(C.byref(d), L.current_stream_ptr()), None, "op_depth_pack")
+        return seg_len, status
+
+    def sizes(self, src, n=None, src_off=None):
+        """the true stream lengths of the frames in `src` (back to back, or at ``src_off``), by a launch with empty windows -> int64
+        numpy [n]; a frame whose pixels leave `src` raises"""
+        import numpy as np
+        if src_off is None:
+            n = src.numel() // self.frame_bytes if n is None else int(n)
+        else:
+            n = len(src_off)
+        rec = depth_pack_records(n, self.H, self.W, 0, src_off=src_off, dst_off=np.zeros(n, dtype=np.int64))
+        seg_len, _ = self.pack(src, rec, self._one[:0])
+        lens = seg_len.cpu().numpy().astype(np.int64)
+        if n and lens.min() <= 0:
+            raise RuntimeError("DepthPacker: a frame's pixels leave src")
+        return lens
+
+
+def depth_pack(frames, device=None, packer=None):
+    """actmi_op_depth_pack: `frames` uint16 [n, H, W] (numpy, or a tensor on any device) packed on the device -> one ``bytes`` per
+    frame (``depth_pack_ref``'s bytes): one launch with empty windows for the lengths, one with exact windows."""
+    import numpy as np
+    t = frames if torch.is_tensor(frames) else torch.from_numpy(_depth_frames(frames))
+    t = t if t.dim() == 3 else t[None]
+    if t.dtype != torch.uint16 or t.dim() != 3 or 0 in t.shape:
+        raise ValueError(f"depth_pack: frames are uint16 [n, H, W], got {t.dtype} {tuple(t.shape)}")
+    n, H, W = (int(v) for v in t.shape)
+    if packer is None:
+        if device is None:
+            device = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        packer = DepthPacker(device, H, W, max_frames=min(n, 256))
+    elif (packer.H, packer.W) != (H, W):
+        raise ValueError(f"depth_pack: the packer is for {packer.H} x {packer.W} frames")
+    src = t.to(packer.device).contiguous().view(torch.uint8).reshape(-1)
+    lens = packer.sizes(src, n)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    dst = torch.empty(int(lens.sum()), dtype=torch.uint8, device=packer.device)
+    rec = depth_pack_records(n, H, W, 0, dst_off=offs)
+    rec["dst_cap"] = lens
+    _, status = packer.pack(src, rec, dst)
+    if bool(status.any()):
+        raise RuntimeError(f"depth_pack: status {status.tolist()} with exact windows")
+    out = dst.cpu().numpy()
+    return [out[o:o + ln].tobytes() for o, ln in zip(offs, lens)]
+
+
+def depth_unpack_raw(stream, records, dst, H, W, sticky=None, status=None):
+    """actmi_op_depth_unpack on the caller's tensors: `stream` and `dst` contiguous uint8 tensors on one device, `records`
+    ``depth_unpack_frame_dtype`` (numpy), or a uint8 tensor of them already on the device -> status int32 [n] on the device.
+    ``sticky``: an int32 [1] tensor on the device that receives the largest status of the launch."""
+    dev = stream.device
+    _depth_dev_tensor("depth_unpack", "stream", stream, dev), _depth_dev_tensor("depth_unpack", "dst", dst, dev)
+    if torch.is_tensor(records):
+        _depth_dev_tensor("depth_unpack", "records", records, dev)
+        n, rec = records.numel() // 32, records
+    else:
+        n, rec = _records_to(records, depth_unpack_frame_dtype(), dev)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return status
+    if n > 65535:
+        raise ValueError("depth_unpack: at most 65535 frames a launch")
+    d = L.DepthUnpackDesc()
+    d.stream, d.stream_bytes, d.frames = stream.data_ptr(), int(stream.numel()), rec.data_ptr()
+    d.dst, d.dst_bytes, d.status = dst.data_ptr(), int(dst.numel()), status.data_ptr()
+    d.sticky, d.n, d.H, d.W = None if sticky is None else sticky.data_ptr(), n, int(H), int(W)
+    with torch.cuda.device(dev):
+        L.check(L.load().actmi_op_depth_unpack(C.byref(d), L.current_stream_ptr()), None, "op_depth_unpack")
+    return status
+
+
+def depth_unpack(bufs, H, W, flip=False, device=None):
+    """actmi_op_depth_unpack: streams (one ``bytes`` per frame) decoded on the device -> (frames uint16 [n, H, W] tensor on the
+    device, status int32 [n] numpy)"""
+    import numpy as np
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lens = np.array([len(b) for b in bufs], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]) if len(bufs) else lens
+    stream = torch.from_numpy(np.frombuffer(b"".join(bytes(b) for b in bufs) or b"\0", dtype=np.uint8).copy()).to(device)
+    out = torch.empty((len(bufs), int(H), int(W)), dtype=torch.uint16, device=device)
+    status = depth_unpack_raw(stream, depth_unpack_records(offs, lens, H, W, flags=DEPTH_FLIP if flip else 0),
+                              out.view(torch.uint8).reshape(-1), H, W)
+    return out, status.cpu().numpy()

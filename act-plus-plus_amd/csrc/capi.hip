@@ -665,6 +665,36 @@ int actmi_jpeg_encode_marked_host(const actmi_jpeg_enc_desc* d, const actmi_jpeg
     return jpeg_encode_marked_host(*d, *m, &g_op_error) == 0 ? ACTMI_OK : ACTMI_E_INVALID;
 }
 
+int64_t actmi_depth_pack_bound(int H, int W) { return depth_pack_bound(H, W); }
+
+int64_t actmi_op_depth_pack_workspace_bytes(int64_t n, int H) { return depth_pack_workspace_bytes(n, H); }
+
+int actmi_op_depth_pack(const actmi_depth_pack_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "depth_pack: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_depth_pack(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
+int actmi_depth_pack_host(const actmi_depth_pack_desc* d) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "depth_pack: null descriptor"; return ACTMI_E_INVALID; }
+    return depth_pack_host(*d, &g_op_error) == 0 ? ACTMI_OK : ACTMI_E_INVALID;
+}
+
+int actmi_op_depth_unpack(const actmi_depth_unpack_desc* d, void* stream) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "depth_unpack: null descriptor"; return ACTMI_E_INVALID; }
+    const int rc = launch_depth_unpack(*d, S(stream), &g_op_error);
+    return rc == 0 ? ACTMI_OK : (rc == -2 ? ACTMI_E_INVALID : ACTMI_E_LAUNCH);
+}
+
+int actmi_depth_unpack_host(const actmi_depth_unpack_desc* d) {
+    g_op_error.clear();
+    if (!d) { g_op_error = "depth_unpack: null descriptor"; return ACTMI_E_INVALID; }
+    return depth_unpack_host(*d, &g_op_error) == 0 ? ACTMI_OK : ACTMI_E_INVALID;
+}
+
 int actmi_op_depth_minmax_u16(const uint16_t* depth, float* lohi_out, int B, int64_t n_per_sample, void* stream) {
     g_op_error.clear();
     const int rc = launch_depth_minmax_u16(depth, lohi_out, B, n_per_sample, S(stream));

@@ -294,6 +294,14 @@ int jpeg_encode_host(const actmi_jpeg_enc_desc& d, std::string* err);   // the s
 int launch_jpeg_encode_marked(const actmi_jpeg_enc_desc& d, const actmi_jpeg_marks& mk, hipStream_t st, std::string* err);
 int jpeg_encode_marked_host(const actmi_jpeg_enc_desc& d, const actmi_jpeg_marks& mk, std::string* err);
 
+// ---- packed depth (depth_pack.hip, depth_pack_core.h; format and contracts at actmi_op_depth_pack in actmi.h) -----------------
+int64_t depth_pack_bound(int H, int W);
+int64_t depth_pack_workspace_bytes(int64_t n, int H);
+int launch_depth_pack(const actmi_depth_pack_desc& d, hipStream_t st, std::string* err);
+int launch_depth_unpack(const actmi_depth_unpack_desc& d, hipStream_t st, std::string* err);
+int depth_pack_host(const actmi_depth_pack_desc& d, std::string* err);      // the serial core on the CPU, host pointers
+int depth_unpack_host(const actmi_depth_unpack_desc& d, std::string* err);
+
 // ---- per-launch event profiler (prof.hip) ------------------------------------------------------------
 bool prof_enabled();
 void prof_begin(const char* name, double flops, double bytes, hipStream_t st);

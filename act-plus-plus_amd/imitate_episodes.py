@@ -971,6 +971,13 @@ def build_config(args):
         config["store_encode"] = True
         config["store_encode_quality"] = int(args.get("store_encode_quality") or 50)
         config["store_encode_subsampling"] = str(args.get("store_encode_subsampling") or "420")
+    if args.get("store_depth_pack"):
+        if not args.get("store_encode"):
+            raise ValueError("--store_depth_pack packs the raw depth of episodes the store encodes as it loads them: it needs "
+                             "--store_encode (and --store_compressed --device_dataset --device_decode)")
+        if not args.get("use_depth"):
+            raise ValueError("--store_depth_pack packs depth frames: it needs --use_depth")
+        config["store_depth_pack"] = True
     if args.get("device_clouds"):
         if not (args.get("device_dataset") and args.get("use_pcd")):
             raise ValueError("--device_clouds puts the stored clouds of a --use_pcd dataset into the device-resident store: it needs "
@@ -1053,6 +1060,7 @@ def _load_episode_data(args, config, task_config, dataset_dir, world, local_rank
                      device_clouds=bool(config.get("device_clouds")), device_decode=bool(config.get("device_decode")),
                      store_compressed=bool(config.get("store_compressed")), store_encode=bool(config.get("store_encode")),
                      encode_quality=config.get("store_encode_quality", 50), encode_subsampling=config.get("store_encode_subsampling", "420"),
+                     depth_pack=bool(config.get("store_depth_pack")),
                      cloud_mirror=tuple(config["cloud_mirror"]) if config.get("cloud_mirror") else None,
                      device=f"cuda:{local_rank}" if world > 1 else None,     # train_bc's device
                      device_budget_bytes=(int(config["device_dataset_gb"] * 2**30)
@@ -1253,6 +1261,10 @@ def make_parser():
     parser.add_argument("--store_encode_quality", action="store", type=int, default=50, help="--store_encode: JPEG quality, 1..100")
     parser.add_argument("--store_encode_subsampling", action="store", type=str, choices=("420", "444"), default="420",
                         help="--store_encode: chroma subsampling")
+    parser.add_argument("--store_depth_pack", action="store_true",
+                        help="--store_encode --use_depth, opt-in: the raw uint16 depth frames of raw episodes, which --store_encode "
+                             "alone refuses, are packed losslessly on the device as the store reads them (actmi_op_depth_pack) and "
+                             "unpacked for every batch (actmi_op_depth_unpack); the depth tensors are those of the decoded store")
     parser.add_argument("--cloud_mirror_axis", action="store", type=str, choices=("x", "y", "z"), default=None,
                         help="--mirror_twins --use_pcd: the twin's stored cloud is the source's reflected across a plane normal to "
                              "this axis of the clouds' frame; lifts the refusal of --mirror_twins with --use_pcd")

@@ -1339,6 +1339,102 @@ int actmi_jpeg_encode_host(const actmi_jpeg_enc_desc* d);
  * same core serially over host pointers. */
 int actmi_op_jpeg_encode_marked(const actmi_jpeg_enc_desc* d, const actmi_jpeg_marks* m, void* stream);
 int actmi_jpeg_encode_marked_host(const actmi_jpeg_enc_desc* d, const actmi_jpeg_marks* m);
+/* ---- packed depth (csrc/depth_pack.hip, csrc/depth_pack_core.h): lossless uint16 frames, enterable at any frame and any row ----
+ * A fixed-width delta packing with a validity mask; no entropy chain.  actmi.ops.depth_pack_ref / depth_unpack_ref state it in
+ * numpy.  A frame is H x W uint16, H and W in 1..65535.  Its stream is:
+ *  1. (H + 1) little-endian u32 row_off[r], byte offsets from the start of the frame's stream: row_off[0] = 4 (H + 1), row_off[H]
+ *     the stream's length, every row at a multiple of 4.
+ *  2. Row r, cut into ng = ceil(W / 8) groups of 8 pixels (the last holds n = W - 8 (ng - 1)), stores in this order: ng HEADER
+ *     bytes (bits 0-4 the width w in 0..16, bit 7 set when the group has a mask byte, bits 5-6 zero); the MASK bytes of the
+ *     flagged groups in group order (bit i set: pixel i of the group is valid, i.e. nonzero; a group without a mask byte has
+ *     every pixel valid; bits at or above n are 0); the PAYLOADS in group order (for the k valid pixels of a group k residuals of
+ *     w bits each, residual j at bit j w, least significant bit first, padded to ceil(k w / 8) bytes, at most 16); zero bytes up
+ *     to a multiple of 4.
+ *  3. The residual chain runs over the valid pixels of the whole row: prev starts at 0; d = int16(x - prev) taken mod 2^16;
+ *     z = ((d << 1) ^ (d >> 15)) & 0xFFFF; prev = x.  w is the bit length of the group's largest z (0 for a group without valid
+ *     pixels or with every z = 0).  An invalid pixel is 0 and leaves prev alone.
+ *  4. The encoder is canonical (the smallest w; a mask byte only where some pixel of the group is 0), so the bytes are a
+ *     function of the frame alone.
+ *  5. actmi_depth_pack_bound(H, W) = 4 (H + 1) + H (2 ng + 2 W + 3): no stream is longer (-1 for H or W outside 1..65535 or a
+ *     bound above int32).
+ *
+ * actmi_op_depth_pack packs n frames of ONE size in three passes: sizes (one wave per row, a lane per pixel: the group widths by
+ * an OR over 8 lanes, the row's bytes summed over its groups), offsets (one wave per frame: the scan of the H row sizes, row_off,
+ * seg_len and status), pack (one wave per row: every valid lane shifts its z to bit rank * w of a 128-bit value, the 8 lanes of a
+ * group OR it together and store the group's bytes; groups are byte-aligned, so no atomics).  Workspace: n slots of
+ * actmi_op_depth_pack_workspace_bytes(1, H) bytes, 4-byte aligned.
+ * Contract (that of actmi_op_jpeg_encode).  seg_len[i] is always the true length of frame i's stream (0 for a frame whose pixels
+ * leave `src`), so a launch with empty windows sizes the streams.  status[i] 0: the stream fit and dst[dst_off .. dst_off +
+ * seg_len) is exact.  ACTMI_DEPTH_ST_DEST: dst_cap is smaller than seg_len or negative, the window [dst_off, dst_off + dst_cap)
+ * leaves `dst`, or the frame's pixels [src_off, src_off + 2 H W) leave `src` or src_off is odd; nothing is written outside the
+ * window (nothing at all when it leaves `dst`) and the bytes in it are unspecified.  Nothing is read outside the frame's pixels,
+ * nothing read or written outside its workspace slot; every loop is bounded by H and W; two launches give the same bytes.
+ * ACTMI_E_INVALID before any launch: a null pointer, n outside [0, 65535], H or W outside [1, 65535], a bound above int32,
+ * negative sizes, misaligned records, src, seg_len, status or workspace, a workspace that cannot hold n slots.
+ *
+ * actmi_op_depth_unpack decodes n frames of one size straight into a uint16 destination, one wave per row: a lane per group
+ * reads the header, finds its mask byte by a scan of the flags and its payload by a scan of the payload sizes (64 groups an
+ * iteration); then a lane per pixel reads the three bytes that hold its residual, undoes the zigzag, and a wave inclusive sum
+ * with the row's carry restores the values; invalid pixels are 0.  flags bit 0: the row is written mirrored, pixel x at W - 1 - x.
+ * No workspace.  Status of a ROW (0 is OK):
+ *   ACTMI_DEPTH_ST_TABLE   the frame's segment leaves `stream`, seg_len < 4 (H + 1) + 4 or row_off[H] != seg_len (every row of the
+ *                          frame); or the row's entries row_off[r], row_off[r + 1] are not 4-aligned, not increasing or outside
+ *                          [4 (H + 1), seg_len]
+ *   ACTMI_DEPTH_ST_HEADER  a header of the row has w > 16 or bits 5-6 set, or a mask byte has bits at or above n
+ *   ACTMI_DEPTH_ST_LENGTH  the bytes the row's headers and masks imply, rounded up to 4, differ from row_off[r + 1] - row_off[r]
+ * A flagged row is written as zeros; the other rows still decode.  status[f] is the smallest nonzero status of the frame's rows (the
+ * checks in their order: table, headers, length), 0 when every row decoded, or ACTMI_DEPTH_ST_DEST when [dst_off, dst_off + 2 H W)
+ * leaves `dst` or dst_off is odd (nothing is written).  sticky, when not null, receives the largest row or frame status of the
+ * launch by a vector atomic (it is never reset by the library).
+ * Contract, for ANY stream bytes and ANY records: reads stay inside the frame's segment, writes inside its destination extent,
+ * every loop is bounded by H and W.  The host twins run the serial row encoder / decoder of the same core. */
+#define ACTMI_DEPTH_ST_OK 0
+#define ACTMI_DEPTH_ST_TABLE 1
+#define ACTMI_DEPTH_ST_HEADER 2
+#define ACTMI_DEPTH_ST_LENGTH 3
+#define ACTMI_DEPTH_ST_DEST 4
+#define ACTMI_DEPTH_FLIP 1
+typedef struct actmi_depth_pack_frame {   /* 32 bytes */
+    int64_t src_off;               /* of the frame's pixels in `src`, bytes, even */
+    int64_t dst_off;               /* of its stream in `dst` */
+    int32_t dst_cap;               /* bytes it may write there */
+    int32_t reserved[3];
+} actmi_depth_pack_frame;
+typedef struct actmi_depth_pack_desc {
+    const uint8_t* src;            /* 2-byte aligned */
+    int64_t src_bytes;
+    const actmi_depth_pack_frame* frames;   /* [n], 8-byte aligned */
+    uint8_t* dst;
+    int64_t dst_bytes;
+    void* ws;                      /* 4-byte aligned */
+    int64_t ws_bytes;
+    int32_t* seg_len;              /* [n] out */
+    int32_t* status;               /* [n] out */
+    int32_t n, H, W, reserved;
+} actmi_depth_pack_desc;
+typedef struct actmi_depth_unpack_frame { /* 32 bytes */
+    int64_t seg_off;               /* of the frame's stream in `stream` */
+    int64_t dst_off;               /* of its H x W uint16 pixels in `dst`, bytes, even */
+    int32_t seg_len;
+    int32_t flags;                 /* ACTMI_DEPTH_FLIP */
+    int32_t reserved[2];
+} actmi_depth_unpack_frame;
+typedef struct actmi_depth_unpack_desc {
+    const uint8_t* stream;
+    int64_t stream_bytes;
+    const actmi_depth_unpack_frame* frames;  /* [n], 8-byte aligned */
+    uint8_t* dst;                  /* 2-byte aligned */
+    int64_t dst_bytes;
+    int32_t* status;               /* [n] out */
+    int32_t* sticky;               /* null, or one word that receives the launch's maximum status */
+    int32_t n, H, W, reserved;
+} actmi_depth_unpack_desc;
+int64_t actmi_depth_pack_bound(int H, int W);
+int64_t actmi_op_depth_pack_workspace_bytes(int64_t n, int H);   /* -1 for a bad argument */
+int actmi_op_depth_pack(const actmi_depth_pack_desc* d, void* stream);
+int actmi_depth_pack_host(const actmi_depth_pack_desc* d);       /* ws is not used and may be null */
+int actmi_op_depth_unpack(const actmi_depth_unpack_desc* d, void* stream);
+int actmi_depth_unpack_host(const actmi_depth_unpack_desc* d);
 /* dst[r][d] (+)= sum_b src[b*batch_stride + r*ld + d] (gradient of a table added to every sample: nn.Embedding positions) */
 int actmi_op_sum_batch(const float* src, int64_t batch_stride, int64_t ld, float* dst, int B, int R, int D, int accumulate,
                        void* stream);
